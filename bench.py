@@ -24,6 +24,12 @@ oracle/, plus the oracle's scalar block encoder -- the reference has no RGBA sta
 configs), "c1" (configs[0]: one 1080p DXT1 frame through plain hap.h, one call, next to the
 reference on one CPU thread), "per_call_hap_h" (one hap.h call per 8K frame from a C client),
 "bc7_opaque" (an opaque format), frames made by the reference encoder, host-pointer rates.
+
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the
+headline line, nothing else.  Everything described above beside the headline -- the serial region, per-kernel events
+and roofline, the bit-exact check, the CPU baseline, the other configs and legs, and at N > 1 the other scaling mode
+and the chunk-group split -- runs with `--full`.  `--dump-outputs DIR` writes what the last timed step handed back
+(encoded frame sizes, a fixed sample of the frames' bytes and of the decoded textures' blocks) as .npy files.
 """
 import argparse
 import ctypes as C
@@ -73,7 +79,7 @@ def parse_args():
     ap.add_argument("--c5-frames", type=int, default=4,
                     help="also time N frames of C5 (16K Hap Q Alpha, the north-star's target config) at N=1; 0 = skip")
     ap.add_argument("--no-extras", action="store_true",
-                    help="the timed pipeline only: no size-for-speed option, texture->RGBA, host-pointer, foreign-frame, CPU "
+                    help="with --full: the timed pipeline only: no size-for-speed option, texture->RGBA, host-pointer, foreign-frame, CPU "
                          "or C5 legs (what tools/prof_bench.sh profiles, so that every dispatch belongs to the headline)")
     ap.add_argument("--extras-deadline", type=int, default=240,
                     help="N > 1: seconds the legs beside the headline (other scaling mode, chunk groups with the RCCL gather) may take "
@@ -87,6 +93,13 @@ def parse_args():
                          "per context, no collective): the multi-GPU road of a C client, same line shape as --gpus N")
     ap.add_argument("--selftest-cpu", action="store_true",
                     help="launch / rank / reduction logic only, gloo on CPU, a sleep in place of the codec (tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: serial region, per-kernel events and roofline, "
+                         "bit-exact check, CPU baseline, other configs and legs; N > 1: the other scaling mode and the chunk-group "
+                         "split.  Default: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (float32 / float64): "
+                         "encoded frame sizes, a fixed seeded sample of the frames' bytes and of the decoded textures' blocks")
     return ap.parse_args()
 
 
@@ -109,6 +122,37 @@ def frames_of_rank(total, rank, world, scaling):
     if scaling == "weak":
         return list(range(rank * total, (rank + 1) * total))
     return list(range(rank, total, world))          # hap_amd.shard.frames_for_rank: 60 over 8 -> 8/8/8/8/7/7/7/7
+
+
+DUMP_BYTES = 48 << 20           # --dump-outputs: float32 values of every rank together stay under this (64 MB cap)
+DUMP_SEED = 0x44554D50
+
+
+def dump_outputs(directory, used, frames, decoded, tex_bytes, block_bytes, frames_total, prefix=""):
+    """--dump-outputs: what the timed path handed its caller in its last step.  used: encoded bytes per frame; frames:
+    the encoded frames; decoded[t][f]: texture t of frame f.  The stream is GBs, so beside the sizes a fixed sample goes
+    out: the same seeded 4x4 blocks of every frame's decoded textures, the first bytes of every frame and bytes at the
+    same seeded fractions of each frame's length.  frames_total (every rank's frames) sizes the samples."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    nf = len(used)
+    per_frame = min(1 << 16, DUMP_BYTES // 4 // max(1, frames_total))
+    np.save(os.path.join(directory, prefix + "frame_bytes.npy"), np.asarray(used, dtype=np.float64))
+    if nf == 0:
+        return
+    head = 256
+    frac = np.random.RandomState(DUMP_SEED).random_sample(max(1, per_frame // 2 - head))
+    rows = []
+    for f in range(nf):
+        pos = np.concatenate([np.minimum(np.arange(head), used[f] - 1), np.sort((frac * used[f]).astype(np.int64))])
+        rows.append(frames[f][: used[f]][torch.from_numpy(pos).to(frames[f].device)].cpu())
+    np.save(os.path.join(directory, prefix + "frames_sample.npy"), torch.stack(rows).float().numpy())
+    for t, (tb, bb) in enumerate(zip(tex_bytes, block_bytes)):
+        nblocks = tb // bb
+        k = min(nblocks, max(1, per_frame // 2 // len(tex_bytes) // bb))
+        idx = torch.from_numpy(np.sort(np.random.RandomState(DUMP_SEED + 1 + t).choice(nblocks, k, replace=False)))
+        blocks = [decoded[t][f].view(-1, bb)[idx.to(decoded[t][f].device)].cpu() for f in range(nf)]
+        np.save(os.path.join(directory, prefix + "texture%d_blocks.npy" % t), torch.stack(blocks).float().numpy())
 
 
 class Stream:
@@ -364,6 +408,9 @@ def devices_from_c(args):
     for _ in range(args.steps):
         used = step()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, used, frames, [[d[t] for d in decs] for t in range(len(fmts))], tex_bytes,
+                     [8 if f in (0x83F0, 0x8DBB) else 16 for f in fmts], nf)
     # the last step's textures against the block encoder's (each on its own device)
     ok = True
     for f in range(0, nf, max(1, nf // 8)):
@@ -450,6 +497,12 @@ def main():
     stream = Stream(hap_amd, ctx, dev, args.config, frames_of_rank(nf_total, rank, world, args.scaling), flags, ctx_dec=ctx_dec)
     elapsed, prof = stream.timed(args.steps, args.warmup, fence, pipelined=pipelined)
     elapsed = max_over_ranks(elapsed)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, stream.used or [], getattr(stream, "last_frames", None) or stream.frames, stream.dec,
+                     stream.tex_bytes, [BLOCK_BYTES[f] for f in stream.fmts],
+                     nf_total if args.scaling == "strong" else nf_total * world, prefix="" if world == 1 else "rank%d_" % rank)
+    if not args.full:
+        return headline_only(args, dist, rank, world, stream, elapsed, nf_total, pipelined)
     serial = None
     timed_bit_exact = stream.bit_exact(reference=(rank == 0))     # what the timed region's last step left, before anything else runs
     if pipelined:
@@ -523,17 +576,7 @@ def main():
             dist.destroy_process_group()
         return
 
-    line = {
-        "metric": "RGBA GB/s + frames/sec, 8K Hap Q encode+decode" if args.config == "C4"
-                  else "RGBA GB/s + frames/sec, %s encode+decode" % args.config,
-        "value": round(value, 2), "unit": "GB/s", "fps": round(total_frames / elapsed, 1),
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": args.scaling,
-        "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-        "step": ("pipelined: K encodes + K decodes inside the timed region, batch k + 1's encode launched (HapGpuEncodeFramesRGBABegin) "
-                 "before batch k is decoded on a second context; frames in alternating buffers") if pipelined
-                else "serial: one blocking encode call + one blocking decode call per step, one context",
-    }
+    line = headline_fields(args, world, elapsed, total_frames, rgba_bytes, pipelined)
     total_frames_per_step = total_frames // args.steps
     if serial is not None:
         line["serial_step"] = {"ms_per_step": round(serial / args.steps * 1e3, 3),
@@ -591,7 +634,7 @@ def main():
         line["roofline"]["events_from"] = ("the serial region of the same K steps (each kernel runs by itself there; in the pipelined region the "
                                            "encode kernel of one batch and the decode kernels of the other share the GPU)") if serial is not None \
             else "the timed region"
-        line["roofline"]["profiled_as"] = "python bench.py --config %s --steps 20 --warmup 5 --frames %d --no-extras --serial (tools/prof_bench.sh -> profiles/%s_kernel_stats_%s.csv)" % (
+        line["roofline"]["profiled_as"] = "python bench.py --full --config %s --steps 20 --warmup 5 --frames %d --no-extras --serial (tools/prof_bench.sh -> profiles/%s_kernel_stats_%s.csv)" % (
             args.config, nf_total, ROUND_TAG, args.config.lower())
         line["kernels"] = kernels
         if not args.no_extras:
@@ -658,6 +701,10 @@ def main():
         line["summary"] = summary_of(line)
     print(json.dumps(line))
     sys.stdout.flush()
+    leave_group(dist, world)
+
+
+def leave_group(dist, world):
     if dist is not None:
         # (the line is out: a rank that never arrives must not keep this one from leaving)
         leave = None
@@ -670,6 +717,46 @@ def main():
         if leave is not None:
             leave.cancel()
         dist.destroy_process_group()
+
+
+def headline_fields(args, world, elapsed, total_frames, rgba_bytes, pipelined):
+    """The head of the line: `value` and `ms_per_step` of the timed region, the same in a plain and a --full run."""
+    return {
+        "metric": "RGBA GB/s + frames/sec, 8K Hap Q encode+decode" if args.config == "C4"
+                  else "RGBA GB/s + frames/sec, %s encode+decode" % args.config,
+        "value": round(total_frames * rgba_bytes / elapsed / 1e9, 2), "unit": "GB/s", "fps": round(total_frames / elapsed, 1),
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": args.scaling,
+        "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+        "step": ("pipelined: K encodes + K decodes inside the timed region, batch k + 1's encode launched (HapGpuEncodeFramesRGBABegin) "
+                 "before batch k is decoded on a second context; frames in alternating buffers") if pipelined
+                else "serial: one blocking encode call + one blocking decode call per step, one context",
+    }
+
+
+def headline_only(args, dist, rank, world, stream, elapsed, nf_total, pipelined):
+    """A plain run: the line of the timed region alone (no second region, no checks, no legs beside it: --full)."""
+    if rank == 0:
+        total_frames = (nf_total if args.scaling == "strong" else nf_total * world) * args.steps
+        line = headline_fields(args, world, elapsed, total_frames, stream.rgba_bytes, pipelined)
+        w, h, fmts, chunks = stream.w, stream.h, stream.fmts, stream.chunks
+        line["config"] = {"workload": "%s: %dx%d %s, %s chunks, Snappy, %d-frame stream, device-resident" % (
+            args.config, w, h, "+".join("%#x" % f for f in fmts), "+".join(map(str, chunks)), nf_total),
+            "frames_per_step": total_frames // args.steps, "fragment_index": not args.no_fragment_index}
+        if world == 1:
+            line["config"]["snappy_ratio"] = round(sum(stream.used) / max(stream.nf, 1) / sum(stream.tex_bytes), 4) if stream.used else None
+            line["config"]["parallelism"] = "single GPU"
+        else:
+            line["config"]["frames_per_rank"] = [len(frames_of_rank(nf_total, r, world, args.scaling)) for r in range(world)]
+            line["config"]["parallelism"] = ("frame f -> GPU f mod %d, no data-path collective" % world if args.scaling == "strong"
+                                             else "a whole stream per GPU, no data-path collective")
+            line["collective_backend"] = str(dist.get_backend())
+            if args.one_gpu_ranks:
+                line["dry_run"] = "all ranks on one GPU, gloo collectives: a functional check of the multi-rank path, not a measurement"
+        line["full"] = False
+        print(json.dumps(line))
+        sys.stdout.flush()
+    leave_group(dist, world)
 
 
 def summary_of(line):

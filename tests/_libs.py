@@ -4,10 +4,15 @@
   ref()     -> oracle/_ref/libhap_ref.so (unmodified reference hap.c + libsnappy 1.1.8;
                                           built here where /root/reference is mounted,
                                           shipped prebuilt to the GPU box)
+  recorded_reference() -> that library's answers recorded as digests in
+                          tests/golden/reference_answers.json (checked against
+                          ref() wherever it is built)
 
 TEST INFRASTRUCTURE ONLY: nothing in hap_amd/ imports this module.
 """
 import ctypes as C
+import hashlib
+import json
 import os
 import subprocess
 
@@ -180,3 +185,76 @@ def oracle_api():
 def ref_api():
     lib = ref_lib()
     return HapApi(lib) if lib is not None else None
+
+
+# ---- the reference's answers, recorded: the pinning tests need no reference library to run ----
+ANSWERS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_answers.json")
+
+
+def digest(x):
+    """A JSON-able fingerprint of an answer: byte strings by length and SHA-256, sequences element by element."""
+    if isinstance(x, (bytes, bytearray, memoryview)):
+        b = bytes(x)
+        return "%d:%s" % (len(b), hashlib.sha256(b).hexdigest()[:24])
+    if isinstance(x, (list, tuple)):
+        return [digest(v) for v in x]
+    if isinstance(x, dict):
+        return {k: digest(v) for k, v in sorted(x.items())}
+    return x
+
+
+class RecordedReference:
+    """What the unmodified reference (hap.c + libsnappy 1.1.8) answers, as digests, from
+    tests/golden/reference_answers.json (written by tests/golden/make_reference_answers.py).  Where the live
+    reference is built its answer is computed too and must equal the recorded one; where it is not, the record
+    stands in for it.  Questions: the HapApi methods by name ("decode" also returns callback_calls) and
+    "snappy_compress" / "snappy_uncompress"."""
+
+    recording = False                   # set by make_reference_answers.py: answers come from the live library
+
+    def __init__(self, live_api, snappy):
+        self.live, self.snappy = live_api, snappy
+        self.table = {}
+        if not self.recording:
+            with open(ANSWERS) as f:
+                self.table = json.load(f)
+
+    @staticmethod
+    def key(question, args):
+        return hashlib.sha256(json.dumps([question, digest(list(args))]).encode()).hexdigest()[:20]
+
+    def _live(self, question, args):
+        if question == "snappy_compress":
+            return self.snappy[0](*args)
+        if question == "snappy_uncompress":
+            return self.snappy[1](*args)
+        got = getattr(self.live, question)(*args)
+        return tuple(got) + (self.live.callback_calls,) if question == "decode" else got
+
+    def ask(self, question, *args):
+        """The reference's answer to question(*args), as a digest (compare with digest(...) of another answer)."""
+        k = self.key(question, args)
+        if self.recording:
+            self.table[k] = digest(self._live(question, args))
+        assert k in self.table, "no recorded reference answer for %s%r: regenerate tests/golden/reference_answers.json" % (
+            question, digest(list(args)))
+        want = self.table[k]
+        if self.live is not None and not self.recording:
+            assert digest(self._live(question, args)) == want, "the live reference disagrees with its record: %s" % question
+        return want
+
+    def save(self):
+        with open(ANSWERS, "w") as f:
+            json.dump(self.table, f, sort_keys=True, separators=(",", ":"))
+            f.write("\n")
+
+
+def recorded_reference():
+    if "recorded" not in _cache:
+        api = ref_api()
+        snappy = None
+        if api is not None:
+            import _data as D
+            snappy = (D.ref_snappy_compress, D.ref_snappy_uncompress)
+        _cache["recorded"] = RecordedReference(api, snappy)
+    return _cache["recorded"]

@@ -13,5 +13,5 @@ bash tools/prof_bench.sh C5 4 > /dev/null 2>&1; cp -r gpurun_out/prof_c5 $E/c5
 bash tools/prof_bench.sh C2 60 > /dev/null 2>&1; cp -r gpurun_out/prof_c2 $E/c2
 bash tools/prof_bench.sh C3 60 > /dev/null 2>&1; cp -r gpurun_out/prof_c3 $E/c3
 bash tools/prof_foreign.sh 24 > $E/foreign_stdout.txt 2>&1; cp -r gpurun_out/foreign $E/foreign
-python bench.py > $E/bench_default.json 2> $E/bench_default.err
+python bench.py --full > $E/bench_default.json 2> $E/bench_default.err
 tail -c 600 $E/bench_default.json

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof
 rm -rf $OUT; mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-CMD="python bench.py --steps 2 --warmup 1 --frames ${FRAMES:-12} --no-cpu-baseline"
+CMD="python bench.py --full --steps 2 --warmup 1 --frames ${FRAMES:-12} --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_trace -o r1 -- $CMD > $OUT/bench_trace.json 2> /tmp/trace.err
 cp $(find /tmp/prof_trace -name "*kernel_stats.csv") $OUT/kernel_stats.csv
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d /tmp/prof_pmc1 -o r1 -- $CMD > /dev/null 2> /tmp/pmc1.err
