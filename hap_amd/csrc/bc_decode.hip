@@ -8,6 +8,7 @@
 // Arithmetic follows oracle/bc_oracle.c (obc_decode_*) exactly; results are bit-identical.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "hapgpu_runtime.hpp"
 
 namespace {
 
@@ -281,9 +282,11 @@ void launch(const void *blocks, const void *alpha, unsigned bx, unsigned by, voi
 
 // format: HapTextureFormat of `blocks` (DXT1, DXT5, YCoCg-DXT5); alpha: optional RGTC1 plane.
 // Returns 0 launched, 1 bad arguments.
-extern "C" int hapgpu_launch_block_decode(const void *blocks, const void *alpha, unsigned width, unsigned height,
-                                          unsigned format, void *rgba, size_t row_bytes, hipStream_t stream)
+extern "C" int hapgpu_k_block_decode(hapgpu_rt *rt, const void *blocks, const void *alpha, unsigned width, unsigned height,
+                                     unsigned format, void *rgba, size_t row_bytes)
 {
+    scoped_timing st(rt, 6);
+    const hipStream_t stream = hapgpu_rt_stream(rt);
     if (!blocks || !rgba || width == 0 || height == 0 || (width & 3u) || (height & 3u) || row_bytes < (size_t)width * 4u)
         return 1;
     if (((uintptr_t)rgba | row_bytes) & 15u)
@@ -303,9 +306,11 @@ extern "C" int hapgpu_launch_block_decode(const void *blocks, const void *alpha,
 // The same for `pictures` textures of one format and geometry: table (device memory) = texture addresses, alpha plane
 // addresses (read when with_alpha), picture addresses, `pictures` of each; a texture address of 0 skips the picture.
 // Alignment as above (the host checks it per picture).
-extern "C" int hapgpu_launch_block_decode_batch(const uint64_t *table, unsigned pictures, int with_alpha, unsigned width,
-                                                unsigned height, unsigned format, size_t row_bytes, hipStream_t stream)
+extern "C" int hapgpu_k_block_decode_batch(hapgpu_rt *rt, const uint64_t *table, unsigned pictures, int with_alpha,
+                                           unsigned width, unsigned height, unsigned format, size_t row_bytes)
 {
+    scoped_timing st(rt, 6);
+    const hipStream_t stream = hapgpu_rt_stream(rt);
     if (!table || pictures == 0 || pictures > 65535u || width == 0 || height == 0 || (width & 3u) || (height & 3u) ||
         row_bytes < (size_t)width * 4u || (row_bytes & 15u))
         return 1;

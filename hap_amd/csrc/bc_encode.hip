@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "bc_encode_core.hpp"
+#include "hapgpu_runtime.hpp"
 
 namespace {
 
@@ -113,9 +114,11 @@ void launch(const void *rgba, size_t row_bytes, unsigned bx, unsigned by, void *
 } // namespace
 
 // format: HapTextureFormat constant. Returns 0 when launched, 1 for bad arguments.
-extern "C" int hapgpu_launch_block_encode(const void *rgba, unsigned width, unsigned height, size_t row_bytes,
-                                          unsigned format, void *out, hipStream_t stream)
+extern "C" int hapgpu_k_block_encode(hapgpu_rt *rt, const void *rgba, unsigned width, unsigned height, size_t row_bytes,
+                                     unsigned format, void *out)
 {
+    scoped_timing st(rt, 0);
+    const hipStream_t stream = hapgpu_rt_stream(rt);
     if (!rgba || !out || width == 0 || height == 0 || (width & 3u) || (height & 3u) || row_bytes < (size_t)width * 4u)
         return 1;
     if (((uintptr_t)rgba & 3u) || (row_bytes & 3u))
@@ -136,10 +139,11 @@ extern "C" int hapgpu_launch_block_encode(const void *rgba, unsigned width, unsi
 
 // Batch variant: `pictures` RGBA images of the same geometry whose addresses (and output addresses) are in device
 // arrays; wide != 0 promises 16-byte aligned sources and row pitch.  Outputs must be 8/16-byte aligned.
-extern "C" int hapgpu_launch_block_encode_batch(const uint64_t *sources, const uint64_t *outputs, unsigned pictures,
-                                                unsigned width, unsigned height, size_t row_bytes, unsigned format,
-                                                int wide, hipStream_t stream)
+extern "C" int hapgpu_k_block_encode_batch(hapgpu_rt *rt, const uint64_t *sources, const uint64_t *outputs, unsigned pictures,
+                                           unsigned width, unsigned height, size_t row_bytes, unsigned format, int wide)
 {
+    scoped_timing st(rt, 0);
+    const hipStream_t stream = hapgpu_rt_stream(rt);
     if (!sources || !outputs || pictures == 0 || width == 0 || height == 0 || (width & 3u) || (height & 3u) ||
         row_bytes < (size_t)width * 4u || (row_bytes & 3u) || pictures > 65535u || height / 4u > 65535u)
         return 1;
@@ -156,10 +160,12 @@ extern "C" int hapgpu_launch_block_encode_batch(const uint64_t *sources, const u
 
 // Hap Q Alpha batch: scaled YCoCg-DXT5 to colour_outputs[i] and the RGTC1 alpha plane to alpha_outputs[i], one read of
 // every RGBA picture.  Same argument rules as above.
-extern "C" int hapgpu_launch_block_encode_batch_ycocg_alpha(const uint64_t *sources, const uint64_t *colour_outputs,
-                                                            const uint64_t *alpha_outputs, unsigned pictures, unsigned width,
-                                                            unsigned height, size_t row_bytes, int wide, hipStream_t stream)
+extern "C" int hapgpu_k_block_encode_batch_ycocg_alpha(hapgpu_rt *rt, const uint64_t *sources, const uint64_t *colour_outputs,
+                                                       const uint64_t *alpha_outputs, unsigned pictures, unsigned width,
+                                                       unsigned height, size_t row_bytes, int wide)
 {
+    scoped_timing st(rt, 0);
+    const hipStream_t stream = hapgpu_rt_stream(rt);
     if (!sources || !colour_outputs || !alpha_outputs || pictures == 0 || width == 0 || height == 0 || (width & 3u) ||
         (height & 3u) || row_bytes < (size_t)width * 4u || (row_bytes & 3u) || pictures > 65535u || height / 4u > 65535u)
         return 1;

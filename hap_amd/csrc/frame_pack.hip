@@ -18,7 +18,7 @@
 // No host round trip: the only thing the host reads back is bytes_used / status per frame.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "hapgpu_abi.h"
+#include "hapgpu_runtime.hpp"
 
 namespace {
 
@@ -358,12 +358,14 @@ __global__ __launch_bounds__(64) void frame_gather_kernel(const HapGpuCopyEntry 
 // pack_scratch: frame_count * chunks_per_frame * hapgpu_pack_scratch_bytes_per_chunk() bytes of device memory
 extern "C" unsigned hapgpu_pack_scratch_bytes_per_chunk(void) { return (unsigned)sizeof(ChunkPack); }
 
-extern "C" int hapgpu_launch_frame_pack(HapGpuFrameEnc *frames, unsigned frame_count, unsigned frag_log2,
-                                        const void *slots, unsigned slot_stride, const uint32_t *frag_sizes,
-                                        const uint8_t *group_tables, HapGpuCopyEntry *copies, unsigned extra_first,
-                                        unsigned chunks_per_frame, unsigned max_chunks_per_texture, unsigned textures,
-                                        void *pack_scratch, hipStream_t stream)
+extern "C" int hapgpu_k_frame_pack(hapgpu_rt *rt, HapGpuFrameEnc *frames, unsigned frame_count, unsigned frag_log2,
+                                   const void *slots, unsigned slot_stride, const uint32_t *frag_sizes,
+                                   const uint8_t *group_tables, HapGpuCopyEntry *copies, unsigned extra_first,
+                                   unsigned chunks_per_frame, unsigned max_chunks_per_texture, unsigned textures,
+                                   void *pack_scratch)
 {
+    scoped_timing st(rt, 2);
+    const hipStream_t stream = hapgpu_rt_stream(rt);
     if (frame_count == 0)
         return 0;
     if (!pack_scratch || max_chunks_per_texture == 0 || textures == 0)
@@ -378,10 +380,11 @@ extern "C" int hapgpu_launch_frame_pack(HapGpuFrameEnc *frames, unsigned frame_c
     return hipGetLastError() == hipSuccess ? 0 : 4;
 }
 
-extern "C" int hapgpu_launch_frame_gather(const HapGpuCopyEntry *copies, unsigned count, hipStream_t stream)
+extern "C" int hapgpu_k_frame_gather(hapgpu_rt *rt, const HapGpuCopyEntry *copies, unsigned count)
 {
+    scoped_timing st(rt, 3);
     if (count == 0)
         return 0;
-    hipLaunchKernelGGL(frame_gather_kernel, dim3(count), dim3(64), 0, stream, copies, count);
+    hipLaunchKernelGGL(frame_gather_kernel, dim3(count), dim3(64), 0, hapgpu_rt_stream(rt), copies, count);
     return hipGetLastError() == hipSuccess ? 0 : 4;
 }

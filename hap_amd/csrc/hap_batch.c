@@ -1482,11 +1482,13 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
     {
         unsigned chunk_cursor = 0, unit_cursor = 0, scan_cursor = 0, seg_cursor = 0, word_cursor = 0, fine_cursor = 0;
         request_marks marks;
+        HapGpuScanRecords scan;      /* the block scan's records, once it has run */
         const void *staged_src = NULL;
         unsigned long staged_len = 0;
         const uint8_t *staged_dev = NULL;
         marks.count = 0;
         marks.requested = NULL;
+        memset(&scan, 0, sizeof(scan));
         for (f = 0; f < frame_count; f++) {
             hapf_texture_plan *p = &plans[f];
             HapGpuDecodeJob *job;
@@ -1637,6 +1639,13 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
         }
         /* streams of other encoders (no fragment table): find their independent 64 KiB blocks first */
         if (scan_chunks && scan_cursor == scan_chunks) {
+            scan.recs = drecs;
+            scan.joins = djoins;
+            scan.chunks = dscan;
+            scan.chunk_count = scan_chunks;
+            /* (about how many 64 KiB blocks the scanned streams hold: an eighth of the 8 KiB pieces the host made room for --
+               what the frames' textures hold -- or, without those, what the compressed bytes would be at three to one) */
+            scan.blocks_hint = fine_total ? fine_total / 8u + 1u : scan_segs / 5u + 1u;
             rc |= hapgpu_rt_h2d(rt, dscan, hscan, sizeof(HapGpuScanChunk) * scan_chunks);
             rc |= hapgpu_rt_zero(rt, dwork, sizeof(uint32_t));
             if (fine_total)
@@ -1647,10 +1656,10 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
                                        fine_total ? dwork : NULL, total_units, fine_total);
         }
         if (dguess && use_guess)
-            rc |= hapgpu_k_guess_group_tables(rt, dunits, total_units, djobs, NULL, 0u);
+            rc |= hapgpu_k_guess_group_tables(rt, dunits, total_units, djobs, NULL, 0u, NULL);
         if (dguess && (frag_kinds & 0x1000u)) {
             if (scan_chunks && scan_cursor == scan_chunks)
-                rc |= hapgpu_k_guess_group_tables(rt, dunits, total_units + fine_total, djobs, dwork, fine_total);
+                rc |= hapgpu_k_guess_group_tables(rt, dunits, total_units + fine_total, djobs, dwork, fine_total, &scan);
             else
                 frag_kinds &= ~0x1000u;
         }
@@ -1658,7 +1667,8 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
                                      /* 3: every stream is as short as one 8 KiB fragment (frames written with
                                         HAPGPU_ENCODE_FINE_CHUNKS): the 2 KiB ring of the block-scan launches instead of the 32 KiB one, 30 wavefronts per CU instead of 4 */
                                      any_stream ? (scan_chunks ? 2 : (max_stream_src <= HAPGPU_SLOT_DATA_BYTES + 64u ? 3 : 1)) : 0,
-                                     (scan_chunks && scan_cursor == scan_chunks && fine_total) ? dwork : NULL, fine_total);
+                                     (scan_chunks && scan_cursor == scan_chunks && fine_total) ? dwork : NULL, fine_total,
+                                     any_stream && scan.recs ? &scan : NULL);
         rc |= hapgpu_rt_d2h(rt, hjobs, djobs, sizeof(HapGpuDecodeJob) * live);
         HAPB_MARK("launched");
         rc |= hapgpu_rt_sync(rt);

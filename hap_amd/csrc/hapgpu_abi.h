@@ -251,7 +251,7 @@ typedef struct HapGpuDecodeUnit {
 } HapGpuDecodeUnit;
 
 /* ------------------------------------------------------------------ */
-/* runtime + launchers (implemented in hapgpu_runtime.hip)              */
+/* runtime (hapgpu_runtime.hip) + launchers (each in its kernels' file) */
 /* ------------------------------------------------------------------ */
 typedef struct hapgpu_rt hapgpu_rt;
 
@@ -337,6 +337,16 @@ int hapgpu_k_scan_blocks(hapgpu_rt *rt, HapGpuDecodeUnit *units, const HapGpuDec
                                                 (room for fine_pool of them), then the pool's cursor (zero on entry) */,
                          unsigned fine_first, unsigned fine_pool /* the 8 KiB blocks' unit slots: units[fine_first .. + fine_pool),
                                                                     handed out to the streams on the device */);
+/* The block scan's records of one call, for the launches behind it (hapgpu_k_guess_group_tables, hapgpu_k_snappy_decode;
+ * a NULL pointer: no scan in this call).  recs / joins / chunks / chunk_count: as given to hapgpu_k_scan_blocks;
+ * blocks_hint: about how many 64 KiB blocks the scanned streams hold */
+typedef struct HapGpuScanRecords {
+    const void *recs;
+    const void *joins;
+    const HapGpuScanChunk *chunks;
+    unsigned chunk_count;
+    unsigned blocks_hint;
+} HapGpuScanRecords;
 /* frag_log2: fragment size of the batch's FRAGMENT units (0: none present);
  * fragment_kinds: bit g set = fragments of granularity_log2 g present */
 /* fragment_kinds bits 8 / 9 / 10: field-stream units of [2,6,4,4] / [4,4] / [2,6] blocks present */
@@ -344,7 +354,8 @@ int hapgpu_k_scan_blocks(hapgpu_rt *rt, HapGpuDecodeUnit *units, const HapGpuDec
 int hapgpu_k_snappy_decode(hapgpu_rt *rt, const HapGpuDecodeUnit *units, unsigned unit_count,
                            HapGpuDecodeJob *jobs, unsigned frag_log2, unsigned fragment_kinds,
                            int any_stream_or_copy_units,
-                           const uint32_t *fine_work, unsigned fine_slots /* the block scan's list and its capacity (0: none) */);
+                           const uint32_t *fine_work, unsigned fine_slots /* the block scan's list and its capacity (0: none) */,
+                           const HapGpuScanRecords *scan);
 
 /* measurement */
 void hapgpu_rt_set_profiling(hapgpu_rt *rt, int enable);
@@ -352,9 +363,10 @@ int hapgpu_rt_collect_profile(hapgpu_rt *rt, unsigned long *launches, double *ms
 /* group tables for the STREAM units of jobs whose reserved bit 16 is set (fragments that came as chunks of their own,
    without a private table): units that turn out to be field streams become FIELDS units (snappy_decode_fields.hip) */
 /* (work != NULL: only the units the block scan listed there -- the 8 KiB pieces of table-less streams of this library;
-   unit_count then spans the fine region behind the ordinary units as well) */
+   unit_count then spans the fine region behind the ordinary units as well; with the scan's records their tables come
+   from those) */
 int hapgpu_k_guess_group_tables(hapgpu_rt *rt, HapGpuDecodeUnit *units, unsigned unit_count, const HapGpuDecodeJob *jobs,
-                                const uint32_t *work, unsigned work_slots);
+                                const uint32_t *work, unsigned work_slots, const HapGpuScanRecords *scan);
 int hapgpu_rt_timer_start(hapgpu_rt *rt);
 int hapgpu_rt_timer_stop(hapgpu_rt *rt, double *ms);
 

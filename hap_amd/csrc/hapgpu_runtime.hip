@@ -1,7 +1,7 @@
-// hapgpu_runtime.hip -- the HIP side of the C ABI in hapgpu_abi.h: device/stream ownership,
-// grow-only scratch arenas, host<->device staging, kernel launchers and the HIP-event
-// instrumentation bench.py reads.  Everything here is plumbing; the kernels live in
-// bc_encode.hip, snappy_compress.hip, frame_pack.hip and snappy_decode.hip.
+// hapgpu_runtime.hip -- the HIP side of the C ABI in hapgpu_abi.h: device/stream ownership, per-runtime launch
+// settings, grow-only scratch arenas, host<->device staging and the HIP-event instrumentation bench.py reads.
+// Everything here is plumbing; the kernels and their hapgpu_k_* launchers live in bc_encode.hip, bc_decode.hip,
+// snappy_compress.hip, frame_pack.hip, snappy_decode.hip and snappy_decode_fields.hip (hapgpu_runtime.hpp).
 #include <hip/hip_runtime.h>
 #include <pthread.h>
 #include <stdint.h>
@@ -9,45 +9,11 @@
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
-#include "hapgpu_abi.h"
-
-extern "C" {
-int hapgpu_launch_block_encode(const void *rgba, unsigned width, unsigned height, size_t row_bytes,
-                               unsigned format, void *out, hipStream_t stream);
-int hapgpu_launch_block_encode_batch(const uint64_t *sources, const uint64_t *outputs, unsigned pictures,
-                                     unsigned width, unsigned height, size_t row_bytes, unsigned format,
-                                     int wide, hipStream_t stream);
-int hapgpu_launch_block_encode_batch_ycocg_alpha(const uint64_t *sources, const uint64_t *colour_outputs,
-                                                 const uint64_t *alpha_outputs, unsigned pictures, unsigned width,
-                                                 unsigned height, size_t row_bytes, int wide, hipStream_t stream);
-int hapgpu_launch_block_decode(const void *blocks, const void *alpha, unsigned width, unsigned height,
-                               unsigned format, void *rgba, size_t row_bytes, hipStream_t stream);
-int hapgpu_launch_snappy_compress(const HapGpuFrameEnc *frames, unsigned frame_count, unsigned max_frags_per_texture,
-                                  unsigned frag_log2, void *slots, unsigned slot_stride, uint32_t *frag_sizes,
-                                  uint8_t *group_tables, unsigned granularity_mask, hipStream_t stream);
-int hapgpu_launch_frame_pack(HapGpuFrameEnc *frames, unsigned frame_count, unsigned frag_log2, const void *slots,
-                             unsigned slot_stride, const uint32_t *frag_sizes, const uint8_t *group_tables,
-                             HapGpuCopyEntry *copies, unsigned extra_first, unsigned chunks_per_frame,
-                             unsigned max_chunks_per_texture, unsigned textures, void *pack_scratch, hipStream_t stream);
-int hapgpu_launch_frame_gather(const HapGpuCopyEntry *copies, unsigned count, hipStream_t stream);
-int hapgpu_launch_decode_plan(HapGpuDecodeJob *jobs, unsigned job_count, unsigned max_chunks, hipStream_t stream);
-int hapgpu_launch_scan_blocks(HapGpuDecodeUnit *units, const HapGpuDecodeJob *jobs, HapGpuScanChunk *chunks, unsigned chunk_count,
-                              HapGpuScanSegment *segs, void *recs, void *joins, unsigned seg_total, uint32_t *fine_work,
-                              unsigned fine_first, unsigned fine_pool, hipStream_t stream);
-int hapgpu_launch_snappy_decode(const HapGpuDecodeUnit *units, unsigned unit_count, HapGpuDecodeJob *jobs,
-                                unsigned frag_log2, unsigned fragment_kinds, int any_stream_or_copy_units,
-                                const uint32_t *fine_work, unsigned fine_slots, const void *scan_recs, const void *scan_joins,
-                                const HapGpuScanChunk *scan_chunks, unsigned scan_chunk_count, unsigned scan_blocks_hint,
-                                uint32_t *resolved, hipStream_t stream);
-}
+#include "hapgpu_runtime.hpp"
 
 namespace {
 constexpr int kSlots = 16;
 
-struct timed_launch {
-    int cls;
-    hipEvent_t start, stop;
-};
 struct recorded_graph {
     uint64_t key;
     hipGraphExec_t exec;
@@ -73,10 +39,7 @@ struct hapgpu_rt {
     uint64_t generation;
     int graphs_off;      // unless HAP_AMD_GRAPHS=1
     int recording;
-    const void *scan_recs, *scan_joins;      // the block scan's records of the call in progress (for its decode launch)
-    unsigned scan_blocks_hint;
-    const HapGpuScanChunk *scan_chunks;
-    unsigned scan_chunk_count;
+    hapgpu_launch_settings settings;
     uint32_t *resolved_blocks;               // device counter: 64 KiB blocks a workgroup decoded
 };
 
@@ -137,6 +100,17 @@ extern "C" int hapgpu_rt_create(int device, hapgpu_rt **out)
     if (hipMalloc((void **)&rt->resolved_blocks, 64u * sizeof(uint32_t)) != hipSuccess || hipMemset(rt->resolved_blocks, 0, 64u * sizeof(uint32_t)) != hipSuccess) {
         (void)hipGetLastError();
         rt->resolved_blocks = nullptr;       // (a statistic: the decoder runs without it)
+    }
+    {
+        hapgpu_launch_settings &s = rt->settings;
+        int cus = 0;
+        s.cus = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0 ? (unsigned)cus : 0u;
+        const char *v = HAP_AB_ENV("HAP_AMD_COPY_KERNELS");
+        s.copy_kernels = !(v && v[0] == '0');
+        hapgpu_prepare_snappy_compress(&s);
+        hapgpu_prepare_snappy_decode(&s);
+        hapgpu_prepare_snappy_decode_fields(&s);
+        (void)hipGetLastError();             // (a refused attribute is settled above: it must not fail a later launch)
     }
     *out = rt;
     return 0;
@@ -273,22 +247,9 @@ static bool in_pinned_scratch(const hapgpu_rt *rt, const void *p, size_t bytes)
 }
 
 static const size_t kSmallCopyBytes = (size_t)1 << 20;
-static bool copy_kernels_enabled()
-{
-    static int on = -1;
-    if (on < 0) {
-        const char *v = HAP_AB_ENV("HAP_AMD_COPY_KERNELS");
-        on = (v && v[0] == '0') ? 0 : 1;
-    }
-    return on != 0;
-}
 
 // 1: kernels may read and write the pinned scratch in place (it is mapped into the device's address space)
-extern "C" int hapgpu_rt_pinned_is_mapped(hapgpu_rt *rt)
-{
-    (void)rt;
-    return copy_kernels_enabled() ? 1 : 0;
-}
+extern "C" int hapgpu_rt_pinned_is_mapped(hapgpu_rt *rt) { return rt->settings.copy_kernels ? 1 : 0; }
 
 static int small_copy(hapgpu_rt *rt, void *dst, const void *src, size_t bytes)
 {
@@ -300,7 +261,7 @@ static int small_copy(hapgpu_rt *rt, void *dst, const void *src, size_t bytes)
 extern "C" int hapgpu_rt_h2d(hapgpu_rt *rt, void *dst, const void *src, size_t bytes)
 {
     if (!bytes) return 0;
-    if (bytes <= kSmallCopyBytes && copy_kernels_enabled() && in_pinned_scratch(rt, src, bytes))
+    if (bytes <= kSmallCopyBytes && rt->settings.copy_kernels && in_pinned_scratch(rt, src, bytes))
         return small_copy(rt, dst, src, bytes);
     hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, rt->stream);
     if (e != hipSuccess) { complain("hipMemcpyAsync(H2D)", e); return 4; }
@@ -310,7 +271,7 @@ extern "C" int hapgpu_rt_h2d(hapgpu_rt *rt, void *dst, const void *src, size_t b
 extern "C" int hapgpu_rt_d2h(hapgpu_rt *rt, void *dst, const void *src, size_t bytes)
 {
     if (!bytes) return 0;
-    if (bytes <= kSmallCopyBytes && copy_kernels_enabled() && in_pinned_scratch(rt, dst, bytes))
+    if (bytes <= kSmallCopyBytes && rt->settings.copy_kernels && in_pinned_scratch(rt, dst, bytes))
         return small_copy(rt, dst, src, bytes);
     hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, rt->stream);
     if (e != hipSuccess) { complain("hipMemcpyAsync(D2H)", e); return 4; }
@@ -464,27 +425,27 @@ static hipEvent_t take_event(hapgpu_rt *rt)
     return ev;
 }
 
-struct scoped_timing {
-    hapgpu_rt *rt;
-    timed_launch t;
-    bool on;
-    scoped_timing(hapgpu_rt *r, int cls) : rt(r), on(r->profiling != 0)
-    {
-        if (on) {
-            t.cls = cls;
-            t.start = take_event(rt);
-            t.stop = take_event(rt);
-            (void)hipEventRecord(t.start, rt->stream);
-        }
+scoped_timing::scoped_timing(hapgpu_rt *r, int cls) : rt(r), on(r->profiling != 0)
+{
+    if (on) {
+        t.cls = cls;
+        t.start = take_event(rt);
+        t.stop = take_event(rt);
+        (void)hipEventRecord(t.start, rt->stream);
     }
-    ~scoped_timing()
-    {
-        if (on) {
-            (void)hipEventRecord(t.stop, rt->stream);
-            rt->pending.push_back(t);
-        }
+}
+
+scoped_timing::~scoped_timing()
+{
+    if (on) {
+        (void)hipEventRecord(t.stop, rt->stream);
+        rt->pending.push_back(t);
     }
-};
+}
+
+hipStream_t hapgpu_rt_stream(hapgpu_rt *rt) { return rt->stream; }
+hapgpu_launch_settings *hapgpu_rt_settings(hapgpu_rt *rt) { return &rt->settings; }
+uint32_t *hapgpu_rt_resolved_counter(hapgpu_rt *rt) { return rt->resolved_blocks; }
 
 extern "C" void hapgpu_rt_set_profiling(hapgpu_rt *rt, int enable) { rt->profiling = enable; }
 
@@ -605,136 +566,6 @@ extern "C" int hapgpu_k_gather_prefixes_far(hapgpu_rt *rt, const uint64_t *frame
     hipLaunchKernelGGL(gather_prefix_kernel, dim3(count), dim3(256), 0, rt->stream, frames_dev, lengths_dev, prefix,
                        (uint8_t *)out_dev, far_dev, (uint8_t *)out2_dev, far_at_dev);
     return hipGetLastError() == hipSuccess ? 0 : 4;
-}
-
-// ---- launchers -----------------------------------------------------------------------------
-
-extern "C" int hapgpu_k_block_encode(hapgpu_rt *rt, const void *rgba, unsigned width, unsigned height,
-                                     size_t row_bytes, unsigned hap_texture_format, void *out)
-{
-    scoped_timing st(rt, 0);
-    return hapgpu_launch_block_encode(rgba, width, height, row_bytes, hap_texture_format, out, rt->stream);
-}
-
-extern "C" int hapgpu_k_block_encode_batch(hapgpu_rt *rt, const uint64_t *sources, const uint64_t *outputs,
-                                           unsigned pictures, unsigned width, unsigned height, size_t row_bytes,
-                                           unsigned hap_texture_format, int wide)
-{
-    scoped_timing st(rt, 0);
-    return hapgpu_launch_block_encode_batch(sources, outputs, pictures, width, height, row_bytes, hap_texture_format,
-                                            wide, rt->stream);
-}
-
-extern "C" int hapgpu_k_block_encode_batch_ycocg_alpha(hapgpu_rt *rt, const uint64_t *sources, const uint64_t *colour_outputs,
-                                                       const uint64_t *alpha_outputs, unsigned pictures, unsigned width,
-                                                       unsigned height, size_t row_bytes, int wide)
-{
-    scoped_timing st(rt, 0);
-    return hapgpu_launch_block_encode_batch_ycocg_alpha(sources, colour_outputs, alpha_outputs, pictures, width, height,
-                                                        row_bytes, wide, rt->stream);
-}
-
-extern "C" int hapgpu_launch_block_decode_batch(const uint64_t *table, unsigned pictures, int with_alpha, unsigned width,
-                                                unsigned height, unsigned format, size_t row_bytes, hipStream_t stream);
-extern "C" int hapgpu_k_block_decode_batch(hapgpu_rt *rt, const uint64_t *table, unsigned pictures, int with_alpha,
-                                           unsigned width, unsigned height, unsigned hap_texture_format, size_t row_bytes)
-{
-    scoped_timing st(rt, 6);
-    return hapgpu_launch_block_decode_batch(table, pictures, with_alpha, width, height, hap_texture_format, row_bytes, rt->stream);
-}
-
-extern "C" int hapgpu_k_block_decode(hapgpu_rt *rt, const void *blocks, const void *alpha, unsigned width,
-                                     unsigned height, unsigned hap_texture_format, void *rgba, size_t row_bytes)
-{
-    scoped_timing st(rt, 6);
-    return hapgpu_launch_block_decode(blocks, alpha, width, height, hap_texture_format, rgba, row_bytes, rt->stream);
-}
-
-extern "C" int hapgpu_k_snappy_compress(hapgpu_rt *rt, const HapGpuFrameEnc *frames, unsigned frame_count,
-                                        unsigned max_frags_per_texture, unsigned frag_log2, void *slots,
-                                        unsigned slot_stride, uint32_t *frag_sizes, uint8_t *group_tables,
-                                        unsigned granularity_mask)
-{
-    scoped_timing st(rt, ((granularity_mask >> 16) & 0xFu) ? 8 : 1);      // (8: the block encoder runs inside, HapGpuKernel_EncodeFused)
-    return hapgpu_launch_snappy_compress(frames, frame_count, max_frags_per_texture, frag_log2, slots, slot_stride,
-                                         frag_sizes, group_tables, granularity_mask, rt->stream);
-}
-
-extern "C" int hapgpu_k_frame_pack(hapgpu_rt *rt, HapGpuFrameEnc *frames, unsigned frame_count, unsigned frag_log2,
-                                   const void *slots, unsigned slot_stride, const uint32_t *frag_sizes,
-                                   const uint8_t *group_tables, HapGpuCopyEntry *copies, unsigned extra_first,
-                                   unsigned chunks_per_frame, unsigned max_chunks_per_texture, unsigned textures,
-                                   void *pack_scratch)
-{
-    scoped_timing st(rt, 2);
-    return hapgpu_launch_frame_pack(frames, frame_count, frag_log2, slots, slot_stride, frag_sizes, group_tables, copies,
-                                    extra_first, chunks_per_frame, max_chunks_per_texture, textures, pack_scratch, rt->stream);
-}
-
-extern "C" int hapgpu_k_frame_gather(hapgpu_rt *rt, const HapGpuCopyEntry *copies, unsigned count)
-{
-    scoped_timing st(rt, 3);
-    return hapgpu_launch_frame_gather(copies, count, rt->stream);
-}
-
-extern "C" int hapgpu_k_decode_plan(hapgpu_rt *rt, HapGpuDecodeJob *jobs, unsigned job_count,
-                                    HapGpuDecodeUnit *units, unsigned unit_count, unsigned max_chunks)
-{
-    // unit slots the planner does not reach (it stops at the first malformed chunk) must read as SKIP
-    if (unit_count && hipMemsetAsync(units, 0, (size_t)unit_count * sizeof(HapGpuDecodeUnit), rt->stream) != hipSuccess)
-        return 4;
-    scoped_timing st(rt, 4);
-    return hapgpu_launch_decode_plan(jobs, job_count, max_chunks, rt->stream);
-}
-
-extern "C" int hapgpu_k_scan_blocks(hapgpu_rt *rt, HapGpuDecodeUnit *units, const HapGpuDecodeJob *jobs, HapGpuScanChunk *chunks,
-                                    unsigned chunk_count, HapGpuScanSegment *segs, void *recs, void *joins, unsigned seg_total,
-                                    uint32_t *fine_work, unsigned fine_first, unsigned fine_pool)
-{
-    scoped_timing st(rt, 7);
-    // (the decode launch of the same call reads the scan's records again: the 64 KiB blocks as workgroups)
-    rt->scan_recs = recs;
-    rt->scan_joins = joins;
-    rt->scan_chunks = chunks;
-    rt->scan_chunk_count = chunk_count;
-    // (about how many 64 KiB blocks the scanned streams hold: an eighth of the 8 KiB pieces the host made room for -- what
-    // the frames' textures hold -- or, without those, what the compressed bytes would be at three to one)
-    rt->scan_blocks_hint = fine_pool ? fine_pool / 8u + 1u : seg_total / 5u + 1u;
-    return hapgpu_launch_scan_blocks(units, jobs, chunks, chunk_count, segs, recs, joins, seg_total, fine_work, fine_first, fine_pool,
-                                     rt->stream);
-}
-
-extern "C" int hapgpu_launch_guess_group_tables(HapGpuDecodeUnit *units, unsigned unit_count, const HapGpuDecodeJob *jobs,
-                                                const uint32_t *work, unsigned work_slots, hipStream_t stream);
-#ifdef BRK_TIMING
-extern "C" void hapgpu_debug_merge_counters(unsigned *out);
-#endif
-extern "C" int hapgpu_launch_group_tables_from_records(HapGpuDecodeUnit *units, unsigned unit_count, const HapGpuDecodeJob *jobs,
-                                                       const uint32_t *work, unsigned work_slots, const void *recs, const void *joins,
-                                                       hipStream_t stream);
-extern "C" int hapgpu_k_guess_group_tables(hapgpu_rt *rt, HapGpuDecodeUnit *units, unsigned unit_count, const HapGpuDecodeJob *jobs,
-                                           const uint32_t *work, unsigned work_slots)
-{
-    scoped_timing st(rt, 7);          // (with the block scan: finding where wavefronts may start in streams that do not say)
-    // the pieces the scan of this call listed: from its records, a wavefront per piece (r06); fragments that are chunks of
-    // their own (no scan): a lane per fragment walks it
-    if (work && rt->scan_recs && rt->scan_joins)
-        return hapgpu_launch_group_tables_from_records(units, unit_count, jobs, work, work_slots, rt->scan_recs, rt->scan_joins, rt->stream);
-    return hapgpu_launch_guess_group_tables(units, unit_count, jobs, work, work_slots, rt->stream);
-}
-
-extern "C" int hapgpu_k_snappy_decode(hapgpu_rt *rt, const HapGpuDecodeUnit *units, unsigned unit_count,
-                                      HapGpuDecodeJob *jobs, unsigned frag_log2, unsigned fragment_kinds,
-                                      int any_stream_or_copy_units, const uint32_t *fine_work, unsigned fine_slots)
-{
-    scoped_timing st(rt, 5);
-    const void *recs = rt->scan_recs, *joins = rt->scan_joins;
-    rt->scan_recs = nullptr;                 // (one call's records: never another's)
-    rt->scan_joins = nullptr;
-    return hapgpu_launch_snappy_decode(units, unit_count, jobs, frag_log2, fragment_kinds, any_stream_or_copy_units,
-                                       fine_work, fine_slots, any_stream_or_copy_units == 2 ? recs : nullptr,
-                                       any_stream_or_copy_units == 2 ? joins : nullptr, rt->scan_chunks, rt->scan_chunk_count,
-                                       rt->scan_blocks_hint, rt->resolved_blocks, rt->stream);
 }
 
 // 64 KiB blocks of other encoders' streams that a workgroup decoded (snappy_decode_block_resolve_kernel) since the runtime

@@ -23,7 +23,7 @@
 #include <type_traits>
 #include <stdint.h>
 #include <stdlib.h>
-#include "hapgpu_abi.h"
+#include "hapgpu_runtime.hpp"
 #include "measurement_guard.h"
 
 namespace {
@@ -485,32 +485,34 @@ __global__ __launch_bounds__(64 * kWgWaves) void snappy_compress_wg_kernel(const
 
 } // namespace
 
-extern "C" int hapgpu_launch_snappy_compress_blocks(const HapGpuFrameEnc *frames, unsigned frame_count,
-                                                    unsigned max_frags_per_texture, unsigned textures, void *slots,
-                                                    unsigned slot_stride, uint32_t *frag_sizes, uint8_t *group_tables,
-                                                    unsigned layouts, unsigned fused, hipStream_t stream);
+// LDS of snappy_compress_wg_kernel<G, 0> for fragments of 2^frag_log2 bytes
+static constexpr unsigned wg_dynamic_lds(unsigned frag_log2) { return (1u << frag_log2) + 32u + kWgHashEntries * 4u + kWgWaves * 4u; }
 
-extern "C" int hapgpu_launch_snappy_compress(const HapGpuFrameEnc *frames, unsigned frame_count,
-                                             unsigned max_frags_per_texture, unsigned frag_log2, void *slots,
-                                             unsigned slot_stride, uint32_t *frag_sizes, uint8_t *group_tables,
-                                             unsigned granularity_mask, hipStream_t stream)
+// (the largest fragments' LDS: whatever a launch asks for is at most that)
+void hapgpu_prepare_snappy_compress(hapgpu_launch_settings *s)
 {
+    const int lds = (int)wg_dynamic_lds(16u);
+    s->compress_big_lds =
+        hipFuncSetAttribute((const void *)snappy_compress_wg_kernel<1u, 0u>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess &&
+        hipFuncSetAttribute((const void *)snappy_compress_wg_kernel<2u, 0u>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess &&
+        hipFuncSetAttribute((const void *)snappy_compress_wg_kernel<4u, 0u>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
+}
+
+extern "C" int hapgpu_k_snappy_compress(hapgpu_rt *rt, const HapGpuFrameEnc *frames, unsigned frame_count,
+                                        unsigned max_frags_per_texture, unsigned frag_log2, void *slots,
+                                        unsigned slot_stride, uint32_t *frag_sizes, uint8_t *group_tables,
+                                        unsigned granularity_mask)
+{
+    scoped_timing st(rt, ((granularity_mask >> 16) & 0xFu) ? 8 : 1);      // (8: the block encoder runs inside, HapGpuKernel_EncodeFused)
+    const hipStream_t stream = hapgpu_rt_stream(rt);
     if (frame_count == 0 || max_frags_per_texture == 0)
         return 0;
     if (frag_log2 < 10 || frag_log2 > 16)
         return 1;
     {
-        const unsigned lds2 = (1u << frag_log2) + 32u + kWgHashEntries * 4u + kWgWaves * 4u;
-        if (lds2 > 65536u) {
-            static bool once2 = false;
-            if (!once2) {
-                if (hipFuncSetAttribute((const void *)snappy_compress_wg_kernel<1u, 0u>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess ||
-                    hipFuncSetAttribute((const void *)snappy_compress_wg_kernel<2u, 0u>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess ||
-                    hipFuncSetAttribute((const void *)snappy_compress_wg_kernel<4u, 0u>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2) != hipSuccess)
-                    return 4;
-                once2 = true;
-            }
-        }
+        const unsigned lds2 = wg_dynamic_lds(frag_log2);
+        if (lds2 > 65536u && !hapgpu_rt_settings(rt)->compress_big_lds)
+            return 4;
         const unsigned textures = ((granularity_mask >> 8) & 0xFFu) == 1u ? 1u : 2u;      // bits 8..15: textures per frame (0 = unknown)
         const unsigned fused = (granularity_mask >> 16) & 0xFu;                 // bits 16..19: textures made from RGBA on the way
         const dim3 grid(max_frags_per_texture, textures, frame_count), block(64 * kWgWaves);
@@ -529,8 +531,8 @@ extern "C" int hapgpu_launch_snappy_compress(const HapGpuFrameEnc *frames, unsig
                 return 1;
             const unsigned layouts = ((granularity_mask & 32u) ? 1u : 0u) | ((granularity_mask & 64u) ? 2u : 0u) |
                                      ((granularity_mask & 16u) ? 4u : 0u) | ((granularity_mask & 128u) ? 8u : 0u);
-            if (hapgpu_launch_snappy_compress_blocks(frames, frame_count, max_frags_per_texture, textures, slots, slot_stride,
-                                                     frag_sizes, group_tables, layouts, fused, stream))
+            if (hapgpu_snappy_compress_blocks(frames, frame_count, max_frags_per_texture, textures, slots, slot_stride,
+                                              frag_sizes, group_tables, layouts, fused, stream))
                 return 4;
         }
         if (granularity_mask & 1u)

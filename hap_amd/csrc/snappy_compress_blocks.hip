@@ -36,7 +36,7 @@
 // HBM traffic: texture read once (the neighbour loads hit L1 / L2), compressed bytes written once.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "hapgpu_abi.h"
+#include "hapgpu_runtime.hpp"
 #include "measurement_guard.h"
 #include "bc_encode_core.hpp"
 
@@ -820,10 +820,9 @@ __global__ __launch_bounds__(64, SCB_MIN_WAVES) void snappy_compress_blocks_kern
 // layouts: bit 0 = [2,6,4,4] textures present, bit 1 = [4,4], bit 2 = [2,6], bit 3 = [4,4,4,4];
 // fused: textures made from the frames' RGBA pictures on the way (HapGpuTexEnc.reserved bits 24..26): bit 0 = scaled
 // YCoCg-DXT5, bit 1 = DXT5, bit 2 = DXT1, bit 3 = RGTC1
-extern "C" int hapgpu_launch_snappy_compress_blocks(const HapGpuFrameEnc *frames, unsigned frame_count,
-                                                    unsigned max_frags_per_texture, unsigned textures, void *slots,
-                                                    unsigned slot_stride, uint32_t *frag_sizes, uint8_t *group_tables,
-                                                    unsigned layouts, unsigned fused, hipStream_t stream)
+int hapgpu_snappy_compress_blocks(const HapGpuFrameEnc *frames, unsigned frame_count, unsigned max_frags_per_texture,
+                                  unsigned textures, void *slots, unsigned slot_stride, uint32_t *frag_sizes,
+                                  uint8_t *group_tables, unsigned layouts, unsigned fused, hipStream_t stream)
 {
     if (frame_count == 0 || max_frags_per_texture == 0 || (layouts | fused) == 0)
         return 0;

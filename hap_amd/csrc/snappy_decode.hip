@@ -33,7 +33,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
-#include "hapgpu_abi.h"
+#include "hapgpu_runtime.hpp"
 #include "measurement_guard.h"
 
 namespace {
@@ -2266,14 +2266,20 @@ __global__ __launch_bounds__(64) void group_tables_from_records_kernel(HapGpuDec
 } // namespace
 
 #ifdef BRK_TIMING
-extern "C" void hapgpu_debug_merge_counters(unsigned *out)
+void hapgpu_debug_merge_counters(unsigned *out)
 {
     (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_merge_dbg), sizeof(unsigned) * 8u);
 }
 #endif
 
-extern "C" int hapgpu_launch_decode_plan(HapGpuDecodeJob *jobs, unsigned job_count, unsigned max_chunks, hipStream_t stream)
+extern "C" int hapgpu_k_decode_plan(hapgpu_rt *rt, HapGpuDecodeJob *jobs, unsigned job_count,
+                                    HapGpuDecodeUnit *units, unsigned unit_count, unsigned max_chunks)
 {
+    const hipStream_t stream = hapgpu_rt_stream(rt);
+    // unit slots the planner does not reach (it stops at the first malformed chunk) must read as SKIP
+    if (unit_count && hipMemsetAsync(units, 0, (size_t)unit_count * sizeof(HapGpuDecodeUnit), stream) != hipSuccess)
+        return 4;
+    scoped_timing st(rt, 4);
     if (job_count == 0)
         return 0;
     hipLaunchKernelGGL(decode_plan_kernel, dim3(job_count), dim3(64), 0, stream, jobs, job_count);
@@ -2286,13 +2292,10 @@ extern "C" int hapgpu_launch_decode_plan(HapGpuDecodeJob *jobs, unsigned job_cou
 // dynamic LDS to request for the v2 kernel: none when its ring + tail fit the static array
 static constexpr unsigned fragment_dynamic_lds(unsigned ring) { return ring + kFragmentTail <= 65536u ? 0u : ring + kFragmentTail; }
 
-extern "C" int hapgpu_launch_snappy_decode_fields(const HapGpuDecodeUnit *units, unsigned unit_count, HapGpuDecodeJob *jobs,
-                                                  unsigned fields_kinds, hipStream_t stream);
-
 // The pieces the block scan listed in `work` ([0]: how many; room for work_slots): their group tables from the scan's records.
-extern "C" int hapgpu_launch_group_tables_from_records(HapGpuDecodeUnit *units, unsigned unit_count, const HapGpuDecodeJob *jobs,
-                                                       const uint32_t *work, unsigned work_slots, const void *recs, const void *joins,
-                                                       hipStream_t stream)
+int hapgpu_group_tables_from_records(HapGpuDecodeUnit *units, unsigned unit_count, const HapGpuDecodeJob *jobs,
+                                     const uint32_t *work, unsigned work_slots, const void *recs, const void *joins,
+                                     hipStream_t stream)
 {
     if (unit_count == 0 || work_slots == 0 || !work || !recs || !joins)
         return 0;
@@ -2305,11 +2308,12 @@ extern "C" int hapgpu_launch_group_tables_from_records(HapGpuDecodeUnit *units, 
 
 // Finds the 64 KiB blocks of the whole-stream units listed in `chunks` (see the block scan above) and writes their
 // BLOCK units; the decode launch that follows must include the stream kernel.
-extern "C" int hapgpu_launch_scan_blocks(HapGpuDecodeUnit *units, const HapGpuDecodeJob *jobs, HapGpuScanChunk *chunks,
-                                         unsigned chunk_count, HapGpuScanSegment *segs, void *recs, void *joins,
-                                         unsigned seg_total, uint32_t *fine_work, unsigned fine_first, unsigned fine_pool,
-                                         hipStream_t stream)
+extern "C" int hapgpu_k_scan_blocks(hapgpu_rt *rt, HapGpuDecodeUnit *units, const HapGpuDecodeJob *jobs, HapGpuScanChunk *chunks,
+                                    unsigned chunk_count, HapGpuScanSegment *segs, void *recs, void *joins, unsigned seg_total,
+                                    uint32_t *fine_work, unsigned fine_first, unsigned fine_pool)
 {
+    scoped_timing st(rt, 7);
+    const hipStream_t stream = hapgpu_rt_stream(rt);
     if (chunk_count == 0 || seg_total == 0)
         return 0;
     // (a single 8K frame is ~3 000 segments; the GPU holds 8 192 wavefronts)
@@ -2328,22 +2332,50 @@ extern "C" int hapgpu_launch_scan_blocks(HapGpuDecodeUnit *units, const HapGpuDe
     return hipGetLastError() == hipSuccess ? 0 : 4;
 }
 
-// scan_recs / scan_joins: what the block scan of THIS call left (hapgpu_launch_scan_blocks), or null; scan_blocks_hint: about
-// how many 64 KiB blocks its streams hold: few enough, and a workgroup each takes them first
-// (snappy_decode_block_resolve_kernel); resolved: a counter of the blocks that went through
-extern "C" int hapgpu_launch_snappy_decode(const HapGpuDecodeUnit *units, unsigned unit_count, HapGpuDecodeJob *jobs,
-                                           unsigned frag_log2, unsigned fragment_kinds, int any_stream_or_copy_units,
-                                           const uint32_t *fine_work, unsigned fine_slots, const void *scan_recs,
-                                           const void *scan_joins, const HapGpuScanChunk *scan_chunks, unsigned scan_chunk_count,
-                                           unsigned scan_blocks_hint, uint32_t *resolved, hipStream_t stream)
+// The 64 KiB-ring fragment kernels and the block-resolve kernel take more than 64 KiB of LDS: their function attributes,
+// and the settings of the stream and block launches below
+void hapgpu_prepare_snappy_decode(hapgpu_launch_settings *s)
 {
+    (void)hipFuncSetAttribute((const void *)snappy_decode_fragment_kernel<65536u, true, 1u>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + kFragmentTail);
+    (void)hipFuncSetAttribute((const void *)snappy_decode_fragment_kernel<65536u, false, 1u>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + kFragmentTail);
+    (void)hipFuncSetAttribute((const void *)snappy_decode_fragment_kernel<65536u, false, 2u>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + kFragmentTail);
+    (void)hipFuncSetAttribute((const void *)snappy_decode_fragment_kernel<65536u, false, 4u>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + kFragmentTail);
+    const char *e = HAP_AB_ENV("HAP_AMD_STREAM_RING_LOG2");
+    s->ring_log2_forced = e && atoi(e) >= 11 && atoi(e) <= 16 ? (unsigned)atoi(e) : 0u;
+    // A workgroup per 64 KiB block shortens the CALL -- a block takes 0.1 ms instead of 0.8 -- at about twice the work
+    // per block (the block scan's records are verified, the pointers jump) and with one workgroup per CU: it pays while
+    // the blocks are few enough for the wavefront-per-block kernel to leave most of the GPU idle.  Measured on an
+    // MI355X, decode kernels of a call, 8K frames of the reference encoder (528 blocks each): DXT5 1 frame 0.82 -> 0.26 ms,
+    // 2 frames 0.89 -> 0.49, 3 frames 0.95 -> 0.91, 4 frames 1.00 -> 1.21; Hap Q (more elements per block) 1 frame 0.38,
+    // 2 frames 0.68, 3 frames 1.11 against 1.12 for FOUR frames the other way: up to four blocks per CU (the host's
+    // estimate: what the scanned streams' textures hold).
+    e = HAP_AB_ENV("HAP_AMD_BLOCK_RESOLVE");
+    s->block_resolve = e ? atoi(e) : 1;
+    s->resolve_workgroups = s->cus ? s->cus : 256u;
+    s->resolve_max_units = s->block_resolve > 1 ? 0xFFFFFFFFu : 4u * s->resolve_workgroups;    // (> 1, measurement builds: every call)
+    if (hipFuncSetAttribute((const void *)snappy_decode_block_resolve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)sizeof(BrkLds)) != hipSuccess)
+        s->block_resolve = 0;
+}
+
+// scan: what the block scan of THIS call left (hapgpu_k_scan_blocks), or null; its blocks_hint: about how many 64 KiB
+// blocks its streams hold: few enough, and a workgroup each takes them first (snappy_decode_block_resolve_kernel), counted
+// in the runtime's resolved-block counter
+extern "C" int hapgpu_k_snappy_decode(hapgpu_rt *rt, const HapGpuDecodeUnit *units, unsigned unit_count,
+                                      HapGpuDecodeJob *jobs, unsigned frag_log2, unsigned fragment_kinds,
+                                      int any_stream_or_copy_units, const uint32_t *fine_work, unsigned fine_slots,
+                                      const HapGpuScanRecords *scan)
+{
+    scoped_timing st(rt, 5);
+    const hipStream_t stream = hapgpu_rt_stream(rt);
+    hapgpu_launch_settings *settings = hapgpu_rt_settings(rt);
     if (unit_count == 0)
         return 0;
     // field streams (fragment table version 3): the block-per-lane decoder of snappy_decode_fields.hip
     // (bit 12: the pre-pass may have turned 8 KiB pieces of scanned streams into such units: they lie behind the ordinary ones)
     if ((fragment_kinds >> 8) & 15u) {
-        if (hapgpu_launch_snappy_decode_fields(units, unit_count + (((fragment_kinds >> 12) & 1u) ? fine_slots : 0u), jobs,
-                                               (fragment_kinds >> 8) & 15u, stream) != 0)
+        if (hapgpu_snappy_decode_fields(units, unit_count + (((fragment_kinds >> 12) & 1u) ? fine_slots : 0u), jobs,
+                                        (fragment_kinds >> 8) & 15u, stream) != 0)
             return 4;
         fragment_kinds &= 0xFFu;
         if (fragment_kinds == 0u)
@@ -2352,64 +2384,29 @@ extern "C" int hapgpu_launch_snappy_decode(const HapGpuDecodeUnit *units, unsign
     if (any_stream_or_copy_units) {
         // any_stream_or_copy_units == 2: most units are 64 KiB blocks found by the block scan -- a 2 KiB ring (copies
         // from further back re-read the output from memory) lets 32 wavefronts share a CU instead of 4
-        static bool once = false;
-        static unsigned ring_forced = 0;
-        if (!once) {
-            (void)hipFuncSetAttribute((const void *)snappy_decode_fragment_kernel<65536u, true, 1u>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + kFragmentTail);
-            const char *e = HAP_AB_ENV("HAP_AMD_STREAM_RING_LOG2");
-            if (e && atoi(e) >= 11 && atoi(e) <= 16)
-                ring_forced = (unsigned)atoi(e);
-            once = true;
-        }
         // (3: every stream of the call is as short as one 8 KiB fragment -- fine chunks: thousands of short streams want
         // wavefronts per CU more than they want their whole output in the ring; 30 8K frames: 2.62 ms against 3.53 with an 8 KiB ring)
-        const unsigned ring_log2 = ring_forced ? ring_forced : (any_stream_or_copy_units == 2 || any_stream_or_copy_units == 3) ? 11u : 15u;
+        const unsigned ring_log2 = settings->ring_log2_forced ? settings->ring_log2_forced : (any_stream_or_copy_units == 2 || any_stream_or_copy_units == 3) ? 11u : 15u;
         // with the block scan: the 8 KiB blocks it listed first (phase 1, over the list's capacity: the count is on the
         // device), then the ordinary units (phase 2) -- a stream whose 8 KiB pieces turned out not to be independent is
         // decoded by its 64 KiB blocks or whole in the second launch
         const bool two = any_stream_or_copy_units == 2 && fine_work != nullptr && fine_slots != 0u;
-        // A workgroup per 64 KiB block shortens the CALL -- a block takes 0.1 ms instead of 0.8 -- at about twice the work
-        // per block (the block scan's records are verified, the pointers jump) and with one workgroup per CU: it pays while
-        // the blocks are few enough for the wavefront-per-block kernel to leave most of the GPU idle.  Measured on an
-        // MI355X, decode kernels of a call, 8K frames of the reference encoder (528 blocks each): DXT5 1 frame 0.82 -> 0.26 ms,
-        // 2 frames 0.89 -> 0.49, 3 frames 0.95 -> 0.91, 4 frames 1.00 -> 1.21; Hap Q (more elements per block) 1 frame 0.38,
-        // 2 frames 0.68, 3 frames 1.11 against 1.12 for FOUR frames the other way: up to four blocks per CU (the host's
-        // estimate: what the scanned streams' textures hold).
-        static int resolve_on = -1;
-        static unsigned resolve_max_units = 0, resolve_workgroups = 256u;
-        if (resolve_on < 0) {
-            const char *e = HAP_AB_ENV("HAP_AMD_BLOCK_RESOLVE");
-            int dev = 0;
-            hipDeviceProp_t prop;
-            resolve_on = e ? atoi(e) : 1;
-            resolve_max_units = 4u * 256u;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) {
-                resolve_workgroups = (unsigned)prop.multiProcessorCount;
-                resolve_max_units = 4u * resolve_workgroups;
-            }
-            if (resolve_on > 1)
-                resolve_max_units = 0xFFFFFFFFu;         // (measurement builds: every call)
-            if (hipFuncSetAttribute((const void *)snappy_decode_block_resolve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)sizeof(BrkLds)) != hipSuccess) {
-                (void)hipGetLastError();
-                resolve_on = 0;
-            }
-        }
+        uint32_t *const resolved = hapgpu_rt_resolved_counter(rt);
         for (unsigned phase = two ? 1u : any_stream_or_copy_units == 2 ? 2u : 0u; phase <= (any_stream_or_copy_units == 2 ? 2u : 0u); phase++) {
             const dim3 grid(phase == 1u ? fine_slots : unit_count);
             // the 64 KiB blocks of the scanned streams, a workgroup each -- after the 8 KiB pieces of phase 1 (whose failures
             // decide which units run), in front of the wavefront-per-unit launch that takes whatever is left
-            if (phase == 2u && resolve_on && scan_recs && scan_joins && scan_chunks && resolved && scan_chunk_count <= kBrkMaxStreams &&
-                scan_blocks_hint <= resolve_max_units) {
+            if (phase == 2u && settings->block_resolve && scan && scan->recs && scan->joins && scan->chunks && resolved &&
+                scan->chunk_count <= kBrkMaxStreams && scan->blocks_hint <= settings->resolve_max_units) {
                 // (resolved[0]: blocks that went through, ever; [1]: this launch's work counter)
                 (void)hipMemsetAsync(resolved + 1, 0, sizeof(uint32_t), stream);
-                hipLaunchKernelGGL(snappy_decode_block_resolve_kernel, dim3(resolve_workgroups), dim3(kBrkThreads), sizeof(BrkLds), stream,
-                                   const_cast<HapGpuDecodeUnit *>(units), unit_count, scan_chunks, scan_chunk_count, jobs,
-                                   (const unsigned long long *)scan_recs, (const uint4 *)scan_joins, resolved, resolved + 1);
+                hipLaunchKernelGGL(snappy_decode_block_resolve_kernel, dim3(settings->resolve_workgroups), dim3(kBrkThreads), sizeof(BrkLds),
+                                   stream, const_cast<HapGpuDecodeUnit *>(units), unit_count, scan->chunks, scan->chunk_count, jobs,
+                                   (const unsigned long long *)scan->recs, (const uint4 *)scan->joins, resolved, resolved + 1);
                 // (an accelerator only: a launch the runtime refuses -- 159 KiB of LDS is nearly all a CU has -- must not fail
                 // the call: the wavefront-per-block launch below decodes every block then, as it did before)
                 if (hipGetLastError() != hipSuccess)
-                    resolve_on = 0;
+                    settings->block_resolve = 0;
             }
             if (ring_log2 == 11)
                 hipLaunchKernelGGL((snappy_decode_fragment_kernel<2048u, true, 1u>), grid, dim3(64), 0, stream, units, grid.x, jobs, phase, fine_work);
@@ -2424,13 +2421,6 @@ extern "C" int hapgpu_launch_snappy_decode(const HapGpuDecodeUnit *units, unsign
             else
                 hipLaunchKernelGGL((snappy_decode_fragment_kernel<65536u, true, 1u>), grid, dim3(64), fragment_dynamic_lds(65536u), stream, units, grid.x, jobs, phase, fine_work);
         }
-    }
-    static bool once16 = false;
-    if (!once16 && frag_log2 == 16) {
-        (void)hipFuncSetAttribute((const void *)snappy_decode_fragment_kernel<65536u, false, 1u>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + kFragmentTail);
-        (void)hipFuncSetAttribute((const void *)snappy_decode_fragment_kernel<65536u, false, 2u>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + kFragmentTail);
-        (void)hipFuncSetAttribute((const void *)snappy_decode_fragment_kernel<65536u, false, 4u>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + kFragmentTail);
-        once16 = true;
     }
 #define HAP_LAUNCH_FRAGMENT(RINGBYTES)                                                                                          \
     do {                                                                                                                        \

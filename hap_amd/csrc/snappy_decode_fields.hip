@@ -44,7 +44,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
-#include "hapgpu_abi.h"
+#include "hapgpu_runtime.hpp"
 #include "measurement_guard.h"
 
 namespace {
@@ -53,7 +53,7 @@ constexpr unsigned kFragBytes = 8192u;
 constexpr unsigned kHalf = 128u;                       // bytes of output per half-tile
 constexpr unsigned kHalves = kFragBytes / kHalf;       // 64: one parse lane each
 constexpr unsigned kMaxFragCompressed = kFragBytes + 320u;
-constexpr int kGuessLdsBytes = 0;          // (see hapgpu_launch_guess_group_tables)
+constexpr int kGuessLdsBytes = 0;          // (see hapgpu_prepare_snappy_decode_fields)
 // Switches of the measurement builds (tools/build_variants.sh, which defines HAP_MEASUREMENT_BUILD and writes to
 // hap_amd/variants/; measurement_guard.h refuses them in any other build): LDS per wave up or down (occupancy
 // studies), the set of DPP hops, one layout's code alone.  None changes what the kernel writes.  (The ablations of
@@ -776,32 +776,40 @@ __global__ __launch_bounds__(64) void guess_group_tables_kernel(HapGpuDecodeUnit
 
 } // namespace
 
-// work == nullptr: every unit of the call is looked at (frames whose chunks are single fragments); else the `work_slots`
-// units the block scan may have listed in `work` (the count is on the device)
-extern "C" int hapgpu_launch_guess_group_tables(HapGpuDecodeUnit *units, unsigned unit_count, const HapGpuDecodeJob *jobs,
-                                                const uint32_t *work, unsigned work_slots, hipStream_t stream)
+// Every lane of guess_group_tables_kernel reads its own stream, a few bytes per turn: a wavefront's 64 lanes keep 64 cache
+// lines alive, and with sixteen wavefronts on a CU none of them survives in its 32 KiB L1 until the lane's next element
+// (every turn then comes from the L2).  Dynamic LDS the kernel never touches keeps the wavefronts per CU down to what the
+// L1 holds.
+void hapgpu_prepare_snappy_decode_fields(hapgpu_launch_settings *s)
 {
+    const char *e = HAP_AB_ENV("HAP_AMD_GUESS_LDS");
+    const int lds_bytes = e ? atoi(e) : kGuessLdsBytes;
+    s->guess_lds_bytes = lds_bytes > 65536 ? 65536u : (unsigned)lds_bytes;
+}
+
+// work == nullptr: every unit of the call is looked at (frames whose chunks are single fragments); else the `work_slots`
+// units the block scan may have listed in `work` (the count is on the device) -- from the scan's records when it left them
+extern "C" int hapgpu_k_guess_group_tables(hapgpu_rt *rt, HapGpuDecodeUnit *units, unsigned unit_count, const HapGpuDecodeJob *jobs,
+                                           const uint32_t *work, unsigned work_slots, const HapGpuScanRecords *scan)
+{
+    scoped_timing st(rt, 7);          // (with the block scan: finding where wavefronts may start in streams that do not say)
+    const hipStream_t stream = hapgpu_rt_stream(rt);
+    // the pieces the scan of this call listed: from its records, a wavefront per piece (r06); fragments that are chunks of
+    // their own (no scan): a lane per fragment walks it
+    if (work && scan && scan->recs && scan->joins)
+        return hapgpu_group_tables_from_records(units, unit_count, jobs, work, work_slots, scan->recs, scan->joins, stream);
     const unsigned lanes = work ? work_slots : unit_count;
     if (unit_count == 0 || lanes == 0)
         return 0;
-    // Every lane reads its own stream, a few bytes per turn: a wavefront's 64 lanes keep 64 cache lines alive, and with
-    // sixteen wavefronts on a CU none of them survives in its 32 KiB L1 until the lane's next element (every turn then
-    // comes from the L2).  Dynamic LDS the kernel never touches keeps the wavefronts per CU down to what the L1 holds.
-    static int lds_bytes = -1;
-    if (lds_bytes < 0) {
-        const char *e = HAP_AB_ENV("HAP_AMD_GUESS_LDS");
-        lds_bytes = e ? atoi(e) : kGuessLdsBytes;
-        if (lds_bytes > 65536)
-            lds_bytes = 65536;
-    }
-    hipLaunchKernelGGL(guess_group_tables_kernel, dim3((lanes + 63u) / 64u), dim3(64), (unsigned)lds_bytes, stream, units, unit_count, jobs, work);
+    hipLaunchKernelGGL(guess_group_tables_kernel, dim3((lanes + 63u) / 64u), dim3(64), hapgpu_rt_settings(rt)->guess_lds_bytes, stream,
+                       units, unit_count, jobs, work);
     return hipGetLastError() == hipSuccess ? 0 : 4;
 }
 
 // fields_kinds: bit 0 = [2, 6, 4, 4] units present (DXT5 / YCoCg-DXT5), bit 1 = [4, 4] units (DXT1), bit 2 = [2, 6] (RGTC1),
 // bit 3 = [4, 4, 4, 4] (opaque 16-byte blocks)
-extern "C" int hapgpu_launch_snappy_decode_fields(const HapGpuDecodeUnit *units, unsigned unit_count, HapGpuDecodeJob *jobs,
-                                                  unsigned fields_kinds, hipStream_t stream)
+int hapgpu_snappy_decode_fields(const HapGpuDecodeUnit *units, unsigned unit_count, HapGpuDecodeJob *jobs, unsigned fields_kinds,
+                                hipStream_t stream)
 {
     if (unit_count == 0)
         return 0;

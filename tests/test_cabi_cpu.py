@@ -335,6 +335,30 @@ def test_every_environment_switch_is_documented_and_tested():
     assert set(ENVIRONMENT_SWITCHES) == product, set(ENVIRONMENT_SWITCHES) ^ product
 
 
+def test_launch_state_is_per_runtime_and_declared_once():
+    """VERDICT r06 / ADVICE r06: no mutable function-local static in the native sources (what a launch depends on is a
+    setting of its runtime, fixed when the runtime is made), and extern "C" in a .hip file only in front of a function
+    definition (what hapgpu_abi.h declares): a hand-copied C prototype links whatever its arguments say."""
+    import glob
+    import re
+    csrc = os.path.join(ROOT, "hap_amd", "csrc")
+    statics, prototypes = [], []
+    for path in sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.c"))):
+        name = os.path.basename(path)
+        text = open(path).read()
+        for number, line in enumerate(text.splitlines(), 1):
+            if re.match(r"^\s+static\s", line) and not re.match(r"^\s+static\s+(const|constexpr|inline)\s", line):
+                statics.append("%s:%d" % (name, number))
+        if name.endswith(".hip"):
+            for m in re.finditer(r'extern\s+"C"', text):
+                rest = text[m.end():]
+                brace, semicolon = rest.find("{"), rest.find(";")
+                if rest.lstrip().startswith("{") or brace < 0 or (0 <= semicolon < brace):
+                    prototypes.append("%s:%d" % (name, text.count("\n", 0, m.start()) + 1))
+    assert statics == [], statics
+    assert prototypes == [], prototypes
+
+
 def test_round5_entry_points_without_a_gpu(hap):
     """The integer side of the round-5 additions needs no GPU: HapGpuFineChunkCount is hap.c:277-300's limiting of
     bytes / 8 KiB chunks to a divisor of the block count (0 for arguments HapEncode would refuse), and the

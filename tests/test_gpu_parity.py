@@ -2611,6 +2611,25 @@ def test_a_batch_dealt_out_over_several_contexts_gives_the_single_context_bytes(
                 assert torch.equal(x, y)
                 want = D.oracle_bc_encode(pics[i].cpu().numpy(), fmts[index])
                 assert x.cpu().numpy().tobytes() == want
+    # frames of another encoder, one per context: every context decodes its frame's 64 KiB blocks by a workgroup each
+    # (launch settings are the context's own: one context's state cannot switch another's off)
+    rw, rh, rfmt, rchunks = 2048, 1024, L.FMT_DXT5, 1
+    _name, api = CHECKERS[-1]
+    texs = [D.oracle_bc_encode(D.rgba(rw, rh, frame=17 + i), rfmt) for i in range(n_ctx)]
+    rframes = []
+    for tex in texs:
+        r, frame = api.encode([tex], [rfmt], [1], [rchunks])
+        assert r == 0
+        rframes.append(torch.from_numpy(np.frombuffer(frame, dtype=np.uint8).copy()).cuda())
+    blocks = [rchunks * ((len(tex) // rchunks + 65535) // 65536) for tex in texs]
+    routs = [torch.full((len(tex),), 0x5A, dtype=torch.uint8, device="cuda") for tex in texs]
+    n0 = [c.resolved_blocks() for c in ctxs]
+    torch.cuda.synchronize()
+    r, du, df, dr = hap.decode_frames_on_devices(ctxs, rframes, [len(f) for f in rframes], 0, routs)
+    assert (r, du, df, dr) == (0, [len(t) for t in texs], [rfmt] * n_ctx, [0] * n_ctx)
+    for out, tex in zip(routs, texs):
+        assert out.cpu().numpy().tobytes() == tex
+    assert [c.resolved_blocks() - n for c, n in zip(ctxs, n0)] == blocks
     # fewer frames than contexts, and none
     r, u2, r2 = hap.encode_frames_rgba_on_devices(ctxs, pics[:1], w, h, w * 4, fmts, [1, 1], chunks, outsn[:1], flags=hap.ENCODE_FRAGMENT_INDEX)
     assert (r, u2, r2) == (0, used1[:1], [0])
