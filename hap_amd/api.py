@@ -35,6 +35,7 @@ DECODE_IGNORE_HALF_TILES = 0x2
 DECODE_NO_BLOCK_SCAN = 0x4
 DECODE_NO_FIELD_GUESS = 0x8
 DECODE_GUESS_FIELDS = 0x10
+DECODE_BPTC_PICTURES = 0x20
 KERNEL_CLASSES = ["block_encode", "snappy_compress", "frame_pack", "frame_gather", "decode_plan", "snappy_decode",
                   "block_decode", "block_scan", "encode_fused"]
 

@@ -280,7 +280,8 @@ void launch(const void *blocks, const void *alpha, unsigned bx, unsigned by, voi
 
 } // namespace
 
-// format: HapTextureFormat of `blocks` (DXT1, DXT5, YCoCg-DXT5); alpha: optional RGTC1 plane.
+// format: HapTextureFormat of `blocks` (DXT1, DXT5, YCoCg-DXT5, BC7 -- bptc_decode.hip); alpha: optional RGTC1 plane
+// (not with BC7).
 // Returns 0 launched, 1 bad arguments.
 extern "C" int hapgpu_k_block_decode(hapgpu_rt *rt, const void *blocks, const void *alpha, unsigned width, unsigned height,
                                      unsigned format, void *rgba, size_t row_bytes)
@@ -298,6 +299,11 @@ extern "C" int hapgpu_k_block_decode(hapgpu_rt *rt, const void *blocks, const vo
     case 0x83F0: launch<0>(blocks, alpha, bx, by, rgba, row_bytes, stream); break;
     case 0x83F3: launch<1>(blocks, alpha, bx, by, rgba, row_bytes, stream); break;
     case 0x01: launch<2>(blocks, alpha, bx, by, rgba, row_bytes, stream); break;
+    case 0x8E8C:
+        if (alpha)
+            return 1;
+        hapgpu_bptc_decode(blocks, bx, by, rgba, row_bytes, stream);
+        break;
     default: return 1;
     }
     return hipGetLastError() == hipSuccess ? 0 : 4;
@@ -319,6 +325,11 @@ extern "C" int hapgpu_k_block_decode_batch(hapgpu_rt *rt, const uint64_t *table,
     case 0x83F0: launch_batch<0>(table, pictures, with_alpha != 0, bx, by, row_bytes, stream); break;
     case 0x83F3: launch_batch<1>(table, pictures, with_alpha != 0, bx, by, row_bytes, stream); break;
     case 0x01: launch_batch<2>(table, pictures, with_alpha != 0, bx, by, row_bytes, stream); break;
+    case 0x8E8C:
+        if (with_alpha)
+            return 1;
+        hapgpu_bptc_decode_batch(table, pictures, bx, by, row_bytes, stream);
+        break;
     default: return 1;
     }
     return hipGetLastError() == hipSuccess ? 0 : 4;

@@ -1,0 +1,232 @@
+// bptc_decode.hip -- BC7 (RGBA_BPTC_UNORM, Hap R) -> RGBA8 for gfx950.
+//
+// Same shape as bc_decode.hip: one 4x4 block per lane, one 16-byte block load per lane, four 16-byte streaming row
+// stores per lane; 16 B read + 64 B written per block.  Semantics: the BPTC definition the Hap spec cites
+// (ARB_texture_compression_bptc / the BC7 section of the Khronos Data Format Specification); reserved blocks (no mode
+// bit in the first byte) decode to (0, 0, 0, 0).
+//
+// Real BC7 content mixes modes inside every wavefront, so there is no switch on the mode: every lane runs the same
+// straight-line code, driven by its mode's descriptor.  Each descriptor field is a nibble of a 32-bit constant (one
+// v_bfe_u32 per field), every field of the block is read at a lane-varying bit offset with v_alignbit_b32 on a dword
+// pair picked by selects, a texel's subset comes from one partition dword (2 bits per texel) and its index position is
+// worked out from the anchors.  Per-lane arrays are only ever indexed by unrolled constants (endpoints, weight tables
+// picked with v_perm_b32), so nothing goes to scratch.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "hapgpu_runtime.hpp"
+
+namespace {
+
+// descriptor fields of modes 0..7, mode m in nibble m
+constexpr unsigned D_SUBSETS = 0x21112323u;   // 3 2 3 2 1 1 1 2
+constexpr unsigned D_PART_BITS = 0x60006664u; // 4 6 6 6 0 0 0 6
+constexpr unsigned D_COLOUR_BITS = 0x57757564u; // 4 6 5 7 5 7 7 5
+constexpr unsigned D_ALPHA_BITS = 0x57860000u;  // 0 0 0 0 6 8 7 5
+constexpr unsigned D_EPB = 0x11001001u;         // endpoint p-bits: modes 0, 3, 6, 7
+constexpr unsigned D_SPB = 0x00000010u;         // shared p-bits: mode 1
+constexpr unsigned D_INDEX_BITS = 0x24222233u;  // 3 3 2 2 2 2 4 2
+constexpr unsigned D_INDEX2_BITS = 0x00230000u; // 0 0 0 0 3 2 0 0
+
+__device__ __forceinline__ unsigned field(unsigned desc, unsigned mode) { return __builtin_amdgcn_ubfe(desc, 4u * mode, 4u); }
+
+// 2 bits per texel: the 64 two-subset partitions (subset 0 / 1), then the 64 three-subset ones
+__constant__ uint32_t k_partitions[128] = {
+    0x50505050u, 0x40404040u, 0x54545454u, 0x54505040u, 0x50404000u, 0x55545450u, 0x55545040u, 0x54504000u,
+    0x50400000u, 0x55555450u, 0x55544000u, 0x54400000u, 0x55555440u, 0x55550000u, 0x55555500u, 0x55000000u,
+    0x55150100u, 0x00004054u, 0x15010000u, 0x00405054u, 0x00004050u, 0x15050100u, 0x05010000u, 0x40505054u,
+    0x00404050u, 0x05010100u, 0x14141414u, 0x05141450u, 0x01155440u, 0x00555500u, 0x15014054u, 0x05414150u,
+    0x44444444u, 0x55005500u, 0x11441144u, 0x05055050u, 0x05500550u, 0x11114444u, 0x41144114u, 0x44111144u,
+    0x15055054u, 0x01055040u, 0x05041050u, 0x05455150u, 0x14414114u, 0x50050550u, 0x41411414u, 0x00141400u,
+    0x00041504u, 0x00105410u, 0x10541000u, 0x04150400u, 0x50410514u, 0x41051450u, 0x05415014u, 0x14054150u,
+    0x41050514u, 0x41505014u, 0x40011554u, 0x54150140u, 0x50505500u, 0x00555050u, 0x15151010u, 0x54540404u,
+    0xAA685050u, 0x6A5A5040u, 0x5A5A4200u, 0x5450A0A8u, 0xA5A50000u, 0xA0A05050u, 0x5555A0A0u, 0x5A5A5050u,
+    0xAA550000u, 0xAA555500u, 0xAAAA5500u, 0x90909090u, 0x94949494u, 0xA4A4A4A4u, 0xA9A59450u, 0x2A0A4250u,
+    0xA5945040u, 0x0A425054u, 0xA5A5A500u, 0x55A0A0A0u, 0xA8A85454u, 0x6A6A4040u, 0xA4A45000u, 0x1A1A0500u,
+    0x0050A4A4u, 0xAAA59090u, 0x14696914u, 0x69691400u, 0xA08585A0u, 0xAA821414u, 0x50A4A450u, 0x6A5A0200u,
+    0xA9A58000u, 0x5090A0A8u, 0xA8A09050u, 0x24242424u, 0x00AA5500u, 0x24924924u, 0x24499224u, 0x50A50A50u,
+    0x500AA550u, 0xAAAA4444u, 0x66660000u, 0xA5A0A5A0u, 0x50A050A0u, 0x69286928u, 0x44AAAA44u, 0x66666600u,
+    0xAA444444u, 0x54A854A8u, 0x95809580u, 0x96969600u, 0xA85454A8u, 0x80959580u, 0xAA141414u, 0x96960000u,
+    0xAAAA1414u, 0xA05050A0u, 0xA0A5A5A0u, 0x96000000u, 0x40804080u, 0xA9A8A9A8u, 0xAAAAAA44u, 0x2A4A5254u,
+};
+
+// anchor texels: subset 1 in the low nibble, subset 2 in the high one (0 where the partition has no such subset: texel 0
+// is subset 0's anchor anyway)
+__constant__ uint8_t k_anchors[128] = {
+    0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F,
+    0x0F, 0x02, 0x08, 0x02, 0x02, 0x08, 0x08, 0x0F, 0x02, 0x08, 0x02, 0x02, 0x08, 0x08, 0x02, 0x02,
+    0x0F, 0x0F, 0x06, 0x08, 0x02, 0x08, 0x0F, 0x0F, 0x02, 0x08, 0x02, 0x02, 0x02, 0x0F, 0x0F, 0x06,
+    0x06, 0x02, 0x06, 0x08, 0x0F, 0x0F, 0x02, 0x02, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x02, 0x02, 0x0F,
+    0xF3, 0x83, 0x8F, 0x3F, 0xF8, 0xF3, 0x3F, 0x8F, 0xF8, 0xF8, 0xF6, 0xF6, 0xF6, 0xF5, 0xF3, 0x83,
+    0xF3, 0x83, 0xF8, 0x3F, 0xF3, 0x83, 0xF6, 0x8A, 0x35, 0xF8, 0x68, 0xA6, 0xF8, 0xF5, 0xAF, 0x8F,
+    0xF8, 0x3F, 0xF3, 0xA5, 0xA6, 0x8A, 0x98, 0xAF, 0x6F, 0xF3, 0x8F, 0xF5, 0x3F, 0x6F, 0x6F, 0x8F,
+    0xF3, 0x3F, 0xF5, 0xF5, 0xF5, 0xF8, 0xF5, 0xFA, 0xF5, 0xFA, 0xF8, 0xFD, 0x3F, 0xFC, 0xF3, 0x83,
+};
+
+// 32 bits of the 128-bit block q0..q3 starting at bit `off` (0..127; bits past the block read as zero)
+__device__ __forceinline__ unsigned bits_at(uint4 q, unsigned off)
+{
+    const unsigned d = off >> 5;
+    const unsigned lo = d == 0u ? q.x : d == 1u ? q.y : d == 2u ? q.z : d == 3u ? q.w : 0u;
+    const unsigned hi = d == 0u ? q.y : d == 1u ? q.z : d == 2u ? q.w : 0u;
+    return __builtin_amdgcn_alignbit(hi, lo, off & 31u);
+}
+
+// the 8-bit endpoint of a `bits`-bit value (p-bit already appended): MSB to bit 7, top bits copied into the low bits
+__device__ __forceinline__ unsigned unquantize(unsigned v, unsigned bits)
+{
+    v <<= 8u - bits;
+    return v | (v >> bits);
+}
+
+// weight of index `i` from a 16-byte table t0..t3
+__device__ __forceinline__ unsigned weight(uint4 t, unsigned i)
+{
+    const unsigned lo = __builtin_amdgcn_perm(t.y, t.x, i & 7u), hi = __builtin_amdgcn_perm(t.w, t.z, i & 7u);
+    return (i & 8u ? hi : lo) & 0xFFu;
+}
+
+// weight tables of 2, 3 and 4 index bits, one byte per entry
+__device__ __forceinline__ uint4 weight_table(unsigned bits)
+{
+    const uint4 w2 = make_uint4(0x402B1500u, 0u, 0u, 0u);
+    const uint4 w3 = make_uint4(0x1B120900u, 0x40372E25u, 0u, 0u);
+    const uint4 w4 = make_uint4(0x0D090400u, 0x1E1A1511u, 0x2F2B2622u, 0x403C3733u);
+    return bits == 2u ? w2 : bits == 3u ? w3 : w4;
+}
+
+typedef unsigned short pk_u16 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ pk_u16 as_pk(unsigned v) { return __builtin_bit_cast(pk_u16, v); }
+__device__ __forceinline__ unsigned as_u32(pk_u16 v) { return __builtin_bit_cast(unsigned, v); }
+
+__device__ __forceinline__ void bptc_decode_body(const uint8_t *__restrict__ blocks, unsigned blocks_x,
+                                                 unsigned blocks_total, uint8_t *__restrict__ rgba, size_t row_bytes)
+{
+    const unsigned id = blockIdx.x * 256u + threadIdx.x;
+    if (id >= blocks_total)
+        return;
+    const unsigned by = id / blocks_x, bx = id - by * blocks_x;
+    const uint4 q = *reinterpret_cast<const uint4 *>(blocks + (size_t)id * 16u);
+
+    // ---- the mode and its descriptor
+    const unsigned mode_raw = __builtin_ctz(q.x | 0x100u);          // 8: reserved block
+    const bool reserved = mode_raw == 8u;
+    const unsigned mode = reserved ? 0u : mode_raw;
+    const unsigned ns = field(D_SUBSETS, mode);
+    const unsigned pb = field(D_PART_BITS, mode);
+    const unsigned cb = field(D_COLOUR_BITS, mode);
+    const unsigned ab = field(D_ALPHA_BITS, mode);
+    const unsigned epb = field(D_EPB, mode), spb = field(D_SPB, mode);
+    const unsigned ib = field(D_INDEX_BITS, mode), ib2 = field(D_INDEX2_BITS, mode);
+    const unsigned rb = ib2 ? 2u : 0u;                               // rotation bits: modes 4 and 5
+    const unsigned isb = ib2 == 3u ? 1u : 0u;                        // index-selection bit: mode 4
+    const unsigned after_mode = __builtin_amdgcn_ubfe(q.x, mode + 1u, 8u);
+    const unsigned partition = after_mode & ((1u << pb) - 1u);
+    const unsigned rotation = __builtin_amdgcn_ubfe(after_mode, 0u, rb);
+    const unsigned selection = __builtin_amdgcn_ubfe(after_mode, 2u, isb);
+
+    // ---- endpoints: per channel all 2 * ns values in one window (at most 30 bits), then the p-bits
+    const unsigned ne = 2u * ns;
+    const unsigned ends_at = mode + 1u + pb + rb + isb;
+    const unsigned cwin = ne * cb;
+    const unsigned win_r = bits_at(q, ends_at), win_g = bits_at(q, ends_at + cwin), win_b = bits_at(q, ends_at + 2u * cwin);
+    const unsigned win_a = bits_at(q, ends_at + 3u * cwin);
+    const unsigned pbits_at = ends_at + ne * (3u * cb + ab);
+    const unsigned win_p = bits_at(q, pbits_at);
+    const unsigned has_p = epb | spb;
+    const unsigned cbits = cb + has_p, abits = ab + (ab ? has_p : 0u);
+    // endpoint e of subset s is endpoint 2s + e; packed as 16-bit pairs (R | G << 16, B | A << 16)
+    unsigned e_rg[6], e_ba[6];
+#pragma unroll
+    for (unsigned j = 0; j < 6u; j++) {
+        const unsigned p = (win_p >> (spb ? (j >> 1) : j)) & has_p;
+        const unsigned r = unquantize((__builtin_amdgcn_ubfe(win_r, j * cb, cb) << has_p) | p, cbits);
+        const unsigned g = unquantize((__builtin_amdgcn_ubfe(win_g, j * cb, cb) << has_p) | p, cbits);
+        const unsigned b = unquantize((__builtin_amdgcn_ubfe(win_b, j * cb, cb) << has_p) | p, cbits);
+        const unsigned a = ab ? unquantize((__builtin_amdgcn_ubfe(win_a, j * ab, ab) << has_p) | p, abits) : 255u;
+        e_rg[j] = r | (g << 16);
+        e_ba[j] = b | (a << 16);
+    }
+
+    // ---- partition map and anchors
+    const unsigned table_index = ((ns == 3u ? 64u : 0u) + partition) & 127u;
+    const unsigned map = ns == 1u ? 0u : k_partitions[table_index];
+    const unsigned anchors = ns == 1u ? 0u : (unsigned)k_anchors[table_index];
+    const unsigned anchor_mask = 1u | (1u << (anchors & 15u)) | (1u << (anchors >> 4));   // bit t: texel t is an anchor
+
+    // ---- index windows: 64 bits from the first index bit of each index set
+    const unsigned idx1_at = 128u - (16u * ib - ns) - (ib2 ? 16u * ib2 - 1u : 0u);
+    const unsigned idx2_at = idx1_at + 16u * ib - ns;
+    const uint64_t x1 = (uint64_t)bits_at(q, idx1_at) | ((uint64_t)bits_at(q, idx1_at + 32u) << 32);
+    const uint64_t x2 = (uint64_t)bits_at(q, idx2_at) | ((uint64_t)bits_at(q, idx2_at + 32u) << 32);
+    const unsigned m1 = (1u << ib) - 1u, m2 = (1u << ib2) - 1u;
+    // colour and alpha: which index set and which weight table (mode 4's selection bit swaps the two sets)
+    const unsigned c_bits = selection ? ib2 : ib, a_bits = ib2 ? (selection ? ib : ib2) : ib;
+    const uint4 wc_table = weight_table(c_bits), wa_table = weight_table(a_bits);
+    // final byte order: R G B A gathered from (R | G << 16, B | A << 16) and the rotation's swap; zeros if reserved
+    const unsigned base_sel = rotation == 0u ? 0x06040200u : rotation == 1u ? 0x00040206u : rotation == 2u ? 0x02040600u : 0x04060200u;
+    const unsigned out_sel = reserved ? 0x0C0C0C0Cu : base_sel;
+
+    uint8_t *dst = rgba + (size_t)(4u * by) * row_bytes + 16u * (size_t)bx;
+    typedef unsigned v4u __attribute__((ext_vector_type(4)));
+#pragma unroll
+    for (unsigned r = 0; r < 4u; r++) {
+        unsigned px[4];
+#pragma unroll
+        for (unsigned c = 0; c < 4u; c++) {
+            const unsigned t = 4u * r + c;
+            const unsigned before = (unsigned)__builtin_popcount(anchor_mask & ((1u << t) - 1u));
+            const unsigned anchor = (anchor_mask >> t) & 1u;
+            const unsigned i1 = (unsigned)(x1 >> (t * ib - before)) & (m1 >> anchor);
+            const unsigned i2 = (unsigned)(x2 >> ((t * ib2 - (t ? 1u : 0u)) & 63u)) & (m2 >> (t ? 0u : 1u));   // (unused without ib2)
+            const unsigned ic = selection ? i2 : i1, ia = ib2 ? (selection ? i1 : i2) : i1;
+            const unsigned wc = weight(wc_table, ic), wa = weight(wa_table, ia);
+            const unsigned s = (map >> (2u * t)) & 3u;
+            const unsigned e0rg = s == 0u ? e_rg[0] : s == 1u ? e_rg[2] : e_rg[4];
+            const unsigned e1rg = s == 0u ? e_rg[1] : s == 1u ? e_rg[3] : e_rg[5];
+            const unsigned e0ba = s == 0u ? e_ba[0] : s == 1u ? e_ba[2] : e_ba[4];
+            const unsigned e1ba = s == 0u ? e_ba[1] : s == 1u ? e_ba[3] : e_ba[5];
+            // ((64 - w) * e0 + w * e1 + 32) >> 6 on two channels at once (at most 16352: no 16-bit overflow)
+            const pk_u16 w_rg = as_pk(wc * 0x10001u), w_ba = as_pk(wc | (wa << 16));
+            const pk_u16 k64 = {64, 64}, k32 = {32, 32}, k6 = {6, 6};
+            const pk_u16 rg = ((k64 - w_rg) * as_pk(e0rg) + w_rg * as_pk(e1rg) + k32) >> k6;
+            const pk_u16 ba = ((k64 - w_ba) * as_pk(e0ba) + w_ba * as_pk(e1ba) + k32) >> k6;
+            px[c] = __builtin_amdgcn_perm(as_u32(ba), as_u32(rg), out_sel);
+        }
+        const v4u v = {px[0], px[1], px[2], px[3]};
+        __builtin_nontemporal_store(v, reinterpret_cast<v4u *>(dst + (size_t)r * row_bytes));
+    }
+}
+
+__global__ __launch_bounds__(256) void bptc_decode_kernel(const uint8_t *__restrict__ blocks, unsigned blocks_x,
+                                                          unsigned blocks_total, uint8_t *__restrict__ rgba, size_t row_bytes)
+{
+    bptc_decode_body(blocks, blocks_x, blocks_total, rgba, row_bytes);
+}
+
+// pictures of one geometry in one launch: the [textures][alpha planes][pictures] table of bc_decode_batch_kernel (the
+// alpha column unused); texture address 0 = not this launch's format: skip
+__global__ __launch_bounds__(256) void bptc_decode_batch_kernel(const uint64_t *__restrict__ table, unsigned pictures,
+                                                                unsigned blocks_x, unsigned blocks_total, size_t row_bytes)
+{
+    const uint8_t *blocks = (const uint8_t *)table[blockIdx.z];
+    if (!blocks)
+        return;
+    bptc_decode_body(blocks, blocks_x, blocks_total, (uint8_t *)table[2u * pictures + blockIdx.z], row_bytes);
+}
+
+} // namespace
+
+void hapgpu_bptc_decode(const void *blocks, unsigned bx, unsigned by, void *rgba, size_t row_bytes, hipStream_t stream)
+{
+    const unsigned total = bx * by;
+    hipLaunchKernelGGL(bptc_decode_kernel, dim3((total + 255u) / 256u), dim3(256), 0, stream, (const uint8_t *)blocks, bx,
+                       total, (uint8_t *)rgba, row_bytes);
+}
+
+void hapgpu_bptc_decode_batch(const uint64_t *table, unsigned pictures, unsigned bx, unsigned by, size_t row_bytes,
+                              hipStream_t stream)
+{
+    const unsigned total = bx * by;
+    hipLaunchKernelGGL(bptc_decode_batch_kernel, dim3((total + 255u) / 256u, 1, pictures), dim3(256), 0, stream, table,
+                       pictures, bx, total, row_bytes);
+}

@@ -771,7 +771,8 @@ unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned 
     if (!texture || !rgba || width == 0 || height == 0 || (width & 3u) || (height & 3u) ||
         row_bytes < (unsigned long)width * 4ul ||
         (format != HapTextureFormat_RGB_DXT1 && format != HapTextureFormat_RGBA_DXT5 &&
-         format != HapTextureFormat_YCoCg_DXT5))
+         format != HapTextureFormat_YCoCg_DXT5 && format != HapTextureFormat_RGBA_BPTC_UNORM) ||
+        (alpha && format == HapTextureFormat_RGBA_BPTC_UNORM))
         return HapResult_Bad_Arguments;
     need = (size_t)(width / 4u) * (height / 4u) * block;
     alpha_need = (size_t)(width / 4u) * (height / 4u) * 8u;
@@ -1769,6 +1770,7 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
     unsigned long *in_bytes, *caps, *used;
     void **outs;
     unsigned *idx, *fmts, *res;
+    const int bptc = (flags & HAPGPU_DECODE_BPTC_PICTURES) != 0;
     if (frame_count == 0)
         return HapResult_No_Error;
     if (!results)
@@ -1830,13 +1832,15 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                 fmts[e] = 0;
             }
         ctx->decode_indices = idx;
-        hapb_decode(ctx, n * texture_count, in, in_bytes, 0, outs, caps, used, fmts, res, flags, NULL, NULL);
+        hapb_decode(ctx, n * texture_count, in, in_bytes, 0, outs, caps, used, fmts, res, flags & ~HAPGPU_DECODE_BPTC_PICTURES,
+                    NULL, NULL);
         {
             /* one block-decode launch per texture format present in the slice: [textures][alpha planes][pictures] in a
                small device table, pictures of other formats (or that failed) with a texture address of 0 */
-            uint64_t *htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, sizeof(uint64_t) * 9u * n);
-            uint64_t *dtab = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, sizeof(uint64_t) * 9u * n);
-            static const unsigned kinds[3] = {HapTextureFormat_RGB_DXT1, HapTextureFormat_RGBA_DXT5, HapTextureFormat_YCoCg_DXT5};
+            uint64_t *htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, sizeof(uint64_t) * 12u * n);
+            uint64_t *dtab = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, sizeof(uint64_t) * 12u * n);
+            static const unsigned kinds[4] = {HapTextureFormat_RGB_DXT1, HapTextureFormat_RGBA_DXT5, HapTextureFormat_YCoCg_DXT5,
+                                              HapTextureFormat_RGBA_BPTC_UNORM};
             unsigned present = 0, k;
             if (!htab || !dtab) {
                 for (f = 0; f < n; f++)
@@ -1844,7 +1848,7 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                 first_error = first_error ? first_error : HapResult_Internal_Error;
                 continue;
             }
-            memset(htab, 0, sizeof(uint64_t) * 9u * n);
+            memset(htab, 0, sizeof(uint64_t) * 12u * n);
             for (f = 0; f < n; f++) {
                 const size_t e = (size_t)f * texture_count;
                 const unsigned fmt = fmts[e];
@@ -1852,12 +1856,17 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                 unsigned r = res[e];
                 if (r == HapResult_No_Error && texture_count == 2)
                     r = res[e + 1];
+                /* (no Hap variant pairs a BC7 texture with a second one) */
+                if (bptc && texture_count == 2 && res[e] == HapResult_No_Error && fmt == HapTextureFormat_RGBA_BPTC_UNORM)
+                    r = HapResult_Bad_Arguments;
                 if (r == HapResult_No_Error && !dst)
                     r = HapResult_Bad_Arguments;
-                /* the frame must hold what the caller's geometry says: a colour texture the block decoder knows, of
-                   exactly width x height, and (two textures) an RGTC1 plane of the same geometry */
+                /* the frame must hold what the caller's geometry says: a colour texture the block decoder knows (BC7
+                   only when the caller asked for Hap R pictures), of exactly width x height, and (two textures) an RGTC1
+                   plane of the same geometry */
                 if (r == HapResult_No_Error &&
-                    ((fmt != HapTextureFormat_RGB_DXT1 && fmt != HapTextureFormat_RGBA_DXT5 && fmt != HapTextureFormat_YCoCg_DXT5) ||
+                    ((fmt != HapTextureFormat_RGB_DXT1 && fmt != HapTextureFormat_RGBA_DXT5 && fmt != HapTextureFormat_YCoCg_DXT5 &&
+                      !(bptc && fmt == HapTextureFormat_RGBA_BPTC_UNORM)) ||
                      used[e] != blocks * (fmt == HapTextureFormat_RGB_DXT1 ? 8u : 16u) ||
                      (texture_count == 2 && (fmts[e + 1] != HapTextureFormat_A_RGTC1 || used[e + 1] != blocks * 8u))))
                     r = HapResult_Bad_Arguments;
@@ -1871,7 +1880,8 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                     r = HapResult_Bad_Arguments;
                 }
                 if (r == HapResult_No_Error) {
-                    k = fmt == HapTextureFormat_RGB_DXT1 ? 0u : fmt == HapTextureFormat_RGBA_DXT5 ? 1u : 2u;
+                    k = fmt == HapTextureFormat_RGB_DXT1 ? 0u : fmt == HapTextureFormat_RGBA_DXT5 ? 1u :
+                        fmt == HapTextureFormat_YCoCg_DXT5 ? 2u : 3u;
                     present |= 1u << k;
                     htab[(size_t)k * 3u * n + f] = (uint64_t)(uintptr_t)outs[e];
                     htab[(size_t)k * 3u * n + n + f] = texture_count == 2 ? (uint64_t)(uintptr_t)outs[e + 1] : 0u;
@@ -1880,8 +1890,8 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                 results[done + f] = r;
             }
             if (present) {
-                rc |= hapgpu_rt_h2d(rt, dtab, htab, sizeof(uint64_t) * 9u * n);
-                for (k = 0; k < 3u; k++)
+                rc |= hapgpu_rt_h2d(rt, dtab, htab, sizeof(uint64_t) * 12u * n);
+                for (k = 0; k < 4u; k++)
                     if (present & (1u << k))
                         rc |= hapgpu_k_block_decode_batch(rt, dtab + (size_t)k * 3u * n, n, texture_count == 2, width, height, kinds[k],
                                                           row_bytes);

@@ -52,6 +52,10 @@ int hapgpu_snappy_compress_blocks(const HapGpuFrameEnc *frames, unsigned frame_c
 // snappy_decode_fields.hip
 int hapgpu_snappy_decode_fields(const HapGpuDecodeUnit *units, unsigned unit_count, HapGpuDecodeJob *jobs,
                                 unsigned fields_kinds, hipStream_t stream);
+// bptc_decode.hip: BC7 -> RGBA8 (one picture; pictures of one geometry from a bc_decode_batch_kernel table)
+void hapgpu_bptc_decode(const void *blocks, unsigned bx, unsigned by, void *rgba, size_t row_bytes, hipStream_t stream);
+void hapgpu_bptc_decode_batch(const uint64_t *table, unsigned pictures, unsigned bx, unsigned by, size_t row_bytes,
+                              hipStream_t stream);
 // snappy_decode.hip
 int hapgpu_group_tables_from_records(HapGpuDecodeUnit *units, unsigned unit_count, const HapGpuDecodeJob *jobs,
                                      const uint32_t *work, unsigned work_slots, const void *recs, const void *joins,

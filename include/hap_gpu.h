@@ -106,6 +106,11 @@ typedef struct HapGpuContext HapGpuContext;
 #define HAPGPU_DECODE_NO_BLOCK_SCAN 0x4u         /* decode other encoders' Snappy streams with one wavefront per
                                                     stream instead of looking for their 64 KiB blocks first: for A/B
                                                     measurements (environment HAP_AMD_NO_BLOCK_SCAN does the same) */
+#define HAPGPU_DECODE_BPTC_PICTURES 0x20u        /* HapGpuDecodeFramesRGBA only: Hap R frames (one BC7 texture) become
+                                                    pictures too.  Without it they are Bad_Arguments, as they were before
+                                                    BC7 could be expanded here -- clients that send Hap R down a path of
+                                                    their own on that result keep working; pass the flag to get the
+                                                    pixels instead.  Ignored by the other decode calls. */
 
 /* Creates a context on HIP device `device` (-1: the current device) with its
  * own non-blocking stream and growable scratch.  Returns a HapResult. */
@@ -164,8 +169,10 @@ unsigned int HapGpuCompressRGBA(HapGpuContext *context,
                                 unsigned long *outputBytesUsed);
 
 /* Block-compressed texture -> RGBA8 (the stage a GPU's texture unit performs for the reference's
- * clients; CDNA has none).  textureFormat: RGB_DXT1, RGBA_DXT5 or YCoCg_DXT5 (converted back to
- * RGB); alphaTexture: optional A_RGTC1 plane that supplies A (Hap Q Alpha), else NULL / 0.
+ * clients; CDNA has none).  textureFormat: RGB_DXT1, RGBA_DXT5, YCoCg_DXT5 (converted back to
+ * RGB) or RGBA_BPTC_UNORM (BC7, Hap R: all eight modes; reserved blocks give (0, 0, 0, 0));
+ * alphaTexture: optional A_RGTC1 plane that supplies A (Hap Q Alpha), else NULL / 0 -- Bad_Arguments
+ * with BC7.  Device textures of 16-byte blocks must be 16-byte aligned, DXT1 ones 8-byte aligned.
  * rgba must be 16-byte aligned with rowBytes a multiple of 16.  Host or device pointers. */
 unsigned int HapGpuDecompressRGBA(HapGpuContext *context,
                                   const void *texture, unsigned long textureBytes, unsigned int textureFormat,
@@ -290,8 +297,11 @@ unsigned int HapGpuDecodeFrameTextures(HapGpuContext *context, unsigned int fram
  * plane becomes the pictures' alpha.  The block textures live in the context's scratch only (at most 4 GiB of them at a
  * time: longer batches are worked through in slices).  results[f]:
  * HapDecode's code for the frame; Bad_Arguments for a frame whose texture is of another format or geometry than the
- * call says (BC7 / BC6H / lone RGTC1 textures have no pixel decoder here).  The reference has no counterpart: it
- * stops at the texture (hap.h:132-140) and leaves the pixels to the consumer's GPU. */
+ * call says (BC6H / lone RGTC1 textures have no pixel decoder here).  Hap R frames (one BC7 texture) are
+ * Bad_Arguments unless flags has HAPGPU_DECODE_BPTC_PICTURES: then, with textureCount 1, they decode to pictures like
+ * the others (textureCount 2 stays Bad_Arguments for them).  A batch may mix Hap, Hap Alpha, Hap Q and Hap R frames:
+ * one block-decode launch per texture format present.  The reference has no counterpart: it stops at the texture
+ * (hap.h:132-140) and leaves the pixels to the consumer's GPU. */
 unsigned int HapGpuDecodeFramesRGBA(HapGpuContext *context, unsigned int frameCount,
                                     const void *const *inputBuffers,
                                     const unsigned long *inputBuffersBytes,
