@@ -310,6 +310,24 @@ class Context:
             return r, (C.string_at(oa, row_bytes * height) if r == 0 else None)
         return r, None
 
+    def decompress_rgba_half(self, texture, texture_format, width, height, out=None, row_bytes=None):
+        """BC6H texture -> RGBA16F (four half bit patterns per texel, alpha 1.0). Returns (result, bytes | None):
+        the picture's bytes when `out` is None, else None (the picture is in `out`: numpy or torch, host or device,
+        e.g. a torch.float16 (H, W, 4) CUDA tensor)."""
+        ta, tn, _k = _addr_len(texture)
+        row_bytes = row_bytes or width * 8
+        own = out is None
+        if own:
+            out = (C.c_ubyte * (row_bytes * height + 16))()
+            base = C.addressof(out)
+            oa = base + (-base) % 16
+        else:
+            oa, _on, _k2 = _addr_len(out)
+        r = lib.HapGpuDecompressRGBAHalf(self.handle, ta, tn, texture_format, width, height, oa, row_bytes)
+        if own:
+            return r, (C.string_at(oa, row_bytes * height) if r == 0 else None)
+        return r, None
+
     def decode_chunk_group(self, frame, index, first_chunk, chunk_count, output):
         """Decodes chunks [first_chunk, first_chunk + chunk_count) into their place in `output`
         (laid out as the whole texture). Returns (result, texture bytes, format)."""
@@ -420,6 +438,19 @@ class Context:
         results = (C.c_uint * nf)()
         r = lib.HapGpuDecodeFramesRGBA(self.handle, nf, ptrs, lens, texture_count, optrs, width, height,
                                        row_bytes or width * 4, results, flags)
+        return r, list(results)
+
+    def decode_frames_rgba_half(self, frames, frame_bytes, pictures, width, height, row_bytes=None, flags=0):
+        """Hap HDR frames -> RGBA16F pictures in one call (HapGpuDecodeFramesRGBAHalf).  Returns (result, results[])."""
+        nf = len(frames)
+        if len(pictures) != nf:
+            raise ValueError("one picture per frame")
+        ptrs, infos = self._ptr_array(frames)
+        lens = (C.c_ulong * nf)(*[fb if fb is not None else infos[i][1] for i, fb in enumerate(frame_bytes)])
+        optrs, _oinfos = self._ptr_array(pictures)
+        results = (C.c_uint * nf)()
+        r = lib.HapGpuDecodeFramesRGBAHalf(self.handle, nf, ptrs, lens, optrs, width, height, row_bytes or width * 8,
+                                           results, flags)
         return r, list(results)
 
     def decode_sequence(self, reader, first, count, index, outputs, batch=0):

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hapgpu_runtime.hpp"
+#include "bptc_tables.hpp"
 
 namespace {
 
@@ -28,39 +29,6 @@ constexpr unsigned D_INDEX_BITS = 0x24222233u;  // 3 3 2 2 2 2 4 2
 constexpr unsigned D_INDEX2_BITS = 0x00230000u; // 0 0 0 0 3 2 0 0
 
 __device__ __forceinline__ unsigned field(unsigned desc, unsigned mode) { return __builtin_amdgcn_ubfe(desc, 4u * mode, 4u); }
-
-// 2 bits per texel: the 64 two-subset partitions (subset 0 / 1), then the 64 three-subset ones
-__constant__ uint32_t k_partitions[128] = {
-    0x50505050u, 0x40404040u, 0x54545454u, 0x54505040u, 0x50404000u, 0x55545450u, 0x55545040u, 0x54504000u,
-    0x50400000u, 0x55555450u, 0x55544000u, 0x54400000u, 0x55555440u, 0x55550000u, 0x55555500u, 0x55000000u,
-    0x55150100u, 0x00004054u, 0x15010000u, 0x00405054u, 0x00004050u, 0x15050100u, 0x05010000u, 0x40505054u,
-    0x00404050u, 0x05010100u, 0x14141414u, 0x05141450u, 0x01155440u, 0x00555500u, 0x15014054u, 0x05414150u,
-    0x44444444u, 0x55005500u, 0x11441144u, 0x05055050u, 0x05500550u, 0x11114444u, 0x41144114u, 0x44111144u,
-    0x15055054u, 0x01055040u, 0x05041050u, 0x05455150u, 0x14414114u, 0x50050550u, 0x41411414u, 0x00141400u,
-    0x00041504u, 0x00105410u, 0x10541000u, 0x04150400u, 0x50410514u, 0x41051450u, 0x05415014u, 0x14054150u,
-    0x41050514u, 0x41505014u, 0x40011554u, 0x54150140u, 0x50505500u, 0x00555050u, 0x15151010u, 0x54540404u,
-    0xAA685050u, 0x6A5A5040u, 0x5A5A4200u, 0x5450A0A8u, 0xA5A50000u, 0xA0A05050u, 0x5555A0A0u, 0x5A5A5050u,
-    0xAA550000u, 0xAA555500u, 0xAAAA5500u, 0x90909090u, 0x94949494u, 0xA4A4A4A4u, 0xA9A59450u, 0x2A0A4250u,
-    0xA5945040u, 0x0A425054u, 0xA5A5A500u, 0x55A0A0A0u, 0xA8A85454u, 0x6A6A4040u, 0xA4A45000u, 0x1A1A0500u,
-    0x0050A4A4u, 0xAAA59090u, 0x14696914u, 0x69691400u, 0xA08585A0u, 0xAA821414u, 0x50A4A450u, 0x6A5A0200u,
-    0xA9A58000u, 0x5090A0A8u, 0xA8A09050u, 0x24242424u, 0x00AA5500u, 0x24924924u, 0x24499224u, 0x50A50A50u,
-    0x500AA550u, 0xAAAA4444u, 0x66660000u, 0xA5A0A5A0u, 0x50A050A0u, 0x69286928u, 0x44AAAA44u, 0x66666600u,
-    0xAA444444u, 0x54A854A8u, 0x95809580u, 0x96969600u, 0xA85454A8u, 0x80959580u, 0xAA141414u, 0x96960000u,
-    0xAAAA1414u, 0xA05050A0u, 0xA0A5A5A0u, 0x96000000u, 0x40804080u, 0xA9A8A9A8u, 0xAAAAAA44u, 0x2A4A5254u,
-};
-
-// anchor texels: subset 1 in the low nibble, subset 2 in the high one (0 where the partition has no such subset: texel 0
-// is subset 0's anchor anyway)
-__constant__ uint8_t k_anchors[128] = {
-    0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F,
-    0x0F, 0x02, 0x08, 0x02, 0x02, 0x08, 0x08, 0x0F, 0x02, 0x08, 0x02, 0x02, 0x08, 0x08, 0x02, 0x02,
-    0x0F, 0x0F, 0x06, 0x08, 0x02, 0x08, 0x0F, 0x0F, 0x02, 0x08, 0x02, 0x02, 0x02, 0x0F, 0x0F, 0x06,
-    0x06, 0x02, 0x06, 0x08, 0x0F, 0x0F, 0x02, 0x02, 0x0F, 0x0F, 0x0F, 0x0F, 0x0F, 0x02, 0x02, 0x0F,
-    0xF3, 0x83, 0x8F, 0x3F, 0xF8, 0xF3, 0x3F, 0x8F, 0xF8, 0xF8, 0xF6, 0xF6, 0xF6, 0xF5, 0xF3, 0x83,
-    0xF3, 0x83, 0xF8, 0x3F, 0xF3, 0x83, 0xF6, 0x8A, 0x35, 0xF8, 0x68, 0xA6, 0xF8, 0xF5, 0xAF, 0x8F,
-    0xF8, 0x3F, 0xF3, 0xA5, 0xA6, 0x8A, 0x98, 0xAF, 0x6F, 0xF3, 0x8F, 0xF5, 0x3F, 0x6F, 0x6F, 0x8F,
-    0xF3, 0x3F, 0xF5, 0xF5, 0xF5, 0xF8, 0xF5, 0xFA, 0xF5, 0xFA, 0xF8, 0xFD, 0x3F, 0xFC, 0xF3, 0x83,
-};
 
 // 32 bits of the 128-bit block q0..q3 starting at bit `off` (0..127; bits past the block read as zero)
 __device__ __forceinline__ unsigned bits_at(uint4 q, unsigned off)

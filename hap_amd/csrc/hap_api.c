@@ -502,6 +502,19 @@ unsigned int HapGpuDecompressRGBA(HapGpuContext *context, const void *texture, u
     return r;
 }
 
+unsigned int HapGpuDecompressRGBAHalf(HapGpuContext *context, const void *texture, unsigned long textureBytes,
+                                      unsigned int textureFormat, unsigned int width, unsigned int height,
+                                      void *rgbaHalf, unsigned long rowBytes)
+{
+    unsigned r;
+    if (!context)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_decompress_rgba_half(context, texture, textureBytes, textureFormat, width, height, rgbaHalf, rowBytes);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
 unsigned int HapGpuEncodeFrames(HapGpuContext *context, unsigned int frameCount, unsigned int count,
                                 const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
                                 const unsigned int *textureFormats, const unsigned int *compressors,
@@ -714,6 +727,21 @@ unsigned int HapGpuDecodeFramesRGBA(HapGpuContext *context, unsigned int frameCo
     hapgpu_rt_lock(context->rt);
     r = hapb_decode_rgba(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, rgbaFrames, width, height,
                          rowBytes, results, flags);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+unsigned int HapGpuDecodeFramesRGBAHalf(HapGpuContext *context, unsigned int frameCount,
+                                        const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
+                                        void *const *rgbaHalfFrames, unsigned int width, unsigned int height,
+                                        unsigned long rowBytes, unsigned int *results, unsigned int flags)
+{
+    unsigned r;
+    if (!context)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_decode_rgba_half(context, frameCount, inputBuffers, inputBuffersBytes, rgbaHalfFrames, width, height,
+                              rowBytes, results, flags);
     hapgpu_rt_unlock(context->rt);
     return r;
 }

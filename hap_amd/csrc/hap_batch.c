@@ -813,6 +813,50 @@ unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned 
     return HapResult_No_Error;
 }
 
+unsigned hapb_decompress_rgba_half(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes,
+                                   unsigned format, unsigned width, unsigned height, void *rgbah, unsigned long row_bytes)
+{
+    hapgpu_rt *rt = ctx->rt;
+    size_t need, bytes;
+    const void *src = texture;
+    void *dst = rgbah;
+    int rc;
+    if (context_busy(ctx, NULL, 0))
+        return HapResult_Internal_Error;
+    if (!texture || !rgbah || width == 0 || height == 0 || (width & 3u) || (height & 3u) ||
+        row_bytes < (unsigned long)width * 8ul || (row_bytes & 15u) ||
+        (format != HapTextureFormat_RGB_BPTC_UNSIGNED_FLOAT && format != HapTextureFormat_RGB_BPTC_SIGNED_FLOAT))
+        return HapResult_Bad_Arguments;
+    need = (size_t)(width / 4u) * (height / 4u) * 16u;
+    if (texture_bytes < need)
+        return HapResult_Bad_Arguments;
+    bytes = (size_t)row_bytes * (height - 1u) + (size_t)width * 8u;
+    if (!is_dev(ctx, texture)) {
+        void *s = hapgpu_rt_device_scratch(rt, D_BC_TEX, need);
+        if (!s || hapgpu_rt_h2d(rt, s, texture, need))
+            return HapResult_Internal_Error;
+        src = s;
+    }
+    if (!is_dev(ctx, rgbah)) {
+        dst = hapgpu_rt_device_scratch(rt, D_RGBA_STAGE, bytes);
+        if (!dst)
+            return HapResult_Internal_Error;
+    }
+    rc = hapgpu_k_block_decode_half(rt, src, width, height, format, dst, row_bytes);
+    if (rc == 1)
+        return HapResult_Bad_Arguments;
+    if (rc)
+        return HapResult_Internal_Error;
+    /* (row by row when the client's rows are longer than the picture's: what lies between them is not ours) */
+    if (dst != rgbah && (row_bytes == (unsigned long)width * 8ul ? hapgpu_rt_d2h(rt, rgbah, dst, bytes)
+                                                                  : hapgpu_rt_d2h_rows(rt, rgbah, row_bytes, dst, row_bytes,
+                                                                                       (size_t)width * 8u, height)))
+        return HapResult_Internal_Error;
+    if (hapgpu_rt_sync(rt))
+        return HapResult_Internal_Error;
+    return HapResult_No_Error;
+}
+
 unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
                           unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
                           const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
@@ -1759,9 +1803,21 @@ fail_alloc:
    player without texture sampling of its own asks of a Hap decoder (the reference leaves this step to the GPU's
    texture units, hap.h:92-95 "the texture format the frame decodes to"). */
 #define RGBA_SLICE_BYTES ((size_t)4u << 30)     /* block textures held at a time */
-unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                          const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
-                          unsigned width, unsigned height, unsigned long row_bytes, unsigned *results, unsigned flags)
+#define PICTURE_KINDS_MAX 4u                    /* texture formats one road decodes */
+
+/* What a road from frames to pictures takes and makes: its pictures' texel size, the texture formats it decodes (one
+   block-decode launch per format present in a slice) and which of them may come with an RGTC1 alpha plane. */
+typedef struct picture_road {
+    unsigned pixel_bytes;       /* 4: RGBA8 (hapgpu_k_block_decode_batch), 8: RGBA16F (..._half_batch) */
+    unsigned kind_count;
+    const unsigned *kinds;
+    unsigned paired_kinds;      /* bit k: kinds[k] may have an alpha plane (textureCount 2) */
+} picture_road;
+
+static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                                const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
+                                unsigned width, unsigned height, unsigned long row_bytes, unsigned *results,
+                                unsigned flags, const picture_road *road)
 {
     hapgpu_rt *rt = ctx->rt;
     size_t blocks, per_frame, alpha_off, rgba_bytes, slice, done;
@@ -1770,7 +1826,7 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
     unsigned long *in_bytes, *caps, *used;
     void **outs;
     unsigned *idx, *fmts, *res;
-    const int bptc = (flags & HAPGPU_DECODE_BPTC_PICTURES) != 0;
+    const size_t pixel_row = (size_t)width * road->pixel_bytes;
     if (frame_count == 0)
         return HapResult_No_Error;
     if (!results)
@@ -1778,7 +1834,7 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
     if (context_busy(ctx, results, frame_count))
         return HapResult_Internal_Error;
     if (!inputs || !input_bytes || !rgba_frames || texture_count == 0 || texture_count > 2 || width == 0 ||
-        height == 0 || (width & 3u) || (height & 3u) || row_bytes < (unsigned long)width * 4ul || (row_bytes & 15u)) {
+        height == 0 || (width & 3u) || (height & 3u) || row_bytes < pixel_row || (row_bytes & 15u)) {
         for (f = 0; f < frame_count; f++)
             results[f] = HapResult_Bad_Arguments;
         return HapResult_Bad_Arguments;
@@ -1786,7 +1842,7 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
     blocks = (size_t)(width / 4u) * (height / 4u);
     alpha_off = align_up(blocks * 16u, 256);
     per_frame = alpha_off + (texture_count == 2 ? align_up(blocks * 8u, 256) : 0u);
-    rgba_bytes = (size_t)row_bytes * (height - 1u) + (size_t)width * 4u;
+    rgba_bytes = (size_t)row_bytes * (height - 1u) + pixel_row;
     slice = RGBA_SLICE_BYTES / per_frame;
     if (slice == 0)
         slice = 1;
@@ -1837,10 +1893,9 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
         {
             /* one block-decode launch per texture format present in the slice: [textures][alpha planes][pictures] in a
                small device table, pictures of other formats (or that failed) with a texture address of 0 */
-            uint64_t *htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, sizeof(uint64_t) * 12u * n);
-            uint64_t *dtab = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, sizeof(uint64_t) * 12u * n);
-            static const unsigned kinds[4] = {HapTextureFormat_RGB_DXT1, HapTextureFormat_RGBA_DXT5, HapTextureFormat_YCoCg_DXT5,
-                                              HapTextureFormat_RGBA_BPTC_UNORM};
+            const size_t tab_bytes = sizeof(uint64_t) * 3u * PICTURE_KINDS_MAX * n;
+            uint64_t *htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, tab_bytes);
+            uint64_t *dtab = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, tab_bytes);
             unsigned present = 0, k;
             if (!htab || !dtab) {
                 for (f = 0; f < n; f++)
@@ -1848,25 +1903,26 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                 first_error = first_error ? first_error : HapResult_Internal_Error;
                 continue;
             }
-            memset(htab, 0, sizeof(uint64_t) * 12u * n);
+            memset(htab, 0, tab_bytes);
             for (f = 0; f < n; f++) {
                 const size_t e = (size_t)f * texture_count;
                 const unsigned fmt = fmts[e];
                 void *dst = rgba_frames[done + f];
                 unsigned r = res[e];
+                for (k = 0; k < road->kind_count && road->kinds[k] != fmt; k++)
+                    ;
                 if (r == HapResult_No_Error && texture_count == 2)
                     r = res[e + 1];
                 /* (no Hap variant pairs a BC7 texture with a second one) */
-                if (bptc && texture_count == 2 && res[e] == HapResult_No_Error && fmt == HapTextureFormat_RGBA_BPTC_UNORM)
+                if (texture_count == 2 && res[e] == HapResult_No_Error && k < road->kind_count && !(road->paired_kinds >> k & 1u))
                     r = HapResult_Bad_Arguments;
                 if (r == HapResult_No_Error && !dst)
                     r = HapResult_Bad_Arguments;
-                /* the frame must hold what the caller's geometry says: a colour texture the block decoder knows (BC7
-                   only when the caller asked for Hap R pictures), of exactly width x height, and (two textures) an RGTC1
-                   plane of the same geometry */
+                /* the frame must hold what the caller's geometry says: a colour texture of the road (BC7 only when the
+                   caller asked for Hap R pictures), of exactly width x height, and (two textures) an RGTC1 plane of the
+                   same geometry */
                 if (r == HapResult_No_Error &&
-                    ((fmt != HapTextureFormat_RGB_DXT1 && fmt != HapTextureFormat_RGBA_DXT5 && fmt != HapTextureFormat_YCoCg_DXT5 &&
-                      !(bptc && fmt == HapTextureFormat_RGBA_BPTC_UNORM)) ||
+                    (k == road->kind_count ||
                      used[e] != blocks * (fmt == HapTextureFormat_RGB_DXT1 ? 8u : 16u) ||
                      (texture_count == 2 && (fmts[e + 1] != HapTextureFormat_A_RGTC1 || used[e + 1] != blocks * 8u))))
                     r = HapResult_Bad_Arguments;
@@ -1880,8 +1936,6 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                     r = HapResult_Bad_Arguments;
                 }
                 if (r == HapResult_No_Error) {
-                    k = fmt == HapTextureFormat_RGB_DXT1 ? 0u : fmt == HapTextureFormat_RGBA_DXT5 ? 1u :
-                        fmt == HapTextureFormat_YCoCg_DXT5 ? 2u : 3u;
                     present |= 1u << k;
                     htab[(size_t)k * 3u * n + f] = (uint64_t)(uintptr_t)outs[e];
                     htab[(size_t)k * 3u * n + n + f] = texture_count == 2 ? (uint64_t)(uintptr_t)outs[e + 1] : 0u;
@@ -1890,20 +1944,23 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                 results[done + f] = r;
             }
             if (present) {
-                rc |= hapgpu_rt_h2d(rt, dtab, htab, sizeof(uint64_t) * 12u * n);
-                for (k = 0; k < 4u; k++)
+                rc |= hapgpu_rt_h2d(rt, dtab, htab, tab_bytes);
+                for (k = 0; k < road->kind_count; k++)
                     if (present & (1u << k))
-                        rc |= hapgpu_k_block_decode_batch(rt, dtab + (size_t)k * 3u * n, n, texture_count == 2, width, height, kinds[k],
-                                                          row_bytes);
+                        rc |= road->pixel_bytes == 8u ?
+                              hapgpu_k_block_decode_half_batch(rt, dtab + (size_t)k * 3u * n, n, width, height, road->kinds[k],
+                                                               row_bytes) :
+                              hapgpu_k_block_decode_batch(rt, dtab + (size_t)k * 3u * n, n, texture_count == 2, width, height,
+                                                          road->kinds[k], row_bytes);
                 for (f = 0; f < n; f++)
                     if (results[done + f] == HapResult_No_Error && stage && !is_dev(ctx, rgba_frames[done + f])) {
                         /* (row by row when the client's rows are longer than the picture's: what lies between them -- the
                            rest of a larger image, perhaps -- is not this call's to overwrite) */
-                        if (row_bytes == (unsigned long)width * 4ul)
+                        if (row_bytes == pixel_row)
                             rc |= hapgpu_rt_d2h(rt, rgba_frames[done + f], stage + align_up(rgba_bytes, 256) * f, rgba_bytes);
                         else
                             rc |= hapgpu_rt_d2h_rows(rt, rgba_frames[done + f], row_bytes, stage + align_up(rgba_bytes, 256) * f, row_bytes,
-                                                     (size_t)width * 4u, height);
+                                                     pixel_row, height);
                     }
             }
         }
@@ -1918,6 +1975,28 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
     }
     free(in); free(in_bytes); free(outs); free(idx);
     return first_error;
+}
+
+unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                          const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
+                          unsigned width, unsigned height, unsigned long row_bytes, unsigned *results, unsigned flags)
+{
+    static const unsigned kinds[4] = {HapTextureFormat_RGB_DXT1, HapTextureFormat_RGBA_DXT5, HapTextureFormat_YCoCg_DXT5,
+                                      HapTextureFormat_RGBA_BPTC_UNORM};
+    const picture_road road = {4u, (flags & HAPGPU_DECODE_BPTC_PICTURES) ? 4u : 3u, kinds, 0x7u};
+    return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, rgba_frames, width, height, row_bytes,
+                           results, flags, &road);
+}
+
+/* Hap HDR frames (one BC6H texture, unsigned or signed) -> RGBA16F pictures: the same road with the BC6H decoder */
+unsigned hapb_decode_rgba_half(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                               const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,
+                               unsigned long row_bytes, unsigned *results, unsigned flags)
+{
+    static const unsigned kinds[2] = {HapTextureFormat_RGB_BPTC_UNSIGNED_FLOAT, HapTextureFormat_RGB_BPTC_SIGNED_FLOAT};
+    const picture_road road = {8u, 2u, kinds, 0u};
+    return decode_pictures(ctx, frame_count, inputs, input_bytes, 1u, pictures, width, height, row_bytes, results, flags,
+                           &road);
 }
 
 /* ============================================================= join on the device */

@@ -89,6 +89,9 @@ unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width
 unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
                               const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
                               void *rgba, unsigned long row_bytes);
+/* BC6H (unsigned or signed) -> RGBA16F */
+unsigned hapb_decompress_rgba_half(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes,
+                                   unsigned format, unsigned width, unsigned height, void *rgbah, unsigned long row_bytes);
 unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
                           unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
                           const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
@@ -105,6 +108,10 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
 unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
                           const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
                           unsigned width, unsigned height, unsigned long row_bytes, unsigned *results, unsigned flags);
+/* Hap HDR frames (one BC6H texture) -> RGBA16F pictures */
+unsigned hapb_decode_rgba_half(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                               const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,
+                               unsigned long row_bytes, unsigned *results, unsigned flags);
 
 /* groups and output in device memory: tables through the host, payloads device to device */
 unsigned hapb_join_device(HapGpuContext *ctx, unsigned group_count, const void *const *frames,

@@ -301,6 +301,12 @@ int hapgpu_k_block_decode(hapgpu_rt *rt, const void *blocks, const void *alpha, 
    [pictures], `pictures` entries each (texture 0 = skip the picture) */
 int hapgpu_k_block_decode_batch(hapgpu_rt *rt, const uint64_t *table, unsigned pictures, int with_alpha, unsigned width,
                                 unsigned height, unsigned hap_texture_format, size_t row_bytes);
+/* BC6H (RGB_BPTC_UNSIGNED_FLOAT / RGB_BPTC_SIGNED_FLOAT) -> RGBA16F, 8 bytes a texel: one picture, and pictures of one
+   format and geometry from a table as above (its alpha column unused) */
+int hapgpu_k_block_decode_half(hapgpu_rt *rt, const void *blocks, unsigned width, unsigned height,
+                               unsigned hap_texture_format, void *rgbah, size_t row_bytes);
+int hapgpu_k_block_decode_half_batch(hapgpu_rt *rt, const uint64_t *table, unsigned pictures, unsigned width,
+                                     unsigned height, unsigned hap_texture_format, size_t row_bytes);
 /* group_tables: HAP_GROUP_TABLE_BYTES bytes per fragment (same indexing as frag_sizes), written for textures whose reserved bit 20 is set */
 int hapgpu_k_snappy_compress(hapgpu_rt *rt, const HapGpuFrameEnc *frames, unsigned frame_count,
                              unsigned max_frags_per_texture, unsigned frag_log2,

@@ -173,12 +173,24 @@ unsigned int HapGpuCompressRGBA(HapGpuContext *context,
  * RGB) or RGBA_BPTC_UNORM (BC7, Hap R: all eight modes; reserved blocks give (0, 0, 0, 0));
  * alphaTexture: optional A_RGTC1 plane that supplies A (Hap Q Alpha), else NULL / 0 -- Bad_Arguments
  * with BC7.  Device textures of 16-byte blocks must be 16-byte aligned, DXT1 ones 8-byte aligned.
- * rgba must be 16-byte aligned with rowBytes a multiple of 16.  Host or device pointers. */
+ * rgba must be 16-byte aligned with rowBytes a multiple of 16.  Host or device pointers.  BC6H
+ * textures are Bad_Arguments here: HapGpuDecompressRGBAHalf expands them. */
 unsigned int HapGpuDecompressRGBA(HapGpuContext *context,
                                   const void *texture, unsigned long textureBytes, unsigned int textureFormat,
                                   const void *alphaTexture, unsigned long alphaBytes,
                                   unsigned int width, unsigned int height,
                                   void *rgba, unsigned long rowBytes);
+
+/* BC6H texture (Hap HDR) -> RGBA16F: four IEEE half bit patterns per texel, 8 bytes, rows rowBytes apart.
+ * textureFormat: RGB_BPTC_UNSIGNED_FLOAT or RGB_BPTC_SIGNED_FLOAT (anything else is Bad_Arguments).  RGB is
+ * the BPTC definition's result bit for bit (signed textures may give -0, 0x8000, which is kept); alpha is
+ * 1.0 (0x3C00); reserved modes give RGB 0.  width and height multiples of 4; rowBytes at least width * 8
+ * and a multiple of 16.  Host or device pointers; a device texture and a device picture must each be
+ * 16-byte aligned.  Only the picture's bytes of each row are written, host or device. */
+unsigned int HapGpuDecompressRGBAHalf(HapGpuContext *context,
+                                      const void *texture, unsigned long textureBytes, unsigned int textureFormat,
+                                      unsigned int width, unsigned int height,
+                                      void *rgbaHalf, unsigned long rowBytes);
 
 /* Batched HapEncode: frame f is made of `count` textures
  * inputBuffers[f*count + i] of inputBuffersBytes[i] bytes each (every frame of
@@ -297,7 +309,8 @@ unsigned int HapGpuDecodeFrameTextures(HapGpuContext *context, unsigned int fram
  * plane becomes the pictures' alpha.  The block textures live in the context's scratch only (at most 4 GiB of them at a
  * time: longer batches are worked through in slices).  results[f]:
  * HapDecode's code for the frame; Bad_Arguments for a frame whose texture is of another format or geometry than the
- * call says (BC6H / lone RGTC1 textures have no pixel decoder here).  Hap R frames (one BC7 texture) are
+ * call says (lone RGTC1 textures have no pixel decoder here; BC6H ones go to HapGpuDecodeFramesRGBAHalf, flag or not).
+ * Hap R frames (one BC7 texture) are
  * Bad_Arguments unless flags has HAPGPU_DECODE_BPTC_PICTURES: then, with textureCount 1, they decode to pictures like
  * the others (textureCount 2 stays Bad_Arguments for them).  A batch may mix Hap, Hap Alpha, Hap Q and Hap R frames:
  * one block-decode launch per texture format present.  The reference has no counterpart: it stops at the texture
@@ -310,6 +323,18 @@ unsigned int HapGpuDecodeFramesRGBA(HapGpuContext *context, unsigned int frameCo
                                     unsigned int width, unsigned int height, unsigned long rowBytes,
                                     unsigned int *results,
                                     unsigned int flags);
+
+/* Hap HDR frames in, RGBA16F pictures out: HapGpuDecodeFramesRGBA for frames of one BC6H texture (unsigned or
+ * signed; a batch may mix the two: one block-decode launch per signedness present), pictures as
+ * HapGpuDecompressRGBAHalf makes them (rowBytes a multiple of 16, at least width * 8; device pictures 16-byte
+ * aligned; host or device; host pictures with longer rows are written row by row).  flags: the decode flags, as for
+ * HapGpuDecodeFrameTextures.  results[f]: HapDecode's code for the frame; Bad_Arguments for a frame of another
+ * format (Hap, Hap Q, Hap R ...) or geometry, whose picture is left untouched. */
+unsigned int HapGpuDecodeFramesRGBAHalf(HapGpuContext *context, unsigned int frameCount,
+                                        const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
+                                        void *const *rgbaHalfFrames,
+                                        unsigned int width, unsigned int height, unsigned long rowBytes,
+                                        unsigned int *results, unsigned int flags);
 
 /* --- one batch over several GPUs: independent frames per GPU ------------------- */
 
