@@ -47,6 +47,7 @@ def _load():
         "HapGpuResolvedBlockCount": (ul, [vp]),
         "HapGpuPlacementTimeoutCount": (ul, [vp]),
         "HapGpuCompressRGBA": (u, [vp, vp, u, u, ul, u, vp, ul, P(ul)]),
+        "HapGpuCompressRGBAFlags": (u, [vp, vp, u, u, ul, u, u, vp, ul, P(ul)]),
         "HapGpuDecompressRGBA": (u, [vp, vp, ul, u, vp, ul, u, u, vp, ul]),
         "HapGpuDecompressRGBAHalf": (u, [vp, vp, ul, u, u, u, vp, ul]),
         "HapGpuEncodeFrames": (u, [vp, u, u, P(vp), P(ul), P(u), P(u), P(u), P(vp), P(ul), P(ul), P(u), u]),

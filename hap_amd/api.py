@@ -30,6 +30,7 @@ ENCODE_FRAGMENT_INDEX = 0x1
 ENCODE_COARSE_MATCHES = 0x2
 ENCODE_SMALLER_FILES = 0x4
 ENCODE_FINE_CHUNKS = 0x8
+ENCODE_BPTC_BLOCKS = 0x10
 DECODE_IGNORE_FRAGMENT_INDEX = 0x1
 DECODE_IGNORE_HALF_TILES = 0x2
 DECODE_NO_BLOCK_SCAN = 0x4
@@ -278,7 +279,9 @@ class Context:
         """frames decoded a second time because their fragment table did not describe their streams"""
         return int(lib.HapGpuTableFallbackCount(self.handle))
 
-    def compress_rgba(self, rgba, width, height, row_bytes, texture_format, output=None):
+    def compress_rgba(self, rgba, width, height, row_bytes, texture_format, output=None, flags=0):
+        """RGBA8 -> one block texture (HapGpuCompressRGBA; with nonzero flags HapGpuCompressRGBAFlags, where
+        ENCODE_BPTC_BLOCKS admits RGBA_BPTC_UNORM).  Returns (result, bytes | None), or (result, bytes used) into `output`."""
         block = 8 if texture_format in (HapTextureFormat.RGB_DXT1, HapTextureFormat.A_RGTC1) else 16
         need = (width // 4) * (height // 4) * block
         a, _n, _k = _addr_len(rgba)
@@ -287,7 +290,10 @@ class Context:
             output = (C.c_ubyte * max(1, need))()
         oa, on, _k2 = _addr_len(output)
         used = C.c_ulong(0)
-        r = lib.HapGpuCompressRGBA(self.handle, a, width, height, row_bytes, texture_format, oa, on, C.byref(used))
+        if flags:
+            r = lib.HapGpuCompressRGBAFlags(self.handle, a, width, height, row_bytes, texture_format, flags, oa, on, C.byref(used))
+        else:
+            r = lib.HapGpuCompressRGBA(self.handle, a, width, height, row_bytes, texture_format, oa, on, C.byref(used))
         if own:
             return r, (C.string_at(output, used.value) if r == 0 else None)
         return r, used.value

@@ -483,7 +483,22 @@ unsigned int HapGpuCompressRGBA(HapGpuContext *context, const void *rgba, unsign
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
     r = hapb_compress_rgba(context, rgba, width, height, rowBytes, textureFormat, output, outputBytes,
-                           outputBytesUsed, 1);
+                           outputBytesUsed, 1, 0u);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+unsigned int HapGpuCompressRGBAFlags(HapGpuContext *context, const void *rgba, unsigned int width,
+                                     unsigned int height, unsigned long rowBytes, unsigned int textureFormat,
+                                     unsigned int flags, void *output, unsigned long outputBytes,
+                                     unsigned long *outputBytesUsed)
+{
+    unsigned r;
+    if (!context)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_compress_rgba(context, rgba, width, height, rowBytes, textureFormat, output, outputBytes,
+                           outputBytesUsed, 1, flags);
     hapgpu_rt_unlock(context->rt);
     return r;
 }

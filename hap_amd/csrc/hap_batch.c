@@ -473,7 +473,12 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                                                                                      job->row_bytes, job->wide);
                     else
                         for (i = 0; i < job->count; i++)
-                            if (!fused[i])
+                            if (job->formats[i] == HapTextureFormat_RGBA_BPTC_UNORM)      /* (never fused) */
+                                launch_rc |= (unsigned)hapgpu_k_bptc_encode_batch(rt, job->device_table,
+                                                                            job->device_table + (size_t)(1u + i) * job->frame_count,
+                                                                            job->frame_count, job->width, job->height, job->row_bytes,
+                                                                            job->wide);
+                            else if (!fused[i])
                                 launch_rc |= (unsigned)hapgpu_k_block_encode_batch(rt, job->device_table,
                                                                              job->device_table + (size_t)(1u + i) * job->frame_count,
                                                                              job->frame_count, job->width, job->height, job->row_bytes,
@@ -712,8 +717,10 @@ void hapb_encode_abandon(HapGpuContext *ctx, HapbEncodePending *pd)
 
 unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width, unsigned height,
                             unsigned long row_bytes, unsigned format, void *output,
-                            unsigned long output_bytes, unsigned long *used, int synchronise)
+                            unsigned long output_bytes, unsigned long *used, int synchronise, unsigned flags)
 {
+    /* BC7 only when asked (HAPGPU_ENCODE_BPTC_BLOCKS) */
+    const int bptc = (flags & HAPGPU_ENCODE_BPTC_BLOCKS) && format == HapTextureFormat_RGBA_BPTC_UNORM;
     hapgpu_rt *rt = ctx->rt;
     size_t block = (format == HapTextureFormat_RGB_DXT1 || format == HapTextureFormat_A_RGTC1) ? 8u : 16u;
     size_t need, rgba_bytes;
@@ -725,7 +732,7 @@ unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width
     if (!rgba || !output || width == 0 || height == 0 || (width & 3u) || (height & 3u) ||
         row_bytes < (unsigned long)width * 4ul ||
         (format != HapTextureFormat_RGB_DXT1 && format != HapTextureFormat_RGBA_DXT5 &&
-         format != HapTextureFormat_YCoCg_DXT5 && format != HapTextureFormat_A_RGTC1))
+         format != HapTextureFormat_YCoCg_DXT5 && format != HapTextureFormat_A_RGTC1 && !bptc))
         return HapResult_Bad_Arguments;
     need = (size_t)(width / 4u) * (height / 4u) * block;
     if (output_bytes < need)
@@ -742,7 +749,8 @@ unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width
         if (!dst)
             return HapResult_Internal_Error;
     }
-    rc = hapgpu_k_block_encode(rt, src, width, height, row_bytes, format, dst);
+    rc = bptc ? hapgpu_k_bptc_encode(rt, src, width, height, row_bytes, dst)
+              : hapgpu_k_block_encode(rt, src, width, height, row_bytes, format, dst);
     if (rc == 1)
         return HapResult_Bad_Arguments;
     if (rc)
@@ -883,8 +891,10 @@ unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
     }
     for (i = 0; i < count; i++) {
         size_t block;
+        /* (BC7 only when asked, and alone: no Hap variant pairs it with a second texture) */
+        const int bptc = (flags & HAPGPU_ENCODE_BPTC_BLOCKS) && count == 1u && formats[i] == HapTextureFormat_RGBA_BPTC_UNORM;
         if (formats[i] != HapTextureFormat_RGB_DXT1 && formats[i] != HapTextureFormat_RGBA_DXT5 &&
-            formats[i] != HapTextureFormat_YCoCg_DXT5 && formats[i] != HapTextureFormat_A_RGTC1) {
+            formats[i] != HapTextureFormat_YCoCg_DXT5 && formats[i] != HapTextureFormat_A_RGTC1 && !bptc) {
             for (f = 0; f < frame_count; f++)
                 results[f] = HapResult_Bad_Arguments;
             return HapResult_Bad_Arguments;

@@ -291,6 +291,11 @@ int hapgpu_k_block_encode(hapgpu_rt *rt, const void *rgba, unsigned width, unsig
 /* pictures of one geometry in one launch; sources / outputs: DEVICE arrays of device addresses (0 = skip) */
 int hapgpu_k_block_encode_batch(hapgpu_rt *rt, const uint64_t *sources, const uint64_t *outputs, unsigned pictures,
                                 unsigned width, unsigned height, size_t row_bytes, unsigned hap_texture_format, int wide);
+/* RGBA8 -> BC7 (RGBA_BPTC_UNORM, bptc_encode.hip): one picture (out 16-byte aligned), and pictures of one geometry from
+   device address arrays as for hapgpu_k_block_encode_batch */
+int hapgpu_k_bptc_encode(hapgpu_rt *rt, const void *rgba, unsigned width, unsigned height, size_t row_bytes, void *out);
+int hapgpu_k_bptc_encode_batch(hapgpu_rt *rt, const uint64_t *sources, const uint64_t *outputs, unsigned pictures,
+                               unsigned width, unsigned height, size_t row_bytes, int wide);
 /* Hap Q Alpha: scaled YCoCg-DXT5 + RGTC1 alpha plane of every picture from one read of its RGBA */
 int hapgpu_k_block_encode_batch_ycocg_alpha(hapgpu_rt *rt, const uint64_t *sources, const uint64_t *colour_outputs,
                                             const uint64_t *alpha_outputs, unsigned pictures, unsigned width,

@@ -90,6 +90,14 @@ typedef struct HapGpuContext HapGpuContext;
                                                wavefront per chunk by the generic kernel ("Frames without a
                                                table").  May be combined with HAPGPU_ENCODE_FRAGMENT_INDEX. */
 
+#define HAPGPU_ENCODE_BPTC_BLOCKS 0x10u     /* the calls that start from RGBA pictures (HapGpuCompressRGBAFlags,
+                                               HapGpuEncodeFramesRGBA and its ...Begin / ...OnDevices forms) accept
+                                               HapTextureFormat_RGBA_BPTC_UNORM: the pictures are BC7-encoded on the GPU
+                                               (Hap R; bptc_encode.hip: modes 6 and 1 for opaque blocks, 6 and 5 for
+                                               blocks with alpha).  One texture per frame.  Without the flag they refuse
+                                               that format with Bad_Arguments, as before; BC6H formats are refused
+                                               either way.  Ignored by the calls that take finished textures. */
+
 /* Decode flags */
 #define HAPGPU_DECODE_IGNORE_FRAGMENT_INDEX 0x1u /* decode as a decoder unaware of section 0x46 would */
 #define HAPGPU_DECODE_IGNORE_HALF_TILES 0x2u     /* use a version-4 table's fragment sizes only (the generic
@@ -168,6 +176,16 @@ unsigned int HapGpuCompressRGBA(HapGpuContext *context,
                                 void *output, unsigned long outputBytes,
                                 unsigned long *outputBytesUsed);
 
+/* HapGpuCompressRGBA with encode flags: flags == 0 is exactly HapGpuCompressRGBA.  With HAPGPU_ENCODE_BPTC_BLOCKS it
+ * also takes textureFormat RGBA_BPTC_UNORM: 16 bytes per block, a device output must be 16-byte aligned.  Other bits
+ * are ignored. */
+unsigned int HapGpuCompressRGBAFlags(HapGpuContext *context,
+                                     const void *rgba, unsigned int width, unsigned int height,
+                                     unsigned long rowBytes, unsigned int textureFormat,
+                                     unsigned int flags,
+                                     void *output, unsigned long outputBytes,
+                                     unsigned long *outputBytesUsed);
+
 /* Block-compressed texture -> RGBA8 (the stage a GPU's texture unit performs for the reference's
  * clients; CDNA has none).  textureFormat: RGB_DXT1, RGBA_DXT5, YCoCg_DXT5 (converted back to
  * RGB) or RGBA_BPTC_UNORM (BC7, Hap R: all eight modes; reserved blocks give (0, 0, 0, 0));
@@ -214,9 +232,10 @@ unsigned int HapGpuEncodeFrames(HapGpuContext *context, unsigned int frameCount,
 
 /* Batched RGBA -> Hap frame: block-compresses every frame into `count`
  * textures of textureFormats[] (e.g. {YCoCg_DXT5} for Hap Q, {YCoCg_DXT5,
- * A_RGTC1} for Hap Q Alpha, {RGB_DXT1} for Hap, {RGBA_DXT5} for Hap Alpha)
- * and packs them exactly as HapGpuEncodeFrames does; the intermediate
- * textures never leave HBM.  rgbaFrames[f]: host or device. */
+ * A_RGTC1} for Hap Q Alpha, {RGB_DXT1} for Hap, {RGBA_DXT5} for Hap Alpha,
+ * {RGBA_BPTC_UNORM} for Hap R with HAPGPU_ENCODE_BPTC_BLOCKS in flags and
+ * count 1) and packs them exactly as HapGpuEncodeFrames does; the
+ * intermediate textures never leave HBM.  rgbaFrames[f]: host or device. */
 unsigned int HapGpuEncodeFramesRGBA(HapGpuContext *context, unsigned int frameCount,
                                     const void *const *rgbaFrames,
                                     unsigned int width, unsigned int height,
