@@ -330,75 +330,28 @@ __device__ __forceinline__ void bc6h_decode_body(const uint8_t *__restrict__ blo
     }
 }
 
+// pictures of one geometry in one launch: picture blockIdx.z, [textures][unused][pictures] of a HapGpuPictureTable;
+// texture address 0 = not this launch's format: skip
 template <bool SIGNED>
-__global__ __launch_bounds__(256) void bc6h_decode_kernel(const uint8_t *__restrict__ blocks, unsigned blocks_x,
-                                                          unsigned blocks_total, uint8_t *__restrict__ rgbah,
+__global__ __launch_bounds__(256) void bc6h_decode_kernel(HapGpuPictureTable t, unsigned blocks_x, unsigned blocks_total,
                                                           size_t row_bytes)
 {
-    bc6h_decode_body<SIGNED>(blocks, blocks_x, blocks_total, rgbah, row_bytes);
-}
-
-// pictures of one geometry in one launch: the [textures][unused][pictures] table of bc_decode_batch_kernel; texture
-// address 0 = not this launch's format: skip
-template <bool SIGNED>
-__global__ __launch_bounds__(256) void bc6h_decode_batch_kernel(const uint64_t *__restrict__ table, unsigned pictures,
-                                                                unsigned blocks_x, unsigned blocks_total, size_t row_bytes)
-{
-    const uint8_t *blocks = (const uint8_t *)table[blockIdx.z];
+    const uint8_t *blocks = (const uint8_t *)picture_address(t, 0);
     if (!blocks)
         return;
-    bc6h_decode_body<SIGNED>(blocks, blocks_x, blocks_total, (uint8_t *)table[2u * pictures + blockIdx.z], row_bytes);
+    bc6h_decode_body<SIGNED>(blocks, blocks_x, blocks_total, (uint8_t *)picture_address(t, 2), row_bytes);
 }
 
 } // namespace
 
-// format: RGB_BPTC_UNSIGNED_FLOAT (0x8E8F) or RGB_BPTC_SIGNED_FLOAT (0x8E8E).  Returns 0 launched, 1 bad arguments.
-extern "C" int hapgpu_k_block_decode_half(hapgpu_rt *rt, const void *blocks, unsigned width, unsigned height,
-                                          unsigned format, void *rgbah, size_t row_bytes)
+// RGB_BPTC_UNSIGNED_FLOAT / RGB_BPTC_SIGNED_FLOAT of hapgpu_k_block_decode (bc_decode.hip): RGBA16F pictures
+void hapgpu_launch_bc6h_decode(const HapGpuPictureTable &t, unsigned pictures, bool is_signed, unsigned bx, unsigned by,
+                               size_t row_bytes, hipStream_t stream)
 {
-    scoped_timing st(rt, 6);
-    const hipStream_t stream = hapgpu_rt_stream(rt);
-    if (!blocks || !rgbah || width == 0 || height == 0 || (width & 3u) || (height & 3u) || row_bytes < (size_t)width * 8u)
-        return 1;
-    if (((uintptr_t)rgbah | row_bytes | (uintptr_t)blocks) & 15u)
-        return 1;
-    const unsigned bx = width / 4u, total = bx * (height / 4u);
-    const dim3 grid((total + 255u) / 256u), block(256);
-    switch (format) {
-    case 0x8E8F:
-        hipLaunchKernelGGL(bc6h_decode_kernel<false>, grid, block, 0, stream, (const uint8_t *)blocks, bx, total,
-                           (uint8_t *)rgbah, row_bytes);
-        break;
-    case 0x8E8E:
-        hipLaunchKernelGGL(bc6h_decode_kernel<true>, grid, block, 0, stream, (const uint8_t *)blocks, bx, total,
-                           (uint8_t *)rgbah, row_bytes);
-        break;
-    default: return 1;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : 4;
-}
-
-// The same for `pictures` textures of one format and geometry: table (device memory) = texture addresses, an unused
-// column, picture addresses, `pictures` of each; a texture address of 0 skips the picture.  Alignment as above (the
-// host checks it per picture).
-extern "C" int hapgpu_k_block_decode_half_batch(hapgpu_rt *rt, const uint64_t *table, unsigned pictures, unsigned width,
-                                                unsigned height, unsigned format, size_t row_bytes)
-{
-    scoped_timing st(rt, 6);
-    const hipStream_t stream = hapgpu_rt_stream(rt);
-    if (!table || pictures == 0 || pictures > 65535u || width == 0 || height == 0 || (width & 3u) || (height & 3u) ||
-        row_bytes < (size_t)width * 8u || (row_bytes & 15u))
-        return 1;
-    const unsigned bx = width / 4u, total = bx * (height / 4u);
+    const unsigned total = bx * by;
     const dim3 grid((total + 255u) / 256u, 1, pictures), block(256);
-    switch (format) {
-    case 0x8E8F:
-        hipLaunchKernelGGL(bc6h_decode_batch_kernel<false>, grid, block, 0, stream, table, pictures, bx, total, row_bytes);
-        break;
-    case 0x8E8E:
-        hipLaunchKernelGGL(bc6h_decode_batch_kernel<true>, grid, block, 0, stream, table, pictures, bx, total, row_bytes);
-        break;
-    default: return 1;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : 4;
+    if (is_signed)
+        hipLaunchKernelGGL(bc6h_decode_kernel<true>, grid, block, 0, stream, t, bx, total, row_bytes);
+    else
+        hipLaunchKernelGGL(bc6h_decode_kernel<false>, grid, block, 0, stream, t, bx, total, row_bytes);
 }

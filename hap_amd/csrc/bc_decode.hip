@@ -234,102 +234,56 @@ __device__ __forceinline__ void bc_decode_body(const uint8_t *__restrict__ block
     }
 }
 
+// pictures of one geometry in one launch: picture blockIdx.z, [textures][alpha planes][pictures] of a
+// HapGpuPictureTable; texture address 0 = not this launch's format: skip
 template <int FMT, bool HAS_ALPHA>
-__global__ __launch_bounds__(256) void bc_decode_kernel(const uint8_t *__restrict__ blocks,
-                                                        const uint8_t *__restrict__ alpha_blocks,
-                                                        unsigned blocks_x, unsigned blocks_total,
-                                                        uint8_t *__restrict__ rgba, size_t row_bytes)
+__global__ __launch_bounds__(256) void bc_decode_kernel(HapGpuPictureTable t, unsigned blocks_x, unsigned blocks_total,
+                                                        size_t row_bytes)
 {
-    bc_decode_body<FMT, HAS_ALPHA>(blocks, alpha_blocks, blocks_x, blocks_total, rgba, row_bytes);
-}
-
-// pictures of one geometry in one launch: picture blockIdx.z; table = [textures][alpha planes][pictures], `pictures`
-// device addresses each; texture address 0 = not this launch's format: skip
-template <int FMT, bool HAS_ALPHA>
-__global__ __launch_bounds__(256) void bc_decode_batch_kernel(const uint64_t *__restrict__ table, unsigned pictures,
-                                                              unsigned blocks_x, unsigned blocks_total, size_t row_bytes)
-{
-    const uint8_t *blocks = (const uint8_t *)table[blockIdx.z];
+    const uint8_t *blocks = (const uint8_t *)picture_address(t, 0);
     if (!blocks)
         return;
-    bc_decode_body<FMT, HAS_ALPHA>(blocks, (const uint8_t *)table[pictures + blockIdx.z], blocks_x, blocks_total,
-                                   (uint8_t *)table[2u * pictures + blockIdx.z], row_bytes);
+    bc_decode_body<FMT, HAS_ALPHA>(blocks, (const uint8_t *)picture_address(t, 1), blocks_x, blocks_total,
+                                   (uint8_t *)picture_address(t, 2), row_bytes);
 }
 
 template <int FMT>
-void launch_batch(const uint64_t *table, unsigned pictures, bool alpha, unsigned bx, unsigned by, size_t row_bytes, hipStream_t stream)
+void launch(const HapGpuPictureTable &t, unsigned pictures, bool alpha, unsigned bx, unsigned by, size_t row_bytes,
+            hipStream_t stream)
 {
     const unsigned total = bx * by;
     const dim3 grid((total + 255u) / 256u, 1, pictures), block(256);
     if (alpha)
-        hipLaunchKernelGGL((bc_decode_batch_kernel<FMT, true>), grid, block, 0, stream, table, pictures, bx, total, row_bytes);
+        hipLaunchKernelGGL((bc_decode_kernel<FMT, true>), grid, block, 0, stream, t, bx, total, row_bytes);
     else
-        hipLaunchKernelGGL((bc_decode_batch_kernel<FMT, false>), grid, block, 0, stream, table, pictures, bx, total, row_bytes);
-}
-
-template <int FMT>
-void launch(const void *blocks, const void *alpha, unsigned bx, unsigned by, void *rgba, size_t row_bytes, hipStream_t stream)
-{
-    const unsigned total = bx * by;
-    const dim3 grid((total + 255u) / 256u), block(256);
-    if (alpha)
-        hipLaunchKernelGGL((bc_decode_kernel<FMT, true>), grid, block, 0, stream, (const uint8_t *)blocks, (const uint8_t *)alpha, bx, total, (uint8_t *)rgba, row_bytes);
-    else
-        hipLaunchKernelGGL((bc_decode_kernel<FMT, false>), grid, block, 0, stream, (const uint8_t *)blocks, (const uint8_t *)nullptr, bx, total, (uint8_t *)rgba, row_bytes);
+        hipLaunchKernelGGL((bc_decode_kernel<FMT, false>), grid, block, 0, stream, t, bx, total, row_bytes);
 }
 
 } // namespace
 
-// format: HapTextureFormat of `blocks` (DXT1, DXT5, YCoCg-DXT5, BC7 -- bptc_decode.hip); alpha: optional RGTC1 plane
-// (not with BC7).
-// Returns 0 launched, 1 bad arguments.
-extern "C" int hapgpu_k_block_decode(hapgpu_rt *rt, const void *blocks, const void *alpha, unsigned width, unsigned height,
-                                     unsigned format, void *rgba, size_t row_bytes)
+// hapgpu_abi.h: DXT1, DXT5, YCoCg-DXT5 (with_alpha: + RGTC1 plane) here, BC7 in bptc_decode.hip (no alpha plane), BC6H
+// in bc6h_decode.hip (no alpha plane, 8-byte texels).  Returns 0 launched, 1 bad arguments, 4 launch failure.
+extern "C" int hapgpu_k_block_decode(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, int with_alpha,
+                                     unsigned width, unsigned height, unsigned format, size_t row_bytes)
 {
     scoped_timing st(rt, 6);
     const hipStream_t stream = hapgpu_rt_stream(rt);
-    if (!blocks || !rgba || width == 0 || height == 0 || (width & 3u) || (height & 3u) || row_bytes < (size_t)width * 4u)
+    const bool half = format == 0x8E8F || format == 0x8E8E;
+    if (!table || !(table->column[0] || table->one[0]) || !(table->column[2] || table->one[2]) ||
+        (with_alpha && !(table->column[1] || table->one[1])) || pictures == 0 || pictures > 65535u || width == 0 ||
+        height == 0 || (width & 3u) || (height & 3u) || row_bytes < (size_t)width * (half ? 8u : 4u) || (row_bytes & 15u))
         return 1;
-    if (((uintptr_t)rgba | row_bytes) & 15u)
-        return 1;
-    if (((uintptr_t)blocks & (format == 0x83F0 ? 7u : 15u)) || ((uintptr_t)alpha & 7u))
-        return 1;
+    const HapGpuPictureTable &t = *table;
     const unsigned bx = width / 4u, by = height / 4u;
-    switch (format) {
-    case 0x83F0: launch<0>(blocks, alpha, bx, by, rgba, row_bytes, stream); break;
-    case 0x83F3: launch<1>(blocks, alpha, bx, by, rgba, row_bytes, stream); break;
-    case 0x01: launch<2>(blocks, alpha, bx, by, rgba, row_bytes, stream); break;
-    case 0x8E8C:
-        if (alpha)
-            return 1;
-        hapgpu_bptc_decode(blocks, bx, by, rgba, row_bytes, stream);
-        break;
-    default: return 1;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : 4;
-}
-
-// The same for `pictures` textures of one format and geometry: table (device memory) = texture addresses, alpha plane
-// addresses (read when with_alpha), picture addresses, `pictures` of each; a texture address of 0 skips the picture.
-// Alignment as above (the host checks it per picture).
-extern "C" int hapgpu_k_block_decode_batch(hapgpu_rt *rt, const uint64_t *table, unsigned pictures, int with_alpha,
-                                           unsigned width, unsigned height, unsigned format, size_t row_bytes)
-{
-    scoped_timing st(rt, 6);
-    const hipStream_t stream = hapgpu_rt_stream(rt);
-    if (!table || pictures == 0 || pictures > 65535u || width == 0 || height == 0 || (width & 3u) || (height & 3u) ||
-        row_bytes < (size_t)width * 4u || (row_bytes & 15u))
+    if (with_alpha && (format == 0x8E8C || half))
         return 1;
-    const unsigned bx = width / 4u, by = height / 4u;
     switch (format) {
-    case 0x83F0: launch_batch<0>(table, pictures, with_alpha != 0, bx, by, row_bytes, stream); break;
-    case 0x83F3: launch_batch<1>(table, pictures, with_alpha != 0, bx, by, row_bytes, stream); break;
-    case 0x01: launch_batch<2>(table, pictures, with_alpha != 0, bx, by, row_bytes, stream); break;
-    case 0x8E8C:
-        if (with_alpha)
-            return 1;
-        hapgpu_bptc_decode_batch(table, pictures, bx, by, row_bytes, stream);
-        break;
+    case 0x83F0: launch<0>(t, pictures, with_alpha != 0, bx, by, row_bytes, stream); break;
+    case 0x83F3: launch<1>(t, pictures, with_alpha != 0, bx, by, row_bytes, stream); break;
+    case 0x01: launch<2>(t, pictures, with_alpha != 0, bx, by, row_bytes, stream); break;
+    case 0x8E8C: hapgpu_launch_bptc_decode(t, pictures, bx, by, row_bytes, stream); break;
+    case 0x8E8F: hapgpu_launch_bc6h_decode(t, pictures, false, bx, by, row_bytes, stream); break;
+    case 0x8E8E: hapgpu_launch_bc6h_decode(t, pictures, true, bx, by, row_bytes, stream); break;
     default: return 1;
     }
     return hipGetLastError() == hipSuccess ? 0 : 4;

@@ -53,127 +53,57 @@ __device__ __forceinline__ void encode_block(const uint8_t *__restrict__ rgba, s
     }
 }
 
+// pictures of one geometry in one launch: picture blockIdx.z, addresses from a HapGpuPictureTable (0: skip the picture).
+// kFmtYCoCgAlpha is Hap Q Alpha: both textures of a picture in one pass over its RGBA (64 + 16 + 8 bytes per
+// block), the RGTC1 plane to the second outputs.
 template <int FMT, bool WIDE>
-__global__ __launch_bounds__(64) void bc_encode_kernel(const uint8_t *__restrict__ rgba, size_t row_bytes,
-                                                       unsigned blocks_x, unsigned blocks_total,
-                                                       uint8_t *__restrict__ out)
+__global__ __launch_bounds__(64) void bc_encode_kernel(HapGpuPictureTable t, size_t row_bytes, unsigned blocks_x)
 {
-    (void)blocks_total;
-    encode_block<FMT, WIDE>(rgba, row_bytes, blocks_x, out);
-}
-
-// a batch of equally sized pictures in one launch: picture blockIdx.z, addresses from device arrays
-template <int FMT, bool WIDE>
-__global__ __launch_bounds__(64) void bc_encode_batch_kernel(const uint64_t *__restrict__ sources,
-                                                             const uint64_t *__restrict__ outputs, size_t row_bytes,
-                                                             unsigned blocks_x)
-{
-    const uint8_t *rgba = (const uint8_t *)sources[blockIdx.z];
-    uint8_t *out = (uint8_t *)outputs[blockIdx.z];
-    if (!rgba || !out)
+    const uint8_t *rgba = (const uint8_t *)picture_address(t, 0);
+    uint8_t *out = (uint8_t *)picture_address(t, 1);
+    uint8_t *out2 = FMT == kFmtYCoCgAlpha ? (uint8_t *)picture_address(t, 2) : nullptr;
+    if (!rgba || !out || (FMT == kFmtYCoCgAlpha && !out2))
         return;
-    encode_block<FMT, WIDE>(rgba, row_bytes, blocks_x, out);
-}
-
-// Hap Q Alpha: both textures of a picture in one pass over its RGBA (64 + 16 + 8 bytes per block)
-template <bool WIDE>
-__global__ __launch_bounds__(64) void bc_encode_batch2_kernel(const uint64_t *__restrict__ sources,
-                                                              const uint64_t *__restrict__ colour_outputs,
-                                                              const uint64_t *__restrict__ alpha_outputs, size_t row_bytes,
-                                                              unsigned blocks_x)
-{
-    const uint8_t *rgba = (const uint8_t *)sources[blockIdx.z];
-    uint8_t *out = (uint8_t *)colour_outputs[blockIdx.z], *out2 = (uint8_t *)alpha_outputs[blockIdx.z];
-    if (!rgba || !out || !out2)
-        return;
-    encode_block<kFmtYCoCgAlpha, WIDE>(rgba, row_bytes, blocks_x, out, out2);
+    encode_block<FMT, WIDE>(rgba, row_bytes, blocks_x, out, out2);
 }
 
 template <int FMT>
-void launch_batch(const uint64_t *sources, const uint64_t *outputs, unsigned pictures, size_t row_bytes, unsigned bx,
-                  unsigned by, bool wide, hipStream_t stream)
+void launch(const HapGpuPictureTable &t, unsigned pictures, size_t row_bytes, unsigned bx, unsigned by, bool wide,
+            hipStream_t stream)
 {
     const dim3 grid((bx + 63u) / 64u, by, pictures), block(64);
     if (wide)
-        hipLaunchKernelGGL((bc_encode_batch_kernel<FMT, true>), grid, block, 0, stream, sources, outputs, row_bytes, bx);
+        hipLaunchKernelGGL((bc_encode_kernel<FMT, true>), grid, block, 0, stream, t, row_bytes, bx);
     else
-        hipLaunchKernelGGL((bc_encode_batch_kernel<FMT, false>), grid, block, 0, stream, sources, outputs, row_bytes, bx);
-}
-
-template <int FMT>
-void launch(const void *rgba, size_t row_bytes, unsigned bx, unsigned by, void *out, bool wide, hipStream_t stream)
-{
-    const unsigned total = bx * by;
-    const dim3 grid((bx + 63u) / 64u, by), block(64);
-    if (wide)
-        hipLaunchKernelGGL((bc_encode_kernel<FMT, true>), grid, block, 0, stream, (const uint8_t *)rgba, row_bytes, bx, total, (uint8_t *)out);
-    else
-        hipLaunchKernelGGL((bc_encode_kernel<FMT, false>), grid, block, 0, stream, (const uint8_t *)rgba, row_bytes, bx, total, (uint8_t *)out);
+        hipLaunchKernelGGL((bc_encode_kernel<FMT, false>), grid, block, 0, stream, t, row_bytes, bx);
 }
 
 } // namespace
 
-// format: HapTextureFormat constant. Returns 0 when launched, 1 for bad arguments.
-extern "C" int hapgpu_k_block_encode(hapgpu_rt *rt, const void *rgba, unsigned width, unsigned height, size_t row_bytes,
-                                     unsigned format, void *out)
+// hapgpu_abi.h.  Returns 0 launched, 1 bad arguments, 4 launch failure.
+extern "C" int hapgpu_k_block_encode(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, unsigned width,
+                                     unsigned height, size_t row_bytes, unsigned format, int with_alpha, int wide)
 {
     scoped_timing st(rt, 0);
     const hipStream_t stream = hapgpu_rt_stream(rt);
-    if (!rgba || !out || width == 0 || height == 0 || (width & 3u) || (height & 3u) || row_bytes < (size_t)width * 4u)
+    if (!table || !(table->column[0] || table->one[0]) || !(table->column[1] || table->one[1]) ||
+        (with_alpha && (format != 0x01 || !(table->column[2] || table->one[2]))) || pictures == 0 || pictures > 65535u ||
+        width == 0 || height == 0 || (width & 3u) || (height & 3u) || row_bytes < (size_t)width * 4u || (row_bytes & 3u))
         return 1;
-    if (((uintptr_t)rgba & 3u) || (row_bytes & 3u))
-        return 1;
-    const unsigned bx = width / 4u, by = height / 4u;
-    if ((unsigned long long)bx * by > 0xFFFFFFFFull / 256u * 255u)
-        return 1;
-    const bool wide = (((uintptr_t)rgba | row_bytes) & 15u) == 0;
-    switch (format) {
-    case 0x83F0: if ((uintptr_t)out & 7u) return 1; launch<kFmtDXT1>(rgba, row_bytes, bx, by, out, wide, stream); break;
-    case 0x83F3: if ((uintptr_t)out & 15u) return 1; launch<kFmtDXT5>(rgba, row_bytes, bx, by, out, wide, stream); break;
-    case 0x01: if ((uintptr_t)out & 15u) return 1; launch<kFmtYCoCg>(rgba, row_bytes, bx, by, out, wide, stream); break;
-    case 0x8DBB: if ((uintptr_t)out & 7u) return 1; launch<kFmtRGTC1>(rgba, row_bytes, bx, by, out, wide, stream); break;
-    default: return 1;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : 4;
-}
-
-// Batch variant: `pictures` RGBA images of the same geometry whose addresses (and output addresses) are in device
-// arrays; wide != 0 promises 16-byte aligned sources and row pitch.  Outputs must be 8/16-byte aligned.
-extern "C" int hapgpu_k_block_encode_batch(hapgpu_rt *rt, const uint64_t *sources, const uint64_t *outputs, unsigned pictures,
-                                           unsigned width, unsigned height, size_t row_bytes, unsigned format, int wide)
-{
-    scoped_timing st(rt, 0);
-    const hipStream_t stream = hapgpu_rt_stream(rt);
-    if (!sources || !outputs || pictures == 0 || width == 0 || height == 0 || (width & 3u) || (height & 3u) ||
-        row_bytes < (size_t)width * 4u || (row_bytes & 3u) || pictures > 65535u || height / 4u > 65535u)
-        return 1;
+    const HapGpuPictureTable &t = *table;
     const unsigned bx = width / 4u, by = height / 4u;
     switch (format) {
-    case 0x83F0: launch_batch<kFmtDXT1>(sources, outputs, pictures, row_bytes, bx, by, wide != 0, stream); break;
-    case 0x83F3: launch_batch<kFmtDXT5>(sources, outputs, pictures, row_bytes, bx, by, wide != 0, stream); break;
-    case 0x01: launch_batch<kFmtYCoCg>(sources, outputs, pictures, row_bytes, bx, by, wide != 0, stream); break;
-    case 0x8DBB: launch_batch<kFmtRGTC1>(sources, outputs, pictures, row_bytes, bx, by, wide != 0, stream); break;
+    case 0x83F0: launch<kFmtDXT1>(t, pictures, row_bytes, bx, by, wide != 0, stream); break;
+    case 0x83F3: launch<kFmtDXT5>(t, pictures, row_bytes, bx, by, wide != 0, stream); break;
+    case 0x01:
+        if (with_alpha)
+            launch<kFmtYCoCgAlpha>(t, pictures, row_bytes, bx, by, wide != 0, stream);
+        else
+            launch<kFmtYCoCg>(t, pictures, row_bytes, bx, by, wide != 0, stream);
+        break;
+    case 0x8DBB: launch<kFmtRGTC1>(t, pictures, row_bytes, bx, by, wide != 0, stream); break;
+    case 0x8E8C: hapgpu_launch_bptc_encode(t, pictures, bx, by, row_bytes, wide != 0, stream); break;
     default: return 1;
     }
-    return hipGetLastError() == hipSuccess ? 0 : 4;
-}
-
-// Hap Q Alpha batch: scaled YCoCg-DXT5 to colour_outputs[i] and the RGTC1 alpha plane to alpha_outputs[i], one read of
-// every RGBA picture.  Same argument rules as above.
-extern "C" int hapgpu_k_block_encode_batch_ycocg_alpha(hapgpu_rt *rt, const uint64_t *sources, const uint64_t *colour_outputs,
-                                                       const uint64_t *alpha_outputs, unsigned pictures, unsigned width,
-                                                       unsigned height, size_t row_bytes, int wide)
-{
-    scoped_timing st(rt, 0);
-    const hipStream_t stream = hapgpu_rt_stream(rt);
-    if (!sources || !colour_outputs || !alpha_outputs || pictures == 0 || width == 0 || height == 0 || (width & 3u) ||
-        (height & 3u) || row_bytes < (size_t)width * 4u || (row_bytes & 3u) || pictures > 65535u || height / 4u > 65535u)
-        return 1;
-    const unsigned bx = width / 4u, by = height / 4u;
-    const dim3 grid((bx + 63u) / 64u, by, pictures), block(64);
-    if (wide)
-        hipLaunchKernelGGL((bc_encode_batch2_kernel<true>), grid, block, 0, stream, sources, colour_outputs, alpha_outputs, row_bytes, bx);
-    else
-        hipLaunchKernelGGL((bc_encode_batch2_kernel<false>), grid, block, 0, stream, sources, colour_outputs, alpha_outputs, row_bytes, bx);
     return hipGetLastError() == hipSuccess ? 0 : 4;
 }

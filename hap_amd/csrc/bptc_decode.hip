@@ -165,36 +165,24 @@ __device__ __forceinline__ void bptc_decode_body(const uint8_t *__restrict__ blo
     }
 }
 
-__global__ __launch_bounds__(256) void bptc_decode_kernel(const uint8_t *__restrict__ blocks, unsigned blocks_x,
-                                                          unsigned blocks_total, uint8_t *__restrict__ rgba, size_t row_bytes)
+// pictures of one geometry in one launch: picture blockIdx.z, [textures][unused][pictures] of a HapGpuPictureTable;
+// texture address 0 = not this launch's format: skip
+__global__ __launch_bounds__(256) void bptc_decode_kernel(HapGpuPictureTable t, unsigned blocks_x, unsigned blocks_total,
+                                                          size_t row_bytes)
 {
-    bptc_decode_body(blocks, blocks_x, blocks_total, rgba, row_bytes);
-}
-
-// pictures of one geometry in one launch: the [textures][alpha planes][pictures] table of bc_decode_batch_kernel (the
-// alpha column unused); texture address 0 = not this launch's format: skip
-__global__ __launch_bounds__(256) void bptc_decode_batch_kernel(const uint64_t *__restrict__ table, unsigned pictures,
-                                                                unsigned blocks_x, unsigned blocks_total, size_t row_bytes)
-{
-    const uint8_t *blocks = (const uint8_t *)table[blockIdx.z];
+    const uint8_t *blocks = (const uint8_t *)picture_address(t, 0);
     if (!blocks)
         return;
-    bptc_decode_body(blocks, blocks_x, blocks_total, (uint8_t *)table[2u * pictures + blockIdx.z], row_bytes);
+    bptc_decode_body(blocks, blocks_x, blocks_total, (uint8_t *)picture_address(t, 2), row_bytes);
 }
 
 } // namespace
 
-void hapgpu_bptc_decode(const void *blocks, unsigned bx, unsigned by, void *rgba, size_t row_bytes, hipStream_t stream)
+// RGBA_BPTC_UNORM of hapgpu_k_block_decode (bc_decode.hip)
+void hapgpu_launch_bptc_decode(const HapGpuPictureTable &t, unsigned pictures, unsigned bx, unsigned by,
+                               size_t row_bytes, hipStream_t stream)
 {
     const unsigned total = bx * by;
-    hipLaunchKernelGGL(bptc_decode_kernel, dim3((total + 255u) / 256u), dim3(256), 0, stream, (const uint8_t *)blocks, bx,
-                       total, (uint8_t *)rgba, row_bytes);
-}
-
-void hapgpu_bptc_decode_batch(const uint64_t *table, unsigned pictures, unsigned bx, unsigned by, size_t row_bytes,
-                              hipStream_t stream)
-{
-    const unsigned total = bx * by;
-    hipLaunchKernelGGL(bptc_decode_batch_kernel, dim3((total + 255u) / 256u, 1, pictures), dim3(256), 0, stream, table,
-                       pictures, bx, total, row_bytes);
+    hipLaunchKernelGGL(bptc_decode_kernel, dim3((total + 255u) / 256u, 1, pictures), dim3(256), 0, stream, t, bx, total,
+                       row_bytes);
 }

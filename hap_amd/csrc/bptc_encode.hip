@@ -526,21 +526,12 @@ __device__ __forceinline__ void encode_block(const uint8_t *__restrict__ rgba, s
     *reinterpret_cast<uint4 *>(out + id * 16u) = hapgpu_bc7_encode_block(p);
 }
 
+// pictures of one geometry in one launch: picture blockIdx.z, addresses from a HapGpuPictureTable (0: skip the picture)
 template <bool WIDE>
-__global__ __launch_bounds__(64) void bptc_encode_kernel(const uint8_t *__restrict__ rgba, size_t row_bytes,
-                                                         unsigned blocks_x, uint8_t *__restrict__ out)
+__global__ __launch_bounds__(64) void bptc_encode_kernel(HapGpuPictureTable t, size_t row_bytes, unsigned blocks_x)
 {
-    encode_block<WIDE>(rgba, row_bytes, blocks_x, out);
-}
-
-// pictures of one geometry in one launch: picture blockIdx.z, addresses from device arrays (0: skip the picture)
-template <bool WIDE>
-__global__ __launch_bounds__(64) void bptc_encode_batch_kernel(const uint64_t *__restrict__ sources,
-                                                               const uint64_t *__restrict__ outputs, size_t row_bytes,
-                                                               unsigned blocks_x)
-{
-    const uint8_t *rgba = (const uint8_t *)sources[blockIdx.z];
-    uint8_t *out = (uint8_t *)outputs[blockIdx.z];
+    const uint8_t *rgba = (const uint8_t *)picture_address(t, 0);
+    uint8_t *out = (uint8_t *)picture_address(t, 1);
     if (!rgba || !out)
         return;
     encode_block<WIDE>(rgba, row_bytes, blocks_x, out);
@@ -548,40 +539,13 @@ __global__ __launch_bounds__(64) void bptc_encode_batch_kernel(const uint64_t *_
 
 } // namespace
 
-// One picture -> BC7 at `out` (16-byte aligned).  rgba 4-byte aligned, row_bytes a multiple of 4; 16-byte loads when
-// both are 16-byte aligned.  Returns 0 launched, 1 bad arguments, 4 launch failure.
-extern "C" int hapgpu_k_bptc_encode(hapgpu_rt *rt, const void *rgba, unsigned width, unsigned height, size_t row_bytes,
-                                    void *out)
+// RGBA_BPTC_UNORM of hapgpu_k_block_encode (bc_encode.hip): outputs 16-byte aligned
+void hapgpu_launch_bptc_encode(const HapGpuPictureTable &t, unsigned pictures, unsigned bx, unsigned by,
+                               size_t row_bytes, bool wide, hipStream_t stream)
 {
-    scoped_timing st(rt, 0);
-    const hipStream_t stream = hapgpu_rt_stream(rt);
-    if (!rgba || !out || width == 0 || height == 0 || (width & 3u) || (height & 3u) || row_bytes < (size_t)width * 4u ||
-        (((uintptr_t)rgba | row_bytes) & 3u) || ((uintptr_t)out & 15u) || height / 4u > 65535u)
-        return 1;
-    const unsigned bx = width / 4u, by = height / 4u;
-    const dim3 grid((bx + 63u) / 64u, by), block(64);
-    if ((((uintptr_t)rgba | row_bytes) & 15u) == 0)
-        hipLaunchKernelGGL(bptc_encode_kernel<true>, grid, block, 0, stream, (const uint8_t *)rgba, row_bytes, bx, (uint8_t *)out);
-    else
-        hipLaunchKernelGGL(bptc_encode_kernel<false>, grid, block, 0, stream, (const uint8_t *)rgba, row_bytes, bx, (uint8_t *)out);
-    return hipGetLastError() == hipSuccess ? 0 : 4;
-}
-
-// Batch: `pictures` RGBA images of one geometry, addresses in device arrays (outputs 16-byte aligned); wide != 0
-// promises 16-byte aligned sources and row pitch.
-extern "C" int hapgpu_k_bptc_encode_batch(hapgpu_rt *rt, const uint64_t *sources, const uint64_t *outputs, unsigned pictures,
-                                          unsigned width, unsigned height, size_t row_bytes, int wide)
-{
-    scoped_timing st(rt, 0);
-    const hipStream_t stream = hapgpu_rt_stream(rt);
-    if (!sources || !outputs || pictures == 0 || width == 0 || height == 0 || (width & 3u) || (height & 3u) ||
-        row_bytes < (size_t)width * 4u || (row_bytes & 3u) || pictures > 65535u || height / 4u > 65535u)
-        return 1;
-    const unsigned bx = width / 4u, by = height / 4u;
     const dim3 grid((bx + 63u) / 64u, by, pictures), block(64);
     if (wide)
-        hipLaunchKernelGGL(bptc_encode_batch_kernel<true>, grid, block, 0, stream, sources, outputs, row_bytes, bx);
+        hipLaunchKernelGGL(bptc_encode_kernel<true>, grid, block, 0, stream, t, row_bytes, bx);
     else
-        hipLaunchKernelGGL(bptc_encode_batch_kernel<false>, grid, block, 0, stream, sources, outputs, row_bytes, bx);
-    return hipGetLastError() == hipSuccess ? 0 : 4;
+        hipLaunchKernelGGL(bptc_encode_kernel<false>, grid, block, 0, stream, t, row_bytes, bx);
 }

@@ -224,8 +224,7 @@ unsigned int HapGpuFineChunkCount(unsigned long textureBytes, unsigned int textu
            walking DOWN to a divisor gave 1080p DXT5 240 chunks of 8640 bytes -- two fragments each, which the table-less
            road into the block-per-lane decoder does not take).  Where the block count has no divisor up to four times that
            many chunks (a prime number of blocks), the largest one below it, as for any chunk count (hap.c:277-300). */
-        const unsigned long block = (textureFormat == HapTextureFormat_RGB_DXT1 || textureFormat == HapTextureFormat_A_RGTC1) ? 8ul : 16ul;
-        const unsigned long blocks = textureBytes / block;
+        const unsigned long blocks = textureBytes / hapf_block_bytes(textureFormat);
         unsigned long c, top = want * 4ul;
         if (top > 3355431ul)
             top = 3355431ul;
@@ -512,7 +511,7 @@ unsigned int HapGpuDecompressRGBA(HapGpuContext *context, const void *texture, u
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
     r = hapb_decompress_rgba(context, texture, textureBytes, textureFormat, alphaTexture, alphaBytes, width, height,
-                             rgba, rowBytes);
+                             rgba, rowBytes, 0);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -525,7 +524,7 @@ unsigned int HapGpuDecompressRGBAHalf(HapGpuContext *context, const void *textur
     if (!context)
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
-    r = hapb_decompress_rgba_half(context, texture, textureBytes, textureFormat, width, height, rgbaHalf, rowBytes);
+    r = hapb_decompress_rgba(context, texture, textureBytes, textureFormat, NULL, 0, width, height, rgbaHalf, rowBytes, 1);
     hapgpu_rt_unlock(context->rt);
     return r;
 }

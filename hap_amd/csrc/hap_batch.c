@@ -428,7 +428,7 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                    small textures, whose block rows are short enough for the row above to lie inside the fragment
                    (rows of up to ~5 KiB: below 1080p for 16-byte blocks, below 4K for 8-byte blocks) */
                 {
-                    const int small_blocks = g[i].format == HapTextureFormat_RGB_DXT1 || g[i].format == HapTextureFormat_A_RGTC1;
+                    const int small_blocks = hapf_block_bytes(g[i].format) == 8u;
                     /* (field streams with their group table are decoded over a whole-fragment ring: no window) */
                     const int windowed = frag_log2 == 13u && !g[i].half_tiles &&
                                          g[i].bytes >= (small_blocks ? ((size_t)2u << 20) : ((size_t)1u << 20));
@@ -465,24 +465,20 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                 if (job) {
                     launch_rc |= (unsigned)hapgpu_rt_h2d(rt, job->device_table, job->host_table,
                                                          sizeof(uint64_t) * (size_t)(1u + job->count) * job->frame_count);
-                    /* Hap Q Alpha: both textures from one pass over the RGBA (64 + 16 + 8 bytes per block) */
-                    if (job->count == 2 && job->formats[0] == HapTextureFormat_YCoCg_DXT5 && job->formats[1] == HapTextureFormat_A_RGTC1)
-                        launch_rc |= (unsigned)hapgpu_k_block_encode_batch_ycocg_alpha(rt, job->device_table, job->device_table + job->frame_count,
-                                                                                     job->device_table + 2u * (size_t)job->frame_count,
-                                                                                     job->frame_count, job->width, job->height,
-                                                                                     job->row_bytes, job->wide);
-                    else
-                        for (i = 0; i < job->count; i++)
-                            if (job->formats[i] == HapTextureFormat_RGBA_BPTC_UNORM)      /* (never fused) */
-                                launch_rc |= (unsigned)hapgpu_k_bptc_encode_batch(rt, job->device_table,
-                                                                            job->device_table + (size_t)(1u + i) * job->frame_count,
-                                                                            job->frame_count, job->width, job->height, job->row_bytes,
-                                                                            job->wide);
-                            else if (!fused[i])
-                                launch_rc |= (unsigned)hapgpu_k_block_encode_batch(rt, job->device_table,
-                                                                             job->device_table + (size_t)(1u + i) * job->frame_count,
-                                                                             job->frame_count, job->width, job->height, job->row_bytes,
-                                                                             job->formats[i], job->wide);
+                    /* Hap Q Alpha: both textures from one pass over the RGBA (64 + 16 + 8 bytes per block);
+                       else one launch per texture that the second stage does not make itself.  (A batch takes at most
+                       65535 block rows.) */
+                    const int pair = job->count == 2 && job->formats[0] == HapTextureFormat_YCoCg_DXT5 &&
+                                     job->formats[1] == HapTextureFormat_A_RGTC1;
+                    for (i = 0; i < (pair ? 1u : job->count); i++)
+                        if (pair || !fused[i]) {
+                            const uint64_t *dt = job->device_table;
+                            const HapGpuPictureTable t = {{dt, dt + (size_t)(1u + i) * job->frame_count,
+                                                           pair ? dt + 2u * (size_t)job->frame_count : NULL}, {0u, 0u, 0u}};
+                            launch_rc |= job->height / 4u > 65535u ? 1u :
+                                         (unsigned)hapgpu_k_block_encode(rt, &t, job->frame_count, job->width, job->height,
+                                                                         job->row_bytes, job->formats[i], pair, job->wide);
+                        }
                 }
                 launch_rc |= (unsigned)hapgpu_rt_h2d(rt, dframes, hframes, sizeof(HapGpuFrameEnc) * live);
                 if (placed) {
@@ -722,7 +718,8 @@ unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width
     /* BC7 only when asked (HAPGPU_ENCODE_BPTC_BLOCKS) */
     const int bptc = (flags & HAPGPU_ENCODE_BPTC_BLOCKS) && format == HapTextureFormat_RGBA_BPTC_UNORM;
     hapgpu_rt *rt = ctx->rt;
-    size_t block = (format == HapTextureFormat_RGB_DXT1 || format == HapTextureFormat_A_RGTC1) ? 8u : 16u;
+    const size_t block = hapf_block_bytes(format);
+    HapGpuPictureTable t = {{NULL, NULL, NULL}, {0u, 0u, 0u}};
     size_t need, rgba_bytes;
     const void *src = rgba;
     void *dst = output;
@@ -737,6 +734,12 @@ unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width
     need = (size_t)(width / 4u) * (height / 4u) * block;
     if (output_bytes < need)
         return HapResult_Buffer_Too_Small;
+    /* device pictures 4-byte aligned with rows a multiple of 4, device outputs aligned to their blocks; at most 65535
+       block rows for BC7, 2^32 * 255/256 blocks for the others */
+    if ((row_bytes & 3u) || (is_dev(ctx, rgba) && ((uintptr_t)rgba & 3u)) ||
+        (is_dev(ctx, output) && ((uintptr_t)output & (block - 1u))) ||
+        (bptc ? height / 4u > 65535u : (unsigned long long)(width / 4u) * (height / 4u) > 0xFFFFFFFFull / 256u * 255u))
+        return HapResult_Bad_Arguments;
     rgba_bytes = (size_t)row_bytes * (height - 1u) + (size_t)width * 4u;
     if (!is_dev(ctx, rgba)) {
         void *s = hapgpu_rt_device_scratch(rt, D_RGBA_STAGE, rgba_bytes);
@@ -749,8 +752,9 @@ unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width
         if (!dst)
             return HapResult_Internal_Error;
     }
-    rc = bptc ? hapgpu_k_bptc_encode(rt, src, width, height, row_bytes, dst)
-              : hapgpu_k_block_encode(rt, src, width, height, row_bytes, format, dst);
+    t.one[0] = (uint64_t)(uintptr_t)src;
+    t.one[1] = (uint64_t)(uintptr_t)dst;
+    rc = hapgpu_k_block_encode(rt, &t, 1u, width, height, row_bytes, format, 0, (((uintptr_t)src | row_bytes) & 15u) == 0);
     if (rc == 1)
         return HapResult_Bad_Arguments;
     if (rc)
@@ -764,29 +768,53 @@ unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width
     return HapResult_No_Error;
 }
 
+/* What block textures a road to pictures takes (one block-decode launch per format present in a slice of frames) and
+   which of them may come with an RGTC1 alpha plane. */
+typedef struct picture_road {
+    unsigned kind_count;
+    const unsigned *kinds;
+    unsigned paired_kinds;      /* bit k: kinds[k] may have an alpha plane (textureCount 2) */
+} picture_road;
+
+/* RGBA8 pictures (BC7 last: frames of it only with HAPGPU_DECODE_BPTC_PICTURES) and RGBA16F ones */
+static const unsigned k_rgba_kinds[4] = {HapTextureFormat_RGB_DXT1, HapTextureFormat_RGBA_DXT5, HapTextureFormat_YCoCg_DXT5,
+                                         HapTextureFormat_RGBA_BPTC_UNORM};
+static const unsigned k_half_kinds[2] = {HapTextureFormat_RGB_BPTC_UNSIGNED_FLOAT, HapTextureFormat_RGB_BPTC_SIGNED_FLOAT};
+
+static size_t texel_bytes(unsigned format)
+{
+    return format == HapTextureFormat_RGB_BPTC_UNSIGNED_FLOAT || format == HapTextureFormat_RGB_BPTC_SIGNED_FLOAT ? 8u : 4u;
+}
+
 unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
                               const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                              void *rgba, unsigned long row_bytes)
+                              void *picture, unsigned long row_bytes, int half)
 {
+    const picture_road road = half ? (picture_road){2u, k_half_kinds, 0u} : (picture_road){4u, k_rgba_kinds, 0x7u};
     hapgpu_rt *rt = ctx->rt;
-    size_t block = format == HapTextureFormat_RGB_DXT1 ? 8u : 16u;
-    size_t need, alpha_need, rgba_bytes;
+    const size_t block = hapf_block_bytes(format), pixel_row = (size_t)width * texel_bytes(format);
+    HapGpuPictureTable t = {{NULL, NULL, NULL}, {0u, 0u, 0u}};
+    size_t need, alpha_need, picture_bytes;
     const void *src = texture, *asrc = alpha;
-    void *dst = rgba;
+    void *dst = picture;
+    unsigned k;
     int rc;
     if (context_busy(ctx, NULL, 0))
         return HapResult_Internal_Error;
-    if (!texture || !rgba || width == 0 || height == 0 || (width & 3u) || (height & 3u) ||
-        row_bytes < (unsigned long)width * 4ul ||
-        (format != HapTextureFormat_RGB_DXT1 && format != HapTextureFormat_RGBA_DXT5 &&
-         format != HapTextureFormat_YCoCg_DXT5 && format != HapTextureFormat_RGBA_BPTC_UNORM) ||
-        (alpha && format == HapTextureFormat_RGBA_BPTC_UNORM))
+    for (k = 0; k < road.kind_count && road.kinds[k] != format; k++)
+        ;
+    if (!texture || !picture || width == 0 || height == 0 || (width & 3u) || (height & 3u) || row_bytes < pixel_row ||
+        k == road.kind_count || (alpha && !(road.paired_kinds >> k & 1u)))
         return HapResult_Bad_Arguments;
     need = (size_t)(width / 4u) * (height / 4u) * block;
     alpha_need = (size_t)(width / 4u) * (height / 4u) * 8u;
     if (texture_bytes < need || (alpha && alpha_bytes < alpha_need))
         return HapResult_Bad_Arguments;
-    rgba_bytes = (size_t)row_bytes * (height - 1u) + (size_t)width * 4u;
+    /* rows a multiple of 16 bytes; device textures aligned to their blocks, alpha planes to 8 bytes, pictures to 16 */
+    if ((row_bytes & 15u) || (is_dev(ctx, texture) && ((uintptr_t)texture & (block - 1u))) ||
+        (alpha && is_dev(ctx, alpha) && ((uintptr_t)alpha & 7u)) || (is_dev(ctx, picture) && ((uintptr_t)picture & 15u)))
+        return HapResult_Bad_Arguments;
+    picture_bytes = (size_t)row_bytes * (height - 1u) + pixel_row;
     if (!is_dev(ctx, texture)) {
         void *s = hapgpu_rt_device_scratch(rt, D_BC_TEX, need + alpha_need + 256);
         if (!s || hapgpu_rt_h2d(rt, s, texture, need))
@@ -804,61 +832,23 @@ unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned 
             return HapResult_Internal_Error;
         asrc = a;
     }
-    if (!is_dev(ctx, rgba)) {
-        dst = hapgpu_rt_device_scratch(rt, D_RGBA_STAGE, rgba_bytes);
+    if (!is_dev(ctx, picture)) {
+        dst = hapgpu_rt_device_scratch(rt, D_RGBA_STAGE, picture_bytes);
         if (!dst)
             return HapResult_Internal_Error;
     }
-    rc = hapgpu_k_block_decode(rt, src, asrc, width, height, format, dst, row_bytes);
-    if (rc == 1)
-        return HapResult_Bad_Arguments;
-    if (rc)
-        return HapResult_Internal_Error;
-    if (dst != rgba && hapgpu_rt_d2h(rt, rgba, dst, rgba_bytes))
-        return HapResult_Internal_Error;
-    if (hapgpu_rt_sync(rt))
-        return HapResult_Internal_Error;
-    return HapResult_No_Error;
-}
-
-unsigned hapb_decompress_rgba_half(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes,
-                                   unsigned format, unsigned width, unsigned height, void *rgbah, unsigned long row_bytes)
-{
-    hapgpu_rt *rt = ctx->rt;
-    size_t need, bytes;
-    const void *src = texture;
-    void *dst = rgbah;
-    int rc;
-    if (context_busy(ctx, NULL, 0))
-        return HapResult_Internal_Error;
-    if (!texture || !rgbah || width == 0 || height == 0 || (width & 3u) || (height & 3u) ||
-        row_bytes < (unsigned long)width * 8ul || (row_bytes & 15u) ||
-        (format != HapTextureFormat_RGB_BPTC_UNSIGNED_FLOAT && format != HapTextureFormat_RGB_BPTC_SIGNED_FLOAT))
-        return HapResult_Bad_Arguments;
-    need = (size_t)(width / 4u) * (height / 4u) * 16u;
-    if (texture_bytes < need)
-        return HapResult_Bad_Arguments;
-    bytes = (size_t)row_bytes * (height - 1u) + (size_t)width * 8u;
-    if (!is_dev(ctx, texture)) {
-        void *s = hapgpu_rt_device_scratch(rt, D_BC_TEX, need);
-        if (!s || hapgpu_rt_h2d(rt, s, texture, need))
-            return HapResult_Internal_Error;
-        src = s;
-    }
-    if (!is_dev(ctx, rgbah)) {
-        dst = hapgpu_rt_device_scratch(rt, D_RGBA_STAGE, bytes);
-        if (!dst)
-            return HapResult_Internal_Error;
-    }
-    rc = hapgpu_k_block_decode_half(rt, src, width, height, format, dst, row_bytes);
+    t.one[0] = (uint64_t)(uintptr_t)src;
+    t.one[1] = (uint64_t)(uintptr_t)asrc;
+    t.one[2] = (uint64_t)(uintptr_t)dst;
+    rc = hapgpu_k_block_decode(rt, &t, 1u, alpha != NULL, width, height, format, row_bytes);
     if (rc == 1)
         return HapResult_Bad_Arguments;
     if (rc)
         return HapResult_Internal_Error;
     /* (row by row when the client's rows are longer than the picture's: what lies between them is not ours) */
-    if (dst != rgbah && (row_bytes == (unsigned long)width * 8ul ? hapgpu_rt_d2h(rt, rgbah, dst, bytes)
-                                                                  : hapgpu_rt_d2h_rows(rt, rgbah, row_bytes, dst, row_bytes,
-                                                                                       (size_t)width * 8u, height)))
+    if (dst != picture && (row_bytes == pixel_row ? hapgpu_rt_d2h(rt, picture, dst, picture_bytes)
+                                                  : hapgpu_rt_d2h_rows(rt, picture, row_bytes, dst, row_bytes, pixel_row,
+                                                                       height)))
         return HapResult_Internal_Error;
     if (hapgpu_rt_sync(rt))
         return HapResult_Internal_Error;
@@ -890,7 +880,6 @@ unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
         return HapResult_Bad_Arguments;
     }
     for (i = 0; i < count; i++) {
-        size_t block;
         /* (BC7 only when asked, and alone: no Hap variant pairs it with a second texture) */
         const int bptc = (flags & HAPGPU_ENCODE_BPTC_BLOCKS) && count == 1u && formats[i] == HapTextureFormat_RGBA_BPTC_UNORM;
         if (formats[i] != HapTextureFormat_RGB_DXT1 && formats[i] != HapTextureFormat_RGBA_DXT5 &&
@@ -899,8 +888,7 @@ unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                 results[f] = HapResult_Bad_Arguments;
             return HapResult_Bad_Arguments;
         }
-        block = (formats[i] == HapTextureFormat_RGB_DXT1 || formats[i] == HapTextureFormat_A_RGTC1) ? 8u : 16u;
-        tex_bytes[i] = (unsigned long)((size_t)(width / 4u) * (height / 4u) * block);
+        tex_bytes[i] = (unsigned long)((size_t)(width / 4u) * (height / 4u) * hapf_block_bytes(formats[i]));
         tex_off[i] = per_frame;
         per_frame += align_up(tex_bytes[i], 256);
     }
@@ -1815,15 +1803,6 @@ fail_alloc:
 #define RGBA_SLICE_BYTES ((size_t)4u << 30)     /* block textures held at a time */
 #define PICTURE_KINDS_MAX 4u                    /* texture formats one road decodes */
 
-/* What a road from frames to pictures takes and makes: its pictures' texel size, the texture formats it decodes (one
-   block-decode launch per format present in a slice) and which of them may come with an RGTC1 alpha plane. */
-typedef struct picture_road {
-    unsigned pixel_bytes;       /* 4: RGBA8 (hapgpu_k_block_decode_batch), 8: RGBA16F (..._half_batch) */
-    unsigned kind_count;
-    const unsigned *kinds;
-    unsigned paired_kinds;      /* bit k: kinds[k] may have an alpha plane (textureCount 2) */
-} picture_road;
-
 static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
                                 const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
                                 unsigned width, unsigned height, unsigned long row_bytes, unsigned *results,
@@ -1836,7 +1815,7 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
     unsigned long *in_bytes, *caps, *used;
     void **outs;
     unsigned *idx, *fmts, *res;
-    const size_t pixel_row = (size_t)width * road->pixel_bytes;
+    const size_t pixel_row = (size_t)width * texel_bytes(road->kinds[0]);
     if (frame_count == 0)
         return HapResult_No_Error;
     if (!results)
@@ -1933,7 +1912,7 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
                    same geometry */
                 if (r == HapResult_No_Error &&
                     (k == road->kind_count ||
-                     used[e] != blocks * (fmt == HapTextureFormat_RGB_DXT1 ? 8u : 16u) ||
+                     used[e] != blocks * hapf_block_bytes(fmt) ||
                      (texture_count == 2 && (fmts[e + 1] != HapTextureFormat_A_RGTC1 || used[e + 1] != blocks * 8u))))
                     r = HapResult_Bad_Arguments;
                 if (r == HapResult_No_Error && !is_dev(ctx, dst)) {
@@ -1956,12 +1935,11 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
             if (present) {
                 rc |= hapgpu_rt_h2d(rt, dtab, htab, tab_bytes);
                 for (k = 0; k < road->kind_count; k++)
-                    if (present & (1u << k))
-                        rc |= road->pixel_bytes == 8u ?
-                              hapgpu_k_block_decode_half_batch(rt, dtab + (size_t)k * 3u * n, n, width, height, road->kinds[k],
-                                                               row_bytes) :
-                              hapgpu_k_block_decode_batch(rt, dtab + (size_t)k * 3u * n, n, texture_count == 2, width, height,
-                                                          road->kinds[k], row_bytes);
+                    if (present & (1u << k)) {
+                        const uint64_t *col = dtab + (size_t)k * 3u * n;
+                        const HapGpuPictureTable t = {{col, col + n, col + 2u * (size_t)n}, {0u, 0u, 0u}};
+                        rc |= hapgpu_k_block_decode(rt, &t, n, texture_count == 2, width, height, road->kinds[k], row_bytes);
+                    }
                 for (f = 0; f < n; f++)
                     if (results[done + f] == HapResult_No_Error && stage && !is_dev(ctx, rgba_frames[done + f])) {
                         /* (row by row when the client's rows are longer than the picture's: what lies between them -- the
@@ -1991,9 +1969,7 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                           const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
                           unsigned width, unsigned height, unsigned long row_bytes, unsigned *results, unsigned flags)
 {
-    static const unsigned kinds[4] = {HapTextureFormat_RGB_DXT1, HapTextureFormat_RGBA_DXT5, HapTextureFormat_YCoCg_DXT5,
-                                      HapTextureFormat_RGBA_BPTC_UNORM};
-    const picture_road road = {4u, (flags & HAPGPU_DECODE_BPTC_PICTURES) ? 4u : 3u, kinds, 0x7u};
+    const picture_road road = {(flags & HAPGPU_DECODE_BPTC_PICTURES) ? 4u : 3u, k_rgba_kinds, 0x7u};
     return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, rgba_frames, width, height, row_bytes,
                            results, flags, &road);
 }
@@ -2003,8 +1979,7 @@ unsigned hapb_decode_rgba_half(HapGpuContext *ctx, unsigned frame_count, const v
                                const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,
                                unsigned long row_bytes, unsigned *results, unsigned flags)
 {
-    static const unsigned kinds[2] = {HapTextureFormat_RGB_BPTC_UNSIGNED_FLOAT, HapTextureFormat_RGB_BPTC_SIGNED_FLOAT};
-    const picture_road road = {8u, 2u, kinds, 0u};
+    const picture_road road = {2u, k_half_kinds, 0u};
     return decode_pictures(ctx, frame_count, inputs, input_bytes, 1u, pictures, width, height, row_bytes, results, flags,
                            &road);
 }

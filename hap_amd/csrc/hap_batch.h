@@ -86,12 +86,11 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
 unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width, unsigned height,
                             unsigned long row_bytes, unsigned format, void *output,
                             unsigned long output_bytes, unsigned long *used, int synchronise, unsigned flags);
+/* one texture -> one picture: half == 0 RGBA8 (DXT1, DXT5, YCoCg-DXT5 with an optional RGTC1 alpha plane, BC7),
+   half != 0 RGBA16F (BC6H unsigned or signed, no alpha plane) */
 unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
                               const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                              void *rgba, unsigned long row_bytes);
-/* BC6H (unsigned or signed) -> RGBA16F */
-unsigned hapb_decompress_rgba_half(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes,
-                                   unsigned format, unsigned width, unsigned height, void *rgbah, unsigned long row_bytes);
+                              void *picture, unsigned long row_bytes, int half);
 unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
                           unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
                           const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,

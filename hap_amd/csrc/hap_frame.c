@@ -118,14 +118,14 @@ void hapf_write_section(uint8_t *p, unsigned header_len, uint32_t length, unsign
 }
 
 /* reference hap.c:215-261 */
-static const struct { unsigned nibble, format; } k_formats[] = {
-    {0xB, HapTextureFormat_RGB_DXT1},
-    {0xE, HapTextureFormat_RGBA_DXT5},
-    {0xF, HapTextureFormat_YCoCg_DXT5},
-    {0x1, HapTextureFormat_A_RGTC1},
-    {0xC, HapTextureFormat_RGBA_BPTC_UNORM},
-    {0x2, HapTextureFormat_RGB_BPTC_UNSIGNED_FLOAT},
-    {0x3, HapTextureFormat_RGB_BPTC_SIGNED_FLOAT},
+static const struct { unsigned nibble, format, block_bytes; } k_formats[] = {
+    {0xB, HapTextureFormat_RGB_DXT1, 8},
+    {0xE, HapTextureFormat_RGBA_DXT5, 16},
+    {0xF, HapTextureFormat_YCoCg_DXT5, 16},
+    {0x1, HapTextureFormat_A_RGTC1, 8},
+    {0xC, HapTextureFormat_RGBA_BPTC_UNORM, 16},
+    {0x2, HapTextureFormat_RGB_BPTC_UNSIGNED_FLOAT, 16},
+    {0x3, HapTextureFormat_RGB_BPTC_SIGNED_FLOAT, 16},
 };
 
 unsigned hapf_format_from_nibble(unsigned nibble)
@@ -146,6 +146,16 @@ unsigned hapf_nibble_from_format(unsigned format)
     return 0;
 }
 
+/* bytes of one 4x4 block: 16 for formats the table does not know, as the reference's size arithmetic (hap.c:277-300) */
+size_t hapf_block_bytes(unsigned format)
+{
+    size_t i;
+    for (i = 0; i < sizeof(k_formats) / sizeof(k_formats[0]); i++)
+        if (k_formats[i].format == format)
+            return k_formats[i].block_bytes;
+    return 16u;
+}
+
 /* ---------------------------------------------------------- size maths -- */
 
 /* snappy_max_compressed_length of libsnappy: 32 + n + n/6 (call site hap.c:313) */
@@ -157,8 +167,7 @@ size_t hapf_instructions_length(unsigned chunks) { return 5u * (size_t)chunks + 
 /* reference hap.c:277-300 */
 unsigned hapf_limit_chunk_count(size_t bytes, unsigned format, unsigned chunks)
 {
-    size_t block = (format == HapTextureFormat_RGB_DXT1 || format == HapTextureFormat_A_RGTC1) ? 8u : 16u;
-    unsigned long blocks = (unsigned long)(bytes / block);
+    unsigned long blocks = (unsigned long)(bytes / hapf_block_bytes(format));
     if (chunks > 3355431u)
         chunks = 3355431u;
     while (blocks % chunks)

@@ -63,6 +63,7 @@ int hapf_read_section(const uint8_t *p, uint32_t available, hapf_section *out);
 void hapf_write_section(uint8_t *p, unsigned header_len, uint32_t length, unsigned type);
 unsigned hapf_format_from_nibble(unsigned nibble);
 unsigned hapf_nibble_from_format(unsigned format);
+size_t hapf_block_bytes(unsigned format);     /* 8: RGB_DXT1, A_RGTC1; 16: every other value */
 size_t hapf_snappy_bound(size_t n);
 size_t hapf_instructions_length(unsigned chunks);
 unsigned hapf_limit_chunk_count(size_t bytes, unsigned format, unsigned chunks);

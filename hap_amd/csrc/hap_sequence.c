@@ -453,10 +453,8 @@ unsigned int HapGpuEncodeSequence(HapGpuContext *ctx, HapSequenceWriter *w, unsi
     if (!ctx || !w || !rgba_frames || count == 0 || texture_count == 0 || texture_count > 2 || !formats || !compressors ||
         !chunk_counts || width == 0 || height == 0 || (width & 3u) || (height & 3u))
         return HapResult_Bad_Arguments;
-    for (i = 0; i < texture_count; i++) {
-        const unsigned long block = (formats[i] == HapTextureFormat_RGB_DXT1 || formats[i] == HapTextureFormat_A_RGTC1) ? 8ul : 16ul;
-        lengths[i] = (unsigned long)(width / 4u) * (height / 4u) * block;
-    }
+    for (i = 0; i < texture_count; i++)
+        lengths[i] = (unsigned long)(width / 4u) * (height / 4u) * hapf_block_bytes(formats[i]);
     cap = HapMaxEncodedLength(texture_count, lengths, (unsigned int *)formats, (unsigned int *)chunk_counts);
     if (cap == 0)
         return HapResult_Bad_Arguments;

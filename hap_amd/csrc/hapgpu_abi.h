@@ -286,32 +286,28 @@ int hapgpu_rt_graph_end(hapgpu_rt *rt, uint64_t key, int failed);
 void hapgpu_rt_graphs_disable(hapgpu_rt *rt);
 
 /* kernels: all asynchronous on the runtime's stream; 0 = launched */
-int hapgpu_k_block_encode(hapgpu_rt *rt, const void *rgba, unsigned width, unsigned height,
-                          size_t row_bytes, unsigned hap_texture_format, void *out);
-/* pictures of one geometry in one launch; sources / outputs: DEVICE arrays of device addresses (0 = skip) */
-int hapgpu_k_block_encode_batch(hapgpu_rt *rt, const uint64_t *sources, const uint64_t *outputs, unsigned pictures,
-                                unsigned width, unsigned height, size_t row_bytes, unsigned hap_texture_format, int wide);
-/* RGBA8 -> BC7 (RGBA_BPTC_UNORM, bptc_encode.hip): one picture (out 16-byte aligned), and pictures of one geometry from
-   device address arrays as for hapgpu_k_block_encode_batch */
-int hapgpu_k_bptc_encode(hapgpu_rt *rt, const void *rgba, unsigned width, unsigned height, size_t row_bytes, void *out);
-int hapgpu_k_bptc_encode_batch(hapgpu_rt *rt, const uint64_t *sources, const uint64_t *outputs, unsigned pictures,
-                               unsigned width, unsigned height, size_t row_bytes, int wide);
-/* Hap Q Alpha: scaled YCoCg-DXT5 + RGTC1 alpha plane of every picture from one read of its RGBA */
-int hapgpu_k_block_encode_batch_ycocg_alpha(hapgpu_rt *rt, const uint64_t *sources, const uint64_t *colour_outputs,
-                                            const uint64_t *alpha_outputs, unsigned pictures, unsigned width,
-                                            unsigned height, size_t row_bytes, int wide);
-int hapgpu_k_block_decode(hapgpu_rt *rt, const void *blocks, const void *alpha, unsigned width, unsigned height,
-                          unsigned hap_texture_format, void *rgba, size_t row_bytes);
-/* pictures of one format and geometry in one launch; table: DEVICE array of device addresses, [textures][alpha planes]
-   [pictures], `pictures` entries each (texture 0 = skip the picture) */
-int hapgpu_k_block_decode_batch(hapgpu_rt *rt, const uint64_t *table, unsigned pictures, int with_alpha, unsigned width,
-                                unsigned height, unsigned hap_texture_format, size_t row_bytes);
-/* BC6H (RGB_BPTC_UNSIGNED_FLOAT / RGB_BPTC_SIGNED_FLOAT) -> RGBA16F, 8 bytes a texel: one picture, and pictures of one
-   format and geometry from a table as above (its alpha column unused) */
-int hapgpu_k_block_decode_half(hapgpu_rt *rt, const void *blocks, unsigned width, unsigned height,
-                               unsigned hap_texture_format, void *rgbah, size_t row_bytes);
-int hapgpu_k_block_decode_half_batch(hapgpu_rt *rt, const uint64_t *table, unsigned pictures, unsigned width,
-                                     unsigned height, unsigned hap_texture_format, size_t row_bytes);
+
+/* [device] Addresses of a block-codec launch: three columns of `pictures` device addresses, each either a DEVICE array
+   (column[c]) or, for one picture, the address itself (one[c], read where column[c] is NULL).  Encode: sources, outputs,
+   second outputs (Hap Q Alpha's RGTC1 plane); decode: textures, alpha planes, pictures.  A source or texture address of
+   0 skips the picture, and so does an encode output of 0. */
+typedef struct HapGpuPictureTable {
+    const uint64_t *column[3];
+    uint64_t one[3];
+} HapGpuPictureTable;
+
+/* RGBA8 -> blocks of `hap_texture_format`: RGB_DXT1, RGBA_DXT5, YCoCg_DXT5, A_RGTC1 or RGBA_BPTC_UNORM (BC7);
+   YCoCg_DXT5 with_alpha: Hap Q Alpha, the RGTC1 alpha plane to the second outputs from the same read of every picture.
+   Sources and row_bytes 4-byte aligned, outputs 8- (DXT1, RGTC1) or 16-byte aligned; wide != 0 promises 16-byte aligned
+   sources and row pitch. */
+int hapgpu_k_block_encode(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, unsigned width,
+                          unsigned height, size_t row_bytes, unsigned hap_texture_format, int with_alpha, int wide);
+/* blocks of `hap_texture_format` -> pictures: RGB_DXT1, RGBA_DXT5, YCoCg_DXT5 (with_alpha: the RGTC1 plane supplies A)
+   and RGBA_BPTC_UNORM to RGBA8, 4 bytes a texel; RGB_BPTC_UNSIGNED_FLOAT / RGB_BPTC_SIGNED_FLOAT (BC6H) to RGBA16F, 8
+   bytes a texel.  Textures 8- (DXT1) or 16-byte aligned, alpha planes 8-byte aligned, pictures and row_bytes 16-byte
+   aligned. */
+int hapgpu_k_block_decode(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, int with_alpha,
+                          unsigned width, unsigned height, unsigned hap_texture_format, size_t row_bytes);
 /* group_tables: HAP_GROUP_TABLE_BYTES bytes per fragment (same indexing as frag_sizes), written for textures whose reserved bit 20 is set */
 int hapgpu_k_snappy_compress(hapgpu_rt *rt, const HapGpuFrameEnc *frames, unsigned frame_count,
                              unsigned max_frags_per_texture, unsigned frag_log2,

@@ -52,10 +52,18 @@ int hapgpu_snappy_compress_blocks(const HapGpuFrameEnc *frames, unsigned frame_c
 // snappy_decode_fields.hip
 int hapgpu_snappy_decode_fields(const HapGpuDecodeUnit *units, unsigned unit_count, HapGpuDecodeJob *jobs,
                                 unsigned fields_kinds, hipStream_t stream);
-// bptc_decode.hip: BC7 -> RGBA8 (one picture; pictures of one geometry from a bc_decode_batch_kernel table)
-void hapgpu_bptc_decode(const void *blocks, unsigned bx, unsigned by, void *rgba, size_t row_bytes, hipStream_t stream);
-void hapgpu_bptc_decode_batch(const uint64_t *table, unsigned pictures, unsigned bx, unsigned by, size_t row_bytes,
-                              hipStream_t stream);
+// address column c of picture blockIdx.z of a block-codec launch: one scalar choice, no table for a single picture
+__device__ __forceinline__ uint64_t picture_address(const HapGpuPictureTable &t, unsigned c)
+{
+    return t.column[c] ? t.column[c][blockIdx.z] : t.one[c];
+}
+// the BC7 and BC6H launches of hapgpu_k_block_encode / hapgpu_k_block_decode (arguments checked there)
+void hapgpu_launch_bptc_encode(const HapGpuPictureTable &t, unsigned pictures, unsigned bx, unsigned by,
+                               size_t row_bytes, bool wide, hipStream_t stream);      // bptc_encode.hip
+void hapgpu_launch_bptc_decode(const HapGpuPictureTable &t, unsigned pictures, unsigned bx, unsigned by,
+                               size_t row_bytes, hipStream_t stream);                 // bptc_decode.hip
+void hapgpu_launch_bc6h_decode(const HapGpuPictureTable &t, unsigned pictures, bool is_signed, unsigned bx,
+                               unsigned by, size_t row_bytes, hipStream_t stream);    // bc6h_decode.hip
 // snappy_decode.hip
 int hapgpu_group_tables_from_records(HapGpuDecodeUnit *units, unsigned unit_count, const HapGpuDecodeJob *jobs,
                                      const uint32_t *work, unsigned work_slots, const void *recs, const void *joins,

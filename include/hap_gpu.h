@@ -191,8 +191,9 @@ unsigned int HapGpuCompressRGBAFlags(HapGpuContext *context,
  * RGB) or RGBA_BPTC_UNORM (BC7, Hap R: all eight modes; reserved blocks give (0, 0, 0, 0));
  * alphaTexture: optional A_RGTC1 plane that supplies A (Hap Q Alpha), else NULL / 0 -- Bad_Arguments
  * with BC7.  Device textures of 16-byte blocks must be 16-byte aligned, DXT1 ones 8-byte aligned.
- * rgba must be 16-byte aligned with rowBytes a multiple of 16.  Host or device pointers.  BC6H
- * textures are Bad_Arguments here: HapGpuDecompressRGBAHalf expands them. */
+ * rgba must be 16-byte aligned with rowBytes a multiple of 16.  Host or device pointers.  Only the
+ * picture's bytes of each row are written, host or device.  BC6H textures are Bad_Arguments here:
+ * HapGpuDecompressRGBAHalf expands them. */
 unsigned int HapGpuDecompressRGBA(HapGpuContext *context,
                                   const void *texture, unsigned long textureBytes, unsigned int textureFormat,
                                   const void *alphaTexture, unsigned long alphaBytes,

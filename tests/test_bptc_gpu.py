@@ -1,6 +1,8 @@
 """Hap R (BC7) to RGBA pictures on the GPU: HapGpuDecompressRGBA with RGBA_BPTC_UNORM textures and
 HapGpuDecodeFramesRGBA with HAPGPU_DECODE_BPTC_PICTURES, bit-exact with the CPU reference of tests/_bptc.py (itself
 pinned to Pillow by tests/test_bptc_reference.py)."""
+import itertools
+
 import numpy as np
 import pytest
 
@@ -77,10 +79,11 @@ def test_host_and_device_textures_and_pictures(ctx, size):
     dtex = dev(data)
     r, got = ctx.decompress_rgba(dtex, L.FMT_BC7, w, h)
     assert r == 0 and np.array_equal(np.frombuffer(got, dtype=np.uint8).reshape(h, w, 4), want)
-    # host texture and device texture into device pictures, tight and with 64 guard bytes after every row
+    # host texture and device texture into device and host pictures, tight and with 64 guard bytes after every row:
+    # only the picture's bytes of each row are written
     for tex in (data, dtex):
-        for stride in (w * 4, w * 4 + 64):
-            out = torch.full((h * stride + 256,), 0xEE, dtype=torch.uint8, device="cuda")
+        for stride, where in itertools.product((w * 4, w * 4 + 64), ("cuda", "cpu")):
+            out = torch.full((h * stride + 256,), 0xEE, dtype=torch.uint8, device=where)
             torch.cuda.synchronize()
             r, _ = ctx.decompress_rgba(tex, L.FMT_BC7, w, h, rgba=out, row_bytes=stride)
             assert r == 0
