@@ -34,6 +34,14 @@ __device__ __forceinline__ int expand5(int q) { return (q << 3) | (q >> 2); }
 __device__ __forceinline__ int expand6(int q) { return (q << 2) | (q >> 4); }
 
 
+// Eight 3-bit fields holding (r + 1) mod 8 of the ramp positions r = 0..7 -> their S3TC codes 0->0, 7->1, r->r+1, all at
+// once: (r + 1) mod 8 is the code already for r = 1..6; the two ends come out as 1 and 0 and want 0 and 1 -- the fields
+// whose upper two bits are clear get their low bit turned over.  (Was a byte-table v_perm per pixel.)
+__device__ __forceinline__ unsigned ramp_codes(unsigned w)
+{
+    return w ^ (~((w >> 1) | (w >> 2)) & 0x249249u);
+}
+
 // 8-byte alpha-style block: a0, a1, 16 x 3-bit codes (S3TC alpha / RGTC1 layout).
 __device__ __forceinline__ uint2 alpha_block(const int (&a)[16])
 {
@@ -49,7 +57,7 @@ __device__ __forceinline__ uint2 alpha_block(const int (&a)[16])
         // oracle/bc_oracle.c: with d = a0 - a1 and u = a0 - a (0..d), the ramp position is
         // r = ((14 u + max(d - 6, 0)) * m) >> 20, m = floor(2^19 / d) + 1 -- the pixel's place on the ramp rounded to
         // the nearest of its 8 steps (x * m >> 20 = x / 2d), thresholds moved by the 3/7 the decoder's steps are
-        // rounded down on average; 0..7 by construction.  Per pixel: one multiply-add, shift, code, insert.
+        // rounded down on average; 0..7 by construction.  Per pixel: one multiply-add, shift, insert; the codes eight pixels at a time.
         const int d = a0 - a1;
         // floor(2^19 / d): the reciprocal from v_rcp_f32, made exact
         unsigned q = (unsigned)(524288.0f * __builtin_amdgcn_rcpf((float)d));
@@ -58,20 +66,20 @@ __device__ __forceinline__ uint2 alpha_block(const int (&a)[16])
         const unsigned m = q + 1u;
         // x = (14 (a0 - a) + bias) m as one multiply-add in a
         const int neg_m14 = -(int)(14u * m);                             // |.| < 2^23
-        const int start = mad24(a0, (int)(14u * m), (int)__umul24((unsigned)max(d - 6, 0), m));
+        // (+ 2^20: the position comes out as r + 1, 1..8, and x stays below 2^24)
+        const int start = mad24(a0, (int)(14u * m), (int)__umul24((unsigned)max(d - 6, 0), m)) + (1 << 20);
 #pragma unroll
         for (int i = 0; i < 16; i++) {
-            const unsigned r = (unsigned)mad24(a[i], neg_m14, start) >> 20;
-            // ramp position -> S3TC code: 0->0, 7->1, r->r+1 (byte table 00 02 03 04 | 05 06 07 01, one v_perm)
-            const unsigned code = __builtin_amdgcn_perm(0x01070605u, 0x04030200u, r);
-            // three bits in from the top: after 8 pixels the codes occupy bits 31:8, pixel 0 lowest
+            const unsigned r1 = (unsigned)mad24(a[i], neg_m14, start) >> 20;
+            // three bits in from the top (the funnel shift drops bit 3 of an 8): after 8 pixels the fields occupy
+            // bits 31:8, pixel 0 lowest
             if (i < 8)
-                lo24 = __builtin_amdgcn_alignbit(code, lo24, 3);
+                lo24 = __builtin_amdgcn_alignbit(r1, lo24, 3);
             else
-                hi24 = __builtin_amdgcn_alignbit(code, hi24, 3);
+                hi24 = __builtin_amdgcn_alignbit(r1, hi24, 3);
         }
-        lo24 >>= 8;
-        hi24 >>= 8;
+        lo24 = ramp_codes(lo24 >> 8);
+        hi24 = ramp_codes(hi24 >> 8);
     }
     const unsigned long long bits = (unsigned long long)lo24 | ((unsigned long long)hi24 << 24);
     const unsigned long long v = (unsigned long long)(unsigned)a0 | ((unsigned long long)(unsigned)a1 << 8) | (bits << 16);
@@ -93,15 +101,27 @@ struct projection {
     unsigned m24;       // floor(3 * 2^24 / len2)
 };
 
+// floor(3 * 2^24 / len2) from the float reciprocal, corrected with the integer remainder (off by one at most)
+__device__ __forceinline__ unsigned index_scale(unsigned len2)
+{
+    unsigned m = (unsigned)(50331648.0f * __builtin_amdgcn_rcpf((float)len2));
+    const int rem = (int)(50331648u - m * len2);
+    m += (rem >= (int)len2 ? 1u : 0u) - (rem < 0 ? 1u : 0u);
+    return m;
+}
+
+// CHANNELS: 3, or 2 for the pairs of a scaled YCoCg block, whose third byte is zero on both sides (a channel with
+// direction 0 adds nothing to any of the sums)
+template <int CHANNELS = 3>
 __device__ __forceinline__ projection make_projection(unsigned p0, unsigned p1)
 {
     projection pr;
     // per-byte |p0 - p1| and the sign bytes: 9-bit lanes of a 32-bit subtraction would borrow across bytes, so per channel
-    int dir[3];
+    int dir[CHANNELS];
     unsigned adir = 0, flip = 0;
     int neg = 0, base = 0;
 #pragma unroll
-    for (int c = 0; c < 3; c++) {
+    for (int c = 0; c < CHANNELS; c++) {
         const int a = (int)((p0 >> (8 * c)) & 255u), b = (int)((p1 >> (8 * c)) & 255u);
         dir[c] = a - b;
         const int ad = abs(dir[c]);
@@ -112,15 +132,11 @@ __device__ __forceinline__ projection make_projection(unsigned p0, unsigned p1)
     }
     const unsigned len2 = __builtin_amdgcn_udot4(adir, adir, 0u, false);                 // 16 .. 195075
     const unsigned sixth = __umulhi(len2, 0xAAAAAAABu) >> 2;                             // len2 / 6
-    // floor(3 * 2^24 / len2) from the float reciprocal, corrected with the integer remainder (off by one at most)
-    unsigned m = (unsigned)(50331648.0f * __builtin_amdgcn_rcpf((float)len2));
-    const int rem = (int)(50331648u - m * len2);
-    m += (rem >= (int)len2 ? 1u : 0u) - (rem < 0 ? 1u : 0u);
     pr.adir = adir;
     pr.flip = flip;
     pr.start = (int)sixth - base - 255 * neg;
     pr.top = (int)(len2 + sixth);
-    pr.m24 = m;
+    pr.m24 = index_scale(len2);
     return pr;
 }
 
@@ -229,26 +245,34 @@ __device__ __forceinline__ uint2 ycocg_colour_block(const unsigned (&cc)[16])
     int ins = (hi_o - lo_o) >> 4; lo_o += ins; hi_o -= ins;
     ins = (hi_g - lo_g) >> 4; lo_g += ins; hi_g -= ins;
     const int ag = cov < 0 ? lo_g : hi_g, bg = cov < 0 ? hi_g : lo_g;
-    const unsigned qa = (unsigned)(quant5(hi_o) << 11 | quant6(ag) << 5 | (s - 1));
-    const unsigned qb = (unsigned)(quant5(lo_o) << 11 | quant6(bg) << 5 | (s - 1));
+    const int qo_a = quant5(hi_o), qo_b = quant5(lo_o), qg_a = quant6(ag), qg_b = quant6(bg);
+    const unsigned qa = (unsigned)(qo_a << 11 | qg_a << 5 | (s - 1));
+    const unsigned qb = (unsigned)(qo_b << 11 | qg_b << 5 | (s - 1));
     const unsigned c0 = max(qa, qb), c1 = min(qa, qb);
     unsigned idx = 0;
     if (c0 != c1) {
-        const projection pr = make_projection(expand_565(c0, false), expand_565(c1, false));
         // project4 on the scaled pixels v = (c - 128) s + 128 without forming them, and without complementing: with the
-        // direction SIGNED per channel (16-bit pair, one v_dot2 on the packed Co | Cg pair) the projection is
-        // t = s (c . dir) + K, K = start + sum |dir| (128 - 128 s) over the channels that point up and
-        // |dir| (127 + 128 s) over the ones that point down (project4's complement, multiplied out).  The dot product
-        // starts from an offset that keeps it non-negative for the unsigned 24-bit multiply; the position is
-        // (t m24) >> 24 = ((c . dir + offset) (s m24) + (K - s offset) m24) >> 24 in 32-bit wrap-around arithmetic (t m24
-        // itself fits).
-        const int a_o = (int)(pr.adir & 255u), a_g = (int)((pr.adir >> 8) & 255u);
-        const bool down_o = (pr.flip & 0x00FFu) != 0u, down_g = (pr.flip & 0xFF00u) != 0u;
-        const pk_i16 dir2 = {(short)(down_o ? -a_o : a_o), (short)(down_g ? -a_g : a_g)};
-        const int K = pr.start + a_o * (down_o ? 127 + 128 * s : 128 - 128 * s) + a_g * (down_g ? 127 + 128 * s : 128 - 128 * s);
+        // direction SIGNED per channel (16-bit pair, one v_dot2 on the packed Co | Cg pair) the projection of
+        // make_projection(expand_565(c0), expand_565(c1)) is t = s (c . dir) + K: the 255 |dir| of project4's
+        // complemented channels and make_projection's - 255 (sum of |dir| over those channels) cancel, which leaves
+        // K = len2 / 6 + sum over the channels of dir (128 - 128 s - p1).  The end entries are expanded from the
+        // quantised channels at hand, in c0 / c1 order, not unpacked from the 5:6:5 words again.
+        // The dot product starts from an offset that keeps it non-negative for the unsigned 24-bit multiply; the
+        // position is (t m24) >> 24 = ((c . dir + offset) (s m24) + (K - s offset) m24) >> 24 in 32-bit wrap-around
+        // arithmetic (t m24 itself fits).
+        const bool sw = qa < qb;                                                             // c0 is qb
+        const int eo_a = expand5(qo_a), eo_b = expand5(qo_b), eg_a = expand6(qg_a), eg_b = expand6(qg_b);
+        const int d_o = sw ? eo_b - eo_a : eo_a - eo_b, d_g = sw ? eg_b - eg_a : eg_a - eg_b;
+        const int p1_o = sw ? eo_a : eo_b, p1_g = sw ? eg_a : eg_b;
+        const unsigned len2 = (unsigned)mad24(d_o, d_o, __mul24(d_g, d_g));                  // 16 .. 130050
+        const int sixth = (int)(__umulhi(len2, 0xAAAAAAABu) >> 2);
+        const unsigned m24 = index_scale(len2);
+        const int centre = 128 - 128 * s;
+        const int K = mad24(d_o, centre - p1_o, mad24(d_g, centre - p1_g, sixth));
+        const pk_i16 dir2 = {(short)d_o, (short)d_g};
         constexpr int kDotOffset = 1 << 17;                                                  // > 2 x 255 x 255
-        const unsigned sm = (unsigned)s * pr.m24;                                            // < 2^24
-        const unsigned Km = (unsigned)(K - s * kDotOffset) * pr.m24;                         // mod 2^32
+        const unsigned sm = (unsigned)s * m24;                                            // < 2^24
+        const unsigned Km = (unsigned)(K - s * kDotOffset) * m24;                         // mod 2^32
         unsigned pos2 = 0;
 #pragma unroll
         for (int i = 0; i < 16; i++) {

@@ -8,6 +8,15 @@ Compiles the file for gfx950 with -gline-tables-only, attributes every instructi
 in front of it and prints VALU / SALU / LDS / VMEM counts per source line (or per named line range).  The counts
 are static (loops once, every inlined layout separately when --func is not given); trip counts are the
 reader's business.  hipcc cross-compiles: no GPU needed.
+
+    python tools/isa_by_line.py --fused-budget [--weights tools/isa_weights_w5.json] [--csrc OTHER/hap_amd/csrc]
+    python tools/isa_by_line.py --resources snappy_compress_blocks.hip [--csrc ...]
+
+The cycle budget of the fused encode kernel (snappy_compress_blocks_kernel<4, YCoCg>, -DSCB_ONLY_FUSED_YCOCG): the same
+attribution, per PHASE (found by anchor text in the sources, so the table follows the code when lines move), each VALU
+instruction weighted by its measured issue cost (tools/micro/valu_rates2.hip at the kernel's five waves per SIMD;
+weights file: opcode -> cycles, "default" for what was not measured), times the phase's trip count for an 8K Hap Q
+fragment.  Also prints the kernel's register and scratch figures from the code object's metadata.
 """
 import collections
 import re
@@ -30,8 +39,192 @@ def classify(op):
     return "other"
 
 
+# Phases of the fused encode kernel: (name, file, anchor text, n-th occurrence, trips per 8K Hap Q fragment).  A phase
+# runs from its anchor's line to the next anchor of the same file.  Trips: 8 steps of 64 blocks; the choose loop 1.2
+# passes, the element list 9.2 turns and the tag walk 7.4 passes (LABNOTES, 8K stream: 470 elements per fragment).
+CORE, SCB = "bc_encode_core.hpp", "snappy_compress_blocks.hip"
+FUSED_PHASES = [
+    ("helpers: mad24 / quant", CORE, "namespace hapbc {", 0, 8.0),
+    ("luma ramp", CORE, "__device__ __forceinline__ uint2 alpha_block", 0, 8.0),
+    ("end points", CORE, "struct projection {", 0, 8.0),
+    ("colour index (RGB)", CORE, "template <bool FLIPPED = false>", 0, 8.0),
+    ("end points", CORE, "__device__ __forceinline__ unsigned pack3", 0, 8.0),
+    ("colour box+covariance (RGB)", CORE, "__device__ __forceinline__ uint2 colour_block", 0, 8.0),
+    ("colour box+covariance", CORE, "__device__ __forceinline__ uint2 ycocg_colour_block", 0, 8.0),
+    ("end points", CORE, "const int mo = lo_o + hi_o", 0, 8.0),
+    ("colour index", CORE, "constexpr int kDotOffset", 0, 8.0),
+    ("YCoCg transform", CORE, "template <int FMT>", 0, 8.0),
+    ("loop+address overhead", SCB, "#include <hip/hip_runtime.h>", 0, 1.0),
+    ("choose", SCB, "__device__ __forceinline__ int scan_add", 0, 1.0),
+    ("nibble transpose", SCB, "// value of lane ^ 4 / ^ 2 / ^ 1", 0, 8.0),
+    ("match compare", SCB, "// 1 where the field differs", 0, 8.0),
+    ("table probe", SCB, "// value of an index field", 0, 8.0),
+    ("loop+address overhead", SCB, "// FUSED >= 0: the texture does not exist yet", 0, 1.0),
+    ("loop+address overhead (step)", SCB, "// ---- 1. match ----", 0, 8.0),
+    ("match compare", SCB, "unsigned differ = 0;", 0, 8.0),
+    ("table probe", SCB, "// table candidates of the index fields", 0, 8.0),
+    ("nibble transpose", SCB, "// nibbles of 8 lanes", 0, 8.0),
+    ("choose", SCB, "// (the table has served", 0, 1.0),
+    ("choose (loop)", SCB, "while (__builtin_amdgcn_ballot_w64(front != 0u)", 0, 1.2),
+    ("choose", SCB, "const unsigned cov = A[0] | A[1]", 0, 1.0),
+    ("choose (element list)", SCB, "while (__builtin_amdgcn_ballot_w64(left != 0u)", 0, 9.2),
+    ("look-back", SCB, "// ---- placed streams", 0, 1.0),
+    ("literal walk", SCB, "// ---- 3a. emit the literal bytes", 0, 1.0),
+    ("literal walk (step)", SCB, "const unsigned hh = 8u * s + (lane >> 3);", 0, 8.0),
+    ("tag walk (set-up)", SCB, "// ---- 3b. emit the elements' tags", 0, 1.0),
+    ("tag walk", SCB, "for (unsigned e0 = 0; e0 < elements; e0 += 64u)", 0, 7.4),
+    ("group table", SCB, "if (want_sizes) {", 0, 1.0),
+]
+
+
+def phase_spans(csrc):
+    """{file: [(first line, last line, name, trips)]} from the anchors."""
+    spans = {}
+    for fname in (CORE, SCB):
+        lines = open(csrc + "/" + fname).read().splitlines()
+        marks = []
+        for name, f, anchor, nth, trips in FUSED_PHASES:
+            if f != fname:
+                continue
+            hits = [i + 1 for i, l in enumerate(lines) if anchor in l]
+            if len(hits) <= nth:
+                raise SystemExit("isa_by_line: anchor %r not found in %s" % (anchor, fname))
+            marks.append((hits[nth], name, trips))
+        marks.sort()
+        spans[fname] = [(lo, (marks[i + 1][0] - 1) if i + 1 < len(marks) else len(lines), name, trips)
+                        for i, (lo, name, trips) in enumerate(marks)]
+    return spans
+
+
+def base_op(op):
+    for suf in ("_e32", "_e64", "_sdwa", "_dpp"):
+        if op.endswith(suf):
+            return op[: -len(suf)] + ("_dpp" if suf == "_dpp" else "")
+    return op
+
+
+def fused_budget(args):
+    import json
+    import os
+    here = os.path.dirname(os.path.abspath(__file__))
+    csrc = os.path.join(here, "..", "hap_amd", "csrc")
+    wfile = os.path.join(here, "isa_weights_w5.json")
+    for i, a in enumerate(args):
+        if a == "--csrc":                   # another checkout's hap_amd/csrc (the parent's table with the same tool)
+            csrc = args[i + 1]
+    defs = [a for a in args if a.startswith("-D")]
+    if not any(a.startswith("-DSCB_ONLY_FUSED") for a in defs):
+        defs.append("-DSCB_ONLY_FUSED_YCOCG")
+    for i, a in enumerate(args):
+        if a == "--weights":
+            wfile = args[i + 1]
+    weights = json.load(open(wfile))
+    default_w = weights["default"]
+    with tempfile.NamedTemporaryFile(suffix=".s") as tmp:
+        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-gline-tables-only",
+               "-DHAP_MEASUREMENT_BUILD", "-I" + csrc, "-S", "--cuda-device-only", "-o", tmp.name, os.path.join(csrc, SCB)] + defs
+        subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
+        text = open(tmp.name).read().splitlines()
+    spans = phase_spans(csrc)
+    files, cur = {}, None
+    acc = collections.OrderedDict()
+    unweighted = collections.Counter()
+    meta = []
+    for line in text:
+        s = line.strip()
+        m = re.match(r"\.file\s+(\d+)\s+\"([^\"]*)\"(?:\s+\"([^\"]*)\")?", s)
+        if m:
+            files[int(m.group(1))] = (m.group(3) or m.group(2)).split("/")[-1]
+            continue
+        m = re.match(r"\.loc\s+(\d+)\s+(\d+)\s+(\d+)", s)
+        if m:
+            cur = (files.get(int(m.group(1)), "?"), int(m.group(2)))
+            continue
+        if re.match(r"\.(name|vgpr_count|sgpr_count|private_segment_fixed_size|group_segment_fixed_size):", s):
+            meta.append(s)
+        if not s or s.startswith((".", ";", "//")) or s.endswith(":") or cur is None:
+            continue
+        op = s.split()[0]
+        kind = classify(op)
+        name, trips = "other: " + cur[0], 1.0
+        for lo, hi, nm, tr in spans.get(cur[0], ()):
+            if lo <= cur[1] <= hi:
+                name, trips = nm, tr
+                break
+        row = acc.setdefault(name, {"trips": trips, "valu": 0, "cycles": 0.0, "salu": 0, "lds": 0, "vmem": 0, "nop": 0})
+        if kind == "valu":
+            w = weights.get(base_op(op))
+            if w is None:
+                w = default_w
+                unweighted[base_op(op)] += 1
+            row["valu"] += 1
+            row["cycles"] += w
+        elif kind == "wait":
+            row["nop"] += 1 if op == "s_nop" else 0
+        elif kind in row:
+            row[kind] += 1
+    print("weights: %s (%d opcodes measured, default %.2f)" % (os.path.basename(wfile), len(weights) - 1, default_w))
+    print("%-30s %6s %7s %9s | %9s %11s | %5s %5s %5s %5s" % ("phase", "trips", "valu", "cycles", "valu/frag", "cycles/frag",
+                                                              "salu", "lds", "vmem", "s_nop"))
+    print("(valu, cycles: per trip -- phases with 8 trips are the eight unrolled steps, listed as one step's share)")
+    tv = tc = 0.0
+    for name, r in sorted(acc.items(), key=lambda kv: -frag(kv[1], "cycles")):
+        per = 8.0 if r["trips"] == 8.0 else 1.0
+        print("%-30s %6.1f %7.1f %9.1f | %9.0f %11.0f | %5d %5d %5d %5d" % (name, r["trips"], r["valu"] / per, r["cycles"] / per,
+                                                                         frag(r, "valu"), frag(r, "cycles"), r["salu"], r["lds"],
+                                                                         r["vmem"], r["nop"]))
+        tv += frag(r, "valu"); tc += frag(r, "cycles")
+    print("%-30s %6s %7s %9s | %9.0f %11.0f |" % ("per fragment", "", "", "", tv, tc))
+    for m in meta:
+        print("  " + m)
+    if unweighted:
+        print("opcodes at the default weight: " + ", ".join("%s x%d" % kv for kv in unweighted.most_common()))
+
+
+def frag(r, key):
+    """A phase's share of one fragment: the eight steps are unrolled (their static count IS the fragment's), loops run
+    `trips` times."""
+    return r[key] * (1.0 if r["trips"] == 8.0 else r["trips"])
+
+
+def resources(args):
+    """--resources FILE.hip [-D...]: registers, scratch and static VALU count of every kernel of a translation unit."""
+    import os
+    here = os.path.dirname(os.path.abspath(__file__))
+    csrc = os.path.join(here, "..", "hap_amd", "csrc")
+    for i, a in enumerate(args):
+        if a == "--csrc":
+            csrc = args[i + 1]
+    src = args[args.index("--resources") + 1]
+    defs = [a for a in args if a.startswith("-D")]
+    with tempfile.NamedTemporaryFile(suffix=".s") as tmp:
+        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + csrc, "-S",
+               "--cuda-device-only", "-o", tmp.name, os.path.join(csrc, src)] + defs
+        subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
+        text = open(tmp.name).read()
+    valu = {}
+    for m in re.finditer(r"^(_Z\w+):.*?s_endpgm", text, re.S | re.M):
+        valu[m.group(1)] = len(re.findall(r"^\s+v_", m.group(0), re.M))
+    try:
+        demangle = subprocess.run(["c++filt"], input="\n".join(valu), capture_output=True, text=True).stdout.split("\n")
+    except OSError:
+        demangle = list(valu)
+    names = dict(zip(valu, demangle))
+    print("%-6s %-6s %-8s %-6s %s" % ("vgpr", "sgpr", "scratch", "valu", "kernel (" + src + ")"))
+    for m in re.finditer(r"\.name:\s+(\S+)\n(.*?)\.wavefront_size", text, re.S):
+        body = m.group(2)
+        get = lambda k: re.search(r"\." + k + r":\s+(\d+)", body).group(1)
+        nm = names.get(m.group(1), m.group(1)).replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
+        print("%-6s %-6s %-8s %-6d %s" % (get("vgpr_count"), get("sgpr_count"), get("private_segment_fixed_size"),
+                                        valu.get(m.group(1), 0), nm))
+
+
 def main():
     args = sys.argv[1:]
+    if "--fused-budget" in args:
+        return fused_budget(args)
+    if "--resources" in args:
+        return resources(args)
     src = args[0]
     defs = [a for a in args[1:] if a.startswith("-D")]
     ranges = []

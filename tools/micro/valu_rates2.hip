@@ -1,6 +1,8 @@
-// Dev probe 2: one opcode per kernel via inline asm (8 independent chains, 8 waves/SIMD).
+// Dev probe 2: one opcode per kernel via inline asm (8 independent chains; waves per SIMD = argv[1], default 8:
+// the fused Hap Q encode kernel runs at 5).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
+#include <stdlib.h>
 #define ITER 4096
 #define KERNEL(NAME, ASM)                                                                          \
     __global__ __launch_bounds__(256) void NAME(unsigned *out, unsigned seed)                      \
@@ -45,16 +47,49 @@
 #define A_FFBL(x) "v_ffbl_b32 " #x ", " #x "\n"
 #define A_MBCNT(x) "v_mbcnt_lo_u32_b32 " #x ", " #x ", %8\n"
 #define A_ADD3(x) "v_add3_u32 " #x ", " #x ", %8, " #x "\n"
+#define A_OR(x) "v_or_b32 " #x ", " #x ", %8\n"
+#define A_SUB(x) "v_sub_u32 " #x ", " #x ", %8\n"
+#define A_LSHR(x) "v_lshrrev_b32 " #x ", 1, " #x "\n"
+#define A_ASHR(x) "v_ashrrev_i32 " #x ", 1, " #x "\n"
+#define A_LSHLADD(x) "v_lshl_add_u32 " #x ", " #x ", 2, %8\n"
+#define A_ADDLSHL(x) "v_add_lshl_u32 " #x ", " #x ", %8, 2\n"
+#define A_ANDOR(x) "v_and_or_b32 " #x ", " #x ", %8, " #x "\n"
+#define A_OR3(x) "v_or3_b32 " #x ", " #x ", %8, " #x "\n"
+#define A_BFI(x) "v_bfi_b32 " #x ", %8, " #x ", " #x "\n"
+#define A_XAD(x) "v_xad_u32 " #x ", " #x ", %8, " #x "\n"
+#define A_MADU16(x) "v_mad_u32_u16 " #x ", " #x ", %8, " #x "\n"
+#define A_MADI16(x) "v_mad_i32_i16 " #x ", " #x ", %8, " #x "\n"
+#define A_MUL24(x) "v_mul_u32_u24 " #x ", " #x ", %8\n"
+#define A_PKADD(x) "v_pk_add_u16 " #x ", " #x ", %8\n"
+#define A_PKLSHR(x) "v_pk_lshrrev_b16 " #x ", 1, " #x "\n"
+#define A_PKMAD(x) "v_pk_mad_u16 " #x ", " #x ", %8, " #x "\n"
+#define A_PKMAX(x) "v_pk_max_u16 " #x ", " #x ", %8\n"
+#define A_ALIGNBIT(x) "v_alignbit_b32 " #x ", %8, " #x ", 2\n"
+#define A_PERM(x) "v_perm_b32 " #x ", " #x ", %8, " #x "\n"
+#define A_MED3I(x) "v_med3_i32 " #x ", " #x ", 0, 3\n"
+#define A_MAX3(x) "v_max3_u32 " #x ", " #x ", %8, " #x "\n"
+#define A_DOT2(x) "v_dot2_i32_i16 " #x ", " #x ", %8, " #x "\n"
+#define A_BCNT(x) "v_bcnt_u32_b32 " #x ", " #x ", %8\n"
+#define A_ADDDPP(x) "v_add_u32_dpp " #x ", " #x ", " #x " quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
+#define A_MOVDPP(x) "v_mov_b32_dpp " #x ", " #x " quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
+#define A_READLANE(x) "v_readlane_b32 s20, " #x ", 5\n"
 KERNEL(k_add, A_ADD) KERNEL(k_and, A_AND) KERNEL(k_lshl, A_LSHL) KERNEL(k_bfe, A_BFE) KERNEL(k_lshlor, A_LSHLOR)
 KERNEL(k_minu, A_MINU) KERNEL(k_mini, A_MINI) KERNEL(k_minf, A_MINF) KERNEL(k_addf, A_ADDF) KERNEL(k_fma, A_FMA)
 KERNEL(k_cvtub, A_CVTUB) KERNEL(k_cvtu, A_CVTU) KERNEL(k_mad24, A_MAD24) KERNEL(k_madi24, A_MADI24) KERNEL(k_cnd, A_CND)
 KERNEL(k_cmp, A_CMP) KERNEL(k_cmpf, A_CMPF) KERNEL(k_mov, A_MOV) KERNEL(k_xor, A_XOR) KERNEL(k_min3, A_MIN3)
 KERNEL(k_med3f, A_MED3F) KERNEL(k_sad, A_SAD) KERNEL(k_pkmin, A_PKMIN) KERNEL(k_dot4, A_DOT4) KERNEL(k_ffbl, A_FFBL)
 KERNEL(k_mbcnt, A_MBCNT) KERNEL(k_add3, A_ADD3) KERNEL(k_cnd64, A_CND64) KERNEL(k_cmpcnd, A_CMPCND) KERNEL(k_cmpcnd64, A_CMPCND64)
+KERNEL(k_or, A_OR) KERNEL(k_sub, A_SUB) KERNEL(k_lshr, A_LSHR) KERNEL(k_ashr, A_ASHR) KERNEL(k_lshladd, A_LSHLADD)
+KERNEL(k_addlshl, A_ADDLSHL) KERNEL(k_andor, A_ANDOR) KERNEL(k_or3, A_OR3) KERNEL(k_bfi, A_BFI) KERNEL(k_xad, A_XAD)
+KERNEL(k_madu16, A_MADU16) KERNEL(k_madi16, A_MADI16) KERNEL(k_mul24, A_MUL24) KERNEL(k_pkadd, A_PKADD) KERNEL(k_pklshr, A_PKLSHR)
+KERNEL(k_pkmad, A_PKMAD) KERNEL(k_pkmax, A_PKMAX) KERNEL(k_alignbit, A_ALIGNBIT) KERNEL(k_perm, A_PERM) KERNEL(k_med3i, A_MED3I)
+KERNEL(k_max3, A_MAX3) KERNEL(k_dot2, A_DOT2) KERNEL(k_bcnt, A_BCNT) KERNEL(k_adddpp, A_ADDDPP) KERNEL(k_movdpp, A_MOVDPP)
+KERNEL(k_readlane, A_READLANE)
+static int g_waves = 8;      // waves per SIMD: workgroups of 4 waves, g_waves of them per CU
 template <typename K> void run(const char *name, K kern, unsigned *d)
 {
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-    const int blocks = 256 * 8;
+    const int blocks = 256 * g_waves;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, 0, d, 1u);
     hipEventRecord(e0);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, 0, d, 3u);
@@ -63,11 +98,19 @@ template <typename K> void run(const char *name, K kern, unsigned *d)
     const double instr_per_simd = blocks * 4.0 / 1024.0 * ITER * 8;
     printf("%-22s %7.3f ms  %.2f ns/instr/SIMD (%.2f cyc @2.4GHz)\n", name, ms, ms * 1e6 / instr_per_simd, ms * 1e6 / instr_per_simd * 2.4);
 }
-int main()
+int main(int argc, char **argv)
 {
+    if (argc > 1)
+        g_waves = atoi(argv[1]);
+    if (g_waves < 1 || g_waves > 8)
+        return 2;
+    printf("waves per SIMD: %d\n", g_waves);
     unsigned *d; hipMalloc(&d, 256 * 8 * 256 * 4);
 #define RUN(n) run(#n, n, d);
     RUN(k_add) RUN(k_and) RUN(k_xor) RUN(k_lshl) RUN(k_bfe) RUN(k_lshlor) RUN(k_add3) RUN(k_minu) RUN(k_mini) RUN(k_min3) RUN(k_sad) RUN(k_mad24) RUN(k_madi24)
     RUN(k_dot4) RUN(k_pkmin) RUN(k_ffbl) RUN(k_mbcnt) RUN(k_mov) RUN(k_cnd) RUN(k_cnd64) RUN(k_cmpcnd) RUN(k_cmpcnd64) RUN(k_cmp) RUN(k_cmpf) RUN(k_minf) RUN(k_addf) RUN(k_fma) RUN(k_med3f) RUN(k_cvtub) RUN(k_cvtu)
+    RUN(k_or) RUN(k_sub) RUN(k_lshr) RUN(k_ashr) RUN(k_lshladd) RUN(k_addlshl) RUN(k_andor) RUN(k_or3) RUN(k_bfi) RUN(k_xad) RUN(k_madu16) RUN(k_madi16)
+    RUN(k_mul24) RUN(k_pkadd) RUN(k_pklshr) RUN(k_pkmad) RUN(k_pkmax) RUN(k_alignbit) RUN(k_perm) RUN(k_med3i) RUN(k_max3) RUN(k_dot2) RUN(k_bcnt)
+    RUN(k_adddpp) RUN(k_movdpp) RUN(k_readlane)
     return 0;
 }
