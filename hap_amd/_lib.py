@@ -48,6 +48,9 @@ def _load():
         "HapGpuPlacementTimeoutCount": (ul, [vp]),
         "HapGpuCompressRGBA": (u, [vp, vp, u, u, ul, u, vp, ul, P(ul)]),
         "HapGpuCompressRGBAFlags": (u, [vp, vp, u, u, ul, u, u, vp, ul, P(ul)]),
+        "HapGpuCompressRGBAHalf": (u, [vp, vp, u, u, ul, u, vp, ul, P(ul)]),
+        "HapGpuEncodeFramesRGBAHalf": (u, [vp, u, P(vp), u, u, ul, u, u, u, P(vp), P(ul), P(ul), P(u), u]),
+        "HapGpuEncodeFramesRGBAHalfBegin": (u, [vp, u, P(vp), u, u, ul, u, u, u, P(vp), P(ul), P(ul), P(u), u]),
         "HapGpuDecompressRGBA": (u, [vp, vp, ul, u, vp, ul, u, u, vp, ul]),
         "HapGpuDecompressRGBAHalf": (u, [vp, vp, ul, u, u, u, vp, ul]),
         "HapGpuEncodeFrames": (u, [vp, u, u, P(vp), P(ul), P(u), P(u), P(u), P(vp), P(ul), P(ul), P(u), u]),

@@ -298,6 +298,22 @@ class Context:
             return r, (C.string_at(output, used.value) if r == 0 else None)
         return r, used.value
 
+    def compress_rgba_half(self, rgba_half, width, height, row_bytes, texture_format, output=None):
+        """RGBA16F picture (numpy uint16 / float16, bytes-like or torch, host or device) -> one BC6H texture
+        (HapGpuCompressRGBAHalf; texture_format RGB_BPTC_UNSIGNED_FLOAT or RGB_BPTC_SIGNED_FLOAT).  Returns
+        (result, bytes | None), or (result, bytes used) into `output`."""
+        need = (width // 4) * (height // 4) * 16
+        a, _n, _k = _addr_len(rgba_half)
+        own = output is None
+        if own:
+            output = (C.c_ubyte * max(1, need))()
+        oa, on, _k2 = _addr_len(output)
+        used = C.c_ulong(0)
+        r = lib.HapGpuCompressRGBAHalf(self.handle, a, width, height, row_bytes, texture_format, oa, on, C.byref(used))
+        if own:
+            return r, (C.string_at(output, used.value) if r == 0 else None)
+        return r, used.value
+
     def decompress_rgba(self, texture, texture_format, width, height, rgba=None, alpha=None, row_bytes=None):
         """Texture (+ optional RGTC1 alpha plane) -> RGBA8. Returns (result, bytes | None)."""
         ta, tn, _k = _addr_len(texture)
@@ -395,6 +411,34 @@ class Context:
                                             (C.c_uint * count)(*formats), (C.c_uint * count)(*compressors),
                                             (C.c_uint * count)(*chunk_counts), optrs, olens, used, results, flags)
         self._pending = (used, results, ptrs, optrs, olens, rgba_frames, outputs)     # alive until the second half
+        return r
+
+    def _encode_half(self, fn, rgba_half_frames, width, height, row_bytes, texture_format, compressor, chunk_count,
+                     outputs, flags):
+        nf = len(rgba_half_frames)
+        ptrs, infos = self._ptr_array(rgba_half_frames)
+        optrs, oinfos = self._ptr_array(outputs)
+        olens = (C.c_ulong * nf)(*[i[1] for i in oinfos])
+        used = (C.c_ulong * nf)()
+        results = (C.c_uint * nf)()
+        r = fn(self.handle, nf, ptrs, width, height, row_bytes, texture_format, compressor, chunk_count, optrs, olens,
+               used, results, flags)
+        return r, used, results, (ptrs, optrs, olens, infos, oinfos)
+
+    def encode_frames_rgba_half(self, rgba_half_frames, width, height, row_bytes, texture_format, compressor,
+                                chunk_count, outputs, flags=0):
+        """RGBA16F pictures -> Hap HDR frames of one BC6H texture (HapGpuEncodeFramesRGBAHalf).  Returns
+        (result, used[], results[])."""
+        r, used, results, _keep = self._encode_half(lib.HapGpuEncodeFramesRGBAHalf, rgba_half_frames, width, height,
+                                                    row_bytes, texture_format, compressor, chunk_count, outputs, flags)
+        return r, list(used), list(results)
+
+    def encode_frames_rgba_half_begin(self, rgba_half_frames, width, height, row_bytes, texture_format, compressor,
+                                      chunk_count, outputs, flags=0):
+        """First half of encode_frames_rgba_half (HapGpuEncodeFramesRGBAHalfBegin); encode_finish() is the second."""
+        r, used, results, keep = self._encode_half(lib.HapGpuEncodeFramesRGBAHalfBegin, rgba_half_frames, width, height,
+                                                   row_bytes, texture_format, compressor, chunk_count, outputs, flags)
+        self._pending = (used, results) + keep                                      # alive until the second half
         return r
 
     def encode_finish(self):

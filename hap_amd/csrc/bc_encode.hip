@@ -86,9 +86,12 @@ extern "C" int hapgpu_k_block_encode(hapgpu_rt *rt, const HapGpuPictureTable *ta
 {
     scoped_timing st(rt, 0);
     const hipStream_t stream = hapgpu_rt_stream(rt);
+    // BC6H is made from RGBA16F pictures: 8 bytes a texel, rows a multiple of 16 bytes
+    const bool half = format == 0x8E8F || format == 0x8E8E;
     if (!table || !(table->column[0] || table->one[0]) || !(table->column[1] || table->one[1]) ||
         (with_alpha && (format != 0x01 || !(table->column[2] || table->one[2]))) || pictures == 0 || pictures > 65535u ||
-        width == 0 || height == 0 || (width & 3u) || (height & 3u) || row_bytes < (size_t)width * 4u || (row_bytes & 3u))
+        width == 0 || height == 0 || (width & 3u) || (height & 3u) || row_bytes < (size_t)width * (half ? 8u : 4u) ||
+        (row_bytes & (half ? 15u : 3u)))
         return 1;
     const HapGpuPictureTable &t = *table;
     const unsigned bx = width / 4u, by = height / 4u;
@@ -103,6 +106,8 @@ extern "C" int hapgpu_k_block_encode(hapgpu_rt *rt, const HapGpuPictureTable *ta
         break;
     case 0x8DBB: launch<kFmtRGTC1>(t, pictures, row_bytes, bx, by, wide != 0, stream); break;
     case 0x8E8C: hapgpu_launch_bptc_encode(t, pictures, bx, by, row_bytes, wide != 0, stream); break;
+    case 0x8E8F:
+    case 0x8E8E: hapgpu_launch_bc6h_encode(t, pictures, format == 0x8E8E, bx, by, row_bytes, stream); break;
     default: return 1;
     }
     return hipGetLastError() == hipSuccess ? 0 : 4;

@@ -482,7 +482,7 @@ unsigned int HapGpuCompressRGBA(HapGpuContext *context, const void *rgba, unsign
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
     r = hapb_compress_rgba(context, rgba, width, height, rowBytes, textureFormat, output, outputBytes,
-                           outputBytesUsed, 1, 0u);
+                           outputBytesUsed, 1, 0u, 0);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -497,7 +497,7 @@ unsigned int HapGpuCompressRGBAFlags(HapGpuContext *context, const void *rgba, u
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
     r = hapb_compress_rgba(context, rgba, width, height, rowBytes, textureFormat, output, outputBytes,
-                           outputBytesUsed, 1, flags);
+                           outputBytesUsed, 1, flags, 0);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -608,6 +608,70 @@ unsigned int HapGpuEncodeFramesRGBABegin(HapGpuContext *context, unsigned int fr
     r = hapb_encode_rgba(context, frameCount, rgbaFrames, width, height, rowBytes, count, textureFormats,
                          compressors, chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed,
                          results, flags);
+    context->defer_encode = 0u;
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+/* RGBA16F pictures -> Hap HDR: the RGBA calls with 8-byte texels and one BC6H texture per frame */
+unsigned int HapGpuCompressRGBAHalf(HapGpuContext *context, const void *rgbaHalf, unsigned int width,
+                                    unsigned int height, unsigned long rowBytes, unsigned int textureFormat,
+                                    void *output, unsigned long outputBytes, unsigned long *outputBytesUsed)
+{
+    unsigned r;
+    if (!context)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_compress_rgba(context, rgbaHalf, width, height, rowBytes, textureFormat, output, outputBytes,
+                           outputBytesUsed, 1, 0u, 1);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+unsigned int HapGpuEncodeFramesRGBAHalf(HapGpuContext *context, unsigned int frameCount,
+                                        const void *const *rgbaHalfFrames, unsigned int width, unsigned int height,
+                                        unsigned long rowBytes, unsigned int textureFormat, unsigned int compressor,
+                                        unsigned int chunkCount, void *const *outputBuffers,
+                                        const unsigned long *outputBuffersBytes,
+                                        unsigned long *outputBuffersBytesUsed, unsigned int *results,
+                                        unsigned int flags)
+{
+    unsigned r = HapResult_No_Error, done;
+    if (!context)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    if (frameCount <= HAP_BATCH_SLICE || !rgbaHalfFrames || !outputBuffers || !outputBuffersBytes || !outputBuffersBytesUsed || !results) {
+        r = hapb_encode_pictures(context, frameCount, rgbaHalfFrames, width, height, rowBytes, 1u, &textureFormat, &compressor,
+                             &chunkCount, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, 1);
+    } else {
+        for (done = 0; done < frameCount; done += HAP_BATCH_SLICE) {
+            const unsigned n = frameCount - done < HAP_BATCH_SLICE ? frameCount - done : HAP_BATCH_SLICE;
+            const unsigned rc = hapb_encode_pictures(context, n, rgbaHalfFrames + done, width, height, rowBytes, 1u, &textureFormat,
+                                                 &compressor, &chunkCount, outputBuffers + done, outputBuffersBytes + done,
+                                                 outputBuffersBytesUsed + done, results + done, flags, 1);
+            if (r == HapResult_No_Error)
+                r = rc;
+        }
+    }
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+unsigned int HapGpuEncodeFramesRGBAHalfBegin(HapGpuContext *context, unsigned int frameCount,
+                                             const void *const *rgbaHalfFrames, unsigned int width, unsigned int height,
+                                             unsigned long rowBytes, unsigned int textureFormat, unsigned int compressor,
+                                             unsigned int chunkCount, void *const *outputBuffers,
+                                             const unsigned long *outputBuffersBytes,
+                                             unsigned long *outputBuffersBytesUsed, unsigned int *results,
+                                             unsigned int flags)
+{
+    unsigned r;
+    if (!context || frameCount > HAP_BATCH_SLICE)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    context->defer_encode = 1u;
+    r = hapb_encode_pictures(context, frameCount, rgbaHalfFrames, width, height, rowBytes, 1u, &textureFormat, &compressor,
+                         &chunkCount, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, 1);
     context->defer_encode = 0u;
     hapgpu_rt_unlock(context->rt);
     return r;

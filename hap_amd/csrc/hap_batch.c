@@ -219,7 +219,7 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
            others (snappy_compress_blocks.hip).  One texture per frame. */
         {
             const HapbBlockEncodeJob *bj = ctx->block_encode_job;
-            if (bj && !ctx->no_fusion && count == 1u && (bj->row_bytes & 3u) == 0 &&
+            if (bj && !ctx->no_fusion && count == 1u && bj->texel_bytes == 4u && (bj->row_bytes & 3u) == 0 &&
                 (unsigned long long)bj->row_bytes * bj->height < 0xFFFFFFFFull && bj->width / 4u >= 1u) {
                 /* (code: HapGpuTexEnc.reserved bits 24..26; mask bit: which kernel the launcher starts) */
                 if (t->field_period == 4u && t->format == HapTextureFormat_YCoCg_DXT5) {
@@ -454,7 +454,7 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                 }
                 if (job) {
                     HAPB_MIX(job->frame_count); HAPB_MIX(job->width); HAPB_MIX(job->height); HAPB_MIX(job->row_bytes);
-                    HAPB_MIX(job->wide + 2);
+                    HAPB_MIX(job->wide + 2); HAPB_MIX(job->texel_bytes);
                 }
                 graph = hapgpu_rt_graph_begin(rt, key);
             }
@@ -711,12 +711,20 @@ void hapb_encode_abandon(HapGpuContext *ctx, HapbEncodePending *pd)
     free(pd);
 }
 
+/* bytes of a texel of the pictures a texture format is made from and decoded to: RGBA16F for BC6H, else RGBA8 */
+static size_t texel_bytes(unsigned format)
+{
+    return format == HapTextureFormat_RGB_BPTC_UNSIGNED_FLOAT || format == HapTextureFormat_RGB_BPTC_SIGNED_FLOAT ? 8u : 4u;
+}
+
 unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width, unsigned height,
                             unsigned long row_bytes, unsigned format, void *output,
-                            unsigned long output_bytes, unsigned long *used, int synchronise, unsigned flags)
+                            unsigned long output_bytes, unsigned long *used, int synchronise, unsigned flags, int half)
 {
-    /* BC7 only when asked (HAPGPU_ENCODE_BPTC_BLOCKS) */
+    /* BC7 only when asked (HAPGPU_ENCODE_BPTC_BLOCKS); BC6H only from half pictures, and nothing else from those */
     const int bptc = (flags & HAPGPU_ENCODE_BPTC_BLOCKS) && format == HapTextureFormat_RGBA_BPTC_UNORM;
+    const int bc6h = texel_bytes(format) == 8u;
+    const size_t texel = half ? 8u : 4u;
     hapgpu_rt *rt = ctx->rt;
     const size_t block = hapf_block_bytes(format);
     HapGpuPictureTable t = {{NULL, NULL, NULL}, {0u, 0u, 0u}};
@@ -727,20 +735,20 @@ unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width
     if (context_busy(ctx, NULL, 0))
         return HapResult_Internal_Error;
     if (!rgba || !output || width == 0 || height == 0 || (width & 3u) || (height & 3u) ||
-        row_bytes < (unsigned long)width * 4ul ||
-        (format != HapTextureFormat_RGB_DXT1 && format != HapTextureFormat_RGBA_DXT5 &&
-         format != HapTextureFormat_YCoCg_DXT5 && format != HapTextureFormat_A_RGTC1 && !bptc))
+        row_bytes < (unsigned long)width * texel ||
+        (half ? !bc6h : (format != HapTextureFormat_RGB_DXT1 && format != HapTextureFormat_RGBA_DXT5 &&
+                         format != HapTextureFormat_YCoCg_DXT5 && format != HapTextureFormat_A_RGTC1 && !bptc)))
         return HapResult_Bad_Arguments;
     need = (size_t)(width / 4u) * (height / 4u) * block;
     if (output_bytes < need)
         return HapResult_Buffer_Too_Small;
-    /* device pictures 4-byte aligned with rows a multiple of 4, device outputs aligned to their blocks; at most 65535
-       block rows for BC7, 2^32 * 255/256 blocks for the others */
-    if ((row_bytes & 3u) || (is_dev(ctx, rgba) && ((uintptr_t)rgba & 3u)) ||
+    /* device pictures 4-byte aligned with rows a multiple of 4 (half pictures: 16 and 16), device outputs aligned to
+       their blocks; at most 65535 block rows for BC7 and BC6H, 2^32 * 255/256 blocks for the others */
+    if ((row_bytes & (half ? 15u : 3u)) || (is_dev(ctx, rgba) && ((uintptr_t)rgba & (half ? 15u : 3u))) ||
         (is_dev(ctx, output) && ((uintptr_t)output & (block - 1u))) ||
-        (bptc ? height / 4u > 65535u : (unsigned long long)(width / 4u) * (height / 4u) > 0xFFFFFFFFull / 256u * 255u))
+        (bptc || half ? height / 4u > 65535u : (unsigned long long)(width / 4u) * (height / 4u) > 0xFFFFFFFFull / 256u * 255u))
         return HapResult_Bad_Arguments;
-    rgba_bytes = (size_t)row_bytes * (height - 1u) + (size_t)width * 4u;
+    rgba_bytes = (size_t)row_bytes * (height - 1u) + (size_t)width * texel;
     if (!is_dev(ctx, rgba)) {
         void *s = hapgpu_rt_device_scratch(rt, D_RGBA_STAGE, rgba_bytes);
         if (!s || hapgpu_rt_h2d(rt, s, rgba, rgba_bytes))
@@ -780,11 +788,6 @@ typedef struct picture_road {
 static const unsigned k_rgba_kinds[4] = {HapTextureFormat_RGB_DXT1, HapTextureFormat_RGBA_DXT5, HapTextureFormat_YCoCg_DXT5,
                                          HapTextureFormat_RGBA_BPTC_UNORM};
 static const unsigned k_half_kinds[2] = {HapTextureFormat_RGB_BPTC_UNSIGNED_FLOAT, HapTextureFormat_RGB_BPTC_SIGNED_FLOAT};
-
-static size_t texel_bytes(unsigned format)
-{
-    return format == HapTextureFormat_RGB_BPTC_UNSIGNED_FLOAT || format == HapTextureFormat_RGB_BPTC_SIGNED_FLOAT ? 8u : 4u;
-}
 
 unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
                               const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
@@ -861,7 +864,18 @@ unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                           void *const *outputs, const unsigned long *output_bytes,
                           unsigned long *output_used, unsigned *results, unsigned flags)
 {
+    return hapb_encode_pictures(ctx, frame_count, rgba_frames, width, height, row_bytes, count, formats, compressors,
+                                chunk_counts, outputs, output_bytes, output_used, results, flags, 0);
+}
+
+unsigned hapb_encode_pictures(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
+                              unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
+                              const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
+                              void *const *outputs, const unsigned long *output_bytes,
+                              unsigned long *output_used, unsigned *results, unsigned flags, int half)
+{
     hapgpu_rt *rt = ctx->rt;
+    const size_t texel = half ? 8u : 4u;
     unsigned long tex_bytes[2] = {0, 0};
     size_t per_frame = 0, rgba_bytes, tex_off[2] = {0, 0};
     unsigned i, f, rc;
@@ -874,7 +888,7 @@ unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
     if (context_busy(ctx, results, frame_count))
         return HapResult_Internal_Error;
     if (!results || !rgba_frames || count == 0 || count > 2 || !formats || width == 0 || height == 0 ||
-        (width & 3u) || (height & 3u) || row_bytes < (unsigned long)width * 4ul) {
+        (width & 3u) || (height & 3u) || row_bytes < (unsigned long)width * texel || (half && (row_bytes & 15u))) {
         for (f = 0; results && f < frame_count; f++)
             results[f] = HapResult_Bad_Arguments;
         return HapResult_Bad_Arguments;
@@ -882,8 +896,10 @@ unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
     for (i = 0; i < count; i++) {
         /* (BC7 only when asked, and alone: no Hap variant pairs it with a second texture) */
         const int bptc = (flags & HAPGPU_ENCODE_BPTC_BLOCKS) && count == 1u && formats[i] == HapTextureFormat_RGBA_BPTC_UNORM;
-        if (formats[i] != HapTextureFormat_RGB_DXT1 && formats[i] != HapTextureFormat_RGBA_DXT5 &&
-            formats[i] != HapTextureFormat_YCoCg_DXT5 && formats[i] != HapTextureFormat_A_RGTC1 && !bptc) {
+        /* (half pictures make BC6H, alone, and nothing else; RGBA8 pictures never make it) */
+        if (half ? count != 1u || texel_bytes(formats[i]) != 8u
+                 : (formats[i] != HapTextureFormat_RGB_DXT1 && formats[i] != HapTextureFormat_RGBA_DXT5 &&
+                    formats[i] != HapTextureFormat_YCoCg_DXT5 && formats[i] != HapTextureFormat_A_RGTC1 && !bptc)) {
             for (f = 0; f < frame_count; f++)
                 results[f] = HapResult_Bad_Arguments;
             return HapResult_Bad_Arguments;
@@ -892,7 +908,7 @@ unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
         tex_off[i] = per_frame;
         per_frame += align_up(tex_bytes[i], 256);
     }
-    rgba_bytes = (size_t)row_bytes * (height - 1u) + (size_t)width * 4u;
+    rgba_bytes = (size_t)row_bytes * (height - 1u) + (size_t)width * texel;
     textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, per_frame * frame_count);
     tex_ptrs = (const void **)malloc(sizeof(void *) * (size_t)frame_count * count);
     /* address table of the batched block-encode launches: [sources][outputs of texture 0][of texture 1] */
@@ -922,6 +938,9 @@ unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                 break;
             src = rgba_stage + align_up(rgba_bytes, 256) * f;
         }
+        /* (a half picture in device memory is read 16 bytes at a time: misaligned, its frame is Bad_Arguments) */
+        if (half && ((uintptr_t)src & 15u))
+            continue;
         hsrc[f] = (uint64_t)(uintptr_t)src;
         if (((uintptr_t)src | row_bytes) & 15u)
             wide = 0;
@@ -944,6 +963,7 @@ unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
         job.height = height;
         job.row_bytes = row_bytes;
         job.wide = wide;
+        job.texel_bytes = (unsigned)texel;
         for (i = 0; i < count; i++)
             job.formats[i] = formats[i];
         ctx->block_encode_job = &job;

@@ -50,6 +50,7 @@ typedef struct HapbBlockEncodeJob {
     const uint64_t *host_table;    /* pinned: [sources][outputs of texture 0][of texture 1], frame_count each */
     uint64_t *device_table;
     unsigned frame_count, count, width, height, formats[2];
+    unsigned texel_bytes;          /* of the pictures: 4 (RGBA8) or 8 (RGBA16F, which make BC6H and are never fused) */
     unsigned long row_bytes;
     int wide;
 } HapbBlockEncodeJob;
@@ -83,14 +84,23 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                      void *const *outputs, const unsigned long *output_bytes,
                      unsigned long *output_used, unsigned *results, unsigned flags,
                      int inputs_are_device);
+/* one picture -> one texture.  half != 0: an RGBA16F picture and a BC6H format (hapb_encode_rgba's rules) */
 unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width, unsigned height,
                             unsigned long row_bytes, unsigned format, void *output,
-                            unsigned long output_bytes, unsigned long *used, int synchronise, unsigned flags);
+                            unsigned long output_bytes, unsigned long *used, int synchronise, unsigned flags, int half);
 /* one texture -> one picture: half == 0 RGBA8 (DXT1, DXT5, YCoCg-DXT5 with an optional RGTC1 alpha plane, BC7),
    half != 0 RGBA16F (BC6H unsigned or signed, no alpha plane) */
 unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
                               const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
                               void *picture, unsigned long row_bytes, int half);
+/* pictures -> frames.  half == 0: RGBA8 pictures and the DXT / RGTC1 formats (BC7 with HAPGPU_ENCODE_BPTC_BLOCKS);
+   half != 0: RGBA16F pictures (rows and device addresses 16-byte aligned) and one BC6H texture */
+unsigned hapb_encode_pictures(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
+                              unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
+                              const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
+                              void *const *outputs, const unsigned long *output_bytes,
+                              unsigned long *output_used, unsigned *results, unsigned flags, int half);
+/* ... with half == 0 */
 unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
                           unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
                           const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,

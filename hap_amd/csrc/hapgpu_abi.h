@@ -296,7 +296,8 @@ typedef struct HapGpuPictureTable {
     uint64_t one[3];
 } HapGpuPictureTable;
 
-/* RGBA8 -> blocks of `hap_texture_format`: RGB_DXT1, RGBA_DXT5, YCoCg_DXT5, A_RGTC1 or RGBA_BPTC_UNORM (BC7);
+/* RGBA8 -> blocks of `hap_texture_format`: RGB_DXT1, RGBA_DXT5, YCoCg_DXT5, A_RGTC1 or RGBA_BPTC_UNORM (BC7); RGBA16F ->
+   RGB_BPTC_UNSIGNED_FLOAT / RGB_BPTC_SIGNED_FLOAT (BC6H: 8 bytes a texel, sources and row_bytes 16-byte aligned);
    YCoCg_DXT5 with_alpha: Hap Q Alpha, the RGTC1 alpha plane to the second outputs from the same read of every picture.
    Sources and row_bytes 4-byte aligned, outputs 8- (DXT1, RGTC1) or 16-byte aligned; wide != 0 promises 16-byte aligned
    sources and row pitch. */

@@ -60,6 +60,8 @@ __device__ __forceinline__ uint64_t picture_address(const HapGpuPictureTable &t,
 // the BC7 and BC6H launches of hapgpu_k_block_encode / hapgpu_k_block_decode (arguments checked there)
 void hapgpu_launch_bptc_encode(const HapGpuPictureTable &t, unsigned pictures, unsigned bx, unsigned by,
                                size_t row_bytes, bool wide, hipStream_t stream);      // bptc_encode.hip
+void hapgpu_launch_bc6h_encode(const HapGpuPictureTable &t, unsigned pictures, bool is_signed, unsigned bx,
+                               unsigned by, size_t row_bytes, hipStream_t stream);    // bc6h_encode.hip
 void hapgpu_launch_bptc_decode(const HapGpuPictureTable &t, unsigned pictures, unsigned bx, unsigned by,
                                size_t row_bytes, hipStream_t stream);                 // bptc_decode.hip
 void hapgpu_launch_bc6h_decode(const HapGpuPictureTable &t, unsigned pictures, bool is_signed, unsigned bx,

@@ -96,7 +96,9 @@ typedef struct HapGpuContext HapGpuContext;
                                                (Hap R; bptc_encode.hip: modes 6 and 1 for opaque blocks, 6 and 5 for
                                                blocks with alpha).  One texture per frame.  Without the flag they refuse
                                                that format with Bad_Arguments, as before; BC6H formats are refused
-                                               either way.  Ignored by the calls that take finished textures. */
+                                               either way: they are made from half-float pictures, by
+                                               HapGpuCompressRGBAHalf and HapGpuEncodeFramesRGBAHalf.  Ignored by the
+                                               calls that take finished textures. */
 
 /* Decode flags */
 #define HAPGPU_DECODE_IGNORE_FRAGMENT_INDEX 0x1u /* decode as a decoder unaware of section 0x46 would */
@@ -211,6 +213,19 @@ unsigned int HapGpuDecompressRGBAHalf(HapGpuContext *context,
                                       unsigned int width, unsigned int height,
                                       void *rgbaHalf, unsigned long rowBytes);
 
+/* RGBA16F picture -> BC6H texture (Hap HDR), the other way.  rgbaHalf: four IEEE half bit patterns per texel, 8 bytes,
+ * rows rowBytes apart; alpha is ignored.  textureFormat: RGB_BPTC_UNSIGNED_FLOAT or RGB_BPTC_SIGNED_FLOAT (anything
+ * else is Bad_Arguments).  Unsigned: negative values, -0 and NaN encode as 0, +Inf as the largest finite half; signed:
+ * NaN as 0, +-Inf as the largest finite half of their sign.  The encoder is bc6h_encode.hip (modes 0x03, 0x07, 0x0B,
+ * 0x0F of one region, 0x1E, 0x01, 0x00 of two; tests/_bc6h_encode.py defines it bit for bit).  width and height
+ * multiples of 4; rowBytes at least width * 8 and a multiple of 16.  Host or device pointers; a device picture and a
+ * device output must each be 16-byte aligned.  16 bytes per block. */
+unsigned int HapGpuCompressRGBAHalf(HapGpuContext *context,
+                                    const void *rgbaHalf, unsigned int width, unsigned int height,
+                                    unsigned long rowBytes, unsigned int textureFormat,
+                                    void *output, unsigned long outputBytes,
+                                    unsigned long *outputBytesUsed);
+
 /* Batched HapEncode: frame f is made of `count` textures
  * inputBuffers[f*count + i] of inputBuffersBytes[i] bytes each (every frame of
  * a batch has the same geometry).  Semantics, frame layout, chunk-count
@@ -288,6 +303,36 @@ unsigned int HapGpuEncodeFramesBegin(HapGpuContext *context, unsigned int frameC
                                      unsigned int *results,
                                      unsigned int flags);
 unsigned int HapGpuEncodeFramesFinish(HapGpuContext *context);
+
+/* Batched RGBA16F -> Hap HDR frame: HapGpuEncodeFramesRGBA for half-float pictures (HapGpuCompressRGBAHalf's rules
+ * for them; a misaligned device picture makes its frame Bad_Arguments) and one BC6H texture per frame, packed exactly
+ * as HapGpuEncodeFrames packs a BC6H texture; the flags mean what they mean there.  textureFormat:
+ * RGB_BPTC_UNSIGNED_FLOAT or RGB_BPTC_SIGNED_FLOAT, else Bad_Arguments.  ...Begin is the first half of the call as
+ * HapGpuEncodeFramesRGBABegin is; HapGpuEncodeFramesFinish finishes it. */
+unsigned int HapGpuEncodeFramesRGBAHalf(HapGpuContext *context, unsigned int frameCount,
+                                        const void *const *rgbaHalfFrames,
+                                        unsigned int width, unsigned int height,
+                                        unsigned long rowBytes,
+                                        unsigned int textureFormat,
+                                        unsigned int compressor,
+                                        unsigned int chunkCount,
+                                        void *const *outputBuffers,
+                                        const unsigned long *outputBuffersBytes,
+                                        unsigned long *outputBuffersBytesUsed,
+                                        unsigned int *results,
+                                        unsigned int flags);
+unsigned int HapGpuEncodeFramesRGBAHalfBegin(HapGpuContext *context, unsigned int frameCount,
+                                             const void *const *rgbaHalfFrames,
+                                             unsigned int width, unsigned int height,
+                                             unsigned long rowBytes,
+                                             unsigned int textureFormat,
+                                             unsigned int compressor,
+                                             unsigned int chunkCount,
+                                             void *const *outputBuffers,
+                                             const unsigned long *outputBuffersBytes,
+                                             unsigned long *outputBuffersBytesUsed,
+                                             unsigned int *results,
+                                             unsigned int flags);
 
 /* Batched HapDecode of texture `index` of every frame.  No callback: all
  * chunks of all frames are decoded by the GPU.  Per-frame result codes,
