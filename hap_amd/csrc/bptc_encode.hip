@@ -539,6 +539,7 @@ __global__ __launch_bounds__(64) void bptc_encode_kernel(HapGpuPictureTable t, s
 
 } // namespace
 
+#ifndef HAPGPU_BPTC_ENCODE_HOST_ONLY
 // RGBA_BPTC_UNORM of hapgpu_k_block_encode (bc_encode.hip): outputs 16-byte aligned
 void hapgpu_launch_bptc_encode(const HapGpuPictureTable &t, unsigned pictures, unsigned bx, unsigned by,
                                size_t row_bytes, bool wide, hipStream_t stream)
@@ -549,3 +550,4 @@ void hapgpu_launch_bptc_encode(const HapGpuPictureTable &t, unsigned pictures, u
     else
         hipLaunchKernelGGL(bptc_encode_kernel<false>, grid, block, 0, stream, t, row_bytes, bx);
 }
+#endif

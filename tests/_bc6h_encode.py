@@ -70,6 +70,15 @@ TWO_REGION_ERROR = 48 * 16 * 16          # 16 half patterns (1/64 stop) a texel 
 ONE = 0x3C00
 _MODE = {H.MODES[i][0]: i for i in range(len(H.MODES))}
 
+# Measurements (tests/_bptc_value_space.py): a list here receives (name, values...) of the intermediates below while an
+# encode runs; None (the default) records nothing.  No result depends on it.
+TRACE = None
+
+
+def _note(*record):
+    if TRACE is not None:
+        TRACE.append(record)
+
 
 def _bitlen(v):
     """bits of v >= 0, elementwise"""
@@ -142,6 +151,7 @@ def quantise(v, prec, signed):
         if best_q is None:
             best_q, best_u, best_e = q, u, e
         else:
+            _note("quant_tie", (e == best_e) & (q != best_q))
             take = (e < best_e) | ((e == best_e) & (q < best_q))
             best_q, best_u, best_e = np.where(take, q, best_q), np.where(take, u, best_u), np.where(take, e, best_e)
     sg = np.where(v < 0, -1, 1)
@@ -161,6 +171,7 @@ def _box_endpoints(x, m):
     pivot = np.argmax(rng, axis=1)
     ar = np.arange(x.shape[0])
     cs = np.maximum(0, _bitlen(rng[ar, pivot]) - 11)
+    _note("cs", rng, pivot, cs)
     px = (2 * x[ar, :, pivot] - (lo[ar, pivot] + hi[ar, pivot])[:, None]) >> cs[:, None]
     cx = (2 * x - (lo + hi)[:, None, :]) >> cs[:, None, None]
     cov = (np.where(m[..., None], cx, 0) * px[..., None]).sum(1)
@@ -176,6 +187,7 @@ def _indices(x, lo, hi, d0, d1, b):
     ds = d >> s[:, None]
     den = (ds * ds).sum(-1)
     num = (((x - d0[:, None, :]) >> s[:, None, None]) * ds[:, None, :]).sum(-1)
+    _note("s", big, s, num, den, b)
     w = W[b]
     idx = np.zeros(num.shape, np.int64)
     for k in range(1, len(w)):
@@ -187,6 +199,7 @@ def _rdiv(n, d, signed):
     top = 0x7FFF if signed else 0xFFFF
     safe = np.where(d > 0, d, 1)
     q = np.minimum(top, (np.abs(n) + safe // 2) // safe)
+    _note("rdiv", n, d)
     if signed:
         return np.sign(n) * q
     return np.where(n < 0, 0, q)
@@ -227,6 +240,7 @@ def _final(x, m, b, fp, prec, signed, anchor):
     ar = np.arange(idx.shape[0])
     swap = (idx[ar, anchor] >> (b - 1)) != 0
     idx = np.where(swap[:, None], (1 << b) - 1 - idx, idx)
+    _note("swap", prec, anchor, swap)
     s = swap[:, None]
     return np.where(s, q1, q0), np.where(s, q0, q1), np.where(s, d1, d0), np.where(s, d0, d1), idx
 
@@ -285,6 +299,7 @@ def _deltas_fit(base, q, dbits):
     ok = np.ones(base.shape[0], bool)
     for c in range(3):
         d = q[:, c] - base[:, c]
+        _note("delta", c, dbits[c], d)
         ok &= (d >= -(1 << (dbits[c] - 1))) & (d <= (1 << (dbits[c] - 1)) - 1)
     return ok
 
@@ -313,6 +328,7 @@ def _one_region(x, h, signed):
 def best_partition(x):
     lo, hi = x.min(1), x.max(1)
     ps = np.maximum(0, _bitlen((hi - lo).max(-1)) - 10)
+    _note("ps", (hi - lo).max(-1), ps)
     y = (x - lo[:, None, :]) >> ps[:, None, None]
     tot = y.sum(1)
     s1 = np.einsum("pt,ntc->npc", P2_MASKS.astype(np.int64), y)
@@ -324,6 +340,7 @@ def best_partition(x):
     best = np.zeros(x.shape[0], np.int64)
     bs, bd = score[:, 0], np.full(x.shape[0], den[0], np.int64)
     for p in range(1, 32):
+        _note("score_tie", (score[:, p] * bd == bs * den[p]) & (score[:, p] > 0))
         better = score[:, p] * bd > bs * den[p]
         best = np.where(better, p, best)
         bs = np.where(better, score[:, p], bs)
@@ -367,6 +384,7 @@ def encode_blocks(texels, signed, two_regions=True, two_region_modes=TWO_REGION,
     x = to_working(h, signed)
     n = x.shape[0]
     cands = _one_region(x, h, signed)
+    _note("candidates", [(c[0], c[3], c[4]) for c in cands])
     mode0, words, dec, err, _valid = cands[0]
     modes = np.full(n, mode0, np.int64)
     for mode, w, d, e, valid in cands[1:]:
@@ -374,7 +392,9 @@ def encode_blocks(texels, signed, two_regions=True, two_region_modes=TWO_REGION,
         words, dec, err, modes = np.where(take[:, None], w, words), np.where(take[:, None, None], d, dec), np.where(take, e, err), np.where(take, mode, modes)
     if two_regions:
         asked = err > threshold
+        _note("asked", err, asked)
         for mode, w, d, e, valid in _two_regions(x, h, signed, two_region_modes):
+            _note("candidates", [(mode, e, valid)])
             take = asked & valid & (e < err)
             words, dec, err, modes = np.where(take[:, None], w, words), np.where(take[:, None, None], d, dec), np.where(take, e, err), np.where(take, mode, modes)
     blocks = np.ascontiguousarray(words.astype("<u4")).view(np.uint8).reshape(n, 16)

@@ -50,6 +50,15 @@ P2_MASKS = np.array([[(m >> t) & 1 for t in range(16)] for m in B.PARTITIONS_2],
 ANCHOR2 = np.array(B.ANCHORS_2, dtype=np.int64)
 MODES_USED = (1, 5, 6)
 
+# Measurements (tests/_bptc_value_space.py): a list here receives (name, values...) of the intermediates below while an
+# encode runs; None (the default) records nothing.  No result depends on it.
+TRACE = None
+
+
+def _note(*record):
+    if TRACE is not None:
+        TRACE.append(record)
+
 
 def _unq(code, bits):
     v = code << (8 - bits)
@@ -68,6 +77,7 @@ def _quant_channel(v, cb, p, has_p):
         if best_q is None:
             best_q, best_u, best_e = q, u, e
         else:
+            _note("quant_tie", (e == best_e) & (q != best_q))
             take = (e < best_e) | ((e == best_e) & (q < best_q))
             best_q, best_u, best_e = np.where(take, q, best_q), np.where(take, u, best_u), np.where(take, e, best_e)
     return best_q, best_u
@@ -87,6 +97,7 @@ def quantize_mode6(e0, e1, opaque):
         zero, one = np.zeros(n, np.int64), np.ones(n, np.int64)
         qa, ua, ea = _quant_p(e, 7, zero)
         qb, ub, eb = _quant_p(e, 7, one)
+        _note("p_tie", 6, (eb == ea) & ~opaque)
         use1 = opaque | (eb < ea)
         out.append((np.where(use1[:, None], qb, qa), np.where(use1, 1, 0), np.where(use1[:, None], ub, ua)))
     (q0, p0, d0), (q1, p1, d1) = out
@@ -101,6 +112,7 @@ def quantize_mode1(e0, e1):
     q1a, u1a, r1a = _quant_p(e1, 6, zero)
     q0b, u0b, r0b = _quant_p(e0, 6, one)
     q1b, u1b, r1b = _quant_p(e1, 6, one)
+    _note("p_tie", 1, (r0b + r1b) == (r0a + r1a))
     use1 = (r0b + r1b) < (r0a + r1a)
     s = use1[:, None]
     return np.where(s, q0b, q0a), np.where(s, q1b, q1a), use1.astype(np.int64), np.where(s, u0b, u0a), np.where(s, u1b, u1a)
@@ -133,6 +145,7 @@ def _indices(x, d0, d1, b):
     d = d1 - d0
     den = (d * d).sum(-1)                                 # [N]
     num = ((x - d0[:, None, :]) * d[:, None, :]).sum(-1)  # [N, 16]
+    _note("index", num, den, b)
     w = W[b]
     idx = np.zeros(num.shape, np.int64)
     for k in range(1, len(w)):
@@ -142,6 +155,7 @@ def _indices(x, d0, d1, b):
 
 def _rdiv(n, d):
     safe = np.where(d > 0, d, 1)
+    _note("rdiv", n, d)
     return np.where(n <= 0, 0, np.minimum(255, (n + safe // 2) // safe))
 
 
@@ -213,6 +227,7 @@ def _swap_for_anchor(idx, b, anchor_t, subset_m, pairs):
     ar = np.arange(idx.shape[0])
     top = 1 << (b - 1)
     swapped = (idx[ar, anchor_t] & top) != 0
+    _note("swap", b, anchor_t, swapped)
     inv = (1 << b) - 1 - idx
     idx = np.where(swapped[:, None] & subset_m, inv, idx)
     out = []
@@ -273,6 +288,7 @@ def best_partition(x):
     best = np.zeros(x.shape[0], np.int64)
     bs, bd = score[:, 0], np.full(x.shape[0], den[0], np.int64)
     for p in range(1, 64):
+        _note("score_tie", (score[:, p] * bd == bs * den[p]) & (score[:, p] > 0))
         better = score[:, p] * bd > bs * den[p]
         best = np.where(better, p, best)
         bs = np.where(better, score[:, p], bs)
@@ -342,6 +358,7 @@ def encode_blocks(texels):
     b5, d5, e5 = _mode5(x)
     # opaque: mode 1 against mode 6 (mode 1 wins a tie); with alpha: mode 5 against mode 6 (mode 5 wins a tie)
     e_other = np.where(opaque, e1, e5)
+    _note("errors", opaque, e6, e1, e5)
     take6 = e6 < e_other
     words = np.where(take6[:, None], b6, np.where(opaque[:, None], b1, b5))
     dec = np.where(take6[:, None, None], d6, np.where(opaque[:, None, None], d1, d5))
