@@ -51,6 +51,11 @@ def _load():
         "HapGpuCompressRGBAHalf": (u, [vp, vp, u, u, ul, u, vp, ul, P(ul)]),
         "HapGpuEncodeFramesRGBAHalf": (u, [vp, u, P(vp), u, u, ul, u, u, u, P(vp), P(ul), P(ul), P(u), u]),
         "HapGpuEncodeFramesRGBAHalfBegin": (u, [vp, u, P(vp), u, u, ul, u, u, u, P(vp), P(ul), P(ul), P(u), u]),
+        "HapGpuCompressAlpha": (u, [vp, vp, u, u, ul, vp, ul, P(ul)]),
+        "HapGpuDecompressAlpha": (u, [vp, vp, ul, u, u, vp, ul]),
+        "HapGpuEncodeFramesAlpha": (u, [vp, u, P(vp), u, u, ul, u, u, P(vp), P(ul), P(ul), P(u), u]),
+        "HapGpuEncodeFramesAlphaBegin": (u, [vp, u, P(vp), u, u, ul, u, u, P(vp), P(ul), P(ul), P(u), u]),
+        "HapGpuDecodeFramesAlpha": (u, [vp, u, P(vp), P(ul), P(vp), u, u, ul, P(u), u]),
         "HapGpuDecompressRGBA": (u, [vp, vp, ul, u, vp, ul, u, u, vp, ul]),
         "HapGpuDecompressRGBAHalf": (u, [vp, vp, ul, u, u, u, vp, ul]),
         "HapGpuEncodeFrames": (u, [vp, u, u, P(vp), P(ul), P(u), P(u), P(u), P(vp), P(ul), P(ul), P(u), u]),

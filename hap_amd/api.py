@@ -314,6 +314,21 @@ class Context:
             return r, (C.string_at(output, used.value) if r == 0 else None)
         return r, used.value
 
+    def compress_alpha(self, alpha, width, height, row_bytes, output=None):
+        """A8 picture (one byte a texel; numpy uint8, bytes-like or torch, host or device) -> one A_RGTC1 texture
+        (HapGpuCompressAlpha).  Returns (result, bytes | None), or (result, bytes used) into `output`."""
+        need = (width // 4) * (height // 4) * 8
+        a, _n, _k = _addr_len(alpha)
+        own = output is None
+        if own:
+            output = (C.c_ubyte * max(1, need))()
+        oa, on, _k2 = _addr_len(output)
+        used = C.c_ulong(0)
+        r = lib.HapGpuCompressAlpha(self.handle, a, width, height, row_bytes, oa, on, C.byref(used))
+        if own:
+            return r, (C.string_at(output, used.value) if r == 0 else None)
+        return r, used.value
+
     def decompress_rgba(self, texture, texture_format, width, height, rgba=None, alpha=None, row_bytes=None):
         """Texture (+ optional RGTC1 alpha plane) -> RGBA8. Returns (result, bytes | None)."""
         ta, tn, _k = _addr_len(texture)
@@ -346,6 +361,24 @@ class Context:
         else:
             oa, _on, _k2 = _addr_len(out)
         r = lib.HapGpuDecompressRGBAHalf(self.handle, ta, tn, texture_format, width, height, oa, row_bytes)
+        if own:
+            return r, (C.string_at(oa, row_bytes * height) if r == 0 else None)
+        return r, None
+
+    def decompress_alpha(self, texture, width, height, out=None, row_bytes=None):
+        """A_RGTC1 texture -> A8 picture (HapGpuDecompressAlpha). Returns (result, bytes | None): the picture's bytes
+        (rows row_bytes apart) when `out` is None, else None (the picture is in `out`: numpy or torch, host or
+        device)."""
+        ta, tn, _k = _addr_len(texture)
+        row_bytes = row_bytes or width
+        own = out is None
+        if own:
+            out = (C.c_ubyte * (row_bytes * height + 16))()
+            base = C.addressof(out)
+            oa = base + (-base) % 16
+        else:
+            oa, _on, _k2 = _addr_len(out)
+        r = lib.HapGpuDecompressAlpha(self.handle, ta, tn, width, height, oa, row_bytes)
         if own:
             return r, (C.string_at(oa, row_bytes * height) if r == 0 else None)
         return r, None
@@ -441,6 +474,30 @@ class Context:
         self._pending = (used, results) + keep                                      # alive until the second half
         return r
 
+    def _encode_alpha(self, fn, alpha_frames, width, height, row_bytes, compressor, chunk_count, outputs, flags):
+        nf = len(alpha_frames)
+        ptrs, infos = self._ptr_array(alpha_frames)
+        optrs, oinfos = self._ptr_array(outputs)
+        olens = (C.c_ulong * nf)(*[i[1] for i in oinfos])
+        used = (C.c_ulong * nf)()
+        results = (C.c_uint * nf)()
+        r = fn(self.handle, nf, ptrs, width, height, row_bytes, compressor, chunk_count, optrs, olens, used, results, flags)
+        return r, used, results, (ptrs, optrs, olens, infos, oinfos)
+
+    def encode_frames_alpha(self, alpha_frames, width, height, row_bytes, compressor, chunk_count, outputs, flags=0):
+        """A8 pictures -> Hap Alpha-Only frames of one A_RGTC1 texture (HapGpuEncodeFramesAlpha).  Returns
+        (result, used[], results[])."""
+        r, used, results, _keep = self._encode_alpha(lib.HapGpuEncodeFramesAlpha, alpha_frames, width, height, row_bytes,
+                                                     compressor, chunk_count, outputs, flags)
+        return r, list(used), list(results)
+
+    def encode_frames_alpha_begin(self, alpha_frames, width, height, row_bytes, compressor, chunk_count, outputs, flags=0):
+        """First half of encode_frames_alpha (HapGpuEncodeFramesAlphaBegin); encode_finish() is the second."""
+        r, used, results, keep = self._encode_alpha(lib.HapGpuEncodeFramesAlphaBegin, alpha_frames, width, height,
+                                                    row_bytes, compressor, chunk_count, outputs, flags)
+        self._pending = (used, results) + keep                                      # alive until the second half
+        return r
+
     def encode_finish(self):
         r = lib.HapGpuEncodeFramesFinish(self.handle)
         pending, self._pending = getattr(self, "_pending", None), None
@@ -501,6 +558,18 @@ class Context:
         results = (C.c_uint * nf)()
         r = lib.HapGpuDecodeFramesRGBAHalf(self.handle, nf, ptrs, lens, optrs, width, height, row_bytes or width * 8,
                                            results, flags)
+        return r, list(results)
+
+    def decode_frames_alpha(self, frames, frame_bytes, pictures, width, height, row_bytes=None, flags=0):
+        """Hap Alpha-Only frames -> A8 pictures in one call (HapGpuDecodeFramesAlpha).  Returns (result, results[])."""
+        nf = len(frames)
+        if len(pictures) != nf:
+            raise ValueError("one picture per frame")
+        ptrs, infos = self._ptr_array(frames)
+        lens = (C.c_ulong * nf)(*[fb if fb is not None else infos[i][1] for i, fb in enumerate(frame_bytes)])
+        optrs, _oinfos = self._ptr_array(pictures)
+        results = (C.c_uint * nf)()
+        r = lib.HapGpuDecodeFramesAlpha(self.handle, nf, ptrs, lens, optrs, width, height, row_bytes or width, results, flags)
         return r, list(results)
 
     def decode_sequence(self, reader, first, count, index, outputs, batch=0):

@@ -8,81 +8,16 @@
 // Arithmetic follows oracle/bc_oracle.c (obc_decode_*) exactly; results are bit-identical.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "bc_decode_core.hpp"
 #include "hapgpu_runtime.hpp"
 
 namespace {
 
+using namespace hapbc;      // decode_alpha, decode_alpha_pairs: the alpha-style half of DXT5 / Hap Q blocks, RGTC1 planes
+
 __device__ __forceinline__ int expand5(int q) { return (q << 3) | (q >> 2); }
 __device__ __forceinline__ int expand6(int q) { return (q << 2) | (q >> 4); }
 __device__ __forceinline__ int clamp255(int v) { return min(max(v, 0), 255); }
-
-// byte `code` (0..7) of the 8-byte table hi:lo
-__device__ __forceinline__ unsigned pick8(unsigned hi, unsigned lo, unsigned code)
-{
-    return __builtin_amdgcn_perm(hi, lo, code) & 0xFFu;
-}
-
-// 16 alpha-style values of an 8-byte block (S3TC alpha / RGTC1): the 8-entry palette is packed into
-// two dwords and every pixel picks its byte with one v_perm_b32
-__device__ __forceinline__ void decode_alpha(uint2 blk, int (&out)[16])
-{
-    const int a0 = (int)(blk.x & 255u), a1 = (int)((blk.x >> 8) & 255u);
-    int v[8];
-    v[0] = a0;
-    v[1] = a1;
-    if (a0 > a1) {
-#pragma unroll
-        for (int i = 1; i < 7; i++)
-            v[i + 1] = (int)(__umul24((unsigned)((7 - i) * a0 + i * a1), 9363u) >> 16);     // / 7, exact below 13107
-    } else {
-#pragma unroll
-        for (int i = 1; i < 5; i++)
-            v[i + 1] = (int)(__umul24((unsigned)((5 - i) * a0 + i * a1), 13108u) >> 16);    // / 5, exact below 3277
-        v[6] = 0;
-        v[7] = 255;
-    }
-    const unsigned lo = (unsigned)v[0] | ((unsigned)v[1] << 8) | ((unsigned)v[2] << 16) | ((unsigned)v[3] << 24);
-    const unsigned hi = (unsigned)v[4] | ((unsigned)v[5] << 8) | ((unsigned)v[6] << 16) | ((unsigned)v[7] << 24);
-    // 48 index bits = blk.x[16..31] | blk.y << 16 : pixels 0..7 in the low 24 bits, 8..15 above
-    const unsigned lo24 = (blk.x >> 16) | ((blk.y & 0xFFu) << 16);
-    const unsigned hi24 = blk.y >> 8;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        out[i] = (int)pick8(hi, lo, (lo24 >> (3 * i)) & 7u);
-        out[8 + i] = (int)pick8(hi, lo, (hi24 >> (3 * i)) & 7u);
-    }
-}
-
-// The same 16 values as packed pairs (pixel 2m in the low half, 2m + 1 in the high half of pairs[m]): one v_perm_b32
-// fetches two palette bytes, the second selector byte of each half (0x0c) reads as zero
-__device__ __forceinline__ void decode_alpha_pairs(uint2 blk, unsigned (&pairs)[8])
-{
-    const int a0 = (int)(blk.x & 255u), a1 = (int)((blk.x >> 8) & 255u);
-    int v[8];
-    v[0] = a0;
-    v[1] = a1;
-    if (a0 > a1) {
-#pragma unroll
-        for (int i = 1; i < 7; i++)
-            v[i + 1] = (int)(__umul24((unsigned)((7 - i) * a0 + i * a1), 9363u) >> 16);
-    } else {
-#pragma unroll
-        for (int i = 1; i < 5; i++)
-            v[i + 1] = (int)(__umul24((unsigned)((5 - i) * a0 + i * a1), 13108u) >> 16);
-        v[6] = 0;
-        v[7] = 255;
-    }
-    const unsigned lo = (unsigned)v[0] | ((unsigned)v[1] << 8) | ((unsigned)v[2] << 16) | ((unsigned)v[3] << 24);
-    const unsigned hi = (unsigned)v[4] | ((unsigned)v[5] << 8) | ((unsigned)v[6] << 16) | ((unsigned)v[7] << 24);
-    const unsigned lo24 = (blk.x >> 16) | ((blk.y & 0xFFu) << 16);
-    const unsigned hi24 = blk.y >> 8;
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-        const unsigned c_lo = (lo24 >> (6 * m)) & 63u, c_hi = (hi24 >> (6 * m)) & 63u;     // two 3-bit codes each
-        pairs[m] = __builtin_amdgcn_perm(hi, lo, ((c_lo | (c_lo << 13)) & 0x00070007u) | 0x0c000c00u);
-        pairs[4 + m] = __builtin_amdgcn_perm(hi, lo, ((c_hi | (c_hi << 13)) & 0x00070007u) | 0x0c000c00u);
-    }
-}
 
 typedef short pk_i16 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ pk_i16 as_pk(unsigned v) { return __builtin_bit_cast(pk_i16, v); }
@@ -262,16 +197,22 @@ void launch(const HapGpuPictureTable &t, unsigned pictures, bool alpha, unsigned
 } // namespace
 
 // hapgpu_abi.h: DXT1, DXT5, YCoCg-DXT5 (with_alpha: + RGTC1 plane) here, BC7 in bptc_decode.hip (no alpha plane), BC6H
-// in bc6h_decode.hip (no alpha plane, 8-byte texels).  Returns 0 launched, 1 bad arguments, 4 launch failure.
+// in bc6h_decode.hip (no alpha plane, 8-byte texels), lone RGTC1 textures to A8 pictures in alpha_plane.hip.  Returns 0
+// launched, 1 bad arguments, 4 launch failure.
 extern "C" int hapgpu_k_block_decode(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, int with_alpha,
-                                     unsigned width, unsigned height, unsigned format, size_t row_bytes)
+                                     unsigned width, unsigned height, unsigned format, size_t row_bytes, int wide,
+                                     unsigned picture_kind)
 {
     scoped_timing st(rt, 6);
     const hipStream_t stream = hapgpu_rt_stream(rt);
-    const bool half = format == 0x8E8F || format == 0x8E8E;
+    const bool half = picture_kind == HAPGPU_PICTURE_RGBA16F, plane = picture_kind == HAPGPU_PICTURE_A8;
+    if (picture_kind > HAPGPU_PICTURE_A8 || half != (format == 0x8E8F || format == 0x8E8E) ||
+        plane != (format == 0x8DBB) || (plane && (with_alpha || height / 4u > 65535u)))
+        return 1;
     if (!table || !(table->column[0] || table->one[0]) || !(table->column[2] || table->one[2]) ||
         (with_alpha && !(table->column[1] || table->one[1])) || pictures == 0 || pictures > 65535u || width == 0 ||
-        height == 0 || (width & 3u) || (height & 3u) || row_bytes < (size_t)width * (half ? 8u : 4u) || (row_bytes & 15u))
+        height == 0 || (width & 3u) || (height & 3u) || row_bytes < (size_t)width * HAPGPU_PICTURE_TEXEL_BYTES(picture_kind) ||
+        (row_bytes & (plane ? 3u : 15u)))
         return 1;
     const HapGpuPictureTable &t = *table;
     const unsigned bx = width / 4u, by = height / 4u;
@@ -281,6 +222,7 @@ extern "C" int hapgpu_k_block_decode(hapgpu_rt *rt, const HapGpuPictureTable *ta
     case 0x83F0: launch<0>(t, pictures, with_alpha != 0, bx, by, row_bytes, stream); break;
     case 0x83F3: launch<1>(t, pictures, with_alpha != 0, bx, by, row_bytes, stream); break;
     case 0x01: launch<2>(t, pictures, with_alpha != 0, bx, by, row_bytes, stream); break;
+    case 0x8DBB: hapgpu_launch_alpha_decode(t, pictures, bx, by, row_bytes, wide != 0, stream); break;
     case 0x8E8C: hapgpu_launch_bptc_decode(t, pictures, bx, by, row_bytes, stream); break;
     case 0x8E8F: hapgpu_launch_bc6h_decode(t, pictures, false, bx, by, row_bytes, stream); break;
     case 0x8E8E: hapgpu_launch_bc6h_decode(t, pictures, true, bx, by, row_bytes, stream); break;

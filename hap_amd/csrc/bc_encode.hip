@@ -82,15 +82,20 @@ void launch(const HapGpuPictureTable &t, unsigned pictures, size_t row_bytes, un
 
 // hapgpu_abi.h.  Returns 0 launched, 1 bad arguments, 4 launch failure.
 extern "C" int hapgpu_k_block_encode(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, unsigned width,
-                                     unsigned height, size_t row_bytes, unsigned format, int with_alpha, int wide)
+                                     unsigned height, size_t row_bytes, unsigned format, int with_alpha, int wide,
+                                     unsigned picture_kind)
 {
     scoped_timing st(rt, 0);
     const hipStream_t stream = hapgpu_rt_stream(rt);
-    // BC6H is made from RGBA16F pictures: 8 bytes a texel, rows a multiple of 16 bytes
-    const bool half = format == 0x8E8F || format == 0x8E8E;
+    // BC6H is made from RGBA16F pictures and nothing else is: 8 bytes a texel, rows a multiple of 16 bytes; A8
+    // pictures (alpha_plane.hip) make RGTC1 alone
+    const bool half = picture_kind == HAPGPU_PICTURE_RGBA16F, plane = picture_kind == HAPGPU_PICTURE_A8;
+    if (picture_kind > HAPGPU_PICTURE_A8 || half != (format == 0x8E8F || format == 0x8E8E) ||
+        (plane && (format != 0x8DBB || with_alpha || height / 4u > 65535u)))
+        return 1;
     if (!table || !(table->column[0] || table->one[0]) || !(table->column[1] || table->one[1]) ||
         (with_alpha && (format != 0x01 || !(table->column[2] || table->one[2]))) || pictures == 0 || pictures > 65535u ||
-        width == 0 || height == 0 || (width & 3u) || (height & 3u) || row_bytes < (size_t)width * (half ? 8u : 4u) ||
+        width == 0 || height == 0 || (width & 3u) || (height & 3u) || row_bytes < (size_t)width * HAPGPU_PICTURE_TEXEL_BYTES(picture_kind) ||
         (row_bytes & (half ? 15u : 3u)))
         return 1;
     const HapGpuPictureTable &t = *table;
@@ -104,7 +109,12 @@ extern "C" int hapgpu_k_block_encode(hapgpu_rt *rt, const HapGpuPictureTable *ta
         else
             launch<kFmtYCoCg>(t, pictures, row_bytes, bx, by, wide != 0, stream);
         break;
-    case 0x8DBB: launch<kFmtRGTC1>(t, pictures, row_bytes, bx, by, wide != 0, stream); break;
+    case 0x8DBB:
+        if (plane)
+            hapgpu_launch_alpha_encode(t, pictures, bx, by, row_bytes, wide != 0, stream);
+        else
+            launch<kFmtRGTC1>(t, pictures, row_bytes, bx, by, wide != 0, stream);
+        break;
     case 0x8E8C: hapgpu_launch_bptc_encode(t, pictures, bx, by, row_bytes, wide != 0, stream); break;
     case 0x8E8F:
     case 0x8E8E: hapgpu_launch_bc6h_encode(t, pictures, format == 0x8E8E, bx, by, row_bytes, stream); break;

@@ -39,6 +39,7 @@ unsigned int HapGpuCreate(int device, HapGpuContext **context)
         c->no_half_tiles = HAP_AB_ENV("HAP_AMD_NO_HALF_TILES") ? 1u : 0u;
         c->no_block_scan = getenv("HAP_AMD_NO_BLOCK_SCAN") ? 1u : 0u;
         c->no_fusion = getenv("HAP_AMD_NO_FUSION") ? 1u : 0u;
+        c->no_wide_planes = HAP_AB_ENV("HAP_AMD_NO_WIDE_PLANES") ? 1u : 0u;
         c->no_placing = getenv("HAP_AMD_NO_PLACING") ? 1u : 0u;
         c->placing_holdoff_calls = getenv("HAP_AMD_PLACING_HOLDOFF") ? (unsigned)atoi(getenv("HAP_AMD_PLACING_HOLDOFF")) : 8u;
         c->placing_min_frames = getenv("HAP_AMD_PLACING_MIN_FRAMES") ? (unsigned)atoi(getenv("HAP_AMD_PLACING_MIN_FRAMES")) : 8u;
@@ -482,7 +483,7 @@ unsigned int HapGpuCompressRGBA(HapGpuContext *context, const void *rgba, unsign
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
     r = hapb_compress_rgba(context, rgba, width, height, rowBytes, textureFormat, output, outputBytes,
-                           outputBytesUsed, 1, 0u, 0);
+                           outputBytesUsed, 1, 0u, HAPGPU_PICTURE_RGBA8);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -497,7 +498,7 @@ unsigned int HapGpuCompressRGBAFlags(HapGpuContext *context, const void *rgba, u
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
     r = hapb_compress_rgba(context, rgba, width, height, rowBytes, textureFormat, output, outputBytes,
-                           outputBytesUsed, 1, flags, 0);
+                           outputBytesUsed, 1, flags, HAPGPU_PICTURE_RGBA8);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -511,7 +512,7 @@ unsigned int HapGpuDecompressRGBA(HapGpuContext *context, const void *texture, u
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
     r = hapb_decompress_rgba(context, texture, textureBytes, textureFormat, alphaTexture, alphaBytes, width, height,
-                             rgba, rowBytes, 0);
+                             rgba, rowBytes, HAPGPU_PICTURE_RGBA8);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -524,7 +525,8 @@ unsigned int HapGpuDecompressRGBAHalf(HapGpuContext *context, const void *textur
     if (!context)
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
-    r = hapb_decompress_rgba(context, texture, textureBytes, textureFormat, NULL, 0, width, height, rgbaHalf, rowBytes, 1);
+    r = hapb_decompress_rgba(context, texture, textureBytes, textureFormat, NULL, 0, width, height, rgbaHalf, rowBytes,
+                             HAPGPU_PICTURE_RGBA16F);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -623,7 +625,7 @@ unsigned int HapGpuCompressRGBAHalf(HapGpuContext *context, const void *rgbaHalf
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
     r = hapb_compress_rgba(context, rgbaHalf, width, height, rowBytes, textureFormat, output, outputBytes,
-                           outputBytesUsed, 1, 0u, 1);
+                           outputBytesUsed, 1, 0u, HAPGPU_PICTURE_RGBA16F);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -642,13 +644,14 @@ unsigned int HapGpuEncodeFramesRGBAHalf(HapGpuContext *context, unsigned int fra
     hapgpu_rt_lock(context->rt);
     if (frameCount <= HAP_BATCH_SLICE || !rgbaHalfFrames || !outputBuffers || !outputBuffersBytes || !outputBuffersBytesUsed || !results) {
         r = hapb_encode_pictures(context, frameCount, rgbaHalfFrames, width, height, rowBytes, 1u, &textureFormat, &compressor,
-                             &chunkCount, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, 1);
+                             &chunkCount, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, HAPGPU_PICTURE_RGBA16F);
     } else {
         for (done = 0; done < frameCount; done += HAP_BATCH_SLICE) {
             const unsigned n = frameCount - done < HAP_BATCH_SLICE ? frameCount - done : HAP_BATCH_SLICE;
             const unsigned rc = hapb_encode_pictures(context, n, rgbaHalfFrames + done, width, height, rowBytes, 1u, &textureFormat,
                                                  &compressor, &chunkCount, outputBuffers + done, outputBuffersBytes + done,
-                                                 outputBuffersBytesUsed + done, results + done, flags, 1);
+                                                 outputBuffersBytesUsed + done, results + done, flags,
+                                                 HAPGPU_PICTURE_RGBA16F);
             if (r == HapResult_No_Error)
                 r = rc;
         }
@@ -671,7 +674,86 @@ unsigned int HapGpuEncodeFramesRGBAHalfBegin(HapGpuContext *context, unsigned in
     hapgpu_rt_lock(context->rt);
     context->defer_encode = 1u;
     r = hapb_encode_pictures(context, frameCount, rgbaHalfFrames, width, height, rowBytes, 1u, &textureFormat, &compressor,
-                         &chunkCount, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, 1);
+                         &chunkCount, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, HAPGPU_PICTURE_RGBA16F);
+    context->defer_encode = 0u;
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+/* A8 pictures -> Hap Alpha-Only: the RGBA calls with 1-byte texels and one RGTC1 texture per frame */
+unsigned int HapGpuCompressAlpha(HapGpuContext *context, const void *alpha, unsigned int width, unsigned int height,
+                                 unsigned long rowBytes, void *output, unsigned long outputBytes,
+                                 unsigned long *outputBytesUsed)
+{
+    unsigned r;
+    if (!context)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_compress_rgba(context, alpha, width, height, rowBytes, HapTextureFormat_A_RGTC1, output, outputBytes,
+                           outputBytesUsed, 1, 0u, HAPGPU_PICTURE_A8);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+unsigned int HapGpuDecompressAlpha(HapGpuContext *context, const void *texture, unsigned long textureBytes,
+                                   unsigned int width, unsigned int height, void *alpha, unsigned long rowBytes)
+{
+    unsigned r;
+    if (!context)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_decompress_rgba(context, texture, textureBytes, HapTextureFormat_A_RGTC1, NULL, 0, width, height, alpha,
+                             rowBytes, HAPGPU_PICTURE_A8);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+unsigned int HapGpuEncodeFramesAlpha(HapGpuContext *context, unsigned int frameCount, const void *const *alphaFrames,
+                                     unsigned int width, unsigned int height, unsigned long rowBytes,
+                                     unsigned int compressor, unsigned int chunkCount, void *const *outputBuffers,
+                                     const unsigned long *outputBuffersBytes, unsigned long *outputBuffersBytesUsed,
+                                     unsigned int *results, unsigned int flags)
+{
+    const unsigned format = HapTextureFormat_A_RGTC1;
+    unsigned r = HapResult_No_Error, done;
+    if (!context)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    if (frameCount <= HAP_BATCH_SLICE || !alphaFrames || !outputBuffers || !outputBuffersBytes || !outputBuffersBytesUsed || !results) {
+        r = hapb_encode_pictures(context, frameCount, alphaFrames, width, height, rowBytes, 1u, &format, &compressor,
+                                 &chunkCount, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags,
+                                 HAPGPU_PICTURE_A8);
+    } else {
+        for (done = 0; done < frameCount; done += HAP_BATCH_SLICE) {
+            const unsigned n = frameCount - done < HAP_BATCH_SLICE ? frameCount - done : HAP_BATCH_SLICE;
+            const unsigned rc = hapb_encode_pictures(context, n, alphaFrames + done, width, height, rowBytes, 1u, &format,
+                                                     &compressor, &chunkCount, outputBuffers + done, outputBuffersBytes + done,
+                                                     outputBuffersBytesUsed + done, results + done, flags,
+                                                     HAPGPU_PICTURE_A8);
+            if (r == HapResult_No_Error)
+                r = rc;
+        }
+    }
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+unsigned int HapGpuEncodeFramesAlphaBegin(HapGpuContext *context, unsigned int frameCount,
+                                          const void *const *alphaFrames, unsigned int width, unsigned int height,
+                                          unsigned long rowBytes, unsigned int compressor, unsigned int chunkCount,
+                                          void *const *outputBuffers, const unsigned long *outputBuffersBytes,
+                                          unsigned long *outputBuffersBytesUsed, unsigned int *results,
+                                          unsigned int flags)
+{
+    const unsigned format = HapTextureFormat_A_RGTC1;
+    unsigned r;
+    if (!context || frameCount > HAP_BATCH_SLICE)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    context->defer_encode = 1u;
+    r = hapb_encode_pictures(context, frameCount, alphaFrames, width, height, rowBytes, 1u, &format, &compressor,
+                             &chunkCount, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags,
+                             HAPGPU_PICTURE_A8);
     context->defer_encode = 0u;
     hapgpu_rt_unlock(context->rt);
     return r;
@@ -820,6 +902,21 @@ unsigned int HapGpuDecodeFramesRGBAHalf(HapGpuContext *context, unsigned int fra
     hapgpu_rt_lock(context->rt);
     r = hapb_decode_rgba_half(context, frameCount, inputBuffers, inputBuffersBytes, rgbaHalfFrames, width, height,
                               rowBytes, results, flags);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+unsigned int HapGpuDecodeFramesAlpha(HapGpuContext *context, unsigned int frameCount,
+                                     const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
+                                     void *const *alphaFrames, unsigned int width, unsigned int height,
+                                     unsigned long rowBytes, unsigned int *results, unsigned int flags)
+{
+    unsigned r;
+    if (!context)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_decode_alpha(context, frameCount, inputBuffers, inputBuffersBytes, alphaFrames, width, height, rowBytes,
+                          results, flags);
     hapgpu_rt_unlock(context->rt);
     return r;
 }

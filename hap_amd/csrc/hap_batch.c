@@ -477,7 +477,8 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                                                            pair ? dt + 2u * (size_t)job->frame_count : NULL}, {0u, 0u, 0u}};
                             launch_rc |= job->height / 4u > 65535u ? 1u :
                                          (unsigned)hapgpu_k_block_encode(rt, &t, job->frame_count, job->width, job->height,
-                                                                         job->row_bytes, job->formats[i], pair, job->wide);
+                                                                         job->row_bytes, job->formats[i], pair, job->wide,
+                                                                         job->picture_kind);
                         }
                 }
                 launch_rc |= (unsigned)hapgpu_rt_h2d(rt, dframes, hframes, sizeof(HapGpuFrameEnc) * live);
@@ -711,20 +712,43 @@ void hapb_encode_abandon(HapGpuContext *ctx, HapbEncodePending *pd)
     free(pd);
 }
 
-/* bytes of a texel of the pictures a texture format is made from and decoded to: RGBA16F for BC6H, else RGBA8 */
-static size_t texel_bytes(unsigned format)
+/* The size of a texel belongs to the pictures (HAPGPU_PICTURE_TEXEL_BYTES of their kind), not to the texture format:
+   RGTC1 is made from RGBA8 pictures and from A8 ones.  What a format does fix is which pictures may hold it. */
+static int is_bc6h(unsigned format)
 {
-    return format == HapTextureFormat_RGB_BPTC_UNSIGNED_FLOAT || format == HapTextureFormat_RGB_BPTC_SIGNED_FLOAT ? 8u : 4u;
+    return format == HapTextureFormat_RGB_BPTC_UNSIGNED_FLOAT || format == HapTextureFormat_RGB_BPTC_SIGNED_FLOAT;
+}
+
+/* pictures of `kind` make `format` (bptc: the caller asked for BC7 from RGBA8): RGBA16F makes BC6H and nothing else
+   does, A8 makes RGTC1 */
+static int kind_makes_format(unsigned kind, unsigned format, int bptc)
+{
+    if (kind == HAPGPU_PICTURE_RGBA16F)
+        return is_bc6h(format);
+    if (kind == HAPGPU_PICTURE_A8)
+        return format == HapTextureFormat_A_RGTC1;
+    return format == HapTextureFormat_RGB_DXT1 || format == HapTextureFormat_RGBA_DXT5 ||
+           format == HapTextureFormat_YCoCg_DXT5 || format == HapTextureFormat_A_RGTC1 || bptc;
+}
+
+/* what the kernels ask of a picture's address (in device memory) and row pitch when they read it: RGBA16F 16 bytes,
+   else 4 */
+static unsigned source_align_mask(unsigned kind)
+{
+    return kind == HAPGPU_PICTURE_RGBA16F ? 15u : 3u;
 }
 
 unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width, unsigned height,
                             unsigned long row_bytes, unsigned format, void *output,
-                            unsigned long output_bytes, unsigned long *used, int synchronise, unsigned flags, int half)
+                            unsigned long output_bytes, unsigned long *used, int synchronise, unsigned flags,
+                            unsigned picture_kind)
 {
-    /* BC7 only when asked (HAPGPU_ENCODE_BPTC_BLOCKS); BC6H only from half pictures, and nothing else from those */
+    /* BC7 only when asked (HAPGPU_ENCODE_BPTC_BLOCKS); BC6H only from half pictures, and nothing else from those; A8
+       pictures make RGTC1 */
     const int bptc = (flags & HAPGPU_ENCODE_BPTC_BLOCKS) && format == HapTextureFormat_RGBA_BPTC_UNORM;
-    const int bc6h = texel_bytes(format) == 8u;
-    const size_t texel = half ? 8u : 4u;
+    const int grid_rows = bptc || picture_kind != HAPGPU_PICTURE_RGBA8;    /* a block row per grid row */
+    const size_t texel = HAPGPU_PICTURE_TEXEL_BYTES(picture_kind);
+    const unsigned align = source_align_mask(picture_kind);
     hapgpu_rt *rt = ctx->rt;
     const size_t block = hapf_block_bytes(format);
     HapGpuPictureTable t = {{NULL, NULL, NULL}, {0u, 0u, 0u}};
@@ -735,18 +759,16 @@ unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width
     if (context_busy(ctx, NULL, 0))
         return HapResult_Internal_Error;
     if (!rgba || !output || width == 0 || height == 0 || (width & 3u) || (height & 3u) ||
-        row_bytes < (unsigned long)width * texel ||
-        (half ? !bc6h : (format != HapTextureFormat_RGB_DXT1 && format != HapTextureFormat_RGBA_DXT5 &&
-                         format != HapTextureFormat_YCoCg_DXT5 && format != HapTextureFormat_A_RGTC1 && !bptc)))
+        row_bytes < (unsigned long)width * texel || !kind_makes_format(picture_kind, format, bptc))
         return HapResult_Bad_Arguments;
     need = (size_t)(width / 4u) * (height / 4u) * block;
     if (output_bytes < need)
         return HapResult_Buffer_Too_Small;
     /* device pictures 4-byte aligned with rows a multiple of 4 (half pictures: 16 and 16), device outputs aligned to
-       their blocks; at most 65535 block rows for BC7 and BC6H, 2^32 * 255/256 blocks for the others */
-    if ((row_bytes & (half ? 15u : 3u)) || (is_dev(ctx, rgba) && ((uintptr_t)rgba & (half ? 15u : 3u))) ||
+       their blocks; at most 65535 block rows for BC7, BC6H and A8 pictures, 2^32 * 255/256 blocks for the others */
+    if ((row_bytes & align) || (is_dev(ctx, rgba) && ((uintptr_t)rgba & align)) ||
         (is_dev(ctx, output) && ((uintptr_t)output & (block - 1u))) ||
-        (bptc || half ? height / 4u > 65535u : (unsigned long long)(width / 4u) * (height / 4u) > 0xFFFFFFFFull / 256u * 255u))
+        (grid_rows ? height / 4u > 65535u : (unsigned long long)(width / 4u) * (height / 4u) > 0xFFFFFFFFull / 256u * 255u))
         return HapResult_Bad_Arguments;
     rgba_bytes = (size_t)row_bytes * (height - 1u) + (size_t)width * texel;
     if (!is_dev(ctx, rgba)) {
@@ -762,7 +784,9 @@ unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width
     }
     t.one[0] = (uint64_t)(uintptr_t)src;
     t.one[1] = (uint64_t)(uintptr_t)dst;
-    rc = hapgpu_k_block_encode(rt, &t, 1u, width, height, row_bytes, format, 0, (((uintptr_t)src | row_bytes) & 15u) == 0);
+    rc = hapgpu_k_block_encode(rt, &t, 1u, width, height, row_bytes, format, 0,
+                               (((uintptr_t)src | row_bytes) & 15u) == 0 && !(picture_kind == HAPGPU_PICTURE_A8 && ctx->no_wide_planes),
+                               picture_kind);
     if (rc == 1)
         return HapResult_Bad_Arguments;
     if (rc)
@@ -782,20 +806,39 @@ typedef struct picture_road {
     unsigned kind_count;
     const unsigned *kinds;
     unsigned paired_kinds;      /* bit k: kinds[k] may have an alpha plane (textureCount 2) */
+    unsigned picture_kind;      /* HAPGPU_PICTURE_*: the pictures' layout, and with it the size of a texel */
 } picture_road;
 
-/* RGBA8 pictures (BC7 last: frames of it only with HAPGPU_DECODE_BPTC_PICTURES) and RGBA16F ones */
+/* RGBA8 pictures (BC7 last: frames of it only with HAPGPU_DECODE_BPTC_PICTURES), RGBA16F ones and A8 ones */
 static const unsigned k_rgba_kinds[4] = {HapTextureFormat_RGB_DXT1, HapTextureFormat_RGBA_DXT5, HapTextureFormat_YCoCg_DXT5,
                                          HapTextureFormat_RGBA_BPTC_UNORM};
 static const unsigned k_half_kinds[2] = {HapTextureFormat_RGB_BPTC_UNSIGNED_FLOAT, HapTextureFormat_RGB_BPTC_SIGNED_FLOAT};
+static const unsigned k_alpha_kinds[1] = {HapTextureFormat_A_RGTC1};
+
+static picture_road road_of(unsigned picture_kind, unsigned flags)
+{
+    if (picture_kind == HAPGPU_PICTURE_RGBA16F)
+        return (picture_road){2u, k_half_kinds, 0u, picture_kind};
+    if (picture_kind == HAPGPU_PICTURE_A8)
+        return (picture_road){1u, k_alpha_kinds, 0u, picture_kind};
+    return (picture_road){(flags & HAPGPU_DECODE_BPTC_PICTURES) ? 4u : 3u, k_rgba_kinds, 0x7u, picture_kind};
+}
+
+/* what the block decoders ask of a picture's address (in device memory) and row pitch when they write it: 16-byte
+   stores for RGBA8 and RGBA16F; A8 pictures take dword stores, and 16-byte ones where address and pitch allow */
+static unsigned picture_align_mask(unsigned kind)
+{
+    return kind == HAPGPU_PICTURE_A8 ? 3u : 15u;
+}
 
 unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
                               const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                              void *picture, unsigned long row_bytes, int half)
+                              void *picture, unsigned long row_bytes, unsigned picture_kind)
 {
-    const picture_road road = half ? (picture_road){2u, k_half_kinds, 0u} : (picture_road){4u, k_rgba_kinds, 0x7u};
+    const picture_road road = road_of(picture_kind, HAPGPU_DECODE_BPTC_PICTURES);
+    const unsigned align = picture_align_mask(picture_kind);
     hapgpu_rt *rt = ctx->rt;
-    const size_t block = hapf_block_bytes(format), pixel_row = (size_t)width * texel_bytes(format);
+    const size_t block = hapf_block_bytes(format), pixel_row = (size_t)width * HAPGPU_PICTURE_TEXEL_BYTES(picture_kind);
     HapGpuPictureTable t = {{NULL, NULL, NULL}, {0u, 0u, 0u}};
     size_t need, alpha_need, picture_bytes;
     const void *src = texture, *asrc = alpha;
@@ -813,9 +856,11 @@ unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned 
     alpha_need = (size_t)(width / 4u) * (height / 4u) * 8u;
     if (texture_bytes < need || (alpha && alpha_bytes < alpha_need))
         return HapResult_Bad_Arguments;
-    /* rows a multiple of 16 bytes; device textures aligned to their blocks, alpha planes to 8 bytes, pictures to 16 */
-    if ((row_bytes & 15u) || (is_dev(ctx, texture) && ((uintptr_t)texture & (block - 1u))) ||
-        (alpha && is_dev(ctx, alpha) && ((uintptr_t)alpha & 7u)) || (is_dev(ctx, picture) && ((uintptr_t)picture & 15u)))
+    /* rows a multiple of 16 bytes; device textures aligned to their blocks, alpha planes to 8 bytes, pictures to 16
+       (A8 pictures: rows and device pictures to 4 bytes, and at most 65535 block rows) */
+    if ((row_bytes & align) || (is_dev(ctx, texture) && ((uintptr_t)texture & (block - 1u))) ||
+        (alpha && is_dev(ctx, alpha) && ((uintptr_t)alpha & 7u)) || (is_dev(ctx, picture) && ((uintptr_t)picture & align)) ||
+        (picture_kind == HAPGPU_PICTURE_A8 && height / 4u > 65535u))
         return HapResult_Bad_Arguments;
     picture_bytes = (size_t)row_bytes * (height - 1u) + pixel_row;
     if (!is_dev(ctx, texture)) {
@@ -843,7 +888,8 @@ unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned 
     t.one[0] = (uint64_t)(uintptr_t)src;
     t.one[1] = (uint64_t)(uintptr_t)asrc;
     t.one[2] = (uint64_t)(uintptr_t)dst;
-    rc = hapgpu_k_block_decode(rt, &t, 1u, alpha != NULL, width, height, format, row_bytes);
+    rc = hapgpu_k_block_decode(rt, &t, 1u, alpha != NULL, width, height, format, row_bytes,
+                               (((uintptr_t)dst | row_bytes) & 15u) == 0 && !ctx->no_wide_planes, picture_kind);
     if (rc == 1)
         return HapResult_Bad_Arguments;
     if (rc)
@@ -865,30 +911,33 @@ unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                           unsigned long *output_used, unsigned *results, unsigned flags)
 {
     return hapb_encode_pictures(ctx, frame_count, rgba_frames, width, height, row_bytes, count, formats, compressors,
-                                chunk_counts, outputs, output_bytes, output_used, results, flags, 0);
+                                chunk_counts, outputs, output_bytes, output_used, results, flags, HAPGPU_PICTURE_RGBA8);
 }
 
 unsigned hapb_encode_pictures(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
                               unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
                               const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
                               void *const *outputs, const unsigned long *output_bytes,
-                              unsigned long *output_used, unsigned *results, unsigned flags, int half)
+                              unsigned long *output_used, unsigned *results, unsigned flags, unsigned picture_kind)
 {
     hapgpu_rt *rt = ctx->rt;
-    const size_t texel = half ? 8u : 4u;
+    const size_t texel = HAPGPU_PICTURE_TEXEL_BYTES(picture_kind);
+    const unsigned align = source_align_mask(picture_kind);
     unsigned long tex_bytes[2] = {0, 0};
     size_t per_frame = 0, rgba_bytes, tex_off[2] = {0, 0};
     unsigned i, f, rc;
     uint8_t *textures, *rgba_stage = NULL;
     const void **tex_ptrs;
     uint64_t *hsrc, *dsrc;
-    int wide = 1;
+    int wide = !(picture_kind == HAPGPU_PICTURE_A8 && ctx->no_wide_planes);
     if (frame_count == 0)
         return HapResult_No_Error;
     if (context_busy(ctx, results, frame_count))
         return HapResult_Internal_Error;
     if (!results || !rgba_frames || count == 0 || count > 2 || !formats || width == 0 || height == 0 ||
-        (width & 3u) || (height & 3u) || row_bytes < (unsigned long)width * texel || (half && (row_bytes & 15u))) {
+        (width & 3u) || (height & 3u) || row_bytes < (unsigned long)width * texel ||
+        (picture_kind != HAPGPU_PICTURE_RGBA8 && (row_bytes & align)) ||
+        (picture_kind == HAPGPU_PICTURE_A8 && height / 4u > 65535u)) {
         for (f = 0; results && f < frame_count; f++)
             results[f] = HapResult_Bad_Arguments;
         return HapResult_Bad_Arguments;
@@ -896,10 +945,8 @@ unsigned hapb_encode_pictures(HapGpuContext *ctx, unsigned frame_count, const vo
     for (i = 0; i < count; i++) {
         /* (BC7 only when asked, and alone: no Hap variant pairs it with a second texture) */
         const int bptc = (flags & HAPGPU_ENCODE_BPTC_BLOCKS) && count == 1u && formats[i] == HapTextureFormat_RGBA_BPTC_UNORM;
-        /* (half pictures make BC6H, alone, and nothing else; RGBA8 pictures never make it) */
-        if (half ? count != 1u || texel_bytes(formats[i]) != 8u
-                 : (formats[i] != HapTextureFormat_RGB_DXT1 && formats[i] != HapTextureFormat_RGBA_DXT5 &&
-                    formats[i] != HapTextureFormat_YCoCg_DXT5 && formats[i] != HapTextureFormat_A_RGTC1 && !bptc)) {
+        /* (half pictures make BC6H, alone, and nothing else; RGBA8 pictures never make it; A8 pictures make RGTC1, alone) */
+        if ((picture_kind != HAPGPU_PICTURE_RGBA8 && count != 1u) || !kind_makes_format(picture_kind, formats[i], bptc)) {
             for (f = 0; f < frame_count; f++)
                 results[f] = HapResult_Bad_Arguments;
             return HapResult_Bad_Arguments;
@@ -938,8 +985,9 @@ unsigned hapb_encode_pictures(HapGpuContext *ctx, unsigned frame_count, const vo
                 break;
             src = rgba_stage + align_up(rgba_bytes, 256) * f;
         }
-        /* (a half picture in device memory is read 16 bytes at a time: misaligned, its frame is Bad_Arguments) */
-        if (half && ((uintptr_t)src & 15u))
+        /* (a half picture in device memory is read 16 bytes at a time, an A8 one 4: misaligned, its frame is
+           Bad_Arguments) */
+        if (picture_kind != HAPGPU_PICTURE_RGBA8 && ((uintptr_t)src & align))
             continue;
         hsrc[f] = (uint64_t)(uintptr_t)src;
         if (((uintptr_t)src | row_bytes) & 15u)
@@ -964,6 +1012,7 @@ unsigned hapb_encode_pictures(HapGpuContext *ctx, unsigned frame_count, const vo
         job.row_bytes = row_bytes;
         job.wide = wide;
         job.texel_bytes = (unsigned)texel;
+        job.picture_kind = picture_kind;
         for (i = 0; i < count; i++)
             job.formats[i] = formats[i];
         ctx->block_encode_job = &job;
@@ -1835,7 +1884,8 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
     unsigned long *in_bytes, *caps, *used;
     void **outs;
     unsigned *idx, *fmts, *res;
-    const size_t pixel_row = (size_t)width * texel_bytes(road->kinds[0]);
+    const size_t pixel_row = (size_t)width * HAPGPU_PICTURE_TEXEL_BYTES(road->picture_kind);
+    const unsigned align = picture_align_mask(road->picture_kind);
     if (frame_count == 0)
         return HapResult_No_Error;
     if (!results)
@@ -1843,7 +1893,8 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
     if (context_busy(ctx, results, frame_count))
         return HapResult_Internal_Error;
     if (!inputs || !input_bytes || !rgba_frames || texture_count == 0 || texture_count > 2 || width == 0 ||
-        height == 0 || (width & 3u) || (height & 3u) || row_bytes < pixel_row || (row_bytes & 15u)) {
+        height == 0 || (width & 3u) || (height & 3u) || row_bytes < pixel_row || (row_bytes & align) ||
+        (road->picture_kind == HAPGPU_PICTURE_A8 && height / 4u > 65535u)) {
         for (f = 0; f < frame_count; f++)
             results[f] = HapResult_Bad_Arguments;
         return HapResult_Bad_Arguments;
@@ -1906,6 +1957,7 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
             uint64_t *htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, tab_bytes);
             uint64_t *dtab = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, tab_bytes);
             unsigned present = 0, k;
+            int wide = (row_bytes & 15u) == 0 && !ctx->no_wide_planes;      /* A8 pictures: every one of the slice 16-byte aligned, and the pitch */
             if (!htab || !dtab) {
                 for (f = 0; f < n; f++)
                     results[done + f] = HapResult_Internal_Error;
@@ -1941,11 +1993,13 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
                     dst = stage ? stage + align_up(rgba_bytes, 256) * f : NULL;
                     if (!dst)
                         r = HapResult_Internal_Error;
-                } else if (r == HapResult_No_Error && ((uintptr_t)dst & 15u)) {
+                } else if (r == HapResult_No_Error && ((uintptr_t)dst & align)) {
                     r = HapResult_Bad_Arguments;
                 }
                 if (r == HapResult_No_Error) {
                     present |= 1u << k;
+                    if ((uintptr_t)dst & 15u)
+                        wide = 0;
                     htab[(size_t)k * 3u * n + f] = (uint64_t)(uintptr_t)outs[e];
                     htab[(size_t)k * 3u * n + n + f] = texture_count == 2 ? (uint64_t)(uintptr_t)outs[e + 1] : 0u;
                     htab[(size_t)k * 3u * n + 2u * n + f] = (uint64_t)(uintptr_t)dst;
@@ -1958,7 +2012,8 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
                     if (present & (1u << k)) {
                         const uint64_t *col = dtab + (size_t)k * 3u * n;
                         const HapGpuPictureTable t = {{col, col + n, col + 2u * (size_t)n}, {0u, 0u, 0u}};
-                        rc |= hapgpu_k_block_decode(rt, &t, n, texture_count == 2, width, height, road->kinds[k], row_bytes);
+                        rc |= hapgpu_k_block_decode(rt, &t, n, texture_count == 2, width, height, road->kinds[k], row_bytes,
+                                                    wide, road->picture_kind);
                     }
                 for (f = 0; f < n; f++)
                     if (results[done + f] == HapResult_No_Error && stage && !is_dev(ctx, rgba_frames[done + f])) {
@@ -1989,7 +2044,7 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                           const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
                           unsigned width, unsigned height, unsigned long row_bytes, unsigned *results, unsigned flags)
 {
-    const picture_road road = {(flags & HAPGPU_DECODE_BPTC_PICTURES) ? 4u : 3u, k_rgba_kinds, 0x7u};
+    const picture_road road = road_of(HAPGPU_PICTURE_RGBA8, flags);
     return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, rgba_frames, width, height, row_bytes,
                            results, flags, &road);
 }
@@ -1999,7 +2054,17 @@ unsigned hapb_decode_rgba_half(HapGpuContext *ctx, unsigned frame_count, const v
                                const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,
                                unsigned long row_bytes, unsigned *results, unsigned flags)
 {
-    const picture_road road = {2u, k_half_kinds, 0u};
+    const picture_road road = road_of(HAPGPU_PICTURE_RGBA16F, flags);
+    return decode_pictures(ctx, frame_count, inputs, input_bytes, 1u, pictures, width, height, row_bytes, results, flags,
+                           &road);
+}
+
+/* Hap Alpha-Only frames (one RGTC1 texture) -> A8 pictures: the same road with the plane decoder of alpha_plane.hip */
+unsigned hapb_decode_alpha(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                           const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,
+                           unsigned long row_bytes, unsigned *results, unsigned flags)
+{
+    const picture_road road = road_of(HAPGPU_PICTURE_A8, flags);
     return decode_pictures(ctx, frame_count, inputs, input_bytes, 1u, pictures, width, height, row_bytes, results, flags,
                            &road);
 }

@@ -26,6 +26,8 @@ struct HapGpuContext {
     unsigned placing_holdoff_calls; /* HAP_AMD_PLACING_HOLDOFF (default 8): how many */
     unsigned no_placing;      /* HAP_AMD_NO_PLACING: compressed fragments go to slots and are gathered (A/B runs; also set
                                  while a frame whose chunks did not all shrink is encoded again) */
+    unsigned no_wide_planes;  /* HAP_AMD_NO_WIDE_PLANES: A8 pictures take the one-block-per-lane road of alpha_plane.hip even
+                                 where they are 16-byte aligned (A/B runs) */
     unsigned no_half_tiles;   /* HAP_AMD_NO_HALF_TILES: fragment table version 1 even for field streams (A/B runs) */
     /* chunk marks collected from the client's HapDecodeCallback, handed to the retry of a frame whose fragment
        table turned out wrong: the callback is invoked exactly once per HapDecode, as in the reference */
@@ -50,7 +52,9 @@ typedef struct HapbBlockEncodeJob {
     const uint64_t *host_table;    /* pinned: [sources][outputs of texture 0][of texture 1], frame_count each */
     uint64_t *device_table;
     unsigned frame_count, count, width, height, formats[2];
-    unsigned texel_bytes;          /* of the pictures: 4 (RGBA8) or 8 (RGBA16F, which make BC6H and are never fused) */
+    unsigned picture_kind;         /* HAPGPU_PICTURE_*: the pictures' layout */
+    unsigned texel_bytes;          /* of that layout: 4 (RGBA8), 8 (RGBA16F, which make BC6H) or 1 (A8, which make RGTC1);
+                                      only RGBA8 pictures are ever fused into the block compressor */
     unsigned long row_bytes;
     int wide;
 } HapbBlockEncodeJob;
@@ -84,23 +88,26 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                      void *const *outputs, const unsigned long *output_bytes,
                      unsigned long *output_used, unsigned *results, unsigned flags,
                      int inputs_are_device);
-/* one picture -> one texture.  half != 0: an RGBA16F picture and a BC6H format (hapb_encode_rgba's rules) */
+/* one picture -> one texture.  picture_kind (HAPGPU_PICTURE_*): RGBA8 and the DXT / RGTC1 formats (BC7 with
+   HAPGPU_ENCODE_BPTC_BLOCKS), RGBA16F and a BC6H format, or A8 and A_RGTC1 (hapb_encode_pictures' rules) */
 unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width, unsigned height,
                             unsigned long row_bytes, unsigned format, void *output,
-                            unsigned long output_bytes, unsigned long *used, int synchronise, unsigned flags, int half);
-/* one texture -> one picture: half == 0 RGBA8 (DXT1, DXT5, YCoCg-DXT5 with an optional RGTC1 alpha plane, BC7),
-   half != 0 RGBA16F (BC6H unsigned or signed, no alpha plane) */
+                            unsigned long output_bytes, unsigned long *used, int synchronise, unsigned flags,
+                            unsigned picture_kind);
+/* one texture -> one picture of picture_kind: RGBA8 (DXT1, DXT5, YCoCg-DXT5 with an optional RGTC1 alpha plane, BC7),
+   RGBA16F (BC6H unsigned or signed, no alpha plane) or A8 (a lone RGTC1 texture) */
 unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
                               const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                              void *picture, unsigned long row_bytes, int half);
-/* pictures -> frames.  half == 0: RGBA8 pictures and the DXT / RGTC1 formats (BC7 with HAPGPU_ENCODE_BPTC_BLOCKS);
-   half != 0: RGBA16F pictures (rows and device addresses 16-byte aligned) and one BC6H texture */
+                              void *picture, unsigned long row_bytes, unsigned picture_kind);
+/* pictures -> frames.  picture_kind RGBA8: the DXT / RGTC1 formats (BC7 with HAPGPU_ENCODE_BPTC_BLOCKS); RGBA16F (rows
+   and device addresses 16-byte aligned): one BC6H texture; A8 (rows and device addresses 4-byte aligned): one RGTC1
+   texture */
 unsigned hapb_encode_pictures(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
                               unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
                               const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
                               void *const *outputs, const unsigned long *output_bytes,
-                              unsigned long *output_used, unsigned *results, unsigned flags, int half);
-/* ... with half == 0 */
+                              unsigned long *output_used, unsigned *results, unsigned flags, unsigned picture_kind);
+/* ... with RGBA8 pictures */
 unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
                           unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
                           const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
@@ -121,6 +128,11 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
 unsigned hapb_decode_rgba_half(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
                                const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,
                                unsigned long row_bytes, unsigned *results, unsigned flags);
+
+/* Hap Alpha-Only frames (one RGTC1 texture) -> A8 pictures */
+unsigned hapb_decode_alpha(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                           const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,
+                           unsigned long row_bytes, unsigned *results, unsigned flags);
 
 /* groups and output in device memory: tables through the host, payloads device to device */
 unsigned hapb_join_device(HapGpuContext *ctx, unsigned group_count, const void *const *frames,

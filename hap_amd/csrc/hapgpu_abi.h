@@ -296,19 +296,31 @@ typedef struct HapGpuPictureTable {
     uint64_t one[3];
 } HapGpuPictureTable;
 
-/* RGBA8 -> blocks of `hap_texture_format`: RGB_DXT1, RGBA_DXT5, YCoCg_DXT5, A_RGTC1 or RGBA_BPTC_UNORM (BC7); RGBA16F ->
-   RGB_BPTC_UNSIGNED_FLOAT / RGB_BPTC_SIGNED_FLOAT (BC6H: 8 bytes a texel, sources and row_bytes 16-byte aligned);
+/* The layout of the pictures a block-codec launch reads or writes */
+enum {
+    HAPGPU_PICTURE_RGBA8 = 0,      /* 4 bytes a texel */
+    HAPGPU_PICTURE_RGBA16F = 1,    /* 8 bytes a texel: four half floats; BC6H textures only, and those from nothing else */
+    HAPGPU_PICTURE_A8 = 2          /* 1 byte a texel: RGTC1 textures only */
+};
+#define HAPGPU_PICTURE_TEXEL_BYTES(kind) ((kind) == HAPGPU_PICTURE_RGBA16F ? 8u : (kind) == HAPGPU_PICTURE_A8 ? 1u : 4u)
+
+/* pictures of layout `picture_kind` -> blocks of `hap_texture_format`.  RGBA8 -> RGB_DXT1, RGBA_DXT5, YCoCg_DXT5,
+   A_RGTC1 (the alpha channel) or RGBA_BPTC_UNORM (BC7); RGBA16F -> RGB_BPTC_UNSIGNED_FLOAT / RGB_BPTC_SIGNED_FLOAT
+   (BC6H: sources and row_bytes 16-byte aligned); A8 -> A_RGTC1, at most 65535 block rows.
    YCoCg_DXT5 with_alpha: Hap Q Alpha, the RGTC1 alpha plane to the second outputs from the same read of every picture.
    Sources and row_bytes 4-byte aligned, outputs 8- (DXT1, RGTC1) or 16-byte aligned; wide != 0 promises 16-byte aligned
    sources and row pitch. */
 int hapgpu_k_block_encode(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, unsigned width,
-                          unsigned height, size_t row_bytes, unsigned hap_texture_format, int with_alpha, int wide);
-/* blocks of `hap_texture_format` -> pictures: RGB_DXT1, RGBA_DXT5, YCoCg_DXT5 (with_alpha: the RGTC1 plane supplies A)
-   and RGBA_BPTC_UNORM to RGBA8, 4 bytes a texel; RGB_BPTC_UNSIGNED_FLOAT / RGB_BPTC_SIGNED_FLOAT (BC6H) to RGBA16F, 8
-   bytes a texel.  Textures 8- (DXT1) or 16-byte aligned, alpha planes 8-byte aligned, pictures and row_bytes 16-byte
-   aligned. */
+                          unsigned height, size_t row_bytes, unsigned hap_texture_format, int with_alpha, int wide,
+                          unsigned picture_kind);
+/* blocks of `hap_texture_format` -> pictures of layout `picture_kind`: RGB_DXT1, RGBA_DXT5, YCoCg_DXT5 (with_alpha: the
+   RGTC1 plane supplies A) and RGBA_BPTC_UNORM to RGBA8; RGB_BPTC_UNSIGNED_FLOAT / RGB_BPTC_SIGNED_FLOAT (BC6H) to
+   RGBA16F; A_RGTC1 to A8 (at most 65535 block rows).  Textures 8- (DXT1, RGTC1) or 16-byte aligned, alpha planes 8-byte
+   aligned.  RGBA8 and RGBA16F pictures and their row_bytes 16-byte aligned; A8 pictures and their row_bytes 4-byte
+   aligned, and wide != 0 promises 16 bytes for them too (ignored for the other layouts). */
 int hapgpu_k_block_decode(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, int with_alpha,
-                          unsigned width, unsigned height, unsigned hap_texture_format, size_t row_bytes);
+                          unsigned width, unsigned height, unsigned hap_texture_format, size_t row_bytes, int wide,
+                          unsigned picture_kind);
 /* group_tables: HAP_GROUP_TABLE_BYTES bytes per fragment (same indexing as frag_sizes), written for textures whose reserved bit 20 is set */
 int hapgpu_k_snappy_compress(hapgpu_rt *rt, const HapGpuFrameEnc *frames, unsigned frame_count,
                              unsigned max_frags_per_texture, unsigned frag_log2,

@@ -66,6 +66,11 @@ void hapgpu_launch_bptc_decode(const HapGpuPictureTable &t, unsigned pictures, u
                                size_t row_bytes, hipStream_t stream);                 // bptc_decode.hip
 void hapgpu_launch_bc6h_decode(const HapGpuPictureTable &t, unsigned pictures, bool is_signed, unsigned bx,
                                unsigned by, size_t row_bytes, hipStream_t stream);    // bc6h_decode.hip
+// ... and the A8 pictures of both (RGTC1 only; wide: 16-byte aligned pictures and pitch)
+void hapgpu_launch_alpha_encode(const HapGpuPictureTable &t, unsigned pictures, unsigned bx, unsigned by,
+                                size_t row_bytes, bool wide, hipStream_t stream);     // alpha_plane.hip
+void hapgpu_launch_alpha_decode(const HapGpuPictureTable &t, unsigned pictures, unsigned bx, unsigned by,
+                                size_t row_bytes, bool wide, hipStream_t stream);     // alpha_plane.hip
 // snappy_decode.hip
 int hapgpu_group_tables_from_records(HapGpuDecodeUnit *units, unsigned unit_count, const HapGpuDecodeJob *jobs,
                                      const uint32_t *work, unsigned work_slots, const void *recs, const void *joins,

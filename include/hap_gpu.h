@@ -170,7 +170,8 @@ unsigned long HapGpuResolvedBlockCount(HapGpuContext *context);
 
 /* RGBA8 (row-major, rowBytes stride, width/height multiples of 4) -> block
  * compressed texture.  textureFormat is one of RGB_DXT1, RGBA_DXT5,
- * YCoCg_DXT5, A_RGTC1 (A_RGTC1 compresses the alpha channel).  rgba and
+ * YCoCg_DXT5, A_RGTC1 (A_RGTC1 compresses the alpha channel; a plane that is
+ * not part of an RGBA8 picture goes through HapGpuCompressAlpha).  rgba and
  * output: host or device.  *outputBytesUsed = width/4 * height/4 * 8 or 16. */
 unsigned int HapGpuCompressRGBA(HapGpuContext *context,
                                 const void *rgba, unsigned int width, unsigned int height,
@@ -195,7 +196,8 @@ unsigned int HapGpuCompressRGBAFlags(HapGpuContext *context,
  * with BC7.  Device textures of 16-byte blocks must be 16-byte aligned, DXT1 ones 8-byte aligned.
  * rgba must be 16-byte aligned with rowBytes a multiple of 16.  Host or device pointers.  Only the
  * picture's bytes of each row are written, host or device.  BC6H textures are Bad_Arguments here:
- * HapGpuDecompressRGBAHalf expands them. */
+ * HapGpuDecompressRGBAHalf expands them.  So is a lone A_RGTC1 texture: HapGpuDecompressAlpha expands it to
+ * an A8 picture. */
 unsigned int HapGpuDecompressRGBA(HapGpuContext *context,
                                   const void *texture, unsigned long textureBytes, unsigned int textureFormat,
                                   const void *alphaTexture, unsigned long alphaBytes,
@@ -225,6 +227,33 @@ unsigned int HapGpuCompressRGBAHalf(HapGpuContext *context,
                                     unsigned long rowBytes, unsigned int textureFormat,
                                     void *output, unsigned long outputBytes,
                                     unsigned long *outputBytesUsed);
+
+/* --- alpha-only pictures (Hap Alpha-Only: mattes and masks) -----------------------------------
+ * An A8 picture is one byte per texel, row-major, rows rowBytes apart.  The rules of every ...Alpha call:
+ *   - width and height are multiples of 4 (height at most 262140);
+ *   - rowBytes is at least width and a multiple of 4;
+ *   - pointers are host or device; a device picture is 4-byte aligned, a device texture 8-byte aligned;
+ *   - only the picture's own bytes of each row are written: host pictures with longer rows are written row by row,
+ *     and the kernels never store between width and rowBytes.
+ * A picture whose address (in device memory) and rowBytes are both 16-byte aligned is read and written 16 bytes at a
+ * time by lanes that take four blocks each (alpha_plane.hip); any other by the one-block-per-lane form.  The bytes
+ * are the same. */
+
+/* A8 picture -> A_RGTC1 texture, 8 bytes a block: byte for byte the texture HapGpuCompressRGBA(..., A_RGTC1) makes
+ * of an RGBA8 picture that carries the plane in its alpha channel, from a quarter of the bytes.
+ * *outputBytesUsed = width/4 * height/4 * 8; a smaller output is Buffer_Too_Small. */
+unsigned int HapGpuCompressAlpha(HapGpuContext *context,
+                                 const void *alpha, unsigned int width, unsigned int height,
+                                 unsigned long rowBytes,
+                                 void *output, unsigned long outputBytes,
+                                 unsigned long *outputBytesUsed);
+
+/* A_RGTC1 texture -> A8 picture (the RGTC definition's values, bit for bit).  textureBytes below
+ * width/4 * height/4 * 8 is Bad_Arguments. */
+unsigned int HapGpuDecompressAlpha(HapGpuContext *context,
+                                   const void *texture, unsigned long textureBytes,
+                                   unsigned int width, unsigned int height,
+                                   void *alpha, unsigned long rowBytes);
 
 /* Batched HapEncode: frame f is made of `count` textures
  * inputBuffers[f*count + i] of inputBuffersBytes[i] bytes each (every frame of
@@ -334,6 +363,34 @@ unsigned int HapGpuEncodeFramesRGBAHalfBegin(HapGpuContext *context, unsigned in
                                              unsigned int *results,
                                              unsigned int flags);
 
+/* Batched A8 -> Hap Alpha-Only frame: HapGpuEncodeFramesRGBA for A8 pictures (the rules above; a misaligned device
+ * picture makes its frame Bad_Arguments) and one A_RGTC1 texture per frame.  A frame is byte for byte the one
+ * HapGpuEncodeFramesRGBA makes with the same flags and {A_RGTC1} of an RGBA8 picture that carries the plane in its
+ * alpha channel; the flags mean what they mean there.  ...Begin is the first half of the call as
+ * HapGpuEncodeFramesRGBABegin is; HapGpuEncodeFramesFinish finishes it. */
+unsigned int HapGpuEncodeFramesAlpha(HapGpuContext *context, unsigned int frameCount,
+                                     const void *const *alphaFrames,
+                                     unsigned int width, unsigned int height,
+                                     unsigned long rowBytes,
+                                     unsigned int compressor,
+                                     unsigned int chunkCount,
+                                     void *const *outputBuffers,
+                                     const unsigned long *outputBuffersBytes,
+                                     unsigned long *outputBuffersBytesUsed,
+                                     unsigned int *results,
+                                     unsigned int flags);
+unsigned int HapGpuEncodeFramesAlphaBegin(HapGpuContext *context, unsigned int frameCount,
+                                          const void *const *alphaFrames,
+                                          unsigned int width, unsigned int height,
+                                          unsigned long rowBytes,
+                                          unsigned int compressor,
+                                          unsigned int chunkCount,
+                                          void *const *outputBuffers,
+                                          const unsigned long *outputBuffersBytes,
+                                          unsigned long *outputBuffersBytesUsed,
+                                          unsigned int *results,
+                                          unsigned int flags);
+
 /* Batched HapDecode of texture `index` of every frame.  No callback: all
  * chunks of all frames are decoded by the GPU.  Per-frame result codes,
  * bytes used and texture formats follow HapDecode (including the hardening
@@ -374,7 +431,8 @@ unsigned int HapGpuDecodeFrameTextures(HapGpuContext *context, unsigned int fram
  * plane becomes the pictures' alpha.  The block textures live in the context's scratch only (at most 4 GiB of them at a
  * time: longer batches are worked through in slices).  results[f]:
  * HapDecode's code for the frame; Bad_Arguments for a frame whose texture is of another format or geometry than the
- * call says (lone RGTC1 textures have no pixel decoder here; BC6H ones go to HapGpuDecodeFramesRGBAHalf, flag or not).
+ * call says (lone RGTC1 textures, Hap Alpha-Only, go to HapGpuDecodeFramesAlpha; BC6H ones go to
+ * HapGpuDecodeFramesRGBAHalf, flag or not).
  * Hap R frames (one BC7 texture) are
  * Bad_Arguments unless flags has HAPGPU_DECODE_BPTC_PICTURES: then, with textureCount 1, they decode to pictures like
  * the others (textureCount 2 stays Bad_Arguments for them).  A batch may mix Hap, Hap Alpha, Hap Q and Hap R frames:
@@ -400,6 +458,19 @@ unsigned int HapGpuDecodeFramesRGBAHalf(HapGpuContext *context, unsigned int fra
                                         void *const *rgbaHalfFrames,
                                         unsigned int width, unsigned int height, unsigned long rowBytes,
                                         unsigned int *results, unsigned int flags);
+
+/* Hap Alpha-Only frames in, A8 pictures out: HapGpuDecodeFramesRGBA for frames of one A_RGTC1 texture, pictures as
+ * HapGpuDecompressAlpha makes them (the rules of the ...Alpha calls above: rowBytes a multiple of 4, at least width;
+ * device pictures 4-byte aligned; host or device; host pictures with longer rows are written row by row).  The batch
+ * is worked through in slices like the other roads.  flags: the decode flags, as for HapGpuDecodeFrameTextures.
+ * results[f]: HapDecode's code for the frame (a broken frame: Bad_Frame); Bad_Arguments for a frame of another format
+ * (Hap, Hap Q, Hap Q Alpha ...) or geometry, whose picture is left untouched.  The function's result is the first
+ * failure. */
+unsigned int HapGpuDecodeFramesAlpha(HapGpuContext *context, unsigned int frameCount,
+                                     const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
+                                     void *const *alphaFrames,
+                                     unsigned int width, unsigned int height, unsigned long rowBytes,
+                                     unsigned int *results, unsigned int flags);
 
 /* --- one batch over several GPUs: independent frames per GPU ------------------- */
 
