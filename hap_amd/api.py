@@ -347,6 +347,29 @@ class Context:
             return r, (C.string_at(oa, row_bytes * height) if r == 0 else None)
         return r, None
 
+    def decompress_rgba_scaled(self, texture, texture_format, width, height, scale_log2, rgba=None, alpha=None,
+                               row_bytes=None):
+        """Texture (+ optional RGTC1 alpha plane) -> the half- (scale_log2 1) or quarter-size (2) RGBA8 picture of
+        (width >> scale_log2) x (height >> scale_log2): the rounded-up box mean of decompress_rgba's texels
+        (HapGpuDecompressRGBAScaled).  Returns (result, bytes | None)."""
+        ta, tn, _k = _addr_len(texture)
+        aa, an, _k2 = _addr_len(alpha) if alpha is not None else (None, 0, None)
+        shift = scale_log2 if 0 < scale_log2 < 3 else 0          # (a refused scale: nothing is written)
+        row_bytes = row_bytes or (width >> shift) * 4
+        rows = height >> shift
+        own = rgba is None
+        if own:
+            rgba = (C.c_ubyte * (row_bytes * rows + 16))()
+            base = C.addressof(rgba)
+            oa = base + (-base) % 16
+        else:
+            oa, _on, _k3 = _addr_len(rgba)
+        r = lib.HapGpuDecompressRGBAScaled(self.handle, ta, tn, texture_format, aa, an, width, height, scale_log2, oa,
+                                           row_bytes)
+        if own:
+            return r, (C.string_at(oa, row_bytes * rows) if r == 0 else None)
+        return r, None
+
     def decompress_rgba_half(self, texture, texture_format, width, height, out=None, row_bytes=None):
         """BC6H texture -> RGBA16F (four half bit patterns per texel, alpha 1.0). Returns (result, bytes | None):
         the picture's bytes when `out` is None, else None (the picture is in `out`: numpy or torch, host or device,
@@ -545,6 +568,22 @@ class Context:
         results = (C.c_uint * nf)()
         r = lib.HapGpuDecodeFramesRGBA(self.handle, nf, ptrs, lens, texture_count, optrs, width, height,
                                        row_bytes or width * 4, results, flags)
+        return r, list(results)
+
+    def decode_frames_rgba_scaled(self, frames, frame_bytes, texture_count, rgba_frames, width, height, scale_log2,
+                                  row_bytes=None, flags=0):
+        """Frames -> half- (scale_log2 1) or quarter-size (2) RGBA8 pictures in one call (HapGpuDecodeFramesRGBAScaled);
+        width and height are the frames'.  Returns (result, results[])."""
+        nf = len(frames)
+        if len(rgba_frames) != nf:
+            raise ValueError("one picture per frame")
+        ptrs, infos = self._ptr_array(frames)
+        lens = (C.c_ulong * nf)(*[fb if fb is not None else infos[i][1] for i, fb in enumerate(frame_bytes)])
+        optrs, _oinfos = self._ptr_array(rgba_frames)
+        results = (C.c_uint * nf)()
+        shift = scale_log2 if 0 < scale_log2 < 3 else 0
+        r = lib.HapGpuDecodeFramesRGBAScaled(self.handle, nf, ptrs, lens, texture_count, optrs, width, height, scale_log2,
+                                             row_bytes or (width >> shift) * 4, results, flags)
         return r, list(results)
 
     def decode_frames_rgba_half(self, frames, frame_bytes, pictures, width, height, row_bytes=None, flags=0):

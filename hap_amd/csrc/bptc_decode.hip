@@ -66,6 +66,11 @@ typedef unsigned short pk_u16 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ pk_u16 as_pk(unsigned v) { return __builtin_bit_cast(pk_u16, v); }
 __device__ __forceinline__ unsigned as_u32(pk_u16 v) { return __builtin_bit_cast(unsigned, v); }
 
+// S = 0: the full-size picture.  S = 1 / 2: the half- / quarter-size one -- the rounded box mean of 2^S x 2^S texels
+// per output texel (bc_decode.hip's scaled kernels): the decoded texels are summed per channel as they come, still
+// packed as 16-bit pairs (at most 16 x 255 a half), in the block's four quadrants (region 2 * qy + qx) or in one; the
+// rotation's byte order is applied once per output texel.  A lane stores two rows of 8 bytes or one texel.
+template <int S>
 __device__ __forceinline__ void bptc_decode_body(const uint8_t *__restrict__ blocks, unsigned blocks_x,
                                                  unsigned blocks_total, uint8_t *__restrict__ rgba, size_t row_bytes)
 {
@@ -134,8 +139,10 @@ __device__ __forceinline__ void bptc_decode_body(const uint8_t *__restrict__ blo
     const unsigned base_sel = rotation == 0u ? 0x06040200u : rotation == 1u ? 0x00040206u : rotation == 2u ? 0x02040600u : 0x04060200u;
     const unsigned out_sel = reserved ? 0x0C0C0C0Cu : base_sel;
 
-    uint8_t *dst = rgba + (size_t)(4u * by) * row_bytes + 16u * (size_t)bx;
+    uint8_t *dst = rgba + (size_t)((4u >> S) * by) * row_bytes + (size_t)(16u >> S) * bx;
     typedef unsigned v4u __attribute__((ext_vector_type(4)));
+    constexpr int Q = S == 1 ? 4 : 1;
+    pk_u16 sum_rg[Q] = {}, sum_ba[Q] = {};
 #pragma unroll
     for (unsigned r = 0; r < 4u; r++) {
         unsigned px[4];
@@ -158,10 +165,34 @@ __device__ __forceinline__ void bptc_decode_body(const uint8_t *__restrict__ blo
             const pk_u16 k64 = {64, 64}, k32 = {32, 32}, k6 = {6, 6};
             const pk_u16 rg = ((k64 - w_rg) * as_pk(e0rg) + w_rg * as_pk(e1rg) + k32) >> k6;
             const pk_u16 ba = ((k64 - w_ba) * as_pk(e0ba) + w_ba * as_pk(e1ba) + k32) >> k6;
-            px[c] = __builtin_amdgcn_perm(as_u32(ba), as_u32(rg), out_sel);
+            if constexpr (S == 0) {
+                px[c] = __builtin_amdgcn_perm(as_u32(ba), as_u32(rg), out_sel);
+            } else {
+                const unsigned q = S == 1 ? ((r >> 1) << 1) | (c >> 1) : 0u;
+                sum_rg[q] += rg;
+                sum_ba[q] += ba;
+            }
         }
-        const v4u v = {px[0], px[1], px[2], px[3]};
-        __builtin_nontemporal_store(v, reinterpret_cast<v4u *>(dst + (size_t)r * row_bytes));
+        if constexpr (S == 0) {
+            const v4u v = {px[0], px[1], px[2], px[3]};
+            __builtin_nontemporal_store(v, reinterpret_cast<v4u *>(dst + (size_t)r * row_bytes));
+        }
+    }
+    if constexpr (S != 0) {
+        constexpr unsigned short half = 1u << (2 * S - 1);
+        const pk_u16 khalf = {half, half}, kshift = {2 * S, 2 * S};
+        unsigned out[Q];
+#pragma unroll
+        for (int q = 0; q < Q; q++)
+            out[q] = __builtin_amdgcn_perm(as_u32((sum_ba[q] + khalf) >> kshift), as_u32((sum_rg[q] + khalf) >> kshift), out_sel);
+        if constexpr (S == 2) {
+            __builtin_nontemporal_store(out[0], reinterpret_cast<unsigned *>(dst));
+        } else {
+            typedef unsigned v2u __attribute__((ext_vector_type(2)));
+            const v2u upper = {out[0], out[1]}, lower = {out[2], out[3]};
+            __builtin_nontemporal_store(upper, reinterpret_cast<v2u *>(dst));
+            __builtin_nontemporal_store(lower, reinterpret_cast<v2u *>(dst + row_bytes));
+        }
     }
 }
 
@@ -173,7 +204,18 @@ __global__ __launch_bounds__(256) void bptc_decode_kernel(HapGpuPictureTable t, 
     const uint8_t *blocks = (const uint8_t *)picture_address(t, 0);
     if (!blocks)
         return;
-    bptc_decode_body(blocks, blocks_x, blocks_total, (uint8_t *)picture_address(t, 2), row_bytes);
+    bptc_decode_body<0>(blocks, blocks_x, blocks_total, (uint8_t *)picture_address(t, 2), row_bytes);
+}
+
+// ... and pictures of (width >> S) x (height >> S), S = 1 or 2
+template <int S>
+__global__ __launch_bounds__(256) void bptc_decode_scaled_kernel(HapGpuPictureTable t, unsigned blocks_x,
+                                                                 unsigned blocks_total, size_t row_bytes)
+{
+    const uint8_t *blocks = (const uint8_t *)picture_address(t, 0);
+    if (!blocks)
+        return;
+    bptc_decode_body<S>(blocks, blocks_x, blocks_total, (uint8_t *)picture_address(t, 2), row_bytes);
 }
 
 } // namespace
@@ -185,4 +227,16 @@ void hapgpu_launch_bptc_decode(const HapGpuPictureTable &t, unsigned pictures, u
     const unsigned total = bx * by;
     hipLaunchKernelGGL(bptc_decode_kernel, dim3((total + 255u) / 256u, 1, pictures), dim3(256), 0, stream, t, bx, total,
                        row_bytes);
+}
+
+// RGBA_BPTC_UNORM of hapgpu_k_block_decode_scaled (bc_decode.hip): scale_log2 1 or 2
+void hapgpu_launch_bptc_decode_scaled(const HapGpuPictureTable &t, unsigned pictures, unsigned bx, unsigned by,
+                                      size_t row_bytes, unsigned scale_log2, hipStream_t stream)
+{
+    const unsigned total = bx * by;
+    const dim3 grid((total + 255u) / 256u, 1, pictures), block(256);
+    if (scale_log2 == 1u)
+        hipLaunchKernelGGL(bptc_decode_scaled_kernel<1>, grid, block, 0, stream, t, bx, total, row_bytes);
+    else
+        hipLaunchKernelGGL(bptc_decode_scaled_kernel<2>, grid, block, 0, stream, t, bx, total, row_bytes);
 }

@@ -512,7 +512,23 @@ unsigned int HapGpuDecompressRGBA(HapGpuContext *context, const void *texture, u
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
     r = hapb_decompress_rgba(context, texture, textureBytes, textureFormat, alphaTexture, alphaBytes, width, height,
-                             rgba, rowBytes, HAPGPU_PICTURE_RGBA8);
+                             rgba, rowBytes, HAPGPU_PICTURE_RGBA8, 0u);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+/* HapGpuDecompressRGBA at half (scaleLog2 1) or quarter (2) size */
+unsigned int HapGpuDecompressRGBAScaled(HapGpuContext *context, const void *texture, unsigned long textureBytes,
+                                        unsigned int textureFormat, const void *alphaTexture,
+                                        unsigned long alphaTextureBytes, unsigned int width, unsigned int height,
+                                        unsigned int scaleLog2, void *rgba, unsigned long rowBytes)
+{
+    unsigned r;
+    if (!context || scaleLog2 < 1u || scaleLog2 > 2u)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_decompress_rgba(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width, height,
+                             rgba, rowBytes, HAPGPU_PICTURE_RGBA8, scaleLog2);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -526,7 +542,7 @@ unsigned int HapGpuDecompressRGBAHalf(HapGpuContext *context, const void *textur
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
     r = hapb_decompress_rgba(context, texture, textureBytes, textureFormat, NULL, 0, width, height, rgbaHalf, rowBytes,
-                             HAPGPU_PICTURE_RGBA16F);
+                             HAPGPU_PICTURE_RGBA16F, 0u);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -703,7 +719,7 @@ unsigned int HapGpuDecompressAlpha(HapGpuContext *context, const void *texture, 
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
     r = hapb_decompress_rgba(context, texture, textureBytes, HapTextureFormat_A_RGTC1, NULL, 0, width, height, alpha,
-                             rowBytes, HAPGPU_PICTURE_A8);
+                             rowBytes, HAPGPU_PICTURE_A8, 0u);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -886,7 +902,29 @@ unsigned int HapGpuDecodeFramesRGBA(HapGpuContext *context, unsigned int frameCo
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
     r = hapb_decode_rgba(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, rgbaFrames, width, height,
-                         rowBytes, results, flags);
+                         0u, rowBytes, results, flags);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+/* HapGpuDecodeFramesRGBA at half (scaleLog2 1) or quarter (2) size; any other scale refuses the whole call */
+unsigned int HapGpuDecodeFramesRGBAScaled(HapGpuContext *context, unsigned int frameCount,
+                                          const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
+                                          unsigned int textureCount, void *const *rgbaFrames, unsigned int width,
+                                          unsigned int height, unsigned int scaleLog2, unsigned long rowBytes,
+                                          unsigned int *results, unsigned int flags)
+{
+    unsigned r, f;
+    if (!context)
+        return HapResult_Bad_Arguments;
+    if (scaleLog2 < 1u || scaleLog2 > 2u) {
+        for (f = 0; results && f < frameCount; f++)
+            results[f] = HapResult_Bad_Arguments;
+        return HapResult_Bad_Arguments;
+    }
+    hapgpu_rt_lock(context->rt);
+    r = hapb_decode_rgba(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, rgbaFrames, width, height,
+                         scaleLog2, rowBytes, results, flags);
     hapgpu_rt_unlock(context->rt);
     return r;
 }

@@ -807,6 +807,8 @@ typedef struct picture_road {
     const unsigned *kinds;
     unsigned paired_kinds;      /* bit k: kinds[k] may have an alpha plane (textureCount 2) */
     unsigned picture_kind;      /* HAPGPU_PICTURE_*: the pictures' layout, and with it the size of a texel */
+    unsigned scale_log2;        /* 0: pictures of the frames' size; 1 / 2 (RGBA8 only): half / quarter size, of
+                                   (width >> scale_log2) x (height >> scale_log2), by hapgpu_k_block_decode_scaled */
 } picture_road;
 
 /* RGBA8 pictures (BC7 last: frames of it only with HAPGPU_DECODE_BPTC_PICTURES), RGBA16F ones and A8 ones */
@@ -815,30 +817,45 @@ static const unsigned k_rgba_kinds[4] = {HapTextureFormat_RGB_DXT1, HapTextureFo
 static const unsigned k_half_kinds[2] = {HapTextureFormat_RGB_BPTC_UNSIGNED_FLOAT, HapTextureFormat_RGB_BPTC_SIGNED_FLOAT};
 static const unsigned k_alpha_kinds[1] = {HapTextureFormat_A_RGTC1};
 
-static picture_road road_of(unsigned picture_kind, unsigned flags)
+static picture_road road_of(unsigned picture_kind, unsigned flags, unsigned scale_log2)
 {
     if (picture_kind == HAPGPU_PICTURE_RGBA16F)
-        return (picture_road){2u, k_half_kinds, 0u, picture_kind};
+        return (picture_road){2u, k_half_kinds, 0u, picture_kind, 0u};
     if (picture_kind == HAPGPU_PICTURE_A8)
-        return (picture_road){1u, k_alpha_kinds, 0u, picture_kind};
-    return (picture_road){(flags & HAPGPU_DECODE_BPTC_PICTURES) ? 4u : 3u, k_rgba_kinds, 0x7u, picture_kind};
+        return (picture_road){1u, k_alpha_kinds, 0u, picture_kind, 0u};
+    return (picture_road){(flags & HAPGPU_DECODE_BPTC_PICTURES) ? 4u : 3u, k_rgba_kinds, 0x7u, picture_kind, scale_log2};
 }
 
 /* what the block decoders ask of a picture's address (in device memory) and row pitch when they write it: 16-byte
-   stores for RGBA8 and RGBA16F; A8 pictures take dword stores, and 16-byte ones where address and pitch allow */
-static unsigned picture_align_mask(unsigned kind)
+   stores for RGBA8 and RGBA16F; A8 pictures take dword stores, and 16-byte ones where address and pitch allow; a scaled
+   picture takes the 16 >> scale_log2 bytes a lane has for each of its rows */
+static unsigned picture_align_mask(const picture_road *road)
 {
-    return kind == HAPGPU_PICTURE_A8 ? 3u : 15u;
+    if (road->scale_log2)
+        return (16u >> road->scale_log2) - 1u;
+    return road->picture_kind == HAPGPU_PICTURE_A8 ? 3u : 15u;
+}
+
+/* the block-decode launch of a road: pictures of the frames' size, or scaled ones */
+static int launch_block_decode(hapgpu_rt *rt, const picture_road *road, const HapGpuPictureTable *t, unsigned pictures,
+                               int with_alpha, unsigned width, unsigned height, unsigned format, size_t row_bytes, int wide)
+{
+    if (road->scale_log2)
+        return hapgpu_k_block_decode_scaled(rt, t, pictures, with_alpha, width, height, format, road->scale_log2, row_bytes);
+    return hapgpu_k_block_decode(rt, t, pictures, with_alpha, width, height, format, row_bytes, wide, road->picture_kind);
 }
 
 unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
                               const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                              void *picture, unsigned long row_bytes, unsigned picture_kind)
+                              void *picture, unsigned long row_bytes, unsigned picture_kind, unsigned scale_log2)
 {
-    const picture_road road = road_of(picture_kind, HAPGPU_DECODE_BPTC_PICTURES);
-    const unsigned align = picture_align_mask(picture_kind);
+    const picture_road road = road_of(picture_kind, HAPGPU_DECODE_BPTC_PICTURES, scale_log2);
+    const unsigned align = picture_align_mask(&road);
     hapgpu_rt *rt = ctx->rt;
-    const size_t block = hapf_block_bytes(format), pixel_row = (size_t)width * HAPGPU_PICTURE_TEXEL_BYTES(picture_kind);
+    /* (the picture's geometry: the texture's, or a scaled road's fraction of it) */
+    const unsigned picture_height = height >> road.scale_log2;
+    const size_t block = hapf_block_bytes(format),
+                 pixel_row = (size_t)(width >> road.scale_log2) * HAPGPU_PICTURE_TEXEL_BYTES(picture_kind);
     HapGpuPictureTable t = {{NULL, NULL, NULL}, {0u, 0u, 0u}};
     size_t need, alpha_need, picture_bytes;
     const void *src = texture, *asrc = alpha;
@@ -857,12 +874,13 @@ unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned 
     if (texture_bytes < need || (alpha && alpha_bytes < alpha_need))
         return HapResult_Bad_Arguments;
     /* rows a multiple of 16 bytes; device textures aligned to their blocks, alpha planes to 8 bytes, pictures to 16
-       (A8 pictures: rows and device pictures to 4 bytes, and at most 65535 block rows) */
+       (A8 pictures: rows and device pictures to 4 bytes, and at most 65535 block rows; scaled pictures: rows and device
+       pictures to 8 bytes at half, 4 at quarter size) */
     if ((row_bytes & align) || (is_dev(ctx, texture) && ((uintptr_t)texture & (block - 1u))) ||
         (alpha && is_dev(ctx, alpha) && ((uintptr_t)alpha & 7u)) || (is_dev(ctx, picture) && ((uintptr_t)picture & align)) ||
         (picture_kind == HAPGPU_PICTURE_A8 && height / 4u > 65535u))
         return HapResult_Bad_Arguments;
-    picture_bytes = (size_t)row_bytes * (height - 1u) + pixel_row;
+    picture_bytes = (size_t)row_bytes * (picture_height - 1u) + pixel_row;
     if (!is_dev(ctx, texture)) {
         void *s = hapgpu_rt_device_scratch(rt, D_BC_TEX, need + alpha_need + 256);
         if (!s || hapgpu_rt_h2d(rt, s, texture, need))
@@ -888,8 +906,8 @@ unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned 
     t.one[0] = (uint64_t)(uintptr_t)src;
     t.one[1] = (uint64_t)(uintptr_t)asrc;
     t.one[2] = (uint64_t)(uintptr_t)dst;
-    rc = hapgpu_k_block_decode(rt, &t, 1u, alpha != NULL, width, height, format, row_bytes,
-                               (((uintptr_t)dst | row_bytes) & 15u) == 0 && !ctx->no_wide_planes, picture_kind);
+    rc = launch_block_decode(rt, &road, &t, 1u, alpha != NULL, width, height, format, row_bytes,
+                             (((uintptr_t)dst | row_bytes) & 15u) == 0 && !ctx->no_wide_planes);
     if (rc == 1)
         return HapResult_Bad_Arguments;
     if (rc)
@@ -897,7 +915,7 @@ unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned 
     /* (row by row when the client's rows are longer than the picture's: what lies between them is not ours) */
     if (dst != picture && (row_bytes == pixel_row ? hapgpu_rt_d2h(rt, picture, dst, picture_bytes)
                                                   : hapgpu_rt_d2h_rows(rt, picture, row_bytes, dst, row_bytes, pixel_row,
-                                                                       height)))
+                                                                       picture_height)))
         return HapResult_Internal_Error;
     if (hapgpu_rt_sync(rt))
         return HapResult_Internal_Error;
@@ -1884,8 +1902,10 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
     unsigned long *in_bytes, *caps, *used;
     void **outs;
     unsigned *idx, *fmts, *res;
-    const size_t pixel_row = (size_t)width * HAPGPU_PICTURE_TEXEL_BYTES(road->picture_kind);
-    const unsigned align = picture_align_mask(road->picture_kind);
+    /* (the pictures' geometry: the frames', or a scaled road's fraction of it) */
+    const unsigned picture_height = height >> road->scale_log2;
+    const size_t pixel_row = (size_t)(width >> road->scale_log2) * HAPGPU_PICTURE_TEXEL_BYTES(road->picture_kind);
+    const unsigned align = picture_align_mask(road);
     if (frame_count == 0)
         return HapResult_No_Error;
     if (!results)
@@ -1902,7 +1922,7 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
     blocks = (size_t)(width / 4u) * (height / 4u);
     alpha_off = align_up(blocks * 16u, 256);
     per_frame = alpha_off + (texture_count == 2 ? align_up(blocks * 8u, 256) : 0u);
-    rgba_bytes = (size_t)row_bytes * (height - 1u) + pixel_row;
+    rgba_bytes = (size_t)row_bytes * (picture_height - 1u) + pixel_row;
     slice = RGBA_SLICE_BYTES / per_frame;
     if (slice == 0)
         slice = 1;
@@ -2012,8 +2032,8 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
                     if (present & (1u << k)) {
                         const uint64_t *col = dtab + (size_t)k * 3u * n;
                         const HapGpuPictureTable t = {{col, col + n, col + 2u * (size_t)n}, {0u, 0u, 0u}};
-                        rc |= hapgpu_k_block_decode(rt, &t, n, texture_count == 2, width, height, road->kinds[k], row_bytes,
-                                                    wide, road->picture_kind);
+                        rc |= launch_block_decode(rt, road, &t, n, texture_count == 2, width, height, road->kinds[k], row_bytes,
+                                                  wide);
                     }
                 for (f = 0; f < n; f++)
                     if (results[done + f] == HapResult_No_Error && stage && !is_dev(ctx, rgba_frames[done + f])) {
@@ -2023,7 +2043,7 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
                             rc |= hapgpu_rt_d2h(rt, rgba_frames[done + f], stage + align_up(rgba_bytes, 256) * f, rgba_bytes);
                         else
                             rc |= hapgpu_rt_d2h_rows(rt, rgba_frames[done + f], row_bytes, stage + align_up(rgba_bytes, 256) * f, row_bytes,
-                                                     pixel_row, height);
+                                                     pixel_row, picture_height);
                     }
             }
         }
@@ -2042,9 +2062,10 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
 
 unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
                           const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
-                          unsigned width, unsigned height, unsigned long row_bytes, unsigned *results, unsigned flags)
+                          unsigned width, unsigned height, unsigned scale_log2, unsigned long row_bytes, unsigned *results,
+                          unsigned flags)
 {
-    const picture_road road = road_of(HAPGPU_PICTURE_RGBA8, flags);
+    const picture_road road = road_of(HAPGPU_PICTURE_RGBA8, flags, scale_log2);
     return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, rgba_frames, width, height, row_bytes,
                            results, flags, &road);
 }
@@ -2054,7 +2075,7 @@ unsigned hapb_decode_rgba_half(HapGpuContext *ctx, unsigned frame_count, const v
                                const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,
                                unsigned long row_bytes, unsigned *results, unsigned flags)
 {
-    const picture_road road = road_of(HAPGPU_PICTURE_RGBA16F, flags);
+    const picture_road road = road_of(HAPGPU_PICTURE_RGBA16F, flags, 0u);
     return decode_pictures(ctx, frame_count, inputs, input_bytes, 1u, pictures, width, height, row_bytes, results, flags,
                            &road);
 }
@@ -2064,7 +2085,7 @@ unsigned hapb_decode_alpha(HapGpuContext *ctx, unsigned frame_count, const void 
                            const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,
                            unsigned long row_bytes, unsigned *results, unsigned flags)
 {
-    const picture_road road = road_of(HAPGPU_PICTURE_A8, flags);
+    const picture_road road = road_of(HAPGPU_PICTURE_A8, flags, 0u);
     return decode_pictures(ctx, frame_count, inputs, input_bytes, 1u, pictures, width, height, row_bytes, results, flags,
                            &road);
 }

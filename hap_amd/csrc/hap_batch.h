@@ -95,10 +95,12 @@ unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width
                             unsigned long output_bytes, unsigned long *used, int synchronise, unsigned flags,
                             unsigned picture_kind);
 /* one texture -> one picture of picture_kind: RGBA8 (DXT1, DXT5, YCoCg-DXT5 with an optional RGTC1 alpha plane, BC7),
-   RGBA16F (BC6H unsigned or signed, no alpha plane) or A8 (a lone RGTC1 texture) */
+   RGBA16F (BC6H unsigned or signed, no alpha plane) or A8 (a lone RGTC1 texture).  scale_log2 0: a picture of
+   width x height; 1 or 2 (RGBA8 only): the half- / quarter-size picture of (width >> scale_log2) x (height >> scale_log2),
+   rows and device pictures aligned to 16 >> scale_log2 bytes */
 unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
                               const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                              void *picture, unsigned long row_bytes, unsigned picture_kind);
+                              void *picture, unsigned long row_bytes, unsigned picture_kind, unsigned scale_log2);
 /* pictures -> frames.  picture_kind RGBA8: the DXT / RGTC1 formats (BC7 with HAPGPU_ENCODE_BPTC_BLOCKS); RGBA16F (rows
    and device addresses 16-byte aligned): one BC6H texture; A8 (rows and device addresses 4-byte aligned): one RGTC1
    texture */
@@ -120,10 +122,12 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
                      unsigned *output_formats, unsigned *results, unsigned flags,
                      HapDecodeCallback callback, void *callback_info);
 
-/* frames -> RGBA8 pictures (texture_count 2: Hap Q Alpha frames, colour + RGTC1 alpha plane) */
+/* frames -> RGBA8 pictures (texture_count 2: Hap Q Alpha frames, colour + RGTC1 alpha plane); scale_log2 as for
+   hapb_decompress_rgba (width and height stay the frames') */
 unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
                           const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
-                          unsigned width, unsigned height, unsigned long row_bytes, unsigned *results, unsigned flags);
+                          unsigned width, unsigned height, unsigned scale_log2, unsigned long row_bytes,
+                          unsigned *results, unsigned flags);
 /* Hap HDR frames (one BC6H texture) -> RGBA16F pictures */
 unsigned hapb_decode_rgba_half(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
                                const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,

@@ -321,6 +321,15 @@ int hapgpu_k_block_encode(hapgpu_rt *rt, const HapGpuPictureTable *table, unsign
 int hapgpu_k_block_decode(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, int with_alpha,
                           unsigned width, unsigned height, unsigned hap_texture_format, size_t row_bytes, int wide,
                           unsigned picture_kind);
+/* ... to RGBA8 pictures of (width >> scale_log2) x (height >> scale_log2), scale_log2 1 or 2: every output texel the box
+   mean of the 2^scale_log2 x 2^scale_log2 texels hapgpu_k_block_decode makes there, per channel, halves rounded up
+   ((sum + (1 << (2 * scale_log2 - 1))) >> (2 * scale_log2)).  RGB_DXT1, RGBA_DXT5, YCoCg_DXT5 (with_alpha: the RGTC1
+   plane supplies A) and RGBA_BPTC_UNORM; width and height are the texture's.  Textures and alpha planes aligned as
+   there; pictures and their row_bytes (at least (width >> scale_log2) * 4) to the 16 >> scale_log2 bytes a lane stores
+   per row.  The same table, profile class and return codes. */
+int hapgpu_k_block_decode_scaled(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, int with_alpha,
+                                 unsigned width, unsigned height, unsigned hap_texture_format, unsigned scale_log2,
+                                 size_t row_bytes);
 /* group_tables: HAP_GROUP_TABLE_BYTES bytes per fragment (same indexing as frag_sizes), written for textures whose reserved bit 20 is set */
 int hapgpu_k_snappy_compress(hapgpu_rt *rt, const HapGpuFrameEnc *frames, unsigned frame_count,
                              unsigned max_frags_per_texture, unsigned frag_log2,

@@ -64,6 +64,8 @@ void hapgpu_launch_bc6h_encode(const HapGpuPictureTable &t, unsigned pictures, b
                                unsigned by, size_t row_bytes, hipStream_t stream);    // bc6h_encode.hip
 void hapgpu_launch_bptc_decode(const HapGpuPictureTable &t, unsigned pictures, unsigned bx, unsigned by,
                                size_t row_bytes, hipStream_t stream);                 // bptc_decode.hip
+void hapgpu_launch_bptc_decode_scaled(const HapGpuPictureTable &t, unsigned pictures, unsigned bx, unsigned by,
+                                      size_t row_bytes, unsigned scale_log2, hipStream_t stream);   // bptc_decode.hip
 void hapgpu_launch_bc6h_decode(const HapGpuPictureTable &t, unsigned pictures, bool is_signed, unsigned bx,
                                unsigned by, size_t row_bytes, hipStream_t stream);    // bc6h_decode.hip
 // ... and the A8 pictures of both (RGTC1 only; wide: 16-byte aligned pictures and pitch)

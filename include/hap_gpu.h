@@ -204,6 +204,24 @@ unsigned int HapGpuDecompressRGBA(HapGpuContext *context,
                                   unsigned int width, unsigned int height,
                                   void *rgba, unsigned long rowBytes);
 
+/* The same texture -> the half- (scaleLog2 1) or quarter-size (scaleLog2 2) RGBA8 picture of
+ * (width >> scaleLog2) x (height >> scaleLog2), without the full-size one in between: a thumbnail, a scrub preview, a
+ * monitor output.  Every output texel is the box mean of the 2^scaleLog2 x 2^scaleLog2 texels HapGpuDecompressRGBA
+ * writes there, per channel (R, G, B and A alike, colour not weighted by alpha), halves rounded up:
+ * (sum + (1 << (2 * scaleLog2 - 1))) >> (2 * scaleLog2), exact, on texels that are bit for bit HapGpuDecompressRGBA's.
+ * width and height are the TEXTURE's (multiples of 4, so no output texel spans two blocks); textures, formats and the
+ * alpha plane as for HapGpuDecompressRGBA.  rowBytes at least (width >> scaleLog2) * 4 and, like a device picture's
+ * address, a multiple of the 16 >> scaleLog2 bytes a lane stores per row: 8 at half, 4 at quarter size (the natural
+ * pitch always qualifies).  Host or device pointers; only the picture's bytes of each row are written.  scaleLog2 0 or
+ * above 2 is Bad_Arguments (the full-size call is HapGpuDecompressRGBA, with its own alignment rules).  Out of scope:
+ * RGBA16F pictures (a float mean needs a summation order defined first) and A8 pictures -- BC6H and lone A_RGTC1
+ * textures are Bad_Arguments here as there. */
+unsigned int HapGpuDecompressRGBAScaled(HapGpuContext *context,
+                                        const void *texture, unsigned long textureBytes, unsigned int textureFormat,
+                                        const void *alphaTexture, unsigned long alphaTextureBytes,
+                                        unsigned int width, unsigned int height, unsigned int scaleLog2,
+                                        void *rgba, unsigned long rowBytes);
+
 /* BC6H texture (Hap HDR) -> RGBA16F: four IEEE half bit patterns per texel, 8 bytes, rows rowBytes apart.
  * textureFormat: RGB_BPTC_UNSIGNED_FLOAT or RGB_BPTC_SIGNED_FLOAT (anything else is Bad_Arguments).  RGB is
  * the BPTC definition's result bit for bit (signed textures may give -0, 0x8000, which is kept); alpha is
@@ -446,6 +464,26 @@ unsigned int HapGpuDecodeFramesRGBA(HapGpuContext *context, unsigned int frameCo
                                     unsigned int width, unsigned int height, unsigned long rowBytes,
                                     unsigned int *results,
                                     unsigned int flags);
+
+/* Frames in, half- (scaleLog2 1) or quarter-size (scaleLog2 2) pixels out: HapGpuDecodeFramesRGBA with the pictures of
+ * HapGpuDecompressRGBAScaled -- (width >> scaleLog2) x (height >> scaleLog2) RGBA8, every texel the rounded-up box mean
+ * of the 2^scaleLog2 x 2^scaleLog2 texels HapGpuDecodeFramesRGBA writes there -- made by the block decoder itself: no
+ * full-size picture is written or read back.  width and height are the FRAMES' geometry; rowBytes and device pictures
+ * follow HapGpuDecompressRGBAScaled's rule (multiples of 8 at half, 4 at quarter size; at least
+ * (width >> scaleLog2) * 4); host pictures with longer rows are written row by row.  textureCount, flags
+ * (HAPGPU_DECODE_BPTC_PICTURES included), mixed batches and results[f] are HapGpuDecodeFramesRGBA's: a frame of another
+ * format or geometry is Bad_Arguments alone and its picture untouched, a broken frame gets HapDecode's code.  scaleLog2
+ * 0 or above 2 is Bad_Arguments for the whole call.  Out of scope: RGBA16F (Hap HDR) and A8 (Hap Alpha-Only) pictures,
+ * and ...OnDevices / ...Sequence forms of this call. */
+unsigned int HapGpuDecodeFramesRGBAScaled(HapGpuContext *context, unsigned int frameCount,
+                                          const void *const *inputBuffers,
+                                          const unsigned long *inputBuffersBytes,
+                                          unsigned int textureCount,
+                                          void *const *rgbaFrames,
+                                          unsigned int width, unsigned int height, unsigned int scaleLog2,
+                                          unsigned long rowBytes,
+                                          unsigned int *results,
+                                          unsigned int flags);
 
 /* Hap HDR frames in, RGBA16F pictures out: HapGpuDecodeFramesRGBA for frames of one BC6H texture (unsigned or
  * signed; a batch may mix the two: one block-decode launch per signedness present), pictures as
