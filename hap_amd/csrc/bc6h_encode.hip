@@ -9,37 +9,21 @@
 // mode counts only where its deltas fit after the anchor rule.  Two regions (modes 0x1E, 0x01, 0x00 on the partition
 // of the best masked-sum estimate) run when a block of the wave asks for them: that is a ballot, uniform over the wave.
 //
-// Shape of bptc_encode.hip: one 4x4 block per lane, a wavefront per 64 blocks of a block row, eight 16-byte row loads
+// One 4x4 block per lane as in bptc_encode.hip, a wavefront per 64 blocks of a block row, eight 16-byte row loads
 // per lane (a block row is 32 bytes), one 16-byte store.  Every lane runs one straight-line path.  The working values
 // are kept two to a dword; the header layouts are compile-time run tables (the rows of bc6h_decode.hip's k_modes read
 // the other way), so every field lands with constant shifts.  Per-lane arrays are indexed by unrolled constants only.
+// The weight tables, index packing and the 128-bit block are bptc_encode_core.hpp's, shared with bptc_encode.hip; the
+// fit itself (rdiv, refit, the anchor rule, the partition search) is that file's rule restated for 16-bit values.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hapgpu_runtime.hpp"
-#include "bptc_tables.hpp"
+#include "bptc_encode_core.hpp"
 
 namespace {
+namespace hapbc6h {
 
-#define HD __host__ __device__ __forceinline__
-
-typedef unsigned long long u64;
-
-HD int imin(int a, int b) { return a < b ? a : b; }
-HD int imax(int a, int b) { return a > b ? a : b; }
-HD int iabs(int a) { return a < 0 ? -a : a; }
-HD int bitlen(int v) { return v > 0 ? 32 - __builtin_clz((unsigned)v) : 0; }
-
-// weight of index i in the BPTC table of B bits, from byte-packed constants (i varies per lane)
-template <int B> HD int wgt(int i)
-{
-    const unsigned u = (unsigned)i;
-    unsigned w;
-    if (B == 3)
-        w = (u & 4u) ? 0x40372E25u : 0x1B120900u;
-    else
-        w = (u & 8u) ? ((u & 4u) ? 0x403C3733u : 0x2F2B2622u) : ((u & 4u) ? 0x1E1A1511u : 0x0D090400u);
-    return (int)((w >> (8u * (u & 3u))) & 0xFFu);
-}
+using namespace hapbptc;
 
 // the block's working values: R | G << 16 and B, 16 bits each (two's complement in the signed format)
 struct texels {
@@ -197,8 +181,6 @@ HD void indices(const texels &x, const fitted &f, const int (&d0)[3], const int 
             hi |= idx << (4 * (t - 8));
     }
 }
-
-HD unsigned idx_of(unsigned lo, unsigned hi, int t) { return ((t < 8 ? lo : hi) >> (4 * (t & 7))) & 15u; }
 
 // rdiv(n, d) = sign(n) min(top, floor((|n| + floor(d / 2)) / d)), 0 for n < 0 in the unsigned format; 0 < d < 2^32
 template <bool S> HD int rdiv(long long n, long long d)
@@ -379,23 +361,6 @@ static_assert(covers(k_mode03, 5, 65) && covers(k_mode07, 5, 65) && covers(k_mod
 static_assert(covers(k_mode1E, 5, 77) && covers(k_mode01, 2, 77) && covers(k_mode00, 2, 77),
               "a two-region layout leaves a header bit out or writes one twice");
 
-// 128 bits; positions are compile-time constants after unrolling
-struct bits128 {
-    u64 lo = 0, hi = 0;
-    HD void put(u64 v, int pos, int n)
-    {
-        v &= n == 64 ? ~0ull : ((1ull << n) - 1ull);
-        if (pos < 64) {
-            lo |= v << pos;
-            if (pos + n > 64)
-                hi |= v >> (64 - pos);
-        } else {
-            hi |= v << (pos - 64);
-        }
-    }
-    HD uint4 words() const { return make_uint4((unsigned)lo, (unsigned)(lo >> 32), (unsigned)hi, (unsigned)(hi >> 32)); }
-};
-
 // the mode bits and the endpoint fields (as stored: deltas already taken) by the mode's run table
 template <const mode_layout &l> HD void put_header(bits128 &o, const int (&field)[12])
 {
@@ -410,19 +375,6 @@ template <const mode_layout &l> HD void put_header(bits128 &o, const int (&field
             v = __builtin_bitreverse32(v) >> (32 - k.len);
         o.put(v, k.src, k.len);
     }
-}
-
-// the index field: B bits per texel, B - 1 at texel 0 and at texel a1 (a1 = 0: no second anchor)
-template <int B> HD u64 index_field(unsigned lo, unsigned hi, int a1)
-{
-    u64 acc = 0ull;
-    int at = 0;
-#pragma unroll
-    for (int t = 0; t < 16; t++) {
-        acc |= (u64)idx_of(lo, hi, t) << at;
-        at += (t == 0 || t == a1) ? B - 1 : B;
-    }
-    return acc;
 }
 
 HD bool delta_fits(int d, int bits) { return d >= -(1 << (bits - 1)) && d <= (1 << (bits - 1)) - 1; }
@@ -556,15 +508,6 @@ HD void try_two_regions(const texels &x, const fitted &f0, const fitted &f1, uns
     keep_better(best, asked && fits, o, sse<S, 3>(x, r0, m0) + sse<S, 3>(x, r1, m1));
 }
 
-HD bool wave_any(bool v)
-{
-#ifdef __HIP_DEVICE_COMPILE__
-    return __builtin_amdgcn_ballot_w64(v) != 0ull;
-#else
-    return v;
-#endif
-}
-
 // blocks whose best one-region error exceeds this ask for the two-region modes (TWO_REGION_ERROR of the definition)
 constexpr u64 kTwoRegionError = 48ull * 16ull * 16ull;
 
@@ -629,6 +572,7 @@ __global__ __launch_bounds__(64) void bc6h_encode_kernel(HapGpuPictureTable t, s
     *reinterpret_cast<uint4 *>(out + id * 16u) = hapgpu_bc6h_encode_block<S>(p);
 }
 
+} // namespace hapbc6h
 } // namespace
 
 #ifndef HAPGPU_BC6H_ENCODE_HOST_ONLY
@@ -639,8 +583,8 @@ void hapgpu_launch_bc6h_encode(const HapGpuPictureTable &t, unsigned pictures, b
 {
     const dim3 grid((bx + 63u) / 64u, by, pictures), block(64);
     if (is_signed)
-        hipLaunchKernelGGL(bc6h_encode_kernel<true>, grid, block, 0, stream, t, row_bytes, bx);
+        hipLaunchKernelGGL(hapbc6h::bc6h_encode_kernel<true>, grid, block, 0, stream, t, row_bytes, bx);
     else
-        hipLaunchKernelGGL(bc6h_encode_kernel<false>, grid, block, 0, stream, t, row_bytes, bx);
+        hipLaunchKernelGGL(hapbc6h::bc6h_encode_kernel<false>, grid, block, 0, stream, t, row_bytes, bx);
 }
 #endif

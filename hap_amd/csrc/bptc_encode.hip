@@ -11,31 +11,16 @@
 // source allows.  Every lane runs one straight-line path for the candidates it may need; the only branches skip mode 1
 // (no opaque block in the wave) or mode 5 (no block with alpha), and both conditions are ballots, uniform over the wave.
 // Per-lane arrays are indexed by unrolled constants only, so nothing goes to scratch.
+// The weight tables, index packing and the 128-bit block are bptc_encode_core.hpp's, shared with bc6h_encode.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hapgpu_runtime.hpp"
-#include "bptc_tables.hpp"
+#include "bptc_encode_core.hpp"
 
 namespace {
+namespace hapbc7 {
 
-#define HD __host__ __device__ __forceinline__
-
-HD int imin(int a, int b) { return a < b ? a : b; }
-HD int imax(int a, int b) { return a > b ? a : b; }
-
-// weight of index i in the BPTC table of B bits, from byte-packed constants (no memory table: i varies per lane)
-template <int B> HD int wgt(int i)
-{
-    const unsigned u = (unsigned)i;
-    unsigned w;
-    if (B == 2)
-        w = 0x402B1500u;
-    else if (B == 3)
-        w = (u & 4u) ? 0x40372E25u : 0x1B120900u;
-    else
-        w = (u & 8u) ? ((u & 4u) ? 0x403C3733u : 0x2F2B2622u) : ((u & 4u) ? 0x1E1A1511u : 0x0D090400u);
-    return (int)((w >> (8u * (u & 3u))) & 0xFFu);
-}
+using namespace hapbptc;
 
 HD int chan(unsigned px, int c) { return (int)((px >> (8 * c)) & 0xFFu); }
 
@@ -200,8 +185,6 @@ HD void indices(const unsigned (&px)[16], const int (&d0)[NC], const int (&d1)[N
     }
 }
 
-HD unsigned idx_of(unsigned lo, unsigned hi, int t) { return ((t < 8 ? lo : hi) >> (4 * (t & 7))) & 15u; }
-
 // rdiv(n, d) = 0 for n <= 0, else min(255, floor((n + floor(d / 2)) / d)); d > 0, n < 2^42
 HD int rdiv(long long n, long long d)
 {
@@ -297,38 +280,16 @@ HD void anchor_rule(quantised<KIND, NC> &r, unsigned m, int anchor, unsigned &lo
     r.p1 = swap ? p0 : r.p1;
 }
 
-// 128 bits appended least significant bit first; positions are compile-time constants after unrolling
-struct bits128 {
-    unsigned long long lo = 0, hi = 0;
+// bits128 filled from bit 0 upwards
+struct bits_appended : bits128 {
     int pos = 0;
-    HD void put(unsigned long long v, int n)
+    using bits128::put;
+    HD void put(u64 v, int n)
     {
-        v &= n == 64 ? ~0ull : ((1ull << n) - 1ull);
-        if (pos < 64) {
-            lo |= v << pos;
-            if (pos + n > 64)
-                hi |= v >> (64 - pos);
-        } else {
-            hi |= v << (pos - 64);
-        }
+        put(v, pos, n);
         pos += n;
     }
-    HD uint4 words() const { return make_uint4((unsigned)lo, (unsigned)(lo >> 32), (unsigned)hi, (unsigned)(hi >> 32)); }
 };
-
-// the index field: B bits per texel, B - 1 at texel 0 and at texel a1 (a1 = 0: no second anchor)
-template <int B>
-HD unsigned long long index_field(unsigned lo, unsigned hi, int a1)
-{
-    unsigned long long acc = 0ull;
-    int at = 0;
-#pragma unroll
-    for (int t = 0; t < 16; t++) {
-        acc |= (unsigned long long)idx_of(lo, hi, t) << at;
-        at += (t == 0 || t == a1) ? B - 1 : B;
-    }
-    return acc;
-}
 
 template <int C0, int NC, int B>
 HD int sse(const unsigned (&px)[16], const int (&d0)[NC], const int (&d1)[NC], unsigned m, unsigned lo, unsigned hi)
@@ -384,15 +345,6 @@ HD int partition_of_block(const unsigned (&px)[16])
     return best;
 }
 
-HD bool wave_any(bool v)
-{
-#ifdef __HIP_DEVICE_COMPILE__
-    return __builtin_amdgcn_ballot_w64(v) != 0ull;
-#else
-    return v;
-#endif
-}
-
 struct candidate {
     uint4 block;
     int err;
@@ -404,7 +356,7 @@ HD candidate mode6(const unsigned (&px)[16], bool opaque)
     unsigned lo, hi;
     fit<0, 4, 4, 6>(px, 0xFFFFu, opaque, r, lo, hi);
     anchor_rule<6, 4, 4>(r, 0xFFFFu, 0, lo, hi);
-    bits128 o;
+    bits_appended o;
     o.put(1u << 6, 7);
 #pragma unroll
     for (int c = 0; c < 4; c++) {
@@ -436,7 +388,7 @@ HD candidate mode1(const unsigned (&px)[16])
         mh |= ((m1 >> (t + 8)) & 1u) * 15u << (4 * t);
     }
     const unsigned lo = (lo0 & ~ml) | (lo1 & ml), hi = (hi0 & ~mh) | (hi1 & mh);
-    bits128 o;
+    bits_appended o;
     o.put(2u, 2);
     o.put((unsigned)part, 6);
 #pragma unroll
@@ -462,7 +414,7 @@ HD candidate mode5(const unsigned (&px)[16])
     anchor_rule<7, 3, 2>(rc, 0xFFFFu, 0, clo, chi);
     fit<3, 1, 2, 8>(px, 0xFFFFu, false, ra, alo, ahi);
     anchor_rule<8, 1, 2>(ra, 0xFFFFu, 0, alo, ahi);
-    bits128 o;
+    bits_appended o;
     o.put(1u << 5, 6);
     o.put(0u, 2);
 #pragma unroll
@@ -537,6 +489,7 @@ __global__ __launch_bounds__(64) void bptc_encode_kernel(HapGpuPictureTable t, s
     encode_block<WIDE>(rgba, row_bytes, blocks_x, out);
 }
 
+} // namespace hapbc7
 } // namespace
 
 #ifndef HAPGPU_BPTC_ENCODE_HOST_ONLY
@@ -546,8 +499,8 @@ void hapgpu_launch_bptc_encode(const HapGpuPictureTable &t, unsigned pictures, u
 {
     const dim3 grid((bx + 63u) / 64u, by, pictures), block(64);
     if (wide)
-        hipLaunchKernelGGL(bptc_encode_kernel<true>, grid, block, 0, stream, t, row_bytes, bx);
+        hipLaunchKernelGGL(hapbc7::bptc_encode_kernel<true>, grid, block, 0, stream, t, row_bytes, bx);
     else
-        hipLaunchKernelGGL(bptc_encode_kernel<false>, grid, block, 0, stream, t, row_bytes, bx);
+        hipLaunchKernelGGL(hapbc7::bptc_encode_kernel<false>, grid, block, 0, stream, t, row_bytes, bx);
 }
 #endif
