@@ -58,6 +58,9 @@ def _load():
         "HapGpuDecodeFramesAlpha": (u, [vp, u, P(vp), P(ul), P(vp), u, u, ul, P(u), u]),
         "HapGpuDecompressRGBA": (u, [vp, vp, ul, u, vp, ul, u, u, vp, ul]),
         "HapGpuDecompressRGBAScaled": (u, [vp, vp, ul, u, vp, ul, u, u, u, vp, ul]),
+        "HapGpuDecompressRGBARegion": (u, [vp, vp, ul, u, vp, ul, u, u, u, u, u, u, vp, ul]),
+        "HapGpuRegionNeedsBytes": (u, [u, u, u, u, u, u, ul, ul]),
+        "HapGpuSkippedTextureBytes": (ul, [vp]),
         "HapGpuDecompressRGBAHalf": (u, [vp, vp, ul, u, u, u, vp, ul]),
         "HapGpuEncodeFrames": (u, [vp, u, u, P(vp), P(ul), P(u), P(u), P(u), P(vp), P(ul), P(ul), P(u), u]),
         "HapGpuEncodeFramesRGBA": (u, [vp, u, P(vp), u, u, ul, u, P(u), P(u), P(u), P(vp), P(ul), P(ul), P(u), u]),
@@ -71,6 +74,7 @@ def _load():
         "HapGpuDecodeFrameTextures": (u, [vp, u, P(vp), P(ul), u, P(vp), P(ul), P(ul), P(u), P(u), u]),
         "HapGpuDecodeFramesRGBA": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, ul, P(u), u]),
         "HapGpuDecodeFramesRGBAScaled": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, ul, P(u), u]),
+        "HapGpuDecodeFramesRGBARegion": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, u, u, u, ul, P(u), u]),
         "HapGpuDecodeFramesRGBAHalf": (u, [vp, u, P(vp), P(ul), P(vp), u, u, ul, P(u), u]),
         "HapGpuDecodeChunkGroup": (u, [vp, vp, ul, u, u, u, vp, ul, P(ul), P(u)]),
         "HapGpuGetFrameTextureChunkLayout": (u, [vp, ul, u, u, P(ul), P(u)]),

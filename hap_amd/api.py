@@ -140,6 +140,13 @@ def HapGpuGetFrameTextureChunkLayout(frame, index):
     return r, (list(offs[: got.value + 1]) if r == 0 else None)
 
 
+def region_needs_bytes(width, block_bytes, region, first_byte, byte_count):
+    """True if bytes [first_byte, first_byte + byte_count) of a `width`-wide texture of `block_bytes`-byte blocks hold a
+    byte of a block of region = (x, y, w, h) (HapGpuRegionNeedsBytes: needs no GPU)."""
+    x, y, w, h = region
+    return bool(lib.HapGpuRegionNeedsBytes(width, block_bytes, x, y, w, h, first_byte, byte_count))
+
+
 def HapGpuJoinChunkGroups(groupFrames, outputBufferBytes=None):
     """Joins frames holding consecutive chunk groups (host buffers). Returns (result, frame bytes | None)."""
     infos = [_addr_len(f) for f in groupFrames]
@@ -267,6 +274,10 @@ class Context:
         """64 KiB blocks of other encoders' streams decoded by a workgroup each (HapGpuResolvedBlockCount)"""
         return int(lib.HapGpuResolvedBlockCount(self.handle))
 
+    def skipped_texture_bytes(self):
+        """decoded bytes of the pieces this context's region calls left undecoded (HapGpuSkippedTextureBytes)"""
+        return int(lib.HapGpuSkippedTextureBytes(self.handle))
+
     def placement_retries(self):
         """frames encoded a second time because one of their chunks did not shrink (HapGpuPlacementRetryCount)"""
         return int(lib.HapGpuPlacementRetryCount(self.handle))
@@ -368,6 +379,27 @@ class Context:
                                            row_bytes)
         if own:
             return r, (C.string_at(oa, row_bytes * rows) if r == 0 else None)
+        return r, None
+
+    def decompress_rgba_region(self, texture, texture_format, width, height, region, rgba=None, alpha=None,
+                               row_bytes=None):
+        """Texture (+ optional RGTC1 alpha plane) -> the RGBA8 picture of region = (x, y, w, h), a block-aligned rectangle
+        of it: the crop of decompress_rgba's picture (HapGpuDecompressRGBARegion).  Returns (result, bytes | None)."""
+        x, y, w, h = region
+        ta, tn, _k = _addr_len(texture)
+        aa, an, _k2 = _addr_len(alpha) if alpha is not None else (None, 0, None)
+        row_bytes = w * 4 if row_bytes is None else row_bytes
+        own = rgba is None
+        if own:
+            rgba = (C.c_ubyte * (row_bytes * max(h, 1) + 16))()
+            base = C.addressof(rgba)
+            oa = base + (-base) % 16
+        else:
+            oa, _on, _k3 = _addr_len(rgba)
+        r = lib.HapGpuDecompressRGBARegion(self.handle, ta, tn, texture_format, aa, an, width, height, x, y, w, h, oa,
+                                           row_bytes)
+        if own:
+            return r, (C.string_at(oa, row_bytes * h) if r == 0 else None)
         return r, None
 
     def decompress_rgba_half(self, texture, texture_format, width, height, out=None, row_bytes=None):
@@ -584,6 +616,22 @@ class Context:
         shift = scale_log2 if 0 < scale_log2 < 3 else 0
         r = lib.HapGpuDecodeFramesRGBAScaled(self.handle, nf, ptrs, lens, texture_count, optrs, width, height, scale_log2,
                                              row_bytes or (width >> shift) * 4, results, flags)
+        return r, list(results)
+
+    def decode_frames_rgba_region(self, frames, frame_bytes, texture_count, rgba_frames, width, height, region,
+                                  row_bytes=None, flags=0):
+        """Frames -> RGBA8 pictures of region = (x, y, w, h), a block-aligned rectangle of every frame, in one call
+        (HapGpuDecodeFramesRGBARegion); width and height are the frames'.  Returns (result, results[])."""
+        x, y, w, h = region
+        nf = len(frames)
+        if len(rgba_frames) != nf:
+            raise ValueError("one picture per frame")
+        ptrs, infos = self._ptr_array(frames)
+        lens = (C.c_ulong * nf)(*[fb if fb is not None else infos[i][1] for i, fb in enumerate(frame_bytes)])
+        optrs, _oinfos = self._ptr_array(rgba_frames)
+        results = (C.c_uint * nf)()
+        r = lib.HapGpuDecodeFramesRGBARegion(self.handle, nf, ptrs, lens, texture_count, optrs, width, height, x, y, w, h,
+                                             w * 4 if row_bytes is None else row_bytes, results, flags)
         return r, list(results)
 
     def decode_frames_rgba_half(self, frames, frame_bytes, pictures, width, height, row_bytes=None, flags=0):

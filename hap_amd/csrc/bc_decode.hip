@@ -101,16 +101,22 @@ __device__ __forceinline__ void ycocg_pair(const ycocg_offsets &o, unsigned indi
 }
 
 // FMT: 0 DXT1, 1 DXT5, 2 YCoCg-DXT5; HAS_ALPHA: separate RGTC1 plane supplies A (Hap Q Alpha)
-template <int FMT, bool HAS_ALPHA>
+// REGION: the grid covers a rectangle of the texture instead of all of it (hapgpu_k_block_decode_region) -- blocks_x and
+// blocks_total are then the rectangle's, lane (bx, by) of it reads texture (and alpha plane) block first + by *
+// texture_blocks_x + bx, and the picture is the rectangle's size.  Everything else is the same code: the texels cannot
+// differ, and without REGION the two extra arguments are not looked at.
+template <int FMT, bool HAS_ALPHA, bool REGION = false>
 __device__ __forceinline__ void bc_decode_body(const uint8_t *__restrict__ blocks,
                                                const uint8_t *__restrict__ alpha_blocks,
                                                unsigned blocks_x, unsigned blocks_total,
-                                               uint8_t *__restrict__ rgba, size_t row_bytes)
+                                               uint8_t *__restrict__ rgba, size_t row_bytes,
+                                               unsigned first = 0u, unsigned texture_blocks_x = 0u)
 {
-    const unsigned id = blockIdx.x * 256u + threadIdx.x;
-    if (id >= blocks_total)
+    const unsigned lane_id = blockIdx.x * 256u + threadIdx.x;
+    if (lane_id >= blocks_total)
         return;
-    const unsigned by = id / blocks_x, bx = id - by * blocks_x;
+    const unsigned by = lane_id / blocks_x, bx = lane_id - by * blocks_x;
+    const unsigned id = REGION ? first + by * texture_blocks_x + bx : lane_id;
     int a[16];
     uint2 colour, luma_block = make_uint2(0u, 0u);
     if (FMT == 0) {
@@ -360,6 +366,28 @@ void launch(const HapGpuPictureTable &t, unsigned pictures, bool alpha, unsigned
         hipLaunchKernelGGL((bc_decode_kernel<FMT, false>), grid, block, 0, stream, t, bx, total, row_bytes);
 }
 
+// ... and a rectangle of every texture to pictures of the rectangle's size: the same table
+template <int FMT, bool HAS_ALPHA>
+__global__ __launch_bounds__(256) void bc_decode_region_kernel(HapGpuPictureTable t, HapGpuRegionBlocks g, size_t row_bytes)
+{
+    const uint8_t *blocks = (const uint8_t *)picture_address(t, 0);
+    if (!blocks)
+        return;
+    bc_decode_body<FMT, HAS_ALPHA, true>(blocks, (const uint8_t *)picture_address(t, 1), g.region_x, g.region_total,
+                                         (uint8_t *)picture_address(t, 2), row_bytes, g.first, g.blocks_x);
+}
+
+template <int FMT>
+void launch_region(const HapGpuPictureTable &t, unsigned pictures, bool alpha, const HapGpuRegionBlocks &g, size_t row_bytes,
+                   hipStream_t stream)
+{
+    const dim3 grid((g.region_total + 255u) / 256u, 1, pictures), block(256);
+    if (alpha)
+        hipLaunchKernelGGL((bc_decode_region_kernel<FMT, true>), grid, block, 0, stream, t, g, row_bytes);
+    else
+        hipLaunchKernelGGL((bc_decode_region_kernel<FMT, false>), grid, block, 0, stream, t, g, row_bytes);
+}
+
 // ... and at half (S = 1) or quarter (S = 2) size: the same table, pictures of (width >> S) x (height >> S)
 template <int FMT, bool HAS_ALPHA, int S>
 __global__ __launch_bounds__(256) void bc_decode_scaled_kernel(HapGpuPictureTable t, unsigned blocks_x,
@@ -456,6 +484,41 @@ extern "C" int hapgpu_k_block_decode_scaled(hapgpu_rt *rt, const HapGpuPictureTa
     case 0x83F3: launch_scaled<1>(t, pictures, with_alpha != 0, bx, by, row_bytes, scale_log2, stream); break;
     case 0x01: launch_scaled<2>(t, pictures, with_alpha != 0, bx, by, row_bytes, scale_log2, stream); break;
     case 0x8E8C: hapgpu_launch_bptc_decode_scaled(t, pictures, bx, by, row_bytes, scale_log2, stream); break;
+    default: return 1;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : 4;
+}
+
+// hapgpu_abi.h: the rectangle (x, y, region_width, region_height) of every texture to an RGBA8 picture of
+// region_width x region_height: DXT1, DXT5, YCoCg-DXT5 (with_alpha: + RGTC1 plane) here, BC7 in bptc_decode.hip.  The
+// per-block bodies are hapgpu_k_block_decode's; only the block a lane takes differs.  Returns 0 launched, 1 bad arguments,
+// 4 launch failure.
+extern "C" int hapgpu_k_block_decode_region(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures,
+                                            int with_alpha, unsigned width, unsigned height, unsigned format, unsigned x,
+                                            unsigned y, unsigned region_width, unsigned region_height, size_t row_bytes)
+{
+    scoped_timing st(rt, 6);
+    const hipStream_t stream = hapgpu_rt_stream(rt);
+    if (!table || !(table->column[0] || table->one[0]) || !(table->column[2] || table->one[2]) ||
+        (with_alpha && !(table->column[1] || table->one[1])) || pictures == 0 || pictures > 65535u || width == 0 ||
+        height == 0 || ((width | height | x | y | region_width | region_height) & 3u) || region_width == 0 ||
+        region_height == 0 || x > width || region_width > width - x || y > height || region_height > height - y ||
+        row_bytes < (size_t)region_width * 4u || (row_bytes & 15u) ||
+        (unsigned long long)(width / 4u) * (height / 4u) > 0xFFFFFFFFull / 256u * 255u)
+        return 1;
+    const HapGpuPictureTable &t = *table;
+    HapGpuRegionBlocks g;
+    g.blocks_x = width / 4u;
+    g.first = (y / 4u) * g.blocks_x + x / 4u;
+    g.region_x = region_width / 4u;
+    g.region_total = g.region_x * (region_height / 4u);
+    if (with_alpha && format == 0x8E8C)
+        return 1;
+    switch (format) {
+    case 0x83F0: launch_region<0>(t, pictures, with_alpha != 0, g, row_bytes, stream); break;
+    case 0x83F3: launch_region<1>(t, pictures, with_alpha != 0, g, row_bytes, stream); break;
+    case 0x01: launch_region<2>(t, pictures, with_alpha != 0, g, row_bytes, stream); break;
+    case 0x8E8C: hapgpu_launch_bptc_decode_region(t, pictures, g, row_bytes, stream); break;
     default: return 1;
     }
     return hipGetLastError() == hipSuccess ? 0 : 4;

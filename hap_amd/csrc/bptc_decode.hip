@@ -70,14 +70,18 @@ __device__ __forceinline__ unsigned as_u32(pk_u16 v) { return __builtin_bit_cast
 // per output texel (bc_decode.hip's scaled kernels): the decoded texels are summed per channel as they come, still
 // packed as 16-bit pairs (at most 16 x 255 a half), in the block's four quadrants (region 2 * qy + qx) or in one; the
 // rotation's byte order is applied once per output texel.  A lane stores two rows of 8 bytes or one texel.
-template <int S>
+// REGION (S = 0): the grid covers a rectangle of the texture (bc_decode.hip's bc_decode_body): blocks_x and blocks_total
+// are the rectangle's, lane (bx, by) reads texture block first + by * texture_blocks_x + bx.
+template <int S, bool REGION = false>
 __device__ __forceinline__ void bptc_decode_body(const uint8_t *__restrict__ blocks, unsigned blocks_x,
-                                                 unsigned blocks_total, uint8_t *__restrict__ rgba, size_t row_bytes)
+                                                 unsigned blocks_total, uint8_t *__restrict__ rgba, size_t row_bytes,
+                                                 unsigned first = 0u, unsigned texture_blocks_x = 0u)
 {
-    const unsigned id = blockIdx.x * 256u + threadIdx.x;
-    if (id >= blocks_total)
+    const unsigned lane_id = blockIdx.x * 256u + threadIdx.x;
+    if (lane_id >= blocks_total)
         return;
-    const unsigned by = id / blocks_x, bx = id - by * blocks_x;
+    const unsigned by = lane_id / blocks_x, bx = lane_id - by * blocks_x;
+    const unsigned id = REGION ? first + by * texture_blocks_x + bx : lane_id;
     const uint4 q = *reinterpret_cast<const uint4 *>(blocks + (size_t)id * 16u);
 
     // ---- the mode and its descriptor
@@ -218,7 +222,24 @@ __global__ __launch_bounds__(256) void bptc_decode_scaled_kernel(HapGpuPictureTa
     bptc_decode_body<S>(blocks, blocks_x, blocks_total, (uint8_t *)picture_address(t, 2), row_bytes);
 }
 
+// ... and a rectangle of every texture (bc_decode.hip's bc_decode_region_kernel): lane id is block (bx, by) of the rectangle
+__global__ __launch_bounds__(256) void bptc_decode_region_kernel(HapGpuPictureTable t, HapGpuRegionBlocks g, size_t row_bytes)
+{
+    const uint8_t *blocks = (const uint8_t *)picture_address(t, 0);
+    if (!blocks)
+        return;
+    bptc_decode_body<0, true>(blocks, g.region_x, g.region_total, (uint8_t *)picture_address(t, 2), row_bytes, g.first, g.blocks_x);
+}
+
 } // namespace
+
+// RGBA_BPTC_UNORM of hapgpu_k_block_decode_region (bc_decode.hip)
+void hapgpu_launch_bptc_decode_region(const HapGpuPictureTable &t, unsigned pictures, const HapGpuRegionBlocks &g,
+                                      size_t row_bytes, hipStream_t stream)
+{
+    hipLaunchKernelGGL(bptc_decode_region_kernel, dim3((g.region_total + 255u) / 256u, 1, pictures), dim3(256), 0, stream, t, g,
+                       row_bytes);
+}
 
 // RGBA_BPTC_UNORM of hapgpu_k_block_decode (bc_decode.hip)
 void hapgpu_launch_bptc_decode(const HapGpuPictureTable &t, unsigned pictures, unsigned bx, unsigned by,

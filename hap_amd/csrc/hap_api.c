@@ -4,6 +4,7 @@
  * and the context / batch functions of include/hap_gpu.h.  Pure C99.
  */
 #include "hap_batch.h"
+#include "hap_region.h"
 #include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -199,6 +200,24 @@ unsigned long HapGpuResolvedBlockCount(HapGpuContext *context)
     n = hapgpu_rt_resolved_blocks(context->rt);
     hapgpu_rt_unlock(context->rt);
     return n;
+}
+
+unsigned long HapGpuSkippedTextureBytes(HapGpuContext *context)
+{
+    unsigned long n;
+    if (!context)
+        return 0;
+    hapgpu_rt_lock(context->rt);
+    n = (unsigned long)hapgpu_rt_skipped_bytes(context->rt);
+    hapgpu_rt_unlock(context->rt);
+    return n;
+}
+
+unsigned int HapGpuRegionNeedsBytes(unsigned int width, unsigned int blockBytes, unsigned int regionX, unsigned int regionY,
+                                    unsigned int regionWidth, unsigned int regionHeight, unsigned long firstByte,
+                                    unsigned long byteCount)
+{
+    return (unsigned)hap_region_needs_bytes(width, blockBytes, regionX, regionY, regionWidth, regionHeight, firstByte, byteCount);
 }
 
 unsigned long HapGpuPlacementRetryCount(HapGpuContext *context)
@@ -512,7 +531,25 @@ unsigned int HapGpuDecompressRGBA(HapGpuContext *context, const void *texture, u
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
     r = hapb_decompress_rgba(context, texture, textureBytes, textureFormat, alphaTexture, alphaBytes, width, height,
-                             rgba, rowBytes, HAPGPU_PICTURE_RGBA8, 0u);
+                             rgba, rowBytes, HAPGPU_PICTURE_RGBA8, 0u, NULL);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+/* HapGpuDecompressRGBA of a block-aligned rectangle of the texture */
+unsigned int HapGpuDecompressRGBARegion(HapGpuContext *context, const void *texture, unsigned long textureBytes,
+                                        unsigned int textureFormat, const void *alphaTexture,
+                                        unsigned long alphaTextureBytes, unsigned int width, unsigned int height,
+                                        unsigned int regionX, unsigned int regionY, unsigned int regionWidth,
+                                        unsigned int regionHeight, void *rgba, unsigned long rowBytes)
+{
+    const HapGpuRegion region = {width, regionX, regionY, regionWidth, regionHeight};
+    unsigned r;
+    if (!context || !hapb_region_fits(&region, height))
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_decompress_rgba(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width, height,
+                             rgba, rowBytes, HAPGPU_PICTURE_RGBA8, 0u, &region);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -528,7 +565,7 @@ unsigned int HapGpuDecompressRGBAScaled(HapGpuContext *context, const void *text
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
     r = hapb_decompress_rgba(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width, height,
-                             rgba, rowBytes, HAPGPU_PICTURE_RGBA8, scaleLog2);
+                             rgba, rowBytes, HAPGPU_PICTURE_RGBA8, scaleLog2, NULL);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -542,7 +579,7 @@ unsigned int HapGpuDecompressRGBAHalf(HapGpuContext *context, const void *textur
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
     r = hapb_decompress_rgba(context, texture, textureBytes, textureFormat, NULL, 0, width, height, rgbaHalf, rowBytes,
-                             HAPGPU_PICTURE_RGBA16F, 0u);
+                             HAPGPU_PICTURE_RGBA16F, 0u, NULL);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -719,7 +756,7 @@ unsigned int HapGpuDecompressAlpha(HapGpuContext *context, const void *texture, 
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
     r = hapb_decompress_rgba(context, texture, textureBytes, HapTextureFormat_A_RGTC1, NULL, 0, width, height, alpha,
-                             rowBytes, HAPGPU_PICTURE_A8, 0u);
+                             rowBytes, HAPGPU_PICTURE_A8, 0u, NULL);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -903,6 +940,30 @@ unsigned int HapGpuDecodeFramesRGBA(HapGpuContext *context, unsigned int frameCo
     hapgpu_rt_lock(context->rt);
     r = hapb_decode_rgba(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, rgbaFrames, width, height,
                          0u, rowBytes, results, flags);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+/* HapGpuDecodeFramesRGBA of a block-aligned rectangle of every frame; any other rectangle refuses the whole call */
+unsigned int HapGpuDecodeFramesRGBARegion(HapGpuContext *context, unsigned int frameCount,
+                                          const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
+                                          unsigned int textureCount, void *const *rgbaFrames, unsigned int width,
+                                          unsigned int height, unsigned int regionX, unsigned int regionY,
+                                          unsigned int regionWidth, unsigned int regionHeight, unsigned long rowBytes,
+                                          unsigned int *results, unsigned int flags)
+{
+    const HapGpuRegion region = {width, regionX, regionY, regionWidth, regionHeight};
+    unsigned r, f;
+    if (!context)
+        return HapResult_Bad_Arguments;
+    if (!hapb_region_fits(&region, height)) {
+        for (f = 0; results && f < frameCount; f++)
+            results[f] = HapResult_Bad_Arguments;
+        return HapResult_Bad_Arguments;
+    }
+    hapgpu_rt_lock(context->rt);
+    r = hapb_decode_rgba_region(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, rgbaFrames, width, height,
+                                &region, rowBytes, results, flags);
     hapgpu_rt_unlock(context->rt);
     return r;
 }

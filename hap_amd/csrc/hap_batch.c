@@ -13,6 +13,7 @@
  * HapEncode (hap.c:506-604, 355-504) and HapDecode (hap.c:993-1040, 732-930).
  */
 #include "hap_batch.h"
+#include "hap_region.h"
 #include "measurement_guard.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -809,6 +810,8 @@ typedef struct picture_road {
     unsigned picture_kind;      /* HAPGPU_PICTURE_*: the pictures' layout, and with it the size of a texel */
     unsigned scale_log2;        /* 0: pictures of the frames' size; 1 / 2 (RGBA8 only): half / quarter size, of
                                    (width >> scale_log2) x (height >> scale_log2), by hapgpu_k_block_decode_scaled */
+    const HapGpuRegion *region; /* NULL: the whole of every texture; else (RGBA8 only, scale_log2 0) pictures of region->w x
+                                   region->h, that rectangle of every texture, by hapgpu_k_block_decode_region */
 } picture_road;
 
 /* RGBA8 pictures (BC7 last: frames of it only with HAPGPU_DECODE_BPTC_PICTURES), RGBA16F ones and A8 ones */
@@ -817,13 +820,32 @@ static const unsigned k_rgba_kinds[4] = {HapTextureFormat_RGB_DXT1, HapTextureFo
 static const unsigned k_half_kinds[2] = {HapTextureFormat_RGB_BPTC_UNSIGNED_FLOAT, HapTextureFormat_RGB_BPTC_SIGNED_FLOAT};
 static const unsigned k_alpha_kinds[1] = {HapTextureFormat_A_RGTC1};
 
-static picture_road road_of(unsigned picture_kind, unsigned flags, unsigned scale_log2)
+static picture_road road_of(unsigned picture_kind, unsigned flags, unsigned scale_log2, const HapGpuRegion *region)
 {
     if (picture_kind == HAPGPU_PICTURE_RGBA16F)
-        return (picture_road){2u, k_half_kinds, 0u, picture_kind, 0u};
+        return (picture_road){2u, k_half_kinds, 0u, picture_kind, 0u, NULL};
     if (picture_kind == HAPGPU_PICTURE_A8)
-        return (picture_road){1u, k_alpha_kinds, 0u, picture_kind, 0u};
-    return (picture_road){(flags & HAPGPU_DECODE_BPTC_PICTURES) ? 4u : 3u, k_rgba_kinds, 0x7u, picture_kind, scale_log2};
+        return (picture_road){1u, k_alpha_kinds, 0u, picture_kind, 0u, NULL};
+    return (picture_road){(flags & HAPGPU_DECODE_BPTC_PICTURES) ? 4u : 3u, k_rgba_kinds, 0x7u, picture_kind,
+                          region ? 0u : scale_log2, region};
+}
+
+/* the geometry of a road's pictures, from the textures' */
+static unsigned picture_width_of(const picture_road *road, unsigned width)
+{
+    return road->region ? road->region->w : width >> road->scale_log2;
+}
+
+static unsigned picture_height_of(const picture_road *road, unsigned height)
+{
+    return road->region ? road->region->h : height >> road->scale_log2;
+}
+
+/* 1: the region is a block-aligned rectangle inside width x height (hap_region.h's rules and the texture's height) */
+int hapb_region_fits(const HapGpuRegion *region, unsigned height)
+{
+    return hap_region_geometry_valid(region->width, region->x, region->y, region->w, region->h) && region->y <= height &&
+           region->h <= height - region->y;
 }
 
 /* what the block decoders ask of a picture's address (in device memory) and row pitch when they write it: 16-byte
@@ -836,10 +858,13 @@ static unsigned picture_align_mask(const picture_road *road)
     return road->picture_kind == HAPGPU_PICTURE_A8 ? 3u : 15u;
 }
 
-/* the block-decode launch of a road: pictures of the frames' size, or scaled ones */
+/* the block-decode launch of a road: pictures of the frames' size, scaled ones, or a rectangle's */
 static int launch_block_decode(hapgpu_rt *rt, const picture_road *road, const HapGpuPictureTable *t, unsigned pictures,
                                int with_alpha, unsigned width, unsigned height, unsigned format, size_t row_bytes, int wide)
 {
+    if (road->region)
+        return hapgpu_k_block_decode_region(rt, t, pictures, with_alpha, width, height, format, road->region->x, road->region->y,
+                                            road->region->w, road->region->h, row_bytes);
     if (road->scale_log2)
         return hapgpu_k_block_decode_scaled(rt, t, pictures, with_alpha, width, height, format, road->scale_log2, row_bytes);
     return hapgpu_k_block_decode(rt, t, pictures, with_alpha, width, height, format, row_bytes, wide, road->picture_kind);
@@ -847,15 +872,16 @@ static int launch_block_decode(hapgpu_rt *rt, const picture_road *road, const Ha
 
 unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
                               const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                              void *picture, unsigned long row_bytes, unsigned picture_kind, unsigned scale_log2)
+                              void *picture, unsigned long row_bytes, unsigned picture_kind, unsigned scale_log2,
+                              const HapGpuRegion *region)
 {
-    const picture_road road = road_of(picture_kind, HAPGPU_DECODE_BPTC_PICTURES, scale_log2);
+    const picture_road road = road_of(picture_kind, HAPGPU_DECODE_BPTC_PICTURES, scale_log2, region);
     const unsigned align = picture_align_mask(&road);
     hapgpu_rt *rt = ctx->rt;
-    /* (the picture's geometry: the texture's, or a scaled road's fraction of it) */
-    const unsigned picture_height = height >> road.scale_log2;
+    /* (the picture's geometry: the texture's, a scaled road's fraction of it, or the rectangle's) */
+    const unsigned picture_height = picture_height_of(&road, height);
     const size_t block = hapf_block_bytes(format),
-                 pixel_row = (size_t)(width >> road.scale_log2) * HAPGPU_PICTURE_TEXEL_BYTES(picture_kind);
+                 pixel_row = (size_t)picture_width_of(&road, width) * HAPGPU_PICTURE_TEXEL_BYTES(picture_kind);
     HapGpuPictureTable t = {{NULL, NULL, NULL}, {0u, 0u, 0u}};
     size_t need, alpha_need, picture_bytes;
     const void *src = texture, *asrc = alpha;
@@ -867,6 +893,7 @@ unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned 
     for (k = 0; k < road.kind_count && road.kinds[k] != format; k++)
         ;
     if (!texture || !picture || width == 0 || height == 0 || (width & 3u) || (height & 3u) || row_bytes < pixel_row ||
+        (road.region && (road.region->width != width || !hapb_region_fits(road.region, height))) ||
         k == road.kind_count || (alpha && !(road.paired_kinds >> k & 1u)))
         return HapResult_Bad_Arguments;
     need = (size_t)(width / 4u) * (height / 4u) * block;
@@ -1178,6 +1205,11 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
     unsigned far_seen = 0;
     /* (a call for several textures of the same frames: HapGpuDecodeFrameTextures hands the per-entry indices over) */
     const unsigned *const entry_index = ctx->decode_indices;
+    /* (a region call: the rectangle the textures are wanted for -- units that hold none of its blocks are blanked on the
+       device, hapgpu_k_skip_units; a texture's block size is its format's, known once the frame is planned) */
+    const HapGpuRegion *const region = ctx->decode_region;
+    const int region_counted = !ctx->decode_region_uncounted;
+    uint32_t *hblock = NULL, *dblock = NULL;                   /* per job, behind the job tables: the texture's block size */
 #define TEXTURE_INDEX(f) (entry_index ? entry_index[f] : index)
     const int block_scan = !(flags & HAPGPU_DECODE_NO_BLOCK_SCAN) && !ctx->no_block_scan;
     uint8_t *prefix = NULL, *in_stage = NULL, *out_stage = NULL;
@@ -1201,6 +1233,8 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
     double hapb_t0 = hapb_now_us();
 #endif
     ctx->decode_indices = NULL;
+    ctx->decode_region = NULL;
+    ctx->decode_region_uncounted = 0;
     if (frame_count == 0)
         return HapResult_No_Error;
     if (!results)
@@ -1565,9 +1599,9 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
     use_scan_guess = fine_total && !(flags & HAPGPU_DECODE_NO_FIELD_GUESS);
 
     /* 3. device descriptors */
-    hjobs = (HapGpuDecodeJob *)hapgpu_rt_pinned_scratch(rt, P_JOBS, sizeof(HapGpuDecodeJob) * live);
+    hjobs = (HapGpuDecodeJob *)hapgpu_rt_pinned_scratch(rt, P_JOBS, (sizeof(HapGpuDecodeJob) + sizeof(uint32_t)) * live);
     hchunks = (HapGpuChunkIn *)hapgpu_rt_pinned_scratch(rt, P_CHUNKS, sizeof(HapGpuChunkIn) * (total_chunks + 1u));
-    djobs = (HapGpuDecodeJob *)hapgpu_rt_device_scratch(rt, D_JOBS, sizeof(HapGpuDecodeJob) * live);
+    djobs = (HapGpuDecodeJob *)hapgpu_rt_device_scratch(rt, D_JOBS, (sizeof(HapGpuDecodeJob) + sizeof(uint32_t)) * live);
     dchunks = (HapGpuChunkIn *)hapgpu_rt_device_scratch(rt, D_CHUNKS, sizeof(HapGpuChunkIn) * (total_chunks + 1u));
     /* (the fine block units of the block scan live behind the ordinary ones: [total_units, total_units + fine_total)) */
     dunits = (HapGpuDecodeUnit *)hapgpu_rt_device_scratch(rt, D_UNITS, sizeof(HapGpuDecodeUnit) * ((size_t)total_units + fine_total + 1u));
@@ -1580,6 +1614,8 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
         rc = 1;
         goto fail_alloc;
     }
+    hblock = (uint32_t *)(hjobs + live);
+    dblock = (uint32_t *)(djobs + live);
     if (scan_chunks) {
         /* one arena: chunk table | segment summaries | block positions | fine work list | joins | window records */
         const size_t o_segs = align_up(sizeof(HapGpuScanChunk) * scan_chunks, 64);
@@ -1649,6 +1685,7 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
             job->unit_count = units;
             job->units = (uint64_t)(uintptr_t)(dunits + unit_cursor);
             job->status = HapResult_Internal_Error;
+            hblock[job_of_frame[f]] = region ? (uint32_t)hapf_block_bytes(p->format) : 0u;
             if (p->mode == HAPGPU_JOB_COMPLEX) {
                 job->payload = (uint64_t)(uintptr_t)(frame_dev + p->payload_offset);
                 job->payload_len = p->payload_length;
@@ -1708,10 +1745,14 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
             unit_cursor += units;
         }
         HAPB_MARK("host plan");
-        rc |= hapgpu_rt_h2d(rt, djobs, hjobs, sizeof(HapGpuDecodeJob) * live);
+        rc |= hapgpu_rt_h2d(rt, djobs, hjobs, (sizeof(HapGpuDecodeJob) + (region ? sizeof(uint32_t) : 0u)) * live);
         if (total_chunks)
             rc |= hapgpu_rt_h2d(rt, dchunks, hchunks, sizeof(HapGpuChunkIn) * total_chunks);
         rc |= hapgpu_k_decode_plan(rt, djobs, live, dunits, total_units, frag_log2_seen ? max_chunks : 0u);
+        /* a region call: the chunks, table fragments and raw pieces that hold none of the rectangle's blocks go here --
+           in front of the block scan, so that a chunk nobody needs is not scanned either (the scan looks at STREAM units) */
+        if (region)
+            rc |= hapgpu_k_skip_units(rt, dunits, total_units, djobs, dblock, region, region_counted);
 
         /* hap.h callback contract (single-frame HapDecode only): the client is asked to "run" the
            chunks once planning succeeded and there is more than one (reference hap.c:852-862) */
@@ -1780,10 +1821,14 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
             rc |= hapgpu_rt_zero(rt, dwork, sizeof(uint32_t));
             if (fine_total)
                 rc |= hapgpu_rt_zero(rt, dwork + 1u + fine_total, sizeof(uint32_t));
-            if (frag_kinds & 0x1000u)       /* (the decoder below walks all the pieces' slots, not only the listed ones) */
+            if ((frag_kinds & 0x1000u) || (region && fine_total))       /* (the decoder below walks all the pieces' slots, not only the listed ones) */
                 rc |= hapgpu_rt_zero(rt, dunits + total_units, sizeof(HapGpuDecodeUnit) * (size_t)fine_total);
             rc |= hapgpu_k_scan_blocks(rt, dunits, djobs, dscan, scan_chunks, dsegs, drecs, djoins, scan_segs,
                                        fine_total ? dwork : NULL, total_units, fine_total);
+            /* ... and the 64 KiB and 8 KiB blocks the scan found: in front of the table maker below, which makes no
+               table for a piece that is blanked */
+            if (region)
+                rc |= hapgpu_k_skip_units(rt, dunits, total_units + fine_total, djobs, dblock, region, region_counted);
         }
         if (dguess && use_guess)
             rc |= hapgpu_k_guess_group_tables(rt, dunits, total_units, djobs, NULL, 0u, NULL);
@@ -1847,6 +1892,10 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
                 ctx->preset_marks = client_marks;
                 ctx->preset_count = client_marks_count;
             }
+            /* (a region call skips again on this road: whole chunks and raw pieces, all it has without table and scan --
+               no more than the first pass skipped of this frame, and counted there) */
+            ctx->decode_region = region;
+            ctx->decode_region_uncounted = 1;
             hapb_decode(ctx, 1, &inputs[f], &input_bytes[f], TEXTURE_INDEX(f), &outputs[f], &output_bytes[f],
                         output_used ? &output_used[f] : NULL, output_formats ? &output_formats[f] : NULL,
                         &results[f], (flags | HAPGPU_DECODE_IGNORE_FRAGMENT_INDEX | HAPGPU_DECODE_NO_BLOCK_SCAN | HAPGPU_DECODE_NO_FIELD_GUESS) &
@@ -1902,9 +1951,13 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
     unsigned long *in_bytes, *caps, *used;
     void **outs;
     unsigned *idx, *fmts, *res;
-    /* (the pictures' geometry: the frames', or a scaled road's fraction of it) */
-    const unsigned picture_height = height >> road->scale_log2;
-    const size_t pixel_row = (size_t)(width >> road->scale_log2) * HAPGPU_PICTURE_TEXEL_BYTES(road->picture_kind);
+    /* (the pictures' geometry: the frames', a scaled road's fraction of it, or the rectangle's) */
+    const unsigned picture_height = picture_height_of(road, height);
+    const size_t pixel_row = (size_t)picture_width_of(road, width) * HAPGPU_PICTURE_TEXEL_BYTES(road->picture_kind);
+    /* (a rectangle that is the whole frame skips nothing) */
+    const HapGpuRegion *const skip_region = road->region && !(road->region->x == 0u && road->region->y == 0u &&
+                                                              road->region->w == width && road->region->h == height)
+                                                ? road->region : NULL;
     const unsigned align = picture_align_mask(road);
     if (frame_count == 0)
         return HapResult_No_Error;
@@ -1914,6 +1967,7 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
         return HapResult_Internal_Error;
     if (!inputs || !input_bytes || !rgba_frames || texture_count == 0 || texture_count > 2 || width == 0 ||
         height == 0 || (width & 3u) || (height & 3u) || row_bytes < pixel_row || (row_bytes & align) ||
+        (road->region && (road->region->width != width || !hapb_region_fits(road->region, height))) ||
         (road->picture_kind == HAPGPU_PICTURE_A8 && height / 4u > 65535u)) {
         for (f = 0; f < frame_count; f++)
             results[f] = HapResult_Bad_Arguments;
@@ -1968,6 +2022,7 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
                 fmts[e] = 0;
             }
         ctx->decode_indices = idx;
+        ctx->decode_region = skip_region;
         hapb_decode(ctx, n * texture_count, in, in_bytes, 0, outs, caps, used, fmts, res, flags & ~HAPGPU_DECODE_BPTC_PICTURES,
                     NULL, NULL);
         {
@@ -2065,7 +2120,19 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                           unsigned width, unsigned height, unsigned scale_log2, unsigned long row_bytes, unsigned *results,
                           unsigned flags)
 {
-    const picture_road road = road_of(HAPGPU_PICTURE_RGBA8, flags, scale_log2);
+    const picture_road road = road_of(HAPGPU_PICTURE_RGBA8, flags, scale_log2, NULL);
+    return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, rgba_frames, width, height, row_bytes,
+                           results, flags, &road);
+}
+
+/* ... and a rectangle of every frame to pictures of the rectangle's size: the same road with the region block decoder,
+   and a second stage that leaves out what holds none of the rectangle's blocks */
+unsigned hapb_decode_rgba_region(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                                 const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
+                                 unsigned width, unsigned height, const HapGpuRegion *region, unsigned long row_bytes,
+                                 unsigned *results, unsigned flags)
+{
+    const picture_road road = road_of(HAPGPU_PICTURE_RGBA8, flags, 0u, region);
     return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, rgba_frames, width, height, row_bytes,
                            results, flags, &road);
 }
@@ -2075,7 +2142,7 @@ unsigned hapb_decode_rgba_half(HapGpuContext *ctx, unsigned frame_count, const v
                                const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,
                                unsigned long row_bytes, unsigned *results, unsigned flags)
 {
-    const picture_road road = road_of(HAPGPU_PICTURE_RGBA16F, flags, 0u);
+    const picture_road road = road_of(HAPGPU_PICTURE_RGBA16F, flags, 0u, NULL);
     return decode_pictures(ctx, frame_count, inputs, input_bytes, 1u, pictures, width, height, row_bytes, results, flags,
                            &road);
 }
@@ -2085,7 +2152,7 @@ unsigned hapb_decode_alpha(HapGpuContext *ctx, unsigned frame_count, const void 
                            const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,
                            unsigned long row_bytes, unsigned *results, unsigned flags)
 {
-    const picture_road road = road_of(HAPGPU_PICTURE_A8, flags, 0u);
+    const picture_road road = road_of(HAPGPU_PICTURE_A8, flags, 0u, NULL);
     return decode_pictures(ctx, frame_count, inputs, input_bytes, 1u, pictures, width, height, row_bytes, results, flags,
                            &road);
 }

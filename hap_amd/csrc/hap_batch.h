@@ -42,6 +42,11 @@ struct HapGpuContext {
     const struct HapbBlockEncodeJob *block_encode_job;
     /* texture index of every entry of the next hapb_decode call (NULL: its `index` argument for all) */
     const unsigned *decode_indices;
+    /* the rectangle the next hapb_decode call's textures are wanted for (NULL: all of them): units that hold none of
+       its blocks stay undecoded.  Per call, like decode_indices. */
+    const HapGpuRegion *decode_region;
+    int decode_region_uncounted;     /* ... and 1 where that call is a frame's second pass, whose first pass has counted
+                                        what it skipped (HapGpuSkippedTextureBytes counts a frame once) */
     /* HapGpuEncodeFramesRGBABegin / HapGpuEncodeFramesFinish: the launched half of an encode call whose results have
        not been asked for yet; while there is one the context takes no other call */
     unsigned defer_encode;
@@ -97,10 +102,14 @@ unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width
 /* one texture -> one picture of picture_kind: RGBA8 (DXT1, DXT5, YCoCg-DXT5 with an optional RGTC1 alpha plane, BC7),
    RGBA16F (BC6H unsigned or signed, no alpha plane) or A8 (a lone RGTC1 texture).  scale_log2 0: a picture of
    width x height; 1 or 2 (RGBA8 only): the half- / quarter-size picture of (width >> scale_log2) x (height >> scale_log2),
-   rows and device pictures aligned to 16 >> scale_log2 bytes */
+   rows and device pictures aligned to 16 >> scale_log2 bytes.  region != NULL (RGBA8 only, scale_log2 0; region->width
+   == width): the picture is that rectangle of the texture, region->w x region->h, and only its blocks are read */
 unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
                               const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                              void *picture, unsigned long row_bytes, unsigned picture_kind, unsigned scale_log2);
+                              void *picture, unsigned long row_bytes, unsigned picture_kind, unsigned scale_log2,
+                              const HapGpuRegion *region);
+/* 1: region is a block-aligned, non-empty rectangle inside region->width x height */
+int hapb_region_fits(const HapGpuRegion *region, unsigned height);
 /* pictures -> frames.  picture_kind RGBA8: the DXT / RGTC1 formats (BC7 with HAPGPU_ENCODE_BPTC_BLOCKS); RGBA16F (rows
    and device addresses 16-byte aligned): one BC6H texture; A8 (rows and device addresses 4-byte aligned): one RGTC1
    texture */
@@ -128,6 +137,11 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                           const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
                           unsigned width, unsigned height, unsigned scale_log2, unsigned long row_bytes,
                           unsigned *results, unsigned flags);
+/* ... a rectangle of every frame (region->width == width) to RGBA8 pictures of region->w x region->h */
+unsigned hapb_decode_rgba_region(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                                 const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
+                                 unsigned width, unsigned height, const HapGpuRegion *region, unsigned long row_bytes,
+                                 unsigned *results, unsigned flags);
 /* Hap HDR frames (one BC6H texture) -> RGBA16F pictures */
 unsigned hapb_decode_rgba_half(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
                                const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,

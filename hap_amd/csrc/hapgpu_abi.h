@@ -250,6 +250,11 @@ typedef struct HapGpuDecodeUnit {
     uint64_t reserved;
 } HapGpuDecodeUnit;
 
+/* [device] the rectangle a region call wants of every texture, in texels of a `width`-wide texture (hap_region.h) */
+typedef struct HapGpuRegion {
+    uint32_t width, x, y, w, h;
+} HapGpuRegion;
+
 /* ------------------------------------------------------------------ */
 /* runtime (hapgpu_runtime.hip) + launchers (each in its kernels' file) */
 /* ------------------------------------------------------------------ */
@@ -330,6 +335,15 @@ int hapgpu_k_block_decode(hapgpu_rt *rt, const HapGpuPictureTable *table, unsign
 int hapgpu_k_block_decode_scaled(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, int with_alpha,
                                  unsigned width, unsigned height, unsigned hap_texture_format, unsigned scale_log2,
                                  size_t row_bytes);
+/* ... the rectangle (x, y, region_width, region_height; multiples of 4 inside width x height) of every texture to an RGBA8
+   picture of region_width x region_height, byte for byte the crop of what hapgpu_k_block_decode writes: lane id is block
+   (id % (region_width / 4), id / (region_width / 4)) of the rectangle and reads texture (and alpha plane) block
+   (id / (region_width / 4) + y / 4) * (width / 4) + id % (region_width / 4) + x / 4 -- no block outside the rectangle is
+   read.  RGB_DXT1, RGBA_DXT5, YCoCg_DXT5 (with_alpha) and RGBA_BPTC_UNORM.  Pictures and row_bytes (at least
+   region_width * 4) 16-byte aligned.  The same table, profile class and return codes. */
+int hapgpu_k_block_decode_region(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, int with_alpha,
+                                 unsigned width, unsigned height, unsigned hap_texture_format, unsigned x, unsigned y,
+                                 unsigned region_width, unsigned region_height, size_t row_bytes);
 /* group_tables: HAP_GROUP_TABLE_BYTES bytes per fragment (same indexing as frag_sizes), written for textures whose reserved bit 20 is set */
 int hapgpu_k_snappy_compress(hapgpu_rt *rt, const HapGpuFrameEnc *frames, unsigned frame_count,
                              unsigned max_frags_per_texture, unsigned frag_log2,
@@ -356,6 +370,18 @@ int hapgpu_k_gather_prefixes_far(hapgpu_rt *rt, const uint64_t *frames_dev, cons
 /* clears `units` (all SKIP) then plans every job; max_chunks: largest chunk_count among the jobs */
 int hapgpu_k_decode_plan(hapgpu_rt *rt, HapGpuDecodeJob *jobs, unsigned job_count,
                          HapGpuDecodeUnit *units, unsigned unit_count, unsigned max_chunks);
+/* A region call: every unit of units[0 .. unit_count) that holds no byte of a block of `region` -- its place in its
+   texture: dst - the job's dst, dst_len; the texture's block size: job_block_bytes[unit.job] (device; 0: leave the job's
+   units alone) -- becomes HAPGPU_UNIT_SKIP, and with `count` its dst_len is added to the runtime's skipped-bytes counter
+   (hapgpu_rt_skipped_bytes; count 0: a frame's second pass, which the first has counted).  Of a scanned stream's 64 KiB and
+   8 KiB blocks, both blanked, the set the decoder is about to run is counted; a stream whose 8 KiB pieces fail later and
+   fall back stays counted by those.  To be run when the unit list is final: after hapgpu_k_decode_plan and, where it adds
+   units, after hapgpu_k_scan_blocks (running it in front of the scan as well keeps chunks nobody needs from being
+   scanned; in front of hapgpu_k_guess_group_tables, no table is made for a blanked piece). */
+int hapgpu_k_skip_units(hapgpu_rt *rt, HapGpuDecodeUnit *units, unsigned unit_count, const HapGpuDecodeJob *jobs,
+                        const uint32_t *job_block_bytes, const HapGpuRegion *region, int count);
+/* decoded bytes of the units hapgpu_k_skip_units blanked since the runtime was made (waits for the stream) */
+unsigned long long hapgpu_rt_skipped_bytes(hapgpu_rt *rt);
 /* splits whole-stream units that consist of independent 64 KiB blocks (what libsnappy writes) into BLOCK units,
  * using the slots reserved behind them; streams that do not qualify stay as they are.  chunks: one entry per stream
  * (host-filled part copied to the device by the caller); segs / recs / joins: device scratch of seg_total entries /

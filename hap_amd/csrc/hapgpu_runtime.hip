@@ -41,6 +41,7 @@ struct hapgpu_rt {
     int recording;
     hapgpu_launch_settings settings;
     uint32_t *resolved_blocks;               // device counter: 64 KiB blocks a workgroup decoded
+    unsigned long long *skipped_bytes;       // device counter: decoded bytes of the units the region calls blanked
 };
 
 #define HIP_OK(expr) ((expr) == hipSuccess)
@@ -101,6 +102,10 @@ extern "C" int hapgpu_rt_create(int device, hapgpu_rt **out)
         (void)hipGetLastError();
         rt->resolved_blocks = nullptr;       // (a statistic: the decoder runs without it)
     }
+    if (hipMalloc((void **)&rt->skipped_bytes, sizeof(unsigned long long)) != hipSuccess || hipMemset(rt->skipped_bytes, 0, sizeof(unsigned long long)) != hipSuccess) {
+        (void)hipGetLastError();
+        rt->skipped_bytes = nullptr;         // (a statistic as well: the region calls skip without counting)
+    }
     {
         hapgpu_launch_settings &s = rt->settings;
         int cus = 0;
@@ -136,6 +141,8 @@ extern "C" void hapgpu_rt_destroy(hapgpu_rt *rt)
         (void)hipGraphExecDestroy(g.exec);
     if (rt->resolved_blocks)
         (void)hipFree(rt->resolved_blocks);
+    if (rt->skipped_bytes)
+        (void)hipFree(rt->skipped_bytes);
     (void)hipEventDestroy(rt->t0);
     (void)hipEventDestroy(rt->t1);
     (void)hipStreamDestroy(rt->stream);
@@ -446,6 +453,7 @@ scoped_timing::~scoped_timing()
 hipStream_t hapgpu_rt_stream(hapgpu_rt *rt) { return rt->stream; }
 hapgpu_launch_settings *hapgpu_rt_settings(hapgpu_rt *rt) { return &rt->settings; }
 uint32_t *hapgpu_rt_resolved_counter(hapgpu_rt *rt) { return rt->resolved_blocks; }
+unsigned long long *hapgpu_rt_skipped_counter(hapgpu_rt *rt) { return rt->skipped_bytes; }
 
 extern "C" void hapgpu_rt_set_profiling(hapgpu_rt *rt, int enable) { rt->profiling = enable; }
 
@@ -591,5 +599,17 @@ extern "C" unsigned hapgpu_rt_resolved_blocks(hapgpu_rt *rt)
         }
     }
 #endif
+    return v;
+}
+
+// decoded bytes of the units hapgpu_k_skip_units blanked since the runtime was made; waits for the stream
+extern "C" unsigned long long hapgpu_rt_skipped_bytes(hapgpu_rt *rt)
+{
+    unsigned long long v = 0;
+    if (!rt->skipped_bytes)
+        return 0;
+    if (hipStreamSynchronize(rt->stream) != hipSuccess ||
+        hipMemcpy(&v, rt->skipped_bytes, sizeof v, hipMemcpyDeviceToHost) != hipSuccess)
+        return 0;
     return v;
 }

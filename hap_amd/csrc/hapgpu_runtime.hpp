@@ -25,6 +25,7 @@ struct hapgpu_launch_settings {
 hipStream_t hapgpu_rt_stream(hapgpu_rt *rt);
 hapgpu_launch_settings *hapgpu_rt_settings(hapgpu_rt *rt);
 uint32_t *hapgpu_rt_resolved_counter(hapgpu_rt *rt);     // device counter of hapgpu_rt_resolved_blocks, or null
+unsigned long long *hapgpu_rt_skipped_counter(hapgpu_rt *rt);   // device counter of hapgpu_rt_skipped_bytes, or null
 
 struct timed_launch {
     int cls;
@@ -68,6 +69,17 @@ void hapgpu_launch_bptc_decode_scaled(const HapGpuPictureTable &t, unsigned pict
                                       size_t row_bytes, unsigned scale_log2, hipStream_t stream);   // bptc_decode.hip
 void hapgpu_launch_bc6h_decode(const HapGpuPictureTable &t, unsigned pictures, bool is_signed, unsigned bx,
                                unsigned by, size_t row_bytes, hipStream_t stream);    // bc6h_decode.hip
+// A rectangle of a texture in blocks, for the kernels of hapgpu_k_block_decode_region: the grid is region_total lanes,
+// lane id block (id % region_x, id / region_x) of the rectangle -- texture block first + (id / region_x) * blocks_x +
+// id % region_x
+struct HapGpuRegionBlocks {
+    unsigned blocks_x;        // blocks in a row of the texture
+    unsigned first;           // the texture block of the rectangle's upper left corner
+    unsigned region_x;        // blocks in a row of the rectangle
+    unsigned region_total;    // blocks of the rectangle
+};
+void hapgpu_launch_bptc_decode_region(const HapGpuPictureTable &t, unsigned pictures, const HapGpuRegionBlocks &g,
+                                      size_t row_bytes, hipStream_t stream);          // bptc_decode.hip
 // ... and the A8 pictures of both (RGTC1 only; wide: 16-byte aligned pictures and pitch)
 void hapgpu_launch_alpha_encode(const HapGpuPictureTable &t, unsigned pictures, unsigned bx, unsigned by,
                                 size_t row_bytes, bool wide, hipStream_t stream);     // alpha_plane.hip

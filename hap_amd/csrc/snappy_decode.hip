@@ -34,6 +34,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "hapgpu_runtime.hpp"
+#include "hap_region.h"
 #include "measurement_guard.h"
 
 namespace {
@@ -291,6 +292,73 @@ __global__ __launch_bounds__(64) void decode_expand_kernel(HapGpuDecodeJob *jobs
 }
 
 // ------------------------------------------------------------------------------------------
+// which units of a scanned stream run
+// ------------------------------------------------------------------------------------------
+
+// A stream the block scan looked at has up to three sets of units: the stream unit, BLOCK units for its 64 KiB blocks and
+// BLOCK units for its 8 KiB pieces.  One set runs, and this is the one place that says which -- the decoder asks it, and
+// so does the kernel that counts what a region call skips.
+
+// every 8 KiB mark of the stream was found (a table-less stream of this library: its fragments)
+__device__ __forceinline__ bool scan_fine_found(const HapGpuScanChunk *scan)
+{
+    return scan->expected_fine != 0u && scan->found_fine == scan->expected_fine;
+}
+
+// 2: the 8 KiB BLOCK units run; 1: every 64 KiB mark was found (libsnappy's blocks) -- the coarse ones; 0: the stream unit.
+// fine_ok: scan_fine_found, and no 8 KiB unit has failed as far as the caller has to know
+__device__ __forceinline__ unsigned scan_stream_mode(const HapGpuScanChunk *scan, bool fine_ok)
+{
+    return scan->ok == 0u ? 0u : fine_ok ? 2u : scan->found == scan->expected ? 1u : 0u;
+}
+
+// the set a unit belongs to, in scan_stream_mode's numbers
+__device__ __forceinline__ unsigned scan_unit_mode(unsigned kind, uint64_t reserved)
+{
+    return kind != HAPGPU_UNIT_SNAPPY_BLOCK ? 0u : (reserved & HAPGPU_BLOCK_FINE) ? 2u : 1u;
+}
+
+// ------------------------------------------------------------------------------------------
+// region calls: units that hold no byte of the rectangle's blocks
+// ------------------------------------------------------------------------------------------
+
+// A lane per unit of a call that wants only a rectangle of every texture (HapGpuDecodeFramesRGBARegion): a unit's place
+// in its texture is u.dst - job.dst and u.dst_len, and a unit for which hap_region_needs_bytes says no becomes SKIP --
+// whatever it was: a chunk's stream, a fragment of the table, a raw copy, a block the scan found.  Its bytes are added to
+// `skipped` (unless null: a frame's second pass, counted by its first) where the unit would have run: once per
+// wavefront.  Of a scanned stream's two sets of BLOCK units (64 KiB and 8 KiB) the one the decoder runs is counted
+// (scan_stream_mode; this kernel runs in front of the decoder, where no 8 KiB unit has failed yet); both are blanked: the
+// other set is what a stream falls back to, and it needs the same bytes.
+__global__ __launch_bounds__(256) void skip_units_kernel(HapGpuDecodeUnit *units, unsigned unit_count, const HapGpuDecodeJob *jobs,
+                                                         const uint32_t *job_block_bytes, HapGpuRegion g,
+                                                         unsigned long long *skipped)
+{
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    unsigned long long bytes = 0;
+    if (i < unit_count) {
+        const HapGpuDecodeUnit u = units[i];
+        if (u.kind != HAPGPU_UNIT_SKIP && u.dst_len != 0u) {
+            const unsigned block_bytes = job_block_bytes[u.job];
+            if (hap_region_valid(g.width, block_bytes, g.x, g.y, g.w, g.h) &&
+                !hap_region_needs_bytes(g.width, block_bytes, g.x, g.y, g.w, g.h, u.dst - jobs[u.job].dst, u.dst_len)) {
+                bool runs = true;
+                if (u.kind == HAPGPU_UNIT_SNAPPY_BLOCK) {
+                    const HapGpuScanChunk *scan = (const HapGpuScanChunk *)u.aux;
+                    runs = scan_stream_mode(scan, scan_fine_found(scan)) == scan_unit_mode(u.kind, u.reserved);
+                }
+                units[i].kind = HAPGPU_UNIT_SKIP;
+                bytes = runs ? u.dst_len : 0u;
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1)
+        bytes += __shfl_down(bytes, d);
+    if ((threadIdx.x & 63u) == 0u && bytes != 0ull && skipped)
+        atomicAdd(skipped, bytes);
+}
+
+// ------------------------------------------------------------------------------------------
 // decode
 // ------------------------------------------------------------------------------------------
 
@@ -510,14 +578,13 @@ __global__ __launch_bounds__(64) void snappy_decode_fragment_kernel(const HapGpu
     if (STREAM && (u.kind == HAPGPU_UNIT_SNAPPY_BLOCK || u.reserved != 0u)) {
         // a stream the block scan looked at: its BLOCK units run when every block start was found, else the stream unit
         const HapGpuScanChunk *scan = (const HapGpuScanChunk *)(u.kind == HAPGPU_UNIT_SNAPPY_BLOCK ? u.aux : u.reserved);
-        // 2: every 8 KiB mark was found (a table-less stream of this library: its fragments) -- the fine BLOCK units run;
-        // 1: every 64 KiB mark (libsnappy's blocks) -- the coarse ones; 0: the stream unit
+        // (scan_stream_mode: 2 the fine BLOCK units run, 1 the coarse ones, 0 the stream unit)
         const bool fine_on = scan->expected_fine != 0u;
         // (fine_failed: written by the fine units of phase 1, read here by the others in phase 2)
-        const bool fine_ok = fine_on && scan->found_fine == scan->expected_fine &&
+        const bool fine_ok = scan_fine_found(scan) &&
                              (fine_unit || __hip_atomic_load(&scan->fine_failed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u);
-        const unsigned mode = scan->ok == 0u ? 0u : fine_ok ? 2u : scan->found == scan->expected ? 1u : 0u;
-        const unsigned mine = u.kind != HAPGPU_UNIT_SNAPPY_BLOCK ? 0u : (u.reserved & HAPGPU_BLOCK_FINE) ? 2u : 1u;
+        const unsigned mode = scan_stream_mode(scan, fine_ok);
+        const unsigned mine = scan_unit_mode(u.kind, u.reserved);
         if (mode != mine)
             return;
         if (mine != 0u) {
@@ -2285,6 +2352,18 @@ extern "C" int hapgpu_k_decode_plan(hapgpu_rt *rt, HapGpuDecodeJob *jobs, unsign
     hipLaunchKernelGGL(decode_plan_kernel, dim3(job_count), dim3(64), 0, stream, jobs, job_count);
     if (max_chunks)
         hipLaunchKernelGGL(decode_expand_kernel, dim3(max_chunks, job_count), dim3(64), 0, stream, jobs, job_count);
+    return hipGetLastError() == hipSuccess ? 0 : 4;
+}
+
+// hapgpu_abi.h: blanks the units of a region call that hold no byte of the rectangle's blocks
+extern "C" int hapgpu_k_skip_units(hapgpu_rt *rt, HapGpuDecodeUnit *units, unsigned unit_count, const HapGpuDecodeJob *jobs,
+                                   const uint32_t *job_block_bytes, const HapGpuRegion *region, int count)
+{
+    scoped_timing st(rt, 4);
+    if (unit_count == 0 || !region)
+        return 0;
+    hipLaunchKernelGGL(skip_units_kernel, dim3((unit_count + 255u) / 256u), dim3(256), 0, hapgpu_rt_stream(rt), units, unit_count,
+                       jobs, job_block_bytes, *region, count ? hapgpu_rt_skipped_counter(rt) : nullptr);
     return hipGetLastError() == hipSuccess ? 0 : 4;
 }
 

@@ -222,6 +222,21 @@ unsigned int HapGpuDecompressRGBAScaled(HapGpuContext *context,
                                         unsigned int width, unsigned int height, unsigned int scaleLog2,
                                         void *rgba, unsigned long rowBytes);
 
+/* The same texture -> the RGBA8 picture of one block-aligned rectangle of it, regionWidth x regionHeight: byte for byte
+ * the crop of what HapGpuDecompressRGBA writes, from the rectangle's blocks alone (no other block of the texture or of
+ * the alpha plane is read).  width and height are the TEXTURE's.  regionX, regionY, regionWidth and regionHeight are
+ * multiples of 4, the last two non-zero, regionX + regionWidth <= width and regionY + regionHeight <= height: anything
+ * else is Bad_Arguments and nothing is written.  rowBytes a multiple of 16 and at least regionWidth * 4, a device picture
+ * 16-byte aligned; host or device pointers; only the picture's bytes of each row are written.  Textures, formats and the
+ * alpha plane as for HapGpuDecompressRGBA.  Out of scope: RGBA16F and A8 pictures, and scaled rectangles. */
+unsigned int HapGpuDecompressRGBARegion(HapGpuContext *context,
+                                        const void *texture, unsigned long textureBytes, unsigned int textureFormat,
+                                        const void *alphaTexture, unsigned long alphaTextureBytes,
+                                        unsigned int width, unsigned int height,
+                                        unsigned int regionX, unsigned int regionY,
+                                        unsigned int regionWidth, unsigned int regionHeight,
+                                        void *rgba, unsigned long rowBytes);
+
 /* BC6H texture (Hap HDR) -> RGBA16F: four IEEE half bit patterns per texel, 8 bytes, rows rowBytes apart.
  * textureFormat: RGB_BPTC_UNSIGNED_FLOAT or RGB_BPTC_SIGNED_FLOAT (anything else is Bad_Arguments).  RGB is
  * the BPTC definition's result bit for bit (signed textures may give -0, 0x8000, which is kept); alpha is
@@ -464,6 +479,51 @@ unsigned int HapGpuDecodeFramesRGBA(HapGpuContext *context, unsigned int frameCo
                                     unsigned int width, unsigned int height, unsigned long rowBytes,
                                     unsigned int *results,
                                     unsigned int flags);
+
+/* Frames in, the pixels of one rectangle out: HapGpuDecodeFramesRGBA for clients that show a tile of a large canvas (one
+ * output of a video wall, one projector of a blend, one GPU's band).  The rectangle (regionX, regionY, regionWidth,
+ * regionHeight, in texels of the FRAMES' width x height) is block-aligned: all four are multiples of 4, width and height
+ * of it are non-zero, regionX + regionWidth <= width and regionY + regionHeight <= height; anything else is Bad_Arguments
+ * for the whole call, every results[f] set to it and nothing written.  Pictures are regionWidth x regionHeight RGBA8,
+ * host or device, rowBytes a multiple of 16 and at least regionWidth * 4, device pictures 16-byte aligned, host pictures
+ * with longer rows written row by row: HapGpuDecodeFramesRGBA's rules at the rectangle's size.  Every picture is byte for
+ * byte the crop of what HapGpuDecodeFramesRGBA writes for the same frame; bytes outside a picture's own rows are never
+ * written.  The block decoder reads the rectangle's blocks only, and the second stage leaves undecoded every
+ * independently decodable piece -- a chunk, a fragment of this library's table, a block found by the scan of a
+ * table-less stream, a 64 KiB piece of an uncompressed chunk -- that holds no byte of them (HapGpuRegionNeedsBytes);
+ * a rectangle that is the whole frame skips nothing.  textureCount, the formats, flags (HAPGPU_DECODE_BPTC_PICTURES
+ * included), mixed batches and slicing are HapGpuDecodeFramesRGBA's.  results[f] too, with one difference: damage that
+ * lies wholly inside skipped pieces is not seen (as HapDecode does not see a chunk its callback never runs); damage in
+ * the container, the tables or a decoded piece gets the full call's code.  A frame of another format or geometry is
+ * Bad_Arguments alone, its picture untouched.  Out of scope: RGBA16F and A8 pictures, a rectangle together with
+ * scaleLog2, ...OnDevices / ...Sequence forms, rectangles off the block grid. */
+unsigned int HapGpuDecodeFramesRGBARegion(HapGpuContext *context, unsigned int frameCount,
+                                          const void *const *inputBuffers,
+                                          const unsigned long *inputBuffersBytes,
+                                          unsigned int textureCount,
+                                          void *const *rgbaFrames,
+                                          unsigned int width, unsigned int height,
+                                          unsigned int regionX, unsigned int regionY,
+                                          unsigned int regionWidth, unsigned int regionHeight,
+                                          unsigned long rowBytes,
+                                          unsigned int *results,
+                                          unsigned int flags);
+
+/* Which bytes of a texture a rectangle needs, without a GPU: 1 if and only if bytes [firstByte, firstByte + byteCount)
+ * of a width-wide texture of blockBytes-byte blocks (8: DXT1, RGTC1; 16: the others) hold at least one byte of a block
+ * of the rectangle; 0 for an empty range and for arguments the region rules refuse (Bad_Arguments above; the texture's
+ * height is not known here).  The very predicate the decoder skips by.  With HapGpuGetFrameTextureChunkLayout's offsets
+ * it tells a client which chunks of a frame it has to read from disk at all. */
+unsigned int HapGpuRegionNeedsBytes(unsigned int width, unsigned int blockBytes,
+                                    unsigned int regionX, unsigned int regionY,
+                                    unsigned int regionWidth, unsigned int regionHeight,
+                                    unsigned long firstByte, unsigned long byteCount);
+
+/* Decoded bytes of all the pieces the region calls of this context left undecoded, summed over the context's life.
+ * A frame counts once: one that is decoded a second time without its fragment table keeps the first pass's figure,
+ * though the second pass skips whole chunks only.  Never more, per call, than the textures' bytes minus the bytes of
+ * the rectangle's blocks.  Waits for the stream: for tests and tools, like HapGpuResolvedBlockCount. */
+unsigned long HapGpuSkippedTextureBytes(HapGpuContext *context);
 
 /* Frames in, half- (scaleLog2 1) or quarter-size (scaleLog2 2) pixels out: HapGpuDecodeFramesRGBA with the pictures of
  * HapGpuDecompressRGBAScaled -- (width >> scaleLog2) x (height >> scaleLog2) RGBA8, every texel the rounded-up box mean
