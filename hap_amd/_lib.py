@@ -75,6 +75,8 @@ def _load():
         "HapGpuDecodeFramesRGBA": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, ul, P(u), u]),
         "HapGpuDecodeFramesRGBAScaled": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, ul, P(u), u]),
         "HapGpuDecodeFramesRGBARegion": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, u, u, u, ul, P(u), u]),
+        "HapGpuTranscodeTexture": (u, [vp, vp, ul, u, vp, ul, u, u, u, u, P(u), P(vp), P(ul), P(ul)]),
+        "HapGpuTranscodeFrames": (u, [vp, u, P(vp), P(ul), u, u, u, u, u, P(u), P(u), P(u), P(vp), P(ul), P(ul), P(u), u, u]),
         "HapGpuDecodeFramesRGBAHalf": (u, [vp, u, P(vp), P(ul), P(vp), u, u, ul, P(u), u]),
         "HapGpuDecodeChunkGroup": (u, [vp, vp, ul, u, u, u, vp, ul, P(ul), P(u)]),
         "HapGpuGetFrameTextureChunkLayout": (u, [vp, ul, u, u, P(ul), P(u)]),

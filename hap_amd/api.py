@@ -618,6 +618,49 @@ class Context:
                                              row_bytes or (width >> shift) * 4, results, flags)
         return r, list(results)
 
+    def transcode_texture(self, texture, texture_format, width, height, scale_log2, output_formats, alpha=None,
+                          outputs=None):
+        """Texture (+ optional RGTC1 alpha plane) -> textures of output_formats at (width >> scale_log2) x
+        (height >> scale_log2), as compress_rgba would make them of decompress_rgba[_scaled]'s picture, without that
+        picture (HapGpuTranscodeTexture).  Returns (result, [bytes] | None), or (result, [bytes used]) into `outputs`."""
+        ta, tn, _k = _addr_len(texture)
+        aa, an, _k2 = _addr_len(alpha) if alpha is not None else (None, 0, None)
+        count = len(output_formats)
+        own = outputs is None
+        if own:
+            shift = scale_log2 if 0 <= scale_log2 < 3 else 0
+            blocks = ((width >> shift) // 4) * ((height >> shift) // 4)
+            outputs = [(C.c_ubyte * max(1, blocks * (8 if f in (HapTextureFormat.RGB_DXT1, HapTextureFormat.A_RGTC1) else 16)))()
+                       for f in output_formats]
+        optrs, oinfos = self._ptr_array(outputs)
+        olens = (C.c_ulong * max(1, count))(*[i[1] for i in oinfos])
+        used = (C.c_ulong * max(1, count))()
+        r = lib.HapGpuTranscodeTexture(self.handle, ta, tn, texture_format, aa, an, width, height, scale_log2, count,
+                                       (C.c_uint * max(1, count))(*output_formats), optrs, olens, used)
+        if own:
+            return r, ([C.string_at(o, used[i]) for i, o in enumerate(outputs)] if r == 0 else None)
+        return r, list(used)[:count]
+
+    def transcode_frames(self, frames, frame_bytes, source_texture_count, width, height, scale_log2, formats, compressors,
+                         chunk_counts, outputs, decode_flags=0, encode_flags=0):
+        """Frames -> frames of the texture formats `formats` at (width >> scale_log2) x (height >> scale_log2) in one call,
+        without a picture in between (HapGpuTranscodeFrames); width and height are the source frames'.  Returns
+        (result, used[], results[])."""
+        nf, count = len(frames), len(formats)
+        if len(outputs) != nf:
+            raise ValueError("one output per frame")
+        ptrs, infos = self._ptr_array(frames)
+        lens = (C.c_ulong * nf)(*[fb if fb is not None else infos[i][1] for i, fb in enumerate(frame_bytes)])
+        optrs, oinfos = self._ptr_array(outputs)
+        olens = (C.c_ulong * nf)(*[i[1] for i in oinfos])
+        used = (C.c_ulong * nf)()
+        results = (C.c_uint * nf)()
+        r = lib.HapGpuTranscodeFrames(self.handle, nf, ptrs, lens, source_texture_count, width, height, scale_log2, count,
+                                      (C.c_uint * max(1, count))(*formats), (C.c_uint * max(1, count))(*compressors),
+                                      (C.c_uint * max(1, count))(*chunk_counts), optrs, olens, used, results,
+                                      decode_flags, encode_flags)
+        return r, list(used), list(results)
+
     def decode_frames_rgba_region(self, frames, frame_bytes, texture_count, rgba_frames, width, height, region,
                                   row_bytes=None, flags=0):
         """Frames -> RGBA8 pictures of region = (x, y, w, h), a block-aligned rectangle of every frame, in one call

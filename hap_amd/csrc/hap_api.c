@@ -990,6 +990,42 @@ unsigned int HapGpuDecodeFramesRGBAScaled(HapGpuContext *context, unsigned int f
     return r;
 }
 
+/* texture(s) -> texture(s) and frames -> frames of another flavour or size, without a picture in between */
+unsigned int HapGpuTranscodeTexture(HapGpuContext *context, const void *texture, unsigned long textureBytes,
+                                    unsigned int textureFormat, const void *alphaTexture, unsigned long alphaTextureBytes,
+                                    unsigned int width, unsigned int height, unsigned int scaleLog2, unsigned int count,
+                                    const unsigned int *outputFormats, void *const *outputs,
+                                    const unsigned long *outputsBytes, unsigned long *outputsBytesUsed)
+{
+    unsigned r;
+    if (!context)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_transcode_texture(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width, height,
+                               scaleLog2, count, outputFormats, outputs, outputsBytes, outputsBytesUsed);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+unsigned int HapGpuTranscodeFrames(HapGpuContext *context, unsigned int frameCount, const void *const *inputBuffers,
+                                   const unsigned long *inputBuffersBytes, unsigned int sourceTextureCount,
+                                   unsigned int width, unsigned int height, unsigned int scaleLog2, unsigned int count,
+                                   const unsigned int *textureFormats, const unsigned int *compressors,
+                                   const unsigned int *chunkCounts, void *const *outputBuffers,
+                                   const unsigned long *outputBuffersBytes, unsigned long *outputBuffersBytesUsed,
+                                   unsigned int *results, unsigned int decodeFlags, unsigned int encodeFlags)
+{
+    unsigned r;
+    if (!context)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_transcode(context, frameCount, inputBuffers, inputBuffersBytes, sourceTextureCount, width, height, scaleLog2,
+                       count, textureFormats, compressors, chunkCounts, outputBuffers, outputBuffersBytes,
+                       outputBuffersBytesUsed, results, decodeFlags, encodeFlags);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
 unsigned int HapGpuDecodeFramesRGBAHalf(HapGpuContext *context, unsigned int frameCount,
                                         const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
                                         void *const *rgbaHalfFrames, unsigned int width, unsigned int height,

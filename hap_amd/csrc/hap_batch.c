@@ -28,6 +28,8 @@ enum {
 #define D_CHUNK_ACC D_JOBS
 #define D_SCAN D_SLOTS       /* ... and the decoder's block-scan arena in an encode-only one */
 #define D_GUESS D_FRAGSIZES  /* ... and the group tables the decoder makes for fragments that came without */
+#define D_TRANSCODED D_RGBA_STAGE /* ... and the textures a transcode call makes, where the calls with pictures stage those: it
+                                     has none, and D_BC_TEX holds its source textures until its encode half is done */
 #define P_SCAN P_FRAMES
 enum { P_FRAMES = 0, P_JOBS, P_CHUNKS, P_PREFIX, P_PTRS, P_BC_PTRS, P_PREFIX2 };   /* (8, 9: hap_sequence.c) */
 
@@ -67,6 +69,28 @@ typedef struct tex_geom {
     unsigned long bytes;
     size_t bound;        /* hap_max_encoded_length for the requested compressor (hap.c:386) */
 } tex_geom;
+
+/* What hapb_encode asks of a call's textures whatever its frames are (reference hap.c:518-559, and per texture
+   hap.c:367-385): Bad_Arguments refuses the whole call.  count 1 or 2. */
+static unsigned encode_textures_valid(unsigned count, const unsigned long *input_bytes, const unsigned *formats,
+                                      const unsigned *compressors, const unsigned *chunk_counts, unsigned flags)
+{
+    const int smaller = (flags & HAPGPU_ENCODE_SMALLER_FILES) != 0;
+    unsigned i;
+    /* (with HAPGPU_ENCODE_FINE_CHUNKS the call's chunk counts are replaced: whatever they say is not looked at) */
+    for (i = 0; i < count; i++)
+        if (chunk_counts[i] == 0 && !((flags & HAPGPU_ENCODE_FINE_CHUNKS) && !smaller && compressors[i] == HapCompressorSnappy))
+            return HapResult_Bad_Arguments;
+    if (count == 2 &&
+        formats[0] != HapTextureFormat_YCoCg_DXT5 && formats[1] != HapTextureFormat_YCoCg_DXT5 &&
+        formats[0] != HapTextureFormat_A_RGTC1 && formats[1] != HapTextureFormat_A_RGTC1)
+        return HapResult_Bad_Arguments;
+    for (i = 0; i < count; i++)
+        if (input_bytes[i] == 0 || input_bytes[i] > 0xFFFFFFFFul || hapf_nibble_from_format(formats[i]) == 0 ||
+            (compressors[i] != HapCompressorNone && compressors[i] != HapCompressorSnappy))
+            return HapResult_Bad_Arguments;
+    return HapResult_No_Error;
+}
 
 unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                      const void *const *inputs, const unsigned long *input_bytes,
@@ -115,19 +139,8 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
         if (count == 0 || count > 2 || !inputs || !input_bytes || !formats || !compressors || !chunk_counts ||
             !outputs || !output_bytes || !output_used)
             rc = HapResult_Bad_Arguments;
-        /* (with HAPGPU_ENCODE_FINE_CHUNKS the call's chunk counts are replaced below: whatever they say is not looked at) */
-        for (i = 0; rc == HapResult_No_Error && i < count; i++)
-            if (chunk_counts[i] == 0 && !((flags & HAPGPU_ENCODE_FINE_CHUNKS) && !smaller && compressors[i] == HapCompressorSnappy))
-                rc = HapResult_Bad_Arguments;
-        if (rc == HapResult_No_Error && count == 2 &&
-            formats[0] != HapTextureFormat_YCoCg_DXT5 && formats[1] != HapTextureFormat_YCoCg_DXT5 &&
-            formats[0] != HapTextureFormat_A_RGTC1 && formats[1] != HapTextureFormat_A_RGTC1)
-            rc = HapResult_Bad_Arguments;
-        /* per-texture checks that do not depend on the frame, reference hap.c:367-385 */
-        for (i = 0; rc == HapResult_No_Error && i < count; i++)
-            if (input_bytes[i] == 0 || input_bytes[i] > 0xFFFFFFFFul || hapf_nibble_from_format(formats[i]) == 0 ||
-                (compressors[i] != HapCompressorNone && compressors[i] != HapCompressorSnappy))
-                rc = HapResult_Bad_Arguments;
+        if (rc == HapResult_No_Error)
+            rc = encode_textures_valid(count, input_bytes, formats, compressors, chunk_counts, flags);
         if (rc != HapResult_No_Error) {
             for (f = 0; f < frame_count; f++)
                 results[f] = rc;
@@ -2155,6 +2168,288 @@ unsigned hapb_decode_alpha(HapGpuContext *ctx, unsigned frame_count, const void 
     const picture_road road = road_of(HAPGPU_PICTURE_A8, flags, 0u, NULL);
     return decode_pictures(ctx, frame_count, inputs, input_bytes, 1u, pictures, width, height, row_bytes, results, flags,
                            &road);
+}
+
+/* ============================================================= transcode */
+/* Frames -> frames of other texture formats or of half / quarter size: hapb_decode into D_BC_TEX as in decode_pictures,
+   the transcode kernel from there into D_TRANSCODED (one launch per source format present in the slice), hapb_encode on
+   those textures -- or, for a frame that holds the wanted formats already, on its own.  No picture anywhere. */
+
+/* the destination sets the kernel makes: 1 DXT1, 2 DXT5, 3 YCoCg-DXT5, 4 YCoCg-DXT5 + RGTC1 (Hap Q Alpha); 0: none of them */
+static unsigned transcode_set(unsigned count, const unsigned *formats)
+{
+    if (count == 1u)
+        return formats[0] == HapTextureFormat_RGB_DXT1 ? 1u : formats[0] == HapTextureFormat_RGBA_DXT5 ? 2u :
+               formats[0] == HapTextureFormat_YCoCg_DXT5 ? 3u : 0u;
+    return count == 2u && formats[0] == HapTextureFormat_YCoCg_DXT5 && formats[1] == HapTextureFormat_A_RGTC1 ? 4u : 0u;
+}
+
+static void transcode_refuse(unsigned *results, unsigned frame_count, unsigned code)
+{
+    unsigned f;
+    for (f = 0; results && f < frame_count; f++)
+        results[f] = code;
+}
+
+unsigned hapb_transcode(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                        const unsigned long *input_bytes, unsigned texture_count, unsigned width, unsigned height,
+                        unsigned scale_log2, unsigned count, const unsigned *formats, const unsigned *compressors,
+                        const unsigned *chunk_counts, void *const *outputs, const unsigned long *output_bytes,
+                        unsigned long *output_used, unsigned *results, unsigned decode_flags, unsigned encode_flags)
+{
+    hapgpu_rt *rt = ctx->rt;
+    /* the three source formats of the kernel, each with or without an alpha plane: the picture road's without BC7 */
+    const picture_road road = road_of(HAPGPU_PICTURE_RGBA8, 0u, 0u, NULL);
+    size_t blocks, per_frame, alpha_off, out_per_frame = 0, out_off[2] = {0, 0}, slice, done;
+    unsigned long out_bytes[2] = {0, 0};
+    unsigned first_error = HapResult_No_Error, f, i, set;
+    const void **in, **tex;
+    unsigned long *in_bytes, *caps, *used;
+    void **outs;
+    unsigned *idx, *fmts, *res;
+    if (frame_count == 0)
+        return HapResult_No_Error;
+    if (!results)
+        return HapResult_Bad_Arguments;
+    if (context_busy(ctx, results, frame_count))
+        return HapResult_Internal_Error;
+    if (!inputs || !input_bytes || !formats || !compressors || !chunk_counts || !outputs || !output_bytes || !output_used ||
+        texture_count == 0 || texture_count > 2 || count == 0 || count > 2 || scale_log2 > 2u || width == 0 || height == 0 ||
+        width % (4u << scale_log2) || height % (4u << scale_log2) || (height >> scale_log2) / 4u > 65535u) {
+        transcode_refuse(results, frame_count, HapResult_Bad_Arguments);
+        return HapResult_Bad_Arguments;
+    }
+    /* a destination the kernel does not make is one a frame can only have already: legal at the frames' own size */
+    set = transcode_set(count, formats);
+    if (!set && scale_log2) {
+        transcode_refuse(results, frame_count, HapResult_Bad_Arguments);
+        return HapResult_Bad_Arguments;
+    }
+    for (i = 0; i < count; i++) {
+        out_bytes[i] = (unsigned long)((size_t)((width >> scale_log2) / 4u) * ((height >> scale_log2) / 4u) * hapf_block_bytes(formats[i]));
+        out_off[i] = out_per_frame;
+        out_per_frame += align_up(out_bytes[i], 256);
+    }
+    encode_flags &= ~HAPGPU_ENCODE_BPTC_BLOCKS;
+    if (encode_textures_valid(count, out_bytes, formats, compressors, chunk_counts, encode_flags) != HapResult_No_Error) {
+        transcode_refuse(results, frame_count, HapResult_Bad_Arguments);
+        return HapResult_Bad_Arguments;
+    }
+    blocks = (size_t)(width / 4u) * (height / 4u);
+    alpha_off = align_up(blocks * 16u, 256);
+    per_frame = alpha_off + (texture_count == 2 ? align_up(blocks * 8u, 256) : 0u);
+    slice = RGBA_SLICE_BYTES / (per_frame + out_per_frame);
+    if (slice == 0)
+        slice = 1;
+    if (slice > frame_count)
+        slice = frame_count;
+    if (slice * texture_count > 32768u)
+        slice = 32768u / texture_count;
+    in = (const void **)malloc(sizeof(*in) * slice * texture_count);
+    in_bytes = (unsigned long *)malloc(sizeof(*in_bytes) * slice * texture_count * 3u);
+    outs = (void **)malloc(sizeof(*outs) * slice * texture_count);
+    idx = (unsigned *)malloc(sizeof(*idx) * slice * (texture_count * 3u + 1u));
+    tex = (const void **)malloc(sizeof(*tex) * slice * count);
+    if (!in || !in_bytes || !outs || !idx || !tex) {
+        free(in); free(in_bytes); free(outs); free(idx); free(tex);
+        transcode_refuse(results, frame_count, HapResult_Internal_Error);
+        return HapResult_Internal_Error;
+    }
+    caps = in_bytes + slice * texture_count;
+    used = caps + slice * texture_count;
+    fmts = idx + slice * texture_count;
+    res = fmts + slice * texture_count;
+    for (done = 0; done < frame_count; done += slice) {
+        const unsigned n = (unsigned)(frame_count - done < slice ? frame_count - done : slice);
+        unsigned *const decoded = res + (size_t)n * texture_count;      /* per frame: what its decode half came to */
+        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, per_frame * n);
+        uint8_t *transcoded = set ? (uint8_t *)hapgpu_rt_device_scratch(rt, D_TRANSCODED, out_per_frame * n) : NULL;
+        /* [source textures][source planes][destination textures][destination planes] per source format */
+        const size_t tab_bytes = sizeof(uint64_t) * 4u * PICTURE_KINDS_MAX * n;
+        uint64_t *htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, tab_bytes);
+        uint64_t *dtab = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, tab_bytes);
+        unsigned present = 0, k, t;
+        int rc = 0;
+        if (!textures || (set && !transcoded) || !htab || !dtab) {
+            transcode_refuse(results + done, n, HapResult_Internal_Error);
+            first_error = first_error ? first_error : HapResult_Internal_Error;
+            continue;
+        }
+        for (f = 0; f < n; f++)
+            for (t = 0; t < texture_count; t++) {
+                const size_t e = (size_t)f * texture_count + t;
+                in[e] = inputs[done + f];
+                in_bytes[e] = input_bytes[done + f];
+                outs[e] = textures + per_frame * f + (t ? alpha_off : 0u);
+                caps[e] = (unsigned long)(t ? blocks * 8u : blocks * 16u);
+                idx[e] = t;
+                used[e] = 0;
+                fmts[e] = 0;
+            }
+        ctx->decode_indices = idx;
+        hapb_decode(ctx, n * texture_count, in, in_bytes, 0, outs, caps, used, fmts, res, decode_flags & ~HAPGPU_DECODE_BPTC_PICTURES,
+                    NULL, NULL);
+        memset(htab, 0, tab_bytes);
+        for (f = 0; f < n; f++) {
+            const size_t e = (size_t)f * texture_count;
+            const unsigned fmt = fmts[e];
+            unsigned r = res[e];
+            int pass = 0;
+            k = road.kind_count;
+            if (r == HapResult_No_Error && texture_count == 2)
+                r = res[e + 1];
+            if (r == HapResult_No_Error) {
+                /* the frame's own formats are the wanted ones, at its own size: its textures go on as they are */
+                pass = scale_log2 == 0u && texture_count == count;
+                for (i = 0; pass && i < count; i++)
+                    if (fmts[e + i] != formats[i] || used[e + i] != out_bytes[i])
+                        pass = 0;
+                for (k = 0; k < road.kind_count && road.kinds[k] != fmt; k++)
+                    ;
+                /* else it must hold what the caller's geometry says, as for decode_pictures: a colour texture the
+                   kernel reads, of exactly width x height, and (two textures) an RGTC1 plane of the same geometry */
+                if (!pass && (!set || k == road.kind_count || used[e] != blocks * hapf_block_bytes(fmt) ||
+                              (texture_count == 2 && (fmts[e + 1] != HapTextureFormat_A_RGTC1 || used[e + 1] != blocks * 8u))))
+                    r = HapResult_Bad_Arguments;
+            }
+            decoded[f] = r;
+            for (i = 0; i < count; i++)
+                tex[(size_t)f * count + i] = r != HapResult_No_Error ? NULL :
+                                             pass ? outs[e + i] : (const void *)(transcoded + out_per_frame * f + out_off[i]);
+            /* (a frame whose output hapb_encode will refuse is not worth the kernel's time either) */
+            if (r == HapResult_No_Error && !pass && outputs[done + f] && output_bytes[done + f]) {
+                uint64_t *col = htab + (size_t)k * 4u * n;
+                present |= 1u << k;
+                col[f] = (uint64_t)(uintptr_t)outs[e];
+                col[n + f] = texture_count == 2 ? (uint64_t)(uintptr_t)outs[e + 1] : 0u;
+                col[2u * n + f] = (uint64_t)(uintptr_t)tex[(size_t)f * count];
+                col[3u * n + f] = count == 2 ? (uint64_t)(uintptr_t)tex[(size_t)f * count + 1] : 0u;
+            }
+        }
+        if (present) {
+            rc |= hapgpu_rt_h2d(rt, dtab, htab, tab_bytes);
+            for (k = 0; k < road.kind_count; k++)
+                if (present & (1u << k)) {
+                    const uint64_t *col = dtab + (size_t)k * 4u * n;
+                    const HapGpuTranscodeTable tt = {{col, col + n, col + 2u * (size_t)n, col + 3u * (size_t)n}, {0u, 0u, 0u, 0u}};
+                    rc |= hapgpu_k_block_transcode(rt, &tt, n, road.kinds[k], texture_count == 2, width, height, scale_log2,
+                                                   formats[0], count == 2);
+                }
+        }
+        if (rc)     /* (nothing of this slice's kernel output may be trusted: its frames fail, the pass-through ones included) */
+            memset(tex, 0, sizeof(*tex) * (size_t)n * count);
+        /* the encode half on the same stream, behind the kernel; it ends with the slice's second and last wait */
+        hapb_encode(ctx, n, count, tex, out_bytes, formats, compressors, chunk_counts, outputs + done, output_bytes + done,
+                    output_used + done, results + done, encode_flags, 1);
+        for (f = 0; f < n; f++) {
+            if (decoded[f] != HapResult_No_Error)
+                results[done + f] = decoded[f];
+            else if (rc && (results[done + f] == HapResult_No_Error || results[done + f] == HapResult_Bad_Arguments))
+                results[done + f] = HapResult_Internal_Error;
+            if (results[done + f] != HapResult_No_Error && first_error == HapResult_No_Error)
+                first_error = results[done + f];
+        }
+    }
+    free(in); free(in_bytes); free(outs); free(idx); free(tex);
+    return first_error;
+}
+
+/* One texture (+ alpha plane) -> `count` textures of one of the kernel's destination sets; the set the source is
+   already, at its own size, is copied. */
+unsigned hapb_transcode_texture(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
+                                const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
+                                unsigned scale_log2, unsigned count, const unsigned *formats, void *const *outputs,
+                                const unsigned long *output_bytes, unsigned long *output_used)
+{
+    const picture_road road = road_of(HAPGPU_PICTURE_RGBA8, 0u, 0u, NULL);
+    hapgpu_rt *rt = ctx->rt;
+    const size_t block = hapf_block_bytes(format);
+    HapGpuTranscodeTable t = {{NULL, NULL, NULL, NULL}, {0u, 0u, 0u, 0u}};
+    size_t need, alpha_need, out_need[2] = {0, 0}, out_off[2] = {0, 0}, out_total = 0;
+    const void *src = texture, *asrc = alpha;
+    uint8_t *staged = NULL;
+    unsigned i, k, set, align;
+    int rc = 0, pass;
+    if (context_busy(ctx, NULL, 0))
+        return HapResult_Internal_Error;
+    for (k = 0; k < road.kind_count && road.kinds[k] != format; k++)
+        ;
+    if (!texture || !formats || !outputs || !output_bytes || count == 0 || count > 2 || scale_log2 > 2u || width == 0 ||
+        height == 0 || width % (4u << scale_log2) || height % (4u << scale_log2) || (height >> scale_log2) / 4u > 65535u ||
+        k == road.kind_count)
+        return HapResult_Bad_Arguments;
+    set = transcode_set(count, formats);
+    if (!set)
+        return HapResult_Bad_Arguments;
+    need = (size_t)(width / 4u) * (height / 4u) * block;
+    alpha_need = (size_t)(width / 4u) * (height / 4u) * 8u;
+    if (texture_bytes < need || (alpha && alpha_bytes < alpha_need))
+        return HapResult_Bad_Arguments;
+    for (i = 0; i < count; i++) {
+        if (!outputs[i])
+            return HapResult_Bad_Arguments;
+        out_need[i] = (size_t)((width >> scale_log2) / 4u) * ((height >> scale_log2) / 4u) * hapf_block_bytes(formats[i]);
+        out_off[i] = out_total;
+        out_total += align_up(out_need[i], 256);
+    }
+    for (i = 0; i < count; i++)
+        if (output_bytes[i] < out_need[i])
+            return HapResult_Buffer_Too_Small;
+    /* device sources aligned to what a lane reads of a block row (the block << scale_log2, at most 16 bytes), device
+       outputs to their blocks */
+    align = (unsigned)(block << scale_log2) > 16u ? 16u : (unsigned)(block << scale_log2);
+    if ((is_dev(ctx, texture) && ((uintptr_t)texture & (align - 1u))) ||
+        (alpha && is_dev(ctx, alpha) && ((uintptr_t)alpha & ((8u << scale_log2 > 16u ? 16u : 8u << scale_log2) - 1u))))
+        return HapResult_Bad_Arguments;
+    for (i = 0; i < count; i++)
+        if (is_dev(ctx, outputs[i]) && ((uintptr_t)outputs[i] & (hapf_block_bytes(formats[i]) - 1u)))
+            return HapResult_Bad_Arguments;
+    if (!is_dev(ctx, texture) || (alpha && !is_dev(ctx, alpha))) {
+        uint8_t *s = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, align_up(need, 256) + alpha_need);
+        if (!s)
+            return HapResult_Internal_Error;
+        if (!is_dev(ctx, texture)) {
+            if (hapgpu_rt_h2d(rt, s, texture, need))
+                return HapResult_Internal_Error;
+            src = s;
+        }
+        if (alpha && !is_dev(ctx, alpha)) {
+            if (hapgpu_rt_h2d(rt, s + align_up(need, 256), alpha, alpha_need))
+                return HapResult_Internal_Error;
+            asrc = s + align_up(need, 256);
+        }
+    }
+    /* the source is the destination set already (its alpha plane counted), at its own size: no generation loss */
+    pass = scale_log2 == 0u && formats[0] == format && (count == 2) == (alpha != NULL);
+    for (i = 0; i < count; i++)
+        if (!is_dev(ctx, outputs[i]) && !pass && !staged) {
+            staged = (uint8_t *)hapgpu_rt_device_scratch(rt, D_TRANSCODED, out_total);
+            if (!staged)
+                return HapResult_Internal_Error;
+        }
+    if (pass) {
+        for (i = 0; i < count; i++) {
+            const void *from = i ? asrc : src;
+            rc |= is_dev(ctx, outputs[i]) ? hapgpu_rt_d2d(rt, outputs[i], from, out_need[i])
+                                          : hapgpu_rt_d2h(rt, outputs[i], from, out_need[i]);
+        }
+    } else {
+        t.one[0] = (uint64_t)(uintptr_t)src;
+        t.one[1] = (uint64_t)(uintptr_t)asrc;
+        for (i = 0; i < count; i++)
+            t.one[2u + i] = (uint64_t)(uintptr_t)(is_dev(ctx, outputs[i]) ? (uint8_t *)outputs[i] : staged + out_off[i]);
+        rc = hapgpu_k_block_transcode(rt, &t, 1u, format, alpha != NULL, width, height, scale_log2, formats[0], count == 2);
+        if (rc == 1)
+            return HapResult_Bad_Arguments;
+        for (i = 0; !rc && i < count; i++)
+            if (!is_dev(ctx, outputs[i]))
+                rc |= hapgpu_rt_d2h(rt, outputs[i], staged + out_off[i], out_need[i]);
+    }
+    if (rc || hapgpu_rt_sync(rt))
+        return HapResult_Internal_Error;
+    for (i = 0; output_used && i < count; i++)
+        output_used[i] = (unsigned long)out_need[i];
+    return HapResult_No_Error;
 }
 
 /* ============================================================= join on the device */

@@ -152,6 +152,20 @@ unsigned hapb_decode_alpha(HapGpuContext *ctx, unsigned frame_count, const void 
                            const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,
                            unsigned long row_bytes, unsigned *results, unsigned flags);
 
+/* frames -> frames of the texture formats `formats` (count 1 or 2) at (width >> scale_log2) x (height >> scale_log2),
+   without a picture in between (include/hap_gpu.h: HapGpuTranscodeFrames); texture_count: the textures read of every
+   frame, as for hapb_decode_rgba */
+unsigned hapb_transcode(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                        const unsigned long *input_bytes, unsigned texture_count, unsigned width, unsigned height,
+                        unsigned scale_log2, unsigned count, const unsigned *formats, const unsigned *compressors,
+                        const unsigned *chunk_counts, void *const *outputs, const unsigned long *output_bytes,
+                        unsigned long *output_used, unsigned *results, unsigned decode_flags, unsigned encode_flags);
+/* ... one texture (+ RGTC1 alpha plane) -> `count` textures (HapGpuTranscodeTexture) */
+unsigned hapb_transcode_texture(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
+                                const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
+                                unsigned scale_log2, unsigned count, const unsigned *formats, void *const *outputs,
+                                const unsigned long *output_bytes, unsigned long *output_used);
+
 /* groups and output in device memory: tables through the host, payloads device to device */
 unsigned hapb_join_device(HapGpuContext *ctx, unsigned group_count, const void *const *frames,
                           const unsigned long *frame_bytes, void *output, unsigned long output_bytes,

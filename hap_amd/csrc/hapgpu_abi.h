@@ -344,6 +344,23 @@ int hapgpu_k_block_decode_scaled(hapgpu_rt *rt, const HapGpuPictureTable *table,
 int hapgpu_k_block_decode_region(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, int with_alpha,
                                  unsigned width, unsigned height, unsigned hap_texture_format, unsigned x, unsigned y,
                                  unsigned region_width, unsigned region_height, size_t row_bytes);
+/* [device] Addresses of a transcode launch, as HapGpuPictureTable's: source textures, source alpha planes, destination
+   textures, destination alpha planes (Hap Q Alpha's second texture). */
+typedef struct HapGpuTranscodeTable {
+    const uint64_t *column[4];
+    uint64_t one[4];
+} HapGpuTranscodeTable;
+/* blocks of `src_format` (RGB_DXT1, RGBA_DXT5 or YCoCg_DXT5; with_alpha: an RGTC1 plane supplies A) -> blocks of
+   `dst_format` (RGB_DXT1, RGBA_DXT5 or YCoCg_DXT5; dst_with_alpha, YCoCg_DXT5 only: + the RGTC1 plane of A) of textures of
+   (width >> scale_log2) x (height >> scale_log2), scale_log2 0 to 2, without a picture in between: byte for byte what
+   hapgpu_k_block_encode makes of the RGBA8 pictures hapgpu_k_block_decode (scale_log2 0) or hapgpu_k_block_decode_scaled
+   writes for the sources.  width and height are the sources', multiples of 4 << scale_log2; at most 65535 destination
+   block rows.  Sources and their planes aligned to what a lane reads of a block row (their block << scale_log2, at
+   most 16 bytes), destinations to their blocks.  A source without alpha gives A = 255; a destination without alpha
+   does not read the plane.  Timed as HapGpuKernel_BlockEncode.  Returns 0 launched, 1 bad arguments, 4 launch failure. */
+int hapgpu_k_block_transcode(hapgpu_rt *rt, const HapGpuTranscodeTable *table, unsigned pictures, unsigned src_format,
+                             int with_alpha, unsigned width, unsigned height, unsigned scale_log2, unsigned dst_format,
+                             int dst_with_alpha);
 /* group_tables: HAP_GROUP_TABLE_BYTES bytes per fragment (same indexing as frag_sizes), written for textures whose reserved bit 20 is set */
 int hapgpu_k_snappy_compress(hapgpu_rt *rt, const HapGpuFrameEnc *frames, unsigned frame_count,
                              unsigned max_frags_per_texture, unsigned frag_log2,

@@ -570,6 +570,72 @@ unsigned int HapGpuDecodeFramesAlpha(HapGpuContext *context, unsigned int frameC
                                      unsigned int width, unsigned int height, unsigned long rowBytes,
                                      unsigned int *results, unsigned int flags);
 
+/* --- frames to frames: another flavour or size without a picture in between ------------------- */
+
+/* One texture (alphaTexture != NULL: + its RGTC1 alpha plane, Hap Q Alpha's second texture) in, `count` textures of
+ * (width >> scaleLog2) x (height >> scaleLog2) out: outputs[i] is byte for byte what HapGpuCompressRGBA(...,
+ * outputFormats[i], ...) makes of the picture HapGpuDecompressRGBA (scaleLog2 0) or HapGpuDecompressRGBAScaled (1, 2)
+ * writes for the source -- made by one kernel that decodes a block's texels and encodes them again in registers; no such
+ * picture ever exists.  So a source without alpha gives A = 255, RGB_DXT1 output drops alpha, and YCoCg is converted
+ * back to RGB and forward again.  Sources: RGB_DXT1, RGBA_DXT5, YCoCg_DXT5.  Outputs, count 1: RGB_DXT1, RGBA_DXT5 or
+ * YCoCg_DXT5; count 2: YCoCg_DXT5 then A_RGTC1 (Hap Q Alpha, both textures in one pass).  The one exception: the
+ * destination set the source is already (the same format, with a plane exactly when count is 2) at scaleLog2 0 is copied,
+ * not encoded again -- no generation loss.
+ * width and height are the SOURCE's, multiples of 4 << scaleLog2, scaleLog2 0 to 2; at most 65535 output block rows.
+ * Buffers may be host or device; a device source is aligned to its block << scaleLog2 (at most 16 bytes; the plane
+ * likewise, from 8), device outputs to their blocks.  outputsBytesUsed may be NULL.  Bad_Arguments for anything else
+ * (nothing is written); Buffer_Too_Small for an output shorter than its texture.
+ * Out of scope: BC7 and BC6H as a source or destination of the kernel, A8 and RGBA16F, rectangles. */
+unsigned int HapGpuTranscodeTexture(HapGpuContext *context,
+                                    const void *texture, unsigned long textureBytes, unsigned int textureFormat,
+                                    const void *alphaTexture, unsigned long alphaTextureBytes,
+                                    unsigned int width, unsigned int height, unsigned int scaleLog2,
+                                    unsigned int count, const unsigned int *outputFormats,
+                                    void *const *outputs, const unsigned long *outputsBytes,
+                                    unsigned long *outputsBytesUsed);
+
+/* Frames in, frames of other texture formats or of half / quarter size out, in one call and without a picture in
+ * between: a Hap Q master to quarter-size Hap proxies, Hap Alpha to Hap Q Alpha, Hap Q to Hap, another encoder's frames
+ * to frames with this library's fragment table.
+ * The definition: a transcoded frame is byte for byte the frame HapGpuEncodeFramesRGBA(..., width >> scaleLog2,
+ * height >> scaleLog2, ..., count, textureFormats, compressors, chunkCounts, ..., encodeFlags) makes of the picture that
+ * HapGpuDecodeFramesRGBA (scaleLog2 1 or 2: HapGpuDecodeFramesRGBAScaled) writes for the source frame with
+ * sourceTextureCount and decodeFlags.  No such picture ever exists: the textures go from the decoder's second stage
+ * through HapGpuTranscodeTexture's kernel (one launch per source format present: a batch may mix flavours) to the
+ * encoder's second stage, 16 + 16 bytes of traffic per block for Hap Q where the two calls move 16 + 64 + 64 + 16, and
+ * the host is waited for twice per slice of frames: for the decode's results and at the end.
+ * width and height are the SOURCE frames', multiples of 4 << scaleLog2; scaleLog2 0 to 2; sources are what
+ * HapGpuDecodeFramesRGBA takes without HAPGPU_DECODE_BPTC_PICTURES (Hap, Hap Alpha, Hap Q, Hap Q Alpha);
+ * destinations, count 1: RGB_DXT1, RGBA_DXT5 or YCoCg_DXT5; count 2: YCoCg_DXT5 then A_RGTC1.
+ * Pass-through, the one exception to the definition: a frame whose own textures (sourceTextureCount of them, in order)
+ * have the formats textureFormats, at scaleLog2 0, is not encoded again -- its textures go to the second stage as they
+ * are, without generation loss.  That holds for every format HapEncode accepts, RGBA_BPTC_UNORM, the BC6H formats and
+ * a lone A_RGTC1 included, and is how another encoder's frames get a fragment table or fine chunks.  A destination set
+ * outside the four above is therefore legal at scaleLog2 0 only, and a frame that cannot pass through it is
+ * Bad_Arguments alone.
+ * The second stage, frame layout, chunk-count limiting, store-raw decisions, outputBuffersBytes / Buffer_Too_Small and
+ * encodeFlags are HapGpuEncodeFrames' (HAPGPU_ENCODE_BPTC_BLOCKS is ignored); decodeFlags are
+ * HapGpuDecodeFrameTextures'.  Buffers may be host or device.
+ * results[f]: where the decode of frame f fails, the decode's code -- HapDecode's (a broken frame: Bad_Frame), or
+ * Bad_Arguments for a frame of another geometry or format; else the encode's code (a NULL output: Bad_Arguments, a short
+ * one: Buffer_Too_Small).  A failed frame's output buffer is not written.  The function's result is the first failure.
+ * Bad_Arguments for the whole call -- every results[f] set, nothing written -- for a NULL array, scaleLog2 above 2, a
+ * width or height that is no multiple of 4 << scaleLog2, sourceTextureCount or count other than 1 or 2, a destination
+ * set that is illegal at that scale, and what HapGpuEncodeFrames refuses of textureFormats, compressors and
+ * chunkCounts.  A context between HapGpuEncodeFramesRGBABegin and HapGpuEncodeFramesFinish: Internal_Error.
+ * Out of scope: BC7 and BC6H as a source or destination of the re-encoding kernel, A8 and RGBA16F pictures'
+ * flavours (Hap Alpha-Only, Hap HDR) other than by pass-through, rectangles, and ...Begin, ...OnDevices and
+ * ...Sequence forms of this call. */
+unsigned int HapGpuTranscodeFrames(HapGpuContext *context, unsigned int frameCount,
+                                   const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
+                                   unsigned int sourceTextureCount,
+                                   unsigned int width, unsigned int height, unsigned int scaleLog2,
+                                   unsigned int count, const unsigned int *textureFormats,
+                                   const unsigned int *compressors, const unsigned int *chunkCounts,
+                                   void *const *outputBuffers, const unsigned long *outputBuffersBytes,
+                                   unsigned long *outputBuffersBytesUsed, unsigned int *results,
+                                   unsigned int decodeFlags, unsigned int encodeFlags);
+
 /* --- one batch over several GPUs: independent frames per GPU ------------------- */
 
 /* HapGpuEncodeFramesRGBA / HapGpuEncodeFrames / HapGpuDecodeFrames with the batch dealt out over `contextCount`
