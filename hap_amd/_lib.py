@@ -58,6 +58,7 @@ def _load():
         "HapGpuDecodeFramesAlpha": (u, [vp, u, P(vp), P(ul), P(vp), u, u, ul, P(u), u]),
         "HapGpuDecompressRGBA": (u, [vp, vp, ul, u, vp, ul, u, u, vp, ul]),
         "HapGpuDecompressRGBAScaled": (u, [vp, vp, ul, u, vp, ul, u, u, u, vp, ul]),
+        "HapGpuDecompressPlanes": (u, [vp, vp, ul, u, vp, ul, u, u, u, u, u, vp, ul, ul, P(C.c_float), P(C.c_float)]),
         "HapGpuDecompressRGBARegion": (u, [vp, vp, ul, u, vp, ul, u, u, u, u, u, u, vp, ul]),
         "HapGpuRegionNeedsBytes": (u, [u, u, u, u, u, u, ul, ul]),
         "HapGpuSkippedTextureBytes": (ul, [vp]),
@@ -74,6 +75,7 @@ def _load():
         "HapGpuDecodeFrameTextures": (u, [vp, u, P(vp), P(ul), u, P(vp), P(ul), P(ul), P(u), P(u), u]),
         "HapGpuDecodeFramesRGBA": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, ul, P(u), u]),
         "HapGpuDecodeFramesRGBAScaled": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, ul, P(u), u]),
+        "HapGpuDecodeFramesPlanes": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, u, u, ul, ul, P(C.c_float), P(C.c_float), P(u), u]),
         "HapGpuDecodeFramesRGBARegion": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, u, u, u, ul, P(u), u]),
         "HapGpuTranscodeTexture": (u, [vp, vp, ul, u, vp, ul, u, u, u, u, P(u), P(vp), P(ul), P(ul)]),
         "HapGpuTranscodeFrames": (u, [vp, u, P(vp), P(ul), u, u, u, u, u, P(u), P(u), P(u), P(vp), P(ul), P(ul), P(u), u, u]),

@@ -41,6 +41,58 @@ KERNEL_CLASSES = ["block_encode", "snappy_compress", "frame_pack", "frame_gather
                   "block_decode", "block_scan", "encode_fused"]
 
 
+PLANE_ELEMENTS = {"torch.float16": 0, "torch.bfloat16": 1, "torch.float32": 2}     # HapGpuPlaneElement by dtype
+
+
+def _plane_tensors(out, single, width, height, scale_log2):
+    """The tensors of a planar call and what they share: ([3-D tensors], channels, element, planeBytes, rowBytes).
+    `out`: one (C, H >> s, W >> s) tensor (single), or one (N, C, H >> s, W >> s) tensor or a list of N 3-D ones."""
+    if single:
+        tensors = [out]
+    elif hasattr(out, "dim"):
+        if out.dim() != 4:
+            raise ValueError("out: one (N, C, H >> s, W >> s) tensor or a list of (C, H >> s, W >> s) tensors")
+        tensors = [out[i] for i in range(out.shape[0])]
+    else:
+        tensors = list(out)
+    if not tensors:
+        raise ValueError("out: no tensors")
+    shift = scale_log2 if 0 <= scale_log2 < 3 else 0          # (a refused scale: nothing is written)
+    shape = None
+    for t in tensors:
+        if t is None:                                          # (a frame without a tensor: Bad_Arguments for it alone)
+            continue
+        if not (hasattr(t, "dim") and hasattr(t, "stride") and hasattr(t, "data_ptr")):
+            raise ValueError("out: torch tensors")
+        if str(t.dtype) not in PLANE_ELEMENTS:
+            raise ValueError("out: dtype float16, bfloat16 or float32, not %s" % t.dtype)
+        if t.dim() != 3 or t.shape[0] not in (3, 4) or tuple(t.shape[1:]) != (height >> shift, width >> shift):
+            raise ValueError("out: (3 or 4, %d, %d) per frame, not %s" % (height >> shift, width >> shift, tuple(t.shape)))
+        if t.stride(2) != 1:
+            raise ValueError("out: stride(-1) must be 1")
+        if t.device.type != "cuda":
+            raise ValueError("out: tensors in device memory")
+        this = (t.shape[0], str(t.dtype), t.stride(0), t.stride(1))
+        if shape is not None and this != shape:
+            raise ValueError("out: the tensors of a call share channels, dtype and strides")
+        shape = this
+    if shape is None:
+        raise ValueError("out: no tensors")
+    e = 4 if shape[1] == "torch.float32" else 2
+    return tensors, shape[0], PLANE_ELEMENTS[shape[1]], shape[2] * e, shape[3] * e
+
+
+def _plane_constants(scale, bias, channels):
+    """scale (default 1/255) and bias (default 0) per channel, through numpy.float32: two C float arrays"""
+    import numpy as np
+    scale = [1.0 / 255.0] * channels if scale is None else list(scale)
+    bias = [0.0] * channels if bias is None else list(bias)
+    if len(scale) != channels or len(bias) != channels:
+        raise ValueError("scale and bias: one value per channel")
+    return ((C.c_float * channels)(*[float(np.float32(v)) for v in scale]),
+            (C.c_float * channels)(*[float(np.float32(v)) for v in bias]))
+
+
 def _addr_len(buf):
     """(address, nbytes, keepalive) of a host or device buffer."""
     if buf is None:
@@ -381,6 +433,20 @@ class Context:
             return r, (C.string_at(oa, row_bytes * rows) if r == 0 else None)
         return r, None
 
+    def decompress_planes(self, texture, texture_format, width, height, out, scale_log2=0, scale=None, bias=None,
+                          alpha=None):
+        """Texture (+ optional RGTC1 alpha plane) -> `out`, a (C, height >> scale_log2, width >> scale_log2) float16,
+        bfloat16 or float32 torch tensor on the device, C 3 or 4: element = float32(byte) * scale[c] + bias[c] (two
+        roundings), the byte being decompress_rgba[_scaled]'s (HapGpuDecompressPlanes).  channels, element, planeBytes and
+        rowBytes are read from the tensor, so a slice with longer rows or planes is accepted; stride(-1) must be 1.
+        scale defaults to 1/255 per channel, bias to 0.  Returns the result."""
+        tensors, channels, element, plane_bytes, row_bytes = _plane_tensors(out, True, width, height, scale_log2)
+        sc, bi = _plane_constants(scale, bias, channels)
+        ta, tn, _k = _addr_len(texture)
+        aa, an, _k2 = _addr_len(alpha) if alpha is not None else (None, 0, None)
+        return lib.HapGpuDecompressPlanes(self.handle, ta, tn, texture_format, aa, an, width, height, scale_log2, channels,
+                                          element, tensors[0].data_ptr(), plane_bytes, row_bytes, sc, bi)
+
     def decompress_rgba_region(self, texture, texture_format, width, height, region, rgba=None, alpha=None,
                                row_bytes=None):
         """Texture (+ optional RGTC1 alpha plane) -> the RGBA8 picture of region = (x, y, w, h), a block-aligned rectangle
@@ -616,6 +682,27 @@ class Context:
         shift = scale_log2 if 0 < scale_log2 < 3 else 0
         r = lib.HapGpuDecodeFramesRGBAScaled(self.handle, nf, ptrs, lens, texture_count, optrs, width, height, scale_log2,
                                              row_bytes or (width >> shift) * 4, results, flags)
+        return r, list(results)
+
+    def decode_frames_planes(self, frames, frame_bytes, texture_count, out, width, height, scale_log2=0, scale=None,
+                             bias=None, flags=0):
+        """Frames -> normalised planar tensors in one call, without RGBA8 pictures in between (HapGpuDecodeFramesPlanes).
+        `out`: one (N, C, height >> scale_log2, width >> scale_log2) torch tensor on the device or a list of N
+        (C, H, W) ones that share their strides (None: no tensor for that frame), float16, bfloat16 or float32, C 3 or 4;
+        channels, element, planeBytes and rowBytes are read from it, stride(-1) must be 1.  element = float32(byte) *
+        scale[c] + bias[c] (two roundings), the byte being decode_frames_rgba[_scaled]'s; scale defaults to 1/255 per
+        channel, bias to 0.  Returns (result, results[])."""
+        nf = len(frames)
+        tensors, channels, element, plane_bytes, row_bytes = _plane_tensors(out, False, width, height, scale_log2)
+        if len(tensors) != nf:
+            raise ValueError("one tensor per frame")
+        sc, bi = _plane_constants(scale, bias, channels)
+        ptrs, infos = self._ptr_array(frames)
+        lens = (C.c_ulong * nf)(*[fb if fb is not None else infos[i][1] for i, fb in enumerate(frame_bytes)])
+        optrs = (C.c_void_p * nf)(*[None if t is None else t.data_ptr() for t in tensors])
+        results = (C.c_uint * nf)()
+        r = lib.HapGpuDecodeFramesPlanes(self.handle, nf, ptrs, lens, texture_count, optrs, width, height, scale_log2,
+                                         channels, element, plane_bytes, row_bytes, sc, bi, results, flags)
         return r, list(results)
 
     def transcode_texture(self, texture, texture_format, width, height, scale_log2, output_formats, alpha=None,

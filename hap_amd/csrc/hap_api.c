@@ -570,6 +570,32 @@ unsigned int HapGpuDecompressRGBAScaled(HapGpuContext *context, const void *text
     return r;
 }
 
+/* 1: what the planar calls take of scaleLog2, channels, element, scale and bias */
+static int planes_arguments_valid(unsigned scaleLog2, unsigned channels, unsigned element, const float *scale,
+                                  const float *bias)
+{
+    return scaleLog2 <= 2u && channels >= 3u && channels <= 4u && element <= HapGpuPlaneElement_F32 && scale && bias;
+}
+
+/* one texture -> one planar float tensor in device memory */
+unsigned int HapGpuDecompressPlanes(HapGpuContext *context, const void *texture, unsigned long textureBytes,
+                                    unsigned int textureFormat, const void *alphaTexture,
+                                    unsigned long alphaTextureBytes, unsigned int width, unsigned int height,
+                                    unsigned int scaleLog2, unsigned int channels, unsigned int element, void *planes,
+                                    unsigned long planeBytes, unsigned long rowBytes, const float *scale,
+                                    const float *bias)
+{
+    const HapbPlanes layout = {channels, element, planeBytes, scale, bias};
+    unsigned r;
+    if (!context || !planes_arguments_valid(scaleLog2, channels, element, scale, bias))
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_decompress_planes(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width,
+                               height, scaleLog2, planes, rowBytes, &layout);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
 unsigned int HapGpuDecompressRGBAHalf(HapGpuContext *context, const void *texture, unsigned long textureBytes,
                                       unsigned int textureFormat, unsigned int width, unsigned int height,
                                       void *rgbaHalf, unsigned long rowBytes)
@@ -986,6 +1012,31 @@ unsigned int HapGpuDecodeFramesRGBAScaled(HapGpuContext *context, unsigned int f
     hapgpu_rt_lock(context->rt);
     r = hapb_decode_rgba(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, rgbaFrames, width, height,
                          scaleLog2, rowBytes, results, flags);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+/* frames -> planar float tensors in device memory; arguments outside the rules refuse the whole call */
+unsigned int HapGpuDecodeFramesPlanes(HapGpuContext *context, unsigned int frameCount,
+                                      const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
+                                      unsigned int textureCount, void *const *planeFrames, unsigned int width,
+                                      unsigned int height, unsigned int scaleLog2, unsigned int channels,
+                                      unsigned int element, unsigned long planeBytes, unsigned long rowBytes,
+                                      const float *scale, const float *bias, unsigned int *results, unsigned int flags)
+{
+    const HapbPlanes layout = {channels, element, planeBytes, scale, bias};
+    unsigned r, f;
+    if (!context)
+        return HapResult_Bad_Arguments;
+    if (!planes_arguments_valid(scaleLog2, channels, element, scale, bias)) {
+        for (f = 0; results && f < frameCount; f++)
+            results[f] = HapResult_Bad_Arguments;
+        return HapResult_Bad_Arguments;
+    }
+    hapgpu_rt_lock(context->rt);
+    /* (Hap R frames are out of scope with or without the flag that asks for their pictures: the road has no BC7) */
+    r = hapb_decode_planes(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, planeFrames, width, height,
+                           scaleLog2, rowBytes, &layout, results, flags);
     hapgpu_rt_unlock(context->rt);
     return r;
 }

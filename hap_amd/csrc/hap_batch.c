@@ -825,6 +825,9 @@ typedef struct picture_road {
                                    (width >> scale_log2) x (height >> scale_log2), by hapgpu_k_block_decode_scaled */
     const HapGpuRegion *region; /* NULL: the whole of every texture; else (RGBA8 only, scale_log2 0) pictures of region->w x
                                    region->h, that rectangle of every texture, by hapgpu_k_block_decode_region */
+    const HapbPlanes *planes;   /* NULL: interleaved pictures of picture_kind; else planar tensors in device memory
+                                   (scale_log2 0 to 2, no region), by hapgpu_k_block_decode_planes: a "texel" is then one
+                                   element of one plane and row_bytes the pitch of a plane's rows */
 } picture_road;
 
 /* RGBA8 pictures (BC7 last: frames of it only with HAPGPU_DECODE_BPTC_PICTURES), RGBA16F ones and A8 ones */
@@ -836,11 +839,25 @@ static const unsigned k_alpha_kinds[1] = {HapTextureFormat_A_RGTC1};
 static picture_road road_of(unsigned picture_kind, unsigned flags, unsigned scale_log2, const HapGpuRegion *region)
 {
     if (picture_kind == HAPGPU_PICTURE_RGBA16F)
-        return (picture_road){2u, k_half_kinds, 0u, picture_kind, 0u, NULL};
+        return (picture_road){2u, k_half_kinds, 0u, picture_kind, 0u, NULL, NULL};
     if (picture_kind == HAPGPU_PICTURE_A8)
-        return (picture_road){1u, k_alpha_kinds, 0u, picture_kind, 0u, NULL};
+        return (picture_road){1u, k_alpha_kinds, 0u, picture_kind, 0u, NULL, NULL};
     return (picture_road){(flags & HAPGPU_DECODE_BPTC_PICTURES) ? 4u : 3u, k_rgba_kinds, 0x7u, picture_kind,
-                          region ? 0u : scale_log2, region};
+                          region ? 0u : scale_log2, region, NULL};
+}
+
+/* ... and to planar tensors: the RGBA8 road's DXT formats (never BC7) at any of the three sizes */
+static picture_road planes_road_of(unsigned scale_log2, const HapbPlanes *planes)
+{
+    return (picture_road){3u, k_rgba_kinds, 0x7u, HAPGPU_PICTURE_RGBA8, scale_log2, NULL, planes};
+}
+
+/* bytes of what a road's row_bytes counts: a texel of an interleaved picture, an element of a plane */
+static size_t picture_texel_bytes(const picture_road *road)
+{
+    if (road->planes)
+        return road->planes->element == HapGpuPlaneElement_F32 ? 4u : 2u;
+    return HAPGPU_PICTURE_TEXEL_BYTES(road->picture_kind);
 }
 
 /* the geometry of a road's pictures, from the textures' */
@@ -863,18 +880,35 @@ int hapb_region_fits(const HapGpuRegion *region, unsigned height)
 
 /* what the block decoders ask of a picture's address (in device memory) and row pitch when they write it: 16-byte
    stores for RGBA8 and RGBA16F; A8 pictures take dword stores, and 16-byte ones where address and pitch allow; a scaled
-   picture takes the 16 >> scale_log2 bytes a lane has for each of its rows */
+   picture takes the 16 >> scale_log2 bytes a lane has for each of its rows, a plane its 4 >> scale_log2 elements */
 static unsigned picture_align_mask(const picture_road *road)
 {
+    if (road->planes)
+        return (4u >> road->scale_log2) * (unsigned)picture_texel_bytes(road) - 1u;
     if (road->scale_log2)
         return (16u >> road->scale_log2) - 1u;
     return road->picture_kind == HAPGPU_PICTURE_A8 ? 3u : 15u;
 }
 
-/* the block-decode launch of a road: pictures of the frames' size, scaled ones, or a rectangle's */
+/* 1: a planar road's tensors are what the calls take (include/hap_gpu.h: HapGpuDecompressPlanes) -- planes that hold
+   their rows and, like the rows, keep every lane's store aligned; pixel_row: the bytes of one row of a plane */
+static int planes_fit(const picture_road *road, size_t pixel_row, unsigned picture_height, unsigned long row_bytes)
+{
+    const HapbPlanes *p = road->planes;
+    return p->channels >= 3u && p->channels <= 4u && p->element <= HapGpuPlaneElement_F32 && road->scale_log2 <= 2u &&
+           p->scale && p->bias && picture_height && !(p->plane_bytes & picture_align_mask(road)) &&
+           p->plane_bytes >= (size_t)row_bytes * (picture_height - 1u) + pixel_row;
+}
+
+/* the block-decode launch of a road: pictures of the frames' size, scaled ones, a rectangle's, or planar tensors (the
+   alpha plane is read only where a fourth plane is written) */
 static int launch_block_decode(hapgpu_rt *rt, const picture_road *road, const HapGpuPictureTable *t, unsigned pictures,
                                int with_alpha, unsigned width, unsigned height, unsigned format, size_t row_bytes, int wide)
 {
+    if (road->planes)
+        return hapgpu_k_block_decode_planes(rt, t, pictures, with_alpha && road->planes->channels == 4u, width, height, format,
+                                            road->scale_log2, road->planes->channels, road->planes->element,
+                                            road->planes->plane_bytes, row_bytes, road->planes->scale, road->planes->bias);
     if (road->region)
         return hapgpu_k_block_decode_region(rt, t, pictures, with_alpha, width, height, format, road->region->x, road->region->y,
                                             road->region->w, road->region->h, row_bytes);
@@ -883,18 +917,19 @@ static int launch_block_decode(hapgpu_rt *rt, const picture_road *road, const Ha
     return hapgpu_k_block_decode(rt, t, pictures, with_alpha, width, height, format, row_bytes, wide, road->picture_kind);
 }
 
-unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
-                              const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                              void *picture, unsigned long row_bytes, unsigned picture_kind, unsigned scale_log2,
-                              const HapGpuRegion *region)
+/* one texture (+ RGTC1 alpha plane) down a road: to one picture, or to one planar tensor */
+static unsigned decompress_picture(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
+                                   const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
+                                   void *picture, unsigned long row_bytes, const picture_road *const proad)
 {
-    const picture_road road = road_of(picture_kind, HAPGPU_DECODE_BPTC_PICTURES, scale_log2, region);
+    const picture_road road = *proad;
+    const unsigned picture_kind = road.picture_kind;
     const unsigned align = picture_align_mask(&road);
     hapgpu_rt *rt = ctx->rt;
     /* (the picture's geometry: the texture's, a scaled road's fraction of it, or the rectangle's) */
     const unsigned picture_height = picture_height_of(&road, height);
     const size_t block = hapf_block_bytes(format),
-                 pixel_row = (size_t)picture_width_of(&road, width) * HAPGPU_PICTURE_TEXEL_BYTES(picture_kind);
+                 pixel_row = (size_t)picture_width_of(&road, width) * picture_texel_bytes(&road);
     HapGpuPictureTable t = {{NULL, NULL, NULL}, {0u, 0u, 0u}};
     size_t need, alpha_need, picture_bytes;
     const void *src = texture, *asrc = alpha;
@@ -907,7 +942,9 @@ unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned 
         ;
     if (!texture || !picture || width == 0 || height == 0 || (width & 3u) || (height & 3u) || row_bytes < pixel_row ||
         (road.region && (road.region->width != width || !hapb_region_fits(road.region, height))) ||
-        k == road.kind_count || (alpha && !(road.paired_kinds >> k & 1u)))
+        k == road.kind_count || (alpha && !(road.paired_kinds >> k & 1u)) ||
+        /* (tensors live in device memory: no host staging road) */
+        (road.planes && (!planes_fit(&road, pixel_row, picture_height, row_bytes) || !is_dev(ctx, picture))))
         return HapResult_Bad_Arguments;
     need = (size_t)(width / 4u) * (height / 4u) * block;
     alpha_need = (size_t)(width / 4u) * (height / 4u) * 8u;
@@ -960,6 +997,25 @@ unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned 
     if (hapgpu_rt_sync(rt))
         return HapResult_Internal_Error;
     return HapResult_No_Error;
+}
+
+unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
+                              const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
+                              void *picture, unsigned long row_bytes, unsigned picture_kind, unsigned scale_log2,
+                              const HapGpuRegion *region)
+{
+    const picture_road road = road_of(picture_kind, HAPGPU_DECODE_BPTC_PICTURES, scale_log2, region);
+    return decompress_picture(ctx, texture, texture_bytes, format, alpha, alpha_bytes, width, height, picture, row_bytes,
+                              &road);
+}
+
+unsigned hapb_decompress_planes(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
+                                const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
+                                unsigned scale_log2, void *tensor, unsigned long row_bytes, const HapbPlanes *planes)
+{
+    const picture_road road = planes_road_of(scale_log2, planes);
+    return decompress_picture(ctx, texture, texture_bytes, format, alpha, alpha_bytes, width, height, tensor, row_bytes,
+                              &road);
 }
 
 unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
@@ -1966,7 +2022,7 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
     unsigned *idx, *fmts, *res;
     /* (the pictures' geometry: the frames', a scaled road's fraction of it, or the rectangle's) */
     const unsigned picture_height = picture_height_of(road, height);
-    const size_t pixel_row = (size_t)picture_width_of(road, width) * HAPGPU_PICTURE_TEXEL_BYTES(road->picture_kind);
+    const size_t pixel_row = (size_t)picture_width_of(road, width) * picture_texel_bytes(road);
     /* (a rectangle that is the whole frame skips nothing) */
     const HapGpuRegion *const skip_region = road->region && !(road->region->x == 0u && road->region->y == 0u &&
                                                               road->region->w == width && road->region->h == height)
@@ -1981,6 +2037,7 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
     if (!inputs || !input_bytes || !rgba_frames || texture_count == 0 || texture_count > 2 || width == 0 ||
         height == 0 || (width & 3u) || (height & 3u) || row_bytes < pixel_row || (row_bytes & align) ||
         (road->region && (road->region->width != width || !hapb_region_fits(road->region, height))) ||
+        (road->planes && !planes_fit(road, pixel_row, picture_height, row_bytes)) ||
         (road->picture_kind == HAPGPU_PICTURE_A8 && height / 4u > 65535u)) {
         for (f = 0; f < frame_count; f++)
             results[f] = HapResult_Bad_Arguments;
@@ -2075,7 +2132,9 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
                      used[e] != blocks * hapf_block_bytes(fmt) ||
                      (texture_count == 2 && (fmts[e + 1] != HapTextureFormat_A_RGTC1 || used[e + 1] != blocks * 8u))))
                     r = HapResult_Bad_Arguments;
-                if (r == HapResult_No_Error && !is_dev(ctx, dst)) {
+                if (r == HapResult_No_Error && road->planes && !is_dev(ctx, dst)) {
+                    r = HapResult_Bad_Arguments;        /* tensors live in device memory: no host staging road */
+                } else if (r == HapResult_No_Error && !is_dev(ctx, dst)) {
                     if (!stage)
                         stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_RGBA_STAGE, align_up(rgba_bytes, 256) * n);
                     dst = stage ? stage + align_up(rgba_bytes, 256) * f : NULL;
@@ -2147,6 +2206,18 @@ unsigned hapb_decode_rgba_region(HapGpuContext *ctx, unsigned frame_count, const
 {
     const picture_road road = road_of(HAPGPU_PICTURE_RGBA8, flags, 0u, region);
     return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, rgba_frames, width, height, row_bytes,
+                           results, flags, &road);
+}
+
+/* ... and to planar tensors, `planes->channels` planes each: the same road with the layout and the launch of
+   bc_decode_planes.hip */
+unsigned hapb_decode_planes(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                            const unsigned long *input_bytes, unsigned texture_count, void *const *tensors,
+                            unsigned width, unsigned height, unsigned scale_log2, unsigned long row_bytes,
+                            const HapbPlanes *planes, unsigned *results, unsigned flags)
+{
+    const picture_road road = planes_road_of(scale_log2, planes);
+    return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, tensors, width, height, row_bytes,
                            results, flags, &road);
 }
 

@@ -108,6 +108,19 @@ unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned 
                               const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
                               void *picture, unsigned long row_bytes, unsigned picture_kind, unsigned scale_log2,
                               const HapGpuRegion *region);
+/* The tensors of the planar roads (include/hap_gpu.h: HapGpuDecompressPlanes, HapGpuDecodeFramesPlanes): what one
+   call's tensors share.  Their rows are the calls' row_bytes apart. */
+typedef struct HapbPlanes {
+    unsigned channels;              /* planes of a tensor: 3 (R, G, B) or 4 (+ A) */
+    unsigned element;               /* HapGpuPlaneElement */
+    unsigned long plane_bytes;      /* from one plane of a tensor to the next */
+    const float *scale, *bias;      /* `channels` floats each: element = (float)byte * scale[c] + bias[c], two roundings */
+} HapbPlanes;
+/* one texture (host or device) -> one planar tensor in device memory of (width >> scale_log2) x (height >> scale_log2),
+   scale_log2 0 to 2: DXT1, DXT5, YCoCg-DXT5 with an optional RGTC1 alpha plane */
+unsigned hapb_decompress_planes(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
+                                const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
+                                unsigned scale_log2, void *tensor, unsigned long row_bytes, const HapbPlanes *planes);
 /* 1: region is a block-aligned, non-empty rectangle inside region->width x height */
 int hapb_region_fits(const HapGpuRegion *region, unsigned height);
 /* pictures -> frames.  picture_kind RGBA8: the DXT / RGTC1 formats (BC7 with HAPGPU_ENCODE_BPTC_BLOCKS); RGBA16F (rows
@@ -137,6 +150,11 @@ unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                           const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
                           unsigned width, unsigned height, unsigned scale_log2, unsigned long row_bytes,
                           unsigned *results, unsigned flags);
+/* ... to planar tensors in device memory (scale_log2 0 to 2), without an RGBA8 picture in between */
+unsigned hapb_decode_planes(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                            const unsigned long *input_bytes, unsigned texture_count, void *const *tensors,
+                            unsigned width, unsigned height, unsigned scale_log2, unsigned long row_bytes,
+                            const HapbPlanes *planes, unsigned *results, unsigned flags);
 /* ... a rectangle of every frame (region->width == width) to RGBA8 pictures of region->w x region->h */
 unsigned hapb_decode_rgba_region(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
                                  const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,

@@ -344,6 +344,20 @@ int hapgpu_k_block_decode_scaled(hapgpu_rt *rt, const HapGpuPictureTable *table,
 int hapgpu_k_block_decode_region(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, int with_alpha,
                                  unsigned width, unsigned height, unsigned hap_texture_format, unsigned x, unsigned y,
                                  unsigned region_width, unsigned region_height, size_t row_bytes);
+/* ... to planar tensors of (width >> scale_log2) x (height >> scale_log2), scale_log2 0 to 2, without an RGBA8 picture in
+   between (bc_decode_planes.hip): `channels` (3 or 4: R, G, B[, A]) planes plane_bytes apart, rows row_bytes apart,
+   elements of element_kind (0 half, 1 bfloat16, 2 float: e = 2, 2, 4 bytes).  For the byte v that
+   hapgpu_k_block_decode (scale_log2 0) or hapgpu_k_block_decode_scaled writes for a texel and channel c, the element is
+   (float)v * scale[c] (one binary32 multiply) + bias[c] (one binary32 add, not fused), rounded to nearest even to the
+   element kind, subnormal halves kept.  scale and bias: `channels` floats each, in host memory, copied by the call.
+   RGB_DXT1, RGBA_DXT5 and YCoCg_DXT5 (with_alpha: the RGTC1 plane supplies A).  Tensors (the third column of the table),
+   plane_bytes and row_bytes aligned to the (4 >> scale_log2) * e bytes a lane stores per row; row_bytes at least
+   (width >> scale_log2) * e, plane_bytes at least row_bytes * ((height >> scale_log2) - 1) + (width >> scale_log2) * e.
+   The same table, profile class and return codes. */
+int hapgpu_k_block_decode_planes(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, int with_alpha,
+                                 unsigned width, unsigned height, unsigned hap_texture_format, unsigned scale_log2,
+                                 unsigned channels, unsigned element_kind, size_t plane_bytes, size_t row_bytes,
+                                 const float *scale, const float *bias);
 /* [device] Addresses of a transcode launch, as HapGpuPictureTable's: source textures, source alpha planes, destination
    textures, destination alpha planes (Hap Q Alpha's second texture). */
 typedef struct HapGpuTranscodeTable {

@@ -222,6 +222,38 @@ unsigned int HapGpuDecompressRGBAScaled(HapGpuContext *context,
                                         unsigned int width, unsigned int height, unsigned int scaleLog2,
                                         void *rgba, unsigned long rowBytes);
 
+/* What the elements of a planar tensor are (HapGpuDecompressPlanes, HapGpuDecodeFramesPlanes): 2, 2 and 4 bytes */
+enum HapGpuPlaneElement { HapGpuPlaneElement_F16 = 0, HapGpuPlaneElement_BF16 = 1, HapGpuPlaneElement_F32 = 2 };
+
+/* The same texture -> one planar float tensor in DEVICE memory, for a consumer that is a model, a filter or an analysis
+ * pass: `channels` planes (3: R, G, B; 4: R, G, B, A) of (width >> scaleLog2) x (height >> scaleLog2) elements, planes
+ * planeBytes apart, rows rowBytes apart, scaled and shifted per channel -- made by the block decoder itself, no RGBA8
+ * picture is written or read back.
+ * The definition.  Let v be the byte that HapGpuDecompressRGBA (scaleLog2 0) or HapGpuDecompressRGBAScaled (1, 2) writes
+ * for a texel and channel c.  The element is
+ *     t = (float)v * scale[c]     one IEEE binary32 multiply, round to nearest even
+ *     r = t + bias[c]             one IEEE binary32 add, round to nearest even: NOT a fused multiply-add
+ * and then r itself (F32), r rounded to nearest even to half (F16; subnormal halves are kept, not flushed) or to
+ * bfloat16 (BF16): numpy's v.astype(float32) * float32(s) + float32(b), then .astype(float16).  scale and bias point to
+ * `channels` finite floats each, which the call does not check.  With channels 3 alpha is not written and the alpha
+ * plane, if given, is not read.
+ * width and height are the TEXTURE's, multiples of 4; scaleLog2 0 to 2; textures (host or device), formats and the alpha
+ * plane as for HapGpuDecompressRGBA, without BC7.  Alignment: with n = 4 >> scaleLog2 elements a lane stores per row and
+ * e the element's size, rowBytes, planeBytes and the tensor's address are multiples of n * e; rowBytes is at least
+ * (width >> scaleLog2) * e and planeBytes at least rowBytes * ((height >> scaleLog2) - 1) + (width >> scaleLog2) * e (a
+ * slice of a larger tensor, with longer rows and planes, qualifies).  Only the elements are written, nothing between
+ * rows or planes.  Bad_Arguments, and nothing written, for anything else: a NULL, host or misaligned tensor, channels
+ * other than 3 or 4, an element or scaleLog2 outside the above, a NULL scale or bias.
+ * Out of scope: RGBA_BPTC_UNORM (BC7), the BC6H formats and a lone A_RGTC1 as sources (Bad_Arguments), rectangles, host
+ * tensors, and the way back (encoding from planar float tensors). */
+unsigned int HapGpuDecompressPlanes(HapGpuContext *context,
+                                    const void *texture, unsigned long textureBytes, unsigned int textureFormat,
+                                    const void *alphaTexture, unsigned long alphaTextureBytes,
+                                    unsigned int width, unsigned int height, unsigned int scaleLog2,
+                                    unsigned int channels, unsigned int element,
+                                    void *planes, unsigned long planeBytes, unsigned long rowBytes,
+                                    const float *scale, const float *bias);
+
 /* The same texture -> the RGBA8 picture of one block-aligned rectangle of it, regionWidth x regionHeight: byte for byte
  * the crop of what HapGpuDecompressRGBA writes, from the rectangle's blocks alone (no other block of the texture or of
  * the alpha plane is read).  width and height are the TEXTURE's.  regionX, regionY, regionWidth and regionHeight are
@@ -544,6 +576,39 @@ unsigned int HapGpuDecodeFramesRGBAScaled(HapGpuContext *context, unsigned int f
                                           unsigned long rowBytes,
                                           unsigned int *results,
                                           unsigned int flags);
+
+/* Frames in, normalised planar float tensors out: HapGpuDecodeFramesRGBA with the tensors of HapGpuDecompressPlanes in
+ * place of pictures -- planeFrames[f] is frame f's tensor in DEVICE memory, `channels` planes of
+ * (width >> scaleLog2) x (height >> scaleLog2) elements, planeBytes and rowBytes shared by all frames (one N x C x H x W
+ * tensor: planeFrames[f] = base + f * channels * planeBytes).  The definition is HapGpuDecompressPlanes': for the byte v
+ * that HapGpuDecodeFramesRGBA (scaleLog2 0) or HapGpuDecodeFramesRGBAScaled (1, 2) writes for the frame at that texel
+ * and channel c, with the same textureCount and flags, one binary32 multiply by scale[c], then one binary32 add of
+ * bias[c] (two roundings, not fused), then the rounding to the element.  No RGBA8 picture ever exists: per Hap Q block
+ * 16 bytes are read and 96 written for three half planes, where decoding to RGBA8 and converting moves 16 + 64 + 64 + 96.
+ * width and height are the FRAMES', multiples of 4; scaleLog2 0 to 2; channels 3 or 4 (with 3 alpha is not written, and a
+ * Hap Q Alpha frame read with textureCount 1 is its colour texture alone); scale and bias point to `channels` floats;
+ * alignment as for HapGpuDecompressPlanes.  textureCount, flags, mixed batches (one block-decode launch per texture
+ * format present), slicing and results[f] are HapGpuDecodeFramesRGBA's: a broken frame gets HapDecode's code; a frame of
+ * another format or geometry, or one whose tensor is NULL, in host memory or misaligned, is Bad_Arguments alone, its
+ * memory untouched, and the other frames are decoded.  The function's result is the first failure.
+ * Bad_Arguments for the whole call -- every results[f] set, nothing written -- for a NULL array, a width or height that
+ * is no multiple of 4, channels other than 3 or 4, an element or scaleLog2 outside the above, a rowBytes or planeBytes
+ * that breaks the alignment rule or is too short.  A context between HapGpuEncodeFramesRGBABegin and
+ * HapGpuEncodeFramesFinish: Internal_Error.
+ * Out of scope: Hap R (BC7), Hap HDR (BC6H) and Hap Alpha-Only (a lone A_RGTC1) frames -- Bad_Arguments alone, with or
+ * without HAPGPU_DECODE_BPTC_PICTURES --, rectangles, host tensors, ...OnDevices and ...Sequence forms of this call, and
+ * the way back: encoding from planar float tensors. */
+unsigned int HapGpuDecodeFramesPlanes(HapGpuContext *context, unsigned int frameCount,
+                                      const void *const *inputBuffers,
+                                      const unsigned long *inputBuffersBytes,
+                                      unsigned int textureCount,
+                                      void *const *planeFrames,
+                                      unsigned int width, unsigned int height, unsigned int scaleLog2,
+                                      unsigned int channels, unsigned int element,
+                                      unsigned long planeBytes, unsigned long rowBytes,
+                                      const float *scale, const float *bias,
+                                      unsigned int *results,
+                                      unsigned int flags);
 
 /* Hap HDR frames in, RGBA16F pictures out: HapGpuDecodeFramesRGBA for frames of one BC6H texture (unsigned or
  * signed; a batch may mix the two: one block-decode launch per signedness present), pictures as
