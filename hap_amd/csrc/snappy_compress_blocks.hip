@@ -62,6 +62,9 @@ template <> struct unit_layout<4u> {
     __device__ static constexpr unsigned fo(unsigned k) { return k == 0u ? 0u : k == 1u ? 2u : k == 2u ? 8u : 12u; }
     __device__ static constexpr unsigned fs(unsigned k) { return k == 0u ? 2u : k == 1u ? 6u : 4u; }
     __device__ static constexpr unsigned cls(unsigned k) { return k == 1u ? 1u : k == 3u ? 3u : 0u; }
+    // byte at which field q of a half-tile begins, q = 0..32: 16 (q / 4) + fo(q % 4) without a table -- four bytes a
+    // field, less two for the fields behind a 2-byte one
+    __device__ static unsigned pos(unsigned q) { const unsigned t = q << 1; return (t << 1) - (t & ~q & 2u); }
 };
 template <> struct unit_layout<2u> {
     static constexpr unsigned block = 8u, code = 10u;
@@ -69,6 +72,7 @@ template <> struct unit_layout<2u> {
     __device__ static constexpr unsigned fo(unsigned k) { return 4u * k; }
     __device__ static constexpr unsigned fs(unsigned) { return 4u; }
     __device__ static constexpr unsigned cls(unsigned k) { return (k & 1u) ? 1u : 0u; }
+    __device__ static unsigned pos(unsigned q) { return 4u * q; }
 };
 template <> struct unit_layout<8u> {     // opaque 16-byte blocks (BC7, BC6H): four dwords, distances in whole blocks
     static constexpr unsigned block = 16u, code = 12u;
@@ -76,6 +80,7 @@ template <> struct unit_layout<8u> {     // opaque 16-byte blocks (BC7, BC6H): f
     __device__ static constexpr unsigned fo(unsigned k) { return 4u * k; }
     __device__ static constexpr unsigned fs(unsigned) { return 4u; }
     __device__ static constexpr unsigned cls(unsigned k) { return k == 1u ? 1u : k == 3u ? 3u : 0u; }
+    __device__ static unsigned pos(unsigned q) { return 4u * q; }
 };
 template <> struct unit_layout<6u> {
     static constexpr unsigned block = 8u, code = 2u;
@@ -84,6 +89,7 @@ template <> struct unit_layout<6u> {
     __device__ static constexpr unsigned fo(unsigned k) { return k == 0u ? 0u : k == 1u ? 2u : k == 2u ? 8u : 10u; }
     __device__ static constexpr unsigned fs(unsigned k) { return (k & 1u) ? 6u : 2u; }
     __device__ static constexpr unsigned cls(unsigned k) { return (k & 1u) ? 1u : 0u; }
+    __device__ static unsigned pos(unsigned q) { return 4u * q - 2u * (q & 1u); }
 };
 
 // memory accesses at any byte address (the fragment of a client's texture may begin anywhere), in the global address
@@ -122,13 +128,17 @@ __device__ __forceinline__ uint2 get64(gsrc_t p)
 __device__ __forceinline__ unsigned rotr(unsigned v, unsigned n) { return __builtin_amdgcn_alignbit(v, v, n); }
 __device__ __forceinline__ unsigned bfi(unsigned mask, unsigned a, unsigned b) { return (a & mask) | (b & ~mask); }
 __device__ __forceinline__ unsigned popc(unsigned v) { return (unsigned)__builtin_popcount(v); }
-// 0 -> 0, anything else -> 1 (kept out of the compiler's hands: it turns min(x, 1) into a compare and a select
-// through a scalar register pair, two instructions and wait states instead of one)
-__device__ __forceinline__ unsigned nonzero(unsigned v)
+// Stream bytes of the fields of a half-tile selected by `under` (a prefix), from its masks: a literal field's own
+// bytes -- 2, 6 or 4: twice (1 + not small + big) -- and per element start one byte, one more for a copy, one more
+// where X3 says so.  Sums of popcounts only (v_bcnt adds on the way), one shift.
+template <class UL>
+__device__ __forceinline__ unsigned bytes_under(unsigned S, unsigned L, unsigned X3, unsigned under, unsigned base)
 {
-    unsigned r;
-    asm("v_min_u32 %0, 1, %1" : "=v"(r) : "v"(v));
-    return r;
+    const unsigned Lu = L & under;
+    unsigned lit = popc(Lu) + popc(Lu & ~UL::small32);
+    if (UL::big32 != 0u)
+        lit += popc(Lu & UL::big32);
+    return (base + popc(S & under) + popc(S & ~L & under) + popc(X3 & under)) + 2u * lit;
 }
 // all ones if bit `bit` of v is set, else 0
 __device__ __forceinline__ unsigned bit_mask(unsigned v, unsigned bit) { return (unsigned)__builtin_amdgcn_sbfe((int)v, bit, 1u); }
@@ -154,24 +164,46 @@ __device__ __forceinline__ unsigned lane_xor4(unsigned v)
 __device__ __forceinline__ unsigned lane_xor2(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false); }
 __device__ __forceinline__ unsigned lane_xor1(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false); }
 
-// 1 where the field differs, per field of the unit, shifted to nibble `d`, OR-ed into acc
-template <unsigned LAYOUT>
-__device__ __forceinline__ unsigned differ_nibble(unsigned acc, const uint4 x, const uint4 y, unsigned d)
+// lane masks of "differs": whole dwords, their low halves, their high halves (kept out of the compiler's hands: it
+// forms the difference, masks it and compares with zero)
+typedef unsigned long long lanes_t;
+__device__ __forceinline__ lanes_t ne32(unsigned a, unsigned b) { return __builtin_amdgcn_uicmp(a, b, 33); }
+__device__ __forceinline__ lanes_t ne_lo16(unsigned a, unsigned b)
 {
-    const unsigned d0 = x.x ^ y.x, d1 = x.y ^ y.y, d2 = x.z ^ y.z, d3 = x.w ^ y.w;
-    unsigned t0, t1, t2, t3;
-    if (LAYOUT == 4u) {
-        t0 = d0 & 0xFFFFu; t1 = (d0 & 0xFFFF0000u) | d1; t2 = d2; t3 = d3;
-    } else if (LAYOUT == 2u || LAYOUT == 8u) {
-        t0 = d0; t1 = d1; t2 = d2; t3 = d3;
-    } else {
-        t0 = d0 & 0xFFFFu; t1 = (d0 & 0xFFFF0000u) | d1; t2 = d2 & 0xFFFFu; t3 = (d2 & 0xFFFF0000u) | d3;
-    }
-    acc |= nonzero(t0) << (4u * d);
-    acc |= nonzero(t1) << (4u * d + 1u);
-    acc |= nonzero(t2) << (4u * d + 2u);
-    acc |= nonzero(t3) << (4u * d + 3u);
+    lanes_t m;
+    asm("v_cmp_ne_u32_sdwa %0, %1, %2 src0_sel:WORD_0 src1_sel:WORD_0" : "=s"(m) : "v"(a), "v"(b));
+    return m;
+}
+__device__ __forceinline__ lanes_t ne_hi16(unsigned a, unsigned b)
+{
+    lanes_t m;
+    asm("v_cmp_ne_u32_sdwa %0, %1, %2 src0_sel:WORD_1 src1_sel:WORD_1" : "=s"(m) : "v"(a), "v"(b));
+    return m;
+}
+// acc + acc + the lane's bit of m: one add with carry shifts a compare's result in from below (the compiler turns
+// acc + acc + (a != b) into a select, a shift and an or)
+__device__ __forceinline__ unsigned shift_in(unsigned acc, lanes_t m)
+{
+    asm("v_addc_co_u32_e64 %0, %1, %0, %0, %1" : "+v"(acc), "+s"(m));
     return acc;
+}
+
+// 1 where the field differs, per field of the unit: four bits shifted into acc from below, field 3 first (the caller
+// goes from the farthest distance to the nearest, so distance d ends up in nibble d) -- a compare and an add with
+// carry per bit, without forming the difference.
+template <unsigned LAYOUT>
+__device__ __forceinline__ unsigned differ_nibble(unsigned acc, const uint4 x, const uint4 y)
+{
+    lanes_t n0, n1, n2, n3;
+    if (LAYOUT == 4u) {
+        n0 = ne_lo16(x.x, y.x); n1 = ne_hi16(x.x, y.x) | ne32(x.y, y.y); n2 = ne32(x.z, y.z); n3 = ne32(x.w, y.w);
+    } else if (LAYOUT == 2u || LAYOUT == 8u) {
+        n0 = ne32(x.x, y.x); n1 = ne32(x.y, y.y); n2 = ne32(x.z, y.z); n3 = ne32(x.w, y.w);
+    } else {
+        n0 = ne_lo16(x.x, y.x); n1 = ne_hi16(x.x, y.x) | ne32(x.y, y.y);
+        n2 = ne_lo16(x.z, y.z); n3 = ne_hi16(x.z, y.z) | ne32(x.w, y.w);
+    }
+    return shift_in(shift_in(shift_in(shift_in(acc, n3), n2), n1), n0);
 }
 
 // value of an index field: low 32 bits and the 16 bits above (0 for 4-byte fields)
@@ -275,7 +307,7 @@ __global__ __launch_bounds__(64, SCB_MIN_WAVES) void snappy_compress_blocks_kern
     __shared__ __attribute__((aligned(16))) uint4 ring[FUSED >= 0 ? 68u : 1u];   // the step's units behind the last four of the one before
     const gsrc_t rgba = (gsrc_t)frames[zf].rgba;
     const unsigned row_bytes = frames[zf].rgba_row_bytes, blocks_x = frames[zf].rgba_blocks_x;
-    unsigned bx[kSub], by[kSub], first_off = 0u;
+    unsigned bx[kSub], row_at[kSub], first_off = 0u;      // block column, byte offset of the block row's first pixel row
     // Pixels a pass ahead of their use -- where that does not cost a wave: the YCoCg kernel has 88 registers without
     // the second pixel buffer (five waves per SIMD) and 112 with it (four), and five waves that wait for their pixels
     // beat four that do not (60 8K frames 2.78 -> 2.72 ms); the DXT5 kernel has four either way.
@@ -285,11 +317,14 @@ __global__ __launch_bounds__(64, SCB_MIN_WAVES) void snappy_compress_blocks_kern
     constexpr bool kPrefetch = FUSED != hapbc::kFmtYCoCg;
 #endif
     unsigned pix[kPrefetch ? 2 : 1][16];
+    // 16-byte blocks: the lane's unit of step s lies wholly inside the data (n is whole blocks) -- the one compare
+    // behind every "is it there" of the step
+    auto whole_unit = [&](unsigned s) { return (int)lane < (int)(n >> 4) - (int)(64u * s); };
     // pass t = kSub s + sub: its pixels
     auto load_pixels = [&](unsigned (&p)[16], unsigned t) {
         const unsigned sub = t % kSub;
-        const bool there = (64u * t + lane + 1u) * B <= n;
-        const unsigned at = there ? (4u * by[sub]) * row_bytes + 16u * bx[sub] : first_off;     // (no lane-varying branch around the loads)
+        const bool there = B == 16u ? whole_unit(t) : (64u * t + lane + 1u) * B <= n;
+        const unsigned at = there ? row_at[sub] + 16u * bx[sub] : first_off;     // (no lane-varying branch around the loads)
 #pragma unroll
         for (unsigned r = 0; r < 4u; r++) {
             const uint4 v = get128(rgba + (at + r * row_bytes));
@@ -301,7 +336,7 @@ __global__ __launch_bounds__(64, SCB_MIN_WAVES) void snappy_compress_blocks_kern
         bx[sub] += 64u * kSub;
         while (bx[sub] >= blocks_x) {
             bx[sub] -= blocks_x;
-            by[sub] += 1u;
+            row_at[sub] += 4u * row_bytes;
         }
     };
     if (FUSED >= 0) {
@@ -313,8 +348,9 @@ __global__ __launch_bounds__(64, SCB_MIN_WAVES) void snappy_compress_blocks_kern
 #pragma unroll
         for (unsigned j = 0; j < kSub; j++) {
             const unsigned b = first_block + 64u * j + lane;
-            by[j] = b / blocks_x;
-            bx[j] = b - by[j] * blocks_x;
+            const unsigned by = b / blocks_x;
+            bx[j] = b - by * blocks_x;
+            row_at[j] = (4u * by) * row_bytes;
         }
         load_pixels(pix[0], 0u);
     }
@@ -410,10 +446,10 @@ __global__ __launch_bounds__(64, SCB_MIN_WAVES) void snappy_compress_blocks_kern
             X[s] = xs;
         unsigned differ = 0;
 #pragma unroll
-        for (unsigned d = 0; d < kDistances; d++)
-            differ = differ_nibble<LAYOUT>(differ, xs, Y[d], d);
+        for (unsigned d = kDistances; d-- > 0u;)
+            differ = differ_nibble<LAYOUT>(differ, xs, Y[d]);
         // fields that exist, and (first step) whose source d blocks back lies inside the fragment
-        unsigned ok = pos + 16u <= n ? 0xFFFFu : 0u;
+        unsigned ok = (B == 16u ? whole_unit(s) : pos + 16u <= n) ? 0xFFFFu : 0u;
         if (B == 8u)
             ok = pos + 16u <= n ? 0xFFFFu : pos + 8u <= n ? 0x3333u : 0u;
         if (s == 0u) {
@@ -435,7 +471,7 @@ __global__ __launch_bounds__(64, SCB_MIN_WAVES) void snappy_compress_blocks_kern
             klo[i] = lo;
             khi[i] = hi | (UL::cls(k) << 16);
             slot[i] = table_slot(lo, hi, UL::cls(k));
-            valid[i] = (i == 0u ? pos + 8u <= n : pos + 16u <= n) ? 0xFFFFFFFFu : 0u;
+            valid[i] = (B == 16u ? whole_unit(s) : i == 0u ? pos + 8u <= n : pos + 16u <= n) ? 0xFFFFFFFFu : 0u;
             e[i] = table[slot[i]];
         }
         unsigned hd2[2];
@@ -532,10 +568,9 @@ __global__ __launch_bounds__(64, SCB_MIN_WAVES) void snappy_compress_blocks_kern
                 // a copy is at most 64 bytes: the one that runs across field 16 (byte 64 of the half-tile) is cut there
                 // if it is longer -- both pieces then fit.  a: its first field (the last start below 16; field 0 always
                 // starts an element), b: the next start, or the end of the data
-                constexpr unsigned FO = LAYOUT == 4u ? 0x0C080200u : (LAYOUT == 2u || LAYOUT == 8u) ? 0x0C080400u : 0x0A080200u;   // fo(k), a byte each
                 const unsigned a = 31u - (unsigned)__builtin_clz((S & 0xFFFFu) | 1u);
                 const unsigned b = 17u + (unsigned)__builtin_ctz(((S | ~valid) >> 17) | 0x8000u);
-                const unsigned bytes = (b >> 2) * 16u + ((FO >> (8u * (b & 3u))) & 0xFFu) - (a >> 2) * 16u - ((FO >> (8u * (a & 3u))) & 0xFFu);
+                const unsigned bytes = UL::pos(b) - UL::pos(a);
                 const unsigned inside = (valid & ~S & ~L) >> 16;          // field 16 lies inside a copy
                 S |= (inside & (bytes > 64u ? 1u : 0u)) << 16;
             }
@@ -702,10 +737,11 @@ __global__ __launch_bounds__(64, SCB_MIN_WAVES) void snappy_compress_blocks_kern
             continue;
         const unsigned hh = 8u * s + (lane >> 3);
         const uint4 ma = *reinterpret_cast<const uint4 *>(&masks[hh * 8u]);
-        const unsigned S = ma.x, L = ma.y, X3 = ma.z, CS = S & ~L;
-        unsigned off = (masks[hh * 8u + 7u] & 0xFFFFu) + 4u * popc(L & below) + 2u * popc(L & UL::big32 & below) -
-                       2u * popc(L & UL::small32 & below) + popc(S & below) + popc(CS & below) + popc(X3 & below);
+        const unsigned S = ma.x, L = ma.y, X3 = ma.z;
+        unsigned off = bytes_under<UL>(S, L, X3, below, masks[hh * 8u + 7u] & 0xFFFFu);
         const unsigned sj = S >> j4, lj = L >> j4, xj = X3 >> j4;
+        // element bytes in front of a field's own, as two bit planes: literal header 1 (+1), copy 2 (+1)
+        const unsigned h1 = sj & (lj ^ xj), h2 = sj & (~lj | xj);
         uint4 xs;
         if (kKeepX) {
             xs = X[s];
@@ -718,9 +754,8 @@ __global__ __launch_bounds__(64, SCB_MIN_WAVES) void snappy_compress_blocks_kern
         const unsigned fw[4] = {xs.x, kDwords ? xs.y : xs.x >> 16, xs.z, LAYOUT == 4u ? xs.w : kDwords ? xs.w : xs.z >> 16};
 #pragma unroll
         for (unsigned k = 0; k < 4u; k++) {
-            const unsigned is_s = bit_mask(sj, k), is_l = bit_mask(lj, k), x3 = bit_mask(xj, k);
-            // element bytes in front of the field's own: literal header 1 (+1), copy 2 (+1)
-            off += is_s & ((is_l & 1u) + (~is_l & 2u) + (x3 & 1u));
+            const unsigned is_l = bit_mask(lj, k);
+            off += ((h1 >> k) & 1u) + 2u * ((h2 >> k) & 1u);
             if (is_l) {
                 if (UL::fs(k) == 2u) {
                     put16(out + off, fw[k]);
@@ -754,27 +789,27 @@ __global__ __launch_bounds__(64, SCB_MIN_WAVES) void snappy_compress_blocks_kern
                 bounds[64u + lane] = stream_bytes | (n << 16);
         }
         __syncthreads();
-        constexpr unsigned FO = LAYOUT == 4u ? 0x0C080200u : (LAYOUT == 2u || LAYOUT == 8u) ? 0x0C080400u : 0x0A080200u;   // fo(k), a byte each
         const uint8_t *elfield = reinterpret_cast<const uint8_t *>(table) + 2048u;
         unsigned carry = 0;                                                    // half-tiles begun before the pass
 #pragma unroll 1
         for (unsigned e0 = 0; e0 < elements; e0 += 64u) {
             const unsigned e = e0 + lane;
             const unsigned info = e < elements ? elfield[e] : 0u;
-            // the half-tile of an element: how many half-tiles have begun up to it (every half-tile has an element)
-            const unsigned begun = (unsigned)scan_add((int)(info >> 7)) + carry;
-            carry = (unsigned)__builtin_amdgcn_readlane((int)begun, 63);
+            // the half-tile of an element: how many half-tiles have begun up to it (every half-tile has an element) --
+            // the marks of the lanes below as one lane mask, counted per lane
+            const unsigned long long firsts = __builtin_amdgcn_ballot_w64((info & 0x80u) != 0u);
+            const unsigned begun = __builtin_amdgcn_mbcnt_hi((unsigned)(firsts >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)firsts, carry)) + (info >> 7);
+            carry += (unsigned)__builtin_popcountll(firsts);
             if (e < elements) {
                 const unsigned h = begun - 1u, q = info & 31u;
                 const uint4 ma = *reinterpret_cast<const uint4 *>(&masks[h * 8u]);
                 const uint4 mb = *reinterpret_cast<const uint4 *>(&masks[h * 8u + 4u]);
-                const unsigned S = ma.x, L = ma.y, X3 = ma.z, D0 = ma.w, D1 = mb.x, Hm = mb.y, Sx1 = mb.z, CS = S & ~L;
+                const unsigned S = ma.x, L = ma.y, X3 = ma.z, D0 = ma.w, D1 = mb.x, Hm = mb.y, Sx1 = mb.z;
                 const unsigned under = (1u << q) - 1u;
-                const unsigned off = (mb.w & 0xFFFFu) + 4u * popc(L & under) + 2u * popc(L & UL::big32 & under) -
-                                     2u * popc(L & UL::small32 & under) + popc(S & under) + popc(CS & under) + popc(X3 & under);
+                const unsigned off = bytes_under<UL>(S, L, X3, under, mb.w & 0xFFFFu);
                 // bytes from this field to the next start (the mask ends with a set bit)
                 const unsigned qn = q + 1u + (unsigned)__builtin_ctz(Sx1 >> q);
-                const unsigned len = (qn >> 2) * 16u + ((FO >> (8u * (qn & 3u))) & 0xFFu) - (q >> 2) * 16u - ((FO >> (8u * (q & 3u))) & 0xFFu);
+                const unsigned at = UL::pos(q), len = UL::pos(qn) - at;
                 const bool is_l = ((L >> q) & 1u) != 0u, x3 = ((X3 >> q) & 1u) != 0u;
                 // literal run: tag = len - 1 (60 = one length byte follows)
                 // copy: copy-2 tag 2 | (len - 1) << 2, offset in the next two bytes; copy-1 (len 4..11, offset < 2048):
@@ -795,7 +830,7 @@ __global__ __launch_bounds__(64, SCB_MIN_WAVES) void snappy_compress_blocks_kern
                     put8(out + off + 2, v >> 16);
                 const unsigned m = (e * inv) >> 20;
                 if (m * G == e)
-                    bounds[m] = off | ((h * 128u + (q >> 2) * 16u + ((FO >> (8u * (q & 3u))) & 0xFFu)) << 16);
+                    bounds[m] = off | ((h * 128u + at) << 16);
             }
         }
         __syncthreads();

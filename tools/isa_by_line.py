@@ -16,7 +16,10 @@ The cycle budget of the fused encode kernel (snappy_compress_blocks_kernel<4, YC
 attribution, per PHASE (found by anchor text in the sources, so the table follows the code when lines move), each VALU
 instruction weighted by its measured issue cost (tools/micro/valu_rates2.hip at the kernel's five waves per SIMD;
 weights file: opcode -> cycles, "default" for what was not measured), times the phase's trip count for an 8K Hap Q
-fragment.  Also prints the kernel's register and scratch figures from the code object's metadata.
+fragment.  Code inlined from the helpers at the top of the file or from a system header (`min`, `max`, popcount, the
+DPP moves) counts under the line of the kernel's body that called it, found from the assembler's inlined-at comments, so
+a phase's row is everything it issues.  Also prints the kernel's register and scratch figures from the code object's
+metadata.
 """
 import collections
 import re
@@ -96,6 +99,26 @@ def phase_spans(csrc):
     return spans
 
 
+def attribute(fname, line, loc, body_first, prev):
+    """The (file, line) an instruction counts under.  The assembler's comment lists where the code was inlined from,
+    innermost first.  Lines of bc_encode_core.hpp count where they stand (its helpers are a phase of their own), and so
+    does what they inlined from a system header (`min` / `max` / `abs`): under the innermost line of that file.  The
+    small helpers at the top of snappy_compress_blocks.hip, and system headers called from it, count under the line
+    of the kernel's body that called them -- the outermost one.  Line 0 (compiler-made code) stays with the phase
+    of the instruction in front of it."""
+    chain = [(f.split("/")[-1], int(l)) for f, l in re.findall(r"([\w./+-]+):(\d+):\d+", loc.split(";", 1)[1])] if ";" in loc else []
+    chain = chain or [(fname, line)]
+    for f, l in chain:
+        if f == CORE:
+            return (f, l)
+    for f, l in reversed(chain):
+        if f == SCB and l >= body_first:
+            return (f, l)
+    if chain[0] == (SCB, 0) and prev is not None:
+        return prev
+    return chain[0]
+
+
 def base_op(op):
     for suf in ("_e32", "_e64", "_sdwa", "_dpp"):
         if op.endswith(suf):
@@ -126,6 +149,7 @@ def fused_budget(args):
         subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
         text = open(tmp.name).read().splitlines()
     spans = phase_spans(csrc)
+    body_first = min(lo for lo, hi, nm, tr in spans[SCB] if nm == "loop+address overhead" and lo > 100)
     files, cur = {}, None
     acc = collections.OrderedDict()
     unweighted = collections.Counter()
@@ -138,7 +162,7 @@ def fused_budget(args):
             continue
         m = re.match(r"\.loc\s+(\d+)\s+(\d+)\s+(\d+)", s)
         if m:
-            cur = (files.get(int(m.group(1)), "?"), int(m.group(2)))
+            cur = attribute(files.get(int(m.group(1)), "?"), int(m.group(2)), s, body_first, cur)
             continue
         if re.match(r"\.(name|vgpr_count|sgpr_count|private_segment_fixed_size|group_segment_fixed_size):", s):
             meta.append(s)

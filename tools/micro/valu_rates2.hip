@@ -73,6 +73,12 @@
 #define A_ADDDPP(x) "v_add_u32_dpp " #x ", " #x ", " #x " quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
 #define A_MOVDPP(x) "v_mov_b32_dpp " #x ", " #x " quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
 #define A_READLANE(x) "v_readlane_b32 s20, " #x ", 5\n"
+#define A_MULLO(x) "v_mul_lo_u32 " #x ", " #x ", %8\n"
+#define A_MULHI(x) "v_mul_hi_u32 " #x ", " #x ", %8\n"
+#define A_BITOP3(x) "v_bitop3_b32 " #x ", " #x ", %8, " #x " bitop3:0x48\n"
+#define A_CMPSDWA(x) "v_cmp_ne_u32_sdwa s[20:21], " #x ", %8 src0_sel:WORD_0 src1_sel:WORD_0\n"
+#define A_ADDC64(x) "v_addc_co_u32_e64 " #x ", s[20:21], " #x ", " #x ", s[20:21]\n"
+#define A_CMPADDC64(x) "v_cmp_ne_u32_e64 s[20:21], " #x ", %8\nv_addc_co_u32_e64 " #x ", s[20:21], " #x ", " #x ", s[20:21]\n"
 KERNEL(k_add, A_ADD) KERNEL(k_and, A_AND) KERNEL(k_lshl, A_LSHL) KERNEL(k_bfe, A_BFE) KERNEL(k_lshlor, A_LSHLOR)
 KERNEL(k_minu, A_MINU) KERNEL(k_mini, A_MINI) KERNEL(k_minf, A_MINF) KERNEL(k_addf, A_ADDF) KERNEL(k_fma, A_FMA)
 KERNEL(k_cvtub, A_CVTUB) KERNEL(k_cvtu, A_CVTU) KERNEL(k_mad24, A_MAD24) KERNEL(k_madi24, A_MADI24) KERNEL(k_cnd, A_CND)
@@ -84,7 +90,8 @@ KERNEL(k_addlshl, A_ADDLSHL) KERNEL(k_andor, A_ANDOR) KERNEL(k_or3, A_OR3) KERNE
 KERNEL(k_madu16, A_MADU16) KERNEL(k_madi16, A_MADI16) KERNEL(k_mul24, A_MUL24) KERNEL(k_pkadd, A_PKADD) KERNEL(k_pklshr, A_PKLSHR)
 KERNEL(k_pkmad, A_PKMAD) KERNEL(k_pkmax, A_PKMAX) KERNEL(k_alignbit, A_ALIGNBIT) KERNEL(k_perm, A_PERM) KERNEL(k_med3i, A_MED3I)
 KERNEL(k_max3, A_MAX3) KERNEL(k_dot2, A_DOT2) KERNEL(k_bcnt, A_BCNT) KERNEL(k_adddpp, A_ADDDPP) KERNEL(k_movdpp, A_MOVDPP)
-KERNEL(k_readlane, A_READLANE)
+KERNEL(k_readlane, A_READLANE) KERNEL(k_mullo, A_MULLO) KERNEL(k_mulhi, A_MULHI) KERNEL(k_bitop3, A_BITOP3)
+KERNEL(k_cmpsdwa, A_CMPSDWA) KERNEL(k_addc64, A_ADDC64) KERNEL(k_cmpaddc64, A_CMPADDC64)
 static int g_waves = 8;      // waves per SIMD: workgroups of 4 waves, g_waves of them per CU
 template <typename K> void run(const char *name, K kern, unsigned *d)
 {
@@ -112,5 +119,6 @@ int main(int argc, char **argv)
     RUN(k_or) RUN(k_sub) RUN(k_lshr) RUN(k_ashr) RUN(k_lshladd) RUN(k_addlshl) RUN(k_andor) RUN(k_or3) RUN(k_bfi) RUN(k_xad) RUN(k_madu16) RUN(k_madi16)
     RUN(k_mul24) RUN(k_pkadd) RUN(k_pklshr) RUN(k_pkmad) RUN(k_pkmax) RUN(k_alignbit) RUN(k_perm) RUN(k_med3i) RUN(k_max3) RUN(k_dot2) RUN(k_bcnt)
     RUN(k_adddpp) RUN(k_movdpp) RUN(k_readlane)
+    RUN(k_mullo) RUN(k_mulhi) RUN(k_bitop3) RUN(k_cmpsdwa) RUN(k_addc64) RUN(k_cmpaddc64)       // (two-instruction kernels: cycles per PAIR)
     return 0;
 }
