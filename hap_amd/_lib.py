@@ -75,6 +75,11 @@ def _load():
         "HapGpuDecodeFrameTextures": (u, [vp, u, P(vp), P(ul), u, P(vp), P(ul), P(ul), P(u), P(u), u]),
         "HapGpuDecodeFramesRGBA": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, ul, P(u), u]),
         "HapGpuDecodeFramesRGBAScaled": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, ul, P(u), u]),
+        "HapGpuCompressPlanes": (u, [vp, vp, ul, ul, u, u, P(C.c_float), P(C.c_float), u, u, u, vp, ul, P(ul)]),
+        "HapGpuEncodeFramesPlanes": (u, [vp, u, P(vp), u, u, ul, ul, P(C.c_float), P(C.c_float), u, u, u, P(u), P(u), P(u),
+                                         P(vp), P(ul), P(ul), P(u), u]),
+        "HapGpuEncodeFramesPlanesBegin": (u, [vp, u, P(vp), u, u, ul, ul, P(C.c_float), P(C.c_float), u, u, u, P(u), P(u),
+                                              P(u), P(vp), P(ul), P(ul), P(u), u]),
         "HapGpuDecodeFramesPlanes": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, u, u, ul, ul, P(C.c_float), P(C.c_float), P(u), u]),
         "HapGpuDecodeFramesRGBARegion": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, u, u, u, ul, P(u), u]),
         "HapGpuTranscodeTexture": (u, [vp, vp, ul, u, vp, ul, u, u, u, u, P(u), P(vp), P(ul), P(ul)]),

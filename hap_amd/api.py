@@ -82,10 +82,11 @@ def _plane_tensors(out, single, width, height, scale_log2):
     return tensors, shape[0], PLANE_ELEMENTS[shape[1]], shape[2] * e, shape[3] * e
 
 
-def _plane_constants(scale, bias, channels):
-    """scale (default 1/255) and bias (default 0) per channel, through numpy.float32: two C float arrays"""
+def _plane_constants(scale, bias, channels, default_scale=1.0 / 255.0):
+    """scale (default 1/255 -- decoding -- or 255 -- encoding) and bias (default 0) per channel, through numpy.float32:
+    two C float arrays"""
     import numpy as np
-    scale = [1.0 / 255.0] * channels if scale is None else list(scale)
+    scale = [default_scale] * channels if scale is None else list(scale)
     bias = [0.0] * channels if bias is None else list(bias)
     if len(scale) != channels or len(bias) != channels:
         raise ValueError("scale and bias: one value per channel")
@@ -447,6 +448,29 @@ class Context:
         return lib.HapGpuDecompressPlanes(self.handle, ta, tn, texture_format, aa, an, width, height, scale_log2, channels,
                                           element, tensors[0].data_ptr(), plane_bytes, row_bytes, sc, bi)
 
+    def compress_planes(self, planes, width, height, texture_format, scale=None, bias=None, output=None):
+        """`planes`, a (C, height, width) float16, bfloat16 or float32 torch tensor on the device, C 3 or 4 -> one block
+        texture (HapGpuCompressPlanes): byte = float32(element) * scale[c] + bias[c] (two roundings), NaN and anything
+        not above 0 to 0, 255 and above to 255, else to nearest with halves to even; compress_rgba's texture of the
+        picture of those bytes (A 255 with C 3).  texture_format RGB_DXT1, RGBA_DXT5, YCoCg_DXT5 or A_RGTC1.  channels,
+        element, planeBytes and rowBytes are read from the tensor, so a slice with longer rows or planes is accepted;
+        stride(-1) must be 1.  scale defaults to 255 per channel, bias to 0.  Returns (result, bytes | None), or
+        (result, bytes used) into `output`."""
+        tensors, channels, element, plane_bytes, row_bytes = _plane_tensors(planes, True, width, height, 0)
+        sc, bi = _plane_constants(scale, bias, channels, 255.0)
+        block = 8 if texture_format in (HapTextureFormat.RGB_DXT1, HapTextureFormat.A_RGTC1) else 16
+        need = (width // 4) * (height // 4) * block
+        own = output is None
+        if own:
+            output = (C.c_ubyte * max(1, need))()
+        oa, on, _k = _addr_len(output)
+        used = C.c_ulong(0)
+        r = lib.HapGpuCompressPlanes(self.handle, tensors[0].data_ptr(), plane_bytes, row_bytes, channels, element, sc, bi,
+                                     width, height, texture_format, oa, on, C.byref(used))
+        if own:
+            return r, (C.string_at(output, used.value) if r == 0 else None)
+        return r, used.value
+
     def decompress_rgba_region(self, texture, texture_format, width, height, region, rgba=None, alpha=None,
                                row_bytes=None):
         """Texture (+ optional RGTC1 alpha plane) -> the RGBA8 picture of region = (x, y, w, h), a block-aligned rectangle
@@ -565,6 +589,45 @@ class Context:
                                             (C.c_uint * count)(*formats), (C.c_uint * count)(*compressors),
                                             (C.c_uint * count)(*chunk_counts), optrs, olens, used, results, flags)
         self._pending = (used, results, ptrs, optrs, olens, rgba_frames, outputs)     # alive until the second half
+        return r
+
+    def _encode_planes(self, fn, described, width, height, formats, compressors, chunk_counts, outputs, scale, bias, flags):
+        tensors, channels, element, plane_bytes, row_bytes = described
+        nf, count = len(tensors), len(formats)
+        if len(outputs) != nf:
+            raise ValueError("one output per tensor")
+        sc, bi = _plane_constants(scale, bias, channels, 255.0)
+        ptrs = (C.c_void_p * nf)(*[None if t is None else t.data_ptr() for t in tensors])
+        optrs, oinfos = self._ptr_array(outputs)
+        olens = (C.c_ulong * nf)(*[i[1] for i in oinfos])
+        used = (C.c_ulong * nf)()
+        results = (C.c_uint * nf)()
+        r = fn(self.handle, nf, ptrs, channels, element, plane_bytes, row_bytes, sc, bi, width, height, count,
+               (C.c_uint * count)(*formats), (C.c_uint * count)(*compressors), (C.c_uint * count)(*chunk_counts),
+               optrs, olens, used, results, flags)
+        return r, used, results, (ptrs, optrs, olens, tensors, outputs)
+
+    def encode_frames_planes(self, planes, width, height, formats, compressors, chunk_counts, outputs, scale=None,
+                             bias=None, flags=0):
+        """Planar tensors -> frames in one call, without RGBA8 pictures in between (HapGpuEncodeFramesPlanes).  `planes`:
+        one (N, C, height, width) torch tensor on the device or a list of N (C, H, W) ones that share their strides
+        (None: no tensor for that frame), float16, bfloat16 or float32, C 3 or 4; channels, element, planeBytes and
+        rowBytes are read from it, stride(-1) must be 1.  byte = float32(element) * scale[c] + bias[c] (two roundings),
+        NaN and anything not above 0 to 0, 255 and above to 255, else to nearest with halves to even; the frames are
+        encode_frames_rgba's of the pictures of those bytes.  formats: [RGB_DXT1], [RGBA_DXT5], [YCoCg_DXT5], [A_RGTC1]
+        or [YCoCg_DXT5, A_RGTC1].  scale defaults to 255 per channel, bias to 0.  Returns (result, used[], results[])."""
+        described = _plane_tensors(planes, False, width, height, 0)               # (refusals first: no context needed)
+        r, used, results, _keep = self._encode_planes(lib.HapGpuEncodeFramesPlanes, described, width, height, formats,
+                                                      compressors, chunk_counts, outputs, scale, bias, flags)
+        return r, list(used), list(results)
+
+    def encode_frames_planes_begin(self, planes, width, height, formats, compressors, chunk_counts, outputs, scale=None,
+                                   bias=None, flags=0):
+        """First half of encode_frames_planes (HapGpuEncodeFramesPlanesBegin); encode_finish() is the second."""
+        described = _plane_tensors(planes, False, width, height, 0)
+        r, used, results, keep = self._encode_planes(lib.HapGpuEncodeFramesPlanesBegin, described, width, height, formats,
+                                                     compressors, chunk_counts, outputs, scale, bias, flags)
+        self._pending = (used, results) + keep                                      # alive until the second half
         return r
 
     def _encode_half(self, fn, rgba_half_frames, width, height, row_bytes, texture_format, compressor, chunk_count,

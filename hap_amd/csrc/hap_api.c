@@ -694,6 +694,98 @@ unsigned int HapGpuEncodeFramesRGBABegin(HapGpuContext *context, unsigned int fr
     return r;
 }
 
+/* Planar float tensors -> textures and frames: the RGBA calls with the block encode of bc_encode_planes.hip */
+unsigned int HapGpuCompressPlanes(HapGpuContext *context, const void *planes, unsigned long planeBytes,
+                                  unsigned long rowBytes, unsigned int channels, unsigned int element,
+                                  const float *scale, const float *bias, unsigned int width, unsigned int height,
+                                  unsigned int textureFormat, void *output, unsigned long outputBytes,
+                                  unsigned long *outputBytesUsed)
+{
+    const HapbPlanes layout = {channels, element, planeBytes, scale, bias};
+    unsigned r;
+    if (!context || !planes || !output || !hapb_planes_encode_valid(width, height, rowBytes, &layout, 1u, &textureFormat))
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_compress_planes(context, planes, width, height, rowBytes, &layout, textureFormat, output, outputBytes,
+                             outputBytesUsed);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+/* what does not depend on a frame or on the context, checked before either is looked at: 0 = in order; else every
+   results[f] is Bad_Arguments */
+static unsigned planes_encode_refused(unsigned frameCount, const void *const *planeFrames, const HapbPlanes *layout,
+                                      unsigned long rowBytes, unsigned width, unsigned height, unsigned count,
+                                      const unsigned *textureFormats, const unsigned *compressors,
+                                      const unsigned *chunkCounts, void *const *outputBuffers,
+                                      const unsigned long *outputBuffersBytes, unsigned long *outputBuffersBytesUsed,
+                                      unsigned *results)
+{
+    unsigned f;
+    if (results && planeFrames && compressors && chunkCounts && outputBuffers && outputBuffersBytes &&
+        outputBuffersBytesUsed && hapb_planes_encode_valid(width, height, rowBytes, layout, count, textureFormats))
+        return 0u;
+    for (f = 0; results && f < frameCount; f++)
+        results[f] = HapResult_Bad_Arguments;
+    return 1u;
+}
+
+unsigned int HapGpuEncodeFramesPlanes(HapGpuContext *context, unsigned int frameCount,
+                                      const void *const *planeFrames, unsigned int channels, unsigned int element,
+                                      unsigned long planeBytes, unsigned long rowBytes, const float *scale,
+                                      const float *bias, unsigned int width, unsigned int height, unsigned int count,
+                                      const unsigned int *textureFormats, const unsigned int *compressors,
+                                      const unsigned int *chunkCounts, void *const *outputBuffers,
+                                      const unsigned long *outputBuffersBytes,
+                                      unsigned long *outputBuffersBytesUsed, unsigned int *results,
+                                      unsigned int flags)
+{
+    const HapbPlanes layout = {channels, element, planeBytes, scale, bias};
+    unsigned r = HapResult_No_Error, done;
+    if (planes_encode_refused(frameCount, planeFrames, &layout, rowBytes, width, height, count, textureFormats, compressors,
+                              chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results) || !context)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    for (done = 0; done < frameCount; done += HAP_BATCH_SLICE) {
+        const unsigned n = frameCount - done < HAP_BATCH_SLICE ? frameCount - done : HAP_BATCH_SLICE;
+        const unsigned rc = hapb_encode_planes(context, n, planeFrames + done, width, height, rowBytes, &layout, count,
+                                               textureFormats, compressors, chunkCounts, outputBuffers + done,
+                                               outputBuffersBytes + done, outputBuffersBytesUsed + done, results + done,
+                                               flags);
+        if (r == HapResult_No_Error)
+            r = rc;
+    }
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+unsigned int HapGpuEncodeFramesPlanesBegin(HapGpuContext *context, unsigned int frameCount,
+                                           const void *const *planeFrames, unsigned int channels,
+                                           unsigned int element, unsigned long planeBytes, unsigned long rowBytes,
+                                           const float *scale, const float *bias, unsigned int width,
+                                           unsigned int height, unsigned int count,
+                                           const unsigned int *textureFormats, const unsigned int *compressors,
+                                           const unsigned int *chunkCounts, void *const *outputBuffers,
+                                           const unsigned long *outputBuffersBytes,
+                                           unsigned long *outputBuffersBytesUsed, unsigned int *results,
+                                           unsigned int flags)
+{
+    const HapbPlanes layout = {channels, element, planeBytes, scale, bias};
+    unsigned r;
+    if (frameCount > HAP_BATCH_SLICE ||
+        planes_encode_refused(frameCount, planeFrames, &layout, rowBytes, width, height, count, textureFormats, compressors,
+                              chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results) || !context)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    context->defer_encode = 1u;
+    r = hapb_encode_planes(context, frameCount, planeFrames, width, height, rowBytes, &layout, count, textureFormats,
+                           compressors, chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results,
+                           flags);
+    context->defer_encode = 0u;
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
 /* RGBA16F pictures -> Hap HDR: the RGBA calls with 8-byte texels and one BC6H texture per frame */
 unsigned int HapGpuCompressRGBAHalf(HapGpuContext *context, const void *rgbaHalf, unsigned int width,
                                     unsigned int height, unsigned long rowBytes, unsigned int textureFormat,

@@ -233,7 +233,7 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
            others (snappy_compress_blocks.hip).  One texture per frame. */
         {
             const HapbBlockEncodeJob *bj = ctx->block_encode_job;
-            if (bj && !ctx->no_fusion && count == 1u && bj->texel_bytes == 4u && (bj->row_bytes & 3u) == 0 &&
+            if (bj && !ctx->no_fusion && count == 1u && bj->texel_bytes == 4u && !bj->planes.channels && (bj->row_bytes & 3u) == 0 &&
                 (unsigned long long)bj->row_bytes * bj->height < 0xFFFFFFFFull && bj->width / 4u >= 1u) {
                 /* (code: HapGpuTexEnc.reserved bits 24..26; mask bit: which kernel the launcher starts) */
                 if (t->field_period == 4u && t->format == HapTextureFormat_YCoCg_DXT5) {
@@ -469,6 +469,16 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                 if (job) {
                     HAPB_MIX(job->frame_count); HAPB_MIX(job->width); HAPB_MIX(job->height); HAPB_MIX(job->row_bytes);
                     HAPB_MIX(job->wide + 2); HAPB_MIX(job->texel_bytes);
+                    if (job->planes.channels) {
+                        /* (scale and bias are kernel arguments: part of what a recording holds) */
+                        HAPB_MIX(job->planes.channels + 8u); HAPB_MIX(job->planes.element); HAPB_MIX(job->planes.plane_bytes);
+                        for (i = 0; i < job->planes.channels; i++) {
+                            uint32_t bits[2];
+                            memcpy(&bits[0], &job->plane_scale[i], 4);
+                            memcpy(&bits[1], &job->plane_bias[i], 4);
+                            HAPB_MIX(bits[0]); HAPB_MIX(bits[1]);
+                        }
+                    }
                 }
                 graph = hapgpu_rt_graph_begin(rt, key);
             }
@@ -490,6 +500,11 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                             const HapGpuPictureTable t = {{dt, dt + (size_t)(1u + i) * job->frame_count,
                                                            pair ? dt + 2u * (size_t)job->frame_count : NULL}, {0u, 0u, 0u}};
                             launch_rc |= job->height / 4u > 65535u ? 1u :
+                                         job->planes.channels ?
+                                         (unsigned)hapgpu_k_block_encode_planes(rt, &t, job->frame_count, job->width, job->height,
+                                                                                job->formats[i], pair, job->planes.channels,
+                                                                                job->planes.element, job->planes.plane_bytes,
+                                                                                job->row_bytes, job->plane_scale, job->plane_bias) :
                                          (unsigned)hapgpu_k_block_encode(rt, &t, job->frame_count, job->width, job->height,
                                                                          job->row_bytes, job->formats[i], pair, job->wide,
                                                                          job->picture_kind);
@@ -1028,15 +1043,44 @@ unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                                 chunk_counts, outputs, output_bytes, output_used, results, flags, HAPGPU_PICTURE_RGBA8);
 }
 
-unsigned hapb_encode_pictures(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
-                              unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
-                              const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
-                              void *const *outputs, const unsigned long *output_bytes,
-                              unsigned long *output_used, unsigned *results, unsigned flags, unsigned picture_kind)
+/* the size of an element of a planar tensor */
+static size_t plane_element_bytes(unsigned element)
+{
+    return element == HapGpuPlaneElement_F32 ? 4u : 2u;
+}
+
+int hapb_planes_encode_valid(unsigned width, unsigned height, unsigned long row_bytes, const HapbPlanes *planes,
+                             unsigned count, const unsigned *formats)
+{
+    size_t e, unit;
+    if (!planes->scale || !planes->bias || planes->channels < 3u || planes->channels > 4u ||
+        planes->element > HapGpuPlaneElement_F32 || width == 0 || height == 0 || (width & 3u) || (height & 3u) ||
+        height / 4u > 65535u || !formats)
+        return 0;
+    /* what a lane loads per row: the tensors' pitches are multiples of it */
+    e = plane_element_bytes(planes->element);
+    unit = 4u * e;
+    if (row_bytes < (unsigned long)width * e || row_bytes % unit || planes->plane_bytes % unit ||
+        planes->plane_bytes / row_bytes < height - 1u ||
+        planes->plane_bytes < row_bytes * (unsigned long)(height - 1u) + (unsigned long)width * e)
+        return 0;
+    if (count == 2u)
+        return formats[0] == HapTextureFormat_YCoCg_DXT5 && formats[1] == HapTextureFormat_A_RGTC1;
+    return count == 1u && kind_makes_format(HAPGPU_PICTURE_RGBA8, formats[0], 0);
+}
+
+/* hapb_encode_pictures, or with `planes` hapb_encode_planes: planar tensors in device memory in place of the pictures
+   (picture_kind is then not looked at, and the arguments have passed hapb_planes_encode_valid) */
+static unsigned encode_pictures(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
+                                unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
+                                const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
+                                void *const *outputs, const unsigned long *output_bytes,
+                                unsigned long *output_used, unsigned *results, unsigned flags, unsigned picture_kind,
+                                const HapbPlanes *planes)
 {
     hapgpu_rt *rt = ctx->rt;
-    const size_t texel = HAPGPU_PICTURE_TEXEL_BYTES(picture_kind);
-    const unsigned align = source_align_mask(picture_kind);
+    const size_t texel = planes ? plane_element_bytes(planes->element) : HAPGPU_PICTURE_TEXEL_BYTES(picture_kind);
+    const unsigned align = planes ? 4u * (unsigned)texel - 1u : source_align_mask(picture_kind);
     unsigned long tex_bytes[2] = {0, 0};
     size_t per_frame = 0, rgba_bytes, tex_off[2] = {0, 0};
     unsigned i, f, rc;
@@ -1058,7 +1102,7 @@ unsigned hapb_encode_pictures(HapGpuContext *ctx, unsigned frame_count, const vo
     }
     for (i = 0; i < count; i++) {
         /* (BC7 only when asked, and alone: no Hap variant pairs it with a second texture) */
-        const int bptc = (flags & HAPGPU_ENCODE_BPTC_BLOCKS) && count == 1u && formats[i] == HapTextureFormat_RGBA_BPTC_UNORM;
+        const int bptc = !planes && (flags & HAPGPU_ENCODE_BPTC_BLOCKS) && count == 1u && formats[i] == HapTextureFormat_RGBA_BPTC_UNORM;
         /* (half pictures make BC6H, alone, and nothing else; RGBA8 pictures never make it; A8 pictures make RGTC1, alone) */
         if ((picture_kind != HAPGPU_PICTURE_RGBA8 && count != 1u) || !kind_makes_format(picture_kind, formats[i], bptc)) {
             for (f = 0; f < frame_count; f++)
@@ -1087,6 +1131,9 @@ unsigned hapb_encode_pictures(HapGpuContext *ctx, unsigned frame_count, const vo
         for (i = 0; i < count; i++)
             tex_ptrs[(size_t)f * count + i] = NULL;     /* NULL input => Bad_Arguments for that frame */
         if (!src)
+            continue;
+        /* (a tensor in host memory, or one the lanes' loads would be misaligned in: its frame is Bad_Arguments) */
+        if (planes && (!is_dev(ctx, src) || ((uintptr_t)src & align)))
             continue;
         if (!is_dev(ctx, src)) {
             /* one staging buffer per frame so that uploads and kernels can overlap on the stream */
@@ -1129,6 +1176,14 @@ unsigned hapb_encode_pictures(HapGpuContext *ctx, unsigned frame_count, const vo
         job.picture_kind = picture_kind;
         for (i = 0; i < count; i++)
             job.formats[i] = formats[i];
+        if (planes) {
+            job.planes = *planes;
+            job.planes.scale = job.planes.bias = NULL;
+            for (i = 0; i < planes->channels; i++) {
+                job.plane_scale[i] = planes->scale[i];
+                job.plane_bias[i] = planes->bias[i];
+            }
+        }
         ctx->block_encode_job = &job;
         rc = hapb_encode(ctx, frame_count, count, tex_ptrs, tex_bytes, formats, compressors, chunk_counts, outputs,
                          output_bytes, output_used, results, flags, rgba_stage ? 2 : 1);
@@ -1136,6 +1191,79 @@ unsigned hapb_encode_pictures(HapGpuContext *ctx, unsigned frame_count, const vo
     }
     free(tex_ptrs);
     return rc;
+}
+
+unsigned hapb_encode_pictures(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
+                              unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
+                              const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
+                              void *const *outputs, const unsigned long *output_bytes,
+                              unsigned long *output_used, unsigned *results, unsigned flags, unsigned picture_kind)
+{
+    return encode_pictures(ctx, frame_count, rgba_frames, width, height, row_bytes, count, formats, compressors,
+                           chunk_counts, outputs, output_bytes, output_used, results, flags, picture_kind, NULL);
+}
+
+unsigned hapb_encode_planes(HapGpuContext *ctx, unsigned frame_count, const void *const *tensors, unsigned width,
+                            unsigned height, unsigned long row_bytes, const HapbPlanes *planes, unsigned count,
+                            const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
+                            void *const *outputs, const unsigned long *output_bytes, unsigned long *output_used,
+                            unsigned *results, unsigned flags)
+{
+    unsigned f;
+    if (frame_count == 0)
+        return HapResult_No_Error;
+    /* everything that does not depend on a frame, before any device is touched */
+    if (!results || !tensors || !compressors || !chunk_counts || !outputs || !output_bytes || !output_used ||
+        !hapb_planes_encode_valid(width, height, row_bytes, planes, count, formats)) {
+        for (f = 0; results && f < frame_count; f++)
+            results[f] = HapResult_Bad_Arguments;
+        return HapResult_Bad_Arguments;
+    }
+    return encode_pictures(ctx, frame_count, tensors, width, height, row_bytes, count, formats, compressors, chunk_counts,
+                           outputs, output_bytes, output_used, results, flags, HAPGPU_PICTURE_RGBA8, planes);
+}
+
+/* One tensor -> one texture: hapb_compress_rgba's output rules, the tensor in device memory */
+unsigned hapb_compress_planes(HapGpuContext *ctx, const void *tensor, unsigned width, unsigned height,
+                              unsigned long row_bytes, const HapbPlanes *planes, unsigned format, void *output,
+                              unsigned long output_bytes, unsigned long *used)
+{
+    hapgpu_rt *rt = ctx->rt;
+    HapGpuPictureTable t = {{NULL, NULL, NULL}, {0u, 0u, 0u}};
+    size_t block, need;
+    void *dst = output;
+    int rc;
+    if (context_busy(ctx, NULL, 0))
+        return HapResult_Internal_Error;
+    if (!tensor || !output || !hapb_planes_encode_valid(width, height, row_bytes, planes, 1u, &format))
+        return HapResult_Bad_Arguments;
+    block = hapf_block_bytes(format);
+    need = (size_t)(width / 4u) * (height / 4u) * block;
+    if (output_bytes < need)
+        return HapResult_Buffer_Too_Small;
+    if (!is_dev(ctx, tensor) || ((uintptr_t)tensor & (4u * plane_element_bytes(planes->element) - 1u)) ||
+        (is_dev(ctx, output) && ((uintptr_t)output & (block - 1u))))
+        return HapResult_Bad_Arguments;
+    if (!is_dev(ctx, output)) {
+        dst = hapgpu_rt_device_scratch(rt, D_BC_TEX, need);
+        if (!dst)
+            return HapResult_Internal_Error;
+    }
+    t.one[0] = (uint64_t)(uintptr_t)tensor;
+    t.one[1] = (uint64_t)(uintptr_t)dst;
+    rc = hapgpu_k_block_encode_planes(rt, &t, 1u, width, height, format, 0, planes->channels, planes->element,
+                                      planes->plane_bytes, row_bytes, planes->scale, planes->bias);
+    if (rc == 1)
+        return HapResult_Bad_Arguments;
+    if (rc)
+        return HapResult_Internal_Error;
+    if (dst != output && hapgpu_rt_d2h(rt, output, dst, need))
+        return HapResult_Internal_Error;
+    if (hapgpu_rt_sync(rt))
+        return HapResult_Internal_Error;
+    if (used)
+        *used = (unsigned long)need;
+    return HapResult_No_Error;
 }
 
 /* ================================================================== decode */

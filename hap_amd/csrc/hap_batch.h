@@ -53,6 +53,18 @@ struct HapGpuContext {
     struct HapbEncodePending *pending_encode;
 };
 
+/* The tensors of the planar roads (include/hap_gpu.h: HapGpuDecompressPlanes, HapGpuDecodeFramesPlanes,
+   HapGpuCompressPlanes, HapGpuEncodeFramesPlanes): what one
+   call's tensors share.  Their rows are the calls' row_bytes apart. */
+typedef struct HapbPlanes {
+    unsigned channels;              /* planes of a tensor: 3 (R, G, B) or 4 (+ A) */
+    unsigned element;               /* HapGpuPlaneElement */
+    unsigned long plane_bytes;      /* from one plane of a tensor to the next */
+    const float *scale, *bias;      /* `channels` floats each.  Decoding: element = (float)byte * scale[c] + bias[c], two
+                                       roundings; encoding: byte = quantise(element * scale[c] + bias[c]), two roundings
+                                       (plane_quantise.hpp) */
+} HapbPlanes;
+
 typedef struct HapbBlockEncodeJob {
     const uint64_t *host_table;    /* pinned: [sources][outputs of texture 0][of texture 1], frame_count each */
     uint64_t *device_table;
@@ -62,6 +74,12 @@ typedef struct HapbBlockEncodeJob {
                                       only RGBA8 pictures are ever fused into the block compressor */
     unsigned long row_bytes;
     int wide;
+    /* planes.channels != 0: the sources are planar tensors in device memory, not pictures (hapb_encode_planes): the block
+       encode is hapgpu_k_block_encode_planes' and never part of the block compressor; picture_kind, texel_bytes and wide
+       mean nothing.  scale and bias are kept here (planes.scale / planes.bias point to the caller's, which need not
+       outlive the first half of a call in two halves: not looked at after hapb_encode_planes has returned). */
+    HapbPlanes planes;
+    float plane_scale[4], plane_bias[4];
 } HapbBlockEncodeJob;
 
 /* What hapb_encode leaves for hapb_encode_complete: the call's arguments (copies: the client's arrays need not outlive
@@ -108,19 +126,21 @@ unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned 
                               const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
                               void *picture, unsigned long row_bytes, unsigned picture_kind, unsigned scale_log2,
                               const HapGpuRegion *region);
-/* The tensors of the planar roads (include/hap_gpu.h: HapGpuDecompressPlanes, HapGpuDecodeFramesPlanes): what one
-   call's tensors share.  Their rows are the calls' row_bytes apart. */
-typedef struct HapbPlanes {
-    unsigned channels;              /* planes of a tensor: 3 (R, G, B) or 4 (+ A) */
-    unsigned element;               /* HapGpuPlaneElement */
-    unsigned long plane_bytes;      /* from one plane of a tensor to the next */
-    const float *scale, *bias;      /* `channels` floats each: element = (float)byte * scale[c] + bias[c], two roundings */
-} HapbPlanes;
 /* one texture (host or device) -> one planar tensor in device memory of (width >> scale_log2) x (height >> scale_log2),
    scale_log2 0 to 2: DXT1, DXT5, YCoCg-DXT5 with an optional RGTC1 alpha plane */
 unsigned hapb_decompress_planes(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
                                 const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
                                 unsigned scale_log2, void *tensor, unsigned long row_bytes, const HapbPlanes *planes);
+/* one planar tensor in device memory -> one texture (host or device): DXT1, DXT5, YCoCg-DXT5, or RGTC1 from the fourth
+   plane (255 where there are three) */
+unsigned hapb_compress_planes(HapGpuContext *ctx, const void *tensor, unsigned width, unsigned height,
+                              unsigned long row_bytes, const HapbPlanes *planes, unsigned format, void *output,
+                              unsigned long output_bytes, unsigned long *used);
+/* what the planar encode calls ask whatever their tensors are: 1 = channels, element, scale, bias, the geometry, the
+   pitches and the set of texture formats are in order (include/hap_gpu.h: HapGpuCompressPlanes,
+   HapGpuEncodeFramesPlanes).  Touches no device. */
+int hapb_planes_encode_valid(unsigned width, unsigned height, unsigned long row_bytes, const HapbPlanes *planes,
+                             unsigned count, const unsigned *formats);
 /* 1: region is a block-aligned, non-empty rectangle inside region->width x height */
 int hapb_region_fits(const HapGpuRegion *region, unsigned height);
 /* pictures -> frames.  picture_kind RGBA8: the DXT / RGTC1 formats (BC7 with HAPGPU_ENCODE_BPTC_BLOCKS); RGBA16F (rows
@@ -137,6 +157,14 @@ unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                           const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
                           void *const *outputs, const unsigned long *output_bytes,
                           unsigned long *output_used, unsigned *results, unsigned flags);
+/* planar tensors in device memory -> frames: hapb_encode_pictures with the block encode of hapgpu_k_block_encode_planes.
+   count 1: DXT1, DXT5, YCoCg-DXT5 or RGTC1; count 2: YCoCg-DXT5 then RGTC1.  A NULL, host or misaligned tensor makes its
+   frame Bad_Arguments. */
+unsigned hapb_encode_planes(HapGpuContext *ctx, unsigned frame_count, const void *const *tensors, unsigned width,
+                            unsigned height, unsigned long row_bytes, const HapbPlanes *planes, unsigned count,
+                            const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
+                            void *const *outputs, const unsigned long *output_bytes, unsigned long *output_used,
+                            unsigned *results, unsigned flags);
 /* callback/callback_info: only honoured for frame_count == 1 (the hap.h HapDecode path) */
 unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
                      const unsigned long *input_bytes, unsigned index, void *const *outputs,

@@ -358,6 +358,21 @@ int hapgpu_k_block_decode_planes(hapgpu_rt *rt, const HapGpuPictureTable *table,
                                  unsigned width, unsigned height, unsigned hap_texture_format, unsigned scale_log2,
                                  unsigned channels, unsigned element_kind, size_t plane_bytes, size_t row_bytes,
                                  const float *scale, const float *bias);
+/* planar tensors -> blocks of `hap_texture_format`, without an RGBA8 picture in between (bc_encode_planes.hip): the way
+   back of hapgpu_k_block_decode_planes.  Tensors (the first column of the table) of `channels` (3 or 4: R, G, B[, A])
+   planes plane_bytes apart, rows row_bytes apart, elements of element_kind (0 half, 1 bfloat16, 2 float: e = 2, 2, 4
+   bytes).  An element x of plane c becomes the texel byte of x * scale[c] (one binary32 multiply) + bias[c] (one binary32
+   add, not fused): 0 for a NaN and anything not above 0, 255 from 255 up, else rounded to nearest, halves to even
+   (plane_quantise.hpp); with three planes A is 255.  The blocks are byte for byte what hapgpu_k_block_encode makes of
+   the RGBA8 pictures of those bytes: RGB_DXT1, RGBA_DXT5, YCoCg_DXT5 (with_alpha: + the RGTC1 plane of A to the second
+   outputs) or A_RGTC1.  scale and bias: `channels` floats each, in host memory, copied by the call.  Tensors, plane_bytes
+   and row_bytes aligned to the 4 * e bytes a lane loads per row; row_bytes at least width * e, plane_bytes at least
+   row_bytes * (height - 1) + width * e; at most 65535 block rows.  Outputs aligned to their blocks.  Timed as
+   HapGpuKernel_BlockEncode.  Returns 0 launched, 1 bad arguments, 4 launch failure. */
+int hapgpu_k_block_encode_planes(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, unsigned width,
+                                 unsigned height, unsigned hap_texture_format, int with_alpha, unsigned channels,
+                                 unsigned element_kind, size_t plane_bytes, size_t row_bytes, const float *scale,
+                                 const float *bias);
 /* [device] Addresses of a transcode launch, as HapGpuPictureTable's: source textures, source alpha planes, destination
    textures, destination alpha planes (Hap Q Alpha's second texture). */
 typedef struct HapGpuTranscodeTable {

@@ -222,7 +222,8 @@ unsigned int HapGpuDecompressRGBAScaled(HapGpuContext *context,
                                         unsigned int width, unsigned int height, unsigned int scaleLog2,
                                         void *rgba, unsigned long rowBytes);
 
-/* What the elements of a planar tensor are (HapGpuDecompressPlanes, HapGpuDecodeFramesPlanes): 2, 2 and 4 bytes */
+/* What the elements of a planar tensor are (HapGpuDecompressPlanes, HapGpuDecodeFramesPlanes, HapGpuCompressPlanes,
+ * HapGpuEncodeFramesPlanes): 2, 2 and 4 bytes */
 enum HapGpuPlaneElement { HapGpuPlaneElement_F16 = 0, HapGpuPlaneElement_BF16 = 1, HapGpuPlaneElement_F32 = 2 };
 
 /* The same texture -> one planar float tensor in DEVICE memory, for a consumer that is a model, a filter or an analysis
@@ -244,8 +245,8 @@ enum HapGpuPlaneElement { HapGpuPlaneElement_F16 = 0, HapGpuPlaneElement_BF16 = 
  * slice of a larger tensor, with longer rows and planes, qualifies).  Only the elements are written, nothing between
  * rows or planes.  Bad_Arguments, and nothing written, for anything else: a NULL, host or misaligned tensor, channels
  * other than 3 or 4, an element or scaleLog2 outside the above, a NULL scale or bias.
- * Out of scope: RGBA_BPTC_UNORM (BC7), the BC6H formats and a lone A_RGTC1 as sources (Bad_Arguments), rectangles, host
- * tensors, and the way back (encoding from planar float tensors). */
+ * Out of scope: RGBA_BPTC_UNORM (BC7), the BC6H formats and a lone A_RGTC1 as sources (Bad_Arguments), rectangles and host
+ * tensors.  The way back, from a planar float tensor to a texture, is HapGpuCompressPlanes. */
 unsigned int HapGpuDecompressPlanes(HapGpuContext *context,
                                     const void *texture, unsigned long textureBytes, unsigned int textureFormat,
                                     const void *alphaTexture, unsigned long alphaTextureBytes,
@@ -253,6 +254,42 @@ unsigned int HapGpuDecompressPlanes(HapGpuContext *context,
                                     unsigned int channels, unsigned int element,
                                     void *planes, unsigned long planeBytes, unsigned long rowBytes,
                                     const float *scale, const float *bias);
+
+/* The way back: one planar float tensor in DEVICE memory -> one block-compressed texture, for a producer that is a model,
+ * a filter or a colour pass -- `channels` planes (3: R, G, B; 4: R, G, B, A) of width x height elements, planes planeBytes
+ * apart, rows rowBytes apart, scaled and shifted per channel and quantised by the block encoder itself as it loads them:
+ * no RGBA8 picture is written or read back.
+ * The definition.  For an element of plane c at a texel, with x its value as binary32 (the conversion from half or
+ * bfloat16 is exact; subnormal inputs are kept, not flushed):
+ *     t = x * scale[c]      one IEEE binary32 multiply, round to nearest even
+ *     r = t + bias[c]       one IEEE binary32 add, round to nearest even: NOT a fused multiply-add (two roundings, not fused)
+ *     v = 0                 if not (r > 0): NaN -> 0, and so -0, everything negative and -Inf
+ *         255               if r >= 255: +Inf too
+ *         rint(r)           otherwise: to nearest, halves to even (0.5 -> 0, 1.5 -> 2, 254.5 -> 254)
+ * numpy's r = x.astype(float32) * float32(s) + float32(b); v = where(isnan(r), 0, clip(rint(r), 0, 255)).  scale and bias
+ * point to `channels` finite floats each, which the call does not check.  With channels 3, A is 255 wherever a format
+ * wants alpha (what HapGpuTranscodeTexture does for a source without alpha).  The picture of a tensor is the RGBA8
+ * picture of these bytes, and the texture is byte for byte what HapGpuCompressRGBA makes of that picture.  It is the
+ * inverse of HapGpuDecompressPlanes: a byte decoded with scale 1/255, bias 0 and quantised with scale 255, bias 0 comes
+ * back, through F16, BF16 and F32 alike.
+ * textureFormat: RGB_DXT1, RGBA_DXT5, YCoCg_DXT5 or A_RGTC1 (the fourth plane, or the constant 255 with three); only the
+ * planes the format looks at are read.  output is host or device, under HapGpuCompressRGBA's rules (a device output
+ * aligned to its blocks; too small: Buffer_Too_Small).  width and height multiples of 4, at most 65535 block rows.
+ * Alignment: with e the element's size, the tensor's address, rowBytes and planeBytes are multiples of 4 * e, what a lane
+ * loads per row; rowBytes is at least width * e and planeBytes at least rowBytes * (height - 1) + width * e (a slice of a
+ * larger tensor, with longer rows and planes, qualifies).  Only the elements are read.  Bad_Arguments, and nothing
+ * written, for anything else: a NULL, host or misaligned tensor, channels other than 3 or 4, an element outside the
+ * enum, a NULL scale or bias, another format.
+ * Out of scope: RGBA_BPTC_UNORM (BC7) and the BC6H formats as destinations (HAPGPU_ENCODE_BPTC_BLOCKS has no form
+ * here), a one-plane tensor as a Hap Alpha-Only source (HapGpuCompressAlpha takes A8), host tensors, and scaled or
+ * rectangular sources. */
+unsigned int HapGpuCompressPlanes(HapGpuContext *context,
+                                  const void *planes, unsigned long planeBytes, unsigned long rowBytes,
+                                  unsigned int channels, unsigned int element,
+                                  const float *scale, const float *bias,
+                                  unsigned int width, unsigned int height, unsigned int textureFormat,
+                                  void *output, unsigned long outputBytes,
+                                  unsigned long *outputBytesUsed);
 
 /* The same texture -> the RGBA8 picture of one block-aligned rectangle of it, regionWidth x regionHeight: byte for byte
  * the crop of what HapGpuDecompressRGBA writes, from the rectangle's blocks alone (no other block of the texture or of
@@ -596,8 +633,8 @@ unsigned int HapGpuDecodeFramesRGBAScaled(HapGpuContext *context, unsigned int f
  * that breaks the alignment rule or is too short.  A context between HapGpuEncodeFramesRGBABegin and
  * HapGpuEncodeFramesFinish: Internal_Error.
  * Out of scope: Hap R (BC7), Hap HDR (BC6H) and Hap Alpha-Only (a lone A_RGTC1) frames -- Bad_Arguments alone, with or
- * without HAPGPU_DECODE_BPTC_PICTURES --, rectangles, host tensors, ...OnDevices and ...Sequence forms of this call, and
- * the way back: encoding from planar float tensors. */
+ * without HAPGPU_DECODE_BPTC_PICTURES --, rectangles, host tensors, ...OnDevices and ...Sequence forms of this call.
+ * The way back, from planar float tensors to frames, is HapGpuEncodeFramesPlanes. */
 unsigned int HapGpuDecodeFramesPlanes(HapGpuContext *context, unsigned int frameCount,
                                       const void *const *inputBuffers,
                                       const unsigned long *inputBuffersBytes,
@@ -609,6 +646,64 @@ unsigned int HapGpuDecodeFramesPlanes(HapGpuContext *context, unsigned int frame
                                       const float *scale, const float *bias,
                                       unsigned int *results,
                                       unsigned int flags);
+
+/* Planar float tensors in, frames out -- the way back of HapGpuDecodeFramesPlanes: HapGpuEncodeFramesRGBA with the tensors of
+ * HapGpuCompressPlanes in place of pictures.  planeFrames[f] is frame f's tensor in DEVICE memory, `channels` planes of
+ * width x height elements, planeBytes and rowBytes shared by all frames (one N x C x H x W tensor: planeFrames[f] = base +
+ * f * channels * planeBytes).  The definition is HapGpuCompressPlanes': per element one binary32 multiply by scale[c],
+ * then one binary32 add of bias[c] (two roundings, not fused), then NaN -> 0, anything not above 0 -> 0, 255 and above ->
+ * 255, else to nearest with halves to even (0.5 -> 0, 1.5 -> 2); with channels 3, A is 255.  Every frame is byte for byte,
+ * and in outputBuffersBytesUsed, what HapGpuEncodeFramesRGBA makes of the tensor's picture with the same count,
+ * textureFormats, compressors, chunkCounts and flags.  No RGBA8 picture ever exists: per Hap Q block 96 bytes are read
+ * from three half planes and 16 written, where converting with a tensor library first reads 96, writes 64 and reads 64
+ * again.  The block encoder runs as a pass of its own in front of the second stage (the road RGB_DXT1 takes from RGBA8
+ * pictures), never inside the fused compress kernel.
+ * count 1: RGB_DXT1 (Hap), RGBA_DXT5 (Hap Alpha), YCoCg_DXT5 (Hap Q) or A_RGTC1 (Hap Alpha-Only, from the fourth plane);
+ * count 2: YCoCg_DXT5 then A_RGTC1 (Hap Q Alpha), both textures from one pass over the planes.  Second stage, frame
+ * layout, chunk limiting, store-raw decisions, Buffer_Too_Small and every encode flag are HapGpuEncodeFrames';
+ * HAPGPU_ENCODE_BPTC_BLOCKS is ignored.  scale and bias point to `channels` floats each and are copied by the call.
+ * Alignment as for HapGpuCompressPlanes.  ...Begin is the first half of the call as HapGpuEncodeFramesRGBABegin is (at
+ * most 32768 frames; scale and bias need live no longer than the other argument arrays); HapGpuEncodeFramesFinish
+ * finishes it.
+ * Bad_Arguments for the whole call -- every results[f] set, nothing written, no device touched -- for a NULL array, scale
+ * or bias, a width or height that is no multiple of 4, channels other than 3 or 4, an element outside the enum, a
+ * rowBytes or planeBytes that breaks the alignment rule or is too short, more than 65535 block rows, a set of formats
+ * outside the above.  A frame whose tensor is NULL, in host memory or misaligned is Bad_Arguments alone, its output
+ * buffer untouched, and the other frames are encoded.  The function's result is the first failure.  A context between a
+ * ...Begin and HapGpuEncodeFramesFinish: Internal_Error.
+ * Out of scope: Hap R (BC7) and Hap HDR (BC6H) destinations, a one-plane tensor as a Hap Alpha-Only source, host
+ * tensors, scaled or rectangular sources, ...OnDevices and ...Sequence forms of this call, and reading the planes inside
+ * the fused compress kernel. */
+unsigned int HapGpuEncodeFramesPlanes(HapGpuContext *context, unsigned int frameCount,
+                                      const void *const *planeFrames,
+                                      unsigned int channels, unsigned int element,
+                                      unsigned long planeBytes, unsigned long rowBytes,
+                                      const float *scale, const float *bias,
+                                      unsigned int width, unsigned int height,
+                                      unsigned int count,
+                                      const unsigned int *textureFormats,
+                                      const unsigned int *compressors,
+                                      const unsigned int *chunkCounts,
+                                      void *const *outputBuffers,
+                                      const unsigned long *outputBuffersBytes,
+                                      unsigned long *outputBuffersBytesUsed,
+                                      unsigned int *results,
+                                      unsigned int flags);
+unsigned int HapGpuEncodeFramesPlanesBegin(HapGpuContext *context, unsigned int frameCount,
+                                           const void *const *planeFrames,
+                                           unsigned int channels, unsigned int element,
+                                           unsigned long planeBytes, unsigned long rowBytes,
+                                           const float *scale, const float *bias,
+                                           unsigned int width, unsigned int height,
+                                           unsigned int count,
+                                           const unsigned int *textureFormats,
+                                           const unsigned int *compressors,
+                                           const unsigned int *chunkCounts,
+                                           void *const *outputBuffers,
+                                           const unsigned long *outputBuffersBytes,
+                                           unsigned long *outputBuffersBytesUsed,
+                                           unsigned int *results,
+                                           unsigned int flags);
 
 /* Hap HDR frames in, RGBA16F pictures out: HapGpuDecodeFramesRGBA for frames of one BC6H texture (unsigned or
  * signed; a batch may mix the two: one block-decode launch per signedness present), pictures as
