@@ -60,6 +60,8 @@ def _load():
         "HapGpuDecompressRGBAScaled": (u, [vp, vp, ul, u, vp, ul, u, u, u, vp, ul]),
         "HapGpuDecompressPlanes": (u, [vp, vp, ul, u, vp, ul, u, u, u, u, u, vp, ul, ul, P(C.c_float), P(C.c_float)]),
         "HapGpuDecompressRGBARegion": (u, [vp, vp, ul, u, vp, ul, u, u, u, u, u, u, vp, ul]),
+        "HapGpuDecompressPlanesRegion": (u, [vp, vp, ul, u, vp, ul, u, u, u, u, u, u, u, u, u, vp, ul, ul, P(C.c_float),
+                                             P(C.c_float)]),
         "HapGpuRegionNeedsBytes": (u, [u, u, u, u, u, u, ul, ul]),
         "HapGpuSkippedTextureBytes": (ul, [vp]),
         "HapGpuDecompressRGBAHalf": (u, [vp, vp, ul, u, u, u, vp, ul]),
@@ -82,6 +84,8 @@ def _load():
                                               P(u), P(vp), P(ul), P(ul), P(u), u]),
         "HapGpuDecodeFramesPlanes": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, u, u, ul, ul, P(C.c_float), P(C.c_float), P(u), u]),
         "HapGpuDecodeFramesRGBARegion": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, u, u, u, ul, P(u), u]),
+        "HapGpuDecodeFramesPlanesRegion": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, P(u), P(u), u, u, u, u, u, ul, ul,
+                                               P(C.c_float), P(C.c_float), P(u), u]),
         "HapGpuTranscodeTexture": (u, [vp, vp, ul, u, vp, ul, u, u, u, u, P(u), P(vp), P(ul), P(ul)]),
         "HapGpuTranscodeFrames": (u, [vp, u, P(vp), P(ul), u, u, u, u, u, P(u), P(u), P(u), P(vp), P(ul), P(ul), P(u), u, u]),
         "HapGpuDecodeFramesRGBAHalf": (u, [vp, u, P(vp), P(ul), P(vp), u, u, ul, P(u), u]),

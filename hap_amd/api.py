@@ -448,6 +448,21 @@ class Context:
         return lib.HapGpuDecompressPlanes(self.handle, ta, tn, texture_format, aa, an, width, height, scale_log2, channels,
                                           element, tensors[0].data_ptr(), plane_bytes, row_bytes, sc, bi)
 
+    def decompress_planes_region(self, texture, texture_format, width, height, region, out, scale_log2=0, scale=None,
+                                 bias=None, alpha=None):
+        """Texture (+ optional RGTC1 alpha plane) -> `out`, the (C, h >> scale_log2, w >> scale_log2) tensor of region =
+        (x, y, w, h), a block-aligned rectangle of the texture: bit for bit that crop of decompress_planes' tensor, from
+        the rectangle's blocks alone (HapGpuDecompressPlanesRegion).  `out`, scale and bias as for decompress_planes.
+        Returns the result."""
+        x, y, w, h = region
+        tensors, channels, element, plane_bytes, row_bytes = _plane_tensors(out, True, w, h, scale_log2)
+        sc, bi = _plane_constants(scale, bias, channels)
+        ta, tn, _k = _addr_len(texture)
+        aa, an, _k2 = _addr_len(alpha) if alpha is not None else (None, 0, None)
+        return lib.HapGpuDecompressPlanesRegion(self.handle, ta, tn, texture_format, aa, an, width, height, x, y, w, h,
+                                                scale_log2, channels, element, tensors[0].data_ptr(), plane_bytes,
+                                                row_bytes, sc, bi)
+
     def compress_planes(self, planes, width, height, texture_format, scale=None, bias=None, output=None):
         """`planes`, a (C, height, width) float16, bfloat16 or float32 torch tensor on the device, C 3 or 4 -> one block
         texture (HapGpuCompressPlanes): byte = float32(element) * scale[c] + bias[c] (two roundings), NaN and anything
@@ -766,6 +781,33 @@ class Context:
         results = (C.c_uint * nf)()
         r = lib.HapGpuDecodeFramesPlanes(self.handle, nf, ptrs, lens, texture_count, optrs, width, height, scale_log2,
                                          channels, element, plane_bytes, row_bytes, sc, bi, results, flags)
+        return r, list(results)
+
+    def decode_frames_planes_region(self, frames, frame_bytes, texture_count, out, width, height, origins, region_size,
+                                    scale_log2=0, scale=None, bias=None, flags=0):
+        """Frames -> normalised planar tensors of a crop per frame in one call (HapGpuDecodeFramesPlanesRegion): frame f's
+        tensor is, bit for bit, the crop of decode_frames_planes' at origins[f] = (x, y), of region_size = (w, h) texels
+        of the frames' width x height, all multiples of 4.  `out`: as for decode_frames_planes, but of the rectangle's
+        scaled size, (N, C, h >> scale_log2, w >> scale_log2); scale and bias likewise.  Pieces of a frame that hold none
+        of its rectangle's blocks stay undecoded (skipped_texture_bytes).  Returns (result, results[])."""
+        nf = len(frames)
+        w, h = region_size
+        origins = [tuple(o) for o in origins]
+        if len(origins) != nf or any(len(o) != 2 for o in origins):
+            raise ValueError("one origin per frame")
+        tensors, channels, element, plane_bytes, row_bytes = _plane_tensors(out, False, w, h, scale_log2)
+        if len(tensors) != nf:
+            raise ValueError("one tensor per frame")
+        sc, bi = _plane_constants(scale, bias, channels)
+        ptrs, infos = self._ptr_array(frames)
+        lens = (C.c_ulong * nf)(*[fb if fb is not None else infos[i][1] for i, fb in enumerate(frame_bytes)])
+        optrs = (C.c_void_p * nf)(*[None if t is None else t.data_ptr() for t in tensors])
+        xs = (C.c_uint * nf)(*[o[0] for o in origins])
+        ys = (C.c_uint * nf)(*[o[1] for o in origins])
+        results = (C.c_uint * nf)()
+        r = lib.HapGpuDecodeFramesPlanesRegion(self.handle, nf, ptrs, lens, texture_count, optrs, width, height, xs, ys,
+                                               w, h, scale_log2, channels, element, plane_bytes, row_bytes, sc, bi,
+                                               results, flags)
         return r, list(results)
 
     def transcode_texture(self, texture, texture_format, width, height, scale_log2, output_formats, alpha=None,

@@ -596,6 +596,27 @@ unsigned int HapGpuDecompressPlanes(HapGpuContext *context, const void *texture,
     return r;
 }
 
+/* HapGpuDecompressPlanes of a block-aligned rectangle of the texture */
+unsigned int HapGpuDecompressPlanesRegion(HapGpuContext *context, const void *texture, unsigned long textureBytes,
+                                          unsigned int textureFormat, const void *alphaTexture,
+                                          unsigned long alphaTextureBytes, unsigned int width, unsigned int height,
+                                          unsigned int regionX, unsigned int regionY, unsigned int regionWidth,
+                                          unsigned int regionHeight, unsigned int scaleLog2, unsigned int channels,
+                                          unsigned int element, void *planes, unsigned long planeBytes,
+                                          unsigned long rowBytes, const float *scale, const float *bias)
+{
+    const HapbPlanes layout = {channels, element, planeBytes, scale, bias};
+    const HapGpuRegion region = {width, regionX, regionY, regionWidth, regionHeight};
+    unsigned r;
+    if (!context || !planes_arguments_valid(scaleLog2, channels, element, scale, bias) || !hapb_region_fits(&region, height))
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_decompress_planes_region(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width,
+                                      height, &region, scaleLog2, planes, rowBytes, &layout);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
 unsigned int HapGpuDecompressRGBAHalf(HapGpuContext *context, const void *texture, unsigned long textureBytes,
                                       unsigned int textureFormat, unsigned int width, unsigned int height,
                                       void *rgbaHalf, unsigned long rowBytes)
@@ -1129,6 +1150,37 @@ unsigned int HapGpuDecodeFramesPlanes(HapGpuContext *context, unsigned int frame
     /* (Hap R frames are out of scope with or without the flag that asks for their pictures: the road has no BC7) */
     r = hapb_decode_planes(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, planeFrames, width, height,
                            scaleLog2, rowBytes, &layout, results, flags);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+/* HapGpuDecodeFramesPlanes of a block-aligned rectangle of every frame, frame f's at (regionXs[f], regionYs[f]); a size
+   that is no rectangle of the frames refuses the whole call, an origin that puts it outside refuses its frame */
+unsigned int HapGpuDecodeFramesPlanesRegion(HapGpuContext *context, unsigned int frameCount,
+                                            const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
+                                            unsigned int textureCount, void *const *planeFrames, unsigned int width,
+                                            unsigned int height, const unsigned int *regionXs,
+                                            const unsigned int *regionYs, unsigned int regionWidth,
+                                            unsigned int regionHeight, unsigned int scaleLog2, unsigned int channels,
+                                            unsigned int element, unsigned long planeBytes, unsigned long rowBytes,
+                                            const float *scale, const float *bias, unsigned int *results,
+                                            unsigned int flags)
+{
+    const HapbPlanes layout = {channels, element, planeBytes, scale, bias};
+    const HapGpuRegion size = {width, 0u, 0u, regionWidth, regionHeight};
+    unsigned r, f;
+    if (!context)
+        return HapResult_Bad_Arguments;
+    if (!planes_arguments_valid(scaleLog2, channels, element, scale, bias) || !regionXs || !regionYs ||
+        !hapb_region_fits(&size, height)) {
+        for (f = 0; results && f < frameCount; f++)
+            results[f] = HapResult_Bad_Arguments;
+        return HapResult_Bad_Arguments;
+    }
+    hapgpu_rt_lock(context->rt);
+    r = hapb_decode_planes_region(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, planeFrames, width,
+                                  height, regionXs, regionYs, regionWidth, regionHeight, scaleLog2, rowBytes, &layout,
+                                  results, flags);
     hapgpu_rt_unlock(context->rt);
     return r;
 }

@@ -841,8 +841,13 @@ typedef struct picture_road {
     const HapGpuRegion *region; /* NULL: the whole of every texture; else (RGBA8 only, scale_log2 0) pictures of region->w x
                                    region->h, that rectangle of every texture, by hapgpu_k_block_decode_region */
     const HapbPlanes *planes;   /* NULL: interleaved pictures of picture_kind; else planar tensors in device memory
-                                   (scale_log2 0 to 2, no region), by hapgpu_k_block_decode_planes: a "texel" is then one
-                                   element of one plane and row_bytes the pitch of a plane's rows */
+                                   (scale_log2 0 to 2), by hapgpu_k_block_decode_planes: a "texel" is then one
+                                   element of one plane and row_bytes the pitch of a plane's rows.  With a region: tensors
+                                   of (region->w >> scale_log2) x (region->h >> scale_log2), that rectangle of every
+                                   texture, by hapgpu_k_block_decode_planes_region */
+    const unsigned *region_xs, *region_ys;  /* NULL: region->x, region->y for every frame; else (planes only, frames only)
+                                   frame f's rectangle begins at (region_xs[f], region_ys[f]), f counted from the call's
+                                   first frame, and region->x, region->y are 0 */
 } picture_road;
 
 /* RGBA8 pictures (BC7 last: frames of it only with HAPGPU_DECODE_BPTC_PICTURES), RGBA16F ones and A8 ones */
@@ -854,17 +859,24 @@ static const unsigned k_alpha_kinds[1] = {HapTextureFormat_A_RGTC1};
 static picture_road road_of(unsigned picture_kind, unsigned flags, unsigned scale_log2, const HapGpuRegion *region)
 {
     if (picture_kind == HAPGPU_PICTURE_RGBA16F)
-        return (picture_road){2u, k_half_kinds, 0u, picture_kind, 0u, NULL, NULL};
+        return (picture_road){2u, k_half_kinds, 0u, picture_kind, 0u, NULL, NULL, NULL, NULL};
     if (picture_kind == HAPGPU_PICTURE_A8)
-        return (picture_road){1u, k_alpha_kinds, 0u, picture_kind, 0u, NULL, NULL};
+        return (picture_road){1u, k_alpha_kinds, 0u, picture_kind, 0u, NULL, NULL, NULL, NULL};
     return (picture_road){(flags & HAPGPU_DECODE_BPTC_PICTURES) ? 4u : 3u, k_rgba_kinds, 0x7u, picture_kind,
-                          region ? 0u : scale_log2, region, NULL};
+                          region ? 0u : scale_log2, region, NULL, NULL, NULL};
 }
 
 /* ... and to planar tensors: the RGBA8 road's DXT formats (never BC7) at any of the three sizes */
 static picture_road planes_road_of(unsigned scale_log2, const HapbPlanes *planes)
 {
-    return (picture_road){3u, k_rgba_kinds, 0x7u, HAPGPU_PICTURE_RGBA8, scale_log2, NULL, planes};
+    return (picture_road){3u, k_rgba_kinds, 0x7u, HAPGPU_PICTURE_RGBA8, scale_log2, NULL, planes, NULL, NULL};
+}
+
+/* ... of a rectangle of every texture: region's for all (xs and ys NULL), or region's size at an origin per frame */
+static picture_road planes_region_road_of(unsigned scale_log2, const HapbPlanes *planes, const HapGpuRegion *region,
+                                          const unsigned *xs, const unsigned *ys)
+{
+    return (picture_road){3u, k_rgba_kinds, 0x7u, HAPGPU_PICTURE_RGBA8, scale_log2, region, planes, xs, ys};
 }
 
 /* bytes of what a road's row_bytes counts: a texel of an interleaved picture, an element of a plane */
@@ -878,12 +890,12 @@ static size_t picture_texel_bytes(const picture_road *road)
 /* the geometry of a road's pictures, from the textures' */
 static unsigned picture_width_of(const picture_road *road, unsigned width)
 {
-    return road->region ? road->region->w : width >> road->scale_log2;
+    return (road->region ? road->region->w : width) >> road->scale_log2;
 }
 
 static unsigned picture_height_of(const picture_road *road, unsigned height)
 {
-    return road->region ? road->region->h : height >> road->scale_log2;
+    return (road->region ? road->region->h : height) >> road->scale_log2;
 }
 
 /* 1: the region is a block-aligned rectangle inside width x height (hap_region.h's rules and the texture's height) */
@@ -915,11 +927,26 @@ static int planes_fit(const picture_road *road, size_t pixel_row, unsigned pictu
            p->plane_bytes >= (size_t)row_bytes * (picture_height - 1u) + pixel_row;
 }
 
-/* the block-decode launch of a road: pictures of the frames' size, scaled ones, a rectangle's, or planar tensors (the
-   alpha plane is read only where a fourth plane is written) */
-static int launch_block_decode(hapgpu_rt *rt, const picture_road *road, const HapGpuPictureTable *t, unsigned pictures,
-                               int with_alpha, unsigned width, unsigned height, unsigned format, size_t row_bytes, int wide)
+/* the texture block a rectangle begins at */
+static uint32_t region_first_block(unsigned width, unsigned x, unsigned y)
 {
+    return (uint32_t)((y / 4u) * (width / 4u) + x / 4u);
+}
+
+/* the block-decode launch of a road: pictures of the frames' size, scaled ones, a rectangle's, or planar tensors (the
+   alpha plane is read only where a fourth plane is written).  origins: a planar road with a rectangle per frame -- the
+   device array of the pictures' first blocks */
+static int launch_block_decode(hapgpu_rt *rt, const picture_road *road, const HapGpuPictureTable *t, unsigned pictures,
+                               int with_alpha, unsigned width, unsigned height, unsigned format, size_t row_bytes, int wide,
+                               const uint32_t *origins)
+{
+    if (road->planes && road->region)
+        return hapgpu_k_block_decode_planes_region(rt, t, pictures, with_alpha && road->planes->channels == 4u, width, height,
+                                                   format, origins,
+                                                   origins ? 0u : region_first_block(width, road->region->x, road->region->y),
+                                                   road->region->w, road->region->h, road->scale_log2, road->planes->channels,
+                                                   road->planes->element, road->planes->plane_bytes, row_bytes,
+                                                   road->planes->scale, road->planes->bias);
     if (road->planes)
         return hapgpu_k_block_decode_planes(rt, t, pictures, with_alpha && road->planes->channels == 4u, width, height, format,
                                             road->scale_log2, road->planes->channels, road->planes->element,
@@ -999,7 +1026,7 @@ static unsigned decompress_picture(HapGpuContext *ctx, const void *texture, unsi
     t.one[1] = (uint64_t)(uintptr_t)asrc;
     t.one[2] = (uint64_t)(uintptr_t)dst;
     rc = launch_block_decode(rt, &road, &t, 1u, alpha != NULL, width, height, format, row_bytes,
-                             (((uintptr_t)dst | row_bytes) & 15u) == 0 && !ctx->no_wide_planes);
+                             (((uintptr_t)dst | row_bytes) & 15u) == 0 && !ctx->no_wide_planes, NULL);
     if (rc == 1)
         return HapResult_Bad_Arguments;
     if (rc)
@@ -1029,6 +1056,16 @@ unsigned hapb_decompress_planes(HapGpuContext *ctx, const void *texture, unsigne
                                 unsigned scale_log2, void *tensor, unsigned long row_bytes, const HapbPlanes *planes)
 {
     const picture_road road = planes_road_of(scale_log2, planes);
+    return decompress_picture(ctx, texture, texture_bytes, format, alpha, alpha_bytes, width, height, tensor, row_bytes,
+                              &road);
+}
+
+unsigned hapb_decompress_planes_region(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
+                                       const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
+                                       const HapGpuRegion *region, unsigned scale_log2, void *tensor,
+                                       unsigned long row_bytes, const HapbPlanes *planes)
+{
+    const picture_road road = planes_region_road_of(scale_log2, planes, region, NULL, NULL);
     return decompress_picture(ctx, texture, texture_bytes, format, alpha, alpha_bytes, width, height, tensor, row_bytes,
                               &road);
 }
@@ -1405,8 +1442,14 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
     /* (a region call: the rectangle the textures are wanted for -- units that hold none of its blocks are blanked on the
        device, hapgpu_k_skip_units; a texture's block size is its format's, known once the frame is planned) */
     const HapGpuRegion *const region = ctx->decode_region;
+    /* (... or a rectangle per entry, HapGpuDecodeFramesPlanesRegion: they travel behind the job table, a rectangle per
+       job, and the skip looks up the one of a unit's job) */
+    const HapGpuRegion *const entry_regions = ctx->decode_regions;
+    const int skipping = region || entry_regions;
     const int region_counted = !ctx->decode_region_uncounted;
     uint32_t *hblock = NULL, *dblock = NULL;                   /* per job, behind the job tables: the texture's block size */
+    HapGpuRegion *hregion = NULL, *dregion = NULL;             /* ... and behind those, per job: its rectangle (entry_regions) */
+    const size_t job_bytes = sizeof(HapGpuDecodeJob) + sizeof(uint32_t) + sizeof(HapGpuRegion);
 #define TEXTURE_INDEX(f) (entry_index ? entry_index[f] : index)
     const int block_scan = !(flags & HAPGPU_DECODE_NO_BLOCK_SCAN) && !ctx->no_block_scan;
     uint8_t *prefix = NULL, *in_stage = NULL, *out_stage = NULL;
@@ -1431,6 +1474,7 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
 #endif
     ctx->decode_indices = NULL;
     ctx->decode_region = NULL;
+    ctx->decode_regions = NULL;
     ctx->decode_region_uncounted = 0;
     if (frame_count == 0)
         return HapResult_No_Error;
@@ -1796,9 +1840,9 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
     use_scan_guess = fine_total && !(flags & HAPGPU_DECODE_NO_FIELD_GUESS);
 
     /* 3. device descriptors */
-    hjobs = (HapGpuDecodeJob *)hapgpu_rt_pinned_scratch(rt, P_JOBS, (sizeof(HapGpuDecodeJob) + sizeof(uint32_t)) * live);
+    hjobs = (HapGpuDecodeJob *)hapgpu_rt_pinned_scratch(rt, P_JOBS, job_bytes * live);
     hchunks = (HapGpuChunkIn *)hapgpu_rt_pinned_scratch(rt, P_CHUNKS, sizeof(HapGpuChunkIn) * (total_chunks + 1u));
-    djobs = (HapGpuDecodeJob *)hapgpu_rt_device_scratch(rt, D_JOBS, (sizeof(HapGpuDecodeJob) + sizeof(uint32_t)) * live);
+    djobs = (HapGpuDecodeJob *)hapgpu_rt_device_scratch(rt, D_JOBS, job_bytes * live);
     dchunks = (HapGpuChunkIn *)hapgpu_rt_device_scratch(rt, D_CHUNKS, sizeof(HapGpuChunkIn) * (total_chunks + 1u));
     /* (the fine block units of the block scan live behind the ordinary ones: [total_units, total_units + fine_total)) */
     dunits = (HapGpuDecodeUnit *)hapgpu_rt_device_scratch(rt, D_UNITS, sizeof(HapGpuDecodeUnit) * ((size_t)total_units + fine_total + 1u));
@@ -1813,6 +1857,8 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
     }
     hblock = (uint32_t *)(hjobs + live);
     dblock = (uint32_t *)(djobs + live);
+    hregion = (HapGpuRegion *)(hblock + live);
+    dregion = (HapGpuRegion *)(dblock + live);
     if (scan_chunks) {
         /* one arena: chunk table | segment summaries | block positions | fine work list | joins | window records */
         const size_t o_segs = align_up(sizeof(HapGpuScanChunk) * scan_chunks, 64);
@@ -1882,7 +1928,9 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
             job->unit_count = units;
             job->units = (uint64_t)(uintptr_t)(dunits + unit_cursor);
             job->status = HapResult_Internal_Error;
-            hblock[job_of_frame[f]] = region ? (uint32_t)hapf_block_bytes(p->format) : 0u;
+            hblock[job_of_frame[f]] = skipping ? (uint32_t)hapf_block_bytes(p->format) : 0u;
+            if (entry_regions)
+                hregion[job_of_frame[f]] = entry_regions[f];
             if (p->mode == HAPGPU_JOB_COMPLEX) {
                 job->payload = (uint64_t)(uintptr_t)(frame_dev + p->payload_offset);
                 job->payload_len = p->payload_length;
@@ -1942,13 +1990,15 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
             unit_cursor += units;
         }
         HAPB_MARK("host plan");
-        rc |= hapgpu_rt_h2d(rt, djobs, hjobs, (sizeof(HapGpuDecodeJob) + (region ? sizeof(uint32_t) : 0u)) * live);
+        rc |= hapgpu_rt_h2d(rt, djobs, hjobs, (entry_regions ? job_bytes : sizeof(HapGpuDecodeJob) + (region ? sizeof(uint32_t) : 0u)) * live);
         if (total_chunks)
             rc |= hapgpu_rt_h2d(rt, dchunks, hchunks, sizeof(HapGpuChunkIn) * total_chunks);
         rc |= hapgpu_k_decode_plan(rt, djobs, live, dunits, total_units, frag_log2_seen ? max_chunks : 0u);
         /* a region call: the chunks, table fragments and raw pieces that hold none of the rectangle's blocks go here --
            in front of the block scan, so that a chunk nobody needs is not scanned either (the scan looks at STREAM units) */
-        if (region)
+        if (entry_regions)
+            rc |= hapgpu_k_skip_units_per_job(rt, dunits, total_units, djobs, dblock, dregion, region_counted);
+        else if (region)
             rc |= hapgpu_k_skip_units(rt, dunits, total_units, djobs, dblock, region, region_counted);
 
         /* hap.h callback contract (single-frame HapDecode only): the client is asked to "run" the
@@ -2018,13 +2068,15 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
             rc |= hapgpu_rt_zero(rt, dwork, sizeof(uint32_t));
             if (fine_total)
                 rc |= hapgpu_rt_zero(rt, dwork + 1u + fine_total, sizeof(uint32_t));
-            if ((frag_kinds & 0x1000u) || (region && fine_total))       /* (the decoder below walks all the pieces' slots, not only the listed ones) */
+            if ((frag_kinds & 0x1000u) || (skipping && fine_total))       /* (the decoder below walks all the pieces' slots, not only the listed ones) */
                 rc |= hapgpu_rt_zero(rt, dunits + total_units, sizeof(HapGpuDecodeUnit) * (size_t)fine_total);
             rc |= hapgpu_k_scan_blocks(rt, dunits, djobs, dscan, scan_chunks, dsegs, drecs, djoins, scan_segs,
                                        fine_total ? dwork : NULL, total_units, fine_total);
             /* ... and the 64 KiB and 8 KiB blocks the scan found: in front of the table maker below, which makes no
                table for a piece that is blanked */
-            if (region)
+            if (entry_regions)
+                rc |= hapgpu_k_skip_units_per_job(rt, dunits, total_units + fine_total, djobs, dblock, dregion, region_counted);
+            else if (region)
                 rc |= hapgpu_k_skip_units(rt, dunits, total_units + fine_total, djobs, dblock, region, region_counted);
         }
         if (dguess && use_guess)
@@ -2092,6 +2144,7 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
             /* (a region call skips again on this road: whole chunks and raw pieces, all it has without table and scan --
                no more than the first pass skipped of this frame, and counted there) */
             ctx->decode_region = region;
+            ctx->decode_regions = entry_regions ? &entry_regions[f] : NULL;      /* (the frame's own rectangle) */
             ctx->decode_region_uncounted = 1;
             hapb_decode(ctx, 1, &inputs[f], &input_bytes[f], TEXTURE_INDEX(f), &outputs[f], &output_bytes[f],
                         output_used ? &output_used[f] : NULL, output_formats ? &output_formats[f] : NULL,
@@ -2156,6 +2209,9 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
                                                               road->region->w == width && road->region->h == height)
                                                 ? road->region : NULL;
     const unsigned align = picture_align_mask(road);
+    /* (a rectangle per frame: the entries' rectangles for hapb_decode, a slice's at a time) */
+    const int per_frame_regions = road->region_xs != NULL;
+    HapGpuRegion *regs = NULL;
     if (frame_count == 0)
         return HapResult_No_Error;
     if (!results)
@@ -2186,8 +2242,10 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
     in_bytes = (unsigned long *)malloc(sizeof(*in_bytes) * slice * texture_count * 3u);
     outs = (void **)malloc(sizeof(*outs) * slice * texture_count);
     idx = (unsigned *)malloc(sizeof(*idx) * slice * texture_count * 3u);
-    if (!in || !in_bytes || !outs || !idx) {
-        free(in); free(in_bytes); free(outs); free(idx);
+    if (per_frame_regions)
+        regs = (HapGpuRegion *)malloc(sizeof(*regs) * slice * texture_count);
+    if (!in || !in_bytes || !outs || !idx || (per_frame_regions && !regs)) {
+        free(in); free(in_bytes); free(outs); free(idx); free(regs);
         for (f = 0; f < frame_count; f++)
             results[f] = HapResult_Internal_Error;
         return HapResult_Internal_Error;
@@ -2201,17 +2259,36 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
         uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, per_frame * n);
         uint8_t *stage = NULL;
         unsigned t;
-        int rc = 0;
+        int rc = 0, any_skip = 0;
         if (!textures) {
             for (f = 0; f < n; f++)
                 results[done + f] = HapResult_Internal_Error;
             first_error = first_error ? first_error : HapResult_Internal_Error;
             continue;
         }
-        for (f = 0; f < n; f++)
+        for (f = 0; f < n; f++) {
+            /* (frame done + f of the call: the rectangle arrays are the call's, not the slice's) */
+            const HapGpuRegion whole = {width, 0u, 0u, width, height};
+            HapGpuRegion own = whole;
+            int refused = 0;
+            if (per_frame_regions) {
+                own.x = road->region_xs[done + f];
+                own.y = road->region_ys[done + f];
+                own.w = road->region->w;
+                own.h = road->region->h;
+                /* a frame whose origin puts the rectangle off the grid or past an edge: Bad_Arguments alone, and nothing
+                   of it goes to the second stage or the block decoder -- a NULL input is hapb_decode's Bad_Arguments */
+                refused = !hapb_region_fits(&own, height);
+                if (refused)
+                    own = whole;
+                else if (own.x != 0u || own.y != 0u || own.w != width || own.h != height)
+                    any_skip = 1;
+            }
             for (t = 0; t < texture_count; t++) {
                 const size_t e = (size_t)f * texture_count + t;
-                in[e] = inputs[done + f];
+                if (regs)
+                    regs[e] = own;
+                in[e] = refused ? NULL : inputs[done + f];
                 in_bytes[e] = input_bytes[done + f];
                 outs[e] = textures + per_frame * f + (t ? alpha_off : 0u);
                 caps[e] = (unsigned long)(t ? blocks * 8u : blocks * 16u);
@@ -2219,16 +2296,23 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
                 used[e] = 0;
                 fmts[e] = 0;
             }
+        }
         ctx->decode_indices = idx;
-        ctx->decode_region = skip_region;
+        ctx->decode_region = per_frame_regions ? NULL : skip_region;
+        /* (rectangles that are all the whole frame skip nothing; one that is among others needs everything) */
+        ctx->decode_regions = any_skip ? regs : NULL;
         hapb_decode(ctx, n * texture_count, in, in_bytes, 0, outs, caps, used, fmts, res, flags & ~HAPGPU_DECODE_BPTC_PICTURES,
                     NULL, NULL);
         {
             /* one block-decode launch per texture format present in the slice: [textures][alpha planes][pictures] in a
                small device table, pictures of other formats (or that failed) with a texture address of 0 */
-            const size_t tab_bytes = sizeof(uint64_t) * 3u * PICTURE_KINDS_MAX * n;
+            /* ... and behind the table, in the same copy, a rectangle per frame's first texture block of every picture */
+            const size_t ptr_words = (size_t)3u * PICTURE_KINDS_MAX * n;
+            const size_t tab_bytes = sizeof(uint64_t) * ptr_words + (per_frame_regions ? sizeof(uint32_t) * n : 0u);
             uint64_t *htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, tab_bytes);
             uint64_t *dtab = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, tab_bytes);
+            uint32_t *horigins = per_frame_regions && htab ? (uint32_t *)(htab + ptr_words) : NULL;
+            const uint32_t *dorigins = per_frame_regions && dtab ? (const uint32_t *)(dtab + ptr_words) : NULL;
             unsigned present = 0, k;
             int wide = (row_bytes & 15u) == 0 && !ctx->no_wide_planes;      /* A8 pictures: every one of the slice 16-byte aligned, and the pitch */
             if (!htab || !dtab) {
@@ -2278,6 +2362,8 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
                     htab[(size_t)k * 3u * n + f] = (uint64_t)(uintptr_t)outs[e];
                     htab[(size_t)k * 3u * n + n + f] = texture_count == 2 ? (uint64_t)(uintptr_t)outs[e + 1] : 0u;
                     htab[(size_t)k * 3u * n + 2u * n + f] = (uint64_t)(uintptr_t)dst;
+                    if (horigins)       /* (inside the frame: a refused origin never gets here) */
+                        horigins[f] = region_first_block(width, road->region_xs[done + f], road->region_ys[done + f]);
                 }
                 results[done + f] = r;
             }
@@ -2288,7 +2374,7 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
                         const uint64_t *col = dtab + (size_t)k * 3u * n;
                         const HapGpuPictureTable t = {{col, col + n, col + 2u * (size_t)n}, {0u, 0u, 0u}};
                         rc |= launch_block_decode(rt, road, &t, n, texture_count == 2, width, height, road->kinds[k], row_bytes,
-                                                  wide);
+                                                  wide, dorigins);
                     }
                 for (f = 0; f < n; f++)
                     if (results[done + f] == HapResult_No_Error && stage && !is_dev(ctx, rgba_frames[done + f])) {
@@ -2311,7 +2397,7 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
             if (results[done + f] != HapResult_No_Error && first_error == HapResult_No_Error)
                 first_error = results[done + f];
     }
-    free(in); free(in_bytes); free(outs); free(idx);
+    free(in); free(in_bytes); free(outs); free(idx); free(regs);
     return first_error;
 }
 
@@ -2345,6 +2431,28 @@ unsigned hapb_decode_planes(HapGpuContext *ctx, unsigned frame_count, const void
                             const HapbPlanes *planes, unsigned *results, unsigned flags)
 {
     const picture_road road = planes_road_of(scale_log2, planes);
+    return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, tensors, width, height, row_bytes,
+                           results, flags, &road);
+}
+
+/* ... and to planar tensors of a rectangle of region_w x region_h of every frame, frame f's at (xs[f], ys[f]): both roads
+   joined -- the planar block decoder over the rectangle's blocks, and a second stage that leaves out, frame by frame,
+   what holds none of that frame's rectangle */
+unsigned hapb_decode_planes_region(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                                   const unsigned long *input_bytes, unsigned texture_count, void *const *tensors,
+                                   unsigned width, unsigned height, const unsigned *xs, const unsigned *ys,
+                                   unsigned region_w, unsigned region_h, unsigned scale_log2, unsigned long row_bytes,
+                                   const HapbPlanes *planes, unsigned *results, unsigned flags)
+{
+    const HapGpuRegion size = {width, 0u, 0u, region_w, region_h};
+    const picture_road road = planes_region_road_of(scale_log2, planes, &size, xs, ys);
+    unsigned f;
+    /* (without origins the road would be the one-rectangle road at (0, 0)) */
+    if ((!xs || !ys) && frame_count && results) {
+        for (f = 0; f < frame_count; f++)
+            results[f] = HapResult_Bad_Arguments;
+        return HapResult_Bad_Arguments;
+    }
     return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, tensors, width, height, row_bytes,
                            results, flags, &road);
 }

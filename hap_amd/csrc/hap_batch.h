@@ -45,6 +45,9 @@ struct HapGpuContext {
     /* the rectangle the next hapb_decode call's textures are wanted for (NULL: all of them): units that hold none of
        its blocks stay undecoded.  Per call, like decode_indices. */
     const HapGpuRegion *decode_region;
+    /* ... or a rectangle per entry of that call (NULL: decode_region for all): an entry that skips nothing carries the
+       whole of its texture.  Per call, like decode_indices. */
+    const HapGpuRegion *decode_regions;
     int decode_region_uncounted;     /* ... and 1 where that call is a frame's second pass, whose first pass has counted
                                         what it skipped (HapGpuSkippedTextureBytes counts a frame once) */
     /* HapGpuEncodeFramesRGBABegin / HapGpuEncodeFramesFinish: the launched half of an encode call whose results have
@@ -131,6 +134,12 @@ unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned 
 unsigned hapb_decompress_planes(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
                                 const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
                                 unsigned scale_log2, void *tensor, unsigned long row_bytes, const HapbPlanes *planes);
+/* ... the rectangle `region` of it (region->width == width) -> one planar tensor of (region->w >> scale_log2) x
+   (region->h >> scale_log2) */
+unsigned hapb_decompress_planes_region(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
+                                       const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
+                                       const HapGpuRegion *region, unsigned scale_log2, void *tensor,
+                                       unsigned long row_bytes, const HapbPlanes *planes);
 /* one planar tensor in device memory -> one texture (host or device): DXT1, DXT5, YCoCg-DXT5, or RGTC1 from the fourth
    plane (255 where there are three) */
 unsigned hapb_compress_planes(HapGpuContext *ctx, const void *tensor, unsigned width, unsigned height,
@@ -188,6 +197,13 @@ unsigned hapb_decode_rgba_region(HapGpuContext *ctx, unsigned frame_count, const
                                  const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
                                  unsigned width, unsigned height, const HapGpuRegion *region, unsigned long row_bytes,
                                  unsigned *results, unsigned flags);
+/* ... a rectangle of region_w x region_h of every frame, frame f's at (xs[f], ys[f]), to planar tensors in device memory of
+   (region_w >> scale_log2) x (region_h >> scale_log2) */
+unsigned hapb_decode_planes_region(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                                   const unsigned long *input_bytes, unsigned texture_count, void *const *tensors,
+                                   unsigned width, unsigned height, const unsigned *xs, const unsigned *ys,
+                                   unsigned region_w, unsigned region_h, unsigned scale_log2, unsigned long row_bytes,
+                                   const HapbPlanes *planes, unsigned *results, unsigned flags);
 /* Hap HDR frames (one BC6H texture) -> RGBA16F pictures */
 unsigned hapb_decode_rgba_half(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
                                const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,

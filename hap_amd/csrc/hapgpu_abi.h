@@ -250,7 +250,7 @@ typedef struct HapGpuDecodeUnit {
     uint64_t reserved;
 } HapGpuDecodeUnit;
 
-/* [device] the rectangle a region call wants of every texture, in texels of a `width`-wide texture (hap_region.h) */
+/* [device] the rectangle a region call wants of a texture, in texels of a `width`-wide texture (hap_region.h) */
 typedef struct HapGpuRegion {
     uint32_t width, x, y, w, h;
 } HapGpuRegion;
@@ -358,6 +358,22 @@ int hapgpu_k_block_decode_planes(hapgpu_rt *rt, const HapGpuPictureTable *table,
                                  unsigned width, unsigned height, unsigned hap_texture_format, unsigned scale_log2,
                                  unsigned channels, unsigned element_kind, size_t plane_bytes, size_t row_bytes,
                                  const float *scale, const float *bias);
+/* ... the rectangle of region_width x region_height (multiples of 4, inside width x height) of every texture to planar
+   tensors of (region_width >> scale_log2) x (region_height >> scale_log2), a different rectangle per picture: bit for bit
+   rows [y >> scale_log2, (y + region_height) >> scale_log2) and columns [x >> scale_log2, (x + region_width) >> scale_log2)
+   of every plane hapgpu_k_block_decode_planes writes (a box mean never spans two blocks).  Where a picture's rectangle
+   begins is a texture block index, (y / 4) * (width / 4) + x / 4: origins[z] for picture z (a DEVICE array; the caller's
+   promise that every rectangle lies inside its texture, as the table's addresses are), or, where origins is NULL, `origin`
+   for all of them (checked).  Lane id is block (bx, by) = (id % (region_width / 4), id / (region_width / 4)) of the
+   rectangle and of its tensor and reads texture (and alpha plane) block origin + by * (width / 4) + bx: no block outside
+   a picture's rectangle is read.  Formats, tensors, scale and bias as for hapgpu_k_block_decode_planes, the layout rules
+   at the rectangle's size.  The same table, profile class and return codes. */
+int hapgpu_k_block_decode_planes_region(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, int with_alpha,
+                                        unsigned width, unsigned height, unsigned hap_texture_format,
+                                        const uint32_t *origins, unsigned origin, unsigned region_width,
+                                        unsigned region_height, unsigned scale_log2, unsigned channels,
+                                        unsigned element_kind, size_t plane_bytes, size_t row_bytes, const float *scale,
+                                        const float *bias);
 /* planar tensors -> blocks of `hap_texture_format`, without an RGBA8 picture in between (bc_encode_planes.hip): the way
    back of hapgpu_k_block_decode_planes.  Tensors (the first column of the table) of `channels` (3 or 4: R, G, B[, A])
    planes plane_bytes apart, rows row_bytes apart, elements of element_kind (0 half, 1 bfloat16, 2 float: e = 2, 2, 4
@@ -426,6 +442,10 @@ int hapgpu_k_decode_plan(hapgpu_rt *rt, HapGpuDecodeJob *jobs, unsigned job_coun
    scanned; in front of hapgpu_k_guess_group_tables, no table is made for a blanked piece). */
 int hapgpu_k_skip_units(hapgpu_rt *rt, HapGpuDecodeUnit *units, unsigned unit_count, const HapGpuDecodeJob *jobs,
                         const uint32_t *job_block_bytes, const HapGpuRegion *region, int count);
+/* ... with a rectangle per job: job_regions[unit.job] (device, next to job_block_bytes) in place of the one `region`.  A
+   job that skips nothing carries a rectangle that needs everything -- the whole of its texture --, or a block size of 0. */
+int hapgpu_k_skip_units_per_job(hapgpu_rt *rt, HapGpuDecodeUnit *units, unsigned unit_count, const HapGpuDecodeJob *jobs,
+                                const uint32_t *job_block_bytes, const HapGpuRegion *job_regions, int count);
 /* decoded bytes of the units hapgpu_k_skip_units blanked since the runtime was made (waits for the stream) */
 unsigned long long hapgpu_rt_skipped_bytes(hapgpu_rt *rt);
 /* splits whole-stream units that consist of independent 64 KiB blocks (what libsnappy writes) into BLOCK units,

@@ -329,9 +329,11 @@ __device__ __forceinline__ unsigned scan_unit_mode(unsigned kind, uint64_t reser
 // wavefront.  Of a scanned stream's two sets of BLOCK units (64 KiB and 8 KiB) the one the decoder runs is counted
 // (scan_stream_mode; this kernel runs in front of the decoder, where no 8 KiB unit has failed yet); both are blanked: the
 // other set is what a stream falls back to, and it needs the same bytes.
+// The rectangle is the unit's job's, job_regions[u.job] (HapGpuDecodeFramesPlanesRegion: a rectangle per frame), or, where
+// that array is null, `one` for every job.
 __global__ __launch_bounds__(256) void skip_units_kernel(HapGpuDecodeUnit *units, unsigned unit_count, const HapGpuDecodeJob *jobs,
-                                                         const uint32_t *job_block_bytes, HapGpuRegion g,
-                                                         unsigned long long *skipped)
+                                                         const uint32_t *job_block_bytes, const HapGpuRegion *job_regions,
+                                                         HapGpuRegion one, unsigned long long *skipped)
 {
     const unsigned i = blockIdx.x * 256u + threadIdx.x;
     unsigned long long bytes = 0;
@@ -339,6 +341,7 @@ __global__ __launch_bounds__(256) void skip_units_kernel(HapGpuDecodeUnit *units
         const HapGpuDecodeUnit u = units[i];
         if (u.kind != HAPGPU_UNIT_SKIP && u.dst_len != 0u) {
             const unsigned block_bytes = job_block_bytes[u.job];
+            const HapGpuRegion g = job_regions ? job_regions[u.job] : one;
             if (hap_region_valid(g.width, block_bytes, g.x, g.y, g.w, g.h) &&
                 !hap_region_needs_bytes(g.width, block_bytes, g.x, g.y, g.w, g.h, u.dst - jobs[u.job].dst, u.dst_len)) {
                 bool runs = true;
@@ -2363,7 +2366,21 @@ extern "C" int hapgpu_k_skip_units(hapgpu_rt *rt, HapGpuDecodeUnit *units, unsig
     if (unit_count == 0 || !region)
         return 0;
     hipLaunchKernelGGL(skip_units_kernel, dim3((unit_count + 255u) / 256u), dim3(256), 0, hapgpu_rt_stream(rt), units, unit_count,
-                       jobs, job_block_bytes, *region, count ? hapgpu_rt_skipped_counter(rt) : nullptr);
+                       jobs, job_block_bytes, (const HapGpuRegion *)nullptr, *region, count ? hapgpu_rt_skipped_counter(rt) : nullptr);
+    return hipGetLastError() == hipSuccess ? 0 : 4;
+}
+
+// hapgpu_abi.h: ... with the rectangle of every unit's job
+extern "C" int hapgpu_k_skip_units_per_job(hapgpu_rt *rt, HapGpuDecodeUnit *units, unsigned unit_count,
+                                           const HapGpuDecodeJob *jobs, const uint32_t *job_block_bytes,
+                                           const HapGpuRegion *job_regions, int count)
+{
+    scoped_timing st(rt, 4);
+    if (unit_count == 0 || !job_regions)
+        return 0;
+    hipLaunchKernelGGL(skip_units_kernel, dim3((unit_count + 255u) / 256u), dim3(256), 0, hapgpu_rt_stream(rt), units, unit_count,
+                       jobs, job_block_bytes, job_regions, HapGpuRegion{0u, 0u, 0u, 0u, 0u},
+                       count ? hapgpu_rt_skipped_counter(rt) : nullptr);
     return hipGetLastError() == hipSuccess ? 0 : 4;
 }
 

@@ -245,8 +245,9 @@ enum HapGpuPlaneElement { HapGpuPlaneElement_F16 = 0, HapGpuPlaneElement_BF16 = 
  * slice of a larger tensor, with longer rows and planes, qualifies).  Only the elements are written, nothing between
  * rows or planes.  Bad_Arguments, and nothing written, for anything else: a NULL, host or misaligned tensor, channels
  * other than 3 or 4, an element or scaleLog2 outside the above, a NULL scale or bias.
- * Out of scope: RGBA_BPTC_UNORM (BC7), the BC6H formats and a lone A_RGTC1 as sources (Bad_Arguments), rectangles and host
- * tensors.  The way back, from a planar float tensor to a texture, is HapGpuCompressPlanes. */
+ * Out of scope: RGBA_BPTC_UNORM (BC7), the BC6H formats and a lone A_RGTC1 as sources (Bad_Arguments), and host tensors;
+ * rectangles: HapGpuDecompressPlanesRegion.  The way back, from a planar float tensor to a texture, is
+ * HapGpuCompressPlanes. */
 unsigned int HapGpuDecompressPlanes(HapGpuContext *context,
                                     const void *texture, unsigned long textureBytes, unsigned int textureFormat,
                                     const void *alphaTexture, unsigned long alphaTextureBytes,
@@ -305,6 +306,33 @@ unsigned int HapGpuDecompressRGBARegion(HapGpuContext *context,
                                         unsigned int regionX, unsigned int regionY,
                                         unsigned int regionWidth, unsigned int regionHeight,
                                         void *rgba, unsigned long rowBytes);
+
+/* The same texture -> the planar float tensor of one block-aligned rectangle of it, in DEVICE memory: HapGpuDecompressPlanes
+ * and HapGpuDecompressRGBARegion joined, the single-texture form of HapGpuDecodeFramesPlanesRegion.
+ * The definition, and the only one.  With s = scaleLog2, the tensor is `channels` planes of (regionWidth >> s) x
+ * (regionHeight >> s) elements, and it equals, bit for bit, rows [regionY >> s, (regionY + regionHeight) >> s) and columns
+ * [regionX >> s, (regionX + regionWidth) >> s) of every plane of the tensor HapGpuDecompressPlanes writes for the same
+ * texture, alpha plane, scaleLog2, channels, element, scale and bias.  A box mean never spans two blocks, so a block-aligned
+ * rectangle is enough at every scale.  The two roundings -- one binary32 multiply by scale[c], then one binary32 add of
+ * bias[c], not fused --, the conversion to the element (subnormal halves kept) and the handling of alpha (with channels 3
+ * it is not written and the alpha plane not read) are HapGpuDecompressPlanes'.  Only the rectangle's blocks are read.
+ * Geometry: width and height are the TEXTURE's; regionX, regionY, regionWidth and regionHeight are multiples of 4, the last
+ * two non-zero, regionX + regionWidth <= width and regionY + regionHeight <= height.  Tensor: HapGpuDecompressPlanes' rules
+ * at the rectangle's size -- device memory only; with n = 4 >> scaleLog2 and e the element's size the address, rowBytes
+ * and planeBytes are multiples of n * e, rowBytes at least (regionWidth >> s) * e and planeBytes at least
+ * rowBytes * ((regionHeight >> s) - 1) + (regionWidth >> s) * e; a slice of a larger tensor qualifies; nothing is written
+ * between rows or planes.  Bad_Arguments, and nothing written, for anything else.
+ * Out of scope: RGBA_BPTC_UNORM (BC7), the BC6H formats and a lone A_RGTC1 as sources (Bad_Arguments), host tensors, and
+ * rectangles off the block grid. */
+unsigned int HapGpuDecompressPlanesRegion(HapGpuContext *context,
+                                          const void *texture, unsigned long textureBytes, unsigned int textureFormat,
+                                          const void *alphaTexture, unsigned long alphaTextureBytes,
+                                          unsigned int width, unsigned int height,
+                                          unsigned int regionX, unsigned int regionY,
+                                          unsigned int regionWidth, unsigned int regionHeight,
+                                          unsigned int scaleLog2, unsigned int channels, unsigned int element,
+                                          void *planes, unsigned long planeBytes, unsigned long rowBytes,
+                                          const float *scale, const float *bias);
 
 /* BC6H texture (Hap HDR) -> RGBA16F: four IEEE half bit patterns per texel, 8 bytes, rows rowBytes apart.
  * textureFormat: RGB_BPTC_UNSIGNED_FLOAT or RGB_BPTC_SIGNED_FLOAT (anything else is Bad_Arguments).  RGB is
@@ -565,7 +593,8 @@ unsigned int HapGpuDecodeFramesRGBA(HapGpuContext *context, unsigned int frameCo
  * lies wholly inside skipped pieces is not seen (as HapDecode does not see a chunk its callback never runs); damage in
  * the container, the tables or a decoded piece gets the full call's code.  A frame of another format or geometry is
  * Bad_Arguments alone, its picture untouched.  Out of scope: RGBA16F and A8 pictures, a rectangle together with
- * scaleLog2, ...OnDevices / ...Sequence forms, rectangles off the block grid. */
+ * scaleLog2, ...OnDevices / ...Sequence forms, rectangles off the block grid.  (Planar float tensors of a rectangle, at
+ * any of the three sizes and with a rectangle per frame: HapGpuDecodeFramesPlanesRegion.) */
 unsigned int HapGpuDecodeFramesRGBARegion(HapGpuContext *context, unsigned int frameCount,
                                           const void *const *inputBuffers,
                                           const unsigned long *inputBuffersBytes,
@@ -591,7 +620,7 @@ unsigned int HapGpuRegionNeedsBytes(unsigned int width, unsigned int blockBytes,
 /* Decoded bytes of all the pieces the region calls of this context left undecoded, summed over the context's life.
  * A frame counts once: one that is decoded a second time without its fragment table keeps the first pass's figure,
  * though the second pass skips whole chunks only.  Never more, per call, than the textures' bytes minus the bytes of
- * the rectangle's blocks.  Waits for the stream: for tests and tools, like HapGpuResolvedBlockCount. */
+ * the rectangle's blocks (HapGpuDecodeFramesPlanesRegion: of the rectangles' blocks, frame by frame).  Waits for the stream: for tests and tools, like HapGpuResolvedBlockCount. */
 unsigned long HapGpuSkippedTextureBytes(HapGpuContext *context);
 
 /* Frames in, half- (scaleLog2 1) or quarter-size (scaleLog2 2) pixels out: HapGpuDecodeFramesRGBA with the pictures of
@@ -633,8 +662,8 @@ unsigned int HapGpuDecodeFramesRGBAScaled(HapGpuContext *context, unsigned int f
  * that breaks the alignment rule or is too short.  A context between HapGpuEncodeFramesRGBABegin and
  * HapGpuEncodeFramesFinish: Internal_Error.
  * Out of scope: Hap R (BC7), Hap HDR (BC6H) and Hap Alpha-Only (a lone A_RGTC1) frames -- Bad_Arguments alone, with or
- * without HAPGPU_DECODE_BPTC_PICTURES --, rectangles, host tensors, ...OnDevices and ...Sequence forms of this call.
- * The way back, from planar float tensors to frames, is HapGpuEncodeFramesPlanes. */
+ * without HAPGPU_DECODE_BPTC_PICTURES --, host tensors, ...OnDevices and ...Sequence forms of this call; rectangles:
+ * HapGpuDecodeFramesPlanesRegion.  The way back, from planar float tensors to frames, is HapGpuEncodeFramesPlanes. */
 unsigned int HapGpuDecodeFramesPlanes(HapGpuContext *context, unsigned int frameCount,
                                       const void *const *inputBuffers,
                                       const unsigned long *inputBuffersBytes,
@@ -646,6 +675,53 @@ unsigned int HapGpuDecodeFramesPlanes(HapGpuContext *context, unsigned int frame
                                       const float *scale, const float *bias,
                                       unsigned int *results,
                                       unsigned int flags);
+
+/* Frames in, normalised planar float tensors of a crop per frame out: HapGpuDecodeFramesPlanes and
+ * HapGpuDecodeFramesRGBARegion joined, for an input pipeline that wants a (random, tracked, tiled) crop of every frame,
+ * often at half or quarter size.  Frame f's rectangle is regionWidth x regionHeight texels at (regionXs[f], regionYs[f])
+ * of the FRAMES' width x height; regionXs and regionYs have frameCount entries each; the size is shared.
+ * The definition, and the only one.  With s = scaleLog2, planeFrames[f] is frame f's tensor in DEVICE memory: `channels`
+ * planes of (regionWidth >> s) x (regionHeight >> s) elements, planeBytes and rowBytes shared by all frames.  It equals, bit
+ * for bit, rows [regionYs[f] >> s, (regionYs[f] + regionHeight) >> s) and columns [regionXs[f] >> s,
+ * (regionXs[f] + regionWidth) >> s) of every plane of the tensor HapGpuDecodeFramesPlanes writes for that frame with the
+ * same textureCount, scaleLog2, channels, element, scale, bias and flags.  A box mean never spans two blocks, so a
+ * block-aligned rectangle is enough at every scale.  The two roundings -- one binary32 multiply by scale[c], then one
+ * binary32 add of bias[c], not fused --, the conversion to the element and the handling of alpha are that call's.
+ * The block decoder reads every frame's own rectangle's blocks only, and the second stage leaves undecoded, frame by
+ * frame, every independently decodable piece that holds no byte of them, as HapGpuDecodeFramesRGBARegion does for its one
+ * rectangle (HapGpuRegionNeedsBytes; counted by HapGpuSkippedTextureBytes); a rectangle that is the whole frame skips
+ * nothing.
+ * Geometry (HapGpuDecodeFramesRGBARegion's rules): regionXs[f], regionYs[f], regionWidth and regionHeight are multiples
+ * of 4, regionWidth and regionHeight non-zero, regionXs[f] + regionWidth <= width and regionYs[f] + regionHeight <= height.
+ * Tensors (HapGpuDecodeFramesPlanes' rules at the rectangle's size): device memory only; with n = 4 >> scaleLog2 and e the
+ * element's size the addresses, rowBytes and planeBytes are multiples of n * e, rowBytes at least (regionWidth >> s) * e
+ * and planeBytes at least rowBytes * ((regionHeight >> s) - 1) + (regionWidth >> s) * e; a slice of a larger tensor
+ * qualifies; nothing is written between rows or planes.
+ * Bad_Arguments for the whole call -- every results[f] set, nothing written -- for what HapGpuDecodeFramesPlanes refuses, a
+ * NULL regionXs or regionYs, a regionWidth or regionHeight that is zero, off the grid or larger than the frame.  A frame
+ * whose own origin puts the rectangle off the grid or past an edge is Bad_Arguments alone: its tensor is untouched,
+ * nothing of it is handed to the second stage or the block decoder, and the other frames are decoded.  So is a frame of
+ * another format or geometry, or one whose tensor is NULL, in host memory or misaligned.  A broken frame gets the full
+ * call's code; damage wholly inside skipped pieces is not seen, as in HapGpuDecodeFramesRGBARegion.  A context between
+ * HapGpuEncodeFramesRGBABegin and HapGpuEncodeFramesFinish: Internal_Error.  Sources, textureCount, flags, mixed batches
+ * (one block-decode launch per texture format present) and slicing are HapGpuDecodeFramesPlanes': Hap, Hap Alpha, Hap Q,
+ * Hap Q Alpha.
+ * Out of scope: Hap R (BC7), Hap HDR (BC6H) and Hap Alpha-Only (a lone A_RGTC1) frames as sources, host tensors,
+ * rectangles off the block grid, rectangles of different sizes in one call, ...OnDevices and ...Sequence forms of this
+ * call, and an RGBA8 "rectangle together with scaleLog2" call. */
+unsigned int HapGpuDecodeFramesPlanesRegion(HapGpuContext *context, unsigned int frameCount,
+                                            const void *const *inputBuffers,
+                                            const unsigned long *inputBuffersBytes,
+                                            unsigned int textureCount,
+                                            void *const *planeFrames,
+                                            unsigned int width, unsigned int height,
+                                            const unsigned int *regionXs, const unsigned int *regionYs,
+                                            unsigned int regionWidth, unsigned int regionHeight,
+                                            unsigned int scaleLog2, unsigned int channels, unsigned int element,
+                                            unsigned long planeBytes, unsigned long rowBytes,
+                                            const float *scale, const float *bias,
+                                            unsigned int *results,
+                                            unsigned int flags);
 
 /* Planar float tensors in, frames out -- the way back of HapGpuDecodeFramesPlanes: HapGpuEncodeFramesRGBA with the tensors of
  * HapGpuCompressPlanes in place of pictures.  planeFrames[f] is frame f's tensor in DEVICE memory, `channels` planes of
