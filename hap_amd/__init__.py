@@ -14,8 +14,17 @@ _API_NAMES = (
     "HapGetFrameTextureFormat", "HapMaxEncodedLength", "Context", "ENCODE_FRAGMENT_INDEX", "ENCODE_COARSE_MATCHES", "ENCODE_SMALLER_FILES",
     "DECODE_IGNORE_FRAGMENT_INDEX", "DECODE_IGNORE_HALF_TILES", "DECODE_NO_BLOCK_SCAN", "KERNEL_CLASSES", "HapGpuGetFrameTextureChunkLayout", "HapGpuJoinChunkGroups", "SequenceWriter", "SequenceReader", "BufferList",
     "encode_frames_rgba_on_devices", "decode_frames_on_devices", "ENCODE_FINE_CHUNKS", "fine_chunk_count", "DECODE_NO_FIELD_GUESS", "DECODE_GUESS_FIELDS",
-    "DECODE_BPTC_PICTURES", "ENCODE_BPTC_BLOCKS", "region_needs_bytes",
+    "DECODE_BPTC_PICTURES", "ENCODE_BPTC_BLOCKS", "region_needs_bytes", "PictureError",
 )
+
+
+def psnr(sse, texels, peak=255.0):
+    """Peak signal-to-noise ratio in dB of `texels` samples whose squared errors add up to `sse` (Context.measure_frames'
+    sums; several channels together: add their sse, multiply texels): 10 * log10(peak^2 * texels / sse), inf for sse 0."""
+    import math
+    if sse == 0:
+        return math.inf
+    return 10.0 * math.log10(float(peak) * float(peak) * float(texels) / float(sse))
 
 
 def __getattr__(name):

@@ -13,6 +13,11 @@ WORK_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint)
 CALLBACK = C.CFUNCTYPE(None, WORK_FN, C.c_void_p, C.c_uint, C.c_void_p)
 
 
+class HapGpuPictureError(C.Structure):
+    """include/hap_gpu.h's HapGpuPictureError: per channel R, G, B, A the exact sums of (d - p)^2 and |d - p|"""
+    _fields_ = [("sse", C.c_ulonglong * 4), ("sad", C.c_ulonglong * 4), ("texels", C.c_ulonglong)]
+
+
 def _load():
     # PyTorch wheels bundle their own libamdhip64/libhsa-runtime64 (same SONAMEs as /opt/rocm's).
     # Two HIP runtimes in one process fight over the device, so when torch is installed let it
@@ -86,6 +91,8 @@ def _load():
         "HapGpuDecodeFramesRGBARegion": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, u, u, u, ul, P(u), u]),
         "HapGpuDecodeFramesPlanesRegion": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, P(u), P(u), u, u, u, u, u, ul, ul,
                                                P(C.c_float), P(C.c_float), P(u), u]),
+        "HapGpuMeasureTexture": (u, [vp, vp, ul, u, vp, ul, u, u, vp, ul, P(HapGpuPictureError)]),
+        "HapGpuMeasureFrames": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, ul, P(HapGpuPictureError), P(u), u]),
         "HapGpuTranscodeTexture": (u, [vp, vp, ul, u, vp, ul, u, u, u, u, P(u), P(vp), P(ul), P(ul)]),
         "HapGpuTranscodeFrames": (u, [vp, u, P(vp), P(ul), u, u, u, u, u, P(u), P(u), P(u), P(vp), P(ul), P(ul), P(u), u, u]),
         "HapGpuDecodeFramesRGBAHalf": (u, [vp, u, P(vp), P(ul), P(vp), u, u, ul, P(u), u]),

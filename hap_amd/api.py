@@ -6,7 +6,7 @@ Buffers may be bytes / bytearray / numpy arrays (host) or objects exposing
 import ctypes as C
 import os
 
-from ._lib import CALLBACK, WORK_FN, lib
+from ._lib import CALLBACK, WORK_FN, HapGpuPictureError, lib
 
 
 class HapTextureFormat:
@@ -92,6 +92,38 @@ def _plane_constants(scale, bias, channels, default_scale=1.0 / 255.0):
         raise ValueError("scale and bias: one value per channel")
     return ((C.c_float * channels)(*[float(np.float32(v)) for v in scale]),
             (C.c_float * channels)(*[float(np.float32(v)) for v in bias]))
+
+
+class PictureError:
+    """A HapGpuPictureError: sse and sad per channel (R, G, B, A) as tuples of ints, and texels (0: not measured)"""
+    __slots__ = ("sse", "sad", "texels")
+
+    def __init__(self, sse=(0, 0, 0, 0), sad=(0, 0, 0, 0), texels=0):
+        self.sse, self.sad, self.texels = tuple(int(v) for v in sse), tuple(int(v) for v in sad), int(texels)
+
+    def __eq__(self, other):
+        return isinstance(other, PictureError) and (self.sse, self.sad, self.texels) == (other.sse, other.sad, other.texels)
+
+    def __repr__(self):
+        return "PictureError(sse=%r, sad=%r, texels=%r)" % (self.sse, self.sad, self.texels)
+
+    def psnr(self, channels=(0, 1, 2), peak=255.0):
+        """PSNR in dB over `channels` together (hap_amd.psnr)"""
+        from . import psnr
+        return psnr(sum(self.sse[c] for c in channels), self.texels * len(channels), peak)
+
+
+def _picture_error(raw):
+    return PictureError(raw.sse, raw.sad, raw.texels)
+
+
+def _picture_address(picture, keep):
+    """the address of a reference picture: a tensor or another buffer (kept alive in `keep`), an integer address, or None"""
+    if picture is None or isinstance(picture, int):
+        return picture
+    address, _n, alive = _addr_len(picture)
+    keep.append(alive)
+    return address
 
 
 def _addr_len(buf):
@@ -410,6 +442,19 @@ class Context:
         if own:
             return r, (C.string_at(oa, row_bytes * height) if r == 0 else None)
         return r, None
+
+    def measure_texture(self, texture, texture_format, width, height, picture, alpha=None, row_bytes=None):
+        """Texture (+ optional RGTC1 alpha plane) against `picture`, an RGBA8 picture in device memory (a tensor or an
+        address): per channel the exact sums of (d - p)^2 and |d - p|, d being decompress_rgba's byte
+        (HapGpuMeasureTexture).  Returns (result, PictureError | None)."""
+        ta, tn, _k = _addr_len(texture)
+        aa, an, _k2 = _addr_len(alpha) if alpha is not None else (None, 0, None)
+        keep = []
+        raw = HapGpuPictureError()
+        r = lib.HapGpuMeasureTexture(self.handle, ta, tn, texture_format, aa, an, width, height,
+                                     _picture_address(picture, keep), width * 4 if row_bytes is None else row_bytes,
+                                     C.byref(raw))
+        return r, (_picture_error(raw) if r == 0 else None)
 
     def decompress_rgba_scaled(self, texture, texture_format, width, height, scale_log2, rgba=None, alpha=None,
                                row_bytes=None):
@@ -745,6 +790,24 @@ class Context:
         r = lib.HapGpuDecodeFramesRGBA(self.handle, nf, ptrs, lens, texture_count, optrs, width, height,
                                        row_bytes or width * 4, results, flags)
         return r, list(results)
+
+    def measure_frames(self, frames, frame_bytes, texture_count, pictures, width, height, row_bytes=None, flags=0):
+        """Frames against their RGBA8 reference pictures in device memory (tensors or addresses; None: no picture for that
+        frame) in one call, without decoded pictures: per frame and channel the exact sums of (d - p)^2 and |d - p|, d
+        being decode_frames_rgba's byte (HapGpuMeasureFrames).  Returns (result, results[], errors[]): PictureError
+        objects, all zero for a frame that failed."""
+        nf = len(frames)
+        if len(pictures) != nf:
+            raise ValueError("one picture per frame")
+        ptrs, infos = self._ptr_array(frames)
+        lens = (C.c_ulong * nf)(*[fb if fb is not None else infos[i][1] for i, fb in enumerate(frame_bytes)])
+        keep = []
+        pptrs = (C.c_void_p * nf)(*[_picture_address(p, keep) for p in pictures])
+        results = (C.c_uint * nf)()
+        raw = (HapGpuPictureError * nf)()
+        r = lib.HapGpuMeasureFrames(self.handle, nf, ptrs, lens, texture_count, pptrs, width, height,
+                                    width * 4 if row_bytes is None else row_bytes, raw, results, flags)
+        return r, list(results), [_picture_error(e) for e in raw]
 
     def decode_frames_rgba_scaled(self, frames, frame_bytes, texture_count, rgba_frames, width, height, scale_log2,
                                   row_bytes=None, flags=0):

@@ -536,6 +536,22 @@ unsigned int HapGpuDecompressRGBA(HapGpuContext *context, const void *texture, u
     return r;
 }
 
+/* one texture against its reference picture in device memory: the sums of the decoder's errors, no picture written */
+unsigned int HapGpuMeasureTexture(HapGpuContext *context, const void *texture, unsigned long textureBytes,
+                                  unsigned int textureFormat, const void *alphaTexture, unsigned long alphaTextureBytes,
+                                  unsigned int width, unsigned int height, const void *rgba, unsigned long rowBytes,
+                                  HapGpuPictureError *error)
+{
+    unsigned r;
+    if (!context || !error)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_measure_texture(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width, height,
+                             rgba, rowBytes, error);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
 /* HapGpuDecompressRGBA of a block-aligned rectangle of the texture */
 unsigned int HapGpuDecompressRGBARegion(HapGpuContext *context, const void *texture, unsigned long textureBytes,
                                         unsigned int textureFormat, const void *alphaTexture,
@@ -1079,6 +1095,28 @@ unsigned int HapGpuDecodeFramesRGBA(HapGpuContext *context, unsigned int frameCo
     hapgpu_rt_lock(context->rt);
     r = hapb_decode_rgba(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, rgbaFrames, width, height,
                          0u, rowBytes, results, flags);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+/* frames against their reference pictures in device memory; a NULL errors refuses the whole call like a NULL results */
+unsigned int HapGpuMeasureFrames(HapGpuContext *context, unsigned int frameCount, const void *const *inputBuffers,
+                                 const unsigned long *inputBuffersBytes, unsigned int textureCount,
+                                 const void *const *rgbaFrames, unsigned int width, unsigned int height,
+                                 unsigned long rowBytes, HapGpuPictureError *errors, unsigned int *results,
+                                 unsigned int flags)
+{
+    unsigned r, f;
+    if (!context)
+        return HapResult_Bad_Arguments;
+    if (!errors) {
+        for (f = 0; results && f < frameCount; f++)
+            results[f] = HapResult_Bad_Arguments;
+        return HapResult_Bad_Arguments;
+    }
+    hapgpu_rt_lock(context->rt);
+    r = hapb_measure_frames(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, rgbaFrames, width, height,
+                            rowBytes, errors, results, flags);
     hapgpu_rt_unlock(context->rt);
     return r;
 }

@@ -30,6 +30,7 @@ enum {
 #define D_GUESS D_FRAGSIZES  /* ... and the group tables the decoder makes for fragments that came without */
 #define D_TRANSCODED D_RGBA_STAGE /* ... and the textures a transcode call makes, where the calls with pictures stage those: it
                                      has none, and D_BC_TEX holds its source textures until its encode half is done */
+#define D_MEASURE D_RGBA_STAGE    /* ... and the totals and partial sums of a measuring call: its pictures are never staged */
 #define P_SCAN P_FRAMES
 enum { P_FRAMES = 0, P_JOBS, P_CHUNKS, P_PREFIX, P_PTRS, P_BC_PTRS, P_PREFIX2 };   /* (8, 9: hap_sequence.c) */
 
@@ -848,6 +849,10 @@ typedef struct picture_road {
     const unsigned *region_xs, *region_ys;  /* NULL: region->x, region->y for every frame; else (planes only, frames only)
                                    frame f's rectangle begins at (region_xs[f], region_ys[f]), f counted from the call's
                                    first frame, and region->x, region->y are 0 */
+    HapGpuPictureError *measure; /* NULL: the pictures are written; else (RGBA8, scale_log2 0, no region, no planes) they
+                                   are reference pictures in device memory and are READ: the launch is
+                                   hapgpu_k_block_measure, and measure[f] gets the sums of frame f against its picture,
+                                   f counted from the call's first frame */
 } picture_road;
 
 /* RGBA8 pictures (BC7 last: frames of it only with HAPGPU_DECODE_BPTC_PICTURES), RGBA16F ones and A8 ones */
@@ -870,6 +875,34 @@ static picture_road road_of(unsigned picture_kind, unsigned flags, unsigned scal
 static picture_road planes_road_of(unsigned scale_log2, const HapbPlanes *planes)
 {
     return (picture_road){3u, k_rgba_kinds, 0x7u, HAPGPU_PICTURE_RGBA8, scale_log2, NULL, planes, NULL, NULL};
+}
+
+/* ... and to nothing: the RGBA8 road's DXT formats (never BC7) against reference pictures, the sums to `errors` */
+static picture_road measure_road_of(HapGpuPictureError *errors)
+{
+    return (picture_road){3u, k_rgba_kinds, 0x7u, HAPGPU_PICTURE_RGBA8, 0u, NULL, NULL, NULL, NULL, errors};
+}
+
+/* a measuring road's device scratch for `pictures` pictures: [pictures][8] 64-bit totals, then the workgroups' partials */
+static unsigned long long *measure_scratch(hapgpu_rt *rt, unsigned pictures, unsigned width, unsigned height,
+                                           uint32_t **partials)
+{
+    const size_t totals_bytes = align_up(sizeof(unsigned long long) * 8u * pictures, 256);
+    uint8_t *s = (uint8_t *)hapgpu_rt_device_scratch(rt, D_MEASURE, totals_bytes +
+                                                     hapgpu_block_measure_partial_bytes(width, height) * pictures);
+    *partials = s ? (uint32_t *)(s + totals_bytes) : NULL;
+    return (unsigned long long *)s;
+}
+
+/* a picture's eight totals (sse R, G, B, A, then sad) as the caller's struct */
+static void measure_result(HapGpuPictureError *error, const unsigned long long *totals, unsigned width, unsigned height)
+{
+    unsigned c;
+    for (c = 0; c < 4u; c++) {
+        error->sse[c] = totals[c];
+        error->sad[c] = totals[4u + c];
+    }
+    error->texels = (unsigned long long)width * height;
 }
 
 /* ... of a rectangle of every texture: region's for all (xs and ys NULL), or region's size at an origin per frame */
@@ -935,11 +968,14 @@ static uint32_t region_first_block(unsigned width, unsigned x, unsigned y)
 
 /* the block-decode launch of a road: pictures of the frames' size, scaled ones, a rectangle's, or planar tensors (the
    alpha plane is read only where a fourth plane is written).  origins: a planar road with a rectangle per frame -- the
-   device array of the pictures' first blocks */
+   device array of the pictures' first blocks; partials, totals: a measuring road's scratch (measure_scratch) */
 static int launch_block_decode(hapgpu_rt *rt, const picture_road *road, const HapGpuPictureTable *t, unsigned pictures,
                                int with_alpha, unsigned width, unsigned height, unsigned format, size_t row_bytes, int wide,
-                               const uint32_t *origins)
+                               const uint32_t *origins, uint32_t *partials, unsigned long long *totals)
 {
+    /* (a measuring road: the block kernel with the pictures as its third column, read, and the reduction behind it) */
+    if (road->measure)
+        return hapgpu_k_block_measure(rt, t, pictures, with_alpha, width, height, format, row_bytes, partials, totals);
     if (road->planes && road->region)
         return hapgpu_k_block_decode_planes_region(rt, t, pictures, with_alpha && road->planes->channels == 4u, width, height,
                                                    format, origins,
@@ -976,6 +1012,8 @@ static unsigned decompress_picture(HapGpuContext *ctx, const void *texture, unsi
     size_t need, alpha_need, picture_bytes;
     const void *src = texture, *asrc = alpha;
     void *dst = picture;
+    uint32_t *partials = NULL;
+    unsigned long long *totals = NULL, *htotals = NULL;
     unsigned k;
     int rc;
     if (context_busy(ctx, NULL, 0))
@@ -986,7 +1024,9 @@ static unsigned decompress_picture(HapGpuContext *ctx, const void *texture, unsi
         (road.region && (road.region->width != width || !hapb_region_fits(road.region, height))) ||
         k == road.kind_count || (alpha && !(road.paired_kinds >> k & 1u)) ||
         /* (tensors live in device memory: no host staging road) */
-        (road.planes && (!planes_fit(&road, pixel_row, picture_height, row_bytes) || !is_dev(ctx, picture))))
+        (road.planes && (!planes_fit(&road, pixel_row, picture_height, row_bytes) || !is_dev(ctx, picture))) ||
+        /* (and so do reference pictures) */
+        (road.measure && !is_dev(ctx, picture)))
         return HapResult_Bad_Arguments;
     need = (size_t)(width / 4u) * (height / 4u) * block;
     alpha_need = (size_t)(width / 4u) * (height / 4u) * 8u;
@@ -1025,12 +1065,25 @@ static unsigned decompress_picture(HapGpuContext *ctx, const void *texture, unsi
     t.one[0] = (uint64_t)(uintptr_t)src;
     t.one[1] = (uint64_t)(uintptr_t)asrc;
     t.one[2] = (uint64_t)(uintptr_t)dst;
+    if (road.measure) {
+        /* (after the textures' scratch: growing an arena waits for the stream, not for copies yet to be issued) */
+        totals = measure_scratch(rt, 1u, width, height, &partials);
+        htotals = (unsigned long long *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, sizeof(*htotals) * 8u);
+        if (!totals || !htotals)
+            return HapResult_Internal_Error;
+    }
     rc = launch_block_decode(rt, &road, &t, 1u, alpha != NULL, width, height, format, row_bytes,
-                             (((uintptr_t)dst | row_bytes) & 15u) == 0 && !ctx->no_wide_planes, NULL);
+                             (((uintptr_t)dst | row_bytes) & 15u) == 0 && !ctx->no_wide_planes, NULL, partials, totals);
     if (rc == 1)
         return HapResult_Bad_Arguments;
     if (rc)
         return HapResult_Internal_Error;
+    if (road.measure) {
+        if (hapgpu_rt_d2h(rt, htotals, totals, sizeof(*htotals) * 8u) || hapgpu_rt_sync(rt))
+            return HapResult_Internal_Error;
+        measure_result(road.measure, htotals, width, height);
+        return HapResult_No_Error;
+    }
     /* (row by row when the client's rows are longer than the picture's: what lies between them is not ours) */
     if (dst != picture && (row_bytes == pixel_row ? hapgpu_rt_d2h(rt, picture, dst, picture_bytes)
                                                   : hapgpu_rt_d2h_rows(rt, picture, row_bytes, dst, row_bytes, pixel_row,
@@ -1058,6 +1111,16 @@ unsigned hapb_decompress_planes(HapGpuContext *ctx, const void *texture, unsigne
     const picture_road road = planes_road_of(scale_log2, planes);
     return decompress_picture(ctx, texture, texture_bytes, format, alpha, alpha_bytes, width, height, tensor, row_bytes,
                               &road);
+}
+
+/* one texture (+ RGTC1 alpha plane) against its RGBA8 reference picture in device memory */
+unsigned hapb_measure_texture(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
+                              const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
+                              const void *rgba, unsigned long row_bytes, HapGpuPictureError *error)
+{
+    const picture_road road = measure_road_of(error);
+    return decompress_picture(ctx, texture, texture_bytes, format, alpha, alpha_bytes, width, height, (void *)(uintptr_t)rgba,
+                              row_bytes, &road);
 }
 
 unsigned hapb_decompress_planes_region(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
@@ -2227,6 +2290,9 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
             results[f] = HapResult_Bad_Arguments;
         return HapResult_Bad_Arguments;
     }
+    /* (a measuring road: a frame that is not measured has an all-zero struct) */
+    if (road->measure)
+        memset(road->measure, 0, sizeof(*road->measure) * frame_count);
     blocks = (size_t)(width / 4u) * (height / 4u);
     alpha_off = align_up(blocks * 16u, 256);
     per_frame = alpha_off + (texture_count == 2 ? align_up(blocks * 8u, 256) : 0u);
@@ -2258,6 +2324,7 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
         const unsigned n = (unsigned)(frame_count - done < slice ? frame_count - done : slice);
         uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, per_frame * n);
         uint8_t *stage = NULL;
+        const unsigned long long *htotals_of_slice = NULL;
         unsigned t;
         int rc = 0, any_skip = 0;
         if (!textures) {
@@ -2307,15 +2374,20 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
             /* one block-decode launch per texture format present in the slice: [textures][alpha planes][pictures] in a
                small device table, pictures of other formats (or that failed) with a texture address of 0 */
             /* ... and behind the table, in the same copy, a rectangle per frame's first texture block of every picture */
+            /* ... and, in the pinned copy alone, a measuring road's totals of every picture on their way back */
             const size_t ptr_words = (size_t)3u * PICTURE_KINDS_MAX * n;
             const size_t tab_bytes = sizeof(uint64_t) * ptr_words + (per_frame_regions ? sizeof(uint32_t) * n : 0u);
-            uint64_t *htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, tab_bytes);
+            const size_t totals_bytes = road->measure ? sizeof(unsigned long long) * 8u * n : 0u;
+            uint64_t *htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, align_up(tab_bytes, 8) + totals_bytes);
             uint64_t *dtab = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, tab_bytes);
+            uint32_t *partials = NULL;
+            unsigned long long *totals = road->measure ? measure_scratch(rt, n, width, height, &partials) : NULL;
+            const unsigned long long *htotals = htab ? (const unsigned long long *)((const uint8_t *)htab + align_up(tab_bytes, 8)) : NULL;
             uint32_t *horigins = per_frame_regions && htab ? (uint32_t *)(htab + ptr_words) : NULL;
             const uint32_t *dorigins = per_frame_regions && dtab ? (const uint32_t *)(dtab + ptr_words) : NULL;
             unsigned present = 0, k;
             int wide = (row_bytes & 15u) == 0 && !ctx->no_wide_planes;      /* A8 pictures: every one of the slice 16-byte aligned, and the pitch */
-            if (!htab || !dtab) {
+            if (!htab || !dtab || (road->measure && !totals)) {
                 for (f = 0; f < n; f++)
                     results[done + f] = HapResult_Internal_Error;
                 first_error = first_error ? first_error : HapResult_Internal_Error;
@@ -2344,8 +2416,8 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
                      used[e] != blocks * hapf_block_bytes(fmt) ||
                      (texture_count == 2 && (fmts[e + 1] != HapTextureFormat_A_RGTC1 || used[e + 1] != blocks * 8u))))
                     r = HapResult_Bad_Arguments;
-                if (r == HapResult_No_Error && road->planes && !is_dev(ctx, dst)) {
-                    r = HapResult_Bad_Arguments;        /* tensors live in device memory: no host staging road */
+                if (r == HapResult_No_Error && (road->planes || road->measure) && !is_dev(ctx, dst)) {
+                    r = HapResult_Bad_Arguments;        /* tensors and reference pictures live in device memory: no host staging road */
                 } else if (r == HapResult_No_Error && !is_dev(ctx, dst)) {
                     if (!stage)
                         stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_RGBA_STAGE, align_up(rgba_bytes, 256) * n);
@@ -2374,8 +2446,12 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
                         const uint64_t *col = dtab + (size_t)k * 3u * n;
                         const HapGpuPictureTable t = {{col, col + n, col + 2u * (size_t)n}, {0u, 0u, 0u}};
                         rc |= launch_block_decode(rt, road, &t, n, texture_count == 2, width, height, road->kinds[k], row_bytes,
-                                                  wide, dorigins);
+                                                  wide, dorigins, partials, totals);
                     }
+                if (road->measure) {
+                    rc |= hapgpu_rt_d2h(rt, (void *)htotals, totals, totals_bytes);
+                    htotals_of_slice = htotals;
+                }
                 for (f = 0; f < n; f++)
                     if (results[done + f] == HapResult_No_Error && stage && !is_dev(ctx, rgba_frames[done + f])) {
                         /* (row by row when the client's rows are longer than the picture's: what lies between them -- the
@@ -2393,6 +2469,11 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
             for (f = 0; f < n; f++)
                 if (results[done + f] == HapResult_No_Error)
                     results[done + f] = HapResult_Internal_Error;
+        /* (the totals have arrived: every picture of a launch got its own eight) */
+        if (road->measure && htotals_of_slice)
+            for (f = 0; f < n; f++)
+                if (results[done + f] == HapResult_No_Error)
+                    measure_result(&road->measure[done + f], htotals_of_slice + 8u * (size_t)f, width, height);
         for (f = 0; f < n; f++)
             if (results[done + f] != HapResult_No_Error && first_error == HapResult_No_Error)
                 first_error = results[done + f];
@@ -2455,6 +2536,19 @@ unsigned hapb_decode_planes_region(HapGpuContext *ctx, unsigned frame_count, con
     }
     return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, tensors, width, height, row_bytes,
                            results, flags, &road);
+}
+
+/* ... and to no pictures at all: every frame against its RGBA8 reference picture in device memory, the sums of the
+   errors to errors[f] -- the same road with the measuring launch of bc_measure.hip, which reads the third column */
+unsigned hapb_measure_frames(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                             const unsigned long *input_bytes, unsigned texture_count, const void *const *rgba_frames,
+                             unsigned width, unsigned height, unsigned long row_bytes, HapGpuPictureError *errors,
+                             unsigned *results, unsigned flags)
+{
+    const picture_road road = measure_road_of(errors);
+    /* (the road's pictures are its third column whichever way the bytes go: this one only reads them) */
+    return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, (void *const *)rgba_frames, width, height,
+                           row_bytes, results, flags & ~HAPGPU_DECODE_BPTC_PICTURES, &road);
 }
 
 /* Hap HDR frames (one BC6H texture, unsigned or signed) -> RGBA16F pictures: the same road with the BC6H decoder */

@@ -150,6 +150,11 @@ unsigned hapb_compress_planes(HapGpuContext *ctx, const void *tensor, unsigned w
    HapGpuEncodeFramesPlanes).  Touches no device. */
 int hapb_planes_encode_valid(unsigned width, unsigned height, unsigned long row_bytes, const HapbPlanes *planes,
                              unsigned count, const unsigned *formats);
+/* one texture (host or device) against its RGBA8 reference picture in DEVICE memory (include/hap_gpu.h:
+   HapGpuMeasureTexture): DXT1, DXT5, YCoCg-DXT5 with an optional RGTC1 alpha plane; *error written on No_Error only */
+unsigned hapb_measure_texture(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
+                              const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
+                              const void *rgba, unsigned long row_bytes, HapGpuPictureError *error);
 /* 1: region is a block-aligned, non-empty rectangle inside region->width x height */
 int hapb_region_fits(const HapGpuRegion *region, unsigned height);
 /* pictures -> frames.  picture_kind RGBA8: the DXT / RGTC1 formats (BC7 with HAPGPU_ENCODE_BPTC_BLOCKS); RGBA16F (rows
@@ -192,6 +197,12 @@ unsigned hapb_decode_planes(HapGpuContext *ctx, unsigned frame_count, const void
                             const unsigned long *input_bytes, unsigned texture_count, void *const *tensors,
                             unsigned width, unsigned height, unsigned scale_log2, unsigned long row_bytes,
                             const HapbPlanes *planes, unsigned *results, unsigned flags);
+/* ... against RGBA8 reference pictures in device memory, which are read: errors[f] (host) gets frame f's sums, all zero
+   for a frame whose result is not No_Error */
+unsigned hapb_measure_frames(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                             const unsigned long *input_bytes, unsigned texture_count, const void *const *rgba_frames,
+                             unsigned width, unsigned height, unsigned long row_bytes, HapGpuPictureError *errors,
+                             unsigned *results, unsigned flags);
 /* ... a rectangle of every frame (region->width == width) to RGBA8 pictures of region->w x region->h */
 unsigned hapb_decode_rgba_region(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
                                  const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,

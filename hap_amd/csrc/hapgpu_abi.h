@@ -374,6 +374,21 @@ int hapgpu_k_block_decode_planes_region(hapgpu_rt *rt, const HapGpuPictureTable 
                                         unsigned region_height, unsigned scale_log2, unsigned channels,
                                         unsigned element_kind, size_t plane_bytes, size_t row_bytes, const float *scale,
                                         const float *bias);
+/* blocks of `hap_texture_format` against RGBA8 reference pictures (the third column of the table: read, not written),
+   without a decoded picture in between (bc_measure.hip): for every picture whose texture address is not 0,
+   totals[picture][0..3] = the sum over all width x height texels of (d - p)^2 for R, G, B, A and totals[picture][4..7] the
+   sum of |d - p|, d the byte hapgpu_k_block_decode writes for the texel and channel and p the reference picture's --
+   exact integers.  RGB_DXT1, RGBA_DXT5 and YCoCg_DXT5 (with_alpha: the RGTC1 plane supplies A; without one A is 255,
+   DXT5's own apart).  Two launches: a workgroup per 1024 blocks stores eight 32-bit partial sums to
+   partials[picture][workgroup][8] (device, 16-byte aligned, pictures * hapgpu_block_measure_partial_bytes(width, height)
+   bytes), then a workgroup per picture adds them in 64 bits to totals (device, 8-byte aligned); the totals of a picture
+   with texture address 0 are left as they are.  Textures and alpha planes aligned as for hapgpu_k_block_decode; reference
+   pictures and row_bytes (at least width * 4) 16-byte aligned, and only width * 4 bytes of each row are read.  The same
+   table, profile class and return codes. */
+int hapgpu_k_block_measure(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, int with_alpha,
+                           unsigned width, unsigned height, unsigned hap_texture_format, size_t row_bytes,
+                           uint32_t *partials, unsigned long long *totals);
+size_t hapgpu_block_measure_partial_bytes(unsigned width, unsigned height);
 /* planar tensors -> blocks of `hap_texture_format`, without an RGBA8 picture in between (bc_encode_planes.hip): the way
    back of hapgpu_k_block_decode_planes.  Tensors (the first column of the table) of `channels` (3 or 4: R, G, B[, A])
    planes plane_bytes apart, rows row_bytes apart, elements of element_kind (0 half, 1 bfloat16, 2 float: e = 2, 2, 4

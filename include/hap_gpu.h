@@ -723,6 +723,70 @@ unsigned int HapGpuDecodeFramesPlanesRegion(HapGpuContext *context, unsigned int
                                             unsigned int *results,
                                             unsigned int flags);
 
+/* How far a texture or a frame is from a picture (HapGpuMeasureTexture, HapGpuMeasureFrames): per channel the exact
+ * integer sums over all width x height texels.  72 bytes. */
+typedef struct HapGpuPictureError {
+    unsigned long long sse[4];   /* R, G, B, A: sum over texels of (d - p)^2 */
+    unsigned long long sad[4];   /* R, G, B, A: sum over texels of |d - p|   */
+    unsigned long long texels;   /* width * height when measured, 0 when not */
+} HapGpuPictureError;
+
+/* One texture (+ optional RGTC1 alpha plane) against the RGBA8 picture it was made from, or any other of its size: how
+ * close is the result to the source?  The block decoder adds up the errors from the texels it holds in registers; no
+ * decoded picture is written.
+ * The definition, and the only one.  d is the byte that HapGpuDecompressRGBA writes for a texel and channel; p is the
+ * byte of the caller's picture `rgba` at that texel and channel.  error->sse[c] is the sum of (d - p)^2 and
+ * error->sad[c] the sum of |d - p| over all width x height texels, c = R, G, B, A, as exact integers; error->texels is
+ * width * height.  A source without alpha decodes to A = 255, as it does in that call, and is compared with the
+ * picture's A like any other channel: the caller ignores sse[3] and sad[3] where they mean nothing.  The sums do not
+ * depend on how the work is laid out on the device: two calls give the same struct.  PSNR of channel c is
+ * 10 * log10(255^2 * texels / sse[c]), of R, G and B together 10 * log10(255^2 * 3 * texels / (sse[0] + sse[1] + sse[2])).
+ * width and height are multiples of 4; textures (host or device), textureFormat -- RGB_DXT1, RGBA_DXT5 or YCoCg_DXT5 --
+ * and the alpha plane follow HapGpuDecompressRGBA's rules.  The reference picture is in DEVICE memory and 16-byte aligned;
+ * rowBytes is a multiple of 16 and at least width * 4; only the picture's width * 4 bytes of each row are read, and
+ * nothing is written to it.  `error` is in host memory and is written on No_Error only.
+ * Bad_Arguments, and nothing written, for anything else: a host picture, a misaligned picture, a NULL error, any other
+ * format.
+ * Out of scope: RGBA_BPTC_UNORM (BC7) and the BC6H formats as sources, a lone A_RGTC1 against A8 pictures, RGBA16F
+ * pictures, scaled or rectangular measurement, host pictures. */
+unsigned int HapGpuMeasureTexture(HapGpuContext *context,
+                                  const void *texture, unsigned long textureBytes, unsigned int textureFormat,
+                                  const void *alphaTexture, unsigned long alphaTextureBytes,
+                                  unsigned int width, unsigned int height,
+                                  const void *rgba, unsigned long rowBytes, HapGpuPictureError *error);
+
+/* Frames in, errors out: HapGpuDecodeFramesRGBA with reference pictures that are read in place of pictures that are
+ * written -- rgbaFrames[f] is the RGBA8 picture in DEVICE memory that frame f is measured against (its source picture,
+ * or the decoded picture of an earlier generation), and errors[f] gets the sums of HapGpuMeasureTexture for it.
+ * The definition, and the only one.  d is the byte that HapGpuDecodeFramesRGBA writes for the frame at a texel and
+ * channel with the same textureCount and flags; p is the byte of rgbaFrames[f] there.  errors[f].sse[c] is the sum of
+ * (d - p)^2 and errors[f].sad[c] the sum of |d - p| over all width x height texels, exact integers; errors[f].texels
+ * is width * height.  A frame without alpha gives A = 255, compared like any other channel.  Two calls give the same
+ * structs.  No decoded picture ever exists: per Hap Q block 16 bytes of texture and 64 of the picture are read and
+ * nothing is written but a few sums.
+ * Frames, textureCount, formats (Hap, Hap Alpha, Hap Q, Hap Q Alpha), the flags of the second stage, mixed batches (one
+ * block launch per texture format present), slicing and results[f] are HapGpuDecodeFramesRGBA's, without
+ * HAPGPU_DECODE_BPTC_PICTURES, which is ignored.  A frame that fails -- a broken frame gets HapDecode's code; a frame of
+ * another format or geometry, or one whose picture is NULL, in host memory or misaligned, Bad_Arguments -- fails alone:
+ * its errors[f] is all zero and the other frames are measured.  The function's result is the first failure.  errors
+ * and results are HOST arrays of frameCount entries.  Pictures are 16-byte aligned, rowBytes is a multiple of 16 and at
+ * least width * 4, shared by all frames; only the pictures' bytes of each row are read.
+ * Bad_Arguments for the whole call -- every results[f] set, nothing else written -- for a NULL array (errors among
+ * them), a width or height that is no multiple of 4, a rowBytes that is too short or no multiple of 16.  A context
+ * between HapGpuEncodeFramesRGBABegin and HapGpuEncodeFramesFinish: Internal_Error.
+ * Out of scope: Hap R (BC7) and Hap HDR (BC6H) frames, Hap Alpha-Only frames (a lone A_RGTC1) against A8 pictures --
+ * Bad_Arguments alone --, RGBA16F pictures, scaled or rectangular measurement, ...OnDevices and ...Sequence forms of
+ * this call, host pictures. */
+unsigned int HapGpuMeasureFrames(HapGpuContext *context, unsigned int frameCount,
+                                 const void *const *inputBuffers,
+                                 const unsigned long *inputBuffersBytes,
+                                 unsigned int textureCount,
+                                 const void *const *rgbaFrames,
+                                 unsigned int width, unsigned int height, unsigned long rowBytes,
+                                 HapGpuPictureError *errors,
+                                 unsigned int *results,
+                                 unsigned int flags);
+
 /* Planar float tensors in, frames out -- the way back of HapGpuDecodeFramesPlanes: HapGpuEncodeFramesRGBA with the tensors of
  * HapGpuCompressPlanes in place of pictures.  planeFrames[f] is frame f's tensor in DEVICE memory, `channels` planes of
  * width x height elements, planeBytes and rowBytes shared by all frames (one N x C x H x W tensor: planeFrames[f] = base +
