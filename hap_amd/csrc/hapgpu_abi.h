@@ -222,6 +222,11 @@ typedef struct HapGpuScanChunk {
     uint32_t probe_found;    /* of the first two 8 KiB marks (output positions 8192 and 16384): the rest of the fine
                                 marks are only looked for when both fall on element boundaries -- in a libsnappy
                                 stream they hardly ever do, and its scan then costs what it did with 64 KiB marks only */
+    /* device: the workgroup-per-block kernel */
+    uint32_t dependent;      /* a 64 KiB block whose element chain it had verified copies from before the block: the
+                                stream's blocks are not independent, and the stream unit decodes it */
+    uint32_t resolved;       /* 64 KiB blocks of the stream it decoded; they count (HapGpuResolvedBlockCount) unless
+                                the stream turned out dependent, where the stream unit writes them again */
 } HapGpuScanChunk;
 
 typedef struct HapGpuScanSegment {   /* device only */

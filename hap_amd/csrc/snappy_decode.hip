@@ -307,9 +307,10 @@ __device__ __forceinline__ bool scan_fine_found(const HapGpuScanChunk *scan)
 
 // 2: the 8 KiB BLOCK units run; 1: every 64 KiB mark was found (libsnappy's blocks) -- the coarse ones; 0: the stream unit.
 // fine_ok: scan_fine_found, and no 8 KiB unit has failed as far as the caller has to know
+// (dependent: the workgroup-per-block kernel, which runs in front of the coarse units, found the blocks not independent)
 __device__ __forceinline__ unsigned scan_stream_mode(const HapGpuScanChunk *scan, bool fine_ok)
 {
-    return scan->ok == 0u ? 0u : fine_ok ? 2u : scan->found == scan->expected ? 1u : 0u;
+    return scan->ok == 0u ? 0u : fine_ok ? 2u : (scan->found == scan->expected && scan->dependent == 0u) ? 1u : 0u;
 }
 
 // the set a unit belongs to, in scan_stream_mode's numbers
@@ -1573,10 +1574,14 @@ __global__ __launch_bounds__(64) void scan_decide_kernel(const HapGpuScanChunk *
 //      chain of copies of copies (3 to 5 for Hap textures), every round over all 64 Ki pointers by all 1024 lanes;
 //   E. every copy byte fetches the literal byte its pointer names from memory and is stored.
 //
-// Anything unexpected -- a record that does not verify, an element the window parser does not take, a copy that reaches
-// before its block -- and the kernel returns without a word: the unit is still there for the wavefront-per-block kernel
-// of the launch that follows, which decides what the stream's fault is called.  A block that went through becomes a SKIP
-// unit.  One 8K frame of the reference encoder: two blocks per CU instead of two wavefronts per CU.
+// Anything unexpected -- a record that does not verify, an element the window parser does not take -- and the kernel
+// returns without a word: the unit is still there for the wavefront-per-block kernel of the launch that follows, which
+// decides what the stream's fault is called.  A block that went through becomes a SKIP unit.  A copy that reaches before
+// its block, in a block whose chain verifies, is no fault: the stream is valid Snappy that is not made of independent
+// blocks.  The kernel says so in the stream's scan entry (`dependent`), the stream unit of the launch that follows
+// decodes the stream whole -- its BLOCK units would fail at that copy and have the frame decoded a second time -- and
+// the stream's blocks that workgroups had taken by then do not count.
+// One 8K frame of the reference encoder: two blocks per CU instead of two wavefronts per CU.
 constexpr unsigned kBrkWaves = 16u, kBrkThreads = 64u * kBrkWaves;
 constexpr unsigned kBrkMaxWindows = 1024u;          // compressed bytes of a block this kernel takes: 64 KiB (libsnappy's blocks: ~21 KiB of a Hap Q texture)
 constexpr unsigned kBrkOwner = 512u;                // output bytes of one production pass of a wavefront
@@ -1593,6 +1598,7 @@ struct BrkLds {
     uint8_t owner[kBrkWaves][kBrkOwner];
     uint8_t stage[kBrkWaves][kBrkStage + 16u];
     uint32_t fail;
+    uint32_t reach;                                 // an element parsed so far is a copy from before the block
     uint32_t ends;                                  // chains that end at the block's end
     uint32_t work;                                  // the block the workgroup has just taken
     uint32_t stream_first[256u + 1u];               // blocks of the call's scanned streams before stream c (kBrkMaxStreams)
@@ -1672,8 +1678,11 @@ __device__ __forceinline__ bool brk_do_window(BrkLds &L, unsigned wave, unsigned
                 dst[op + done] = src_al[at + done];
             }
             op += llen;
-            e += h + llen;                           // (far beyond this window)
-            break;
+            // (far beyond this window as a rule -- but a few bytes written with 2..4 length bytes, which is valid if not
+            // canonical, may end inside it: the elements behind them are this pass's too, or the window's exit would
+            // lie in the window itself and the block be declined for it)
+            e += h + llen;
+            continue;
         }
         bool is_tok = __builtin_amdgcn_inverse_ballot_w64(T);
         const int incl = wave_scan_add(is_tok ? (int)len : 0);
@@ -1683,9 +1692,14 @@ __device__ __forceinline__ bool brk_do_window(BrkLds &L, unsigned wave, unsigned
         const unsigned last = 63u - (unsigned)__builtin_clzll(T);
         const unsigned N = (unsigned)__builtin_amdgcn_readlane(incl, (int)last);
         const unsigned adv = last + (unsigned)__builtin_amdgcn_readlane((int)tokbytes, (int)last);
-        const bool bad = is_tok && ((kind != 0u && (off == 0u || off > op + o_t)) || len > out_len - op - o_t || o_t > out_len - op);
+        const bool bad = is_tok && ((kind != 0u && off == 0u) || len > out_len - op - o_t || o_t > out_len - op);
         if (op > out_len || ballot64(bad) != 0ull)
-            return false;                            // (a copy from before the block among them: not this kernel's business)
+            return false;
+        // a copy from before the block: noted, and parsed on as if it copied itself (whatever its bytes get is never
+        // used) -- once the block's chain is verified the note says that the STREAM is not made of independent blocks
+        const bool reach = is_tok && kind != 0u && off > op + o_t;
+        if (ballot64(reach) != 0ull && lane == 0u)
+            L.reach = 1u;
         for (unsigned k4 = lane * 4u; k4 < N; k4 += 256u)
             *reinterpret_cast<uint32_t *>(owner + k4) = 0u;
         if (is_tok)
@@ -1694,7 +1708,7 @@ __device__ __forceinline__ bool brk_do_window(BrkLds &L, unsigned wave, unsigned
         // at 511, << 20 (it only matters where it is shorter than the copy); a1 = where the bytes come from: the
         // literal's place in the staged bytes, or the copy's source position in the block
         const int a0 = (int)(o_t | (len << 10) | (kind == 0u ? (1u << 19) : 0u) | (min(off, 511u) << 20));
-        const int a1 = (int)(kind == 0u ? lane + hdr : op + o_t - off);
+        const int a1 = (int)(kind == 0u ? lane + hdr : op + o_t - (reach ? 0u : off));
         unsigned carry = 0;
         for (unsigned B = 0; B < N; B += 64u) {
             const unsigned bb = B + lane;
@@ -1813,6 +1827,7 @@ __device__ __forceinline__ void brk_block(BrkLds &L, HapGpuDecodeUnit *units, un
         *reinterpret_cast<uint4 *>(&L.ptr[i]) = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
     if (tid == 0) {
         L.fail = 0u;
+        L.reach = 0u;
         L.ends = 0u;
     }
     __syncthreads();
@@ -1930,6 +1945,14 @@ __device__ __forceinline__ void brk_block(BrkLds &L, HapGpuDecodeUnit *units, un
         BRK_WHY(L.fail != 0u ? 3 : L.ends != 1u ? 4 : 5);
         return;
     }
+    if (L.reach != 0u) {
+        // (every window that was parsed lies on the block's verified chain: the copy from before the block is the
+        // stream's own.  Its 64 KiB units stand back for the stream unit in the launch that follows -- they would fail
+        // at that copy and have the whole frame decoded again)
+        if (tid == 0)
+            __hip_atomic_store(&const_cast<HapGpuScanChunk *>(scan)->dependent, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
     BRK_STAMP(3);
 
     // ---- C. pointer jumping: a group of four whose pointers have stopped moving is left alone from then on ----
@@ -1954,10 +1977,12 @@ __device__ __forceinline__ void brk_block(BrkLds &L, HapGpuDecodeUnit *units, un
                 for (unsigned k = 0; k < 4u; k++)
                     if (k >= n)
                         p[k] = base + k;             // (beyond a short block's end: nobody's bytes)
+                // (... and not to be looked up: their slots still hold the 0xFFFF they were initialised with, which would
+                // keep the group moving through every round and have the finished block declined)
                 unsigned q[4];
 #pragma unroll
                 for (unsigned k = 0; k < 4u; k++)
-                    q[k] = L.ptr[p[k]];
+                    q[k] = k < n ? L.ptr[p[k]] : p[k];
                 if (q[0] == p[0] && q[1] == p[1] && q[2] == p[2] && q[3] == p[3]) {
                     pending &= ~(1u << it);          // (what they point at points at itself: literal bytes)
                 } else {
@@ -2009,8 +2034,7 @@ __device__ __forceinline__ void brk_block(BrkLds &L, HapGpuDecodeUnit *units, un
     BRK_STAMP(5);
     if (tid == 0) {
         units[unit_index].kind = HAPGPU_UNIT_SKIP;
-        if (resolved_counter)
-            atomicAdd(resolved_counter, 1u);
+        atomicAdd(&const_cast<HapGpuScanChunk *>(scan)->resolved, 1u);       // (counted when the launch ends: see there)
 #ifdef BRK_TIMING
         if (resolved_counter) {
             for (unsigned k = 0; k < 5u; k++)
@@ -2027,6 +2051,7 @@ __device__ __forceinline__ void brk_block(BrkLds &L, HapGpuDecodeUnit *units, un
 // blocks of an 8K frame, this takes 258), full blocks first.  The blocks are those of the call's scanned streams (scan_merge
 // wrote their units behind each stream's own): stream c's block b is units[chunks[c].unit + 1 + b].
 constexpr unsigned kBrkMaxStreams = 256u;
+constexpr unsigned kBrkDoneWord = 40u;             // (of the runtime's 64 counter words; measurement builds use 2..21)
 __global__ __launch_bounds__(kBrkThreads) void snappy_decode_block_resolve_kernel(HapGpuDecodeUnit *units, unsigned unit_count,
                                                                                   const HapGpuScanChunk *chunks, unsigned chunk_count,
                                                                                   const HapGpuDecodeJob *jobs,
@@ -2079,6 +2104,26 @@ __global__ __launch_bounds__(kBrkThreads) void snappy_decode_block_resolve_kerne
         }
         brk_block(L, units, chunks[lo].unit + 1u + (j - L.stream_first[lo]), only_full, jobs, recs, joins, resolved_counter);
         __syncthreads();
+    }
+    // The blocks that went through count for the streams that were not found dependent meanwhile (whose stream unit
+    // writes them again): the workgroup that finishes last adds them up.  resolved_counter[kBrkDoneWord]: workgroups that
+    // have finished (zero between launches: the last one puts it back).
+    if (resolved_counter) {
+        __threadfence();
+        if (tid == 0)
+            L.work = atomicAdd(resolved_counter + kBrkDoneWord, 1u);
+        __syncthreads();
+        if (L.work == gridDim.x - 1u) {
+            __threadfence();
+            if (tid < chunk_count) {
+                HapGpuScanChunk *sc = const_cast<HapGpuScanChunk *>(chunks) + tid;
+                const unsigned n = __hip_atomic_load(&sc->resolved, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (n != 0u && __hip_atomic_load(&sc->dependent, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
+                    atomicAdd(resolved_counter, n);
+            }
+            if (tid == 0)
+                resolved_counter[kBrkDoneWord] = 0u;
+        }
     }
 }
 

@@ -1880,26 +1880,7 @@ def test_field_stream_promises_are_checked_on_hand_made_streams(ctx, hap):
 
 
 # ------------------------------------------ other encoders' streams: block scan, then one unit per 64 KiB block --
-def _varint(v):
-    out = bytearray()
-    while v >= 0x80:
-        out.append((v & 0x7F) | 0x80)
-        v >>= 7
-    out.append(v)
-    return bytes(out)
-
-
-def _frame_of_streams(streams, fmt_byte=0xCE):
-    """A Hap frame whose texture is these Snappy streams, one chunk each (decode instructions container with
-    compressor and size tables)."""
-    n = len(streams)
-    comp = bytes([n & 255, n >> 8 & 255, n >> 16, 2]) + bytes([0x0B] * n)
-    sizes = bytes([(4 * n) & 255, (4 * n) >> 8 & 255, (4 * n) >> 16, 3]) + b"".join(len(s).to_bytes(4, "little") for s in streams)
-    tables = comp + sizes
-    body = len(tables).to_bytes(3, "little") + bytes([1]) + tables + b"".join(streams)
-    if len(body) < (1 << 24):
-        return len(body).to_bytes(3, "little") + bytes([fmt_byte]) + body
-    return bytes([0, 0, 0, fmt_byte]) + len(body).to_bytes(4, "little") + body
+from _snappy_streams import frame_of_streams as _frame_of_streams, varint as _varint  # noqa: E402
 
 
 def test_block_scan_decodes_what_the_whole_stream_decoder_decodes(ctx, hap):
@@ -1959,14 +1940,17 @@ def test_block_scan_decodes_what_the_whole_stream_decoder_decodes(ctx, hap):
             made += n
         return b"".join(els)
 
-    def check(frame, nbytes, what, expect_ok=True):
+    def check(frame, nbytes, what, expect_ok=True, blocks=None):
         rc, want, fmt = ORA.decode(frame, 0, nbytes)
         assert (rc == 0) == expect_ok, (what, rc)
         got = {}
         for flags in (0, hap_amd_flags.DECODE_NO_BLOCK_SCAN):
             out = np.full(nbytes, 0x5A, dtype=np.uint8)
+            n0 = ctx.resolved_blocks()
             r, used, fmts, res = ctx.decode_frames([frame], [len(frame)], 0, [out], flags)
             got[flags] = (r, res[0], used[0] if r == 0 else 0, out.tobytes() if r == 0 else None)
+            # (blocks: how many of them a workgroup each must have taken when the scan ran, none when it did not)
+            assert blocks is None or ctx.resolved_blocks() - n0 == (blocks if flags == 0 else 0), (what, flags, blocks)
         assert got[0] == got[hap_amd_flags.DECODE_NO_BLOCK_SCAN], what
         if rc == 0:
             assert got[0] == (0, 0, nbytes, want), what
@@ -1975,12 +1959,18 @@ def test_block_scan_decodes_what_the_whole_stream_decoder_decodes(ctx, hap):
             assert got[0][0] == rc and got[0][1] == rc, (what, got[0][:2], rc)
 
     import hap_amd as hap_amd_flags
+    import _snappy_streams as _SS
     K = 65536
     # 1. honest streams: 1..5 blocks, last one short / exactly full / one byte; several chunks of different length
     for name, lens in [("two full", [K, K]), ("short tail", [K, K, 1000]), ("one byte tail", [K, K, K, 1]),
                        ("five", [K] * 4 + [K - 1]), ("single", [K]), ("just over", [K, 1])]:
         stream = _varint(sum(lens)) + b"".join(block(n, 100 + i) for i, n in enumerate(lens))
-        check(_frame_of_streams([stream]), sum(lens), name)
+        # a stream of one block is not scanned; of the others a workgroup takes every block, whatever its length, that
+        # is compressed to at most 1024 windows of 64 bytes -- counted here for the streams that hold no other block
+        spans = [_SS.windows_spanned(a, b, s) for a, b, _n, _ok in _SS.blocks_of(stream) for s in _SS.ADDRESS_PHASES]
+        taken = 0 if len(lens) == 1 else len(lens) if max(spans) <= _SS.MAX_WINDOWS else None
+        assert taken is not None or name not in ("one byte tail", "five"), (name, max(spans))
+        check(_frame_of_streams([stream]), sum(lens), name, blocks=taken)
     many = [_varint(3 * K + 77 * c) + block(K, c) + block(K, c + 50) + block(K, c + 90) + block(77 * c, c + 7)
             for c in range(1, 6)]
     check(_frame_of_streams(many), sum(3 * K + 77 * c for c in range(1, 6)), "five chunks")
@@ -2159,6 +2149,8 @@ def test_block_scan_on_corrupted_streams_matches_the_checker(ctx, hap):
             f[i] = int(rng.choice([0xF4, 0xF8, 0xFC, 0xF0, 0x03, 0xFF]))
         f = bytes(f)
         ro, oo, fo = ORA.decode(f, 0, len(tex))
+        for name, api in CHECKERS:
+            assert api.decode(f, 0, len(tex)) == (ro, oo, fo), (name, trial, i)
         got = {}
         for flags in (0, hap.DECODE_NO_BLOCK_SCAN):
             out = np.zeros(len(tex), dtype=np.uint8)
