@@ -6,8 +6,12 @@
 // fragment + hash table fit in LDS many times per CU.  Output is ordinary Snappy elements
 // (literal / copy-1 / copy-2); a chunk's stream is varint(chunk bytes) followed by its fragments'
 // element runs, concatenated by the pack/gather kernels (frame_pack.hip).  The produced bytes
-// differ from libsnappy's (Snappy encoding is not unique); parity is defined as: the reference
-// decoder reproduces the input exactly.
+// differ from libsnappy's (Snappy encoding is not unique).  Parity is defined twice: the reference
+// decoder reproduces the input exactly, and every byte is the one the scalar definition
+// tests/_position_streams.py writes (its header states the rules one by one).  The definition is pinned to
+// libsnappy, the oracle and hand-written streams by tests/test_position_streams.py; the kernel is held to it on
+// every road of the library that reaches it by tests/test_position_streams_gpu.py, sweeps of repeat lengths,
+// offsets, positions, literal lengths, table timing and short last fragments.
 //
 // Block textures (DXT1 / DXT5 / YCoCg-DXT5, large RGTC1 planes) go to the block-per-lane kernels of
 // snappy_compress_blocks.hip; this file holds the compressor for everything else:
@@ -72,12 +76,13 @@ __device__ __forceinline__ unsigned run_from(unsigned long long cur, unsigned lo
 // workgroup-per-fragment compressor
 // ------------------------------------------------------------------------------------------
 //
-// Same element stream rules as the kernel above, restructured for throughput:
+// The element stream rules are those of tests/_position_streams.py; how the kernel gets there:
 //   * 4 wavefronts share one fragment (data + hash table in LDS once, 4x the waves per CU);
 //     in every ROUND wave w takes the 128-byte supertile 4*round + w (two 64-byte tiles).
 //   * rounds are synchronous: all lookups of a round read the hash table as it was after the
 //     previous round, then all waves insert with LDS atomicMax (u32 entries, the most recent
-//     position wins) -- the output does not depend on wave timing (deterministic).
+//     position wins) -- the output does not depend on wave timing (deterministic: the definition knows no
+//     waves, and the GPU tests encode every input in a batch of three as well).
 //   * copies never cross a supertile boundary, so supertiles are independent; their sizes are
 //     exchanged through LDS at the round barrier and every wave writes its bytes straight to
 //     their final position (no staging, no compaction pass).
@@ -214,7 +219,7 @@ __global__ __launch_bounds__(64 * kWgWaves) void snappy_compress_wg_kernel(const
     const unsigned x = blockIdx.x;
     // (one combined test, no short-circuit: every field is requested before the first wait)
     if ((blockIdx.y >= tex_count) | (tex.compressor != 1u) | ((1u << (tex.reserved & 0xFFu)) != GRAN) |
-        (((tex.reserved >> 16) & 0xFu) != 0u) |        // field-per-lane textures belong to the kernel below
+        (((tex.reserved >> 16) & 0xFu) != 0u) |        // field-per-lane textures belong to snappy_compress_blocks.hip
         (x >= tex.chunk_count * tex.frags_per_chunk) | (tex.src == 0) | (tex.chunk_bytes == 0))
         return;
     const unsigned chunk = x / tex.frags_per_chunk, j = x - chunk * tex.frags_per_chunk;
@@ -359,8 +364,9 @@ __global__ __launch_bounds__(64 * kWgWaves) void snappy_compress_wg_kernel(const
 #pragma unroll
             for (int sub = 0; sub < (int)kSubs; sub++) {
                 const unsigned room = room2[sub];
-                // best candidate as one key: (length << 3) | priority, nearer fixed distances win ties,
-                // the hash candidate (priority 0) only when strictly longer
+                // best candidate as one key: (length << 3) | priority.  The priority of a fixed distance is its number
+                // of pitches, so the FARTHER of two fixed distances wins a tie (as often as not a copy that does not
+                // overlap its own output); the hash candidate (priority 0) only when strictly longer
                 unsigned best_key = (hlen[sub] & ~(GRAN - 1u)) << 3;
 #pragma unroll
                 for (int d = kFixed - 1; d >= 0; d--) {
@@ -435,7 +441,7 @@ __global__ __launch_bounds__(64 * kWgWaves) void snappy_compress_wg_kernel(const
                 m_e0[sub] = e0;
                 m_e1[sub] = e1;
                 m_e2[sub] = e2;
-                m_insert[sub] = (lit | sel) & mask4[sub];       // only element starts are remembered (see the single-wave kernel)
+                m_insert[sub] = (lit | sel) & mask4[sub];       // literal granules and copy starts with 4 bytes left; what a copy covers is not entered
             }
         }
         if (lane == 0)
