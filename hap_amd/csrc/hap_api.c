@@ -335,7 +335,7 @@ unsigned int HapEncode(unsigned int count, const void **inputBuffers, unsigned l
     if (!ctx)
         return HapResult_Internal_Error;
     rc = hapb_encode(ctx, 1, count, (const void *const *)inputBuffers, inputBuffersBytes, textureFormats,
-                     compressors, chunkCounts, &out, &outputBufferBytes, &used, &result, flags, 0);
+                     compressors, chunkCounts, &out, &outputBufferBytes, &used, &result, flags, NULL);
     release_default_context(ctx);
     if (rc == HapResult_No_Error)
         *outputBufferBytesUsed = used;
@@ -348,6 +348,7 @@ unsigned int HapDecode(const void *inputBuffer, unsigned long inputBufferBytes, 
                        unsigned long outputBufferBytes, unsigned long *outputBufferBytesUsed,
                        unsigned int *outputBufferTextureFormat)
 {
+    const HapbDecodeArgs client = {NULL, NULL, NULL, 0, NULL, 0u, callback, info};
     HapGpuContext *ctx;
     unsigned result = HapResult_Internal_Error, rc, fmt = 0;
     unsigned long used = 0;
@@ -357,7 +358,7 @@ unsigned int HapDecode(const void *inputBuffer, unsigned long inputBufferBytes, 
     if (!ctx)
         return HapResult_Internal_Error;
     rc = hapb_decode(ctx, 1, &inputBuffer, &inputBufferBytes, index, &outputBuffer, &outputBufferBytes, &used,
-                     &fmt, &result, 0, callback, info);
+                     &fmt, &result, 0, &client);
     release_default_context(ctx);
     /* the reference stores the format as soon as the section type has been read (hap.c:754) */
     *outputBufferTextureFormat = fmt;
@@ -662,13 +663,13 @@ unsigned int HapGpuEncodeFrames(HapGpuContext *context, unsigned int frameCount,
     if (frameCount <= HAP_BATCH_SLICE || !inputBuffers || !outputBuffers || !outputBuffersBytes || !outputBuffersBytesUsed || !results ||
         count == 0 || count > 2) {
         r = hapb_encode(context, frameCount, count, inputBuffers, inputBuffersBytes, textureFormats, compressors,
-                        chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, 0);
+                        chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, NULL);
     } else {
         for (done = 0; done < frameCount; done += HAP_BATCH_SLICE) {
             const unsigned n = frameCount - done < HAP_BATCH_SLICE ? frameCount - done : HAP_BATCH_SLICE;
             const unsigned rc = hapb_encode(context, n, count, inputBuffers + (size_t)done * count, inputBuffersBytes, textureFormats,
                                             compressors, chunkCounts, outputBuffers + done, outputBuffersBytes + done,
-                                            outputBuffersBytesUsed + done, results + done, flags, 0);
+                                            outputBuffersBytesUsed + done, results + done, flags, NULL);
             if (r == HapResult_No_Error)
                 r = rc;
         }
@@ -722,11 +723,9 @@ unsigned int HapGpuEncodeFramesRGBABegin(HapGpuContext *context, unsigned int fr
     if (!context || frameCount > HAP_BATCH_SLICE)
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
-    context->defer_encode = 1u;
-    r = hapb_encode_rgba(context, frameCount, rgbaFrames, width, height, rowBytes, count, textureFormats,
-                         compressors, chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed,
-                         results, flags);
-    context->defer_encode = 0u;
+    r = hapb_encode_pictures(context, frameCount, rgbaFrames, width, height, rowBytes, count, textureFormats,
+                             compressors, chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed,
+                             results, flags, HAPGPU_PICTURE_RGBA8, 1);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -788,7 +787,7 @@ unsigned int HapGpuEncodeFramesPlanes(HapGpuContext *context, unsigned int frame
         const unsigned rc = hapb_encode_planes(context, n, planeFrames + done, width, height, rowBytes, &layout, count,
                                                textureFormats, compressors, chunkCounts, outputBuffers + done,
                                                outputBuffersBytes + done, outputBuffersBytesUsed + done, results + done,
-                                               flags);
+                                               flags, 0);
         if (r == HapResult_No_Error)
             r = rc;
     }
@@ -814,11 +813,9 @@ unsigned int HapGpuEncodeFramesPlanesBegin(HapGpuContext *context, unsigned int 
                               chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results) || !context)
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
-    context->defer_encode = 1u;
     r = hapb_encode_planes(context, frameCount, planeFrames, width, height, rowBytes, &layout, count, textureFormats,
                            compressors, chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results,
-                           flags);
-    context->defer_encode = 0u;
+                           flags, 1);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -852,14 +849,14 @@ unsigned int HapGpuEncodeFramesRGBAHalf(HapGpuContext *context, unsigned int fra
     hapgpu_rt_lock(context->rt);
     if (frameCount <= HAP_BATCH_SLICE || !rgbaHalfFrames || !outputBuffers || !outputBuffersBytes || !outputBuffersBytesUsed || !results) {
         r = hapb_encode_pictures(context, frameCount, rgbaHalfFrames, width, height, rowBytes, 1u, &textureFormat, &compressor,
-                             &chunkCount, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, HAPGPU_PICTURE_RGBA16F);
+                             &chunkCount, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, HAPGPU_PICTURE_RGBA16F, 0);
     } else {
         for (done = 0; done < frameCount; done += HAP_BATCH_SLICE) {
             const unsigned n = frameCount - done < HAP_BATCH_SLICE ? frameCount - done : HAP_BATCH_SLICE;
             const unsigned rc = hapb_encode_pictures(context, n, rgbaHalfFrames + done, width, height, rowBytes, 1u, &textureFormat,
                                                  &compressor, &chunkCount, outputBuffers + done, outputBuffersBytes + done,
                                                  outputBuffersBytesUsed + done, results + done, flags,
-                                                 HAPGPU_PICTURE_RGBA16F);
+                                                 HAPGPU_PICTURE_RGBA16F, 0);
             if (r == HapResult_No_Error)
                 r = rc;
         }
@@ -880,10 +877,8 @@ unsigned int HapGpuEncodeFramesRGBAHalfBegin(HapGpuContext *context, unsigned in
     if (!context || frameCount > HAP_BATCH_SLICE)
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
-    context->defer_encode = 1u;
     r = hapb_encode_pictures(context, frameCount, rgbaHalfFrames, width, height, rowBytes, 1u, &textureFormat, &compressor,
-                         &chunkCount, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, HAPGPU_PICTURE_RGBA16F);
-    context->defer_encode = 0u;
+                         &chunkCount, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, HAPGPU_PICTURE_RGBA16F, 1);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -930,14 +925,14 @@ unsigned int HapGpuEncodeFramesAlpha(HapGpuContext *context, unsigned int frameC
     if (frameCount <= HAP_BATCH_SLICE || !alphaFrames || !outputBuffers || !outputBuffersBytes || !outputBuffersBytesUsed || !results) {
         r = hapb_encode_pictures(context, frameCount, alphaFrames, width, height, rowBytes, 1u, &format, &compressor,
                                  &chunkCount, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags,
-                                 HAPGPU_PICTURE_A8);
+                                 HAPGPU_PICTURE_A8, 0);
     } else {
         for (done = 0; done < frameCount; done += HAP_BATCH_SLICE) {
             const unsigned n = frameCount - done < HAP_BATCH_SLICE ? frameCount - done : HAP_BATCH_SLICE;
             const unsigned rc = hapb_encode_pictures(context, n, alphaFrames + done, width, height, rowBytes, 1u, &format,
                                                      &compressor, &chunkCount, outputBuffers + done, outputBuffersBytes + done,
                                                      outputBuffersBytesUsed + done, results + done, flags,
-                                                     HAPGPU_PICTURE_A8);
+                                                     HAPGPU_PICTURE_A8, 0);
             if (r == HapResult_No_Error)
                 r = rc;
         }
@@ -958,11 +953,9 @@ unsigned int HapGpuEncodeFramesAlphaBegin(HapGpuContext *context, unsigned int f
     if (!context || frameCount > HAP_BATCH_SLICE)
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
-    context->defer_encode = 1u;
     r = hapb_encode_pictures(context, frameCount, alphaFrames, width, height, rowBytes, 1u, &format, &compressor,
                              &chunkCount, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags,
-                             HAPGPU_PICTURE_A8);
-    context->defer_encode = 0u;
+                             HAPGPU_PICTURE_A8, 1);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -975,14 +968,13 @@ unsigned int HapGpuEncodeFramesBegin(HapGpuContext *context, unsigned int frameC
                                      unsigned long *outputBuffersBytesUsed, unsigned int *results,
                                      unsigned int flags)
 {
+    const HapbEncodeArgs deferred = {0, NULL, 1, 0};
     unsigned r;
     if (!context || frameCount > HAP_BATCH_SLICE)
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
-    context->defer_encode = 1u;
     r = hapb_encode(context, frameCount, count, inputBuffers, inputBuffersBytes, textureFormats, compressors, chunkCounts,
-                    outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, 0);
-    context->defer_encode = 0u;
+                    outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, &deferred);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -1014,13 +1006,13 @@ unsigned int HapGpuDecodeFrames(HapGpuContext *context, unsigned int frameCount,
     hapgpu_rt_lock(context->rt);
     if (frameCount <= HAP_BATCH_SLICE || !inputBuffers || !inputBuffersBytes || !outputBuffers || !outputBuffersBytes || !results) {
         r = hapb_decode(context, frameCount, inputBuffers, inputBuffersBytes, index, outputBuffers,
-                        outputBuffersBytes, outputBuffersBytesUsed, outputTextureFormats, results, flags, NULL, NULL);
+                        outputBuffersBytes, outputBuffersBytesUsed, outputTextureFormats, results, flags, NULL);
     } else {
         for (done = 0; done < frameCount; done += HAP_BATCH_SLICE) {
             const unsigned n = frameCount - done < HAP_BATCH_SLICE ? frameCount - done : HAP_BATCH_SLICE;
             const unsigned rc = hapb_decode(context, n, inputBuffers + done, inputBuffersBytes + done, index, outputBuffers + done,
                                             outputBuffersBytes + done, outputBuffersBytesUsed ? outputBuffersBytesUsed + done : NULL,
-                                            outputTextureFormats ? outputTextureFormats + done : NULL, results + done, flags, NULL, NULL);
+                                            outputTextureFormats ? outputTextureFormats + done : NULL, results + done, flags, NULL);
             if (r == HapResult_No_Error)
                 r = rc;
         }
@@ -1070,11 +1062,11 @@ unsigned int HapGpuDecodeFrameTextures(HapGpuContext *context, unsigned int fram
     hapgpu_rt_lock(context->rt);
     for (done = 0; done < entries; done += HAP_BATCH_SLICE) {
         const unsigned n = (unsigned)(entries - done < HAP_BATCH_SLICE ? entries - done : HAP_BATCH_SLICE);
-        unsigned rc;
-        context->decode_indices = indices + done;
-        rc = hapb_decode(context, n, inputs + done, bytes + done, 0, outputBuffers + done, outputBuffersBytes + done,
-                         outputBuffersBytesUsed ? outputBuffersBytesUsed + done : NULL,
-                         outputTextureFormats ? outputTextureFormats + done : NULL, results + done, flags, NULL, NULL);
+        const HapbDecodeArgs entries_of = {indices + done, NULL, NULL, 0, NULL, 0u, NULL, NULL};
+        const unsigned rc = hapb_decode(context, n, inputs + done, bytes + done, 0, outputBuffers + done, outputBuffersBytes + done,
+                                        outputBuffersBytesUsed ? outputBuffersBytesUsed + done : NULL,
+                                        outputTextureFormats ? outputTextureFormats + done : NULL, results + done, flags,
+                                        &entries_of);
         if (r == HapResult_No_Error)
             r = rc;
     }
@@ -1322,16 +1314,15 @@ unsigned int HapGpuDecodeChunkGroup(HapGpuContext *context, const void *inputBuf
                                     void *outputBuffer, unsigned long outputBufferBytes,
                                     unsigned long *outputBufferBytesUsed, unsigned int *outputBufferTextureFormat)
 {
-    chunk_group g;
+    chunk_group g = {firstChunk, chunkCount};
+    const HapbDecodeArgs group = {NULL, NULL, NULL, 0, NULL, 0u, run_chunk_group, &g};
     unsigned result = HapResult_Internal_Error, rc, fmt = 0;
     unsigned long used = 0;
     if (!context || !inputBuffer || index > 1 || !outputBuffer)
         return HapResult_Bad_Arguments;
-    g.first = firstChunk;
-    g.count = chunkCount;
     hapgpu_rt_lock(context->rt);
     rc = hapb_decode(context, 1, &inputBuffer, &inputBufferBytes, index, &outputBuffer, &outputBufferBytes, &used,
-                     &fmt, &result, 0, run_chunk_group, &g);
+                     &fmt, &result, 0, &group);
     hapgpu_rt_unlock(context->rt);
     if (outputBufferTextureFormat)
         *outputBufferTextureFormat = fmt;

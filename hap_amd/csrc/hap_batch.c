@@ -98,8 +98,12 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                      const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
                      void *const *outputs, const unsigned long *output_bytes,
                      unsigned long *output_used, unsigned *results, unsigned flags,
-                     int inputs_are_device)
+                     const HapbEncodeArgs *args)
 {
+    static const HapbEncodeArgs no_args;
+    const HapbEncodeArgs *const a = args ? args : &no_args;
+    const int inputs_are_device = a->inputs_are_device;
+    const HapbBlockEncodeJob *const job = a->job;
     tex_geom g[2];
     unsigned fine_counts[2] = {0u, 0u};
     unsigned i, f, first_error = HapResult_No_Error;
@@ -233,9 +237,8 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
            fragment itself, one pass less over the texture and the pixel loads of one wave under the matching of the
            others (snappy_compress_blocks.hip).  One texture per frame. */
         {
-            const HapbBlockEncodeJob *bj = ctx->block_encode_job;
-            if (bj && !ctx->no_fusion && count == 1u && bj->texel_bytes == 4u && !bj->planes.channels && (bj->row_bytes & 3u) == 0 &&
-                (unsigned long long)bj->row_bytes * bj->height < 0xFFFFFFFFull && bj->width / 4u >= 1u) {
+            if (job && !ctx->no_fusion && count == 1u && job->texel_bytes == 4u && !job->planes.channels && (job->row_bytes & 3u) == 0 &&
+                (unsigned long long)job->row_bytes * job->height < 0xFFFFFFFFull && job->width / 4u >= 1u) {
                 /* (code: HapGpuTexEnc.reserved bits 24..26; mask bit: which kernel the launcher starts) */
                 if (t->field_period == 4u && t->format == HapTextureFormat_YCoCg_DXT5) {
                     fused[i] = 3u; fused_mask |= 1u;
@@ -286,7 +289,7 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
        larger share of its life than in the kernel that makes its blocks itself.  16 8K Hap Q Alpha frames, 24 + 24
        chunks: compress 0.493 -> 0.722 ms for a gather of 0.106 -> 0.036; 4 16K frames, 64 + 64: 0.922 -> 1.537 for
        0.219 -> 0.082.  One texture per frame.) */
-    placed = (!ctx->no_placing && !ctx->placing_off && count == 1u && g[0].compressor == HapCompressorSnappy && g[0].field_period != 0u && frag_log2 == 13u &&
+    placed = (!ctx->no_placing && !a->never_place && !ctx->placing_off && count == 1u && g[0].compressor == HapCompressorSnappy && g[0].field_period != 0u && frag_log2 == 13u &&
               g[0].chunk_count <= 64u) ? 1u : 0u;
     slot_stride = (unsigned)align_up(frag_bytes + frag_bytes / 32u + 64u + HAPGPU_SLOT_SCRATCH_BYTES, 16);
     /* how far placed fragments can reach into the frame buffer if nothing shrinks (the frame is then encoded again, but
@@ -416,9 +419,9 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
             if (placed)
                 fe->chunk_acc = (uint64_t)(uintptr_t)(dacc + (size_t)k * chunks_per_frame);
             if (fused_mask) {
-                fe->rgba = ctx->block_encode_job->host_table[f];
-                fe->rgba_row_bytes = (uint32_t)ctx->block_encode_job->row_bytes;
-                fe->rgba_blocks_x = ctx->block_encode_job->width / 4u;
+                fe->rgba = job->host_table[f];
+                fe->rgba_row_bytes = (uint32_t)job->row_bytes;
+                fe->rgba_blocks_x = job->width / 4u;
             }
             for (i = 0; i < count; i++) {
                 HapGpuTexEnc *te = &fe->tex[i];
@@ -456,7 +459,6 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
             /* The launches of this call as one sequence.  With every buffer in device memory (nothing staged) nothing
                in it depends on the buffers themselves -- their addresses are in the tables copied from pinned memory --
                so the sequence is recorded once per geometry as a HIP graph and replayed with one launch. */
-            const HapbBlockEncodeJob *job = ctx->block_encode_job;
             uint64_t key = 0xCBF29CE484222325ull;
             int graph = 2;
             unsigned launch_rc = 0;
@@ -584,12 +586,12 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
             pd->stage_off_out = stage_off_out;
             pd->hframes = hframes;
             pd->out_stage = out_stage;
-            if (ctx->block_encode_job) {
-                pd->job = *ctx->block_encode_job;
+            if (job) {
+                pd->job = *job;
                 pd->has_job = 1;
             }
             free(stage_off_in);
-            if (ctx->defer_encode) {
+            if (a->defer) {
                 ctx->pending_encode = pd;
                 return first_error;
             }
@@ -654,8 +656,8 @@ unsigned hapb_encode_complete(HapGpuContext *ctx, HapbEncodePending *pd)
             again += results[f] == HAPGPU_STATUS_NOT_PLACED;
         if (again) {
             /* all of them in one batch */
-            const HapbBlockEncodeJob *const outer_job = ctx->block_encode_job;
-            const unsigned saved_no_placing = ctx->no_placing, saved_defer = ctx->defer_encode;
+            /* (results before it returns, and through slots: such a call cannot report a frame as not placed) */
+            HapbEncodeArgs again_args = {pd->inputs_are_device, NULL, 0, 1};
             HapbBlockEncodeJob rjob;
             uint64_t *rtable = NULL;
             const void **rin = (const void **)malloc(sizeof(void *) * (size_t)again * count);
@@ -683,7 +685,6 @@ unsigned hapb_encode_complete(HapGpuContext *ctx, HapbEncodePending *pd)
                         }
                         rmap[m++] = f;
                     }
-                ctx->block_encode_job = NULL;
                 if (pd->has_job) {
                     /* the table goes where the first pass's was: pinned memory at an address that stays -- a recorded
                        launch sequence (HAP_AMD_GRAPHS) copies from THAT address again when it is replayed (found by
@@ -697,17 +698,11 @@ unsigned hapb_encode_complete(HapGpuContext *ctx, HapbEncodePending *pd)
                     } else {
                         rjob.host_table = rtable;
                     }
-                    ctx->block_encode_job = &rjob;
+                    again_args.job = &rjob;
                 }
-                ctx->no_placing = 1u;
-                ctx->defer_encode = 0u;
                 hapb_encode(ctx, again, count, rin, pd->input_bytes, pd->formats, pd->compressors, pd->chunk_counts, rout, rcap, rused, rres,
-                            flags, pd->inputs_are_device);
-                ctx->defer_encode = saved_defer;
-                ctx->no_placing = saved_no_placing;
-                ctx->block_encode_job = outer_job;
+                            flags, &again_args);
                 for (m = 0; m < again; m++) {
-                    /* (a call without placing cannot report a frame as not placed) */
                     results[rmap[m]] = rres[m] == HAPGPU_STATUS_NOT_PLACED ? HapResult_Internal_Error : rres[m];
                     output_used[rmap[m]] = rused[m];
                 }
@@ -1140,7 +1135,7 @@ unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *
                           unsigned long *output_used, unsigned *results, unsigned flags)
 {
     return hapb_encode_pictures(ctx, frame_count, rgba_frames, width, height, row_bytes, count, formats, compressors,
-                                chunk_counts, outputs, output_bytes, output_used, results, flags, HAPGPU_PICTURE_RGBA8);
+                                chunk_counts, outputs, output_bytes, output_used, results, flags, HAPGPU_PICTURE_RGBA8, 0);
 }
 
 /* the size of an element of a planar tensor */
@@ -1176,7 +1171,7 @@ static unsigned encode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
                                 const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
                                 void *const *outputs, const unsigned long *output_bytes,
                                 unsigned long *output_used, unsigned *results, unsigned flags, unsigned picture_kind,
-                                const HapbPlanes *planes)
+                                const HapbPlanes *planes, int defer)
 {
     hapgpu_rt *rt = ctx->rt;
     const size_t texel = planes ? plane_element_bytes(planes->element) : HAPGPU_PICTURE_TEXEL_BYTES(picture_kind);
@@ -1263,6 +1258,7 @@ static unsigned encode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
        issued by hapb_encode at the head of its own launches: one sequence per call */
     {
         HapbBlockEncodeJob job;
+        const HapbEncodeArgs args = {rgba_stage ? 2 : 1, &job, defer, 0};
         memset(&job, 0, sizeof(job));
         job.host_table = hsrc;
         job.device_table = dsrc;
@@ -1284,10 +1280,8 @@ static unsigned encode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
                 job.plane_bias[i] = planes->bias[i];
             }
         }
-        ctx->block_encode_job = &job;
         rc = hapb_encode(ctx, frame_count, count, tex_ptrs, tex_bytes, formats, compressors, chunk_counts, outputs,
-                         output_bytes, output_used, results, flags, rgba_stage ? 2 : 1);
-        ctx->block_encode_job = NULL;
+                         output_bytes, output_used, results, flags, &args);
     }
     free(tex_ptrs);
     return rc;
@@ -1297,17 +1291,18 @@ unsigned hapb_encode_pictures(HapGpuContext *ctx, unsigned frame_count, const vo
                               unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
                               const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
                               void *const *outputs, const unsigned long *output_bytes,
-                              unsigned long *output_used, unsigned *results, unsigned flags, unsigned picture_kind)
+                              unsigned long *output_used, unsigned *results, unsigned flags, unsigned picture_kind,
+                              int defer)
 {
     return encode_pictures(ctx, frame_count, rgba_frames, width, height, row_bytes, count, formats, compressors,
-                           chunk_counts, outputs, output_bytes, output_used, results, flags, picture_kind, NULL);
+                           chunk_counts, outputs, output_bytes, output_used, results, flags, picture_kind, NULL, defer);
 }
 
 unsigned hapb_encode_planes(HapGpuContext *ctx, unsigned frame_count, const void *const *tensors, unsigned width,
                             unsigned height, unsigned long row_bytes, const HapbPlanes *planes, unsigned count,
                             const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
                             void *const *outputs, const unsigned long *output_bytes, unsigned long *output_used,
-                            unsigned *results, unsigned flags)
+                            unsigned *results, unsigned flags, int defer)
 {
     unsigned f;
     if (frame_count == 0)
@@ -1320,7 +1315,7 @@ unsigned hapb_encode_planes(HapGpuContext *ctx, unsigned frame_count, const void
         return HapResult_Bad_Arguments;
     }
     return encode_pictures(ctx, frame_count, tensors, width, height, row_bytes, count, formats, compressors, chunk_counts,
-                           outputs, output_bytes, output_used, results, flags, HAPGPU_PICTURE_RGBA8, planes);
+                           outputs, output_bytes, output_used, results, flags, HAPGPU_PICTURE_RGBA8, planes, defer);
 }
 
 /* One tensor -> one texture: hapb_compress_rgba's output rules, the tensor in device memory */
@@ -1479,9 +1474,10 @@ static void scan_entry(HapGpuScanChunk *e, unsigned unit, unsigned long src_len,
 unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
                      const unsigned long *input_bytes, unsigned index, void *const *outputs,
                      const unsigned long *output_bytes, unsigned long *output_used,
-                     unsigned *output_formats, unsigned *results, unsigned flags,
-                     HapDecodeCallback callback, void *callback_info)
+                     unsigned *output_formats, unsigned *results, unsigned flags, const HapbDecodeArgs *args)
 {
+    static const HapbDecodeArgs no_args;
+    const HapbDecodeArgs *const a = args ? args : &no_args;
     hapgpu_rt *rt = ctx->rt;
     hapf_texture_plan *plans;
     hapf_reader *readers;
@@ -1501,15 +1497,15 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
     uint32_t *dwork = NULL;                                    /* [0]: count, then the fine units the scan listed */
     unsigned far_seen = 0;
     /* (a call for several textures of the same frames: HapGpuDecodeFrameTextures hands the per-entry indices over) */
-    const unsigned *const entry_index = ctx->decode_indices;
+    const unsigned *const entry_index = a->indices;
     /* (a region call: the rectangle the textures are wanted for -- units that hold none of its blocks are blanked on the
        device, hapgpu_k_skip_units; a texture's block size is its format's, known once the frame is planned) */
-    const HapGpuRegion *const region = ctx->decode_region;
+    const HapGpuRegion *const region = a->region;
     /* (... or a rectangle per entry, HapGpuDecodeFramesPlanesRegion: they travel behind the job table, a rectangle per
        job, and the skip looks up the one of a unit's job) */
-    const HapGpuRegion *const entry_regions = ctx->decode_regions;
+    const HapGpuRegion *const entry_regions = a->regions;
     const int skipping = region || entry_regions;
-    const int region_counted = !ctx->decode_region_uncounted;
+    const int region_counted = !a->region_uncounted;
     uint32_t *hblock = NULL, *dblock = NULL;                   /* per job, behind the job tables: the texture's block size */
     HapGpuRegion *hregion = NULL, *dregion = NULL;             /* ... and behind those, per job: its rectangle (entry_regions) */
     const size_t job_bytes = sizeof(HapGpuDecodeJob) + sizeof(uint32_t) + sizeof(HapGpuRegion);
@@ -1535,10 +1531,6 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
 #ifdef HAPB_TRACE
     double hapb_t0 = hapb_now_us();
 #endif
-    ctx->decode_indices = NULL;
-    ctx->decode_region = NULL;
-    ctx->decode_regions = NULL;
-    ctx->decode_region_uncounted = 0;
     if (frame_count == 0)
         return HapResult_No_Error;
     if (!results)
@@ -2066,7 +2058,7 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
 
         /* hap.h callback contract (single-frame HapDecode only): the client is asked to "run" the
            chunks once planning succeeded and there is more than one (reference hap.c:852-862) */
-        if (callback && frame_count == 1 && !rc && results[0] == HapResult_No_Error &&
+        if (a->callback && frame_count == 1 && !rc && results[0] == HapResult_No_Error &&
             plans[0].mode == HAPGPU_JOB_COMPLEX && plans[0].chunk_count > 1) {
             unsigned char *req;
             int c, all = 1;
@@ -2079,10 +2071,10 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
                 } else {
                     marks.count = (unsigned)plans[0].chunk_count;
                     marks.requested = req;
-                    if (ctx->preset_marks && ctx->preset_count == marks.count)
-                        memcpy(req, ctx->preset_marks, marks.count);      /* retry: the client was asked already */
+                    if (a->marks && a->mark_count == marks.count)
+                        memcpy(req, a->marks, marks.count);      /* a second pass: the client was asked already */
                     else
-                        callback(mark_chunk, &marks, marks.count, callback_info);
+                        a->callback(mark_chunk, &marks, marks.count, a->callback_info);
                     free(client_marks);
                     client_marks = (unsigned char *)malloc(marks.count);
                     if (client_marks) {
@@ -2198,24 +2190,18 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
         for (f = 0; f < frame_count; f++) {
             if (results[f] != HAPGPU_STATUS_INDEX_MISMATCH)
                 continue;
+            /* (a region call skips again on this road: whole chunks and raw pieces, all it has without table and scan --
+               no more than the first pass skipped of this frame, and counted there: the frame's own rectangle, uncounted.
+               The client of a single frame has given its marks: they go along, and the callback with them) */
+            const HapbDecodeArgs again = {NULL, region, entry_regions ? &entry_regions[f] : NULL, 1,
+                                          frame_count == 1 ? client_marks : NULL, client_marks_count,
+                                          frame_count == 1 ? a->callback : NULL, a->callback_info};
             results[f] = HapResult_No_Error;
             ctx->table_fallbacks += 1;
-            if (frame_count == 1 && client_marks) {
-                ctx->preset_marks = client_marks;
-                ctx->preset_count = client_marks_count;
-            }
-            /* (a region call skips again on this road: whole chunks and raw pieces, all it has without table and scan --
-               no more than the first pass skipped of this frame, and counted there) */
-            ctx->decode_region = region;
-            ctx->decode_regions = entry_regions ? &entry_regions[f] : NULL;      /* (the frame's own rectangle) */
-            ctx->decode_region_uncounted = 1;
             hapb_decode(ctx, 1, &inputs[f], &input_bytes[f], TEXTURE_INDEX(f), &outputs[f], &output_bytes[f],
                         output_used ? &output_used[f] : NULL, output_formats ? &output_formats[f] : NULL,
                         &results[f], (flags | HAPGPU_DECODE_IGNORE_FRAGMENT_INDEX | HAPGPU_DECODE_NO_BLOCK_SCAN | HAPGPU_DECODE_NO_FIELD_GUESS) &
-                                     ~HAPGPU_DECODE_GUESS_FIELDS,
-                        frame_count == 1 ? callback : NULL, callback_info);
-            ctx->preset_marks = NULL;
-            ctx->preset_count = 0;
+                                     ~HAPGPU_DECODE_GUESS_FIELDS, &again);
         }
     }
 
@@ -2252,29 +2238,124 @@ fail_alloc:
 #define RGBA_SLICE_BYTES ((size_t)4u << 30)     /* block textures held at a time */
 #define PICTURE_KINDS_MAX 4u                    /* texture formats one road decodes */
 
+/* The second stage of a slice of a call's frames into texture scratch, for the roads that go on from block textures
+   (decode_pictures, hapb_transcode).  Entry f * texture_count + t is texture t of the slice's frame f: the colour texture
+   at per_frame * f of the slice's D_BC_TEX scratch, the RGTC1 alpha plane at + alpha_off, both 256-byte aligned. */
+typedef struct slice_textures {
+    unsigned texture_count, width, height;
+    size_t blocks, alpha_off, per_frame;    /* blocks of a texture; the scratch layout */
+    size_t slice;                           /* frames of a slice at most */
+    /* per entry, one allocation (`in` is its start): what hapb_decode is given ... */
+    const void **in;
+    unsigned long *in_bytes, *caps;
+    unsigned *idx;
+    HapGpuRegion *decode_regions;           /* (a call with a rectangle per frame; else NULL) */
+    /* ... and what it gives back: the texture's address, bytes, format and result */
+    void **outs;
+    unsigned long *used;
+    unsigned *fmts, *res;
+} slice_textures;
+
+/* extra_per_frame: what else the caller holds per frame while a slice's textures are held; rectangles != 0: room for a
+   rectangle per entry.  0: out of memory */
+static int slice_textures_init(slice_textures *s, unsigned frame_count, unsigned texture_count, unsigned width,
+                               unsigned height, size_t extra_per_frame, int rectangles)
+{
+    size_t entries;
+    s->texture_count = texture_count;
+    s->width = width;
+    s->height = height;
+    s->blocks = (size_t)(width / 4u) * (height / 4u);
+    s->alpha_off = align_up(s->blocks * 16u, 256);
+    s->per_frame = s->alpha_off + (texture_count == 2 ? align_up(s->blocks * 8u, 256) : 0u);
+    s->slice = RGBA_SLICE_BYTES / (s->per_frame + extra_per_frame);
+    if (s->slice == 0)
+        s->slice = 1;
+    if (s->slice > frame_count)
+        s->slice = frame_count;
+    if (s->slice * texture_count > 32768u)
+        s->slice = 32768u / texture_count;
+    entries = s->slice * texture_count;
+    s->in = (const void **)malloc(entries * (2u * sizeof(void *) + 3u * sizeof(unsigned long) + 3u * sizeof(unsigned) +
+                                             (rectangles ? sizeof(HapGpuRegion) : 0u)));
+    if (!s->in)
+        return 0;
+    s->outs = (void **)(s->in + entries);
+    s->in_bytes = (unsigned long *)(s->outs + entries);
+    s->caps = s->in_bytes + entries;
+    s->used = s->caps + entries;
+    s->idx = (unsigned *)(s->used + entries);
+    s->fmts = s->idx + entries;
+    s->res = s->fmts + entries;
+    s->decode_regions = rectangles ? (HapGpuRegion *)(s->res + entries) : NULL;
+    return 1;
+}
+
+/* Frames done .. done + n of the call (n <= s->slice) into `textures`, per_frame * n bytes of D_BC_TEX scratch.  region
+   (NULL: whole textures): the rectangle wanted of every frame -- or, with xs and ys, its size alone, frame f's origin being
+   (xs[f], ys[f]): a frame whose origin puts the rectangle off the grid or past an edge goes to hapb_decode with a NULL
+   input, its Bad_Arguments, and nothing of it is decoded. */
+static void slice_textures_decode(HapGpuContext *ctx, const slice_textures *s, uint8_t *textures, const void *const *inputs,
+                                  const unsigned long *input_bytes, size_t done, unsigned n, const HapGpuRegion *region,
+                                  const unsigned *xs, const unsigned *ys, unsigned flags)
+{
+    const unsigned width = s->width, height = s->height;
+    const HapGpuRegion whole = {width, 0u, 0u, width, height};
+    HapbDecodeArgs args = {s->idx, NULL, NULL, 0, NULL, 0u, NULL, NULL};
+    unsigned f, t;
+    int any_skip = 0;
+    for (f = 0; f < n; f++) {
+        /* (frame done + f of the call: the origins are the call's, not the slice's) */
+        HapGpuRegion own = whole;
+        int refused = 0;
+        if (xs) {
+            own.x = xs[done + f];
+            own.y = ys[done + f];
+            own.w = region->w;
+            own.h = region->h;
+            refused = !hapb_region_fits(&own, height);
+            if (refused)
+                own = whole;
+            else if (own.x != 0u || own.y != 0u || own.w != width || own.h != height)
+                any_skip = 1;
+        }
+        for (t = 0; t < s->texture_count; t++) {
+            const size_t e = (size_t)f * s->texture_count + t;
+            if (s->decode_regions)
+                s->decode_regions[e] = own;
+            s->in[e] = refused ? NULL : inputs[done + f];
+            s->in_bytes[e] = input_bytes[done + f];
+            s->outs[e] = textures + s->per_frame * f + (t ? s->alpha_off : 0u);
+            s->caps[e] = (unsigned long)(t ? s->blocks * 8u : s->blocks * 16u);
+            s->idx[e] = t;
+            s->used[e] = 0;
+            s->fmts[e] = 0;
+        }
+    }
+    /* (rectangles that are all the whole frame skip nothing -- one that is among others needs everything -- and nor does
+       one rectangle for all that is the whole frame) */
+    if (xs)
+        args.regions = any_skip ? s->decode_regions : NULL;
+    else if (region && !(region->x == 0u && region->y == 0u && region->w == width && region->h == height))
+        args.region = region;
+    hapb_decode(ctx, n * s->texture_count, s->in, s->in_bytes, 0, s->outs, s->caps, s->used, s->fmts, s->res,
+                flags & ~HAPGPU_DECODE_BPTC_PICTURES, &args);
+}
+
 static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
                                 const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
                                 unsigned width, unsigned height, unsigned long row_bytes, unsigned *results,
                                 unsigned flags, const picture_road *road)
 {
     hapgpu_rt *rt = ctx->rt;
-    size_t blocks, per_frame, alpha_off, rgba_bytes, slice, done;
+    size_t rgba_bytes, done;
     unsigned first_error = HapResult_No_Error, f;
-    const void **in;
-    unsigned long *in_bytes, *caps, *used;
-    void **outs;
-    unsigned *idx, *fmts, *res;
+    slice_textures s;
     /* (the pictures' geometry: the frames', a scaled road's fraction of it, or the rectangle's) */
     const unsigned picture_height = picture_height_of(road, height);
     const size_t pixel_row = (size_t)picture_width_of(road, width) * picture_texel_bytes(road);
-    /* (a rectangle that is the whole frame skips nothing) */
-    const HapGpuRegion *const skip_region = road->region && !(road->region->x == 0u && road->region->y == 0u &&
-                                                              road->region->w == width && road->region->h == height)
-                                                ? road->region : NULL;
     const unsigned align = picture_align_mask(road);
-    /* (a rectangle per frame: the entries' rectangles for hapb_decode, a slice's at a time) */
     const int per_frame_regions = road->region_xs != NULL;
-    HapGpuRegion *regs = NULL;
     if (frame_count == 0)
         return HapResult_No_Error;
     if (!results)
@@ -2293,83 +2374,26 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
     /* (a measuring road: a frame that is not measured has an all-zero struct) */
     if (road->measure)
         memset(road->measure, 0, sizeof(*road->measure) * frame_count);
-    blocks = (size_t)(width / 4u) * (height / 4u);
-    alpha_off = align_up(blocks * 16u, 256);
-    per_frame = alpha_off + (texture_count == 2 ? align_up(blocks * 8u, 256) : 0u);
     rgba_bytes = (size_t)row_bytes * (picture_height - 1u) + pixel_row;
-    slice = RGBA_SLICE_BYTES / per_frame;
-    if (slice == 0)
-        slice = 1;
-    if (slice > frame_count)
-        slice = frame_count;
-    if (slice * texture_count > 32768u)
-        slice = 32768u / texture_count;
-    in = (const void **)malloc(sizeof(*in) * slice * texture_count);
-    in_bytes = (unsigned long *)malloc(sizeof(*in_bytes) * slice * texture_count * 3u);
-    outs = (void **)malloc(sizeof(*outs) * slice * texture_count);
-    idx = (unsigned *)malloc(sizeof(*idx) * slice * texture_count * 3u);
-    if (per_frame_regions)
-        regs = (HapGpuRegion *)malloc(sizeof(*regs) * slice * texture_count);
-    if (!in || !in_bytes || !outs || !idx || (per_frame_regions && !regs)) {
-        free(in); free(in_bytes); free(outs); free(idx); free(regs);
+    if (!slice_textures_init(&s, frame_count, texture_count, width, height, 0u, per_frame_regions)) {
         for (f = 0; f < frame_count; f++)
             results[f] = HapResult_Internal_Error;
         return HapResult_Internal_Error;
     }
-    caps = in_bytes + slice * texture_count;
-    used = caps + slice * texture_count;
-    fmts = idx + slice * texture_count;
-    res = fmts + slice * texture_count;
-    for (done = 0; done < frame_count; done += slice) {
-        const unsigned n = (unsigned)(frame_count - done < slice ? frame_count - done : slice);
-        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, per_frame * n);
+    for (done = 0; done < frame_count; done += s.slice) {
+        const unsigned n = (unsigned)(frame_count - done < s.slice ? frame_count - done : s.slice);
+        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, s.per_frame * n);
         uint8_t *stage = NULL;
         const unsigned long long *htotals_of_slice = NULL;
-        unsigned t;
-        int rc = 0, any_skip = 0;
+        int rc = 0;
         if (!textures) {
             for (f = 0; f < n; f++)
                 results[done + f] = HapResult_Internal_Error;
             first_error = first_error ? first_error : HapResult_Internal_Error;
             continue;
         }
-        for (f = 0; f < n; f++) {
-            /* (frame done + f of the call: the rectangle arrays are the call's, not the slice's) */
-            const HapGpuRegion whole = {width, 0u, 0u, width, height};
-            HapGpuRegion own = whole;
-            int refused = 0;
-            if (per_frame_regions) {
-                own.x = road->region_xs[done + f];
-                own.y = road->region_ys[done + f];
-                own.w = road->region->w;
-                own.h = road->region->h;
-                /* a frame whose origin puts the rectangle off the grid or past an edge: Bad_Arguments alone, and nothing
-                   of it goes to the second stage or the block decoder -- a NULL input is hapb_decode's Bad_Arguments */
-                refused = !hapb_region_fits(&own, height);
-                if (refused)
-                    own = whole;
-                else if (own.x != 0u || own.y != 0u || own.w != width || own.h != height)
-                    any_skip = 1;
-            }
-            for (t = 0; t < texture_count; t++) {
-                const size_t e = (size_t)f * texture_count + t;
-                if (regs)
-                    regs[e] = own;
-                in[e] = refused ? NULL : inputs[done + f];
-                in_bytes[e] = input_bytes[done + f];
-                outs[e] = textures + per_frame * f + (t ? alpha_off : 0u);
-                caps[e] = (unsigned long)(t ? blocks * 8u : blocks * 16u);
-                idx[e] = t;
-                used[e] = 0;
-                fmts[e] = 0;
-            }
-        }
-        ctx->decode_indices = idx;
-        ctx->decode_region = per_frame_regions ? NULL : skip_region;
-        /* (rectangles that are all the whole frame skip nothing; one that is among others needs everything) */
-        ctx->decode_regions = any_skip ? regs : NULL;
-        hapb_decode(ctx, n * texture_count, in, in_bytes, 0, outs, caps, used, fmts, res, flags & ~HAPGPU_DECODE_BPTC_PICTURES,
-                    NULL, NULL);
+        slice_textures_decode(ctx, &s, textures, inputs, input_bytes, done, n, road->region, road->region_xs, road->region_ys,
+                              flags);
         {
             /* one block-decode launch per texture format present in the slice: [textures][alpha planes][pictures] in a
                small device table, pictures of other formats (or that failed) with a texture address of 0 */
@@ -2396,15 +2420,15 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
             memset(htab, 0, tab_bytes);
             for (f = 0; f < n; f++) {
                 const size_t e = (size_t)f * texture_count;
-                const unsigned fmt = fmts[e];
+                const unsigned fmt = s.fmts[e];
                 void *dst = rgba_frames[done + f];
-                unsigned r = res[e];
+                unsigned r = s.res[e];
                 for (k = 0; k < road->kind_count && road->kinds[k] != fmt; k++)
                     ;
                 if (r == HapResult_No_Error && texture_count == 2)
-                    r = res[e + 1];
+                    r = s.res[e + 1];
                 /* (no Hap variant pairs a BC7 texture with a second one) */
-                if (texture_count == 2 && res[e] == HapResult_No_Error && k < road->kind_count && !(road->paired_kinds >> k & 1u))
+                if (texture_count == 2 && s.res[e] == HapResult_No_Error && k < road->kind_count && !(road->paired_kinds >> k & 1u))
                     r = HapResult_Bad_Arguments;
                 if (r == HapResult_No_Error && !dst)
                     r = HapResult_Bad_Arguments;
@@ -2413,8 +2437,8 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
                    same geometry */
                 if (r == HapResult_No_Error &&
                     (k == road->kind_count ||
-                     used[e] != blocks * hapf_block_bytes(fmt) ||
-                     (texture_count == 2 && (fmts[e + 1] != HapTextureFormat_A_RGTC1 || used[e + 1] != blocks * 8u))))
+                     s.used[e] != s.blocks * hapf_block_bytes(fmt) ||
+                     (texture_count == 2 && (s.fmts[e + 1] != HapTextureFormat_A_RGTC1 || s.used[e + 1] != s.blocks * 8u))))
                     r = HapResult_Bad_Arguments;
                 if (r == HapResult_No_Error && (road->planes || road->measure) && !is_dev(ctx, dst)) {
                     r = HapResult_Bad_Arguments;        /* tensors and reference pictures live in device memory: no host staging road */
@@ -2431,8 +2455,8 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
                     present |= 1u << k;
                     if ((uintptr_t)dst & 15u)
                         wide = 0;
-                    htab[(size_t)k * 3u * n + f] = (uint64_t)(uintptr_t)outs[e];
-                    htab[(size_t)k * 3u * n + n + f] = texture_count == 2 ? (uint64_t)(uintptr_t)outs[e + 1] : 0u;
+                    htab[(size_t)k * 3u * n + f] = (uint64_t)(uintptr_t)s.outs[e];
+                    htab[(size_t)k * 3u * n + n + f] = texture_count == 2 ? (uint64_t)(uintptr_t)s.outs[e + 1] : 0u;
                     htab[(size_t)k * 3u * n + 2u * n + f] = (uint64_t)(uintptr_t)dst;
                     if (horigins)       /* (inside the frame: a refused origin never gets here) */
                         horigins[f] = region_first_block(width, road->region_xs[done + f], road->region_ys[done + f]);
@@ -2478,7 +2502,7 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
             if (results[done + f] != HapResult_No_Error && first_error == HapResult_No_Error)
                 first_error = results[done + f];
     }
-    free(in); free(in_bytes); free(outs); free(idx); free(regs);
+    free(s.in);
     return first_error;
 }
 
@@ -2601,13 +2625,13 @@ unsigned hapb_transcode(HapGpuContext *ctx, unsigned frame_count, const void *co
     hapgpu_rt *rt = ctx->rt;
     /* the three source formats of the kernel, each with or without an alpha plane: the picture road's without BC7 */
     const picture_road road = road_of(HAPGPU_PICTURE_RGBA8, 0u, 0u, NULL);
-    size_t blocks, per_frame, alpha_off, out_per_frame = 0, out_off[2] = {0, 0}, slice, done;
+    const HapbEncodeArgs device_textures = {1, NULL, 0, 0};
+    size_t out_per_frame = 0, out_off[2] = {0, 0}, done;
     unsigned long out_bytes[2] = {0, 0};
     unsigned first_error = HapResult_No_Error, f, i, set;
-    const void **in, **tex;
-    unsigned long *in_bytes, *caps, *used;
-    void **outs;
-    unsigned *idx, *fmts, *res;
+    slice_textures s;
+    const void **tex;       /* per frame and destination texture: what the encode half reads */
+    unsigned *decoded;      /* per frame: what its decode half came to */
     if (frame_count == 0)
         return HapResult_No_Error;
     if (!results)
@@ -2636,93 +2660,66 @@ unsigned hapb_transcode(HapGpuContext *ctx, unsigned frame_count, const void *co
         transcode_refuse(results, frame_count, HapResult_Bad_Arguments);
         return HapResult_Bad_Arguments;
     }
-    blocks = (size_t)(width / 4u) * (height / 4u);
-    alpha_off = align_up(blocks * 16u, 256);
-    per_frame = alpha_off + (texture_count == 2 ? align_up(blocks * 8u, 256) : 0u);
-    slice = RGBA_SLICE_BYTES / (per_frame + out_per_frame);
-    if (slice == 0)
-        slice = 1;
-    if (slice > frame_count)
-        slice = frame_count;
-    if (slice * texture_count > 32768u)
-        slice = 32768u / texture_count;
-    in = (const void **)malloc(sizeof(*in) * slice * texture_count);
-    in_bytes = (unsigned long *)malloc(sizeof(*in_bytes) * slice * texture_count * 3u);
-    outs = (void **)malloc(sizeof(*outs) * slice * texture_count);
-    idx = (unsigned *)malloc(sizeof(*idx) * slice * (texture_count * 3u + 1u));
-    tex = (const void **)malloc(sizeof(*tex) * slice * count);
-    if (!in || !in_bytes || !outs || !idx || !tex) {
-        free(in); free(in_bytes); free(outs); free(idx); free(tex);
+    if (!slice_textures_init(&s, frame_count, texture_count, width, height, out_per_frame, 0)) {
         transcode_refuse(results, frame_count, HapResult_Internal_Error);
         return HapResult_Internal_Error;
     }
-    caps = in_bytes + slice * texture_count;
-    used = caps + slice * texture_count;
-    fmts = idx + slice * texture_count;
-    res = fmts + slice * texture_count;
-    for (done = 0; done < frame_count; done += slice) {
-        const unsigned n = (unsigned)(frame_count - done < slice ? frame_count - done : slice);
-        unsigned *const decoded = res + (size_t)n * texture_count;      /* per frame: what its decode half came to */
-        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, per_frame * n);
+    tex = (const void **)malloc((sizeof(*tex) * count + sizeof(*decoded)) * s.slice);
+    if (!tex) {
+        free(s.in);
+        transcode_refuse(results, frame_count, HapResult_Internal_Error);
+        return HapResult_Internal_Error;
+    }
+    decoded = (unsigned *)(tex + s.slice * count);
+    for (done = 0; done < frame_count; done += s.slice) {
+        const unsigned n = (unsigned)(frame_count - done < s.slice ? frame_count - done : s.slice);
+        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, s.per_frame * n);
         uint8_t *transcoded = set ? (uint8_t *)hapgpu_rt_device_scratch(rt, D_TRANSCODED, out_per_frame * n) : NULL;
         /* [source textures][source planes][destination textures][destination planes] per source format */
         const size_t tab_bytes = sizeof(uint64_t) * 4u * PICTURE_KINDS_MAX * n;
         uint64_t *htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, tab_bytes);
         uint64_t *dtab = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, tab_bytes);
-        unsigned present = 0, k, t;
+        unsigned present = 0, k;
         int rc = 0;
         if (!textures || (set && !transcoded) || !htab || !dtab) {
             transcode_refuse(results + done, n, HapResult_Internal_Error);
             first_error = first_error ? first_error : HapResult_Internal_Error;
             continue;
         }
-        for (f = 0; f < n; f++)
-            for (t = 0; t < texture_count; t++) {
-                const size_t e = (size_t)f * texture_count + t;
-                in[e] = inputs[done + f];
-                in_bytes[e] = input_bytes[done + f];
-                outs[e] = textures + per_frame * f + (t ? alpha_off : 0u);
-                caps[e] = (unsigned long)(t ? blocks * 8u : blocks * 16u);
-                idx[e] = t;
-                used[e] = 0;
-                fmts[e] = 0;
-            }
-        ctx->decode_indices = idx;
-        hapb_decode(ctx, n * texture_count, in, in_bytes, 0, outs, caps, used, fmts, res, decode_flags & ~HAPGPU_DECODE_BPTC_PICTURES,
-                    NULL, NULL);
+        slice_textures_decode(ctx, &s, textures, inputs, input_bytes, done, n, NULL, NULL, NULL, decode_flags);
         memset(htab, 0, tab_bytes);
         for (f = 0; f < n; f++) {
             const size_t e = (size_t)f * texture_count;
-            const unsigned fmt = fmts[e];
-            unsigned r = res[e];
+            const unsigned fmt = s.fmts[e];
+            unsigned r = s.res[e];
             int pass = 0;
             k = road.kind_count;
             if (r == HapResult_No_Error && texture_count == 2)
-                r = res[e + 1];
+                r = s.res[e + 1];
             if (r == HapResult_No_Error) {
                 /* the frame's own formats are the wanted ones, at its own size: its textures go on as they are */
                 pass = scale_log2 == 0u && texture_count == count;
                 for (i = 0; pass && i < count; i++)
-                    if (fmts[e + i] != formats[i] || used[e + i] != out_bytes[i])
+                    if (s.fmts[e + i] != formats[i] || s.used[e + i] != out_bytes[i])
                         pass = 0;
                 for (k = 0; k < road.kind_count && road.kinds[k] != fmt; k++)
                     ;
                 /* else it must hold what the caller's geometry says, as for decode_pictures: a colour texture the
                    kernel reads, of exactly width x height, and (two textures) an RGTC1 plane of the same geometry */
-                if (!pass && (!set || k == road.kind_count || used[e] != blocks * hapf_block_bytes(fmt) ||
-                              (texture_count == 2 && (fmts[e + 1] != HapTextureFormat_A_RGTC1 || used[e + 1] != blocks * 8u))))
+                if (!pass && (!set || k == road.kind_count || s.used[e] != s.blocks * hapf_block_bytes(fmt) ||
+                              (texture_count == 2 && (s.fmts[e + 1] != HapTextureFormat_A_RGTC1 || s.used[e + 1] != s.blocks * 8u))))
                     r = HapResult_Bad_Arguments;
             }
             decoded[f] = r;
             for (i = 0; i < count; i++)
                 tex[(size_t)f * count + i] = r != HapResult_No_Error ? NULL :
-                                             pass ? outs[e + i] : (const void *)(transcoded + out_per_frame * f + out_off[i]);
+                                             pass ? s.outs[e + i] : (const void *)(transcoded + out_per_frame * f + out_off[i]);
             /* (a frame whose output hapb_encode will refuse is not worth the kernel's time either) */
             if (r == HapResult_No_Error && !pass && outputs[done + f] && output_bytes[done + f]) {
                 uint64_t *col = htab + (size_t)k * 4u * n;
                 present |= 1u << k;
-                col[f] = (uint64_t)(uintptr_t)outs[e];
-                col[n + f] = texture_count == 2 ? (uint64_t)(uintptr_t)outs[e + 1] : 0u;
+                col[f] = (uint64_t)(uintptr_t)s.outs[e];
+                col[n + f] = texture_count == 2 ? (uint64_t)(uintptr_t)s.outs[e + 1] : 0u;
                 col[2u * n + f] = (uint64_t)(uintptr_t)tex[(size_t)f * count];
                 col[3u * n + f] = count == 2 ? (uint64_t)(uintptr_t)tex[(size_t)f * count + 1] : 0u;
             }
@@ -2741,7 +2738,7 @@ unsigned hapb_transcode(HapGpuContext *ctx, unsigned frame_count, const void *co
             memset(tex, 0, sizeof(*tex) * (size_t)n * count);
         /* the encode half on the same stream, behind the kernel; it ends with the slice's second and last wait */
         hapb_encode(ctx, n, count, tex, out_bytes, formats, compressors, chunk_counts, outputs + done, output_bytes + done,
-                    output_used + done, results + done, encode_flags, 1);
+                    output_used + done, results + done, encode_flags, &device_textures);
         for (f = 0; f < n; f++) {
             if (decoded[f] != HapResult_No_Error)
                 results[done + f] = decoded[f];
@@ -2751,7 +2748,7 @@ unsigned hapb_transcode(HapGpuContext *ctx, unsigned frame_count, const void *co
                 first_error = results[done + f];
         }
     }
-    free(in); free(in_bytes); free(outs); free(idx); free(tex);
+    free(s.in); free(tex);
     return first_error;
 }
 

@@ -24,35 +24,17 @@ struct HapGpuContext {
                                     0.545 against 0.559 ms per step of 8 8K frames) */
     unsigned placing_holdoff; /* calls left that gather although they could place: the last placing call encoded most frames twice */
     unsigned placing_holdoff_calls; /* HAP_AMD_PLACING_HOLDOFF (default 8): how many */
-    unsigned no_placing;      /* HAP_AMD_NO_PLACING: compressed fragments go to slots and are gathered (A/B runs; also set
-                                 while a frame whose chunks did not all shrink is encoded again) */
+    unsigned no_placing;      /* HAP_AMD_NO_PLACING: compressed fragments go to slots and are gathered (A/B runs); a single
+                                 call asks for the same with HapbEncodeArgs.never_place */
     unsigned no_wide_planes;  /* HAP_AMD_NO_WIDE_PLANES: A8 pictures take the one-block-per-lane road of alpha_plane.hip even
                                  where they are 16-byte aligned (A/B runs) */
     unsigned no_half_tiles;   /* HAP_AMD_NO_HALF_TILES: fragment table version 1 even for field streams (A/B runs) */
-    /* chunk marks collected from the client's HapDecodeCallback, handed to the retry of a frame whose fragment
-       table turned out wrong: the callback is invoked exactly once per HapDecode, as in the reference */
     unsigned long placement_retries; /* frames encoded a second time, through slots (a chunk of theirs was stored raw) */
     unsigned long placement_timeouts; /* ... of which: a wavefront waited for its predecessors' sizes longer than the bound */
     unsigned placing_off;     /* after such a timeout: encode calls left that gather before placing is tried again */
     unsigned long table_fallbacks;   /* frames decoded again without their fragment table (it did not match) */
-    const unsigned char *preset_marks;
-    unsigned preset_count;
-    /* block encode of a batch, handed from hapb_encode_rgba to hapb_encode so that the whole call is one launch
-       sequence (recorded and replayed as one HIP graph) */
-    const struct HapbBlockEncodeJob *block_encode_job;
-    /* texture index of every entry of the next hapb_decode call (NULL: its `index` argument for all) */
-    const unsigned *decode_indices;
-    /* the rectangle the next hapb_decode call's textures are wanted for (NULL: all of them): units that hold none of
-       its blocks stay undecoded.  Per call, like decode_indices. */
-    const HapGpuRegion *decode_region;
-    /* ... or a rectangle per entry of that call (NULL: decode_region for all): an entry that skips nothing carries the
-       whole of its texture.  Per call, like decode_indices. */
-    const HapGpuRegion *decode_regions;
-    int decode_region_uncounted;     /* ... and 1 where that call is a frame's second pass, whose first pass has counted
-                                        what it skipped (HapGpuSkippedTextureBytes counts a frame once) */
     /* HapGpuEncodeFramesRGBABegin / HapGpuEncodeFramesFinish: the launched half of an encode call whose results have
        not been asked for yet; while there is one the context takes no other call */
-    unsigned defer_encode;
     struct HapbEncodePending *pending_encode;
 };
 
@@ -107,13 +89,22 @@ unsigned hapb_encode_complete(HapGpuContext *ctx, HapbEncodePending *pending);
 /* ... or lets go of it without touching the client's arrays (the context is being destroyed): waits for the launches, frees `pending` */
 void hapb_encode_abandon(HapGpuContext *ctx, HapbEncodePending *pending);
 
-/* inputs_are_device != 0: every input pointer is known to be device memory (skips classification) */
+/* What one hapb_encode call is told beyond its frames.  NULL stands for all zero: textures that may lie anywhere, made by
+   the client, results before the call returns, placing where the context and the geometry allow it. */
+typedef struct HapbEncodeArgs {
+    int inputs_are_device;          /* != 0: every input pointer is known to be device memory (skips classification); 2: and
+                                       pictures were staged for them, so the launches are not recorded as a graph */
+    const HapbBlockEncodeJob *job;  /* the block encode that makes the textures, issued at the head of the call's launches:
+                                       the whole call is one launch sequence (recorded and replayed as one HIP graph) */
+    int defer;                      /* 1: return once everything is launched and leave the rest in ctx->pending_encode */
+    int never_place;                /* 1: fragments go to slots and are gathered, as with ctx->no_placing */
+} HapbEncodeArgs;
 unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                      const void *const *inputs, const unsigned long *input_bytes,
                      const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
                      void *const *outputs, const unsigned long *output_bytes,
                      unsigned long *output_used, unsigned *results, unsigned flags,
-                     int inputs_are_device);
+                     const HapbEncodeArgs *args);
 /* one picture -> one texture.  picture_kind (HAPGPU_PICTURE_*): RGBA8 and the DXT / RGTC1 formats (BC7 with
    HAPGPU_ENCODE_BPTC_BLOCKS), RGBA16F and a BC6H format, or A8 and A_RGTC1 (hapb_encode_pictures' rules) */
 unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width, unsigned height,
@@ -159,13 +150,14 @@ unsigned hapb_measure_texture(HapGpuContext *ctx, const void *texture, unsigned 
 int hapb_region_fits(const HapGpuRegion *region, unsigned height);
 /* pictures -> frames.  picture_kind RGBA8: the DXT / RGTC1 formats (BC7 with HAPGPU_ENCODE_BPTC_BLOCKS); RGBA16F (rows
    and device addresses 16-byte aligned): one BC6H texture; A8 (rows and device addresses 4-byte aligned): one RGTC1
-   texture */
+   texture.  defer: HapbEncodeArgs.defer of the call's hapb_encode */
 unsigned hapb_encode_pictures(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
                               unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
                               const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
                               void *const *outputs, const unsigned long *output_bytes,
-                              unsigned long *output_used, unsigned *results, unsigned flags, unsigned picture_kind);
-/* ... with RGBA8 pictures */
+                              unsigned long *output_used, unsigned *results, unsigned flags, unsigned picture_kind,
+                              int defer);
+/* ... with RGBA8 pictures, and results before it returns */
 unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
                           unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
                           const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
@@ -178,13 +170,27 @@ unsigned hapb_encode_planes(HapGpuContext *ctx, unsigned frame_count, const void
                             unsigned height, unsigned long row_bytes, const HapbPlanes *planes, unsigned count,
                             const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
                             void *const *outputs, const unsigned long *output_bytes, unsigned long *output_used,
-                            unsigned *results, unsigned flags);
-/* callback/callback_info: only honoured for frame_count == 1 (the hap.h HapDecode path) */
+                            unsigned *results, unsigned flags, int defer);
+/* What one hapb_decode call is told beyond its frames.  NULL stands for all zero: texture `index` of every entry, whole
+   textures, nobody to ask which chunks are wanted. */
+typedef struct HapbDecodeArgs {
+    const unsigned *indices;        /* texture index of every entry (NULL: the `index` argument for all) */
+    const HapGpuRegion *region;     /* the rectangle the textures are wanted for (NULL: all of them): units that hold none
+                                       of its blocks stay undecoded */
+    const HapGpuRegion *regions;    /* ... or a rectangle per entry (NULL: `region` for all): an entry that skips nothing
+                                       carries the whole of its texture */
+    int region_uncounted;           /* 1: the call is a frame's second pass, whose first pass has counted what it skipped
+                                       (HapGpuSkippedTextureBytes counts a frame once) */
+    const unsigned char *marks;     /* mark_count chunk marks the client's callback has given for this frame already: a
+                                       second pass uses them, so that the callback runs once per HapDecode */
+    unsigned mark_count;
+    HapDecodeCallback callback;     /* only honoured for frame_count == 1 (the hap.h HapDecode path) */
+    void *callback_info;
+} HapbDecodeArgs;
 unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
                      const unsigned long *input_bytes, unsigned index, void *const *outputs,
                      const unsigned long *output_bytes, unsigned long *output_used,
-                     unsigned *output_formats, unsigned *results, unsigned flags,
-                     HapDecodeCallback callback, void *callback_info);
+                     unsigned *output_formats, unsigned *results, unsigned flags, const HapbDecodeArgs *args);
 
 /* frames -> RGBA8 pictures (texture_count 2: Hap Q Alpha frames, colour + RGTC1 alpha plane); scale_log2 as for
    hapb_decompress_rgba (width and height stay the frames') */

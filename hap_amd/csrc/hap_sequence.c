@@ -377,7 +377,7 @@ unsigned int HapGpuDecodeSequence(HapGpuContext *ctx, HapSequenceReader *r, unsi
         }
         rc = hapb_decode(ctx, n, ptrs, lens, index, outputs + done, output_bytes + done,
                          output_used ? output_used + done : NULL, output_formats ? output_formats + done : NULL,
-                         results + done, 0, NULL, NULL);
+                         results + done, 0, NULL);
         if (rc != HapResult_No_Error && first_error == HapResult_No_Error)
             first_error = rc;
         done += n;

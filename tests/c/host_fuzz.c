@@ -14,10 +14,10 @@
 unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
                      const unsigned long *input_bytes, unsigned index, void *const *outputs,
                      const unsigned long *output_bytes, unsigned long *output_used, unsigned *output_formats,
-                     unsigned *results, unsigned flags, HapDecodeCallback callback, void *callback_info)
+                     unsigned *results, unsigned flags, const HapbDecodeArgs *args)
 {
     (void)ctx; (void)frame_count; (void)inputs; (void)input_bytes; (void)index; (void)outputs; (void)output_bytes;
-    (void)output_used; (void)output_formats; (void)results; (void)flags; (void)callback; (void)callback_info;
+    (void)output_used; (void)output_formats; (void)results; (void)flags; (void)args;
     abort();
 }
 unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,

@@ -1160,6 +1160,26 @@ def test_corrupt_fragment_table_falls_back(ctx, hap):
     frame[pos + 4:pos + 8] = (e1 - 1).to_bytes(4, "little")   # but splits in the wrong place
     assert ORA.decode(bytes(frame), 0, len(tex)) == (0, tex, L.FMT_DXT5)
     assert hap.HapDecode(bytes(frame), 0, outputBufferBytes=len(tex)) == (0, tex, L.FMT_DXT5)
+    # a client that marks some chunks only is asked once, also where the frame is then decoded a second time without
+    # its table, and that second pass decodes what the client marked and nothing else.  The two entries that lie are
+    # chunk 0's: marks that leave chunk 0 out leave them unread, and nothing is decoded again.
+    from hap_amd._lib import CALLBACK, lib
+    q = len(tex) // 4
+    for asked, noticed in (((1, 3), 0), ((0, 2), 1)):
+        calls = []
+
+        def cb(fn, p, count, info):
+            calls.append(count)
+            for c in asked:
+                fn(p, c)
+        n0 = lib.HapGpuTableFallbackCount(lib.HapGpuDefaultContext())
+        part = np.full(len(tex), 0xEE, dtype=np.uint8)
+        r, _used, _fmt = hap.HapDecode(bytes(frame), 0, callback=CALLBACK(cb), outputBuffer=part)
+        assert r == 0 and calls == [4], (asked, r, calls)
+        got = part.tobytes()
+        for c in range(4):
+            assert got[c * q:(c + 1) * q] == (tex[c * q:(c + 1) * q] if c in asked else b"\xEE" * q), (asked, c)
+        assert lib.HapGpuTableFallbackCount(lib.HapGpuDefaultContext()) == n0 + noticed, asked
     # entries that no longer add up to the chunk size (found by tools/fuzz_decode.py: the planner must
     # hand the whole texture back to the generic path, not leave the chunk undecoded)
     for delta in (1, 0x10000, -3):
