@@ -42,7 +42,10 @@ __device__ __forceinline__ unsigned ramp_codes(unsigned w)
     return w ^ (~((w >> 1) | (w >> 2)) & 0x249249u);
 }
 
-// 8-byte alpha-style block: a0, a1, 16 x 3-bit codes (S3TC alpha / RGTC1 layout).
+// 8-byte alpha-style block: a0, a1, 16 x 3-bit codes (S3TC alpha / RGTC1 layout).  a[] holds the values less BIAS (the
+// centred luma of a scaled YCoCg block: BIAS 128): box, range and ramp use only differences, the two end bytes get the
+// BIAS back once per block.
+template <int BIAS = 0>
 __device__ __forceinline__ uint2 alpha_block(const int (&a)[16])
 {
     int lo = a[0], hi = a[0];
@@ -82,7 +85,8 @@ __device__ __forceinline__ uint2 alpha_block(const int (&a)[16])
         hi24 = ramp_codes(hi24 >> 8);
     }
     const unsigned long long bits = (unsigned long long)lo24 | ((unsigned long long)hi24 << 24);
-    const unsigned long long v = (unsigned long long)(unsigned)a0 | ((unsigned long long)(unsigned)a1 << 8) | (bits << 16);
+    // a0 + BIAS | (a1 + BIAS) << 8 as one sum: the two bytes do not meet
+    const unsigned long long v = (unsigned long long)(unsigned)(a0 + (a1 << 8) + BIAS * 257) | (bits << 16);
     return make_uint2((unsigned)v, (unsigned)(v >> 32));
 }
 
@@ -140,25 +144,56 @@ __device__ __forceinline__ projection make_projection(unsigned p0, unsigned p1)
     return pr;
 }
 
-template <bool FLIPPED = false>
-__device__ __forceinline__ unsigned project4(const unsigned (&px)[16], const projection &pr)
+// The clamp the definition states, t to 0 .. top, on four pixels at a time: four dot products, then four v_med3_i32 with
+// a register as the upper bound (the compiler forms v_med3 between constants only).  The three dot products behind a
+// pixel's own are the three wait states gfx950 wants between a dot product and another VALU reader of its result --
+// inside one statement, where the compiler cannot see them, they have to stand there by construction.
+#define HAPBC_CLAMPED_DOTS(OP)                                                                                           \
+    asm(OP " %0, %4, %8, %9\n\t" OP " %1, %5, %8, %9\n\t" OP " %2, %6, %8, %9\n\t" OP " %3, %7, %8, %9\n\t"              \
+        "v_med3_i32 %0, %0, 0, %10\n\tv_med3_i32 %1, %1, 0, %10\n\tv_med3_i32 %2, %2, 0, %10\n\tv_med3_i32 %3, %3, 0, %10" \
+        : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3])                                                             \
+        : "v"(q0), "v"(q1), "v"(q2), "v"(q3), "v"(dir), "v"(start), "v"(top))
+// byte pixels . byte direction + start
+__device__ __forceinline__ void clamped_dot4(unsigned (&t)[4], unsigned q0, unsigned q1, unsigned q2, unsigned q3, unsigned dir, int start, int top)
 {
+    HAPBC_CLAMPED_DOTS("v_dot4_u32_u8");
+}
+// pairs of signed halves . pair of signed halves + start
+__device__ __forceinline__ void clamped_dot2(unsigned (&t)[4], unsigned q0, unsigned q1, unsigned q2, unsigned q3, unsigned dir, int start, int top)
+{
+    HAPBC_CLAMPED_DOTS("v_dot2_i32_i16");
+}
+#undef HAPBC_CLAMPED_DOTS
+
+// sixteen clamped projections -> sixteen 2-bit indices, pixel 0 in bits 1:0.  m24 * 64 moves the position,
+// (t m24) >> 24, to the top two bits of a 32-bit product: top m24 < 3.5 x 2^24, so the product does not wrap, and
+// top m24 >= 3 x 2^24, so a pixel clamped to top has position 3 (tests/test_index_selection_identity.py: every len2).
+// The funnel shift takes the positions in from below, so the pixels are walked from the last to the first.
+template <typename DOTS>
+__device__ __forceinline__ unsigned gather_indices(unsigned m24, DOTS dots)
+{
+    const unsigned m30 = m24 << 6;
     unsigned pos2 = 0;
 #pragma unroll
-    for (int i = 0; i < 16; i++) {
-        const unsigned q = FLIPPED ? px[i] : px[i] ^ pr.flip;
-        // (t is not clamped first: the product stays far inside 32 bits -- pixels lie within a few segment lengths of
-        // p1 -- and clamping the position to 0..3 afterwards gives what the definition's clamp of t gives; the clamp is
-        // left to the compiler's v_med3: an inline-asm reader right behind the dot product would miss its wait states)
-        const int t = (int)__builtin_amdgcn_udot4(q, pr.adir, (unsigned)pr.start, false);
-        const int pos = min(max(__mul24(t, (int)pr.m24) >> 24, 0), 3);
-        // shift the two position bits in from the top: after 16 pixels pixel 0 sits in bits 1:0
-        pos2 = __builtin_amdgcn_alignbit((unsigned)pos, pos2, 2);
+    for (int g = 3; g >= 0; g--) {
+        unsigned t[4];
+        dots(t, 4 * g);
+#pragma unroll
+        for (int k = 3; k >= 0; k--)
+            pos2 = __builtin_amdgcn_alignbit(pos2, t[k] * m30, 30);          // pos2 << 2 | position
     }
     // positions -> indices {1, 3, 2, 0}, all 16 at once: index high bit = pos.hi ^ pos.lo, low bit = ~pos.hi
     const unsigned hi = pos2 & 0xAAAAAAAAu;
-    const unsigned idx = (hi ^ ((pos2 << 1) & 0xAAAAAAAAu)) | ((~hi >> 1) & 0x55555555u);
-    return idx;
+    return (hi ^ ((pos2 << 1) & 0xAAAAAAAAu)) | ((~hi >> 1) & 0x55555555u);
+}
+
+template <bool FLIPPED = false>
+__device__ __forceinline__ unsigned project4(const unsigned (&px)[16], const projection &pr)
+{
+    return gather_indices(pr.m24, [&](unsigned (&t)[4], int i) {
+        clamped_dot4(t, FLIPPED ? px[i] : px[i] ^ pr.flip, FLIPPED ? px[i + 1] : px[i + 1] ^ pr.flip,
+                     FLIPPED ? px[i + 2] : px[i + 2] ^ pr.flip, FLIPPED ? px[i + 3] : px[i + 3] ^ pr.flip, pr.adir, pr.start, pr.top);
+    });
 }
 
 __device__ __forceinline__ unsigned pack3(int a, int b, int c) { return (unsigned)a | ((unsigned)b << 8) | ((unsigned)c << 16); }
@@ -213,35 +248,37 @@ __device__ __forceinline__ uint2 colour_block(const unsigned (&px)[16])
 typedef unsigned short pk_u16 __attribute__((ext_vector_type(2)));
 typedef short pk_i16 __attribute__((ext_vector_type(2)));
 
-// Colour half of a scaled YCoCg-DXT5 block; cc[i] = Co | Cg << 16, both biased by 128 (0..255): the box, the
-// covariance terms and the scaling work on both halves at once (v_pk_min/max_u16, v_pk_mad_i16, v_mad_i32_i16).
+// Colour half of a scaled YCoCg-DXT5 block; cc[i] = Co - 128 | (Cg - 128) << 16, signed halves (-127..128): the box, the
+// covariance terms and the scaling work on both halves at once (v_pk_min/max_i16, v_pk_add, v_mad_i32_i16).
 __device__ __forceinline__ uint2 ycocg_colour_block(const unsigned (&cc)[16])
 {
-    pk_u16 lo = __builtin_bit_cast(pk_u16, cc[0]), hi = lo;
+    pk_i16 lo = __builtin_bit_cast(pk_i16, cc[0]), hi = lo;
 #pragma unroll
     for (int i = 1; i < 16; i++) {
-        const pk_u16 v = __builtin_bit_cast(pk_u16, cc[i]);
+        const pk_i16 v = __builtin_bit_cast(pk_i16, cc[i]);
         lo = __builtin_elementwise_min(lo, v);
         hi = __builtin_elementwise_max(hi, v);
     }
     int lo_o = lo.x, hi_o = hi.x, lo_g = lo.y, hi_g = hi.y;
-    const int m = max(max(128 - lo_o, hi_o - 128), max(128 - lo_g, hi_g - 128));
+    const int m = max(max(-lo_o, hi_o), max(-lo_g, hi_g));
     const int s = m <= 31 ? 4 : (m <= 63 ? 2 : 1);
     // covariance sign: sum (2 Co - mo)(2 Cg - mg) = 4 sum Co Cg - 2 mg sum Co - 2 mo sum Cg + 16 mo mg with mo = lo + hi
-    // of Co, mg of Cg: per pixel one product-accumulate and one packed add
+    // of Co, mg of Cg: per pixel one product-accumulate and one packed add.  (The same number whatever is subtracted
+    // from every Co and every Cg: the centred values stand for the biased ones.)
     int prod = 0;
-    pk_u16 sums = {0, 0};
+    pk_i16 sums = {0, 0};                                                                          // |.| <= 2048
 #pragma unroll
     for (int i = 0; i < 16; i++) {
         int r;
         asm("v_mad_i32_i16 %0, %1, %1, %2 op_sel:[0,1,0,0]" : "=v"(r) : "v"(cc[i]), "v"(prod));   // low half x high half + prod
         prod = r;
-        sums += __builtin_bit_cast(pk_u16, cc[i]);
+        sums += __builtin_bit_cast(pk_i16, cc[i]);
     }
     const int mo = lo_o + hi_o, mg = lo_g + hi_g;
     const int cov = 4 * prod - 2 * mg * (int)sums.x - 2 * mo * (int)sums.y + 16 * mo * mg;
-    lo_o = (lo_o - 128) * s + 128; hi_o = (hi_o - 128) * s + 128;
-    lo_g = (lo_g - 128) * s + 128; hi_g = (hi_g - 128) * s + 128;
+    // the box scaled about the centre and biased: (x - 128) s + 128 from x - 128
+    lo_o = lo_o * s + 128; hi_o = hi_o * s + 128;
+    lo_g = lo_g * s + 128; hi_g = hi_g * s + 128;
     int ins = (hi_o - lo_o) >> 4; lo_o += ins; hi_o -= ins;
     ins = (hi_g - lo_g) >> 4; lo_g += ins; hi_g -= ins;
     const int ag = cov < 0 ? lo_g : hi_g, bg = cov < 0 ? hi_g : lo_g;
@@ -257,9 +294,9 @@ __device__ __forceinline__ uint2 ycocg_colour_block(const unsigned (&cc)[16])
         // complemented channels and make_projection's - 255 (sum of |dir| over those channels) cancel, which leaves
         // K = len2 / 6 + sum over the channels of dir (128 - 128 s - p1).  The end entries are expanded from the
         // quantised channels at hand, in c0 / c1 order, not unpacked from the 5:6:5 words again.
-        // The dot product starts from an offset that keeps it non-negative for the unsigned 24-bit multiply; the
-        // position is (t m24) >> 24 = ((c . dir + offset) (s m24) + (K - s offset) m24) >> 24 in 32-bit wrap-around
-        // arithmetic (t m24 itself fits).
+        // With the centred c' = c - 128 at hand, t = (c' . s dir) + K', K' = len2 / 6 + sum of dir (128 - p1): the scale
+        // rides in the 16-bit direction (|s dir| <= 1020), K' is the dot product's accumulator, and t is the
+        // definition's own, clamped and turned into a position as in project4.
         const bool sw = qa < qb;                                                             // c0 is qb
         const int eo_a = expand5(qo_a), eo_b = expand5(qo_b), eg_a = expand6(qg_a), eg_b = expand6(qg_b);
         const int d_o = sw ? eo_b - eo_a : eo_a - eo_b, d_g = sw ? eg_b - eg_a : eg_a - eg_b;
@@ -267,27 +304,30 @@ __device__ __forceinline__ uint2 ycocg_colour_block(const unsigned (&cc)[16])
         const unsigned len2 = (unsigned)mad24(d_o, d_o, __mul24(d_g, d_g));                  // 16 .. 130050
         const int sixth = (int)(__umulhi(len2, 0xAAAAAAABu) >> 2);
         const unsigned m24 = index_scale(len2);
-        const int centre = 128 - 128 * s;
-        const int K = mad24(d_o, centre - p1_o, mad24(d_g, centre - p1_g, sixth));
-        const pk_i16 dir2 = {(short)d_o, (short)d_g};
-        constexpr int kDotOffset = 1 << 17;                                                  // > 2 x 255 x 255
-        const unsigned sm = (unsigned)s * m24;                                            // < 2^24
-        const unsigned Km = (unsigned)(K - s * kDotOffset) * m24;                         // mod 2^32
-        unsigned pos2 = 0;
-#pragma unroll
-        for (int i = 0; i < 16; i++) {
-            // (the offset from a scalar register: the compiler's choice, v_dot2c, accumulates into its destination and
-            // pays a v_mov of the constant per pixel; the wait states a dot product needs before another VALU
-            // instruction reads its result are part of the statement, the compiler does not see into it)
-            unsigned dot;                                                                                                        // 1 .. 2^18
-            asm("v_dot2_i32_i16 %0, %1, %2, %3\n\ts_nop 2" : "=v"(dot) : "v"(cc[i]), "v"(__builtin_bit_cast(unsigned, dir2)), "s"(kDotOffset));
-            const int pos = min(max((int)(__umul24(dot, sm) + Km) >> 24, 0), 3);
-            pos2 = __builtin_amdgcn_alignbit((unsigned)pos, pos2, 2);
-        }
-        const unsigned hi = pos2 & 0xAAAAAAAAu;
-        idx = (hi ^ ((pos2 << 1) & 0xAAAAAAAAu)) | ((~hi >> 1) & 0x55555555u);
+        const int K = mad24(d_o, 128 - p1_o, mad24(d_g, 128 - p1_g, sixth));
+        const unsigned dir2 = ((unsigned)(d_o * s) & 0xFFFFu) | ((unsigned)(d_g * s) << 16);
+        const int top = (int)len2 + sixth;
+        idx = gather_indices(m24, [&](unsigned (&t)[4], int i) { clamped_dot2(t, cc[i], cc[i + 1], cc[i + 2], cc[i + 3], dir2, K, top); });
     }
     return make_uint2(c0 | (c1 << 16), idx);
+}
+
+// 2 (Co - 128) | 4 (Cg - 128) << 16 of four pixels, signed halves, from the pixels' bytes less 128 (q ^ 0x80808080, signed
+// bytes): R - B + 1 and -R + 2G - B + 2 are SIGNED byte dot products, the 128s cancel since each set of weights sums to
+// zero, and one v_perm_b32 puts the low halves side by side.  In one statement because the compiler makes v_dot4c of
+// the builtin -- it accumulates into its destination and pays a v_mov of the constant per dot product -- and, not
+// seeing into a statement, would not keep a dot product's three wait states in front of the v_perm: here at least
+// three instructions stand between every dot product and the reader of its result.
+__device__ __forceinline__ void chroma4(unsigned (&raw)[4], int q0, int q1, int q2, int q3)
+{
+    unsigned co[4];
+    asm("v_dot4_i32_i8 %4, %8, %12, 1\n\tv_dot4_i32_i8 %0, %8, %13, 2\n\t"
+        "v_dot4_i32_i8 %5, %9, %12, 1\n\tv_dot4_i32_i8 %1, %9, %13, 2\n\t"
+        "v_dot4_i32_i8 %6, %10, %12, 1\n\tv_dot4_i32_i8 %2, %10, %13, 2\n\t"
+        "v_dot4_i32_i8 %7, %11, %12, 1\n\tv_dot4_i32_i8 %3, %11, %13, 2\n\t"
+        "v_perm_b32 %0, %0, %4, %14\n\tv_perm_b32 %1, %1, %5, %14\n\tv_perm_b32 %2, %2, %6, %14\n\tv_perm_b32 %3, %3, %7, %14"
+        : "=&v"(raw[0]), "=&v"(raw[1]), "=&v"(raw[2]), "=&v"(raw[3]), "=&v"(co[0]), "=&v"(co[1]), "=&v"(co[2]), "=&v"(co[3])
+        : "v"(q0), "v"(q1), "v"(q2), "v"(q3), "s"(0x00FF0001), "s"(0x00FF02FF), "s"(0x05040100));
 }
 
 // the 8 or 16 bytes of a block from its sixteen RGBA8 pixels (row-major); 8-byte formats leave z, w zero
@@ -323,16 +363,23 @@ __device__ __forceinline__ uint4 block_of(const unsigned (&p)[16])
         unsigned cc[16];
 #pragma unroll
         for (int i = 0; i < 16; i++) {
-            // Y = (R+2G+B+2)>>2 ; Co = ((R-B+1)>>1)+128 = (R+(255-B)+2)>>1 ; Cg = ((-R+2G-B+2)>>2)+128 =
-            // ((255-R)+2G+(255-B)+4)>>2 -- three byte dot products (alpha weight 0); no clamp (oracle/bc_oracle.c)
-            const unsigned q = p[i];
-            y[i] = (int)(__builtin_amdgcn_udot4(q, 0x00010201u, 2u, false) >> 2);
-            const unsigned co2 = __builtin_amdgcn_udot4(q ^ 0x00FF0000u, 0x00010001u, 2u, false);           // 2 Co: 2..512
-            const unsigned cg4 = __builtin_amdgcn_udot4(q ^ 0x00FF00FFu, 0x00010201u, 4u, false);           // 4 Cg: 4..1024
-            const pk_u16 raw = __builtin_bit_cast(pk_u16, co2 | (cg4 << 16)), sh = {1, 2};
-            cc[i] = __builtin_bit_cast(unsigned, (pk_u16)(raw >> sh));                                       // halve / quarter, both at once: 1 .. 256
+            // Y = (R+2G+B+2)>>2 ; Co = ((R-B+1)>>1)+128 ; Cg = ((-R+2G-B+2)>>2)+128 ; no clamp (oracle/bc_oracle.c).
+            // All three leave here less 128 and nothing downstream subtracts the bias again: Y's dot product starts
+            // at 2 - 512 (wrap-around; a whole multiple of the divisor, so the arithmetic shift gives exactly Y - 128),
+            // the other two are the definitions' own numerators, halved / quartered as a pair of signed halves.
+            y[i] = (int)__builtin_amdgcn_udot4(p[i], 0x00010201u, (unsigned)(2 - 512), false) >> 2;                   // -128 .. 127
         }
-        const uint2 ab = alpha_block(y), cb = ycocg_colour_block(cc);
+#pragma unroll
+        for (int i = 0; i < 16; i += 4) {
+            unsigned raw[4];
+            chroma4(raw, (int)(p[i] ^ 0x80808080u), (int)(p[i + 1] ^ 0x80808080u), (int)(p[i + 2] ^ 0x80808080u), (int)(p[i + 3] ^ 0x80808080u));
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const pk_i16 sh = {1, 2};
+                cc[i + k] = __builtin_bit_cast(unsigned, (pk_i16)(__builtin_bit_cast(pk_i16, raw[k]) >> sh));         // -127 .. 128 each
+            }
+        }
+        const uint2 ab = alpha_block<128>(y), cb = ycocg_colour_block(cc);
         return make_uint4(ab.x, ab.y, cb.x, cb.y);
     }
 }

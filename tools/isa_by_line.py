@@ -43,19 +43,22 @@ def classify(op):
 
 
 # Phases of the fused encode kernel: (name, file, anchor text, n-th occurrence, trips per 8K Hap Q fragment).  A phase
-# runs from its anchor's line to the next anchor of the same file.  Trips: 8 steps of 64 blocks; the choose loop 1.2
+# runs from its anchor's line to the next anchor of the same file.  An anchor with None for its occurrence is one that
+# older trees (--csrc) do not have: first occurrence where present, skipped where not.  Trips: 8 steps of 64 blocks; the choose loop 1.2
 # passes, the element list 9.2 turns and the tag walk 7.4 passes (LABNOTES, 8K stream: 470 elements per fragment).
 CORE, SCB = "bc_encode_core.hpp", "snappy_compress_blocks.hip"
 FUSED_PHASES = [
     ("helpers: mad24 / quant", CORE, "namespace hapbc {", 0, 8.0),
     ("luma ramp", CORE, "__device__ __forceinline__ uint2 alpha_block", 0, 8.0),
     ("end points", CORE, "struct projection {", 0, 8.0),
+    ("colour index", CORE, "// The clamp the definition states, t to 0 .. top", None, 8.0),
     ("colour index (RGB)", CORE, "template <bool FLIPPED = false>", 0, 8.0),
     ("end points", CORE, "__device__ __forceinline__ unsigned pack3", 0, 8.0),
     ("colour box+covariance (RGB)", CORE, "__device__ __forceinline__ uint2 colour_block", 0, 8.0),
     ("colour box+covariance", CORE, "__device__ __forceinline__ uint2 ycocg_colour_block", 0, 8.0),
     ("end points", CORE, "const int mo = lo_o + hi_o", 0, 8.0),
-    ("colour index", CORE, "constexpr int kDotOffset", 0, 8.0),
+    ("colour index", CORE, "const int K = mad24(d_o", 0, 8.0),
+    ("YCoCg transform", CORE, "// 2 (Co - 128) | 4 (Cg - 128) << 16 of four pixels", None, 8.0),
     ("YCoCg transform", CORE, "template <int FMT>", 0, 8.0),
     ("loop+address overhead", SCB, "#include <hip/hip_runtime.h>", 0, 1.0),
     ("choose", SCB, "__device__ __forceinline__ int scan_add", 0, 1.0),
@@ -90,6 +93,10 @@ def phase_spans(csrc):
             if f != fname:
                 continue
             hits = [i + 1 for i, l in enumerate(lines) if anchor in l]
+            if nth is None:
+                if not hits:
+                    continue
+                nth = 0
             if len(hits) <= nth:
                 raise SystemExit("isa_by_line: anchor %r not found in %s" % (anchor, fname))
             marks.append((hits[nth], name, trips))
