@@ -93,6 +93,8 @@ def _load():
                                                P(C.c_float), P(C.c_float), P(u), u]),
         "HapGpuMeasureTexture": (u, [vp, vp, ul, u, vp, ul, u, u, vp, ul, P(HapGpuPictureError)]),
         "HapGpuMeasureFrames": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, ul, P(HapGpuPictureError), P(u), u]),
+        "HapGpuCompositeTextures": (u, [vp, u, P(vp), P(ul), P(u), P(vp), P(ul), P(C.c_ubyte), P(C.c_ubyte), u, u, vp, ul]),
+        "HapGpuCompositeFrames": (u, [vp, u, u, P(vp), P(ul), P(u), P(C.c_ubyte), P(C.c_ubyte), P(vp), u, u, ul, P(u), u]),
         "HapGpuTranscodeTexture": (u, [vp, vp, ul, u, vp, ul, u, u, u, u, P(u), P(vp), P(ul), P(ul)]),
         "HapGpuTranscodeFrames": (u, [vp, u, P(vp), P(ul), u, u, u, u, u, P(u), P(u), P(u), P(vp), P(ul), P(ul), P(u), u, u]),
         "HapGpuDecodeFramesRGBAHalf": (u, [vp, u, P(vp), P(ul), P(vp), u, u, ul, P(u), u]),

@@ -37,6 +37,7 @@ DECODE_NO_BLOCK_SCAN = 0x4
 DECODE_NO_FIELD_GUESS = 0x8
 DECODE_GUESS_FIELDS = 0x10
 DECODE_BPTC_PICTURES = 0x20
+COMPOSITE_MAX_LAYERS = 16          # HAPGPU_COMPOSITE_MAX_LAYERS
 KERNEL_CLASSES = ["block_encode", "snappy_compress", "frame_pack", "frame_gather", "decode_plan", "snappy_decode",
                   "block_decode", "block_scan", "encode_fused"]
 
@@ -790,6 +791,62 @@ class Context:
         r = lib.HapGpuDecodeFramesRGBA(self.handle, nf, ptrs, lens, texture_count, optrs, width, height,
                                        row_bytes or width * 4, results, flags)
         return r, list(results)
+
+    def composite_textures(self, layers, width, height, opacities=None, background=None, rgba=None, row_bytes=None):
+        """Layers of textures "over" a background colour -> one RGBA8 picture (HapGpuCompositeTextures).  layers: a list,
+        bottom to top, of (texture, format, alpha plane or None); opacities: a byte per layer (None: all 255); background:
+        (R, G, B, A) bytes (None: 0, 0, 0, 255).  Per texel, with the layer's decompress_rgba bytes (Rs, Gs, Bs, As):
+        a = rdiv255(As * o), Cd = rdiv255(Cs * a + Cd * (255 - a)), Ad = a + rdiv255(Ad * (255 - a)), in integers.
+        Returns (result, bytes | None), or (result, None) into `rgba`."""
+        n = len(layers)
+        infos = [_addr_len(t) for t, _f, _a in layers]
+        ainfos = [_addr_len(a) for _t, _f, a in layers]
+        ptrs = (C.c_void_p * n)(*[i[0] for i in infos])
+        lens = (C.c_ulong * n)(*[i[1] for i in infos])
+        fmts = (C.c_uint * n)(*[f for _t, f, _a in layers])
+        aptrs = (C.c_void_p * n)(*[i[0] for i in ainfos])
+        alens = (C.c_ulong * n)(*[i[1] for i in ainfos])
+        ops = (C.c_ubyte * n)(*opacities) if opacities is not None else None
+        bg = (C.c_ubyte * 4)(*background) if background is not None else None
+        row_bytes = row_bytes or width * 4
+        own = rgba is None
+        if own:
+            rgba = (C.c_ubyte * (row_bytes * height + 16))()
+            base = C.addressof(rgba)
+            oa = base + (-base) % 16
+        else:
+            oa, _on, _k = _addr_len(rgba)
+        r = lib.HapGpuCompositeTextures(self.handle, n, ptrs, lens, fmts, aptrs, alens, ops, bg, width, height, oa, row_bytes)
+        if own:
+            return r, (C.string_at(oa, row_bytes * height) if r == 0 else None)
+        return r, None
+
+    def composite_frames(self, frames, frame_bytes, texture_counts, rgba_frames, width, height, opacities=None,
+                         background=None, row_bytes=None, flags=0):
+        """Layers of Hap frames "over" a background colour -> one RGBA8 picture per output frame in one call
+        (HapGpuCompositeFrames).  frames: a list (output frames) of lists (layers, bottom to top) of buffers; frame_bytes
+        likewise (None entries, or None for all: the buffers' sizes); texture_counts: 1 or 2 per layer (None: all 1);
+        opacities: a list per output frame of a byte per layer (None: all 255); background: (R, G, B, A) (None:
+        0, 0, 0, 255).  The definition is composite_textures' with decode_frames_rgba's bytes.
+        Returns (result, results[]): one entry per output frame and layer, entry f * layers + l."""
+        nf = len(frames)
+        nl = len(frames[0]) if nf else 0
+        if len(rgba_frames) != nf:
+            raise ValueError("one picture per output frame")
+        if any(len(fr) != nl for fr in frames):
+            raise ValueError("every output frame has the same number of layers")
+        flat = [b for fr in frames for b in fr]
+        ptrs, infos = self._ptr_array(flat)
+        given = [None] * len(flat) if frame_bytes is None else [b for fr in frame_bytes for b in fr]
+        lens = (C.c_ulong * len(flat))(*[fb if fb is not None else infos[i][1] for i, fb in enumerate(given)])
+        counts = (C.c_uint * nl)(*texture_counts) if texture_counts is not None else None
+        ops = (C.c_ubyte * len(flat))(*[o for fr in opacities for o in fr]) if opacities is not None else None
+        bg = (C.c_ubyte * 4)(*background) if background is not None else None
+        optrs, _oinfos = self._ptr_array(rgba_frames)
+        results = (C.c_uint * max(1, len(flat)))()
+        r = lib.HapGpuCompositeFrames(self.handle, nf, nl, ptrs, lens, counts, ops, bg, optrs, width, height,
+                                      row_bytes or width * 4, results, flags)
+        return r, list(results)[: len(flat)]
 
     def measure_frames(self, frames, frame_bytes, texture_count, pictures, width, height, row_bytes=None, flags=0):
         """Frames against their RGBA8 reference pictures in device memory (tensors or addresses; None: no picture for that

@@ -1,0 +1,174 @@
+// bc_composite.hip -- layers of DXT1 / DXT5 / scaled YCoCg-DXT5 (+ RGTC1 alpha plane) textures composited "over" a
+// background colour to one RGBA8 picture per output frame, for gfx950, without the layers' decoded pictures in between.
+//
+// The decoder's body (bc_decode_texels.hpp, IN_REGISTERS) leaves a block's sixteen texels in registers, bit for bit what
+// hapgpu_k_block_decode would have stored; this kernel blends them into a canvas block it keeps in registers
+// (composite_blend.hpp: the definition) and stores the canvas after the last layer.  Mapping: bc_decode.hip's -- one
+// block per lane, consecutive lanes consecutive blocks of a block row, output picture blockIdx.z, 256 lanes per
+// workgroup, four 16-byte row stores per lane (1 KiB contiguous per wave-instruction).  Traffic per block and layer:
+// 8 / 16 (+ 8) bytes of texture read; per block 64 bytes written, once.
+//
+// A picture's layers are HapGpuCompositeLayer descriptors [pictures][layers] in device memory.  Their address depends
+// on blockIdx.z alone, so a descriptor is scalar loads and the choice among the six decoder bodies a uniform branch;
+// layers of one picture may differ in format.  The canvas is held as two registers per texel, R | B << 16 and
+// G | A << 16, the packed 16-bit lanes the blend works in: it is unpacked once, from the background, and packed once,
+// for the stores.  Per texel and layer: two v_perm_b32 spread the layer's texel the same way (with 255 in A's lane --
+// composite_blend.hpp), a shift and a 24-bit multiply-add make a = rdiv255(As * o), a v_perm_b32 doubles it, a
+// subtraction makes 255 - a, and each of the two pairs costs a packed multiply-add, a second one, and shift, add,
+// shift for rdiv255 -- sixteen instructions.  Wave-uniform shortcuts, exact: a layer of opacity 0 is not loaded; a
+// layer without alpha (DXT1, YCoCg-DXT5 without a plane: As = 255, so a = o) skips the four instructions of a per
+// texel, and at opacity 255 replaces the canvas.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "bc_decode_texels.hpp"
+#include "composite_blend.hpp"
+#include "hapgpu_runtime.hpp"
+
+namespace {
+
+using hapbc::texels::bc_decode_body;
+using hapbc::texels::block_in_registers;
+using namespace hapbc::composite;
+
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
+
+// the canvas block: texel i as R | B << 16 and G | A << 16
+struct canvas_block {
+    unsigned rb[16], ga[16];
+};
+
+// layer `d`'s block `id` as sixteen texels R | G << 8 | B << 16 | A << 24: the body of the picture decoder, from
+// registers to registers
+template <int FMT, bool HAS_ALPHA>
+__device__ __forceinline__ void layer_texels(const uint8_t *blocks, const uint8_t *plane, unsigned id, unsigned (&px)[16])
+{
+    block_in_registers reg;
+    if (FMT == 0) {
+        const uint2 v = *reinterpret_cast<const uint2 *>(blocks + (size_t)id * 8u);
+        reg.block = make_uint4(v.x, v.y, 0u, 0u);
+    } else {
+        reg.block = *reinterpret_cast<const uint4 *>(blocks + (size_t)id * 16u);
+    }
+    reg.plane = HAS_ALPHA ? *reinterpret_cast<const uint2 *>(plane + (size_t)id * 8u) : make_uint2(0u, 0u);
+    reg.texels = px;
+    bc_decode_body<FMT, HAS_ALPHA, false, true>(nullptr, nullptr, 1u, 0u, nullptr, 0u, 0u, 0u, &reg);
+}
+
+// SOURCE_ALPHA: the layer's texels carry an alpha of their own (DXT5, an RGTC1 plane); else As = 255 and a = o
+template <bool SOURCE_ALPHA>
+__device__ __forceinline__ void blend_block(const unsigned (&px)[16], unsigned opacity, canvas_block &c)
+{
+    const unsigned o257 = opacity_scaled(opacity);
+    if (!SOURCE_ALPHA && opacity == 255u) {
+        // a = 255 replaces the texel
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            c.rb[i] = __builtin_amdgcn_perm(0u, px[i], 0x0c020c00u);          // R . B .
+            c.ga[i] = __builtin_amdgcn_perm(0u, px[i], 0x0c0d0c01u);          // G . 255 .
+        }
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const unsigned rb = __builtin_amdgcn_perm(0u, px[i], 0x0c020c00u);    // Rs . Bs .
+        const unsigned ga = __builtin_amdgcn_perm(0u, px[i], 0x0c0d0c01u);    // Gs . 255 .: the canvas's alpha as a colour
+        // (As * o257 + 32896 < 2^24: a 24-bit multiply-add, a in byte 2; without source alpha a scalar)
+        const unsigned m = layer_alpha_in_byte_2(SOURCE_ALPHA ? px[i] >> 24 : 255u, o257);
+        const unsigned a2 = __builtin_amdgcn_perm(0u, m, 0x0c020c02u);        // a . a .
+        const unsigned inv2 = 0x00FF00FFu - a2;
+        c.rb[i] = as_dword(blend_pair(as_pk_u16(rb), as_pk_u16(c.rb[i]), as_pk_u16(a2), as_pk_u16(inv2)));
+        c.ga[i] = as_dword(blend_pair(as_pk_u16(ga), as_pk_u16(c.ga[i]), as_pk_u16(a2), as_pk_u16(inv2)));
+    }
+}
+
+// One launch for `gridDim.z` output pictures of one geometry.  layers: [pictures][layer_count]; outputs: the pictures'
+// addresses.  An output address of 0, or a texture address of 0 in any layer, skips the picture.
+// background: R | G << 8 | B << 16 | A << 24, taken as it is.
+__global__ __launch_bounds__(256) void bc_composite_kernel(const HapGpuCompositeLayer *__restrict__ layers,
+                                                           unsigned layer_count, const uint64_t *__restrict__ outputs,
+                                                           unsigned background, unsigned blocks_x, unsigned blocks_total,
+                                                           size_t row_bytes)
+{
+    const HapGpuCompositeLayer *mine = layers + (size_t)blockIdx.z * layer_count;
+    uint8_t *rgba = (uint8_t *)outputs[blockIdx.z];
+    if (!rgba)
+        return;                     // (the whole workgroup: blockIdx.z is its picture)
+    for (unsigned l = 0; l < layer_count; l++)
+        if (!mine[l].texture)
+            return;
+    const unsigned id = blockIdx.x * 256u + threadIdx.x;
+    if (id >= blocks_total)
+        return;
+    const unsigned by = id / blocks_x, bx = id - by * blocks_x;
+    canvas_block c;
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        c.rb[i] = (background & 0xFFu) | ((background & 0x00FF0000u));
+        c.ga[i] = ((background >> 8) & 0xFFu) | ((background >> 8) & 0x00FF0000u);
+    }
+#pragma unroll 1
+    for (unsigned l = 0; l < layer_count; l++) {
+        // (wave-uniform: the descriptor's address is; readfirstlane says so to the branches below)
+        const unsigned opacity = __builtin_amdgcn_readfirstlane(mine[l].opacity);
+        if (opacity == 0u)
+            continue;               // a = 0 keeps every texel: the layer is not loaded
+        const unsigned format = __builtin_amdgcn_readfirstlane(mine[l].format);
+        const uint8_t *blocks = (const uint8_t *)mine[l].texture, *plane = (const uint8_t *)mine[l].alpha;
+        unsigned px[16];
+        bool source_alpha = plane != nullptr;
+        if (format == 0x83F0u) {
+            if (plane)
+                layer_texels<0, true>(blocks, plane, id, px);
+            else
+                layer_texels<0, false>(blocks, plane, id, px);
+        } else if (format == 0x83F3u) {
+            source_alpha = true;
+            if (plane)
+                layer_texels<1, true>(blocks, plane, id, px);
+            else
+                layer_texels<1, false>(blocks, plane, id, px);
+        } else {
+            if (plane)
+                layer_texels<2, true>(blocks, plane, id, px);
+            else
+                layer_texels<2, false>(blocks, plane, id, px);
+        }
+        if (source_alpha)
+            blend_block<true>(px, opacity, c);
+        else
+            blend_block<false>(px, opacity, c);
+    }
+    uint8_t *dst = rgba + (size_t)(4u * by) * row_bytes + 16u * (size_t)bx;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        v4u v;
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            v[k] = __builtin_amdgcn_perm(c.ga[4 * r + k], c.rb[4 * r + k], 0x06020400u);     // R G B A
+        // (streaming stores, as the picture decoder's: written once, not read back)
+        __builtin_nontemporal_store(v, reinterpret_cast<v4u *>(dst + (size_t)r * row_bytes));
+    }
+}
+
+} // namespace
+
+// hapgpu_abi.h.  Returns 0 launched, 1 bad arguments, 4 launch failure.
+extern "C" int hapgpu_k_block_composite(hapgpu_rt *rt, const HapGpuCompositeLayer *layers, unsigned layer_count,
+                                        const uint64_t *outputs, unsigned pictures, const unsigned char *background,
+                                        unsigned width, unsigned height, size_t row_bytes)
+{
+    scoped_timing st(rt, 6);
+    const hipStream_t stream = hapgpu_rt_stream(rt);
+    if (!layers || !outputs || !background || layer_count == 0 || layer_count > HAPGPU_COMPOSITE_LAYERS_MAX ||
+        pictures == 0 || pictures > 65535u || width == 0 || height == 0 || (width & 3u) || (height & 3u) ||
+        row_bytes < (size_t)width * 4u || (row_bytes & 15u) ||
+        (unsigned long long)(width / 4u) * (height / 4u) > 0xFFFFFFFFull / 256u * 255u)
+        return 1;
+    const unsigned blocks_x = width / 4u, blocks_total = blocks_x * (height / 4u);
+    const unsigned colour = (unsigned)background[0] | ((unsigned)background[1] << 8) | ((unsigned)background[2] << 16) |
+                            ((unsigned)background[3] << 24);
+    const dim3 grid((blocks_total + 255u) / 256u, 1, pictures);
+    hipLaunchKernelGGL(bc_composite_kernel, grid, dim3(256), 0, stream, layers, layer_count, outputs, colour, blocks_x,
+                       blocks_total, row_bytes);
+    return hipGetLastError() == hipSuccess ? 0 : 4;
+}

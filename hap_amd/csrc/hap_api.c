@@ -1113,6 +1113,50 @@ unsigned int HapGpuMeasureFrames(HapGpuContext *context, unsigned int frameCount
     return r;
 }
 
+/* layers of textures over a background colour: one picture, no decoded layer in between */
+unsigned int HapGpuCompositeTextures(HapGpuContext *context, unsigned int layerCount, const void *const *textures,
+                                     const unsigned long *texturesBytes, const unsigned int *textureFormats,
+                                     const void *const *alphaTextures, const unsigned long *alphaTexturesBytes,
+                                     const unsigned char *opacities, const unsigned char *background, unsigned int width,
+                                     unsigned int height, void *rgba, unsigned long rowBytes)
+{
+    unsigned r;
+    /* (what is wrong with the call whatever its layers hold is seen before the context is looked at) */
+    if (!context || !textures || !texturesBytes || !textureFormats || !rgba ||
+        !hapb_composite_valid(layerCount, width, height, rowBytes, NULL))
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_composite_textures(context, layerCount, textures, texturesBytes, textureFormats, alphaTextures,
+                                alphaTexturesBytes, opacities, background, width, height, rgba, rowBytes);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+/* layers of frames over a background colour: one picture per output frame; a NULL results refuses the whole call, and
+   so does anything wrong with it whatever its frames hold -- every result set, before the context is looked at */
+unsigned int HapGpuCompositeFrames(HapGpuContext *context, unsigned int frameCount, unsigned int layerCount,
+                                   const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
+                                   const unsigned int *textureCounts, const unsigned char *opacities,
+                                   const unsigned char *background, void *const *rgbaFrames, unsigned int width,
+                                   unsigned int height, unsigned long rowBytes, unsigned int *results, unsigned int flags)
+{
+    unsigned r;
+    size_t i;
+    if (!context || !results)
+        return HapResult_Bad_Arguments;
+    if (!inputBuffers || !inputBuffersBytes || !rgbaFrames ||
+        !hapb_composite_valid(layerCount, width, height, rowBytes, textureCounts)) {
+        for (i = 0; i < (size_t)frameCount * layerCount; i++)
+            results[i] = HapResult_Bad_Arguments;
+        return HapResult_Bad_Arguments;
+    }
+    hapgpu_rt_lock(context->rt);
+    r = hapb_composite_frames(context, frameCount, layerCount, inputBuffers, inputBuffersBytes, textureCounts, opacities,
+                              background, rgbaFrames, width, height, rowBytes, results, flags);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
 /* HapGpuDecodeFramesRGBA of a block-aligned rectangle of every frame; any other rectangle refuses the whole call */
 unsigned int HapGpuDecodeFramesRGBARegion(HapGpuContext *context, unsigned int frameCount,
                                           const void *const *inputBuffers, const unsigned long *inputBuffersBytes,

@@ -2575,6 +2575,306 @@ unsigned hapb_measure_frames(HapGpuContext *ctx, unsigned frame_count, const voi
                            row_bytes, results, flags & ~HAPGPU_DECODE_BPTC_PICTURES, &road);
 }
 
+/* ============================================================= compositing */
+/* Layers of textures or frames "over" a background colour -> one RGBA8 picture per output frame, by bc_composite.hip:
+   the layers' pictures never exist.  The textures form stages what lies in host memory into D_BC_TEX; the frames form
+   runs the second stage of all frameCount * layerCount frames of a slice in one batch into D_BC_TEX, as decode_pictures
+   does, with a texture count per LAYER -- its entries are staged here, slice_textures being one count per call --, and
+   one composite launch per slice follows.  The descriptors and the pictures' addresses go out in one small table. */
+
+static const unsigned char k_composite_background[4] = {0u, 0u, 0u, 255u};
+/* (the public limit is the kernel's) */
+typedef char composite_limits_agree[HAPGPU_COMPOSITE_MAX_LAYERS == HAPGPU_COMPOSITE_LAYERS_MAX ? 1 : -1];
+
+/* the colour formats a layer may have */
+static int composite_format(unsigned format)
+{
+    return format == HapTextureFormat_RGB_DXT1 || format == HapTextureFormat_RGBA_DXT5 || format == HapTextureFormat_YCoCg_DXT5;
+}
+
+int hapb_composite_valid(unsigned layer_count, unsigned width, unsigned height, unsigned long row_bytes,
+                         const unsigned *texture_counts)
+{
+    unsigned l;
+    if (layer_count == 0 || layer_count > HAPGPU_COMPOSITE_MAX_LAYERS || width == 0 || height == 0 || (width & 3u) ||
+        (height & 3u) || row_bytes < (unsigned long)width * 4u || (row_bytes & 15u))
+        return 0;
+    for (l = 0; texture_counts && l < layer_count; l++)
+        if (texture_counts[l] != 1u && texture_counts[l] != 2u)
+            return 0;
+    return 1;
+}
+
+/* the table of a composite launch for n pictures of layer_count layers: [n] picture addresses, then [n][layer_count]
+   descriptors; *device gets its device copy's address (filled by the caller's h2d of `bytes`) */
+static uint64_t *composite_table(hapgpu_rt *rt, unsigned n, unsigned layer_count, uint64_t **device, size_t *bytes)
+{
+    uint64_t *htab;
+    *bytes = sizeof(uint64_t) * n + sizeof(HapGpuCompositeLayer) * (size_t)n * layer_count;
+    htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, *bytes);
+    *device = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, *bytes);
+    if (!htab || !*device)
+        return NULL;
+    memset(htab, 0, *bytes);
+    return htab;
+}
+
+unsigned hapb_composite_textures(HapGpuContext *ctx, unsigned layer_count, const void *const *textures,
+                                 const unsigned long *texture_bytes, const unsigned *formats,
+                                 const void *const *alphas, const unsigned long *alpha_bytes,
+                                 const unsigned char *opacities, const unsigned char *background, unsigned width,
+                                 unsigned height, void *picture, unsigned long row_bytes)
+{
+    hapgpu_rt *rt = ctx->rt;
+    const size_t blocks = (size_t)(width / 4u) * (height / 4u), pixel_row = (size_t)width * 4u;
+    const size_t picture_bytes = (size_t)row_bytes * (height ? height - 1u : 0u) + pixel_row;
+    size_t staged = 0, tab_bytes, at = 0;
+    uint64_t *htab, *dtab;
+    HapGpuCompositeLayer *hlayers;
+    uint8_t *stage = NULL;
+    void *dst = picture;
+    unsigned l;
+    int rc;
+    if (!hapb_composite_valid(layer_count, width, height, row_bytes, NULL) || !textures || !texture_bytes || !formats ||
+        !picture)
+        return HapResult_Bad_Arguments;
+    if (context_busy(ctx, NULL, 0))
+        return HapResult_Internal_Error;
+    /* every layer: HapGpuDecompressRGBA's rules for its texture and its plane */
+    for (l = 0; l < layer_count; l++) {
+        const void *alpha = alphas ? alphas[l] : NULL;
+        const size_t need = composite_format(formats[l]) ? blocks * hapf_block_bytes(formats[l]) : 0u;
+        if (!textures[l] || !need || texture_bytes[l] < need || (alpha && (!alpha_bytes || alpha_bytes[l] < blocks * 8u)) ||
+            (is_dev(ctx, textures[l]) && ((uintptr_t)textures[l] & (hapf_block_bytes(formats[l]) - 1u))) ||
+            (alpha && is_dev(ctx, alpha) && ((uintptr_t)alpha & 7u)))
+            return HapResult_Bad_Arguments;
+        if (!is_dev(ctx, textures[l]))
+            staged += align_up(need, 256);
+        if (alpha && !is_dev(ctx, alpha))
+            staged += align_up(blocks * 8u, 256);
+    }
+    if (is_dev(ctx, picture) && ((uintptr_t)picture & 15u))
+        return HapResult_Bad_Arguments;
+    /* (one request for all that is staged: an arena that grows forgets what it held) */
+    if (staged && !(stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, staged)))
+        return HapResult_Internal_Error;
+    if (!is_dev(ctx, picture) && !(dst = hapgpu_rt_device_scratch(rt, D_RGBA_STAGE, picture_bytes)))
+        return HapResult_Internal_Error;
+    htab = composite_table(rt, 1u, layer_count, &dtab, &tab_bytes);
+    if (!htab)
+        return HapResult_Internal_Error;
+    hlayers = (HapGpuCompositeLayer *)(htab + 1);
+    htab[0] = (uint64_t)(uintptr_t)dst;
+    for (l = 0; l < layer_count; l++) {
+        const void *alpha = alphas ? alphas[l] : NULL, *src = textures[l];
+        if (!is_dev(ctx, src)) {
+            const size_t need = blocks * hapf_block_bytes(formats[l]);
+            if (hapgpu_rt_h2d(rt, stage + at, src, need))
+                return HapResult_Internal_Error;
+            src = stage + at;
+            at += align_up(need, 256);
+        }
+        if (alpha && !is_dev(ctx, alpha)) {
+            if (hapgpu_rt_h2d(rt, stage + at, alpha, blocks * 8u))
+                return HapResult_Internal_Error;
+            alpha = stage + at;
+            at += align_up(blocks * 8u, 256);
+        }
+        hlayers[l].texture = (uint64_t)(uintptr_t)src;
+        hlayers[l].alpha = (uint64_t)(uintptr_t)alpha;
+        hlayers[l].format = formats[l];
+        hlayers[l].opacity = opacities ? opacities[l] : 255u;
+    }
+    if (hapgpu_rt_h2d(rt, dtab, htab, tab_bytes))
+        return HapResult_Internal_Error;
+    rc = hapgpu_k_block_composite(rt, (const HapGpuCompositeLayer *)(dtab + 1), layer_count, dtab, 1u,
+                                  background ? background : k_composite_background, width, height, row_bytes);
+    if (rc == 1)
+        return HapResult_Bad_Arguments;
+    if (rc)
+        return HapResult_Internal_Error;
+    /* (row by row when the client's rows are longer than the picture's: what lies between them is not ours) */
+    if (dst != picture && (row_bytes == pixel_row ? hapgpu_rt_d2h(rt, picture, dst, picture_bytes)
+                                                  : hapgpu_rt_d2h_rows(rt, picture, row_bytes, dst, row_bytes, pixel_row, height)))
+        return HapResult_Internal_Error;
+    if (hapgpu_rt_sync(rt))
+        return HapResult_Internal_Error;
+    return HapResult_No_Error;
+}
+
+unsigned hapb_composite_frames(HapGpuContext *ctx, unsigned frame_count, unsigned layer_count, const void *const *inputs,
+                               const unsigned long *input_bytes, const unsigned *texture_counts,
+                               const unsigned char *opacities, const unsigned char *background, void *const *rgba_frames,
+                               unsigned width, unsigned height, unsigned long row_bytes, unsigned *results, unsigned flags)
+{
+    hapgpu_rt *rt = ctx->rt;
+    const size_t blocks = (size_t)(width / 4u) * (height / 4u), pixel_row = (size_t)width * 4u;
+    const size_t colour_bytes = align_up(blocks * 16u, 256), plane_bytes = align_up(blocks * 8u, 256);
+    const size_t rgba_bytes = (size_t)row_bytes * (height ? height - 1u : 0u) + pixel_row;
+    const size_t total = (size_t)frame_count * layer_count;
+    size_t per_frame = 0, slice, entries, done, i;
+    unsigned first_error = HapResult_No_Error, per_frame_entries = 0, f, l;
+    /* a layer's first entry within its frame's, and where its textures lie within its frame's scratch */
+    unsigned entry_of[HAPGPU_COMPOSITE_MAX_LAYERS];
+    size_t offset_of[HAPGPU_COMPOSITE_MAX_LAYERS];
+    /* per entry, one allocation (`in` is its start): what hapb_decode is given and what it gives back */
+    const void **in;
+    void **outs;
+    unsigned long *in_bytes, *caps, *used;
+    unsigned *idx, *fmts, *res;
+    if (!results)
+        return HapResult_Bad_Arguments;
+    if (!hapb_composite_valid(layer_count, width, height, row_bytes, texture_counts) || !inputs || !input_bytes ||
+        !rgba_frames) {
+        for (i = 0; i < total; i++)
+            results[i] = HapResult_Bad_Arguments;
+        return HapResult_Bad_Arguments;
+    }
+    if (frame_count == 0)
+        return HapResult_No_Error;
+    if (context_busy(ctx, NULL, 0)) {
+        for (i = 0; i < total; i++)
+            results[i] = HapResult_Internal_Error;
+        return HapResult_Internal_Error;
+    }
+    for (l = 0; l < layer_count; l++) {
+        const unsigned count = texture_counts ? texture_counts[l] : 1u;
+        entry_of[l] = per_frame_entries;
+        offset_of[l] = per_frame;
+        per_frame_entries += count;
+        per_frame += colour_bytes + (count == 2u ? plane_bytes : 0u);
+    }
+    /* output frames of a slice: at most 4 GiB of block textures and 32768 entries of the second stage at a time */
+    slice = RGBA_SLICE_BYTES / per_frame;
+    if (slice == 0)
+        slice = 1;
+    if (slice > frame_count)
+        slice = frame_count;
+    if (slice * per_frame_entries > 32768u)
+        slice = 32768u / per_frame_entries;
+    entries = slice * per_frame_entries;
+    in = (const void **)malloc(entries * (2u * sizeof(void *) + 3u * sizeof(unsigned long) + 3u * sizeof(unsigned)));
+    if (!in) {
+        for (i = 0; i < total; i++)
+            results[i] = HapResult_Internal_Error;
+        return HapResult_Internal_Error;
+    }
+    outs = (void **)(in + entries);
+    in_bytes = (unsigned long *)(outs + entries);
+    caps = in_bytes + entries;
+    used = caps + entries;
+    idx = (unsigned *)(used + entries);
+    fmts = idx + entries;
+    res = fmts + entries;
+    for (done = 0; done < frame_count; done += slice) {
+        const unsigned n = (unsigned)(frame_count - done < slice ? frame_count - done : slice);
+        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, per_frame * n);
+        const HapbDecodeArgs args = {idx, NULL, NULL, 0, NULL, 0u, NULL, NULL};
+        uint8_t *stage = NULL;
+        uint64_t *htab = NULL, *dtab = NULL;
+        HapGpuCompositeLayer *hlayers;
+        size_t tab_bytes = 0;
+        unsigned present = 0;
+        int rc = 0;
+        /* the second stage of every layer of every output frame of the slice, one batch */
+        for (f = 0; textures && f < n; f++)
+            for (l = 0; l < layer_count; l++) {
+                const unsigned count = texture_counts ? texture_counts[l] : 1u;
+                unsigned t;
+                for (t = 0; t < count; t++) {
+                    const size_t e = (size_t)f * per_frame_entries + entry_of[l] + t;
+                    in[e] = inputs[(done + f) * layer_count + l];
+                    in_bytes[e] = input_bytes[(done + f) * layer_count + l];
+                    outs[e] = textures + per_frame * f + offset_of[l] + (t ? colour_bytes : 0u);
+                    caps[e] = (unsigned long)(t ? blocks * 8u : blocks * 16u);
+                    idx[e] = t;
+                    used[e] = 0;
+                    fmts[e] = 0;
+                }
+            }
+        if (textures) {
+            hapb_decode(ctx, n * per_frame_entries, in, in_bytes, 0, outs, caps, used, fmts, res,
+                        flags & ~HAPGPU_DECODE_BPTC_PICTURES, &args);
+            /* (after the second stage, which has tables of its own) */
+            htab = composite_table(rt, n, layer_count, &dtab, &tab_bytes);
+        }
+        if (!htab) {
+            for (i = done * layer_count; i < (done + n) * layer_count; i++)
+                results[i] = HapResult_Internal_Error;
+            first_error = first_error ? first_error : HapResult_Internal_Error;
+            continue;
+        }
+        hlayers = (HapGpuCompositeLayer *)(htab + n);
+        for (f = 0; f < n; f++) {
+            unsigned *frame_results = results + (done + f) * layer_count;
+            void *dst = rgba_frames[done + f];
+            unsigned picture = HapResult_No_Error, all = HapResult_No_Error;
+            for (l = 0; l < layer_count; l++) {
+                const unsigned count = texture_counts ? texture_counts[l] : 1u;
+                const size_t e = (size_t)f * per_frame_entries + entry_of[l];
+                HapGpuCompositeLayer *d = &hlayers[(size_t)f * layer_count + l];
+                unsigned r = res[e];
+                if (r == HapResult_No_Error && count == 2u)
+                    r = res[e + 1];
+                /* the frame must hold what the caller's geometry says: a colour texture of the three formats, of
+                   exactly width x height, and (two textures) an RGTC1 plane of the same geometry */
+                if (r == HapResult_No_Error &&
+                    (!composite_format(fmts[e]) || used[e] != blocks * hapf_block_bytes(fmts[e]) ||
+                     (count == 2u && (fmts[e + 1] != HapTextureFormat_A_RGTC1 || used[e + 1] != blocks * 8u))))
+                    r = HapResult_Bad_Arguments;
+                frame_results[l] = r;
+                if (r != HapResult_No_Error && all == HapResult_No_Error)
+                    all = r;
+                d->texture = (uint64_t)(uintptr_t)outs[e];
+                d->alpha = count == 2u ? (uint64_t)(uintptr_t)outs[e + 1] : 0u;
+                d->format = fmts[e];
+                d->opacity = opacities ? opacities[(done + f) * layer_count + l] : 255u;
+            }
+            /* the picture: NULL or misaligned fails every layer's entry; host pictures are staged */
+            if (!dst || (is_dev(ctx, dst) && ((uintptr_t)dst & 15u))) {
+                picture = HapResult_Bad_Arguments;
+            } else if (all == HapResult_No_Error && !is_dev(ctx, dst)) {
+                if (!stage)
+                    stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_RGBA_STAGE, align_up(rgba_bytes, 256) * n);
+                dst = stage ? stage + align_up(rgba_bytes, 256) * f : NULL;
+                if (!dst)
+                    picture = HapResult_Internal_Error;
+            }
+            if (picture != HapResult_No_Error)
+                for (l = 0; l < layer_count; l++)
+                    frame_results[l] = picture;
+            /* (an output frame that is not written: picture address 0 skips it) */
+            if (picture == HapResult_No_Error && all == HapResult_No_Error) {
+                htab[f] = (uint64_t)(uintptr_t)dst;
+                present = 1;
+            }
+        }
+        if (present) {
+            rc |= hapgpu_rt_h2d(rt, dtab, htab, tab_bytes);
+            rc |= hapgpu_k_block_composite(rt, (const HapGpuCompositeLayer *)(dtab + n), layer_count, dtab, n,
+                                           background ? background : k_composite_background, width, height, row_bytes);
+            for (f = 0; f < n; f++)
+                if (htab[f] && !is_dev(ctx, rgba_frames[done + f])) {
+                    /* (row by row when the client's rows are longer than the picture's) */
+                    if (row_bytes == pixel_row)
+                        rc |= hapgpu_rt_d2h(rt, rgba_frames[done + f], stage + align_up(rgba_bytes, 256) * f, rgba_bytes);
+                    else
+                        rc |= hapgpu_rt_d2h_rows(rt, rgba_frames[done + f], row_bytes, stage + align_up(rgba_bytes, 256) * f,
+                                                 row_bytes, pixel_row, height);
+                }
+        }
+        rc |= hapgpu_rt_sync(rt);
+        for (i = done * layer_count; i < (done + n) * layer_count; i++) {
+            if (rc && results[i] == HapResult_No_Error && htab[i / layer_count - done])
+                results[i] = HapResult_Internal_Error;
+            if (results[i] != HapResult_No_Error && first_error == HapResult_No_Error)
+                first_error = results[i];
+        }
+    }
+    free(in);
+    return first_error;
+}
+
 /* Hap HDR frames (one BC6H texture, unsigned or signed) -> RGBA16F pictures: the same road with the BC6H decoder */
 unsigned hapb_decode_rgba_half(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
                                const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,

@@ -245,6 +245,25 @@ unsigned hapb_transcode_texture(HapGpuContext *ctx, const void *texture, unsigne
                                 unsigned scale_log2, unsigned count, const unsigned *formats, void *const *outputs,
                                 const unsigned long *output_bytes, unsigned long *output_used);
 
+/* what both compositing calls ask whatever their layers are: 1 = the layer count, the geometry, the pitch and (where
+   given) every texture count are in order (include/hap_gpu.h: HapGpuCompositeTextures, HapGpuCompositeFrames).
+   Touches no device. */
+int hapb_composite_valid(unsigned layer_count, unsigned width, unsigned height, unsigned long row_bytes,
+                         const unsigned *texture_counts);
+/* layer_count textures (+ RGTC1 alpha planes; host or device), layer 0 at the bottom, "over" a background colour -> one
+   RGBA8 picture (HapGpuCompositeTextures) */
+unsigned hapb_composite_textures(HapGpuContext *ctx, unsigned layer_count, const void *const *textures,
+                                 const unsigned long *texture_bytes, const unsigned *formats,
+                                 const void *const *alphas, const unsigned long *alpha_bytes,
+                                 const unsigned char *opacities, const unsigned char *background, unsigned width,
+                                 unsigned height, void *picture, unsigned long row_bytes);
+/* ... of frames: entry f * layer_count + l is layer l of output frame f, texture_counts[l] textures read of it; one RGBA8
+   picture per output frame (HapGpuCompositeFrames); results: frame_count * layer_count entries */
+unsigned hapb_composite_frames(HapGpuContext *ctx, unsigned frame_count, unsigned layer_count, const void *const *inputs,
+                               const unsigned long *input_bytes, const unsigned *texture_counts,
+                               const unsigned char *opacities, const unsigned char *background, void *const *rgba_frames,
+                               unsigned width, unsigned height, unsigned long row_bytes, unsigned *results, unsigned flags);
+
 /* groups and output in device memory: tables through the host, payloads device to device */
 unsigned hapb_join_device(HapGpuContext *ctx, unsigned group_count, const void *const *frames,
                           const unsigned long *frame_bytes, void *output, unsigned long output_bytes,

@@ -394,6 +394,30 @@ int hapgpu_k_block_measure(hapgpu_rt *rt, const HapGpuPictureTable *table, unsig
                            unsigned width, unsigned height, unsigned hap_texture_format, size_t row_bytes,
                            uint32_t *partials, unsigned long long *totals);
 size_t hapgpu_block_measure_partial_bytes(unsigned width, unsigned height);
+/* [device] One layer of one output picture of a composite launch: its texture (device address; 0 skips the whole
+   picture, as a texture address of 0 does in HapGpuPictureTable), its RGTC1 alpha plane or 0, the texture's format
+   (HapTextureFormat: RGB_DXT1, RGBA_DXT5 or YCoCg_DXT5) and the layer's opacity byte.  24 bytes. */
+typedef struct HapGpuCompositeLayer {
+    uint64_t texture;
+    uint64_t alpha;
+    uint32_t format;
+    uint32_t opacity;        /* 0 .. 255 */
+} HapGpuCompositeLayer;
+#define HAPGPU_COMPOSITE_LAYERS_MAX 16u     /* include/hap_gpu.h: HAPGPU_COMPOSITE_MAX_LAYERS */
+/* layers of blocks "over" a background colour -> RGBA8 pictures, without the layers' pictures in between
+   (bc_composite.hip).  layers: [pictures][layer_count] descriptors (device), layer 0 at the bottom; outputs: `pictures`
+   device addresses (a device array; 0 skips the picture); background: 4 bytes R, G, B, A in host memory, copied by the
+   call.  Every texel of picture z starts as the background and takes, for l = 0 .. layer_count - 1, with (Rs, Gs, Bs, As)
+   the bytes hapgpu_k_block_decode writes there for layers[z][l]'s texture (and plane) and o its opacity,
+       a = rdiv255(As * o);  Cd = rdiv255(Cs * a + Cd * (255 - a)) for R, G, B;  Ad = a + rdiv255(Ad * (255 - a))
+   (composite_blend.hpp; rdiv255(x) = the integer nearest to x / 255); the picture is the canvas after the last layer.
+   All layers have the pictures' width x height; layers of one picture may differ in format.  Textures 8- (DXT1) or
+   16-byte aligned, alpha planes 8-byte aligned, pictures and row_bytes (at least width * 4) 16-byte aligned; only
+   width * 4 bytes of each row are written.  The profile class of hapgpu_k_block_decode.  Returns 0 launched, 1 bad
+   arguments, 4 launch failure. */
+int hapgpu_k_block_composite(hapgpu_rt *rt, const HapGpuCompositeLayer *layers, unsigned layer_count,
+                             const uint64_t *outputs, unsigned pictures, const unsigned char *background, unsigned width,
+                             unsigned height, size_t row_bytes);
 /* planar tensors -> blocks of `hap_texture_format`, without an RGBA8 picture in between (bc_encode_planes.hip): the way
    back of hapgpu_k_block_decode_planes.  Tensors (the first column of the table) of `channels` (3 or 4: R, G, B[, A])
    planes plane_bytes apart, rows row_bytes apart, elements of element_kind (0 half, 1 bfloat16, 2 float: e = 2, 2, 4

@@ -787,6 +787,97 @@ unsigned int HapGpuMeasureFrames(HapGpuContext *context, unsigned int frameCount
                                  unsigned int *results,
                                  unsigned int flags);
 
+/* The most layers one compositing call takes (HapGpuCompositeTextures, HapGpuCompositeFrames) */
+#define HAPGPU_COMPOSITE_MAX_LAYERS 16u
+
+/* Textures in, one picture out: layerCount textures (+ optional RGTC1 alpha planes) of one geometry go "over" a
+ * background colour, bottom to top, and the result is one RGBA8 picture of width x height -- a matte, a keyed clip or a
+ * title over a background; with two layers and an opacity, a cross-dissolve.  The block decoder blends the texels it
+ * holds in registers into a canvas block it keeps there too: no layer's decoded picture is written or read.
+ * The definition, and the only one; all of it is integer arithmetic on bytes.  The canvas is an RGBA8 picture whose
+ * colour is premultiplied by its alpha (with an opaque background: the same as straight alpha); layers are straight
+ * alpha, as HapGpuDecompressRGBA writes them.  rdiv255(x) is the integer nearest to x / 255 for 0 <= x <= 65025 (no x
+ * lies on a tie: 255 is odd); it equals t = x + 128; (t + (t >> 8)) >> 8, and (2x + 255) / 510 rounded down.  Every
+ * texel of the canvas starts as background[0 .. 3] = R, G, B, A, taken as they are (R, G, B <= A is not checked; NULL:
+ * 0, 0, 0, 255).  Layers are applied in order l = 0 .. layerCount - 1.  For a texel, (Rs, Gs, Bs, As) are the bytes
+ * HapGpuDecompressRGBA writes there for textures[l] with textureFormats[l] and alphaTextures[l] (a source without alpha:
+ * As = 255), o = opacities[l] (NULL: all 255), (Rd, Gd, Bd, Ad) the canvas:
+ *     a  = rdiv255(As * o)
+ *     Cd = rdiv255(Cs * a + Cd * (255 - a))      for C = R, G, B
+ *     Ad = a + rdiv255(Ad * (255 - a))           (never above 255)
+ * The picture written is the canvas after the last layer.  So a = 255 replaces the texel, a = 0 leaves it unchanged,
+ * and a single RGB_DXT1 or YCoCg_DXT5 layer without a plane at opacity 255 gives HapGpuDecompressRGBA's picture byte for
+ * byte, whatever the background.  Two calls give the same bytes.
+ * Every layer has the canvas's width x height, both multiples of 4.  textures, texturesBytes and textureFormats have
+ * layerCount entries; the formats are RGB_DXT1, RGBA_DXT5 and YCoCg_DXT5, and layers may differ in format.
+ * alphaTextures (and alphaTexturesBytes) may be NULL, and so may any entry: a layer with an entry has that RGTC1 plane
+ * for its alpha.  Textures and planes are in host or device memory and follow HapGpuDecompressRGBA's rules (device
+ * textures aligned to their blocks, device planes to 8 bytes).  The picture follows them too: host or device, rowBytes a
+ * multiple of 16 and at least width * 4, a device picture 16-byte aligned, a host picture with longer rows written row
+ * by row; only the picture's own width * 4 bytes of each row are ever written.
+ * Bad_Arguments, and nothing written, for a NULL required array or picture, a layerCount of 0 or above
+ * HAPGPU_COMPOSITE_MAX_LAYERS, a width or height that is no multiple of 4, a rowBytes that is short or misaligned, a NULL
+ * or short texture, any other format, a misaligned device address.  A context between HapGpuEncodeFramesRGBABegin and
+ * HapGpuEncodeFramesFinish: Internal_Error.
+ * Out of scope: layers of other sizes or at an offset, scaled or rectangular canvases; blend modes other than "over"; an
+ * existing picture as the bottom layer; RGBA_BPTC_UNORM (Hap R), BC6H (Hap HDR) and lone A_RGTC1 (Hap Alpha-Only) layers;
+ * planar or RGBA16F output; skipping layers hidden under an opaque one. */
+unsigned int HapGpuCompositeTextures(HapGpuContext *context, unsigned int layerCount,
+                                     const void *const *textures, const unsigned long *texturesBytes,
+                                     const unsigned int *textureFormats,
+                                     const void *const *alphaTextures, const unsigned long *alphaTexturesBytes,
+                                     const unsigned char *opacities,
+                                     const unsigned char *background,
+                                     unsigned int width, unsigned int height, void *rgba, unsigned long rowBytes);
+
+/* Frames in, one picture per output frame out: HapGpuCompositeTextures for frameCount output frames of layerCount layers
+ * each.  inputBuffers[f * layerCount + l] (inputBuffersBytes likewise) is the Hap frame of layer l of output frame f,
+ * layer 0 at the bottom; rgbaFrames[f] is output frame f's RGBA8 picture.  All frameCount * layerCount frames of a slice
+ * go through the second stage in one batch into the context's texture scratch (at most 4 GiB of block textures and
+ * 32768 textures at a time: longer calls are worked through in slices of output frames), and one compositing launch per
+ * slice follows.  A dissolve is two layers with opacities that change from output frame to output frame.
+ * The definition, and the only one; all of it is integer arithmetic on bytes.  The canvas is an RGBA8 picture whose
+ * colour is premultiplied by its alpha; layers are straight alpha.  rdiv255(x) is the integer nearest to x / 255 for
+ * 0 <= x <= 65025: t = x + 128; (t + (t >> 8)) >> 8.  Every texel of output frame f's canvas starts as background[0 .. 3]
+ * = R, G, B, A, taken as they are (NULL: 0, 0, 0, 255); then, for l = 0 .. layerCount - 1, with (Rs, Gs, Bs, As) the
+ * bytes HapGpuDecodeFramesRGBA writes there for that layer's frame with textureCounts[l] and the call's flags (a source
+ * without alpha: As = 255), o = opacities[f * layerCount + l] (NULL: all 255) and (Rd, Gd, Bd, Ad) the canvas:
+ *     a  = rdiv255(As * o)
+ *     Cd = rdiv255(Cs * a + Cd * (255 - a))      for C = R, G, B
+ *     Ad = a + rdiv255(Ad * (255 - a))           (never above 255)
+ * The picture written is the canvas after the last layer: a = 255 replaces the texel, a = 0 leaves it unchanged, and a
+ * single Hap or Hap Q layer at opacity 255 gives HapGpuDecodeFramesRGBA's picture byte for byte, whatever the background.
+ * Two calls give the same bytes.
+ * Every layer has the canvas's width x height, both multiples of 4.  textureCounts has layerCount entries (NULL: all 1):
+ * with 2, layer l holds Hap Q Alpha frames; with 1, Hap, Hap Alpha or Hap Q frames, and a Hap Q Alpha frame read with 1
+ * is its colour texture alone, as in HapGpuDecodeFramesRGBA.  A layer may hold different flavours in different output
+ * frames.  Frames are in host or device memory, as for HapGpuDecodeFramesRGBA; flags are the decode flags of
+ * HapGpuDecodeFrameTextures, and HAPGPU_DECODE_BPTC_PICTURES is ignored.  Pictures follow HapGpuDecodeFramesRGBA's
+ * rules: host or device, rowBytes a multiple of 16 and at least width * 4, shared by all output frames, device pictures
+ * 16-byte aligned, host pictures with longer rows written row by row; only a picture's own bytes of each row are ever
+ * written.
+ * results is a HOST array of frameCount * layerCount entries: results[f * layerCount + l] is HapDecode's code for that
+ * layer's frame, and Bad_Arguments for a frame of another format or geometry than the call says.  Output picture f is
+ * written if and only if all its layers are No_Error and its picture pointer is usable; otherwise it is untouched, and
+ * the other output frames are still composited.  For a NULL or misaligned picture every entry of that output frame is
+ * Bad_Arguments.  The function's result is the first failure.
+ * Bad_Arguments for the whole call -- every result set, nothing written, no device touched -- for a NULL required
+ * array (a NULL results: nothing to set), a layerCount of 0 or above HAPGPU_COMPOSITE_MAX_LAYERS, a width or height that
+ * is no multiple of 4, a rowBytes that is short or misaligned, a textureCounts entry other than 1 or 2.  A context
+ * between HapGpuEncodeFramesRGBABegin and HapGpuEncodeFramesFinish: Internal_Error.
+ * Out of scope: layers of other sizes or at an offset, scaled or rectangular canvases; blend modes other than "over"; an
+ * existing picture as the bottom layer; Hap R, Hap HDR and Hap Alpha-Only layers -- Bad_Arguments alone --; planar or
+ * RGBA16F output; skipping layers hidden under an opaque one; ...OnDevices and ...Sequence forms of this call. */
+unsigned int HapGpuCompositeFrames(HapGpuContext *context, unsigned int frameCount, unsigned int layerCount,
+                                   const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
+                                   const unsigned int *textureCounts,
+                                   const unsigned char *opacities,
+                                   const unsigned char *background,
+                                   void *const *rgbaFrames,
+                                   unsigned int width, unsigned int height, unsigned long rowBytes,
+                                   unsigned int *results,
+                                   unsigned int flags);
+
 /* Planar float tensors in, frames out -- the way back of HapGpuDecodeFramesPlanes: HapGpuEncodeFramesRGBA with the tensors of
  * HapGpuCompressPlanes in place of pictures.  planeFrames[f] is frame f's tensor in DEVICE memory, `channels` planes of
  * width x height elements, planeBytes and rowBytes shared by all frames (one N x C x H x W tensor: planeFrames[f] = base +
