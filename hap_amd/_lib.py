@@ -91,6 +91,10 @@ def _load():
         "HapGpuDecodeFramesRGBARegion": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, u, u, u, ul, P(u), u]),
         "HapGpuDecodeFramesPlanesRegion": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, P(u), P(u), u, u, u, u, u, ul, ul,
                                                P(C.c_float), P(C.c_float), P(u), u]),
+        "HapGpuDecompressPlanesResized": (u, [vp, vp, ul, u, vp, ul, u, u, u, u, u, u, u, u, u, u, u, vp, ul, ul,
+                                              P(C.c_float), P(C.c_float)]),
+        "HapGpuDecodeFramesPlanesResized": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, P(u), P(u), P(u), P(u), u, u, u, u,
+                                                ul, ul, P(C.c_float), P(C.c_float), P(u), u]),
         "HapGpuMeasureTexture": (u, [vp, vp, ul, u, vp, ul, u, u, vp, ul, P(HapGpuPictureError)]),
         "HapGpuMeasureFrames": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, ul, P(HapGpuPictureError), P(u), u]),
         "HapGpuCompositeTextures": (u, [vp, u, P(vp), P(ul), P(u), P(vp), P(ul), P(C.c_ubyte), P(C.c_ubyte), u, u, vp, ul]),

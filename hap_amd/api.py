@@ -509,6 +509,25 @@ class Context:
                                                 scale_log2, channels, element, tensors[0].data_ptr(), plane_bytes,
                                                 row_bytes, sc, bi)
 
+    def decompress_planes_resized(self, texture, texture_format, width, height, crop, out, scale_log2=0, scale=None,
+                                  bias=None, alpha=None):
+        """Texture (+ optional RGTC1 alpha plane) -> `out`, a (C, out_h, out_w) tensor: crop = (x, y, w, h), at any texel
+        position and size of the (width >> scale_log2) x (height >> scale_log2) picture, resized to the tensor's size by
+        the integer bilinear filter of HapGpuDecodeFramesPlanesResized (HapGpuDecompressPlanesResized).  channels, element,
+        strides and the output size are read from the tensor; scale and bias as for decompress_planes.  Returns the
+        result."""
+        x, y, w, h = crop
+        if not hasattr(out, "shape") or len(out.shape) != 3:
+            raise ValueError("out: one (C, out_h, out_w) tensor")
+        out_h, out_w = int(out.shape[1]), int(out.shape[2])
+        tensors, channels, element, plane_bytes, row_bytes = _plane_tensors(out, True, out_w, out_h, 0)
+        sc, bi = _plane_constants(scale, bias, channels)
+        ta, tn, _k = _addr_len(texture)
+        aa, an, _k2 = _addr_len(alpha) if alpha is not None else (None, 0, None)
+        return lib.HapGpuDecompressPlanesResized(self.handle, ta, tn, texture_format, aa, an, width, height, scale_log2,
+                                                 x, y, w, h, out_w, out_h, channels, element, tensors[0].data_ptr(),
+                                                 plane_bytes, row_bytes, sc, bi)
+
     def compress_planes(self, planes, width, height, texture_format, scale=None, bias=None, output=None):
         """`planes`, a (C, height, width) float16, bfloat16 or float32 torch tensor on the device, C 3 or 4 -> one block
         texture (HapGpuCompressPlanes): byte = float32(element) * scale[c] + bias[c] (two roundings), NaN and anything
@@ -928,6 +947,33 @@ class Context:
         r = lib.HapGpuDecodeFramesPlanesRegion(self.handle, nf, ptrs, lens, texture_count, optrs, width, height, xs, ys,
                                                w, h, scale_log2, channels, element, plane_bytes, row_bytes, sc, bi,
                                                results, flags)
+        return r, list(results)
+
+    def decode_frames_planes_resized(self, frames, frame_bytes, texture_count, out, width, height, crops, out_size,
+                                     scale_log2=0, scale=None, bias=None, flags=0):
+        """Frames -> normalised planar tensors of a resized crop per frame in one call (HapGpuDecodeFramesPlanesResized):
+        crops[f] = (x, y, w, h), at any texel position and size of frame f's (width >> scale_log2) x
+        (height >> scale_log2) picture, comes out as out_size = (out_w, out_h) elements by the call's integer bilinear
+        filter; w <= 4 * out_w and h <= 4 * out_h.  `out`: as for decode_frames_planes, but (N, C, out_h, out_w); scale and
+        bias likewise.  Pieces of a frame that hold none of the blocks under its crop stay undecoded
+        (skipped_texture_bytes).  Returns (result, results[])."""
+        nf = len(frames)
+        out_w, out_h = out_size
+        crops = [tuple(c) for c in crops]
+        if len(crops) != nf or any(len(c) != 4 for c in crops):
+            raise ValueError("one crop (x, y, w, h) per frame")
+        tensors, channels, element, plane_bytes, row_bytes = _plane_tensors(out, False, out_w, out_h, 0)
+        if len(tensors) != nf:
+            raise ValueError("one tensor per frame")
+        sc, bi = _plane_constants(scale, bias, channels)
+        ptrs, infos = self._ptr_array(frames)
+        lens = (C.c_ulong * nf)(*[fb if fb is not None else infos[i][1] for i, fb in enumerate(frame_bytes)])
+        optrs = (C.c_void_p * nf)(*[None if t is None else t.data_ptr() for t in tensors])
+        xs, ys, ws, hs = [(C.c_uint * nf)(*[c[k] for c in crops]) for k in range(4)]
+        results = (C.c_uint * nf)()
+        r = lib.HapGpuDecodeFramesPlanesResized(self.handle, nf, ptrs, lens, texture_count, optrs, width, height, scale_log2,
+                                                xs, ys, ws, hs, out_w, out_h, channels, element, plane_bytes, row_bytes, sc,
+                                                bi, results, flags)
         return r, list(results)
 
     def transcode_texture(self, texture, texture_format, width, height, scale_log2, output_formats, alpha=None,

@@ -634,6 +634,31 @@ unsigned int HapGpuDecompressPlanesRegion(HapGpuContext *context, const void *te
     return r;
 }
 
+/* HapGpuDecompressPlanes of one crop of the scaled picture, at any texel position and size, resized to outWidth x
+   outHeight */
+unsigned int HapGpuDecompressPlanesResized(HapGpuContext *context, const void *texture, unsigned long textureBytes,
+                                           unsigned int textureFormat, const void *alphaTexture,
+                                           unsigned long alphaTextureBytes, unsigned int width, unsigned int height,
+                                           unsigned int scaleLog2, unsigned int cropX, unsigned int cropY,
+                                           unsigned int cropWidth, unsigned int cropHeight, unsigned int outWidth,
+                                           unsigned int outHeight, unsigned int channels, unsigned int element,
+                                           void *planes, unsigned long planeBytes, unsigned long rowBytes,
+                                           const float *scale, const float *bias)
+{
+    const HapbPlanes layout = {channels, element, planeBytes, scale, bias};
+    const HapbResize resize = {&cropX, &cropY, &cropWidth, &cropHeight, outWidth, outHeight};
+    HapGpuRegion blocks;
+    unsigned r;
+    if (!context || !planes_arguments_valid(scaleLog2, channels, element, scale, bias) || (width & 3u) || (height & 3u) ||
+        !hapb_resize_out_valid(&resize) || !hapb_resize_region(&resize, 0u, width, height, scaleLog2, &blocks))
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_decompress_planes_resized(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width,
+                                       height, &resize, scaleLog2, planes, rowBytes, &layout);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
 unsigned int HapGpuDecompressRGBAHalf(HapGpuContext *context, const void *texture, unsigned long textureBytes,
                                       unsigned int textureFormat, unsigned int width, unsigned int height,
                                       void *rgbaHalf, unsigned long rowBytes)
@@ -1255,6 +1280,37 @@ unsigned int HapGpuDecodeFramesPlanesRegion(HapGpuContext *context, unsigned int
     r = hapb_decode_planes_region(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, planeFrames, width,
                                   height, regionXs, regionYs, regionWidth, regionHeight, scaleLog2, rowBytes, &layout,
                                   results, flags);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+/* HapGpuDecodeFramesPlanes of a crop per frame of the scaled picture, at any texel position and size, every one resized
+   to outWidth x outHeight; a NULL crop array or an output size outside 1 .. 16384 refuses the whole call, a crop that is
+   empty, past an edge or more than 4 x the output refuses its frame */
+unsigned int HapGpuDecodeFramesPlanesResized(HapGpuContext *context, unsigned int frameCount,
+                                             const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
+                                             unsigned int textureCount, void *const *planeFrames, unsigned int width,
+                                             unsigned int height, unsigned int scaleLog2, const unsigned int *cropXs,
+                                             const unsigned int *cropYs, const unsigned int *cropWidths,
+                                             const unsigned int *cropHeights, unsigned int outWidth,
+                                             unsigned int outHeight, unsigned int channels, unsigned int element,
+                                             unsigned long planeBytes, unsigned long rowBytes, const float *scale,
+                                             const float *bias, unsigned int *results, unsigned int flags)
+{
+    const HapbPlanes layout = {channels, element, planeBytes, scale, bias};
+    const HapbResize resize = {cropXs, cropYs, cropWidths, cropHeights, outWidth, outHeight};
+    unsigned r, f;
+    if (!context)
+        return HapResult_Bad_Arguments;
+    if (!planes_arguments_valid(scaleLog2, channels, element, scale, bias) || !cropXs || !cropYs || !cropWidths ||
+        !cropHeights || !hapb_resize_out_valid(&resize)) {
+        for (f = 0; results && f < frameCount; f++)
+            results[f] = HapResult_Bad_Arguments;
+        return HapResult_Bad_Arguments;
+    }
+    hapgpu_rt_lock(context->rt);
+    r = hapb_decode_planes_resized(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, planeFrames, width,
+                                   height, &resize, scaleLog2, rowBytes, &layout, results, flags);
     hapgpu_rt_unlock(context->rt);
     return r;
 }

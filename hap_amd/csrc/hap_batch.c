@@ -848,6 +848,9 @@ typedef struct picture_road {
                                    are reference pictures in device memory and are READ: the launch is
                                    hapgpu_k_block_measure, and measure[f] gets the sums of frame f against its picture,
                                    f counted from the call's first frame */
+    const HapbResize *resize;   /* NULL: tensors of the rectangle's or the frames' (scaled) size; else (planes only, no region)
+                                   tensors of resize->out_w x resize->out_h, entry f's crop of the scaled picture resized,
+                                   by hapgpu_k_block_decode_planes_resized */
 } picture_road;
 
 /* RGBA8 pictures (BC7 last: frames of it only with HAPGPU_DECODE_BPTC_PICTURES), RGBA16F ones and A8 ones */
@@ -907,6 +910,34 @@ static picture_road planes_region_road_of(unsigned scale_log2, const HapbPlanes 
     return (picture_road){3u, k_rgba_kinds, 0x7u, HAPGPU_PICTURE_RGBA8, scale_log2, region, planes, xs, ys};
 }
 
+/* ... of a crop per entry at any texel position and size of the scaled picture, resized to one output size */
+static picture_road planes_resized_road_of(unsigned scale_log2, const HapbPlanes *planes, const HapbResize *resize)
+{
+    return (picture_road){3u, k_rgba_kinds, 0x7u, HAPGPU_PICTURE_RGBA8, scale_log2, NULL, planes, NULL, NULL, NULL, resize};
+}
+
+int hapb_resize_out_valid(const HapbResize *resize)
+{
+    return resize->out_w >= 1u && resize->out_w <= 16384u && resize->out_h >= 1u && resize->out_h <= 16384u;
+}
+
+int hapb_resize_region(const HapbResize *resize, size_t f, unsigned width, unsigned height, unsigned scale_log2,
+                       HapGpuRegion *region)
+{
+    const unsigned x = resize->xs[f], y = resize->ys[f], w = resize->ws[f], h = resize->hs[f];
+    const unsigned level_w = width >> scale_log2, level_h = height >> scale_log2;
+    if (scale_log2 > 2u || w == 0u || h == 0u || x > level_w || w > level_w - x || y > level_h || h > level_h - y ||
+        w > 4u * resize->out_w || h > 4u * resize->out_h)
+        return 0;
+    /* (outward to the grid: width and height are multiples of 4, so the far edges stay inside) */
+    region->width = width;
+    region->x = (x << scale_log2) & ~3u;
+    region->y = (y << scale_log2) & ~3u;
+    region->w = ((((x + w) << scale_log2) + 3u) & ~3u) - region->x;
+    region->h = ((((y + h) << scale_log2) + 3u) & ~3u) - region->y;
+    return hapb_region_fits(region, height);
+}
+
 /* bytes of what a road's row_bytes counts: a texel of an interleaved picture, an element of a plane */
 static size_t picture_texel_bytes(const picture_road *road)
 {
@@ -918,11 +949,15 @@ static size_t picture_texel_bytes(const picture_road *road)
 /* the geometry of a road's pictures, from the textures' */
 static unsigned picture_width_of(const picture_road *road, unsigned width)
 {
+    if (road->resize)
+        return road->resize->out_w;
     return (road->region ? road->region->w : width) >> road->scale_log2;
 }
 
 static unsigned picture_height_of(const picture_road *road, unsigned height)
 {
+    if (road->resize)
+        return road->resize->out_h;
     return (road->region ? road->region->h : height) >> road->scale_log2;
 }
 
@@ -935,9 +970,12 @@ int hapb_region_fits(const HapGpuRegion *region, unsigned height)
 
 /* what the block decoders ask of a picture's address (in device memory) and row pitch when they write it: 16-byte
    stores for RGBA8 and RGBA16F; A8 pictures take dword stores, and 16-byte ones where address and pitch allow; a scaled
-   picture takes the 16 >> scale_log2 bytes a lane has for each of its rows, a plane its 4 >> scale_log2 elements */
+   picture takes the 16 >> scale_log2 bytes a lane has for each of its rows, a plane its 4 >> scale_log2 elements -- or,
+   resized, the one element a lane stores */
 static unsigned picture_align_mask(const picture_road *road)
 {
+    if (road->resize)
+        return (unsigned)picture_texel_bytes(road) - 1u;
     if (road->planes)
         return (4u >> road->scale_log2) * (unsigned)picture_texel_bytes(road) - 1u;
     if (road->scale_log2)
@@ -963,7 +1001,8 @@ static uint32_t region_first_block(unsigned width, unsigned x, unsigned y)
 
 /* the block-decode launch of a road: pictures of the frames' size, scaled ones, a rectangle's, or planar tensors (the
    alpha plane is read only where a fourth plane is written).  origins: a planar road with a rectangle per frame -- the
-   device array of the pictures' first blocks; partials, totals: a measuring road's scratch (measure_scratch) */
+   device array of the pictures' first blocks, or, resized, of their crops (four words each; NULL: the road's first crop
+   for all); partials, totals: a measuring road's scratch (measure_scratch) */
 static int launch_block_decode(hapgpu_rt *rt, const picture_road *road, const HapGpuPictureTable *t, unsigned pictures,
                                int with_alpha, unsigned width, unsigned height, unsigned format, size_t row_bytes, int wide,
                                const uint32_t *origins, uint32_t *partials, unsigned long long *totals)
@@ -971,6 +1010,14 @@ static int launch_block_decode(hapgpu_rt *rt, const picture_road *road, const Ha
     /* (a measuring road: the block kernel with the pictures as its third column, read, and the reduction behind it) */
     if (road->measure)
         return hapgpu_k_block_measure(rt, t, pictures, with_alpha, width, height, format, row_bytes, partials, totals);
+    if (road->resize) {
+        const unsigned crop[4] = {road->resize->xs[0], road->resize->ys[0], road->resize->ws[0], road->resize->hs[0]};
+        return hapgpu_k_block_decode_planes_resized(rt, t, pictures, with_alpha && road->planes->channels == 4u, width, height,
+                                                    format, origins, origins ? NULL : crop, road->resize->out_w,
+                                                    road->resize->out_h, road->scale_log2, road->planes->channels,
+                                                    road->planes->element, road->planes->plane_bytes, row_bytes,
+                                                    road->planes->scale, road->planes->bias);
+    }
     if (road->planes && road->region)
         return hapgpu_k_block_decode_planes_region(rt, t, pictures, with_alpha && road->planes->channels == 4u, width, height,
                                                    format, origins,
@@ -1009,6 +1056,7 @@ static unsigned decompress_picture(HapGpuContext *ctx, const void *texture, unsi
     void *dst = picture;
     uint32_t *partials = NULL;
     unsigned long long *totals = NULL, *htotals = NULL;
+    HapGpuRegion resized;       /* (a resized road's crop as a rectangle of blocks: only asked whether there is one) */
     unsigned k;
     int rc;
     if (context_busy(ctx, NULL, 0))
@@ -1017,6 +1065,8 @@ static unsigned decompress_picture(HapGpuContext *ctx, const void *texture, unsi
         ;
     if (!texture || !picture || width == 0 || height == 0 || (width & 3u) || (height & 3u) || row_bytes < pixel_row ||
         (road.region && (road.region->width != width || !hapb_region_fits(road.region, height))) ||
+        (road.resize && (!hapb_resize_out_valid(road.resize) ||
+                         !hapb_resize_region(road.resize, 0u, width, height, road.scale_log2, &resized))) ||
         k == road.kind_count || (alpha && !(road.paired_kinds >> k & 1u)) ||
         /* (tensors live in device memory: no host staging road) */
         (road.planes && (!planes_fit(&road, pixel_row, picture_height, row_bytes) || !is_dev(ctx, picture))) ||
@@ -1124,6 +1174,16 @@ unsigned hapb_decompress_planes_region(HapGpuContext *ctx, const void *texture, 
                                        unsigned long row_bytes, const HapbPlanes *planes)
 {
     const picture_road road = planes_region_road_of(scale_log2, planes, region, NULL, NULL);
+    return decompress_picture(ctx, texture, texture_bytes, format, alpha, alpha_bytes, width, height, tensor, row_bytes,
+                              &road);
+}
+
+unsigned hapb_decompress_planes_resized(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
+                                        const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
+                                        const HapbResize *resize, unsigned scale_log2, void *tensor,
+                                        unsigned long row_bytes, const HapbPlanes *planes)
+{
+    const picture_road road = planes_resized_road_of(scale_log2, planes, resize);
     return decompress_picture(ctx, texture, texture_bytes, format, alpha, alpha_bytes, width, height, tensor, row_bytes,
                               &road);
 }
@@ -2294,10 +2354,12 @@ static int slice_textures_init(slice_textures *s, unsigned frame_count, unsigned
 /* Frames done .. done + n of the call (n <= s->slice) into `textures`, per_frame * n bytes of D_BC_TEX scratch.  region
    (NULL: whole textures): the rectangle wanted of every frame -- or, with xs and ys, its size alone, frame f's origin being
    (xs[f], ys[f]): a frame whose origin puts the rectangle off the grid or past an edge goes to hapb_decode with a NULL
-   input, its Bad_Arguments, and nothing of it is decoded. */
+   input, its Bad_Arguments, and nothing of it is decoded.  resize (NULL, or region NULL): frame f's rectangle is its crop
+   at scale_log2 rounded outward to the blocks (hapb_resize_region), and a crop that is none refuses its frame alike. */
 static void slice_textures_decode(HapGpuContext *ctx, const slice_textures *s, uint8_t *textures, const void *const *inputs,
                                   const unsigned long *input_bytes, size_t done, unsigned n, const HapGpuRegion *region,
-                                  const unsigned *xs, const unsigned *ys, unsigned flags)
+                                  const unsigned *xs, const unsigned *ys, const HapbResize *resize, unsigned scale_log2,
+                                  unsigned flags)
 {
     const unsigned width = s->width, height = s->height;
     const HapGpuRegion whole = {width, 0u, 0u, width, height};
@@ -2318,6 +2380,12 @@ static void slice_textures_decode(HapGpuContext *ctx, const slice_textures *s, u
                 own = whole;
             else if (own.x != 0u || own.y != 0u || own.w != width || own.h != height)
                 any_skip = 1;
+        } else if (resize) {
+            refused = !hapb_resize_region(resize, done + f, width, height, scale_log2, &own);
+            if (refused)
+                own = whole;
+            else if (own.x != 0u || own.y != 0u || own.w != width || own.h != height)
+                any_skip = 1;
         }
         for (t = 0; t < s->texture_count; t++) {
             const size_t e = (size_t)f * s->texture_count + t;
@@ -2334,7 +2402,7 @@ static void slice_textures_decode(HapGpuContext *ctx, const slice_textures *s, u
     }
     /* (rectangles that are all the whole frame skip nothing -- one that is among others needs everything -- and nor does
        one rectangle for all that is the whole frame) */
-    if (xs)
+    if (xs || resize)
         args.regions = any_skip ? s->decode_regions : NULL;
     else if (region && !(region->x == 0u && region->y == 0u && region->w == width && region->h == height))
         args.region = region;
@@ -2355,7 +2423,8 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
     const unsigned picture_height = picture_height_of(road, height);
     const size_t pixel_row = (size_t)picture_width_of(road, width) * picture_texel_bytes(road);
     const unsigned align = picture_align_mask(road);
-    const int per_frame_regions = road->region_xs != NULL;
+    const int per_frame_regions = road->region_xs != NULL || road->resize != NULL;
+    const size_t frame_words = road->resize ? 4u : 1u;      /* what travels behind the table per frame */
     if (frame_count == 0)
         return HapResult_No_Error;
     if (!results)
@@ -2365,6 +2434,8 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
     if (!inputs || !input_bytes || !rgba_frames || texture_count == 0 || texture_count > 2 || width == 0 ||
         height == 0 || (width & 3u) || (height & 3u) || row_bytes < pixel_row || (row_bytes & align) ||
         (road->region && (road->region->width != width || !hapb_region_fits(road->region, height))) ||
+        (road->resize && (!hapb_resize_out_valid(road->resize) || !road->resize->xs || !road->resize->ys ||
+                          !road->resize->ws || !road->resize->hs)) ||
         (road->planes && !planes_fit(road, pixel_row, picture_height, row_bytes)) ||
         (road->picture_kind == HAPGPU_PICTURE_A8 && height / 4u > 65535u)) {
         for (f = 0; f < frame_count; f++)
@@ -2393,14 +2464,15 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
             continue;
         }
         slice_textures_decode(ctx, &s, textures, inputs, input_bytes, done, n, road->region, road->region_xs, road->region_ys,
-                              flags);
+                              road->resize, road->scale_log2, flags);
         {
             /* one block-decode launch per texture format present in the slice: [textures][alpha planes][pictures] in a
                small device table, pictures of other formats (or that failed) with a texture address of 0 */
-            /* ... and behind the table, in the same copy, a rectangle per frame's first texture block of every picture */
+            /* ... and behind the table, in the same copy, a rectangle per frame's first texture block of every picture -- or,
+               resized, every picture's crop: four words, x, y, w, h */
             /* ... and, in the pinned copy alone, a measuring road's totals of every picture on their way back */
             const size_t ptr_words = (size_t)3u * PICTURE_KINDS_MAX * n;
-            const size_t tab_bytes = sizeof(uint64_t) * ptr_words + (per_frame_regions ? sizeof(uint32_t) * n : 0u);
+            const size_t tab_bytes = sizeof(uint64_t) * ptr_words + (per_frame_regions ? sizeof(uint32_t) * frame_words * n : 0u);
             const size_t totals_bytes = road->measure ? sizeof(unsigned long long) * 8u * n : 0u;
             uint64_t *htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, align_up(tab_bytes, 8) + totals_bytes);
             uint64_t *dtab = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, tab_bytes);
@@ -2458,8 +2530,14 @@ static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
                     htab[(size_t)k * 3u * n + f] = (uint64_t)(uintptr_t)s.outs[e];
                     htab[(size_t)k * 3u * n + n + f] = texture_count == 2 ? (uint64_t)(uintptr_t)s.outs[e + 1] : 0u;
                     htab[(size_t)k * 3u * n + 2u * n + f] = (uint64_t)(uintptr_t)dst;
-                    if (horigins)       /* (inside the frame: a refused origin never gets here) */
+                    if (horigins && road->resize) {     /* (a crop of the frame: a refused one never gets here) */
+                        horigins[4u * f] = road->resize->xs[done + f];
+                        horigins[4u * f + 1u] = road->resize->ys[done + f];
+                        horigins[4u * f + 2u] = road->resize->ws[done + f];
+                        horigins[4u * f + 3u] = road->resize->hs[done + f];
+                    } else if (horigins) {              /* (inside the frame: a refused origin never gets here) */
                         horigins[f] = region_first_block(width, road->region_xs[done + f], road->region_ys[done + f]);
+                    }
                 }
                 results[done + f] = r;
             }
@@ -2558,6 +2636,19 @@ unsigned hapb_decode_planes_region(HapGpuContext *ctx, unsigned frame_count, con
             results[f] = HapResult_Bad_Arguments;
         return HapResult_Bad_Arguments;
     }
+    return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, tensors, width, height, row_bytes,
+                           results, flags, &road);
+}
+
+/* ... and to planar tensors of out_w x out_h of a crop per frame, at any texel position and size of the scaled picture:
+   the resampling block decoder over the blocks under every output tile, and a second stage that leaves out, frame by
+   frame, what holds none of the blocks the frame's crop touches */
+unsigned hapb_decode_planes_resized(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                                    const unsigned long *input_bytes, unsigned texture_count, void *const *tensors,
+                                    unsigned width, unsigned height, const HapbResize *resize, unsigned scale_log2,
+                                    unsigned long row_bytes, const HapbPlanes *planes, unsigned *results, unsigned flags)
+{
+    const picture_road road = planes_resized_road_of(scale_log2, planes, resize);
     return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, tensors, width, height, row_bytes,
                            results, flags, &road);
 }
@@ -2986,7 +3077,7 @@ unsigned hapb_transcode(HapGpuContext *ctx, unsigned frame_count, const void *co
             first_error = first_error ? first_error : HapResult_Internal_Error;
             continue;
         }
-        slice_textures_decode(ctx, &s, textures, inputs, input_bytes, done, n, NULL, NULL, NULL, decode_flags);
+        slice_textures_decode(ctx, &s, textures, inputs, input_bytes, done, n, NULL, NULL, NULL, NULL, 0u, decode_flags);
         memset(htab, 0, tab_bytes);
         for (f = 0; f < n; f++) {
             const size_t e = (size_t)f * texture_count;

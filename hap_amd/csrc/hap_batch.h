@@ -131,6 +131,26 @@ unsigned hapb_decompress_planes_region(HapGpuContext *ctx, const void *texture, 
                                        const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
                                        const HapGpuRegion *region, unsigned scale_log2, void *tensor,
                                        unsigned long row_bytes, const HapbPlanes *planes);
+/* The crops of the resized planar roads (include/hap_gpu.h: HapGpuDecompressPlanesResized,
+   HapGpuDecodeFramesPlanesResized): entry f's crop is (xs[f], ys[f], ws[f], hs[f]) in texels of the scaled picture, f
+   counted from the call's first frame, and every tensor is out_w x out_h elements */
+typedef struct HapbResize {
+    const unsigned *xs, *ys, *ws, *hs;
+    unsigned out_w, out_h;
+} HapbResize;
+/* 1: out_w and out_h are sizes the resized roads take (1 to 16384) */
+int hapb_resize_out_valid(const HapbResize *resize);
+/* 1: crop f of `resize` is one of a width x height texture at scale_log2 -- not empty, inside the scaled picture, at most
+   4 x the output per axis; *region then gets it in full-size texels, rounded outward to the block grid: a rectangle of
+   hapb_region_fits */
+int hapb_resize_region(const HapbResize *resize, size_t f, unsigned width, unsigned height, unsigned scale_log2,
+                       HapGpuRegion *region);
+/* ... one crop of it, at any texel position and size of the scaled picture, resized -> one planar tensor of
+   resize->out_w x resize->out_h (the arrays hold one entry) */
+unsigned hapb_decompress_planes_resized(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
+                                        const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
+                                        const HapbResize *resize, unsigned scale_log2, void *tensor,
+                                        unsigned long row_bytes, const HapbPlanes *planes);
 /* one planar tensor in device memory -> one texture (host or device): DXT1, DXT5, YCoCg-DXT5, or RGTC1 from the fourth
    plane (255 where there are three) */
 unsigned hapb_compress_planes(HapGpuContext *ctx, const void *tensor, unsigned width, unsigned height,
@@ -221,6 +241,12 @@ unsigned hapb_decode_planes_region(HapGpuContext *ctx, unsigned frame_count, con
                                    unsigned width, unsigned height, const unsigned *xs, const unsigned *ys,
                                    unsigned region_w, unsigned region_h, unsigned scale_log2, unsigned long row_bytes,
                                    const HapbPlanes *planes, unsigned *results, unsigned flags);
+/* ... a crop per frame of the scaled picture, frame f's (resize->xs[f], ys[f], ws[f], hs[f]) at any texel position and
+   size, resized to planar tensors in device memory of resize->out_w x resize->out_h */
+unsigned hapb_decode_planes_resized(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                                    const unsigned long *input_bytes, unsigned texture_count, void *const *tensors,
+                                    unsigned width, unsigned height, const HapbResize *resize, unsigned scale_log2,
+                                    unsigned long row_bytes, const HapbPlanes *planes, unsigned *results, unsigned flags);
 /* Hap HDR frames (one BC6H texture) -> RGBA16F pictures */
 unsigned hapb_decode_rgba_half(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
                                const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,

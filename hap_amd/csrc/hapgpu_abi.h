@@ -379,6 +379,23 @@ int hapgpu_k_block_decode_planes_region(hapgpu_rt *rt, const HapGpuPictureTable 
                                         unsigned region_height, unsigned scale_log2, unsigned channels,
                                         unsigned element_kind, size_t plane_bytes, size_t row_bytes, const float *scale,
                                         const float *bias);
+/* ... a crop per picture, at any texel position and size, resized to planar tensors of out_width x out_height (1 to 16384
+   each), bc_resample_planes.hip.  With s = scale_log2 and P the (width >> s) x (height >> s) RGBA8 picture
+   hapgpu_k_block_decode (s 0) or hapgpu_k_block_decode_scaled writes, picture z's crop is (x, y, w, h) in texels of P:
+   crops[4 * z ..] (a DEVICE array), or, where crops is NULL, the four words at `crop` (host) for all of them.  w, h >= 1,
+   x + w <= width >> s, y + h <= height >> s, w <= 4 * out_width, h <= 4 * out_height: checked for `crop`; a picture of
+   `crops` that breaks them is left unwritten.  Every output byte is resample_taps.hpp's blend of four texels of P inside
+   the crop -- include/hap_gpu.h: HapGpuDecodeFramesPlanesResized has the definition -- and the element is
+   hapgpu_k_block_decode_planes' conversion of it.  Only the blocks that hold texels of the crop are read.  Formats,
+   scale and bias as for hapgpu_k_block_decode_planes.  A lane stores single elements: tensors, plane_bytes and row_bytes
+   multiples of e, row_bytes at least out_width * e, plane_bytes at least row_bytes * (out_height - 1) + out_width * e.
+   The same table, profile class and return codes. */
+int hapgpu_k_block_decode_planes_resized(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, int with_alpha,
+                                         unsigned width, unsigned height, unsigned hap_texture_format,
+                                         const uint32_t *crops, const unsigned *crop, unsigned out_width,
+                                         unsigned out_height, unsigned scale_log2, unsigned channels,
+                                         unsigned element_kind, size_t plane_bytes, size_t row_bytes, const float *scale,
+                                         const float *bias);
 /* blocks of `hap_texture_format` against RGBA8 reference pictures (the third column of the table: read, not written),
    without a decoded picture in between (bc_measure.hip): for every picture whose texture address is not 0,
    totals[picture][0..3] = the sum over all width x height texels of (d - p)^2 for R, G, B, A and totals[picture][4..7] the

@@ -334,6 +334,30 @@ unsigned int HapGpuDecompressPlanesRegion(HapGpuContext *context,
                                           void *planes, unsigned long planeBytes, unsigned long rowBytes,
                                           const float *scale, const float *bias);
 
+/* The same texture -> the planar float tensor, in DEVICE memory, of one crop of it at any texel position and size,
+ * resized to outWidth x outHeight: the single-texture form of HapGpuDecodeFramesPlanesResized, which has the definition
+ * -- P is here what HapGpuDecompressRGBA (scaleLog2 0) or HapGpuDecompressRGBAScaled (1, 2) writes, (cropX, cropY,
+ * cropWidth, cropHeight) the crop in texels of P, and the taps, the blend, the two roundings (one binary32 multiply, one
+ * binary32 add, not fused) and the limits are that call's.  Only the blocks that hold texels of the crop are read.
+ * width and height are the TEXTURE's, multiples of 4; textures (host or device), formats and the alpha plane as for
+ * HapGpuDecompressPlanes.  Tensor: device memory only; with e the element's size the address, rowBytes and planeBytes are
+ * multiples of e, rowBytes at least outWidth * e and planeBytes at least rowBytes * (outHeight - 1) + outWidth * e; a
+ * slice of a larger tensor qualifies; nothing is written between rows or planes.  Bad_Arguments, and nothing written, for
+ * anything else: a crop that is empty, past an edge of P or more than 4 x the output in either axis, an output size of 0
+ * or above 16384, and what HapGpuDecompressPlanes refuses.
+ * Out of scope: RGBA_BPTC_UNORM (BC7), the BC6H formats and a lone A_RGTC1 as sources (Bad_Arguments), host tensors,
+ * other filters, RGBA8 output. */
+unsigned int HapGpuDecompressPlanesResized(HapGpuContext *context,
+                                           const void *texture, unsigned long textureBytes, unsigned int textureFormat,
+                                           const void *alphaTexture, unsigned long alphaTextureBytes,
+                                           unsigned int width, unsigned int height, unsigned int scaleLog2,
+                                           unsigned int cropX, unsigned int cropY,
+                                           unsigned int cropWidth, unsigned int cropHeight,
+                                           unsigned int outWidth, unsigned int outHeight,
+                                           unsigned int channels, unsigned int element,
+                                           void *planes, unsigned long planeBytes, unsigned long rowBytes,
+                                           const float *scale, const float *bias);
+
 /* BC6H texture (Hap HDR) -> RGBA16F: four IEEE half bit patterns per texel, 8 bytes, rows rowBytes apart.
  * textureFormat: RGB_BPTC_UNSIGNED_FLOAT or RGB_BPTC_SIGNED_FLOAT (anything else is Bad_Arguments).  RGB is
  * the BPTC definition's result bit for bit (signed textures may give -0, 0x8000, which is kept); alpha is
@@ -663,7 +687,8 @@ unsigned int HapGpuDecodeFramesRGBAScaled(HapGpuContext *context, unsigned int f
  * HapGpuEncodeFramesFinish: Internal_Error.
  * Out of scope: Hap R (BC7), Hap HDR (BC6H) and Hap Alpha-Only (a lone A_RGTC1) frames -- Bad_Arguments alone, with or
  * without HAPGPU_DECODE_BPTC_PICTURES --, host tensors, ...OnDevices and ...Sequence forms of this call; rectangles:
- * HapGpuDecodeFramesPlanesRegion.  The way back, from planar float tensors to frames, is HapGpuEncodeFramesPlanes. */
+ * HapGpuDecodeFramesPlanesRegion.  The way back, from planar float tensors to frames, is HapGpuEncodeFramesPlanes.  A crop
+ * per frame at any texel position and size, every one resized to one output size: HapGpuDecodeFramesPlanesResized. */
 unsigned int HapGpuDecodeFramesPlanes(HapGpuContext *context, unsigned int frameCount,
                                       const void *const *inputBuffers,
                                       const unsigned long *inputBuffersBytes,
@@ -708,7 +733,8 @@ unsigned int HapGpuDecodeFramesPlanes(HapGpuContext *context, unsigned int frame
  * Hap Q Alpha.
  * Out of scope: Hap R (BC7), Hap HDR (BC6H) and Hap Alpha-Only (a lone A_RGTC1) frames as sources, host tensors,
  * rectangles off the block grid, rectangles of different sizes in one call, ...OnDevices and ...Sequence forms of this
- * call, and an RGBA8 "rectangle together with scaleLog2" call. */
+ * call, and an RGBA8 "rectangle together with scaleLog2" call.  (Rectangles of a size of their own per frame, at any texel
+ * position, resized to one output size: HapGpuDecodeFramesPlanesResized.) */
 unsigned int HapGpuDecodeFramesPlanesRegion(HapGpuContext *context, unsigned int frameCount,
                                             const void *const *inputBuffers,
                                             const unsigned long *inputBuffersBytes,
@@ -722,6 +748,68 @@ unsigned int HapGpuDecodeFramesPlanesRegion(HapGpuContext *context, unsigned int
                                             const float *scale, const float *bias,
                                             unsigned int *results,
                                             unsigned int flags);
+
+/* Frames in, normalised planar float tensors of a RESIZED crop per frame out: what a training or inference loader does
+ * with video -- a random-resized crop, a tracked box, a tile -- in one call.  Every frame has a crop of its own, at any
+ * texel position and of any size, and every crop comes out at one size, outWidth x outHeight (224 x 224, say):
+ * planeFrames[f] is frame f's tensor in DEVICE memory, `channels` planes of outWidth x outHeight elements, planeBytes and
+ * rowBytes shared by all frames.  cropXs, cropYs, cropWidths and cropHeights have frameCount entries each.
+ * The definition, and the only one.  Let s = scaleLog2, 0 to 2, and P the picture that HapGpuDecodeFramesRGBA (s = 0) or
+ * HapGpuDecodeFramesRGBAScaled (s = 1, 2) writes for the frame with the same textureCount and flags: (width >> s) x
+ * (height >> s) texels.  Frame f's crop is (x, y, cw, ch) = (cropXs[f], cropYs[f], cropWidths[f], cropHeights[f]) in
+ * texels of P: arbitrary integers -- no grid -- with cw, ch >= 1, x + cw <= width >> s and y + ch <= height >> s.
+ * The taps of an output axis of o elements over a crop axis of c texels, in integers only (pixel centres, what torch
+ * calls align_corners = false):
+ *     num  = max((2 * i + 1) * c - o, 0)            i = 0 .. o - 1
+ *     i0   = min(num / (2 * o), c - 1)      i1 = min(i0 + 1, c - 1)        taps never leave the crop: edge texels repeat
+ *     frac = num % (2 * o)                  w  = (frac * 256 + o) / (2 * o)     0 .. 256: nearest, halves up
+ * The byte of output texel (ox, oy), channel k, with x0, x1, wx from (outWidth, cw) at ox and y0, y1, wy from
+ * (outHeight, ch) at oy:
+ *     top = P[y + y0][x + x0][k] * (256 - wx) + P[y + y0][x + x1][k] * wx
+ *     bot = P[y + y1][x + x0][k] * (256 - wx) + P[y + y1][x + x1][k] * wx
+ *     v   = (top * (256 - wy) + bot * wy + 32768) >> 16                        0 .. 255
+ * and the element is HapGpuDecodeFramesPlanes' conversion of v: one binary32 multiply by scale[k], then one binary32 add
+ * of bias[k] (two roundings, not fused), then the rounding to the element.  All intermediates fit 32 bits.  With
+ * outWidth == cw and outHeight == ch every weight is 0 and the call is an exact crop; on a block-aligned crop of that kind
+ * it equals HapGpuDecodeFramesPlanesRegion bit for bit.  Bilinear filters of other libraries come close (within a byte
+ * of torch's bilinear, antialias = False) but are not the definition.
+ * Limits.  outWidth and outHeight are 1 to 16384.  Per frame cw <= 4 * outWidth and ch <= 4 * outHeight: the block decoder
+ * stages the texels under a tile of the output in on-chip memory, and that bounds them.  With scaleLog2 that is 16 x in
+ * all.  A bilinear filter aliases beyond a ratio of 2: a client that minds picks scaleLog2 so that the remaining ratio
+ * is at most 2 -- the box mean of the level is the prefilter.
+ * The block decoder reads only the blocks that hold texels of a frame's crop, and the second stage leaves undecoded, frame
+ * by frame, every independently decodable piece that holds no byte of them (the crop taken back to full-size texels and
+ * rounded outward to the block grid: HapGpuRegionNeedsBytes; counted by HapGpuSkippedTextureBytes), as
+ * HapGpuDecodeFramesPlanesRegion does.
+ * Tensors: device memory only.  A lane stores single elements, so the rule is the plain one: with e the element's size the
+ * addresses, rowBytes and planeBytes are multiples of e, rowBytes at least outWidth * e and planeBytes at least
+ * rowBytes * (outHeight - 1) + outWidth * e; a slice of a larger tensor qualifies; nothing is written between rows or
+ * planes.
+ * Bad_Arguments for the whole call -- every results[f] set, nothing written -- for what HapGpuDecodeFramesPlanes refuses
+ * (its tensor rule replaced by the one above), a NULL crop array, an outWidth or outHeight of 0 or above 16384.  A frame
+ * whose crop is empty, past an edge of P or over the ratio cap is Bad_Arguments alone: its tensor is untouched, nothing
+ * of it is handed to the second stage or the block decoder, and the other frames are decoded.  So is a frame of another
+ * format or geometry, or one whose tensor is NULL, in host memory or misaligned.  A broken frame gets HapDecode's code;
+ * damage wholly inside skipped pieces is not seen.  A context between HapGpuEncodeFramesRGBABegin and
+ * HapGpuEncodeFramesFinish: Internal_Error.  Sources, textureCount, flags, mixed batches (one block-decode launch per
+ * texture format present), slicing and result codes are HapGpuDecodeFramesPlanes': Hap, Hap Alpha, Hap Q, Hap Q Alpha.
+ * Out of scope: Hap R (BC7), Hap HDR (BC6H) and Hap Alpha-Only (a lone A_RGTC1) frames as sources, host tensors, an
+ * output size per frame, other filters (nearest, bicubic, antialiased), ...OnDevices and ...Sequence forms of this call,
+ * and RGBA8 output. */
+unsigned int HapGpuDecodeFramesPlanesResized(HapGpuContext *context, unsigned int frameCount,
+                                             const void *const *inputBuffers,
+                                             const unsigned long *inputBuffersBytes,
+                                             unsigned int textureCount,
+                                             void *const *planeFrames,
+                                             unsigned int width, unsigned int height, unsigned int scaleLog2,
+                                             const unsigned int *cropXs, const unsigned int *cropYs,
+                                             const unsigned int *cropWidths, const unsigned int *cropHeights,
+                                             unsigned int outWidth, unsigned int outHeight,
+                                             unsigned int channels, unsigned int element,
+                                             unsigned long planeBytes, unsigned long rowBytes,
+                                             const float *scale, const float *bias,
+                                             unsigned int *results,
+                                             unsigned int flags);
 
 /* How far a texture or a frame is from a picture (HapGpuMeasureTexture, HapGpuMeasureFrames): per channel the exact
  * integer sums over all width x height texels.  72 bytes. */
