@@ -1638,36 +1638,9 @@ def _group_table(frame):
     return at + 5, n, at + 5 + 4 * n
 
 
-def _unpack_groups(table):
-    """(compressed bytes of the 64 groups, bytes they produce, element count)"""
-    table = bytes(table)
-    assert len(table) == GT and table[194:196] == bytes(2)
-    entries = [int.from_bytes(table[3 * g: 3 * g + 3], "little") for g in range(64)]
-    return [e & 0xFFF for e in entries], [e >> 12 for e in entries], int.from_bytes(table[192:194], "little")
-
-
-def _pack_groups(sizes, made, elements):
-    assert len(sizes) == 64 and len(made) == 64 and all(0 <= v < 4096 for v in list(sizes) + list(made))
-    return b"".join((c | (m << 12)).to_bytes(3, "little") for c, m in zip(sizes, made)) + elements.to_bytes(2, "little") + bytes(2)
-
-
-def _element_lengths(e):
-    """(bytes of the element in the stream, bytes it produces) of one hand-made Snappy element"""
-    tag = e[0]
-    kind = tag & 3
-    if kind == 0:
-        code = tag >> 2
-        return len(e), code + 1 if code < 60 else int.from_bytes(e[1: code - 58], "little") + 1
-    return len(e), 4 + ((tag >> 2) & 7) if kind == 1 else (tag >> 2) + 1
-
-
-def _groups_of(elements):
-    """The group table of a fragment made of these elements (byte strings): 64 groups of ceil(N / 64) elements."""
-    lens = [_element_lengths(e) for e in elements]
-    n = len(lens)
-    per = (n + 63) // 64
-    return _pack_groups([sum(c for c, _m in lens[g * per: (g + 1) * per]) for g in range(64)],
-                        [sum(m for _c, m in lens[g * per: (g + 1) * per]) for g in range(64)], n)
+# (the table's packing and a fragment's table from its elements: tests/_field_streams.py, which builds whole sweeps with them)
+from _field_streams import (element_lengths as _element_lengths, group_table as _groups_of,  # noqa: E402,F401
+                            pack_groups as _pack_groups, unpack_groups as _unpack_groups)
 
 
 def test_field_stream_table_is_described_exactly_and_every_lie_falls_back(ctx, hap):
