@@ -494,6 +494,42 @@ unsigned int HapGetFrameTextureChunkCount(const void *inputBuffer, unsigned long
 
 /* ----------------------------------------------------------- hap_gpu.h -- */
 
+/* the whole-call refusal: every result set (a NULL results: none), Bad_Arguments returned */
+static unsigned refuse_call(unsigned int *results, size_t count)
+{
+    size_t i;
+    for (i = 0; results && i < count; i++)
+        results[i] = HapResult_Bad_Arguments;
+    return HapResult_Bad_Arguments;
+}
+
+/* a call down a road (hap_batch.h: HapbRoad) with the context's lock held: one texture, or frames */
+static unsigned texture_down_road(HapGpuContext *context, const void *texture, unsigned long textureBytes,
+                                  unsigned textureFormat, const void *alphaTexture, unsigned long alphaTextureBytes,
+                                  unsigned width, unsigned height, void *picture, unsigned long rowBytes,
+                                  const HapbRoad *road)
+{
+    unsigned r;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_road_texture(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width, height,
+                          picture, rowBytes, road);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+static unsigned frames_down_road(HapGpuContext *context, unsigned frameCount, const void *const *inputBuffers,
+                                 const unsigned long *inputBuffersBytes, unsigned textureCount, void *const *pictures,
+                                 unsigned width, unsigned height, unsigned long rowBytes, unsigned int *results,
+                                 unsigned flags, const HapbRoad *road)
+{
+    unsigned r;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_road_frames(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, pictures, width, height,
+                         rowBytes, results, flags, road);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
 unsigned int HapGpuCompressRGBA(HapGpuContext *context, const void *rgba, unsigned int width,
                                 unsigned int height, unsigned long rowBytes, unsigned int textureFormat,
                                 void *output, unsigned long outputBytes, unsigned long *outputBytesUsed)
@@ -527,14 +563,12 @@ unsigned int HapGpuDecompressRGBA(HapGpuContext *context, const void *texture, u
                                   unsigned int textureFormat, const void *alphaTexture, unsigned long alphaBytes,
                                   unsigned int width, unsigned int height, void *rgba, unsigned long rowBytes)
 {
-    unsigned r;
+    /* (one texture: BC7 is always taken; frames of it only with HAPGPU_DECODE_BPTC_PICTURES) */
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA8, .bptc = 1};
     if (!context)
         return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_decompress_rgba(context, texture, textureBytes, textureFormat, alphaTexture, alphaBytes, width, height,
-                             rgba, rowBytes, HAPGPU_PICTURE_RGBA8, 0u, NULL);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    return texture_down_road(context, texture, textureBytes, textureFormat, alphaTexture, alphaBytes, width, height, rgba,
+                             rowBytes, &road);
 }
 
 /* one texture against its reference picture in device memory: the sums of the decoder's errors, no picture written */
@@ -543,14 +577,12 @@ unsigned int HapGpuMeasureTexture(HapGpuContext *context, const void *texture, u
                                   unsigned int width, unsigned int height, const void *rgba, unsigned long rowBytes,
                                   HapGpuPictureError *error)
 {
-    unsigned r;
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA8, .measure = error};
     if (!context || !error)
         return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_measure_texture(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width, height,
-                             rgba, rowBytes, error);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    /* (the road's pictures are its third column whichever way the bytes go: this one only reads them) */
+    return texture_down_road(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width,
+                             height, (void *)(uintptr_t)rgba, rowBytes, &road);
 }
 
 /* HapGpuDecompressRGBA of a block-aligned rectangle of the texture */
@@ -561,14 +593,11 @@ unsigned int HapGpuDecompressRGBARegion(HapGpuContext *context, const void *text
                                         unsigned int regionHeight, void *rgba, unsigned long rowBytes)
 {
     const HapGpuRegion region = {width, regionX, regionY, regionWidth, regionHeight};
-    unsigned r;
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA8, .bptc = 1, .region = &region};
     if (!context || !hapb_region_fits(&region, height))
         return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_decompress_rgba(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width, height,
-                             rgba, rowBytes, HAPGPU_PICTURE_RGBA8, 0u, &region);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    return texture_down_road(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width,
+                             height, rgba, rowBytes, &road);
 }
 
 /* HapGpuDecompressRGBA at half (scaleLog2 1) or quarter (2) size */
@@ -577,14 +606,11 @@ unsigned int HapGpuDecompressRGBAScaled(HapGpuContext *context, const void *text
                                         unsigned long alphaTextureBytes, unsigned int width, unsigned int height,
                                         unsigned int scaleLog2, void *rgba, unsigned long rowBytes)
 {
-    unsigned r;
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA8, .scale_log2 = scaleLog2, .bptc = 1};
     if (!context || scaleLog2 < 1u || scaleLog2 > 2u)
         return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_decompress_rgba(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width, height,
-                             rgba, rowBytes, HAPGPU_PICTURE_RGBA8, scaleLog2, NULL);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    return texture_down_road(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width,
+                             height, rgba, rowBytes, &road);
 }
 
 /* 1: what the planar calls take of scaleLog2, channels, element, scale and bias */
@@ -603,14 +629,11 @@ unsigned int HapGpuDecompressPlanes(HapGpuContext *context, const void *texture,
                                     const float *bias)
 {
     const HapbPlanes layout = {channels, element, planeBytes, scale, bias};
-    unsigned r;
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA8, .scale_log2 = scaleLog2, .planes = &layout};
     if (!context || !planes_arguments_valid(scaleLog2, channels, element, scale, bias))
         return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_decompress_planes(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width,
-                               height, scaleLog2, planes, rowBytes, &layout);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    return texture_down_road(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width,
+                             height, planes, rowBytes, &road);
 }
 
 /* HapGpuDecompressPlanes of a block-aligned rectangle of the texture */
@@ -624,14 +647,12 @@ unsigned int HapGpuDecompressPlanesRegion(HapGpuContext *context, const void *te
 {
     const HapbPlanes layout = {channels, element, planeBytes, scale, bias};
     const HapGpuRegion region = {width, regionX, regionY, regionWidth, regionHeight};
-    unsigned r;
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA8, .scale_log2 = scaleLog2, .region = &region,
+                           .planes = &layout};
     if (!context || !planes_arguments_valid(scaleLog2, channels, element, scale, bias) || !hapb_region_fits(&region, height))
         return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_decompress_planes_region(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width,
-                                      height, &region, scaleLog2, planes, rowBytes, &layout);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    return texture_down_road(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width,
+                             height, planes, rowBytes, &road);
 }
 
 /* HapGpuDecompressPlanes of one crop of the scaled picture, at any texel position and size, resized to outWidth x
@@ -647,30 +668,25 @@ unsigned int HapGpuDecompressPlanesResized(HapGpuContext *context, const void *t
 {
     const HapbPlanes layout = {channels, element, planeBytes, scale, bias};
     const HapbResize resize = {&cropX, &cropY, &cropWidth, &cropHeight, outWidth, outHeight};
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA8, .scale_log2 = scaleLog2, .planes = &layout,
+                           .resize = &resize};
     HapGpuRegion blocks;
-    unsigned r;
     if (!context || !planes_arguments_valid(scaleLog2, channels, element, scale, bias) || (width & 3u) || (height & 3u) ||
         !hapb_resize_out_valid(&resize) || !hapb_resize_region(&resize, 0u, width, height, scaleLog2, &blocks))
         return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_decompress_planes_resized(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width,
-                                       height, &resize, scaleLog2, planes, rowBytes, &layout);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    return texture_down_road(context, texture, textureBytes, textureFormat, alphaTexture, alphaTextureBytes, width,
+                             height, planes, rowBytes, &road);
 }
 
 unsigned int HapGpuDecompressRGBAHalf(HapGpuContext *context, const void *texture, unsigned long textureBytes,
                                       unsigned int textureFormat, unsigned int width, unsigned int height,
                                       void *rgbaHalf, unsigned long rowBytes)
 {
-    unsigned r;
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA16F};
     if (!context)
         return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_decompress_rgba(context, texture, textureBytes, textureFormat, NULL, 0, width, height, rgbaHalf, rowBytes,
-                             HAPGPU_PICTURE_RGBA16F, 0u, NULL);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    return texture_down_road(context, texture, textureBytes, textureFormat, NULL, 0, width, height, rgbaHalf, rowBytes,
+                             &road);
 }
 
 unsigned int HapGpuEncodeFrames(HapGpuContext *context, unsigned int frameCount, unsigned int count,
@@ -782,12 +798,10 @@ static unsigned planes_encode_refused(unsigned frameCount, const void *const *pl
                                       const unsigned long *outputBuffersBytes, unsigned long *outputBuffersBytesUsed,
                                       unsigned *results)
 {
-    unsigned f;
     if (results && planeFrames && compressors && chunkCounts && outputBuffers && outputBuffersBytes &&
         outputBuffersBytesUsed && hapb_planes_encode_valid(width, height, rowBytes, layout, count, textureFormats))
         return 0u;
-    for (f = 0; results && f < frameCount; f++)
-        results[f] = HapResult_Bad_Arguments;
+    refuse_call(results, frameCount);
     return 1u;
 }
 
@@ -926,14 +940,12 @@ unsigned int HapGpuCompressAlpha(HapGpuContext *context, const void *alpha, unsi
 unsigned int HapGpuDecompressAlpha(HapGpuContext *context, const void *texture, unsigned long textureBytes,
                                    unsigned int width, unsigned int height, void *alpha, unsigned long rowBytes)
 {
-    unsigned r;
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_A8};
     if (!context)
         return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_decompress_rgba(context, texture, textureBytes, HapTextureFormat_A_RGTC1, NULL, 0, width, height, alpha,
-                             rowBytes, HAPGPU_PICTURE_A8, 0u, NULL);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    return texture_down_road(context, texture, textureBytes, HapTextureFormat_A_RGTC1, NULL, 0, width, height, alpha,
+                             rowBytes,
+                             &road);
 }
 
 unsigned int HapGpuEncodeFramesAlpha(HapGpuContext *context, unsigned int frameCount, const void *const *alphaFrames,
@@ -1106,14 +1118,11 @@ unsigned int HapGpuDecodeFramesRGBA(HapGpuContext *context, unsigned int frameCo
                                     unsigned int height, unsigned long rowBytes, unsigned int *results,
                                     unsigned int flags)
 {
-    unsigned r;
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA8, .bptc = (flags & HAPGPU_DECODE_BPTC_PICTURES) != 0};
     if (!context)
         return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_decode_rgba(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, rgbaFrames, width, height,
-                         0u, rowBytes, results, flags);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    return frames_down_road(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, rgbaFrames, width, height,
+                            rowBytes, results, flags, &road);
 }
 
 /* frames against their reference pictures in device memory; a NULL errors refuses the whole call like a NULL results */
@@ -1123,19 +1132,16 @@ unsigned int HapGpuMeasureFrames(HapGpuContext *context, unsigned int frameCount
                                  unsigned long rowBytes, HapGpuPictureError *errors, unsigned int *results,
                                  unsigned int flags)
 {
-    unsigned r, f;
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA8, .measure = errors};
     if (!context)
         return HapResult_Bad_Arguments;
-    if (!errors) {
-        for (f = 0; results && f < frameCount; f++)
-            results[f] = HapResult_Bad_Arguments;
-        return HapResult_Bad_Arguments;
-    }
-    hapgpu_rt_lock(context->rt);
-    r = hapb_measure_frames(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, rgbaFrames, width, height,
-                            rowBytes, errors, results, flags);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    if (!errors)
+        return refuse_call(results, frameCount);
+    /* (the road's pictures are its third column whichever way the bytes go: this one only reads them.  Hap R frames
+       are out of scope with or without the flag that asks for their pictures) */
+    return frames_down_road(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, (void *const *)rgbaFrames,
+                            width, height, rowBytes, results,
+                            flags & ~HAPGPU_DECODE_BPTC_PICTURES, &road);
 }
 
 /* layers of textures over a background colour: one picture, no decoded layer in between */
@@ -1166,15 +1172,11 @@ unsigned int HapGpuCompositeFrames(HapGpuContext *context, unsigned int frameCou
                                    unsigned int height, unsigned long rowBytes, unsigned int *results, unsigned int flags)
 {
     unsigned r;
-    size_t i;
     if (!context || !results)
         return HapResult_Bad_Arguments;
     if (!inputBuffers || !inputBuffersBytes || !rgbaFrames ||
-        !hapb_composite_valid(layerCount, width, height, rowBytes, textureCounts)) {
-        for (i = 0; i < (size_t)frameCount * layerCount; i++)
-            results[i] = HapResult_Bad_Arguments;
-        return HapResult_Bad_Arguments;
-    }
+        !hapb_composite_valid(layerCount, width, height, rowBytes, textureCounts))
+        return refuse_call(results, (size_t)frameCount * layerCount);
     hapgpu_rt_lock(context->rt);
     r = hapb_composite_frames(context, frameCount, layerCount, inputBuffers, inputBuffersBytes, textureCounts, opacities,
                               background, rgbaFrames, width, height, rowBytes, results, flags);
@@ -1191,19 +1193,14 @@ unsigned int HapGpuDecodeFramesRGBARegion(HapGpuContext *context, unsigned int f
                                           unsigned int *results, unsigned int flags)
 {
     const HapGpuRegion region = {width, regionX, regionY, regionWidth, regionHeight};
-    unsigned r, f;
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA8, .bptc = (flags & HAPGPU_DECODE_BPTC_PICTURES) != 0,
+                           .region = &region};
     if (!context)
         return HapResult_Bad_Arguments;
-    if (!hapb_region_fits(&region, height)) {
-        for (f = 0; results && f < frameCount; f++)
-            results[f] = HapResult_Bad_Arguments;
-        return HapResult_Bad_Arguments;
-    }
-    hapgpu_rt_lock(context->rt);
-    r = hapb_decode_rgba_region(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, rgbaFrames, width, height,
-                                &region, rowBytes, results, flags);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    if (!hapb_region_fits(&region, height))
+        return refuse_call(results, frameCount);
+    return frames_down_road(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, rgbaFrames, width, height,
+                            rowBytes, results, flags, &road);
 }
 
 /* HapGpuDecodeFramesRGBA at half (scaleLog2 1) or quarter (2) size; any other scale refuses the whole call */
@@ -1213,19 +1210,15 @@ unsigned int HapGpuDecodeFramesRGBAScaled(HapGpuContext *context, unsigned int f
                                           unsigned int height, unsigned int scaleLog2, unsigned long rowBytes,
                                           unsigned int *results, unsigned int flags)
 {
-    unsigned r, f;
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA8, .scale_log2 = scaleLog2,
+                           .bptc = (flags & HAPGPU_DECODE_BPTC_PICTURES) != 0};
     if (!context)
         return HapResult_Bad_Arguments;
-    if (scaleLog2 < 1u || scaleLog2 > 2u) {
-        for (f = 0; results && f < frameCount; f++)
-            results[f] = HapResult_Bad_Arguments;
-        return HapResult_Bad_Arguments;
-    }
-    hapgpu_rt_lock(context->rt);
-    r = hapb_decode_rgba(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, rgbaFrames, width, height,
-                         scaleLog2, rowBytes, results, flags);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    /* (the road underneath takes scale 0: that is HapGpuDecodeFramesRGBA's to ask for) */
+    if (scaleLog2 < 1u || scaleLog2 > 2u)
+        return refuse_call(results, frameCount);
+    return frames_down_road(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, rgbaFrames, width, height,
+                            rowBytes, results, flags, &road);
 }
 
 /* frames -> planar float tensors in device memory; arguments outside the rules refuse the whole call */
@@ -1237,20 +1230,14 @@ unsigned int HapGpuDecodeFramesPlanes(HapGpuContext *context, unsigned int frame
                                       const float *scale, const float *bias, unsigned int *results, unsigned int flags)
 {
     const HapbPlanes layout = {channels, element, planeBytes, scale, bias};
-    unsigned r, f;
+    /* (Hap R frames are out of scope with or without the flag that asks for their pictures: the road has no BC7) */
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA8, .scale_log2 = scaleLog2, .planes = &layout};
     if (!context)
         return HapResult_Bad_Arguments;
-    if (!planes_arguments_valid(scaleLog2, channels, element, scale, bias)) {
-        for (f = 0; results && f < frameCount; f++)
-            results[f] = HapResult_Bad_Arguments;
-        return HapResult_Bad_Arguments;
-    }
-    hapgpu_rt_lock(context->rt);
-    /* (Hap R frames are out of scope with or without the flag that asks for their pictures: the road has no BC7) */
-    r = hapb_decode_planes(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, planeFrames, width, height,
-                           scaleLog2, rowBytes, &layout, results, flags);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    if (!planes_arguments_valid(scaleLog2, channels, element, scale, bias))
+        return refuse_call(results, frameCount);
+    return frames_down_road(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, planeFrames, width,
+                            height, rowBytes, results, flags, &road);
 }
 
 /* HapGpuDecodeFramesPlanes of a block-aligned rectangle of every frame, frame f's at (regionXs[f], regionYs[f]); a size
@@ -1267,21 +1254,16 @@ unsigned int HapGpuDecodeFramesPlanesRegion(HapGpuContext *context, unsigned int
 {
     const HapbPlanes layout = {channels, element, planeBytes, scale, bias};
     const HapGpuRegion size = {width, 0u, 0u, regionWidth, regionHeight};
-    unsigned r, f;
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA8, .scale_log2 = scaleLog2, .region = &size,
+                           .region_xs = regionXs, .region_ys = regionYs, .planes = &layout};
     if (!context)
         return HapResult_Bad_Arguments;
+    /* (without origins the road would be the one-rectangle road at (0, 0)) */
     if (!planes_arguments_valid(scaleLog2, channels, element, scale, bias) || !regionXs || !regionYs ||
-        !hapb_region_fits(&size, height)) {
-        for (f = 0; results && f < frameCount; f++)
-            results[f] = HapResult_Bad_Arguments;
-        return HapResult_Bad_Arguments;
-    }
-    hapgpu_rt_lock(context->rt);
-    r = hapb_decode_planes_region(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, planeFrames, width,
-                                  height, regionXs, regionYs, regionWidth, regionHeight, scaleLog2, rowBytes, &layout,
-                                  results, flags);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+        !hapb_region_fits(&size, height))
+        return refuse_call(results, frameCount);
+    return frames_down_road(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, planeFrames, width,
+                            height, rowBytes, results, flags, &road);
 }
 
 /* HapGpuDecodeFramesPlanes of a crop per frame of the scaled picture, at any texel position and size, every one resized
@@ -1299,20 +1281,15 @@ unsigned int HapGpuDecodeFramesPlanesResized(HapGpuContext *context, unsigned in
 {
     const HapbPlanes layout = {channels, element, planeBytes, scale, bias};
     const HapbResize resize = {cropXs, cropYs, cropWidths, cropHeights, outWidth, outHeight};
-    unsigned r, f;
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA8, .scale_log2 = scaleLog2, .planes = &layout,
+                           .resize = &resize};
     if (!context)
         return HapResult_Bad_Arguments;
     if (!planes_arguments_valid(scaleLog2, channels, element, scale, bias) || !cropXs || !cropYs || !cropWidths ||
-        !cropHeights || !hapb_resize_out_valid(&resize)) {
-        for (f = 0; results && f < frameCount; f++)
-            results[f] = HapResult_Bad_Arguments;
-        return HapResult_Bad_Arguments;
-    }
-    hapgpu_rt_lock(context->rt);
-    r = hapb_decode_planes_resized(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, planeFrames, width,
-                                   height, &resize, scaleLog2, rowBytes, &layout, results, flags);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+        !cropHeights || !hapb_resize_out_valid(&resize))
+        return refuse_call(results, frameCount);
+    return frames_down_road(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, planeFrames, width,
+                            height, rowBytes, results, flags, &road);
 }
 
 /* texture(s) -> texture(s) and frames -> frames of another flavour or size, without a picture in between */
@@ -1356,14 +1333,11 @@ unsigned int HapGpuDecodeFramesRGBAHalf(HapGpuContext *context, unsigned int fra
                                         void *const *rgbaHalfFrames, unsigned int width, unsigned int height,
                                         unsigned long rowBytes, unsigned int *results, unsigned int flags)
 {
-    unsigned r;
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA16F};
     if (!context)
         return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_decode_rgba_half(context, frameCount, inputBuffers, inputBuffersBytes, rgbaHalfFrames, width, height,
-                              rowBytes, results, flags);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    return frames_down_road(context, frameCount, inputBuffers, inputBuffersBytes, 1u, rgbaHalfFrames, width, height,
+                            rowBytes, results, flags, &road);
 }
 
 unsigned int HapGpuDecodeFramesAlpha(HapGpuContext *context, unsigned int frameCount,
@@ -1371,14 +1345,11 @@ unsigned int HapGpuDecodeFramesAlpha(HapGpuContext *context, unsigned int frameC
                                      void *const *alphaFrames, unsigned int width, unsigned int height,
                                      unsigned long rowBytes, unsigned int *results, unsigned int flags)
 {
-    unsigned r;
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_A8};
     if (!context)
         return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_decode_alpha(context, frameCount, inputBuffers, inputBuffersBytes, alphaFrames, width, height, rowBytes,
-                          results, flags);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    return frames_down_road(context, frameCount, inputBuffers, inputBuffersBytes, 1u, alphaFrames, width, height,
+                            rowBytes, results, flags, &road);
 }
 
 unsigned int HapGpuJoinChunkGroupsDevice(HapGpuContext *context, unsigned int groupCount,

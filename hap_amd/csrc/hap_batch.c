@@ -8,31 +8,18 @@
  * descriptor arrays of hapgpu_abi.h; every byte of texture payload is moved,
  * compressed or decompressed by HIP kernels.  There is no CPU fallback: when
  * no HIP device is present the functions fail with HapResult_Internal_Error.
+ * Here: frames from textures, pictures and tensors (hapb_encode and the block
+ * encoders before it), textures from frames (hapb_decode), the join on the
+ * device.  What goes on from block textures is hap_pictures.c's.
  *
  * Reference behaviour mirrored here: argument checks and result codes of
  * HapEncode (hap.c:506-604, 355-504) and HapDecode (hap.c:993-1040, 732-930).
  */
-#include "hap_batch.h"
-#include "hap_region.h"
+#include "hap_batch_private.h"
 #include "measurement_guard.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-
-enum {
-    D_FRAMES = 0, D_SLOTS, D_FRAGSIZES, D_COPIES, D_TEX_STAGE, D_FRAME_STAGE, D_BC_TEX, D_RGBA_STAGE,
-    D_JOBS, D_CHUNKS, D_UNITS, D_IN_STAGE, D_OUT_STAGE, D_PTRS, D_PREFIX, D_BC_PTRS
-};
-#define D_GROUPTABLES D_PTRS   /* encode-only arenas in decode-only slots: one call never needs both */
-#define D_PACK D_PREFIX
-#define D_CHUNK_ACC D_JOBS
-#define D_SCAN D_SLOTS       /* ... and the decoder's block-scan arena in an encode-only one */
-#define D_GUESS D_FRAGSIZES  /* ... and the group tables the decoder makes for fragments that came without */
-#define D_TRANSCODED D_RGBA_STAGE /* ... and the textures a transcode call makes, where the calls with pictures stage those: it
-                                     has none, and D_BC_TEX holds its source textures until its encode half is done */
-#define D_MEASURE D_RGBA_STAGE    /* ... and the totals and partial sums of a measuring call: its pictures are never staged */
-#define P_SCAN P_FRAMES
-enum { P_FRAMES = 0, P_JOBS, P_CHUNKS, P_PREFIX, P_PTRS, P_BC_PTRS, P_PREFIX2 };   /* (8, 9: hap_sequence.c) */
 
 #ifdef HAPB_TRACE
 #include <stdio.h>
@@ -46,13 +33,7 @@ static double hapb_now_us(void) { struct timespec ts; clock_gettime(CLOCK_MONOTO
 #define PREFIX_BATCH_MAX_BYTES ((size_t)32u << 20)   /* the longer second prefix, all frames of a call together (x2: a far window each) */
 #define COPY_PIECE 65536u
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-static int is_dev(HapGpuContext *c, const void *p) { return hapgpu_rt_is_device_ptr(c->rt, p); }
-
-/* A context whose last encode call has been begun and not finished (HapGpuEncodeFramesRGBABegin) holds that call's
-   tables and scratch: it takes no other call until HapGpuEncodeFramesFinish. */
-static int context_busy(HapGpuContext *c, unsigned *results, unsigned frame_count)
+int context_busy(HapGpuContext *c, unsigned *results, unsigned frame_count)
 {
     unsigned f;
     if (!c->pending_encode)
@@ -71,10 +52,8 @@ typedef struct tex_geom {
     size_t bound;        /* hap_max_encoded_length for the requested compressor (hap.c:386) */
 } tex_geom;
 
-/* What hapb_encode asks of a call's textures whatever its frames are (reference hap.c:518-559, and per texture
-   hap.c:367-385): Bad_Arguments refuses the whole call.  count 1 or 2. */
-static unsigned encode_textures_valid(unsigned count, const unsigned long *input_bytes, const unsigned *formats,
-                                      const unsigned *compressors, const unsigned *chunk_counts, unsigned flags)
+unsigned encode_textures_valid(unsigned count, const unsigned long *input_bytes, const unsigned *formats,
+                               const unsigned *compressors, const unsigned *chunk_counts, unsigned flags)
 {
     const int smaller = (flags & HAPGPU_ENCODE_SMALLER_FILES) != 0;
     unsigned i;
@@ -825,368 +804,6 @@ unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width
     return HapResult_No_Error;
 }
 
-/* What block textures a road to pictures takes (one block-decode launch per format present in a slice of frames) and
-   which of them may come with an RGTC1 alpha plane. */
-typedef struct picture_road {
-    unsigned kind_count;
-    const unsigned *kinds;
-    unsigned paired_kinds;      /* bit k: kinds[k] may have an alpha plane (textureCount 2) */
-    unsigned picture_kind;      /* HAPGPU_PICTURE_*: the pictures' layout, and with it the size of a texel */
-    unsigned scale_log2;        /* 0: pictures of the frames' size; 1 / 2 (RGBA8 only): half / quarter size, of
-                                   (width >> scale_log2) x (height >> scale_log2), by hapgpu_k_block_decode_scaled */
-    const HapGpuRegion *region; /* NULL: the whole of every texture; else (RGBA8 only, scale_log2 0) pictures of region->w x
-                                   region->h, that rectangle of every texture, by hapgpu_k_block_decode_region */
-    const HapbPlanes *planes;   /* NULL: interleaved pictures of picture_kind; else planar tensors in device memory
-                                   (scale_log2 0 to 2), by hapgpu_k_block_decode_planes: a "texel" is then one
-                                   element of one plane and row_bytes the pitch of a plane's rows.  With a region: tensors
-                                   of (region->w >> scale_log2) x (region->h >> scale_log2), that rectangle of every
-                                   texture, by hapgpu_k_block_decode_planes_region */
-    const unsigned *region_xs, *region_ys;  /* NULL: region->x, region->y for every frame; else (planes only, frames only)
-                                   frame f's rectangle begins at (region_xs[f], region_ys[f]), f counted from the call's
-                                   first frame, and region->x, region->y are 0 */
-    HapGpuPictureError *measure; /* NULL: the pictures are written; else (RGBA8, scale_log2 0, no region, no planes) they
-                                   are reference pictures in device memory and are READ: the launch is
-                                   hapgpu_k_block_measure, and measure[f] gets the sums of frame f against its picture,
-                                   f counted from the call's first frame */
-    const HapbResize *resize;   /* NULL: tensors of the rectangle's or the frames' (scaled) size; else (planes only, no region)
-                                   tensors of resize->out_w x resize->out_h, entry f's crop of the scaled picture resized,
-                                   by hapgpu_k_block_decode_planes_resized */
-} picture_road;
-
-/* RGBA8 pictures (BC7 last: frames of it only with HAPGPU_DECODE_BPTC_PICTURES), RGBA16F ones and A8 ones */
-static const unsigned k_rgba_kinds[4] = {HapTextureFormat_RGB_DXT1, HapTextureFormat_RGBA_DXT5, HapTextureFormat_YCoCg_DXT5,
-                                         HapTextureFormat_RGBA_BPTC_UNORM};
-static const unsigned k_half_kinds[2] = {HapTextureFormat_RGB_BPTC_UNSIGNED_FLOAT, HapTextureFormat_RGB_BPTC_SIGNED_FLOAT};
-static const unsigned k_alpha_kinds[1] = {HapTextureFormat_A_RGTC1};
-
-static picture_road road_of(unsigned picture_kind, unsigned flags, unsigned scale_log2, const HapGpuRegion *region)
-{
-    if (picture_kind == HAPGPU_PICTURE_RGBA16F)
-        return (picture_road){2u, k_half_kinds, 0u, picture_kind, 0u, NULL, NULL, NULL, NULL};
-    if (picture_kind == HAPGPU_PICTURE_A8)
-        return (picture_road){1u, k_alpha_kinds, 0u, picture_kind, 0u, NULL, NULL, NULL, NULL};
-    return (picture_road){(flags & HAPGPU_DECODE_BPTC_PICTURES) ? 4u : 3u, k_rgba_kinds, 0x7u, picture_kind,
-                          region ? 0u : scale_log2, region, NULL, NULL, NULL};
-}
-
-/* ... and to planar tensors: the RGBA8 road's DXT formats (never BC7) at any of the three sizes */
-static picture_road planes_road_of(unsigned scale_log2, const HapbPlanes *planes)
-{
-    return (picture_road){3u, k_rgba_kinds, 0x7u, HAPGPU_PICTURE_RGBA8, scale_log2, NULL, planes, NULL, NULL};
-}
-
-/* ... and to nothing: the RGBA8 road's DXT formats (never BC7) against reference pictures, the sums to `errors` */
-static picture_road measure_road_of(HapGpuPictureError *errors)
-{
-    return (picture_road){3u, k_rgba_kinds, 0x7u, HAPGPU_PICTURE_RGBA8, 0u, NULL, NULL, NULL, NULL, errors};
-}
-
-/* a measuring road's device scratch for `pictures` pictures: [pictures][8] 64-bit totals, then the workgroups' partials */
-static unsigned long long *measure_scratch(hapgpu_rt *rt, unsigned pictures, unsigned width, unsigned height,
-                                           uint32_t **partials)
-{
-    const size_t totals_bytes = align_up(sizeof(unsigned long long) * 8u * pictures, 256);
-    uint8_t *s = (uint8_t *)hapgpu_rt_device_scratch(rt, D_MEASURE, totals_bytes +
-                                                     hapgpu_block_measure_partial_bytes(width, height) * pictures);
-    *partials = s ? (uint32_t *)(s + totals_bytes) : NULL;
-    return (unsigned long long *)s;
-}
-
-/* a picture's eight totals (sse R, G, B, A, then sad) as the caller's struct */
-static void measure_result(HapGpuPictureError *error, const unsigned long long *totals, unsigned width, unsigned height)
-{
-    unsigned c;
-    for (c = 0; c < 4u; c++) {
-        error->sse[c] = totals[c];
-        error->sad[c] = totals[4u + c];
-    }
-    error->texels = (unsigned long long)width * height;
-}
-
-/* ... of a rectangle of every texture: region's for all (xs and ys NULL), or region's size at an origin per frame */
-static picture_road planes_region_road_of(unsigned scale_log2, const HapbPlanes *planes, const HapGpuRegion *region,
-                                          const unsigned *xs, const unsigned *ys)
-{
-    return (picture_road){3u, k_rgba_kinds, 0x7u, HAPGPU_PICTURE_RGBA8, scale_log2, region, planes, xs, ys};
-}
-
-/* ... of a crop per entry at any texel position and size of the scaled picture, resized to one output size */
-static picture_road planes_resized_road_of(unsigned scale_log2, const HapbPlanes *planes, const HapbResize *resize)
-{
-    return (picture_road){3u, k_rgba_kinds, 0x7u, HAPGPU_PICTURE_RGBA8, scale_log2, NULL, planes, NULL, NULL, NULL, resize};
-}
-
-int hapb_resize_out_valid(const HapbResize *resize)
-{
-    return resize->out_w >= 1u && resize->out_w <= 16384u && resize->out_h >= 1u && resize->out_h <= 16384u;
-}
-
-int hapb_resize_region(const HapbResize *resize, size_t f, unsigned width, unsigned height, unsigned scale_log2,
-                       HapGpuRegion *region)
-{
-    const unsigned x = resize->xs[f], y = resize->ys[f], w = resize->ws[f], h = resize->hs[f];
-    const unsigned level_w = width >> scale_log2, level_h = height >> scale_log2;
-    if (scale_log2 > 2u || w == 0u || h == 0u || x > level_w || w > level_w - x || y > level_h || h > level_h - y ||
-        w > 4u * resize->out_w || h > 4u * resize->out_h)
-        return 0;
-    /* (outward to the grid: width and height are multiples of 4, so the far edges stay inside) */
-    region->width = width;
-    region->x = (x << scale_log2) & ~3u;
-    region->y = (y << scale_log2) & ~3u;
-    region->w = ((((x + w) << scale_log2) + 3u) & ~3u) - region->x;
-    region->h = ((((y + h) << scale_log2) + 3u) & ~3u) - region->y;
-    return hapb_region_fits(region, height);
-}
-
-/* bytes of what a road's row_bytes counts: a texel of an interleaved picture, an element of a plane */
-static size_t picture_texel_bytes(const picture_road *road)
-{
-    if (road->planes)
-        return road->planes->element == HapGpuPlaneElement_F32 ? 4u : 2u;
-    return HAPGPU_PICTURE_TEXEL_BYTES(road->picture_kind);
-}
-
-/* the geometry of a road's pictures, from the textures' */
-static unsigned picture_width_of(const picture_road *road, unsigned width)
-{
-    if (road->resize)
-        return road->resize->out_w;
-    return (road->region ? road->region->w : width) >> road->scale_log2;
-}
-
-static unsigned picture_height_of(const picture_road *road, unsigned height)
-{
-    if (road->resize)
-        return road->resize->out_h;
-    return (road->region ? road->region->h : height) >> road->scale_log2;
-}
-
-/* 1: the region is a block-aligned rectangle inside width x height (hap_region.h's rules and the texture's height) */
-int hapb_region_fits(const HapGpuRegion *region, unsigned height)
-{
-    return hap_region_geometry_valid(region->width, region->x, region->y, region->w, region->h) && region->y <= height &&
-           region->h <= height - region->y;
-}
-
-/* what the block decoders ask of a picture's address (in device memory) and row pitch when they write it: 16-byte
-   stores for RGBA8 and RGBA16F; A8 pictures take dword stores, and 16-byte ones where address and pitch allow; a scaled
-   picture takes the 16 >> scale_log2 bytes a lane has for each of its rows, a plane its 4 >> scale_log2 elements -- or,
-   resized, the one element a lane stores */
-static unsigned picture_align_mask(const picture_road *road)
-{
-    if (road->resize)
-        return (unsigned)picture_texel_bytes(road) - 1u;
-    if (road->planes)
-        return (4u >> road->scale_log2) * (unsigned)picture_texel_bytes(road) - 1u;
-    if (road->scale_log2)
-        return (16u >> road->scale_log2) - 1u;
-    return road->picture_kind == HAPGPU_PICTURE_A8 ? 3u : 15u;
-}
-
-/* 1: a planar road's tensors are what the calls take (include/hap_gpu.h: HapGpuDecompressPlanes) -- planes that hold
-   their rows and, like the rows, keep every lane's store aligned; pixel_row: the bytes of one row of a plane */
-static int planes_fit(const picture_road *road, size_t pixel_row, unsigned picture_height, unsigned long row_bytes)
-{
-    const HapbPlanes *p = road->planes;
-    return p->channels >= 3u && p->channels <= 4u && p->element <= HapGpuPlaneElement_F32 && road->scale_log2 <= 2u &&
-           p->scale && p->bias && picture_height && !(p->plane_bytes & picture_align_mask(road)) &&
-           p->plane_bytes >= (size_t)row_bytes * (picture_height - 1u) + pixel_row;
-}
-
-/* the texture block a rectangle begins at */
-static uint32_t region_first_block(unsigned width, unsigned x, unsigned y)
-{
-    return (uint32_t)((y / 4u) * (width / 4u) + x / 4u);
-}
-
-/* the block-decode launch of a road: pictures of the frames' size, scaled ones, a rectangle's, or planar tensors (the
-   alpha plane is read only where a fourth plane is written).  origins: a planar road with a rectangle per frame -- the
-   device array of the pictures' first blocks, or, resized, of their crops (four words each; NULL: the road's first crop
-   for all); partials, totals: a measuring road's scratch (measure_scratch) */
-static int launch_block_decode(hapgpu_rt *rt, const picture_road *road, const HapGpuPictureTable *t, unsigned pictures,
-                               int with_alpha, unsigned width, unsigned height, unsigned format, size_t row_bytes, int wide,
-                               const uint32_t *origins, uint32_t *partials, unsigned long long *totals)
-{
-    /* (a measuring road: the block kernel with the pictures as its third column, read, and the reduction behind it) */
-    if (road->measure)
-        return hapgpu_k_block_measure(rt, t, pictures, with_alpha, width, height, format, row_bytes, partials, totals);
-    if (road->resize) {
-        const unsigned crop[4] = {road->resize->xs[0], road->resize->ys[0], road->resize->ws[0], road->resize->hs[0]};
-        return hapgpu_k_block_decode_planes_resized(rt, t, pictures, with_alpha && road->planes->channels == 4u, width, height,
-                                                    format, origins, origins ? NULL : crop, road->resize->out_w,
-                                                    road->resize->out_h, road->scale_log2, road->planes->channels,
-                                                    road->planes->element, road->planes->plane_bytes, row_bytes,
-                                                    road->planes->scale, road->planes->bias);
-    }
-    if (road->planes && road->region)
-        return hapgpu_k_block_decode_planes_region(rt, t, pictures, with_alpha && road->planes->channels == 4u, width, height,
-                                                   format, origins,
-                                                   origins ? 0u : region_first_block(width, road->region->x, road->region->y),
-                                                   road->region->w, road->region->h, road->scale_log2, road->planes->channels,
-                                                   road->planes->element, road->planes->plane_bytes, row_bytes,
-                                                   road->planes->scale, road->planes->bias);
-    if (road->planes)
-        return hapgpu_k_block_decode_planes(rt, t, pictures, with_alpha && road->planes->channels == 4u, width, height, format,
-                                            road->scale_log2, road->planes->channels, road->planes->element,
-                                            road->planes->plane_bytes, row_bytes, road->planes->scale, road->planes->bias);
-    if (road->region)
-        return hapgpu_k_block_decode_region(rt, t, pictures, with_alpha, width, height, format, road->region->x, road->region->y,
-                                            road->region->w, road->region->h, row_bytes);
-    if (road->scale_log2)
-        return hapgpu_k_block_decode_scaled(rt, t, pictures, with_alpha, width, height, format, road->scale_log2, row_bytes);
-    return hapgpu_k_block_decode(rt, t, pictures, with_alpha, width, height, format, row_bytes, wide, road->picture_kind);
-}
-
-/* one texture (+ RGTC1 alpha plane) down a road: to one picture, or to one planar tensor */
-static unsigned decompress_picture(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
-                                   const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                                   void *picture, unsigned long row_bytes, const picture_road *const proad)
-{
-    const picture_road road = *proad;
-    const unsigned picture_kind = road.picture_kind;
-    const unsigned align = picture_align_mask(&road);
-    hapgpu_rt *rt = ctx->rt;
-    /* (the picture's geometry: the texture's, a scaled road's fraction of it, or the rectangle's) */
-    const unsigned picture_height = picture_height_of(&road, height);
-    const size_t block = hapf_block_bytes(format),
-                 pixel_row = (size_t)picture_width_of(&road, width) * picture_texel_bytes(&road);
-    HapGpuPictureTable t = {{NULL, NULL, NULL}, {0u, 0u, 0u}};
-    size_t need, alpha_need, picture_bytes;
-    const void *src = texture, *asrc = alpha;
-    void *dst = picture;
-    uint32_t *partials = NULL;
-    unsigned long long *totals = NULL, *htotals = NULL;
-    HapGpuRegion resized;       /* (a resized road's crop as a rectangle of blocks: only asked whether there is one) */
-    unsigned k;
-    int rc;
-    if (context_busy(ctx, NULL, 0))
-        return HapResult_Internal_Error;
-    for (k = 0; k < road.kind_count && road.kinds[k] != format; k++)
-        ;
-    if (!texture || !picture || width == 0 || height == 0 || (width & 3u) || (height & 3u) || row_bytes < pixel_row ||
-        (road.region && (road.region->width != width || !hapb_region_fits(road.region, height))) ||
-        (road.resize && (!hapb_resize_out_valid(road.resize) ||
-                         !hapb_resize_region(road.resize, 0u, width, height, road.scale_log2, &resized))) ||
-        k == road.kind_count || (alpha && !(road.paired_kinds >> k & 1u)) ||
-        /* (tensors live in device memory: no host staging road) */
-        (road.planes && (!planes_fit(&road, pixel_row, picture_height, row_bytes) || !is_dev(ctx, picture))) ||
-        /* (and so do reference pictures) */
-        (road.measure && !is_dev(ctx, picture)))
-        return HapResult_Bad_Arguments;
-    need = (size_t)(width / 4u) * (height / 4u) * block;
-    alpha_need = (size_t)(width / 4u) * (height / 4u) * 8u;
-    if (texture_bytes < need || (alpha && alpha_bytes < alpha_need))
-        return HapResult_Bad_Arguments;
-    /* rows a multiple of 16 bytes; device textures aligned to their blocks, alpha planes to 8 bytes, pictures to 16
-       (A8 pictures: rows and device pictures to 4 bytes, and at most 65535 block rows; scaled pictures: rows and device
-       pictures to 8 bytes at half, 4 at quarter size) */
-    if ((row_bytes & align) || (is_dev(ctx, texture) && ((uintptr_t)texture & (block - 1u))) ||
-        (alpha && is_dev(ctx, alpha) && ((uintptr_t)alpha & 7u)) || (is_dev(ctx, picture) && ((uintptr_t)picture & align)) ||
-        (picture_kind == HAPGPU_PICTURE_A8 && height / 4u > 65535u))
-        return HapResult_Bad_Arguments;
-    picture_bytes = (size_t)row_bytes * (picture_height - 1u) + pixel_row;
-    if (!is_dev(ctx, texture)) {
-        void *s = hapgpu_rt_device_scratch(rt, D_BC_TEX, need + alpha_need + 256);
-        if (!s || hapgpu_rt_h2d(rt, s, texture, need))
-            return HapResult_Internal_Error;
-        src = s;
-        if (alpha && !is_dev(ctx, alpha)) {
-            uint8_t *a = (uint8_t *)s + align_up(need, 256);
-            if (hapgpu_rt_h2d(rt, a, alpha, alpha_need))
-                return HapResult_Internal_Error;
-            asrc = a;
-        }
-    } else if (alpha && !is_dev(ctx, alpha)) {
-        void *a = hapgpu_rt_device_scratch(rt, D_BC_TEX, alpha_need);
-        if (!a || hapgpu_rt_h2d(rt, a, alpha, alpha_need))
-            return HapResult_Internal_Error;
-        asrc = a;
-    }
-    if (!is_dev(ctx, picture)) {
-        dst = hapgpu_rt_device_scratch(rt, D_RGBA_STAGE, picture_bytes);
-        if (!dst)
-            return HapResult_Internal_Error;
-    }
-    t.one[0] = (uint64_t)(uintptr_t)src;
-    t.one[1] = (uint64_t)(uintptr_t)asrc;
-    t.one[2] = (uint64_t)(uintptr_t)dst;
-    if (road.measure) {
-        /* (after the textures' scratch: growing an arena waits for the stream, not for copies yet to be issued) */
-        totals = measure_scratch(rt, 1u, width, height, &partials);
-        htotals = (unsigned long long *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, sizeof(*htotals) * 8u);
-        if (!totals || !htotals)
-            return HapResult_Internal_Error;
-    }
-    rc = launch_block_decode(rt, &road, &t, 1u, alpha != NULL, width, height, format, row_bytes,
-                             (((uintptr_t)dst | row_bytes) & 15u) == 0 && !ctx->no_wide_planes, NULL, partials, totals);
-    if (rc == 1)
-        return HapResult_Bad_Arguments;
-    if (rc)
-        return HapResult_Internal_Error;
-    if (road.measure) {
-        if (hapgpu_rt_d2h(rt, htotals, totals, sizeof(*htotals) * 8u) || hapgpu_rt_sync(rt))
-            return HapResult_Internal_Error;
-        measure_result(road.measure, htotals, width, height);
-        return HapResult_No_Error;
-    }
-    /* (row by row when the client's rows are longer than the picture's: what lies between them is not ours) */
-    if (dst != picture && (row_bytes == pixel_row ? hapgpu_rt_d2h(rt, picture, dst, picture_bytes)
-                                                  : hapgpu_rt_d2h_rows(rt, picture, row_bytes, dst, row_bytes, pixel_row,
-                                                                       picture_height)))
-        return HapResult_Internal_Error;
-    if (hapgpu_rt_sync(rt))
-        return HapResult_Internal_Error;
-    return HapResult_No_Error;
-}
-
-unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
-                              const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                              void *picture, unsigned long row_bytes, unsigned picture_kind, unsigned scale_log2,
-                              const HapGpuRegion *region)
-{
-    const picture_road road = road_of(picture_kind, HAPGPU_DECODE_BPTC_PICTURES, scale_log2, region);
-    return decompress_picture(ctx, texture, texture_bytes, format, alpha, alpha_bytes, width, height, picture, row_bytes,
-                              &road);
-}
-
-unsigned hapb_decompress_planes(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
-                                const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                                unsigned scale_log2, void *tensor, unsigned long row_bytes, const HapbPlanes *planes)
-{
-    const picture_road road = planes_road_of(scale_log2, planes);
-    return decompress_picture(ctx, texture, texture_bytes, format, alpha, alpha_bytes, width, height, tensor, row_bytes,
-                              &road);
-}
-
-/* one texture (+ RGTC1 alpha plane) against its RGBA8 reference picture in device memory */
-unsigned hapb_measure_texture(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
-                              const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                              const void *rgba, unsigned long row_bytes, HapGpuPictureError *error)
-{
-    const picture_road road = measure_road_of(error);
-    return decompress_picture(ctx, texture, texture_bytes, format, alpha, alpha_bytes, width, height, (void *)(uintptr_t)rgba,
-                              row_bytes, &road);
-}
-
-unsigned hapb_decompress_planes_region(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
-                                       const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                                       const HapGpuRegion *region, unsigned scale_log2, void *tensor,
-                                       unsigned long row_bytes, const HapbPlanes *planes)
-{
-    const picture_road road = planes_region_road_of(scale_log2, planes, region, NULL, NULL);
-    return decompress_picture(ctx, texture, texture_bytes, format, alpha, alpha_bytes, width, height, tensor, row_bytes,
-                              &road);
-}
-
-unsigned hapb_decompress_planes_resized(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
-                                        const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                                        const HapbResize *resize, unsigned scale_log2, void *tensor,
-                                        unsigned long row_bytes, const HapbPlanes *planes)
-{
-    const picture_road road = planes_resized_road_of(scale_log2, planes, resize);
-    return decompress_picture(ctx, texture, texture_bytes, format, alpha, alpha_bytes, width, height, tensor, row_bytes,
-                              &road);
-}
 
 unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
                           unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
@@ -2287,958 +1904,6 @@ fail_alloc:
     free(plans); free(readers); free(fetchers); free(in_off); free(out_off); free(job_of_frame);
     free(in_dev); free(out_dev); free(client_marks); free(guess_frame);
     return HapResult_Internal_Error;
-}
-
-/* ============================================================= frames to pixels */
-/* Hap frames -> RGBA8 pictures with nothing but frames going in and pixels coming out: the second stage of a slice of
-   frames is undone into a scratch of block textures (one batch through hapb_decode: texture 0, and the RGTC1 alpha
-   plane of Hap Q Alpha frames), then every picture is expanded by the block decoder on the same stream.  What a
-   player without texture sampling of its own asks of a Hap decoder (the reference leaves this step to the GPU's
-   texture units, hap.h:92-95 "the texture format the frame decodes to"). */
-#define RGBA_SLICE_BYTES ((size_t)4u << 30)     /* block textures held at a time */
-#define PICTURE_KINDS_MAX 4u                    /* texture formats one road decodes */
-
-/* The second stage of a slice of a call's frames into texture scratch, for the roads that go on from block textures
-   (decode_pictures, hapb_transcode).  Entry f * texture_count + t is texture t of the slice's frame f: the colour texture
-   at per_frame * f of the slice's D_BC_TEX scratch, the RGTC1 alpha plane at + alpha_off, both 256-byte aligned. */
-typedef struct slice_textures {
-    unsigned texture_count, width, height;
-    size_t blocks, alpha_off, per_frame;    /* blocks of a texture; the scratch layout */
-    size_t slice;                           /* frames of a slice at most */
-    /* per entry, one allocation (`in` is its start): what hapb_decode is given ... */
-    const void **in;
-    unsigned long *in_bytes, *caps;
-    unsigned *idx;
-    HapGpuRegion *decode_regions;           /* (a call with a rectangle per frame; else NULL) */
-    /* ... and what it gives back: the texture's address, bytes, format and result */
-    void **outs;
-    unsigned long *used;
-    unsigned *fmts, *res;
-} slice_textures;
-
-/* extra_per_frame: what else the caller holds per frame while a slice's textures are held; rectangles != 0: room for a
-   rectangle per entry.  0: out of memory */
-static int slice_textures_init(slice_textures *s, unsigned frame_count, unsigned texture_count, unsigned width,
-                               unsigned height, size_t extra_per_frame, int rectangles)
-{
-    size_t entries;
-    s->texture_count = texture_count;
-    s->width = width;
-    s->height = height;
-    s->blocks = (size_t)(width / 4u) * (height / 4u);
-    s->alpha_off = align_up(s->blocks * 16u, 256);
-    s->per_frame = s->alpha_off + (texture_count == 2 ? align_up(s->blocks * 8u, 256) : 0u);
-    s->slice = RGBA_SLICE_BYTES / (s->per_frame + extra_per_frame);
-    if (s->slice == 0)
-        s->slice = 1;
-    if (s->slice > frame_count)
-        s->slice = frame_count;
-    if (s->slice * texture_count > 32768u)
-        s->slice = 32768u / texture_count;
-    entries = s->slice * texture_count;
-    s->in = (const void **)malloc(entries * (2u * sizeof(void *) + 3u * sizeof(unsigned long) + 3u * sizeof(unsigned) +
-                                             (rectangles ? sizeof(HapGpuRegion) : 0u)));
-    if (!s->in)
-        return 0;
-    s->outs = (void **)(s->in + entries);
-    s->in_bytes = (unsigned long *)(s->outs + entries);
-    s->caps = s->in_bytes + entries;
-    s->used = s->caps + entries;
-    s->idx = (unsigned *)(s->used + entries);
-    s->fmts = s->idx + entries;
-    s->res = s->fmts + entries;
-    s->decode_regions = rectangles ? (HapGpuRegion *)(s->res + entries) : NULL;
-    return 1;
-}
-
-/* Frames done .. done + n of the call (n <= s->slice) into `textures`, per_frame * n bytes of D_BC_TEX scratch.  region
-   (NULL: whole textures): the rectangle wanted of every frame -- or, with xs and ys, its size alone, frame f's origin being
-   (xs[f], ys[f]): a frame whose origin puts the rectangle off the grid or past an edge goes to hapb_decode with a NULL
-   input, its Bad_Arguments, and nothing of it is decoded.  resize (NULL, or region NULL): frame f's rectangle is its crop
-   at scale_log2 rounded outward to the blocks (hapb_resize_region), and a crop that is none refuses its frame alike. */
-static void slice_textures_decode(HapGpuContext *ctx, const slice_textures *s, uint8_t *textures, const void *const *inputs,
-                                  const unsigned long *input_bytes, size_t done, unsigned n, const HapGpuRegion *region,
-                                  const unsigned *xs, const unsigned *ys, const HapbResize *resize, unsigned scale_log2,
-                                  unsigned flags)
-{
-    const unsigned width = s->width, height = s->height;
-    const HapGpuRegion whole = {width, 0u, 0u, width, height};
-    HapbDecodeArgs args = {s->idx, NULL, NULL, 0, NULL, 0u, NULL, NULL};
-    unsigned f, t;
-    int any_skip = 0;
-    for (f = 0; f < n; f++) {
-        /* (frame done + f of the call: the origins are the call's, not the slice's) */
-        HapGpuRegion own = whole;
-        int refused = 0;
-        if (xs) {
-            own.x = xs[done + f];
-            own.y = ys[done + f];
-            own.w = region->w;
-            own.h = region->h;
-            refused = !hapb_region_fits(&own, height);
-            if (refused)
-                own = whole;
-            else if (own.x != 0u || own.y != 0u || own.w != width || own.h != height)
-                any_skip = 1;
-        } else if (resize) {
-            refused = !hapb_resize_region(resize, done + f, width, height, scale_log2, &own);
-            if (refused)
-                own = whole;
-            else if (own.x != 0u || own.y != 0u || own.w != width || own.h != height)
-                any_skip = 1;
-        }
-        for (t = 0; t < s->texture_count; t++) {
-            const size_t e = (size_t)f * s->texture_count + t;
-            if (s->decode_regions)
-                s->decode_regions[e] = own;
-            s->in[e] = refused ? NULL : inputs[done + f];
-            s->in_bytes[e] = input_bytes[done + f];
-            s->outs[e] = textures + s->per_frame * f + (t ? s->alpha_off : 0u);
-            s->caps[e] = (unsigned long)(t ? s->blocks * 8u : s->blocks * 16u);
-            s->idx[e] = t;
-            s->used[e] = 0;
-            s->fmts[e] = 0;
-        }
-    }
-    /* (rectangles that are all the whole frame skip nothing -- one that is among others needs everything -- and nor does
-       one rectangle for all that is the whole frame) */
-    if (xs || resize)
-        args.regions = any_skip ? s->decode_regions : NULL;
-    else if (region && !(region->x == 0u && region->y == 0u && region->w == width && region->h == height))
-        args.region = region;
-    hapb_decode(ctx, n * s->texture_count, s->in, s->in_bytes, 0, s->outs, s->caps, s->used, s->fmts, s->res,
-                flags & ~HAPGPU_DECODE_BPTC_PICTURES, &args);
-}
-
-static unsigned decode_pictures(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                                const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
-                                unsigned width, unsigned height, unsigned long row_bytes, unsigned *results,
-                                unsigned flags, const picture_road *road)
-{
-    hapgpu_rt *rt = ctx->rt;
-    size_t rgba_bytes, done;
-    unsigned first_error = HapResult_No_Error, f;
-    slice_textures s;
-    /* (the pictures' geometry: the frames', a scaled road's fraction of it, or the rectangle's) */
-    const unsigned picture_height = picture_height_of(road, height);
-    const size_t pixel_row = (size_t)picture_width_of(road, width) * picture_texel_bytes(road);
-    const unsigned align = picture_align_mask(road);
-    const int per_frame_regions = road->region_xs != NULL || road->resize != NULL;
-    const size_t frame_words = road->resize ? 4u : 1u;      /* what travels behind the table per frame */
-    if (frame_count == 0)
-        return HapResult_No_Error;
-    if (!results)
-        return HapResult_Bad_Arguments;
-    if (context_busy(ctx, results, frame_count))
-        return HapResult_Internal_Error;
-    if (!inputs || !input_bytes || !rgba_frames || texture_count == 0 || texture_count > 2 || width == 0 ||
-        height == 0 || (width & 3u) || (height & 3u) || row_bytes < pixel_row || (row_bytes & align) ||
-        (road->region && (road->region->width != width || !hapb_region_fits(road->region, height))) ||
-        (road->resize && (!hapb_resize_out_valid(road->resize) || !road->resize->xs || !road->resize->ys ||
-                          !road->resize->ws || !road->resize->hs)) ||
-        (road->planes && !planes_fit(road, pixel_row, picture_height, row_bytes)) ||
-        (road->picture_kind == HAPGPU_PICTURE_A8 && height / 4u > 65535u)) {
-        for (f = 0; f < frame_count; f++)
-            results[f] = HapResult_Bad_Arguments;
-        return HapResult_Bad_Arguments;
-    }
-    /* (a measuring road: a frame that is not measured has an all-zero struct) */
-    if (road->measure)
-        memset(road->measure, 0, sizeof(*road->measure) * frame_count);
-    rgba_bytes = (size_t)row_bytes * (picture_height - 1u) + pixel_row;
-    if (!slice_textures_init(&s, frame_count, texture_count, width, height, 0u, per_frame_regions)) {
-        for (f = 0; f < frame_count; f++)
-            results[f] = HapResult_Internal_Error;
-        return HapResult_Internal_Error;
-    }
-    for (done = 0; done < frame_count; done += s.slice) {
-        const unsigned n = (unsigned)(frame_count - done < s.slice ? frame_count - done : s.slice);
-        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, s.per_frame * n);
-        uint8_t *stage = NULL;
-        const unsigned long long *htotals_of_slice = NULL;
-        int rc = 0;
-        if (!textures) {
-            for (f = 0; f < n; f++)
-                results[done + f] = HapResult_Internal_Error;
-            first_error = first_error ? first_error : HapResult_Internal_Error;
-            continue;
-        }
-        slice_textures_decode(ctx, &s, textures, inputs, input_bytes, done, n, road->region, road->region_xs, road->region_ys,
-                              road->resize, road->scale_log2, flags);
-        {
-            /* one block-decode launch per texture format present in the slice: [textures][alpha planes][pictures] in a
-               small device table, pictures of other formats (or that failed) with a texture address of 0 */
-            /* ... and behind the table, in the same copy, a rectangle per frame's first texture block of every picture -- or,
-               resized, every picture's crop: four words, x, y, w, h */
-            /* ... and, in the pinned copy alone, a measuring road's totals of every picture on their way back */
-            const size_t ptr_words = (size_t)3u * PICTURE_KINDS_MAX * n;
-            const size_t tab_bytes = sizeof(uint64_t) * ptr_words + (per_frame_regions ? sizeof(uint32_t) * frame_words * n : 0u);
-            const size_t totals_bytes = road->measure ? sizeof(unsigned long long) * 8u * n : 0u;
-            uint64_t *htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, align_up(tab_bytes, 8) + totals_bytes);
-            uint64_t *dtab = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, tab_bytes);
-            uint32_t *partials = NULL;
-            unsigned long long *totals = road->measure ? measure_scratch(rt, n, width, height, &partials) : NULL;
-            const unsigned long long *htotals = htab ? (const unsigned long long *)((const uint8_t *)htab + align_up(tab_bytes, 8)) : NULL;
-            uint32_t *horigins = per_frame_regions && htab ? (uint32_t *)(htab + ptr_words) : NULL;
-            const uint32_t *dorigins = per_frame_regions && dtab ? (const uint32_t *)(dtab + ptr_words) : NULL;
-            unsigned present = 0, k;
-            int wide = (row_bytes & 15u) == 0 && !ctx->no_wide_planes;      /* A8 pictures: every one of the slice 16-byte aligned, and the pitch */
-            if (!htab || !dtab || (road->measure && !totals)) {
-                for (f = 0; f < n; f++)
-                    results[done + f] = HapResult_Internal_Error;
-                first_error = first_error ? first_error : HapResult_Internal_Error;
-                continue;
-            }
-            memset(htab, 0, tab_bytes);
-            for (f = 0; f < n; f++) {
-                const size_t e = (size_t)f * texture_count;
-                const unsigned fmt = s.fmts[e];
-                void *dst = rgba_frames[done + f];
-                unsigned r = s.res[e];
-                for (k = 0; k < road->kind_count && road->kinds[k] != fmt; k++)
-                    ;
-                if (r == HapResult_No_Error && texture_count == 2)
-                    r = s.res[e + 1];
-                /* (no Hap variant pairs a BC7 texture with a second one) */
-                if (texture_count == 2 && s.res[e] == HapResult_No_Error && k < road->kind_count && !(road->paired_kinds >> k & 1u))
-                    r = HapResult_Bad_Arguments;
-                if (r == HapResult_No_Error && !dst)
-                    r = HapResult_Bad_Arguments;
-                /* the frame must hold what the caller's geometry says: a colour texture of the road (BC7 only when the
-                   caller asked for Hap R pictures), of exactly width x height, and (two textures) an RGTC1 plane of the
-                   same geometry */
-                if (r == HapResult_No_Error &&
-                    (k == road->kind_count ||
-                     s.used[e] != s.blocks * hapf_block_bytes(fmt) ||
-                     (texture_count == 2 && (s.fmts[e + 1] != HapTextureFormat_A_RGTC1 || s.used[e + 1] != s.blocks * 8u))))
-                    r = HapResult_Bad_Arguments;
-                if (r == HapResult_No_Error && (road->planes || road->measure) && !is_dev(ctx, dst)) {
-                    r = HapResult_Bad_Arguments;        /* tensors and reference pictures live in device memory: no host staging road */
-                } else if (r == HapResult_No_Error && !is_dev(ctx, dst)) {
-                    if (!stage)
-                        stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_RGBA_STAGE, align_up(rgba_bytes, 256) * n);
-                    dst = stage ? stage + align_up(rgba_bytes, 256) * f : NULL;
-                    if (!dst)
-                        r = HapResult_Internal_Error;
-                } else if (r == HapResult_No_Error && ((uintptr_t)dst & align)) {
-                    r = HapResult_Bad_Arguments;
-                }
-                if (r == HapResult_No_Error) {
-                    present |= 1u << k;
-                    if ((uintptr_t)dst & 15u)
-                        wide = 0;
-                    htab[(size_t)k * 3u * n + f] = (uint64_t)(uintptr_t)s.outs[e];
-                    htab[(size_t)k * 3u * n + n + f] = texture_count == 2 ? (uint64_t)(uintptr_t)s.outs[e + 1] : 0u;
-                    htab[(size_t)k * 3u * n + 2u * n + f] = (uint64_t)(uintptr_t)dst;
-                    if (horigins && road->resize) {     /* (a crop of the frame: a refused one never gets here) */
-                        horigins[4u * f] = road->resize->xs[done + f];
-                        horigins[4u * f + 1u] = road->resize->ys[done + f];
-                        horigins[4u * f + 2u] = road->resize->ws[done + f];
-                        horigins[4u * f + 3u] = road->resize->hs[done + f];
-                    } else if (horigins) {              /* (inside the frame: a refused origin never gets here) */
-                        horigins[f] = region_first_block(width, road->region_xs[done + f], road->region_ys[done + f]);
-                    }
-                }
-                results[done + f] = r;
-            }
-            if (present) {
-                rc |= hapgpu_rt_h2d(rt, dtab, htab, tab_bytes);
-                for (k = 0; k < road->kind_count; k++)
-                    if (present & (1u << k)) {
-                        const uint64_t *col = dtab + (size_t)k * 3u * n;
-                        const HapGpuPictureTable t = {{col, col + n, col + 2u * (size_t)n}, {0u, 0u, 0u}};
-                        rc |= launch_block_decode(rt, road, &t, n, texture_count == 2, width, height, road->kinds[k], row_bytes,
-                                                  wide, dorigins, partials, totals);
-                    }
-                if (road->measure) {
-                    rc |= hapgpu_rt_d2h(rt, (void *)htotals, totals, totals_bytes);
-                    htotals_of_slice = htotals;
-                }
-                for (f = 0; f < n; f++)
-                    if (results[done + f] == HapResult_No_Error && stage && !is_dev(ctx, rgba_frames[done + f])) {
-                        /* (row by row when the client's rows are longer than the picture's: what lies between them -- the
-                           rest of a larger image, perhaps -- is not this call's to overwrite) */
-                        if (row_bytes == pixel_row)
-                            rc |= hapgpu_rt_d2h(rt, rgba_frames[done + f], stage + align_up(rgba_bytes, 256) * f, rgba_bytes);
-                        else
-                            rc |= hapgpu_rt_d2h_rows(rt, rgba_frames[done + f], row_bytes, stage + align_up(rgba_bytes, 256) * f, row_bytes,
-                                                     pixel_row, picture_height);
-                    }
-            }
-        }
-        rc |= hapgpu_rt_sync(rt);
-        if (rc)
-            for (f = 0; f < n; f++)
-                if (results[done + f] == HapResult_No_Error)
-                    results[done + f] = HapResult_Internal_Error;
-        /* (the totals have arrived: every picture of a launch got its own eight) */
-        if (road->measure && htotals_of_slice)
-            for (f = 0; f < n; f++)
-                if (results[done + f] == HapResult_No_Error)
-                    measure_result(&road->measure[done + f], htotals_of_slice + 8u * (size_t)f, width, height);
-        for (f = 0; f < n; f++)
-            if (results[done + f] != HapResult_No_Error && first_error == HapResult_No_Error)
-                first_error = results[done + f];
-    }
-    free(s.in);
-    return first_error;
-}
-
-unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                          const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
-                          unsigned width, unsigned height, unsigned scale_log2, unsigned long row_bytes, unsigned *results,
-                          unsigned flags)
-{
-    const picture_road road = road_of(HAPGPU_PICTURE_RGBA8, flags, scale_log2, NULL);
-    return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, rgba_frames, width, height, row_bytes,
-                           results, flags, &road);
-}
-
-/* ... and a rectangle of every frame to pictures of the rectangle's size: the same road with the region block decoder,
-   and a second stage that leaves out what holds none of the rectangle's blocks */
-unsigned hapb_decode_rgba_region(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                                 const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
-                                 unsigned width, unsigned height, const HapGpuRegion *region, unsigned long row_bytes,
-                                 unsigned *results, unsigned flags)
-{
-    const picture_road road = road_of(HAPGPU_PICTURE_RGBA8, flags, 0u, region);
-    return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, rgba_frames, width, height, row_bytes,
-                           results, flags, &road);
-}
-
-/* ... and to planar tensors, `planes->channels` planes each: the same road with the layout and the launch of
-   bc_decode_planes.hip */
-unsigned hapb_decode_planes(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                            const unsigned long *input_bytes, unsigned texture_count, void *const *tensors,
-                            unsigned width, unsigned height, unsigned scale_log2, unsigned long row_bytes,
-                            const HapbPlanes *planes, unsigned *results, unsigned flags)
-{
-    const picture_road road = planes_road_of(scale_log2, planes);
-    return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, tensors, width, height, row_bytes,
-                           results, flags, &road);
-}
-
-/* ... and to planar tensors of a rectangle of region_w x region_h of every frame, frame f's at (xs[f], ys[f]): both roads
-   joined -- the planar block decoder over the rectangle's blocks, and a second stage that leaves out, frame by frame,
-   what holds none of that frame's rectangle */
-unsigned hapb_decode_planes_region(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                                   const unsigned long *input_bytes, unsigned texture_count, void *const *tensors,
-                                   unsigned width, unsigned height, const unsigned *xs, const unsigned *ys,
-                                   unsigned region_w, unsigned region_h, unsigned scale_log2, unsigned long row_bytes,
-                                   const HapbPlanes *planes, unsigned *results, unsigned flags)
-{
-    const HapGpuRegion size = {width, 0u, 0u, region_w, region_h};
-    const picture_road road = planes_region_road_of(scale_log2, planes, &size, xs, ys);
-    unsigned f;
-    /* (without origins the road would be the one-rectangle road at (0, 0)) */
-    if ((!xs || !ys) && frame_count && results) {
-        for (f = 0; f < frame_count; f++)
-            results[f] = HapResult_Bad_Arguments;
-        return HapResult_Bad_Arguments;
-    }
-    return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, tensors, width, height, row_bytes,
-                           results, flags, &road);
-}
-
-/* ... and to planar tensors of out_w x out_h of a crop per frame, at any texel position and size of the scaled picture:
-   the resampling block decoder over the blocks under every output tile, and a second stage that leaves out, frame by
-   frame, what holds none of the blocks the frame's crop touches */
-unsigned hapb_decode_planes_resized(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                                    const unsigned long *input_bytes, unsigned texture_count, void *const *tensors,
-                                    unsigned width, unsigned height, const HapbResize *resize, unsigned scale_log2,
-                                    unsigned long row_bytes, const HapbPlanes *planes, unsigned *results, unsigned flags)
-{
-    const picture_road road = planes_resized_road_of(scale_log2, planes, resize);
-    return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, tensors, width, height, row_bytes,
-                           results, flags, &road);
-}
-
-/* ... and to no pictures at all: every frame against its RGBA8 reference picture in device memory, the sums of the
-   errors to errors[f] -- the same road with the measuring launch of bc_measure.hip, which reads the third column */
-unsigned hapb_measure_frames(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                             const unsigned long *input_bytes, unsigned texture_count, const void *const *rgba_frames,
-                             unsigned width, unsigned height, unsigned long row_bytes, HapGpuPictureError *errors,
-                             unsigned *results, unsigned flags)
-{
-    const picture_road road = measure_road_of(errors);
-    /* (the road's pictures are its third column whichever way the bytes go: this one only reads them) */
-    return decode_pictures(ctx, frame_count, inputs, input_bytes, texture_count, (void *const *)rgba_frames, width, height,
-                           row_bytes, results, flags & ~HAPGPU_DECODE_BPTC_PICTURES, &road);
-}
-
-/* ============================================================= compositing */
-/* Layers of textures or frames "over" a background colour -> one RGBA8 picture per output frame, by bc_composite.hip:
-   the layers' pictures never exist.  The textures form stages what lies in host memory into D_BC_TEX; the frames form
-   runs the second stage of all frameCount * layerCount frames of a slice in one batch into D_BC_TEX, as decode_pictures
-   does, with a texture count per LAYER -- its entries are staged here, slice_textures being one count per call --, and
-   one composite launch per slice follows.  The descriptors and the pictures' addresses go out in one small table. */
-
-static const unsigned char k_composite_background[4] = {0u, 0u, 0u, 255u};
-/* (the public limit is the kernel's) */
-typedef char composite_limits_agree[HAPGPU_COMPOSITE_MAX_LAYERS == HAPGPU_COMPOSITE_LAYERS_MAX ? 1 : -1];
-
-/* the colour formats a layer may have */
-static int composite_format(unsigned format)
-{
-    return format == HapTextureFormat_RGB_DXT1 || format == HapTextureFormat_RGBA_DXT5 || format == HapTextureFormat_YCoCg_DXT5;
-}
-
-int hapb_composite_valid(unsigned layer_count, unsigned width, unsigned height, unsigned long row_bytes,
-                         const unsigned *texture_counts)
-{
-    unsigned l;
-    if (layer_count == 0 || layer_count > HAPGPU_COMPOSITE_MAX_LAYERS || width == 0 || height == 0 || (width & 3u) ||
-        (height & 3u) || row_bytes < (unsigned long)width * 4u || (row_bytes & 15u))
-        return 0;
-    for (l = 0; texture_counts && l < layer_count; l++)
-        if (texture_counts[l] != 1u && texture_counts[l] != 2u)
-            return 0;
-    return 1;
-}
-
-/* the table of a composite launch for n pictures of layer_count layers: [n] picture addresses, then [n][layer_count]
-   descriptors; *device gets its device copy's address (filled by the caller's h2d of `bytes`) */
-static uint64_t *composite_table(hapgpu_rt *rt, unsigned n, unsigned layer_count, uint64_t **device, size_t *bytes)
-{
-    uint64_t *htab;
-    *bytes = sizeof(uint64_t) * n + sizeof(HapGpuCompositeLayer) * (size_t)n * layer_count;
-    htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, *bytes);
-    *device = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, *bytes);
-    if (!htab || !*device)
-        return NULL;
-    memset(htab, 0, *bytes);
-    return htab;
-}
-
-unsigned hapb_composite_textures(HapGpuContext *ctx, unsigned layer_count, const void *const *textures,
-                                 const unsigned long *texture_bytes, const unsigned *formats,
-                                 const void *const *alphas, const unsigned long *alpha_bytes,
-                                 const unsigned char *opacities, const unsigned char *background, unsigned width,
-                                 unsigned height, void *picture, unsigned long row_bytes)
-{
-    hapgpu_rt *rt = ctx->rt;
-    const size_t blocks = (size_t)(width / 4u) * (height / 4u), pixel_row = (size_t)width * 4u;
-    const size_t picture_bytes = (size_t)row_bytes * (height ? height - 1u : 0u) + pixel_row;
-    size_t staged = 0, tab_bytes, at = 0;
-    uint64_t *htab, *dtab;
-    HapGpuCompositeLayer *hlayers;
-    uint8_t *stage = NULL;
-    void *dst = picture;
-    unsigned l;
-    int rc;
-    if (!hapb_composite_valid(layer_count, width, height, row_bytes, NULL) || !textures || !texture_bytes || !formats ||
-        !picture)
-        return HapResult_Bad_Arguments;
-    if (context_busy(ctx, NULL, 0))
-        return HapResult_Internal_Error;
-    /* every layer: HapGpuDecompressRGBA's rules for its texture and its plane */
-    for (l = 0; l < layer_count; l++) {
-        const void *alpha = alphas ? alphas[l] : NULL;
-        const size_t need = composite_format(formats[l]) ? blocks * hapf_block_bytes(formats[l]) : 0u;
-        if (!textures[l] || !need || texture_bytes[l] < need || (alpha && (!alpha_bytes || alpha_bytes[l] < blocks * 8u)) ||
-            (is_dev(ctx, textures[l]) && ((uintptr_t)textures[l] & (hapf_block_bytes(formats[l]) - 1u))) ||
-            (alpha && is_dev(ctx, alpha) && ((uintptr_t)alpha & 7u)))
-            return HapResult_Bad_Arguments;
-        if (!is_dev(ctx, textures[l]))
-            staged += align_up(need, 256);
-        if (alpha && !is_dev(ctx, alpha))
-            staged += align_up(blocks * 8u, 256);
-    }
-    if (is_dev(ctx, picture) && ((uintptr_t)picture & 15u))
-        return HapResult_Bad_Arguments;
-    /* (one request for all that is staged: an arena that grows forgets what it held) */
-    if (staged && !(stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, staged)))
-        return HapResult_Internal_Error;
-    if (!is_dev(ctx, picture) && !(dst = hapgpu_rt_device_scratch(rt, D_RGBA_STAGE, picture_bytes)))
-        return HapResult_Internal_Error;
-    htab = composite_table(rt, 1u, layer_count, &dtab, &tab_bytes);
-    if (!htab)
-        return HapResult_Internal_Error;
-    hlayers = (HapGpuCompositeLayer *)(htab + 1);
-    htab[0] = (uint64_t)(uintptr_t)dst;
-    for (l = 0; l < layer_count; l++) {
-        const void *alpha = alphas ? alphas[l] : NULL, *src = textures[l];
-        if (!is_dev(ctx, src)) {
-            const size_t need = blocks * hapf_block_bytes(formats[l]);
-            if (hapgpu_rt_h2d(rt, stage + at, src, need))
-                return HapResult_Internal_Error;
-            src = stage + at;
-            at += align_up(need, 256);
-        }
-        if (alpha && !is_dev(ctx, alpha)) {
-            if (hapgpu_rt_h2d(rt, stage + at, alpha, blocks * 8u))
-                return HapResult_Internal_Error;
-            alpha = stage + at;
-            at += align_up(blocks * 8u, 256);
-        }
-        hlayers[l].texture = (uint64_t)(uintptr_t)src;
-        hlayers[l].alpha = (uint64_t)(uintptr_t)alpha;
-        hlayers[l].format = formats[l];
-        hlayers[l].opacity = opacities ? opacities[l] : 255u;
-    }
-    if (hapgpu_rt_h2d(rt, dtab, htab, tab_bytes))
-        return HapResult_Internal_Error;
-    rc = hapgpu_k_block_composite(rt, (const HapGpuCompositeLayer *)(dtab + 1), layer_count, dtab, 1u,
-                                  background ? background : k_composite_background, width, height, row_bytes);
-    if (rc == 1)
-        return HapResult_Bad_Arguments;
-    if (rc)
-        return HapResult_Internal_Error;
-    /* (row by row when the client's rows are longer than the picture's: what lies between them is not ours) */
-    if (dst != picture && (row_bytes == pixel_row ? hapgpu_rt_d2h(rt, picture, dst, picture_bytes)
-                                                  : hapgpu_rt_d2h_rows(rt, picture, row_bytes, dst, row_bytes, pixel_row, height)))
-        return HapResult_Internal_Error;
-    if (hapgpu_rt_sync(rt))
-        return HapResult_Internal_Error;
-    return HapResult_No_Error;
-}
-
-unsigned hapb_composite_frames(HapGpuContext *ctx, unsigned frame_count, unsigned layer_count, const void *const *inputs,
-                               const unsigned long *input_bytes, const unsigned *texture_counts,
-                               const unsigned char *opacities, const unsigned char *background, void *const *rgba_frames,
-                               unsigned width, unsigned height, unsigned long row_bytes, unsigned *results, unsigned flags)
-{
-    hapgpu_rt *rt = ctx->rt;
-    const size_t blocks = (size_t)(width / 4u) * (height / 4u), pixel_row = (size_t)width * 4u;
-    const size_t colour_bytes = align_up(blocks * 16u, 256), plane_bytes = align_up(blocks * 8u, 256);
-    const size_t rgba_bytes = (size_t)row_bytes * (height ? height - 1u : 0u) + pixel_row;
-    const size_t total = (size_t)frame_count * layer_count;
-    size_t per_frame = 0, slice, entries, done, i;
-    unsigned first_error = HapResult_No_Error, per_frame_entries = 0, f, l;
-    /* a layer's first entry within its frame's, and where its textures lie within its frame's scratch */
-    unsigned entry_of[HAPGPU_COMPOSITE_MAX_LAYERS];
-    size_t offset_of[HAPGPU_COMPOSITE_MAX_LAYERS];
-    /* per entry, one allocation (`in` is its start): what hapb_decode is given and what it gives back */
-    const void **in;
-    void **outs;
-    unsigned long *in_bytes, *caps, *used;
-    unsigned *idx, *fmts, *res;
-    if (!results)
-        return HapResult_Bad_Arguments;
-    if (!hapb_composite_valid(layer_count, width, height, row_bytes, texture_counts) || !inputs || !input_bytes ||
-        !rgba_frames) {
-        for (i = 0; i < total; i++)
-            results[i] = HapResult_Bad_Arguments;
-        return HapResult_Bad_Arguments;
-    }
-    if (frame_count == 0)
-        return HapResult_No_Error;
-    if (context_busy(ctx, NULL, 0)) {
-        for (i = 0; i < total; i++)
-            results[i] = HapResult_Internal_Error;
-        return HapResult_Internal_Error;
-    }
-    for (l = 0; l < layer_count; l++) {
-        const unsigned count = texture_counts ? texture_counts[l] : 1u;
-        entry_of[l] = per_frame_entries;
-        offset_of[l] = per_frame;
-        per_frame_entries += count;
-        per_frame += colour_bytes + (count == 2u ? plane_bytes : 0u);
-    }
-    /* output frames of a slice: at most 4 GiB of block textures and 32768 entries of the second stage at a time */
-    slice = RGBA_SLICE_BYTES / per_frame;
-    if (slice == 0)
-        slice = 1;
-    if (slice > frame_count)
-        slice = frame_count;
-    if (slice * per_frame_entries > 32768u)
-        slice = 32768u / per_frame_entries;
-    entries = slice * per_frame_entries;
-    in = (const void **)malloc(entries * (2u * sizeof(void *) + 3u * sizeof(unsigned long) + 3u * sizeof(unsigned)));
-    if (!in) {
-        for (i = 0; i < total; i++)
-            results[i] = HapResult_Internal_Error;
-        return HapResult_Internal_Error;
-    }
-    outs = (void **)(in + entries);
-    in_bytes = (unsigned long *)(outs + entries);
-    caps = in_bytes + entries;
-    used = caps + entries;
-    idx = (unsigned *)(used + entries);
-    fmts = idx + entries;
-    res = fmts + entries;
-    for (done = 0; done < frame_count; done += slice) {
-        const unsigned n = (unsigned)(frame_count - done < slice ? frame_count - done : slice);
-        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, per_frame * n);
-        const HapbDecodeArgs args = {idx, NULL, NULL, 0, NULL, 0u, NULL, NULL};
-        uint8_t *stage = NULL;
-        uint64_t *htab = NULL, *dtab = NULL;
-        HapGpuCompositeLayer *hlayers;
-        size_t tab_bytes = 0;
-        unsigned present = 0;
-        int rc = 0;
-        /* the second stage of every layer of every output frame of the slice, one batch */
-        for (f = 0; textures && f < n; f++)
-            for (l = 0; l < layer_count; l++) {
-                const unsigned count = texture_counts ? texture_counts[l] : 1u;
-                unsigned t;
-                for (t = 0; t < count; t++) {
-                    const size_t e = (size_t)f * per_frame_entries + entry_of[l] + t;
-                    in[e] = inputs[(done + f) * layer_count + l];
-                    in_bytes[e] = input_bytes[(done + f) * layer_count + l];
-                    outs[e] = textures + per_frame * f + offset_of[l] + (t ? colour_bytes : 0u);
-                    caps[e] = (unsigned long)(t ? blocks * 8u : blocks * 16u);
-                    idx[e] = t;
-                    used[e] = 0;
-                    fmts[e] = 0;
-                }
-            }
-        if (textures) {
-            hapb_decode(ctx, n * per_frame_entries, in, in_bytes, 0, outs, caps, used, fmts, res,
-                        flags & ~HAPGPU_DECODE_BPTC_PICTURES, &args);
-            /* (after the second stage, which has tables of its own) */
-            htab = composite_table(rt, n, layer_count, &dtab, &tab_bytes);
-        }
-        if (!htab) {
-            for (i = done * layer_count; i < (done + n) * layer_count; i++)
-                results[i] = HapResult_Internal_Error;
-            first_error = first_error ? first_error : HapResult_Internal_Error;
-            continue;
-        }
-        hlayers = (HapGpuCompositeLayer *)(htab + n);
-        for (f = 0; f < n; f++) {
-            unsigned *frame_results = results + (done + f) * layer_count;
-            void *dst = rgba_frames[done + f];
-            unsigned picture = HapResult_No_Error, all = HapResult_No_Error;
-            for (l = 0; l < layer_count; l++) {
-                const unsigned count = texture_counts ? texture_counts[l] : 1u;
-                const size_t e = (size_t)f * per_frame_entries + entry_of[l];
-                HapGpuCompositeLayer *d = &hlayers[(size_t)f * layer_count + l];
-                unsigned r = res[e];
-                if (r == HapResult_No_Error && count == 2u)
-                    r = res[e + 1];
-                /* the frame must hold what the caller's geometry says: a colour texture of the three formats, of
-                   exactly width x height, and (two textures) an RGTC1 plane of the same geometry */
-                if (r == HapResult_No_Error &&
-                    (!composite_format(fmts[e]) || used[e] != blocks * hapf_block_bytes(fmts[e]) ||
-                     (count == 2u && (fmts[e + 1] != HapTextureFormat_A_RGTC1 || used[e + 1] != blocks * 8u))))
-                    r = HapResult_Bad_Arguments;
-                frame_results[l] = r;
-                if (r != HapResult_No_Error && all == HapResult_No_Error)
-                    all = r;
-                d->texture = (uint64_t)(uintptr_t)outs[e];
-                d->alpha = count == 2u ? (uint64_t)(uintptr_t)outs[e + 1] : 0u;
-                d->format = fmts[e];
-                d->opacity = opacities ? opacities[(done + f) * layer_count + l] : 255u;
-            }
-            /* the picture: NULL or misaligned fails every layer's entry; host pictures are staged */
-            if (!dst || (is_dev(ctx, dst) && ((uintptr_t)dst & 15u))) {
-                picture = HapResult_Bad_Arguments;
-            } else if (all == HapResult_No_Error && !is_dev(ctx, dst)) {
-                if (!stage)
-                    stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_RGBA_STAGE, align_up(rgba_bytes, 256) * n);
-                dst = stage ? stage + align_up(rgba_bytes, 256) * f : NULL;
-                if (!dst)
-                    picture = HapResult_Internal_Error;
-            }
-            if (picture != HapResult_No_Error)
-                for (l = 0; l < layer_count; l++)
-                    frame_results[l] = picture;
-            /* (an output frame that is not written: picture address 0 skips it) */
-            if (picture == HapResult_No_Error && all == HapResult_No_Error) {
-                htab[f] = (uint64_t)(uintptr_t)dst;
-                present = 1;
-            }
-        }
-        if (present) {
-            rc |= hapgpu_rt_h2d(rt, dtab, htab, tab_bytes);
-            rc |= hapgpu_k_block_composite(rt, (const HapGpuCompositeLayer *)(dtab + n), layer_count, dtab, n,
-                                           background ? background : k_composite_background, width, height, row_bytes);
-            for (f = 0; f < n; f++)
-                if (htab[f] && !is_dev(ctx, rgba_frames[done + f])) {
-                    /* (row by row when the client's rows are longer than the picture's) */
-                    if (row_bytes == pixel_row)
-                        rc |= hapgpu_rt_d2h(rt, rgba_frames[done + f], stage + align_up(rgba_bytes, 256) * f, rgba_bytes);
-                    else
-                        rc |= hapgpu_rt_d2h_rows(rt, rgba_frames[done + f], row_bytes, stage + align_up(rgba_bytes, 256) * f,
-                                                 row_bytes, pixel_row, height);
-                }
-        }
-        rc |= hapgpu_rt_sync(rt);
-        for (i = done * layer_count; i < (done + n) * layer_count; i++) {
-            if (rc && results[i] == HapResult_No_Error && htab[i / layer_count - done])
-                results[i] = HapResult_Internal_Error;
-            if (results[i] != HapResult_No_Error && first_error == HapResult_No_Error)
-                first_error = results[i];
-        }
-    }
-    free(in);
-    return first_error;
-}
-
-/* Hap HDR frames (one BC6H texture, unsigned or signed) -> RGBA16F pictures: the same road with the BC6H decoder */
-unsigned hapb_decode_rgba_half(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                               const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,
-                               unsigned long row_bytes, unsigned *results, unsigned flags)
-{
-    const picture_road road = road_of(HAPGPU_PICTURE_RGBA16F, flags, 0u, NULL);
-    return decode_pictures(ctx, frame_count, inputs, input_bytes, 1u, pictures, width, height, row_bytes, results, flags,
-                           &road);
-}
-
-/* Hap Alpha-Only frames (one RGTC1 texture) -> A8 pictures: the same road with the plane decoder of alpha_plane.hip */
-unsigned hapb_decode_alpha(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                           const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,
-                           unsigned long row_bytes, unsigned *results, unsigned flags)
-{
-    const picture_road road = road_of(HAPGPU_PICTURE_A8, flags, 0u, NULL);
-    return decode_pictures(ctx, frame_count, inputs, input_bytes, 1u, pictures, width, height, row_bytes, results, flags,
-                           &road);
-}
-
-/* ============================================================= transcode */
-/* Frames -> frames of other texture formats or of half / quarter size: hapb_decode into D_BC_TEX as in decode_pictures,
-   the transcode kernel from there into D_TRANSCODED (one launch per source format present in the slice), hapb_encode on
-   those textures -- or, for a frame that holds the wanted formats already, on its own.  No picture anywhere. */
-
-/* the destination sets the kernel makes: 1 DXT1, 2 DXT5, 3 YCoCg-DXT5, 4 YCoCg-DXT5 + RGTC1 (Hap Q Alpha); 0: none of them */
-static unsigned transcode_set(unsigned count, const unsigned *formats)
-{
-    if (count == 1u)
-        return formats[0] == HapTextureFormat_RGB_DXT1 ? 1u : formats[0] == HapTextureFormat_RGBA_DXT5 ? 2u :
-               formats[0] == HapTextureFormat_YCoCg_DXT5 ? 3u : 0u;
-    return count == 2u && formats[0] == HapTextureFormat_YCoCg_DXT5 && formats[1] == HapTextureFormat_A_RGTC1 ? 4u : 0u;
-}
-
-static void transcode_refuse(unsigned *results, unsigned frame_count, unsigned code)
-{
-    unsigned f;
-    for (f = 0; results && f < frame_count; f++)
-        results[f] = code;
-}
-
-unsigned hapb_transcode(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                        const unsigned long *input_bytes, unsigned texture_count, unsigned width, unsigned height,
-                        unsigned scale_log2, unsigned count, const unsigned *formats, const unsigned *compressors,
-                        const unsigned *chunk_counts, void *const *outputs, const unsigned long *output_bytes,
-                        unsigned long *output_used, unsigned *results, unsigned decode_flags, unsigned encode_flags)
-{
-    hapgpu_rt *rt = ctx->rt;
-    /* the three source formats of the kernel, each with or without an alpha plane: the picture road's without BC7 */
-    const picture_road road = road_of(HAPGPU_PICTURE_RGBA8, 0u, 0u, NULL);
-    const HapbEncodeArgs device_textures = {1, NULL, 0, 0};
-    size_t out_per_frame = 0, out_off[2] = {0, 0}, done;
-    unsigned long out_bytes[2] = {0, 0};
-    unsigned first_error = HapResult_No_Error, f, i, set;
-    slice_textures s;
-    const void **tex;       /* per frame and destination texture: what the encode half reads */
-    unsigned *decoded;      /* per frame: what its decode half came to */
-    if (frame_count == 0)
-        return HapResult_No_Error;
-    if (!results)
-        return HapResult_Bad_Arguments;
-    if (context_busy(ctx, results, frame_count))
-        return HapResult_Internal_Error;
-    if (!inputs || !input_bytes || !formats || !compressors || !chunk_counts || !outputs || !output_bytes || !output_used ||
-        texture_count == 0 || texture_count > 2 || count == 0 || count > 2 || scale_log2 > 2u || width == 0 || height == 0 ||
-        width % (4u << scale_log2) || height % (4u << scale_log2) || (height >> scale_log2) / 4u > 65535u) {
-        transcode_refuse(results, frame_count, HapResult_Bad_Arguments);
-        return HapResult_Bad_Arguments;
-    }
-    /* a destination the kernel does not make is one a frame can only have already: legal at the frames' own size */
-    set = transcode_set(count, formats);
-    if (!set && scale_log2) {
-        transcode_refuse(results, frame_count, HapResult_Bad_Arguments);
-        return HapResult_Bad_Arguments;
-    }
-    for (i = 0; i < count; i++) {
-        out_bytes[i] = (unsigned long)((size_t)((width >> scale_log2) / 4u) * ((height >> scale_log2) / 4u) * hapf_block_bytes(formats[i]));
-        out_off[i] = out_per_frame;
-        out_per_frame += align_up(out_bytes[i], 256);
-    }
-    encode_flags &= ~HAPGPU_ENCODE_BPTC_BLOCKS;
-    if (encode_textures_valid(count, out_bytes, formats, compressors, chunk_counts, encode_flags) != HapResult_No_Error) {
-        transcode_refuse(results, frame_count, HapResult_Bad_Arguments);
-        return HapResult_Bad_Arguments;
-    }
-    if (!slice_textures_init(&s, frame_count, texture_count, width, height, out_per_frame, 0)) {
-        transcode_refuse(results, frame_count, HapResult_Internal_Error);
-        return HapResult_Internal_Error;
-    }
-    tex = (const void **)malloc((sizeof(*tex) * count + sizeof(*decoded)) * s.slice);
-    if (!tex) {
-        free(s.in);
-        transcode_refuse(results, frame_count, HapResult_Internal_Error);
-        return HapResult_Internal_Error;
-    }
-    decoded = (unsigned *)(tex + s.slice * count);
-    for (done = 0; done < frame_count; done += s.slice) {
-        const unsigned n = (unsigned)(frame_count - done < s.slice ? frame_count - done : s.slice);
-        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, s.per_frame * n);
-        uint8_t *transcoded = set ? (uint8_t *)hapgpu_rt_device_scratch(rt, D_TRANSCODED, out_per_frame * n) : NULL;
-        /* [source textures][source planes][destination textures][destination planes] per source format */
-        const size_t tab_bytes = sizeof(uint64_t) * 4u * PICTURE_KINDS_MAX * n;
-        uint64_t *htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, tab_bytes);
-        uint64_t *dtab = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, tab_bytes);
-        unsigned present = 0, k;
-        int rc = 0;
-        if (!textures || (set && !transcoded) || !htab || !dtab) {
-            transcode_refuse(results + done, n, HapResult_Internal_Error);
-            first_error = first_error ? first_error : HapResult_Internal_Error;
-            continue;
-        }
-        slice_textures_decode(ctx, &s, textures, inputs, input_bytes, done, n, NULL, NULL, NULL, NULL, 0u, decode_flags);
-        memset(htab, 0, tab_bytes);
-        for (f = 0; f < n; f++) {
-            const size_t e = (size_t)f * texture_count;
-            const unsigned fmt = s.fmts[e];
-            unsigned r = s.res[e];
-            int pass = 0;
-            k = road.kind_count;
-            if (r == HapResult_No_Error && texture_count == 2)
-                r = s.res[e + 1];
-            if (r == HapResult_No_Error) {
-                /* the frame's own formats are the wanted ones, at its own size: its textures go on as they are */
-                pass = scale_log2 == 0u && texture_count == count;
-                for (i = 0; pass && i < count; i++)
-                    if (s.fmts[e + i] != formats[i] || s.used[e + i] != out_bytes[i])
-                        pass = 0;
-                for (k = 0; k < road.kind_count && road.kinds[k] != fmt; k++)
-                    ;
-                /* else it must hold what the caller's geometry says, as for decode_pictures: a colour texture the
-                   kernel reads, of exactly width x height, and (two textures) an RGTC1 plane of the same geometry */
-                if (!pass && (!set || k == road.kind_count || s.used[e] != s.blocks * hapf_block_bytes(fmt) ||
-                              (texture_count == 2 && (s.fmts[e + 1] != HapTextureFormat_A_RGTC1 || s.used[e + 1] != s.blocks * 8u))))
-                    r = HapResult_Bad_Arguments;
-            }
-            decoded[f] = r;
-            for (i = 0; i < count; i++)
-                tex[(size_t)f * count + i] = r != HapResult_No_Error ? NULL :
-                                             pass ? s.outs[e + i] : (const void *)(transcoded + out_per_frame * f + out_off[i]);
-            /* (a frame whose output hapb_encode will refuse is not worth the kernel's time either) */
-            if (r == HapResult_No_Error && !pass && outputs[done + f] && output_bytes[done + f]) {
-                uint64_t *col = htab + (size_t)k * 4u * n;
-                present |= 1u << k;
-                col[f] = (uint64_t)(uintptr_t)s.outs[e];
-                col[n + f] = texture_count == 2 ? (uint64_t)(uintptr_t)s.outs[e + 1] : 0u;
-                col[2u * n + f] = (uint64_t)(uintptr_t)tex[(size_t)f * count];
-                col[3u * n + f] = count == 2 ? (uint64_t)(uintptr_t)tex[(size_t)f * count + 1] : 0u;
-            }
-        }
-        if (present) {
-            rc |= hapgpu_rt_h2d(rt, dtab, htab, tab_bytes);
-            for (k = 0; k < road.kind_count; k++)
-                if (present & (1u << k)) {
-                    const uint64_t *col = dtab + (size_t)k * 4u * n;
-                    const HapGpuTranscodeTable tt = {{col, col + n, col + 2u * (size_t)n, col + 3u * (size_t)n}, {0u, 0u, 0u, 0u}};
-                    rc |= hapgpu_k_block_transcode(rt, &tt, n, road.kinds[k], texture_count == 2, width, height, scale_log2,
-                                                   formats[0], count == 2);
-                }
-        }
-        if (rc)     /* (nothing of this slice's kernel output may be trusted: its frames fail, the pass-through ones included) */
-            memset(tex, 0, sizeof(*tex) * (size_t)n * count);
-        /* the encode half on the same stream, behind the kernel; it ends with the slice's second and last wait */
-        hapb_encode(ctx, n, count, tex, out_bytes, formats, compressors, chunk_counts, outputs + done, output_bytes + done,
-                    output_used + done, results + done, encode_flags, &device_textures);
-        for (f = 0; f < n; f++) {
-            if (decoded[f] != HapResult_No_Error)
-                results[done + f] = decoded[f];
-            else if (rc && (results[done + f] == HapResult_No_Error || results[done + f] == HapResult_Bad_Arguments))
-                results[done + f] = HapResult_Internal_Error;
-            if (results[done + f] != HapResult_No_Error && first_error == HapResult_No_Error)
-                first_error = results[done + f];
-        }
-    }
-    free(s.in); free(tex);
-    return first_error;
-}
-
-/* One texture (+ alpha plane) -> `count` textures of one of the kernel's destination sets; the set the source is
-   already, at its own size, is copied. */
-unsigned hapb_transcode_texture(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
-                                const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                                unsigned scale_log2, unsigned count, const unsigned *formats, void *const *outputs,
-                                const unsigned long *output_bytes, unsigned long *output_used)
-{
-    const picture_road road = road_of(HAPGPU_PICTURE_RGBA8, 0u, 0u, NULL);
-    hapgpu_rt *rt = ctx->rt;
-    const size_t block = hapf_block_bytes(format);
-    HapGpuTranscodeTable t = {{NULL, NULL, NULL, NULL}, {0u, 0u, 0u, 0u}};
-    size_t need, alpha_need, out_need[2] = {0, 0}, out_off[2] = {0, 0}, out_total = 0;
-    const void *src = texture, *asrc = alpha;
-    uint8_t *staged = NULL;
-    unsigned i, k, set, align;
-    int rc = 0, pass;
-    if (context_busy(ctx, NULL, 0))
-        return HapResult_Internal_Error;
-    for (k = 0; k < road.kind_count && road.kinds[k] != format; k++)
-        ;
-    if (!texture || !formats || !outputs || !output_bytes || count == 0 || count > 2 || scale_log2 > 2u || width == 0 ||
-        height == 0 || width % (4u << scale_log2) || height % (4u << scale_log2) || (height >> scale_log2) / 4u > 65535u ||
-        k == road.kind_count)
-        return HapResult_Bad_Arguments;
-    set = transcode_set(count, formats);
-    if (!set)
-        return HapResult_Bad_Arguments;
-    need = (size_t)(width / 4u) * (height / 4u) * block;
-    alpha_need = (size_t)(width / 4u) * (height / 4u) * 8u;
-    if (texture_bytes < need || (alpha && alpha_bytes < alpha_need))
-        return HapResult_Bad_Arguments;
-    for (i = 0; i < count; i++) {
-        if (!outputs[i])
-            return HapResult_Bad_Arguments;
-        out_need[i] = (size_t)((width >> scale_log2) / 4u) * ((height >> scale_log2) / 4u) * hapf_block_bytes(formats[i]);
-        out_off[i] = out_total;
-        out_total += align_up(out_need[i], 256);
-    }
-    for (i = 0; i < count; i++)
-        if (output_bytes[i] < out_need[i])
-            return HapResult_Buffer_Too_Small;
-    /* device sources aligned to what a lane reads of a block row (the block << scale_log2, at most 16 bytes), device
-       outputs to their blocks */
-    align = (unsigned)(block << scale_log2) > 16u ? 16u : (unsigned)(block << scale_log2);
-    if ((is_dev(ctx, texture) && ((uintptr_t)texture & (align - 1u))) ||
-        (alpha && is_dev(ctx, alpha) && ((uintptr_t)alpha & ((8u << scale_log2 > 16u ? 16u : 8u << scale_log2) - 1u))))
-        return HapResult_Bad_Arguments;
-    for (i = 0; i < count; i++)
-        if (is_dev(ctx, outputs[i]) && ((uintptr_t)outputs[i] & (hapf_block_bytes(formats[i]) - 1u)))
-            return HapResult_Bad_Arguments;
-    if (!is_dev(ctx, texture) || (alpha && !is_dev(ctx, alpha))) {
-        uint8_t *s = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, align_up(need, 256) + alpha_need);
-        if (!s)
-            return HapResult_Internal_Error;
-        if (!is_dev(ctx, texture)) {
-            if (hapgpu_rt_h2d(rt, s, texture, need))
-                return HapResult_Internal_Error;
-            src = s;
-        }
-        if (alpha && !is_dev(ctx, alpha)) {
-            if (hapgpu_rt_h2d(rt, s + align_up(need, 256), alpha, alpha_need))
-                return HapResult_Internal_Error;
-            asrc = s + align_up(need, 256);
-        }
-    }
-    /* the source is the destination set already (its alpha plane counted), at its own size: no generation loss */
-    pass = scale_log2 == 0u && formats[0] == format && (count == 2) == (alpha != NULL);
-    for (i = 0; i < count; i++)
-        if (!is_dev(ctx, outputs[i]) && !pass && !staged) {
-            staged = (uint8_t *)hapgpu_rt_device_scratch(rt, D_TRANSCODED, out_total);
-            if (!staged)
-                return HapResult_Internal_Error;
-        }
-    if (pass) {
-        for (i = 0; i < count; i++) {
-            const void *from = i ? asrc : src;
-            rc |= is_dev(ctx, outputs[i]) ? hapgpu_rt_d2d(rt, outputs[i], from, out_need[i])
-                                          : hapgpu_rt_d2h(rt, outputs[i], from, out_need[i]);
-        }
-    } else {
-        t.one[0] = (uint64_t)(uintptr_t)src;
-        t.one[1] = (uint64_t)(uintptr_t)asrc;
-        for (i = 0; i < count; i++)
-            t.one[2u + i] = (uint64_t)(uintptr_t)(is_dev(ctx, outputs[i]) ? (uint8_t *)outputs[i] : staged + out_off[i]);
-        rc = hapgpu_k_block_transcode(rt, &t, 1u, format, alpha != NULL, width, height, scale_log2, formats[0], count == 2);
-        if (rc == 1)
-            return HapResult_Bad_Arguments;
-        for (i = 0; !rc && i < count; i++)
-            if (!is_dev(ctx, outputs[i]))
-                rc |= hapgpu_rt_d2h(rt, outputs[i], staged + out_off[i], out_need[i]);
-    }
-    if (rc || hapgpu_rt_sync(rt))
-        return HapResult_Internal_Error;
-    for (i = 0; output_used && i < count; i++)
-        output_used[i] = (unsigned long)out_need[i];
-    return HapResult_No_Error;
 }
 
 /* ============================================================= join on the device */

@@ -1,6 +1,6 @@
 /*
  * hap_batch.h -- internal interface between hap_api.c (public symbols) and
- * hap_batch.c (GPU orchestration).  Pure C.
+ * hap_batch.c / hap_pictures.c (GPU orchestration).  Pure C.
  */
 #ifndef HAP_BATCH_H
 #define HAP_BATCH_H
@@ -111,26 +111,6 @@ unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width
                             unsigned long row_bytes, unsigned format, void *output,
                             unsigned long output_bytes, unsigned long *used, int synchronise, unsigned flags,
                             unsigned picture_kind);
-/* one texture -> one picture of picture_kind: RGBA8 (DXT1, DXT5, YCoCg-DXT5 with an optional RGTC1 alpha plane, BC7),
-   RGBA16F (BC6H unsigned or signed, no alpha plane) or A8 (a lone RGTC1 texture).  scale_log2 0: a picture of
-   width x height; 1 or 2 (RGBA8 only): the half- / quarter-size picture of (width >> scale_log2) x (height >> scale_log2),
-   rows and device pictures aligned to 16 >> scale_log2 bytes.  region != NULL (RGBA8 only, scale_log2 0; region->width
-   == width): the picture is that rectangle of the texture, region->w x region->h, and only its blocks are read */
-unsigned hapb_decompress_rgba(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
-                              const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                              void *picture, unsigned long row_bytes, unsigned picture_kind, unsigned scale_log2,
-                              const HapGpuRegion *region);
-/* one texture (host or device) -> one planar tensor in device memory of (width >> scale_log2) x (height >> scale_log2),
-   scale_log2 0 to 2: DXT1, DXT5, YCoCg-DXT5 with an optional RGTC1 alpha plane */
-unsigned hapb_decompress_planes(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
-                                const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                                unsigned scale_log2, void *tensor, unsigned long row_bytes, const HapbPlanes *planes);
-/* ... the rectangle `region` of it (region->width == width) -> one planar tensor of (region->w >> scale_log2) x
-   (region->h >> scale_log2) */
-unsigned hapb_decompress_planes_region(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
-                                       const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                                       const HapGpuRegion *region, unsigned scale_log2, void *tensor,
-                                       unsigned long row_bytes, const HapbPlanes *planes);
 /* The crops of the resized planar roads (include/hap_gpu.h: HapGpuDecompressPlanesResized,
    HapGpuDecodeFramesPlanesResized): entry f's crop is (xs[f], ys[f], ws[f], hs[f]) in texels of the scaled picture, f
    counted from the call's first frame, and every tensor is out_w x out_h elements */
@@ -145,12 +125,6 @@ int hapb_resize_out_valid(const HapbResize *resize);
    hapb_region_fits */
 int hapb_resize_region(const HapbResize *resize, size_t f, unsigned width, unsigned height, unsigned scale_log2,
                        HapGpuRegion *region);
-/* ... one crop of it, at any texel position and size of the scaled picture, resized -> one planar tensor of
-   resize->out_w x resize->out_h (the arrays hold one entry) */
-unsigned hapb_decompress_planes_resized(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
-                                        const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                                        const HapbResize *resize, unsigned scale_log2, void *tensor,
-                                        unsigned long row_bytes, const HapbPlanes *planes);
 /* one planar tensor in device memory -> one texture (host or device): DXT1, DXT5, YCoCg-DXT5, or RGTC1 from the fourth
    plane (255 where there are three) */
 unsigned hapb_compress_planes(HapGpuContext *ctx, const void *tensor, unsigned width, unsigned height,
@@ -161,11 +135,6 @@ unsigned hapb_compress_planes(HapGpuContext *ctx, const void *tensor, unsigned w
    HapGpuEncodeFramesPlanes).  Touches no device. */
 int hapb_planes_encode_valid(unsigned width, unsigned height, unsigned long row_bytes, const HapbPlanes *planes,
                              unsigned count, const unsigned *formats);
-/* one texture (host or device) against its RGBA8 reference picture in DEVICE memory (include/hap_gpu.h:
-   HapGpuMeasureTexture): DXT1, DXT5, YCoCg-DXT5 with an optional RGTC1 alpha plane; *error written on No_Error only */
-unsigned hapb_measure_texture(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
-                              const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height,
-                              const void *rgba, unsigned long row_bytes, HapGpuPictureError *error);
 /* 1: region is a block-aligned, non-empty rectangle inside region->width x height */
 int hapb_region_fits(const HapGpuRegion *region, unsigned height);
 /* pictures -> frames.  picture_kind RGBA8: the DXT / RGTC1 formats (BC7 with HAPGPU_ENCODE_BPTC_BLOCKS); RGBA16F (rows
@@ -212,54 +181,48 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
                      const unsigned long *output_bytes, unsigned long *output_used,
                      unsigned *output_formats, unsigned *results, unsigned flags, const HapbDecodeArgs *args);
 
-/* frames -> RGBA8 pictures (texture_count 2: Hap Q Alpha frames, colour + RGTC1 alpha plane); scale_log2 as for
-   hapb_decompress_rgba (width and height stay the frames') */
-unsigned hapb_decode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                          const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
-                          unsigned width, unsigned height, unsigned scale_log2, unsigned long row_bytes,
-                          unsigned *results, unsigned flags);
-/* ... to planar tensors in device memory (scale_log2 0 to 2), without an RGBA8 picture in between */
-unsigned hapb_decode_planes(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                            const unsigned long *input_bytes, unsigned texture_count, void *const *tensors,
-                            unsigned width, unsigned height, unsigned scale_log2, unsigned long row_bytes,
-                            const HapbPlanes *planes, unsigned *results, unsigned flags);
-/* ... against RGBA8 reference pictures in device memory, which are read: errors[f] (host) gets frame f's sums, all zero
-   for a frame whose result is not No_Error */
-unsigned hapb_measure_frames(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                             const unsigned long *input_bytes, unsigned texture_count, const void *const *rgba_frames,
-                             unsigned width, unsigned height, unsigned long row_bytes, HapGpuPictureError *errors,
-                             unsigned *results, unsigned flags);
-/* ... a rectangle of every frame (region->width == width) to RGBA8 pictures of region->w x region->h */
-unsigned hapb_decode_rgba_region(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                                 const unsigned long *input_bytes, unsigned texture_count, void *const *rgba_frames,
-                                 unsigned width, unsigned height, const HapGpuRegion *region, unsigned long row_bytes,
-                                 unsigned *results, unsigned flags);
-/* ... a rectangle of region_w x region_h of every frame, frame f's at (xs[f], ys[f]), to planar tensors in device memory of
-   (region_w >> scale_log2) x (region_h >> scale_log2) */
-unsigned hapb_decode_planes_region(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                                   const unsigned long *input_bytes, unsigned texture_count, void *const *tensors,
-                                   unsigned width, unsigned height, const unsigned *xs, const unsigned *ys,
-                                   unsigned region_w, unsigned region_h, unsigned scale_log2, unsigned long row_bytes,
-                                   const HapbPlanes *planes, unsigned *results, unsigned flags);
-/* ... a crop per frame of the scaled picture, frame f's (resize->xs[f], ys[f], ws[f], hs[f]) at any texel position and
-   size, resized to planar tensors in device memory of resize->out_w x resize->out_h */
-unsigned hapb_decode_planes_resized(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                                    const unsigned long *input_bytes, unsigned texture_count, void *const *tensors,
-                                    unsigned width, unsigned height, const HapbResize *resize, unsigned scale_log2,
-                                    unsigned long row_bytes, const HapbPlanes *planes, unsigned *results, unsigned flags);
-/* Hap HDR frames (one BC6H texture) -> RGBA16F pictures */
-unsigned hapb_decode_rgba_half(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                               const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,
-                               unsigned long row_bytes, unsigned *results, unsigned flags);
-
-/* Hap Alpha-Only frames (one RGTC1 texture) -> A8 pictures */
-unsigned hapb_decode_alpha(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
-                           const unsigned long *input_bytes, void *const *pictures, unsigned width, unsigned height,
-                           unsigned long row_bytes, unsigned *results, unsigned flags);
+/* A road from block textures to pictures: what the caller wants made of every texture (+ RGTC1 alpha plane) or frame.
+   Filled with designated initialisers, everything not named being 0 / NULL: RGBA8 pictures of the textures' size.
+   Which texture formats the road takes follows from it (hap_pictures.c: road_formats) -- RGBA8: DXT1, DXT5 and
+   YCoCg-DXT5, each with an optional alpha plane, and with `bptc` BC7; RGBA16F: BC6H unsigned or signed; A8: RGTC1. */
+typedef struct HapbRoad {
+    unsigned picture_kind;      /* HAPGPU_PICTURE_*: the pictures' layout, and with it the size of a texel */
+    unsigned scale_log2;        /* 0: pictures of the textures' size; 1 / 2 (RGBA8 only): half / quarter size, of
+                                   (width >> scale_log2) x (height >> scale_log2); rows and device pictures are then
+                                   aligned to 16 >> scale_log2 bytes */
+    int bptc;                   /* != 0 (interleaved RGBA8 pictures only): BC7 textures are taken too */
+    const HapGpuRegion *region; /* NULL: the whole of every texture; else (RGBA8; interleaved pictures: scale_log2 0;
+                                   region->width == width) pictures of region->w x region->h, planar tensors of
+                                   (region->w >> scale_log2) x (region->h >> scale_log2): that rectangle of every texture,
+                                   and only its blocks are read */
+    const unsigned *region_xs, *region_ys;  /* NULL: region->x, region->y for every frame; else (planes only, frames only)
+                                   frame f's rectangle begins at (region_xs[f], region_ys[f]), f counted from the call's
+                                   first frame, and region->x, region->y are 0 */
+    const HapbPlanes *planes;   /* NULL: interleaved pictures of picture_kind; else (RGBA8, scale_log2 0 to 2) planar
+                                   tensors in device memory: a "texel" is then one element of one plane and row_bytes
+                                   the pitch of a plane's rows */
+    const HapbResize *resize;   /* NULL: tensors of the rectangle's or the textures' (scaled) size; else (planes only, no
+                                   region) tensors of resize->out_w x resize->out_h, entry f's crop of the scaled picture
+                                   resized */
+    HapGpuPictureError *measure; /* NULL: the pictures are written; else (RGBA8, scale_log2 0, no region, no planes) they
+                                   are reference pictures in device memory and are READ: measure[f] gets the sums of
+                                   frame f against its picture, f counted from the call's first frame, all zero for a
+                                   frame whose result is not No_Error (one texture: *measure, written on No_Error only) */
+} HapbRoad;
+/* one texture (host or device; + RGTC1 alpha plane) down a road: to one picture, one planar tensor, or one set of sums */
+unsigned hapb_road_texture(HapGpuContext *ctx, const void *texture, unsigned long texture_bytes, unsigned format,
+                           const void *alpha, unsigned long alpha_bytes, unsigned width, unsigned height, void *picture,
+                           unsigned long row_bytes, const HapbRoad *road);
+/* frames down a road, one picture each (texture_count 2: Hap Q Alpha frames, colour + RGTC1 alpha plane; width and
+   height are the frames') */
+unsigned hapb_road_frames(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
+                          const unsigned long *input_bytes, unsigned texture_count, void *const *pictures, unsigned width,
+                          unsigned height, unsigned long row_bytes, unsigned *results, unsigned flags,
+                          const HapbRoad *road);
 
 /* frames -> frames of the texture formats `formats` (count 1 or 2) at (width >> scale_log2) x (height >> scale_log2),
    without a picture in between (include/hap_gpu.h: HapGpuTranscodeFrames); texture_count: the textures read of every
-   frame, as for hapb_decode_rgba */
+   frame, as for hapb_road_frames */
 unsigned hapb_transcode(HapGpuContext *ctx, unsigned frame_count, const void *const *inputs,
                         const unsigned long *input_bytes, unsigned texture_count, unsigned width, unsigned height,
                         unsigned scale_log2, unsigned count, const unsigned *formats, const unsigned *compressors,

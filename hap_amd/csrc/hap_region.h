@@ -1,6 +1,6 @@
 /*
  * hap_region.h -- which bytes of a block texture a block-aligned rectangle needs.  Plain C, one definition: the host
- * code (hap_batch.c, and HapGpuRegionNeedsBytes in hap_api.c) and the kernel that blanks decode units
+ * code (hap_pictures.c, and HapGpuRegionNeedsBytes in hap_api.c) and the kernel that blanks decode units
  * (snappy_decode.hip) include this file and nothing else decides the question.
  *
  * A texture of `width` texels is rows of width / 4 blocks of block_bytes (8 or 16) bytes, row after row.  The region

@@ -382,3 +382,53 @@ def test_the_same_call_twice_gives_the_same_bytes(ctx, movie):
     _host, device, _decoded = stack(ctx, CASES, w, h)
     once = composited(ctx, device, w, h, [254, 127, 128, 1], K.BACKGROUNDS[3], True)
     assert np.array_equal(once, composited(ctx, device, w, h, [254, 127, 128, 1], K.BACKGROUNDS[3], True))
+
+
+# ------------------------------------------------------------------------------------------------------ 8. slicing --
+def test_more_output_frames_than_one_slice_holds(ctx, hap):
+    """A call stages its layers' textures 32768 at a time; opacities, inputs and pictures are the call's.  Two layers
+    with texture counts (1, 2) are three entries an output frame, so a slice holds 10922 output frames: 10922 + 9 of
+    8 x 4 texels, cycling through 5 layer pairs of random blocks and 7 opacity pairs -- 10922 is 2 modulo 7, so an
+    opacity looked up by a frame's place in its slice is another frame's."""
+    w, h, counts = 8, 4, (1, 2)
+    n = 32768 // 3 + 9
+    rng = np.random.default_rng(8)
+
+    def blocks(nbytes):
+        return rng.integers(0, 256, nbytes, dtype=np.uint8).tobytes()
+
+    made = [[hap.HapEncode([blocks(32)], [L.FMT_DXT5], [1], [1]), hap.HapEncode([blocks(32), blocks(16)], [L.FMT_YCOCG, L.FMT_RGTC1], [1, 1], [1, 1])]
+            for _ in range(5)]
+    assert all(r == 0 for pair in made for r, _frame in pair)
+    made = [[frame for _r, frame in pair] for pair in made]
+    decoded = []
+    for pair in made:
+        pictures = []
+        for frame, count in zip(pair, counts):
+            out = np.zeros(h * w * 4, dtype=np.uint8)
+            _r, res = ctx.decode_frames_rgba([frame], [len(frame)], count, [out], w, h)
+            assert res == [0]
+            pictures.append(out.reshape(h, w, 4))
+        decoded.append(pictures)
+    levels = [(255, 255), (254, 1), (128, 127), (0, 255), (127, 254), (1, 128), (255, 0)]
+    background = K.BACKGROUNDS[3]
+    want = np.stack([np.stack([K.composite(decoded[i], o, background) for o in levels]) for i in range(5)])    # [5, 7, h, w, 4]
+    assert len({want[i, o].tobytes() for i in range(5) for o in range(7)}) == 35
+    # the frames in device memory, behind each other at 256-byte steps
+    step = 256
+    assert max(len(f) for pair in made for f in pair) <= step
+    store = np.zeros(10 * step, dtype=np.uint8)
+    for i, pair in enumerate(made):
+        for l, f in enumerate(pair):
+            store[(2 * i + l) * step: (2 * i + l) * step + len(f)] = np.frombuffer(f, np.uint8)
+    store = torch.from_numpy(store).cuda()
+    frames = [[store[(2 * (f % 5) + l) * step: (2 * (f % 5) + l + 1) * step] for l in range(2)] for f in range(n)]
+    lens = [[len(made[f % 5][l]) for l in range(2)] for f in range(n)]
+    out = torch.full((n, h * w * 4), SENTINEL, dtype=torch.uint8, device="cuda")
+    r, res = ctx.composite_frames(frames, lens, counts, list(out), w, h, opacities=[levels[f % 7] for f in range(n)],
+                                  background=background)
+    assert r == 0 and res == [0] * (2 * n)
+    f = np.arange(n)
+    got = out.cpu().numpy().reshape(n, h, w, 4)
+    wrong = np.argwhere((got != want[f % 5, f % 7]).reshape(n, -1).any(axis=1)).ravel()
+    assert wrong.size == 0, wrong[:8].tolist()

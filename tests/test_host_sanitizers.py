@@ -44,3 +44,16 @@ def test_container_code_is_clean_under_asan_and_ubsan(tmp_path):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     done = subprocess.run([exe, str(tmp_path / "scratch.hapseq")] + paths, capture_output=True, text=True, env=env, timeout=600)
     assert done.returncode == 0 and done.stdout.strip().endswith("ok"), (done.returncode, done.stderr[-3000:])
+
+
+def test_the_slice_arithmetic_is_clean_and_is_the_rule(tmp_path):
+    """hap_slice.h -- the scratch layout and the slice size of every call that goes on from block textures -- walked by
+    tests/c/slice_layout.c under AddressSanitizer + UBSan: a plain executable, nothing preloaded."""
+    exe = str(tmp_path / "slice_layout")
+    cmd = ["gcc", "-std=c99", "-g", "-O1", "-fsanitize=address,undefined",
+           "-fno-sanitize-recover=undefined", "-I", os.path.join(ROOT, "hap_amd", "csrc"),
+           os.path.join(ROOT, "tests", "c", "slice_layout.c"), "-o", exe]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    done = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
+    assert done.returncode == 0 and done.stdout.strip().endswith("ok"), (done.returncode, done.stdout, done.stderr[-3000:])

@@ -176,11 +176,11 @@ def test_the_predicate_still_has_one_definition_and_the_new_road_restates_nothin
         assert re.search(r"\bint %s\(" % entry, sources["hapgpu_abi.h"]), entry
         assert re.search(r'extern "C" int %s\(' % entry, kernel), entry
     # the host: whether a frame's rectangle is one is hapb_region_fits' answer (hap_region_geometry_valid and the height)
-    batch = sources["hap_batch.c"]
-    assert "hapgpu_k_skip_units_per_job(" in batch and "decode_regions" in batch
-    fits = batch[batch.index("int hapb_region_fits("):]
+    pictures = sources["hap_pictures.c"]
+    assert "hapgpu_k_skip_units_per_job(" in sources["hap_batch.c"] and "decode_regions" in pictures
+    fits = pictures[pictures.index("int hapb_region_fits("):]
     assert "hap_region_geometry_valid(" in fits[: fits.index("\n}\n")]
-    assert "refused = !hapb_region_fits(&own, height)" in batch
+    assert "refused = !hapb_region_fits(&own, height)" in pictures
     api = sources["hap_api.c"]
     for name in NAMES:
         body = api[api.index("unsigned int %s(" % name):]

@@ -174,11 +174,11 @@ def test_the_new_road_restates_nothing():
     for function in ("hap_region_needs_bytes", "hap_region_valid", "hap_region_geometry_valid"):
         defined = [name for name, text in sources.items() if re.search(r"\bint %s\(" % function, text)]
         assert defined == ["hap_region.h"], (function, defined)
-    batch = sources["hap_batch.c"]
-    body = batch[batch.index("int hapb_resize_region("):]
+    pictures = sources["hap_pictures.c"]
+    body = pictures[pictures.index("int hapb_resize_region("):]
     body = body[: body.index("\n}\n")]
     assert "return hapb_region_fits(region, height);" in body
-    assert "refused = !hapb_resize_region(resize, done + f, width, height, scale_log2, &own)" in batch
+    assert "refused = !hapb_resize_region(resize, done + f, width, height, scale_log2, &own)" in pictures
     api = sources["hap_api.c"]
     for name in NAMES:
         body = api[api.index("unsigned int %s(" % name):]

@@ -59,7 +59,7 @@ def test_there_is_one_definition_of_the_predicate():
         if '#include "hap_region.h"' in text:
             users.append(name)
     assert defined == ["hap_region.h"]
-    assert {"hap_api.c", "hap_batch.c", "snappy_decode.hip"} <= set(users)
+    assert {"hap_api.c", "hap_pictures.c", "snappy_decode.hip"} <= set(users)
     header = open(os.path.join(csrc, "hap_region.h")).read()
     assert "static inline" in header and "template" not in header and "::" not in header      # plain C
 

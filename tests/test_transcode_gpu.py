@@ -522,3 +522,52 @@ def test_argument_rules(ctx, hap, foreign, mixed):
     outs = [filled(1 << 16, "cuda") for _ in frames]
     r, used, res = ctx.transcode_frames(frames, lens, 1, W, H, 1, [L.FMT_DXT5], snappy, two, outs)
     assert r == 0 and res == [0, 0, 0]
+
+
+# --------------------------------------------------------------------------------------------------------- 7. slicing --
+def test_more_frames_than_one_slice_holds(ctx, hap):
+    """A call transcodes its frames 32768 at a time; outputs and their sizes are the call's.  32768 + 40 Hap Alpha frames
+    of 8 x 4 texels to Hap, cycling through 5 frames of random blocks and 7 output sizes -- 32768 is 1 modulo 7, so an
+    output looked up by a frame's place in its slice is another frame's, with or without room."""
+    w, h, fmts = 8, 4, [L.FMT_DXT1]
+    n = 32768 + 40
+    made = []
+    for i in range(5):
+        r, frame = hap.HapEncode([random_bytes(32, 70 + i)], [L.FMT_DXT5], [L.COMP_SNAPPY], [1])
+        assert r == 0
+        made.append(frame)
+    room = (True, False, True, True, False, False, True)
+    cap = hap.HapMaxEncodedLength(texture_bytes(w, h, fmts), fmts, [1])
+    # what a call of the five makes of each, with room and with none
+    small = filled(5 * cap, "cuda").reshape(5, cap)
+    lens5 = [len(f) for f in made]
+    r, used5, res5 = ctx.transcode_frames(made, lens5, 1, w, h, 0, fmts, [L.COMP_SNAPPY], [1], list(small))
+    assert r == 0 and res5 == [0] * 5
+    small = host(small)
+    want = [small[i, : used5[i]].tobytes() for i in range(5)]
+    assert len(set(want)) == 5 and all((small[i, used5[i]:] == SENTINEL).all() for i in range(5))
+    none = filled(5 * cap, "cuda").reshape(5, cap)
+    _r, none_used, none_res = ctx.transcode_frames(made, lens5, 1, w, h, 0, fmts, [L.COMP_SNAPPY], [1], [row[:0] for row in none])
+    assert all(code != 0 for code in none_res) and none_used == [0] * 5 and (host(none) == SENTINEL).all()
+    # the frames in device memory, behind each other at 256-byte steps
+    step = 256
+    assert max(lens5) <= step
+    store = np.zeros(5 * step, dtype=np.uint8)
+    for i, f in enumerate(made):
+        store[i * step: i * step + len(f)] = np.frombuffer(f, np.uint8)
+    store = torch.from_numpy(store).cuda()
+    frames = [store[(f % 5) * step: (f % 5 + 1) * step] for f in range(n)]
+    out = filled(n * cap, "cuda").reshape(n, cap)
+    outputs = [out[f] if room[f % 7] else out[f, :0] for f in range(n)]
+    r, used, res = ctx.transcode_frames(frames, [lens5[f % 5] for f in range(n)], 1, w, h, 0, fmts, [L.COMP_SNAPPY], [1], outputs)
+    got = host(out)
+    f = np.arange(n)
+    has_room = np.array(room)[f % 7]
+    assert r == none_res[np.argmin(has_room) % 5]                    # (the first frame that fails)
+    assert res == [0 if has_room[i] else none_res[i % 5] for i in range(n)]
+    assert used == [used5[i % 5] if has_room[i] else 0 for i in range(n)]
+    expect = np.full((5, cap), SENTINEL, dtype=np.uint8)
+    for i in range(5):
+        expect[i, : used5[i]] = np.frombuffer(want[i], np.uint8)
+    wrong = np.argwhere((got != np.where(has_room[:, None], expect[f % 5], SENTINEL)).any(axis=1)).ravel()
+    assert wrong.size == 0, wrong[:8].tolist()
