@@ -22,7 +22,7 @@ using namespace hapbc;
 
 template <int FMT, bool WIDE>
 __device__ __forceinline__ void encode_block(const uint8_t *__restrict__ rgba, size_t row_bytes, unsigned blocks_x,
-                                             uint8_t *__restrict__ out, uint8_t *__restrict__ out2 = nullptr)
+                                             uint8_t *__restrict__ out, uint8_t *__restrict__ out2, unsigned ycocg_rows)
 {
     // one wavefront per 64 blocks of one block row: the row's address is scalar, no division per lane
     const unsigned by = blockIdx.y, bx = blockIdx.x * 64u + threadIdx.x;
@@ -45,7 +45,7 @@ __device__ __forceinline__ void encode_block(const uint8_t *__restrict__ rgba, s
         const uint4 b = block_of<FMT>(p);
         *reinterpret_cast<uint2 *>(out + id * 8u) = make_uint2(b.x, b.y);
     } else {
-        *reinterpret_cast<uint4 *>(out + id * 16u) = block_of<FMT == kFmtYCoCgAlpha ? kFmtYCoCg : FMT>(p);
+        *reinterpret_cast<uint4 *>(out + id * 16u) = block_of<FMT == kFmtYCoCgAlpha ? kFmtYCoCg : FMT, FMT == kFmtYCoCg>(p, ycocg_rows);
         if (FMT == kFmtYCoCgAlpha) {
             const uint4 a = block_of<kFmtRGTC1>(p);
             *reinterpret_cast<uint2 *>(out2 + id * 8u) = make_uint2(a.x, a.y);
@@ -59,12 +59,15 @@ __device__ __forceinline__ void encode_block(const uint8_t *__restrict__ rgba, s
 template <int FMT, bool WIDE>
 __global__ __launch_bounds__(64) void bc_encode_kernel(HapGpuPictureTable t, size_t row_bytes, unsigned blocks_x)
 {
+    // (before any return: every lane of the wave must hold its weight row, bc_encode_core.hpp; Hap Q Alpha keeps the
+    // dot-product form -- its kernels hold the pixels for the alpha plane and would lose a wave to the result tuples)
+    const unsigned ycocg_rows = FMT == kFmtYCoCg ? ycocg_weight_rows() : 0u;
     const uint8_t *rgba = (const uint8_t *)picture_address(t, 0);
     uint8_t *out = (uint8_t *)picture_address(t, 1);
     uint8_t *out2 = FMT == kFmtYCoCgAlpha ? (uint8_t *)picture_address(t, 2) : nullptr;
     if (!rgba || !out || (FMT == kFmtYCoCgAlpha && !out2))
         return;
-    encode_block<FMT, WIDE>(rgba, row_bytes, blocks_x, out, out2);
+    encode_block<FMT, WIDE>(rgba, row_bytes, blocks_x, out, out2, ycocg_rows);
 }
 
 template <int FMT>

@@ -312,8 +312,87 @@ __device__ __forceinline__ uint2 ycocg_colour_block(const unsigned (&cc)[16])
     return make_uint2(c0 | (c1 << 16), idx);
 }
 
-// 2 (Co - 128) | 4 (Cg - 128) << 16 of four pixels, signed halves, from the pixels' bytes less 128 (q ^ 0x80808080, signed
-// bytes): R - B + 1 and -R + 2G - B + 2 are SIGNED byte dot products, the 128s cancel since each set of weights sums to
+// ---- the YCoCg transform as one 4x4x4 signed-byte matrix product a pixel (v_mfma_i32_4x4x4_16b_i8) ----
+// The instruction makes sixteen independent products D = A B + C, one per group of four lanes: lane l supplies row l & 3
+// of A and column l & 3 of B (four signed bytes each, k = byte index) and gets column l & 3 of D in four registers
+// (tools/micro/mfma_beside_valu.hip prints the layout).  B's column is the lane's own pixel less 128 a channel
+// (p ^ 0x80808080 as signed bytes R', G', B', A'), the rows of A are weights, C is the inline constant 2:
+//     row 0:  1,  2,  1, 0  ->  R + 2G + B + 2 - 512          >> 2 = Y - 128   (512 is a whole multiple of the divisor)
+//     row 1:  2,  0, -2, 0  ->  2 (R - B + 1)                 >> 2 = (R - B + 1) >> 1 = Co - 128
+//     row 2: -1,  2, -1, 0  ->  -R + 2G - B + 2               >> 2 = Cg - 128
+//     row 3:  0                                                    (spare)
+// (the 128s of rows 1 and 2 cancel: their weights sum to zero; Co's row is doubled so that one constant serves all
+// three).  Per pixel: v_xor, the matrix instruction, v_ashrrev (Y), v_perm_b32 + v_pk_ashrrev_i16 (Co | Cg << 16, signed
+// halves) -- four vector instructions and one on the matrix pipe, where the dot-product form has seven.
+//
+// The matrix instruction READS all 64 lanes whatever EXEC says (it writes the active ones only): a lane's result needs
+// the weight dwords of lanes 0..2 of its group whether or not those run.  So the weight register is made ONCE, at the
+// kernel's entry with every lane active, by ycocg_weight_rows(), and handed down to block_of: its value is opaque to
+// the optimiser (a volatile asm move), which therefore cannot make it again inside a divergent region.
+typedef int mfma_i32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ unsigned ycocg_weight_rows()
+{
+    const unsigned row = threadIdx.x & 3u;
+    const unsigned w = row == 0u ? 0x00010201u : (row == 1u ? 0x00FE0002u : (row == 2u ? 0x00FF02FFu : 0u));
+    unsigned r;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "v"(w));
+    return r;
+}
+
+// Two pixels a statement, software-pipelined by one statement: the statement reads the results of the two pixels
+// BEFORE its own, then issues its own two matrix instructions.  The compiler sees neither the instruction nor its
+// hazards, so both stand here by position: two wait states between the v_xor that writes B and the matrix instruction
+// that reads it, five between a matrix instruction and the first reader of its result (the ISA's MAI hazard table for
+// a two-pass instruction; what the compiler pads the builtin with).  Every statement ENDS five states behind its last
+// matrix instruction, so whatever the compiler puts between two statements (a copy of a result included) is safe too.
+// Every reader of the old results stands IN FRONT of the new matrix instructions, and the new results are tied to the
+// old ones' registers: two tuples live instead of four.  Every other output is early-clobber: the matrix
+// instructions read the weights last, and an output that may share a register with an input could take THEIRS where
+// the statement is their last use.
+#define HAPBC_YCOCG_MFMA "v_mfma_i32_4x4x4_16b_i8 "
+#define HAPBC_YCOCG_SHIFT(CC) "v_pk_ashrrev_i16 " CC ", 2, " CC " op_sel_hi:[0,1]\n\t"
+// first statement of a block: nothing to read yet
+__device__ __forceinline__ void ycocg_pair_first(mfma_i32x4 &ta, mfma_i32x4 &tb, unsigned pa, unsigned pb, unsigned rows)
+{
+    unsigned qa, qb;
+    asm("v_xor_b32 %[qa], %[k80], %[pa]\n\tv_xor_b32 %[qb], %[k80], %[pb]\n\ts_nop 0\n\t"
+        HAPBC_YCOCG_MFMA "%[ta], %[w], %[qa], 2\n\t" HAPBC_YCOCG_MFMA "%[tb], %[w], %[qb], 2\n\ts_nop 4"
+        : [ta] "=&v"(ta), [tb] "=&v"(tb), [qa] "=&v"(qa), [qb] "=&v"(qb)
+        : [pa] "v"(pa), [pb] "v"(pb), [w] "v"(rows), [k80] "s"(0x80808080u));
+}
+// pixels pa, pb in, their results to ta, tb; Y - 128 and (Co - 128) | (Cg - 128) << 16 of the two pixels whose results
+// ta, tb held before out
+__device__ __forceinline__ void ycocg_pair(mfma_i32x4 &ta, mfma_i32x4 &tb, int &ya, int &yb, unsigned &cca, unsigned &ccb,
+                                           unsigned pa, unsigned pb, unsigned rows)
+{
+    const mfma_i32x4 oa = ta, ob = tb;
+    unsigned qa, qb;
+    asm("v_xor_b32 %[qa], %[k80], %[pa]\n\tv_xor_b32 %[qb], %[k80], %[pb]\n\t"
+        "v_ashrrev_i32 %[ya], 2, %[oax]\n\tv_ashrrev_i32 %[yb], 2, %[obx]\n\t"
+        "v_perm_b32 %[ca], %[oaz], %[oay], %[sel]\n\tv_perm_b32 %[cb], %[obz], %[oby], %[sel]\n\t"
+        HAPBC_YCOCG_SHIFT("%[ca]")
+        HAPBC_YCOCG_MFMA "%[ta], %[w], %[qa], 2\n\t" HAPBC_YCOCG_MFMA "%[tb], %[w], %[qb], 2\n\t"
+        HAPBC_YCOCG_SHIFT("%[cb]") "s_nop 3"
+        : [ta] "+v"(ta), [tb] "+v"(tb), [ya] "=&v"(ya), [yb] "=&v"(yb), [ca] "=&v"(cca), [cb] "=&v"(ccb), [qa] "=&v"(qa), [qb] "=&v"(qb)
+        : [pa] "v"(pa), [pb] "v"(pb), [w] "v"(rows), [k80] "s"(0x80808080u), [sel] "s"(0x05040100),
+          [oax] "v"(oa.x), [oay] "v"(oa.y), [oaz] "v"(oa.z), [obx] "v"(ob.x), [oby] "v"(ob.y), [obz] "v"(ob.z));
+}
+// last statement of a block: the readers alone
+__device__ __forceinline__ void ycocg_pair_last(int &ya, int &yb, unsigned &cca, unsigned &ccb, mfma_i32x4 oa, mfma_i32x4 ob)
+{
+    asm("v_ashrrev_i32 %[ya], 2, %[oax]\n\tv_ashrrev_i32 %[yb], 2, %[obx]\n\t"
+        "v_perm_b32 %[ca], %[oaz], %[oay], %[sel]\n\tv_perm_b32 %[cb], %[obz], %[oby], %[sel]\n\t"
+        HAPBC_YCOCG_SHIFT("%[ca]") "v_pk_ashrrev_i16 %[cb], 2, %[cb] op_sel_hi:[0,1]"
+        : [ya] "=&v"(ya), [yb] "=&v"(yb), [ca] "=&v"(cca), [cb] "=&v"(ccb)
+        : [sel] "s"(0x05040100), [oax] "v"(oa.x), [oay] "v"(oa.y), [oaz] "v"(oa.z), [obx] "v"(ob.x), [oby] "v"(ob.y), [obz] "v"(ob.z));
+}
+#undef HAPBC_YCOCG_SHIFT
+#undef HAPBC_YCOCG_MFMA
+
+// The dot-product form of the transform (block_of<FMT, false>: the kernels that would lose a wave to the matrix form's
+// result tuples, the Hap Q Alpha ones).  2 (Co - 128) | 4 (Cg - 128) << 16 of four pixels, signed halves, from the
+// pixels' bytes less 128 (q ^ 0x80808080, signed bytes): R - B + 1 and -R + 2G - B + 2 are SIGNED byte dot products, the 128s cancel since each set of weights sums to
 // zero, and one v_perm_b32 puts the low halves side by side.  In one statement because the compiler makes v_dot4c of
 // the builtin -- it accumulates into its destination and pays a v_mov of the constant per dot product -- and, not
 // seeing into a statement, would not keep a dot product's three wait states in front of the v_perm: here at least
@@ -331,8 +410,9 @@ __device__ __forceinline__ void chroma4(unsigned (&raw)[4], int q0, int q1, int 
 }
 
 // the 8 or 16 bytes of a block from its sixteen RGBA8 pixels (row-major); 8-byte formats leave z, w zero
-template <int FMT>
-__device__ __forceinline__ uint4 block_of(const unsigned (&p)[16])
+// (MATRIX: the YCoCg transform on the matrix pipe, `rows` the kernel's ycocg_weight_rows(); the same bytes either way)
+template <int FMT, bool MATRIX = false>
+__device__ __forceinline__ uint4 block_of(const unsigned (&p)[16], unsigned rows = 0u)
 {
     if (FMT == kFmtRGTC1) {
         int a[16];
@@ -359,24 +439,34 @@ __device__ __forceinline__ uint4 block_of(const unsigned (&p)[16])
         const uint2 ab = alpha_block(a), cb = colour_block(px);
         return make_uint4(ab.x, ab.y, cb.x, cb.y);
     } else {
+        // Y = (R+2G+B+2)>>2 ; Co = ((R-B+1)>>1)+128 ; Cg = ((-R+2G-B+2)>>2)+128 ; no clamp (oracle/bc_oracle.c).  All
+        // three leave here less 128 and nothing downstream subtracts the bias again.
         int y[16];
         unsigned cc[16];
+        if (MATRIX) {
+            mfma_i32x4 ta, tb;
+            ycocg_pair_first(ta, tb, p[0], p[1], rows);
 #pragma unroll
-        for (int i = 0; i < 16; i++) {
-            // Y = (R+2G+B+2)>>2 ; Co = ((R-B+1)>>1)+128 ; Cg = ((-R+2G-B+2)>>2)+128 ; no clamp (oracle/bc_oracle.c).
-            // All three leave here less 128 and nothing downstream subtracts the bias again: Y's dot product starts
-            // at 2 - 512 (wrap-around; a whole multiple of the divisor, so the arithmetic shift gives exactly Y - 128),
-            // the other two are the definitions' own numerators, halved / quartered as a pair of signed halves.
-            y[i] = (int)__builtin_amdgcn_udot4(p[i], 0x00010201u, (unsigned)(2 - 512), false) >> 2;                   // -128 .. 127
-        }
+            for (int i = 2; i < 16; i += 2)
+                ycocg_pair(ta, tb, y[i - 2], y[i - 1], cc[i - 2], cc[i - 1], p[i], p[i + 1], rows);
+            ycocg_pair_last(y[14], y[15], cc[14], cc[15], ta, tb);
+        } else {
 #pragma unroll
-        for (int i = 0; i < 16; i += 4) {
-            unsigned raw[4];
-            chroma4(raw, (int)(p[i] ^ 0x80808080u), (int)(p[i + 1] ^ 0x80808080u), (int)(p[i + 2] ^ 0x80808080u), (int)(p[i + 3] ^ 0x80808080u));
+            for (int i = 0; i < 16; i++) {
+                // Y's dot product starts at 2 - 512 (wrap-around; a whole multiple of the divisor, so the arithmetic shift
+                // gives exactly Y - 128), the other two are the definitions' own numerators, halved / quartered as a pair
+                // of signed halves.
+                y[i] = (int)__builtin_amdgcn_udot4(p[i], 0x00010201u, (unsigned)(2 - 512), false) >> 2;                   // -128 .. 127
+            }
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const pk_i16 sh = {1, 2};
-                cc[i + k] = __builtin_bit_cast(unsigned, (pk_i16)(__builtin_bit_cast(pk_i16, raw[k]) >> sh));         // -127 .. 128 each
+            for (int i = 0; i < 16; i += 4) {
+                unsigned raw[4];
+                chroma4(raw, (int)(p[i] ^ 0x80808080u), (int)(p[i + 1] ^ 0x80808080u), (int)(p[i + 2] ^ 0x80808080u), (int)(p[i + 3] ^ 0x80808080u));
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const pk_i16 sh = {1, 2};
+                    cc[i + k] = __builtin_bit_cast(unsigned, (pk_i16)(__builtin_bit_cast(pk_i16, raw[k]) >> sh));         // -127 .. 128 each
+                }
             }
         }
         const uint2 ab = alpha_block<128>(y), cb = ycocg_colour_block(cc);

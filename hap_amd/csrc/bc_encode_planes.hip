@@ -107,6 +107,9 @@ __device__ __forceinline__ void gather_block(const plane_layout &l, const uint8_
 template <int FMT>
 __global__ __launch_bounds__(64) void bc_encode_planes_kernel(HapGpuPictureTable t, unsigned blocks_x, plane_layout l)
 {
+    // (before any return: every lane of the wave must hold its weight row, bc_encode_core.hpp; Hap Q Alpha keeps the
+    // dot-product form -- its kernels hold the pixels for the alpha plane and would lose a wave to the result tuples)
+    const unsigned ycocg_rows = FMT == kFmtYCoCg ? ycocg_weight_rows() : 0u;
     const uint8_t *tensor = (const uint8_t *)picture_address(t, 0);
     uint8_t *out = (uint8_t *)picture_address(t, 1);
     uint8_t *out2 = FMT == kFmtYCoCgAlpha ? (uint8_t *)picture_address(t, 2) : nullptr;
@@ -127,7 +130,7 @@ __global__ __launch_bounds__(64) void bc_encode_planes_kernel(HapGpuPictureTable
         const uint4 b = block_of<FMT>(p);
         *reinterpret_cast<uint2 *>(out + id * 8u) = make_uint2(b.x, b.y);
     } else {
-        *reinterpret_cast<uint4 *>(out + id * 16u) = block_of<FMT == kFmtYCoCgAlpha ? kFmtYCoCg : FMT>(p);
+        *reinterpret_cast<uint4 *>(out + id * 16u) = block_of<FMT == kFmtYCoCgAlpha ? kFmtYCoCg : FMT, FMT == kFmtYCoCg>(p, ycocg_rows);
         if (FMT == kFmtYCoCgAlpha) {
             const uint4 a = block_of<kFmtRGTC1>(p);
             *reinterpret_cast<uint2 *>(out2 + id * 8u) = make_uint2(a.x, a.y);

@@ -127,6 +127,9 @@ __device__ __forceinline__ void source_texels(const uint8_t *__restrict__ blocks
 template <int SRC, bool HAS_ALPHA, int DST, int S>
 __global__ __launch_bounds__(64) void bc_transcode_kernel(HapGpuTranscodeTable t, unsigned blocks_x)
 {
+    // (before any return: every lane of the wave must hold its weight row, bc_encode_core.hpp; Hap Q Alpha keeps the
+    // dot-product form -- its kernels hold the pixels for the alpha plane and would lose a wave to the result tuples)
+    const unsigned ycocg_rows = DST == kFmtYCoCg ? ycocg_weight_rows() : 0u;
     const uint8_t *blocks = (const uint8_t *)transcode_address(t, 0);
     const uint8_t *planes = HAS_ALPHA ? (const uint8_t *)transcode_address(t, 1) : nullptr;
     uint8_t *out = (uint8_t *)transcode_address(t, 2);
@@ -144,7 +147,7 @@ __global__ __launch_bounds__(64) void bc_transcode_kernel(HapGpuTranscodeTable t
         const uint4 b = block_of<kFmtDXT1>(p);
         *reinterpret_cast<uint2 *>(out + id * 8u) = make_uint2(b.x, b.y);
     } else {
-        *reinterpret_cast<uint4 *>(out + id * 16u) = block_of<DST == kFmtYCoCgAlpha ? kFmtYCoCg : DST>(p);
+        *reinterpret_cast<uint4 *>(out + id * 16u) = block_of<DST == kFmtYCoCgAlpha ? kFmtYCoCg : DST, DST == kFmtYCoCg>(p, ycocg_rows);
         if (DST == kFmtYCoCgAlpha) {
             const uint4 a = block_of<kFmtRGTC1>(p);
             *reinterpret_cast<uint2 *>(out2 + id * 8u) = make_uint2(a.x, a.y);

@@ -238,8 +238,11 @@ __device__ __forceinline__ unsigned table_slot(unsigned lo, unsigned hi, unsigne
 #ifndef SCB_MIN_WAVES
 #define SCB_MIN_WAVES 1          // (measurement builds: waves per SIMD the register allocation must leave room for)
 #endif
+// The fused Hap Q kernel is bound to the five waves it has always had: left to itself the allocator parks the
+// transform's two result tuples (four consecutive registers each, bc_encode_core.hpp) above the 96 registers that five
+// waves allow although fewer are live; under the bound it uses 91, without scratch.
 template <unsigned LAYOUT, int FUSED>
-__global__ __launch_bounds__(64, SCB_MIN_WAVES) void snappy_compress_blocks_kernel(const HapGpuFrameEnc *__restrict__ frames,
+__global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5) ? 5 : SCB_MIN_WAVES) void snappy_compress_blocks_kernel(const HapGpuFrameEnc *__restrict__ frames,
                                                                     uint8_t *__restrict__ slots, unsigned slot_stride,
                                                                     uint32_t *__restrict__ frag_sizes,
                                                                     uint8_t *__restrict__ group_tables)
@@ -251,6 +254,8 @@ __global__ __launch_bounds__(64, SCB_MIN_WAVES) void snappy_compress_blocks_kern
     __shared__ uint32_t bounds[66];                      // per group: stream offset of its first element | its output position << 16 (+ the end)
 
     const unsigned lane = threadIdx.x;
+    // (before any return or branch: every lane of the wave must hold its weight row, bc_encode_core.hpp)
+    const unsigned ycocg_rows = FUSED == hapbc::kFmtYCoCg ? hapbc::ycocg_weight_rows() : 0u;
     // Single-texture launches take their frames interleaved: consecutive workgroups work on different frames, so the
     // fragments of one frame that are in flight together are few -- a placed stream waits for the sizes of everything
     // before it in its frame, and with a whole frame in flight every wavefront waited for the slowest of 4000.
@@ -389,7 +394,7 @@ __global__ __launch_bounds__(64, SCB_MIN_WAVES) void snappy_compress_blocks_kern
                         next_block((t + 1u) % kSub);
                     load_pixels(pix[(t + 1u) & 1u], t + 1u);
                 }
-                const uint4 blk = hapbc::block_of<FUSED>(pix[kPrefetch ? t & 1u : 0u]);
+                const uint4 blk = hapbc::block_of<FUSED, FUSED == hapbc::kFmtYCoCg>(pix[kPrefetch ? t & 1u : 0u], ycocg_rows);
                 made = blk;
                 const unsigned bpos = (64u * t + lane) * B;
                 // (the texture is kept for chunks that Snappy does not shrink -- they are stored from there.  A PLACED

@@ -15,7 +15,8 @@ reader's business.  hipcc cross-compiles: no GPU needed.
 The cycle budget of the fused encode kernel (snappy_compress_blocks_kernel<4, YCoCg>, -DSCB_ONLY_FUSED_YCOCG): the same
 attribution, per PHASE (found by anchor text in the sources, so the table follows the code when lines move), each VALU
 instruction weighted by its measured issue cost (tools/micro/valu_rates2.hip at the kernel's five waves per SIMD;
-weights file: opcode -> cycles, "default" for what was not measured), times the phase's trip count for an 8K Hap Q
+weights file: opcode -> cycles, "default" for what was not measured; a matrix instruction has a column of its own and
+counts in `cycles` with what it costs beside VALU, tools/micro/mfma_beside_valu.hip), times the phase's trip count for an 8K Hap Q
 fragment.  Code inlined from the helpers at the top of the file or from a system header (`min`, `max`, popcount, the
 DPP moves) counts under the line of the kernel's body that called it, found from the assembler's inlined-at comments, so
 a phase's row is everything it issues.  Also prints the kernel's register and scratch figures from the code object's
@@ -58,8 +59,9 @@ FUSED_PHASES = [
     ("colour box+covariance", CORE, "__device__ __forceinline__ uint2 ycocg_colour_block", 0, 8.0),
     ("end points", CORE, "const int mo = lo_o + hi_o", 0, 8.0),
     ("colour index", CORE, "const int K = mad24(d_o", 0, 8.0),
-    ("YCoCg transform", CORE, "// 2 (Co - 128) | 4 (Cg - 128) << 16 of four pixels", None, 8.0),
-    ("YCoCg transform", CORE, "template <int FMT>", 0, 8.0),
+    ("YCoCg transform", CORE, "// ---- the YCoCg transform as one 4x4x4 signed-byte matrix product", None, 8.0),
+    ("YCoCg transform", CORE, "2 (Co - 128) | 4 (Cg - 128) << 16 of four pixels", None, 8.0),
+    ("YCoCg transform", CORE, "template <int FMT", 0, 8.0),
     ("loop+address overhead", SCB, "#include <hip/hip_runtime.h>", 0, 1.0),
     ("choose", SCB, "__device__ __forceinline__ int scan_add", 0, 1.0),
     ("nibble transpose", SCB, "// value of lane ^ 4 / ^ 2 / ^ 1", 0, 8.0),
@@ -182,8 +184,11 @@ def fused_budget(args):
             if lo <= cur[1] <= hi:
                 name, trips = nm, tr
                 break
-        row = acc.setdefault(name, {"trips": trips, "valu": 0, "cycles": 0.0, "salu": 0, "lds": 0, "vmem": 0, "nop": 0})
-        if kind == "valu":
+        row = acc.setdefault(name, {"trips": trips, "valu": 0, "mfma": 0, "cycles": 0.0, "salu": 0, "lds": 0, "vmem": 0, "nop": 0})
+        if op.startswith("v_mfma"):         # the matrix pipe: priced in cycles (what it costs beside VALU), not a VALU
+            row["mfma"] += 1
+            row["cycles"] += weights.get(base_op(op), default_w)
+        elif kind == "valu":
             w = weights.get(base_op(op))
             if w is None:
                 w = default_w
@@ -195,17 +200,17 @@ def fused_budget(args):
         elif kind in row:
             row[kind] += 1
     print("weights: %s (%d opcodes measured, default %.2f)" % (os.path.basename(wfile), len(weights) - 1, default_w))
-    print("%-30s %6s %7s %9s | %9s %11s | %5s %5s %5s %5s" % ("phase", "trips", "valu", "cycles", "valu/frag", "cycles/frag",
-                                                              "salu", "lds", "vmem", "s_nop"))
+    print("%-30s %6s %7s %6s %9s | %9s %9s %11s | %5s %5s %5s %5s" % ("phase", "trips", "valu", "mfma", "cycles", "valu/frag",
+                                                                      "mfma/frag", "cycles/frag", "salu", "lds", "vmem", "s_nop"))
     print("(valu, cycles: per trip -- phases with 8 trips are the eight unrolled steps, listed as one step's share)")
-    tv = tc = 0.0
+    tv = tm = tc = 0.0
     for name, r in sorted(acc.items(), key=lambda kv: -frag(kv[1], "cycles")):
         per = 8.0 if r["trips"] == 8.0 else 1.0
-        print("%-30s %6.1f %7.1f %9.1f | %9.0f %11.0f | %5d %5d %5d %5d" % (name, r["trips"], r["valu"] / per, r["cycles"] / per,
-                                                                         frag(r, "valu"), frag(r, "cycles"), r["salu"], r["lds"],
-                                                                         r["vmem"], r["nop"]))
-        tv += frag(r, "valu"); tc += frag(r, "cycles")
-    print("%-30s %6s %7s %9s | %9.0f %11.0f |" % ("per fragment", "", "", "", tv, tc))
+        print("%-30s %6.1f %7.1f %6.1f %9.1f | %9.0f %9.0f %11.0f | %5d %5d %5d %5d" % (
+            name, r["trips"], r["valu"] / per, r["mfma"] / per, r["cycles"] / per, frag(r, "valu"), frag(r, "mfma"),
+            frag(r, "cycles"), r["salu"], r["lds"], r["vmem"], r["nop"]))
+        tv += frag(r, "valu"); tm += frag(r, "mfma"); tc += frag(r, "cycles")
+    print("%-30s %6s %7s %6s %9s | %9.0f %9.0f %11.0f |" % ("per fragment", "", "", "", "", tv, tm, tc))
     for m in meta:
         print("  " + m)
     if unweighted:
