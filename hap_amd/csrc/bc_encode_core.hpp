@@ -33,6 +33,18 @@ __device__ __forceinline__ int quant6(int v) { int t = mad24k<63>(v, 128); retur
 __device__ __forceinline__ int expand5(int q) { return (q << 3) | (q >> 2); }
 __device__ __forceinline__ int expand6(int q) { return (q << 2) | (q >> 4); }
 
+// two 16-bit halves of one register: the Co | Cg pairs of a scaled YCoCg block
+typedef unsigned short pk_u16 __attribute__((ext_vector_type(2)));
+typedef short pk_i16 __attribute__((ext_vector_type(2)));
+
+// both halves of v shifted left by the same count (the low half of sh's register serves both: op_sel_hi)
+__device__ __forceinline__ pk_u16 pk_shl(pk_u16 v, unsigned sh)
+{
+    unsigned r;
+    asm("v_pk_lshlrev_b16 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(r) : "v"(sh), "v"(__builtin_bit_cast(unsigned, v)));
+    return __builtin_bit_cast(pk_u16, r);
+}
+
 
 // Eight 3-bit fields holding (r + 1) mod 8 of the ramp positions r = 0..7 -> their S3TC codes 0->0, 7->1, r->r+1, all at
 // once: (r + 1) mod 8 is the code already for r = 1..6; the two ends come out as 1 and 0 and want 0 and 1 -- the fields
@@ -62,11 +74,12 @@ __device__ __forceinline__ uint2 alpha_block(const int (&a)[16])
         // the nearest of its 8 steps (x * m >> 20 = x / 2d), thresholds moved by the 3/7 the decoder's steps are
         // rounded down on average; 0..7 by construction.  Per pixel: one multiply-add, shift, insert; the codes eight pixels at a time.
         const int d = a0 - a1;
-        // floor(2^19 / d): the reciprocal from v_rcp_f32, made exact
-        unsigned q = (unsigned)(524288.0f * __builtin_amdgcn_rcpf((float)d));
-        const int rem = 524288 - (int)__umul24(q, (unsigned)d);
-        q += (rem >= d ? 1u : 0u) - (rem < 0 ? 1u : 0u);
-        const unsigned m = q + 1u;
+        // floor(2^19 / d) from v_rcp_f32, exact as it comes for d = 1..255: where d does not divide 2^19 the quotient
+        // lies 1 / d or more from a whole number, the reciprocal's one unit in the last place moves it by 1 / (16 d)
+        // at most (2^19 / d x 2^-23; the product with 2^19 is exact), and a power of two has an exact reciprocal.
+        // (tools/micro/rcp_floor_probe.hip asks the instruction: all 255 right; the luma-range sweep of
+        // tests/test_packed_endpoints_gpu.py holds every d with every position against the definition.)
+        const unsigned m = (unsigned)(524288.0f * __builtin_amdgcn_rcpf((float)d)) + 1u;
         // x = (14 (a0 - a) + bias) m as one multiply-add in a
         const int neg_m14 = -(int)(14u * m);                             // |.| < 2^23
         // (+ 2^20: the position comes out as r + 1, 1..8, and x stays below 2^24)
@@ -245,12 +258,107 @@ __device__ __forceinline__ uint2 colour_block(const unsigned (&px)[16])
     return make_uint2(c0 | (c1 << 16), idx);
 }
 
-typedef unsigned short pk_u16 __attribute__((ext_vector_type(2)));
-typedef short pk_i16 __attribute__((ext_vector_type(2)));
-
-// Colour half of a scaled YCoCg-DXT5 block; cc[i] = Co - 128 | (Cg - 128) << 16, signed halves (-127..128): the box, the
-// covariance terms and the scaling work on both halves at once (v_pk_min/max_i16, v_pk_add, v_mad_i32_i16).
+// Colour half of a scaled YCoCg-DXT5 block; cc[i] = Co - 128 | (Cg - 128) << 16, signed halves (-127..128).  Co and Cg
+// stay side by side as a pair of 16-bit halves from the box to the index constants: the box and the sums
+// (v_pk_min/max_i16, v_pk_add), the scale (v_pk_lshlrev_b16), the inset, the quantisation (v_pk_mad_u16 by 31 | 63) and
+// the expansion are packed instructions on both channels at once, the 5:6:5 words, len2, K and the linear term of the
+// covariance are one 16-bit dot product each.  Every intermediate fits its half: the box -127..128, scaled the same
+// range again (the scale is what the range leaves room for), 31 v + 128 and 63 v + 128 at most 16256, directions +-255, scaled directions +-1020, sums +-2048.  The values
+// stay CENTRED (less 128) throughout: the quantiser's constant carries the bias, 31 * 128 + 128 | 63 * 128 + 128, and the
+// 16-bit wrap-around of a negative half times 31 or 63 is undone by adding it (the true sum lies in 0..16256).
+// (tests/test_packed_endpoints_identity.py states this form in 16-bit numpy arrays and compares it with the definition.)
+// The form of the Hap Q destinations (block_of<kFmtYCoCg, true>: the fused kernel, bound by instruction issue, and the
+// block-per-lane kernels); Hap Q Alpha keeps ycocg_colour_block_scalar below.
 __device__ __forceinline__ uint2 ycocg_colour_block(const unsigned (&cc)[16])
+{
+    pk_i16 lo = __builtin_bit_cast(pk_i16, cc[0]), hi = lo;
+#pragma unroll
+    for (int i = 1; i < 16; i++) {
+        const pk_i16 v = __builtin_bit_cast(pk_i16, cc[i]);
+        lo = __builtin_elementwise_min(lo, v);
+        hi = __builtin_elementwise_max(hi, v);
+    }
+    // m = max(-lo, hi) over both channels, 0..128; the scale s = 4, 2, 1 for m <= 31, <= 63, above as a shift count
+    const pk_i16 mm = __builtin_elementwise_max((pk_i16)-lo, hi);
+    const int m = max((int)mm.x, (int)mm.y);
+    const unsigned sh = (unsigned)max(2 - (m >> 5), 0);
+    const unsigned s1 = (1u << sh) - 1u;                                                           // s - 1: the blue field
+    // covariance sign: sum (2 Co - mo)(2 Cg - mg) = 4 sum Co Cg - 2 mg sum Co - 2 mo sum Cg + 16 mo mg with mo = lo + hi
+    // of Co, mg of Cg: per pixel one product-accumulate and one packed add.  (The same number whatever is subtracted
+    // from every Co and every Cg: the centred values stand for the biased ones.)
+    int prod = 0;
+    pk_i16 sums = {0, 0};                                                                          // |.| <= 2048
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        int r;
+        asm("v_mad_i32_i16 %0, %1, %1, %2 op_sel:[0,1,0,0]" : "=v"(r) : "v"(cc[i]), "v"(prod));   // low half x high half + prod
+        prod = r;
+        sums += __builtin_bit_cast(pk_i16, cc[i]);
+    }
+    const pk_i16 mid = lo + hi;                                                                    // mo | mg, -254..256
+    // half the covariance: cov / 2 = 2 prod + mg (4 mo - sum Co) + mo (4 mg - sum Cg), the two products one dot product
+    // of the pair of reduced sums (|.| <= 3072) and mg | mo, with 2 prod as its accumulator
+    const pk_i16 rest = mid * (short)4 - sums;
+    const int half_cov = __builtin_amdgcn_sdot2(rest, mid.yx, 2 * prod, false);
+    // the box scaled about the centre, (x - 128) s, and inset by a sixteenth of its extent
+    pk_u16 ls = pk_shl(__builtin_bit_cast(pk_u16, lo), sh), hs = pk_shl(__builtin_bit_cast(pk_u16, hi), sh);
+    const pk_u16 ins = (pk_u16)(hs - ls) >> 4;                                                     // extent 0..255: no sign
+    ls += ins;
+    hs -= ins;
+    // the two ends: Co's upper end with Cg's upper or, under a negative covariance, lower end -- Cg's halves change
+    // places under a mask made of the covariance's sign (two v_bfi)
+    const unsigned cross = (unsigned)(half_cov >> 31) & 0xFFFF0000u, lsw = __builtin_bit_cast(unsigned, ls), hsw = __builtin_bit_cast(unsigned, hs);
+    const pk_u16 end_a = __builtin_bit_cast(pk_u16, (lsw & cross) | (hsw & ~cross));
+    const pk_u16 end_b = __builtin_bit_cast(pk_u16, (hsw & cross) | (lsw & ~cross));
+    // quant5 | quant6 of the biased values from the centred ones: t = 31 (v + 128) + 128 | 63 (v + 128) + 128
+    const pk_u16 q_mul = {31, 63}, q_add = {31 * 128 + 128, 63 * 128 + 128};
+    const pk_u16 ta = end_a * q_mul + q_add, tb = end_b * q_mul + q_add;
+    const pk_u16 pa = (pk_u16)(ta + (ta >> 8)) >> 8, pb = (pk_u16)(tb + (tb >> 8)) >> 8;           // qo | qg << 16
+    // the 5:6:5 words qo << 11 | qg << 5 | s - 1: the two fields do not meet, so the sum of products is the word
+    const pk_u16 q_place = {1 << 11, 1 << 5};
+    const unsigned qa = __builtin_amdgcn_udot2(pa, q_place, s1, false), qb = __builtin_amdgcn_udot2(pb, q_place, s1, false);
+    const unsigned c0 = max(qa, qb), c1 = min(qa, qb);
+    unsigned idx = 0;
+    if (c0 != c1) {
+        // project4 on the scaled pixels v = (c - 128) s + 128 without forming them, and without complementing: with the
+        // direction SIGNED per channel (16-bit pair, one v_dot2 on the packed Co | Cg pair) the projection of
+        // make_projection(expand_565(c0), expand_565(c1)) is t = s (c . dir) + K: the 255 |dir| of project4's
+        // complemented channels and make_projection's - 255 (sum of |dir| over those channels) cancel, which leaves
+        // K = len2 / 6 + sum over the channels of dir (128 - 128 s - p1).  The end entries are expanded from the
+        // quantised channels at hand, in c0 / c1 order, not unpacked from the 5:6:5 words again.
+        // With the centred c' = c - 128 at hand, t = (c' . s dir) + K', K' = len2 / 6 + sum of dir (128 - p1): the scale
+        // rides in the 16-bit direction (|s dir| <= 1020), K' is the dot product's accumulator, and t is the
+        // definition's own, clamped and turned into a position as in project4.
+        // On pairs: the quantised pairs in c0 / c1 order, expand5 | expand6 of both, dir and 128 - p1 one packed
+        // subtraction each, len2 = dir . dir and K' = dir . (128 - p1) + len2 / 6 one dot product each, s dir one shift.
+        const bool sw = qa < qb;                                                             // c0 is qb
+        const pk_u16 q0 = sw ? pb : pa, q1 = sw ? pa : pb;
+        const pk_u16 up = {3, 2}, down = {2, 4};
+        const pk_u16 p0 = (q0 << up) | (q0 >> down), p1 = (q1 << up) | (q1 >> down);
+        const pk_i16 dir = __builtin_bit_cast(pk_i16, (pk_u16)(p0 - p1)), back = __builtin_bit_cast(pk_i16, (pk_u16)(128 - p1));
+        // The two dot products in one statement, in the three-operand form with the constant 0 (from the builtin the
+        // compiler makes the form that accumulates into its destination, and pays a v_mov of the 0 for each), and with
+        // their wait states by position: the scaled direction and two idle states behind the second, so that every
+        // reader outside the statement, the compiler's or clamped_dot2's, is a safe one.
+        unsigned len2, dir2;                                                                 // len2: 16 .. 130050
+        int dot_back;
+        asm("v_dot2_i32_i16 %[len2], %[d], %[d], 0\n\tv_dot2_i32_i16 %[k], %[d], %[b], 0\n\t"
+            "v_pk_lshlrev_b16 %[d2], %[sh], %[d] op_sel_hi:[0,1]\n\ts_nop 1"
+            : [len2] "=&v"(len2), [k] "=&v"(dot_back), [d2] "=&v"(dir2)
+            : [d] "v"(dir), [b] "v"(back), [sh] "v"(sh));
+        const int sixth = (int)(__umulhi(len2, 0xAAAAAAABu) >> 2);
+        const unsigned m24 = index_scale(len2);
+        const int K = dot_back + sixth, top = (int)len2 + sixth;
+        idx = gather_indices(m24, [&](unsigned (&t)[4], int i) { clamped_dot2(t, cc[i], cc[i + 1], cc[i + 2], cc[i + 3], dir2, K, top); });
+    }
+    return make_uint2(c0 | (c1 << 16), idx);
+}
+
+// The same colour half with the box taken apart into four ints and every step once per value: the form the Hap Q Alpha
+// kernels keep (block_of<kFmtYCoCg, false>).  They run at eight waves and are not bound by instruction issue; with the
+// pair form's fewer but longer-chained instructions their block kernel measured 1.3 - 3.6 % SLOWER (LABNOTES, Part R11),
+// so their code stays what it was.  The same bytes either way (tests/test_packed_endpoints_identity.py).
+__device__ __forceinline__ uint2 ycocg_colour_block_scalar(const unsigned (&cc)[16])
 {
     pk_i16 lo = __builtin_bit_cast(pk_i16, cc[0]), hi = lo;
 #pragma unroll
@@ -262,9 +370,7 @@ __device__ __forceinline__ uint2 ycocg_colour_block(const unsigned (&cc)[16])
     int lo_o = lo.x, hi_o = hi.x, lo_g = lo.y, hi_g = hi.y;
     const int m = max(max(-lo_o, hi_o), max(-lo_g, hi_g));
     const int s = m <= 31 ? 4 : (m <= 63 ? 2 : 1);
-    // covariance sign: sum (2 Co - mo)(2 Cg - mg) = 4 sum Co Cg - 2 mg sum Co - 2 mo sum Cg + 16 mo mg with mo = lo + hi
-    // of Co, mg of Cg: per pixel one product-accumulate and one packed add.  (The same number whatever is subtracted
-    // from every Co and every Cg: the centred values stand for the biased ones.)
+    // covariance sign, as in ycocg_colour_block
     int prod = 0;
     pk_i16 sums = {0, 0};                                                                          // |.| <= 2048
 #pragma unroll
@@ -288,15 +394,7 @@ __device__ __forceinline__ uint2 ycocg_colour_block(const unsigned (&cc)[16])
     const unsigned c0 = max(qa, qb), c1 = min(qa, qb);
     unsigned idx = 0;
     if (c0 != c1) {
-        // project4 on the scaled pixels v = (c - 128) s + 128 without forming them, and without complementing: with the
-        // direction SIGNED per channel (16-bit pair, one v_dot2 on the packed Co | Cg pair) the projection of
-        // make_projection(expand_565(c0), expand_565(c1)) is t = s (c . dir) + K: the 255 |dir| of project4's
-        // complemented channels and make_projection's - 255 (sum of |dir| over those channels) cancel, which leaves
-        // K = len2 / 6 + sum over the channels of dir (128 - 128 s - p1).  The end entries are expanded from the
-        // quantised channels at hand, in c0 / c1 order, not unpacked from the 5:6:5 words again.
-        // With the centred c' = c - 128 at hand, t = (c' . s dir) + K', K' = len2 / 6 + sum of dir (128 - p1): the scale
-        // rides in the 16-bit direction (|s dir| <= 1020), K' is the dot product's accumulator, and t is the
-        // definition's own, clamped and turned into a position as in project4.
+        // t = (c' . s dir) + K', K' = len2 / 6 + sum of dir (128 - p1), as in ycocg_colour_block, per channel
         const bool sw = qa < qb;                                                             // c0 is qb
         const int eo_a = expand5(qo_a), eo_b = expand5(qo_b), eg_a = expand6(qg_a), eg_b = expand6(qg_b);
         const int d_o = sw ? eo_b - eo_a : eo_a - eo_b, d_g = sw ? eg_b - eg_a : eg_a - eg_b;
@@ -410,7 +508,9 @@ __device__ __forceinline__ void chroma4(unsigned (&raw)[4], int q0, int q1, int 
 }
 
 // the 8 or 16 bytes of a block from its sixteen RGBA8 pixels (row-major); 8-byte formats leave z, w zero
-// (MATRIX: the YCoCg transform on the matrix pipe, `rows` the kernel's ycocg_weight_rows(); the same bytes either way)
+// (MATRIX: the Hap Q destinations -- the YCoCg transform on the matrix pipe, `rows` the kernel's ycocg_weight_rows(), and
+// the colour half on Co | Cg pairs; without it, Hap Q Alpha, the dot-product transform and the scalar colour half.  The
+// same bytes either way)
 template <int FMT, bool MATRIX = false>
 __device__ __forceinline__ uint4 block_of(const unsigned (&p)[16], unsigned rows = 0u)
 {
@@ -469,7 +569,7 @@ __device__ __forceinline__ uint4 block_of(const unsigned (&p)[16], unsigned rows
                 }
             }
         }
-        const uint2 ab = alpha_block<128>(y), cb = ycocg_colour_block(cc);
+        const uint2 ab = alpha_block<128>(y), cb = MATRIX ? ycocg_colour_block(cc) : ycocg_colour_block_scalar(cc);
         return make_uint4(ab.x, ab.y, cb.x, cb.y);
     }
 }

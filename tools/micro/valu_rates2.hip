@@ -79,6 +79,15 @@
 #define A_CMPSDWA(x) "v_cmp_ne_u32_sdwa s[20:21], " #x ", %8 src0_sel:WORD_0 src1_sel:WORD_0\n"
 #define A_ADDC64(x) "v_addc_co_u32_e64 " #x ", s[20:21], " #x ", " #x ", s[20:21]\n"
 #define A_CMPADDC64(x) "v_cmp_ne_u32_e64 s[20:21], " #x ", %8\nv_addc_co_u32_e64 " #x ", s[20:21], " #x ", " #x ", s[20:21]\n"
+#define A_PKSUBI(x) "v_pk_sub_i16 " #x ", " #x ", %8\n"
+#define A_PKLSHL(x) "v_pk_lshlrev_b16 " #x ", 1, " #x " op_sel_hi:[0,1]\n"
+#define A_PKMAXI(x) "v_pk_max_i16 " #x ", " #x ", %8\n"
+#define A_PKMINI(x) "v_pk_min_i16 " #x ", " #x ", %8\n"
+#define A_UDOT2(x) "v_dot2_u32_u16 " #x ", " #x ", %8, " #x "\n"
+#define A_DOT2C(x) "v_dot2c_i32_i16 " #x ", " #x ", %8\n"
+#define A_MAXI16(x) "v_max_i16 " #x ", " #x ", %8\n"
+#define A_ASHRI16(x) "v_ashrrev_i16 " #x ", 1, " #x "\n"
+#define A_SUBU16(x) "v_sub_u16 " #x ", " #x ", %8\n"
 KERNEL(k_add, A_ADD) KERNEL(k_and, A_AND) KERNEL(k_lshl, A_LSHL) KERNEL(k_bfe, A_BFE) KERNEL(k_lshlor, A_LSHLOR)
 KERNEL(k_minu, A_MINU) KERNEL(k_mini, A_MINI) KERNEL(k_minf, A_MINF) KERNEL(k_addf, A_ADDF) KERNEL(k_fma, A_FMA)
 KERNEL(k_cvtub, A_CVTUB) KERNEL(k_cvtu, A_CVTU) KERNEL(k_mad24, A_MAD24) KERNEL(k_madi24, A_MADI24) KERNEL(k_cnd, A_CND)
@@ -92,6 +101,8 @@ KERNEL(k_pkmad, A_PKMAD) KERNEL(k_pkmax, A_PKMAX) KERNEL(k_alignbit, A_ALIGNBIT)
 KERNEL(k_max3, A_MAX3) KERNEL(k_dot2, A_DOT2) KERNEL(k_bcnt, A_BCNT) KERNEL(k_adddpp, A_ADDDPP) KERNEL(k_movdpp, A_MOVDPP)
 KERNEL(k_readlane, A_READLANE) KERNEL(k_mullo, A_MULLO) KERNEL(k_mulhi, A_MULHI) KERNEL(k_bitop3, A_BITOP3)
 KERNEL(k_cmpsdwa, A_CMPSDWA) KERNEL(k_addc64, A_ADDC64) KERNEL(k_cmpaddc64, A_CMPADDC64)
+KERNEL(k_pksubi, A_PKSUBI) KERNEL(k_pklshl, A_PKLSHL) KERNEL(k_pkmaxi, A_PKMAXI) KERNEL(k_pkmini, A_PKMINI) KERNEL(k_udot2, A_UDOT2)
+KERNEL(k_dot2c, A_DOT2C) KERNEL(k_maxi16, A_MAXI16) KERNEL(k_ashri16, A_ASHRI16) KERNEL(k_subu16, A_SUBU16)
 static int g_waves = 8;      // waves per SIMD: workgroups of 4 waves, g_waves of them per CU
 template <typename K> void run(const char *name, K kern, unsigned *d)
 {
@@ -120,5 +131,6 @@ int main(int argc, char **argv)
     RUN(k_mul24) RUN(k_pkadd) RUN(k_pklshr) RUN(k_pkmad) RUN(k_pkmax) RUN(k_alignbit) RUN(k_perm) RUN(k_med3i) RUN(k_max3) RUN(k_dot2) RUN(k_bcnt)
     RUN(k_adddpp) RUN(k_movdpp) RUN(k_readlane)
     RUN(k_mullo) RUN(k_mulhi) RUN(k_bitop3) RUN(k_cmpsdwa) RUN(k_addc64) RUN(k_cmpaddc64)       // (two-instruction kernels: cycles per PAIR)
+    RUN(k_pksubi) RUN(k_pklshl) RUN(k_pkmaxi) RUN(k_pkmini) RUN(k_udot2) RUN(k_dot2c) RUN(k_maxi16) RUN(k_ashri16) RUN(k_subu16)      // round 11: the pair form
     return 0;
 }
