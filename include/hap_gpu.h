@@ -39,6 +39,11 @@
  * Section 0x46, version 1:  [1][log2 F][granularity log2][match window / 256 B][LE32 compressed size x fragments]
  *               version 4:  [4][13][granularity log2 | fields per block << 4][window][LE32 size x fragments]
  *                           [196-byte group table x fragments]
+ * Version 1 promises, of every fragment: it is Snappy elements of any form (literals with up to four length bytes,
+ * copy-1, copy-2, copy-4) that make exactly F bytes (the last fragment of a chunk: the rest); no copy reaches before
+ * the fragment's first byte; every length and every copy offset is a multiple of the granularity; and, where the
+ * window byte is 1..12 and F is 8 KiB, no copy offset exceeds 3072.  The entries of a chunk add up to the chunk less
+ * its length prefix.
  * Version 4 ("field streams": block textures, 8 KiB fragments) adds, per fragment, a table of 64 groups of its
  * elements -- the elements in stream order, ceil(N / 64) to a group, the last groups shorter or empty: 24 bits per
  * group, little endian, the group's compressed bytes | the bytes it produces << 12; then N (LE16) and two zero bytes --
