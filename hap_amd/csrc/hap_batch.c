@@ -281,6 +281,13 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
         if (flags & HAPGPU_ENCODE_FRAGMENT_INDEX)
             ilen += 8u + (g[0].half_tiles ? 4u + HAP_GROUP_TABLE_BYTES : 4u) * frags;
         placed_extent = outer_header + 8u + 4u + ilen + 5u * (size_t)g[0].chunk_count + g[0].bytes + frags * (frag_bytes / 32u + 64u);
+        /* the compressor's wavefronts add up what lies before them in the frame in 32 bits: every such sum is a
+           position below this extent (a texture is below 4 GiB, but its fragments at their largest need not be).
+           Beyond it the frame goes through slots. */
+        if (placed_extent > 0xFFFFFFFFul) {
+            placed = 0u;
+            placed_extent = 0;
+        }
     }
 
     /* per-frame checks; frames that fail are left out of the launch */
@@ -401,6 +408,7 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                 fe->rgba = job->host_table[f];
                 fe->rgba_row_bytes = (uint32_t)job->row_bytes;
                 fe->rgba_blocks_x = job->width / 4u;
+                fe->rgba_blocks_x_inv = HAPGPU_DIV_INV(job->width / 4u);
             }
             for (i = 0; i < count; i++) {
                 HapGpuTexEnc *te = &fe->tex[i];
@@ -419,6 +427,7 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                 te->chunk_bytes = g[i].chunk_bytes;
                 te->header_len = g[i].header_len;
                 te->frags_per_chunk = g[i].fpc;
+                te->frags_per_chunk_inv = HAPGPU_DIV_INV(g[i].fpc ? g[i].fpc : 1u);
                 te->frag_first = k * frags_per_frame + (i ? g[0].chunk_count * g[0].fpc : 0u);
                 te->emit_index = (flags & HAPGPU_ENCODE_FRAGMENT_INDEX) ? 1u : 0u;
                 /* 8 KiB fragments keep hash matches within 3 KiB so that the decoder can halve its ring -- except for

@@ -86,7 +86,11 @@ typedef struct HapGpuTexEnc {
                                 assumption that every chunk shrinks; the pack kernel reports HAPGPU_STATUS_NOT_PLACED
                                 for a frame where one did not (or a wavefront gave up waiting), and the host encodes that
                                 frame again through slots.  First texture of a frame only. */
+    uint32_t frags_per_chunk_inv; /* HAPGPU_DIV_INV(frags_per_chunk) */
 } HapGpuTexEnc;
+/* what the compressor's wavefronts divide by without dividing: floor(x inv / 2^32) is x / d or one short of it for
+   every 32-bit x (d >= 1) */
+#define HAPGPU_DIV_INV(d) (0xFFFFFFFFu / (uint32_t)(d))
 #define HAPGPU_FRAG_PUBLISHED 0x80000000u
 #define HAPGPU_STATUS_NOT_PLACED 0x7E50u
 
@@ -105,6 +109,8 @@ typedef struct HapGpuFrameEnc {
     uint64_t rgba;
     uint32_t rgba_row_bytes; /* (the picture is smaller than 4 GiB) */
     uint32_t rgba_blocks_x;  /* width / 4 */
+    uint32_t rgba_blocks_x_inv; /* HAPGPU_DIV_INV(rgba_blocks_x) */
+    uint32_t reserved2;
     /* textures whose reserved bit 27 is set: one 64-bit word per chunk of the frame (zero before the launch), in which
        the compressor's wavefronts add up fragments << 32 | bytes as they learn their sizes */
     uint64_t chunk_acc;

@@ -143,6 +143,22 @@ __device__ __forceinline__ unsigned bytes_under(unsigned S, unsigned L, unsigned
 // all ones if bit `bit` of v is set, else 0
 __device__ __forceinline__ unsigned bit_mask(unsigned v, unsigned bit) { return (unsigned)__builtin_amdgcn_sbfe((int)v, bit, 1u); }
 
+// (1 << 20) / G + 1 for the G = 1 .. 32 elements a group of the fragment table can have (at most 2048 elements a
+// fragment): G is wave-uniform, the entry one scalar load where the division was a vector reciprocal sequence
+__constant__ const unsigned kGroupInv[33] = {
+    0u, 1048577u, 524289u, 349526u, 262145u, 209716u, 174763u, 149797u, 131073u, 116509u, 104858u,
+    95326u, 87382u, 80660u, 74899u, 69906u, 65537u, 61681u, 58255u, 55189u, 52429u, 49933u,
+    47663u, 45591u, 43691u, 41944u, 40330u, 38837u, 37450u, 36158u, 34953u, 33826u, 32769u};
+
+// x / d with inv = HAPGPU_DIV_INV(d) from the host (hapgpu_abi.h): floor(x inv / 2^32) is the quotient or one short of
+// it for every 32-bit x, so a multiply-high and one correction -- scalar instructions where x is wave-uniform, five
+// vector ones where it is the lane's own, where a division is a reciprocal sequence of twenty
+__device__ __forceinline__ unsigned div_by(unsigned x, unsigned d, unsigned inv)
+{
+    const unsigned q = __umulhi(x, inv);
+    return q + (x - q * d >= d ? 1u : 0u);
+}
+
 __device__ __forceinline__ int scan_add(int v)          // inclusive, across the wavefront
 {
     v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);
@@ -245,7 +261,7 @@ template <unsigned LAYOUT, int FUSED>
 __global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5) ? 5 : SCB_MIN_WAVES) void snappy_compress_blocks_kernel(const HapGpuFrameEnc *__restrict__ frames,
                                                                     uint8_t *__restrict__ slots, unsigned slot_stride,
                                                                     uint32_t *__restrict__ frag_sizes,
-                                                                    uint8_t *__restrict__ group_tables)
+                                                                    uint8_t *__restrict__ group_tables, unsigned frames_inv)
 {
     using UL = unit_layout<LAYOUT>;
     constexpr unsigned B = UL::block;
@@ -263,8 +279,9 @@ __global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5
     const unsigned zf = blockIdx.z, x = blockIdx.x;
 #else
     const unsigned linear = blockIdx.z * gridDim.x + blockIdx.x;
-    const unsigned zf = gridDim.y == 1u ? linear % gridDim.z : blockIdx.z;
-    const unsigned x = gridDim.y == 1u ? linear / gridDim.z : blockIdx.x;
+    const unsigned round = div_by(linear, gridDim.z, frames_inv);            // (frames_inv: HAPGPU_DIV_INV(gridDim.z), the launcher's)
+    const unsigned zf = gridDim.y == 1u ? linear - round * gridDim.z : blockIdx.z;
+    const unsigned x = gridDim.y == 1u ? round : blockIdx.x;
 #endif
     const HapGpuTexEnc tex = frames[zf].tex[blockIdx.y < 2u ? blockIdx.y : 0u];
     const unsigned tex_count = frames[zf].tex_count;
@@ -272,7 +289,7 @@ __global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5
         (x >= tex.chunk_count * tex.frags_per_chunk) | (tex.src == 0) | (tex.chunk_bytes == 0) |
         (((tex.reserved >> 24) & 7u) != (unsigned)(FUSED + 1)))
         return;
-    const unsigned chunk = x / tex.frags_per_chunk, fj = x - chunk * tex.frags_per_chunk;
+    const unsigned chunk = div_by(x, tex.frags_per_chunk, tex.frags_per_chunk_inv), fj = x - chunk * tex.frags_per_chunk;
     const unsigned begin = fj * kFragBytes;
     const unsigned n = min(kFragBytes, tex.chunk_bytes - begin);          // whole blocks (host-checked)
     const gsrc_t src = (gsrc_t)(tex.src + (uint64_t)chunk * tex.chunk_bytes + begin);
@@ -311,7 +328,7 @@ __global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5
     constexpr unsigned kSub = 16u / B;
     __shared__ __attribute__((aligned(16))) uint4 ring[FUSED >= 0 ? 68u : 1u];   // the step's units behind the last four of the one before
     const gsrc_t rgba = (gsrc_t)frames[zf].rgba;
-    const unsigned row_bytes = frames[zf].rgba_row_bytes, blocks_x = frames[zf].rgba_blocks_x;
+    const unsigned row_bytes = frames[zf].rgba_row_bytes, blocks_x = frames[zf].rgba_blocks_x, blocks_x_inv = frames[zf].rgba_blocks_x_inv;
     unsigned bx[kSub], row_at[kSub], first_off = 0u;      // block column, byte offset of the block row's first pixel row
     // Pixels a pass ahead of their use -- where that does not cost a wave: the YCoCg kernel has 88 registers without
     // the second pixel buffer (five waves per SIMD) and 112 with it (four), and five waves that wait for their pixels
@@ -325,6 +342,15 @@ __global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5
     // 16-byte blocks: the lane's unit of step s lies wholly inside the data (n is whole blocks) -- the one compare
     // behind every "is it there" of the step
     auto whole_unit = [&](unsigned s) { return (int)lane < (int)(n >> 4) - (int)(64u * s); };
+    // The four pixel rows of a block: their bases rgba + r row_bytes are wave-uniform and stay in scalar registers, the
+    // lane's part is one 32-bit offset a pass -- the load's scalar-base form, no 64-bit vector add a row.  (Opaque to
+    // the optimiser, which otherwise adds the lane's offset to rgba first and r row_bytes to that, as a vector pair.)
+    unsigned long long row_base[4];
+#pragma unroll
+    for (unsigned r = 0; r < 4u; r++) {
+        row_base[r] = (unsigned long long)(uintptr_t)rgba + (unsigned long long)r * row_bytes;
+        asm("" : "+s"(row_base[r]));
+    }
     // pass t = kSub s + sub: its pixels
     auto load_pixels = [&](unsigned (&p)[16], unsigned t) {
         const unsigned sub = t % kSub;
@@ -332,7 +358,7 @@ __global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5
         const unsigned at = there ? row_at[sub] + 16u * bx[sub] : first_off;     // (no lane-varying branch around the loads)
 #pragma unroll
         for (unsigned r = 0; r < 4u; r++) {
-            const uint4 v = get128(rgba + (at + r * row_bytes));
+            const uint4 v = get128((gsrc_t)(uintptr_t)row_base[r] + at);
             p[4u * r] = v.x; p[4u * r + 1u] = v.y; p[4u * r + 2u] = v.z; p[4u * r + 3u] = v.w;
         }
     };
@@ -347,13 +373,13 @@ __global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5
     if (FUSED >= 0) {
         const unsigned first_block = (unsigned)(((uint64_t)chunk * tex.chunk_bytes + begin) / B);
         {
-            const unsigned fy = first_block / blocks_x, fx = first_block - fy * blocks_x;
+            const unsigned fy = div_by(first_block, blocks_x, blocks_x_inv), fx = first_block - fy * blocks_x;
             first_off = (4u * fy) * row_bytes + 16u * fx;
         }
 #pragma unroll
         for (unsigned j = 0; j < kSub; j++) {
             const unsigned b = first_block + 64u * j + lane;
-            const unsigned by = b / blocks_x;
+            const unsigned by = div_by(b, blocks_x, blocks_x_inv);
             bx[j] = b - by * blocks_x;
             row_at[j] = (4u * by) * row_bytes;
         }
@@ -653,7 +679,9 @@ __global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5
     if (placed) {
         const unsigned long long *acc = reinterpret_cast<const unsigned long long *>(frames[zf].chunk_acc);
         const uint32_t *mine = frag_sizes + tex.frag_first + chunk * tex.frags_per_chunk;
-        unsigned long long sum = 0;
+        // (both totals are byte counts inside ONE frame's section, below 2^32: hap_batch.c places a frame only if its
+        // furthest possible extent is; they widen where the address is formed)
+        unsigned sum = 0;
         unsigned in_chunk = 0;
         unsigned tries = 0;
         bool settled = true;
@@ -666,7 +694,7 @@ __global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5
                 const unsigned long long v = c < chunk ? __hip_atomic_load(&acc[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                                                        : (1ull << 32);
                 if (__builtin_amdgcn_ballot_w64((unsigned)(v >> 32) == 0u) == 0ull) {
-                    sum += v & 0xFFFFFFFFull;
+                    sum += (unsigned)v;
                     settled = __builtin_amdgcn_ballot_w64((unsigned)(v >> 32) != 1u) == 0ull;      // (2: a chunk that gave up)
                     break;
                 }
@@ -694,11 +722,9 @@ __global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5
         }
         const unsigned own_bytes = (unsigned)__builtin_amdgcn_readlane((int)counts_and_bytes, 63) & 0xFFFFu;
         if (settled) {
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) {
-                sum += __shfl_xor(sum, d);
-                in_chunk += __shfl_xor(in_chunk, d);
-            }
+            // the wavefront's totals: a scan across it each (DPP adds, no LDS), read from its last lane into scalars
+            sum = (unsigned)__builtin_amdgcn_readlane(scan_add((int)sum), 63);
+            in_chunk = (unsigned)__builtin_amdgcn_readlane(scan_add((int)in_chunk), 63);
             // the chunk's last fragment has just added up the whole chunk: its total, for the chunks behind
             // (plain stores and loads only: read-modify-writes from every wavefront on a few words were served one
             // after the other, 60 ns each)
@@ -786,7 +812,7 @@ __global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5
         const unsigned stream_bytes = (unsigned)__builtin_amdgcn_readlane((int)both, 63) & 0xFFFFu;
         const unsigned elements = (unsigned)__builtin_amdgcn_readlane((int)both, 63) >> 16;        // >= 1
         const unsigned G = (elements + 63u) >> 6;
-        const unsigned inv = (1u << 20) / G + 1u;                              // x / G = (x inv) >> 20 for x < 2^11 + 32
+        const unsigned inv = kGroupInv[min(G, 32u)];                           // (1 << 20) / G + 1: x / G = (x inv) >> 20 for x < 2^11 + 32
         const uint32_t *hd_tab = reinterpret_cast<const uint32_t *>(table);
         {
             bounds[lane] = stream_bytes | (n << 16);                           // (groups beyond the last element: empty)
@@ -869,7 +895,7 @@ int hapgpu_snappy_compress_blocks(const HapGpuFrameEnc *frames, unsigned frame_c
     const dim3 grid(max_frags_per_texture, textures, frame_count), block(64);
 #define HAP_LAUNCH_BLOCKS(L, F)                                                                                                  \
     hipLaunchKernelGGL((snappy_compress_blocks_kernel<L, F>), grid, block, 0, stream, frames, (uint8_t *)slots, slot_stride,    \
-                       frag_sizes, group_tables)
+                       frag_sizes, group_tables, HAPGPU_DIV_INV(frame_count))
     if (fused & 1u)
         HAP_LAUNCH_BLOCKS(4u, hapbc::kFmtYCoCg);
 #ifndef SCB_ONLY_FUSED_YCOCG          // (instruction-count studies, tools/isa_by_line.py: that instantiation alone)

@@ -191,7 +191,7 @@ def fused_budget(args):
             row["mfma"] += 1
             row["cycles"] += weights.get(base_op(op), default_w)
         elif kind == "valu":
-            w = weights.get(base_op(op))
+            w = weights.get(op, weights.get(base_op(op)))      # (an SDWA form weighed on its own goes by its own name)
             if w is None:
                 w = default_w
                 unweighted[base_op(op)] += 1

@@ -88,6 +88,18 @@
 #define A_MAXI16(x) "v_max_i16 " #x ", " #x ", %8\n"
 #define A_ASHRI16(x) "v_ashrrev_i16 " #x ", 1, " #x "\n"
 #define A_SUBU16(x) "v_sub_u16 " #x ", " #x ", %8\n"
+// round 12: the Co | Cg pack -- a 32-bit arithmetic shift straight into a half of its destination (SDWA), the second
+// one keeping the first one's half, and the two back to back on one register as the kernel would issue them; beside
+// it the packed shift and the v_perm_b32 + packed shift pair they would replace
+#define A_ASHRSDWA0(x) "v_ashrrev_i32_sdwa " #x ", 2, " #x " dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:DWORD\n"
+#define A_ASHRSDWA1(x) "v_ashrrev_i32_sdwa " #x ", 2, %8 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n"
+#define A_ASHRSDWA01(x) "v_ashrrev_i32_sdwa " #x ", 2, " #x " dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:DWORD\n" \
+                        "s_nop 0\n"                                                                                                  \
+                        "v_ashrrev_i32_sdwa " #x ", 2, %8 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n"
+#define A_PKASHRI(x) "v_pk_ashrrev_i16 " #x ", 2, " #x " op_sel_hi:[0,1]\n"
+#define A_PERMPKASHR(x) "v_perm_b32 " #x ", %8, " #x ", s22\nv_pk_ashrrev_i16 " #x ", 2, " #x " op_sel_hi:[0,1]\n"
+KERNEL(k_ashrsdwa0, A_ASHRSDWA0) KERNEL(k_ashrsdwa1, A_ASHRSDWA1) KERNEL(k_ashrsdwa01, A_ASHRSDWA01) KERNEL(k_pkashri, A_PKASHRI)
+KERNEL(k_permpkashr, A_PERMPKASHR)
 KERNEL(k_add, A_ADD) KERNEL(k_and, A_AND) KERNEL(k_lshl, A_LSHL) KERNEL(k_bfe, A_BFE) KERNEL(k_lshlor, A_LSHLOR)
 KERNEL(k_minu, A_MINU) KERNEL(k_mini, A_MINI) KERNEL(k_minf, A_MINF) KERNEL(k_addf, A_ADDF) KERNEL(k_fma, A_FMA)
 KERNEL(k_cvtub, A_CVTUB) KERNEL(k_cvtu, A_CVTU) KERNEL(k_mad24, A_MAD24) KERNEL(k_madi24, A_MADI24) KERNEL(k_cnd, A_CND)
@@ -132,5 +144,6 @@ int main(int argc, char **argv)
     RUN(k_adddpp) RUN(k_movdpp) RUN(k_readlane)
     RUN(k_mullo) RUN(k_mulhi) RUN(k_bitop3) RUN(k_cmpsdwa) RUN(k_addc64) RUN(k_cmpaddc64)       // (two-instruction kernels: cycles per PAIR)
     RUN(k_pksubi) RUN(k_pklshl) RUN(k_pkmaxi) RUN(k_pkmini) RUN(k_udot2) RUN(k_dot2c) RUN(k_maxi16) RUN(k_ashri16) RUN(k_subu16)      // round 11: the pair form
+    RUN(k_ashrsdwa0) RUN(k_ashrsdwa1) RUN(k_pkashri) RUN(k_ashrsdwa01) RUN(k_permpkashr)      // round 12: the Co | Cg pack (the last two: cycles per PAIR)
     return 0;
 }
