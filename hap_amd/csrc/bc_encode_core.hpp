@@ -258,48 +258,96 @@ __device__ __forceinline__ uint2 colour_block(const unsigned (&px)[16])
     return make_uint2(c0 | (c1 << 16), idx);
 }
 
-// Colour half of a scaled YCoCg-DXT5 block; cc[i] = Co - 128 | (Cg - 128) << 16, signed halves (-127..128).  Co and Cg
-// stay side by side as a pair of 16-bit halves from the box to the index constants: the box and the sums
-// (v_pk_min/max_i16, v_pk_add), the scale (v_pk_lshlrev_b16), the inset, the quantisation (v_pk_mad_u16 by 31 | 63) and
-// the expansion are packed instructions on both channels at once, the 5:6:5 words, len2, K and the linear term of the
-// covariance are one 16-bit dot product each.  Every intermediate fits its half: the box -127..128, scaled the same
-// range again (the scale is what the range leaves room for), 31 v + 128 and 63 v + 128 at most 16256, directions +-255, scaled directions +-1020, sums +-2048.  The values
-// stay CENTRED (less 128) throughout: the quantiser's constant carries the bias, 31 * 128 + 128 | 63 * 128 + 128, and the
-// 16-bit wrap-around of a negative half times 31 or 63 is undone by adding it (the true sum lies in 0..16256).
-// (tests/test_packed_endpoints_identity.py states this form in 16-bit numpy arrays and compares it with the definition.)
-// The form of the Hap Q destinations (block_of<kFmtYCoCg, true>: the fused kernel, bound by instruction issue, and the
-// block-per-lane kernels); Hap Q Alpha keeps ycocg_colour_block_scalar below.
+// Colour half of a scaled YCoCg-DXT5 block.  Co and Cg stay side by side as a pair of 16-bit halves from the box to the
+// index constants, in one of two representations of the pixels:
+//   BIASED       cc[i] = Co | Cg << 16, the definition's own values, 1..256 a half (the transform's addend tuple carries
+//                the 128, ycocg_addend()): the fused kernel, which is bound by instruction issue;
+//   not BIASED   cc[i] = Co - 128 | (Cg - 128) << 16, signed halves -127..128 (the transform with the inline constant):
+//                the block-per-lane kernels, which are bound by memory and by their registers -- the tuple's four would
+//                cost them a wave -- and keep the box by v_pk_min/max_i16 and the sums by v_pk_add_u16.
+// The BIASED pixel loops use what NON-NEGATIVE halves allow:
+//   * the box by v_pk_minimum3_f16 / v_pk_maximum3_f16, three pairs an instruction (8 + 8 where the two-input integer
+//     forms took 15 + 16): a non-negative 16-bit integer below 0x7C00 read as an IEEE half orders as the integer does, and
+//     the instruction returns one of its operands bit for bit -- 1..256 are subnormal halves, which the kernels' float
+//     mode keeps (tools/micro/pk_minmax3_probe.hip asks the hardware);
+//   * sum Co | sum Cg by 32-bit adds on the words (v_add3_u32): sixteen halves of at most 256 make at most 4096, so
+//     nothing carries from Co's half into Cg's;
+//   * sum Co Cg by v_mad_i32_i16 as before, products at most 2^16, sixteen of them at most 2^20.
+// The covariance's sign is the same number whatever is added to every Co and every Cg, so it is taken from the biased
+// values as they stand (mid = lo + hi 2..512, 4 mid - sums -3068..2032).  Once a block the box is RECENTRED, lo and hi
+// less 128 | 128 (-127..128), and from there on the per-block work is the same in both representations: the scale (v_pk_lshlrev_b16; the
+// scale is what the range leaves room for), the inset, the quantisation (v_pk_mad_u16 by 31 | 63, the constant carries
+// the bias, 31 * 128 + 128 | 63 * 128 + 128, and the 16-bit wrap-around of a negative half times 31 or 63 is undone by
+// adding it: the true sum lies in 0..16256) and the expansion are packed instructions on both channels at once, the
+// 5:6:5 words, len2 and K one 16-bit dot product each (directions +-255, scaled directions +-1020).  The projection
+// takes the pixels as they are: for BIASED ones its constant carries the - 128 (s d_o + s d_g), one more dot product a
+// block.
+// (tests/test_packed_endpoints_identity.py states the per-block form in 16-bit numpy arrays and compares it with the
+// definition, tests/test_biased_pairs_identity.py the biased pixel loops and the projection constant.)
+// The form of the Hap Q destinations (block_of<kFmtYCoCg, true, BIASED>); Hap Q Alpha keeps ycocg_colour_block_scalar
+// below, on centred halves.
+template <bool BIASED>
 __device__ __forceinline__ uint2 ycocg_colour_block(const unsigned (&cc)[16])
 {
-    pk_i16 lo = __builtin_bit_cast(pk_i16, cc[0]), hi = lo;
+    const auto pk_minimum3 = [](unsigned a, unsigned b, unsigned c) {
+        unsigned r;
+        asm("v_pk_minimum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+        return r;
+    };
+    const auto pk_maximum3 = [](unsigned a, unsigned b, unsigned c) {
+        unsigned r;
+        asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+        return r;
+    };
+    pk_i16 lo_b = __builtin_bit_cast(pk_i16, cc[0]), hi_b = lo_b;                                  // the box as cc has it
+    if (BIASED) {
+        unsigned lo_w = pk_minimum3(cc[0], cc[1], cc[2]), hi_w = pk_maximum3(cc[0], cc[1], cc[2]);
 #pragma unroll
-    for (int i = 1; i < 16; i++) {
-        const pk_i16 v = __builtin_bit_cast(pk_i16, cc[i]);
-        lo = __builtin_elementwise_min(lo, v);
-        hi = __builtin_elementwise_max(hi, v);
+        for (int i = 3; i < 15; i += 2) {
+            lo_w = pk_minimum3(lo_w, cc[i], cc[i + 1]);
+            hi_w = pk_maximum3(hi_w, cc[i], cc[i + 1]);
+        }
+        lo_b = __builtin_bit_cast(pk_i16, pk_minimum3(lo_w, cc[15], cc[15]));                      // 1..256
+        hi_b = __builtin_bit_cast(pk_i16, pk_maximum3(hi_w, cc[15], cc[15]));
+    } else {
+#pragma unroll
+        for (int i = 1; i < 16; i++) {
+            const pk_i16 v = __builtin_bit_cast(pk_i16, cc[i]);
+            lo_b = __builtin_elementwise_min(lo_b, v);
+            hi_b = __builtin_elementwise_max(hi_b, v);
+        }
     }
-    // m = max(-lo, hi) over both channels, 0..128; the scale s = 4, 2, 1 for m <= 31, <= 63, above as a shift count
-    const pk_i16 mm = __builtin_elementwise_max((pk_i16)-lo, hi);
-    const int m = max((int)mm.x, (int)mm.y);
-    const unsigned sh = (unsigned)max(2 - (m >> 5), 0);
-    const unsigned s1 = (1u << sh) - 1u;                                                           // s - 1: the blue field
     // covariance sign: sum (2 Co - mo)(2 Cg - mg) = 4 sum Co Cg - 2 mg sum Co - 2 mo sum Cg + 16 mo mg with mo = lo + hi
-    // of Co, mg of Cg: per pixel one product-accumulate and one packed add.  (The same number whatever is subtracted
-    // from every Co and every Cg: the centred values stand for the biased ones.)
+    // of Co, mg of Cg: per pixel one product-accumulate and one add of the pair, 32-bit where no half is negative,
+    // packed otherwise.  (The same number whatever is added to every Co and every Cg: centred or biased, the values
+    // stand for themselves.)
     int prod = 0;
-    pk_i16 sums = {0, 0};                                                                          // |.| <= 2048
+    unsigned sum_w = 0;                                                                            // <= 4096 a half
+    pk_i16 sum_pk = {0, 0};                                                                        // |.| <= 2048
 #pragma unroll
     for (int i = 0; i < 16; i++) {
         int r;
         asm("v_mad_i32_i16 %0, %1, %1, %2 op_sel:[0,1,0,0]" : "=v"(r) : "v"(cc[i]), "v"(prod));   // low half x high half + prod
         prod = r;
-        sums += __builtin_bit_cast(pk_i16, cc[i]);
+        if (BIASED)
+            sum_w += cc[i];
+        else
+            sum_pk += __builtin_bit_cast(pk_i16, cc[i]);
     }
-    const pk_i16 mid = lo + hi;                                                                    // mo | mg, -254..256
+    const pk_i16 sums = BIASED ? __builtin_bit_cast(pk_i16, sum_w) : sum_pk;
+    const pk_i16 mid = lo_b + hi_b;                                                                // mo | mg, 2..512 or -254..256
     // half the covariance: cov / 2 = 2 prod + mg (4 mo - sum Co) + mo (4 mg - sum Cg), the two products one dot product
     // of the pair of reduced sums (|.| <= 3072) and mg | mo, with 2 prod as its accumulator
     const pk_i16 rest = mid * (short)4 - sums;
     const int half_cov = __builtin_amdgcn_sdot2(rest, mid.yx, 2 * prod, false);
+    // the box recentred, -127..128: what m, the scale, the scaled box and the inset are stated on
+    const pk_i16 centre = {128, 128};
+    const pk_i16 lo = BIASED ? lo_b - centre : lo_b, hi = BIASED ? hi_b - centre : hi_b;
+    // m = max(-lo, hi) over both channels, 0..128; the scale s = 4, 2, 1 for m <= 31, <= 63, above as a shift count
+    const pk_i16 mm = __builtin_elementwise_max((pk_i16)-lo, hi);
+    const int m = max((int)mm.x, (int)mm.y);
+    const unsigned sh = (unsigned)max(2 - (m >> 5), 0);
+    const unsigned s1 = (1u << sh) - 1u;                                                           // s - 1: the blue field
     // the box scaled about the centre, (x - 128) s, and inset by a sixteenth of its extent
     pk_u16 ls = pk_shl(__builtin_bit_cast(pk_u16, lo), sh), hs = pk_shl(__builtin_bit_cast(pk_u16, hi), sh);
     const pk_u16 ins = (pk_u16)(hs - ls) >> 4;                                                     // extent 0..255: no sign
@@ -326,9 +374,10 @@ __device__ __forceinline__ uint2 ycocg_colour_block(const unsigned (&cc)[16])
         // complemented channels and make_projection's - 255 (sum of |dir| over those channels) cancel, which leaves
         // K = len2 / 6 + sum over the channels of dir (128 - 128 s - p1).  The end entries are expanded from the
         // quantised channels at hand, in c0 / c1 order, not unpacked from the 5:6:5 words again.
-        // With the centred c' = c - 128 at hand, t = (c' . s dir) + K', K' = len2 / 6 + sum of dir (128 - p1): the scale
-        // rides in the 16-bit direction (|s dir| <= 1020), K' is the dot product's accumulator, and t is the
-        // definition's own, clamped and turned into a position as in project4.
+        // With the centred c' = c - 128, t = (c' . s dir) + K', K' = len2 / 6 + sum of dir (128 - p1): the scale rides in
+        // the 16-bit direction (|s dir| <= 1020).  Where the pixels at hand are the biased c, the dot product's
+        // accumulator is K = K' - 128 (s d_o + s d_g), |.| below 2^19, one dot product of s dir with -128 | -128 on top
+        // of dir . (128 - p1); t is the definition's own, clamped and turned into a position as in project4.
         // On pairs: the quantised pairs in c0 / c1 order, expand5 | expand6 of both, dir and 128 - p1 one packed
         // subtraction each, len2 = dir . dir and K' = dir . (128 - p1) + len2 / 6 one dot product each, s dir one shift.
         const bool sw = qa < qb;                                                             // c0 is qb
@@ -339,13 +388,22 @@ __device__ __forceinline__ uint2 ycocg_colour_block(const unsigned (&cc)[16])
         // The two dot products in one statement, in the three-operand form with the constant 0 (from the builtin the
         // compiler makes the form that accumulates into its destination, and pays a v_mov of the 0 for each), and with
         // their wait states by position: the scaled direction and two idle states behind the second, so that every
-        // reader outside the statement, the compiler's or clamped_dot2's, is a safe one.
+        // reader outside the statement, the compiler's or clamped_dot2's, is a safe one.  The BIASED form's third takes
+        // the second's result as its accumulator, which a dot product of the same opcode may do without waiting, and
+        // three idle states follow it.
         unsigned len2, dir2;                                                                 // len2: 16 .. 130050
         int dot_back;
-        asm("v_dot2_i32_i16 %[len2], %[d], %[d], 0\n\tv_dot2_i32_i16 %[k], %[d], %[b], 0\n\t"
-            "v_pk_lshlrev_b16 %[d2], %[sh], %[d] op_sel_hi:[0,1]\n\ts_nop 1"
-            : [len2] "=&v"(len2), [k] "=&v"(dot_back), [d2] "=&v"(dir2)
-            : [d] "v"(dir), [b] "v"(back), [sh] "v"(sh));
+        if (BIASED)
+            asm("v_dot2_i32_i16 %[len2], %[d], %[d], 0\n\tv_dot2_i32_i16 %[k], %[d], %[b], 0\n\t"
+                "v_pk_lshlrev_b16 %[d2], %[sh], %[d] op_sel_hi:[0,1]\n\t"
+                "v_dot2_i32_i16 %[k], %[d2], %[uncentre], %[k]\n\ts_nop 2"
+                : [len2] "=&v"(len2), [k] "=&v"(dot_back), [d2] "=&v"(dir2)
+                : [d] "v"(dir), [b] "v"(back), [sh] "v"(sh), [uncentre] "s"(0xFF80FF80u));
+        else
+            asm("v_dot2_i32_i16 %[len2], %[d], %[d], 0\n\tv_dot2_i32_i16 %[k], %[d], %[b], 0\n\t"
+                "v_pk_lshlrev_b16 %[d2], %[sh], %[d] op_sel_hi:[0,1]\n\ts_nop 1"
+                : [len2] "=&v"(len2), [k] "=&v"(dot_back), [d2] "=&v"(dir2)
+                : [d] "v"(dir), [b] "v"(back), [sh] "v"(sh));
         const int sixth = (int)(__umulhi(len2, 0xAAAAAAABu) >> 2);
         const unsigned m24 = index_scale(len2);
         const int K = dot_back + sixth, top = (int)len2 + sixth;
@@ -422,6 +480,10 @@ __device__ __forceinline__ uint2 ycocg_colour_block_scalar(const unsigned (&cc)[
 // (the 128s of rows 1 and 2 cancel: their weights sum to zero; Co's row is doubled so that one constant serves all
 // three).  Per pixel: v_xor, the matrix instruction, v_ashrrev (Y), v_perm_b32 + v_pk_ashrrev_i16 (Co | Cg << 16, signed
 // halves) -- four vector instructions and one on the matrix pipe, where the dot-product form has seven.
+// BIASED: C is a register tuple instead, one addend a row (ycocg_addend(): 2, 2 + 512, 2 + 512, 0 in every lane), so
+// rows 1 and 2 come out 512 higher and the same v_perm_b32 + v_pk_ashrrev_i16 deliver Co | Cg << 16 as the definition's
+// own values, 1..256 a half, which is what ycocg_colour_block<true>'s pixel loops want; Y stays centred, which is what
+// alpha_block<128> takes.  The same instructions a pixel; the tuple's four registers are the price.
 //
 // The matrix instruction READS all 64 lanes whatever EXEC says (it writes the active ones only): a lane's result needs
 // the weight dwords of lanes 0..2 of its group whether or not those run.  So the weight register is made ONCE, at the
@@ -438,6 +500,15 @@ __device__ __forceinline__ unsigned ycocg_weight_rows()
     return r;
 }
 
+// The BIASED form's addend tuple, made beside the weights at the kernel's entry and handed down with them: a value the
+// optimiser cannot see through is one it cannot make again, register by register, between two matrix instructions.
+__device__ __forceinline__ mfma_i32x4 ycocg_addend()
+{
+    mfma_i32x4 c = {2, 2 + 512, 2 + 512, 0};
+    asm volatile("" : "+v"(c));
+    return c;
+}
+
 // Two pixels a statement, software-pipelined by one statement: the statement reads the results of the two pixels
 // BEFORE its own, then issues its own two matrix instructions.  The compiler sees neither the instruction nor its
 // hazards, so both stand here by position: two wait states between the v_xor that writes B and the matrix instruction
@@ -447,34 +518,53 @@ __device__ __forceinline__ unsigned ycocg_weight_rows()
 // Every reader of the old results stands IN FRONT of the new matrix instructions, and the new results are tied to the
 // old ones' registers: two tuples live instead of four.  Every other output is early-clobber: the matrix
 // instructions read the weights last, and an output that may share a register with an input could take THEIRS where
-// the statement is their last use.
+// the statement is their last use.  (BIASED: the addend tuple in place of the inline constant, nothing else.)
 #define HAPBC_YCOCG_MFMA "v_mfma_i32_4x4x4_16b_i8 "
 #define HAPBC_YCOCG_SHIFT(CC) "v_pk_ashrrev_i16 " CC ", 2, " CC " op_sel_hi:[0,1]\n\t"
 // first statement of a block: nothing to read yet
-__device__ __forceinline__ void ycocg_pair_first(mfma_i32x4 &ta, mfma_i32x4 &tb, unsigned pa, unsigned pb, unsigned rows)
+template <bool BIASED>
+__device__ __forceinline__ void ycocg_pair_first(mfma_i32x4 &ta, mfma_i32x4 &tb, unsigned pa, unsigned pb, unsigned rows, const mfma_i32x4 &addend)
 {
     unsigned qa, qb;
-    asm("v_xor_b32 %[qa], %[k80], %[pa]\n\tv_xor_b32 %[qb], %[k80], %[pb]\n\ts_nop 0\n\t"
-        HAPBC_YCOCG_MFMA "%[ta], %[w], %[qa], 2\n\t" HAPBC_YCOCG_MFMA "%[tb], %[w], %[qb], 2\n\ts_nop 4"
-        : [ta] "=&v"(ta), [tb] "=&v"(tb), [qa] "=&v"(qa), [qb] "=&v"(qb)
-        : [pa] "v"(pa), [pb] "v"(pb), [w] "v"(rows), [k80] "s"(0x80808080u));
+    if (BIASED)
+        asm("v_xor_b32 %[qa], %[k80], %[pa]\n\tv_xor_b32 %[qb], %[k80], %[pb]\n\ts_nop 0\n\t"
+            HAPBC_YCOCG_MFMA "%[ta], %[w], %[qa], %[c]\n\t" HAPBC_YCOCG_MFMA "%[tb], %[w], %[qb], %[c]\n\ts_nop 4"
+            : [ta] "=&v"(ta), [tb] "=&v"(tb), [qa] "=&v"(qa), [qb] "=&v"(qb)
+            : [pa] "v"(pa), [pb] "v"(pb), [w] "v"(rows), [c] "v"(addend), [k80] "s"(0x80808080u));
+    else
+        asm("v_xor_b32 %[qa], %[k80], %[pa]\n\tv_xor_b32 %[qb], %[k80], %[pb]\n\ts_nop 0\n\t"
+            HAPBC_YCOCG_MFMA "%[ta], %[w], %[qa], 2\n\t" HAPBC_YCOCG_MFMA "%[tb], %[w], %[qb], 2\n\ts_nop 4"
+            : [ta] "=&v"(ta), [tb] "=&v"(tb), [qa] "=&v"(qa), [qb] "=&v"(qb)
+            : [pa] "v"(pa), [pb] "v"(pb), [w] "v"(rows), [k80] "s"(0x80808080u));
 }
-// pixels pa, pb in, their results to ta, tb; Y - 128 and (Co - 128) | (Cg - 128) << 16 of the two pixels whose results
-// ta, tb held before out
+// pixels pa, pb in, their results to ta, tb; Y - 128 and Co | Cg << 16 (centred or BIASED) of the two pixels whose
+// results ta, tb held before out
+template <bool BIASED>
 __device__ __forceinline__ void ycocg_pair(mfma_i32x4 &ta, mfma_i32x4 &tb, int &ya, int &yb, unsigned &cca, unsigned &ccb,
-                                           unsigned pa, unsigned pb, unsigned rows)
+                                           unsigned pa, unsigned pb, unsigned rows, const mfma_i32x4 &addend)
 {
     const mfma_i32x4 oa = ta, ob = tb;
     unsigned qa, qb;
-    asm("v_xor_b32 %[qa], %[k80], %[pa]\n\tv_xor_b32 %[qb], %[k80], %[pb]\n\t"
-        "v_ashrrev_i32 %[ya], 2, %[oax]\n\tv_ashrrev_i32 %[yb], 2, %[obx]\n\t"
-        "v_perm_b32 %[ca], %[oaz], %[oay], %[sel]\n\tv_perm_b32 %[cb], %[obz], %[oby], %[sel]\n\t"
-        HAPBC_YCOCG_SHIFT("%[ca]")
-        HAPBC_YCOCG_MFMA "%[ta], %[w], %[qa], 2\n\t" HAPBC_YCOCG_MFMA "%[tb], %[w], %[qb], 2\n\t"
-        HAPBC_YCOCG_SHIFT("%[cb]") "s_nop 3"
-        : [ta] "+v"(ta), [tb] "+v"(tb), [ya] "=&v"(ya), [yb] "=&v"(yb), [ca] "=&v"(cca), [cb] "=&v"(ccb), [qa] "=&v"(qa), [qb] "=&v"(qb)
-        : [pa] "v"(pa), [pb] "v"(pb), [w] "v"(rows), [k80] "s"(0x80808080u), [sel] "s"(0x05040100),
-          [oax] "v"(oa.x), [oay] "v"(oa.y), [oaz] "v"(oa.z), [obx] "v"(ob.x), [oby] "v"(ob.y), [obz] "v"(ob.z));
+    if (BIASED)
+        asm("v_xor_b32 %[qa], %[k80], %[pa]\n\tv_xor_b32 %[qb], %[k80], %[pb]\n\t"
+            "v_ashrrev_i32 %[ya], 2, %[oax]\n\tv_ashrrev_i32 %[yb], 2, %[obx]\n\t"
+            "v_perm_b32 %[ca], %[oaz], %[oay], %[sel]\n\tv_perm_b32 %[cb], %[obz], %[oby], %[sel]\n\t"
+            HAPBC_YCOCG_SHIFT("%[ca]")
+            HAPBC_YCOCG_MFMA "%[ta], %[w], %[qa], %[c]\n\t" HAPBC_YCOCG_MFMA "%[tb], %[w], %[qb], %[c]\n\t"
+            HAPBC_YCOCG_SHIFT("%[cb]") "s_nop 3"
+            : [ta] "+v"(ta), [tb] "+v"(tb), [ya] "=&v"(ya), [yb] "=&v"(yb), [ca] "=&v"(cca), [cb] "=&v"(ccb), [qa] "=&v"(qa), [qb] "=&v"(qb)
+            : [pa] "v"(pa), [pb] "v"(pb), [w] "v"(rows), [c] "v"(addend), [k80] "s"(0x80808080u), [sel] "s"(0x05040100),
+              [oax] "v"(oa.x), [oay] "v"(oa.y), [oaz] "v"(oa.z), [obx] "v"(ob.x), [oby] "v"(ob.y), [obz] "v"(ob.z));
+    else
+        asm("v_xor_b32 %[qa], %[k80], %[pa]\n\tv_xor_b32 %[qb], %[k80], %[pb]\n\t"
+            "v_ashrrev_i32 %[ya], 2, %[oax]\n\tv_ashrrev_i32 %[yb], 2, %[obx]\n\t"
+            "v_perm_b32 %[ca], %[oaz], %[oay], %[sel]\n\tv_perm_b32 %[cb], %[obz], %[oby], %[sel]\n\t"
+            HAPBC_YCOCG_SHIFT("%[ca]")
+            HAPBC_YCOCG_MFMA "%[ta], %[w], %[qa], 2\n\t" HAPBC_YCOCG_MFMA "%[tb], %[w], %[qb], 2\n\t"
+            HAPBC_YCOCG_SHIFT("%[cb]") "s_nop 3"
+            : [ta] "+v"(ta), [tb] "+v"(tb), [ya] "=&v"(ya), [yb] "=&v"(yb), [ca] "=&v"(cca), [cb] "=&v"(ccb), [qa] "=&v"(qa), [qb] "=&v"(qb)
+            : [pa] "v"(pa), [pb] "v"(pb), [w] "v"(rows), [k80] "s"(0x80808080u), [sel] "s"(0x05040100),
+              [oax] "v"(oa.x), [oay] "v"(oa.y), [oaz] "v"(oa.z), [obx] "v"(ob.x), [oby] "v"(ob.y), [obz] "v"(ob.z));
 }
 // last statement of a block: the readers alone
 __device__ __forceinline__ void ycocg_pair_last(int &ya, int &yb, unsigned &cca, unsigned &ccb, mfma_i32x4 oa, mfma_i32x4 ob)
@@ -508,11 +598,11 @@ __device__ __forceinline__ void chroma4(unsigned (&raw)[4], int q0, int q1, int 
 }
 
 // the 8 or 16 bytes of a block from its sixteen RGBA8 pixels (row-major); 8-byte formats leave z, w zero
-// (MATRIX: the Hap Q destinations -- the YCoCg transform on the matrix pipe, `rows` the kernel's ycocg_weight_rows(), and
-// the colour half on Co | Cg pairs; without it, Hap Q Alpha, the dot-product transform and the scalar colour half.  The
+// (MATRIX: the Hap Q destinations -- the YCoCg transform on the matrix pipe, `rows` the kernel's ycocg_weight_rows(),
+// and the colour half on Co | Cg pairs -- BIASED: non-negative pairs, `addend` the kernel's ycocg_addend(); without MATRIX, Hap Q Alpha, the dot-product transform and the scalar colour half.  The
 // same bytes either way)
-template <int FMT, bool MATRIX = false>
-__device__ __forceinline__ uint4 block_of(const unsigned (&p)[16], unsigned rows = 0u)
+template <int FMT, bool MATRIX = false, bool BIASED = false>
+__device__ __forceinline__ uint4 block_of(const unsigned (&p)[16], unsigned rows = 0u, const mfma_i32x4 &addend = mfma_i32x4{})
 {
     if (FMT == kFmtRGTC1) {
         int a[16];
@@ -539,16 +629,16 @@ __device__ __forceinline__ uint4 block_of(const unsigned (&p)[16], unsigned rows
         const uint2 ab = alpha_block(a), cb = colour_block(px);
         return make_uint4(ab.x, ab.y, cb.x, cb.y);
     } else {
-        // Y = (R+2G+B+2)>>2 ; Co = ((R-B+1)>>1)+128 ; Cg = ((-R+2G-B+2)>>2)+128 ; no clamp (oracle/bc_oracle.c).  All
-        // three leave here less 128 and nothing downstream subtracts the bias again.
+        // Y = (R+2G+B+2)>>2 ; Co = ((R-B+1)>>1)+128 ; Cg = ((-R+2G-B+2)>>2)+128 ; no clamp (oracle/bc_oracle.c).  Y
+        // leaves here less 128; Co and Cg as they are from the BIASED matrix form, less 128 otherwise.
         int y[16];
         unsigned cc[16];
         if (MATRIX) {
             mfma_i32x4 ta, tb;
-            ycocg_pair_first(ta, tb, p[0], p[1], rows);
+            ycocg_pair_first<BIASED>(ta, tb, p[0], p[1], rows, addend);
 #pragma unroll
             for (int i = 2; i < 16; i += 2)
-                ycocg_pair(ta, tb, y[i - 2], y[i - 1], cc[i - 2], cc[i - 1], p[i], p[i + 1], rows);
+                ycocg_pair<BIASED>(ta, tb, y[i - 2], y[i - 1], cc[i - 2], cc[i - 1], p[i], p[i + 1], rows, addend);
             ycocg_pair_last(y[14], y[15], cc[14], cc[15], ta, tb);
         } else {
 #pragma unroll
@@ -569,7 +659,7 @@ __device__ __forceinline__ uint4 block_of(const unsigned (&p)[16], unsigned rows
                 }
             }
         }
-        const uint2 ab = alpha_block<128>(y), cb = MATRIX ? ycocg_colour_block(cc) : ycocg_colour_block_scalar(cc);
+        const uint2 ab = alpha_block<128>(y), cb = MATRIX ? ycocg_colour_block<BIASED>(cc) : ycocg_colour_block_scalar(cc);
         return make_uint4(ab.x, ab.y, cb.x, cb.y);
     }
 }

@@ -272,6 +272,7 @@ __global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5
     const unsigned lane = threadIdx.x;
     // (before any return or branch: every lane of the wave must hold its weight row, bc_encode_core.hpp)
     const unsigned ycocg_rows = FUSED == hapbc::kFmtYCoCg ? hapbc::ycocg_weight_rows() : 0u;
+    const hapbc::mfma_i32x4 ycocg_add = FUSED == hapbc::kFmtYCoCg ? hapbc::ycocg_addend() : hapbc::mfma_i32x4{};
     // Single-texture launches take their frames interleaved: consecutive workgroups work on different frames, so the
     // fragments of one frame that are in flight together are few -- a placed stream waits for the sizes of everything
     // before it in its frame, and with a whole frame in flight every wavefront waited for the slowest of 4000.
@@ -420,7 +421,7 @@ __global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5
                         next_block((t + 1u) % kSub);
                     load_pixels(pix[(t + 1u) & 1u], t + 1u);
                 }
-                const uint4 blk = hapbc::block_of<FUSED, FUSED == hapbc::kFmtYCoCg>(pix[kPrefetch ? t & 1u : 0u], ycocg_rows);
+                const uint4 blk = hapbc::block_of<FUSED, FUSED == hapbc::kFmtYCoCg, FUSED == hapbc::kFmtYCoCg>(pix[kPrefetch ? t & 1u : 0u], ycocg_rows, ycocg_add);
                 made = blk;
                 const unsigned bpos = (64u * t + lane) * B;
                 // (the texture is kept for chunks that Snappy does not shrink -- they are stored from there.  A PLACED

@@ -60,6 +60,7 @@ FUSED_PHASES = [
     ("end points", CORE, "const int mo = lo_o + hi_o", None, 8.0),              # (the scalar form, before R11)
     ("colour index", CORE, "const int K = mad24(d_o", None, 8.0),
     ("end points", CORE, "const pk_i16 mid = lo + hi;", None, 8.0),             # (the pair form)
+    ("end points", CORE, "const pk_i16 mid = lo_b + hi_b;", None, 8.0),         # (the pair form on biased pairs, R13)
     ("colour index", CORE, "const int K = dot_back + sixth", None, 8.0),
     ("YCoCg transform", CORE, "// ---- the YCoCg transform as one 4x4x4 signed-byte matrix product", None, 8.0),
     ("YCoCg transform", CORE, "2 (Co - 128) | 4 (Cg - 128) << 16 of four pixels", None, 8.0),

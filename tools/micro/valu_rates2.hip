@@ -1,4 +1,5 @@
-// Dev probe 2: one opcode per kernel via inline asm (8 independent chains; waves per SIMD = argv[1], default 8:
+// Dev probe 2: one opcode per kernel via inline asm (8 independent chains; v20 is kept free as a third, constant source;
+// waves per SIMD = argv[1], default 8:
 // the fused Hap Q encode kernel runs at 5).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -12,7 +13,7 @@
         unsigned b = seed | 1u;                                                                    \
         for (int i = 0; i < ITER; i++) {                                                           \
             asm volatile(ASM(%0) ASM(%1) ASM(%2) ASM(%3) ASM(%4) ASM(%5) ASM(%6) ASM(%7)            \
-                         : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(b) : "vcc", "s20", "s21"); \
+                         : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(b) : "vcc", "s20", "s21", "v20"); \
         }                                                                                          \
         out[blockIdx.x * 256 + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7;               \
     }
@@ -98,6 +99,13 @@
                         "v_ashrrev_i32_sdwa " #x ", 2, %8 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n"
 #define A_PKASHRI(x) "v_pk_ashrrev_i16 " #x ", 2, " #x " op_sel_hi:[0,1]\n"
 #define A_PERMPKASHR(x) "v_perm_b32 " #x ", %8, " #x ", s22\nv_pk_ashrrev_i16 " #x ", 2, " #x " op_sel_hi:[0,1]\n"
+// round 13: the colour box on non-negative Co | Cg pairs -- the three-input packed half minimum / maximum (two and three
+// distinct sources, as the box's steps and its padded last step have them) and v_add3_u32 on words holding pairs
+#define A_PKMINIMUM3(x) "v_pk_minimum3_f16 " #x ", " #x ", %8, " #x "\n"
+#define A_PKMAXIMUM3(x) "v_pk_maximum3_f16 " #x ", " #x ", %8, " #x "\n"
+#define A_PKMINIMUM3V(x) "v_pk_minimum3_f16 " #x ", " #x ", %8, v20\n"
+#define A_ADD3PAIRS(x) "v_add3_u32 " #x ", " #x ", %8, v20\n"
+KERNEL(k_pkminimum3, A_PKMINIMUM3) KERNEL(k_pkmaximum3, A_PKMAXIMUM3) KERNEL(k_pkminimum3v, A_PKMINIMUM3V) KERNEL(k_add3pairs, A_ADD3PAIRS)
 KERNEL(k_ashrsdwa0, A_ASHRSDWA0) KERNEL(k_ashrsdwa1, A_ASHRSDWA1) KERNEL(k_ashrsdwa01, A_ASHRSDWA01) KERNEL(k_pkashri, A_PKASHRI)
 KERNEL(k_permpkashr, A_PERMPKASHR)
 KERNEL(k_add, A_ADD) KERNEL(k_and, A_AND) KERNEL(k_lshl, A_LSHL) KERNEL(k_bfe, A_BFE) KERNEL(k_lshlor, A_LSHLOR)
@@ -145,5 +153,6 @@ int main(int argc, char **argv)
     RUN(k_mullo) RUN(k_mulhi) RUN(k_bitop3) RUN(k_cmpsdwa) RUN(k_addc64) RUN(k_cmpaddc64)       // (two-instruction kernels: cycles per PAIR)
     RUN(k_pksubi) RUN(k_pklshl) RUN(k_pkmaxi) RUN(k_pkmini) RUN(k_udot2) RUN(k_dot2c) RUN(k_maxi16) RUN(k_ashri16) RUN(k_subu16)      // round 11: the pair form
     RUN(k_ashrsdwa0) RUN(k_ashrsdwa1) RUN(k_pkashri) RUN(k_ashrsdwa01) RUN(k_permpkashr)      // round 12: the Co | Cg pack (the last two: cycles per PAIR)
+    RUN(k_pkminimum3) RUN(k_pkmaximum3) RUN(k_pkminimum3v) RUN(k_add3pairs)      // round 13: the box and the sums on non-negative pairs
     return 0;
 }
