@@ -10,6 +10,8 @@ len2), the scale thresholds).  Random blocks reach a few per cent of those range
                          both the c0 > c1 and the c0 <= c1 order, c0 == c1 for every 16-bit colour, all four indices
   hapq_colour_blocks()   scaled YCoCg colour halves: every (Co byte, scale) and (Cg byte, scale) that a 5:6:5 palette
                          can hold, in each of the four palette slots (scale 1..32 through the interpolated blue entries)
+  *_scaled_sweep()       the endpoints of the above with seeded random codes and every fourth block flat, for the
+                         half- and quarter-size decoders: every residue of the region sums, not the even ones only
   ramp_picture()         every lo < hi ramp, the blocks of a pair holding every value lo..hi (every d and u of the
                          alpha encoder), in A and in R = G = B
   all_colours_picture()  every 24-bit RGB colour once
@@ -172,6 +174,39 @@ def hapq_sweep():
     blocks = pad_blocks(np.concatenate([cycle_to(ramps, n), cycle_to(cols, n)], axis=1))
     alpha = cycle_to(np.roll(ramps, 32768, axis=0), len(blocks))
     return blocks, np.ascontiguousarray(alpha)
+
+
+# --------------------------------------------------------------- block sweeps (decode at half and quarter size) --
+# The code fields above rotate ((p + k) % n): every 2 x 2 or 4 x 4 region of a block then holds every index equally
+# often, its sums are multiples of 2 (half size) or 4 (quarter size), and the neighbours of the rounding term never
+# occur.  The sweeps below keep the endpoints and take their codes from a seeded generator.
+def recoded(blocks, field_offset, bits, seed):
+    """A copy of `blocks` (uint8 [n, b]) whose 16-code field of 2 * bits bytes at byte field_offset holds seeded random
+    codes; block k with k % 4 == 0 is flat, all 16 texels carrying code (k // 4) % (1 << bits).  Endpoints are kept."""
+    n = len(blocks)
+    codes = np.random.default_rng(seed).integers(0, 1 << bits, (n, 16))
+    k = np.arange(0, n, 4)
+    codes[k] = ((k // 4) % (1 << bits))[:, None]
+    out = np.array(blocks, dtype=np.uint8, copy=True)
+    out[:, field_offset: field_offset + 2 * bits] = _pack_codes(codes, bits)
+    return out
+
+
+def dxt1_scaled_sweep():
+    """uint8 [77824, 8]: the colour sweep's endpoints with random indices."""
+    return recoded(pad_blocks(colour_blocks()), 4, 2, 0xD171)
+
+
+def dxt5_scaled_sweep():
+    """uint8 [n, 16]: dxt5_sweep()'s endpoints, the alpha codes and the colour indices random (seeds of their own)."""
+    return recoded(recoded(dxt5_sweep(), 2, 3, 0xD175A), 12, 2, 0xD175C)
+
+
+def hapq_scaled_sweep():
+    """(uint8 [n, 16] Hap Q blocks, uint8 [n, 8] RGTC1 alpha plane): hapq_sweep()'s endpoints -- the plane rolled as
+    there -- with random luma codes, colour indices and plane codes."""
+    blocks, alpha = hapq_sweep()
+    return recoded(recoded(blocks, 2, 3, 0x4A91), 12, 2, 0x4A9C), recoded(alpha, 2, 3, 0x4A9A)
 
 
 # ------------------------------------------------------------------------------------ pictures (encode) --

@@ -133,6 +133,28 @@ def test_sums_beyond_32_bits(ctx):
     assert r == 0 and as_tuple(error) == want
 
 
+def test_more_workgroups_than_the_reduction_has_lanes(ctx):
+    """bc_measure_reduce_kernel's 1024 lanes stride over a picture's workgroup partials.  4100 x 4096 texels are
+    1 049 600 blocks and 1025 workgroups of 1024 blocks: lane 0 takes a second turn, for a full workgroup's partials."""
+    w, h = 4100, 4096
+    assert (w // 4) * (h // 4) == 1025 * 1024
+    rng = np.random.default_rng([12, w, h])
+    tex = rng.integers(0, 256, (w // 4) * (h // 4) * 8, dtype=np.uint8).tobytes()
+    picture = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+    r, out = ctx.decompress_rgba(tex, L.FMT_DXT1, w, h)                # (not random_texture: nothing this large is kept)
+    assert r == 0
+    decoded = np.frombuffer(out, dtype=np.uint8).reshape(h, w, 4)
+    sse, sad = np.zeros(4, dtype=np.int64), np.zeros(4, dtype=np.int64)
+    for y in range(0, h, 256):                                         # by row bands: the differences of 64 MiB in int32
+        d = decoded[y: y + 256].astype(np.int32) - picture[y: y + 256].astype(np.int32)
+        sse += (d * d).sum(axis=(0, 1), dtype=np.int64)
+        sad += np.abs(d).sum(axis=(0, 1), dtype=np.int64)
+    want = (tuple(int(v) for v in sse), tuple(int(v) for v in sad), w * h)
+    assert all(v > 1 << 32 for v in want[0][:3])
+    r, error = ctx.measure_texture(tex, L.FMT_DXT1, w, h, dev_picture(picture))
+    assert r == 0 and as_tuple(error) == want, (as_tuple(error), want)
+
+
 # ------------------------------------------------------------------------------------------------------- 3. frames --
 W, H = 64, 32
 NB = (W // 4) * (H // 4)

@@ -1,7 +1,8 @@
 """CPU half of the value-space sweeps (tests/_value_space.py): the coverage each sweep claims is reached, the oracle's
 block decoders equal a plain integer restatement of the formats on every sweep, and Pillow's DDS reader agrees on
 the DXT1, DXT5 and RGTC1 sweeps.  The GPU half, tests/test_value_space_gpu.py, holds the kernels to the oracle on the
-same sweeps."""
+same sweeps; tests/test_value_space_derived_gpu.py does so for the half- and quarter-size, region, planes, composite
+and measure launches, whose sweeps with random codes are held here to every residue of the region sums."""
 import numpy as np
 import pytest
 
@@ -188,6 +189,100 @@ def test_encode_picture_coverage(capsys):
             "the %d the inset endpoint rule allows (%d formable by any two 5:6:5 codes), scale edges %s" % (
                 255 * 256 // 2, len(np.unique(d)), len(du), 1 << 24, len(got), len(want), len(formable),
                 sorted(set(m.tolist()) & set(V.SCALE_EDGES + (127, 128)))))
+
+
+# ------------------------------------------------------------- sweeps for the half- and quarter-size decoders --
+def _region_sums(pic, s):
+    """[h, w, c] -> int64 [h >> s, w >> s, c]: the sums of the 2^s x 2^s regions"""
+    k = 1 << s
+    h, w, c = pic.shape
+    return pic.astype(np.int64).reshape(h // k, k, w // k, k, c).sum(axis=(1, 3))
+
+
+def _picture(blocks, fmt, plane=None):
+    """The oracle's picture of a sweep (A from the RGTC1 plane where there is one)"""
+    w, h = 4 * V.BLOCK_ROW, 4 * len(blocks) // V.BLOCK_ROW
+    pic = D.oracle_bc_decode(np.ascontiguousarray(blocks).tobytes(), fmt, w, h)
+    if plane is not None:
+        pic[..., 3] = D.oracle_bc_decode(np.ascontiguousarray(plane).tobytes(), L.FMT_RGTC1, w, h)
+    return pic
+
+
+def _scaled_sweep(name):
+    """(blocks, the rotating sweep they come from, format, plane | None, its rotating form | None)"""
+    if name == "dxt1":
+        return V.dxt1_scaled_sweep(), V.pad_blocks(V.colour_blocks()), L.FMT_DXT1, None, None
+    if name == "dxt5":
+        return V.dxt5_scaled_sweep(), V.dxt5_sweep(), L.FMT_DXT5, None, None
+    (blocks, plane), (old, old_plane) = V.hapq_scaled_sweep(), V.hapq_sweep()
+    if name == "hapq":
+        plane = old_plane = None
+    return blocks, old, L.FMT_YCOCG, plane, old_plane
+
+
+def _flat_codes(codes):
+    """the codes of the blocks whose 16 texels all carry the same one"""
+    return set(codes[(codes == codes[:, :1]).all(axis=1), 0].tolist())
+
+
+def test_rotating_codes_reach_only_even_region_sums():
+    """Why the sweeps above are not enough at half and quarter size: with the code (p + k) % 4 at texel p, every region
+    of a block holds every index it holds equally often, so the colour sums are multiples of 2 (s = 1) or 4 (s = 2)
+    and the neighbours of the rounding term, half - 1 and half + 1, never occur."""
+    pic = _picture(V.dxt5_sweep(), L.FMT_DXT5)
+    for s in (1, 2):
+        seen = np.unique(_region_sums(pic, s)[..., :3] % (1 << 2 * s))
+        assert seen.tolist() == list(range(0, 1 << 2 * s, 1 << s)), (s, seen)
+
+
+@pytest.mark.parametrize("name", ["dxt1", "dxt5", "hapq", "hapq_alpha"])
+def test_scaled_sweep_coverage(capsys, name):
+    blocks, old, fmt, plane, old_plane = _scaled_sweep(name)
+    assert blocks.shape == old.shape and len(blocks) % V.BLOCK_ROW == 0
+    # endpoints kept, code fields replaced: the value coverage of the rotating sweeps carries over
+    colour = blocks if fmt == L.FMT_DXT1 else blocks[:, 8:]
+    ramps = {} if fmt == L.FMT_DXT1 else {"first": blocks[:, :8]}
+    assert np.array_equal(colour[:, :4], (old if fmt == L.FMT_DXT1 else old[:, 8:])[:, :4])
+    if ramps:
+        assert np.array_equal(blocks[:, :2], old[:, :2])
+    if plane is not None:
+        assert plane.shape == old_plane.shape and np.array_equal(plane[:, :2], old_plane[:, :2])
+        ramps["plane"] = plane
+    # both ramp orders and a0 == a1; all three colour orders; flat blocks with every code
+    for what, half in ramps.items():
+        a0, a1, codes = _alpha_fields(half)
+        assert (a0 > a1).any() and (a0 < a1).any() and (a0 == a1).any(), what
+        assert _flat_codes(codes) == set(range(8)), what
+        assert len(np.unique(codes[1::4], axis=0)) > len(codes) // 8, what          # (the others are not flat)
+    c0, c1, idx = _colour_fields(colour)
+    assert (c0 > c1).any() and (c0 < c1).any() and (c0 == c1).any()
+    assert _flat_codes(idx) == set(range(4))
+    pic = _picture(blocks, fmt, plane)
+    if fmt == L.FMT_YCOCG:
+        # every scale code at a texel that picks it, and texels beyond either end of the byte range
+        y = restated_alpha(blocks[:, :8])
+        pal = restated_colour(colour, np.zeros(len(blocks), bool))
+        scale = (pal[..., 2] >> 3) + 1
+        assert set(np.unique(scale).tolist()) == set(range(1, 33))
+        co, cg = truncating_divide(pal[..., 0] - 128, scale), truncating_divide(pal[..., 1] - 128, scale)
+        rgb = np.stack([y + co - cg, y + cg, y - co - cg], axis=-1)
+        texels = V.blocks_of_picture(pic)[..., :3]
+        assert (rgb < 0).any() and (texels[rgb < 0] == 0).all()
+        assert (rgb > 255).any() and (texels[rgb > 255] == 255).all()
+    # the oracle's picture: every residue of the region sums in every channel that is not constant
+    live = [c for c in range(4) if pic[..., c].min() != pic[..., c].max()]
+    assert live == ([0, 1, 2] if name in ("dxt1", "hapq") else [0, 1, 2, 3])
+    rarest = {}
+    for s in (1, 2):
+        texels = 1 << 2 * s
+        sums = _region_sums(pic, s)
+        counts = np.stack([np.bincount(sums[..., c].ravel() % texels, minlength=texels) for c in live])
+        assert counts.min() > 0, (s, counts.tolist())
+        rarest[s] = int(counts.min())
+        if 3 in live:
+            assert sums[..., 3].max() == texels * 255, s                            # no accumulator may wrap there
+    _report(capsys, "%s at half / quarter size: %d blocks, rarest residue of a region sum %d / %d times" % (
+        name, len(blocks), rarest[1], rarest[2]))
 
 
 # ------------------------------------------------------------------------ oracle against the restatement --
