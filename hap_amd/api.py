@@ -31,6 +31,7 @@ ENCODE_COARSE_MATCHES = 0x2
 ENCODE_SMALLER_FILES = 0x4
 ENCODE_FINE_CHUNKS = 0x8
 ENCODE_BPTC_BLOCKS = 0x10
+ENCODE_REFINE_ENDPOINTS = 0x20     # HAPGPU_ENCODE_REFINE_ENDPOINTS: refined end points for RGB_DXT1 / RGBA_DXT5 colour blocks
 DECODE_IGNORE_FRAGMENT_INDEX = 0x1
 DECODE_IGNORE_HALF_TILES = 0x2
 DECODE_NO_BLOCK_SCAN = 0x4
@@ -378,7 +379,9 @@ class Context:
 
     def compress_rgba(self, rgba, width, height, row_bytes, texture_format, output=None, flags=0):
         """RGBA8 -> one block texture (HapGpuCompressRGBA; with nonzero flags HapGpuCompressRGBAFlags, where
-        ENCODE_BPTC_BLOCKS admits RGBA_BPTC_UNORM).  Returns (result, bytes | None), or (result, bytes used) into `output`."""
+        ENCODE_BPTC_BLOCKS admits RGBA_BPTC_UNORM and ENCODE_REFINE_ENDPOINTS makes the colour blocks of RGB_DXT1 and
+        RGBA_DXT5 with least-squares refined end points: slower, never a larger error in any block, the other formats
+        unchanged).  Returns (result, bytes | None), or (result, bytes used) into `output`."""
         block = 8 if texture_format in (HapTextureFormat.RGB_DXT1, HapTextureFormat.A_RGTC1) else 16
         need = (width // 4) * (height // 4) * block
         a, _n, _k = _addr_len(rgba)
@@ -644,6 +647,10 @@ class Context:
 
     def encode_frames_rgba(self, rgba_frames, width, height, row_bytes, formats, compressors, chunk_counts,
                            outputs, flags=0):
+        """RGBA8 pictures -> frames in one call (HapGpuEncodeFramesRGBA).  flags: the ENCODE_* bits; with
+        ENCODE_REFINE_ENDPOINTS the textures of [RGB_DXT1] and [RGBA_DXT5] frames are compress_rgba's with that flag (the
+        quality tier of Hap and Hap Alpha; every other format, and frames of two textures, as without it).  Returns
+        (result, used[], results[])."""
         nf, count = len(rgba_frames), len(formats)
         ptrs, _infos = self._ptr_array(rgba_frames)
         optrs, oinfos = self._ptr_array(outputs)
@@ -695,7 +702,8 @@ class Context:
         rowBytes are read from it, stride(-1) must be 1.  byte = float32(element) * scale[c] + bias[c] (two roundings),
         NaN and anything not above 0 to 0, 255 and above to 255, else to nearest with halves to even; the frames are
         encode_frames_rgba's of the pictures of those bytes.  formats: [RGB_DXT1], [RGBA_DXT5], [YCoCg_DXT5], [A_RGTC1]
-        or [YCoCg_DXT5, A_RGTC1].  scale defaults to 255 per channel, bias to 0.  Returns (result, used[], results[])."""
+        or [YCoCg_DXT5, A_RGTC1].  scale defaults to 255 per channel, bias to 0.  flags: encode_frames_rgba's,
+        ENCODE_REFINE_ENDPOINTS included (ENCODE_BPTC_BLOCKS is ignored).  Returns (result, used[], results[])."""
         described = _plane_tensors(planes, False, width, height, 0)               # (refusals first: no context needed)
         r, used, results, _keep = self._encode_planes(lib.HapGpuEncodeFramesPlanes, described, width, height, formats,
                                                       compressors, chunk_counts, outputs, scale, bias, flags)

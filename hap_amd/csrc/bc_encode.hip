@@ -10,6 +10,9 @@
 // coalesced without an LDS stage.  Bounded by HBM: 64 B read + 8/16 B written per block.
 // Endpoint fitting uses per-lane min/max; index selection uses v_dot4_u32_u8 to get the
 // |p-c|^2 ordering of four palette entries in four instructions per pixel.
+// With HAPGPU_ENCODE_REFINE_ENDPOINTS the DXT1 and DXT5 kernels are instantiations of their own (REFINE): two rounds of
+// bc_refine_core.hpp behind the default colour block, about 1900 vector instructions a block instead of 480 -- those are
+// bound by instruction issue, not by HBM.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -20,7 +23,7 @@ namespace {
 
 using namespace hapbc;
 
-template <int FMT, bool WIDE>
+template <int FMT, bool WIDE, bool REFINE>
 __device__ __forceinline__ void encode_block(const uint8_t *__restrict__ rgba, size_t row_bytes, unsigned blocks_x,
                                              uint8_t *__restrict__ out, uint8_t *__restrict__ out2, unsigned ycocg_rows)
 {
@@ -42,10 +45,10 @@ __device__ __forceinline__ void encode_block(const uint8_t *__restrict__ rgba, s
         }
     }
     if (FMT == kFmtRGTC1 || FMT == kFmtDXT1) {
-        const uint4 b = block_of<FMT>(p);
+        const uint4 b = block_of<FMT, false, false, REFINE>(p);
         *reinterpret_cast<uint2 *>(out + id * 8u) = make_uint2(b.x, b.y);
     } else {
-        *reinterpret_cast<uint4 *>(out + id * 16u) = block_of<FMT == kFmtYCoCgAlpha ? kFmtYCoCg : FMT, FMT == kFmtYCoCg>(p, ycocg_rows);
+        *reinterpret_cast<uint4 *>(out + id * 16u) = block_of<FMT == kFmtYCoCgAlpha ? kFmtYCoCg : FMT, FMT == kFmtYCoCg, false, REFINE>(p, ycocg_rows);
         if (FMT == kFmtYCoCgAlpha) {
             const uint4 a = block_of<kFmtRGTC1>(p);
             *reinterpret_cast<uint2 *>(out2 + id * 8u) = make_uint2(a.x, a.y);
@@ -55,8 +58,9 @@ __device__ __forceinline__ void encode_block(const uint8_t *__restrict__ rgba, s
 
 // pictures of one geometry in one launch: picture blockIdx.z, addresses from a HapGpuPictureTable (0: skip the picture).
 // kFmtYCoCgAlpha is Hap Q Alpha: both textures of a picture in one pass over its RGBA (64 + 16 + 8 bytes per
-// block), the RGTC1 plane to the second outputs.
-template <int FMT, bool WIDE>
+// block), the RGTC1 plane to the second outputs.  REFINE (kFmtDXT1 and kFmtDXT5 only): the colour blocks with refined
+// end points, HAPGPU_ENCODE_REFINE_ENDPOINTS -- kernels of their own, the others are what they were.
+template <int FMT, bool WIDE, bool REFINE = false>
 __global__ __launch_bounds__(64) void bc_encode_kernel(HapGpuPictureTable t, size_t row_bytes, unsigned blocks_x)
 {
     // (before any return: every lane of the wave must hold its weight row, bc_encode_core.hpp; Hap Q Alpha keeps the
@@ -67,27 +71,29 @@ __global__ __launch_bounds__(64) void bc_encode_kernel(HapGpuPictureTable t, siz
     uint8_t *out2 = FMT == kFmtYCoCgAlpha ? (uint8_t *)picture_address(t, 2) : nullptr;
     if (!rgba || !out || (FMT == kFmtYCoCgAlpha && !out2))
         return;
-    encode_block<FMT, WIDE>(rgba, row_bytes, blocks_x, out, out2, ycocg_rows);
+    encode_block<FMT, WIDE, REFINE>(rgba, row_bytes, blocks_x, out, out2, ycocg_rows);
 }
 
-template <int FMT>
+template <int FMT, bool REFINE = false>
 void launch(const HapGpuPictureTable &t, unsigned pictures, size_t row_bytes, unsigned bx, unsigned by, bool wide,
             hipStream_t stream)
 {
     const dim3 grid((bx + 63u) / 64u, by, pictures), block(64);
     if (wide)
-        hipLaunchKernelGGL((bc_encode_kernel<FMT, true>), grid, block, 0, stream, t, row_bytes, bx);
+        hipLaunchKernelGGL((bc_encode_kernel<FMT, true, REFINE>), grid, block, 0, stream, t, row_bytes, bx);
     else
-        hipLaunchKernelGGL((bc_encode_kernel<FMT, false>), grid, block, 0, stream, t, row_bytes, bx);
+        hipLaunchKernelGGL((bc_encode_kernel<FMT, false, REFINE>), grid, block, 0, stream, t, row_bytes, bx);
 }
 
 } // namespace
 
 // hapgpu_abi.h.  Returns 0 launched, 1 bad arguments, 4 launch failure.
 extern "C" int hapgpu_k_block_encode(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, unsigned width,
-                                     unsigned height, size_t row_bytes, unsigned format, int with_alpha, int wide,
+                                     unsigned height, size_t row_bytes, unsigned format, unsigned flags, int wide,
                                      unsigned picture_kind)
 {
+    const int with_alpha = (flags & HAPGPU_BLOCK_ENCODE_WITH_ALPHA) != 0;
+    const bool refine = (flags & HAPGPU_BLOCK_ENCODE_REFINE) != 0;      // looked at for DXT1 and DXT5, ignored otherwise
     scoped_timing st(rt, 0);
     const hipStream_t stream = hapgpu_rt_stream(rt);
     // BC6H is made from RGBA16F pictures and nothing else is: 8 bytes a texel, rows a multiple of 16 bytes; A8
@@ -104,8 +110,18 @@ extern "C" int hapgpu_k_block_encode(hapgpu_rt *rt, const HapGpuPictureTable *ta
     const HapGpuPictureTable &t = *table;
     const unsigned bx = width / 4u, by = height / 4u;
     switch (format) {
-    case 0x83F0: launch<kFmtDXT1>(t, pictures, row_bytes, bx, by, wide != 0, stream); break;
-    case 0x83F3: launch<kFmtDXT5>(t, pictures, row_bytes, bx, by, wide != 0, stream); break;
+    case 0x83F0:
+        if (refine)
+            launch<kFmtDXT1, true>(t, pictures, row_bytes, bx, by, wide != 0, stream);
+        else
+            launch<kFmtDXT1>(t, pictures, row_bytes, bx, by, wide != 0, stream);
+        break;
+    case 0x83F3:
+        if (refine)
+            launch<kFmtDXT5, true>(t, pictures, row_bytes, bx, by, wide != 0, stream);
+        else
+            launch<kFmtDXT5>(t, pictures, row_bytes, bx, by, wide != 0, stream);
+        break;
     case 0x01:
         if (with_alpha)
             launch<kFmtYCoCgAlpha>(t, pictures, row_bytes, bx, by, wide != 0, stream);

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bc_refine_core.hpp"
+
 namespace hapbc {
 
 constexpr int kFmtDXT1 = 0, kFmtDXT5 = 1, kFmtYCoCg = 2, kFmtRGTC1 = 3;
@@ -219,6 +221,13 @@ __device__ __forceinline__ unsigned expand_565(unsigned c, bool blue)
 }
 
 // DXT1-style colour block from 16 packed RGB pixels (alpha byte already cleared).
+// REFINE (HAPGPU_ENCODE_REFINE_ENDPOINTS): the block below is the start, and two rounds of bc_refine_core.hpp follow.  A
+// round makes the least-squares end points for the indices the block has, gives them their indices with the same
+// projection, and the pair replaces the block where its error is strictly smaller.  A round that does not win leaves
+// the block as it was and the next makes the same candidate again, so two unconditional rounds with selects are the
+// definition's "stop at the first failure"; the only branches are the ones around a projection that has no segment
+// to project onto, as below.
+template <bool REFINE = false>
 __device__ __forceinline__ uint2 colour_block(const unsigned (&px)[16])
 {
     int lo[3] = {255, 255, 255}, hi[3] = {0, 0, 0};
@@ -255,6 +264,26 @@ __device__ __forceinline__ uint2 colour_block(const unsigned (&px)[16])
     unsigned idx = 0;
     if (c0 != c1)
         idx = project4(px, make_projection(expand_565(c0, true), expand_565(c1, true)));
+    if constexpr (REFINE) {
+        unsigned best0 = c0, best1 = c1, best_idx = idx;
+        int best_rank = refine_rank(px, refine_make_palette(c0, c1), idx);
+        const refine_sums plain = refine_plain_sums(px);
+#pragma unroll
+        for (int round = 0; round < 2; round++) {
+            unsigned n0, n1, nidx = 0;
+            const bool valid = refine_candidate(px, plain, refine_weights(best_idx), n0, n1);
+            const refine_palette pal = refine_make_palette(n0, n1);
+            if (valid && n0 != n1)
+                nidx = project4(px, make_projection(pal.entry[0], pal.entry[1]));
+            const int rank = refine_rank(px, pal, nidx);
+            const bool win = valid && rank < best_rank;
+            best0 = win ? n0 : best0;
+            best1 = win ? n1 : best1;
+            best_idx = win ? nidx : best_idx;
+            best_rank = win ? rank : best_rank;
+        }
+        return make_uint2(best0 | (best1 << 16), best_idx);
+    }
     return make_uint2(c0 | (c1 << 16), idx);
 }
 
@@ -600,10 +629,11 @@ __device__ __forceinline__ void chroma4(unsigned (&raw)[4], int q0, int q1, int 
 // the 8 or 16 bytes of a block from its sixteen RGBA8 pixels (row-major); 8-byte formats leave z, w zero
 // (MATRIX: the Hap Q destinations -- the YCoCg transform on the matrix pipe, `rows` the kernel's ycocg_weight_rows(),
 // and the colour half on Co | Cg pairs -- BIASED: non-negative pairs, `addend` the kernel's ycocg_addend(); without MATRIX, Hap Q Alpha, the dot-product transform and the scalar colour half.  The
-// same bytes either way)
-template <int FMT, bool MATRIX = false, bool BIASED = false>
+// same bytes either way.  REFINE, DXT1 and DXT5 only: the colour block with refined end points, colour_block<true>)
+template <int FMT, bool MATRIX = false, bool BIASED = false, bool REFINE = false>
 __device__ __forceinline__ uint4 block_of(const unsigned (&p)[16], unsigned rows = 0u, const mfma_i32x4 &addend = mfma_i32x4{})
 {
+    static_assert(!REFINE || FMT == kFmtDXT1 || FMT == kFmtDXT5, "refined end points: the S3TC colour block only");
     if (FMT == kFmtRGTC1) {
         int a[16];
 #pragma unroll
@@ -616,7 +646,7 @@ __device__ __forceinline__ uint4 block_of(const unsigned (&p)[16], unsigned rows
 #pragma unroll
         for (int i = 0; i < 16; i++)
             px[i] = p[i] & 0x00FFFFFFu;
-        const uint2 cb = colour_block(px);
+        const uint2 cb = colour_block<REFINE>(px);
         return make_uint4(cb.x, cb.y, 0u, 0u);
     } else if (FMT == kFmtDXT5) {
         int a[16];
@@ -626,7 +656,7 @@ __device__ __forceinline__ uint4 block_of(const unsigned (&p)[16], unsigned rows
             a[i] = (int)(p[i] >> 24);
             px[i] = p[i] & 0x00FFFFFFu;
         }
-        const uint2 ab = alpha_block(a), cb = colour_block(px);
+        const uint2 ab = alpha_block(a), cb = colour_block<REFINE>(px);
         return make_uint4(ab.x, ab.y, cb.x, cb.y);
     } else {
         // Y = (R+2G+B+2)>>2 ; Co = ((R-B+1)>>1)+128 ; Cg = ((-R+2G-B+2)>>2)+128 ; no clamp (oracle/bc_oracle.c).  Y

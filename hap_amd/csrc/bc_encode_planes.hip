@@ -15,7 +15,7 @@
 // read, 16 written, where the road over a picture reads 96, writes 64 and reads 64 again.
 //
 // Instantiated per destination format (5 kernels: what block_of is a template of, and what fixes the registers a lane
-// holds).  The element kind is a wave-uniform branch around the loads and the quantiser, the number of planes one around
+// holds), and once more for DXT1 and DXT5 with refined end points (HAPGPU_ENCODE_REFINE_ENDPOINTS: colour_block<true>).  The element kind is a wave-uniform branch around the loads and the quantiser, the number of planes one around
 // the fourth plane: as template parameters they would make 30 kernels of the same encoder code.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -104,7 +104,7 @@ __device__ __forceinline__ void gather_block(const plane_layout &l, const uint8_
 
 // Tensors of one geometry in one launch: tensor blockIdx.z, [tensors][outputs][second outputs] of a HapGpuPictureTable
 // (address 0: skip).  kFmtYCoCgAlpha is Hap Q Alpha: both textures from one pass over the planes.
-template <int FMT>
+template <int FMT, bool REFINE = false>
 __global__ __launch_bounds__(64) void bc_encode_planes_kernel(HapGpuPictureTable t, unsigned blocks_x, plane_layout l)
 {
     // (before any return: every lane of the wave must hold its weight row, bc_encode_core.hpp; Hap Q Alpha keeps the
@@ -127,10 +127,10 @@ __global__ __launch_bounds__(64) void bc_encode_planes_kernel(HapGpuPictureTable
     else
         gather_block<FMT, kF32>(l, tensor, bx, by, p);
     if (FMT == kFmtRGTC1 || FMT == kFmtDXT1) {
-        const uint4 b = block_of<FMT>(p);
+        const uint4 b = block_of<FMT, false, false, REFINE>(p);
         *reinterpret_cast<uint2 *>(out + id * 8u) = make_uint2(b.x, b.y);
     } else {
-        *reinterpret_cast<uint4 *>(out + id * 16u) = block_of<FMT == kFmtYCoCgAlpha ? kFmtYCoCg : FMT, FMT == kFmtYCoCg>(p, ycocg_rows);
+        *reinterpret_cast<uint4 *>(out + id * 16u) = block_of<FMT == kFmtYCoCgAlpha ? kFmtYCoCg : FMT, FMT == kFmtYCoCg, false, REFINE>(p, ycocg_rows);
         if (FMT == kFmtYCoCgAlpha) {
             const uint4 a = block_of<kFmtRGTC1>(p);
             *reinterpret_cast<uint2 *>(out2 + id * 8u) = make_uint2(a.x, a.y);
@@ -138,24 +138,26 @@ __global__ __launch_bounds__(64) void bc_encode_planes_kernel(HapGpuPictureTable
     }
 }
 
-template <int FMT>
+template <int FMT, bool REFINE = false>
 void launch(const HapGpuPictureTable &t, unsigned pictures, unsigned bx, unsigned by, const plane_layout &l,
             hipStream_t stream)
 {
     const dim3 grid((bx + 63u) / 64u, by, pictures), block(64);
-    hipLaunchKernelGGL((bc_encode_planes_kernel<FMT>), grid, block, 0, stream, t, bx, l);
+    hipLaunchKernelGGL((bc_encode_planes_kernel<FMT, REFINE>), grid, block, 0, stream, t, bx, l);
 }
 
 } // namespace
 
 // hapgpu_abi.h.  Returns 0 launched, 1 bad arguments, 4 launch failure.
 extern "C" int hapgpu_k_block_encode_planes(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures,
-                                            unsigned width, unsigned height, unsigned format, int with_alpha,
+                                            unsigned width, unsigned height, unsigned format, unsigned flags,
                                             unsigned channels, unsigned element_kind, size_t plane_bytes,
                                             size_t row_bytes, const float *scale, const float *bias)
 {
     scoped_timing st(rt, 0);
     const hipStream_t stream = hapgpu_rt_stream(rt);
+    const int with_alpha = (flags & HAPGPU_BLOCK_ENCODE_WITH_ALPHA) != 0;
+    const bool refine = (flags & HAPGPU_BLOCK_ENCODE_REFINE) != 0;      // looked at for DXT1 and DXT5, ignored otherwise
     if (element_kind > (unsigned)kF32 || channels < 3u || channels > 4u || !scale || !bias)
         return 1;
     const size_t e = element_kind == (unsigned)kF32 ? 4u : 2u, unit = 4u * e;
@@ -178,8 +180,18 @@ extern "C" int hapgpu_k_block_encode_planes(hapgpu_rt *rt, const HapGpuPictureTa
     }
     const unsigned bx = width / 4u, by = height / 4u;
     switch (format) {
-    case 0x83F0: launch<kFmtDXT1>(*table, pictures, bx, by, l, stream); break;
-    case 0x83F3: launch<kFmtDXT5>(*table, pictures, bx, by, l, stream); break;
+    case 0x83F0:
+        if (refine)
+            launch<kFmtDXT1, true>(*table, pictures, bx, by, l, stream);
+        else
+            launch<kFmtDXT1>(*table, pictures, bx, by, l, stream);
+        break;
+    case 0x83F3:
+        if (refine)
+            launch<kFmtDXT5, true>(*table, pictures, bx, by, l, stream);
+        else
+            launch<kFmtDXT5>(*table, pictures, bx, by, l, stream);
+        break;
     case 0x01:
         if (with_alpha)
             launch<kFmtYCoCgAlpha>(*table, pictures, bx, by, l, stream);

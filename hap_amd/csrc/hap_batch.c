@@ -83,6 +83,9 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
     const HapbEncodeArgs *const a = args ? args : &no_args;
     const int inputs_are_device = a->inputs_are_device;
     const HapbBlockEncodeJob *const job = a->job;
+    /* HAPGPU_ENCODE_REFINE_ENDPOINTS: looked at where this call makes the blocks itself, of one texture a frame (the
+       kernels look at it for RGB_DXT1 and RGBA_DXT5 alone) */
+    const unsigned refine = (job && count == 1u && (flags & HAPGPU_ENCODE_REFINE_ENDPOINTS)) ? HAPGPU_BLOCK_ENCODE_REFINE : 0u;
     tex_geom g[2];
     unsigned fine_counts[2] = {0u, 0u};
     unsigned i, f, first_error = HapResult_No_Error;
@@ -221,7 +224,9 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                 /* (code: HapGpuTexEnc.reserved bits 24..26; mask bit: which kernel the launcher starts) */
                 if (t->field_period == 4u && t->format == HapTextureFormat_YCoCg_DXT5) {
                     fused[i] = 3u; fused_mask |= 1u;
-                } else if (t->field_period == 4u && t->format == HapTextureFormat_RGBA_DXT5) {
+                } else if (t->field_period == 4u && t->format == HapTextureFormat_RGBA_DXT5 && !refine) {
+                    /* (refined end points: the fused block compressor keeps its one definition of a block, and the
+                       texture comes from the block kernel like a DXT1 one) */
                     fused[i] = 2u; fused_mask |= 2u;
                 }
                 /* (DXT1, two blocks to a lane: built and measured -- 115 registers once the match stage's units are read
@@ -493,11 +498,11 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                             launch_rc |= job->height / 4u > 65535u ? 1u :
                                          job->planes.channels ?
                                          (unsigned)hapgpu_k_block_encode_planes(rt, &t, job->frame_count, job->width, job->height,
-                                                                                job->formats[i], pair, job->planes.channels,
+                                                                                job->formats[i], (unsigned)pair | refine, job->planes.channels,
                                                                                 job->planes.element, job->planes.plane_bytes,
                                                                                 job->row_bytes, job->plane_scale, job->plane_bias) :
                                          (unsigned)hapgpu_k_block_encode(rt, &t, job->frame_count, job->width, job->height,
-                                                                         job->row_bytes, job->formats[i], pair, job->wide,
+                                                                         job->row_bytes, job->formats[i], (unsigned)pair | refine, job->wide,
                                                                          job->picture_kind);
                         }
                 }
@@ -797,7 +802,8 @@ unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width
     }
     t.one[0] = (uint64_t)(uintptr_t)src;
     t.one[1] = (uint64_t)(uintptr_t)dst;
-    rc = hapgpu_k_block_encode(rt, &t, 1u, width, height, row_bytes, format, 0,
+    rc = hapgpu_k_block_encode(rt, &t, 1u, width, height, row_bytes, format,
+                               (flags & HAPGPU_ENCODE_REFINE_ENDPOINTS) ? HAPGPU_BLOCK_ENCODE_REFINE : 0u,
                                (((uintptr_t)src | row_bytes) & 15u) == 0 && !(picture_kind == HAPGPU_PICTURE_A8 && ctx->no_wide_planes),
                                picture_kind);
     if (rc == 1)
@@ -1032,7 +1038,7 @@ unsigned hapb_compress_planes(HapGpuContext *ctx, const void *tensor, unsigned w
     }
     t.one[0] = (uint64_t)(uintptr_t)tensor;
     t.one[1] = (uint64_t)(uintptr_t)dst;
-    rc = hapgpu_k_block_encode_planes(rt, &t, 1u, width, height, format, 0, planes->channels, planes->element,
+    rc = hapgpu_k_block_encode_planes(rt, &t, 1u, width, height, format, 0u, planes->channels, planes->element,
                                       planes->plane_bytes, row_bytes, planes->scale, planes->bias);
     if (rc == 1)
         return HapResult_Bad_Arguments;

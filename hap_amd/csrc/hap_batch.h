@@ -106,7 +106,8 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                      unsigned long *output_used, unsigned *results, unsigned flags,
                      const HapbEncodeArgs *args);
 /* one picture -> one texture.  picture_kind (HAPGPU_PICTURE_*): RGBA8 and the DXT / RGTC1 formats (BC7 with
-   HAPGPU_ENCODE_BPTC_BLOCKS), RGBA16F and a BC6H format, or A8 and A_RGTC1 (hapb_encode_pictures' rules) */
+   HAPGPU_ENCODE_BPTC_BLOCKS), RGBA16F and a BC6H format, or A8 and A_RGTC1 (hapb_encode_pictures' rules).
+   HAPGPU_ENCODE_REFINE_ENDPOINTS in flags goes down to the block kernel, which looks at it for DXT1 and DXT5 */
 unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width, unsigned height,
                             unsigned long row_bytes, unsigned format, void *output,
                             unsigned long output_bytes, unsigned long *used, int synchronise, unsigned flags,
@@ -139,7 +140,8 @@ int hapb_planes_encode_valid(unsigned width, unsigned height, unsigned long row_
 int hapb_region_fits(const HapGpuRegion *region, unsigned height);
 /* pictures -> frames.  picture_kind RGBA8: the DXT / RGTC1 formats (BC7 with HAPGPU_ENCODE_BPTC_BLOCKS); RGBA16F (rows
    and device addresses 16-byte aligned): one BC6H texture; A8 (rows and device addresses 4-byte aligned): one RGTC1
-   texture.  defer: HapbEncodeArgs.defer of the call's hapb_encode */
+   texture.  HAPGPU_ENCODE_REFINE_ENDPOINTS in flags: hapb_encode hands it to the block kernels of one-texture frames
+   and does not fuse a DXT5 texture.  defer: HapbEncodeArgs.defer of the call's hapb_encode */
 unsigned hapb_encode_pictures(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
                               unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
                               const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,

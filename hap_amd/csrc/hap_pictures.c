@@ -902,7 +902,8 @@ unsigned hapb_transcode(HapGpuContext *ctx, unsigned frame_count, const void *co
         out_off[i] = out_per_frame;
         out_per_frame += align_up(out_bytes[i], 256);
     }
-    encode_flags &= ~HAPGPU_ENCODE_BPTC_BLOCKS;
+    /* (the destination blocks are the default encode's: no BC7, no refined end points) */
+    encode_flags &= ~(HAPGPU_ENCODE_BPTC_BLOCKS | HAPGPU_ENCODE_REFINE_ENDPOINTS);
     if (encode_textures_valid(count, out_bytes, formats, compressors, chunk_counts, encode_flags) != HapResult_No_Error) {
         transcode_refuse(results, frame_count, HapResult_Bad_Arguments);
         return HapResult_Bad_Arguments;

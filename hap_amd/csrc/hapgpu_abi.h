@@ -325,9 +325,14 @@ enum {
    (BC6H: sources and row_bytes 16-byte aligned); A8 -> A_RGTC1, at most 65535 block rows.
    YCoCg_DXT5 with_alpha: Hap Q Alpha, the RGTC1 alpha plane to the second outputs from the same read of every picture.
    Sources and row_bytes 4-byte aligned, outputs 8- (DXT1, RGTC1) or 16-byte aligned; wide != 0 promises 16-byte aligned
-   sources and row pitch. */
+   sources and row pitch.
+   flags (the word that was with_alpha: 0 and 1 mean what they meant): HAPGPU_BLOCK_ENCODE_WITH_ALPHA as above;
+   HAPGPU_BLOCK_ENCODE_REFINE makes the colour blocks of RGB_DXT1 and RGBA_DXT5 with refined end points
+   (HAPGPU_ENCODE_REFINE_ENDPOINTS, hap_gpu.h; bc_refine_core.hpp) and is ignored for every other format. */
+#define HAPGPU_BLOCK_ENCODE_WITH_ALPHA 1u
+#define HAPGPU_BLOCK_ENCODE_REFINE 2u
 int hapgpu_k_block_encode(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, unsigned width,
-                          unsigned height, size_t row_bytes, unsigned hap_texture_format, int with_alpha, int wide,
+                          unsigned height, size_t row_bytes, unsigned hap_texture_format, unsigned flags, int wide,
                           unsigned picture_kind);
 /* blocks of `hap_texture_format` -> pictures of layout `picture_kind`: RGB_DXT1, RGBA_DXT5, YCoCg_DXT5 (with_alpha: the
    RGTC1 plane supplies A) and RGBA_BPTC_UNORM to RGBA8; RGB_BPTC_UNSIGNED_FLOAT / RGB_BPTC_SIGNED_FLOAT (BC6H) to
@@ -450,10 +455,11 @@ int hapgpu_k_block_composite(hapgpu_rt *rt, const HapGpuCompositeLayer *layers, 
    the RGBA8 pictures of those bytes: RGB_DXT1, RGBA_DXT5, YCoCg_DXT5 (with_alpha: + the RGTC1 plane of A to the second
    outputs) or A_RGTC1.  scale and bias: `channels` floats each, in host memory, copied by the call.  Tensors, plane_bytes
    and row_bytes aligned to the 4 * e bytes a lane loads per row; row_bytes at least width * e, plane_bytes at least
-   row_bytes * (height - 1) + width * e; at most 65535 block rows.  Outputs aligned to their blocks.  Timed as
+   row_bytes * (height - 1) + width * e; at most 65535 block rows.  Outputs aligned to their blocks.  flags:
+   hapgpu_k_block_encode's (HAPGPU_BLOCK_ENCODE_WITH_ALPHA, HAPGPU_BLOCK_ENCODE_REFINE).  Timed as
    HapGpuKernel_BlockEncode.  Returns 0 launched, 1 bad arguments, 4 launch failure. */
 int hapgpu_k_block_encode_planes(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, unsigned width,
-                                 unsigned height, unsigned hap_texture_format, int with_alpha, unsigned channels,
+                                 unsigned height, unsigned hap_texture_format, unsigned flags, unsigned channels,
                                  unsigned element_kind, size_t plane_bytes, size_t row_bytes, const float *scale,
                                  const float *bias);
 /* [device] Addresses of a transcode launch, as HapGpuPictureTable's: source textures, source alpha planes, destination

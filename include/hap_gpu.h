@@ -105,6 +105,36 @@ typedef struct HapGpuContext HapGpuContext;
                                                HapGpuCompressRGBAHalf and HapGpuEncodeFramesRGBAHalf.  Ignored by the
                                                calls that take finished textures. */
 
+#define HAPGPU_ENCODE_REFINE_ENDPOINTS 0x20u /* a quality tier for Hap and Hap Alpha: better colour blocks, slower, the same
+                                               sizes and layouts.  The calls that make blocks from pictures or planes
+                                               (HapGpuCompressRGBAFlags; HapGpuEncodeFramesRGBA and its ...Begin and
+                                               ...OnDevices forms; HapGpuEncodeFramesPlanes[Begin]; HapGpuEncodeSequence)
+                                               replace the colour block of RGB_DXT1, and of the colour half of RGBA_DXT5,
+                                               by the following.  px: the block's 16 RGB pixels; all numbers integers.
+                                               1. Start: best = (c0, c1, idx), exactly the default block.
+                                               2. err(best) = sum_i sum_c (px[i][c] - pal[idx_i][c])^2, pal the palette a
+                                                  decoder builds with c0 > c1: the two expanded 5:6:5 words,
+                                                  (2 p0 + p1) / 3, (p0 + 2 p1) / 3, floor.
+                                               3. Two rounds, each from the current best.  w_i = {3, 0, 2, 1}[idx_i] (the
+                                                  thirds of pal[0] in entry idx_i), v_i = 3 - w_i; A = sum w^2,
+                                                  B = sum w v, C = sum v^2, det = A C - B^2; per channel P = sum w x,
+                                                  Q = sum v x.  det == 0 (every pixel on one entry): no candidate.  Else
+                                                  per channel a = clamp((2 * 3 (C P - B Q) + det) div (2 det), 0, 255) and
+                                                  b the same from A Q - B P (div: floor) -- the least-squares end points
+                                                  rounded to nearest; qa = quant5(a_r) << 11 | quant6(a_g) << 5 |
+                                                  quant5(a_b) with the default's quantisers, qb likewise;
+                                                  c0' = max(qa, qb), c1' = min(qa, qb); idx' from the default's index
+                                                  selection on the new palette, 0 if c0' == c1'.  The candidate replaces
+                                                  best only if err(candidate) < err(best), strictly.
+                                               4. The block is best.
+                                               So per block the error never grows, a block no round improves keeps the
+                                               default's bytes, and the DXT5 alpha half is untouched.  RGBA_DXT5 frames
+                                               of a flagged call do not go through the fused block compressor.
+                                               Ignored, with the default's bytes: every other texture format, frames of
+                                               two textures, the calls that take finished textures, HapGpuCompressPlanes
+                                               (which has no flags) and HapGpuTranscodeFrames' encodeFlags.
+                                               (tests/_refined_endpoints.py states the definition in numpy.) */
+
 /* Decode flags */
 #define HAPGPU_DECODE_IGNORE_FRAGMENT_INDEX 0x1u /* decode as a decoder unaware of section 0x46 would */
 #define HAPGPU_DECODE_IGNORE_HALF_TILES 0x2u     /* use a version-4 table's fragment sizes only (the generic
@@ -185,8 +215,9 @@ unsigned int HapGpuCompressRGBA(HapGpuContext *context,
                                 unsigned long *outputBytesUsed);
 
 /* HapGpuCompressRGBA with encode flags: flags == 0 is exactly HapGpuCompressRGBA.  With HAPGPU_ENCODE_BPTC_BLOCKS it
- * also takes textureFormat RGBA_BPTC_UNORM: 16 bytes per block, a device output must be 16-byte aligned.  Other bits
- * are ignored. */
+ * also takes textureFormat RGBA_BPTC_UNORM: 16 bytes per block, a device output must be 16-byte aligned.  With
+ * HAPGPU_ENCODE_REFINE_ENDPOINTS the colour blocks of RGB_DXT1 and RGBA_DXT5 have refined end points (every other format:
+ * the same bytes as without).  Other bits are ignored. */
 unsigned int HapGpuCompressRGBAFlags(HapGpuContext *context,
                                      const void *rgba, unsigned int width, unsigned int height,
                                      unsigned long rowBytes, unsigned int textureFormat,
@@ -985,7 +1016,8 @@ unsigned int HapGpuCompositeFrames(HapGpuContext *context, unsigned int frameCou
  * count 1: RGB_DXT1 (Hap), RGBA_DXT5 (Hap Alpha), YCoCg_DXT5 (Hap Q) or A_RGTC1 (Hap Alpha-Only, from the fourth plane);
  * count 2: YCoCg_DXT5 then A_RGTC1 (Hap Q Alpha), both textures from one pass over the planes.  Second stage, frame
  * layout, chunk limiting, store-raw decisions, Buffer_Too_Small and every encode flag are HapGpuEncodeFrames';
- * HAPGPU_ENCODE_BPTC_BLOCKS is ignored.  scale and bias point to `channels` floats each and are copied by the call.
+ * HAPGPU_ENCODE_BPTC_BLOCKS is ignored, HAPGPU_ENCODE_REFINE_ENDPOINTS is honoured (count 1, RGB_DXT1 and RGBA_DXT5: the
+ * blocks HapGpuEncodeFramesRGBA makes with it of the pictures of the quantised bytes).  scale and bias point to `channels` floats each and are copied by the call.
  * Alignment as for HapGpuCompressPlanes.  ...Begin is the first half of the call as HapGpuEncodeFramesRGBABegin is (at
  * most 32768 frames; scale and bias need live no longer than the other argument arrays); HapGpuEncodeFramesFinish
  * finishes it.
@@ -1098,7 +1130,8 @@ unsigned int HapGpuTranscodeTexture(HapGpuContext *context,
  * outside the four above is therefore legal at scaleLog2 0 only, and a frame that cannot pass through it is
  * Bad_Arguments alone.
  * The second stage, frame layout, chunk-count limiting, store-raw decisions, outputBuffersBytes / Buffer_Too_Small and
- * encodeFlags are HapGpuEncodeFrames' (HAPGPU_ENCODE_BPTC_BLOCKS is ignored); decodeFlags are
+ * encodeFlags are HapGpuEncodeFrames' (HAPGPU_ENCODE_BPTC_BLOCKS and HAPGPU_ENCODE_REFINE_ENDPOINTS are ignored: the
+ * destination blocks stay as the default encode would make them); decodeFlags are
  * HapGpuDecodeFrameTextures'.  Buffers may be host or device.
  * results[f]: where the decode of frame f fails, the decode's code -- HapDecode's (a broken frame: Bad_Frame), or
  * Bad_Arguments for a frame of another geometry or format; else the encode's code (a NULL output: Bad_Arguments, a short
