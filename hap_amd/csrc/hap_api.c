@@ -96,7 +96,6 @@ HapGpuContext *HapGpuDefaultContext(void)
  * outer call is still waiting for it.  A context serves one call at a time, so the hap.h entry points take
  * whichever default context is free and add one (same device, own stream and scratch) when all are busy. */
 #define HAP_DEFAULT_POOL 8
-#define HAP_BATCH_SLICE 32768u      /* frames per launch sequence: grid dimensions y / z hold at most 65535 */
 static HapGpuContext *g_pool[HAP_DEFAULT_POOL];
 static pthread_t g_pool_owner[HAP_DEFAULT_POOL];     /* the thread inside a hap.h call on that member, if g_pool_busy */
 static unsigned char g_pool_busy[HAP_DEFAULT_POOL];
@@ -530,18 +529,42 @@ static unsigned frames_down_road(HapGpuContext *context, unsigned frameCount, co
     return r;
 }
 
-unsigned int HapGpuCompressRGBA(HapGpuContext *context, const void *rgba, unsigned int width,
-                                unsigned int height, unsigned long rowBytes, unsigned int textureFormat,
-                                void *output, unsigned long outputBytes, unsigned long *outputBytesUsed)
+/* an encode call from a source (hap_batch.h: HapbSource): the context checked and its lock held; one texture, or frames */
+static unsigned texture_from_source(HapGpuContext *context, const HapbSource *source, const void *picture,
+                                    unsigned textureFormat, void *output, unsigned long outputBytes,
+                                    unsigned long *outputBytesUsed, unsigned flags)
 {
     unsigned r;
     if (!context)
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
-    r = hapb_compress_rgba(context, rgba, width, height, rowBytes, textureFormat, output, outputBytes,
-                           outputBytesUsed, 1, 0u, HAPGPU_PICTURE_RGBA8);
+    r = hapb_source_texture(context, source, picture, textureFormat, output, outputBytes, outputBytesUsed, flags);
     hapgpu_rt_unlock(context->rt);
     return r;
+}
+
+static unsigned frames_from_source(HapGpuContext *context, const HapbSource *source, unsigned frameCount,
+                                   const void *const *pictures, unsigned count, const unsigned *textureFormats,
+                                   const unsigned *compressors, const unsigned *chunkCounts, void *const *outputBuffers,
+                                   const unsigned long *outputBuffersBytes, unsigned long *outputBuffersBytesUsed,
+                                   unsigned *results, unsigned flags, int defer)
+{
+    unsigned r;
+    if (!context)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_source_frames(context, source, frameCount, pictures, count, textureFormats, compressors, chunkCounts,
+                           outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, defer);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+unsigned int HapGpuCompressRGBA(HapGpuContext *context, const void *rgba, unsigned int width,
+                                unsigned int height, unsigned long rowBytes, unsigned int textureFormat,
+                                void *output, unsigned long outputBytes, unsigned long *outputBytesUsed)
+{
+    const HapbSource source = {.picture_kind = HAPGPU_PICTURE_RGBA8, .width = width, .height = height, .row_bytes = rowBytes};
+    return texture_from_source(context, &source, rgba, textureFormat, output, outputBytes, outputBytesUsed, 0u);
 }
 
 unsigned int HapGpuCompressRGBAFlags(HapGpuContext *context, const void *rgba, unsigned int width,
@@ -549,14 +572,8 @@ unsigned int HapGpuCompressRGBAFlags(HapGpuContext *context, const void *rgba, u
                                      unsigned int flags, void *output, unsigned long outputBytes,
                                      unsigned long *outputBytesUsed)
 {
-    unsigned r;
-    if (!context)
-        return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_compress_rgba(context, rgba, width, height, rowBytes, textureFormat, output, outputBytes,
-                           outputBytesUsed, 1, flags, HAPGPU_PICTURE_RGBA8);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    const HapbSource source = {.picture_kind = HAPGPU_PICTURE_RGBA8, .width = width, .height = height, .row_bytes = rowBytes};
+    return texture_from_source(context, &source, rgba, textureFormat, output, outputBytes, outputBytesUsed, flags);
 }
 
 unsigned int HapGpuDecompressRGBA(HapGpuContext *context, const void *texture, unsigned long textureBytes,
@@ -701,13 +718,13 @@ unsigned int HapGpuEncodeFrames(HapGpuContext *context, unsigned int frameCount,
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
     /* (the kernels index frames with a grid dimension that holds 65535: larger batches go in slices) */
-    if (frameCount <= HAP_BATCH_SLICE || !inputBuffers || !outputBuffers || !outputBuffersBytes || !outputBuffersBytesUsed || !results ||
+    if (frameCount <= HAP_SLICE_ENTRIES || !inputBuffers || !outputBuffers || !outputBuffersBytes || !outputBuffersBytesUsed || !results ||
         count == 0 || count > 2) {
         r = hapb_encode(context, frameCount, count, inputBuffers, inputBuffersBytes, textureFormats, compressors,
                         chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, NULL);
     } else {
-        for (done = 0; done < frameCount; done += HAP_BATCH_SLICE) {
-            const unsigned n = frameCount - done < HAP_BATCH_SLICE ? frameCount - done : HAP_BATCH_SLICE;
+        for (done = 0; done < frameCount; done += HAP_SLICE_ENTRIES) {
+            const unsigned n = frameCount - done < HAP_SLICE_ENTRIES ? frameCount - done : HAP_SLICE_ENTRIES;
             const unsigned rc = hapb_encode(context, n, count, inputBuffers + (size_t)done * count, inputBuffersBytes, textureFormats,
                                             compressors, chunkCounts, outputBuffers + done, outputBuffersBytes + done,
                                             outputBuffersBytesUsed + done, results + done, flags, NULL);
@@ -728,26 +745,9 @@ unsigned int HapGpuEncodeFramesRGBA(HapGpuContext *context, unsigned int frameCo
                                     unsigned long *outputBuffersBytesUsed, unsigned int *results,
                                     unsigned int flags)
 {
-    unsigned r = HapResult_No_Error, done;
-    if (!context)
-        return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    if (frameCount <= HAP_BATCH_SLICE || !rgbaFrames || !outputBuffers || !outputBuffersBytes || !outputBuffersBytesUsed || !results) {
-        r = hapb_encode_rgba(context, frameCount, rgbaFrames, width, height, rowBytes, count, textureFormats,
-                             compressors, chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed,
-                             results, flags);
-    } else {
-        for (done = 0; done < frameCount; done += HAP_BATCH_SLICE) {
-            const unsigned n = frameCount - done < HAP_BATCH_SLICE ? frameCount - done : HAP_BATCH_SLICE;
-            const unsigned rc = hapb_encode_rgba(context, n, rgbaFrames + done, width, height, rowBytes, count, textureFormats,
-                                                 compressors, chunkCounts, outputBuffers + done, outputBuffersBytes + done,
-                                                 outputBuffersBytesUsed + done, results + done, flags);
-            if (r == HapResult_No_Error)
-                r = rc;
-        }
-    }
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    const HapbSource source = {.picture_kind = HAPGPU_PICTURE_RGBA8, .width = width, .height = height, .row_bytes = rowBytes};
+    return frames_from_source(context, &source, frameCount, rgbaFrames, count, textureFormats, compressors, chunkCounts,
+                              outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, 0);
 }
 
 /* The two halves of HapGpuEncodeFramesRGBA / HapGpuEncodeFrames (include/hap_gpu.h): everything launched, nothing waited for. */
@@ -760,15 +760,9 @@ unsigned int HapGpuEncodeFramesRGBABegin(HapGpuContext *context, unsigned int fr
                                          unsigned long *outputBuffersBytesUsed, unsigned int *results,
                                          unsigned int flags)
 {
-    unsigned r;
-    if (!context || frameCount > HAP_BATCH_SLICE)
-        return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_encode_pictures(context, frameCount, rgbaFrames, width, height, rowBytes, count, textureFormats,
-                             compressors, chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed,
-                             results, flags, HAPGPU_PICTURE_RGBA8, 1);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    const HapbSource source = {.picture_kind = HAPGPU_PICTURE_RGBA8, .width = width, .height = height, .row_bytes = rowBytes};
+    return frames_from_source(context, &source, frameCount, rgbaFrames, count, textureFormats, compressors, chunkCounts,
+                              outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, 1);
 }
 
 /* Planar float tensors -> textures and frames: the RGBA calls with the block encode of bc_encode_planes.hip */
@@ -779,14 +773,11 @@ unsigned int HapGpuCompressPlanes(HapGpuContext *context, const void *planes, un
                                   unsigned long *outputBytesUsed)
 {
     const HapbPlanes layout = {channels, element, planeBytes, scale, bias};
-    unsigned r;
-    if (!context || !planes || !output || !hapb_planes_encode_valid(width, height, rowBytes, &layout, 1u, &textureFormat))
+    const HapbSource source = {.picture_kind = HAPGPU_PICTURE_RGBA8, .planes = &layout, .width = width, .height = height,
+                               .row_bytes = rowBytes};
+    if (!planes || !output || !hapb_planes_encode_valid(width, height, rowBytes, &layout, 1u, &textureFormat))
         return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_compress_planes(context, planes, width, height, rowBytes, &layout, textureFormat, output, outputBytes,
-                             outputBytesUsed);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    return texture_from_source(context, &source, planes, textureFormat, output, outputBytes, outputBytesUsed, 0u);
 }
 
 /* what does not depend on a frame or on the context, checked before either is looked at: 0 = in order; else every
@@ -816,22 +807,13 @@ unsigned int HapGpuEncodeFramesPlanes(HapGpuContext *context, unsigned int frame
                                       unsigned int flags)
 {
     const HapbPlanes layout = {channels, element, planeBytes, scale, bias};
-    unsigned r = HapResult_No_Error, done;
+    const HapbSource source = {.picture_kind = HAPGPU_PICTURE_RGBA8, .planes = &layout, .width = width, .height = height,
+                               .row_bytes = rowBytes};
     if (planes_encode_refused(frameCount, planeFrames, &layout, rowBytes, width, height, count, textureFormats, compressors,
-                              chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results) || !context)
+                              chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results))
         return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    for (done = 0; done < frameCount; done += HAP_BATCH_SLICE) {
-        const unsigned n = frameCount - done < HAP_BATCH_SLICE ? frameCount - done : HAP_BATCH_SLICE;
-        const unsigned rc = hapb_encode_planes(context, n, planeFrames + done, width, height, rowBytes, &layout, count,
-                                               textureFormats, compressors, chunkCounts, outputBuffers + done,
-                                               outputBuffersBytes + done, outputBuffersBytesUsed + done, results + done,
-                                               flags, 0);
-        if (r == HapResult_No_Error)
-            r = rc;
-    }
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    return frames_from_source(context, &source, frameCount, planeFrames, count, textureFormats, compressors, chunkCounts,
+                              outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, 0);
 }
 
 unsigned int HapGpuEncodeFramesPlanesBegin(HapGpuContext *context, unsigned int frameCount,
@@ -846,17 +828,14 @@ unsigned int HapGpuEncodeFramesPlanesBegin(HapGpuContext *context, unsigned int 
                                            unsigned int flags)
 {
     const HapbPlanes layout = {channels, element, planeBytes, scale, bias};
-    unsigned r;
-    if (frameCount > HAP_BATCH_SLICE ||
+    const HapbSource source = {.picture_kind = HAPGPU_PICTURE_RGBA8, .planes = &layout, .width = width, .height = height,
+                               .row_bytes = rowBytes};
+    if (frameCount > HAP_SLICE_ENTRIES ||
         planes_encode_refused(frameCount, planeFrames, &layout, rowBytes, width, height, count, textureFormats, compressors,
-                              chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results) || !context)
+                              chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results))
         return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_encode_planes(context, frameCount, planeFrames, width, height, rowBytes, &layout, count, textureFormats,
-                           compressors, chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results,
-                           flags, 1);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    return frames_from_source(context, &source, frameCount, planeFrames, count, textureFormats, compressors, chunkCounts,
+                              outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, 1);
 }
 
 /* RGBA16F pictures -> Hap HDR: the RGBA calls with 8-byte texels and one BC6H texture per frame */
@@ -864,14 +843,8 @@ unsigned int HapGpuCompressRGBAHalf(HapGpuContext *context, const void *rgbaHalf
                                     unsigned int height, unsigned long rowBytes, unsigned int textureFormat,
                                     void *output, unsigned long outputBytes, unsigned long *outputBytesUsed)
 {
-    unsigned r;
-    if (!context)
-        return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_compress_rgba(context, rgbaHalf, width, height, rowBytes, textureFormat, output, outputBytes,
-                           outputBytesUsed, 1, 0u, HAPGPU_PICTURE_RGBA16F);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    const HapbSource source = {.picture_kind = HAPGPU_PICTURE_RGBA16F, .width = width, .height = height, .row_bytes = rowBytes};
+    return texture_from_source(context, &source, rgbaHalf, textureFormat, output, outputBytes, outputBytesUsed, 0u);
 }
 
 unsigned int HapGpuEncodeFramesRGBAHalf(HapGpuContext *context, unsigned int frameCount,
@@ -882,26 +855,9 @@ unsigned int HapGpuEncodeFramesRGBAHalf(HapGpuContext *context, unsigned int fra
                                         unsigned long *outputBuffersBytesUsed, unsigned int *results,
                                         unsigned int flags)
 {
-    unsigned r = HapResult_No_Error, done;
-    if (!context)
-        return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    if (frameCount <= HAP_BATCH_SLICE || !rgbaHalfFrames || !outputBuffers || !outputBuffersBytes || !outputBuffersBytesUsed || !results) {
-        r = hapb_encode_pictures(context, frameCount, rgbaHalfFrames, width, height, rowBytes, 1u, &textureFormat, &compressor,
-                             &chunkCount, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, HAPGPU_PICTURE_RGBA16F, 0);
-    } else {
-        for (done = 0; done < frameCount; done += HAP_BATCH_SLICE) {
-            const unsigned n = frameCount - done < HAP_BATCH_SLICE ? frameCount - done : HAP_BATCH_SLICE;
-            const unsigned rc = hapb_encode_pictures(context, n, rgbaHalfFrames + done, width, height, rowBytes, 1u, &textureFormat,
-                                                 &compressor, &chunkCount, outputBuffers + done, outputBuffersBytes + done,
-                                                 outputBuffersBytesUsed + done, results + done, flags,
-                                                 HAPGPU_PICTURE_RGBA16F, 0);
-            if (r == HapResult_No_Error)
-                r = rc;
-        }
-    }
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    const HapbSource source = {.picture_kind = HAPGPU_PICTURE_RGBA16F, .width = width, .height = height, .row_bytes = rowBytes};
+    return frames_from_source(context, &source, frameCount, rgbaHalfFrames, 1u, &textureFormat, &compressor, &chunkCount,
+                              outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, 0);
 }
 
 unsigned int HapGpuEncodeFramesRGBAHalfBegin(HapGpuContext *context, unsigned int frameCount,
@@ -912,14 +868,9 @@ unsigned int HapGpuEncodeFramesRGBAHalfBegin(HapGpuContext *context, unsigned in
                                              unsigned long *outputBuffersBytesUsed, unsigned int *results,
                                              unsigned int flags)
 {
-    unsigned r;
-    if (!context || frameCount > HAP_BATCH_SLICE)
-        return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_encode_pictures(context, frameCount, rgbaHalfFrames, width, height, rowBytes, 1u, &textureFormat, &compressor,
-                         &chunkCount, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, HAPGPU_PICTURE_RGBA16F, 1);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    const HapbSource source = {.picture_kind = HAPGPU_PICTURE_RGBA16F, .width = width, .height = height, .row_bytes = rowBytes};
+    return frames_from_source(context, &source, frameCount, rgbaHalfFrames, 1u, &textureFormat, &compressor, &chunkCount,
+                              outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, 1);
 }
 
 /* A8 pictures -> Hap Alpha-Only: the RGBA calls with 1-byte texels and one RGTC1 texture per frame */
@@ -927,14 +878,8 @@ unsigned int HapGpuCompressAlpha(HapGpuContext *context, const void *alpha, unsi
                                  unsigned long rowBytes, void *output, unsigned long outputBytes,
                                  unsigned long *outputBytesUsed)
 {
-    unsigned r;
-    if (!context)
-        return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_compress_rgba(context, alpha, width, height, rowBytes, HapTextureFormat_A_RGTC1, output, outputBytes,
-                           outputBytesUsed, 1, 0u, HAPGPU_PICTURE_A8);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    const HapbSource source = {.picture_kind = HAPGPU_PICTURE_A8, .width = width, .height = height, .row_bytes = rowBytes};
+    return texture_from_source(context, &source, alpha, HapTextureFormat_A_RGTC1, output, outputBytes, outputBytesUsed, 0u);
 }
 
 unsigned int HapGpuDecompressAlpha(HapGpuContext *context, const void *texture, unsigned long textureBytes,
@@ -954,28 +899,10 @@ unsigned int HapGpuEncodeFramesAlpha(HapGpuContext *context, unsigned int frameC
                                      const unsigned long *outputBuffersBytes, unsigned long *outputBuffersBytesUsed,
                                      unsigned int *results, unsigned int flags)
 {
+    const HapbSource source = {.picture_kind = HAPGPU_PICTURE_A8, .width = width, .height = height, .row_bytes = rowBytes};
     const unsigned format = HapTextureFormat_A_RGTC1;
-    unsigned r = HapResult_No_Error, done;
-    if (!context)
-        return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    if (frameCount <= HAP_BATCH_SLICE || !alphaFrames || !outputBuffers || !outputBuffersBytes || !outputBuffersBytesUsed || !results) {
-        r = hapb_encode_pictures(context, frameCount, alphaFrames, width, height, rowBytes, 1u, &format, &compressor,
-                                 &chunkCount, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags,
-                                 HAPGPU_PICTURE_A8, 0);
-    } else {
-        for (done = 0; done < frameCount; done += HAP_BATCH_SLICE) {
-            const unsigned n = frameCount - done < HAP_BATCH_SLICE ? frameCount - done : HAP_BATCH_SLICE;
-            const unsigned rc = hapb_encode_pictures(context, n, alphaFrames + done, width, height, rowBytes, 1u, &format,
-                                                     &compressor, &chunkCount, outputBuffers + done, outputBuffersBytes + done,
-                                                     outputBuffersBytesUsed + done, results + done, flags,
-                                                     HAPGPU_PICTURE_A8, 0);
-            if (r == HapResult_No_Error)
-                r = rc;
-        }
-    }
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    return frames_from_source(context, &source, frameCount, alphaFrames, 1u, &format, &compressor, &chunkCount,
+                              outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, 0);
 }
 
 unsigned int HapGpuEncodeFramesAlphaBegin(HapGpuContext *context, unsigned int frameCount,
@@ -985,16 +912,10 @@ unsigned int HapGpuEncodeFramesAlphaBegin(HapGpuContext *context, unsigned int f
                                           unsigned long *outputBuffersBytesUsed, unsigned int *results,
                                           unsigned int flags)
 {
+    const HapbSource source = {.picture_kind = HAPGPU_PICTURE_A8, .width = width, .height = height, .row_bytes = rowBytes};
     const unsigned format = HapTextureFormat_A_RGTC1;
-    unsigned r;
-    if (!context || frameCount > HAP_BATCH_SLICE)
-        return HapResult_Bad_Arguments;
-    hapgpu_rt_lock(context->rt);
-    r = hapb_encode_pictures(context, frameCount, alphaFrames, width, height, rowBytes, 1u, &format, &compressor,
-                             &chunkCount, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags,
-                             HAPGPU_PICTURE_A8, 1);
-    hapgpu_rt_unlock(context->rt);
-    return r;
+    return frames_from_source(context, &source, frameCount, alphaFrames, 1u, &format, &compressor, &chunkCount,
+                              outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, 1);
 }
 
 unsigned int HapGpuEncodeFramesBegin(HapGpuContext *context, unsigned int frameCount, unsigned int count,
@@ -1007,7 +928,7 @@ unsigned int HapGpuEncodeFramesBegin(HapGpuContext *context, unsigned int frameC
 {
     const HapbEncodeArgs deferred = {0, NULL, 1, 0};
     unsigned r;
-    if (!context || frameCount > HAP_BATCH_SLICE)
+    if (!context || frameCount > HAP_SLICE_ENTRIES)
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
     r = hapb_encode(context, frameCount, count, inputBuffers, inputBuffersBytes, textureFormats, compressors, chunkCounts,
@@ -1041,12 +962,12 @@ unsigned int HapGpuDecodeFrames(HapGpuContext *context, unsigned int frameCount,
     if (!context)
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
-    if (frameCount <= HAP_BATCH_SLICE || !inputBuffers || !inputBuffersBytes || !outputBuffers || !outputBuffersBytes || !results) {
+    if (frameCount <= HAP_SLICE_ENTRIES || !inputBuffers || !inputBuffersBytes || !outputBuffers || !outputBuffersBytes || !results) {
         r = hapb_decode(context, frameCount, inputBuffers, inputBuffersBytes, index, outputBuffers,
                         outputBuffersBytes, outputBuffersBytesUsed, outputTextureFormats, results, flags, NULL);
     } else {
-        for (done = 0; done < frameCount; done += HAP_BATCH_SLICE) {
-            const unsigned n = frameCount - done < HAP_BATCH_SLICE ? frameCount - done : HAP_BATCH_SLICE;
+        for (done = 0; done < frameCount; done += HAP_SLICE_ENTRIES) {
+            const unsigned n = frameCount - done < HAP_SLICE_ENTRIES ? frameCount - done : HAP_SLICE_ENTRIES;
             const unsigned rc = hapb_decode(context, n, inputBuffers + done, inputBuffersBytes + done, index, outputBuffers + done,
                                             outputBuffersBytes + done, outputBuffersBytesUsed ? outputBuffersBytesUsed + done : NULL,
                                             outputTextureFormats ? outputTextureFormats + done : NULL, results + done, flags, NULL);
@@ -1097,8 +1018,8 @@ unsigned int HapGpuDecodeFrameTextures(HapGpuContext *context, unsigned int fram
             indices[(size_t)f * textureCount + t] = t;
         }
     hapgpu_rt_lock(context->rt);
-    for (done = 0; done < entries; done += HAP_BATCH_SLICE) {
-        const unsigned n = (unsigned)(entries - done < HAP_BATCH_SLICE ? entries - done : HAP_BATCH_SLICE);
+    for (done = 0; done < entries; done += HAP_SLICE_ENTRIES) {
+        const unsigned n = (unsigned)(entries - done < HAP_SLICE_ENTRIES ? entries - done : HAP_SLICE_ENTRIES);
         const HapbDecodeArgs entries_of = {indices + done, NULL, NULL, 0, NULL, 0u, NULL, NULL};
         const unsigned rc = hapb_decode(context, n, inputs + done, bytes + done, 0, outputBuffers + done, outputBuffersBytes + done,
                                         outputBuffersBytesUsed ? outputBuffersBytesUsed + done : NULL,

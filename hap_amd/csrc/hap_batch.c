@@ -215,12 +215,13 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                          !ctx->no_half_tiles) ? 1u : 0u;
         if (t->half_tiles)
             any_half_tiles = 1;
-        /* a call that starts from RGBA pictures (hapb_encode_rgba): the block compressor makes the blocks of its
+        /* a call that starts from RGBA8 pictures (hapb_source_frames): the block compressor makes the blocks of its
            fragment itself, one pass less over the texture and the pixel loads of one wave under the matching of the
            others (snappy_compress_blocks.hip).  One texture per frame. */
         {
-            if (job && !ctx->no_fusion && count == 1u && job->texel_bytes == 4u && !job->planes.channels && (job->row_bytes & 3u) == 0 &&
-                (unsigned long long)job->row_bytes * job->height < 0xFFFFFFFFull && job->width / 4u >= 1u) {
+            if (job && !ctx->no_fusion && count == 1u && job->source.picture_kind == HAPGPU_PICTURE_RGBA8 && !job->source.planes &&
+                (job->source.row_bytes & 3u) == 0 && (unsigned long long)job->source.row_bytes * job->source.height < 0xFFFFFFFFull &&
+                job->source.width / 4u >= 1u) {
                 /* (code: HapGpuTexEnc.reserved bits 24..26; mask bit: which kernel the launcher starts) */
                 if (t->field_period == 4u && t->format == HapTextureFormat_YCoCg_DXT5) {
                     fused[i] = 3u; fused_mask |= 1u;
@@ -411,9 +412,9 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                 fe->chunk_acc = (uint64_t)(uintptr_t)(dacc + (size_t)k * chunks_per_frame);
             if (fused_mask) {
                 fe->rgba = job->host_table[f];
-                fe->rgba_row_bytes = (uint32_t)job->row_bytes;
-                fe->rgba_blocks_x = job->width / 4u;
-                fe->rgba_blocks_x_inv = HAPGPU_DIV_INV(job->width / 4u);
+                fe->rgba_row_bytes = (uint32_t)job->source.row_bytes;
+                fe->rgba_blocks_x = job->source.width / 4u;
+                fe->rgba_blocks_x_inv = HAPGPU_DIV_INV(job->source.width / 4u);
             }
             for (i = 0; i < count; i++) {
                 HapGpuTexEnc *te = &fe->tex[i];
@@ -463,12 +464,13 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                     HAPB_MIX(g[i].format); HAPB_MIX(g[i].compressor); HAPB_MIX(g[i].chunk_count); HAPB_MIX(g[i].bytes);
                 }
                 if (job) {
-                    HAPB_MIX(job->frame_count); HAPB_MIX(job->width); HAPB_MIX(job->height); HAPB_MIX(job->row_bytes);
-                    HAPB_MIX(job->wide + 2); HAPB_MIX(job->texel_bytes);
-                    if (job->planes.channels) {
+                    const HapbSource *const src = &job->source;
+                    HAPB_MIX(job->frame_count); HAPB_MIX(src->width); HAPB_MIX(src->height); HAPB_MIX(src->row_bytes);
+                    HAPB_MIX(job->wide + 2); HAPB_MIX(src->picture_kind);
+                    if (src->planes) {
                         /* (scale and bias are kernel arguments: part of what a recording holds) */
-                        HAPB_MIX(job->planes.channels + 8u); HAPB_MIX(job->planes.element); HAPB_MIX(job->planes.plane_bytes);
-                        for (i = 0; i < job->planes.channels; i++) {
+                        HAPB_MIX(src->planes->channels + 8u); HAPB_MIX(src->planes->element); HAPB_MIX(src->planes->plane_bytes);
+                        for (i = 0; i < src->planes->channels; i++) {
                             uint32_t bits[2];
                             memcpy(&bits[0], &job->plane_scale[i], 4);
                             memcpy(&bits[1], &job->plane_bias[i], 4);
@@ -483,6 +485,7 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                this context and the same launches are issued once more, plainly) */
             while (graph != 1) {
                 if (job) {
+                    const HapbSource *const src = &job->source;
                     launch_rc |= (unsigned)hapgpu_rt_h2d(rt, job->device_table, job->host_table,
                                                          sizeof(uint64_t) * (size_t)(1u + job->count) * job->frame_count);
                     /* Hap Q Alpha: both textures from one pass over the RGBA (64 + 16 + 8 bytes per block);
@@ -495,15 +498,15 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                             const uint64_t *dt = job->device_table;
                             const HapGpuPictureTable t = {{dt, dt + (size_t)(1u + i) * job->frame_count,
                                                            pair ? dt + 2u * (size_t)job->frame_count : NULL}, {0u, 0u, 0u}};
-                            launch_rc |= job->height / 4u > 65535u ? 1u :
-                                         job->planes.channels ?
-                                         (unsigned)hapgpu_k_block_encode_planes(rt, &t, job->frame_count, job->width, job->height,
-                                                                                job->formats[i], (unsigned)pair | refine, job->planes.channels,
-                                                                                job->planes.element, job->planes.plane_bytes,
-                                                                                job->row_bytes, job->plane_scale, job->plane_bias) :
-                                         (unsigned)hapgpu_k_block_encode(rt, &t, job->frame_count, job->width, job->height,
-                                                                         job->row_bytes, job->formats[i], (unsigned)pair | refine, job->wide,
-                                                                         job->picture_kind);
+                            launch_rc |= src->height / 4u > 65535u ? 1u :
+                                         src->planes ?
+                                         (unsigned)hapgpu_k_block_encode_planes(rt, &t, job->frame_count, src->width, src->height,
+                                                                                job->formats[i], (unsigned)pair | refine, src->planes->channels,
+                                                                                src->planes->element, src->planes->plane_bytes,
+                                                                                src->row_bytes, job->plane_scale, job->plane_bias) :
+                                         (unsigned)hapgpu_k_block_encode(rt, &t, job->frame_count, src->width, src->height,
+                                                                         src->row_bytes, job->formats[i], (unsigned)pair | refine, job->wide,
+                                                                         src->picture_kind);
                         }
                 }
                 launch_rc |= (unsigned)hapgpu_rt_h2d(rt, dframes, hframes, sizeof(HapGpuFrameEnc) * live);
@@ -582,6 +585,12 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
             if (job) {
                 pd->job = *job;
                 pd->has_job = 1;
+                if (job->source.planes) {
+                    /* (the caller's description need not outlive the first half either) */
+                    pd->planes = *job->source.planes;
+                    pd->planes.scale = pd->planes.bias = NULL;
+                    pd->job.source.planes = &pd->planes;
+                }
             }
             free(stage_off_in);
             if (a->defer) {
@@ -749,87 +758,6 @@ static int kind_makes_format(unsigned kind, unsigned format, int bptc)
            format == HapTextureFormat_YCoCg_DXT5 || format == HapTextureFormat_A_RGTC1 || bptc;
 }
 
-/* what the kernels ask of a picture's address (in device memory) and row pitch when they read it: RGBA16F 16 bytes,
-   else 4 */
-static unsigned source_align_mask(unsigned kind)
-{
-    return kind == HAPGPU_PICTURE_RGBA16F ? 15u : 3u;
-}
-
-unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width, unsigned height,
-                            unsigned long row_bytes, unsigned format, void *output,
-                            unsigned long output_bytes, unsigned long *used, int synchronise, unsigned flags,
-                            unsigned picture_kind)
-{
-    /* BC7 only when asked (HAPGPU_ENCODE_BPTC_BLOCKS); BC6H only from half pictures, and nothing else from those; A8
-       pictures make RGTC1 */
-    const int bptc = (flags & HAPGPU_ENCODE_BPTC_BLOCKS) && format == HapTextureFormat_RGBA_BPTC_UNORM;
-    const int grid_rows = bptc || picture_kind != HAPGPU_PICTURE_RGBA8;    /* a block row per grid row */
-    const size_t texel = HAPGPU_PICTURE_TEXEL_BYTES(picture_kind);
-    const unsigned align = source_align_mask(picture_kind);
-    hapgpu_rt *rt = ctx->rt;
-    const size_t block = hapf_block_bytes(format);
-    HapGpuPictureTable t = {{NULL, NULL, NULL}, {0u, 0u, 0u}};
-    size_t need, rgba_bytes;
-    const void *src = rgba;
-    void *dst = output;
-    int rc = 0;
-    if (context_busy(ctx, NULL, 0))
-        return HapResult_Internal_Error;
-    if (!rgba || !output || width == 0 || height == 0 || (width & 3u) || (height & 3u) ||
-        row_bytes < (unsigned long)width * texel || !kind_makes_format(picture_kind, format, bptc))
-        return HapResult_Bad_Arguments;
-    need = (size_t)(width / 4u) * (height / 4u) * block;
-    if (output_bytes < need)
-        return HapResult_Buffer_Too_Small;
-    /* device pictures 4-byte aligned with rows a multiple of 4 (half pictures: 16 and 16), device outputs aligned to
-       their blocks; at most 65535 block rows for BC7, BC6H and A8 pictures, 2^32 * 255/256 blocks for the others */
-    if ((row_bytes & align) || (is_dev(ctx, rgba) && ((uintptr_t)rgba & align)) ||
-        (is_dev(ctx, output) && ((uintptr_t)output & (block - 1u))) ||
-        (grid_rows ? height / 4u > 65535u : (unsigned long long)(width / 4u) * (height / 4u) > 0xFFFFFFFFull / 256u * 255u))
-        return HapResult_Bad_Arguments;
-    rgba_bytes = (size_t)row_bytes * (height - 1u) + (size_t)width * texel;
-    if (!is_dev(ctx, rgba)) {
-        void *s = hapgpu_rt_device_scratch(rt, D_RGBA_STAGE, rgba_bytes);
-        if (!s || hapgpu_rt_h2d(rt, s, rgba, rgba_bytes))
-            return HapResult_Internal_Error;
-        src = s;
-    }
-    if (!is_dev(ctx, output)) {
-        dst = hapgpu_rt_device_scratch(rt, D_BC_TEX, need);
-        if (!dst)
-            return HapResult_Internal_Error;
-    }
-    t.one[0] = (uint64_t)(uintptr_t)src;
-    t.one[1] = (uint64_t)(uintptr_t)dst;
-    rc = hapgpu_k_block_encode(rt, &t, 1u, width, height, row_bytes, format,
-                               (flags & HAPGPU_ENCODE_REFINE_ENDPOINTS) ? HAPGPU_BLOCK_ENCODE_REFINE : 0u,
-                               (((uintptr_t)src | row_bytes) & 15u) == 0 && !(picture_kind == HAPGPU_PICTURE_A8 && ctx->no_wide_planes),
-                               picture_kind);
-    if (rc == 1)
-        return HapResult_Bad_Arguments;
-    if (rc)
-        return HapResult_Internal_Error;
-    if (dst != output && hapgpu_rt_d2h(rt, output, dst, need))
-        return HapResult_Internal_Error;
-    if ((synchronise || dst != output) && hapgpu_rt_sync(rt))
-        return HapResult_Internal_Error;
-    if (used)
-        *used = (unsigned long)need;
-    return HapResult_No_Error;
-}
-
-
-unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
-                          unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
-                          const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
-                          void *const *outputs, const unsigned long *output_bytes,
-                          unsigned long *output_used, unsigned *results, unsigned flags)
-{
-    return hapb_encode_pictures(ctx, frame_count, rgba_frames, width, height, row_bytes, count, formats, compressors,
-                                chunk_counts, outputs, output_bytes, output_used, results, flags, HAPGPU_PICTURE_RGBA8, 0);
-}
-
 /* the size of an element of a planar tensor */
 static size_t plane_element_bytes(unsigned element)
 {
@@ -856,18 +784,109 @@ int hapb_planes_encode_valid(unsigned width, unsigned height, unsigned long row_
     return count == 1u && kind_makes_format(HAPGPU_PICTURE_RGBA8, formats[0], 0);
 }
 
-/* hapb_encode_pictures, or with `planes` hapb_encode_planes: planar tensors in device memory in place of the pictures
-   (picture_kind is then not looked at, and the arguments have passed hapb_planes_encode_valid) */
-static unsigned encode_pictures(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
-                                unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
-                                const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
-                                void *const *outputs, const unsigned long *output_bytes,
-                                unsigned long *output_used, unsigned *results, unsigned flags, unsigned picture_kind,
-                                const HapbPlanes *planes, int defer)
+/* the size of a source's texel: of a tensor, one element of one plane */
+static size_t source_texel_bytes(const HapbSource *source)
+{
+    return source->planes ? plane_element_bytes(source->planes->element) : HAPGPU_PICTURE_TEXEL_BYTES(source->picture_kind);
+}
+
+/* what the kernels ask of a source's address (in device memory) and row pitch when they read it: tensors four
+   elements, RGBA16F pictures 16 bytes, else 4 */
+static unsigned source_align_mask(const HapbSource *source)
+{
+    if (source->planes)
+        return 4u * (unsigned)plane_element_bytes(source->planes->element) - 1u;
+    return source->picture_kind == HAPGPU_PICTURE_RGBA16F ? 15u : 3u;
+}
+
+/* the whole-call answer: every result set (a NULL results: none), `code` returned */
+static unsigned answer_all(unsigned *results, unsigned frame_count, unsigned code)
+{
+    unsigned f;
+    for (f = 0; results && f < frame_count; f++)
+        results[f] = code;
+    return code;
+}
+
+unsigned hapb_source_texture(HapGpuContext *ctx, const HapbSource *source, const void *picture, unsigned format,
+                             void *output, unsigned long output_bytes, unsigned long *used, unsigned flags)
+{
+    const HapbPlanes *const planes = source->planes;
+    const unsigned kind = source->picture_kind, width = source->width, height = source->height;
+    const unsigned long row_bytes = source->row_bytes;
+    /* BC7 only when asked (HAPGPU_ENCODE_BPTC_BLOCKS); BC6H only from half pictures, and nothing else from those; A8
+       pictures make RGTC1 */
+    const int bptc = !planes && (flags & HAPGPU_ENCODE_BPTC_BLOCKS) && format == HapTextureFormat_RGBA_BPTC_UNORM;
+    const int grid_rows = bptc || kind != HAPGPU_PICTURE_RGBA8;    /* a block row per grid row */
+    const size_t texel = source_texel_bytes(source), block = hapf_block_bytes(format);
+    const unsigned align = source_align_mask(source);
+    hapgpu_rt *rt = ctx->rt;
+    HapGpuPictureTable t = {{NULL, NULL, NULL}, {0u, 0u, 0u}};
+    size_t need;
+    const void *src = picture;
+    void *dst = output;
+    int rc;
+    if (context_busy(ctx, NULL, 0))
+        return HapResult_Internal_Error;
+    if (!picture || !output ||
+        (planes ? !hapb_planes_encode_valid(width, height, row_bytes, planes, 1u, &format)
+                : width == 0 || height == 0 || (width & 3u) || (height & 3u) || row_bytes < (unsigned long)width * texel ||
+                  !kind_makes_format(kind, format, bptc)))
+        return HapResult_Bad_Arguments;
+    need = (size_t)(width / 4u) * (height / 4u) * block;
+    if (output_bytes < need)
+        return HapResult_Buffer_Too_Small;
+    /* tensors in device memory, aligned to what a lane loads; device pictures 4-byte aligned with rows a multiple of 4
+       (half pictures: 16 and 16), at most 65535 block rows for BC7, BC6H and A8 pictures, 2^32 * 255/256 blocks for the
+       others; device outputs aligned to their blocks */
+    if ((planes ? !is_dev(ctx, picture) || ((uintptr_t)picture & align)
+                : (row_bytes & align) || (is_dev(ctx, picture) && ((uintptr_t)picture & align)) ||
+                  (grid_rows ? height / 4u > 65535u : (unsigned long long)(width / 4u) * (height / 4u) > 0xFFFFFFFFull / 256u * 255u)) ||
+        (is_dev(ctx, output) && ((uintptr_t)output & (block - 1u))))
+        return HapResult_Bad_Arguments;
+    if (!is_dev(ctx, picture)) {
+        const size_t picture_bytes = (size_t)row_bytes * (height - 1u) + (size_t)width * texel;
+        void *s = hapgpu_rt_device_scratch(rt, D_RGBA_STAGE, picture_bytes);
+        if (!s || hapgpu_rt_h2d(rt, s, picture, picture_bytes))
+            return HapResult_Internal_Error;
+        src = s;
+    }
+    if (!is_dev(ctx, output)) {
+        dst = hapgpu_rt_device_scratch(rt, D_BC_TEX, need);
+        if (!dst)
+            return HapResult_Internal_Error;
+    }
+    t.one[0] = (uint64_t)(uintptr_t)src;
+    t.one[1] = (uint64_t)(uintptr_t)dst;
+    rc = planes ? hapgpu_k_block_encode_planes(rt, &t, 1u, width, height, format, 0u, planes->channels, planes->element,
+                                               planes->plane_bytes, row_bytes, planes->scale, planes->bias)
+                : hapgpu_k_block_encode(rt, &t, 1u, width, height, row_bytes, format,
+                                        (flags & HAPGPU_ENCODE_REFINE_ENDPOINTS) ? HAPGPU_BLOCK_ENCODE_REFINE : 0u,
+                                        (((uintptr_t)src | row_bytes) & 15u) == 0 && !(kind == HAPGPU_PICTURE_A8 && ctx->no_wide_planes),
+                                        kind);
+    if (rc == 1)
+        return HapResult_Bad_Arguments;
+    if (rc || (dst != output && hapgpu_rt_d2h(rt, output, dst, need)) || hapgpu_rt_sync(rt))
+        return HapResult_Internal_Error;
+    if (used)
+        *used = (unsigned long)need;
+    return HapResult_No_Error;
+}
+
+/* one slice of hapb_source_frames: at most HAP_SLICE_ENTRIES frames, or a call that is refused as a whole.  A planar
+   source has passed hapb_planes_encode_valid */
+static unsigned source_slice(HapGpuContext *ctx, const HapbSource *source, unsigned frame_count,
+                             const void *const *pictures, unsigned count, const unsigned *formats,
+                             const unsigned *compressors, const unsigned *chunk_counts, void *const *outputs,
+                             const unsigned long *output_bytes, unsigned long *output_used, unsigned *results,
+                             unsigned flags, int defer)
 {
     hapgpu_rt *rt = ctx->rt;
-    const size_t texel = planes ? plane_element_bytes(planes->element) : HAPGPU_PICTURE_TEXEL_BYTES(picture_kind);
-    const unsigned align = planes ? 4u * (unsigned)texel - 1u : source_align_mask(picture_kind);
+    const HapbPlanes *const planes = source->planes;
+    const unsigned picture_kind = source->picture_kind, width = source->width, height = source->height;
+    const unsigned long row_bytes = source->row_bytes;
+    const size_t texel = source_texel_bytes(source);
+    const unsigned align = source_align_mask(source);
     unsigned long tex_bytes[2] = {0, 0};
     size_t per_frame = 0, rgba_bytes, tex_off[2] = {0, 0};
     unsigned i, f, rc;
@@ -875,27 +894,19 @@ static unsigned encode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
     const void **tex_ptrs;
     uint64_t *hsrc, *dsrc;
     int wide = !(picture_kind == HAPGPU_PICTURE_A8 && ctx->no_wide_planes);
-    if (frame_count == 0)
-        return HapResult_No_Error;
     if (context_busy(ctx, results, frame_count))
         return HapResult_Internal_Error;
-    if (!results || !rgba_frames || count == 0 || count > 2 || !formats || width == 0 || height == 0 ||
+    if (!results || !pictures || count == 0 || count > 2 || !formats || width == 0 || height == 0 ||
         (width & 3u) || (height & 3u) || row_bytes < (unsigned long)width * texel ||
         (picture_kind != HAPGPU_PICTURE_RGBA8 && (row_bytes & align)) ||
-        (picture_kind == HAPGPU_PICTURE_A8 && height / 4u > 65535u)) {
-        for (f = 0; results && f < frame_count; f++)
-            results[f] = HapResult_Bad_Arguments;
-        return HapResult_Bad_Arguments;
-    }
+        (picture_kind == HAPGPU_PICTURE_A8 && height / 4u > 65535u))
+        return answer_all(results, frame_count, HapResult_Bad_Arguments);
     for (i = 0; i < count; i++) {
         /* (BC7 only when asked, and alone: no Hap variant pairs it with a second texture) */
         const int bptc = !planes && (flags & HAPGPU_ENCODE_BPTC_BLOCKS) && count == 1u && formats[i] == HapTextureFormat_RGBA_BPTC_UNORM;
         /* (half pictures make BC6H, alone, and nothing else; RGBA8 pictures never make it; A8 pictures make RGTC1, alone) */
-        if ((picture_kind != HAPGPU_PICTURE_RGBA8 && count != 1u) || !kind_makes_format(picture_kind, formats[i], bptc)) {
-            for (f = 0; f < frame_count; f++)
-                results[f] = HapResult_Bad_Arguments;
-            return HapResult_Bad_Arguments;
-        }
+        if ((picture_kind != HAPGPU_PICTURE_RGBA8 && count != 1u) || !kind_makes_format(picture_kind, formats[i], bptc))
+            return answer_all(results, frame_count, HapResult_Bad_Arguments);
         tex_bytes[i] = (unsigned long)((size_t)(width / 4u) * (height / 4u) * hapf_block_bytes(formats[i]));
         tex_off[i] = per_frame;
         per_frame += align_up(tex_bytes[i], 256);
@@ -908,13 +919,11 @@ static unsigned encode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
     dsrc = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, sizeof(uint64_t) * 3u * frame_count);
     if (!textures || !tex_ptrs || !hsrc || !dsrc) {
         free(tex_ptrs);
-        for (f = 0; f < frame_count; f++)
-            results[f] = HapResult_Internal_Error;
-        return HapResult_Internal_Error;
+        return answer_all(results, frame_count, HapResult_Internal_Error);
     }
     memset(hsrc, 0, sizeof(uint64_t) * 3u * frame_count);       /* address 0: the kernel skips the picture */
     for (f = 0; f < frame_count; f++) {
-        const void *src = rgba_frames[f];
+        const void *src = pictures[f];
         for (i = 0; i < count; i++)
             tex_ptrs[(size_t)f * count + i] = NULL;     /* NULL input => Bad_Arguments for that frame */
         if (!src)
@@ -956,21 +965,13 @@ static unsigned encode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
         job.device_table = dsrc;
         job.frame_count = frame_count;
         job.count = count;
-        job.width = width;
-        job.height = height;
-        job.row_bytes = row_bytes;
+        job.source = *source;
         job.wide = wide;
-        job.texel_bytes = (unsigned)texel;
-        job.picture_kind = picture_kind;
         for (i = 0; i < count; i++)
             job.formats[i] = formats[i];
-        if (planes) {
-            job.planes = *planes;
-            job.planes.scale = job.planes.bias = NULL;
-            for (i = 0; i < planes->channels; i++) {
-                job.plane_scale[i] = planes->scale[i];
-                job.plane_bias[i] = planes->bias[i];
-            }
+        for (i = 0; planes && i < planes->channels; i++) {
+            job.plane_scale[i] = planes->scale[i];
+            job.plane_bias[i] = planes->bias[i];
         }
         rc = hapb_encode(ctx, frame_count, count, tex_ptrs, tex_bytes, formats, compressors, chunk_counts, outputs,
                          output_bytes, output_used, results, flags, &args);
@@ -979,78 +980,35 @@ static unsigned encode_pictures(HapGpuContext *ctx, unsigned frame_count, const 
     return rc;
 }
 
-unsigned hapb_encode_pictures(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
-                              unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
-                              const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
-                              void *const *outputs, const unsigned long *output_bytes,
-                              unsigned long *output_used, unsigned *results, unsigned flags, unsigned picture_kind,
-                              int defer)
+unsigned hapb_source_frames(HapGpuContext *ctx, const HapbSource *source, unsigned frame_count,
+                            const void *const *pictures, unsigned count, const unsigned *formats,
+                            const unsigned *compressors, const unsigned *chunk_counts, void *const *outputs,
+                            const unsigned long *output_bytes, unsigned long *output_used, unsigned *results,
+                            unsigned flags, int defer)
 {
-    return encode_pictures(ctx, frame_count, rgba_frames, width, height, row_bytes, count, formats, compressors,
-                           chunk_counts, outputs, output_bytes, output_used, results, flags, picture_kind, NULL, defer);
-}
-
-unsigned hapb_encode_planes(HapGpuContext *ctx, unsigned frame_count, const void *const *tensors, unsigned width,
-                            unsigned height, unsigned long row_bytes, const HapbPlanes *planes, unsigned count,
-                            const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
-                            void *const *outputs, const unsigned long *output_bytes, unsigned long *output_used,
-                            unsigned *results, unsigned flags, int defer)
-{
-    unsigned f;
+    unsigned r = HapResult_No_Error, done;
+    if (defer && frame_count > HAP_SLICE_ENTRIES)
+        return HapResult_Bad_Arguments;
     if (frame_count == 0)
         return HapResult_No_Error;
-    /* everything that does not depend on a frame, before any device is touched */
-    if (!results || !tensors || !compressors || !chunk_counts || !outputs || !output_bytes || !output_used ||
-        !hapb_planes_encode_valid(width, height, row_bytes, planes, count, formats)) {
-        for (f = 0; results && f < frame_count; f++)
-            results[f] = HapResult_Bad_Arguments;
-        return HapResult_Bad_Arguments;
+    /* tensors: everything that does not depend on a frame, before any device is touched */
+    if (source->planes &&
+        (!results || !pictures || !compressors || !chunk_counts || !outputs || !output_bytes || !output_used ||
+         !hapb_planes_encode_valid(source->width, source->height, source->row_bytes, source->planes, count, formats)))
+        return answer_all(results, frame_count, HapResult_Bad_Arguments);
+    /* (the kernels index frames with a grid dimension that holds 65535: larger batches go in slices; a call without the
+       arrays the slices would be cut from is refused in one piece) */
+    if (frame_count <= HAP_SLICE_ENTRIES || !pictures || !outputs || !output_bytes || !output_used || !results)
+        return source_slice(ctx, source, frame_count, pictures, count, formats, compressors, chunk_counts, outputs,
+                            output_bytes, output_used, results, flags, defer);
+    for (done = 0; done < frame_count; done += HAP_SLICE_ENTRIES) {
+        const unsigned n = frame_count - done < HAP_SLICE_ENTRIES ? frame_count - done : HAP_SLICE_ENTRIES;
+        const unsigned rc = source_slice(ctx, source, n, pictures + done, count, formats, compressors, chunk_counts,
+                                         outputs + done, output_bytes + done, output_used + done, results + done, flags, 0);
+        if (r == HapResult_No_Error)
+            r = rc;
     }
-    return encode_pictures(ctx, frame_count, tensors, width, height, row_bytes, count, formats, compressors, chunk_counts,
-                           outputs, output_bytes, output_used, results, flags, HAPGPU_PICTURE_RGBA8, planes, defer);
-}
-
-/* One tensor -> one texture: hapb_compress_rgba's output rules, the tensor in device memory */
-unsigned hapb_compress_planes(HapGpuContext *ctx, const void *tensor, unsigned width, unsigned height,
-                              unsigned long row_bytes, const HapbPlanes *planes, unsigned format, void *output,
-                              unsigned long output_bytes, unsigned long *used)
-{
-    hapgpu_rt *rt = ctx->rt;
-    HapGpuPictureTable t = {{NULL, NULL, NULL}, {0u, 0u, 0u}};
-    size_t block, need;
-    void *dst = output;
-    int rc;
-    if (context_busy(ctx, NULL, 0))
-        return HapResult_Internal_Error;
-    if (!tensor || !output || !hapb_planes_encode_valid(width, height, row_bytes, planes, 1u, &format))
-        return HapResult_Bad_Arguments;
-    block = hapf_block_bytes(format);
-    need = (size_t)(width / 4u) * (height / 4u) * block;
-    if (output_bytes < need)
-        return HapResult_Buffer_Too_Small;
-    if (!is_dev(ctx, tensor) || ((uintptr_t)tensor & (4u * plane_element_bytes(planes->element) - 1u)) ||
-        (is_dev(ctx, output) && ((uintptr_t)output & (block - 1u))))
-        return HapResult_Bad_Arguments;
-    if (!is_dev(ctx, output)) {
-        dst = hapgpu_rt_device_scratch(rt, D_BC_TEX, need);
-        if (!dst)
-            return HapResult_Internal_Error;
-    }
-    t.one[0] = (uint64_t)(uintptr_t)tensor;
-    t.one[1] = (uint64_t)(uintptr_t)dst;
-    rc = hapgpu_k_block_encode_planes(rt, &t, 1u, width, height, format, 0u, planes->channels, planes->element,
-                                      planes->plane_bytes, row_bytes, planes->scale, planes->bias);
-    if (rc == 1)
-        return HapResult_Bad_Arguments;
-    if (rc)
-        return HapResult_Internal_Error;
-    if (dst != output && hapgpu_rt_d2h(rt, output, dst, need))
-        return HapResult_Internal_Error;
-    if (hapgpu_rt_sync(rt))
-        return HapResult_Internal_Error;
-    if (used)
-        *used = (unsigned long)need;
-    return HapResult_No_Error;
+    return r;
 }
 
 /* ================================================================== decode */

@@ -7,6 +7,7 @@
 
 #include "../../include/hap_gpu.h"
 #include "hap_frame.h"
+#include "hap_slice.h"
 #include "hapgpu_abi.h"
 
 struct HapGpuContext {
@@ -50,20 +51,26 @@ typedef struct HapbPlanes {
                                        (plane_quantise.hpp) */
 } HapbPlanes;
 
+/* What an encode call's textures are made from: the mirror of HapbRoad, filled the same way. */
+typedef struct HapbSource {
+    unsigned picture_kind;      /* HAPGPU_PICTURE_*: RGBA8, RGBA16F, A8 */
+    const HapbPlanes *planes;   /* NULL: interleaved pictures of picture_kind; else (RGBA8: they make what those make)
+                                   planar tensors in device memory: row_bytes is the pitch of a plane's rows */
+    unsigned width, height;
+    unsigned long row_bytes;
+} HapbSource;
+
 typedef struct HapbBlockEncodeJob {
     const uint64_t *host_table;    /* pinned: [sources][outputs of texture 0][of texture 1], frame_count each */
     uint64_t *device_table;
-    unsigned frame_count, count, width, height, formats[2];
-    unsigned picture_kind;         /* HAPGPU_PICTURE_*: the pictures' layout */
-    unsigned texel_bytes;          /* of that layout: 4 (RGBA8), 8 (RGBA16F, which make BC6H) or 1 (A8, which make RGTC1);
-                                      only RGBA8 pictures are ever fused into the block compressor */
-    unsigned long row_bytes;
+    unsigned frame_count, count, formats[2];
+    /* source.planes != NULL: the sources are planar tensors in device memory, not pictures: the block encode is
+       hapgpu_k_block_encode_planes' and never part of the block compressor; source.picture_kind and wide mean nothing.
+       Only RGBA8 pictures are ever fused into the block compressor.  scale and bias are kept here (source.planes->scale
+       and ->bias are the caller's, which need not outlive the first half of a call in two halves: not looked at after
+       hapb_source_frames has returned). */
+    HapbSource source;
     int wide;
-    /* planes.channels != 0: the sources are planar tensors in device memory, not pictures (hapb_encode_planes): the block
-       encode is hapgpu_k_block_encode_planes' and never part of the block compressor; picture_kind, texel_bytes and wide
-       mean nothing.  scale and bias are kept here (planes.scale / planes.bias point to the caller's, which need not
-       outlive the first half of a call in two halves: not looked at after hapb_encode_planes has returned). */
-    HapbPlanes planes;
     float plane_scale[4], plane_bias[4];
 } HapbBlockEncodeJob;
 
@@ -84,6 +91,7 @@ typedef struct HapbEncodePending {
     HapGpuFrameEnc *hframes;          /* pinned scratch: stays as it is while the context takes no other call */
     uint8_t *out_stage;
     HapbBlockEncodeJob job;           /* a call that started from pictures (has_job) */
+    HapbPlanes planes;                /* ... from tensors: what job.source.planes points to (the caller's is gone) */
 } HapbEncodePending;
 unsigned hapb_encode_complete(HapGpuContext *ctx, HapbEncodePending *pending);
 /* ... or lets go of it without touching the client's arrays (the context is being destroyed): waits for the launches, frees `pending` */
@@ -105,13 +113,13 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                      void *const *outputs, const unsigned long *output_bytes,
                      unsigned long *output_used, unsigned *results, unsigned flags,
                      const HapbEncodeArgs *args);
-/* one picture -> one texture.  picture_kind (HAPGPU_PICTURE_*): RGBA8 and the DXT / RGTC1 formats (BC7 with
-   HAPGPU_ENCODE_BPTC_BLOCKS), RGBA16F and a BC6H format, or A8 and A_RGTC1 (hapb_encode_pictures' rules).
-   HAPGPU_ENCODE_REFINE_ENDPOINTS in flags goes down to the block kernel, which looks at it for DXT1 and DXT5 */
-unsigned hapb_compress_rgba(HapGpuContext *ctx, const void *rgba, unsigned width, unsigned height,
-                            unsigned long row_bytes, unsigned format, void *output,
-                            unsigned long output_bytes, unsigned long *used, int synchronise, unsigned flags,
-                            unsigned picture_kind);
+/* one picture or planar tensor -> one texture (host or device), results before it returns.  Pictures (host or device):
+   RGBA8 and the DXT / RGTC1 formats (BC7 with HAPGPU_ENCODE_BPTC_BLOCKS), RGBA16F and a BC6H format, or A8 and A_RGTC1
+   (hapb_source_frames' rules); HAPGPU_ENCODE_REFINE_ENDPOINTS in flags goes down to the block kernel, which looks at it
+   for DXT1 and DXT5.  A tensor (device memory): DXT1, DXT5, YCoCg-DXT5, or RGTC1 from the fourth plane (255 where there
+   are three); flags are not looked at */
+unsigned hapb_source_texture(HapGpuContext *ctx, const HapbSource *source, const void *picture, unsigned format,
+                             void *output, unsigned long output_bytes, unsigned long *used, unsigned flags);
 /* The crops of the resized planar roads (include/hap_gpu.h: HapGpuDecompressPlanesResized,
    HapGpuDecodeFramesPlanesResized): entry f's crop is (xs[f], ys[f], ws[f], hs[f]) in texels of the scaled picture, f
    counted from the call's first frame, and every tensor is out_w x out_h elements */
@@ -126,11 +134,6 @@ int hapb_resize_out_valid(const HapbResize *resize);
    hapb_region_fits */
 int hapb_resize_region(const HapbResize *resize, size_t f, unsigned width, unsigned height, unsigned scale_log2,
                        HapGpuRegion *region);
-/* one planar tensor in device memory -> one texture (host or device): DXT1, DXT5, YCoCg-DXT5, or RGTC1 from the fourth
-   plane (255 where there are three) */
-unsigned hapb_compress_planes(HapGpuContext *ctx, const void *tensor, unsigned width, unsigned height,
-                              unsigned long row_bytes, const HapbPlanes *planes, unsigned format, void *output,
-                              unsigned long output_bytes, unsigned long *used);
 /* what the planar encode calls ask whatever their tensors are: 1 = channels, element, scale, bias, the geometry, the
    pitches and the set of texture formats are in order (include/hap_gpu.h: HapGpuCompressPlanes,
    HapGpuEncodeFramesPlanes).  Touches no device. */
@@ -138,30 +141,18 @@ int hapb_planes_encode_valid(unsigned width, unsigned height, unsigned long row_
                              unsigned count, const unsigned *formats);
 /* 1: region is a block-aligned, non-empty rectangle inside region->width x height */
 int hapb_region_fits(const HapGpuRegion *region, unsigned height);
-/* pictures -> frames.  picture_kind RGBA8: the DXT / RGTC1 formats (BC7 with HAPGPU_ENCODE_BPTC_BLOCKS); RGBA16F (rows
-   and device addresses 16-byte aligned): one BC6H texture; A8 (rows and device addresses 4-byte aligned): one RGTC1
-   texture.  HAPGPU_ENCODE_REFINE_ENDPOINTS in flags: hapb_encode hands it to the block kernels of one-texture frames
-   and does not fuse a DXT5 texture.  defer: HapbEncodeArgs.defer of the call's hapb_encode */
-unsigned hapb_encode_pictures(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
-                              unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
-                              const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
-                              void *const *outputs, const unsigned long *output_bytes,
-                              unsigned long *output_used, unsigned *results, unsigned flags, unsigned picture_kind,
-                              int defer);
-/* ... with RGBA8 pictures, and results before it returns */
-unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
-                          unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
-                          const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
-                          void *const *outputs, const unsigned long *output_bytes,
-                          unsigned long *output_used, unsigned *results, unsigned flags);
-/* planar tensors in device memory -> frames: hapb_encode_pictures with the block encode of hapgpu_k_block_encode_planes.
-   count 1: DXT1, DXT5, YCoCg-DXT5 or RGTC1; count 2: YCoCg-DXT5 then RGTC1.  A NULL, host or misaligned tensor makes its
-   frame Bad_Arguments. */
-unsigned hapb_encode_planes(HapGpuContext *ctx, unsigned frame_count, const void *const *tensors, unsigned width,
-                            unsigned height, unsigned long row_bytes, const HapbPlanes *planes, unsigned count,
-                            const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
-                            void *const *outputs, const unsigned long *output_bytes, unsigned long *output_used,
-                            unsigned *results, unsigned flags, int defer);
+/* pictures or planar tensors -> frames, HAP_SLICE_ENTRIES frames at a time: every slice reports for itself and the first
+   slice's error is returned.  Pictures of kind RGBA8: the DXT / RGTC1 formats (BC7 with HAPGPU_ENCODE_BPTC_BLOCKS);
+   RGBA16F (rows and device addresses 16-byte aligned): one BC6H texture; A8 (rows and device addresses 4-byte aligned):
+   one RGTC1 texture.  Tensors (hapb_planes_encode_valid): count 1: DXT1, DXT5, YCoCg-DXT5 or RGTC1; count 2: YCoCg-DXT5
+   then RGTC1; a NULL, host or misaligned tensor makes its frame Bad_Arguments.  HAPGPU_ENCODE_REFINE_ENDPOINTS in flags:
+   hapb_encode hands it to the block kernels of one-texture frames and does not fuse a DXT5 texture.  defer:
+   HapbEncodeArgs.defer of the call's hapb_encode; such a call takes one slice at most */
+unsigned hapb_source_frames(HapGpuContext *ctx, const HapbSource *source, unsigned frame_count,
+                            const void *const *pictures, unsigned count, const unsigned *formats,
+                            const unsigned *compressors, const unsigned *chunk_counts, void *const *outputs,
+                            const unsigned long *output_bytes, unsigned long *output_used, unsigned *results,
+                            unsigned flags, int defer);
 /* What one hapb_decode call is told beyond its frames.  NULL stands for all zero: texture `index` of every entry, whole
    textures, nobody to ask which chunks are wanted. */
 typedef struct HapbDecodeArgs {

@@ -315,8 +315,8 @@ unsigned int HapGpuDecodeSequence(HapGpuContext *ctx, HapSequenceReader *r, unsi
         batch = 16;
     if (batch > count)
         batch = count;
-    if (batch > 32768u)
-        batch = 32768u;                                 /* (one launch sequence: grid dimensions hold at most 65535) */
+    if (batch > HAP_SLICE_ENTRIES)
+        batch = HAP_SLICE_ENTRIES;                      /* (one launch sequence: grid dimensions hold at most 65535) */
     batches = (count + batch - 1u) / batch;
     for (b = 0; b < batches; b++) {
         const unsigned f0 = first + b * batch, n = (count - b * batch) < batch ? (count - b * batch) : batch;
@@ -438,6 +438,7 @@ unsigned int HapGpuEncodeSequence(HapGpuContext *ctx, HapSequenceWriter *w, unsi
                                   unsigned int flags, unsigned int batch, unsigned long *frame_bytes,
                                   unsigned int *results)
 {
+    const HapbSource source = {.picture_kind = HAPGPU_PICTURE_RGBA8, .width = width, .height = height, .row_bytes = row_bytes};
     unsigned first_error = HapResult_No_Error, done = 0, b, batches, i;
     unsigned long lengths[2] = {0, 0}, cap;
     size_t stride;
@@ -462,8 +463,8 @@ unsigned int HapGpuEncodeSequence(HapGpuContext *ctx, HapSequenceWriter *w, unsi
         batch = 16;
     if (batch > count)
         batch = count;
-    if (batch > 32768u)
-        batch = 32768u;                                 /* (one launch sequence: grid dimensions hold at most 65535) */
+    if (batch > HAP_SLICE_ENTRIES)
+        batch = HAP_SLICE_ENTRIES;                      /* (one launch sequence: grid dimensions hold at most 65535) */
     batches = (count + batch - 1u) / batch;
     stride = ((size_t)cap + 255u) & ~(size_t)255u;
     outs = (void **)malloc(sizeof(void *) * batch);
@@ -499,8 +500,8 @@ unsigned int HapGpuEncodeSequence(HapGpuContext *ctx, HapSequenceWriter *w, unsi
             caps[i] = cap;
         }
         /* (the helper may still be writing batch b - 1 from the OTHER buffer: the GPU fills this one meanwhile) */
-        rc = hapb_encode_rgba(ctx, n, rgba_frames + done, width, height, row_bytes, texture_count, formats, compressors,
-                              chunk_counts, outs, caps, used[b & 1u], res[b & 1u], flags);
+        rc = hapb_source_frames(ctx, &source, n, rgba_frames + done, texture_count, formats, compressors, chunk_counts, outs,
+                                caps, used[b & 1u], res[b & 1u], flags, 0);
         if (thread_live) {
             pthread_join(thread, NULL);
             thread_live = 0;

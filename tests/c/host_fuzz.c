@@ -20,15 +20,14 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
     (void)output_used; (void)output_formats; (void)results; (void)flags; (void)args;
     abort();
 }
-unsigned hapb_encode_rgba(HapGpuContext *ctx, unsigned frame_count, const void *const *rgba_frames,
-                          unsigned width, unsigned height, unsigned long row_bytes, unsigned count,
-                          const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
-                          void *const *outputs, const unsigned long *output_bytes,
-                          unsigned long *output_used, unsigned *results, unsigned flags)
+unsigned hapb_source_frames(HapGpuContext *ctx, const HapbSource *source, unsigned frame_count,
+                            const void *const *pictures, unsigned count, const unsigned *formats,
+                            const unsigned *compressors, const unsigned *chunk_counts, void *const *outputs,
+                            const unsigned long *output_bytes, unsigned long *output_used, unsigned *results,
+                            unsigned flags, int defer)
 {
-    (void)ctx; (void)frame_count; (void)rgba_frames; (void)width; (void)height; (void)row_bytes; (void)count;
-    (void)formats; (void)compressors; (void)chunk_counts; (void)outputs; (void)output_bytes; (void)output_used;
-    (void)results; (void)flags;
+    (void)ctx; (void)source; (void)frame_count; (void)pictures; (void)count; (void)formats; (void)compressors;
+    (void)chunk_counts; (void)outputs; (void)output_bytes; (void)output_used; (void)results; (void)flags; (void)defer;
     abort();
 }
 unsigned long HapMaxEncodedLength(unsigned int count, unsigned long *lengths, unsigned int *formats, unsigned int *chunks)
