@@ -15,6 +15,7 @@ _API_NAMES = (
     "DECODE_IGNORE_FRAGMENT_INDEX", "DECODE_IGNORE_HALF_TILES", "DECODE_NO_BLOCK_SCAN", "KERNEL_CLASSES", "HapGpuGetFrameTextureChunkLayout", "HapGpuJoinChunkGroups", "SequenceWriter", "SequenceReader", "BufferList",
     "encode_frames_rgba_on_devices", "decode_frames_on_devices", "ENCODE_FINE_CHUNKS", "fine_chunk_count", "DECODE_NO_FIELD_GUESS", "DECODE_GUESS_FIELDS",
     "DECODE_BPTC_PICTURES", "ENCODE_BPTC_BLOCKS", "ENCODE_REFINE_ENDPOINTS", "region_needs_bytes", "PictureError", "COMPOSITE_MAX_LAYERS",
+    "YCBCR_BT601", "YCBCR_BT709", "YCBCR_LIMITED", "YCBCR_FULL",
 )
 
 

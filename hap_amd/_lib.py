@@ -87,6 +87,11 @@ def _load():
                                          P(vp), P(ul), P(ul), P(u), u]),
         "HapGpuEncodeFramesPlanesBegin": (u, [vp, u, P(vp), u, u, ul, ul, P(C.c_float), P(C.c_float), u, u, u, P(u), P(u),
                                               P(u), P(vp), P(ul), P(ul), P(u), u]),
+        "HapGpuCompressNV12": (u, [vp, vp, ul, vp, ul, u, u, u, u, u, vp, ul, P(ul)]),
+        "HapGpuEncodeFramesNV12": (u, [vp, u, P(vp), ul, P(vp), ul, u, u, u, u, u, P(u), P(u), P(u), P(vp), P(ul), P(ul),
+                                       P(u), u]),
+        "HapGpuEncodeFramesNV12Begin": (u, [vp, u, P(vp), ul, P(vp), ul, u, u, u, u, u, P(u), P(u), P(u), P(vp), P(ul),
+                                            P(ul), P(u), u]),
         "HapGpuDecodeFramesPlanes": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, u, u, ul, ul, P(C.c_float), P(C.c_float), P(u), u]),
         "HapGpuDecodeFramesRGBARegion": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, u, u, u, ul, P(u), u]),
         "HapGpuDecodeFramesPlanesRegion": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, P(u), P(u), u, u, u, u, u, ul, ul,

@@ -96,6 +96,59 @@ def _plane_constants(scale, bias, channels, default_scale=1.0 / 255.0):
             (C.c_float * channels)(*[float(np.float32(v)) for v in bias]))
 
 
+YCBCR_BT601, YCBCR_BT709 = 0, 1    # HapGpuYCbCrMatrix
+YCBCR_LIMITED, YCBCR_FULL = 0, 1   # HapGpuYCbCrRange
+
+
+def _video_planes(planes, single, rows, row_len, row_bytes, what):
+    """The Y or CbCr planes of a video call: ([addresses], rowBytes, keepalive).  `planes`: one plane (single), or one
+    batch tensor or a list of planes; a plane is a torch uint8 tensor on the device of (rows, row_len) bytes -- CbCr
+    planes also as (rows, row_len / 2, 2) pairs -- with stride(-1) 1, whose pitch is read from it, or an integer address
+    (then row_bytes says the pitch), or None (no plane for that frame)."""
+    if single:
+        planes = [planes]
+    elif hasattr(planes, "dim"):
+        planes = [planes[i] for i in range(planes.shape[0])]
+    else:
+        planes = list(planes)
+    addresses, pitch = [], row_bytes
+    for t in planes:
+        if t is None or isinstance(t, int):
+            addresses.append(t)
+            continue
+        if not (hasattr(t, "dim") and hasattr(t, "stride") and hasattr(t, "data_ptr")):
+            raise ValueError("%s: torch tensors or addresses" % what)
+        if str(t.dtype) != "torch.uint8":
+            raise ValueError("%s: dtype uint8, not %s" % (what, t.dtype))
+        if t.dim() == 3 and t.shape[2] == 2:
+            shape, unit = (t.shape[0], 2 * t.shape[1]), t.stride(1) == 2 and t.stride(2) == 1
+        else:
+            shape, unit = tuple(t.shape), t.dim() == 2 and t.stride(1) == 1
+        if shape != (rows, row_len):
+            raise ValueError("%s: (%d, %d) bytes per frame, not %s" % (what, rows, row_len, tuple(t.shape)))
+        if not unit:
+            raise ValueError("%s: stride(-1) must be 1" % what)
+        if t.device.type != "cuda":
+            raise ValueError("%s: planes in device memory" % what)
+        if pitch is not None and t.stride(0) != pitch:
+            raise ValueError("%s: the planes of a call share their pitch" % what)
+        pitch = t.stride(0)
+        addresses.append(t.data_ptr())
+    if pitch is None:
+        raise ValueError("%s: addresses need row_bytes" % what)
+    return addresses, pitch, planes
+
+
+def _video_frames(luma_planes, chroma_planes, width, height, luma_row_bytes, chroma_row_bytes, outputs):
+    """The planes of a video frames call: _video_planes of both, ([Y addresses], lumaRowBytes, keepalive, [CbCr addresses],
+    chromaRowBytes, keepalive), one pair per output"""
+    y = _video_planes(luma_planes, False, height, width, luma_row_bytes, "luma_planes")
+    c = _video_planes(chroma_planes, False, height // 2, width, chroma_row_bytes, "chroma_planes")
+    if len(c[0]) != len(y[0]) or outputs != len(y[0]):
+        raise ValueError("one chroma plane and one output per luma plane")
+    return y + c
+
+
 class PictureError:
     """A HapGpuPictureError: sse and sad per channel (R, G, B, A) as tuples of ints, and texels (0: not measured)"""
     __slots__ = ("sse", "sad", "texels")
@@ -715,6 +768,67 @@ class Context:
         described = _plane_tensors(planes, False, width, height, 0)
         r, used, results, keep = self._encode_planes(lib.HapGpuEncodeFramesPlanesBegin, described, width, height, formats,
                                                      compressors, chunk_counts, outputs, scale, bias, flags)
+        self._pending = (used, results) + keep                                      # alive until the second half
+        return r
+
+    def compress_nv12(self, luma, chroma, width, height, texture_format, matrix=YCBCR_BT709, range=YCBCR_LIMITED,
+                      luma_row_bytes=None, chroma_row_bytes=None, output=None):
+        """One NV12 video picture on the device -> one block texture (HapGpuCompressNV12).  `luma`: a (height, width)
+        torch uint8 tensor, `chroma`: a (height / 2, width) one or (height / 2, width / 2, 2) Cb, Cr pairs; stride(-1)
+        must be 1 and the pitches are read from the tensors (a slice with longer rows is accepted), or integer addresses
+        with luma_row_bytes / chroma_row_bytes.  Texel (x, y) is the integer conversion of Y[y][x] and the pair at
+        [y >> 1][x >> 1] under matrix (YCBCR_BT601, YCBCR_BT709) and range (YCBCR_LIMITED, YCBCR_FULL), A 255; the
+        texture is compress_rgba's of that picture.  texture_format RGB_DXT1 or YCoCg_DXT5.  Returns
+        (result, bytes | None), or (result, bytes used) into `output`."""
+        ya, luma_row_bytes, _k1 = _video_planes(luma, True, height, width, luma_row_bytes, "luma")
+        ca, chroma_row_bytes, _k2 = _video_planes(chroma, True, height // 2, width, chroma_row_bytes, "chroma")
+        need = (width // 4) * (height // 4) * (8 if texture_format == HapTextureFormat.RGB_DXT1 else 16)
+        own = output is None
+        if own:
+            output = (C.c_ubyte * max(1, need))()
+        oa, on, _k = _addr_len(output)
+        used = C.c_ulong(0)
+        r = lib.HapGpuCompressNV12(self.handle, ya[0], luma_row_bytes, ca[0], chroma_row_bytes, matrix, range, width,
+                                   height, texture_format, oa, on, C.byref(used))
+        if own:
+            return r, (C.string_at(output, used.value) if r == 0 else None)
+        return r, used.value
+
+    def _encode_nv12(self, fn, described, width, height, formats, compressors, chunk_counts, outputs, matrix, range, flags):
+        ya, luma_row_bytes, keep_y, ca, chroma_row_bytes, keep_c = described
+        nf, count = len(ya), len(formats)
+        yptrs, cptrs = (C.c_void_p * nf)(*ya), (C.c_void_p * nf)(*ca)
+        optrs, oinfos = self._ptr_array(outputs)
+        olens = (C.c_ulong * nf)(*[i[1] for i in oinfos])
+        used = (C.c_ulong * nf)()
+        results = (C.c_uint * nf)()
+        r = fn(self.handle, nf, yptrs, luma_row_bytes, cptrs, chroma_row_bytes, matrix, range, width, height, count,
+               (C.c_uint * count)(*formats), (C.c_uint * count)(*compressors), (C.c_uint * count)(*chunk_counts),
+               optrs, olens, used, results, flags)
+        return r, used, results, (yptrs, cptrs, optrs, olens, keep_y, keep_c, outputs)
+
+    def encode_frames_nv12(self, luma_planes, chroma_planes, width, height, formats, compressors, chunk_counts, outputs,
+                           matrix=YCBCR_BT709, range=YCBCR_LIMITED, luma_row_bytes=None, chroma_row_bytes=None, flags=0):
+        """NV12 video pictures on the device -> frames in one call, without RGBA8 pictures in between
+        (HapGpuEncodeFramesNV12).  luma_planes / chroma_planes: one (N, height, width) / (N, height / 2, width) torch
+        uint8 tensor each, or lists of N planes as compress_nv12 takes them that share their pitch (None: no plane for
+        that frame; integer addresses with luma_row_bytes / chroma_row_bytes).  The frames are encode_frames_rgba's of
+        the converted pictures.  formats: [RGB_DXT1] or [YCoCg_DXT5].  flags: encode_frames_rgba's,
+        ENCODE_REFINE_ENDPOINTS included (ENCODE_BPTC_BLOCKS is ignored).  Returns (result, used[], results[])."""
+        described = _video_frames(luma_planes, chroma_planes, width, height, luma_row_bytes, chroma_row_bytes,
+                                  len(outputs))                                     # (refusals first: no context needed)
+        r, used, results, _keep = self._encode_nv12(lib.HapGpuEncodeFramesNV12, described, width, height, formats,
+                                                    compressors, chunk_counts, outputs, matrix, range, flags)
+        return r, list(used), list(results)
+
+    def encode_frames_nv12_begin(self, luma_planes, chroma_planes, width, height, formats, compressors, chunk_counts,
+                                 outputs, matrix=YCBCR_BT709, range=YCBCR_LIMITED, luma_row_bytes=None,
+                                 chroma_row_bytes=None, flags=0):
+        """First half of encode_frames_nv12 (HapGpuEncodeFramesNV12Begin); encode_finish() is the second."""
+        described = _video_frames(luma_planes, chroma_planes, width, height, luma_row_bytes, chroma_row_bytes,
+                                  len(outputs))
+        r, used, results, keep = self._encode_nv12(lib.HapGpuEncodeFramesNV12Begin, described, width, height, formats,
+                                                   compressors, chunk_counts, outputs, matrix, range, flags)
         self._pending = (used, results) + keep                                      # alive until the second half
         return r
 

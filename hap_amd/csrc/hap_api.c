@@ -838,6 +838,77 @@ unsigned int HapGpuEncodeFramesPlanesBegin(HapGpuContext *context, unsigned int 
                               outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, 1);
 }
 
+/* NV12 video pictures -> textures and frames: the RGBA calls with the block encode of bc_encode_video.hip */
+unsigned int HapGpuCompressNV12(HapGpuContext *context, const void *luma, unsigned long lumaRowBytes,
+                                const void *chroma, unsigned long chromaRowBytes, unsigned int matrix,
+                                unsigned int range, unsigned int width, unsigned int height,
+                                unsigned int textureFormat, void *output, unsigned long outputBytes,
+                                unsigned long *outputBytesUsed)
+{
+    const HapbVideo video = {&chroma, chromaRowBytes, matrix, range};
+    const HapbSource source = {.picture_kind = HAPGPU_PICTURE_RGBA8, .video = &video, .width = width, .height = height,
+                               .row_bytes = lumaRowBytes};
+    if (!luma || !chroma || !output || !hapb_video_encode_valid(width, height, lumaRowBytes, &video, 1u, &textureFormat))
+        return HapResult_Bad_Arguments;
+    return texture_from_source(context, &source, luma, textureFormat, output, outputBytes, outputBytesUsed, 0u);
+}
+
+/* what does not depend on a frame or on the context, checked before either is looked at: 0 = in order; else every
+   results[f] is Bad_Arguments */
+static unsigned video_encode_refused(unsigned frameCount, const void *const *lumaPlanes, const HapbVideo *video,
+                                     unsigned long lumaRowBytes, unsigned width, unsigned height, unsigned count,
+                                     const unsigned *textureFormats, const unsigned *compressors,
+                                     const unsigned *chunkCounts, void *const *outputBuffers,
+                                     const unsigned long *outputBuffersBytes, unsigned long *outputBuffersBytesUsed,
+                                     unsigned *results)
+{
+    if (results && lumaPlanes && video->chroma && compressors && chunkCounts && outputBuffers && outputBuffersBytes &&
+        outputBuffersBytesUsed && hapb_video_encode_valid(width, height, lumaRowBytes, video, count, textureFormats))
+        return 0u;
+    refuse_call(results, frameCount);
+    return 1u;
+}
+
+unsigned int HapGpuEncodeFramesNV12(HapGpuContext *context, unsigned int frameCount,
+                                    const void *const *lumaPlanes, unsigned long lumaRowBytes,
+                                    const void *const *chromaPlanes, unsigned long chromaRowBytes,
+                                    unsigned int matrix, unsigned int range, unsigned int width, unsigned int height,
+                                    unsigned int count, const unsigned int *textureFormats,
+                                    const unsigned int *compressors, const unsigned int *chunkCounts,
+                                    void *const *outputBuffers, const unsigned long *outputBuffersBytes,
+                                    unsigned long *outputBuffersBytesUsed, unsigned int *results, unsigned int flags)
+{
+    const HapbVideo video = {chromaPlanes, chromaRowBytes, matrix, range};
+    const HapbSource source = {.picture_kind = HAPGPU_PICTURE_RGBA8, .video = &video, .width = width, .height = height,
+                               .row_bytes = lumaRowBytes};
+    if (video_encode_refused(frameCount, lumaPlanes, &video, lumaRowBytes, width, height, count, textureFormats, compressors,
+                             chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results))
+        return HapResult_Bad_Arguments;
+    return frames_from_source(context, &source, frameCount, lumaPlanes, count, textureFormats, compressors, chunkCounts,
+                              outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, 0);
+}
+
+unsigned int HapGpuEncodeFramesNV12Begin(HapGpuContext *context, unsigned int frameCount,
+                                         const void *const *lumaPlanes, unsigned long lumaRowBytes,
+                                         const void *const *chromaPlanes, unsigned long chromaRowBytes,
+                                         unsigned int matrix, unsigned int range, unsigned int width,
+                                         unsigned int height, unsigned int count, const unsigned int *textureFormats,
+                                         const unsigned int *compressors, const unsigned int *chunkCounts,
+                                         void *const *outputBuffers, const unsigned long *outputBuffersBytes,
+                                         unsigned long *outputBuffersBytesUsed, unsigned int *results,
+                                         unsigned int flags)
+{
+    const HapbVideo video = {chromaPlanes, chromaRowBytes, matrix, range};
+    const HapbSource source = {.picture_kind = HAPGPU_PICTURE_RGBA8, .video = &video, .width = width, .height = height,
+                               .row_bytes = lumaRowBytes};
+    if (frameCount > HAP_SLICE_ENTRIES ||
+        video_encode_refused(frameCount, lumaPlanes, &video, lumaRowBytes, width, height, count, textureFormats, compressors,
+                             chunkCounts, outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results))
+        return HapResult_Bad_Arguments;
+    return frames_from_source(context, &source, frameCount, lumaPlanes, count, textureFormats, compressors, chunkCounts,
+                              outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, results, flags, 1);
+}
+
 /* RGBA16F pictures -> Hap HDR: the RGBA calls with 8-byte texels and one BC6H texture per frame */
 unsigned int HapGpuCompressRGBAHalf(HapGpuContext *context, const void *rgbaHalf, unsigned int width,
                                     unsigned int height, unsigned long rowBytes, unsigned int textureFormat,

@@ -72,6 +72,13 @@ unsigned encode_textures_valid(unsigned count, const unsigned long *input_bytes,
     return HapResult_No_Error;
 }
 
+/* the columns of a block-encode job's address table, frame_count entries each: the sources and an output per texture;
+   video pictures: Y planes, outputs, CbCr planes */
+static unsigned job_table_columns(const HapbBlockEncodeJob *job)
+{
+    return job->source.video ? 3u : 1u + job->count;
+}
+
 unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                      const void *const *inputs, const unsigned long *input_bytes,
                      const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
@@ -220,7 +227,7 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
            others (snappy_compress_blocks.hip).  One texture per frame. */
         {
             if (job && !ctx->no_fusion && count == 1u && job->source.picture_kind == HAPGPU_PICTURE_RGBA8 && !job->source.planes &&
-                (job->source.row_bytes & 3u) == 0 && (unsigned long long)job->source.row_bytes * job->source.height < 0xFFFFFFFFull &&
+                !job->source.video && (job->source.row_bytes & 3u) == 0 && (unsigned long long)job->source.row_bytes * job->source.height < 0xFFFFFFFFull &&
                 job->source.width / 4u >= 1u) {
                 /* (code: HapGpuTexEnc.reserved bits 24..26; mask bit: which kernel the launcher starts) */
                 if (t->field_period == 4u && t->format == HapTextureFormat_YCoCg_DXT5) {
@@ -477,6 +484,10 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                             HAPB_MIX(bits[0]); HAPB_MIX(bits[1]);
                         }
                     }
+                    if (src->video) {
+                        /* (the pitch, the matrix and the range are kernel arguments too) */
+                        HAPB_MIX(16u); HAPB_MIX(src->video->chroma_row_bytes); HAPB_MIX(src->video->matrix); HAPB_MIX(src->video->range);
+                    }
                 }
                 graph = hapgpu_rt_graph_begin(rt, key);
             }
@@ -487,7 +498,7 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                 if (job) {
                     const HapbSource *const src = &job->source;
                     launch_rc |= (unsigned)hapgpu_rt_h2d(rt, job->device_table, job->host_table,
-                                                         sizeof(uint64_t) * (size_t)(1u + job->count) * job->frame_count);
+                                                         sizeof(uint64_t) * (size_t)job_table_columns(job) * job->frame_count);
                     /* Hap Q Alpha: both textures from one pass over the RGBA (64 + 16 + 8 bytes per block);
                        else one launch per texture that the second stage does not make itself.  (A batch takes at most
                        65535 block rows.) */
@@ -496,9 +507,15 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                     for (i = 0; i < (pair ? 1u : job->count); i++)
                         if (pair || !fused[i]) {
                             const uint64_t *dt = job->device_table;
+                            /* (video pictures: one texture a frame, and the third column holds their CbCr planes) */
                             const HapGpuPictureTable t = {{dt, dt + (size_t)(1u + i) * job->frame_count,
-                                                           pair ? dt + 2u * (size_t)job->frame_count : NULL}, {0u, 0u, 0u}};
+                                                           pair || src->video ? dt + 2u * (size_t)job->frame_count : NULL}, {0u, 0u, 0u}};
                             launch_rc |= src->height / 4u > 65535u ? 1u :
+                                         src->video ?
+                                         (unsigned)hapgpu_k_block_encode_video(rt, &t, job->frame_count, src->width, src->height,
+                                                                               job->formats[i], refine, src->row_bytes,
+                                                                               src->video->chroma_row_bytes, src->video->matrix,
+                                                                               src->video->range) :
                                          src->planes ?
                                          (unsigned)hapgpu_k_block_encode_planes(rt, &t, job->frame_count, src->width, src->height,
                                                                                 job->formats[i], (unsigned)pair | refine, src->planes->channels,
@@ -591,6 +608,12 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                     pd->planes.scale = pd->planes.bias = NULL;
                     pd->job.source.planes = &pd->planes;
                 }
+                if (job->source.video) {
+                    /* (... nor need its array of CbCr planes: their addresses are in the job's table) */
+                    pd->video = *job->source.video;
+                    pd->video.chroma = NULL;
+                    pd->job.source.video = &pd->video;
+                }
             }
             free(stage_off_in);
             if (a->defer) {
@@ -667,7 +690,7 @@ unsigned hapb_encode_complete(HapGpuContext *ctx, HapbEncodePending *pd)
             unsigned long *rcap = (unsigned long *)malloc(sizeof(unsigned long) * again * 2u);
             unsigned *rres = (unsigned *)malloc(sizeof(unsigned) * again * 2u);
             if (pd->has_job)
-                rtable = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(1u + pd->job.count) * again);
+                rtable = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)job_table_columns(&pd->job) * again);
             if (rin && rout && rcap && rres && (!pd->has_job || rtable)) {
                 unsigned long *rused = rcap + again;
                 unsigned *rmap = rres + again, m = 0;
@@ -682,7 +705,7 @@ unsigned hapb_encode_complete(HapGpuContext *ctx, HapbEncodePending *pd)
                         if (pd->has_job) {
                             /* the pictures and texture places of these frames, as a table of its own */
                             unsigned t;
-                            for (t = 0; t < 1u + pd->job.count; t++)
+                            for (t = 0; t < job_table_columns(&pd->job); t++)
                                 rtable[(size_t)t * again + m] = pd->job.host_table[(size_t)t * pd->job.frame_count + f];
                         }
                         rmap[m++] = f;
@@ -691,11 +714,11 @@ unsigned hapb_encode_complete(HapGpuContext *ctx, HapbEncodePending *pd)
                     /* the table goes where the first pass's was: pinned memory at an address that stays -- a recorded
                        launch sequence (HAP_AMD_GRAPHS) copies from THAT address again when it is replayed (found by
                        tools/stress.py: a table in malloc'd memory was gone by then) */
-                    uint64_t *pinned = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, sizeof(uint64_t) * (size_t)(1u + pd->job.count) * again);
+                    uint64_t *pinned = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, sizeof(uint64_t) * (size_t)job_table_columns(&pd->job) * again);
                     rjob = pd->job;
                     rjob.frame_count = again;
                     if (pinned) {
-                        memcpy(pinned, rtable, sizeof(uint64_t) * (size_t)(1u + pd->job.count) * again);
+                        memcpy(pinned, rtable, sizeof(uint64_t) * (size_t)job_table_columns(&pd->job) * again);
                         rjob.host_table = pinned;
                     } else {
                         rjob.host_table = rtable;
@@ -784,16 +807,33 @@ int hapb_planes_encode_valid(unsigned width, unsigned height, unsigned long row_
     return count == 1u && kind_makes_format(HAPGPU_PICTURE_RGBA8, formats[0], 0);
 }
 
-/* the size of a source's texel: of a tensor, one element of one plane */
+int hapb_video_encode_valid(unsigned width, unsigned height, unsigned long row_bytes, const HapbVideo *video,
+                            unsigned count, const unsigned *formats)
+{
+    if (video->matrix > HapGpuYCbCrMatrix_BT709 || video->range > HapGpuYCbCrRange_Full || width == 0 || height == 0 ||
+        (width & 3u) || (height & 3u) || height / 4u > 65535u || !formats)
+        return 0;
+    /* a lane loads a dword per row of either plane; width / 2 pairs are width bytes */
+    if (row_bytes < width || (row_bytes & 3u) || video->chroma_row_bytes < width || (video->chroma_row_bytes & 3u))
+        return 0;
+    /* opaque pictures: Hap and Hap Q */
+    return count == 1u && (formats[0] == HapTextureFormat_RGB_DXT1 || formats[0] == HapTextureFormat_YCoCg_DXT5);
+}
+
+/* the size of a source's texel: of a tensor, one element of one plane; of a video picture, one Y sample */
 static size_t source_texel_bytes(const HapbSource *source)
 {
+    if (source->video)
+        return 1u;
     return source->planes ? plane_element_bytes(source->planes->element) : HAPGPU_PICTURE_TEXEL_BYTES(source->picture_kind);
 }
 
 /* what the kernels ask of a source's address (in device memory) and row pitch when they read it: tensors four
-   elements, RGBA16F pictures 16 bytes, else 4 */
+   elements, RGBA16F pictures 16 bytes, else 4 (video pictures: of both planes) */
 static unsigned source_align_mask(const HapbSource *source)
 {
+    if (source->video)
+        return 3u;
     if (source->planes)
         return 4u * (unsigned)plane_element_bytes(source->planes->element) - 1u;
     return source->picture_kind == HAPGPU_PICTURE_RGBA16F ? 15u : 3u;
@@ -812,11 +852,13 @@ unsigned hapb_source_texture(HapGpuContext *ctx, const HapbSource *source, const
                              void *output, unsigned long output_bytes, unsigned long *used, unsigned flags)
 {
     const HapbPlanes *const planes = source->planes;
+    const HapbVideo *const video = source->video;
+    const void *const chroma = video && video->chroma ? video->chroma[0] : NULL;
     const unsigned kind = source->picture_kind, width = source->width, height = source->height;
     const unsigned long row_bytes = source->row_bytes;
     /* BC7 only when asked (HAPGPU_ENCODE_BPTC_BLOCKS); BC6H only from half pictures, and nothing else from those; A8
        pictures make RGTC1 */
-    const int bptc = !planes && (flags & HAPGPU_ENCODE_BPTC_BLOCKS) && format == HapTextureFormat_RGBA_BPTC_UNORM;
+    const int bptc = !planes && !video && (flags & HAPGPU_ENCODE_BPTC_BLOCKS) && format == HapTextureFormat_RGBA_BPTC_UNORM;
     const int grid_rows = bptc || kind != HAPGPU_PICTURE_RGBA8;    /* a block row per grid row */
     const size_t texel = source_texel_bytes(source), block = hapf_block_bytes(format);
     const unsigned align = source_align_mask(source);
@@ -828,18 +870,20 @@ unsigned hapb_source_texture(HapGpuContext *ctx, const HapbSource *source, const
     int rc;
     if (context_busy(ctx, NULL, 0))
         return HapResult_Internal_Error;
-    if (!picture || !output ||
-        (planes ? !hapb_planes_encode_valid(width, height, row_bytes, planes, 1u, &format)
+    if (!picture || !output || (video && !chroma) ||
+        (video  ? !hapb_video_encode_valid(width, height, row_bytes, video, 1u, &format) :
+         planes ? !hapb_planes_encode_valid(width, height, row_bytes, planes, 1u, &format)
                 : width == 0 || height == 0 || (width & 3u) || (height & 3u) || row_bytes < (unsigned long)width * texel ||
                   !kind_makes_format(kind, format, bptc)))
         return HapResult_Bad_Arguments;
     need = (size_t)(width / 4u) * (height / 4u) * block;
     if (output_bytes < need)
         return HapResult_Buffer_Too_Small;
-    /* tensors in device memory, aligned to what a lane loads; device pictures 4-byte aligned with rows a multiple of 4
-       (half pictures: 16 and 16), at most 65535 block rows for BC7, BC6H and A8 pictures, 2^32 * 255/256 blocks for the
-       others; device outputs aligned to their blocks */
-    if ((planes ? !is_dev(ctx, picture) || ((uintptr_t)picture & align)
+    /* tensors and both planes of a video picture in device memory, aligned to what a lane loads; device pictures 4-byte
+       aligned with rows a multiple of 4 (half pictures: 16 and 16), at most 65535 block rows for BC7, BC6H and A8
+       pictures, 2^32 * 255/256 blocks for the others; device outputs aligned to their blocks */
+    if ((video  ? !is_dev(ctx, picture) || !is_dev(ctx, chroma) || (((uintptr_t)picture | (uintptr_t)chroma) & align) :
+         planes ? !is_dev(ctx, picture) || ((uintptr_t)picture & align)
                 : (row_bytes & align) || (is_dev(ctx, picture) && ((uintptr_t)picture & align)) ||
                   (grid_rows ? height / 4u > 65535u : (unsigned long long)(width / 4u) * (height / 4u) > 0xFFFFFFFFull / 256u * 255u)) ||
         (is_dev(ctx, output) && ((uintptr_t)output & (block - 1u))))
@@ -858,7 +902,10 @@ unsigned hapb_source_texture(HapGpuContext *ctx, const HapbSource *source, const
     }
     t.one[0] = (uint64_t)(uintptr_t)src;
     t.one[1] = (uint64_t)(uintptr_t)dst;
-    rc = planes ? hapgpu_k_block_encode_planes(rt, &t, 1u, width, height, format, 0u, planes->channels, planes->element,
+    t.one[2] = (uint64_t)(uintptr_t)chroma;
+    rc = video  ? hapgpu_k_block_encode_video(rt, &t, 1u, width, height, format, 0u, row_bytes, video->chroma_row_bytes,
+                                              video->matrix, video->range) :
+         planes ? hapgpu_k_block_encode_planes(rt, &t, 1u, width, height, format, 0u, planes->channels, planes->element,
                                                planes->plane_bytes, row_bytes, planes->scale, planes->bias)
                 : hapgpu_k_block_encode(rt, &t, 1u, width, height, row_bytes, format,
                                         (flags & HAPGPU_ENCODE_REFINE_ENDPOINTS) ? HAPGPU_BLOCK_ENCODE_REFINE : 0u,
@@ -874,7 +921,8 @@ unsigned hapb_source_texture(HapGpuContext *ctx, const HapbSource *source, const
 }
 
 /* one slice of hapb_source_frames: at most HAP_SLICE_ENTRIES frames, or a call that is refused as a whole.  A planar
-   source has passed hapb_planes_encode_valid */
+   source has passed hapb_planes_encode_valid, a video source hapb_video_encode_valid, and its array of CbCr planes is
+   there */
 static unsigned source_slice(HapGpuContext *ctx, const HapbSource *source, unsigned frame_count,
                              const void *const *pictures, unsigned count, const unsigned *formats,
                              const unsigned *compressors, const unsigned *chunk_counts, void *const *outputs,
@@ -883,6 +931,7 @@ static unsigned source_slice(HapGpuContext *ctx, const HapbSource *source, unsig
 {
     hapgpu_rt *rt = ctx->rt;
     const HapbPlanes *const planes = source->planes;
+    const HapbVideo *const video = source->video;
     const unsigned picture_kind = source->picture_kind, width = source->width, height = source->height;
     const unsigned long row_bytes = source->row_bytes;
     const size_t texel = source_texel_bytes(source);
@@ -903,7 +952,7 @@ static unsigned source_slice(HapGpuContext *ctx, const HapbSource *source, unsig
         return answer_all(results, frame_count, HapResult_Bad_Arguments);
     for (i = 0; i < count; i++) {
         /* (BC7 only when asked, and alone: no Hap variant pairs it with a second texture) */
-        const int bptc = !planes && (flags & HAPGPU_ENCODE_BPTC_BLOCKS) && count == 1u && formats[i] == HapTextureFormat_RGBA_BPTC_UNORM;
+        const int bptc = !planes && !video && (flags & HAPGPU_ENCODE_BPTC_BLOCKS) && count == 1u && formats[i] == HapTextureFormat_RGBA_BPTC_UNORM;
         /* (half pictures make BC6H, alone, and nothing else; RGBA8 pictures never make it; A8 pictures make RGTC1, alone) */
         if ((picture_kind != HAPGPU_PICTURE_RGBA8 && count != 1u) || !kind_makes_format(picture_kind, formats[i], bptc))
             return answer_all(results, frame_count, HapResult_Bad_Arguments);
@@ -914,7 +963,8 @@ static unsigned source_slice(HapGpuContext *ctx, const HapbSource *source, unsig
     rgba_bytes = (size_t)row_bytes * (height - 1u) + (size_t)width * texel;
     textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, per_frame * frame_count);
     tex_ptrs = (const void **)malloc(sizeof(void *) * (size_t)frame_count * count);
-    /* address table of the batched block-encode launches: [sources][outputs of texture 0][of texture 1] */
+    /* address table of the batched block-encode launches: [sources][outputs of texture 0][of texture 1]; video pictures,
+       one texture a frame: [Y planes][outputs][CbCr planes] */
     hsrc = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, sizeof(uint64_t) * 3u * frame_count);
     dsrc = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, sizeof(uint64_t) * 3u * frame_count);
     if (!textures || !tex_ptrs || !hsrc || !dsrc) {
@@ -931,6 +981,13 @@ static unsigned source_slice(HapGpuContext *ctx, const HapbSource *source, unsig
         /* (a tensor in host memory, or one the lanes' loads would be misaligned in: its frame is Bad_Arguments) */
         if (planes && (!is_dev(ctx, src) || ((uintptr_t)src & align)))
             continue;
+        /* (... and so is a video picture either of whose planes is missing, in host memory or misaligned) */
+        if (video) {
+            const void *const chroma = video->chroma[f];
+            if (!chroma || !is_dev(ctx, src) || !is_dev(ctx, chroma) || (((uintptr_t)src | (uintptr_t)chroma) & align))
+                continue;
+            hsrc[2u * (size_t)frame_count + f] = (uint64_t)(uintptr_t)chroma;
+        }
         if (!is_dev(ctx, src)) {
             /* one staging buffer per frame so that uploads and kernels can overlap on the stream */
             if (!rgba_stage) {
@@ -996,6 +1053,12 @@ unsigned hapb_source_frames(HapGpuContext *ctx, const HapbSource *source, unsign
         (!results || !pictures || !compressors || !chunk_counts || !outputs || !output_bytes || !output_used ||
          !hapb_planes_encode_valid(source->width, source->height, source->row_bytes, source->planes, count, formats)))
         return answer_all(results, frame_count, HapResult_Bad_Arguments);
+    /* video pictures: the same */
+    if (source->video &&
+        (!results || !pictures || !source->video->chroma || !compressors || !chunk_counts || !outputs || !output_bytes ||
+         !output_used ||
+         !hapb_video_encode_valid(source->width, source->height, source->row_bytes, source->video, count, formats)))
+        return answer_all(results, frame_count, HapResult_Bad_Arguments);
     /* (the kernels index frames with a grid dimension that holds 65535: larger batches go in slices; a call without the
        arrays the slices would be cut from is refused in one piece) */
     if (frame_count <= HAP_SLICE_ENTRIES || !pictures || !outputs || !output_bytes || !output_used || !results)
@@ -1003,8 +1066,17 @@ unsigned hapb_source_frames(HapGpuContext *ctx, const HapbSource *source, unsign
                             output_bytes, output_used, results, flags, defer);
     for (done = 0; done < frame_count; done += HAP_SLICE_ENTRIES) {
         const unsigned n = frame_count - done < HAP_SLICE_ENTRIES ? frame_count - done : HAP_SLICE_ENTRIES;
-        const unsigned rc = source_slice(ctx, source, n, pictures + done, count, formats, compressors, chunk_counts,
-                                         outputs + done, output_bytes + done, output_used + done, results + done, flags, 0);
+        /* (a slice's CbCr planes are cut from the call's like its pictures) */
+        HapbVideo video;
+        HapbSource cut = *source;
+        unsigned rc;
+        if (source->video) {
+            video = *source->video;
+            video.chroma += done;
+            cut.video = &video;
+        }
+        rc = source_slice(ctx, &cut, n, pictures + done, count, formats, compressors, chunk_counts, outputs + done,
+                          output_bytes + done, output_used + done, results + done, flags, 0);
         if (r == HapResult_No_Error)
             r = rc;
     }

@@ -51,11 +51,22 @@ typedef struct HapbPlanes {
                                        (plane_quantise.hpp) */
 } HapbPlanes;
 
+/* The NV12 pictures of the video roads (include/hap_gpu.h: HapGpuCompressNV12, HapGpuEncodeFramesNV12): what lies beside
+   the Y planes, which are the call's pictures with the call's row_bytes as their pitch. */
+typedef struct HapbVideo {
+    const void *const *chroma;      /* chroma[f]: the plane of interleaved Cb, Cr pairs of pictures[f], f counted from the
+                                       call's first frame (one texture: one entry) */
+    unsigned long chroma_row_bytes; /* the pitch of its rows */
+    unsigned matrix, range;         /* HapGpuYCbCrMatrix, HapGpuYCbCrRange */
+} HapbVideo;
+
 /* What an encode call's textures are made from: the mirror of HapbRoad, filled the same way. */
 typedef struct HapbSource {
     unsigned picture_kind;      /* HAPGPU_PICTURE_*: RGBA8, RGBA16F, A8 */
     const HapbPlanes *planes;   /* NULL: interleaved pictures of picture_kind; else (RGBA8: they make what those make)
                                    planar tensors in device memory: row_bytes is the pitch of a plane's rows */
+    const HapbVideo *video;     /* NULL: as above; else (RGBA8: they make what those make; no planes) NV12 pictures in
+                                   device memory: the pictures are Y planes and row_bytes is the pitch of their rows */
     unsigned width, height;
     unsigned long row_bytes;
 } HapbSource;
@@ -68,7 +79,10 @@ typedef struct HapbBlockEncodeJob {
        hapgpu_k_block_encode_planes' and never part of the block compressor; source.picture_kind and wide mean nothing.
        Only RGBA8 pictures are ever fused into the block compressor.  scale and bias are kept here (source.planes->scale
        and ->bias are the caller's, which need not outlive the first half of a call in two halves: not looked at after
-       hapb_source_frames has returned). */
+       hapb_source_frames has returned).
+       source.video != NULL: the sources are NV12 pictures in device memory, Y planes in the table's first column and
+       CbCr planes in its third: the block encode is hapgpu_k_block_encode_video's, never part of the block compressor
+       either; source.video->chroma is not looked at (the table holds the addresses). */
     HapbSource source;
     int wide;
     float plane_scale[4], plane_bias[4];
@@ -92,6 +106,7 @@ typedef struct HapbEncodePending {
     uint8_t *out_stage;
     HapbBlockEncodeJob job;           /* a call that started from pictures (has_job) */
     HapbPlanes planes;                /* ... from tensors: what job.source.planes points to (the caller's is gone) */
+    HapbVideo video;                  /* ... from video pictures: what job.source.video points to */
 } HapbEncodePending;
 unsigned hapb_encode_complete(HapGpuContext *ctx, HapbEncodePending *pending);
 /* ... or lets go of it without touching the client's arrays (the context is being destroyed): waits for the launches, frees `pending` */
@@ -117,7 +132,8 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
    RGBA8 and the DXT / RGTC1 formats (BC7 with HAPGPU_ENCODE_BPTC_BLOCKS), RGBA16F and a BC6H format, or A8 and A_RGTC1
    (hapb_source_frames' rules); HAPGPU_ENCODE_REFINE_ENDPOINTS in flags goes down to the block kernel, which looks at it
    for DXT1 and DXT5.  A tensor (device memory): DXT1, DXT5, YCoCg-DXT5, or RGTC1 from the fourth plane (255 where there
-   are three); flags are not looked at */
+   are three); flags are not looked at.  A video picture (device memory; `picture` its Y plane, source->video->chroma[0]
+   its CbCr plane): DXT1 or YCoCg-DXT5; flags are not looked at */
 unsigned hapb_source_texture(HapGpuContext *ctx, const HapbSource *source, const void *picture, unsigned format,
                              void *output, unsigned long output_bytes, unsigned long *used, unsigned flags);
 /* The crops of the resized planar roads (include/hap_gpu.h: HapGpuDecompressPlanesResized,
@@ -139,13 +155,19 @@ int hapb_resize_region(const HapbResize *resize, size_t f, unsigned width, unsig
    HapGpuEncodeFramesPlanes).  Touches no device. */
 int hapb_planes_encode_valid(unsigned width, unsigned height, unsigned long row_bytes, const HapbPlanes *planes,
                              unsigned count, const unsigned *formats);
+/* ... and the video encode calls whatever their planes are: 1 = matrix, range, the geometry, both pitches and the set of
+   texture formats are in order (include/hap_gpu.h: HapGpuCompressNV12, HapGpuEncodeFramesNV12).  Touches no device. */
+int hapb_video_encode_valid(unsigned width, unsigned height, unsigned long row_bytes, const HapbVideo *video,
+                            unsigned count, const unsigned *formats);
 /* 1: region is a block-aligned, non-empty rectangle inside region->width x height */
 int hapb_region_fits(const HapGpuRegion *region, unsigned height);
 /* pictures or planar tensors -> frames, HAP_SLICE_ENTRIES frames at a time: every slice reports for itself and the first
    slice's error is returned.  Pictures of kind RGBA8: the DXT / RGTC1 formats (BC7 with HAPGPU_ENCODE_BPTC_BLOCKS);
    RGBA16F (rows and device addresses 16-byte aligned): one BC6H texture; A8 (rows and device addresses 4-byte aligned):
    one RGTC1 texture.  Tensors (hapb_planes_encode_valid): count 1: DXT1, DXT5, YCoCg-DXT5 or RGTC1; count 2: YCoCg-DXT5
-   then RGTC1; a NULL, host or misaligned tensor makes its frame Bad_Arguments.  HAPGPU_ENCODE_REFINE_ENDPOINTS in flags:
+   then RGTC1; a NULL, host or misaligned tensor makes its frame Bad_Arguments.  Video pictures
+   (hapb_video_encode_valid): count 1: DXT1 or YCoCg-DXT5; a NULL, host or misaligned Y or CbCr plane makes its frame
+   Bad_Arguments; HAPGPU_ENCODE_BPTC_BLOCKS is ignored.  HAPGPU_ENCODE_REFINE_ENDPOINTS in flags:
    hapb_encode hands it to the block kernels of one-texture frames and does not fuse a DXT5 texture.  defer:
    HapbEncodeArgs.defer of the call's hapb_encode; such a call takes one slice at most */
 unsigned hapb_source_frames(HapGpuContext *ctx, const HapbSource *source, unsigned frame_count,

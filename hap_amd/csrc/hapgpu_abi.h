@@ -305,7 +305,7 @@ void hapgpu_rt_graphs_disable(hapgpu_rt *rt);
 
 /* [device] Addresses of a block-codec launch: three columns of `pictures` device addresses, each either a DEVICE array
    (column[c]) or, for one picture, the address itself (one[c], read where column[c] is NULL).  Encode: sources, outputs,
-   second outputs (Hap Q Alpha's RGTC1 plane); decode: textures, alpha planes, pictures.  A source or texture address of
+   second outputs (Hap Q Alpha's RGTC1 plane; video pictures: their CbCr planes, a 0 skipping the picture); decode: textures, alpha planes, pictures.  A source or texture address of
    0 skips the picture, and so does an encode output of 0. */
 typedef struct HapGpuPictureTable {
     const uint64_t *column[3];
@@ -462,6 +462,18 @@ int hapgpu_k_block_encode_planes(hapgpu_rt *rt, const HapGpuPictureTable *table,
                                  unsigned height, unsigned hap_texture_format, unsigned flags, unsigned channels,
                                  unsigned element_kind, size_t plane_bytes, size_t row_bytes, const float *scale,
                                  const float *bias);
+/* NV12 video pictures -> blocks of `hap_texture_format`, without an RGBA8 picture in between (bc_encode_video.hip).  The
+   table's columns are [Y planes][outputs][CbCr planes]: a Y plane of width x height bytes, rows luma_row_bytes apart, and
+   a plane of (width / 2) x (height / 2) interleaved Cb, Cr pairs, rows chroma_row_bytes apart; a 0 in any column skips
+   the picture.  Texel (x, y) is ycbcr_rgb.hpp's RGBA of Y[y][x] and the pair at [y >> 1][x >> 1] under `matrix`
+   (HapGpuYCbCrMatrix) and `range` (HapGpuYCbCrRange), A 255; the blocks are byte for byte what hapgpu_k_block_encode
+   makes of the RGBA8 pictures of those texels: RGB_DXT1 or YCoCg_DXT5.  Planes and both pitches 4-byte aligned, both
+   pitches at least width, at most 65535 block rows.  Outputs aligned to their blocks.  flags:
+   HAPGPU_BLOCK_ENCODE_REFINE (RGB_DXT1; ignored for YCoCg_DXT5); HAPGPU_BLOCK_ENCODE_WITH_ALPHA is refused.  Timed as
+   HapGpuKernel_BlockEncode.  Returns 0 launched, 1 bad arguments, 4 launch failure. */
+int hapgpu_k_block_encode_video(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, unsigned width,
+                                unsigned height, unsigned hap_texture_format, unsigned flags, size_t luma_row_bytes,
+                                size_t chroma_row_bytes, unsigned matrix, unsigned range);
 /* [device] Addresses of a transcode launch, as HapGpuPictureTable's: source textures, source alpha planes, destination
    textures, destination alpha planes (Hap Q Alpha's second texture). */
 typedef struct HapGpuTranscodeTable {

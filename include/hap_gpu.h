@@ -1061,6 +1061,107 @@ unsigned int HapGpuEncodeFramesPlanesBegin(HapGpuContext *context, unsigned int 
                                            unsigned int *results,
                                            unsigned int flags);
 
+/* The colour matrix and the range of a video picture's Y, Cb, Cr samples (HapGpuCompressNV12, HapGpuEncodeFramesNV12) */
+enum HapGpuYCbCrMatrix { HapGpuYCbCrMatrix_BT601 = 0, HapGpuYCbCrMatrix_BT709 = 1 };
+enum HapGpuYCbCrRange { HapGpuYCbCrRange_Limited = 0, HapGpuYCbCrRange_Full = 1 };
+
+/* One NV12 video picture in DEVICE memory -> one block-compressed texture: what a hardware video decoder leaves of
+ * H.264, HEVC or ProRes footage, converted to RGB by the block encoder itself as it loads the samples: no RGBA8 picture
+ * is written or read back.  NV12 is a Y plane of width x height bytes (luma, rows lumaRowBytes apart) and a plane of
+ * (width / 2) x (height / 2) interleaved Cb, Cr byte pairs (chroma, rows chromaRowBytes apart).
+ * The definition.  Texel (x, y) takes Y[y][x] and the pair Cb, Cr = UV[y >> 1][2 * (x >> 1)], UV[y >> 1][2 * (x >> 1) + 1]:
+ * chroma is replicated over its 2 x 2 luma samples, with no filtering across samples.  With y' = Y - 16 (Limited) or Y
+ * (Full), u = Cb - 128 and v = Cr - 128, all in 32-bit signed integers with >> arithmetic:
+ *     R = clamp255((cy * y' + crv * v           + 32768) >> 16)
+ *     G = clamp255((cy * y' - cgu * u - cgv * v + 32768) >> 16)
+ *     B = clamp255((cy * y' + cbu * u           + 32768) >> 16)        A = 255
+ * where clamp255 holds its argument to 0 .. 255 and the coefficients are the standards' exact rationals times 65536,
+ * rounded to nearest -- Kr, Kb = 0.299, 0.114 (BT601) or 0.2126, 0.0722 (BT709); Limited scales luma by 255/219 and
+ * chroma by 255/224:
+ *     matrix, range        cy     crv     cbu    cgu    cgv
+ *     BT601  Limited    76309  104597  132201  25675  53279
+ *     BT601  Full       65536   91881  116130  22553  46802
+ *     BT709  Limited    76309  117489  138438  13975  34925
+ *     BT709  Full       65536  103206  121609  12276  30679
+ * The accumulators stay below 3.6e7 in magnitude; before the clamp every channel is within 0.5016 of the exact real
+ * value.  Samples outside the nominal range or the gamut (Y < 16, Y > 235, ...) are simply clamped: defined behaviour,
+ * not an error.  The picture of an NV12 source is the RGBA8 picture of these bytes, and the texture is byte for byte what
+ * HapGpuCompressRGBA makes of that picture: YCoCg_DXT5 goes YCbCr -> RGB bytes -> the YCoCg block code, with no direct
+ * YCbCr -> YCoCg shortcut.
+ * textureFormat: RGB_DXT1 or YCoCg_DXT5.  output is host or device, under HapGpuCompressRGBA's rules (a device output
+ * aligned to its blocks; too small: Buffer_Too_Small).  width and height multiples of 4, at most 65535 block rows.  Both
+ * planes are in device memory; their addresses and both pitches are multiples of 4, what a lane loads per row;
+ * lumaRowBytes >= width and chromaRowBytes >= width (width / 2 pairs).  Only the samples are read, nothing between rows.
+ * Bad_Arguments, and nothing written, for anything else: a NULL, host or misaligned plane, a matrix or range outside the
+ * enums, another format, a bad pitch.
+ * Out of scope: the way back (textures or frames -> NV12); P010 and other 10/16-bit layouts; planar I420, 4:2:2 and
+ * 4:4:4; filtered or sited chroma upsampling, which needs neighbours across blocks; a separate A8 plane, and with it Hap
+ * Alpha, Hap Q Alpha and Hap Alpha-Only destinations; BC7 / BC6H destinations; host pictures. */
+unsigned int HapGpuCompressNV12(HapGpuContext *context,
+                                const void *luma, unsigned long lumaRowBytes,
+                                const void *chroma, unsigned long chromaRowBytes,
+                                unsigned int matrix, unsigned int range,
+                                unsigned int width, unsigned int height, unsigned int textureFormat,
+                                void *output, unsigned long outputBytes,
+                                unsigned long *outputBytesUsed);
+
+/* NV12 video pictures in, frames out: HapGpuEncodeFramesRGBA with the pictures of HapGpuCompressNV12 in place of RGBA8
+ * ones.  lumaPlanes[f] and chromaPlanes[f] are frame f's Y plane and its plane of interleaved Cb, Cr pairs, both in DEVICE
+ * memory, lumaRowBytes and chromaRowBytes shared by all frames.  The definition is HapGpuCompressNV12's: texel (x, y)
+ * takes Y[y][x] and the pair UV[y >> 1][2 * (x >> 1)], UV[y >> 1][2 * (x >> 1) + 1] (chroma replicated over 2 x 2 luma
+ * samples, no filtering), and with y' = Y - 16 (Limited) or Y (Full), u = Cb - 128, v = Cr - 128 in 32-bit integers
+ *     R = clamp255((cy * y' + crv * v + 32768) >> 16)      G = clamp255((cy * y' - cgu * u - cgv * v + 32768) >> 16)
+ *     B = clamp255((cy * y' + cbu * u + 32768) >> 16)      A = 255
+ * with the coefficients of the table there (matrix: HapGpuYCbCrMatrix, range: HapGpuYCbCrRange).  Every frame is byte
+ * for byte, and in outputBuffersBytesUsed, what HapGpuEncodeFramesRGBA makes of the RGBA8 picture of these bytes with
+ * the same count, textureFormats, compressors, chunkCounts and flags.  No RGBA8 picture ever exists: per block 24 bytes
+ * are read and 8 or 16 written, where converting with a tensor library first reads 24, writes 64 and reads 64 again.
+ * The block encoder runs as a pass of its own in front of the second stage, never inside the fused compress kernel.
+ * count == 1 with RGB_DXT1 (Hap) or YCoCg_DXT5 (Hap Q).  Second stage, frame layout, chunk limiting, store-raw
+ * decisions, Buffer_Too_Small, results[] and every encode flag are HapGpuEncodeFramesPlanes': HAPGPU_ENCODE_BPTC_BLOCKS
+ * is ignored, HAPGPU_ENCODE_REFINE_ENDPOINTS is honoured (RGB_DXT1: the blocks HapGpuEncodeFramesRGBA makes with it of
+ * the converted pictures).  Plane addresses and both pitches are multiples of 4; lumaRowBytes >= width, chromaRowBytes >=
+ * width; width and height multiples of 4, at most 65535 block rows.  ...Begin is the first half of the call as
+ * HapGpuEncodeFramesRGBABegin is (at most 32768 frames; the two arrays of planes are copied by the call and need live
+ * no longer than the other argument arrays); HapGpuEncodeFramesFinish finishes it.
+ * Bad_Arguments for the whole call -- every results[f] set, nothing written, no device touched -- for a NULL array, a
+ * matrix or range outside the enums, a width or height that is no multiple of 4, a pitch that is no multiple of 4 or
+ * below width, more than 65535 block rows, count == 2 or another format.  A frame either of whose planes is NULL, in
+ * host memory or misaligned is Bad_Arguments alone, its output buffer untouched, and the other frames are encoded.  The
+ * function's result is the first failure.  A context between a ...Begin and HapGpuEncodeFramesFinish: Internal_Error.
+ * Out of scope: the way back (frames -> NV12); P010 and other 10/16-bit layouts; planar I420, 4:2:2 and 4:4:4; filtered
+ * or sited chroma upsampling, which needs neighbours across blocks; a separate A8 plane, and with it Hap Alpha, Hap Q
+ * Alpha and Hap Alpha-Only destinations; BC7 / BC6H destinations; host pictures; ...OnDevices and ...Sequence forms of
+ * this call; and reading the planes inside the fused compress kernel. */
+unsigned int HapGpuEncodeFramesNV12(HapGpuContext *context, unsigned int frameCount,
+                                    const void *const *lumaPlanes, unsigned long lumaRowBytes,
+                                    const void *const *chromaPlanes, unsigned long chromaRowBytes,
+                                    unsigned int matrix, unsigned int range,
+                                    unsigned int width, unsigned int height,
+                                    unsigned int count,
+                                    const unsigned int *textureFormats,
+                                    const unsigned int *compressors,
+                                    const unsigned int *chunkCounts,
+                                    void *const *outputBuffers,
+                                    const unsigned long *outputBuffersBytes,
+                                    unsigned long *outputBuffersBytesUsed,
+                                    unsigned int *results,
+                                    unsigned int flags);
+unsigned int HapGpuEncodeFramesNV12Begin(HapGpuContext *context, unsigned int frameCount,
+                                         const void *const *lumaPlanes, unsigned long lumaRowBytes,
+                                         const void *const *chromaPlanes, unsigned long chromaRowBytes,
+                                         unsigned int matrix, unsigned int range,
+                                         unsigned int width, unsigned int height,
+                                         unsigned int count,
+                                         const unsigned int *textureFormats,
+                                         const unsigned int *compressors,
+                                         const unsigned int *chunkCounts,
+                                         void *const *outputBuffers,
+                                         const unsigned long *outputBuffersBytes,
+                                         unsigned long *outputBuffersBytesUsed,
+                                         unsigned int *results,
+                                         unsigned int flags);
+
 /* Hap HDR frames in, RGBA16F pictures out: HapGpuDecodeFramesRGBA for frames of one BC6H texture (unsigned or
  * signed; a batch may mix the two: one block-decode launch per signedness present), pictures as
  * HapGpuDecompressRGBAHalf makes them (rowBytes a multiple of 16, at least width * 8; device pictures 16-byte
