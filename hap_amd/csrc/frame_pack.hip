@@ -126,8 +126,8 @@ __global__ __launch_bounds__(256) void frame_pack_kernel(HapGpuFrameEnc *frames,
     unsigned long long sections_total = 0;
     unsigned extra_at = extra_first + blockIdx.x * chunks_per_frame;      // this frame's group table moves
     ChunkPack *pk = packs + (size_t)blockIdx.x * chunks_per_frame;
-    // placed streams (HapGpuTexEnc.reserved bit 27) lie where this kernel's sums put them only if every chunk shrank
-    int not_placed = (frame.reserved & 1u) != 0u && ((frame.tex[0].reserved >> 27) & 1u) != 0u;
+    // placed streams lie where this kernel's sums put them only if every chunk shrank
+    int not_placed = (frame.notes & HAPGPU_FRAME_NOTE_WAVE_TIMED_OUT) != 0u && hapgpu_control_placed(frame.tex[0].control) != 0u;
 
     for (unsigned t = 0; t < frame.tex_count; t++) {
         const HapGpuTexEnc tex = frame.tex[t];
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void frame_pack_kernel(HapGpuFrameEnc *frames,
         if (tex.compressor == 1u) {
             const unsigned vlen = varint_len(cb);
             // fragment table version 3 (field streams): + a 96-byte group table per fragment
-            const bool with_tiles = tex.emit_index && ((tex.reserved >> 20) & 1u) != 0u && group_tables != nullptr;
+            const bool with_tiles = tex.emit_index && hapgpu_control_half_tiles(tex.control) != 0u && group_tables != nullptr;
             const unsigned index_len = tex.emit_index ? 8u + (with_tiles ? 4u + HAP_GROUP_TABLE_BYTES : 4u) * n * fpc : 0u;
             const unsigned ilen = 5u * n + 8u + index_len;
             // pass 1: total stored payload
@@ -171,11 +171,10 @@ __global__ __launch_bounds__(256) void frame_pack_kernel(HapGpuFrameEnc *frames,
                         write_section(itab, 4u, index_len - 4u, HAP_SECTION_FRAGMENTS);
                         itab[4] = (uint8_t)(with_tiles ? HAP_FRAGMENT_TABLE_VERSION_FIELDS : HAP_FRAGMENT_TABLE_VERSION);
                         itab[5] = (uint8_t)frag_log2;
-                        // granularity_log2 of the element streams (version 3: | block layout << 4;
-                        // compressor code 4 -> 4 = [2,6,4,4], 10 -> 2 = [4,4], 2 -> 6 = [2,6], 12 -> 8 = [4,4,4,4])
-                        const unsigned code = (tex.reserved >> 16) & 0xFu;
-                        itab[6] = (uint8_t)((tex.reserved & 0xFu) | (with_tiles ? (code == 4u ? 4u : code == 10u ? 2u : code == 12u ? 8u : 6u) << 4 : 0u));
-                        itab[7] = (uint8_t)(tex.reserved >> 8);   // match window in 256-byte units, 0 = whole fragment
+                        // granularity_log2 of the element streams (field streams: | HAPGPU_LAYOUT_* << 4)
+                        itab[6] = (uint8_t)(hapgpu_control_granularity_log2(tex.control) |
+                                            (with_tiles ? hapgpu_control_layout(tex.control) << 4 : 0u));
+                        itab[7] = (uint8_t)hapgpu_control_window_256(tex.control);   // match window in 256-byte units, 0 = whole fragment
                     }
                 }
                 // pass 2: positions and the per-chunk table entries
@@ -192,7 +191,7 @@ __global__ __launch_bounds__(256) void frame_pack_kernel(HapGpuFrameEnc *frames,
                     run += tile_total;
                     if (i < n) {
                         const bool raw = csize >= cb;
-                        if (raw && t == 0u && ((tex.reserved >> 27) & 1u))
+                        if (raw && t == 0u && hapgpu_control_placed(tex.control))
                             not_placed = 1;
                         ctab[i] = raw ? (uint8_t)HAP_NIBBLE_NONE : (uint8_t)HAP_NIBBLE_SNAPPY;   // hap.c:465,470
                         put32(stab + 4u * i, (unsigned)stored);                                  // hap.c:472
@@ -210,13 +209,13 @@ __global__ __launch_bounds__(256) void frame_pack_kernel(HapGpuFrameEnc *frames,
                         e.src = (uint64_t)(group_tables + (size_t)(tex.frag_first + i * fpc) * HAP_GROUP_TABLE_BYTES);
                         e.dst = (uint64_t)(itab + 8u + 4u * n * fpc + (size_t)i * fpc * HAP_GROUP_TABLE_BYTES);
                         // (a placed texture's wavefronts have written their group tables here themselves)
-                        e.len = with_tiles && !(t == 0u && ((tex.reserved >> 27) & 1u)) ? fpc * HAP_GROUP_TABLE_BYTES : 0u;
+                        e.len = with_tiles && !(t == 0u && hapgpu_control_placed(tex.control)) ? fpc * HAP_GROUP_TABLE_BYTES : 0u;
                         copies[extra_at + i] = e;
                     }
                 }
             }
         }
-        if (!complex_frame && t == 0u && tex.compressor == 1u && ((tex.reserved >> 27) & 1u))
+        if (!complex_frame && t == 0u && tex.compressor == 1u && hapgpu_control_placed(tex.control))
             not_placed = 1;
         if (!complex_frame) {
             // whole texture stored as-is, reference hap.c:490-495
@@ -301,7 +300,7 @@ __global__ __launch_bounds__(64) void frame_moves_kernel(const HapGpuFrameEnc *f
             e.src = pk.how == 0u ? (uint64_t)(slots + (size_t)f * slot_stride) : (uint64_t)(tsrc + (size_t)i * cb + begin);
             e.dst = pk.dst + at;
             // (a placed stream is where it belongs already)
-            e.len = (t == 0u && ((tex.reserved >> 27) & 1u) && pk.how == 0u) ? 0u : len;
+            e.len = (t == 0u && hapgpu_control_placed(tex.control) && pk.how == 0u) ? 0u : len;
             copies[f] = e;
             if (pk.itab)
                 put32((uint8_t *)pk.itab + 4u * k, pk.how == 0u ? len : 0u);

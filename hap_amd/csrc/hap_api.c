@@ -232,28 +232,7 @@ unsigned long HapGpuPlacementRetryCount(HapGpuContext *context)
 
 unsigned int HapGpuFineChunkCount(unsigned long textureBytes, unsigned int textureFormat)
 {
-    unsigned long want;
-    if (textureBytes == 0 || textureBytes > 0xFFFFFFFFul || hapf_nibble_from_format(textureFormat) == 0)
-        return 0;
-    want = (textureBytes + 8191ul) / 8192ul;
-    if (textureBytes < 16ul)
-        return 1;
-    {
-        /* The SMALLEST divisor of the block count that is at least bytes / 8 KiB: chunks of at most one fragment (ADVICE r05:
-           walking DOWN to a divisor gave 1080p DXT5 240 chunks of 8640 bytes -- two fragments each, which the table-less
-           road into the block-per-lane decoder does not take).  Where the block count has no divisor up to four times that
-           many chunks (a prime number of blocks), the largest one below it, as for any chunk count (hap.c:277-300). */
-        const unsigned long blocks = textureBytes / hapf_block_bytes(textureFormat);
-        unsigned long c, top = want * 4ul;
-        if (top > 3355431ul)
-            top = 3355431ul;
-        if (top > blocks)
-            top = blocks;
-        for (c = want; c <= top; c++)
-            if (c != 0ul && blocks % c == 0ul)
-                return (unsigned)c;
-    }
-    return hapf_limit_chunk_count(textureBytes, textureFormat, want > 3355431ul ? 3355431u : (unsigned)want);
+    return hapf_fine_chunk_count(textureBytes, textureFormat);
 }
 
 unsigned long HapGpuPlacementTimeoutCount(HapGpuContext *context)

@@ -16,6 +16,7 @@
  * HapEncode (hap.c:506-604, 355-504) and HapDecode (hap.c:993-1040, 732-930).
  */
 #include "hap_batch_private.h"
+#include "hap_encode_plan.h"
 #include "measurement_guard.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -44,13 +45,16 @@ int context_busy(HapGpuContext *c, unsigned *results, unsigned frame_count)
     return 1;
 }
 
-/* ================================================================== encode */
+/* the whole-call answer: every result set (a NULL results: none), `code` returned */
+static unsigned answer_all(unsigned *results, unsigned frame_count, unsigned code)
+{
+    unsigned f;
+    for (f = 0; results && f < frame_count; f++)
+        results[f] = code;
+    return code;
+}
 
-typedef struct tex_geom {
-    unsigned format, compressor, chunk_count, chunk_bytes, header_len, fpc, nibble, gran_log2, field_period, half_tiles;
-    unsigned long bytes;
-    size_t bound;        /* hap_max_encoded_length for the requested compressor (hap.c:386) */
-} tex_geom;
+/* ================================================================== encode */
 
 unsigned encode_textures_valid(unsigned count, const unsigned long *input_bytes, const unsigned *formats,
                                const unsigned *compressors, const unsigned *chunk_counts, unsigned flags)
@@ -79,6 +83,400 @@ static unsigned job_table_columns(const HapbBlockEncodeJob *job)
     return job->source.video ? 3u : 1u + job->count;
 }
 
+/* What one hapb_encode call holds from step to step: its arguments, the plan (hap_encode_plan.h), which frames it
+   launches, and its scratch. */
+typedef struct encode_call {
+    HapGpuContext *ctx;
+    const HapbBlockEncodeJob *job;
+    int inputs_are_device;
+    unsigned frame_count, count;
+    const void *const *inputs;
+    void *const *outputs;
+    const unsigned long *output_bytes;
+    unsigned long *output_used;
+    unsigned *results;
+    hap_encode_plan plan;
+    unsigned placed;                  /* plan.placed, after the frames, their number and the context have had their say */
+    /* admission: the frames that are launched, and where in staging those with host buffers lie (+ 1; 0: not staged) */
+    unsigned live, first_error;
+    unsigned *live_index;
+    size_t *stage_off_in, *stage_off_out;
+    size_t stage_in_bytes, stage_out_bytes;
+    /* scratch */
+    HapGpuFrameEnc *hframes, *dframes;
+    uint8_t *dslots, *tex_stage, *out_stage, *dgrouptables;
+    uint32_t *dfragsizes;
+    HapGpuCopyEntry *dcopies;
+    void *dpack;
+    uint64_t *dacc;
+} encode_call;
+
+/* the one owner of a call's admission arrays (what a HapbEncodePending has taken over is NULL here) */
+static void encode_call_free(encode_call *c)
+{
+    free(c->live_index); free(c->stage_off_in); free(c->stage_off_out);
+    c->live_index = NULL;
+    c->stage_off_in = c->stage_off_out = NULL;
+}
+
+/* ... and of a HapbEncodePending and its arrays */
+static void encode_pending_free(HapbEncodePending *pd)
+{
+    free(pd->live_index); free(pd->stage_off_out);
+    free(pd->inputs); free(pd->outputs); free(pd->output_bytes);
+    free(pd);
+}
+
+/* every frame the call would have launched: Internal_Error */
+static unsigned encode_fail_live(const encode_call *c)
+{
+    unsigned k;
+    for (k = 0; k < c->live; k++)
+        c->results[c->live_index[k]] = HapResult_Internal_Error;
+    return HapResult_Internal_Error;
+}
+
+/* 1. per-frame checks: result codes, live_index, staging offsets, and a frame's veto against placing.  Frames that fail
+   are left out of the launch.  0: out of memory */
+static int encode_admit_frames(encode_call *c)
+{
+    const hap_encode_plan *const p = &c->plan;
+    const unsigned count = c->count;
+    size_t in_total = 0, out_total = 0;
+    unsigned f, i;
+    c->live_index = (unsigned *)malloc(sizeof(unsigned) * c->frame_count);
+    c->stage_off_in = (size_t *)calloc(c->frame_count, sizeof(size_t));
+    c->stage_off_out = (size_t *)calloc(c->frame_count, sizeof(size_t));
+    if (!c->live_index || !c->stage_off_in || !c->stage_off_out)
+        return 0;
+    for (f = 0; f < c->frame_count; f++) {
+        unsigned rc = HapResult_No_Error;
+        if (!c->outputs[f] || c->output_bytes[f] == 0)
+            rc = HapResult_Bad_Arguments;
+        for (i = 0; rc == HapResult_No_Error && i < count; i++)
+            if (!c->inputs[(size_t)f * count + i])
+                rc = HapResult_Bad_Arguments;
+        if (rc == HapResult_No_Error) {
+            /* hap.c:386-389 for the first texture; later textures are re-checked against
+               the space actually left once the sizes are known */
+            size_t avail = c->output_bytes[f] > p->outer_header ? c->output_bytes[f] - p->outer_header : 0;
+            if (avail < p->tex[0].bound || c->output_bytes[f] < p->frame_raw_bound)
+                rc = HapResult_Buffer_Too_Small;
+            /* second texture: the reference compares its bound with what is left after the
+               first section's ACTUAL size (hap.c:589); that size is not known before the
+               launch, so the first section's maximum (raw storage) is assumed */
+            else if (count == 2 && avail - (p->tex[0].header_len + p->tex[0].bytes) < p->tex[1].bound)
+                rc = HapResult_Buffer_Too_Small;
+        }
+        c->results[f] = rc;
+        c->output_used[f] = 0;
+        if (rc != HapResult_No_Error) {
+            if (c->first_error == HapResult_No_Error)
+                c->first_error = rc;
+            continue;
+        }
+        c->live_index[c->live++] = f;
+        if (c->output_bytes[f] < p->placed_extent)
+            c->placed = 0u;
+        if (!c->inputs_are_device) {
+            int staged = 0;
+            for (i = 0; i < count; i++)
+                if (!is_dev(c->ctx, c->inputs[(size_t)f * count + i]))
+                    staged = 1;
+            if (staged) {
+                c->stage_off_in[f] = in_total + 1;         /* +1: 0 means "not staged" */
+                in_total += p->stage_in_bytes;
+            }
+        }
+        if (!is_dev(c->ctx, c->outputs[f])) {
+            c->stage_off_out[f] = out_total + 1;
+            /* (+8 per texture: a section written in the chunked form may exceed header + bytes by up to
+               header_len - 1 bytes, see the comparison in frame_pack_kernel / hap.c:478) */
+            out_total += align_up(p->frame_raw_bound + 8u * count > p->placed_extent ? p->frame_raw_bound + 8u * count : p->placed_extent, 256);
+        }
+    }
+    c->stage_in_bytes = in_total;
+    c->stage_out_bytes = out_total;
+    return 1;
+}
+
+/* 2. what the call's size and the context's history say about placing */
+static void encode_placing_policy(encode_call *c)
+{
+    HapGpuContext *const ctx = c->ctx;
+    /* (frames are interleaved over the workgroups: with a dozen of them, few fragments of the same frame are in flight
+       together and the waiting costs less than the gather pass; measured on 8K frames: 1 frame 0.130 against 0.114 ms,
+       8 the same, 16 0.885 against 0.914, 60 2.90 against 3.08) */
+    if (c->live < ctx->placing_min_frames)
+        c->placed = 0u;
+    if (c->placed && ctx->placing_holdoff) {
+        ctx->placing_holdoff -= 1u;
+        c->placed = 0u;
+    }
+    if (ctx->placing_off)                            /* (after a timeout: counted down call by call, then placing is back) */
+        ctx->placing_off -= 1u;
+}
+
+/* 3. scratch for the live frames.  0: out of memory */
+static int encode_scratch(encode_call *c)
+{
+    const hap_encode_plan *const p = &c->plan;
+    hapgpu_rt *const rt = c->ctx->rt;
+    const size_t live = c->live, frags = (size_t)p->frags_per_frame * live, chunks = (size_t)p->chunks_per_frame * live;
+    c->hframes = (HapGpuFrameEnc *)hapgpu_rt_pinned_scratch(rt, P_FRAMES, sizeof(HapGpuFrameEnc) * live);
+    c->dframes = (HapGpuFrameEnc *)hapgpu_rt_device_scratch(rt, D_FRAMES, sizeof(HapGpuFrameEnc) * live);
+    c->dslots = p->any_snappy ? (uint8_t *)hapgpu_rt_device_scratch(rt, D_SLOTS, (size_t)p->slot_stride * frags) : NULL;
+    c->dfragsizes = (uint32_t *)hapgpu_rt_device_scratch(rt, D_FRAGSIZES, sizeof(uint32_t) * frags);
+    c->dcopies = (HapGpuCopyEntry *)hapgpu_rt_device_scratch(rt, D_COPIES, sizeof(HapGpuCopyEntry) * (frags + chunks));
+    c->dpack = hapgpu_rt_device_scratch(rt, D_PACK, (size_t)hapgpu_pack_scratch_bytes_per_chunk() * chunks);
+    if (c->placed)
+        c->dacc = (uint64_t *)hapgpu_rt_device_scratch(rt, D_CHUNK_ACC, sizeof(uint64_t) * chunks);
+    if (p->any_half_tiles)
+        c->dgrouptables = (uint8_t *)hapgpu_rt_device_scratch(rt, D_GROUPTABLES, (size_t)HAP_GROUP_TABLE_BYTES * frags);
+    if (c->stage_in_bytes)
+        c->tex_stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_TEX_STAGE, c->stage_in_bytes);
+    if (c->stage_out_bytes)
+        c->out_stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_FRAME_STAGE, c->stage_out_bytes);
+    return c->hframes && c->dframes && (!c->placed || c->dacc) && (!p->any_snappy || c->dslots) && c->dfragsizes && c->dcopies &&
+           c->dpack && (!p->any_half_tiles || c->dgrouptables) && (!c->stage_in_bytes || c->tex_stage) &&
+           (!c->stage_out_bytes || c->out_stage);
+}
+
+/* 4. the frames' descriptors in pinned memory, and host textures on their way to staging.  != 0: a copy failed */
+static unsigned encode_fill_descriptors(const encode_call *c)
+{
+    const hap_encode_plan *const p = &c->plan;
+    const unsigned count = c->count;
+    unsigned i, k, rc = 0;
+    for (k = 0; k < c->live; k++) {
+        HapGpuFrameEnc *fe = &c->hframes[k];
+        const unsigned f = c->live_index[k];
+        size_t in_cursor = 0;
+        memset(fe, 0, sizeof(*fe));
+        fe->dst = (uint64_t)(uintptr_t)(c->stage_off_out[f] ? c->out_stage + (c->stage_off_out[f] - 1) : (uint8_t *)c->outputs[f]);
+        fe->dst_cap = c->output_bytes[f];
+        fe->tex_count = count;
+        fe->outer_header_len = p->outer_header;
+        fe->status = HapResult_Internal_Error;   /* overwritten by the pack kernel */
+        if (c->placed)
+            fe->chunk_acc = (uint64_t)(uintptr_t)(c->dacc + (size_t)k * p->chunks_per_frame);
+        if (p->kinds.fused) {
+            fe->rgba = c->job->host_table[f];
+            fe->rgba_row_bytes = (uint32_t)c->job->source.row_bytes;
+            fe->rgba_blocks_x = c->job->source.width / 4u;
+            fe->rgba_blocks_x_inv = HAPGPU_DIV_INV(c->job->source.width / 4u);
+        }
+        for (i = 0; i < count; i++) {
+            const hap_encode_tex *t = &p->tex[i];
+            HapGpuTexEnc *te = &fe->tex[i];
+            const void *src = c->inputs[(size_t)f * count + i];
+            if (c->stage_off_in[f] && !is_dev(c->ctx, src)) {
+                uint8_t *d = c->tex_stage + (c->stage_off_in[f] - 1) + in_cursor;
+                rc |= (unsigned)hapgpu_rt_h2d(c->ctx->rt, d, src, t->bytes);
+                src = d;
+            }
+            in_cursor += align_up(t->bytes, 256);
+            te->src = (uint64_t)(uintptr_t)src;
+            te->bytes = (uint32_t)t->bytes;
+            te->format_nibble = t->nibble;
+            te->compressor = t->compressor;
+            te->chunk_count = t->chunk_count;
+            te->chunk_bytes = t->chunk_bytes;
+            te->header_len = t->header_len;
+            te->frags_per_chunk = t->fpc;
+            te->frags_per_chunk_inv = HAPGPU_DIV_INV(t->fpc ? t->fpc : 1u);
+            te->frag_first = k * p->frags_per_frame + (i ? p->tex[0].chunk_count * p->tex[0].fpc : 0u);
+            te->emit_index = (p->flags & HAPGPU_ENCODE_FRAGMENT_INDEX) ? 1u : 0u;
+            te->control = hap_encode_plan_control(p, i, c->placed);
+        }
+    }
+    return rc;
+}
+
+/* 5. With every buffer in device memory (nothing staged) nothing in the call's launches depends on the buffers
+   themselves -- their addresses are in the tables copied from pinned memory -- so the sequence is recorded once per
+   geometry as a HIP graph and replayed with one launch.  1: such a call, *key_out everything its kernel arguments and
+   copy sizes depend on */
+static int encode_graph_key(const encode_call *c, uint64_t *key_out)
+{
+    const hap_encode_plan *const p = &c->plan;
+    const HapGpuContext *const ctx = c->ctx;
+    const HapbBlockEncodeJob *const job = c->job;
+    uint64_t key = 0xCBF29CE484222325ull;
+    unsigned i;
+    if (c->stage_in_bytes != 0 || c->stage_out_bytes != 0 || c->inputs_are_device == 2 ||
+        (p->flags & HAPGPU_ENCODE_SMALLER_FILES) || p->frag_log2 != 13u)
+        return 0;
+#define HAPB_MIX(v) (key = (key ^ (uint64_t)(v)) * 0x100000001B3ull)
+    HAPB_MIX(c->live); HAPB_MIX(c->count); HAPB_MIX(p->flags); HAPB_MIX(p->frag_log2); HAPB_MIX(ctx->byte_granular);
+    HAPB_MIX(ctx->position_lanes); HAPB_MIX(ctx->rgtc1_fields); HAPB_MIX(ctx->no_half_tiles); HAPB_MIX(p->kinds.fused); HAPB_MIX(c->placed);
+    for (i = 0; i < c->count; i++) {
+        HAPB_MIX(p->tex[i].format); HAPB_MIX(p->tex[i].compressor); HAPB_MIX(p->tex[i].chunk_count); HAPB_MIX(p->tex[i].bytes);
+    }
+    if (job) {
+        const HapbSource *const src = &job->source;
+        HAPB_MIX(job->frame_count); HAPB_MIX(src->width); HAPB_MIX(src->height); HAPB_MIX(src->row_bytes);
+        HAPB_MIX(job->wide + 2); HAPB_MIX(src->picture_kind);
+        if (src->planes) {
+            /* (scale and bias are kernel arguments: part of what a recording holds) */
+            HAPB_MIX(src->planes->channels + 8u); HAPB_MIX(src->planes->element); HAPB_MIX(src->planes->plane_bytes);
+            for (i = 0; i < src->planes->channels; i++) {
+                uint32_t bits[2];
+                memcpy(&bits[0], &job->plane_scale[i], 4);
+                memcpy(&bits[1], &job->plane_bias[i], 4);
+                HAPB_MIX(bits[0]); HAPB_MIX(bits[1]);
+            }
+        }
+        if (src->video) {
+            /* (the pitch, the matrix and the range are kernel arguments too) */
+            HAPB_MIX(16u); HAPB_MIX(src->video->chroma_row_bytes); HAPB_MIX(src->video->matrix); HAPB_MIX(src->video->range);
+        }
+    }
+#undef HAPB_MIX
+    *key_out = key;
+    return 1;
+}
+
+/* 6. the launches of the call as one sequence.  != 0: one of them failed */
+static unsigned encode_launches(const encode_call *c)
+{
+    const hap_encode_plan *const p = &c->plan;
+    const HapbBlockEncodeJob *const job = c->job;
+    hapgpu_rt *const rt = c->ctx->rt;
+    const unsigned live = c->live, count = c->count;
+    unsigned i, rc = 0;
+    if (job) {
+        const HapbSource *const src = &job->source;
+        /* Hap Q Alpha: both textures from one pass over the RGBA (64 + 16 + 8 bytes per block);
+           else one launch per texture that the second stage does not make itself.  (A batch takes at most
+           65535 block rows.) */
+        const int pair = job->count == 2 && job->formats[0] == HapTextureFormat_YCoCg_DXT5 &&
+                         job->formats[1] == HapTextureFormat_A_RGTC1;
+        rc |= (unsigned)hapgpu_rt_h2d(rt, job->device_table, job->host_table,
+                                      sizeof(uint64_t) * (size_t)job_table_columns(job) * job->frame_count);
+        for (i = 0; i < (pair ? 1u : job->count); i++)
+            if (pair || !p->tex[i].fused) {
+                const uint64_t *dt = job->device_table;
+                /* (video pictures: one texture a frame, and the third column holds their CbCr planes) */
+                const HapGpuPictureTable t = {{dt, dt + (size_t)(1u + i) * job->frame_count,
+                                               pair || src->video ? dt + 2u * (size_t)job->frame_count : NULL}, {0u, 0u, 0u}};
+                rc |= src->height / 4u > 65535u ? 1u :
+                      src->video ?
+                      (unsigned)hapgpu_k_block_encode_video(rt, &t, job->frame_count, src->width, src->height,
+                                                            job->formats[i], p->refine, src->row_bytes,
+                                                            src->video->chroma_row_bytes, src->video->matrix,
+                                                            src->video->range) :
+                      src->planes ?
+                      (unsigned)hapgpu_k_block_encode_planes(rt, &t, job->frame_count, src->width, src->height,
+                                                             job->formats[i], (unsigned)pair | p->refine, src->planes->channels,
+                                                             src->planes->element, src->planes->plane_bytes,
+                                                             src->row_bytes, job->plane_scale, job->plane_bias) :
+                      (unsigned)hapgpu_k_block_encode(rt, &t, job->frame_count, src->width, src->height,
+                                                      src->row_bytes, job->formats[i], (unsigned)pair | p->refine, job->wide,
+                                                      src->picture_kind);
+            }
+    }
+    rc |= (unsigned)hapgpu_rt_h2d(rt, c->dframes, c->hframes, sizeof(HapGpuFrameEnc) * live);
+    if (c->placed) {
+        rc |= (unsigned)hapgpu_rt_zero(rt, c->dacc, sizeof(uint64_t) * (size_t)p->chunks_per_frame * live);
+        rc |= (unsigned)hapgpu_rt_zero(rt, c->dfragsizes, sizeof(uint32_t) * (size_t)p->frags_per_frame * live);
+    }
+    if (p->any_snappy)
+        rc |= (unsigned)hapgpu_k_snappy_compress(rt, c->dframes, live, p->max_frags_per_tex, p->frag_log2, c->dslots, p->slot_stride,
+                                                 c->dfragsizes, c->dgrouptables, &p->kinds);
+    rc |= (unsigned)hapgpu_k_frame_pack(rt, c->dframes, live, p->frag_log2, c->dslots, p->slot_stride, c->dfragsizes, c->dgrouptables,
+                                        c->dcopies, p->frags_per_frame * live, p->chunks_per_frame, p->max_chunks_per_tex, count, c->dpack);
+    /* (placed fragments -- single-texture frames -- and their group tables are where they belong: nothing to
+       gather.  A frame reported as not placed is encoded again as a whole.) */
+    if (!(c->placed && count == 1u))
+        rc |= (unsigned)hapgpu_k_frame_gather(rt, c->dcopies, (p->frags_per_frame + p->chunks_per_frame) * live);
+    rc |= (unsigned)hapgpu_rt_d2h(rt, c->hframes, c->dframes, sizeof(HapGpuFrameEnc) * live);
+    return rc;
+}
+
+/* ... replayed where the runtime holds a recording of them, recorded where it wants one, else issued plainly */
+static unsigned encode_launch(const encode_call *c)
+{
+    hapgpu_rt *const rt = c->ctx->rt;
+    uint64_t key = 0;
+    const int graph = encode_graph_key(c, &key) ? hapgpu_rt_graph_begin(rt, key) : 2;
+    unsigned rc;
+    if (graph == 1)
+        return 0;
+    rc = encode_launches(c);
+    /* (a recording that cannot be ended, instantiated or launched has run nothing: graphs are switched off for
+       this context and the same launches are issued once more, plainly.  A recording can also be invalidated from
+       outside -- another thread of the process synchronising the device while it runs: then the launches themselves
+       report errors.  Either way nothing has run.) */
+    if (graph == 0 && (hapgpu_rt_graph_end(rt, key, rc != 0) != 0 || rc != 0)) {
+        hapgpu_rt_graphs_disable(rt);
+        rc = encode_launches(c);
+    }
+    return rc;
+}
+
+/* 7. what hapb_encode_complete needs of the call: copies of the client's arrays, and the call's admission arrays, which
+   are the pending call's from here.  NULL: out of memory */
+static HapbEncodePending *encode_pending(encode_call *c, const unsigned long *input_bytes, const unsigned *formats,
+                                         const unsigned *compressors, unsigned launch_rc)
+{
+    const HapbBlockEncodeJob *const job = c->job;
+    const size_t n_in = (size_t)c->frame_count * c->count;
+    HapbEncodePending *pd = (HapbEncodePending *)calloc(1, sizeof(*pd));
+    unsigned i;
+    if (!pd)
+        return NULL;
+    pd->inputs = (const void **)malloc(sizeof(void *) * n_in);
+    pd->outputs = (void **)malloc(sizeof(void *) * c->frame_count);
+    pd->output_bytes = (unsigned long *)malloc(sizeof(unsigned long) * c->frame_count);
+    if (!pd->inputs || !pd->outputs || !pd->output_bytes) {
+        encode_pending_free(pd);
+        return NULL;
+    }
+    memcpy(pd->inputs, c->inputs, sizeof(void *) * n_in);
+    memcpy(pd->outputs, c->outputs, sizeof(void *) * c->frame_count);
+    memcpy(pd->output_bytes, c->output_bytes, sizeof(unsigned long) * c->frame_count);
+    for (i = 0; i < c->count; i++) {
+        pd->input_bytes[i] = input_bytes[i];
+        pd->formats[i] = formats[i];
+        pd->compressors[i] = compressors[i];
+        pd->chunk_counts[i] = c->plan.chunk_counts[i];
+    }
+    pd->frame_count = c->frame_count;
+    pd->count = c->count;
+    pd->flags = c->plan.flags;
+    pd->inputs_are_device = c->inputs_are_device;
+    pd->output_used = c->output_used;
+    pd->results = c->results;
+    pd->live = c->live;
+    pd->placed = c->placed;
+    pd->first_error = c->first_error;
+    pd->launch_rc = launch_rc;
+    pd->live_index = c->live_index;
+    pd->stage_off_out = c->stage_off_out;
+    c->live_index = NULL;
+    c->stage_off_out = NULL;
+    pd->hframes = c->hframes;
+    pd->out_stage = c->out_stage;
+    if (job) {
+        pd->job = *job;
+        pd->has_job = 1;
+        if (job->source.planes) {
+            /* (the caller's description need not outlive the first half either) */
+            pd->planes = *job->source.planes;
+            pd->planes.scale = pd->planes.bias = NULL;
+            pd->job.source.planes = &pd->planes;
+        }
+        if (job->source.video) {
+            /* (... nor need its array of CbCr planes: their addresses are in the job's table) */
+            pd->video = *job->source.video;
+            pd->video.chroma = NULL;
+            pd->job.source.video = &pd->video;
+        }
+    }
+    return pd;
+}
+
 unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                      const void *const *inputs, const unsigned long *input_bytes,
                      const unsigned *formats, const unsigned *compressors, const unsigned *chunk_counts,
@@ -87,39 +485,11 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
                      const HapbEncodeArgs *args)
 {
     static const HapbEncodeArgs no_args;
+    static const encode_call no_call;
     const HapbEncodeArgs *const a = args ? args : &no_args;
-    const int inputs_are_device = a->inputs_are_device;
-    const HapbBlockEncodeJob *const job = a->job;
-    /* HAPGPU_ENCODE_REFINE_ENDPOINTS: looked at where this call makes the blocks itself, of one texture a frame (the
-       kernels look at it for RGB_DXT1 and RGBA_DXT5 alone) */
-    const unsigned refine = (job && count == 1u && (flags & HAPGPU_ENCODE_REFINE_ENDPOINTS)) ? HAPGPU_BLOCK_ENCODE_REFINE : 0u;
-    tex_geom g[2];
-    unsigned fine_counts[2] = {0u, 0u};
-    unsigned i, f, first_error = HapResult_No_Error;
-    unsigned outer_header = 0, frags_per_frame = 0, max_frags_per_tex = 0, live = 0, chunks_per_frame = 0;
-    int any_half_tiles = 0;
-    uint8_t *dgrouptables = NULL;
-    void *dpack = NULL;
-    unsigned max_chunks_per_tex = 0;
-    /* HAPGPU_ENCODE_SMALLER_FILES: 64 KiB fragments (a match may lie 64 KiB back, like libsnappy's), elements on
-       16-bit positions anywhere instead of whole block fields, and no fragment table */
-    const int smaller = (flags & HAPGPU_ENCODE_SMALLER_FILES) != 0;
-    unsigned frag_log2 = smaller ? 16u : ctx->frag_log2, frag_bytes = 1u << frag_log2;
-    unsigned slot_stride;
-    int any_snappy = 0;
-    unsigned gran_mask = 0;
-    size_t placed_extent = 0;
-    unsigned placed = 0u;                            /* texture 0's fragments are written where they belong in the frame (bit 27) */
-    uint64_t *dacc = NULL;
-    unsigned fused[2] = {0u, 0u}, fused_mask = 0u;   /* textures the second stage makes from the RGBA itself (code: reserved bits 24..26) */
-    size_t stage_in_bytes = 0, stage_out_bytes = 0, frame_raw_bound = 0;
-    hapgpu_rt *rt = ctx->rt;
-    HapGpuFrameEnc *hframes, *dframes;
-    uint8_t *dslots, *tex_stage = NULL, *out_stage = NULL;
-    uint32_t *dfragsizes;
-    HapGpuCopyEntry *dcopies;
-    size_t *stage_off_in = NULL, *stage_off_out = NULL;
-    unsigned *live_index = NULL;
+    encode_call c = no_call;
+    HapbEncodePending *pd = NULL;
+    unsigned f, rc = HapResult_No_Error;
 
     if (frame_count == 0)
         return HapResult_No_Error;
@@ -128,501 +498,77 @@ unsigned hapb_encode(HapGpuContext *ctx, unsigned frame_count, unsigned count,
     if (context_busy(ctx, results, frame_count))
         return HapResult_Internal_Error;
     /* frame-independent argument checks, reference hap.c:518-559 */
+    if (count == 0 || count > 2 || !inputs || !input_bytes || !formats || !compressors || !chunk_counts ||
+        !outputs || !output_bytes || !output_used)
+        rc = HapResult_Bad_Arguments;
+    if (rc == HapResult_No_Error)
+        rc = encode_textures_valid(count, input_bytes, formats, compressors, chunk_counts, flags);
+    if (rc != HapResult_No_Error)
+        return answer_all(results, frame_count, rc);
+    /* geometry and policy shared by every frame of the batch */
     {
-        unsigned rc = HapResult_No_Error;
-        if (count == 0 || count > 2 || !inputs || !input_bytes || !formats || !compressors || !chunk_counts ||
-            !outputs || !output_bytes || !output_used)
-            rc = HapResult_Bad_Arguments;
-        if (rc == HapResult_No_Error)
-            rc = encode_textures_valid(count, input_bytes, formats, compressors, chunk_counts, flags);
+        const hap_encode_knobs knobs = {ctx->frag_log2, ctx->byte_granular, ctx->position_lanes, ctx->rgtc1_fields,
+                                        ctx->no_half_tiles, ctx->no_fusion,
+                                        !ctx->no_placing && !a->never_place && !ctx->placing_off};
+        hap_encode_source source = {0u, 0, 0, 0u, 0u, 0ul};
+        if (a->job) {
+            const HapbSource *const s = &a->job->source;
+            source.picture_kind = s->picture_kind;
+            source.planes = s->planes != NULL;
+            source.video = s->video != NULL;
+            source.width = s->width;
+            source.height = s->height;
+            source.row_bytes = s->row_bytes;
+        }
+        rc = hap_encode_plan_of(&c.plan, &knobs, flags, count, input_bytes, formats, compressors, chunk_counts,
+                                a->job ? &source : NULL);
         if (rc != HapResult_No_Error) {
             for (f = 0; f < frame_count; f++)
-                results[f] = rc;
-            return rc;
+                output_used[f] = 0;
+            return answer_all(results, frame_count, rc);
         }
     }
-    if (smaller)
-        flags &= ~HAPGPU_ENCODE_FRAGMENT_INDEX;
-    /* HAPGPU_ENCODE_FINE_CHUNKS: one chunk per Snappy fragment (8 KiB of texture) -- the chunk size table every Hap parser
-       reads (hap.c:265-300) then says where each independently compressed piece begins */
-    if ((flags & HAPGPU_ENCODE_FINE_CHUNKS) && !smaller) {
-        for (i = 0; i < count; i++)
-            fine_counts[i] = compressors[i] == HapCompressorSnappy ? HapGpuFineChunkCount(input_bytes[i], formats[i]) : chunk_counts[i];
-        chunk_counts = fine_counts;
-    }
-    /* geometry shared by every frame of the batch */
-    if (count == 2) {
-        size_t worst = 0;                                             /* hap.c:563-576 */
-        for (i = 0; i < count; i++)
-            worst += input_bytes[i] + hapf_instructions_length(chunk_counts[i]) + 4u;
-        outer_header = worst > 0xFFFFFFu ? 8u : 4u;
-    }
-    for (i = 0; i < count; i++) {
-        tex_geom *t = &g[i];
-        t->format = formats[i];
-        t->nibble = hapf_nibble_from_format(formats[i]);
-        t->compressor = compressors[i];
-        t->bytes = input_bytes[i];
-        t->bound = hapf_texture_bound(t->bytes, t->format, t->compressor, chunk_counts[i]);
-        t->header_len = t->bytes > 0xFFFFFFu ? 8u : 4u;              /* hap.c:398-405 */
-        if (t->compressor == HapCompressorSnappy) {
-            t->chunk_count = hapf_limit_chunk_count(t->bytes, t->format, chunk_counts[i]);
-            t->chunk_bytes = (unsigned)(t->bytes / t->chunk_count);
-        }
-        if (t->compressor == HapCompressorSnappy && t->chunk_bytes == 0) {
-            /* less than one block per chunk (not a real texture): the reference compresses
-               zero-length chunks, finds no gain and stores the section as-is (hap.c:478-495) */
-            t->compressor = HapCompressorNone;
-        }
-        if (t->compressor == HapCompressorSnappy) {
-            any_snappy = 1;
+    c.ctx = ctx;
+    c.job = a->job;
+    c.inputs_are_device = a->inputs_are_device;
+    c.frame_count = frame_count;
+    c.count = count;
+    c.inputs = inputs;
+    c.outputs = outputs;
+    c.output_bytes = output_bytes;
+    c.output_used = output_used;
+    c.results = results;
+    c.placed = c.plan.placed;
+
+    if (!encode_admit_frames(&c)) {
+        rc = HapResult_Internal_Error;
+    } else if (c.live == 0) {
+        rc = c.first_error;
+    } else {
+        encode_placing_policy(&c);
+        if (!encode_scratch(&c)) {
+            rc = encode_fail_live(&c);
         } else {
-            t->chunk_count = 1;
-            t->chunk_bytes = (unsigned)t->bytes;
-        }
-        t->fpc = (t->chunk_bytes + frag_bytes - 1) / frag_bytes;
-        /* 16-bit granular element streams need even chunk sizes (always true for block textures) */
-        t->gran_log2 = 0u;
-        if (t->compressor == HapCompressorSnappy && !ctx->byte_granular) {
-            /* DXT1 blocks are two 4-byte fields (endpoints, indices): everything repeats on 4-byte
-               boundaries.  The alpha-style blocks of RGTC1 / DXT5 / YCoCg start their index bytes at
-               byte 2, so those streams are 2-byte granular. */
-            if ((t->format == HapTextureFormat_RGB_DXT1 || (flags & HAPGPU_ENCODE_COARSE_MATCHES) ||
-                 (t->format == HapTextureFormat_A_RGTC1 && ctx->rgtc1_fields && ctx->rgtc1_fields != 26u)) && (t->chunk_bytes & 3u) == 0)
-                t->gran_log2 = 2u;
-            else if ((t->chunk_bytes & 1u) == 0)
-                t->gran_log2 = 1u;
-        }
-        /* alpha-style blocks (2 endpoint + 6 index bytes [+ 4 + 4 of the colour half]) go to the field-per-lane
-           compressor when everything lines up: default fragment size, whole blocks per chunk, 16-bit streams */
-        t->field_period = 0u;
-        if (t->compressor == HapCompressorSnappy && frag_log2 == 13u && !ctx->position_lanes && !smaller) {
-            if (t->gran_log2 == 1u && (t->format == HapTextureFormat_RGBA_DXT5 || t->format == HapTextureFormat_YCoCg_DXT5) &&
-                (t->chunk_bytes & 15u) == 0)
-                t->field_period = 4u;
-            else if (t->gran_log2 == 2u && (t->format == HapTextureFormat_RGB_DXT1 ||
-                                            (t->format == HapTextureFormat_A_RGTC1 && ctx->rgtc1_fields)) && (t->chunk_bytes & 7u) == 0)
-                t->field_period = 10u;      /* 2 fields per block, the [4, 4] layout (code 2 | 8) */
-            else if (t->gran_log2 == 1u && t->format == HapTextureFormat_A_RGTC1 && ctx->rgtc1_fields == 26u &&
-                     (t->chunk_bytes & 7u) == 0 && t->bytes >= ((size_t)2u << 20))
-                t->field_period = 2u;       /* [2, 6]: endpoints, indices */
-            else if ((flags & HAPGPU_ENCODE_COARSE_MATCHES) && t->gran_log2 == 2u && (t->chunk_bytes & 15u) == 0 &&
-                     (t->format == HapTextureFormat_RGBA_BPTC_UNORM || t->format == HapTextureFormat_RGB_BPTC_UNSIGNED_FLOAT ||
-                      t->format == HapTextureFormat_RGB_BPTC_SIGNED_FLOAT))
-                t->field_period = 12u;      /* opaque 16-byte blocks as four dwords (the size-for-speed option): the block
-                                               kernels instead of the position-per-lane ones */
-            /* (RGTC1 planes of 2 MiB and more -- block rows longer than a fragment -- take their natural [2, 6] layout:
-               same size as the position-per-lane kernel there (0.171 against 0.169 of an 8K alpha plane).  Smaller
-               ones stay with positions per lane: their matches start inside the index bytes of the row above, which
-               lies inside the fragment -- 0.25 against 0.45 of a 2048 x 512 plane) */
-        }
-        /* field streams (fragment table version 3): with the table requested, the block compressor's streams come with
-           a group table per fragment (96 bytes: where each of the decoder's 64 lanes starts reading) */
-        t->half_tiles = ((t->field_period == 4u || t->field_period == 10u || t->field_period == 2u || t->field_period == 12u) && (flags & HAPGPU_ENCODE_FRAGMENT_INDEX) &&
-                         !ctx->no_half_tiles) ? 1u : 0u;
-        if (t->half_tiles)
-            any_half_tiles = 1;
-        /* a call that starts from RGBA8 pictures (hapb_source_frames): the block compressor makes the blocks of its
-           fragment itself, one pass less over the texture and the pixel loads of one wave under the matching of the
-           others (snappy_compress_blocks.hip).  One texture per frame. */
-        {
-            if (job && !ctx->no_fusion && count == 1u && job->source.picture_kind == HAPGPU_PICTURE_RGBA8 && !job->source.planes &&
-                !job->source.video && (job->source.row_bytes & 3u) == 0 && (unsigned long long)job->source.row_bytes * job->source.height < 0xFFFFFFFFull &&
-                job->source.width / 4u >= 1u) {
-                /* (code: HapGpuTexEnc.reserved bits 24..26; mask bit: which kernel the launcher starts) */
-                if (t->field_period == 4u && t->format == HapTextureFormat_YCoCg_DXT5) {
-                    fused[i] = 3u; fused_mask |= 1u;
-                } else if (t->field_period == 4u && t->format == HapTextureFormat_RGBA_DXT5 && !refine) {
-                    /* (refined end points: the fused block compressor keeps its one definition of a block, and the
-                       texture comes from the block kernel like a DXT1 one) */
-                    fused[i] = 2u; fused_mask |= 2u;
-                }
-                /* (DXT1, two blocks to a lane: built and measured -- 115 registers once the match stage's units are read
-                   back from the texture instead of kept; 60 4K frames 0.663 against 0.658 ms, 60 1080p frames 0.241
-                   against 0.233: its block encoder is further from its instruction-issue limit than the 16-byte ones',
-                   nothing to win.  The kernel keeps the two-pass form; the launcher does not start it.) */
+            unsigned launch_rc = encode_fill_descriptors(&c);
+            launch_rc |= encode_launch(&c);
+            /* everything the call launches is on the stream: the rest -- waiting, reading the results, the second pass
+               over frames that were not placed -- is hapb_encode_complete's, at once or (HapGpuEncodeFramesRGBABegin /
+               ...Finish) when the client asks for the results */
+            pd = encode_pending(&c, input_bytes, formats, compressors, launch_rc);
+            if (!pd) {
+                hapgpu_rt_sync(ctx->rt);
+                rc = encode_fail_live(&c);
             }
-        }
-        if (t->compressor == HapCompressorSnappy && !fused[i])
-            gran_mask |= t->field_period == 4u ? 32u : t->field_period == 10u ? 64u : t->field_period == 2u ? 16u
-                         : t->field_period == 12u ? 128u : 1u << t->gran_log2;
-        if (t->compressor == HapCompressorSnappy) {
-            /* header choice uses the layout that will actually be written (hap.c:425-428) */
-            size_t ilen = hapf_instructions_length(t->chunk_count);
-            if (flags & HAPGPU_ENCODE_FRAGMENT_INDEX)
-                ilen += 8u + (t->half_tiles ? 4u + HAP_GROUP_TABLE_BYTES : 4u) * (size_t)t->chunk_count * t->fpc;
-            if (ilen + 4u > 0xFFFFFFu) {          /* instruction container must fit a 24-bit length */
-                for (f = 0; f < frame_count; f++) {
-                    results[f] = HapResult_Bad_Arguments;
-                    output_used[f] = 0;
-                }
-                return HapResult_Bad_Arguments;
-            }
-            if (t->bytes + ilen + 4u > 0xFFFFFFu)
-                t->header_len = 8u;
-        }
-        if ((size_t)t->chunk_count * t->fpc > max_frags_per_tex)
-            max_frags_per_tex = t->chunk_count * t->fpc;
-        frags_per_frame += t->chunk_count * t->fpc;
-        chunks_per_frame += t->chunk_count;
-        if (t->chunk_count > max_chunks_per_tex)
-            max_chunks_per_tex = t->chunk_count;
-        stage_in_bytes += align_up(t->bytes, 256);
-        frame_raw_bound += t->header_len + t->bytes;
-    }
-    frame_raw_bound += outer_header;
-    /* the block compressor can put the first texture's fragments straight into the frame (no gather pass over them):
-       its wavefronts learn the sizes of what lies before them from each other (snappy_compress_blocks.hip) */
-    /* (up to 64 chunks: their totals are one load per wavefront.  16 8K frames of 400 chunks: 0.966 ms placed against 0.880
-       gathered; of 1 chunk -- 4050 fragments to look back over -- 1.110 against 1.111) */
-    /* (frames of two textures -- Hap Q Alpha -- with their FIRST texture placed and the second one gathered behind it:
-       measured in round 5 and slower at every chunk count, because such calls run the compressor that reads finished
-       textures, whose wavefronts are short: what a placed one waits for -- every fragment before it compressed -- is a
-       larger share of its life than in the kernel that makes its blocks itself.  16 8K Hap Q Alpha frames, 24 + 24
-       chunks: compress 0.493 -> 0.722 ms for a gather of 0.106 -> 0.036; 4 16K frames, 64 + 64: 0.922 -> 1.537 for
-       0.219 -> 0.082.  One texture per frame.) */
-    placed = (!ctx->no_placing && !a->never_place && !ctx->placing_off && count == 1u && g[0].compressor == HapCompressorSnappy && g[0].field_period != 0u && frag_log2 == 13u &&
-              g[0].chunk_count <= 64u) ? 1u : 0u;
-    slot_stride = (unsigned)align_up(frag_bytes + frag_bytes / 32u + 64u + HAPGPU_SLOT_SCRATCH_BYTES, 16);
-    /* how far placed fragments can reach into the frame buffer if nothing shrinks (the frame is then encoded again, but
-       the bytes have been written): the chunked layout's headers and tables + every fragment at its largest (what a slot
-       holds).  The bound hap.h asks of the client's buffer covers it except for chunks of a few hundred bytes with the
-       private table requested; buffers that do not are served through slots. */
-    if (placed) {
-        const size_t frags = (size_t)g[0].chunk_count * g[0].fpc;
-        size_t ilen = hapf_instructions_length(g[0].chunk_count);
-        if (flags & HAPGPU_ENCODE_FRAGMENT_INDEX)
-            ilen += 8u + (g[0].half_tiles ? 4u + HAP_GROUP_TABLE_BYTES : 4u) * frags;
-        placed_extent = outer_header + 8u + 4u + ilen + 5u * (size_t)g[0].chunk_count + g[0].bytes + frags * (frag_bytes / 32u + 64u);
-        /* the compressor's wavefronts add up what lies before them in the frame in 32 bits: every such sum is a
-           position below this extent (a texture is below 4 GiB, but its fragments at their largest need not be).
-           Beyond it the frame goes through slots. */
-        if (placed_extent > 0xFFFFFFFFul) {
-            placed = 0u;
-            placed_extent = 0;
         }
     }
-
-    /* per-frame checks; frames that fail are left out of the launch */
-    live_index = (unsigned *)malloc(sizeof(unsigned) * frame_count);
-    stage_off_in = (size_t *)calloc(frame_count, sizeof(size_t));
-    stage_off_out = (size_t *)calloc(frame_count, sizeof(size_t));
-    if (!live_index || !stage_off_in || !stage_off_out) {
-        free(live_index); free(stage_off_in); free(stage_off_out);
-        return HapResult_Internal_Error;
+    encode_call_free(&c);
+    if (!pd)
+        return rc;
+    if (a->defer) {
+        ctx->pending_encode = pd;
+        return c.first_error;
     }
-    {
-        size_t in_total = 0, out_total = 0;
-        for (f = 0; f < frame_count; f++) {
-            unsigned rc = HapResult_No_Error;
-            if (!outputs[f] || output_bytes[f] == 0)
-                rc = HapResult_Bad_Arguments;
-            for (i = 0; rc == HapResult_No_Error && i < count; i++)
-                if (!inputs[(size_t)f * count + i])
-                    rc = HapResult_Bad_Arguments;
-            if (rc == HapResult_No_Error) {
-                /* hap.c:386-389 for the first texture; later textures are re-checked against
-                   the space actually left once the sizes are known */
-                size_t avail = output_bytes[f] > outer_header ? output_bytes[f] - outer_header : 0;
-                if (avail < g[0].bound || output_bytes[f] < frame_raw_bound)
-                    rc = HapResult_Buffer_Too_Small;
-                /* second texture: the reference compares its bound with what is left after the
-                   first section's ACTUAL size (hap.c:589); that size is not known before the
-                   launch, so the first section's maximum (raw storage) is assumed */
-                else if (count == 2 && avail - (g[0].header_len + g[0].bytes) < g[1].bound)
-                    rc = HapResult_Buffer_Too_Small;
-            }
-            results[f] = rc;
-            output_used[f] = 0;
-            if (rc != HapResult_No_Error) {
-                if (first_error == HapResult_No_Error)
-                    first_error = rc;
-                continue;
-            }
-            live_index[live++] = f;
-            if (output_bytes[f] < placed_extent)
-                placed = 0u;
-            if (!inputs_are_device) {
-                int staged = 0;
-                for (i = 0; i < count; i++)
-                    if (!is_dev(ctx, inputs[(size_t)f * count + i]))
-                        staged = 1;
-                if (staged) {
-                    stage_off_in[f] = in_total + 1;         /* +1: 0 means "not staged" */
-                    in_total += stage_in_bytes;
-                }
-            }
-            if (!is_dev(ctx, outputs[f])) {
-                stage_off_out[f] = out_total + 1;
-                /* (+8 per texture: a section written in the chunked form may exceed header + bytes by up to
-                   header_len - 1 bytes, see the comparison in frame_pack_kernel / hap.c:478) */
-                out_total += align_up(frame_raw_bound + 8u * count > placed_extent ? frame_raw_bound + 8u * count : placed_extent, 256);
-            }
-        }
-        stage_in_bytes = in_total;
-        stage_out_bytes = out_total;
-    }
-    if (live == 0) {
-        free(live_index); free(stage_off_in); free(stage_off_out);
-        return first_error;
-    }
-    /* (frames are interleaved over the workgroups: with a dozen of them, few fragments of the same frame are in flight
-       together and the waiting costs less than the gather pass; measured on 8K frames: 1 frame 0.130 against 0.114 ms,
-       8 the same, 16 0.885 against 0.914, 60 2.90 against 3.08) */
-    if (live < ctx->placing_min_frames)
-        placed = 0u;
-    if (placed && ctx->placing_holdoff) {
-        ctx->placing_holdoff -= 1u;
-        placed = 0u;
-    }
-    if (ctx->placing_off)                            /* (after a timeout: counted down call by call, then placing is back) */
-        ctx->placing_off -= 1u;
-
-    /* scratch */
-    hframes = (HapGpuFrameEnc *)hapgpu_rt_pinned_scratch(rt, P_FRAMES, sizeof(HapGpuFrameEnc) * live);
-    dframes = (HapGpuFrameEnc *)hapgpu_rt_device_scratch(rt, D_FRAMES, sizeof(HapGpuFrameEnc) * live);
-    dslots = any_snappy ? (uint8_t *)hapgpu_rt_device_scratch(rt, D_SLOTS, (size_t)slot_stride * frags_per_frame * live) : NULL;
-    dfragsizes = (uint32_t *)hapgpu_rt_device_scratch(rt, D_FRAGSIZES, sizeof(uint32_t) * (size_t)frags_per_frame * live);
-    dcopies = (HapGpuCopyEntry *)hapgpu_rt_device_scratch(rt, D_COPIES, sizeof(HapGpuCopyEntry) * ((size_t)frags_per_frame + chunks_per_frame) * live);
-    dpack = hapgpu_rt_device_scratch(rt, D_PACK, (size_t)hapgpu_pack_scratch_bytes_per_chunk() * chunks_per_frame * live);
-    if (placed)
-        dacc = (uint64_t *)hapgpu_rt_device_scratch(rt, D_CHUNK_ACC, sizeof(uint64_t) * (size_t)chunks_per_frame * live);
-    if (any_half_tiles)
-        dgrouptables = (uint8_t *)hapgpu_rt_device_scratch(rt, D_GROUPTABLES, (size_t)HAP_GROUP_TABLE_BYTES * frags_per_frame * live);
-    if (stage_in_bytes)
-        tex_stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_TEX_STAGE, stage_in_bytes);
-    if (stage_out_bytes)
-        out_stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_FRAME_STAGE, stage_out_bytes);
-    if (!hframes || !dframes || (placed && !dacc) || (any_snappy && !dslots) || !dfragsizes || !dcopies || !dpack || (any_half_tiles && !dgrouptables) ||
-        (stage_in_bytes && !tex_stage) || (stage_out_bytes && !out_stage)) {
-        free(live_index); free(stage_off_in); free(stage_off_out);
-        for (f = 0; f < frame_count; f++)
-            if (results[f] == HapResult_No_Error)
-                results[f] = HapResult_Internal_Error;
-        return HapResult_Internal_Error;
-    }
-
-    /* descriptors (+ host->device staging of textures) */
-    {
-        unsigned k, rc = 0;
-        for (k = 0; k < live; k++) {
-            HapGpuFrameEnc *fe = &hframes[k];
-            size_t in_cursor = 0;
-            f = live_index[k];
-            memset(fe, 0, sizeof(*fe));
-            fe->dst = (uint64_t)(uintptr_t)(stage_off_out[f] ? out_stage + (stage_off_out[f] - 1) : (uint8_t *)outputs[f]);
-            fe->dst_cap = output_bytes[f];
-            fe->tex_count = count;
-            fe->outer_header_len = outer_header;
-            fe->status = HapResult_Internal_Error;   /* overwritten by the pack kernel */
-            if (placed)
-                fe->chunk_acc = (uint64_t)(uintptr_t)(dacc + (size_t)k * chunks_per_frame);
-            if (fused_mask) {
-                fe->rgba = job->host_table[f];
-                fe->rgba_row_bytes = (uint32_t)job->source.row_bytes;
-                fe->rgba_blocks_x = job->source.width / 4u;
-                fe->rgba_blocks_x_inv = HAPGPU_DIV_INV(job->source.width / 4u);
-            }
-            for (i = 0; i < count; i++) {
-                HapGpuTexEnc *te = &fe->tex[i];
-                const void *src = inputs[(size_t)f * count + i];
-                if (stage_off_in[f] && !is_dev(ctx, src)) {
-                    uint8_t *d = tex_stage + (stage_off_in[f] - 1) + in_cursor;
-                    rc |= (unsigned)hapgpu_rt_h2d(rt, d, src, g[i].bytes);
-                    src = d;
-                }
-                in_cursor += align_up(g[i].bytes, 256);
-                te->src = (uint64_t)(uintptr_t)src;
-                te->bytes = (uint32_t)g[i].bytes;
-                te->format_nibble = g[i].nibble;
-                te->compressor = g[i].compressor;
-                te->chunk_count = g[i].chunk_count;
-                te->chunk_bytes = g[i].chunk_bytes;
-                te->header_len = g[i].header_len;
-                te->frags_per_chunk = g[i].fpc;
-                te->frags_per_chunk_inv = HAPGPU_DIV_INV(g[i].fpc ? g[i].fpc : 1u);
-                te->frag_first = k * frags_per_frame + (i ? g[0].chunk_count * g[0].fpc : 0u);
-                te->emit_index = (flags & HAPGPU_ENCODE_FRAGMENT_INDEX) ? 1u : 0u;
-                /* 8 KiB fragments keep hash matches within 3 KiB so that the decoder can halve its ring -- except for
-                   small textures, whose block rows are short enough for the row above to lie inside the fragment
-                   (rows of up to ~5 KiB: below 1080p for 16-byte blocks, below 4K for 8-byte blocks) */
-                {
-                    const int small_blocks = hapf_block_bytes(g[i].format) == 8u;
-                    /* (field streams with their group table are decoded over a whole-fragment ring: no window) */
-                    const int windowed = frag_log2 == 13u && !g[i].half_tiles &&
-                                         g[i].bytes >= (small_blocks ? ((size_t)2u << 20) : ((size_t)1u << 20));
-                    te->reserved = g[i].gran_log2 | (windowed ? (HAP_FRAGMENT_WINDOW_256 << 8) : 0u) | (g[i].field_period << 16) |
-                                   (g[i].half_tiles << 20) | (fused[i] << 24) | ((i == 0u ? placed : 0u) << 27);
-                }
-            }
-        }
-        {
-            /* The launches of this call as one sequence.  With every buffer in device memory (nothing staged) nothing
-               in it depends on the buffers themselves -- their addresses are in the tables copied from pinned memory --
-               so the sequence is recorded once per geometry as a HIP graph and replayed with one launch. */
-            uint64_t key = 0xCBF29CE484222325ull;
-            int graph = 2;
-            unsigned launch_rc = 0;
-#define HAPB_MIX(v) (key = (key ^ (uint64_t)(v)) * 0x100000001B3ull)
-            if (stage_in_bytes == 0 && stage_out_bytes == 0 && inputs_are_device != 2 && !smaller && frag_log2 == 13u) {
-                HAPB_MIX(live); HAPB_MIX(count); HAPB_MIX(flags); HAPB_MIX(frag_log2); HAPB_MIX(ctx->byte_granular);
-                HAPB_MIX(ctx->position_lanes); HAPB_MIX(ctx->rgtc1_fields); HAPB_MIX(ctx->no_half_tiles); HAPB_MIX(fused_mask); HAPB_MIX(placed);
-                for (i = 0; i < count; i++) {
-                    HAPB_MIX(g[i].format); HAPB_MIX(g[i].compressor); HAPB_MIX(g[i].chunk_count); HAPB_MIX(g[i].bytes);
-                }
-                if (job) {
-                    const HapbSource *const src = &job->source;
-                    HAPB_MIX(job->frame_count); HAPB_MIX(src->width); HAPB_MIX(src->height); HAPB_MIX(src->row_bytes);
-                    HAPB_MIX(job->wide + 2); HAPB_MIX(src->picture_kind);
-                    if (src->planes) {
-                        /* (scale and bias are kernel arguments: part of what a recording holds) */
-                        HAPB_MIX(src->planes->channels + 8u); HAPB_MIX(src->planes->element); HAPB_MIX(src->planes->plane_bytes);
-                        for (i = 0; i < src->planes->channels; i++) {
-                            uint32_t bits[2];
-                            memcpy(&bits[0], &job->plane_scale[i], 4);
-                            memcpy(&bits[1], &job->plane_bias[i], 4);
-                            HAPB_MIX(bits[0]); HAPB_MIX(bits[1]);
-                        }
-                    }
-                    if (src->video) {
-                        /* (the pitch, the matrix and the range are kernel arguments too) */
-                        HAPB_MIX(16u); HAPB_MIX(src->video->chroma_row_bytes); HAPB_MIX(src->video->matrix); HAPB_MIX(src->video->range);
-                    }
-                }
-                graph = hapgpu_rt_graph_begin(rt, key);
-            }
-#undef HAPB_MIX
-            /* (a recording that cannot be ended, instantiated or launched has run nothing: graphs are switched off for
-               this context and the same launches are issued once more, plainly) */
-            while (graph != 1) {
-                if (job) {
-                    const HapbSource *const src = &job->source;
-                    launch_rc |= (unsigned)hapgpu_rt_h2d(rt, job->device_table, job->host_table,
-                                                         sizeof(uint64_t) * (size_t)job_table_columns(job) * job->frame_count);
-                    /* Hap Q Alpha: both textures from one pass over the RGBA (64 + 16 + 8 bytes per block);
-                       else one launch per texture that the second stage does not make itself.  (A batch takes at most
-                       65535 block rows.) */
-                    const int pair = job->count == 2 && job->formats[0] == HapTextureFormat_YCoCg_DXT5 &&
-                                     job->formats[1] == HapTextureFormat_A_RGTC1;
-                    for (i = 0; i < (pair ? 1u : job->count); i++)
-                        if (pair || !fused[i]) {
-                            const uint64_t *dt = job->device_table;
-                            /* (video pictures: one texture a frame, and the third column holds their CbCr planes) */
-                            const HapGpuPictureTable t = {{dt, dt + (size_t)(1u + i) * job->frame_count,
-                                                           pair || src->video ? dt + 2u * (size_t)job->frame_count : NULL}, {0u, 0u, 0u}};
-                            launch_rc |= src->height / 4u > 65535u ? 1u :
-                                         src->video ?
-                                         (unsigned)hapgpu_k_block_encode_video(rt, &t, job->frame_count, src->width, src->height,
-                                                                               job->formats[i], refine, src->row_bytes,
-                                                                               src->video->chroma_row_bytes, src->video->matrix,
-                                                                               src->video->range) :
-                                         src->planes ?
-                                         (unsigned)hapgpu_k_block_encode_planes(rt, &t, job->frame_count, src->width, src->height,
-                                                                                job->formats[i], (unsigned)pair | refine, src->planes->channels,
-                                                                                src->planes->element, src->planes->plane_bytes,
-                                                                                src->row_bytes, job->plane_scale, job->plane_bias) :
-                                         (unsigned)hapgpu_k_block_encode(rt, &t, job->frame_count, src->width, src->height,
-                                                                         src->row_bytes, job->formats[i], (unsigned)pair | refine, job->wide,
-                                                                         src->picture_kind);
-                        }
-                }
-                launch_rc |= (unsigned)hapgpu_rt_h2d(rt, dframes, hframes, sizeof(HapGpuFrameEnc) * live);
-                if (placed) {
-                    launch_rc |= (unsigned)hapgpu_rt_zero(rt, dacc, sizeof(uint64_t) * (size_t)chunks_per_frame * live);
-                    launch_rc |= (unsigned)hapgpu_rt_zero(rt, dfragsizes, sizeof(uint32_t) * (size_t)frags_per_frame * live);
-                }
-                if (any_snappy)
-                    launch_rc |= (unsigned)hapgpu_k_snappy_compress(rt, dframes, live, max_frags_per_tex, frag_log2, dslots, slot_stride,
-                                                                    dfragsizes, dgrouptables, gran_mask | (count << 8) | (fused_mask << 16));   /* bits 8..15: textures per frame */
-                launch_rc |= (unsigned)hapgpu_k_frame_pack(rt, dframes, live, frag_log2, dslots, slot_stride, dfragsizes, dgrouptables,
-                                                           dcopies, frags_per_frame * live, chunks_per_frame, max_chunks_per_tex, count, dpack);
-                /* (placed fragments -- single-texture frames -- and their group tables are where they belong: nothing to
-                   gather.  A frame reported as not placed is encoded again as a whole.) */
-                if (!(placed && count == 1u))
-                    launch_rc |= (unsigned)hapgpu_k_frame_gather(rt, dcopies, (frags_per_frame + chunks_per_frame) * live);
-                launch_rc |= (unsigned)hapgpu_rt_d2h(rt, hframes, dframes, sizeof(HapGpuFrameEnc) * live);
-                if (graph == 0) {
-                    /* (a recording can also be invalidated from outside -- another thread of the process synchronising the
-                       device while it runs: then the launches themselves report errors.  Either way nothing has run.) */
-                    const int ended = hapgpu_rt_graph_end(rt, key, launch_rc != 0);
-                    if (ended != 0 || launch_rc != 0) {
-                        hapgpu_rt_graphs_disable(rt);
-                        graph = 2;
-                        launch_rc = 0;
-                        continue;
-                    }
-                }
-                break;
-            }
-            rc |= launch_rc;
-        }
-        /* everything the call launches is on the stream: the rest -- waiting, reading the results, the second pass over
-           frames that were not placed -- is hapb_encode_complete's, at once or (HapGpuEncodeFramesRGBABegin / ...Finish)
-           when the client asks for the results */
-        {
-            HapbEncodePending *pd = (HapbEncodePending *)calloc(1, sizeof(*pd));
-            const size_t n_in = (size_t)frame_count * count;
-            if (pd) {
-                pd->inputs = (const void **)malloc(sizeof(void *) * n_in);
-                pd->outputs = (void **)malloc(sizeof(void *) * frame_count);
-                pd->output_bytes = (unsigned long *)malloc(sizeof(unsigned long) * frame_count);
-            }
-            if (!pd || !pd->inputs || !pd->outputs || !pd->output_bytes) {
-                if (pd) { free(pd->inputs); free(pd->outputs); free(pd->output_bytes); }
-                free(pd);
-                hapgpu_rt_sync(rt);
-                for (k = 0; k < live; k++)
-                    results[live_index[k]] = HapResult_Internal_Error;
-                free(live_index); free(stage_off_in); free(stage_off_out);
-                return HapResult_Internal_Error;
-            }
-            memcpy(pd->inputs, inputs, sizeof(void *) * n_in);
-            memcpy(pd->outputs, outputs, sizeof(void *) * frame_count);
-            memcpy(pd->output_bytes, output_bytes, sizeof(unsigned long) * frame_count);
-            for (i = 0; i < count; i++) {
-                pd->input_bytes[i] = input_bytes[i];
-                pd->formats[i] = formats[i];
-                pd->compressors[i] = compressors[i];
-                pd->chunk_counts[i] = chunk_counts[i];
-            }
-            pd->frame_count = frame_count;
-            pd->count = count;
-            pd->flags = flags;
-            pd->inputs_are_device = inputs_are_device;
-            pd->output_used = output_used;
-            pd->results = results;
-            pd->live = live;
-            pd->placed = placed;
-            pd->first_error = first_error;
-            pd->launch_rc = rc;
-            pd->live_index = live_index;
-            pd->stage_off_out = stage_off_out;
-            pd->hframes = hframes;
-            pd->out_stage = out_stage;
-            if (job) {
-                pd->job = *job;
-                pd->has_job = 1;
-                if (job->source.planes) {
-                    /* (the caller's description need not outlive the first half either) */
-                    pd->planes = *job->source.planes;
-                    pd->planes.scale = pd->planes.bias = NULL;
-                    pd->job.source.planes = &pd->planes;
-                }
-                if (job->source.video) {
-                    /* (... nor need its array of CbCr planes: their addresses are in the job's table) */
-                    pd->video = *job->source.video;
-                    pd->video.chroma = NULL;
-                    pd->job.source.video = &pd->video;
-                }
-            }
-            free(stage_off_in);
-            if (a->defer) {
-                ctx->pending_encode = pd;
-                return first_error;
-            }
-            return hapb_encode_complete(ctx, pd);
-        }
-    }
+    return hapb_encode_complete(ctx, pd);
 }
 
 /* The second half of hapb_encode: waits for the launches, reads the per-frame results back, copies staged frames to the
@@ -648,7 +594,7 @@ unsigned hapb_encode_complete(HapGpuContext *ctx, HapbEncodePending *pd)
             HapGpuFrameEnc *fe = &pd->hframes[k];
             f = pd->live_index[k];
             results[f] = fe->status;
-            if (fe->status == HAPGPU_STATUS_NOT_PLACED && (fe->reserved & 1u)) {
+            if (fe->status == HAPGPU_STATUS_NOT_PLACED && (fe->notes & HAPGPU_FRAME_NOTE_WAVE_TIMED_OUT)) {
                 /* a wavefront gave up waiting for its predecessors (snappy_compress_blocks.hip): something keeps the
                    grid from advancing in order -- this context gathers from now on */
                 ctx->placement_timeouts += 1u;
@@ -748,18 +694,14 @@ unsigned hapb_encode_complete(HapGpuContext *ctx, HapbEncodePending *pd)
         }
     }
 done:
-    free(pd->live_index); free(pd->stage_off_out);
-    free(pd->inputs); free(pd->outputs); free(pd->output_bytes);
-    free(pd);
+    encode_pending_free(pd);
     return first_error;
 }
 
 void hapb_encode_abandon(HapGpuContext *ctx, HapbEncodePending *pd)
 {
     (void)hapgpu_rt_sync(ctx->rt);
-    free(pd->live_index); free(pd->stage_off_out);
-    free(pd->inputs); free(pd->outputs); free(pd->output_bytes);
-    free(pd);
+    encode_pending_free(pd);
 }
 
 /* The size of a texel belongs to the pictures (HAPGPU_PICTURE_TEXEL_BYTES of their kind), not to the texture format:
@@ -837,15 +779,6 @@ static unsigned source_align_mask(const HapbSource *source)
     if (source->planes)
         return 4u * (unsigned)plane_element_bytes(source->planes->element) - 1u;
     return source->picture_kind == HAPGPU_PICTURE_RGBA16F ? 15u : 3u;
-}
-
-/* the whole-call answer: every result set (a NULL results: none), `code` returned */
-static unsigned answer_all(unsigned *results, unsigned frame_count, unsigned code)
-{
-    unsigned f;
-    for (f = 0; results && f < frame_count; f++)
-        results[f] = code;
-    return code;
 }
 
 unsigned hapb_source_texture(HapGpuContext *ctx, const HapbSource *source, const void *picture, unsigned format,
@@ -1090,10 +1023,10 @@ static unsigned field_layout_of_format(unsigned format)
 {
     switch (format) {
     case HapTextureFormat_RGBA_DXT5:
-    case HapTextureFormat_YCoCg_DXT5: return 4u;
-    case HapTextureFormat_RGB_DXT1: return 2u;
-    case HapTextureFormat_A_RGTC1: return 6u;
-    default: return 0u;
+    case HapTextureFormat_YCoCg_DXT5: return HAPGPU_LAYOUT_2_6_4_4;
+    case HapTextureFormat_RGB_DXT1: return HAPGPU_LAYOUT_4_4;
+    case HapTextureFormat_A_RGTC1: return HAPGPU_LAYOUT_2_6;
+    default: return HAPGPU_LAYOUT_NONE;
     }
 }
 
@@ -1723,7 +1656,7 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
                     if (p->frag_tiles_offset && p->frag_fields && !(flags & HAPGPU_DECODE_IGNORE_HALF_TILES)) {
                         job->fields_period = p->frag_fields;
                         job->group_tables = (uint64_t)(uintptr_t)(frame_dev + p->frag_tiles_offset);
-                        frag_kinds |= p->frag_fields == 4u ? 0x100u : p->frag_fields == 2u ? 0x200u : p->frag_fields == 8u ? 0x800u : 0x400u;
+                        frag_kinds |= p->frag_fields == HAPGPU_LAYOUT_2_6_4_4 ? 0x100u : p->frag_fields == HAPGPU_LAYOUT_4_4 ? 0x200u : p->frag_fields == HAPGPU_LAYOUT_4_4_4_4 ? 0x800u : 0x400u;
                     } else if (p->frag_log2 == 13u && p->frag_window256 != 0 && p->frag_window256 <= HAP_FRAGMENT_WINDOW_256)
                         frag_kinds |= 16u << p->frag_gran_log2;
                     else
@@ -1734,7 +1667,7 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
                     job->fields_period = layout;
                     job->group_tables = (uint64_t)(uintptr_t)dguess;
                     job->reserved |= 1u << 16;
-                    frag_kinds |= layout == 4u ? 0x100u : layout == 2u ? 0x200u : layout == 8u ? 0x800u : 0x400u;
+                    frag_kinds |= layout == HAPGPU_LAYOUT_2_6_4_4 ? 0x100u : layout == HAPGPU_LAYOUT_4_4 ? 0x200u : layout == HAPGPU_LAYOUT_4_4_4_4 ? 0x800u : 0x400u;
                 }
                 if (p->chunk_count > 0)
                     memcpy(hchunks + chunk_cursor, p->chunks, sizeof(HapGpuChunkIn) * (size_t)p->chunk_count);
@@ -1762,7 +1695,7 @@ unsigned hapb_decode(HapGpuContext *ctx, unsigned frame_count, const void *const
                 job->group_tables = (uint64_t)(uintptr_t)dguess;
                 job->reserved |= 1u << 16;
                 /* 0x1000: units for the block-per-lane decoder may appear among the scan's pieces as well */
-                frag_kinds |= (layout == 4u ? 0x100u : layout == 2u ? 0x200u : 0x400u) | 0x1000u;
+                frag_kinds |= (layout == HAPGPU_LAYOUT_2_6_4_4 ? 0x100u : layout == HAPGPU_LAYOUT_4_4 ? 0x200u : 0x400u) | 0x1000u;
             }
             unit_cursor += units;
         }

@@ -175,6 +175,33 @@ unsigned hapf_limit_chunk_count(size_t bytes, unsigned format, unsigned chunks)
     return chunks;
 }
 
+/* one chunk per 8 KiB fragment (HapGpuFineChunkCount, HAPGPU_ENCODE_FINE_CHUNKS) */
+unsigned hapf_fine_chunk_count(unsigned long bytes, unsigned format)
+{
+    unsigned long want;
+    if (bytes == 0 || bytes > 0xFFFFFFFFul || hapf_nibble_from_format(format) == 0)
+        return 0;
+    want = (bytes + 8191ul) / 8192ul;
+    if (bytes < 16ul)
+        return 1;
+    {
+        /* The SMALLEST divisor of the block count that is at least bytes / 8 KiB: chunks of at most one fragment (ADVICE r05:
+           walking DOWN to a divisor gave 1080p DXT5 240 chunks of 8640 bytes -- two fragments each, which the table-less
+           road into the block-per-lane decoder does not take).  Where the block count has no divisor up to four times that
+           many chunks (a prime number of blocks), the largest one below it, as for any chunk count (hap.c:277-300). */
+        const unsigned long blocks = bytes / hapf_block_bytes(format);
+        unsigned long c, top = want * 4ul;
+        if (top > 3355431ul)
+            top = 3355431ul;
+        if (top > blocks)
+            top = blocks;
+        for (c = want; c <= top; c++)
+            if (c != 0ul && blocks % c == 0ul)
+                return (unsigned)c;
+    }
+    return hapf_limit_chunk_count(bytes, format, want > 3355431ul ? 3355431u : (unsigned)want);
+}
+
 /* reference hap.c:302-322 */
 size_t hapf_texture_bound(size_t bytes, unsigned format, unsigned compressor, unsigned chunks)
 {

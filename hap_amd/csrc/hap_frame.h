@@ -52,7 +52,7 @@ typedef struct hapf_texture_plan {
     uint32_t frag_log2;
     uint32_t frag_gran_log2;/* 1: the table promises 16-bit granular element streams */
     uint32_t frag_window256;/* copy offsets never exceed this many 256-byte units (0: no promise) */
-    uint32_t frag_fields;   /* table version 3 ("field streams"): block layout, 4 = [2,6,4,4], 2 = [4,4], 6 = [2,6], 8 = [4,4,4,4]; else 0 */
+    uint32_t frag_fields;   /* table version 3 ("field streams"): block layout, HAPGPU_LAYOUT_* (hapgpu_abi.h); else 0 */
     uint64_t frag_tiles_offset; /* frame offset of the group tables (96 bytes per fragment entry), 0 if absent */
     unsigned unit_count;    /* filled by the batch layer: GPU work units reserved for this texture */
 } hapf_texture_plan;
@@ -67,6 +67,8 @@ size_t hapf_block_bytes(unsigned format);     /* 8: RGB_DXT1, A_RGTC1; 16: every
 size_t hapf_snappy_bound(size_t n);
 size_t hapf_instructions_length(unsigned chunks);
 unsigned hapf_limit_chunk_count(size_t bytes, unsigned format, unsigned chunks);
+/* the chunk count HAPGPU_ENCODE_FINE_CHUNKS gives a texture: 8 KiB of texture per chunk where the block count divides so */
+unsigned hapf_fine_chunk_count(unsigned long bytes, unsigned format);
 size_t hapf_texture_bound(size_t bytes, unsigned format, unsigned compressor, unsigned chunks);
 
 /* Locates texture `index` (reference hap.c:932-991). Returns a HapResult. */

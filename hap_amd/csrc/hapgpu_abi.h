@@ -71,23 +71,79 @@ typedef struct HapGpuTexEnc {
     uint32_t frags_per_chunk;
     uint32_t frag_first;     /* global index of this texture's first fragment */
     uint32_t emit_index;     /* write the fragment-size section */
-    uint32_t reserved;       /* bit 20: "field stream": no element crosses a 128-byte half-tile and the compressor
-                                writes every fragment's group table (fragment table version 4);
-                                bits 16..19: fields per block for the field-per-lane compressor (0: position per lane,
-                                2: RGTC1 layout, 4: DXT5 / YCoCg-DXT5, 10: DXT1, 12: opaque 16-byte blocks); bits 8..15: match window in 256-byte units (0 = whole fragment); bits 0..7:
-                                granularity_log2 of the element stream: 0 = bytes, 1 = every position, offset
-                                and length even (lets the decoder move 16 bits per lane);
-                                bits 24..26: 0 = the texture is at src; else the block-per-lane compressor makes it from
-                                the frame's RGBA picture (1 DXT1, 2 DXT5, 3 scaled YCoCg-DXT5, 4 RGTC1 from alpha) and
-                                writes it to src on the way;
-                                bit 27: "placed": the block-per-lane compressor writes every fragment's stream at its final
-                                place in the frame (the sizes of everything before it: frag_sizes entries with
-                                HAPGPU_FRAG_PUBLISHED set, chunk_acc words of the chunks before) instead of a slot, on the
-                                assumption that every chunk shrinks; the pack kernel reports HAPGPU_STATUS_NOT_PLACED
-                                for a frame where one did not (or a wavefront gave up waiting), and the host encodes that
-                                frame again through slots.  First texture of a frame only. */
+    uint32_t control;        /* what the host has decided for the compressor and the pack kernel: HAPGPU_CONTROL_* below */
     uint32_t frags_per_chunk_inv; /* HAPGPU_DIV_INV(frags_per_chunk) */
 } HapGpuTexEnc;
+
+/* The field layouts of the block compressor, by the value the file format gives them (the fragment table's byte 6,
+   high nibble; hapf_texture_plan.frag_fields; HapGpuDecodeJob.fields_period; the kernels' LAYOUT): the one numbering. */
+enum {
+    HAPGPU_LAYOUT_NONE = 0,        /* a position per lane (snappy_compress.hip) */
+    HAPGPU_LAYOUT_4_4 = 2,         /* DXT1: 8-byte blocks of [4, 4] */
+    HAPGPU_LAYOUT_2_6_4_4 = 4,     /* DXT5 / YCoCg-DXT5: 16-byte blocks of [2, 6, 4, 4] */
+    HAPGPU_LAYOUT_2_6 = 6,         /* RGTC1: 8-byte blocks of [2, 6] */
+    HAPGPU_LAYOUT_4_4_4_4 = 8      /* opaque 16-byte blocks (BC7, BC6H) as four dwords */
+};
+/* What the block compressor makes from the frame's RGBA8 picture itself instead of reading it at src (and writes to src
+   on the way): bc_encode_core.hpp's kFmt* + 1 (snappy_compress_blocks.hip asserts it). */
+enum {
+    HAPGPU_FUSED_NONE = 0,         /* the texture is at src */
+    HAPGPU_FUSED_DXT1 = 1,
+    HAPGPU_FUSED_DXT5 = 2,
+    HAPGPU_FUSED_YCOCG = 3,        /* scaled YCoCg-DXT5 */
+    HAPGPU_FUSED_RGTC1 = 4         /* from alpha */
+};
+
+/* HapGpuTexEnc.control, field by field.  Nobody shifts or masks the word but the functions below. */
+#define HAPGPU_CONTROL_GRANULARITY_SHIFT 0u   /* granularity_log2 of the element stream: 0 = bytes, 1 = every position, offset
+                                                 and length even (lets the decoder move 16 bits per lane), 2 = multiples of 4 */
+#define HAPGPU_CONTROL_GRANULARITY_MASK 0xFFu
+#define HAPGPU_CONTROL_WINDOW_SHIFT 8u        /* match window in 256-byte units (0 = whole fragment) */
+#define HAPGPU_CONTROL_WINDOW_MASK 0xFFu
+#define HAPGPU_CONTROL_LAYOUT_SHIFT 16u       /* HAPGPU_LAYOUT_* */
+#define HAPGPU_CONTROL_LAYOUT_MASK 0xFu
+#define HAPGPU_CONTROL_HALF_TILES_SHIFT 20u   /* "field stream": no element crosses a 128-byte half-tile and the compressor
+                                                 writes every fragment's group table (fragment table version 4) */
+#define HAPGPU_CONTROL_HALF_TILES_MASK 1u
+#define HAPGPU_CONTROL_FUSED_SHIFT 24u        /* HAPGPU_FUSED_* */
+#define HAPGPU_CONTROL_FUSED_MASK 7u
+#define HAPGPU_CONTROL_PLACED_SHIFT 27u       /* "placed": the block-per-lane compressor writes every fragment's stream at its
+                                                 final place in the frame (the sizes of everything before it: frag_sizes entries
+                                                 with HAPGPU_FRAG_PUBLISHED set, chunk_acc words of the chunks before) instead of
+                                                 a slot, on the assumption that every chunk shrinks; the pack kernel reports
+                                                 HAPGPU_STATUS_NOT_PLACED for a frame where one did not (or a wavefront gave up
+                                                 waiting), and the host encodes that frame again through slots.  First texture
+                                                 of a frame only. */
+#define HAPGPU_CONTROL_PLACED_MASK 1u
+/* (const: values of their arguments alone -- a kernel's single combined test may hold them) */
+#ifdef __HIP__
+#define HAPGPU_ABI_INLINE static inline __attribute__((const)) __attribute__((host)) __attribute__((device))
+#else
+#define HAPGPU_ABI_INLINE static inline __attribute__((const))
+#endif
+#define HAPGPU_CONTROL_FIELD(control, NAME) (((control) >> HAPGPU_CONTROL_##NAME##_SHIFT) & HAPGPU_CONTROL_##NAME##_MASK)
+HAPGPU_ABI_INLINE uint32_t hapgpu_control(unsigned granularity_log2, unsigned window_256, unsigned layout, unsigned half_tiles,
+                                          unsigned fused, unsigned placed)
+{
+    return (uint32_t)(granularity_log2 << HAPGPU_CONTROL_GRANULARITY_SHIFT | window_256 << HAPGPU_CONTROL_WINDOW_SHIFT |
+                      layout << HAPGPU_CONTROL_LAYOUT_SHIFT | half_tiles << HAPGPU_CONTROL_HALF_TILES_SHIFT |
+                      fused << HAPGPU_CONTROL_FUSED_SHIFT | placed << HAPGPU_CONTROL_PLACED_SHIFT);
+}
+HAPGPU_ABI_INLINE unsigned hapgpu_control_granularity_log2(uint32_t control) { return HAPGPU_CONTROL_FIELD(control, GRANULARITY); }
+HAPGPU_ABI_INLINE unsigned hapgpu_control_window_256(uint32_t control) { return HAPGPU_CONTROL_FIELD(control, WINDOW); }
+HAPGPU_ABI_INLINE unsigned hapgpu_control_layout(uint32_t control) { return HAPGPU_CONTROL_FIELD(control, LAYOUT); }
+HAPGPU_ABI_INLINE unsigned hapgpu_control_half_tiles(uint32_t control) { return HAPGPU_CONTROL_FIELD(control, HALF_TILES); }
+HAPGPU_ABI_INLINE unsigned hapgpu_control_fused(uint32_t control) { return HAPGPU_CONTROL_FIELD(control, FUSED); }
+HAPGPU_ABI_INLINE unsigned hapgpu_control_placed(uint32_t control) { return HAPGPU_CONTROL_FIELD(control, PLACED); }
+/* 1: a texture of the position-per-lane compressor's kernel for granularity_log2 (no layout, that granularity): both
+   fields in one comparison, which is that kernel's test */
+HAPGPU_ABI_INLINE int hapgpu_control_is_positions(uint32_t control, unsigned granularity_log2)
+{
+    return (control & (HAPGPU_CONTROL_GRANULARITY_MASK << HAPGPU_CONTROL_GRANULARITY_SHIFT |
+                       HAPGPU_CONTROL_LAYOUT_MASK << HAPGPU_CONTROL_LAYOUT_SHIFT)) ==
+           (granularity_log2 << HAPGPU_CONTROL_GRANULARITY_SHIFT | (unsigned)HAPGPU_LAYOUT_NONE << HAPGPU_CONTROL_LAYOUT_SHIFT);
+}
+
 /* what the compressor's wavefronts divide by without dividing: floor(x inv / 2^32) is x / d or one short of it for
    every 32-bit x (d >= 1) */
 #define HAPGPU_DIV_INV(d) (0xFFFFFFFFu / (uint32_t)(d))
@@ -104,17 +160,25 @@ typedef struct HapGpuFrameEnc {
     /* results */
     uint64_t bytes_used;
     uint32_t status;
-    uint32_t reserved;
-    /* textures whose reserved bits 24..26 are set are made from this RGBA8 picture by the second stage itself */
+    uint32_t notes;          /* HAPGPU_FRAME_NOTE_*: what the kernels tell the host beside the status (zero before the launch) */
+    /* textures whose control word names a HAPGPU_FUSED_* kind are made from this RGBA8 picture by the second stage itself */
     uint64_t rgba;
     uint32_t rgba_row_bytes; /* (the picture is smaller than 4 GiB) */
     uint32_t rgba_blocks_x;  /* width / 4 */
     uint32_t rgba_blocks_x_inv; /* HAPGPU_DIV_INV(rgba_blocks_x) */
     uint32_t reserved2;
-    /* textures whose reserved bit 27 is set: one 64-bit word per chunk of the frame (zero before the launch), in which
-       the compressor's wavefronts add up fragments << 32 | bytes as they learn their sizes */
+    /* placed textures: one 64-bit word per chunk of the frame (zero before the launch), in which the compressor's
+       wavefronts add up fragments << 32 | bytes as they learn their sizes */
     uint64_t chunk_acc;
 } HapGpuFrameEnc;
+/* a wavefront of a placed texture gave up waiting for its predecessors' sizes (snappy_compress_blocks.hip): the frame
+   comes back HAPGPU_STATUS_NOT_PLACED for that reason, not for a chunk that did not shrink */
+#define HAPGPU_FRAME_NOTE_WAVE_TIMED_OUT 1u
+
+/* the layouts that hapgpu_abi.h promises the device: pinned (C99 has no static assertion: an array of negative size) */
+typedef char hapgpu_abi_tex_enc_is_56_bytes[sizeof(HapGpuTexEnc) == 56 ? 1 : -1];
+typedef char hapgpu_abi_frame_enc_is_184_bytes[sizeof(HapGpuFrameEnc) == 184 ? 1 : -1];
+typedef char hapgpu_abi_control_is_at_44[offsetof(HapGpuTexEnc, control) == 44 ? 1 : -1];
 
 /* [device] one byte-range move of the gather pass (one per fragment) */
 typedef struct HapGpuCopyEntry {
@@ -171,7 +235,7 @@ typedef struct HapGpuDecodeJob {
     /* results */
     uint64_t bytes_used;
     uint32_t status;         /* HapResult or HAPGPU_STATUS_* */
-    uint32_t fields_period;  /* 4 / 2 / 6 / 8: the table is version 3 and promises [2,6,4,4] / [4,4] / [2,6] / [4,4,4,4] field streams; 0 otherwise */
+    uint32_t fields_period;  /* HAPGPU_LAYOUT_*: the table is version 3 and promises field streams of that layout; NONE otherwise */
     uint64_t group_tables;     /* device address of the group tables inside the frame (96 bytes per fragment entry), or 0 */
 } HapGpuDecodeJob;
 
@@ -491,11 +555,20 @@ typedef struct HapGpuTranscodeTable {
 int hapgpu_k_block_transcode(hapgpu_rt *rt, const HapGpuTranscodeTable *table, unsigned pictures, unsigned src_format,
                              int with_alpha, unsigned width, unsigned height, unsigned scale_log2, unsigned dst_format,
                              int dst_with_alpha);
-/* group_tables: HAP_GROUP_TABLE_BYTES bytes per fragment (same indexing as frag_sizes), written for textures whose reserved bit 20 is set */
+/* Which compressor kernels a call's textures need: sets over the values their control words hold, bit v for value v.  A
+   texture is in exactly one set: fused (it is made on the way), else layouts (a layout other than NONE), else
+   granularities (a position per lane). */
+typedef struct HapGpuCompressKinds {
+    unsigned granularities;  /* bit g: some position-per-lane texture has granularity_log2 g (0..2) */
+    unsigned layouts;        /* bit HAPGPU_LAYOUT_*: some texture that exists has that field layout */
+    unsigned fused;          /* bit HAPGPU_FUSED_*: some texture is made from its frame's picture by the block compressor */
+    unsigned textures;       /* textures per frame */
+} HapGpuCompressKinds;
+/* group_tables: HAP_GROUP_TABLE_BYTES bytes per fragment (same indexing as frag_sizes), written for textures with half-tiles */
 int hapgpu_k_snappy_compress(hapgpu_rt *rt, const HapGpuFrameEnc *frames, unsigned frame_count,
                              unsigned max_frags_per_texture, unsigned frag_log2,
                              void *slots, unsigned slot_stride, uint32_t *frag_sizes, uint8_t *group_tables,
-                             unsigned granularity_mask /* bit g (0..2) set: some position-per-lane texture has granularity_log2 == g; bit 4 / 5 / 6 / 7: some texture uses the field-per-lane kernel ([2,6] / [2,6,4,4] / [4,4] / [4,4,4,4] fields per block); bits 8..: textures per frame */);
+                             const HapGpuCompressKinds *kinds);
 /* copies: one entry per fragment, then (from index extra_first) chunks_per_frame entries per frame for the
  * group tables of field streams */
 int hapgpu_k_frame_pack(hapgpu_rt *rt, HapGpuFrameEnc *frames, unsigned frame_count,

@@ -218,8 +218,10 @@ __global__ __launch_bounds__(64 * kWgWaves) void snappy_compress_wg_kernel(const
     const unsigned tex_count = frames[blockIdx.z].tex_count;
     const unsigned x = blockIdx.x;
     // (one combined test, no short-circuit: every field is requested before the first wait)
-    if ((blockIdx.y >= tex_count) | (tex.compressor != 1u) | ((1u << (tex.reserved & 0xFFu)) != GRAN) |
-        (((tex.reserved >> 16) & 0xFu) != 0u) |        // field-per-lane textures belong to snappy_compress_blocks.hip
+    // (field-per-lane textures belong to snappy_compress_blocks.hip)
+    constexpr unsigned kGranLog2 = GRAN == 1u ? 0u : GRAN == 2u ? 1u : 2u;
+    static_assert(GRAN == 1u << kGranLog2, "GRAN: 1, 2 or 4 bytes");
+    if ((blockIdx.y >= tex_count) | (tex.compressor != 1u) | !hapgpu_control_is_positions(tex.control, kGranLog2) |
         (x >= tex.chunk_count * tex.frags_per_chunk) | (tex.src == 0) | (tex.chunk_bytes == 0))
         return;
     const unsigned chunk = x / tex.frags_per_chunk, j = x - chunk * tex.frags_per_chunk;
@@ -227,7 +229,7 @@ __global__ __launch_bounds__(64 * kWgWaves) void snappy_compress_wg_kernel(const
     const unsigned n = min(frag_bytes, tex.chunk_bytes - begin);
     const uint8_t *src = (const uint8_t *)tex.src + (size_t)chunk * tex.chunk_bytes + begin;
     const unsigned f = tex.frag_first + x;
-    const unsigned window = (tex.reserved >> 8) ? (tex.reserved >> 8) * 256u : 0xFFFFFFFFu;
+    const unsigned window = hapgpu_control_window_256(tex.control) ? hapgpu_control_window_256(tex.control) * 256u : 0xFFFFFFFFu;
     uint8_t *out = slots + (size_t)f * slot_stride;
 
     if (((uintptr_t)src & 15u) == 0) {
@@ -507,9 +509,9 @@ void hapgpu_prepare_snappy_compress(hapgpu_launch_settings *s)
 extern "C" int hapgpu_k_snappy_compress(hapgpu_rt *rt, const HapGpuFrameEnc *frames, unsigned frame_count,
                                         unsigned max_frags_per_texture, unsigned frag_log2, void *slots,
                                         unsigned slot_stride, uint32_t *frag_sizes, uint8_t *group_tables,
-                                        unsigned granularity_mask)
+                                        const HapGpuCompressKinds *kinds)
 {
-    scoped_timing st(rt, ((granularity_mask >> 16) & 0xFu) ? 8 : 1);      // (8: the block encoder runs inside, HapGpuKernel_EncodeFused)
+    scoped_timing st(rt, kinds->fused ? 8 : 1);      // (8: the block encoder runs inside, HapGpuKernel_EncodeFused)
     const hipStream_t stream = hapgpu_rt_stream(rt);
     if (frame_count == 0 || max_frags_per_texture == 0)
         return 0;
@@ -519,8 +521,7 @@ extern "C" int hapgpu_k_snappy_compress(hapgpu_rt *rt, const HapGpuFrameEnc *fra
         const unsigned lds2 = wg_dynamic_lds(frag_log2);
         if (lds2 > 65536u && !hapgpu_rt_settings(rt)->compress_big_lds)
             return 4;
-        const unsigned textures = ((granularity_mask >> 8) & 0xFFu) == 1u ? 1u : 2u;      // bits 8..15: textures per frame (0 = unknown)
-        const unsigned fused = (granularity_mask >> 16) & 0xFu;                 // bits 16..19: textures made from RGBA on the way
+        const unsigned textures = kinds->textures == 1u ? 1u : 2u;
         const dim3 grid(max_frags_per_texture, textures, frame_count), block(64 * kWgWaves);
 #define HAP_LAUNCH_COMPRESS(G)                                                                                                  \
         do {                                                                                                                    \
@@ -532,20 +533,18 @@ extern "C" int hapgpu_k_snappy_compress(hapgpu_rt *rt, const HapGpuFrameEnc *fra
                                    (uint8_t *)slots, slot_stride, frag_sizes);                                                  \
         } while (0)
         // block textures: the block-per-lane kernels of snappy_compress_blocks.hip
-        if ((granularity_mask & 0xF0u) | fused) {
+        if (kinds->layouts | kinds->fused) {
             if (frag_log2 != 13u)
                 return 1;
-            const unsigned layouts = ((granularity_mask & 32u) ? 1u : 0u) | ((granularity_mask & 64u) ? 2u : 0u) |
-                                     ((granularity_mask & 16u) ? 4u : 0u) | ((granularity_mask & 128u) ? 8u : 0u);
             if (hapgpu_snappy_compress_blocks(frames, frame_count, max_frags_per_texture, textures, slots, slot_stride,
-                                              frag_sizes, group_tables, layouts, fused, stream))
+                                              frag_sizes, group_tables, kinds->layouts, kinds->fused, stream))
                 return 4;
         }
-        if (granularity_mask & 1u)
+        if (kinds->granularities & 1u)
             HAP_LAUNCH_COMPRESS(1u);
-        if (granularity_mask & 2u)
+        if (kinds->granularities & 2u)
             HAP_LAUNCH_COMPRESS(2u);
-        if (granularity_mask & 4u)
+        if (kinds->granularities & 4u)
             HAP_LAUNCH_COMPRESS(4u);
 #undef HAP_LAUNCH_COMPRESS
         return hipGetLastError() == hipSuccess ? 0 : 4;

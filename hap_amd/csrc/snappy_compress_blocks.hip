@@ -50,10 +50,16 @@ constexpr unsigned kDistances = 4u;
 // Layout of a 16-byte unit: field k begins at fo(k) and has fs(k) bytes; copy distances are multiples of `block`.
 //   4: DXT5 / YCoCg-DXT5 [2, 6, 4, 4], one block;  2: DXT1 [4, 4] x 2 blocks;  6: RGTC1 [2, 6] x 2 blocks;
 //   8: an opaque 16-byte block [4, 4, 4, 4].
-// (`code` is what the host puts into HapGpuTexEnc.reserved bits 16..19 for the layout.)
+// (LAYOUT is the HAPGPU_LAYOUT_* value of hapgpu_abi.h: what the host puts into the texture's control word.)
 template <unsigned LAYOUT> struct unit_layout;
+static_assert(HAPGPU_LAYOUT_2_6_4_4 == 4 && HAPGPU_LAYOUT_4_4 == 2 && HAPGPU_LAYOUT_2_6 == 6 && HAPGPU_LAYOUT_4_4_4_4 == 8,
+              "the specialisations below are the layouts of hapgpu_abi.h");
+// the control word's fused kinds are bc_encode_core.hpp's formats + 1 (0: the texture exists)
+static_assert(HAPGPU_FUSED_DXT1 == hapbc::kFmtDXT1 + 1 && HAPGPU_FUSED_DXT5 == hapbc::kFmtDXT5 + 1 &&
+              HAPGPU_FUSED_YCOCG == hapbc::kFmtYCoCg + 1 && HAPGPU_FUSED_RGTC1 == hapbc::kFmtRGTC1 + 1 && HAPGPU_FUSED_NONE == 0,
+              "snappy_compress_blocks_kernel compares the control word's kind with FUSED + 1");
 template <> struct unit_layout<4u> {
-    static constexpr unsigned block = 16u, code = 4u;
+    static constexpr unsigned block = 16u;
     static constexpr unsigned small32 = 0x11111111u;     // 2-byte fields of a half-tile
     static constexpr unsigned big32 = 0x22222222u;       // 6-byte fields
     static constexpr unsigned four32 = 0xCCCCCCCCu;      // 4-byte fields
@@ -67,7 +73,7 @@ template <> struct unit_layout<4u> {
     __device__ static unsigned pos(unsigned q) { const unsigned t = q << 1; return (t << 1) - (t & ~q & 2u); }
 };
 template <> struct unit_layout<2u> {
-    static constexpr unsigned block = 8u, code = 10u;
+    static constexpr unsigned block = 8u;
     static constexpr unsigned small32 = 0u, big32 = 0u, four32 = 0xFFFFFFFFu, run3_12 = 0xFFFFFFFFu, run15_61 = 0u;
     __device__ static constexpr unsigned fo(unsigned k) { return 4u * k; }
     __device__ static constexpr unsigned fs(unsigned) { return 4u; }
@@ -75,7 +81,7 @@ template <> struct unit_layout<2u> {
     __device__ static unsigned pos(unsigned q) { return 4u * q; }
 };
 template <> struct unit_layout<8u> {     // opaque 16-byte blocks (BC7, BC6H): four dwords, distances in whole blocks
-    static constexpr unsigned block = 16u, code = 12u;
+    static constexpr unsigned block = 16u;
     static constexpr unsigned small32 = 0u, big32 = 0u, four32 = 0xFFFFFFFFu, run3_12 = 0xFFFFFFFFu, run15_61 = 0u;
     __device__ static constexpr unsigned fo(unsigned k) { return 4u * k; }
     __device__ static constexpr unsigned fs(unsigned) { return 4u; }
@@ -83,7 +89,7 @@ template <> struct unit_layout<8u> {     // opaque 16-byte blocks (BC7, BC6H): f
     __device__ static unsigned pos(unsigned q) { return 4u * q; }
 };
 template <> struct unit_layout<6u> {
-    static constexpr unsigned block = 8u, code = 2u;
+    static constexpr unsigned block = 8u;
     static constexpr unsigned small32 = 0x55555555u, big32 = 0xAAAAAAAAu, four32 = 0u, run3_12 = 0xAAAAAAAAu,
                               run15_61 = 0xAAAAAAAAu;
     __device__ static constexpr unsigned fo(unsigned k) { return k == 0u ? 0u : k == 1u ? 2u : k == 2u ? 8u : 10u; }
@@ -286,9 +292,9 @@ __global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5
 #endif
     const HapGpuTexEnc tex = frames[zf].tex[blockIdx.y < 2u ? blockIdx.y : 0u];
     const unsigned tex_count = frames[zf].tex_count;
-    if ((blockIdx.y >= tex_count) | (tex.compressor != 1u) | (((tex.reserved >> 16) & 0xFu) != UL::code) |
+    if ((blockIdx.y >= tex_count) | (tex.compressor != 1u) | (hapgpu_control_layout(tex.control) != LAYOUT) |
         (x >= tex.chunk_count * tex.frags_per_chunk) | (tex.src == 0) | (tex.chunk_bytes == 0) |
-        (((tex.reserved >> 24) & 7u) != (unsigned)(FUSED + 1)))
+        (hapgpu_control_fused(tex.control) != (unsigned)(FUSED + 1)))
         return;
     const unsigned chunk = div_by(x, tex.frags_per_chunk, tex.frags_per_chunk_inv), fj = x - chunk * tex.frags_per_chunk;
     const unsigned begin = fj * kFragBytes;
@@ -296,9 +302,9 @@ __global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5
     const gsrc_t src = (gsrc_t)(tex.src + (uint64_t)chunk * tex.chunk_bytes + begin);
     const unsigned f = tex.frag_first + x;
     gdst_t out = (gdst_t)((uintptr_t)slots + (size_t)f * slot_stride);
-    const bool placed = ((tex.reserved >> 27) & 1u) != 0u && blockIdx.y == 0u;
-    const unsigned window = ((tex.reserved >> 8) & 0xFFu) ? ((tex.reserved >> 8) & 0xFFu) * 256u : 0xFFFFFFFFu;
-    const bool want_sizes = ((tex.reserved >> 20) & 1u) != 0u && group_tables != nullptr;
+    const bool placed = hapgpu_control_placed(tex.control) != 0u && blockIdx.y == 0u;
+    const unsigned window = hapgpu_control_window_256(tex.control) ? hapgpu_control_window_256(tex.control) * 256u : 0xFFFFFFFFu;
+    const bool want_sizes = hapgpu_control_half_tiles(tex.control) != 0u && group_tables != nullptr;
     // where the fragment's group table goes: the table array (gathered into the frame later) -- or, for a placed
     // fragment, straight into the frame's fragment section
     gdst_t table_at = (gdst_t)((uintptr_t)group_tables + (size_t)f * HAP_GROUP_TABLE_BYTES);
@@ -751,8 +757,8 @@ __global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5
                                                (unsigned long long)(chunk * fpc + fj) * HAP_GROUP_TABLE_BYTES);
         } else if (lane == 0u) {
             // (a frame with such a fragment is encoded again through slots, and the chunks behind it need not wait
-            // for the total; bit 0 of the frame's reserved word tells the host that it was a timeout)
-            __hip_atomic_fetch_or(const_cast<uint32_t *>(&frames[zf].reserved), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            // for the total; the note tells the host that it was a timeout)
+            __hip_atomic_fetch_or(const_cast<uint32_t *>(&frames[zf].notes), HAPGPU_FRAME_NOTE_WAVE_TIMED_OUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (fj + 1u == tex.frags_per_chunk)
                 __hip_atomic_store(const_cast<unsigned long long *>(&acc[chunk]), 2ull << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -884,9 +890,7 @@ __global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5
 
 } // namespace
 
-// layouts: bit 0 = [2,6,4,4] textures present, bit 1 = [4,4], bit 2 = [2,6], bit 3 = [4,4,4,4];
-// fused: textures made from the frames' RGBA pictures on the way (HapGpuTexEnc.reserved bits 24..26): bit 0 = scaled
-// YCoCg-DXT5, bit 1 = DXT5, bit 2 = DXT1, bit 3 = RGTC1
+// layouts, fused: HapGpuCompressKinds' sets (bit HAPGPU_LAYOUT_* / HAPGPU_FUSED_*), as hapgpu_k_snappy_compress got them
 int hapgpu_snappy_compress_blocks(const HapGpuFrameEnc *frames, unsigned frame_count, unsigned max_frags_per_texture,
                                   unsigned textures, void *slots, unsigned slot_stride, uint32_t *frag_sizes,
                                   uint8_t *group_tables, unsigned layouts, unsigned fused, hipStream_t stream)
@@ -897,21 +901,21 @@ int hapgpu_snappy_compress_blocks(const HapGpuFrameEnc *frames, unsigned frame_c
 #define HAP_LAUNCH_BLOCKS(L, F)                                                                                                  \
     hipLaunchKernelGGL((snappy_compress_blocks_kernel<L, F>), grid, block, 0, stream, frames, (uint8_t *)slots, slot_stride,    \
                        frag_sizes, group_tables, HAPGPU_DIV_INV(frame_count))
-    if (fused & 1u)
-        HAP_LAUNCH_BLOCKS(4u, hapbc::kFmtYCoCg);
+    if (fused & (1u << HAPGPU_FUSED_YCOCG))
+        HAP_LAUNCH_BLOCKS(HAPGPU_LAYOUT_2_6_4_4, hapbc::kFmtYCoCg);
 #ifndef SCB_ONLY_FUSED_YCOCG          // (instruction-count studies, tools/isa_by_line.py: that instantiation alone)
-    if (fused & 2u)
-        HAP_LAUNCH_BLOCKS(4u, hapbc::kFmtDXT5);
-    if (fused & 12u)          // (DXT1 / RGTC1: the fused form was no faster than the two passes, hap_batch.c; not instantiated)
+    if (fused & (1u << HAPGPU_FUSED_DXT5))
+        HAP_LAUNCH_BLOCKS(HAPGPU_LAYOUT_2_6_4_4, hapbc::kFmtDXT5);
+    if (fused & (1u << HAPGPU_FUSED_DXT1 | 1u << HAPGPU_FUSED_RGTC1))   // (the fused form was no faster than the two passes, hap_encode_plan.h; not instantiated)
         return 1;
-    if (layouts & 1u)
-        HAP_LAUNCH_BLOCKS(4u, -1);
-    if (layouts & 2u)
-        HAP_LAUNCH_BLOCKS(2u, -1);
-    if (layouts & 4u)
-        HAP_LAUNCH_BLOCKS(6u, -1);
-    if (layouts & 8u)
-        HAP_LAUNCH_BLOCKS(8u, -1);
+    if (layouts & (1u << HAPGPU_LAYOUT_2_6_4_4))
+        HAP_LAUNCH_BLOCKS(HAPGPU_LAYOUT_2_6_4_4, -1);
+    if (layouts & (1u << HAPGPU_LAYOUT_4_4))
+        HAP_LAUNCH_BLOCKS(HAPGPU_LAYOUT_4_4, -1);
+    if (layouts & (1u << HAPGPU_LAYOUT_2_6))
+        HAP_LAUNCH_BLOCKS(HAPGPU_LAYOUT_2_6, -1);
+    if (layouts & (1u << HAPGPU_LAYOUT_4_4_4_4))
+        HAP_LAUNCH_BLOCKS(HAPGPU_LAYOUT_4_4_4_4, -1);
 #endif
 #undef HAP_LAUNCH_BLOCKS
     return hipGetLastError() == hipSuccess ? 0 : 4;

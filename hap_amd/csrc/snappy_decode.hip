@@ -250,9 +250,9 @@ __global__ __launch_bounds__(64) void decode_expand_kernel(HapGpuDecodeJob *jobs
         kind |= HAPGPU_UNIT_WINDOWED;
     const bool fields = job->fields_period != 0u && job->group_tables != 0u;
     if (fields)       // field stream (table version 3): block-per-lane decoder, with the fragment's group table
-        kind = job->fields_period == 4u ? HAPGPU_UNIT_SNAPPY_FIELDS4
-             : job->fields_period == 2u ? HAPGPU_UNIT_SNAPPY_FIELDS2
-             : job->fields_period == 8u ? HAPGPU_UNIT_SNAPPY_FIELDS44 : HAPGPU_UNIT_SNAPPY_FIELDS26;
+        kind = job->fields_period == HAPGPU_LAYOUT_2_6_4_4 ? HAPGPU_UNIT_SNAPPY_FIELDS4
+             : job->fields_period == HAPGPU_LAYOUT_4_4 ? HAPGPU_UNIT_SNAPPY_FIELDS2
+             : job->fields_period == HAPGPU_LAYOUT_4_4_4_4 ? HAPGPU_UNIT_SNAPPY_FIELDS44 : HAPGPU_UNIT_SNAPPY_FIELDS26;
     unsigned long long run = c.plan_hdr;
     for (unsigned base = 0; base < per_chunk; base += 64u) {
         const unsigned k = base + lane;

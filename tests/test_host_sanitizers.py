@@ -57,3 +57,19 @@ def test_the_slice_arithmetic_is_clean_and_is_the_rule(tmp_path):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     done = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
     assert done.returncode == 0 and done.stdout.strip().endswith("ok"), (done.returncode, done.stdout, done.stderr[-3000:])
+
+
+def test_the_encode_plan_is_clean_and_is_what_it_was(tmp_path):
+    """hap_encode_plan.h -- what hapb_encode decides about a call before it looks at a frame -- walked by
+    tests/c/encode_plan.c under AddressSanitizer + UBSan: a plain executable, nothing preloaded.  Every plan equals the
+    row recorded for it from the function the header was lifted out of, and the control word, the layouts, half-tiles,
+    fusion and placing keep their rules over a product of the inputs."""
+    exe = str(tmp_path / "encode_plan")
+    csrc = os.path.join(ROOT, "hap_amd", "csrc")
+    cmd = ["gcc", "-std=c99", "-g", "-O1", "-fsanitize=address,undefined",
+           "-fno-sanitize-recover=undefined", "-I", csrc, "-I", os.path.join(ROOT, "include"),
+           os.path.join(ROOT, "tests", "c", "encode_plan.c"), os.path.join(csrc, "hap_frame.c"), "-o", exe]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    done = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
+    assert done.returncode == 0 and done.stdout.strip().endswith("ok"), (done.returncode, done.stdout, done.stderr[-3000:])

@@ -1,4 +1,4 @@
-"""GPU probe: fragments written straight to their places in the frame (HapGpuTexEnc.reserved bit 27): timing of the
+"""GPU probe: fragments written straight to their places in the frame (the "placed" bit of HapGpuTexEnc.control): timing of the
 encode call, how many frames had to be encoded again.    python tools/probe_placed.py [C4|C2|C3|C5] [frames] [reps]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
