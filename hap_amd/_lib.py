@@ -92,6 +92,8 @@ def _load():
                                        P(u), u]),
         "HapGpuEncodeFramesNV12Begin": (u, [vp, u, P(vp), ul, P(vp), ul, u, u, u, u, u, P(u), P(u), P(u), P(vp), P(ul),
                                             P(ul), P(u), u]),
+        "HapGpuDecompressNV12": (u, [vp, vp, ul, u, u, u, u, u, u, vp, ul, vp, ul]),
+        "HapGpuDecodeFramesNV12": (u, [vp, u, P(vp), P(ul), u, P(vp), ul, P(vp), ul, u, u, u, u, u, P(u), u]),
         "HapGpuDecodeFramesPlanes": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, u, u, ul, ul, P(C.c_float), P(C.c_float), P(u), u]),
         "HapGpuDecodeFramesRGBARegion": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, u, u, u, u, ul, P(u), u]),
         "HapGpuDecodeFramesPlanesRegion": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, P(u), P(u), u, u, u, u, u, ul, ul,

@@ -1023,6 +1023,44 @@ class Context:
                                              row_bytes or (width >> shift) * 4, results, flags)
         return r, list(results)
 
+    def decompress_nv12(self, texture, texture_format, width, height, luma, chroma, scale_log2=0, matrix=YCBCR_BT709,
+                        range=YCBCR_LIMITED, luma_row_bytes=None, chroma_row_bytes=None):
+        """One block texture -> one NV12 video picture on the device (HapGpuDecompressNV12), of W x H =
+        (width >> scale_log2) x (height >> scale_log2).  `luma`: a (H, W) torch uint8 tensor, `chroma`: a (H / 2, W) one
+        or (H / 2, W / 2, 2) Cb, Cr pairs; stride(-1) must be 1 and the pitches are read from the tensors (a slice with
+        longer rows is accepted), or integer addresses with luma_row_bytes / chroma_row_bytes.  Y[y][x] is the integer
+        luma of decompress_rgba[_scaled]'s texel (x, y), pair [j][i] the integer chroma of the mean of its 2 x 2 texels,
+        under matrix (YCBCR_BT601, YCBCR_BT709) and range (YCBCR_LIMITED, YCBCR_FULL); alpha is ignored.  texture_format
+        RGB_DXT1, RGBA_DXT5 or YCoCg_DXT5.  Returns the result."""
+        shift = scale_log2 if 0 <= scale_log2 < 3 else 0            # (a refused scale: nothing is written)
+        ya, luma_row_bytes, _k1 = _video_planes(luma, True, height >> shift, width >> shift, luma_row_bytes, "luma")
+        ca, chroma_row_bytes, _k2 = _video_planes(chroma, True, (height >> shift) // 2, width >> shift, chroma_row_bytes,
+                                                  "chroma")
+        ta, tn, _k = _addr_len(texture)
+        return lib.HapGpuDecompressNV12(self.handle, ta, tn, texture_format, width, height, scale_log2, matrix, range,
+                                        ya[0], luma_row_bytes, ca[0], chroma_row_bytes)
+
+    def decode_frames_nv12(self, frames, frame_bytes, texture_count, luma_planes, chroma_planes, width, height,
+                           scale_log2=0, matrix=YCBCR_BT709, range=YCBCR_LIMITED, luma_row_bytes=None,
+                           chroma_row_bytes=None, flags=0):
+        """Frames -> NV12 video pictures on the device in one call, without RGBA8 pictures in between
+        (HapGpuDecodeFramesNV12); width and height are the frames', the pictures W x H = (width >> scale_log2) x
+        (height >> scale_log2).  luma_planes / chroma_planes: one (N, H, W) / (N, H / 2, W) torch uint8 tensor each, or
+        lists of N planes as decompress_nv12 takes them that share their pitch (None: no plane for that frame; integer
+        addresses with luma_row_bytes / chroma_row_bytes).  The samples are decompress_nv12's of
+        decode_frames_rgba[_scaled]'s pictures.  Returns (result, results[])."""
+        nf = len(frames)
+        shift = scale_log2 if 0 <= scale_log2 < 3 else 0
+        ya, luma_row_bytes, _ky, ca, chroma_row_bytes, _kc = _video_frames(
+            luma_planes, chroma_planes, width >> shift, height >> shift, luma_row_bytes, chroma_row_bytes, nf)
+        ptrs, infos = self._ptr_array(frames)
+        lens = (C.c_ulong * nf)(*[fb if fb is not None else infos[i][1] for i, fb in enumerate(frame_bytes)])
+        yptrs, cptrs = (C.c_void_p * nf)(*ya), (C.c_void_p * nf)(*ca)
+        results = (C.c_uint * nf)()
+        r = lib.HapGpuDecodeFramesNV12(self.handle, nf, ptrs, lens, texture_count, yptrs, luma_row_bytes, cptrs,
+                                       chroma_row_bytes, matrix, range, width, height, scale_log2, results, flags)
+        return r, list(results)
+
     def decode_frames_planes(self, frames, frame_bytes, texture_count, out, width, height, scale_log2=0, scale=None,
                              bias=None, flags=0):
         """Frames -> normalised planar tensors in one call, without RGBA8 pictures in between (HapGpuDecodeFramesPlanes).

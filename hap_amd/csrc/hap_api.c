@@ -609,6 +609,22 @@ unsigned int HapGpuDecompressRGBAScaled(HapGpuContext *context, const void *text
                              height, rgba, rowBytes, &road);
 }
 
+/* one texture -> one NV12 video picture in device memory, at full, half or quarter size: the block decode of
+   bc_decode_video.hip */
+unsigned int HapGpuDecompressNV12(HapGpuContext *context, const void *texture, unsigned long textureBytes,
+                                  unsigned int textureFormat, unsigned int width, unsigned int height,
+                                  unsigned int scaleLog2, unsigned int matrix, unsigned int range, void *luma,
+                                  unsigned long lumaRowBytes, void *chroma, unsigned long chromaRowBytes)
+{
+    const void *const chroma_plane = chroma;
+    const HapbVideo video = {&chroma_plane, chromaRowBytes, matrix, range};
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA8, .scale_log2 = scaleLog2, .video = &video};
+    if (!context || !luma || !chroma || !hapb_video_decode_valid(width, height, scaleLog2, lumaRowBytes, &video))
+        return HapResult_Bad_Arguments;
+    return texture_down_road(context, texture, textureBytes, textureFormat, NULL, 0ul, width, height, luma, lumaRowBytes,
+                             &road);
+}
+
 /* 1: what the planar calls take of scaleLog2, channels, element, scale and bias */
 static int planes_arguments_valid(unsigned scaleLog2, unsigned channels, unsigned element, const float *scale,
                                   const float *bias)
@@ -1190,6 +1206,29 @@ unsigned int HapGpuDecodeFramesRGBAScaled(HapGpuContext *context, unsigned int f
         return refuse_call(results, frameCount);
     return frames_down_road(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, rgbaFrames, width, height,
                             rowBytes, results, flags, &road);
+}
+
+/* frames -> NV12 video pictures in device memory; arguments outside the rules refuse the whole call, before the
+   context is looked at */
+unsigned int HapGpuDecodeFramesNV12(HapGpuContext *context, unsigned int frameCount,
+                                    const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
+                                    unsigned int textureCount, void *const *lumaPlanes, unsigned long lumaRowBytes,
+                                    void *const *chromaPlanes, unsigned long chromaRowBytes, unsigned int matrix,
+                                    unsigned int range, unsigned int width, unsigned int height,
+                                    unsigned int scaleLog2, unsigned int *results, unsigned int flags)
+{
+    const HapbVideo video = {(const void *const *)chromaPlanes, chromaRowBytes, matrix, range};
+    /* (Hap R frames are out of scope with or without the flag that asks for their pictures: the road has no BC7) */
+    const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA8, .scale_log2 = scaleLog2, .video = &video};
+    if (!results)
+        return HapResult_Bad_Arguments;
+    if (!inputBuffers || !inputBuffersBytes || !lumaPlanes || !chromaPlanes || textureCount == 0 || textureCount > 2 ||
+        !hapb_video_decode_valid(width, height, scaleLog2, lumaRowBytes, &video))
+        return refuse_call(results, frameCount);
+    if (!context)
+        return HapResult_Bad_Arguments;
+    return frames_down_road(context, frameCount, inputBuffers, inputBuffersBytes, textureCount, lumaPlanes, width, height,
+                            lumaRowBytes, results, flags & ~HAPGPU_DECODE_BPTC_PICTURES, &road);
 }
 
 /* frames -> planar float tensors in device memory; arguments outside the rules refuse the whole call */

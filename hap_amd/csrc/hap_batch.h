@@ -159,6 +159,11 @@ int hapb_planes_encode_valid(unsigned width, unsigned height, unsigned long row_
    texture formats are in order (include/hap_gpu.h: HapGpuCompressNV12, HapGpuEncodeFramesNV12).  Touches no device. */
 int hapb_video_encode_valid(unsigned width, unsigned height, unsigned long row_bytes, const HapbVideo *video,
                             unsigned count, const unsigned *formats);
+/* ... and the video decode calls whatever their frames and planes are: 1 = scale_log2, matrix, range, the geometry
+   (multiples of 4 << scale_log2, at most 65535 block rows of the output) and both pitches are in order
+   (include/hap_gpu.h: HapGpuDecompressNV12, HapGpuDecodeFramesNV12).  Touches no device. */
+int hapb_video_decode_valid(unsigned width, unsigned height, unsigned scale_log2, unsigned long row_bytes,
+                            const HapbVideo *video);
 /* 1: region is a block-aligned, non-empty rectangle inside region->width x height */
 int hapb_region_fits(const HapGpuRegion *region, unsigned height);
 /* pictures or planar tensors -> frames, HAP_SLICE_ENTRIES frames at a time: every slice reports for itself and the first
@@ -219,6 +224,12 @@ typedef struct HapbRoad {
     const HapbResize *resize;   /* NULL: tensors of the rectangle's or the textures' (scaled) size; else (planes only, no
                                    region) tensors of resize->out_w x resize->out_h, entry f's crop of the scaled picture
                                    resized */
+    const HapbVideo *video;     /* NULL: as above; else (RGBA8, scale_log2 0 to 2; no bptc, region, planes, resize or
+                                   measure) NV12 pictures in device memory are WRITTEN: the road's pictures are their Y
+                                   planes, a "texel" one byte and row_bytes the pitch of a Y plane's rows; video->chroma[f]
+                                   is the CbCr plane of pictures[f], f counted from the call's first frame (one texture:
+                                   one entry).  It travels in the alpha column of the launch's HapGpuPictureTable, free
+                                   here: the RGTC1 plane of a frame is never block-decoded */
     HapGpuPictureError *measure; /* NULL: the pictures are written; else (RGBA8, scale_log2 0, no region, no planes) they
                                    are reference pictures in device memory and are READ: measure[f] gets the sums of
                                    frame f against its picture, f counted from the call's first frame, all zero for a

@@ -101,6 +101,8 @@ static size_t picture_texel_bytes(const HapbRoad *road)
 {
     if (road->planes)
         return road->planes->element == HapGpuPlaneElement_F32 ? 4u : 2u;
+    if (road->video)
+        return 1u;          /* (a Y sample) */
     return HAPGPU_PICTURE_TEXEL_BYTES(road->picture_kind);
 }
 
@@ -126,16 +128,37 @@ int hapb_region_fits(const HapGpuRegion *region, unsigned height)
            region->h <= height - region->y;
 }
 
+int hapb_video_decode_valid(unsigned width, unsigned height, unsigned scale_log2, unsigned long row_bytes,
+                            const HapbVideo *video)
+{
+    unsigned step, out_width;
+    if (scale_log2 > 2u || video->matrix > HapGpuYCbCrMatrix_BT709 || video->range > HapGpuYCbCrRange_Full)
+        return 0;
+    step = 4u << scale_log2;
+    out_width = width >> scale_log2;
+    /* (width / 2 pairs of two bytes: a chroma row is as long as a luma row) */
+    return width && height && !(width % step) && !(height % step) && height / step <= 65535u && row_bytes >= out_width &&
+           video->chroma_row_bytes >= out_width && !(row_bytes & 3u) && !(video->chroma_row_bytes & 3u);
+}
+
+/* 1: `plane` is where a video road can write a CbCr plane: in device memory, dword aligned */
+static int chroma_plane_fits(HapGpuContext *ctx, const void *plane)
+{
+    return plane && is_dev(ctx, plane) && !((uintptr_t)plane & 3u);
+}
+
 /* what the block decoders ask of a picture's address (in device memory) and row pitch when they write it: 16-byte
    stores for RGBA8 and RGBA16F; A8 pictures take dword stores, and 16-byte ones where address and pitch allow; a scaled
    picture takes the 16 >> scale_log2 bytes a lane has for each of its rows, a plane its 4 >> scale_log2 elements -- or,
-   resized, the one element a lane stores */
+   resized, the one element a lane stores; the planes of a video picture take dword stores */
 static unsigned picture_align_mask(const HapbRoad *road)
 {
     if (road->resize)
         return (unsigned)picture_texel_bytes(road) - 1u;
     if (road->planes)
         return (4u >> road->scale_log2) * (unsigned)picture_texel_bytes(road) - 1u;
+    if (road->video)
+        return 3u;          /* (at every size: a lane stores a destination block's rows) */
     if (road->scale_log2)
         return (16u >> road->scale_log2) - 1u;
     return road->picture_kind == HAPGPU_PICTURE_A8 ? 3u : 15u;
@@ -181,8 +204,9 @@ static int picture_unstage(hapgpu_rt *rt, void *picture, const void *staged, con
     return hapgpu_rt_d2h_rows(rt, picture, p->row_bytes, staged, p->row_bytes, p->pixel_row, p->rows);
 }
 
-/* the block-decode launch of a road: pictures of the frames' size, scaled ones, a rectangle's, or planar tensors (the
-   alpha plane is read only where a fourth plane is written).  origins: a planar road with a rectangle per frame -- the
+/* the block-decode launch of a road: pictures of the frames' size, scaled ones, a rectangle's, planar tensors (the
+   alpha plane is read only where a fourth plane is written) or video pictures (whose CbCr planes are the table's second
+   column; with_alpha is not looked at).  origins: a planar road with a rectangle per frame -- the
    device array of the pictures' first blocks, or, resized, of their crops (four words each; NULL: the road's first crop
    for all); partials, totals: a measuring road's scratch (measure_scratch) */
 static int launch_block_decode(hapgpu_rt *rt, const HapbRoad *road, const HapGpuPictureTable *t, unsigned pictures,
@@ -190,6 +214,9 @@ static int launch_block_decode(hapgpu_rt *rt, const HapbRoad *road, const HapGpu
                                const uint32_t *origins, uint32_t *partials, unsigned long long *totals)
 {
     /* (a measuring road: the block kernel with the pictures as its third column, read, and the reduction behind it) */
+    if (road->video)
+        return hapgpu_k_block_decode_video(rt, t, pictures, width, height, format, road->scale_log2, row_bytes,
+                                           road->video->chroma_row_bytes, road->video->matrix, road->video->range);
     if (road->measure)
         return hapgpu_k_block_measure(rt, t, pictures, with_alpha, width, height, format, row_bytes, partials, totals);
     if (road->resize) {
@@ -257,7 +284,10 @@ unsigned hapb_road_texture(HapGpuContext *ctx, const void *texture, unsigned lon
         /* (tensors live in device memory: no host staging road) */
         (road.planes && (!planes_fit(&road, pixel_row, picture_height, row_bytes) || !is_dev(ctx, picture))) ||
         /* (and so do reference pictures) */
-        (road.measure && !is_dev(ctx, picture)))
+        (road.measure && !is_dev(ctx, picture)) ||
+        /* (and video pictures, both planes; no alpha plane is taken) */
+        (road.video && (alpha || !hapb_video_decode_valid(width, height, road.scale_log2, row_bytes, road.video) ||
+                        !is_dev(ctx, picture) || !chroma_plane_fits(ctx, road.video->chroma[0]))))
         return HapResult_Bad_Arguments;
     need = (size_t)(width / 4u) * (height / 4u) * block;
     alpha_need = (size_t)(width / 4u) * (height / 4u) * 8u;
@@ -267,6 +297,8 @@ unsigned hapb_road_texture(HapGpuContext *ctx, const void *texture, unsigned lon
        (A8 pictures: rows and device pictures to 4 bytes, and at most 65535 block rows; scaled pictures: rows and device
        pictures to 8 bytes at half, 4 at quarter size) */
     if ((row_bytes & align) || (is_dev(ctx, texture) && ((uintptr_t)texture & (block - 1u))) ||
+        /* (a video road's lane reads what of a block row lies under its destination block in one load) */
+        (road.video && is_dev(ctx, texture) && ((uintptr_t)texture & ((block << road.scale_log2) - 1u) & 15u)) ||
         (alpha && is_dev(ctx, alpha) && ((uintptr_t)alpha & 7u)) || (is_dev(ctx, picture) && ((uintptr_t)picture & align)) ||
         (picture_kind == HAPGPU_PICTURE_A8 && height / 4u > 65535u))
         return HapResult_Bad_Arguments;
@@ -291,7 +323,7 @@ unsigned hapb_road_texture(HapGpuContext *ctx, const void *texture, unsigned lon
     if (!is_dev(ctx, picture) && !(dst = picture_stage(rt, &stage, shape.bytes, 1u, 0u)))
         return HapResult_Internal_Error;
     t.one[0] = (uint64_t)(uintptr_t)src;
-    t.one[1] = (uint64_t)(uintptr_t)asrc;
+    t.one[1] = (uint64_t)(uintptr_t)(road.video ? road.video->chroma[0] : asrc);
     t.one[2] = (uint64_t)(uintptr_t)dst;
     if (road.measure) {
         /* (after the textures' scratch: growing an arena waits for the stream, not for copies yet to be issued) */
@@ -475,6 +507,8 @@ unsigned hapb_road_frames(HapGpuContext *ctx, unsigned frame_count, const void *
         (road->resize && (!hapb_resize_out_valid(road->resize) || !road->resize->xs || !road->resize->ys ||
                           !road->resize->ws || !road->resize->hs)) ||
         (road->planes && !planes_fit(road, pixel_row, picture_height, row_bytes)) ||
+        (road->video && (!road->video->chroma ||
+                         !hapb_video_decode_valid(width, height, road->scale_log2, row_bytes, road->video))) ||
         (road->picture_kind == HAPGPU_PICTURE_A8 && height / 4u > 65535u)) {
         for (f = 0; f < frame_count; f++)
             results[f] = HapResult_Bad_Arguments;
@@ -543,8 +577,11 @@ unsigned hapb_road_frames(HapGpuContext *ctx, unsigned frame_count, const void *
                    asked for Hap R pictures) */
                 if (r == HapResult_No_Error && !slice_entry_fits(&s, e, texture_count, kinds, kind_count))
                     r = HapResult_Bad_Arguments;
-                if (r == HapResult_No_Error && (road->planes || road->measure) && !is_dev(ctx, dst)) {
-                    r = HapResult_Bad_Arguments;        /* tensors and reference pictures live in device memory: no host staging road */
+                /* (a video picture's other plane: NULL, in host memory or misaligned refuses the frame) */
+                if (r == HapResult_No_Error && road->video && !chroma_plane_fits(ctx, road->video->chroma[done + f]))
+                    r = HapResult_Bad_Arguments;
+                if (r == HapResult_No_Error && (road->planes || road->measure || road->video) && !is_dev(ctx, dst)) {
+                    r = HapResult_Bad_Arguments;        /* tensors, reference and video pictures live in device memory: no host staging road */
                 } else if (r == HapResult_No_Error && !is_dev(ctx, dst)) {
                     dst = picture_stage(rt, &stage, align_up(shape.bytes, 256), n, f);
                     if (!dst)
@@ -557,7 +594,8 @@ unsigned hapb_road_frames(HapGpuContext *ctx, unsigned frame_count, const void *
                     if ((uintptr_t)dst & 15u)
                         wide = 0;
                     htab[(size_t)k * 3u * n + f] = (uint64_t)(uintptr_t)s.outs[e];
-                    htab[(size_t)k * 3u * n + n + f] = texture_count == 2 ? (uint64_t)(uintptr_t)s.outs[e + 1] : 0u;
+                    htab[(size_t)k * 3u * n + n + f] = road->video ? (uint64_t)(uintptr_t)road->video->chroma[done + f] :
+                                                       texture_count == 2 ? (uint64_t)(uintptr_t)s.outs[e + 1] : 0u;
                     htab[(size_t)k * 3u * n + 2u * n + f] = (uint64_t)(uintptr_t)dst;
                     if (horigins && road->resize) {     /* (a crop of the frame: a refused one never gets here) */
                         horigins[4u * f] = road->resize->xs[done + f];

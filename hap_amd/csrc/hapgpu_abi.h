@@ -369,7 +369,8 @@ void hapgpu_rt_graphs_disable(hapgpu_rt *rt);
 
 /* [device] Addresses of a block-codec launch: three columns of `pictures` device addresses, each either a DEVICE array
    (column[c]) or, for one picture, the address itself (one[c], read where column[c] is NULL).  Encode: sources, outputs,
-   second outputs (Hap Q Alpha's RGTC1 plane; video pictures: their CbCr planes, a 0 skipping the picture); decode: textures, alpha planes, pictures.  A source or texture address of
+   second outputs (Hap Q Alpha's RGTC1 plane; video pictures: their CbCr planes, a 0 skipping the picture); decode: textures, alpha planes, pictures
+   (to video pictures: textures, CbCr planes, Y planes, a 0 in any column skipping the picture).  A source or texture address of
    0 skips the picture, and so does an encode output of 0. */
 typedef struct HapGpuPictureTable {
     const uint64_t *column[3];
@@ -537,6 +538,20 @@ int hapgpu_k_block_encode_planes(hapgpu_rt *rt, const HapGpuPictureTable *table,
    HapGpuKernel_BlockEncode.  Returns 0 launched, 1 bad arguments, 4 launch failure. */
 int hapgpu_k_block_encode_video(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, unsigned width,
                                 unsigned height, unsigned hap_texture_format, unsigned flags, size_t luma_row_bytes,
+                                size_t chroma_row_bytes, unsigned matrix, unsigned range);
+/* blocks of `hap_texture_format` (RGB_DXT1, RGBA_DXT5 or YCoCg_DXT5; alpha is never read) -> NV12 video pictures of
+   (width >> scale_log2) x (height >> scale_log2), scale_log2 0 to 2, without an RGBA8 picture in between
+   (bc_decode_video.hip).  The table's columns are [textures][CbCr planes][Y planes]: a Y plane of W x H bytes, rows
+   luma_row_bytes apart, and a plane of (W / 2) x (H / 2) interleaved Cb, Cr pairs, rows chroma_row_bytes apart; a 0 in any
+   column skips the picture.  With d the RGBA8 picture hapgpu_k_block_decode (scale_log2 0) or
+   hapgpu_k_block_decode_scaled writes for the texture, Y[y][x] is rgb_ycbcr.hpp's luma of d(x, y) and pair [j][i] its pair
+   of the sums over d(2i..2i+1, 2j..2j+1), under `matrix` (HapGpuYCbCrMatrix) and `range` (HapGpuYCbCrRange).  width and
+   height are the textures', multiples of 4 << scale_log2; at most 65535 destination block rows.  Textures aligned to what
+   a lane reads of a block row (their block << scale_log2, at most 16 bytes); planes and both pitches 4-byte aligned, both
+   pitches at least W.  Only the samples are written.  Timed as HapGpuKernel_BlockDecode.  Returns 0 launched, 1 bad
+   arguments, 4 launch failure. */
+int hapgpu_k_block_decode_video(hapgpu_rt *rt, const HapGpuPictureTable *table, unsigned pictures, unsigned width,
+                                unsigned height, unsigned hap_texture_format, unsigned scale_log2, size_t luma_row_bytes,
                                 size_t chroma_row_bytes, unsigned matrix, unsigned range);
 /* [device] Addresses of a transcode launch, as HapGpuPictureTable's: source textures, source alpha planes, destination
    textures, destination alpha planes (Hap Q Alpha's second texture). */

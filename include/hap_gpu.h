@@ -1061,7 +1061,8 @@ unsigned int HapGpuEncodeFramesPlanesBegin(HapGpuContext *context, unsigned int 
                                            unsigned int *results,
                                            unsigned int flags);
 
-/* The colour matrix and the range of a video picture's Y, Cb, Cr samples (HapGpuCompressNV12, HapGpuEncodeFramesNV12) */
+/* The colour matrix and the range of a video picture's Y, Cb, Cr samples (HapGpuCompressNV12, HapGpuEncodeFramesNV12,
+ * HapGpuDecompressNV12, HapGpuDecodeFramesNV12) */
 enum HapGpuYCbCrMatrix { HapGpuYCbCrMatrix_BT601 = 0, HapGpuYCbCrMatrix_BT709 = 1 };
 enum HapGpuYCbCrRange { HapGpuYCbCrRange_Limited = 0, HapGpuYCbCrRange_Full = 1 };
 
@@ -1094,9 +1095,10 @@ enum HapGpuYCbCrRange { HapGpuYCbCrRange_Limited = 0, HapGpuYCbCrRange_Full = 1 
  * lumaRowBytes >= width and chromaRowBytes >= width (width / 2 pairs).  Only the samples are read, nothing between rows.
  * Bad_Arguments, and nothing written, for anything else: a NULL, host or misaligned plane, a matrix or range outside the
  * enums, another format, a bad pitch.
- * Out of scope: the way back (textures or frames -> NV12); P010 and other 10/16-bit layouts; planar I420, 4:2:2 and
- * 4:4:4; filtered or sited chroma upsampling, which needs neighbours across blocks; a separate A8 plane, and with it Hap
- * Alpha, Hap Q Alpha and Hap Alpha-Only destinations; BC7 / BC6H destinations; host pictures. */
+ * Out of scope here: the way back (textures or frames -> NV12) is HapGpuDecompressNV12 and HapGpuDecodeFramesNV12's; P010
+ * and other 10/16-bit layouts; planar I420, 4:2:2 and 4:4:4; filtered or sited chroma upsampling, which needs neighbours
+ * across blocks; a separate A8 plane, and with it Hap Alpha, Hap Q Alpha and Hap Alpha-Only destinations; BC7 / BC6H
+ * destinations; host pictures. */
 unsigned int HapGpuCompressNV12(HapGpuContext *context,
                                 const void *luma, unsigned long lumaRowBytes,
                                 const void *chroma, unsigned long chromaRowBytes,
@@ -1129,10 +1131,10 @@ unsigned int HapGpuCompressNV12(HapGpuContext *context,
  * below width, more than 65535 block rows, count == 2 or another format.  A frame either of whose planes is NULL, in
  * host memory or misaligned is Bad_Arguments alone, its output buffer untouched, and the other frames are encoded.  The
  * function's result is the first failure.  A context between a ...Begin and HapGpuEncodeFramesFinish: Internal_Error.
- * Out of scope: the way back (frames -> NV12); P010 and other 10/16-bit layouts; planar I420, 4:2:2 and 4:4:4; filtered
- * or sited chroma upsampling, which needs neighbours across blocks; a separate A8 plane, and with it Hap Alpha, Hap Q
- * Alpha and Hap Alpha-Only destinations; BC7 / BC6H destinations; host pictures; ...OnDevices and ...Sequence forms of
- * this call; and reading the planes inside the fused compress kernel. */
+ * Out of scope here: the way back (frames -> NV12) is HapGpuDecodeFramesNV12's; P010 and other 10/16-bit layouts; planar
+ * I420, 4:2:2 and 4:4:4; filtered or sited chroma upsampling, which needs neighbours across blocks; a separate A8 plane,
+ * and with it Hap Alpha, Hap Q Alpha and Hap Alpha-Only destinations; BC7 / BC6H destinations; host pictures;
+ * ...OnDevices and ...Sequence forms of this call; and reading the planes inside the fused compress kernel. */
 unsigned int HapGpuEncodeFramesNV12(HapGpuContext *context, unsigned int frameCount,
                                     const void *const *lumaPlanes, unsigned long lumaRowBytes,
                                     const void *const *chromaPlanes, unsigned long chromaRowBytes,
@@ -1161,6 +1163,91 @@ unsigned int HapGpuEncodeFramesNV12Begin(HapGpuContext *context, unsigned int fr
                                          unsigned long *outputBuffersBytesUsed,
                                          unsigned int *results,
                                          unsigned int flags);
+
+/* The way back of HapGpuCompressNV12: one block-compressed texture -> one NV12 video picture in DEVICE memory, what a
+ * video encoder or a network sender takes, converted from RGB by the block decoder itself before it stores: no RGBA8
+ * picture is written or read back.  The picture is W x H = (width >> scaleLog2) x (height >> scaleLog2): a Y plane of
+ * W x H bytes (luma, rows lumaRowBytes apart) and a plane of (W / 2) x (H / 2) interleaved Cb, Cr byte pairs (chroma,
+ * rows chromaRowBytes apart).
+ * The definition.  d is the RGBA8 picture HapGpuDecompressRGBA writes for the texture at scaleLog2 == 0, and at
+ * scaleLog2 1 or 2 the one HapGpuDecompressRGBAScaled writes; alpha is ignored.  All in 32-bit signed integers with >>
+ * arithmetic:
+ *     Y[y][x]  = lo + ((yr * R + yg * G + yb * B + 32768) >> 16)      of texel d(x, y); no clamp is ever needed
+ *     Rs, Gs, Bs = the sums of R, G, B over the four texels d(2i..2i+1, 2j..2j+1)      (0 .. 1020)
+ *     Cb[j][i] = clamp255((-cbr * Rs - cbg * Gs + ch * Bs + (128 << 18) + (1 << 17)) >> 18)
+ *     Cr[j][i] = clamp255(( ch * Rs - crg * Gs - crb * Bs + (128 << 18) + (1 << 17)) >> 18)
+ * with Cb[j][i], Cr[j][i] = UV[j][2 * i], UV[j][2 * i + 1].  Each chroma sample is the mean of its 2 x 2 texels with one
+ * rounding, the counterpart of the encode side's replication; no filtering reaches across samples, so a 4 x 4 block gives
+ * exactly 4 x 4 Y samples and 2 x 2 pairs.  The coefficients are the standards' exact rationals times 65536 -- Kr, Kb =
+ * 0.299, 0.114 (BT601) or 0.2126, 0.0722 (BT709); Limited scales luma by 219/255 and chroma by 224/255 -- rounded to
+ * nearest, except one per row that is chosen by subtraction so that the row sums are exact: yg = round(65536 * sy) - yr -
+ * yb, cbg = ch - cbr, crg = ch - crb:
+ *     matrix, range        yr     yg    yb    cbr    cbg     ch    crg   crb   lo
+ *     BT601  Limited    16829  33039  6416   9714  19070  28784  24103  4681   16
+ *     BT601  Full       19595  38470  7471  11058  21710  32768  27439  5329    0
+ *     BT709  Limited    11966  40254  4064   6596  22188  28784  26145  2639   16
+ *     BT709  Full       13933  46871  4732   7509  25259  32768  29763  3005    0
+ * Greys give Cb = Cr = 128 exactly; white and black give 235 / 16 (Limited) or 255 / 0 (Full).  The chroma accumulators
+ * stay within 0 .. 2^26; Full range reaches 256 before the clamp, so the clamp is part of the definition.  Over all 2^24
+ * colours with four equal texels every sample is within 0.5021 of the exact real value, and RGB -> this definition ->
+ * HapGpuCompressNV12's comes back within 1, 1, 2 (Limited) and 1, 1, 1 (Full) of R, G, B.  With four different texels
+ * luma is per texel and keeps its bound; chroma, over every one of the 1021^3 sums (Rs, Gs, Bs), is within 0.5024 of the
+ * exact chroma of the texels' exact mean.
+ * textureFormat: RGB_DXT1, RGBA_DXT5 or YCoCg_DXT5; texture is host or device, under HapGpuDecompressRGBA's rules, and a
+ * device texture is aligned to what a lane reads of a block row (its block << scaleLog2, at most 16 bytes).  width and
+ * height are the texture's, multiples of 4 << scaleLog2; scaleLog2 0 to 2; at most 65535 output block rows.  Both planes
+ * are in DEVICE memory; their addresses and both pitches are multiples of 4, what a lane stores per row; lumaRowBytes >=
+ * W and chromaRowBytes >= W (W / 2 pairs).  Only the samples are written, nothing between rows.  Bad_Arguments, and
+ * nothing written, for anything else: a NULL, host or misaligned plane, a matrix or range outside the enums, another
+ * format, scaleLog2 above 2, a bad size or pitch.
+ * Out of scope: Hap R (BC7), Hap HDR (BC6H) and Alpha-Only (RGTC1) sources; an A8 plane beside the NV12; P010 and other
+ * 10/16-bit layouts, planar I420, 4:2:2 and 4:4:4; sited or filtered chroma, which needs neighbours across blocks;
+ * rectangles; host planes. */
+unsigned int HapGpuDecompressNV12(HapGpuContext *context,
+                                  const void *texture, unsigned long textureBytes, unsigned int textureFormat,
+                                  unsigned int width, unsigned int height, unsigned int scaleLog2,
+                                  unsigned int matrix, unsigned int range,
+                                  void *luma, unsigned long lumaRowBytes,
+                                  void *chroma, unsigned long chromaRowBytes);
+
+/* Frames in, NV12 video pictures out -- the way back of HapGpuEncodeFramesNV12: HapGpuDecodeFramesRGBA[Scaled] with the
+ * pictures of HapGpuDecompressNV12 in place of RGBA8 ones.  lumaPlanes[f] and chromaPlanes[f] are frame f's Y plane and
+ * its plane of interleaved Cb, Cr pairs, both in DEVICE memory, lumaRowBytes and chromaRowBytes shared by all frames;
+ * the pictures are W x H = (width >> scaleLog2) x (height >> scaleLog2), width and height being the FRAMES' geometry.
+ * The definition is HapGpuDecompressNV12's, with d the RGBA8 picture HapGpuDecodeFramesRGBA (scaleLog2 0) or
+ * HapGpuDecodeFramesRGBAScaled (1, 2) writes for the frame with the same textureCount and flags, alpha ignored, in
+ * 32-bit integers:
+ *     Y[y][x]  = lo + ((yr * R + yg * G + yb * B + 32768) >> 16)      of texel d(x, y)
+ *     Cb[j][i] = clamp255((-cbr * Rs - cbg * Gs + ch * Bs + (128 << 18) + (1 << 17)) >> 18)
+ *     Cr[j][i] = clamp255(( ch * Rs - crg * Gs - crb * Bs + (128 << 18) + (1 << 17)) >> 18)
+ * Rs, Gs, Bs being the sums over the four texels d(2i..2i+1, 2j..2j+1) and the coefficients those of the table there
+ * (matrix: HapGpuYCbCrMatrix, range: HapGpuYCbCrRange).  No RGBA8 picture ever exists: per Hap Q block 16 bytes are read
+ * and 24 written at full size, where decoding to RGBA8 and converting with a tensor library moves 16 + 64 + 64 + 24.
+ * Frames: Hap, Hap Alpha, Hap Q, and Hap Q Alpha with textureCount 2; the alpha plane is never block-decoded.  Mixed
+ * batches (one block-decode launch per format present), slicing, the second-stage flags and results[f] are
+ * HapGpuDecodeFramesRGBA's; HAPGPU_DECODE_BPTC_PICTURES is ignored.  Plane addresses and both pitches are multiples of
+ * 4; lumaRowBytes >= W and chromaRowBytes >= W; width and height multiples of 4 << scaleLog2; scaleLog2 0 to 2; at most
+ * 65535 output block rows.  Only the samples are written, nothing between rows.
+ * A broken frame (HapDecode's code), a frame of another format or geometry, or a frame either of whose planes is NULL, in
+ * host memory or misaligned (Bad_Arguments) fails alone: its planes are left untouched and the other frames are
+ * decoded.  The function's result is the first failure.  Bad_Arguments for the whole call -- every results[f] set,
+ * nothing written, no device touched -- for a NULL array, scaleLog2 above 2, a width or height that is no multiple of
+ * 4 << scaleLog2, a pitch that is no multiple of 4 or below W, more than 65535 output block rows, a textureCount other
+ * than 1 or 2, or a matrix or range outside the enums.  A context between a ...Begin and HapGpuEncodeFramesFinish:
+ * Internal_Error.
+ * Out of scope: Hap R (BC7), Hap HDR (BC6H) and Alpha-Only (RGTC1) sources; an A8 plane beside the NV12; P010 and other
+ * 10/16-bit layouts, planar I420, 4:2:2 and 4:4:4; sited or filtered chroma, which needs neighbours across blocks;
+ * rectangles; host planes; ...OnDevices and ...Sequence forms of this call. */
+unsigned int HapGpuDecodeFramesNV12(HapGpuContext *context, unsigned int frameCount,
+                                    const void *const *inputBuffers,
+                                    const unsigned long *inputBuffersBytes,
+                                    unsigned int textureCount,
+                                    void *const *lumaPlanes, unsigned long lumaRowBytes,
+                                    void *const *chromaPlanes, unsigned long chromaRowBytes,
+                                    unsigned int matrix, unsigned int range,
+                                    unsigned int width, unsigned int height, unsigned int scaleLog2,
+                                    unsigned int *results,
+                                    unsigned int flags);
 
 /* Hap HDR frames in, RGBA16F pictures out: HapGpuDecodeFramesRGBA for frames of one BC6H texture (unsigned or
  * signed; a batch may mix the two: one block-decode launch per signedness present), pictures as
