@@ -29,6 +29,20 @@ __device__ __forceinline__ int mad24k(int a, int c)
     asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "i"(K), "v"(c));
     return r;
 }
+// a * b + c on the unsigned 24-bit multiplier: the low 24 bits of a and of b, the low 32 bits of the sum
+__device__ __forceinline__ unsigned mad24u(unsigned a, unsigned b, unsigned c)
+{
+    unsigned r;
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+template <int K>      // a * K + K, K an inline constant: K (a + 1)
+__device__ __forceinline__ unsigned mad24uk(unsigned a)
+{
+    unsigned r;
+    asm("v_mad_u32_u24 %0, %1, %2, %2" : "=v"(r) : "v"(a), "i"(K));
+    return r;
+}
 
 __device__ __forceinline__ int quant5(int v) { int t = mad24k<31>(v, 128); return (t + (t >> 8)) >> 8; }
 __device__ __forceinline__ int quant6(int v) { int t = mad24k<63>(v, 128); return (t + (t >> 8)) >> 8; }
@@ -103,6 +117,50 @@ __device__ __forceinline__ uint2 alpha_block(const int (&a)[16])
     // a0 + BIAS | (a1 + BIAS) << 8 as one sum: the two bytes do not meet
     const unsigned long long v = (unsigned long long)(unsigned)(a0 + (a1 << 8) + BIAS * 257) | (bits << 16);
     return make_uint2((unsigned)v, (unsigned)(v >> 32));
+}
+
+// The luma half of a scaled YCoCg block from NEGATED luma in byte 1: v[i] = 256 (255 - Y), what row 0 of the BIASED
+// matrix form delivers less its junk byte (ycocg_weight_rows_biased(); the fused kernel alone).  The same block as
+// alpha_block<128> makes from Y - 128, at two instructions a pixel for the ramp where that has three.
+// With n = 255 - Y the definition's u = a0 - a is n - min n, so the box is taken on v as it stands and
+//     x = (14 u + max(d - 6, 0)) m + 2^20  =  14 m n + start,   start = max(d - 6, 0) m + 2^20 - 14 m min n,
+// whose bits 22..20 are (r + 1) mod 8 (x is below 2^24; its bit 23, set for r = 7 alone, is what the field drops anyway).
+// v (2 * 14 m) = 512 * 14 m n: the unsigned 24-bit multiply-add (v below 2^16, 28 m at most 28 (2^19 + 1), below 2^24)
+// leaves x << 9 modulo 2^32 when it starts from start << 9, so the field stands in the TOP three bits of the result and
+// the funnel shift takes it from there, v_alignbit(acc, x9, 29) = acc << 3 | field -- the form gather_indices has, and
+// like it walking each eight pixels from the last to the first.  The codes then stand in bits 23..0, pixel 0 lowest.
+// Once a block the two end bytes come back as 255 - n, minimum and maximum changing places.
+// (tests/test_luma_row_identity.py: the row for every R, G, B, and this form against alpha_block's and the
+// definition's for every range, offset and pixel value.)
+__device__ __forceinline__ uint2 luma_block_negated(const unsigned (&v)[16])
+{
+    unsigned lo = v[0], hi = v[0];
+#pragma unroll
+    for (int i = 1; i < 16; i++) {
+        lo = min(lo, v[i]);
+        hi = max(hi, v[i]);
+    }
+    unsigned lo24 = 0, hi24 = 0;       // 3-bit codes of pixels 0..7 and 8..15
+    if (lo != hi) {
+        const unsigned d = (hi - lo) >> 8;
+        // m = floor(2^19 / d) + 1 as in alpha_block; the products on the 24-bit multiplier by name (left to itself the
+        // compiler folds the + 1 into 64-bit multiply-adds, quarter rate)
+        const unsigned m1 = (unsigned)(524288.0f * __builtin_amdgcn_rcpf((float)d));          // m - 1
+        const unsigned m28 = mad24uk<28>(m1);
+        const unsigned d6 = (unsigned)max((int)d - 6, 0);
+        const unsigned start9 = ((mad24u(d6, m1, d6) << 9) + (1u << 29)) - mad24u(lo, m28, 0u);   // modulo 2^32
+#pragma unroll
+        for (int i = 7; i >= 0; i--) {
+            lo24 = __builtin_amdgcn_alignbit(lo24, mad24u(v[i], m28, start9), 29);
+            hi24 = __builtin_amdgcn_alignbit(hi24, mad24u(v[i + 8], m28, start9), 29);
+        }
+        lo24 = ramp_codes(lo24);
+        hi24 = ramp_codes(hi24);
+    }
+    const unsigned long long bits = (unsigned long long)lo24 | ((unsigned long long)hi24 << 24);
+    // a0 | a1 << 8 = 255 - min n | (255 - max n) << 8: min n from byte 1 of lo to byte 0, max n where it stands
+    const unsigned long long w = (unsigned long long)(((lo >> 8) | hi) ^ 0xFFFFu) | (bits << 16);
+    return make_uint2((unsigned)w, (unsigned)(w >> 32));
 }
 
 // 2-bit indices of 16 pixels for the palette p0, p1, (2 p0 + p1) / 3, (p0 + 2 p1) / 3 (oracle/bc_oracle.c,
@@ -509,10 +567,11 @@ __device__ __forceinline__ uint2 ycocg_colour_block_scalar(const unsigned (&cc)[
 // (the 128s of rows 1 and 2 cancel: their weights sum to zero; Co's row is doubled so that one constant serves all
 // three).  Per pixel: v_xor, the matrix instruction, v_ashrrev (Y), v_perm_b32 + v_pk_ashrrev_i16 (Co | Cg << 16, signed
 // halves) -- four vector instructions and one on the matrix pipe, where the dot-product form has seven.
-// BIASED: C is a register tuple instead, one addend a row (ycocg_addend(): 2, 2 + 512, 2 + 512, 0 in every lane), so
+// BIASED: C is a register tuple instead, one addend a row (ycocg_addend(): 32576, 2 + 512, 2 + 512, 0 in every lane), so
 // rows 1 and 2 come out 512 higher and the same v_perm_b32 + v_pk_ashrrev_i16 deliver Co | Cg << 16 as the definition's
-// own values, 1..256 a half, which is what ycocg_colour_block<true>'s pixel loops want; Y stays centred, which is what
-// alpha_block<128> takes.  The same instructions a pixel; the tuple's four registers are the price.
+// own values, 1..256 a half, which is what ycocg_colour_block<true>'s pixel loops want; row 0 has weights of its own
+// (ycocg_weight_rows_biased()) and delivers 256 (255 - Y) + junk below 256, one v_and_b32 where the v_ashrrev_i32 stands,
+// which is what luma_block_negated() takes.  The same instructions a pixel; the tuple's four registers are the price.
 //
 // The matrix instruction READS all 64 lanes whatever EXEC says (it writes the active ones only): a lane's result needs
 // the weight dwords of lanes 0..2 of its group whether or not those run.  So the weight register is made ONCE, at the
@@ -529,11 +588,25 @@ __device__ __forceinline__ unsigned ycocg_weight_rows()
     return r;
 }
 
+// The BIASED form's weights: rows 1 and 2 as above, row 0 NEGATED and scaled by 64, -64, -128, -64, 0 (+128 is no signed
+// byte; -128 is).  With S = R + 2G + B + 2 = 4 Y + f the row makes -64 (S - 2 - 512), and its addend 32576 brings that to
+//     65472 - 64 S  =  256 (255 - Y) + 64 (3 - f):
+// a non-negative 16-bit number whose byte 1 is 255 - Y exactly and whose byte 0 (0, 64, 128 or 192) is dropped by one
+// v_and_b32 where the centred form has its v_ashrrev_i32 -- luma in the form luma_block_negated() takes.
+__device__ __forceinline__ unsigned ycocg_weight_rows_biased()
+{
+    const unsigned row = threadIdx.x & 3u;
+    const unsigned w = row == 0u ? 0x00C080C0u : (row == 1u ? 0x00FE0002u : (row == 2u ? 0x00FF02FFu : 0u));
+    unsigned r;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(r) : "v"(w));
+    return r;
+}
+
 // The BIASED form's addend tuple, made beside the weights at the kernel's entry and handed down with them: a value the
 // optimiser cannot see through is one it cannot make again, register by register, between two matrix instructions.
 __device__ __forceinline__ mfma_i32x4 ycocg_addend()
 {
-    mfma_i32x4 c = {2, 2 + 512, 2 + 512, 0};
+    mfma_i32x4 c = {32576, 2 + 512, 2 + 512, 0};
     asm volatile("" : "+v"(c));
     return c;
 }
@@ -566,8 +639,8 @@ __device__ __forceinline__ void ycocg_pair_first(mfma_i32x4 &ta, mfma_i32x4 &tb,
             : [ta] "=&v"(ta), [tb] "=&v"(tb), [qa] "=&v"(qa), [qb] "=&v"(qb)
             : [pa] "v"(pa), [pb] "v"(pb), [w] "v"(rows), [k80] "s"(0x80808080u));
 }
-// pixels pa, pb in, their results to ta, tb; Y - 128 and Co | Cg << 16 (centred or BIASED) of the two pixels whose
-// results ta, tb held before out
+// pixels pa, pb in, their results to ta, tb; Y - 128 (BIASED: 256 (255 - Y)) and Co | Cg << 16 (centred or BIASED) of
+// the two pixels whose results ta, tb held before out
 template <bool BIASED>
 __device__ __forceinline__ void ycocg_pair(mfma_i32x4 &ta, mfma_i32x4 &tb, int &ya, int &yb, unsigned &cca, unsigned &ccb,
                                            unsigned pa, unsigned pb, unsigned rows, const mfma_i32x4 &addend)
@@ -576,13 +649,13 @@ __device__ __forceinline__ void ycocg_pair(mfma_i32x4 &ta, mfma_i32x4 &tb, int &
     unsigned qa, qb;
     if (BIASED)
         asm("v_xor_b32 %[qa], %[k80], %[pa]\n\tv_xor_b32 %[qb], %[k80], %[pb]\n\t"
-            "v_ashrrev_i32 %[ya], 2, %[oax]\n\tv_ashrrev_i32 %[yb], 2, %[obx]\n\t"
+            "v_and_b32 %[ya], %[kff], %[oax]\n\tv_and_b32 %[yb], %[kff], %[obx]\n\t"
             "v_perm_b32 %[ca], %[oaz], %[oay], %[sel]\n\tv_perm_b32 %[cb], %[obz], %[oby], %[sel]\n\t"
             HAPBC_YCOCG_SHIFT("%[ca]")
             HAPBC_YCOCG_MFMA "%[ta], %[w], %[qa], %[c]\n\t" HAPBC_YCOCG_MFMA "%[tb], %[w], %[qb], %[c]\n\t"
             HAPBC_YCOCG_SHIFT("%[cb]") "s_nop 3"
             : [ta] "+v"(ta), [tb] "+v"(tb), [ya] "=&v"(ya), [yb] "=&v"(yb), [ca] "=&v"(cca), [cb] "=&v"(ccb), [qa] "=&v"(qa), [qb] "=&v"(qb)
-            : [pa] "v"(pa), [pb] "v"(pb), [w] "v"(rows), [c] "v"(addend), [k80] "s"(0x80808080u), [sel] "s"(0x05040100),
+            : [pa] "v"(pa), [pb] "v"(pb), [w] "v"(rows), [c] "v"(addend), [k80] "s"(0x80808080u), [kff] "s"(0xFF00u), [sel] "s"(0x05040100),
               [oax] "v"(oa.x), [oay] "v"(oa.y), [oaz] "v"(oa.z), [obx] "v"(ob.x), [oby] "v"(ob.y), [obz] "v"(ob.z));
     else
         asm("v_xor_b32 %[qa], %[k80], %[pa]\n\tv_xor_b32 %[qb], %[k80], %[pb]\n\t"
@@ -596,8 +669,16 @@ __device__ __forceinline__ void ycocg_pair(mfma_i32x4 &ta, mfma_i32x4 &tb, int &
               [oax] "v"(oa.x), [oay] "v"(oa.y), [oaz] "v"(oa.z), [obx] "v"(ob.x), [oby] "v"(ob.y), [obz] "v"(ob.z));
 }
 // last statement of a block: the readers alone
+template <bool BIASED>
 __device__ __forceinline__ void ycocg_pair_last(int &ya, int &yb, unsigned &cca, unsigned &ccb, mfma_i32x4 oa, mfma_i32x4 ob)
 {
+    if (BIASED)
+        asm("v_and_b32 %[ya], %[kff], %[oax]\n\tv_and_b32 %[yb], %[kff], %[obx]\n\t"
+            "v_perm_b32 %[ca], %[oaz], %[oay], %[sel]\n\tv_perm_b32 %[cb], %[obz], %[oby], %[sel]\n\t"
+            HAPBC_YCOCG_SHIFT("%[ca]") "v_pk_ashrrev_i16 %[cb], 2, %[cb] op_sel_hi:[0,1]"
+            : [ya] "=&v"(ya), [yb] "=&v"(yb), [ca] "=&v"(cca), [cb] "=&v"(ccb)
+            : [sel] "s"(0x05040100), [kff] "s"(0xFF00u), [oax] "v"(oa.x), [oay] "v"(oa.y), [oaz] "v"(oa.z), [obx] "v"(ob.x), [oby] "v"(ob.y), [obz] "v"(ob.z));
+    else
     asm("v_ashrrev_i32 %[ya], 2, %[oax]\n\tv_ashrrev_i32 %[yb], 2, %[obx]\n\t"
         "v_perm_b32 %[ca], %[oaz], %[oay], %[sel]\n\tv_perm_b32 %[cb], %[obz], %[oby], %[sel]\n\t"
         HAPBC_YCOCG_SHIFT("%[ca]") "v_pk_ashrrev_i16 %[cb], 2, %[cb] op_sel_hi:[0,1]"
@@ -660,7 +741,8 @@ __device__ __forceinline__ uint4 block_of(const unsigned (&p)[16], unsigned rows
         return make_uint4(ab.x, ab.y, cb.x, cb.y);
     } else {
         // Y = (R+2G+B+2)>>2 ; Co = ((R-B+1)>>1)+128 ; Cg = ((-R+2G-B+2)>>2)+128 ; no clamp (oracle/bc_oracle.c).  Y
-        // leaves here less 128; Co and Cg as they are from the BIASED matrix form, less 128 otherwise.
+        // leaves here less 128 (from the BIASED matrix form as 256 (255 - Y)); Co and Cg as they are from the BIASED
+        // matrix form, less 128 otherwise.
         int y[16];
         unsigned cc[16];
         if (MATRIX) {
@@ -669,7 +751,7 @@ __device__ __forceinline__ uint4 block_of(const unsigned (&p)[16], unsigned rows
 #pragma unroll
             for (int i = 2; i < 16; i += 2)
                 ycocg_pair<BIASED>(ta, tb, y[i - 2], y[i - 1], cc[i - 2], cc[i - 1], p[i], p[i + 1], rows, addend);
-            ycocg_pair_last(y[14], y[15], cc[14], cc[15], ta, tb);
+            ycocg_pair_last<BIASED>(y[14], y[15], cc[14], cc[15], ta, tb);
         } else {
 #pragma unroll
             for (int i = 0; i < 16; i++) {
@@ -689,7 +771,9 @@ __device__ __forceinline__ uint4 block_of(const unsigned (&p)[16], unsigned rows
                 }
             }
         }
-        const uint2 ab = alpha_block<128>(y), cb = MATRIX ? ycocg_colour_block<BIASED>(cc) : ycocg_colour_block_scalar(cc);
+        // (BIASED: y holds 256 (255 - Y), non-negative, and the luma half takes it as that)
+        const uint2 ab = (MATRIX && BIASED) ? luma_block_negated(reinterpret_cast<const unsigned (&)[16]>(y)) : alpha_block<128>(y);
+        const uint2 cb = MATRIX ? ycocg_colour_block<BIASED>(cc) : ycocg_colour_block_scalar(cc);
         return make_uint4(ab.x, ab.y, cb.x, cb.y);
     }
 }

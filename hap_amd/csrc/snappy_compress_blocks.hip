@@ -277,7 +277,7 @@ __global__ __launch_bounds__(64, (FUSED == hapbc::kFmtYCoCg && SCB_MIN_WAVES < 5
 
     const unsigned lane = threadIdx.x;
     // (before any return or branch: every lane of the wave must hold its weight row, bc_encode_core.hpp)
-    const unsigned ycocg_rows = FUSED == hapbc::kFmtYCoCg ? hapbc::ycocg_weight_rows() : 0u;
+    const unsigned ycocg_rows = FUSED == hapbc::kFmtYCoCg ? hapbc::ycocg_weight_rows_biased() : 0u;
     const hapbc::mfma_i32x4 ycocg_add = FUSED == hapbc::kFmtYCoCg ? hapbc::ycocg_addend() : hapbc::mfma_i32x4{};
     // Single-texture launches take their frames interleaved: consecutive workgroups work on different frames, so the
     // fragments of one frame that are in flight together are few -- a placed stream waits for the sizes of everything
