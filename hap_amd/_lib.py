@@ -18,6 +18,12 @@ class HapGpuPictureError(C.Structure):
     _fields_ = [("sse", C.c_ulonglong * 4), ("sad", C.c_ulonglong * 4), ("texels", C.c_ulonglong)]
 
 
+class HapGpuPlacement(C.Structure):
+    """include/hap_gpu.h's HapGpuPlacement: a rectangle of a layer's picture and where it lands on the canvas"""
+    _fields_ = [("srcX", C.c_uint), ("srcY", C.c_uint), ("width", C.c_uint), ("height", C.c_uint), ("dstX", C.c_int),
+                ("dstY", C.c_int)]
+
+
 def _load():
     # PyTorch wheels bundle their own libamdhip64/libhsa-runtime64 (same SONAMEs as /opt/rocm's).
     # Two HIP runtimes in one process fight over the device, so when torch is installed let it
@@ -106,6 +112,10 @@ def _load():
         "HapGpuMeasureFrames": (u, [vp, u, P(vp), P(ul), u, P(vp), u, u, ul, P(HapGpuPictureError), P(u), u]),
         "HapGpuCompositeTextures": (u, [vp, u, P(vp), P(ul), P(u), P(vp), P(ul), P(C.c_ubyte), P(C.c_ubyte), u, u, vp, ul]),
         "HapGpuCompositeFrames": (u, [vp, u, u, P(vp), P(ul), P(u), P(C.c_ubyte), P(C.c_ubyte), P(vp), u, u, ul, P(u), u]),
+        "HapGpuCompositeTexturesPlaced": (u, [vp, u, P(vp), P(ul), P(u), P(vp), P(ul), P(u), P(u), P(HapGpuPlacement),
+                                              P(C.c_ubyte), P(C.c_ubyte), u, u, vp, ul]),
+        "HapGpuCompositeFramesPlaced": (u, [vp, u, u, P(vp), P(ul), P(u), P(u), P(u), P(HapGpuPlacement), P(C.c_ubyte),
+                                            P(C.c_ubyte), P(vp), u, u, ul, P(u), u]),
         "HapGpuTranscodeTexture": (u, [vp, vp, ul, u, vp, ul, u, u, u, u, P(u), P(vp), P(ul), P(ul)]),
         "HapGpuTranscodeFrames": (u, [vp, u, P(vp), P(ul), u, u, u, u, u, P(u), P(u), P(u), P(vp), P(ul), P(ul), P(u), u, u]),
         "HapGpuDecodeFramesRGBAHalf": (u, [vp, u, P(vp), P(ul), P(vp), u, u, ul, P(u), u]),

@@ -6,7 +6,7 @@ Buffers may be bytes / bytearray / numpy arrays (host) or objects exposing
 import ctypes as C
 import os
 
-from ._lib import CALLBACK, WORK_FN, HapGpuPictureError, lib
+from ._lib import CALLBACK, WORK_FN, HapGpuPictureError, HapGpuPlacement, lib
 
 
 class HapTextureFormat:
@@ -179,6 +179,16 @@ def _picture_address(picture, keep):
     address, _n, alive = _addr_len(picture)
     keep.append(alive)
     return address
+
+
+def _placement_array(placements, count):
+    """`count` 6-tuples (srcX, srcY, width, height, dstX, dstY) as a HapGpuPlacement array; None stays None"""
+    if placements is None:
+        return None
+    placements = [tuple(p) for p in placements]
+    if len(placements) != count or any(len(p) != 6 for p in placements):
+        raise ValueError("one placement of six numbers per layer")
+    return (HapGpuPlacement * max(1, count))(*[HapGpuPlacement(*p) for p in placements])
 
 
 def _addr_len(buf):
@@ -987,6 +997,76 @@ class Context:
         results = (C.c_uint * max(1, len(flat)))()
         r = lib.HapGpuCompositeFrames(self.handle, nf, nl, ptrs, lens, counts, ops, bg, optrs, width, height,
                                       row_bytes or width * 4, results, flags)
+        return r, list(results)[: len(flat)]
+
+    def composite_textures_placed(self, layers, layer_sizes, width, height, placements=None, opacities=None, background=None,
+                                  rgba=None, row_bytes=None):
+        """composite_textures for layers of sizes of their own, each placed and clipped on the width x height canvas
+        (HapGpuCompositeTexturesPlaced).  layer_sizes: (width, height) per layer; placements: per layer a 6-tuple
+        (srcX, srcY, width, height, dstX, dstY), all multiples of 4 -- the rectangle of the layer's picture and where its
+        top-left texel lands on the canvas (None: every layer whole at (0, 0)).  A canvas texel a rectangle does not
+        cover keeps what it has; what falls outside the canvas is clipped.
+        Returns (result, bytes | None), or (result, None) into `rgba`."""
+        n = len(layers)
+        if len(layer_sizes) != n:
+            raise ValueError("one size per layer")
+        infos = [_addr_len(t) for t, _f, _a in layers]
+        ainfos = [_addr_len(a) for _t, _f, a in layers]
+        ptrs = (C.c_void_p * n)(*[i[0] for i in infos])
+        lens = (C.c_ulong * n)(*[i[1] for i in infos])
+        fmts = (C.c_uint * n)(*[f for _t, f, _a in layers])
+        aptrs = (C.c_void_p * n)(*[i[0] for i in ainfos])
+        alens = (C.c_ulong * n)(*[i[1] for i in ainfos])
+        lws = (C.c_uint * n)(*[w for w, _h in layer_sizes])
+        lhs = (C.c_uint * n)(*[h for _w, h in layer_sizes])
+        places = _placement_array(placements, n)
+        ops = (C.c_ubyte * n)(*opacities) if opacities is not None else None
+        bg = (C.c_ubyte * 4)(*background) if background is not None else None
+        row_bytes = row_bytes or width * 4
+        own = rgba is None
+        if own:
+            rgba = (C.c_ubyte * (row_bytes * height + 16))()
+            base = C.addressof(rgba)
+            oa = base + (-base) % 16
+        else:
+            oa, _on, _k = _addr_len(rgba)
+        r = lib.HapGpuCompositeTexturesPlaced(self.handle, n, ptrs, lens, fmts, aptrs, alens, lws, lhs, places, ops, bg, width,
+                                              height, oa, row_bytes)
+        if own:
+            return r, (C.string_at(oa, row_bytes * height) if r == 0 else None)
+        return r, None
+
+    def composite_frames_placed(self, frames, frame_bytes, texture_counts, layer_sizes, rgba_frames, width, height,
+                                placements=None, opacities=None, background=None, row_bytes=None, flags=0):
+        """composite_frames for layers of sizes of their own, each placed and clipped on the width x height canvas
+        (HapGpuCompositeFramesPlaced).  layer_sizes: (width, height) per layer, the same in every output frame;
+        placements: a list per output frame of a 6-tuple (srcX, srcY, width, height, dstX, dstY) per layer (None: every
+        layer whole at (0, 0)).  The definition is composite_textures_placed's with decode_frames_rgba's bytes.
+        Returns (result, results[]): one entry per output frame and layer, entry f * layers + l."""
+        nf = len(frames)
+        nl = len(frames[0]) if nf else len(layer_sizes)
+        if len(rgba_frames) != nf:
+            raise ValueError("one picture per output frame")
+        if any(len(fr) != nl for fr in frames):
+            raise ValueError("every output frame has the same number of layers")
+        if len(layer_sizes) != nl:
+            raise ValueError("one size per layer")
+        if placements is not None and (len(placements) != nf or any(len(fr) != nl for fr in placements)):
+            raise ValueError("one placement per output frame and layer")
+        flat = [b for fr in frames for b in fr]
+        ptrs, infos = self._ptr_array(flat)
+        given = [None] * len(flat) if frame_bytes is None else [b for fr in frame_bytes for b in fr]
+        lens = (C.c_ulong * len(flat))(*[fb if fb is not None else infos[i][1] for i, fb in enumerate(given)])
+        counts = (C.c_uint * nl)(*texture_counts) if texture_counts is not None else None
+        lws = (C.c_uint * max(1, nl))(*[w for w, _h in layer_sizes])
+        lhs = (C.c_uint * max(1, nl))(*[h for _w, h in layer_sizes])
+        places = _placement_array(None if placements is None else [p for fr in placements for p in fr], len(flat))
+        ops = (C.c_ubyte * len(flat))(*[o for fr in opacities for o in fr]) if opacities is not None else None
+        bg = (C.c_ubyte * 4)(*background) if background is not None else None
+        optrs, _oinfos = self._ptr_array(rgba_frames)
+        results = (C.c_uint * max(1, len(flat)))()
+        r = lib.HapGpuCompositeFramesPlaced(self.handle, nf, nl, ptrs, lens, counts, lws, lhs, places, ops, bg, optrs, width,
+                                            height, row_bytes or width * 4, results, flags)
         return r, list(results)[: len(flat)]
 
     def measure_frames(self, frames, frame_bytes, texture_count, pictures, width, height, row_bytes=None, flags=0):

@@ -150,6 +150,85 @@ __global__ __launch_bounds__(256) void bc_composite_kernel(const HapGpuComposite
     }
 }
 
+// The same for layers of sizes of their own, placed and clipped on the canvas (hap_place.h).  A layer's descriptor adds
+// its clip in blocks; a lane is inside when its canvas block (bx, by) has bx - cx0 < cw and by - cy0 < ch, unsigned, and
+// then the layer's block under it is first + (by - cy0) * layer_blocks_x + (bx - cx0).  Only lanes inside load, decode
+// and blend: the whole of a layer's work is under that one divergent branch, so lanes outside keep their canvas
+// registers -- on the "opaque at opacity 255 replaces the canvas" shortcut too, wave-uniform in its condition and
+// lane-masked in its effect -- and a wave with no lane inside skips the layer's loads.  A layer of opacity 0 or with an
+// empty clip is not loaded.
+__global__ __launch_bounds__(256) void bc_composite_placed_kernel(const HapGpuPlacedLayer *__restrict__ layers,
+                                                                  unsigned layer_count, const uint64_t *__restrict__ outputs,
+                                                                  unsigned background, unsigned blocks_x,
+                                                                  unsigned blocks_total, size_t row_bytes)
+{
+    const HapGpuPlacedLayer *mine = layers + (size_t)blockIdx.z * layer_count;
+    uint8_t *rgba = (uint8_t *)outputs[blockIdx.z];
+    if (!rgba)
+        return;                     // (the whole workgroup: blockIdx.z is its picture)
+    for (unsigned l = 0; l < layer_count; l++)
+        if (!mine[l].texture)
+            return;
+    const unsigned id = blockIdx.x * 256u + threadIdx.x;
+    if (id >= blocks_total)
+        return;
+    const unsigned by = id / blocks_x, bx = id - by * blocks_x;
+    canvas_block c;
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        c.rb[i] = (background & 0xFFu) | ((background & 0x00FF0000u));
+        c.ga[i] = ((background >> 8) & 0xFFu) | ((background >> 8) & 0x00FF0000u);
+    }
+#pragma unroll 1
+    for (unsigned l = 0; l < layer_count; l++) {
+        // (wave-uniform: the descriptor's address is; readfirstlane says so to the branches below)
+        const unsigned opacity = __builtin_amdgcn_readfirstlane(mine[l].opacity);
+        const unsigned cw = __builtin_amdgcn_readfirstlane(mine[l].cw);
+        if (opacity == 0u || cw == 0u)
+            continue;               // a = 0 keeps every texel, an empty clip covers none: the layer is not loaded
+        const unsigned format = __builtin_amdgcn_readfirstlane(mine[l].format);
+        const unsigned ux = bx - __builtin_amdgcn_readfirstlane(mine[l].cx0);
+        const unsigned uy = by - __builtin_amdgcn_readfirstlane(mine[l].cy0);
+        const uint8_t *blocks = (const uint8_t *)mine[l].texture, *plane = (const uint8_t *)mine[l].alpha;
+        if (ux < cw && uy < __builtin_amdgcn_readfirstlane(mine[l].ch)) {
+            const unsigned lid = __builtin_amdgcn_readfirstlane(mine[l].first) +
+                                 uy * __builtin_amdgcn_readfirstlane(mine[l].layer_blocks_x) + ux;
+            unsigned px[16];
+            bool source_alpha = plane != nullptr;
+            if (format == 0x83F0u) {
+                if (plane)
+                    layer_texels<0, true>(blocks, plane, lid, px);
+                else
+                    layer_texels<0, false>(blocks, plane, lid, px);
+            } else if (format == 0x83F3u) {
+                source_alpha = true;
+                if (plane)
+                    layer_texels<1, true>(blocks, plane, lid, px);
+                else
+                    layer_texels<1, false>(blocks, plane, lid, px);
+            } else {
+                if (plane)
+                    layer_texels<2, true>(blocks, plane, lid, px);
+                else
+                    layer_texels<2, false>(blocks, plane, lid, px);
+            }
+            if (source_alpha)
+                blend_block<true>(px, opacity, c);
+            else
+                blend_block<false>(px, opacity, c);
+        }
+    }
+    uint8_t *dst = rgba + (size_t)(4u * by) * row_bytes + 16u * (size_t)bx;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        v4u v;
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            v[k] = __builtin_amdgcn_perm(c.ga[4 * r + k], c.rb[4 * r + k], 0x06020400u);     // R G B A
+        __builtin_nontemporal_store(v, reinterpret_cast<v4u *>(dst + (size_t)r * row_bytes));
+    }
+}
+
 } // namespace
 
 // hapgpu_abi.h.  Returns 0 launched, 1 bad arguments, 4 launch failure.
@@ -170,5 +249,26 @@ extern "C" int hapgpu_k_block_composite(hapgpu_rt *rt, const HapGpuCompositeLaye
     const dim3 grid((blocks_total + 255u) / 256u, 1, pictures);
     hipLaunchKernelGGL(bc_composite_kernel, grid, dim3(256), 0, stream, layers, layer_count, outputs, colour, blocks_x,
                        blocks_total, row_bytes);
+    return hipGetLastError() == hipSuccess ? 0 : 4;
+}
+
+// hapgpu_abi.h.  Returns 0 launched, 1 bad arguments, 4 launch failure.
+extern "C" int hapgpu_k_block_composite_placed(hapgpu_rt *rt, const HapGpuPlacedLayer *layers, unsigned layer_count,
+                                               const uint64_t *outputs, unsigned pictures, const unsigned char *background,
+                                               unsigned width, unsigned height, size_t row_bytes)
+{
+    scoped_timing st(rt, 6);
+    const hipStream_t stream = hapgpu_rt_stream(rt);
+    if (!layers || !outputs || !background || layer_count == 0 || layer_count > HAPGPU_COMPOSITE_LAYERS_MAX ||
+        pictures == 0 || pictures > 65535u || width == 0 || height == 0 || (width & 3u) || (height & 3u) ||
+        row_bytes < (size_t)width * 4u || (row_bytes & 15u) ||
+        (unsigned long long)(width / 4u) * (height / 4u) > 0xFFFFFFFFull / 256u * 255u)
+        return 1;
+    const unsigned blocks_x = width / 4u, blocks_total = blocks_x * (height / 4u);
+    const unsigned colour = (unsigned)background[0] | ((unsigned)background[1] << 8) | ((unsigned)background[2] << 16) |
+                            ((unsigned)background[3] << 24);
+    const dim3 grid((blocks_total + 255u) / 256u, 1, pictures);
+    hipLaunchKernelGGL(bc_composite_placed_kernel, grid, dim3(256), 0, stream, layers, layer_count, outputs, colour,
+                       blocks_x, blocks_total, row_bytes);
     return hipGetLastError() == hipSuccess ? 0 : 4;
 }

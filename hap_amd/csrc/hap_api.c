@@ -1171,6 +1171,54 @@ unsigned int HapGpuCompositeFrames(HapGpuContext *context, unsigned int frameCou
     return r;
 }
 
+/* ... with layers of sizes of their own, placed and clipped on the canvas: a layer size or a placement that is not in
+   order refuses the call like everything above, before the context is looked at */
+unsigned int HapGpuCompositeTexturesPlaced(HapGpuContext *context, unsigned int layerCount, const void *const *textures,
+                                           const unsigned long *texturesBytes, const unsigned int *textureFormats,
+                                           const void *const *alphaTextures, const unsigned long *alphaTexturesBytes,
+                                           const unsigned int *layerWidths, const unsigned int *layerHeights,
+                                           const HapGpuPlacement *placements, const unsigned char *opacities,
+                                           const unsigned char *background, unsigned int width, unsigned int height,
+                                           void *rgba, unsigned long rowBytes)
+{
+    unsigned r;
+    if (!context || !textures || !texturesBytes || !textureFormats || !rgba ||
+        !hapb_composite_placed_valid(layerCount, layerWidths, layerHeights, placements, 1u, width, height, rowBytes, NULL))
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_composite_textures_placed(context, layerCount, textures, texturesBytes, textureFormats, alphaTextures,
+                                       alphaTexturesBytes, layerWidths, layerHeights, placements, opacities, background,
+                                       width, height, rgba, rowBytes);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+unsigned int HapGpuCompositeFramesPlaced(HapGpuContext *context, unsigned int frameCount, unsigned int layerCount,
+                                         const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
+                                         const unsigned int *textureCounts, const unsigned int *layerWidths,
+                                         const unsigned int *layerHeights, const HapGpuPlacement *placements,
+                                         const unsigned char *opacities, const unsigned char *background,
+                                         void *const *rgbaFrames, unsigned int width, unsigned int height,
+                                         unsigned long rowBytes, unsigned int *results, unsigned int flags)
+{
+    unsigned r;
+    if (!results)
+        return HapResult_Bad_Arguments;
+    /* (what is wrong with the call itself sets every result whatever the context is, a NULL one included) */
+    if (!inputBuffers || !inputBuffersBytes || !rgbaFrames ||
+        !hapb_composite_placed_valid(layerCount, layerWidths, layerHeights, placements, frameCount, width, height,
+                                     rowBytes, textureCounts))
+        return refuse_call(results, (size_t)frameCount * layerCount);
+    if (!context)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_composite_frames_placed(context, frameCount, layerCount, inputBuffers, inputBuffersBytes, textureCounts,
+                                     layerWidths, layerHeights, placements, opacities, background, rgbaFrames, width,
+                                     height, rowBytes, results, flags);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
 /* HapGpuDecodeFramesRGBA of a block-aligned rectangle of every frame; any other rectangle refuses the whole call */
 unsigned int HapGpuDecodeFramesRGBARegion(HapGpuContext *context, unsigned int frameCount,
                                           const void *const *inputBuffers, const unsigned long *inputBuffersBytes,

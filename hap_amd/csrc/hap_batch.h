@@ -278,6 +278,29 @@ unsigned hapb_composite_frames(HapGpuContext *ctx, unsigned frame_count, unsigne
                                const unsigned long *input_bytes, const unsigned *texture_counts,
                                const unsigned char *opacities, const unsigned char *background, void *const *rgba_frames,
                                unsigned width, unsigned height, unsigned long row_bytes, unsigned *results, unsigned flags);
+/* what both placed compositing calls ask on top of hapb_composite_valid: 1 = every layer's size and every one of the
+   frame_count * layer_count placements (NULL: none to look at) are in order (hap_place.h; include/hap_gpu.h:
+   HapGpuCompositeTexturesPlaced, HapGpuCompositeFramesPlaced).  Touches no device. */
+int hapb_composite_placed_valid(unsigned layer_count, const unsigned *layer_widths, const unsigned *layer_heights,
+                                const HapGpuPlacement *placements, size_t frame_count, unsigned width, unsigned height,
+                                unsigned long row_bytes, const unsigned *texture_counts);
+/* hapb_composite_textures for layers of layer_widths[l] x layer_heights[l], placements[l] of each (NULL: whole, at
+   (0, 0)) placed and clipped on the width x height canvas (HapGpuCompositeTexturesPlaced) */
+unsigned hapb_composite_textures_placed(HapGpuContext *ctx, unsigned layer_count, const void *const *textures,
+                                        const unsigned long *texture_bytes, const unsigned *formats,
+                                        const void *const *alphas, const unsigned long *alpha_bytes,
+                                        const unsigned *layer_widths, const unsigned *layer_heights,
+                                        const HapGpuPlacement *placements, const unsigned char *opacities,
+                                        const unsigned char *background, unsigned width, unsigned height, void *picture,
+                                        unsigned long row_bytes);
+/* ... of frames: placements[f * layer_count + l] (HapGpuCompositeFramesPlaced) */
+unsigned hapb_composite_frames_placed(HapGpuContext *ctx, unsigned frame_count, unsigned layer_count,
+                                      const void *const *inputs, const unsigned long *input_bytes,
+                                      const unsigned *texture_counts, const unsigned *layer_widths,
+                                      const unsigned *layer_heights, const HapGpuPlacement *placements,
+                                      const unsigned char *opacities, const unsigned char *background,
+                                      void *const *rgba_frames, unsigned width, unsigned height, unsigned long row_bytes,
+                                      unsigned *results, unsigned flags);
 
 /* groups and output in device memory: tables through the host, payloads device to device */
 unsigned hapb_join_device(HapGpuContext *ctx, unsigned group_count, const void *const *frames,

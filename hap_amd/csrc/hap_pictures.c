@@ -6,6 +6,7 @@
  * which texture formats and what of its pictures follow from that description in one place each.
  */
 #include "hap_batch_private.h"
+#include "hap_place.h"
 #include "hap_region.h"
 #include "hap_slice.h"
 #include <stdlib.h>
@@ -368,6 +369,7 @@ typedef char slice_members_hold_layers[HAPGPU_COMPOSITE_MAX_LAYERS <= HAP_SLICE_
    (hap_slice.h).  The textures of one member stay adjacent: hapb_decode uploads a host frame once for them. */
 typedef struct slice_textures {
     hap_slice_layout at;
+    const hap_place_layout *placed;         /* (members of sizes of their own: their blocks and planes; else NULL) */
     unsigned width, height;
     /* per entry, one allocation (`in` is its start): what hapb_decode is given ... */
     const void **in;
@@ -380,16 +382,21 @@ typedef struct slice_textures {
     unsigned *fmts, *res;
 } slice_textures;
 
-/* counts: the members' texture counts (NULL: all 1); extra_per_frame: what else the caller holds per frame while a
-   slice's textures are held; rectangles != 0: room for a rectangle per entry.  0: out of memory */
-static int slice_textures_init(slice_textures *s, unsigned frame_count, unsigned member_count, const unsigned *counts,
-                               unsigned width, unsigned height, size_t extra_per_frame, int rectangles)
+/* the blocks of member m's textures, and how far behind its colour texture its plane lies */
+static size_t member_blocks(const slice_textures *s, unsigned m)
 {
-    size_t entries;
-    s->width = width;
-    s->height = height;
-    hap_slice_layout_of(&s->at, member_count, counts, width, height, extra_per_frame, frame_count);
-    entries = s->at.slice * s->at.entries_per_frame;
+    return s->placed ? s->placed->blocks_of[m] : s->at.blocks;
+}
+
+static size_t member_alpha_off(const slice_textures *s, unsigned m)
+{
+    return s->placed ? s->placed->alpha_off_of[m] : s->at.alpha_off;
+}
+
+/* the arrays of a slice's entries, s->at being laid out.  0: out of memory */
+static int slice_textures_alloc(slice_textures *s, int rectangles)
+{
+    const size_t entries = s->at.slice * s->at.entries_per_frame;
     s->in = (const void **)malloc(entries * (2u * sizeof(void *) + 3u * sizeof(unsigned long) + 3u * sizeof(unsigned) +
                                              (rectangles ? sizeof(HapGpuRegion) : 0u)));
     if (!s->in)
@@ -403,6 +410,29 @@ static int slice_textures_init(slice_textures *s, unsigned frame_count, unsigned
     s->res = s->fmts + entries;
     s->decode_regions = rectangles ? (HapGpuRegion *)(s->res + entries) : NULL;
     return 1;
+}
+
+/* counts: the members' texture counts (NULL: all 1); extra_per_frame: what else the caller holds per frame while a
+   slice's textures are held; rectangles != 0: room for a rectangle per entry.  0: out of memory */
+static int slice_textures_init(slice_textures *s, unsigned frame_count, unsigned member_count, const unsigned *counts,
+                               unsigned width, unsigned height, size_t extra_per_frame, int rectangles)
+{
+    s->placed = NULL;
+    s->width = width;
+    s->height = height;
+    hap_slice_layout_of(&s->at, member_count, counts, width, height, extra_per_frame, frame_count);
+    return slice_textures_alloc(s, rectangles);
+}
+
+/* ... for members of sizes of their own (`placed`: their layout, which the caller keeps while s is used); whole frames
+   alone: width and height are no member's and 0 */
+static int slice_textures_init_placed(slice_textures *s, const hap_place_layout *placed)
+{
+    s->placed = placed;
+    s->width = 0u;
+    s->height = 0u;
+    s->at = placed->at;
+    return slice_textures_alloc(s, 0);
 }
 
 /* Output frames done .. done + n of the call (n <= s->at.slice) into `textures`, at.per_frame * n bytes of D_BC_TEX
@@ -448,8 +478,8 @@ static void slice_textures_decode(HapGpuContext *ctx, const slice_textures *s, u
                     s->decode_regions[e] = own;
                 s->in[e] = refused ? NULL : inputs[(done + f) * members + m];
                 s->in_bytes[e] = input_bytes[(done + f) * members + m];
-                s->outs[e] = textures + s->at.per_frame * f + s->at.offset_of[m] + (t ? s->at.alpha_off : 0u);
-                s->caps[e] = (unsigned long)(t ? s->at.blocks * 8u : s->at.blocks * 16u);
+                s->outs[e] = textures + s->at.per_frame * f + s->at.offset_of[m] + (t ? member_alpha_off(s, m) : 0u);
+                s->caps[e] = (unsigned long)(t ? member_blocks(s, m) * 8u : member_blocks(s, m) * 16u);
                 s->idx[e] = t;
                 s->used[e] = 0;
                 s->fmts[e] = 0;
@@ -472,6 +502,15 @@ static int slice_entry_fits(const slice_textures *s, size_t e, unsigned count, c
     const unsigned fmt = s->fmts[e];
     return kind_of(kinds, kind_count, fmt) != kind_count && s->used[e] == s->at.blocks * hapf_block_bytes(fmt) &&
            (count != 2u || (s->fmts[e + 1] == HapTextureFormat_A_RGTC1 && s->used[e + 1] == s->at.blocks * 8u));
+}
+
+/* ... for member m of a slice whose members have sizes of their own: exactly that member's blocks */
+static int slice_entry_fits_member(const slice_textures *s, size_t e, unsigned m, const unsigned *kinds, unsigned kind_count)
+{
+    const unsigned fmt = s->fmts[e];
+    const size_t blocks = member_blocks(s, m);
+    return kind_of(kinds, kind_count, fmt) != kind_count && s->used[e] == blocks * hapf_block_bytes(fmt) &&
+           (s->at.count_of[m] != 2u || (s->fmts[e + 1] == HapTextureFormat_A_RGTC1 && s->used[e + 1] == blocks * 8u));
 }
 
 /* frames down a road (DESIGN.md's `decode_pictures`, its roads' descriptions being `picture_road`s): one picture each */
@@ -862,6 +901,267 @@ unsigned hapb_composite_frames(HapGpuContext *ctx, unsigned frame_count, unsigne
             rc |= hapgpu_rt_h2d(rt, dtab, htab, tab_bytes);
             rc |= hapgpu_k_block_composite(rt, (const HapGpuCompositeLayer *)(dtab + n), layer_count, dtab, n,
                                            background ? background : k_composite_background, width, height, row_bytes);
+            for (f = 0; f < n; f++)
+                if (htab[f] && !is_dev(ctx, rgba_frames[done + f]))
+                    rc |= picture_unstage(rt, rgba_frames[done + f], stage + align_up(shape.bytes, 256) * f, &shape);
+        }
+        rc |= hapgpu_rt_sync(rt);
+        for (i = done * layer_count; i < (done + n) * layer_count; i++) {
+            if (rc && results[i] == HapResult_No_Error && htab[i / layer_count - done])
+                results[i] = HapResult_Internal_Error;
+            if (results[i] != HapResult_No_Error && first_error == HapResult_No_Error)
+                first_error = results[i];
+        }
+    }
+    free(s.in);
+    return first_error;
+}
+
+/* ------------------------------------------------------------- ... of layers placed on the canvas */
+/* The two calls above for layers of sizes of their own, each with a rectangle of it placed and clipped on the canvas
+   (hap_place.h: the rules and the clip; bc_composite.hip's placed kernel).  A descriptor carries its layer's clip in
+   blocks; the second stage still decodes every layer's whole frame, into a scratch laid out by hap_place_layout_of. */
+
+int hapb_composite_placed_valid(unsigned layer_count, const unsigned *layer_widths, const unsigned *layer_heights,
+                                const HapGpuPlacement *placements, size_t frame_count, unsigned width, unsigned height,
+                                unsigned long row_bytes, const unsigned *texture_counts)
+{
+    size_t f;
+    unsigned l;
+    if (!hapb_composite_valid(layer_count, width, height, row_bytes, texture_counts) || !layer_widths || !layer_heights ||
+        !hap_place_layer_valid(width, height))
+        return 0;
+    for (l = 0; l < layer_count; l++)
+        if (!hap_place_layer_valid(layer_widths[l], layer_heights[l]))
+            return 0;
+    for (f = 0; placements && f < frame_count; f++)
+        for (l = 0; l < layer_count; l++) {
+            const HapGpuPlacement *p = &placements[f * layer_count + l];
+            if (!hap_place_valid(p->srcX, p->srcY, p->width, p->height, p->dstX, p->dstY, layer_widths[l], layer_heights[l]))
+                return 0;
+        }
+    return 1;
+}
+
+/* a descriptor's six clip words: placement p (NULL: the layer whole at (0, 0)) of a layer_w x layer_h layer on the canvas */
+static void placed_layer_clip(HapGpuPlacedLayer *d, const HapGpuPlacement *p, unsigned layer_w, unsigned layer_h,
+                              unsigned width, unsigned height)
+{
+    const HapGpuPlacement whole = {0u, 0u, layer_w, layer_h, 0, 0};
+    hap_place_clip c;
+    if (!p)
+        p = &whole;
+    hap_place_clip_of(&c, p->srcX, p->srcY, p->width, p->height, p->dstX, p->dstY, layer_w, width, height);
+    d->cx0 = c.cx0;
+    d->cy0 = c.cy0;
+    d->cw = c.cw;
+    d->ch = c.ch;
+    d->first = c.first;
+    d->layer_blocks_x = c.layer_blocks_x;
+}
+
+/* composite_table's for placed layers */
+static uint64_t *composite_placed_table(hapgpu_rt *rt, unsigned n, unsigned layer_count, uint64_t **device, size_t *bytes)
+{
+    uint64_t *htab;
+    *bytes = sizeof(uint64_t) * n + sizeof(HapGpuPlacedLayer) * (size_t)n * layer_count;
+    htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, *bytes);
+    *device = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, *bytes);
+    if (!htab || !*device)
+        return NULL;
+    memset(htab, 0, *bytes);
+    return htab;
+}
+
+unsigned hapb_composite_textures_placed(HapGpuContext *ctx, unsigned layer_count, const void *const *textures,
+                                        const unsigned long *texture_bytes, const unsigned *formats,
+                                        const void *const *alphas, const unsigned long *alpha_bytes,
+                                        const unsigned *layer_widths, const unsigned *layer_heights,
+                                        const HapGpuPlacement *placements, const unsigned char *opacities,
+                                        const unsigned char *background, unsigned width, unsigned height, void *picture,
+                                        unsigned long row_bytes)
+{
+    hapgpu_rt *rt = ctx->rt;
+    const size_t pixel_row = (size_t)width * 4u;
+    const picture_shape shape = {row_bytes, pixel_row, (size_t)row_bytes * (height ? height - 1u : 0u) + pixel_row, height};
+    size_t staged = 0, tab_bytes, at = 0;
+    uint64_t *htab, *dtab;
+    HapGpuPlacedLayer *hlayers;
+    uint8_t *stage = NULL, *picture_staged = NULL;
+    void *dst = picture;
+    unsigned l;
+    int rc;
+    if (!hapb_composite_placed_valid(layer_count, layer_widths, layer_heights, placements, 1u, width, height, row_bytes, NULL) ||
+        !textures || !texture_bytes || !formats || !picture)
+        return HapResult_Bad_Arguments;
+    if (context_busy(ctx, NULL, 0))
+        return HapResult_Internal_Error;
+    /* every layer: HapGpuDecompressRGBA's rules for its texture and its plane, at the layer's own size */
+    for (l = 0; l < layer_count; l++) {
+        const void *alpha = alphas ? alphas[l] : NULL;
+        const size_t blocks = (size_t)(layer_widths[l] / 4u) * (layer_heights[l] / 4u);
+        const size_t need = composite_format(formats[l]) ? blocks * hapf_block_bytes(formats[l]) : 0u;
+        if (!textures[l] || !need || texture_bytes[l] < need || (alpha && (!alpha_bytes || alpha_bytes[l] < blocks * 8u)) ||
+            (is_dev(ctx, textures[l]) && ((uintptr_t)textures[l] & (hapf_block_bytes(formats[l]) - 1u))) ||
+            (alpha && is_dev(ctx, alpha) && ((uintptr_t)alpha & 7u)))
+            return HapResult_Bad_Arguments;
+        if (!is_dev(ctx, textures[l]))
+            staged += align_up(need, 256);
+        if (alpha && !is_dev(ctx, alpha))
+            staged += align_up(blocks * 8u, 256);
+    }
+    if (is_dev(ctx, picture) && ((uintptr_t)picture & 15u))
+        return HapResult_Bad_Arguments;
+    /* (one request for all that is staged: an arena that grows forgets what it held) */
+    if (staged && !(stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, staged)))
+        return HapResult_Internal_Error;
+    if (!is_dev(ctx, picture) && !(dst = picture_stage(rt, &picture_staged, shape.bytes, 1u, 0u)))
+        return HapResult_Internal_Error;
+    htab = composite_placed_table(rt, 1u, layer_count, &dtab, &tab_bytes);
+    if (!htab)
+        return HapResult_Internal_Error;
+    hlayers = (HapGpuPlacedLayer *)(htab + 1);
+    htab[0] = (uint64_t)(uintptr_t)dst;
+    for (l = 0; l < layer_count; l++) {
+        const void *alpha = alphas ? alphas[l] : NULL, *src = textures[l];
+        const size_t blocks = (size_t)(layer_widths[l] / 4u) * (layer_heights[l] / 4u);
+        if (!is_dev(ctx, src)) {
+            const size_t need = blocks * hapf_block_bytes(formats[l]);
+            if (hapgpu_rt_h2d(rt, stage + at, src, need))
+                return HapResult_Internal_Error;
+            src = stage + at;
+            at += align_up(need, 256);
+        }
+        if (alpha && !is_dev(ctx, alpha)) {
+            if (hapgpu_rt_h2d(rt, stage + at, alpha, blocks * 8u))
+                return HapResult_Internal_Error;
+            alpha = stage + at;
+            at += align_up(blocks * 8u, 256);
+        }
+        hlayers[l].texture = (uint64_t)(uintptr_t)src;
+        hlayers[l].alpha = (uint64_t)(uintptr_t)alpha;
+        hlayers[l].format = formats[l];
+        hlayers[l].opacity = opacities ? opacities[l] : 255u;
+        placed_layer_clip(&hlayers[l], placements ? &placements[l] : NULL, layer_widths[l], layer_heights[l], width, height);
+    }
+    if (hapgpu_rt_h2d(rt, dtab, htab, tab_bytes))
+        return HapResult_Internal_Error;
+    rc = hapgpu_k_block_composite_placed(rt, (const HapGpuPlacedLayer *)(dtab + 1), layer_count, dtab, 1u,
+                                         background ? background : k_composite_background, width, height, row_bytes);
+    if (rc == 1)
+        return HapResult_Bad_Arguments;
+    if (rc)
+        return HapResult_Internal_Error;
+    if (dst != picture && picture_unstage(rt, picture, dst, &shape))
+        return HapResult_Internal_Error;
+    if (hapgpu_rt_sync(rt))
+        return HapResult_Internal_Error;
+    return HapResult_No_Error;
+}
+
+unsigned hapb_composite_frames_placed(HapGpuContext *ctx, unsigned frame_count, unsigned layer_count,
+                                      const void *const *inputs, const unsigned long *input_bytes,
+                                      const unsigned *texture_counts, const unsigned *layer_widths,
+                                      const unsigned *layer_heights, const HapGpuPlacement *placements,
+                                      const unsigned char *opacities, const unsigned char *background,
+                                      void *const *rgba_frames, unsigned width, unsigned height, unsigned long row_bytes,
+                                      unsigned *results, unsigned flags)
+{
+    hapgpu_rt *rt = ctx->rt;
+    const size_t pixel_row = (size_t)width * 4u;
+    const picture_shape shape = {row_bytes, pixel_row, (size_t)row_bytes * (height ? height - 1u : 0u) + pixel_row, height};
+    const size_t total = (size_t)frame_count * layer_count;
+    size_t done, i;
+    unsigned first_error = HapResult_No_Error, f, l;
+    hap_place_layout layout;
+    slice_textures s;
+    if (!results)
+        return HapResult_Bad_Arguments;
+    if (!hapb_composite_placed_valid(layer_count, layer_widths, layer_heights, placements, frame_count, width, height,
+                                     row_bytes, texture_counts) || !inputs || !input_bytes || !rgba_frames) {
+        for (i = 0; i < total; i++)
+            results[i] = HapResult_Bad_Arguments;
+        return HapResult_Bad_Arguments;
+    }
+    if (frame_count == 0)
+        return HapResult_No_Error;
+    /* output frames of a slice: at most 4 GiB of block textures and 32768 entries of the second stage at a time */
+    hap_place_layout_of(&layout, layer_count, texture_counts, layer_widths, layer_heights, 0u, frame_count);
+    if (context_busy(ctx, NULL, 0) || !slice_textures_init_placed(&s, &layout)) {
+        for (i = 0; i < total; i++)
+            results[i] = HapResult_Internal_Error;
+        return HapResult_Internal_Error;
+    }
+    for (done = 0; done < frame_count; done += s.at.slice) {
+        const unsigned n = (unsigned)(frame_count - done < s.at.slice ? frame_count - done : s.at.slice);
+        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, s.at.per_frame * n);
+        uint8_t *stage = NULL;
+        uint64_t *htab = NULL, *dtab = NULL;
+        HapGpuPlacedLayer *hlayers;
+        size_t tab_bytes = 0;
+        unsigned present = 0;
+        int rc = 0;
+        if (textures) {
+            /* the second stage of every layer of every output frame of the slice, one batch: whole frames */
+            slice_textures_decode(ctx, &s, textures, inputs, input_bytes, done, n, NULL, flags);
+            /* (after the second stage, which has tables of its own) */
+            htab = composite_placed_table(rt, n, layer_count, &dtab, &tab_bytes);
+        }
+        if (!htab) {
+            for (i = done * layer_count; i < (done + n) * layer_count; i++)
+                results[i] = HapResult_Internal_Error;
+            first_error = first_error ? first_error : HapResult_Internal_Error;
+            continue;
+        }
+        hlayers = (HapGpuPlacedLayer *)(htab + n);
+        for (f = 0; f < n; f++) {
+            unsigned *frame_results = results + (done + f) * layer_count;
+            void *dst = rgba_frames[done + f];
+            unsigned picture = HapResult_No_Error, all = HapResult_No_Error;
+            for (l = 0; l < layer_count; l++) {
+                const unsigned count = s.at.count_of[l];
+                const size_t e = (size_t)f * s.at.entries_per_frame + s.at.entry_of[l];
+                HapGpuPlacedLayer *d = &hlayers[(size_t)f * layer_count + l];
+                unsigned r = s.res[e];
+                if (r == HapResult_No_Error && count == 2u)
+                    r = s.res[e + 1];
+                /* the frame must hold exactly its layer's geometry, in one of the three formats a layer may have: a
+                   texture with more blocks than the layer's room holds is of another size like one with fewer */
+                if (r == HapResult_Buffer_Too_Small ||
+                    (r == HapResult_No_Error && !slice_entry_fits_member(&s, e, l, k_rgba_kinds, 3u)))
+                    r = HapResult_Bad_Arguments;
+                frame_results[l] = r;
+                if (r != HapResult_No_Error && all == HapResult_No_Error)
+                    all = r;
+                d->texture = (uint64_t)(uintptr_t)s.outs[e];
+                d->alpha = count == 2u ? (uint64_t)(uintptr_t)s.outs[e + 1] : 0u;
+                d->format = s.fmts[e];
+                d->opacity = opacities ? opacities[(done + f) * layer_count + l] : 255u;
+                placed_layer_clip(d, placements ? &placements[(done + f) * layer_count + l] : NULL, layer_widths[l],
+                                  layer_heights[l], width, height);
+            }
+            /* the picture: NULL or misaligned fails every layer's entry; host pictures are staged */
+            if (!dst || (is_dev(ctx, dst) && ((uintptr_t)dst & 15u))) {
+                picture = HapResult_Bad_Arguments;
+            } else if (all == HapResult_No_Error && !is_dev(ctx, dst)) {
+                dst = picture_stage(rt, &stage, align_up(shape.bytes, 256), n, f);
+                if (!dst)
+                    picture = HapResult_Internal_Error;
+            }
+            if (picture != HapResult_No_Error)
+                for (l = 0; l < layer_count; l++)
+                    frame_results[l] = picture;
+            /* (an output frame that is not written: picture address 0 skips it) */
+            if (picture == HapResult_No_Error && all == HapResult_No_Error) {
+                htab[f] = (uint64_t)(uintptr_t)dst;
+                present = 1;
+            }
+        }
+        if (present) {
+            rc |= hapgpu_rt_h2d(rt, dtab, htab, tab_bytes);
+            rc |= hapgpu_k_block_composite_placed(rt, (const HapGpuPlacedLayer *)(dtab + n), layer_count, dtab, n,
+                                                  background ? background : k_composite_background, width, height,
+                                                  row_bytes);
             for (f = 0; f < n; f++)
                 if (htab[f] && !is_dev(ctx, rgba_frames[done + f]))
                     rc |= picture_unstage(rt, rgba_frames[done + f], stage + align_up(shape.bytes, 256) * f, &shape);

@@ -511,6 +511,26 @@ typedef struct HapGpuCompositeLayer {
 int hapgpu_k_block_composite(hapgpu_rt *rt, const HapGpuCompositeLayer *layers, unsigned layer_count,
                              const uint64_t *outputs, unsigned pictures, const unsigned char *background, unsigned width,
                              unsigned height, size_t row_bytes);
+/* [device] One layer of one output picture of a placed composite launch: HapGpuCompositeLayer's four members, then
+   what of the layer is visible on the canvas, in blocks (hap_place.h: hap_place_clip) -- canvas blocks
+   cx0 <= bx < cx0 + cw, cy0 <= by < cy0 + ch have the layer's block first + (by - cy0) * layer_blocks_x + (bx - cx0)
+   under them, every other canvas block none of this layer; cw == 0: nothing visible.  48 bytes. */
+typedef struct HapGpuPlacedLayer {
+    uint64_t texture;
+    uint64_t alpha;
+    uint32_t format;
+    uint32_t opacity;        /* 0 .. 255 */
+    uint32_t cx0, cy0, cw, ch;
+    uint32_t first, layer_blocks_x;
+} HapGpuPlacedLayer;
+/* hapgpu_k_block_composite for layers of sizes of their own, placed and clipped on the canvas (bc_composite.hip): a
+   texel of a canvas block inside a layer's clip takes that layer's texel by the same three formulas, every other texel
+   is left as the canvas has it.  Every block index first + (ch - 1) * layer_blocks_x + cw - 1 and below must lie inside
+   the layer's texture (and plane): the launch does not know the layers' sizes.  Everything else -- outputs, background,
+   alignment, the profile class, the return codes -- as hapgpu_k_block_composite. */
+int hapgpu_k_block_composite_placed(hapgpu_rt *rt, const HapGpuPlacedLayer *layers, unsigned layer_count,
+                                    const uint64_t *outputs, unsigned pictures, const unsigned char *background,
+                                    unsigned width, unsigned height, size_t row_bytes);
 /* planar tensors -> blocks of `hap_texture_format`, without an RGBA8 picture in between (bc_encode_planes.hip): the way
    back of hapgpu_k_block_decode_planes.  Tensors (the first column of the table) of `channels` (3 or 4: R, G, B[, A])
    planes plane_bytes apart, rows row_bytes apart, elements of element_kind (0 half, 1 bfloat16, 2 float: e = 2, 2, 4

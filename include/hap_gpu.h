@@ -1002,6 +1002,90 @@ unsigned int HapGpuCompositeFrames(HapGpuContext *context, unsigned int frameCou
                                    unsigned int *results,
                                    unsigned int flags);
 
+/* A rectangle of a layer's picture and where it goes on the canvas of a placed compositing call
+ * (HapGpuCompositeTexturesPlaced, HapGpuCompositeFramesPlaced).  All six fields are multiples of 4: placements stay on the
+ * grid of 4 x 4 blocks. */
+typedef struct HapGpuPlacement {
+    unsigned int srcX, srcY, width, height;  /* a rectangle of the layer's picture, in texels */
+    int dstX, dstY;                          /* where the rectangle's top-left texel lands on the canvas */
+} HapGpuPlacement;
+
+/* HapGpuCompositeTextures for layers of sizes of their own, each placed and clipped on the canvas: a picture-in-picture
+ * inset, a lower third, a logo in a corner, a mosaic of clips, a window of a large clip on a smaller output.  The block
+ * decoder still blends the texels it holds in registers into a canvas block it keeps there: no layer's decoded picture
+ * is written or read, and a canvas block outside a layer's rectangle does not read that layer at all.
+ * The definition, and the only one.  The canvas is width x height, both multiples of 4.  Layer l is
+ * layerWidths[l] x layerHeights[l], both multiples of 4 and not 0; placements[l] is its placement.  A canvas texel (x, y)
+ * is covered by the layer when dstX <= x < dstX + width and dstY <= y < dstY + height (the placement's).  For a covered
+ * texel, (Rs, Gs, Bs, As) are the bytes HapGpuDecompressRGBA writes at (srcX + x - dstX, srcY + y - dstY) of the layer's
+ * picture, and HapGpuCompositeTextures' three formulas apply unchanged, with its canvas, background, opacities and order
+ * of layers:
+ *     a  = rdiv255(As * o)
+ *     Cd = rdiv255(Cs * a + Cd * (255 - a))      for C = R, G, B
+ *     Ad = a + rdiv255(Ad * (255 - a))           (never above 255)
+ * A texel that is not covered is left as the canvas has it.  Whatever of the rectangle falls outside the canvas is
+ * clipped; a rectangle wholly outside contributes nothing and is no error.  placements == NULL means every layer whole
+ * at (0, 0): {0, 0, layerWidths[l], layerHeights[l], 0, 0}; with every layer of the canvas's size that is
+ * HapGpuCompositeTextures' picture byte for byte.  Two calls give the same bytes.
+ * textures, texturesBytes, textureFormats, alphaTextures, alphaTexturesBytes, opacities, background, rgba and rowBytes are
+ * HapGpuCompositeTextures' and follow its rules, a texture and a plane having their own layer's blocks.
+ * Bad_Arguments, and nothing written and no device touched, for any of the six placement fields not a multiple of 4, a
+ * placement width or height of 0, a rectangle that leaves its layer (srcX + width above layerWidths[l], srcY + height
+ * above layerHeights[l]), |dstX| or |dstY| above 1 << 20, a layer size that is 0 or no multiple of 4 (or of 2^32 blocks
+ * and more), a NULL layerWidths or layerHeights, and everything HapGpuCompositeTextures refuses already.
+ * Out of scope: placements off the block grid; scaled or rotated layers; blend modes other than "over"; an existing
+ * picture as the bottom layer; Hap R, Hap HDR and Hap Alpha-Only layers; planar, NV12 or encoded output. */
+unsigned int HapGpuCompositeTexturesPlaced(HapGpuContext *context, unsigned int layerCount,
+                                           const void *const *textures, const unsigned long *texturesBytes,
+                                           const unsigned int *textureFormats,
+                                           const void *const *alphaTextures, const unsigned long *alphaTexturesBytes,
+                                           const unsigned int *layerWidths, const unsigned int *layerHeights,
+                                           const HapGpuPlacement *placements,
+                                           const unsigned char *opacities,
+                                           const unsigned char *background,
+                                           unsigned int width, unsigned int height, void *rgba, unsigned long rowBytes);
+
+/* HapGpuCompositeFrames for layers of sizes of their own, each placed and clipped on the canvas, with a placement per
+ * layer and output frame: placements[f * layerCount + l] is layer l's in output frame f, so an inset may move from frame
+ * to frame.  The canvas is width x height and layer l is layerWidths[l] x layerHeights[l], all multiples of 4 and not 0;
+ * a layer's size is the same in every output frame.
+ * The definition, and the only one, is HapGpuCompositeTexturesPlaced's with HapGpuDecodeFramesRGBA's bytes: a canvas
+ * texel (x, y) of output frame f is covered by layer l when dstX <= x < dstX + width and dstY <= y < dstY + height; for a
+ * covered texel, (Rs, Gs, Bs, As) are the bytes HapGpuDecodeFramesRGBA writes at (srcX + x - dstX, srcY + y - dstY) of
+ * the picture of that layer's frame, read with textureCounts[l] and the call's flags, and HapGpuCompositeFrames' three
+ * formulas apply unchanged:
+ *     a  = rdiv255(As * o)
+ *     Cd = rdiv255(Cs * a + Cd * (255 - a))      for C = R, G, B
+ *     Ad = a + rdiv255(Ad * (255 - a))           (never above 255)
+ * A texel that is not covered is left as the canvas has it.  Whatever of the rectangle falls outside the canvas is
+ * clipped; a rectangle wholly outside contributes nothing and is no error.  placements == NULL means every layer whole
+ * at (0, 0) in every output frame: {0, 0, layerWidths[l], layerHeights[l], 0, 0}; with every layer of the canvas's size
+ * that is HapGpuCompositeFrames' picture byte for byte.  Two calls give the same bytes.
+ * A layer's frame must hold a colour texture of exactly layerWidths[l] x layerHeights[l], and with textureCounts[l] == 2
+ * an RGTC1 plane of the same size: otherwise that entry of results is Bad_Arguments and that output frame is untouched.
+ * The second stage decodes every layer's whole frame, whatever of it the clip hides.  results, and that output picture f
+ * is written if and only if all its layers are No_Error and its picture pointer is usable; frames and pictures in host
+ * or device memory and the staging of host pictures; slices of at most 4 GiB of block textures and 32768 textures: all
+ * as HapGpuCompositeFrames has them.
+ * Bad_Arguments for the whole call -- every result set, nothing written, no device touched -- for any of the six
+ * placement fields of any placement not a multiple of 4, a placement width or height of 0, a rectangle that leaves its
+ * layer, |dstX| or |dstY| above 1 << 20, a layer size that is 0 or no multiple of 4 (or of 2^32 blocks and more), a NULL
+ * layerWidths or layerHeights, and everything HapGpuCompositeFrames refuses already.
+ * Out of scope: placements off the block grid; scaled or rotated layers; skipping the second stage of what a clip
+ * hides; blend modes other than "over"; an existing picture as the bottom layer; Hap R, Hap HDR and Hap Alpha-Only
+ * layers; planar, NV12 or encoded output; ...OnDevices and ...Sequence forms of this call. */
+unsigned int HapGpuCompositeFramesPlaced(HapGpuContext *context, unsigned int frameCount, unsigned int layerCount,
+                                         const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
+                                         const unsigned int *textureCounts,
+                                         const unsigned int *layerWidths, const unsigned int *layerHeights,
+                                         const HapGpuPlacement *placements,
+                                         const unsigned char *opacities,
+                                         const unsigned char *background,
+                                         void *const *rgbaFrames,
+                                         unsigned int width, unsigned int height, unsigned long rowBytes,
+                                         unsigned int *results,
+                                         unsigned int flags);
+
 /* Planar float tensors in, frames out -- the way back of HapGpuDecodeFramesPlanes: HapGpuEncodeFramesRGBA with the tensors of
  * HapGpuCompressPlanes in place of pictures.  planeFrames[f] is frame f's tensor in DEVICE memory, `channels` planes of
  * width x height elements, planeBytes and rowBytes shared by all frames (one N x C x H x W tensor: planeFrames[f] = base +
