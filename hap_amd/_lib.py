@@ -116,6 +116,10 @@ def _load():
                                               P(C.c_ubyte), P(C.c_ubyte), u, u, vp, ul]),
         "HapGpuCompositeFramesPlaced": (u, [vp, u, u, P(vp), P(ul), P(u), P(u), P(u), P(HapGpuPlacement), P(C.c_ubyte),
                                             P(C.c_ubyte), P(vp), u, u, ul, P(u), u]),
+        "HapGpuCompositeTexturesEncoded": (u, [vp, u, P(vp), P(ul), P(u), P(vp), P(ul), P(u), P(u), P(HapGpuPlacement),
+                                               P(C.c_ubyte), P(C.c_ubyte), u, u, u, P(u), P(vp), P(ul), P(ul)]),
+        "HapGpuCompositeFramesEncoded": (u, [vp, u, u, P(vp), P(ul), P(u), P(u), P(u), P(HapGpuPlacement), P(C.c_ubyte),
+                                             P(C.c_ubyte), u, u, u, P(u), P(u), P(u), P(vp), P(ul), P(ul), P(u), P(u), u, u]),
         "HapGpuTranscodeTexture": (u, [vp, vp, ul, u, vp, ul, u, u, u, u, P(u), P(vp), P(ul), P(ul)]),
         "HapGpuTranscodeFrames": (u, [vp, u, P(vp), P(ul), u, u, u, u, u, P(u), P(u), P(u), P(vp), P(ul), P(ul), P(u), u, u]),
         "HapGpuDecodeFramesRGBAHalf": (u, [vp, u, P(vp), P(ul), P(vp), u, u, ul, P(u), u]),

@@ -1069,6 +1069,85 @@ class Context:
                                             height, row_bytes or width * 4, results, flags)
         return r, list(results)[: len(flat)]
 
+    def composite_textures_encoded(self, layers, layer_sizes, width, height, output_formats, placements=None, opacities=None,
+                                   background=None, outputs=None):
+        """composite_textures_placed with the canvas going out as textures of output_formats instead of a picture: as
+        compress_rgba would make them of composite_textures_placed's picture, without that picture
+        (HapGpuCompositeTexturesEncoded).  The canvas bytes are encoded as they are, premultiplied.
+        Returns (result, [bytes] | None), or (result, [bytes used]) into `outputs`."""
+        n = len(layers)
+        if len(layer_sizes) != n:
+            raise ValueError("one size per layer")
+        infos = [_addr_len(t) for t, _f, _a in layers]
+        ainfos = [_addr_len(a) for _t, _f, a in layers]
+        ptrs = (C.c_void_p * n)(*[i[0] for i in infos])
+        lens = (C.c_ulong * n)(*[i[1] for i in infos])
+        fmts = (C.c_uint * n)(*[f for _t, f, _a in layers])
+        aptrs = (C.c_void_p * n)(*[i[0] for i in ainfos])
+        alens = (C.c_ulong * n)(*[i[1] for i in ainfos])
+        lws = (C.c_uint * n)(*[w for w, _h in layer_sizes])
+        lhs = (C.c_uint * n)(*[h for _w, h in layer_sizes])
+        places = _placement_array(placements, n)
+        ops = (C.c_ubyte * n)(*opacities) if opacities is not None else None
+        bg = (C.c_ubyte * 4)(*background) if background is not None else None
+        count = len(output_formats)
+        own = outputs is None
+        if own:
+            blocks = (width // 4) * (height // 4)
+            outputs = [(C.c_ubyte * max(1, blocks * (8 if f in (HapTextureFormat.RGB_DXT1, HapTextureFormat.A_RGTC1) else 16)))()
+                       for f in output_formats]
+        if len(outputs) != count:
+            raise ValueError("one output per format")
+        optrs, oinfos = self._ptr_array(outputs)
+        olens = (C.c_ulong * max(1, count))(*[i[1] for i in oinfos])
+        used = (C.c_ulong * max(1, count))()
+        r = lib.HapGpuCompositeTexturesEncoded(self.handle, n, ptrs, lens, fmts, aptrs, alens, lws, lhs, places, ops, bg, width,
+                                               height, count, (C.c_uint * max(1, count))(*output_formats), optrs, olens, used)
+        if own:
+            return r, ([C.string_at(o, used[i]) for i, o in enumerate(outputs)] if r == 0 else None)
+        return r, list(used)[:count]
+
+    def composite_frames_encoded(self, frames, frame_bytes, texture_counts, layer_sizes, width, height, formats, compressors,
+                                 chunk_counts, outputs, placements=None, opacities=None, background=None, decode_flags=0,
+                                 encode_flags=0):
+        """composite_frames_placed whose canvases go on to the encoder: one Hap frame of `formats` per output frame, byte
+        for byte what encode_frames_rgba makes of composite_frames_placed's pictures, without those pictures
+        (HapGpuCompositeFramesEncoded).  frames, frame_bytes, texture_counts, layer_sizes, placements, opacities and
+        background as for composite_frames_placed; formats, compressors, chunk_counts and outputs as for
+        transcode_frames.  Returns (result, used[], results[], layer_results[]): results has an entry per output frame,
+        layer_results one per output frame and layer, entry f * layers + l."""
+        nf, count = len(frames), len(formats)
+        nl = len(frames[0]) if nf else len(layer_sizes)
+        if len(outputs) != nf:
+            raise ValueError("one output per output frame")
+        if any(len(fr) != nl for fr in frames):
+            raise ValueError("every output frame has the same number of layers")
+        if len(layer_sizes) != nl:
+            raise ValueError("one size per layer")
+        if placements is not None and (len(placements) != nf or any(len(fr) != nl for fr in placements)):
+            raise ValueError("one placement per output frame and layer")
+        flat = [b for fr in frames for b in fr]
+        ptrs, infos = self._ptr_array(flat)
+        given = [None] * len(flat) if frame_bytes is None else [b for fr in frame_bytes for b in fr]
+        lens = (C.c_ulong * len(flat))(*[fb if fb is not None else infos[i][1] for i, fb in enumerate(given)])
+        counts = (C.c_uint * nl)(*texture_counts) if texture_counts is not None else None
+        lws = (C.c_uint * max(1, nl))(*[w for w, _h in layer_sizes])
+        lhs = (C.c_uint * max(1, nl))(*[h for _w, h in layer_sizes])
+        places = _placement_array(None if placements is None else [p for fr in placements for p in fr], len(flat))
+        ops = (C.c_ubyte * len(flat))(*[o for fr in opacities for o in fr]) if opacities is not None else None
+        bg = (C.c_ubyte * 4)(*background) if background is not None else None
+        optrs, oinfos = self._ptr_array(outputs)
+        olens = (C.c_ulong * max(1, nf))(*[i[1] for i in oinfos])
+        used = (C.c_ulong * max(1, nf))()
+        results = (C.c_uint * max(1, nf))()
+        layer_results = (C.c_uint * max(1, len(flat)))()
+        r = lib.HapGpuCompositeFramesEncoded(self.handle, nf, nl, ptrs, lens, counts, lws, lhs, places, ops, bg, width, height,
+                                             count, (C.c_uint * max(1, count))(*formats),
+                                             (C.c_uint * max(1, count))(*compressors),
+                                             (C.c_uint * max(1, count))(*chunk_counts), optrs, olens, used, layer_results,
+                                             results, decode_flags, encode_flags)
+        return r, list(used)[:nf], list(results)[:nf], list(layer_results)[: len(flat)]
+
     def measure_frames(self, frames, frame_bytes, texture_count, pictures, width, height, row_bytes=None, flags=0):
         """Frames against their RGBA8 reference pictures in device memory (tensors or addresses; None: no picture for that
         frame) in one call, without decoded pictures: per frame and channel the exact sums of (d - p)^2 and |d - p|, d

@@ -20,66 +20,15 @@
 // texel, and at opacity 255 replaces the canvas.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "bc_decode_texels.hpp"
-#include "composite_blend.hpp"
+#include "bc_composite_canvas.hpp"
 #include "hapgpu_runtime.hpp"
 
 namespace {
 
-using hapbc::texels::bc_decode_body;
-using hapbc::texels::block_in_registers;
-using namespace hapbc::composite;
+// (the canvas block, a layer's texels and the blend: bc_composite_canvas.hpp, shared with bc_composite_encode.hip)
+using namespace hapbc::canvas;
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
-
-// the canvas block: texel i as R | B << 16 and G | A << 16
-struct canvas_block {
-    unsigned rb[16], ga[16];
-};
-
-// layer `d`'s block `id` as sixteen texels R | G << 8 | B << 16 | A << 24: the body of the picture decoder, from
-// registers to registers
-template <int FMT, bool HAS_ALPHA>
-__device__ __forceinline__ void layer_texels(const uint8_t *blocks, const uint8_t *plane, unsigned id, unsigned (&px)[16])
-{
-    block_in_registers reg;
-    if (FMT == 0) {
-        const uint2 v = *reinterpret_cast<const uint2 *>(blocks + (size_t)id * 8u);
-        reg.block = make_uint4(v.x, v.y, 0u, 0u);
-    } else {
-        reg.block = *reinterpret_cast<const uint4 *>(blocks + (size_t)id * 16u);
-    }
-    reg.plane = HAS_ALPHA ? *reinterpret_cast<const uint2 *>(plane + (size_t)id * 8u) : make_uint2(0u, 0u);
-    reg.texels = px;
-    bc_decode_body<FMT, HAS_ALPHA, false, true>(nullptr, nullptr, 1u, 0u, nullptr, 0u, 0u, 0u, &reg);
-}
-
-// SOURCE_ALPHA: the layer's texels carry an alpha of their own (DXT5, an RGTC1 plane); else As = 255 and a = o
-template <bool SOURCE_ALPHA>
-__device__ __forceinline__ void blend_block(const unsigned (&px)[16], unsigned opacity, canvas_block &c)
-{
-    const unsigned o257 = opacity_scaled(opacity);
-    if (!SOURCE_ALPHA && opacity == 255u) {
-        // a = 255 replaces the texel
-#pragma unroll
-        for (int i = 0; i < 16; i++) {
-            c.rb[i] = __builtin_amdgcn_perm(0u, px[i], 0x0c020c00u);          // R . B .
-            c.ga[i] = __builtin_amdgcn_perm(0u, px[i], 0x0c0d0c01u);          // G . 255 .
-        }
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        const unsigned rb = __builtin_amdgcn_perm(0u, px[i], 0x0c020c00u);    // Rs . Bs .
-        const unsigned ga = __builtin_amdgcn_perm(0u, px[i], 0x0c0d0c01u);    // Gs . 255 .: the canvas's alpha as a colour
-        // (As * o257 + 32896 < 2^24: a 24-bit multiply-add, a in byte 2; without source alpha a scalar)
-        const unsigned m = layer_alpha_in_byte_2(SOURCE_ALPHA ? px[i] >> 24 : 255u, o257);
-        const unsigned a2 = __builtin_amdgcn_perm(0u, m, 0x0c020c02u);        // a . a .
-        const unsigned inv2 = 0x00FF00FFu - a2;
-        c.rb[i] = as_dword(blend_pair(as_pk_u16(rb), as_pk_u16(c.rb[i]), as_pk_u16(a2), as_pk_u16(inv2)));
-        c.ga[i] = as_dword(blend_pair(as_pk_u16(ga), as_pk_u16(c.ga[i]), as_pk_u16(a2), as_pk_u16(inv2)));
-    }
-}
 
 // One launch for `gridDim.z` output pictures of one geometry.  layers: [pictures][layer_count]; outputs: the pictures'
 // addresses.  An output address of 0, or a texture address of 0 in any layer, skips the picture.
@@ -101,11 +50,7 @@ __global__ __launch_bounds__(256) void bc_composite_kernel(const HapGpuComposite
         return;
     const unsigned by = id / blocks_x, bx = id - by * blocks_x;
     canvas_block c;
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        c.rb[i] = (background & 0xFFu) | ((background & 0x00FF0000u));
-        c.ga[i] = ((background >> 8) & 0xFFu) | ((background >> 8) & 0x00FF0000u);
-    }
+    canvas_background(c, background);
 #pragma unroll 1
     for (unsigned l = 0; l < layer_count; l++) {
         // (wave-uniform: the descriptor's address is; readfirstlane says so to the branches below)
@@ -144,7 +89,7 @@ __global__ __launch_bounds__(256) void bc_composite_kernel(const HapGpuComposite
         v4u v;
 #pragma unroll
         for (int k = 0; k < 4; k++)
-            v[k] = __builtin_amdgcn_perm(c.ga[4 * r + k], c.rb[4 * r + k], 0x06020400u);     // R G B A
+            v[k] = canvas_texel(c, 4 * r + k);
         // (streaming stores, as the picture decoder's: written once, not read back)
         __builtin_nontemporal_store(v, reinterpret_cast<v4u *>(dst + (size_t)r * row_bytes));
     }
@@ -156,7 +101,8 @@ __global__ __launch_bounds__(256) void bc_composite_kernel(const HapGpuComposite
 // and blend: the whole of a layer's work is under that one divergent branch, so lanes outside keep their canvas
 // registers -- on the "opaque at opacity 255 replaces the canvas" shortcut too, wave-uniform in its condition and
 // lane-masked in its effect -- and a wave with no lane inside skips the layer's loads.  A layer of opacity 0 or with an
-// empty clip is not loaded.
+// empty clip is not loaded.  (The canvas and that loop are placed_canvas_block, bc_composite_canvas.hpp: the kernel that
+// encodes the canvas calls it too.)
 __global__ __launch_bounds__(256) void bc_composite_placed_kernel(const HapGpuPlacedLayer *__restrict__ layers,
                                                                   unsigned layer_count, const uint64_t *__restrict__ outputs,
                                                                   unsigned background, unsigned blocks_x,
@@ -174,57 +120,14 @@ __global__ __launch_bounds__(256) void bc_composite_placed_kernel(const HapGpuPl
         return;
     const unsigned by = id / blocks_x, bx = id - by * blocks_x;
     canvas_block c;
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        c.rb[i] = (background & 0xFFu) | ((background & 0x00FF0000u));
-        c.ga[i] = ((background >> 8) & 0xFFu) | ((background >> 8) & 0x00FF0000u);
-    }
-#pragma unroll 1
-    for (unsigned l = 0; l < layer_count; l++) {
-        // (wave-uniform: the descriptor's address is; readfirstlane says so to the branches below)
-        const unsigned opacity = __builtin_amdgcn_readfirstlane(mine[l].opacity);
-        const unsigned cw = __builtin_amdgcn_readfirstlane(mine[l].cw);
-        if (opacity == 0u || cw == 0u)
-            continue;               // a = 0 keeps every texel, an empty clip covers none: the layer is not loaded
-        const unsigned format = __builtin_amdgcn_readfirstlane(mine[l].format);
-        const unsigned ux = bx - __builtin_amdgcn_readfirstlane(mine[l].cx0);
-        const unsigned uy = by - __builtin_amdgcn_readfirstlane(mine[l].cy0);
-        const uint8_t *blocks = (const uint8_t *)mine[l].texture, *plane = (const uint8_t *)mine[l].alpha;
-        if (ux < cw && uy < __builtin_amdgcn_readfirstlane(mine[l].ch)) {
-            const unsigned lid = __builtin_amdgcn_readfirstlane(mine[l].first) +
-                                 uy * __builtin_amdgcn_readfirstlane(mine[l].layer_blocks_x) + ux;
-            unsigned px[16];
-            bool source_alpha = plane != nullptr;
-            if (format == 0x83F0u) {
-                if (plane)
-                    layer_texels<0, true>(blocks, plane, lid, px);
-                else
-                    layer_texels<0, false>(blocks, plane, lid, px);
-            } else if (format == 0x83F3u) {
-                source_alpha = true;
-                if (plane)
-                    layer_texels<1, true>(blocks, plane, lid, px);
-                else
-                    layer_texels<1, false>(blocks, plane, lid, px);
-            } else {
-                if (plane)
-                    layer_texels<2, true>(blocks, plane, lid, px);
-                else
-                    layer_texels<2, false>(blocks, plane, lid, px);
-            }
-            if (source_alpha)
-                blend_block<true>(px, opacity, c);
-            else
-                blend_block<false>(px, opacity, c);
-        }
-    }
+    placed_canvas_block(mine, layer_count, background, bx, by, c);
     uint8_t *dst = rgba + (size_t)(4u * by) * row_bytes + 16u * (size_t)bx;
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         v4u v;
 #pragma unroll
         for (int k = 0; k < 4; k++)
-            v[k] = __builtin_amdgcn_perm(c.ga[4 * r + k], c.rb[4 * r + k], 0x06020400u);     // R G B A
+            v[k] = canvas_texel(c, 4 * r + k);
         __builtin_nontemporal_store(v, reinterpret_cast<v4u *>(dst + (size_t)r * row_bytes));
     }
 }

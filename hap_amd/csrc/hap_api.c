@@ -1219,6 +1219,63 @@ unsigned int HapGpuCompositeFramesPlaced(HapGpuContext *context, unsigned int fr
     return r;
 }
 
+/* ... with the canvas encoded to textures, and to frames, instead of written as a picture: what is wrong with the call
+   itself -- the placed calls' refusals, a destination set the kernel does not make, what the encoder refuses of the
+   formats, compressors and chunk counts, a NULL results or layerResults -- is seen before the context is looked at, and
+   sets every entry of every result array there is */
+unsigned int HapGpuCompositeTexturesEncoded(HapGpuContext *context, unsigned int layerCount, const void *const *textures,
+                                            const unsigned long *texturesBytes, const unsigned int *textureFormats,
+                                            const void *const *alphaTextures, const unsigned long *alphaTexturesBytes,
+                                            const unsigned int *layerWidths, const unsigned int *layerHeights,
+                                            const HapGpuPlacement *placements, const unsigned char *opacities,
+                                            const unsigned char *background, unsigned int width, unsigned int height,
+                                            unsigned int count, const unsigned int *outputFormats, void *const *outputs,
+                                            const unsigned long *outputsBytes, unsigned long *outputsBytesUsed)
+{
+    unsigned r;
+    if (!context || !textures || !texturesBytes || !textureFormats || !outputs || !outputsBytes ||
+        !hapb_composite_encode_textures_valid(layerCount, layerWidths, layerHeights, placements, 1u, width, height, NULL,
+                                              count, outputFormats))
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_composite_encode_textures(context, layerCount, textures, texturesBytes, textureFormats, alphaTextures,
+                                       alphaTexturesBytes, layerWidths, layerHeights, placements, opacities, background,
+                                       width, height, count, outputFormats, outputs, outputsBytes, outputsBytesUsed);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
+unsigned int HapGpuCompositeFramesEncoded(HapGpuContext *context, unsigned int frameCount, unsigned int layerCount,
+                                          const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
+                                          const unsigned int *textureCounts, const unsigned int *layerWidths,
+                                          const unsigned int *layerHeights, const HapGpuPlacement *placements,
+                                          const unsigned char *opacities, const unsigned char *background,
+                                          unsigned int width, unsigned int height, unsigned int count,
+                                          const unsigned int *textureFormats, const unsigned int *compressors,
+                                          const unsigned int *chunkCounts, void *const *outputBuffers,
+                                          const unsigned long *outputBuffersBytes, unsigned long *outputBuffersBytesUsed,
+                                          unsigned int *layerResults, unsigned int *results, unsigned int decodeFlags,
+                                          unsigned int encodeFlags)
+{
+    unsigned r;
+    if (!results || !layerResults || !inputBuffers || !inputBuffersBytes || !outputBuffers || !outputBuffersBytes ||
+        !outputBuffersBytesUsed ||
+        !hapb_composite_encode_frames_valid(layerCount, layerWidths, layerHeights, placements, frameCount, width, height,
+                                            textureCounts, count, textureFormats, compressors, chunkCounts, encodeFlags)) {
+        refuse_call(layerResults, (size_t)frameCount * layerCount);
+        return refuse_call(results, frameCount);
+    }
+    if (!context)
+        return HapResult_Bad_Arguments;
+    hapgpu_rt_lock(context->rt);
+    r = hapb_composite_encode_frames(context, frameCount, layerCount, inputBuffers, inputBuffersBytes, textureCounts,
+                                     layerWidths, layerHeights, placements, opacities, background, width, height, count,
+                                     textureFormats, compressors, chunkCounts, outputBuffers, outputBuffersBytes,
+                                     outputBuffersBytesUsed, layerResults, results, decodeFlags, encodeFlags);
+    hapgpu_rt_unlock(context->rt);
+    return r;
+}
+
 /* HapGpuDecodeFramesRGBA of a block-aligned rectangle of every frame; any other rectangle refuses the whole call */
 unsigned int HapGpuDecodeFramesRGBARegion(HapGpuContext *context, unsigned int frameCount,
                                           const void *const *inputBuffers, const unsigned long *inputBuffersBytes,

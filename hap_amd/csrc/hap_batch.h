@@ -301,6 +301,42 @@ unsigned hapb_composite_frames_placed(HapGpuContext *ctx, unsigned frame_count, 
                                       const unsigned char *opacities, const unsigned char *background,
                                       void *const *rgba_frames, unsigned width, unsigned height, unsigned long row_bytes,
                                       unsigned *results, unsigned flags);
+/* what both compositing calls that end in textures ask whatever their layers hold: 1 = hapb_composite_placed_valid for
+   a canvas with rows of width * 4 bytes, at most 65535 block rows, and `count` formats that are one of the four
+   destination sets of hapb_transcode's kernel (include/hap_gpu.h: HapGpuCompositeTexturesEncoded).  Touches no device. */
+int hapb_composite_encode_textures_valid(unsigned layer_count, const unsigned *layer_widths, const unsigned *layer_heights,
+                                         const HapGpuPlacement *placements, size_t frame_count, unsigned width,
+                                         unsigned height, const unsigned *texture_counts, unsigned count,
+                                         const unsigned *formats);
+/* ... and what the frames call asks on top: compressors and chunk_counts, neither NULL, that hapb_encode takes with the
+   formats and encode_flags for textures of the canvas's size (HapGpuCompositeFramesEncoded).  Touches no device. */
+int hapb_composite_encode_frames_valid(unsigned layer_count, const unsigned *layer_widths, const unsigned *layer_heights,
+                                       const HapGpuPlacement *placements, size_t frame_count, unsigned width,
+                                       unsigned height, const unsigned *texture_counts, unsigned count,
+                                       const unsigned *formats, const unsigned *compressors,
+                                       const unsigned *chunk_counts, unsigned encode_flags);
+/* hapb_composite_textures_placed with the canvas encoded to `count` textures of out_formats (host or device) instead of
+   written as a picture (HapGpuCompositeTexturesEncoded) */
+unsigned hapb_composite_encode_textures(HapGpuContext *ctx, unsigned layer_count, const void *const *textures,
+                                        const unsigned long *texture_bytes, const unsigned *formats,
+                                        const void *const *alphas, const unsigned long *alpha_bytes,
+                                        const unsigned *layer_widths, const unsigned *layer_heights,
+                                        const HapGpuPlacement *placements, const unsigned char *opacities,
+                                        const unsigned char *background, unsigned width, unsigned height, unsigned count,
+                                        const unsigned *out_formats, void *const *outputs,
+                                        const unsigned long *output_bytes, unsigned long *output_used);
+/* hapb_composite_frames_placed up to its launch, hapb_transcode from its launch on: one frame of `formats` per output
+   frame (HapGpuCompositeFramesEncoded); layer_results: frame_count * layer_count entries, results: frame_count */
+unsigned hapb_composite_encode_frames(HapGpuContext *ctx, unsigned frame_count, unsigned layer_count,
+                                      const void *const *inputs, const unsigned long *input_bytes,
+                                      const unsigned *texture_counts, const unsigned *layer_widths,
+                                      const unsigned *layer_heights, const HapGpuPlacement *placements,
+                                      const unsigned char *opacities, const unsigned char *background, unsigned width,
+                                      unsigned height, unsigned count, const unsigned *formats,
+                                      const unsigned *compressors, const unsigned *chunk_counts, void *const *outputs,
+                                      const unsigned long *output_bytes, unsigned long *output_used,
+                                      unsigned *layer_results, unsigned *results, unsigned decode_flags,
+                                      unsigned encode_flags);
 
 /* groups and output in device memory: tables through the host, payloads device to device */
 unsigned hapb_join_device(HapGpuContext *ctx, unsigned group_count, const void *const *frames,

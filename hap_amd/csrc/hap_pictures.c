@@ -1433,3 +1433,302 @@ unsigned hapb_transcode_texture(HapGpuContext *ctx, const void *texture, unsigne
     return HapResult_No_Error;
 }
 
+/* ============================================================= compositing to frames */
+/* Layers of frames -> frames, and layers of textures -> textures: the placed compositing calls up to their launch, then
+   hapb_transcode from its launch on.  hapgpu_k_block_composite_encode takes the descriptors of
+   hapgpu_k_block_composite_placed and, where that has the pictures' addresses, the destination textures' -- a slice's lie
+   in D_TRANSCODED --, and hapb_encode follows on those textures on the same stream.  No picture anywhere. */
+
+int hapb_composite_encode_textures_valid(unsigned layer_count, const unsigned *layer_widths, const unsigned *layer_heights,
+                                         const HapGpuPlacement *placements, size_t frame_count, unsigned width,
+                                         unsigned height, const unsigned *texture_counts, unsigned count,
+                                         const unsigned *formats)
+{
+    /* (the canvas is the placed calls' with rows of exactly width * 4 bytes; a block row per blockIdx.y of the kernel) */
+    return hapb_composite_placed_valid(layer_count, layer_widths, layer_heights, placements, frame_count, width, height,
+                                       (unsigned long)width * 4u, texture_counts) &&
+           height / 4u <= 65535u && formats && count != 0 && count <= 2 && transcode_set(count, formats);
+}
+
+int hapb_composite_encode_frames_valid(unsigned layer_count, const unsigned *layer_widths, const unsigned *layer_heights,
+                                       const HapGpuPlacement *placements, size_t frame_count, unsigned width,
+                                       unsigned height, const unsigned *texture_counts, unsigned count,
+                                       const unsigned *formats, const unsigned *compressors,
+                                       const unsigned *chunk_counts, unsigned encode_flags)
+{
+    unsigned long out_bytes[2] = {0, 0};
+    unsigned i;
+    if (!compressors || !chunk_counts ||
+        !hapb_composite_encode_textures_valid(layer_count, layer_widths, layer_heights, placements, frame_count, width,
+                                              height, texture_counts, count, formats))
+        return 0;
+    for (i = 0; i < count; i++)
+        out_bytes[i] = (unsigned long)((size_t)(width / 4u) * (height / 4u) * hapf_block_bytes(formats[i]));
+    encode_flags &= ~(HAPGPU_ENCODE_BPTC_BLOCKS | HAPGPU_ENCODE_REFINE_ENDPOINTS);
+    return encode_textures_valid(count, out_bytes, formats, compressors, chunk_counts, encode_flags) == HapResult_No_Error;
+}
+
+/* the table of a composite-encode launch for n canvases of layer_count layers: [n] destination textures, [n] destination
+   planes, then [n][layer_count] descriptors; as composite_placed_table */
+static uint64_t *composite_encode_table(hapgpu_rt *rt, unsigned n, unsigned layer_count, uint64_t **device, size_t *bytes)
+{
+    uint64_t *htab;
+    *bytes = sizeof(uint64_t) * 2u * n + sizeof(HapGpuPlacedLayer) * (size_t)n * layer_count;
+    htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, *bytes);
+    *device = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, *bytes);
+    if (!htab || !*device)
+        return NULL;
+    memset(htab, 0, *bytes);
+    return htab;
+}
+
+static void composite_encode_refuse(unsigned *layer_results, size_t layer_entries, unsigned *results, size_t frame_count,
+                                    unsigned code)
+{
+    size_t i;
+    for (i = 0; layer_results && i < layer_entries; i++)
+        layer_results[i] = code;
+    for (i = 0; results && i < frame_count; i++)
+        results[i] = code;
+}
+
+unsigned hapb_composite_encode_textures(HapGpuContext *ctx, unsigned layer_count, const void *const *textures,
+                                        const unsigned long *texture_bytes, const unsigned *formats,
+                                        const void *const *alphas, const unsigned long *alpha_bytes,
+                                        const unsigned *layer_widths, const unsigned *layer_heights,
+                                        const HapGpuPlacement *placements, const unsigned char *opacities,
+                                        const unsigned char *background, unsigned width, unsigned height, unsigned count,
+                                        const unsigned *out_formats, void *const *outputs,
+                                        const unsigned long *output_bytes, unsigned long *output_used)
+{
+    hapgpu_rt *rt = ctx->rt;
+    size_t staged = 0, tab_bytes, at = 0, out_need[2] = {0, 0}, out_off[2] = {0, 0}, out_total = 0;
+    uint64_t *htab, *dtab;
+    HapGpuPlacedLayer *hlayers;
+    uint8_t *stage = NULL, *out_stage = NULL;
+    unsigned l, i;
+    int rc, any_host_output = 0;
+    if (!hapb_composite_encode_textures_valid(layer_count, layer_widths, layer_heights, placements, 1u, width, height, NULL,
+                                              count, out_formats) ||
+        !textures || !texture_bytes || !formats || !outputs || !output_bytes)
+        return HapResult_Bad_Arguments;
+    if (context_busy(ctx, NULL, 0))
+        return HapResult_Internal_Error;
+    /* every layer: HapGpuDecompressRGBA's rules for its texture and its plane, at the layer's own size */
+    for (l = 0; l < layer_count; l++) {
+        const void *alpha = alphas ? alphas[l] : NULL;
+        const size_t blocks = (size_t)(layer_widths[l] / 4u) * (layer_heights[l] / 4u);
+        const size_t need = composite_format(formats[l]) ? blocks * hapf_block_bytes(formats[l]) : 0u;
+        if (!textures[l] || !need || texture_bytes[l] < need || (alpha && (!alpha_bytes || alpha_bytes[l] < blocks * 8u)) ||
+            (is_dev(ctx, textures[l]) && ((uintptr_t)textures[l] & (hapf_block_bytes(formats[l]) - 1u))) ||
+            (alpha && is_dev(ctx, alpha) && ((uintptr_t)alpha & 7u)))
+            return HapResult_Bad_Arguments;
+        if (!is_dev(ctx, textures[l]))
+            staged += align_up(need, 256);
+        if (alpha && !is_dev(ctx, alpha))
+            staged += align_up(blocks * 8u, 256);
+    }
+    /* every output: HapGpuTranscodeTexture's rules */
+    for (i = 0; i < count; i++) {
+        if (!outputs[i])
+            return HapResult_Bad_Arguments;
+        out_need[i] = (size_t)(width / 4u) * (height / 4u) * hapf_block_bytes(out_formats[i]);
+        out_off[i] = out_total;
+        out_total += align_up(out_need[i], 256);
+    }
+    for (i = 0; i < count; i++)
+        if (output_bytes[i] < out_need[i])
+            return HapResult_Buffer_Too_Small;
+    for (i = 0; i < count; i++) {
+        if (is_dev(ctx, outputs[i]) && ((uintptr_t)outputs[i] & (hapf_block_bytes(out_formats[i]) - 1u)))
+            return HapResult_Bad_Arguments;
+        if (!is_dev(ctx, outputs[i]))
+            any_host_output = 1;
+    }
+    /* (one request for all that is staged: an arena that grows forgets what it held) */
+    if (staged && !(stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, staged)))
+        return HapResult_Internal_Error;
+    if (any_host_output && !(out_stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_TRANSCODED, out_total)))
+        return HapResult_Internal_Error;
+    htab = composite_encode_table(rt, 1u, layer_count, &dtab, &tab_bytes);
+    if (!htab)
+        return HapResult_Internal_Error;
+    hlayers = (HapGpuPlacedLayer *)(htab + 2);
+    for (i = 0; i < count; i++)
+        htab[i] = (uint64_t)(uintptr_t)(is_dev(ctx, outputs[i]) ? (uint8_t *)outputs[i] : out_stage + out_off[i]);
+    for (l = 0; l < layer_count; l++) {
+        const void *alpha = alphas ? alphas[l] : NULL, *src = textures[l];
+        const size_t blocks = (size_t)(layer_widths[l] / 4u) * (layer_heights[l] / 4u);
+        if (!is_dev(ctx, src)) {
+            const size_t need = blocks * hapf_block_bytes(formats[l]);
+            if (hapgpu_rt_h2d(rt, stage + at, src, need))
+                return HapResult_Internal_Error;
+            src = stage + at;
+            at += align_up(need, 256);
+        }
+        if (alpha && !is_dev(ctx, alpha)) {
+            if (hapgpu_rt_h2d(rt, stage + at, alpha, blocks * 8u))
+                return HapResult_Internal_Error;
+            alpha = stage + at;
+            at += align_up(blocks * 8u, 256);
+        }
+        hlayers[l].texture = (uint64_t)(uintptr_t)src;
+        hlayers[l].alpha = (uint64_t)(uintptr_t)alpha;
+        hlayers[l].format = formats[l];
+        hlayers[l].opacity = opacities ? opacities[l] : 255u;
+        placed_layer_clip(&hlayers[l], placements ? &placements[l] : NULL, layer_widths[l], layer_heights[l], width, height);
+    }
+    if (hapgpu_rt_h2d(rt, dtab, htab, tab_bytes))
+        return HapResult_Internal_Error;
+    rc = hapgpu_k_block_composite_encode(rt, (const HapGpuPlacedLayer *)(dtab + 2), layer_count, dtab, dtab + 1, 1u,
+                                         background ? background : k_composite_background, width, height, out_formats[0],
+                                         count == 2);
+    if (rc == 1)
+        return HapResult_Bad_Arguments;
+    for (i = 0; !rc && i < count; i++)
+        if (!is_dev(ctx, outputs[i]))
+            rc |= hapgpu_rt_d2h(rt, outputs[i], out_stage + out_off[i], out_need[i]);
+    if (rc || hapgpu_rt_sync(rt))
+        return HapResult_Internal_Error;
+    for (i = 0; output_used && i < count; i++)
+        output_used[i] = (unsigned long)out_need[i];
+    return HapResult_No_Error;
+}
+
+unsigned hapb_composite_encode_frames(HapGpuContext *ctx, unsigned frame_count, unsigned layer_count,
+                                      const void *const *inputs, const unsigned long *input_bytes,
+                                      const unsigned *texture_counts, const unsigned *layer_widths,
+                                      const unsigned *layer_heights, const HapGpuPlacement *placements,
+                                      const unsigned char *opacities, const unsigned char *background, unsigned width,
+                                      unsigned height, unsigned count, const unsigned *formats,
+                                      const unsigned *compressors, const unsigned *chunk_counts, void *const *outputs,
+                                      const unsigned long *output_bytes, unsigned long *output_used,
+                                      unsigned *layer_results, unsigned *results, unsigned decode_flags,
+                                      unsigned encode_flags)
+{
+    hapgpu_rt *rt = ctx->rt;
+    const HapbEncodeArgs device_textures = {1, NULL, 0, 0};
+    const size_t total = (size_t)frame_count * layer_count;
+    size_t out_per_frame = 0, out_off[2] = {0, 0}, done, i;
+    unsigned long out_bytes[2] = {0, 0};
+    unsigned first_error = HapResult_No_Error, f, l;
+    hap_place_layout layout;
+    slice_textures s;
+    const void **tex;       /* per output frame and destination texture: what the encode half reads */
+    unsigned *composited;   /* per output frame: what its layers came to */
+    if (!results || !layer_results)
+        return HapResult_Bad_Arguments;
+    if (!hapb_composite_encode_frames_valid(layer_count, layer_widths, layer_heights, placements, frame_count, width, height,
+                                            texture_counts, count, formats, compressors, chunk_counts, encode_flags) ||
+        !inputs || !input_bytes || !outputs || !output_bytes || !output_used) {
+        composite_encode_refuse(layer_results, total, results, frame_count, HapResult_Bad_Arguments);
+        return HapResult_Bad_Arguments;
+    }
+    if (frame_count == 0)
+        return HapResult_No_Error;
+    /* (the destination blocks are the default encode's: no BC7, no refined end points) */
+    encode_flags &= ~(HAPGPU_ENCODE_BPTC_BLOCKS | HAPGPU_ENCODE_REFINE_ENDPOINTS);
+    for (i = 0; i < count; i++) {
+        out_bytes[i] = (unsigned long)((size_t)(width / 4u) * (height / 4u) * hapf_block_bytes(formats[i]));
+        out_off[i] = out_per_frame;
+        out_per_frame += align_up(out_bytes[i], 256);
+    }
+    /* output frames of a slice: at most 4 GiB of block textures, the canvases' among them, and 32768 entries of the second
+       stage at a time */
+    hap_place_layout_of(&layout, layer_count, texture_counts, layer_widths, layer_heights, out_per_frame, frame_count);
+    if (context_busy(ctx, NULL, 0) || !slice_textures_init_placed(&s, &layout)) {
+        composite_encode_refuse(layer_results, total, results, frame_count, HapResult_Internal_Error);
+        return HapResult_Internal_Error;
+    }
+    tex = (const void **)malloc((sizeof(*tex) * count + sizeof(*composited)) * s.at.slice);
+    if (!tex) {
+        free(s.in);
+        composite_encode_refuse(layer_results, total, results, frame_count, HapResult_Internal_Error);
+        return HapResult_Internal_Error;
+    }
+    composited = (unsigned *)(tex + s.at.slice * count);
+    for (done = 0; done < frame_count; done += s.at.slice) {
+        const unsigned n = (unsigned)(frame_count - done < s.at.slice ? frame_count - done : s.at.slice);
+        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, s.at.per_frame * n);
+        uint8_t *encoded = (uint8_t *)hapgpu_rt_device_scratch(rt, D_TRANSCODED, out_per_frame * n);
+        uint64_t *htab = NULL, *dtab = NULL;
+        HapGpuPlacedLayer *hlayers;
+        size_t tab_bytes = 0;
+        unsigned present = 0;
+        int rc = 0;
+        if (textures && encoded) {
+            /* the second stage of every layer of every output frame of the slice, one batch: whole frames */
+            slice_textures_decode(ctx, &s, textures, inputs, input_bytes, done, n, NULL, decode_flags);
+            /* (after the second stage, which has tables of its own) */
+            htab = composite_encode_table(rt, n, layer_count, &dtab, &tab_bytes);
+        }
+        if (!htab) {
+            composite_encode_refuse(layer_results + done * layer_count, (size_t)n * layer_count, results + done, n,
+                                    HapResult_Internal_Error);
+            for (f = 0; f < n; f++)
+                output_used[done + f] = 0;
+            first_error = first_error ? first_error : HapResult_Internal_Error;
+            continue;
+        }
+        hlayers = (HapGpuPlacedLayer *)(htab + 2u * (size_t)n);
+        for (f = 0; f < n; f++) {
+            unsigned *frame_results = layer_results + (done + f) * layer_count;
+            unsigned all = HapResult_No_Error;
+            for (l = 0; l < layer_count; l++) {
+                const unsigned layer_textures = s.at.count_of[l];
+                const size_t e = (size_t)f * s.at.entries_per_frame + s.at.entry_of[l];
+                HapGpuPlacedLayer *d = &hlayers[(size_t)f * layer_count + l];
+                unsigned r = s.res[e];
+                if (r == HapResult_No_Error && layer_textures == 2u)
+                    r = s.res[e + 1];
+                /* the placed call's checks: exactly the layer's geometry, in one of the three formats a layer may have */
+                if (r == HapResult_Buffer_Too_Small ||
+                    (r == HapResult_No_Error && !slice_entry_fits_member(&s, e, l, k_rgba_kinds, 3u)))
+                    r = HapResult_Bad_Arguments;
+                frame_results[l] = r;
+                if (r != HapResult_No_Error && all == HapResult_No_Error)
+                    all = r;
+                d->texture = (uint64_t)(uintptr_t)s.outs[e];
+                d->alpha = layer_textures == 2u ? (uint64_t)(uintptr_t)s.outs[e + 1] : 0u;
+                d->format = s.fmts[e];
+                d->opacity = opacities ? opacities[(done + f) * layer_count + l] : 255u;
+                placed_layer_clip(d, placements ? &placements[(done + f) * layer_count + l] : NULL, layer_widths[l],
+                                  layer_heights[l], width, height);
+            }
+            composited[f] = all;
+            /* (an output frame with a failed layer has NULL textures: hapb_encode leaves it out) */
+            for (i = 0; i < count; i++)
+                tex[(size_t)f * count + i] = all != HapResult_No_Error ? NULL :
+                                             (const void *)(encoded + out_per_frame * f + out_off[i]);
+            /* (a frame whose output hapb_encode will refuse is not worth the kernel's time either: address 0 skips it) */
+            if (all == HapResult_No_Error && outputs[done + f] && output_bytes[done + f]) {
+                htab[f] = (uint64_t)(uintptr_t)tex[(size_t)f * count];
+                htab[n + f] = count == 2 ? (uint64_t)(uintptr_t)tex[(size_t)f * count + 1] : 0u;
+                present = 1;
+            }
+        }
+        if (present) {
+            rc |= hapgpu_rt_h2d(rt, dtab, htab, tab_bytes);
+            rc |= hapgpu_k_block_composite_encode(rt, (const HapGpuPlacedLayer *)(dtab + 2u * (size_t)n), layer_count, dtab,
+                                                  dtab + n, n, background ? background : k_composite_background, width,
+                                                  height, formats[0], count == 2);
+        }
+        if (rc)     /* (nothing of this slice's kernel output may be trusted: its frames fail) */
+            memset(tex, 0, sizeof(*tex) * (size_t)n * count);
+        /* the encode half on the same stream, behind the kernel; it ends with the slice's second and last wait */
+        hapb_encode(ctx, n, count, tex, out_bytes, formats, compressors, chunk_counts, outputs + done, output_bytes + done,
+                    output_used + done, results + done, encode_flags, &device_textures);
+        for (f = 0; f < n; f++) {
+            if (composited[f] != HapResult_No_Error) {
+                results[done + f] = composited[f];
+                output_used[done + f] = 0;
+            } else if (rc && (results[done + f] == HapResult_No_Error || results[done + f] == HapResult_Bad_Arguments)) {
+                results[done + f] = HapResult_Internal_Error;
+            }
+            if (results[done + f] != HapResult_No_Error && first_error == HapResult_No_Error)
+                first_error = results[done + f];
+        }
+    }
+    free(s.in); free(tex);
+    return first_error;
+}

@@ -531,6 +531,18 @@ typedef struct HapGpuPlacedLayer {
 int hapgpu_k_block_composite_placed(hapgpu_rt *rt, const HapGpuPlacedLayer *layers, unsigned layer_count,
                                     const uint64_t *outputs, unsigned pictures, const unsigned char *background,
                                     unsigned width, unsigned height, size_t row_bytes);
+/* hapgpu_k_block_composite_placed with the canvases going to the block encoder in registers, not to memory as pictures
+   (bc_composite_encode.hip): blocks of `dst_format` (RGB_DXT1, RGBA_DXT5 or YCoCg_DXT5; dst_with_alpha, YCoCg_DXT5 only:
+   + the RGTC1 plane of A) of textures of width x height, byte for byte what hapgpu_k_block_encode makes of the RGBA8
+   pictures hapgpu_k_block_composite_placed writes for the same layers and background -- the canvas bytes as they are,
+   premultiplied.  outputs: `pictures` device addresses of the destination textures (a device array; 0 skips the
+   picture), outputs2: of the destination planes (dst_with_alpha only; else not read and may be NULL).  At most 65535
+   block rows.  Layers, their alignment and the background as hapgpu_k_block_composite_placed has them, destinations
+   aligned to their blocks.  Timed as HapGpuKernel_BlockEncode.  Returns 0 launched, 1 bad arguments, 4 launch failure. */
+int hapgpu_k_block_composite_encode(hapgpu_rt *rt, const HapGpuPlacedLayer *layers, unsigned layer_count,
+                                    const uint64_t *outputs, const uint64_t *outputs2, unsigned pictures,
+                                    const unsigned char *background, unsigned width, unsigned height, unsigned dst_format,
+                                    int dst_with_alpha);
 /* planar tensors -> blocks of `hap_texture_format`, without an RGBA8 picture in between (bc_encode_planes.hip): the way
    back of hapgpu_k_block_decode_planes.  Tensors (the first column of the table) of `channels` (3 or 4: R, G, B[, A])
    planes plane_bytes apart, rows row_bytes apart, elements of element_kind (0 half, 1 bfloat16, 2 float: e = 2, 2, 4

@@ -1086,6 +1086,88 @@ unsigned int HapGpuCompositeFramesPlaced(HapGpuContext *context, unsigned int fr
                                          unsigned int *results,
                                          unsigned int flags);
 
+/* HapGpuCompositeTexturesPlaced with the canvas going out as `count` block textures instead of an RGBA8 picture: the
+ * compositing kernel hands the canvas block it holds in registers to the block encoder, as HapGpuTranscodeTexture's kernel
+ * hands over a decoded block.  No picture of the canvas is written or read: per canvas block one block is stored, where
+ * a compositing call followed by HapGpuCompressRGBA writes 64 bytes and reads them again.
+ * The definition, and the only one: outputs[i] is byte for byte what HapGpuCompressRGBA(..., outputFormats[i], ...,
+ * flags 0) makes of the picture HapGpuCompositeTexturesPlaced writes for the same layers, layerWidths, layerHeights,
+ * placements, opacities, background, width and height, with rowBytes = width * 4.  The canvas bytes go to the encoder as
+ * they are: the canvas is premultiplied by its alpha, so with an opaque background the result is opaque and the same
+ * as straight alpha, and with any other background the textures hold premultiplied colour.  Two calls give the same
+ * bytes.
+ * Destination sets, the four HapGpuTranscodeTexture makes -- count 1: RGB_DXT1 (Hap), RGBA_DXT5 (Hap Alpha) or
+ * YCoCg_DXT5 (Hap Q); count 2: YCoCg_DXT5 then A_RGTC1 (Hap Q Alpha, both textures in one pass).  Outputs are in host or
+ * device memory, device outputs aligned to their blocks; outputsBytesUsed may be NULL.  The layer arguments are
+ * HapGpuCompositeTexturesPlaced's and follow its rules.
+ * Bad_Arguments, and nothing written and no device touched, for everything HapGpuCompositeTexturesPlaced refuses of its
+ * layer sizes, placements, layerCount, width and height, a canvas of more than 65535 block rows, a count of 0 or above
+ * 2, any other destination set, a NULL required array; Bad_Arguments, and nothing written, for a NULL or short texture,
+ * another layer format, a NULL output, a misaligned device address; Buffer_Too_Small for an output shorter than its
+ * texture.  A context between HapGpuEncodeFramesRGBABegin and HapGpuEncodeFramesFinish: Internal_Error.
+ * Out of scope: scaled or rotated layers; RGBA_BPTC_UNORM (BC7), BC6H and Alpha-Only (lone A_RGTC1) layers or
+ * destinations; refined end points; NV12 or planar output; un-premultiplying the canvas. */
+unsigned int HapGpuCompositeTexturesEncoded(HapGpuContext *context, unsigned int layerCount,
+                                            const void *const *textures, const unsigned long *texturesBytes,
+                                            const unsigned int *textureFormats,
+                                            const void *const *alphaTextures, const unsigned long *alphaTexturesBytes,
+                                            const unsigned int *layerWidths, const unsigned int *layerHeights,
+                                            const HapGpuPlacement *placements,
+                                            const unsigned char *opacities,
+                                            const unsigned char *background,
+                                            unsigned int width, unsigned int height,
+                                            unsigned int count, const unsigned int *outputFormats,
+                                            void *const *outputs, const unsigned long *outputsBytes,
+                                            unsigned long *outputsBytesUsed);
+
+/* Layers of frames in, one Hap frame per output frame out: HapGpuCompositeFramesPlaced whose canvases go on to the encoder
+ * as HapGpuTranscodeFrames' textures do -- a title or lower third baked into a master, a dissolve or a mosaic rendered
+ * into one Hap movie, a programme output recorded.  The input side (inputBuffers, inputBuffersBytes, textureCounts,
+ * layerWidths, layerHeights, placements, opacities, background, width, height, decodeFlags) is
+ * HapGpuCompositeFramesPlaced's; the output side (count, textureFormats, compressors, chunkCounts, outputBuffers,
+ * outputBuffersBytes, outputBuffersBytesUsed, results, encodeFlags) is HapGpuTranscodeFrames'.
+ * The definition, and the only one: output frame f is byte for byte, and in outputBuffersBytesUsed, the frame
+ * HapGpuEncodeFramesRGBA(..., width, height, width * 4, count, textureFormats, compressors, chunkCounts, ...,
+ * encodeFlags) makes of the picture HapGpuCompositeFramesPlaced writes for the same layers, placements, opacities and
+ * background -- encodeFlags without HAPGPU_ENCODE_BPTC_BLOCKS and HAPGPU_ENCODE_REFINE_ENDPOINTS, which are ignored as
+ * in HapGpuTranscodeFrames.  The canvas bytes go to the encoder as they are: the canvas is premultiplied by its alpha,
+ * so with an opaque background the result is opaque.  No such picture ever exists: the layers' textures go from the
+ * decoder's second stage through HapGpuCompositeTexturesEncoded's kernel (one launch per slice) to the encoder's second
+ * stage, and the host is waited for twice per slice.  Two calls give the same bytes.
+ * Destination sets, the four of HapGpuCompositeTexturesEncoded -- count 1: RGB_DXT1, RGBA_DXT5 or YCoCg_DXT5; count 2:
+ * YCoCg_DXT5 then A_RGTC1.  Buffers may be host or device.  Slices: at most 4 GiB of block textures, the canvases' among
+ * them, and 32768 textures of the second stage at a time.
+ * layerResults is a HOST array of frameCount * layerCount entries: layerResults[f * layerCount + l] is what
+ * HapGpuCompositeFramesPlaced sets for that layer's frame -- HapDecode's code, Bad_Arguments for a frame of another
+ * format or geometry than the call says.  results is a HOST array of frameCount entries.  Output frame f is encoded if
+ * and only if all its layers are No_Error; otherwise results[f] is the first failing layer's code,
+ * outputBuffersBytesUsed[f] is 0 and its output buffer is untouched.  Where the layers are in order results[f] is the
+ * encode's code, as HapGpuEncodeFramesRGBA sets it (a NULL output: Bad_Arguments, a short one: Buffer_Too_Small), and
+ * a failed frame does not disturb its neighbours.  The function's result is the first failure in results.
+ * Bad_Arguments for the whole call -- every entry of results and of layerResults set, nothing written, no device
+ * touched, before the context is looked at -- for everything HapGpuCompositeFramesPlaced refuses of its layer sizes,
+ * placements, layerCount, textureCounts, width and height, a canvas of more than 65535 block rows, a count of 0 or
+ * above 2, any other destination set, what HapGpuEncodeFrames refuses of textureFormats, compressors and chunkCounts,
+ * and a NULL required array (a NULL results or layerResults: the other is still set).  A context between
+ * HapGpuEncodeFramesRGBABegin and HapGpuEncodeFramesFinish: Internal_Error.
+ * Out of scope: scaled or rotated layers; Hap R (BC7), Hap HDR (BC6H) and Hap Alpha-Only layers or destinations;
+ * refined end points; NV12 or planar output; un-premultiplying the canvas; ...OnDevices, ...Sequence and ...Begin forms
+ * of this call. */
+unsigned int HapGpuCompositeFramesEncoded(HapGpuContext *context, unsigned int frameCount, unsigned int layerCount,
+                                          const void *const *inputBuffers, const unsigned long *inputBuffersBytes,
+                                          const unsigned int *textureCounts,
+                                          const unsigned int *layerWidths, const unsigned int *layerHeights,
+                                          const HapGpuPlacement *placements,
+                                          const unsigned char *opacities,
+                                          const unsigned char *background,
+                                          unsigned int width, unsigned int height,
+                                          unsigned int count, const unsigned int *textureFormats,
+                                          const unsigned int *compressors, const unsigned int *chunkCounts,
+                                          void *const *outputBuffers, const unsigned long *outputBuffersBytes,
+                                          unsigned long *outputBuffersBytesUsed,
+                                          unsigned int *layerResults, unsigned int *results,
+                                          unsigned int decodeFlags, unsigned int encodeFlags);
+
 /* Planar float tensors in, frames out -- the way back of HapGpuDecodeFramesPlanes: HapGpuEncodeFramesRGBA with the tensors of
  * HapGpuCompressPlanes in place of pictures.  planeFrames[f] is frame f's tensor in DEVICE memory, `channels` planes of
  * width x height elements, planeBytes and rowBytes shared by all frames (one N x C x H x W tensor: planeFrames[f] = base +
