@@ -1138,14 +1138,16 @@ unsigned int HapGpuCompositeTextures(HapGpuContext *context, unsigned int layerC
                                      const unsigned char *opacities, const unsigned char *background, unsigned int width,
                                      unsigned int height, void *rgba, unsigned long rowBytes)
 {
+    const HapbComposite composite = {.layer_count = layerCount, .width = width, .height = height, .background = background,
+                                     .opacities = opacities, .row_bytes = rowBytes};
+    void *const picture[1] = {rgba};
     unsigned r;
     /* (what is wrong with the call whatever its layers hold is seen before the context is looked at) */
-    if (!context || !textures || !texturesBytes || !textureFormats || !rgba ||
-        !hapb_composite_valid(layerCount, width, height, rowBytes, NULL))
+    if (!context || !textures || !texturesBytes || !textureFormats || !rgba || !hapb_composite_valid(&composite, 1u, NULL, 0))
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
-    r = hapb_composite_textures(context, layerCount, textures, texturesBytes, textureFormats, alphaTextures,
-                                alphaTexturesBytes, opacities, background, width, height, rgba, rowBytes);
+    r = hapb_composite_textures(context, &composite, textures, texturesBytes, textureFormats, alphaTextures,
+                                alphaTexturesBytes, picture, NULL, NULL);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -1158,15 +1160,16 @@ unsigned int HapGpuCompositeFrames(HapGpuContext *context, unsigned int frameCou
                                    const unsigned char *background, void *const *rgbaFrames, unsigned int width,
                                    unsigned int height, unsigned long rowBytes, unsigned int *results, unsigned int flags)
 {
+    const HapbComposite composite = {.layer_count = layerCount, .width = width, .height = height, .background = background,
+                                     .opacities = opacities, .row_bytes = rowBytes};
     unsigned r;
     if (!context || !results)
         return HapResult_Bad_Arguments;
-    if (!inputBuffers || !inputBuffersBytes || !rgbaFrames ||
-        !hapb_composite_valid(layerCount, width, height, rowBytes, textureCounts))
+    if (!inputBuffers || !inputBuffersBytes || !rgbaFrames || !hapb_composite_valid(&composite, frameCount, textureCounts, 1))
         return refuse_call(results, (size_t)frameCount * layerCount);
     hapgpu_rt_lock(context->rt);
-    r = hapb_composite_frames(context, frameCount, layerCount, inputBuffers, inputBuffersBytes, textureCounts, opacities,
-                              background, rgbaFrames, width, height, rowBytes, results, flags);
+    r = hapb_composite_frames(context, &composite, frameCount, inputBuffers, inputBuffersBytes, textureCounts, rgbaFrames,
+                              NULL, NULL, results, NULL, flags);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -1181,14 +1184,18 @@ unsigned int HapGpuCompositeTexturesPlaced(HapGpuContext *context, unsigned int 
                                            const unsigned char *background, unsigned int width, unsigned int height,
                                            void *rgba, unsigned long rowBytes)
 {
+    const HapbComposite composite = {.layer_count = layerCount, .width = width, .height = height, .background = background,
+                                     .opacities = opacities, .layer_widths = layerWidths, .layer_heights = layerHeights,
+                                     .placements = placements, .row_bytes = rowBytes};
+    void *const picture[1] = {rgba};
     unsigned r;
-    if (!context || !textures || !texturesBytes || !textureFormats || !rgba ||
-        !hapb_composite_placed_valid(layerCount, layerWidths, layerHeights, placements, 1u, width, height, rowBytes, NULL))
+    /* (a description without layer sizes is the call above: this one has them) */
+    if (!context || !textures || !texturesBytes || !textureFormats || !rgba || !layerWidths ||
+        !hapb_composite_valid(&composite, 1u, NULL, 0))
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
-    r = hapb_composite_textures_placed(context, layerCount, textures, texturesBytes, textureFormats, alphaTextures,
-                                       alphaTexturesBytes, layerWidths, layerHeights, placements, opacities, background,
-                                       width, height, rgba, rowBytes);
+    r = hapb_composite_textures(context, &composite, textures, texturesBytes, textureFormats, alphaTextures,
+                                alphaTexturesBytes, picture, NULL, NULL);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -1201,20 +1208,21 @@ unsigned int HapGpuCompositeFramesPlaced(HapGpuContext *context, unsigned int fr
                                          void *const *rgbaFrames, unsigned int width, unsigned int height,
                                          unsigned long rowBytes, unsigned int *results, unsigned int flags)
 {
+    const HapbComposite composite = {.layer_count = layerCount, .width = width, .height = height, .background = background,
+                                     .opacities = opacities, .layer_widths = layerWidths, .layer_heights = layerHeights,
+                                     .placements = placements, .row_bytes = rowBytes};
     unsigned r;
     if (!results)
         return HapResult_Bad_Arguments;
     /* (what is wrong with the call itself sets every result whatever the context is, a NULL one included) */
-    if (!inputBuffers || !inputBuffersBytes || !rgbaFrames ||
-        !hapb_composite_placed_valid(layerCount, layerWidths, layerHeights, placements, frameCount, width, height,
-                                     rowBytes, textureCounts))
+    if (!inputBuffers || !inputBuffersBytes || !rgbaFrames || !layerWidths ||
+        !hapb_composite_valid(&composite, frameCount, textureCounts, 1))
         return refuse_call(results, (size_t)frameCount * layerCount);
     if (!context)
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
-    r = hapb_composite_frames_placed(context, frameCount, layerCount, inputBuffers, inputBuffersBytes, textureCounts,
-                                     layerWidths, layerHeights, placements, opacities, background, rgbaFrames, width,
-                                     height, rowBytes, results, flags);
+    r = hapb_composite_frames(context, &composite, frameCount, inputBuffers, inputBuffersBytes, textureCounts, rgbaFrames,
+                              NULL, NULL, results, NULL, flags);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -1232,15 +1240,16 @@ unsigned int HapGpuCompositeTexturesEncoded(HapGpuContext *context, unsigned int
                                             unsigned int count, const unsigned int *outputFormats, void *const *outputs,
                                             const unsigned long *outputsBytes, unsigned long *outputsBytesUsed)
 {
+    const HapbComposite composite = {.layer_count = layerCount, .width = width, .height = height, .background = background,
+                                     .opacities = opacities, .layer_widths = layerWidths, .layer_heights = layerHeights,
+                                     .placements = placements, .encoded = 1, .count = count, .formats = outputFormats};
     unsigned r;
     if (!context || !textures || !texturesBytes || !textureFormats || !outputs || !outputsBytes ||
-        !hapb_composite_encode_textures_valid(layerCount, layerWidths, layerHeights, placements, 1u, width, height, NULL,
-                                              count, outputFormats))
+        !hapb_composite_valid(&composite, 1u, NULL, 0))
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
-    r = hapb_composite_encode_textures(context, layerCount, textures, texturesBytes, textureFormats, alphaTextures,
-                                       alphaTexturesBytes, layerWidths, layerHeights, placements, opacities, background,
-                                       width, height, count, outputFormats, outputs, outputsBytes, outputsBytesUsed);
+    r = hapb_composite_textures(context, &composite, textures, texturesBytes, textureFormats, alphaTextures,
+                                alphaTexturesBytes, outputs, outputsBytes, outputsBytesUsed);
     hapgpu_rt_unlock(context->rt);
     return r;
 }
@@ -1257,21 +1266,21 @@ unsigned int HapGpuCompositeFramesEncoded(HapGpuContext *context, unsigned int f
                                           unsigned int *layerResults, unsigned int *results, unsigned int decodeFlags,
                                           unsigned int encodeFlags)
 {
+    const HapbComposite composite = {.layer_count = layerCount, .width = width, .height = height, .background = background,
+                                     .opacities = opacities, .layer_widths = layerWidths, .layer_heights = layerHeights,
+                                     .placements = placements, .encoded = 1, .count = count, .formats = textureFormats,
+                                     .compressors = compressors, .chunk_counts = chunkCounts, .encode_flags = encodeFlags};
     unsigned r;
     if (!results || !layerResults || !inputBuffers || !inputBuffersBytes || !outputBuffers || !outputBuffersBytes ||
-        !outputBuffersBytesUsed ||
-        !hapb_composite_encode_frames_valid(layerCount, layerWidths, layerHeights, placements, frameCount, width, height,
-                                            textureCounts, count, textureFormats, compressors, chunkCounts, encodeFlags)) {
+        !outputBuffersBytesUsed || !hapb_composite_valid(&composite, frameCount, textureCounts, 1)) {
         refuse_call(layerResults, (size_t)frameCount * layerCount);
         return refuse_call(results, frameCount);
     }
     if (!context)
         return HapResult_Bad_Arguments;
     hapgpu_rt_lock(context->rt);
-    r = hapb_composite_encode_frames(context, frameCount, layerCount, inputBuffers, inputBuffersBytes, textureCounts,
-                                     layerWidths, layerHeights, placements, opacities, background, width, height, count,
-                                     textureFormats, compressors, chunkCounts, outputBuffers, outputBuffersBytes,
-                                     outputBuffersBytesUsed, layerResults, results, decodeFlags, encodeFlags);
+    r = hapb_composite_frames(context, &composite, frameCount, inputBuffers, inputBuffersBytes, textureCounts,
+                              outputBuffers, outputBuffersBytes, outputBuffersBytesUsed, layerResults, results, decodeFlags);
     hapgpu_rt_unlock(context->rt);
     return r;
 }

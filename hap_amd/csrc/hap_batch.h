@@ -260,83 +260,52 @@ unsigned hapb_transcode_texture(HapGpuContext *ctx, const void *texture, unsigne
                                 unsigned scale_log2, unsigned count, const unsigned *formats, void *const *outputs,
                                 const unsigned long *output_bytes, unsigned long *output_used);
 
-/* what both compositing calls ask whatever their layers are: 1 = the layer count, the geometry, the pitch and (where
-   given) every texture count are in order (include/hap_gpu.h: HapGpuCompositeTextures, HapGpuCompositeFrames).
-   Touches no device. */
-int hapb_composite_valid(unsigned layer_count, unsigned width, unsigned height, unsigned long row_bytes,
-                         const unsigned *texture_counts);
-/* layer_count textures (+ RGTC1 alpha planes; host or device), layer 0 at the bottom, "over" a background colour -> one
-   RGBA8 picture (HapGpuCompositeTextures) */
-unsigned hapb_composite_textures(HapGpuContext *ctx, unsigned layer_count, const void *const *textures,
+/* A compositing call: the canvas, what the layers are on it and where the canvas goes.  Filled with designated
+   initialisers, everything not named being 0 / NULL: layers of the canvas's size, whole at (0, 0), fully opaque over
+   opaque black, to RGBA8 pictures.  What follows from it -- the rules, the descriptors, the kernel -- is decided in one
+   place each (hap_pictures.c: hapb_composite_valid, composite_descriptor, launch_composite). */
+typedef struct HapbComposite {
+    unsigned layer_count;               /* layer 0 at the bottom */
+    unsigned width, height;             /* the canvas */
+    const unsigned char *background;    /* 4 bytes R, G, B, A (NULL: 0, 0, 0, 255) */
+    const unsigned char *opacities;     /* one byte per layer of every output frame (NULL: all 255) */
+    const unsigned *layer_widths, *layer_heights;   /* NULL: every layer has the canvas's size (HapGpuCompositeTextures,
+                                           HapGpuCompositeFrames); else layer l is layer_widths[l] x layer_heights[l] */
+    const HapGpuPlacement *placements;  /* (layer sizes only) one per layer of every output frame: the rectangle of the
+                                           layer and where it goes, clipped to the canvas (hap_place.h); NULL: every layer
+                                           whole at (0, 0) */
+    /* the destination, one of two: RGBA8 pictures, host or device, rows row_bytes apart ... */
+    unsigned long row_bytes;
+    /* ... or (encoded != 0; layer sizes only) the canvas encoded to `count` block textures of `formats`, one of the four
+       destination sets of hapb_transcode's kernel, never written as a picture -- and, for frames, made frames of by
+       hapb_encode with compressors, chunk_counts and encode_flags */
+    int encoded;
+    unsigned count;
+    const unsigned *formats, *compressors, *chunk_counts;
+    unsigned encode_flags;
+} HapbComposite;
+/* what a compositing call asks whatever its layers hold: 1 = the layer count, the canvas, the pitch, every texture count
+   (frames; NULL: all 1), every layer's size and every one of the frame_count * layer_count placements (hap_place.h) are
+   in order; encoded: at most 65535 block rows and a destination set the kernel makes, and for `frames` compressors and
+   chunk counts that hapb_encode takes with it (include/hap_gpu.h: HapGpuCompositeTextures to
+   HapGpuCompositeFramesEncoded).  Touches no device. */
+int hapb_composite_valid(const HapbComposite *composite, size_t frame_count, const unsigned *texture_counts, int frames);
+/* layer_count textures (+ RGTC1 alpha planes; host or device) -> one canvas: outputs[0] the picture, or outputs[i]
+   destination texture i (host or device) of output_bytes[i], output_used[i] (NULL: not wanted) the bytes written; a
+   call to pictures takes neither */
+unsigned hapb_composite_textures(HapGpuContext *ctx, const HapbComposite *composite, const void *const *textures,
                                  const unsigned long *texture_bytes, const unsigned *formats,
-                                 const void *const *alphas, const unsigned long *alpha_bytes,
-                                 const unsigned char *opacities, const unsigned char *background, unsigned width,
-                                 unsigned height, void *picture, unsigned long row_bytes);
-/* ... of frames: entry f * layer_count + l is layer l of output frame f, texture_counts[l] textures read of it; one RGBA8
-   picture per output frame (HapGpuCompositeFrames); results: frame_count * layer_count entries */
-unsigned hapb_composite_frames(HapGpuContext *ctx, unsigned frame_count, unsigned layer_count, const void *const *inputs,
-                               const unsigned long *input_bytes, const unsigned *texture_counts,
-                               const unsigned char *opacities, const unsigned char *background, void *const *rgba_frames,
-                               unsigned width, unsigned height, unsigned long row_bytes, unsigned *results, unsigned flags);
-/* what both placed compositing calls ask on top of hapb_composite_valid: 1 = every layer's size and every one of the
-   frame_count * layer_count placements (NULL: none to look at) are in order (hap_place.h; include/hap_gpu.h:
-   HapGpuCompositeTexturesPlaced, HapGpuCompositeFramesPlaced).  Touches no device. */
-int hapb_composite_placed_valid(unsigned layer_count, const unsigned *layer_widths, const unsigned *layer_heights,
-                                const HapGpuPlacement *placements, size_t frame_count, unsigned width, unsigned height,
-                                unsigned long row_bytes, const unsigned *texture_counts);
-/* hapb_composite_textures for layers of layer_widths[l] x layer_heights[l], placements[l] of each (NULL: whole, at
-   (0, 0)) placed and clipped on the width x height canvas (HapGpuCompositeTexturesPlaced) */
-unsigned hapb_composite_textures_placed(HapGpuContext *ctx, unsigned layer_count, const void *const *textures,
-                                        const unsigned long *texture_bytes, const unsigned *formats,
-                                        const void *const *alphas, const unsigned long *alpha_bytes,
-                                        const unsigned *layer_widths, const unsigned *layer_heights,
-                                        const HapGpuPlacement *placements, const unsigned char *opacities,
-                                        const unsigned char *background, unsigned width, unsigned height, void *picture,
-                                        unsigned long row_bytes);
-/* ... of frames: placements[f * layer_count + l] (HapGpuCompositeFramesPlaced) */
-unsigned hapb_composite_frames_placed(HapGpuContext *ctx, unsigned frame_count, unsigned layer_count,
-                                      const void *const *inputs, const unsigned long *input_bytes,
-                                      const unsigned *texture_counts, const unsigned *layer_widths,
-                                      const unsigned *layer_heights, const HapGpuPlacement *placements,
-                                      const unsigned char *opacities, const unsigned char *background,
-                                      void *const *rgba_frames, unsigned width, unsigned height, unsigned long row_bytes,
-                                      unsigned *results, unsigned flags);
-/* what both compositing calls that end in textures ask whatever their layers hold: 1 = hapb_composite_placed_valid for
-   a canvas with rows of width * 4 bytes, at most 65535 block rows, and `count` formats that are one of the four
-   destination sets of hapb_transcode's kernel (include/hap_gpu.h: HapGpuCompositeTexturesEncoded).  Touches no device. */
-int hapb_composite_encode_textures_valid(unsigned layer_count, const unsigned *layer_widths, const unsigned *layer_heights,
-                                         const HapGpuPlacement *placements, size_t frame_count, unsigned width,
-                                         unsigned height, const unsigned *texture_counts, unsigned count,
-                                         const unsigned *formats);
-/* ... and what the frames call asks on top: compressors and chunk_counts, neither NULL, that hapb_encode takes with the
-   formats and encode_flags for textures of the canvas's size (HapGpuCompositeFramesEncoded).  Touches no device. */
-int hapb_composite_encode_frames_valid(unsigned layer_count, const unsigned *layer_widths, const unsigned *layer_heights,
-                                       const HapGpuPlacement *placements, size_t frame_count, unsigned width,
-                                       unsigned height, const unsigned *texture_counts, unsigned count,
-                                       const unsigned *formats, const unsigned *compressors,
-                                       const unsigned *chunk_counts, unsigned encode_flags);
-/* hapb_composite_textures_placed with the canvas encoded to `count` textures of out_formats (host or device) instead of
-   written as a picture (HapGpuCompositeTexturesEncoded) */
-unsigned hapb_composite_encode_textures(HapGpuContext *ctx, unsigned layer_count, const void *const *textures,
-                                        const unsigned long *texture_bytes, const unsigned *formats,
-                                        const void *const *alphas, const unsigned long *alpha_bytes,
-                                        const unsigned *layer_widths, const unsigned *layer_heights,
-                                        const HapGpuPlacement *placements, const unsigned char *opacities,
-                                        const unsigned char *background, unsigned width, unsigned height, unsigned count,
-                                        const unsigned *out_formats, void *const *outputs,
-                                        const unsigned long *output_bytes, unsigned long *output_used);
-/* hapb_composite_frames_placed up to its launch, hapb_transcode from its launch on: one frame of `formats` per output
-   frame (HapGpuCompositeFramesEncoded); layer_results: frame_count * layer_count entries, results: frame_count */
-unsigned hapb_composite_encode_frames(HapGpuContext *ctx, unsigned frame_count, unsigned layer_count,
-                                      const void *const *inputs, const unsigned long *input_bytes,
-                                      const unsigned *texture_counts, const unsigned *layer_widths,
-                                      const unsigned *layer_heights, const HapGpuPlacement *placements,
-                                      const unsigned char *opacities, const unsigned char *background, unsigned width,
-                                      unsigned height, unsigned count, const unsigned *formats,
-                                      const unsigned *compressors, const unsigned *chunk_counts, void *const *outputs,
-                                      const unsigned long *output_bytes, unsigned long *output_used,
-                                      unsigned *layer_results, unsigned *results, unsigned decode_flags,
-                                      unsigned encode_flags);
+                                 const void *const *alphas, const unsigned long *alpha_bytes, void *const *outputs,
+                                 const unsigned long *output_bytes, unsigned long *output_used);
+/* ... of frames: entry f * layer_count + l is layer l of output frame f, texture_counts[l] textures read of it, its
+   result layer_results[f * layer_count + l]; outputs[f] the picture of output frame f -- a NULL or misaligned one fails
+   every layer entry of its frame, and results is NULL -- or, encoded, its frame with output_bytes, output_used and
+   results as hapb_transcode has them, the result of an output frame with a failed layer being that layer's */
+unsigned hapb_composite_frames(HapGpuContext *ctx, const HapbComposite *composite, unsigned frame_count,
+                               const void *const *inputs, const unsigned long *input_bytes,
+                               const unsigned *texture_counts, void *const *outputs, const unsigned long *output_bytes,
+                               unsigned long *output_used, unsigned *layer_results, unsigned *results,
+                               unsigned decode_flags);
 
 /* groups and output in device memory: tables through the host, payloads device to device */
 unsigned hapb_join_device(HapGpuContext *ctx, unsigned group_count, const void *const *frames,

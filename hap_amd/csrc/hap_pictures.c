@@ -363,14 +363,14 @@ typedef char slice_members_hold_layers[HAPGPU_COMPOSITE_MAX_LAYERS <= HAP_SLICE_
 
 /* The second stage of a slice of a call's output frames into texture scratch, for everything that goes on from block
    textures (hapb_road_frames, hapb_composite_frames, hapb_transcode).  An output frame has at.member_count members --
-   one, or a layer each --, member m of the call's output frame f being the call's input f * member_count + m.  Entry
-   f * at.entries_per_frame + at.entry_of[m] + t is texture t of member m of the slice's frame f: the colour texture at
-   at.per_frame * f + at.offset_of[m] of the slice's D_BC_TEX scratch, the RGTC1 alpha plane at + at.alpha_off
-   (hap_slice.h).  The textures of one member stay adjacent: hapb_decode uploads a host frame once for them. */
+   one, or a layer each, of a size of its own --, member m of the call's output frame f being the call's input
+   f * member_count + m.  Entry f * at.entries_per_frame + at.entry_of[m] + t is texture t of member m of the slice's
+   frame f: the colour texture at at.per_frame * f + at.offset_of[m] of the slice's D_BC_TEX scratch, the RGTC1 alpha
+   plane at + layout.alpha_off_of[m] (hap_place.h; `at` is layout.at).  The textures of one member stay adjacent:
+   hapb_decode uploads a host frame once for them. */
 typedef struct slice_textures {
-    hap_slice_layout at;
-    const hap_place_layout *placed;         /* (members of sizes of their own: their blocks and planes; else NULL) */
-    unsigned width, height;
+    hap_place_layout layout;
+    unsigned width, height;                 /* (member 0's: a road with rectangles has one member) */
     /* per entry, one allocation (`in` is its start): what hapb_decode is given ... */
     const void **in;
     unsigned long *in_bytes, *caps;
@@ -382,21 +382,17 @@ typedef struct slice_textures {
     unsigned *fmts, *res;
 } slice_textures;
 
-/* the blocks of member m's textures, and how far behind its colour texture its plane lies */
-static size_t member_blocks(const slice_textures *s, unsigned m)
+/* The arrays of a slice's entries and its layout.  counts: the members' texture counts (NULL: all 1); widths, heights:
+   their sizes, one each; extra_per_frame: what else the caller holds per frame while a slice's textures are held;
+   rectangles != 0: room for a rectangle per entry.  0: out of memory */
+static int slice_textures_init(slice_textures *s, unsigned frame_count, unsigned member_count, const unsigned *counts,
+                               const unsigned *widths, const unsigned *heights, size_t extra_per_frame, int rectangles)
 {
-    return s->placed ? s->placed->blocks_of[m] : s->at.blocks;
-}
-
-static size_t member_alpha_off(const slice_textures *s, unsigned m)
-{
-    return s->placed ? s->placed->alpha_off_of[m] : s->at.alpha_off;
-}
-
-/* the arrays of a slice's entries, s->at being laid out.  0: out of memory */
-static int slice_textures_alloc(slice_textures *s, int rectangles)
-{
-    const size_t entries = s->at.slice * s->at.entries_per_frame;
+    size_t entries;
+    s->width = widths[0];
+    s->height = heights[0];
+    hap_place_layout_of(&s->layout, member_count, counts, widths, heights, extra_per_frame, frame_count);
+    entries = s->layout.at.slice * s->layout.at.entries_per_frame;
     s->in = (const void **)malloc(entries * (2u * sizeof(void *) + 3u * sizeof(unsigned long) + 3u * sizeof(unsigned) +
                                              (rectangles ? sizeof(HapGpuRegion) : 0u)));
     if (!s->in)
@@ -412,30 +408,7 @@ static int slice_textures_alloc(slice_textures *s, int rectangles)
     return 1;
 }
 
-/* counts: the members' texture counts (NULL: all 1); extra_per_frame: what else the caller holds per frame while a
-   slice's textures are held; rectangles != 0: room for a rectangle per entry.  0: out of memory */
-static int slice_textures_init(slice_textures *s, unsigned frame_count, unsigned member_count, const unsigned *counts,
-                               unsigned width, unsigned height, size_t extra_per_frame, int rectangles)
-{
-    s->placed = NULL;
-    s->width = width;
-    s->height = height;
-    hap_slice_layout_of(&s->at, member_count, counts, width, height, extra_per_frame, frame_count);
-    return slice_textures_alloc(s, rectangles);
-}
-
-/* ... for members of sizes of their own (`placed`: their layout, which the caller keeps while s is used); whole frames
-   alone: width and height are no member's and 0 */
-static int slice_textures_init_placed(slice_textures *s, const hap_place_layout *placed)
-{
-    s->placed = placed;
-    s->width = 0u;
-    s->height = 0u;
-    s->at = placed->at;
-    return slice_textures_alloc(s, 0);
-}
-
-/* Output frames done .. done + n of the call (n <= s->at.slice) into `textures`, at.per_frame * n bytes of D_BC_TEX
+/* Output frames done .. done + n of the call (n <= at.slice) into `textures`, at.per_frame * n bytes of D_BC_TEX
    scratch.  road (NULL: whole textures) -- its region: the rectangle wanted of every frame -- or, with region_xs and
    region_ys, its size alone, frame f's origin being (xs[f], ys[f]): a frame whose origin puts the rectangle off the grid or
    past an edge goes to hapb_decode with a NULL input, its Bad_Arguments, and nothing of it is decoded.  Its resize: frame
@@ -445,7 +418,8 @@ static void slice_textures_decode(HapGpuContext *ctx, const slice_textures *s, u
                                   const unsigned long *input_bytes, size_t done, unsigned n, const HapbRoad *road,
                                   unsigned flags)
 {
-    const unsigned width = s->width, height = s->height, members = s->at.member_count;
+    const hap_slice_layout *const at = &s->layout.at;
+    const unsigned width = s->width, height = s->height, members = at->member_count;
     const HapGpuRegion whole = {width, 0u, 0u, width, height};
     const HapGpuRegion *const region = road ? road->region : NULL;
     const unsigned *const xs = road ? road->region_xs : NULL, *const ys = road ? road->region_ys : NULL;
@@ -472,14 +446,14 @@ static void slice_textures_decode(HapGpuContext *ctx, const slice_textures *s, u
         else if (own.x != 0u || own.y != 0u || own.w != width || own.h != height)
             any_skip = 1;
         for (m = 0; m < members; m++)
-            for (t = 0; t < s->at.count_of[m]; t++) {
-                const size_t e = (size_t)f * s->at.entries_per_frame + s->at.entry_of[m] + t;
+            for (t = 0; t < at->count_of[m]; t++) {
+                const size_t e = (size_t)f * at->entries_per_frame + at->entry_of[m] + t;
                 if (s->decode_regions)
                     s->decode_regions[e] = own;
                 s->in[e] = refused ? NULL : inputs[(done + f) * members + m];
                 s->in_bytes[e] = input_bytes[(done + f) * members + m];
-                s->outs[e] = textures + s->at.per_frame * f + s->at.offset_of[m] + (t ? member_alpha_off(s, m) : 0u);
-                s->caps[e] = (unsigned long)(t ? member_blocks(s, m) * 8u : member_blocks(s, m) * 16u);
+                s->outs[e] = textures + at->per_frame * f + at->offset_of[m] + (t ? s->layout.alpha_off_of[m] : 0u);
+                s->caps[e] = (unsigned long)(s->layout.blocks_of[m] * (t ? 8u : 16u));
                 s->idx[e] = t;
                 s->used[e] = 0;
                 s->fmts[e] = 0;
@@ -491,26 +465,19 @@ static void slice_textures_decode(HapGpuContext *ctx, const slice_textures *s, u
         args.regions = any_skip ? s->decode_regions : NULL;
     else if (region && !(region->x == 0u && region->y == 0u && region->w == width && region->h == height))
         args.region = region;
-    hapb_decode(ctx, n * s->at.entries_per_frame, s->in, s->in_bytes, 0, s->outs, s->caps, s->used, s->fmts, s->res,
+    hapb_decode(ctx, n * at->entries_per_frame, s->in, s->in_bytes, 0, s->outs, s->caps, s->used, s->fmts, s->res,
                 flags & ~HAPGPU_DECODE_BPTC_PICTURES, &args);
 }
 
-/* 1: entry e of a decoded slice (and, count 2, entry e + 1) holds what the caller's geometry says: a colour texture of
-   `kinds`, of exactly width x height, and (two textures) an RGTC1 plane of the same geometry */
-static int slice_entry_fits(const slice_textures *s, size_t e, unsigned count, const unsigned *kinds, unsigned kind_count)
+/* 1: entry e of a decoded slice, member m's first (and, two textures read of it, entry e + 1), holds what the caller's
+   geometry says: a colour texture of `kinds`, of exactly the member's blocks, and (two textures) an RGTC1 plane of the
+   same geometry */
+static int slice_entry_fits(const slice_textures *s, size_t e, unsigned m, const unsigned *kinds, unsigned kind_count)
 {
     const unsigned fmt = s->fmts[e];
-    return kind_of(kinds, kind_count, fmt) != kind_count && s->used[e] == s->at.blocks * hapf_block_bytes(fmt) &&
-           (count != 2u || (s->fmts[e + 1] == HapTextureFormat_A_RGTC1 && s->used[e + 1] == s->at.blocks * 8u));
-}
-
-/* ... for member m of a slice whose members have sizes of their own: exactly that member's blocks */
-static int slice_entry_fits_member(const slice_textures *s, size_t e, unsigned m, const unsigned *kinds, unsigned kind_count)
-{
-    const unsigned fmt = s->fmts[e];
-    const size_t blocks = member_blocks(s, m);
+    const size_t blocks = s->layout.blocks_of[m];
     return kind_of(kinds, kind_count, fmt) != kind_count && s->used[e] == blocks * hapf_block_bytes(fmt) &&
-           (s->at.count_of[m] != 2u || (s->fmts[e + 1] == HapTextureFormat_A_RGTC1 && s->used[e + 1] == blocks * 8u));
+           (s->layout.at.count_of[m] != 2u || (s->fmts[e + 1] == HapTextureFormat_A_RGTC1 && s->used[e + 1] == blocks * 8u));
 }
 
 /* frames down a road (DESIGN.md's `decode_pictures`, its roads' descriptions being `picture_road`s): one picture each */
@@ -557,14 +524,14 @@ unsigned hapb_road_frames(HapGpuContext *ctx, unsigned frame_count, const void *
     if (road->measure)
         memset(road->measure, 0, sizeof(*road->measure) * frame_count);
     shape.bytes = (size_t)row_bytes * (picture_height - 1u) + pixel_row;
-    if (!slice_textures_init(&s, frame_count, 1u, &texture_count, width, height, 0u, per_frame_regions)) {
+    if (!slice_textures_init(&s, frame_count, 1u, &texture_count, &width, &height, 0u, per_frame_regions)) {
         for (f = 0; f < frame_count; f++)
             results[f] = HapResult_Internal_Error;
         return HapResult_Internal_Error;
     }
-    for (done = 0; done < frame_count; done += s.at.slice) {
-        const unsigned n = (unsigned)(frame_count - done < s.at.slice ? frame_count - done : s.at.slice);
-        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, s.at.per_frame * n);
+    for (done = 0; done < frame_count; done += s.layout.at.slice) {
+        const unsigned n = (unsigned)(frame_count - done < s.layout.at.slice ? frame_count - done : s.layout.at.slice);
+        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, s.layout.at.per_frame * n);
         uint8_t *stage = NULL;
         const unsigned long long *htotals_of_slice = NULL;
         int rc = 0;
@@ -614,7 +581,7 @@ unsigned hapb_road_frames(HapGpuContext *ctx, unsigned frame_count, const void *
                     r = HapResult_Bad_Arguments;
                 /* the frame must hold what the caller's geometry says, in a format of the road (BC7 only when the caller
                    asked for Hap R pictures) */
-                if (r == HapResult_No_Error && !slice_entry_fits(&s, e, texture_count, kinds, kind_count))
+                if (r == HapResult_No_Error && !slice_entry_fits(&s, e, 0u, kinds, kind_count))
                     r = HapResult_Bad_Arguments;
                 /* (a video picture's other plane: NULL, in host memory or misaligned refuses the frame) */
                 if (r == HapResult_No_Error && road->video && !chroma_plane_fits(ctx, road->video->chroma[done + f]))
@@ -683,16 +650,109 @@ unsigned hapb_road_frames(HapGpuContext *ctx, unsigned frame_count, const void *
     return first_error;
 }
 
+/* ============================================================= destinations of block textures */
+/* What the calls that end in block textures or in frames of them share (transcoding, compositing to textures): the sets
+   of textures their kernels make, where a call's destination textures lie, and the encode half of a slice. */
+
+/* the destination sets the kernels make: 1 DXT1, 2 DXT5, 3 YCoCg-DXT5, 4 YCoCg-DXT5 + RGTC1 (Hap Q Alpha); 0: none of them */
+static unsigned transcode_set(unsigned count, const unsigned *formats)
+{
+    if (count == 1u)
+        return formats[0] == HapTextureFormat_RGB_DXT1 ? 1u : formats[0] == HapTextureFormat_RGBA_DXT5 ? 2u :
+               formats[0] == HapTextureFormat_YCoCg_DXT5 ? 3u : 0u;
+    return count == 2u && formats[0] == HapTextureFormat_YCoCg_DXT5 && formats[1] == HapTextureFormat_A_RGTC1 ? 4u : 0u;
+}
+
+/* (the destination blocks are the default encode's: no BC7, no refined end points) */
+#define DESTINATION_ENCODE_FLAGS(flags) ((flags) & ~(unsigned)(HAPGPU_ENCODE_BPTC_BLOCKS | HAPGPU_ENCODE_REFINE_ENDPOINTS))
+
+/* the `count` destination textures of one frame: their sizes, and where they lie, 256-byte aligned, in scratch of `total`
+   bytes a frame (D_TRANSCODED) */
+typedef struct destination_layout {
+    unsigned long bytes[2];
+    size_t off[2], total;
+} destination_layout;
+
+static void destination_layout_of(destination_layout *d, unsigned count, const unsigned *formats, unsigned width,
+                                  unsigned height)
+{
+    unsigned i;
+    memset(d, 0, sizeof(*d));
+    for (i = 0; i < count; i++) {
+        d->bytes[i] = (unsigned long)((size_t)(width / 4u) * (height / 4u) * hapf_block_bytes(formats[i]));
+        d->off[i] = d->total;
+        d->total += align_up(d->bytes[i], 256);
+    }
+}
+
+/* every output of a call that writes textures, HapGpuTranscodeTexture's rules: there, large enough, and in device memory
+   aligned to its blocks */
+static unsigned destination_textures_fit(HapGpuContext *ctx, const destination_layout *d, unsigned count,
+                                         const unsigned *formats, void *const *outputs, const unsigned long *output_bytes)
+{
+    unsigned i;
+    for (i = 0; i < count; i++)
+        if (!outputs[i])
+            return HapResult_Bad_Arguments;
+    for (i = 0; i < count; i++)
+        if (output_bytes[i] < d->bytes[i])
+            return HapResult_Buffer_Too_Small;
+    for (i = 0; i < count; i++)
+        if (is_dev(ctx, outputs[i]) && ((uintptr_t)outputs[i] & (hapf_block_bytes(formats[i]) - 1u)))
+            return HapResult_Bad_Arguments;
+    return HapResult_No_Error;
+}
+
+/* The encode half of a slice of n frames, on the same stream behind the kernel; it ends with the slice's second and last
+   wait.  tex: per frame and destination texture, what hapb_encode reads (device memory; NULL: the frame is left out);
+   first_half[f]: what frame f's decode or compositing half came to, which is its result where it failed -- and, with
+   failed_use_nothing, its output_used is then 0 whatever hapb_encode left there; rc: the slice's launches and copies.
+   results, outputs, output_bytes, output_used: the slice's. */
+static void slice_encode_half(HapGpuContext *ctx, unsigned n, const void **tex, const unsigned *first_half, int rc,
+                              int failed_use_nothing, const destination_layout *d, unsigned count, const unsigned *formats,
+                              const unsigned *compressors, const unsigned *chunk_counts, unsigned encode_flags,
+                              void *const *outputs, const unsigned long *output_bytes, unsigned long *output_used,
+                              unsigned *results, unsigned *first_error)
+{
+    const HapbEncodeArgs device_textures = {1, NULL, 0, 0};
+    unsigned f;
+    if (rc)     /* (nothing of this slice's kernel output may be trusted: its frames fail, the pass-through ones included) */
+        memset(tex, 0, sizeof(*tex) * (size_t)n * count);
+    hapb_encode(ctx, n, count, tex, d->bytes, formats, compressors, chunk_counts, outputs, output_bytes, output_used, results,
+                DESTINATION_ENCODE_FLAGS(encode_flags), &device_textures);
+    for (f = 0; f < n; f++) {
+        if (first_half[f] != HapResult_No_Error) {
+            results[f] = first_half[f];
+            if (failed_use_nothing)
+                output_used[f] = 0;
+        } else if (rc && (results[f] == HapResult_No_Error || results[f] == HapResult_Bad_Arguments)) {
+            results[f] = HapResult_Internal_Error;
+        }
+        if (results[f] != HapResult_No_Error && *first_error == HapResult_No_Error)
+            *first_error = results[f];
+    }
+}
+
 /* ============================================================= compositing */
-/* Layers of textures or frames "over" a background colour -> one RGBA8 picture per output frame, by bc_composite.hip:
-   the layers' pictures never exist.  The textures form stages what lies in host memory into D_BC_TEX; the frames form
-   runs the second stage of all frameCount * layerCount frames of a slice in one batch into D_BC_TEX, as hapb_road_frames
-   does, a layer being a member of slice_textures with a texture count of its own, and one composite launch per slice
-   follows.  The descriptors and the pictures' addresses go out in one small table. */
+/* Layers of textures or frames "over" a background colour -> one canvas per output frame, by bc_composite.hip and
+   bc_composite_encode.hip: the layers' pictures never exist.  The call is its caller's description (HapbComposite,
+   hap_batch.h): layers of the canvas's size or of sizes of their own, placed and clipped (hap_place.h: the rules and the
+   clip), and a canvas that is written as an RGBA8 picture or goes to the block encoder in registers and comes out as
+   textures, which the frames form hands to hapb_encode as hapb_transcode does -- no picture anywhere.  The textures
+   form stages what lies in host memory into D_BC_TEX; the frames form runs the second stage of all frameCount *
+   layerCount frames of a slice in one batch into D_BC_TEX, as hapb_road_frames does, a layer being a member of
+   slice_textures with a texture count and a size of its own -- whole frames, whatever of them is visible --, and one
+   composite launch per slice follows.  The destinations' addresses and the descriptors go out in one small table. */
 
 static const unsigned char k_composite_background[4] = {0u, 0u, 0u, 255u};
 /* (the public limit is the kernel's) */
 typedef char composite_limits_agree[HAPGPU_COMPOSITE_MAX_LAYERS == HAPGPU_COMPOSITE_LAYERS_MAX ? 1 : -1];
+/* (a placed descriptor begins as a plain one: composite_descriptor writes both) */
+typedef char placed_layer_begins_plain[offsetof(HapGpuPlacedLayer, texture) == offsetof(HapGpuCompositeLayer, texture) &&
+                                       offsetof(HapGpuPlacedLayer, alpha) == offsetof(HapGpuCompositeLayer, alpha) &&
+                                       offsetof(HapGpuPlacedLayer, format) == offsetof(HapGpuCompositeLayer, format) &&
+                                       offsetof(HapGpuPlacedLayer, opacity) == offsetof(HapGpuCompositeLayer, opacity) &&
+                                       offsetof(HapGpuPlacedLayer, cx0) == sizeof(HapGpuCompositeLayer) ? 1 : -1];
 
 /* the colour formats a layer may have */
 static int composite_format(unsigned format)
@@ -700,247 +760,81 @@ static int composite_format(unsigned format)
     return format == HapTextureFormat_RGB_DXT1 || format == HapTextureFormat_RGBA_DXT5 || format == HapTextureFormat_YCoCg_DXT5;
 }
 
-int hapb_composite_valid(unsigned layer_count, unsigned width, unsigned height, unsigned long row_bytes,
-                         const unsigned *texture_counts)
+/* what the calls that end in textures ask on top (a block row per blockIdx.y of the kernel), and the frames form of them
+   on top of that */
+static int composite_destination_valid(const HapbComposite *c, int frames)
 {
+    destination_layout out;
+    if (!c->layer_widths || c->height / 4u > 65535u || !c->formats || c->count == 0 || c->count > 2 ||
+        !transcode_set(c->count, c->formats))
+        return 0;
+    if (!frames)
+        return 1;
+    if (!c->compressors || !c->chunk_counts)
+        return 0;
+    destination_layout_of(&out, c->count, c->formats, c->width, c->height);
+    return encode_textures_valid(c->count, out.bytes, c->formats, c->compressors, c->chunk_counts,
+                                 DESTINATION_ENCODE_FLAGS(c->encode_flags)) == HapResult_No_Error;
+}
+
+int hapb_composite_valid(const HapbComposite *c, size_t frame_count, const unsigned *texture_counts, int frames)
+{
+    const unsigned layer_count = c->layer_count, width = c->width, height = c->height;
+    size_t f;
     unsigned l;
     if (layer_count == 0 || layer_count > HAPGPU_COMPOSITE_MAX_LAYERS || width == 0 || height == 0 || (width & 3u) ||
-        (height & 3u) || row_bytes < (unsigned long)width * 4u || (row_bytes & 15u))
+        (height & 3u))
+        return 0;
+    /* (an encoded canvas has rows of exactly width * 4 bytes, and nobody's pitch to ask about) */
+    if (!c->encoded && (c->row_bytes < (unsigned long)width * 4u || (c->row_bytes & 15u)))
         return 0;
     for (l = 0; texture_counts && l < layer_count; l++)
         if (texture_counts[l] != 1u && texture_counts[l] != 2u)
             return 0;
+    if (c->encoded && !composite_destination_valid(c, frames))
+        return 0;
+    if (!c->layer_widths)
+        return 1;
+    if (!c->layer_heights || !hap_place_layer_valid(width, height))
+        return 0;
+    for (l = 0; l < layer_count; l++)
+        if (!hap_place_layer_valid(c->layer_widths[l], c->layer_heights[l]))
+            return 0;
+    for (f = 0; c->placements && f < frame_count; f++)
+        for (l = 0; l < layer_count; l++) {
+            const HapGpuPlacement *p = &c->placements[f * layer_count + l];
+            if (!hap_place_valid(p->srcX, p->srcY, p->width, p->height, p->dstX, p->dstY, c->layer_widths[l],
+                                 c->layer_heights[l]))
+                return 0;
+        }
     return 1;
 }
 
-/* the table of a composite launch for n pictures of layer_count layers: [n] picture addresses, then [n][layer_count]
-   descriptors; *device gets its device copy's address (filled by the caller's h2d of `bytes`) */
-static uint64_t *composite_table(hapgpu_rt *rt, unsigned n, unsigned layer_count, uint64_t **device, size_t *bytes)
+/* what a launch's table holds in front of the descriptors, n addresses each: the pictures, or the destination textures
+   and their planes; and a descriptor's size: a placed one where layers have sizes of their own */
+static unsigned composite_columns(const HapbComposite *c)
+{
+    return c->encoded ? 2u : 1u;
+}
+
+static size_t composite_stride(const HapbComposite *c)
+{
+    return c->layer_widths ? sizeof(HapGpuPlacedLayer) : sizeof(HapGpuCompositeLayer);
+}
+
+/* the table of a composite launch for n canvases: [columns][n] addresses, then [n][layer_count] descriptors of `stride`
+   bytes; *device gets its device copy's address (filled by the caller's h2d of `bytes`) */
+static uint64_t *composite_table(hapgpu_rt *rt, unsigned columns, unsigned n, unsigned layer_count, size_t stride,
+                                 uint64_t **device, size_t *bytes)
 {
     uint64_t *htab;
-    *bytes = sizeof(uint64_t) * n + sizeof(HapGpuCompositeLayer) * (size_t)n * layer_count;
+    *bytes = sizeof(uint64_t) * columns * n + stride * (size_t)n * layer_count;
     htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, *bytes);
     *device = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, *bytes);
     if (!htab || !*device)
         return NULL;
     memset(htab, 0, *bytes);
     return htab;
-}
-
-unsigned hapb_composite_textures(HapGpuContext *ctx, unsigned layer_count, const void *const *textures,
-                                 const unsigned long *texture_bytes, const unsigned *formats,
-                                 const void *const *alphas, const unsigned long *alpha_bytes,
-                                 const unsigned char *opacities, const unsigned char *background, unsigned width,
-                                 unsigned height, void *picture, unsigned long row_bytes)
-{
-    hapgpu_rt *rt = ctx->rt;
-    const size_t blocks = (size_t)(width / 4u) * (height / 4u), pixel_row = (size_t)width * 4u;
-    const picture_shape shape = {row_bytes, pixel_row, (size_t)row_bytes * (height ? height - 1u : 0u) + pixel_row, height};
-    size_t staged = 0, tab_bytes, at = 0;
-    uint64_t *htab, *dtab;
-    HapGpuCompositeLayer *hlayers;
-    uint8_t *stage = NULL, *picture_staged = NULL;
-    void *dst = picture;
-    unsigned l;
-    int rc;
-    if (!hapb_composite_valid(layer_count, width, height, row_bytes, NULL) || !textures || !texture_bytes || !formats ||
-        !picture)
-        return HapResult_Bad_Arguments;
-    if (context_busy(ctx, NULL, 0))
-        return HapResult_Internal_Error;
-    /* every layer: HapGpuDecompressRGBA's rules for its texture and its plane */
-    for (l = 0; l < layer_count; l++) {
-        const void *alpha = alphas ? alphas[l] : NULL;
-        const size_t need = composite_format(formats[l]) ? blocks * hapf_block_bytes(formats[l]) : 0u;
-        if (!textures[l] || !need || texture_bytes[l] < need || (alpha && (!alpha_bytes || alpha_bytes[l] < blocks * 8u)) ||
-            (is_dev(ctx, textures[l]) && ((uintptr_t)textures[l] & (hapf_block_bytes(formats[l]) - 1u))) ||
-            (alpha && is_dev(ctx, alpha) && ((uintptr_t)alpha & 7u)))
-            return HapResult_Bad_Arguments;
-        if (!is_dev(ctx, textures[l]))
-            staged += align_up(need, 256);
-        if (alpha && !is_dev(ctx, alpha))
-            staged += align_up(blocks * 8u, 256);
-    }
-    if (is_dev(ctx, picture) && ((uintptr_t)picture & 15u))
-        return HapResult_Bad_Arguments;
-    /* (one request for all that is staged: an arena that grows forgets what it held) */
-    if (staged && !(stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, staged)))
-        return HapResult_Internal_Error;
-    if (!is_dev(ctx, picture) && !(dst = picture_stage(rt, &picture_staged, shape.bytes, 1u, 0u)))
-        return HapResult_Internal_Error;
-    htab = composite_table(rt, 1u, layer_count, &dtab, &tab_bytes);
-    if (!htab)
-        return HapResult_Internal_Error;
-    hlayers = (HapGpuCompositeLayer *)(htab + 1);
-    htab[0] = (uint64_t)(uintptr_t)dst;
-    for (l = 0; l < layer_count; l++) {
-        const void *alpha = alphas ? alphas[l] : NULL, *src = textures[l];
-        if (!is_dev(ctx, src)) {
-            const size_t need = blocks * hapf_block_bytes(formats[l]);
-            if (hapgpu_rt_h2d(rt, stage + at, src, need))
-                return HapResult_Internal_Error;
-            src = stage + at;
-            at += align_up(need, 256);
-        }
-        if (alpha && !is_dev(ctx, alpha)) {
-            if (hapgpu_rt_h2d(rt, stage + at, alpha, blocks * 8u))
-                return HapResult_Internal_Error;
-            alpha = stage + at;
-            at += align_up(blocks * 8u, 256);
-        }
-        hlayers[l].texture = (uint64_t)(uintptr_t)src;
-        hlayers[l].alpha = (uint64_t)(uintptr_t)alpha;
-        hlayers[l].format = formats[l];
-        hlayers[l].opacity = opacities ? opacities[l] : 255u;
-    }
-    if (hapgpu_rt_h2d(rt, dtab, htab, tab_bytes))
-        return HapResult_Internal_Error;
-    rc = hapgpu_k_block_composite(rt, (const HapGpuCompositeLayer *)(dtab + 1), layer_count, dtab, 1u,
-                                  background ? background : k_composite_background, width, height, row_bytes);
-    if (rc == 1)
-        return HapResult_Bad_Arguments;
-    if (rc)
-        return HapResult_Internal_Error;
-    if (dst != picture && picture_unstage(rt, picture, dst, &shape))
-        return HapResult_Internal_Error;
-    if (hapgpu_rt_sync(rt))
-        return HapResult_Internal_Error;
-    return HapResult_No_Error;
-}
-
-unsigned hapb_composite_frames(HapGpuContext *ctx, unsigned frame_count, unsigned layer_count, const void *const *inputs,
-                               const unsigned long *input_bytes, const unsigned *texture_counts,
-                               const unsigned char *opacities, const unsigned char *background, void *const *rgba_frames,
-                               unsigned width, unsigned height, unsigned long row_bytes, unsigned *results, unsigned flags)
-{
-    hapgpu_rt *rt = ctx->rt;
-    const size_t pixel_row = (size_t)width * 4u;
-    const picture_shape shape = {row_bytes, pixel_row, (size_t)row_bytes * (height ? height - 1u : 0u) + pixel_row, height};
-    const size_t total = (size_t)frame_count * layer_count;
-    size_t done, i;
-    unsigned first_error = HapResult_No_Error, f, l;
-    slice_textures s;
-    if (!results)
-        return HapResult_Bad_Arguments;
-    if (!hapb_composite_valid(layer_count, width, height, row_bytes, texture_counts) || !inputs || !input_bytes ||
-        !rgba_frames) {
-        for (i = 0; i < total; i++)
-            results[i] = HapResult_Bad_Arguments;
-        return HapResult_Bad_Arguments;
-    }
-    if (frame_count == 0)
-        return HapResult_No_Error;
-    /* output frames of a slice: at most 4 GiB of block textures and 32768 entries of the second stage at a time */
-    if (context_busy(ctx, NULL, 0) || !slice_textures_init(&s, frame_count, layer_count, texture_counts, width, height, 0u, 0)) {
-        for (i = 0; i < total; i++)
-            results[i] = HapResult_Internal_Error;
-        return HapResult_Internal_Error;
-    }
-    for (done = 0; done < frame_count; done += s.at.slice) {
-        const unsigned n = (unsigned)(frame_count - done < s.at.slice ? frame_count - done : s.at.slice);
-        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, s.at.per_frame * n);
-        uint8_t *stage = NULL;
-        uint64_t *htab = NULL, *dtab = NULL;
-        HapGpuCompositeLayer *hlayers;
-        size_t tab_bytes = 0;
-        unsigned present = 0;
-        int rc = 0;
-        if (textures) {
-            /* the second stage of every layer of every output frame of the slice, one batch */
-            slice_textures_decode(ctx, &s, textures, inputs, input_bytes, done, n, NULL, flags);
-            /* (after the second stage, which has tables of its own) */
-            htab = composite_table(rt, n, layer_count, &dtab, &tab_bytes);
-        }
-        if (!htab) {
-            for (i = done * layer_count; i < (done + n) * layer_count; i++)
-                results[i] = HapResult_Internal_Error;
-            first_error = first_error ? first_error : HapResult_Internal_Error;
-            continue;
-        }
-        hlayers = (HapGpuCompositeLayer *)(htab + n);
-        for (f = 0; f < n; f++) {
-            unsigned *frame_results = results + (done + f) * layer_count;
-            void *dst = rgba_frames[done + f];
-            unsigned picture = HapResult_No_Error, all = HapResult_No_Error;
-            for (l = 0; l < layer_count; l++) {
-                const unsigned count = s.at.count_of[l];
-                const size_t e = (size_t)f * s.at.entries_per_frame + s.at.entry_of[l];
-                HapGpuCompositeLayer *d = &hlayers[(size_t)f * layer_count + l];
-                unsigned r = s.res[e];
-                if (r == HapResult_No_Error && count == 2u)
-                    r = s.res[e + 1];
-                /* the frame must hold what the caller's geometry says, in one of the three formats a layer may have */
-                if (r == HapResult_No_Error && !slice_entry_fits(&s, e, count, k_rgba_kinds, 3u))
-                    r = HapResult_Bad_Arguments;
-                frame_results[l] = r;
-                if (r != HapResult_No_Error && all == HapResult_No_Error)
-                    all = r;
-                d->texture = (uint64_t)(uintptr_t)s.outs[e];
-                d->alpha = count == 2u ? (uint64_t)(uintptr_t)s.outs[e + 1] : 0u;
-                d->format = s.fmts[e];
-                d->opacity = opacities ? opacities[(done + f) * layer_count + l] : 255u;
-            }
-            /* the picture: NULL or misaligned fails every layer's entry; host pictures are staged */
-            if (!dst || (is_dev(ctx, dst) && ((uintptr_t)dst & 15u))) {
-                picture = HapResult_Bad_Arguments;
-            } else if (all == HapResult_No_Error && !is_dev(ctx, dst)) {
-                dst = picture_stage(rt, &stage, align_up(shape.bytes, 256), n, f);
-                if (!dst)
-                    picture = HapResult_Internal_Error;
-            }
-            if (picture != HapResult_No_Error)
-                for (l = 0; l < layer_count; l++)
-                    frame_results[l] = picture;
-            /* (an output frame that is not written: picture address 0 skips it) */
-            if (picture == HapResult_No_Error && all == HapResult_No_Error) {
-                htab[f] = (uint64_t)(uintptr_t)dst;
-                present = 1;
-            }
-        }
-        if (present) {
-            rc |= hapgpu_rt_h2d(rt, dtab, htab, tab_bytes);
-            rc |= hapgpu_k_block_composite(rt, (const HapGpuCompositeLayer *)(dtab + n), layer_count, dtab, n,
-                                           background ? background : k_composite_background, width, height, row_bytes);
-            for (f = 0; f < n; f++)
-                if (htab[f] && !is_dev(ctx, rgba_frames[done + f]))
-                    rc |= picture_unstage(rt, rgba_frames[done + f], stage + align_up(shape.bytes, 256) * f, &shape);
-        }
-        rc |= hapgpu_rt_sync(rt);
-        for (i = done * layer_count; i < (done + n) * layer_count; i++) {
-            if (rc && results[i] == HapResult_No_Error && htab[i / layer_count - done])
-                results[i] = HapResult_Internal_Error;
-            if (results[i] != HapResult_No_Error && first_error == HapResult_No_Error)
-                first_error = results[i];
-        }
-    }
-    free(s.in);
-    return first_error;
-}
-
-/* ------------------------------------------------------------- ... of layers placed on the canvas */
-/* The two calls above for layers of sizes of their own, each with a rectangle of it placed and clipped on the canvas
-   (hap_place.h: the rules and the clip; bc_composite.hip's placed kernel).  A descriptor carries its layer's clip in
-   blocks; the second stage still decodes every layer's whole frame, into a scratch laid out by hap_place_layout_of. */
-
-int hapb_composite_placed_valid(unsigned layer_count, const unsigned *layer_widths, const unsigned *layer_heights,
-                                const HapGpuPlacement *placements, size_t frame_count, unsigned width, unsigned height,
-                                unsigned long row_bytes, const unsigned *texture_counts)
-{
-    size_t f;
-    unsigned l;
-    if (!hapb_composite_valid(layer_count, width, height, row_bytes, texture_counts) || !layer_widths || !layer_heights ||
-        !hap_place_layer_valid(width, height))
-        return 0;
-    for (l = 0; l < layer_count; l++)
-        if (!hap_place_layer_valid(layer_widths[l], layer_heights[l]))
-            return 0;
-    for (f = 0; placements && f < frame_count; f++)
-        for (l = 0; l < layer_count; l++) {
-            const HapGpuPlacement *p = &placements[f * layer_count + l];
-            if (!hap_place_valid(p->srcX, p->srcY, p->width, p->height, p->dstX, p->dstY, layer_widths[l], layer_heights[l]))
-                return 0;
-        }
-    return 1;
 }
 
 /* a descriptor's six clip words: placement p (NULL: the layer whole at (0, 0)) of a layer_w x layer_h layer on the canvas */
@@ -960,46 +854,63 @@ static void placed_layer_clip(HapGpuPlacedLayer *d, const HapGpuPlacement *p, un
     d->layer_blocks_x = c.layer_blocks_x;
 }
 
-/* composite_table's for placed layers */
-static uint64_t *composite_placed_table(hapgpu_rt *rt, unsigned n, unsigned layer_count, uint64_t **device, size_t *bytes)
+/* Descriptor `slot` of a host table (htab) for n canvases: layer l of the call's output frame f, its texture and plane
+   (NULL: none) in device memory.  A placed descriptor begins with a plain one's four members, and has its clip where the
+   layers have sizes. */
+static void composite_descriptor(const HapbComposite *c, uint64_t *htab, unsigned n, size_t slot, size_t f, unsigned l,
+                                 const void *texture, const void *alpha, unsigned format)
 {
-    uint64_t *htab;
-    *bytes = sizeof(uint64_t) * n + sizeof(HapGpuPlacedLayer) * (size_t)n * layer_count;
-    htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, *bytes);
-    *device = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, *bytes);
-    if (!htab || !*device)
-        return NULL;
-    memset(htab, 0, *bytes);
-    return htab;
+    void *const at = (uint8_t *)(htab + (size_t)composite_columns(c) * n) + composite_stride(c) * slot;
+    HapGpuCompositeLayer *const d = (HapGpuCompositeLayer *)at;
+    const size_t entry = f * c->layer_count + l;
+    d->texture = (uint64_t)(uintptr_t)texture;
+    d->alpha = (uint64_t)(uintptr_t)alpha;
+    d->format = format;
+    d->opacity = c->opacities ? c->opacities[entry] : 255u;
+    if (c->layer_widths)
+        placed_layer_clip((HapGpuPlacedLayer *)at, c->placements ? &c->placements[entry] : NULL, c->layer_widths[l],
+                          c->layer_heights[l], c->width, c->height);
 }
 
-unsigned hapb_composite_textures_placed(HapGpuContext *ctx, unsigned layer_count, const void *const *textures,
+/* the composite launch of a description for the n canvases of a device table: layers of the canvas's size keep the
+   kernel and the 24-byte descriptors they have had from the start */
+static int launch_composite(hapgpu_rt *rt, const HapbComposite *c, const uint64_t *dtab, unsigned n)
+{
+    const unsigned char *const background = c->background ? c->background : k_composite_background;
+    const void *const layers = dtab + (size_t)composite_columns(c) * n;
+    if (c->encoded)
+        return hapgpu_k_block_composite_encode(rt, (const HapGpuPlacedLayer *)layers, c->layer_count, dtab, dtab + n, n,
+                                               background, c->width, c->height, c->formats[0], c->count == 2);
+    if (c->layer_widths)
+        return hapgpu_k_block_composite_placed(rt, (const HapGpuPlacedLayer *)layers, c->layer_count, dtab, n, background,
+                                               c->width, c->height, c->row_bytes);
+    return hapgpu_k_block_composite(rt, (const HapGpuCompositeLayer *)layers, c->layer_count, dtab, n, background, c->width,
+                                    c->height, c->row_bytes);
+}
+
+/* the blocks of layer l's textures */
+static size_t composite_layer_blocks(const HapbComposite *c, unsigned l)
+{
+    return c->layer_widths ? (size_t)(c->layer_widths[l] / 4u) * (c->layer_heights[l] / 4u)
+                           : (size_t)(c->width / 4u) * (c->height / 4u);
+}
+
+/* The layers of the textures form.  Every layer: HapGpuDecompressRGBA's rules for its texture and its plane, at the
+   layer's own size.  Then what lies in host memory is staged into D_BC_TEX: src[l] and asrc[l] get layer l's texture and
+   plane (NULL: none) in device memory.  refused_otherwise: what the caller has against its destination, No_Error if
+   nothing -- the call's answer once the layers are in order.  Returns a HapResult. */
+static unsigned composite_layers_staged(HapGpuContext *ctx, const HapbComposite *c, const void *const *textures,
                                         const unsigned long *texture_bytes, const unsigned *formats,
                                         const void *const *alphas, const unsigned long *alpha_bytes,
-                                        const unsigned *layer_widths, const unsigned *layer_heights,
-                                        const HapGpuPlacement *placements, const unsigned char *opacities,
-                                        const unsigned char *background, unsigned width, unsigned height, void *picture,
-                                        unsigned long row_bytes)
+                                        unsigned refused_otherwise, const void **src, const void **asrc)
 {
     hapgpu_rt *rt = ctx->rt;
-    const size_t pixel_row = (size_t)width * 4u;
-    const picture_shape shape = {row_bytes, pixel_row, (size_t)row_bytes * (height ? height - 1u : 0u) + pixel_row, height};
-    size_t staged = 0, tab_bytes, at = 0;
-    uint64_t *htab, *dtab;
-    HapGpuPlacedLayer *hlayers;
-    uint8_t *stage = NULL, *picture_staged = NULL;
-    void *dst = picture;
+    size_t staged = 0, at = 0;
+    uint8_t *stage = NULL;
     unsigned l;
-    int rc;
-    if (!hapb_composite_placed_valid(layer_count, layer_widths, layer_heights, placements, 1u, width, height, row_bytes, NULL) ||
-        !textures || !texture_bytes || !formats || !picture)
-        return HapResult_Bad_Arguments;
-    if (context_busy(ctx, NULL, 0))
-        return HapResult_Internal_Error;
-    /* every layer: HapGpuDecompressRGBA's rules for its texture and its plane, at the layer's own size */
-    for (l = 0; l < layer_count; l++) {
+    for (l = 0; l < c->layer_count; l++) {
         const void *alpha = alphas ? alphas[l] : NULL;
-        const size_t blocks = (size_t)(layer_widths[l] / 4u) * (layer_heights[l] / 4u);
+        const size_t blocks = composite_layer_blocks(c, l);
         const size_t need = composite_format(formats[l]) ? blocks * hapf_block_bytes(formats[l]) : 0u;
         if (!textures[l] || !need || texture_bytes[l] < need || (alpha && (!alpha_bytes || alpha_bytes[l] < blocks * 8u)) ||
             (is_dev(ctx, textures[l]) && ((uintptr_t)textures[l] & (hapf_block_bytes(formats[l]) - 1u))) ||
@@ -1010,171 +921,261 @@ unsigned hapb_composite_textures_placed(HapGpuContext *ctx, unsigned layer_count
         if (alpha && !is_dev(ctx, alpha))
             staged += align_up(blocks * 8u, 256);
     }
-    if (is_dev(ctx, picture) && ((uintptr_t)picture & 15u))
-        return HapResult_Bad_Arguments;
+    /* (what the caller refuses of its destination comes behind the layers' refusals and before any copy) */
+    if (refused_otherwise != HapResult_No_Error)
+        return refused_otherwise;
     /* (one request for all that is staged: an arena that grows forgets what it held) */
     if (staged && !(stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, staged)))
         return HapResult_Internal_Error;
-    if (!is_dev(ctx, picture) && !(dst = picture_stage(rt, &picture_staged, shape.bytes, 1u, 0u)))
-        return HapResult_Internal_Error;
-    htab = composite_placed_table(rt, 1u, layer_count, &dtab, &tab_bytes);
-    if (!htab)
-        return HapResult_Internal_Error;
-    hlayers = (HapGpuPlacedLayer *)(htab + 1);
-    htab[0] = (uint64_t)(uintptr_t)dst;
-    for (l = 0; l < layer_count; l++) {
-        const void *alpha = alphas ? alphas[l] : NULL, *src = textures[l];
-        const size_t blocks = (size_t)(layer_widths[l] / 4u) * (layer_heights[l] / 4u);
-        if (!is_dev(ctx, src)) {
+    for (l = 0; l < c->layer_count; l++) {
+        const size_t blocks = composite_layer_blocks(c, l);
+        src[l] = textures[l];
+        asrc[l] = alphas ? alphas[l] : NULL;
+        if (!is_dev(ctx, src[l])) {
             const size_t need = blocks * hapf_block_bytes(formats[l]);
-            if (hapgpu_rt_h2d(rt, stage + at, src, need))
+            if (hapgpu_rt_h2d(rt, stage + at, src[l], need))
                 return HapResult_Internal_Error;
-            src = stage + at;
+            src[l] = stage + at;
             at += align_up(need, 256);
         }
-        if (alpha && !is_dev(ctx, alpha)) {
-            if (hapgpu_rt_h2d(rt, stage + at, alpha, blocks * 8u))
+        if (asrc[l] && !is_dev(ctx, asrc[l])) {
+            if (hapgpu_rt_h2d(rt, stage + at, asrc[l], blocks * 8u))
                 return HapResult_Internal_Error;
-            alpha = stage + at;
+            asrc[l] = stage + at;
             at += align_up(blocks * 8u, 256);
         }
-        hlayers[l].texture = (uint64_t)(uintptr_t)src;
-        hlayers[l].alpha = (uint64_t)(uintptr_t)alpha;
-        hlayers[l].format = formats[l];
-        hlayers[l].opacity = opacities ? opacities[l] : 255u;
-        placed_layer_clip(&hlayers[l], placements ? &placements[l] : NULL, layer_widths[l], layer_heights[l], width, height);
     }
-    if (hapgpu_rt_h2d(rt, dtab, htab, tab_bytes))
-        return HapResult_Internal_Error;
-    rc = hapgpu_k_block_composite_placed(rt, (const HapGpuPlacedLayer *)(dtab + 1), layer_count, dtab, 1u,
-                                         background ? background : k_composite_background, width, height, row_bytes);
-    if (rc == 1)
-        return HapResult_Bad_Arguments;
-    if (rc)
-        return HapResult_Internal_Error;
-    if (dst != picture && picture_unstage(rt, picture, dst, &shape))
-        return HapResult_Internal_Error;
-    if (hapgpu_rt_sync(rt))
-        return HapResult_Internal_Error;
     return HapResult_No_Error;
 }
 
-unsigned hapb_composite_frames_placed(HapGpuContext *ctx, unsigned frame_count, unsigned layer_count,
-                                      const void *const *inputs, const unsigned long *input_bytes,
-                                      const unsigned *texture_counts, const unsigned *layer_widths,
-                                      const unsigned *layer_heights, const HapGpuPlacement *placements,
-                                      const unsigned char *opacities, const unsigned char *background,
-                                      void *const *rgba_frames, unsigned width, unsigned height, unsigned long row_bytes,
-                                      unsigned *results, unsigned flags)
+unsigned hapb_composite_textures(HapGpuContext *ctx, const HapbComposite *c, const void *const *textures,
+                                 const unsigned long *texture_bytes, const unsigned *formats,
+                                 const void *const *alphas, const unsigned long *alpha_bytes, void *const *outputs,
+                                 const unsigned long *output_bytes, unsigned long *output_used)
 {
     hapgpu_rt *rt = ctx->rt;
-    const size_t pixel_row = (size_t)width * 4u;
-    const picture_shape shape = {row_bytes, pixel_row, (size_t)row_bytes * (height ? height - 1u : 0u) + pixel_row, height};
+    const size_t pixel_row = (size_t)c->width * 4u;
+    const picture_shape shape = {c->row_bytes, pixel_row, (size_t)c->row_bytes * (c->height ? c->height - 1u : 0u) + pixel_row,
+                                 c->height};
+    const unsigned count = c->encoded ? c->count : 1u;
+    const void *src[HAPGPU_COMPOSITE_MAX_LAYERS], *asrc[HAPGPU_COMPOSITE_MAX_LAYERS];
+    destination_layout out = {{0, 0}, {0, 0}, 0};
+    size_t tab_bytes;
+    uint64_t *htab, *dtab;
+    uint8_t *stage = NULL;              /* (of the destinations that lie in host memory) */
+    unsigned refused = HapResult_No_Error, l, i, r;
+    int rc, any_host_output = 0;
+    if (!hapb_composite_valid(c, 1u, NULL, 0) || !textures || !texture_bytes || !formats || !outputs ||
+        (c->encoded ? !output_bytes : !outputs[0]))
+        return HapResult_Bad_Arguments;
+    if (context_busy(ctx, NULL, 0))
+        return HapResult_Internal_Error;
+    /* every output: HapGpuTranscodeTexture's rules; a picture in device memory: 16-byte aligned */
+    if (c->encoded) {
+        destination_layout_of(&out, count, c->formats, c->width, c->height);
+        refused = destination_textures_fit(ctx, &out, count, c->formats, outputs, output_bytes);
+    } else if (is_dev(ctx, outputs[0]) && ((uintptr_t)outputs[0] & 15u)) {
+        refused = HapResult_Bad_Arguments;
+    }
+    r = composite_layers_staged(ctx, c, textures, texture_bytes, formats, alphas, alpha_bytes, refused, src, asrc);
+    if (r != HapResult_No_Error)
+        return r;
+    for (i = 0; i < count; i++)
+        if (!is_dev(ctx, outputs[i]))
+            any_host_output = 1;
+    /* (a destination in host memory is made in scratch and copied back) */
+    if (any_host_output) {
+        if (c->encoded)
+            stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_TRANSCODED, out.total);
+        else
+            (void)picture_stage(rt, &stage, shape.bytes, 1u, 0u);
+        if (!stage)
+            return HapResult_Internal_Error;
+    }
+    htab = composite_table(rt, composite_columns(c), 1u, c->layer_count, composite_stride(c), &dtab, &tab_bytes);
+    if (!htab)
+        return HapResult_Internal_Error;
+    for (i = 0; i < count; i++)
+        htab[i] = (uint64_t)(uintptr_t)(is_dev(ctx, outputs[i]) ? (uint8_t *)outputs[i] : c->encoded ? stage + out.off[i] : stage);
+    for (l = 0; l < c->layer_count; l++)
+        composite_descriptor(c, htab, 1u, l, 0u, l, src[l], asrc[l], formats[l]);
+    if (hapgpu_rt_h2d(rt, dtab, htab, tab_bytes))
+        return HapResult_Internal_Error;
+    rc = launch_composite(rt, c, dtab, 1u);
+    if (rc == 1)
+        return HapResult_Bad_Arguments;
+    for (i = 0; !rc && i < count; i++)
+        if (!is_dev(ctx, outputs[i]))
+            rc |= c->encoded ? hapgpu_rt_d2h(rt, outputs[i], stage + out.off[i], out.bytes[i])
+                             : picture_unstage(rt, outputs[0], stage, &shape);
+    if (rc || hapgpu_rt_sync(rt))
+        return HapResult_Internal_Error;
+    for (i = 0; c->encoded && output_used && i < count; i++)
+        output_used[i] = out.bytes[i];
+    return HapResult_No_Error;
+}
+
+/* every entry of the result arrays a refusal sets (results: NULL for a call to pictures) */
+static void composite_refuse(unsigned *layer_results, size_t layer_entries, unsigned *results, size_t frame_count,
+                             unsigned code)
+{
+    size_t i;
+    for (i = 0; i < layer_entries; i++)
+        layer_results[i] = code;
+    for (i = 0; results && i < frame_count; i++)
+        results[i] = code;
+}
+
+unsigned hapb_composite_frames(HapGpuContext *ctx, const HapbComposite *c, unsigned frame_count,
+                               const void *const *inputs, const unsigned long *input_bytes,
+                               const unsigned *texture_counts, void *const *outputs, const unsigned long *output_bytes,
+                               unsigned long *output_used, unsigned *layer_results, unsigned *results,
+                               unsigned decode_flags)
+{
+    hapgpu_rt *rt = ctx->rt;
+    const unsigned layer_count = c->layer_count, count = c->count;
+    const size_t pixel_row = (size_t)c->width * 4u;
+    const picture_shape shape = {c->row_bytes, pixel_row, (size_t)c->row_bytes * (c->height ? c->height - 1u : 0u) + pixel_row,
+                                 c->height};
     const size_t total = (size_t)frame_count * layer_count;
+    destination_layout out = {{0, 0}, {0, 0}, 0};
+    unsigned canvas_widths[HAPGPU_COMPOSITE_MAX_LAYERS], canvas_heights[HAPGPU_COMPOSITE_MAX_LAYERS];
     size_t done, i;
     unsigned first_error = HapResult_No_Error, f, l;
-    hap_place_layout layout;
     slice_textures s;
-    if (!results)
+    const void **tex = NULL;    /* (encoded) per output frame and destination texture: what the encode half reads */
+    unsigned *composited = NULL;    /* ... and per output frame: what its layers came to */
+    if (!layer_results || (c->encoded && !results))
         return HapResult_Bad_Arguments;
-    if (!hapb_composite_placed_valid(layer_count, layer_widths, layer_heights, placements, frame_count, width, height,
-                                     row_bytes, texture_counts) || !inputs || !input_bytes || !rgba_frames) {
-        for (i = 0; i < total; i++)
-            results[i] = HapResult_Bad_Arguments;
+    if (!hapb_composite_valid(c, frame_count, texture_counts, 1) || !inputs || !input_bytes || !outputs ||
+        (c->encoded && (!output_bytes || !output_used))) {
+        composite_refuse(layer_results, total, results, frame_count, HapResult_Bad_Arguments);
         return HapResult_Bad_Arguments;
     }
     if (frame_count == 0)
         return HapResult_No_Error;
-    /* output frames of a slice: at most 4 GiB of block textures and 32768 entries of the second stage at a time */
-    hap_place_layout_of(&layout, layer_count, texture_counts, layer_widths, layer_heights, 0u, frame_count);
-    if (context_busy(ctx, NULL, 0) || !slice_textures_init_placed(&s, &layout)) {
-        for (i = 0; i < total; i++)
-            results[i] = HapResult_Internal_Error;
+    if (c->encoded)
+        destination_layout_of(&out, count, c->formats, c->width, c->height);
+    for (l = 0; l < layer_count; l++) {
+        canvas_widths[l] = c->width;
+        canvas_heights[l] = c->height;
+    }
+    /* output frames of a slice: at most 4 GiB of block textures, an encoded canvas's among them, and 32768 entries of the
+       second stage at a time */
+    if (context_busy(ctx, NULL, 0) ||
+        !slice_textures_init(&s, frame_count, layer_count, texture_counts, c->layer_widths ? c->layer_widths : canvas_widths,
+                             c->layer_widths ? c->layer_heights : canvas_heights, out.total, 0)) {
+        composite_refuse(layer_results, total, results, frame_count, HapResult_Internal_Error);
         return HapResult_Internal_Error;
     }
-    for (done = 0; done < frame_count; done += s.at.slice) {
-        const unsigned n = (unsigned)(frame_count - done < s.at.slice ? frame_count - done : s.at.slice);
-        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, s.at.per_frame * n);
+    if (c->encoded) {
+        tex = (const void **)malloc((sizeof(*tex) * count + sizeof(*composited)) * s.layout.at.slice);
+        if (!tex) {
+            free(s.in);
+            composite_refuse(layer_results, total, results, frame_count, HapResult_Internal_Error);
+            return HapResult_Internal_Error;
+        }
+        composited = (unsigned *)(tex + s.layout.at.slice * count);
+    }
+    for (done = 0; done < frame_count; done += s.layout.at.slice) {
+        const hap_slice_layout *const at = &s.layout.at;
+        const unsigned n = (unsigned)(frame_count - done < at->slice ? frame_count - done : at->slice);
+        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, at->per_frame * n);
+        uint8_t *encoded = c->encoded ? (uint8_t *)hapgpu_rt_device_scratch(rt, D_TRANSCODED, out.total * n) : NULL;
         uint8_t *stage = NULL;
         uint64_t *htab = NULL, *dtab = NULL;
-        HapGpuPlacedLayer *hlayers;
         size_t tab_bytes = 0;
         unsigned present = 0;
         int rc = 0;
-        if (textures) {
+        if (textures && (encoded || !c->encoded)) {
             /* the second stage of every layer of every output frame of the slice, one batch: whole frames */
-            slice_textures_decode(ctx, &s, textures, inputs, input_bytes, done, n, NULL, flags);
+            slice_textures_decode(ctx, &s, textures, inputs, input_bytes, done, n, NULL, decode_flags);
             /* (after the second stage, which has tables of its own) */
-            htab = composite_placed_table(rt, n, layer_count, &dtab, &tab_bytes);
+            htab = composite_table(rt, composite_columns(c), n, layer_count, composite_stride(c), &dtab, &tab_bytes);
         }
         if (!htab) {
-            for (i = done * layer_count; i < (done + n) * layer_count; i++)
-                results[i] = HapResult_Internal_Error;
+            composite_refuse(layer_results + done * layer_count, (size_t)n * layer_count, results ? results + done : NULL, n,
+                             HapResult_Internal_Error);
+            for (f = 0; c->encoded && f < n; f++)
+                output_used[done + f] = 0;
             first_error = first_error ? first_error : HapResult_Internal_Error;
             continue;
         }
-        hlayers = (HapGpuPlacedLayer *)(htab + n);
         for (f = 0; f < n; f++) {
-            unsigned *frame_results = results + (done + f) * layer_count;
-            void *dst = rgba_frames[done + f];
-            unsigned picture = HapResult_No_Error, all = HapResult_No_Error;
+            unsigned *frame_results = layer_results + (done + f) * layer_count;
+            unsigned all = HapResult_No_Error;
             for (l = 0; l < layer_count; l++) {
-                const unsigned count = s.at.count_of[l];
-                const size_t e = (size_t)f * s.at.entries_per_frame + s.at.entry_of[l];
-                HapGpuPlacedLayer *d = &hlayers[(size_t)f * layer_count + l];
+                const size_t e = (size_t)f * at->entries_per_frame + at->entry_of[l];
                 unsigned r = s.res[e];
-                if (r == HapResult_No_Error && count == 2u)
+                if (r == HapResult_No_Error && at->count_of[l] == 2u)
                     r = s.res[e + 1];
-                /* the frame must hold exactly its layer's geometry, in one of the three formats a layer may have: a
-                   texture with more blocks than the layer's room holds is of another size like one with fewer */
-                if (r == HapResult_Buffer_Too_Small ||
-                    (r == HapResult_No_Error && !slice_entry_fits_member(&s, e, l, k_rgba_kinds, 3u)))
+                /* the frame must hold exactly its layer's geometry, in one of the three formats a layer may have.  Where
+                   layers have sizes of their own, a texture with more blocks than the layer's room holds is of another
+                   size like one with fewer; a layer of the canvas's size keeps the second stage's code for that */
+                if ((r == HapResult_Buffer_Too_Small && c->layer_widths) ||
+                    (r == HapResult_No_Error && !slice_entry_fits(&s, e, l, k_rgba_kinds, 3u)))
                     r = HapResult_Bad_Arguments;
                 frame_results[l] = r;
                 if (r != HapResult_No_Error && all == HapResult_No_Error)
                     all = r;
-                d->texture = (uint64_t)(uintptr_t)s.outs[e];
-                d->alpha = count == 2u ? (uint64_t)(uintptr_t)s.outs[e + 1] : 0u;
-                d->format = s.fmts[e];
-                d->opacity = opacities ? opacities[(done + f) * layer_count + l] : 255u;
-                placed_layer_clip(d, placements ? &placements[(done + f) * layer_count + l] : NULL, layer_widths[l],
-                                  layer_heights[l], width, height);
+                composite_descriptor(c, htab, n, (size_t)f * layer_count + l, done + f, l, s.outs[e],
+                                     at->count_of[l] == 2u ? s.outs[e + 1] : NULL, s.fmts[e]);
             }
-            /* the picture: NULL or misaligned fails every layer's entry; host pictures are staged */
-            if (!dst || (is_dev(ctx, dst) && ((uintptr_t)dst & 15u))) {
-                picture = HapResult_Bad_Arguments;
-            } else if (all == HapResult_No_Error && !is_dev(ctx, dst)) {
-                dst = picture_stage(rt, &stage, align_up(shape.bytes, 256), n, f);
-                if (!dst)
-                    picture = HapResult_Internal_Error;
-            }
-            if (picture != HapResult_No_Error)
-                for (l = 0; l < layer_count; l++)
-                    frame_results[l] = picture;
-            /* (an output frame that is not written: picture address 0 skips it) */
-            if (picture == HapResult_No_Error && all == HapResult_No_Error) {
-                htab[f] = (uint64_t)(uintptr_t)dst;
-                present = 1;
+            if (c->encoded) {
+                composited[f] = all;
+                /* (an output frame with a failed layer has NULL textures: hapb_encode leaves it out) */
+                for (i = 0; i < count; i++)
+                    tex[(size_t)f * count + i] = all != HapResult_No_Error ? NULL :
+                                                 (const void *)(encoded + out.total * f + out.off[i]);
+                /* (a frame whose output hapb_encode will refuse is not worth the kernel's time either: address 0 skips it) */
+                if (all == HapResult_No_Error && outputs[done + f] && output_bytes[done + f]) {
+                    htab[f] = (uint64_t)(uintptr_t)tex[(size_t)f * count];
+                    htab[n + f] = count == 2 ? (uint64_t)(uintptr_t)tex[(size_t)f * count + 1] : 0u;
+                    present = 1;
+                }
+            } else {
+                void *dst = outputs[done + f];
+                unsigned picture = HapResult_No_Error;
+                /* the picture: NULL or misaligned fails every layer's entry; host pictures are staged */
+                if (!dst || (is_dev(ctx, dst) && ((uintptr_t)dst & 15u))) {
+                    picture = HapResult_Bad_Arguments;
+                } else if (all == HapResult_No_Error && !is_dev(ctx, dst)) {
+                    dst = picture_stage(rt, &stage, align_up(shape.bytes, 256), n, f);
+                    if (!dst)
+                        picture = HapResult_Internal_Error;
+                }
+                if (picture != HapResult_No_Error)
+                    for (l = 0; l < layer_count; l++)
+                        frame_results[l] = picture;
+                /* (an output frame that is not written: picture address 0 skips it) */
+                if (picture == HapResult_No_Error && all == HapResult_No_Error) {
+                    htab[f] = (uint64_t)(uintptr_t)dst;
+                    present = 1;
+                }
             }
         }
         if (present) {
             rc |= hapgpu_rt_h2d(rt, dtab, htab, tab_bytes);
-            rc |= hapgpu_k_block_composite_placed(rt, (const HapGpuPlacedLayer *)(dtab + n), layer_count, dtab, n,
-                                                  background ? background : k_composite_background, width, height,
-                                                  row_bytes);
-            for (f = 0; f < n; f++)
-                if (htab[f] && !is_dev(ctx, rgba_frames[done + f]))
-                    rc |= picture_unstage(rt, rgba_frames[done + f], stage + align_up(shape.bytes, 256) * f, &shape);
+            rc |= launch_composite(rt, c, dtab, n);
+            for (f = 0; !c->encoded && f < n; f++)
+                if (htab[f] && !is_dev(ctx, outputs[done + f]))
+                    rc |= picture_unstage(rt, outputs[done + f], stage + align_up(shape.bytes, 256) * f, &shape);
+        }
+        if (c->encoded) {
+            slice_encode_half(ctx, n, tex, composited, rc, 1, &out, count, c->formats, c->compressors, c->chunk_counts,
+                              c->encode_flags, outputs + done, output_bytes + done, output_used + done, results + done,
+                              &first_error);
+            continue;
         }
         rc |= hapgpu_rt_sync(rt);
         for (i = done * layer_count; i < (done + n) * layer_count; i++) {
-            if (rc && results[i] == HapResult_No_Error && htab[i / layer_count - done])
-                results[i] = HapResult_Internal_Error;
-            if (results[i] != HapResult_No_Error && first_error == HapResult_No_Error)
-                first_error = results[i];
+            if (rc && layer_results[i] == HapResult_No_Error && htab[i / layer_count - done])
+                layer_results[i] = HapResult_Internal_Error;
+            if (layer_results[i] != HapResult_No_Error && first_error == HapResult_No_Error)
+                first_error = layer_results[i];
         }
     }
-    free(s.in);
+    free(s.in); free(tex);
     return first_error;
 }
 
@@ -1182,15 +1183,6 @@ unsigned hapb_composite_frames_placed(HapGpuContext *ctx, unsigned frame_count, 
 /* Frames -> frames of other texture formats or of half / quarter size: hapb_decode into D_BC_TEX as in hapb_road_frames,
    the transcode kernel from there into D_TRANSCODED (one launch per source format present in the slice), hapb_encode on
    those textures -- or, for a frame that holds the wanted formats already, on its own.  No picture anywhere. */
-
-/* the destination sets the kernel makes: 1 DXT1, 2 DXT5, 3 YCoCg-DXT5, 4 YCoCg-DXT5 + RGTC1 (Hap Q Alpha); 0: none of them */
-static unsigned transcode_set(unsigned count, const unsigned *formats)
-{
-    if (count == 1u)
-        return formats[0] == HapTextureFormat_RGB_DXT1 ? 1u : formats[0] == HapTextureFormat_RGBA_DXT5 ? 2u :
-               formats[0] == HapTextureFormat_YCoCg_DXT5 ? 3u : 0u;
-    return count == 2u && formats[0] == HapTextureFormat_YCoCg_DXT5 && formats[1] == HapTextureFormat_A_RGTC1 ? 4u : 0u;
-}
 
 static void transcode_refuse(unsigned *results, unsigned frame_count, unsigned code)
 {
@@ -1210,9 +1202,8 @@ unsigned hapb_transcode(HapGpuContext *ctx, unsigned frame_count, const void *co
     const HapbRoad road = {.picture_kind = HAPGPU_PICTURE_RGBA8};
     const unsigned *kinds;
     const unsigned kind_count = road_formats(&road, &kinds, NULL);
-    const HapbEncodeArgs device_textures = {1, NULL, 0, 0};
-    size_t out_per_frame = 0, out_off[2] = {0, 0}, done;
-    unsigned long out_bytes[2] = {0, 0};
+    destination_layout out;
+    size_t done;
     unsigned first_error = HapResult_No_Error, f, i, set;
     slice_textures s;
     const void **tex;       /* per frame and destination texture: what the encode half reads */
@@ -1235,32 +1226,27 @@ unsigned hapb_transcode(HapGpuContext *ctx, unsigned frame_count, const void *co
         transcode_refuse(results, frame_count, HapResult_Bad_Arguments);
         return HapResult_Bad_Arguments;
     }
-    for (i = 0; i < count; i++) {
-        out_bytes[i] = (unsigned long)((size_t)((width >> scale_log2) / 4u) * ((height >> scale_log2) / 4u) * hapf_block_bytes(formats[i]));
-        out_off[i] = out_per_frame;
-        out_per_frame += align_up(out_bytes[i], 256);
-    }
-    /* (the destination blocks are the default encode's: no BC7, no refined end points) */
-    encode_flags &= ~(HAPGPU_ENCODE_BPTC_BLOCKS | HAPGPU_ENCODE_REFINE_ENDPOINTS);
-    if (encode_textures_valid(count, out_bytes, formats, compressors, chunk_counts, encode_flags) != HapResult_No_Error) {
+    destination_layout_of(&out, count, formats, width >> scale_log2, height >> scale_log2);
+    if (encode_textures_valid(count, out.bytes, formats, compressors, chunk_counts,
+                              DESTINATION_ENCODE_FLAGS(encode_flags)) != HapResult_No_Error) {
         transcode_refuse(results, frame_count, HapResult_Bad_Arguments);
         return HapResult_Bad_Arguments;
     }
-    if (!slice_textures_init(&s, frame_count, 1u, &texture_count, width, height, out_per_frame, 0)) {
+    if (!slice_textures_init(&s, frame_count, 1u, &texture_count, &width, &height, out.total, 0)) {
         transcode_refuse(results, frame_count, HapResult_Internal_Error);
         return HapResult_Internal_Error;
     }
-    tex = (const void **)malloc((sizeof(*tex) * count + sizeof(*decoded)) * s.at.slice);
+    tex = (const void **)malloc((sizeof(*tex) * count + sizeof(*decoded)) * s.layout.at.slice);
     if (!tex) {
         free(s.in);
         transcode_refuse(results, frame_count, HapResult_Internal_Error);
         return HapResult_Internal_Error;
     }
-    decoded = (unsigned *)(tex + s.at.slice * count);
-    for (done = 0; done < frame_count; done += s.at.slice) {
-        const unsigned n = (unsigned)(frame_count - done < s.at.slice ? frame_count - done : s.at.slice);
-        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, s.at.per_frame * n);
-        uint8_t *transcoded = set ? (uint8_t *)hapgpu_rt_device_scratch(rt, D_TRANSCODED, out_per_frame * n) : NULL;
+    decoded = (unsigned *)(tex + s.layout.at.slice * count);
+    for (done = 0; done < frame_count; done += s.layout.at.slice) {
+        const unsigned n = (unsigned)(frame_count - done < s.layout.at.slice ? frame_count - done : s.layout.at.slice);
+        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, s.layout.at.per_frame * n);
+        uint8_t *transcoded = set ? (uint8_t *)hapgpu_rt_device_scratch(rt, D_TRANSCODED, out.total * n) : NULL;
         /* [source textures][source planes][destination textures][destination planes] per source format */
         const size_t tab_bytes = sizeof(uint64_t) * 4u * PICTURE_KINDS_MAX * n;
         uint64_t *htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, tab_bytes);
@@ -1285,17 +1271,17 @@ unsigned hapb_transcode(HapGpuContext *ctx, unsigned frame_count, const void *co
                 /* the frame's own formats are the wanted ones, at its own size: its textures go on as they are */
                 pass = scale_log2 == 0u && texture_count == count;
                 for (i = 0; pass && i < count; i++)
-                    if (s.fmts[e + i] != formats[i] || s.used[e + i] != out_bytes[i])
+                    if (s.fmts[e + i] != formats[i] || s.used[e + i] != out.bytes[i])
                         pass = 0;
                 k = kind_of(kinds, kind_count, s.fmts[e]);
                 /* else it must hold what the caller's geometry says, as for hapb_road_frames, in a format the kernel reads */
-                if (!pass && (!set || !slice_entry_fits(&s, e, texture_count, kinds, kind_count)))
+                if (!pass && (!set || !slice_entry_fits(&s, e, 0u, kinds, kind_count)))
                     r = HapResult_Bad_Arguments;
             }
             decoded[f] = r;
             for (i = 0; i < count; i++)
                 tex[(size_t)f * count + i] = r != HapResult_No_Error ? NULL :
-                                             pass ? s.outs[e + i] : (const void *)(transcoded + out_per_frame * f + out_off[i]);
+                                             pass ? s.outs[e + i] : (const void *)(transcoded + out.total * f + out.off[i]);
             /* (a frame whose output hapb_encode will refuse is not worth the kernel's time either) */
             if (r == HapResult_No_Error && !pass && outputs[done + f] && output_bytes[done + f]) {
                 uint64_t *col = htab + (size_t)k * 4u * n;
@@ -1316,19 +1302,9 @@ unsigned hapb_transcode(HapGpuContext *ctx, unsigned frame_count, const void *co
                                                    formats[0], count == 2);
                 }
         }
-        if (rc)     /* (nothing of this slice's kernel output may be trusted: its frames fail, the pass-through ones included) */
-            memset(tex, 0, sizeof(*tex) * (size_t)n * count);
-        /* the encode half on the same stream, behind the kernel; it ends with the slice's second and last wait */
-        hapb_encode(ctx, n, count, tex, out_bytes, formats, compressors, chunk_counts, outputs + done, output_bytes + done,
-                    output_used + done, results + done, encode_flags, &device_textures);
-        for (f = 0; f < n; f++) {
-            if (decoded[f] != HapResult_No_Error)
-                results[done + f] = decoded[f];
-            else if (rc && (results[done + f] == HapResult_No_Error || results[done + f] == HapResult_Bad_Arguments))
-                results[done + f] = HapResult_Internal_Error;
-            if (results[done + f] != HapResult_No_Error && first_error == HapResult_No_Error)
-                first_error = results[done + f];
-        }
+        /* (a frame whose decode half failed keeps what hapb_encode leaves in output_used) */
+        slice_encode_half(ctx, n, tex, decoded, rc, 0, &out, count, formats, compressors, chunk_counts, encode_flags,
+                          outputs + done, output_bytes + done, output_used + done, results + done, &first_error);
     }
     free(s.in); free(tex);
     return first_error;
@@ -1347,10 +1323,11 @@ unsigned hapb_transcode_texture(HapGpuContext *ctx, const void *texture, unsigne
     hapgpu_rt *rt = ctx->rt;
     const size_t block = hapf_block_bytes(format);
     HapGpuTranscodeTable t = {{NULL, NULL, NULL, NULL}, {0u, 0u, 0u, 0u}};
-    size_t need, alpha_need, out_need[2] = {0, 0}, out_off[2] = {0, 0}, out_total = 0;
+    destination_layout out;
+    size_t need, alpha_need;
     const void *src = texture, *asrc = alpha;
     uint8_t *staged = NULL;
-    unsigned i, k, set, align;
+    unsigned i, k, set, align, r;
     int rc = 0, pass;
     if (context_busy(ctx, NULL, 0))
         return HapResult_Internal_Error;
@@ -1366,25 +1343,16 @@ unsigned hapb_transcode_texture(HapGpuContext *ctx, const void *texture, unsigne
     alpha_need = (size_t)(width / 4u) * (height / 4u) * 8u;
     if (texture_bytes < need || (alpha && alpha_bytes < alpha_need))
         return HapResult_Bad_Arguments;
-    for (i = 0; i < count; i++) {
-        if (!outputs[i])
-            return HapResult_Bad_Arguments;
-        out_need[i] = (size_t)((width >> scale_log2) / 4u) * ((height >> scale_log2) / 4u) * hapf_block_bytes(formats[i]);
-        out_off[i] = out_total;
-        out_total += align_up(out_need[i], 256);
-    }
-    for (i = 0; i < count; i++)
-        if (output_bytes[i] < out_need[i])
-            return HapResult_Buffer_Too_Small;
-    /* device sources aligned to what a lane reads of a block row (the block << scale_log2, at most 16 bytes), device
-       outputs to their blocks */
+    /* every output there, large enough and, in device memory, aligned to its blocks; device sources aligned to what a
+       lane reads of a block row (the block << scale_log2, at most 16 bytes) */
+    destination_layout_of(&out, count, formats, width >> scale_log2, height >> scale_log2);
+    r = destination_textures_fit(ctx, &out, count, formats, outputs, output_bytes);
+    if (r != HapResult_No_Error)
+        return r;
     align = (unsigned)(block << scale_log2) > 16u ? 16u : (unsigned)(block << scale_log2);
     if ((is_dev(ctx, texture) && ((uintptr_t)texture & (align - 1u))) ||
         (alpha && is_dev(ctx, alpha) && ((uintptr_t)alpha & ((8u << scale_log2 > 16u ? 16u : 8u << scale_log2) - 1u))))
         return HapResult_Bad_Arguments;
-    for (i = 0; i < count; i++)
-        if (is_dev(ctx, outputs[i]) && ((uintptr_t)outputs[i] & (hapf_block_bytes(formats[i]) - 1u)))
-            return HapResult_Bad_Arguments;
     if (!is_dev(ctx, texture) || (alpha && !is_dev(ctx, alpha))) {
         uint8_t *s = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, align_up(need, 256) + alpha_need);
         if (!s)
@@ -1404,331 +1372,31 @@ unsigned hapb_transcode_texture(HapGpuContext *ctx, const void *texture, unsigne
     pass = scale_log2 == 0u && formats[0] == format && (count == 2) == (alpha != NULL);
     for (i = 0; i < count; i++)
         if (!is_dev(ctx, outputs[i]) && !pass && !staged) {
-            staged = (uint8_t *)hapgpu_rt_device_scratch(rt, D_TRANSCODED, out_total);
+            staged = (uint8_t *)hapgpu_rt_device_scratch(rt, D_TRANSCODED, out.total);
             if (!staged)
                 return HapResult_Internal_Error;
         }
     if (pass) {
         for (i = 0; i < count; i++) {
             const void *from = i ? asrc : src;
-            rc |= is_dev(ctx, outputs[i]) ? hapgpu_rt_d2d(rt, outputs[i], from, out_need[i])
-                                          : hapgpu_rt_d2h(rt, outputs[i], from, out_need[i]);
+            rc |= is_dev(ctx, outputs[i]) ? hapgpu_rt_d2d(rt, outputs[i], from, out.bytes[i])
+                                          : hapgpu_rt_d2h(rt, outputs[i], from, out.bytes[i]);
         }
     } else {
         t.one[0] = (uint64_t)(uintptr_t)src;
         t.one[1] = (uint64_t)(uintptr_t)asrc;
         for (i = 0; i < count; i++)
-            t.one[2u + i] = (uint64_t)(uintptr_t)(is_dev(ctx, outputs[i]) ? (uint8_t *)outputs[i] : staged + out_off[i]);
+            t.one[2u + i] = (uint64_t)(uintptr_t)(is_dev(ctx, outputs[i]) ? (uint8_t *)outputs[i] : staged + out.off[i]);
         rc = hapgpu_k_block_transcode(rt, &t, 1u, format, alpha != NULL, width, height, scale_log2, formats[0], count == 2);
         if (rc == 1)
             return HapResult_Bad_Arguments;
         for (i = 0; !rc && i < count; i++)
             if (!is_dev(ctx, outputs[i]))
-                rc |= hapgpu_rt_d2h(rt, outputs[i], staged + out_off[i], out_need[i]);
+                rc |= hapgpu_rt_d2h(rt, outputs[i], staged + out.off[i], out.bytes[i]);
     }
     if (rc || hapgpu_rt_sync(rt))
         return HapResult_Internal_Error;
     for (i = 0; output_used && i < count; i++)
-        output_used[i] = (unsigned long)out_need[i];
+        output_used[i] = out.bytes[i];
     return HapResult_No_Error;
-}
-
-/* ============================================================= compositing to frames */
-/* Layers of frames -> frames, and layers of textures -> textures: the placed compositing calls up to their launch, then
-   hapb_transcode from its launch on.  hapgpu_k_block_composite_encode takes the descriptors of
-   hapgpu_k_block_composite_placed and, where that has the pictures' addresses, the destination textures' -- a slice's lie
-   in D_TRANSCODED --, and hapb_encode follows on those textures on the same stream.  No picture anywhere. */
-
-int hapb_composite_encode_textures_valid(unsigned layer_count, const unsigned *layer_widths, const unsigned *layer_heights,
-                                         const HapGpuPlacement *placements, size_t frame_count, unsigned width,
-                                         unsigned height, const unsigned *texture_counts, unsigned count,
-                                         const unsigned *formats)
-{
-    /* (the canvas is the placed calls' with rows of exactly width * 4 bytes; a block row per blockIdx.y of the kernel) */
-    return hapb_composite_placed_valid(layer_count, layer_widths, layer_heights, placements, frame_count, width, height,
-                                       (unsigned long)width * 4u, texture_counts) &&
-           height / 4u <= 65535u && formats && count != 0 && count <= 2 && transcode_set(count, formats);
-}
-
-int hapb_composite_encode_frames_valid(unsigned layer_count, const unsigned *layer_widths, const unsigned *layer_heights,
-                                       const HapGpuPlacement *placements, size_t frame_count, unsigned width,
-                                       unsigned height, const unsigned *texture_counts, unsigned count,
-                                       const unsigned *formats, const unsigned *compressors,
-                                       const unsigned *chunk_counts, unsigned encode_flags)
-{
-    unsigned long out_bytes[2] = {0, 0};
-    unsigned i;
-    if (!compressors || !chunk_counts ||
-        !hapb_composite_encode_textures_valid(layer_count, layer_widths, layer_heights, placements, frame_count, width,
-                                              height, texture_counts, count, formats))
-        return 0;
-    for (i = 0; i < count; i++)
-        out_bytes[i] = (unsigned long)((size_t)(width / 4u) * (height / 4u) * hapf_block_bytes(formats[i]));
-    encode_flags &= ~(HAPGPU_ENCODE_BPTC_BLOCKS | HAPGPU_ENCODE_REFINE_ENDPOINTS);
-    return encode_textures_valid(count, out_bytes, formats, compressors, chunk_counts, encode_flags) == HapResult_No_Error;
-}
-
-/* the table of a composite-encode launch for n canvases of layer_count layers: [n] destination textures, [n] destination
-   planes, then [n][layer_count] descriptors; as composite_placed_table */
-static uint64_t *composite_encode_table(hapgpu_rt *rt, unsigned n, unsigned layer_count, uint64_t **device, size_t *bytes)
-{
-    uint64_t *htab;
-    *bytes = sizeof(uint64_t) * 2u * n + sizeof(HapGpuPlacedLayer) * (size_t)n * layer_count;
-    htab = (uint64_t *)hapgpu_rt_pinned_scratch(rt, P_BC_PTRS, *bytes);
-    *device = (uint64_t *)hapgpu_rt_device_scratch(rt, D_BC_PTRS, *bytes);
-    if (!htab || !*device)
-        return NULL;
-    memset(htab, 0, *bytes);
-    return htab;
-}
-
-static void composite_encode_refuse(unsigned *layer_results, size_t layer_entries, unsigned *results, size_t frame_count,
-                                    unsigned code)
-{
-    size_t i;
-    for (i = 0; layer_results && i < layer_entries; i++)
-        layer_results[i] = code;
-    for (i = 0; results && i < frame_count; i++)
-        results[i] = code;
-}
-
-unsigned hapb_composite_encode_textures(HapGpuContext *ctx, unsigned layer_count, const void *const *textures,
-                                        const unsigned long *texture_bytes, const unsigned *formats,
-                                        const void *const *alphas, const unsigned long *alpha_bytes,
-                                        const unsigned *layer_widths, const unsigned *layer_heights,
-                                        const HapGpuPlacement *placements, const unsigned char *opacities,
-                                        const unsigned char *background, unsigned width, unsigned height, unsigned count,
-                                        const unsigned *out_formats, void *const *outputs,
-                                        const unsigned long *output_bytes, unsigned long *output_used)
-{
-    hapgpu_rt *rt = ctx->rt;
-    size_t staged = 0, tab_bytes, at = 0, out_need[2] = {0, 0}, out_off[2] = {0, 0}, out_total = 0;
-    uint64_t *htab, *dtab;
-    HapGpuPlacedLayer *hlayers;
-    uint8_t *stage = NULL, *out_stage = NULL;
-    unsigned l, i;
-    int rc, any_host_output = 0;
-    if (!hapb_composite_encode_textures_valid(layer_count, layer_widths, layer_heights, placements, 1u, width, height, NULL,
-                                              count, out_formats) ||
-        !textures || !texture_bytes || !formats || !outputs || !output_bytes)
-        return HapResult_Bad_Arguments;
-    if (context_busy(ctx, NULL, 0))
-        return HapResult_Internal_Error;
-    /* every layer: HapGpuDecompressRGBA's rules for its texture and its plane, at the layer's own size */
-    for (l = 0; l < layer_count; l++) {
-        const void *alpha = alphas ? alphas[l] : NULL;
-        const size_t blocks = (size_t)(layer_widths[l] / 4u) * (layer_heights[l] / 4u);
-        const size_t need = composite_format(formats[l]) ? blocks * hapf_block_bytes(formats[l]) : 0u;
-        if (!textures[l] || !need || texture_bytes[l] < need || (alpha && (!alpha_bytes || alpha_bytes[l] < blocks * 8u)) ||
-            (is_dev(ctx, textures[l]) && ((uintptr_t)textures[l] & (hapf_block_bytes(formats[l]) - 1u))) ||
-            (alpha && is_dev(ctx, alpha) && ((uintptr_t)alpha & 7u)))
-            return HapResult_Bad_Arguments;
-        if (!is_dev(ctx, textures[l]))
-            staged += align_up(need, 256);
-        if (alpha && !is_dev(ctx, alpha))
-            staged += align_up(blocks * 8u, 256);
-    }
-    /* every output: HapGpuTranscodeTexture's rules */
-    for (i = 0; i < count; i++) {
-        if (!outputs[i])
-            return HapResult_Bad_Arguments;
-        out_need[i] = (size_t)(width / 4u) * (height / 4u) * hapf_block_bytes(out_formats[i]);
-        out_off[i] = out_total;
-        out_total += align_up(out_need[i], 256);
-    }
-    for (i = 0; i < count; i++)
-        if (output_bytes[i] < out_need[i])
-            return HapResult_Buffer_Too_Small;
-    for (i = 0; i < count; i++) {
-        if (is_dev(ctx, outputs[i]) && ((uintptr_t)outputs[i] & (hapf_block_bytes(out_formats[i]) - 1u)))
-            return HapResult_Bad_Arguments;
-        if (!is_dev(ctx, outputs[i]))
-            any_host_output = 1;
-    }
-    /* (one request for all that is staged: an arena that grows forgets what it held) */
-    if (staged && !(stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, staged)))
-        return HapResult_Internal_Error;
-    if (any_host_output && !(out_stage = (uint8_t *)hapgpu_rt_device_scratch(rt, D_TRANSCODED, out_total)))
-        return HapResult_Internal_Error;
-    htab = composite_encode_table(rt, 1u, layer_count, &dtab, &tab_bytes);
-    if (!htab)
-        return HapResult_Internal_Error;
-    hlayers = (HapGpuPlacedLayer *)(htab + 2);
-    for (i = 0; i < count; i++)
-        htab[i] = (uint64_t)(uintptr_t)(is_dev(ctx, outputs[i]) ? (uint8_t *)outputs[i] : out_stage + out_off[i]);
-    for (l = 0; l < layer_count; l++) {
-        const void *alpha = alphas ? alphas[l] : NULL, *src = textures[l];
-        const size_t blocks = (size_t)(layer_widths[l] / 4u) * (layer_heights[l] / 4u);
-        if (!is_dev(ctx, src)) {
-            const size_t need = blocks * hapf_block_bytes(formats[l]);
-            if (hapgpu_rt_h2d(rt, stage + at, src, need))
-                return HapResult_Internal_Error;
-            src = stage + at;
-            at += align_up(need, 256);
-        }
-        if (alpha && !is_dev(ctx, alpha)) {
-            if (hapgpu_rt_h2d(rt, stage + at, alpha, blocks * 8u))
-                return HapResult_Internal_Error;
-            alpha = stage + at;
-            at += align_up(blocks * 8u, 256);
-        }
-        hlayers[l].texture = (uint64_t)(uintptr_t)src;
-        hlayers[l].alpha = (uint64_t)(uintptr_t)alpha;
-        hlayers[l].format = formats[l];
-        hlayers[l].opacity = opacities ? opacities[l] : 255u;
-        placed_layer_clip(&hlayers[l], placements ? &placements[l] : NULL, layer_widths[l], layer_heights[l], width, height);
-    }
-    if (hapgpu_rt_h2d(rt, dtab, htab, tab_bytes))
-        return HapResult_Internal_Error;
-    rc = hapgpu_k_block_composite_encode(rt, (const HapGpuPlacedLayer *)(dtab + 2), layer_count, dtab, dtab + 1, 1u,
-                                         background ? background : k_composite_background, width, height, out_formats[0],
-                                         count == 2);
-    if (rc == 1)
-        return HapResult_Bad_Arguments;
-    for (i = 0; !rc && i < count; i++)
-        if (!is_dev(ctx, outputs[i]))
-            rc |= hapgpu_rt_d2h(rt, outputs[i], out_stage + out_off[i], out_need[i]);
-    if (rc || hapgpu_rt_sync(rt))
-        return HapResult_Internal_Error;
-    for (i = 0; output_used && i < count; i++)
-        output_used[i] = (unsigned long)out_need[i];
-    return HapResult_No_Error;
-}
-
-unsigned hapb_composite_encode_frames(HapGpuContext *ctx, unsigned frame_count, unsigned layer_count,
-                                      const void *const *inputs, const unsigned long *input_bytes,
-                                      const unsigned *texture_counts, const unsigned *layer_widths,
-                                      const unsigned *layer_heights, const HapGpuPlacement *placements,
-                                      const unsigned char *opacities, const unsigned char *background, unsigned width,
-                                      unsigned height, unsigned count, const unsigned *formats,
-                                      const unsigned *compressors, const unsigned *chunk_counts, void *const *outputs,
-                                      const unsigned long *output_bytes, unsigned long *output_used,
-                                      unsigned *layer_results, unsigned *results, unsigned decode_flags,
-                                      unsigned encode_flags)
-{
-    hapgpu_rt *rt = ctx->rt;
-    const HapbEncodeArgs device_textures = {1, NULL, 0, 0};
-    const size_t total = (size_t)frame_count * layer_count;
-    size_t out_per_frame = 0, out_off[2] = {0, 0}, done, i;
-    unsigned long out_bytes[2] = {0, 0};
-    unsigned first_error = HapResult_No_Error, f, l;
-    hap_place_layout layout;
-    slice_textures s;
-    const void **tex;       /* per output frame and destination texture: what the encode half reads */
-    unsigned *composited;   /* per output frame: what its layers came to */
-    if (!results || !layer_results)
-        return HapResult_Bad_Arguments;
-    if (!hapb_composite_encode_frames_valid(layer_count, layer_widths, layer_heights, placements, frame_count, width, height,
-                                            texture_counts, count, formats, compressors, chunk_counts, encode_flags) ||
-        !inputs || !input_bytes || !outputs || !output_bytes || !output_used) {
-        composite_encode_refuse(layer_results, total, results, frame_count, HapResult_Bad_Arguments);
-        return HapResult_Bad_Arguments;
-    }
-    if (frame_count == 0)
-        return HapResult_No_Error;
-    /* (the destination blocks are the default encode's: no BC7, no refined end points) */
-    encode_flags &= ~(HAPGPU_ENCODE_BPTC_BLOCKS | HAPGPU_ENCODE_REFINE_ENDPOINTS);
-    for (i = 0; i < count; i++) {
-        out_bytes[i] = (unsigned long)((size_t)(width / 4u) * (height / 4u) * hapf_block_bytes(formats[i]));
-        out_off[i] = out_per_frame;
-        out_per_frame += align_up(out_bytes[i], 256);
-    }
-    /* output frames of a slice: at most 4 GiB of block textures, the canvases' among them, and 32768 entries of the second
-       stage at a time */
-    hap_place_layout_of(&layout, layer_count, texture_counts, layer_widths, layer_heights, out_per_frame, frame_count);
-    if (context_busy(ctx, NULL, 0) || !slice_textures_init_placed(&s, &layout)) {
-        composite_encode_refuse(layer_results, total, results, frame_count, HapResult_Internal_Error);
-        return HapResult_Internal_Error;
-    }
-    tex = (const void **)malloc((sizeof(*tex) * count + sizeof(*composited)) * s.at.slice);
-    if (!tex) {
-        free(s.in);
-        composite_encode_refuse(layer_results, total, results, frame_count, HapResult_Internal_Error);
-        return HapResult_Internal_Error;
-    }
-    composited = (unsigned *)(tex + s.at.slice * count);
-    for (done = 0; done < frame_count; done += s.at.slice) {
-        const unsigned n = (unsigned)(frame_count - done < s.at.slice ? frame_count - done : s.at.slice);
-        uint8_t *textures = (uint8_t *)hapgpu_rt_device_scratch(rt, D_BC_TEX, s.at.per_frame * n);
-        uint8_t *encoded = (uint8_t *)hapgpu_rt_device_scratch(rt, D_TRANSCODED, out_per_frame * n);
-        uint64_t *htab = NULL, *dtab = NULL;
-        HapGpuPlacedLayer *hlayers;
-        size_t tab_bytes = 0;
-        unsigned present = 0;
-        int rc = 0;
-        if (textures && encoded) {
-            /* the second stage of every layer of every output frame of the slice, one batch: whole frames */
-            slice_textures_decode(ctx, &s, textures, inputs, input_bytes, done, n, NULL, decode_flags);
-            /* (after the second stage, which has tables of its own) */
-            htab = composite_encode_table(rt, n, layer_count, &dtab, &tab_bytes);
-        }
-        if (!htab) {
-            composite_encode_refuse(layer_results + done * layer_count, (size_t)n * layer_count, results + done, n,
-                                    HapResult_Internal_Error);
-            for (f = 0; f < n; f++)
-                output_used[done + f] = 0;
-            first_error = first_error ? first_error : HapResult_Internal_Error;
-            continue;
-        }
-        hlayers = (HapGpuPlacedLayer *)(htab + 2u * (size_t)n);
-        for (f = 0; f < n; f++) {
-            unsigned *frame_results = layer_results + (done + f) * layer_count;
-            unsigned all = HapResult_No_Error;
-            for (l = 0; l < layer_count; l++) {
-                const unsigned layer_textures = s.at.count_of[l];
-                const size_t e = (size_t)f * s.at.entries_per_frame + s.at.entry_of[l];
-                HapGpuPlacedLayer *d = &hlayers[(size_t)f * layer_count + l];
-                unsigned r = s.res[e];
-                if (r == HapResult_No_Error && layer_textures == 2u)
-                    r = s.res[e + 1];
-                /* the placed call's checks: exactly the layer's geometry, in one of the three formats a layer may have */
-                if (r == HapResult_Buffer_Too_Small ||
-                    (r == HapResult_No_Error && !slice_entry_fits_member(&s, e, l, k_rgba_kinds, 3u)))
-                    r = HapResult_Bad_Arguments;
-                frame_results[l] = r;
-                if (r != HapResult_No_Error && all == HapResult_No_Error)
-                    all = r;
-                d->texture = (uint64_t)(uintptr_t)s.outs[e];
-                d->alpha = layer_textures == 2u ? (uint64_t)(uintptr_t)s.outs[e + 1] : 0u;
-                d->format = s.fmts[e];
-                d->opacity = opacities ? opacities[(done + f) * layer_count + l] : 255u;
-                placed_layer_clip(d, placements ? &placements[(done + f) * layer_count + l] : NULL, layer_widths[l],
-                                  layer_heights[l], width, height);
-            }
-            composited[f] = all;
-            /* (an output frame with a failed layer has NULL textures: hapb_encode leaves it out) */
-            for (i = 0; i < count; i++)
-                tex[(size_t)f * count + i] = all != HapResult_No_Error ? NULL :
-                                             (const void *)(encoded + out_per_frame * f + out_off[i]);
-            /* (a frame whose output hapb_encode will refuse is not worth the kernel's time either: address 0 skips it) */
-            if (all == HapResult_No_Error && outputs[done + f] && output_bytes[done + f]) {
-                htab[f] = (uint64_t)(uintptr_t)tex[(size_t)f * count];
-                htab[n + f] = count == 2 ? (uint64_t)(uintptr_t)tex[(size_t)f * count + 1] : 0u;
-                present = 1;
-            }
-        }
-        if (present) {
-            rc |= hapgpu_rt_h2d(rt, dtab, htab, tab_bytes);
-            rc |= hapgpu_k_block_composite_encode(rt, (const HapGpuPlacedLayer *)(dtab + 2u * (size_t)n), layer_count, dtab,
-                                                  dtab + n, n, background ? background : k_composite_background, width,
-                                                  height, formats[0], count == 2);
-        }
-        if (rc)     /* (nothing of this slice's kernel output may be trusted: its frames fail) */
-            memset(tex, 0, sizeof(*tex) * (size_t)n * count);
-        /* the encode half on the same stream, behind the kernel; it ends with the slice's second and last wait */
-        hapb_encode(ctx, n, count, tex, out_bytes, formats, compressors, chunk_counts, outputs + done, output_bytes + done,
-                    output_used + done, results + done, encode_flags, &device_textures);
-        for (f = 0; f < n; f++) {
-            if (composited[f] != HapResult_No_Error) {
-                results[done + f] = composited[f];
-                output_used[done + f] = 0;
-            } else if (rc && (results[done + f] == HapResult_No_Error || results[done + f] == HapResult_Bad_Arguments)) {
-                results[done + f] = HapResult_Internal_Error;
-            }
-            if (results[done + f] != HapResult_No_Error && first_error == HapResult_No_Error)
-                first_error = results[done + f];
-        }
-    }
-    free(s.in); free(tex);
-    return first_error;
 }

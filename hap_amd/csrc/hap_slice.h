@@ -29,7 +29,10 @@ typedef struct hap_slice_layout {
 static inline size_t hap_slice_align(size_t v) { return (v + 255u) / 256u * 256u; }
 
 /* counts: member_count texture counts (NULL: all 1); extra_per_frame: what else the caller holds per frame while a
-   slice's textures are held; frame_count: the call's, at least 1 */
+   slice's textures are held; frame_count: the call's, at least 1.  The library itself lays every slice out with
+   hap_place.h's hap_place_layout_of, members of one size included, and no longer calls this: it stays as the definition
+   of the one-size layout, which tests/c/slice_layout.c walks and tests/c/place_layout.c holds hap_place_layout_of
+   against, member by member. */
 static inline void hap_slice_layout_of(hap_slice_layout *s, unsigned member_count, const unsigned *counts, unsigned width,
                                        unsigned height, size_t extra_per_frame, size_t frame_count)
 {

@@ -195,7 +195,7 @@ static void walk_refusals(void)
 
 static size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
 
-static unsigned long layouts_walked;
+static unsigned long layouts_walked, one_size_walked, one_size_with_extra_walked, one_member_walked;
 
 static void walk_layout(unsigned members, const unsigned *counts, const unsigned *ws, const unsigned *hs, size_t extra, size_t frames)
 {
@@ -234,16 +234,23 @@ static void walk_layout(unsigned members, const unsigned *counts, const unsigned
     CHECK(p.at.slice == slice);
     CHECK(p.at.slice >= 1u && p.at.slice <= frames && p.at.slice * entries <= 32768u);
     CHECK(p.at.slice == 1u || p.at.slice * (per_frame + extra) <= ((size_t)4u << 30));
-    /* members of one size: hap_slice.h's layout */
+    /* members of one size: hap_slice.h's layout, number for number -- what lets every road lay its slices out with
+       hap_place_layout_of, the roads whose members have one size included */
     for (m = 1; m < members && ws[m] == ws[0] && hs[m] == hs[0]; m++)
         ;
     if (m == members) {
         hap_slice_layout s;
         hap_slice_layout_of(&s, members, counts, ws[0], hs[0], extra, frames);
+        CHECK(s.member_count == p.at.member_count);
         CHECK(s.per_frame == p.at.per_frame && s.slice == p.at.slice && s.entries_per_frame == p.at.entries_per_frame);
         for (m = 0; m < members; m++)
-            CHECK(s.offset_of[m] == p.at.offset_of[m] && s.entry_of[m] == p.at.entry_of[m] && s.alpha_off == p.alpha_off_of[m] &&
-                  s.blocks == p.blocks_of[m]);
+            CHECK(s.offset_of[m] == p.at.offset_of[m] && s.entry_of[m] == p.at.entry_of[m] && s.count_of[m] == p.at.count_of[m] &&
+                  s.alpha_off == p.alpha_off_of[m] && s.blocks == p.blocks_of[m]);
+        one_size_walked++;
+        if (extra)
+            one_size_with_extra_walked++;
+        if (members == 1u)
+            one_member_walked++;
     }
     layouts_walked++;
 }
@@ -281,6 +288,8 @@ int main(void)
     walk_extremes();
     walk_refusals();
     walk_layouts();
+    /* (the agreement with hap_slice.h was asked for: one member, several of one size, and with something else held per frame) */
+    CHECK(one_member_walked != 0 && one_size_walked > one_member_walked && one_size_with_extra_walked != 0);
     if (failures) {
         fprintf(stderr, "%lu checks failed\n", failures);
         return 1;

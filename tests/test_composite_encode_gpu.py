@@ -223,6 +223,24 @@ def test_short_and_missing_outputs_are_refused(ctx, hap):
     assert r == hap.HapResult.Bad_Arguments and (host(outs[0]) == SENTINEL).all()
 
 
+def test_everything_in_host_memory_is_everything_in_device_memory(ctx):
+    """The textures form stages what lies in host memory: two layers of different sizes, one of them with an alpha plane,
+    and a two-texture destination, all in host memory, give the bytes of the same call with all of them in device
+    memory -- the CPU definition's"""
+    canvas_size = (260, 12)
+    cases, sizes, placements = (part[:2] for part in stack_b(canvas_size))
+    assert cases == ("ycocg_alpha", "dxt5") and sizes[0] != sizes[1]
+    opacities, background = [200, 255], BACKGROUNDS[1]
+    on_host = encoded(ctx, [host_layer(c, w, h, 1) for c, (w, h) in zip(cases, sizes)], sizes, canvas_size, placements,
+                      opacities, background, "ycocg_alpha", "cpu")
+    on_device = encoded(ctx, [device_layer(c, w, h, 1) for c, (w, h) in zip(cases, sizes)], sizes, canvas_size, placements,
+                        opacities, background, "ycocg_alpha", "cuda")
+    assert len(on_host) == 2
+    same(on_host, on_device, "host against device")
+    pictures = [random_layer(c, w, h, 1)[2] for c, (w, h) in zip(cases, sizes)]
+    same(on_host, cpu_textures(canvas_size, pictures, placements, opacities, background, "ycocg_alpha"), "host against the CPU")
+
+
 # ------------------------------------------------------------------------------------------------- 2. the shortcuts --
 def test_an_opaque_layer_replaces_what_is_below(ctx):
     """Opaque at opacity 255: the canvas is replaced, lane by lane, whatever lies below -- here every kind of layer at

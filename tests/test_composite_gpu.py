@@ -369,6 +369,29 @@ def test_a_misaligned_device_picture_fails_alone(ctx, hap, movie):
     check_frames([pictures[0], None, pictures[2]], decoded, None, None, [True, False, True])
 
 
+@pytest.mark.parametrize("kinds", (("device",) * 3, ("host",) * 3), ids=("device", "host"))
+def test_a_frame_with_more_blocks_than_the_canvas(ctx, hap, movie, kinds):
+    """One layer's DXT5 frame a block row taller than the canvas: the second stage has no room for it, and the call hands
+    its Buffer_Too_Small on for that entry; as a placed layer of the canvas's size the same frame is one of another size,
+    Bad_Arguments.  The other output frames are written either way."""
+    frames, decoded = movie
+    bad, too_small = hap.HapResult.Bad_Arguments, hap.HapResult.Buffer_Too_Small
+    tall_picture = np.ascontiguousarray(np.concatenate([source_picture(30), source_picture(31)[:4]]))
+    tall = np.zeros(hap.HapMaxEncodedLength([(W // 4) * (H // 4 + 1) * 16], [L.FMT_DXT5], [1]), dtype=np.uint8)
+    r, used, res = ctx.encode_frames_rgba([tall_picture], W, H + 4, W * 4, [L.FMT_DXT5], [1], [1], [tall])
+    assert r == 0 and res == [0]
+    other = [list(fr) for fr in frames]
+    other[1][0] = tall[: used[0]].tobytes()
+    pictures = canvases(kinds)
+    r, res = ctx.composite_frames(other, None, COUNTS, pictures, W, H, opacities=DISSOLVE)
+    assert r == too_small and res == [0, 0, 0, too_small, 0, 0, 0, 0, 0]
+    check_frames(pictures, decoded, DISSOLVE, None, [True, False, True])
+    pictures = canvases(kinds)
+    r, res = ctx.composite_frames_placed(other, None, COUNTS, [(W, H)] * LAYERS, pictures, W, H, opacities=DISSOLVE)
+    assert r == bad and res == [0, 0, 0, bad, 0, 0, 0, 0, 0]
+    check_frames(pictures, decoded, DISSOLVE, None, [True, False, True])
+
+
 # ------------------------------------------------------------------------------------------------ 7. repeatability --
 def test_the_same_call_twice_gives_the_same_bytes(ctx, movie):
     frames, _decoded = movie

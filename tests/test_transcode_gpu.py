@@ -419,6 +419,30 @@ def test_a_mixed_batch_and_per_frame_results(ctx, hap, mixed, dst, s):
     assert (r, res) == (0, [0]) and 0 < used[0] <= limit
 
 
+@pytest.mark.parametrize("where", ("cuda", "cpu"))
+def test_a_truncated_frame_between_two_good_ones(ctx, hap, mixed, where):
+    """Three frames, the middle one cut short: its result is its decode's code, nothing of its output is written and its
+    outputBuffersBytesUsed entry is 0; its neighbours' frames are made as if it were not there"""
+    good, textures, cases = mixed
+    fmts = SETS["dxt5"]
+    sizes = texture_bytes(W, H, fmts)
+    cap = hap.HapMaxEncodedLength(sizes, fmts, [2])
+    frames = [good[2], good[4], good[3]]
+    lens = [len(f) for f in frames]
+    _r, decode_res = ctx.decode_frames_rgba(frames, lens, 1, [np.zeros(W * H * 4, dtype=np.uint8) for _ in frames], W, H)
+    code = decode_res[1]
+    assert decode_res == [0, hap.HapResult.Bad_Frame, 0]
+    whole = [filled(cap + 64, where) for _ in frames]
+    r, used, res = ctx.transcode_frames(frames, lens, 1, W, H, 0, fmts, [L.COMP_SNAPPY], [2], [o[:cap] for o in whole])
+    assert r == code and res == [0, code, 0]
+    assert used[1] == 0 and (host(whole[1]) == SENTINEL).all()
+    for f, i in ((0, 2), (2, 3)):
+        got = host(whole[f])
+        assert 0 < used[f] <= cap and (got[cap:] == SENTINEL).all(), f
+        want = expected_textures(cases[i], textures[i][0], None, W, H, 0, "dxt5")
+        assert frame_textures(ctx, [got[: used[f]].tobytes()], 1, max(sizes))[0] == want, f
+
+
 # -------------------------------------------------------------------------------------------------- 5. pass-through --
 def random_bytes(n, seed):
     return np.random.default_rng(seed).integers(0, 256, n, dtype=np.uint8).tobytes()
